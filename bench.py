@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: queries/sec of exact MoL top-k (BASELINE.json metric) on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (config.workload): amzn-books HSTU+MoL 8x8x32, N = 695 762 items, B = 32 queries per batch --
@@ -599,6 +599,37 @@ def full_shard_legs(B: int, k: int, dev) -> list:
     return legs
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def host_copy(outputs):
+    """(top_k_ids, top_k_scores) of a step as host tensors: taken after the timed region, before later calls can reuse the buffers."""
+    return tuple(t.detach().to("cpu", copy=True) for t in outputs)
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """--dump-outputs: every (rows, ...) tensor of `arrays` as dirname/<name>.npy -- integers as float64 (exact below 2^53), floats as
+    float32 (float64 stays float64).  Above DUMP_MAX_BYTES in all, the same fixed seeded sample of rows is kept of every array, its row
+    indices written beside them as rows.npy."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    host = {name: t.to(torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32).numpy()
+            for name, t in arrays.items()}
+    n_rows = next(iter(host.values())).shape[0]
+    row_bytes = sum(a.nbytes for a in host.values()) // max(n_rows, 1)
+    budget = DUMP_MAX_BYTES - 1024     # room for the .npy headers
+    sampled = row_bytes * n_rows > budget
+    if sampled:
+        keep = max(1, budget // (row_bytes + 8))
+        rows = torch.randperm(n_rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values.numpy()
+        host = {name: a[rows] for name, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "files": {name + ".npy": [list(a.shape), str(a.dtype)] for name, a in host.items()}, "sampled_rows": bool(sampled)}
+
+
 def main() -> None:
     # The cyclic garbage collector stays off while anything is timed: a generation-2 collection of this process (torch modules, numpy
     # fixtures, thousands of event objects) is a 30-40 ms host pause, and a step is 2-6 ms -- one collection inside a 20-step region
@@ -638,17 +669,22 @@ def main() -> None:
     ap.add_argument("--pipeline", action="store_true",
                     help="N > 1: time the steps with batch i's all-gather + merge + filter overlapped with batch i+1's prologue + scoring "
                          "(ShardedTopK.submit / result, two streams); without it the pipelined rate is still reported next to `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the run, write what the path reported as `value` returned in its last timed step (top_k_ids as float64, "
+                         "top_k_scores as float32) to DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run, same argv
+        # plain `python bench.py --gpus N`: launch torch.distributed.run with one rank per GPU and the same argv as a fresh child process
         import socket
+        import subprocess
 
         with socket.socket() as s:
             s.bind(("127.0.0.1", 0))
             port = s.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]])
+        rc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                             "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]).returncode
+        sys.exit(rc)
 
     from oracle import mol_oracle as O  # inputs generator + cpu_baseline checker only
 
@@ -741,6 +777,7 @@ def main() -> None:
         uid_cpu = torch.randint(0, cfg.uid_embedding_hash_sizes[0], (B,), generator=g, dtype=torch.int64)
         kw["user_ids"] = uid_cpu.to(dev)
 
+    last_outputs = {}   # leg -> (top_k_ids, top_k_scores) of its last timed step, copied to the host after the timed region (--dump-outputs)
     recall_info = None
     if two_pass and not args.no_recall:
         # north_star: config 5 "with recall@k vs exact reported".  Untimed, BEFORE the timed module exists (one index per rank at a
@@ -863,16 +900,17 @@ def main() -> None:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if pipelined_headline:
-            run_pipelined(args.steps)
+            last_out = run_pipelined(args.steps)
         else:
             for i in range(args.steps):
                 ev_step[i].record()
-                step(i)
+                last_out = step(i)
         ev_step[args.steps].record()
         torch.cuda.synchronize()
         if sharded:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+        last_outputs["headline"] = host_copy(last_out)
 
         sharded_info = None
         if sharded and not two_pass:
@@ -1108,12 +1146,13 @@ def main() -> None:
                 t0 = time.perf_counter()
                 for i in range(args.steps):
                     p_step[i].record()
-                    step_proved(i)
+                    p_last = step_proved(i)
                 p_step[args.steps].record()
                 torch.cuda.synchronize()
                 if sharded:
                     dist.barrier()
                 p_elapsed = time.perf_counter() - t0
+                last_outputs["proved"] = host_copy(p_last)
                 if sharded:
                     tpv = torch.tensor([p_elapsed], dtype=torch.float64, device="cpu" if test_backend else dev)
                     dist.all_reduce(tpv, op=dist.ReduceOp.MAX)
@@ -1133,10 +1172,11 @@ def main() -> None:
                     dist.barrier()
                     torch.cuda.synchronize()
                     tpp0 = time.perf_counter()
-                    run_pipelined(args.steps)
+                    pp_last = run_pipelined(args.steps)
                     torch.cuda.synchronize()
                     dist.barrier()
                     pp_elapsed = time.perf_counter() - tpp0
+                    last_outputs["proved_pipelined"] = host_copy(pp_last)
                     tpp_t = torch.tensor([pp_elapsed], dtype=torch.float64, device="cpu" if test_backend else dev)
                     dist.all_reduce(tpp_t, op=dist.ReduceOp.MAX)
                     pp_elapsed = float(tpp_t.item())
@@ -1343,6 +1383,7 @@ def main() -> None:
             "index_build_s": index_build_s,
         }
         out["config"]["item_table"] = table_kind
+        value_leg = "headline"    # the leg whose timed steps `value` reports (--dump-outputs writes its last step)
         if not two_pass:
             out["config"]["exact_path"] = "dense fp32 kernels over the whole corpus"
         if proved is not None:
@@ -1379,10 +1420,12 @@ def main() -> None:
                 out["fp32_dense"] = {"value": out["value"], "unit": "queries/s", "ms_per_step": out["ms_per_step"], "ms_per_step_stdev": out["ms_per_step_stdev"],
                                      "roofline": out["roofline"], "what": "the dense fp32 kernels over the whole corpus (exact_mode 'dense'), same step, same protocol, timed in this run"}
                 out["value"], out["ms_per_step"], out["ms_per_step_stdev"] = leg["value"], leg["ms_per_step"], leg["ms_per_step_stdev"]
+                value_leg = "proved"
                 pp = proved.get("pipelined")
                 if args.pipeline and pp and pp["output_equal_to_unpipelined"] and pp["proved_calls"] == pp["timed_calls"] and pp["dense_fp32_fallbacks"] == 0:
                     # --pipeline: the headline is the rate with one batch in flight (the plain rate stays in `proved`)
                     out["value"], out["ms_per_step"] = pp["queries_per_s"], pp["ms_per_step"]
+                    value_leg = "proved_pipelined"
                     out["config"]["pipelined"] = "batch i + 1 submitted before batch i's result is taken (ShardedTopK.submit / result)"
                 kind = "per-pair a-priori upper bound" if proved.get("upper_bound_poly") else "a-priori eps"
                 out["config"]["exact_path"] = (f"proved under the measured arithmetic model (H1-H3 re-checked on this device): f16x3 first pass + fp32 re-scoring, {kind} "
@@ -1474,6 +1517,9 @@ def main() -> None:
                                     "oracle_row": ",".join(f"{hp[m]['oracle']}" for m in ("hr@1", "hr@5", "hr@10", "hr@50", "hr@100")),
                                     "note": "HR columns: hr_parity corpus with planted targets (HIP path; oracle_row = the CPU oracle chain on the same inputs); "
                                             "time columns: the headline step of this run"}
+        if args.dump_outputs:
+            top_ids, top_scores = last_outputs[value_leg]
+            out["dump_outputs"] = {"leg": value_leg, **dump_outputs(args.dump_outputs, {"top_k_ids": top_ids, "top_k_scores": top_scores})}
         print(json.dumps(out), flush=True)
     if sharded:
         dist.destroy_process_group()

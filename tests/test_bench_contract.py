@@ -102,10 +102,39 @@ def test_committed_round5_bench_line_is_the_proved_exact_path():
     assert c4["ms_per_step"] < 0.45 * legs["fp32"]["ms_per_step"]
 
 
+def test_dump_outputs_writes_float_arrays_within_the_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs: ids exactly as float64, scores as float32; above the cap the same seeded rows of every array, listed in rows.npy."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    g = torch.Generator().manual_seed(1)
+    ids = torch.randint(0, 125_000_000, (32, 120), generator=g)
+    scores = torch.randn((32, 120), generator=g)
+    info = bench.dump_outputs(str(tmp_path / "all"), {"top_k_ids": ids, "top_k_scores": scores})
+    assert info["sampled_rows"] is False and set(info["files"]) == {"top_k_ids.npy", "top_k_scores.npy"}
+    got_ids, got_scores = np.load(tmp_path / "all" / "top_k_ids.npy"), np.load(tmp_path / "all" / "top_k_scores.npy")
+    assert got_ids.dtype == np.float64 and np.array_equal(got_ids.astype(np.int64), ids.numpy())
+    assert got_scores.dtype == np.float32 and np.array_equal(got_scores, scores.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 << 10)
+    runs = []
+    for name in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / name), {"top_k_ids": ids, "top_k_scores": scores})
+        assert info["sampled_rows"] is True
+        assert sum(f.stat().st_size for f in (tmp_path / name).iterdir()) <= bench.DUMP_MAX_BYTES
+        runs.append({f.name: np.load(f) for f in (tmp_path / name).iterdir()})
+    rows = runs[0]["rows.npy"].astype(np.int64)
+    assert 0 < len(rows) < 32 and np.array_equal(runs[0]["rows.npy"], runs[1]["rows.npy"])
+    assert np.array_equal(runs[0]["top_k_ids.npy"].astype(np.int64), ids.numpy()[rows]) and np.array_equal(runs[0]["top_k_scores.npy"], scores.numpy()[rows])
+
+
 @pytest.mark.gpu
-def test_live_bench_line():
+def test_live_bench_line(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-fast-path", "--no-matrix",
-                          "--no-other-workloads", "--no-weights-sweep"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-other-workloads", "--no-weights-sweep", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -128,3 +157,11 @@ def test_live_bench_line():
     assert 0.0 < hp["hr@50"]["hip"] < hp["hr@100"]["hip"] < 1.0      # planted targets: neither trivially 0 nor 1
     csv = d["reference_csv"]                                           # eval_from_checkpoint.py:507-515
     assert csv["header"] == "HR@1,HR@5,HR@10,HR@50,HR@100,BatchTimeMsAvg,BatchTimeMsDev" and len(csv["row"].split(",")) == 7
+    # --dump-outputs: the last timed step of the leg `value` reports -- B rows of k (id, score), ids from the corpus, scores descending
+    import numpy as np
+
+    assert d["dump_outputs"]["leg"] == "proved" and d["dump_outputs"]["sampled_rows"] is False
+    got_ids, got_scores = np.load(tmp_path / "dump" / "top_k_ids.npy"), np.load(tmp_path / "dump" / "top_k_scores.npy")
+    B, k = d["config"]["global_batch"], d["config"]["k"]
+    assert got_ids.shape == got_scores.shape == (B, k) and got_ids.dtype == np.float64 and got_scores.dtype == np.float32
+    assert ((got_ids >= 1) & (got_ids <= d["config"]["n_items"])).all() and (np.diff(got_scores, axis=1) <= 0).all()
