@@ -38,9 +38,10 @@ extern "C" {
  * 9: rails_candidates_* -- the threshold selection and the fused finish of the proved exact top-k -- and rails_merge_candidates_verdict
  * are new, rails_mol_score_indexed_rows gained cand_counts, the component table became item-group-major (rails_mol_component_build
  * gained n_total / first_item, rails_mol_component_topk its out_of_range flag, rails_mol_component_topk_capacity is new);
- * 10: rails_topk_candidates_filtered, rails_rerank_topk_filtered / rails_rerank_workspace_bytes and rails_mol_coarse_topk_capacity are new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
+ * 10: rails_topk_candidates_filtered, rails_rerank_topk_filtered / rails_rerank_workspace_bytes and rails_mol_coarse_topk_capacity are new;
+ * 11: the SASRec encoder entries rails_sasrec_* and rails_gemm_f32_id_masked are new, rails_gemm_f32 gained act 2 (relu) / 3 (gelu)).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
-#define RAILS_ABI_VERSION 10
+#define RAILS_ABI_VERSION 11
 int rails_abi_version(void);
 
 #define RAILS_OK 0
@@ -511,11 +512,21 @@ int rails_hstu_preprocess(const float* embeddings, const int64_t* ids, const int
 int rails_rows_layer_norm(const float* x, int64_t ldx, int64_t rows, int32_t dim, float eps, const float* mul, int64_t ldm,
                           float* out, int64_t ldo, void* stream);
 /* C = act(A W + bias) + residual.  w_is_nk 0: W is (K, N) row-major (the `_uvqk` parameter); 1: W is (N, K), a torch Linear
- * weight (`_o.weight`).  act 0 none / 1 silu.  With lengths != NULL rows r = b * seq_len + n, n >= lengths[b], are written
- * as zeros.  hstu.py:374-378 (torch.mm + silu), :426-434 (the output Linear + residual). */
+ * weight (`_o.weight`).  act RAILS_ACT_*: 0 none / 1 silu / 2 relu / 3 gelu (erf, torch.nn.GELU()).  With lengths != NULL rows
+ * r = b * seq_len + n, n >= lengths[b], are written as zeros.  hstu.py:374-378 (torch.mm + silu), :426-434 (the output Linear +
+ * residual). */
+#define RAILS_ACT_NONE 0
+#define RAILS_ACT_SILU 1
+#define RAILS_ACT_RELU 2
+#define RAILS_ACT_GELU 3
 int rails_gemm_f32(const float* a, int64_t lda, const float* w, int32_t w_is_nk, const float* bias, const float* residual,
                    int64_t ldr, int64_t m, int32_t n, int32_t k, int32_t act, const int64_t* lengths, int32_t seq_len, float* c,
                    int64_t ldc, void* stream);
+/* The same GEMM with SASRec's row mask instead of the lengths mask: rows r with row_ids[r] == 0 are written as zeros
+ * (sasrec.py:213, `user_embeddings *= valid_mask`; row_ids is the (m) id array of the rows). */
+int rails_gemm_f32_id_masked(const float* a, int64_t lda, const float* w, int32_t w_is_nk, const float* bias, const float* residual,
+                             int64_t ldr, int64_t m, int32_t n, int32_t k, int32_t act, const int64_t* row_ids, float* c, int64_t ldc,
+                             void* stream);
 /* MoLGatingFn.forward's combination + SoftmaxDropoutCombiner.forward as a stand-alone unit (reference
  * rails/similarities/mol/similarity_fn.py:148-201 and :31-46/:66-96, eval mode), for callers that use the modules on their own --
  * inside the scoring path all of this is fused into the scoring kernels.  Row r = b * items_per_query + x:
@@ -565,6 +576,37 @@ int rails_hstu_encode_fused(const float* embeddings, const int64_t* ids, const i
                             const float* pos_emb, const rails_hstu_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len,
                             int32_t dim, int32_t heads, int32_t dqk, int32_t dv, int32_t num_buckets, int32_t postproc_mode, float eps,
                             float* out, void* stream);
+/* ---- SASRec query encoder, eval path ----------------------------------------------------------------------------------
+ * modeling/sequential/sasrec.py (SASRec.encode / forward, dropout off).  The per-layer route: rails_hstu_preprocess with every
+ * length = seq_len (x = (ids != 0) * (emb * sqrt(dim) + pos_emb)), then per block rails_rows_layer_norm (eps 1e-8),
+ * rails_gemm_f32 (the in-projection, unmasked: q from LN(x), k / v from x), rails_sasrec_attention, rails_gemm_f32 (out_proj +
+ * the LN(x) residual), rails_rows_layer_norm, rails_gemm_f32 (conv1 + relu / gelu), rails_gemm_f32_id_masked (conv2 + residual,
+ * times the id mask); rails_rows_normalize last.
+ *
+ * Causal softmax attention (torch.nn.MultiheadAttention with the bool causal mask): qkv is (batch * seq_len, ld) with rows
+ * [q | k | v], each `dim` wide (heads x head_dim, head_dim = dim / heads <= 64); out (batch * seq_len, dim) dense:
+ *   out[b, i, h, :] = sum_{j <= i} softmax_j(q_i . k_j / sqrt(head_dim)) v_j      (every key j <= i; no key is masked by id) */
+int rails_sasrec_attention(const float* qkv, int64_t ld, int32_t batch, int32_t seq_len, int32_t dim, int32_t heads, float* out,
+                           void* stream);
+/* The whole encoder in ONE launch for short sequences (rails_sasrec_fused_supported: seq_len <= 64, dim <= 128, ffn_dim <= 128,
+ * head_dim <= 64): one workgroup per sequence, everything in LDS; writes the postprocessed embedding at position lengths[b] - 1
+ * (SASRec.encode).  `layers`: DEVICE array of n_blocks rails_sasrec_layer.  ffn_act RAILS_ACT_RELU / RAILS_ACT_GELU;
+ * postproc_mode 0 LayerNorm, 1 L2 norm, with eps.  RAILS_ENOTSUP for other geometries: chain the per-layer entries instead. */
+typedef struct rails_sasrec_layer {
+  const float* in_proj_weight;   /* (3 * dim, dim) */
+  const float* in_proj_bias;     /* (3 * dim) */
+  const float* out_proj_weight;  /* (dim, dim) */
+  const float* out_proj_bias;    /* (dim) */
+  const float* conv1_weight;     /* (ffn_dim, dim[, 1]) */
+  const float* conv1_bias;       /* (ffn_dim) */
+  const float* conv2_weight;     /* (dim, ffn_dim[, 1]) */
+  const float* conv2_bias;       /* (dim) */
+} rails_sasrec_layer;
+int rails_sasrec_fused_supported(int32_t seq_len, int32_t dim, int32_t heads, int32_t ffn_dim);
+int rails_sasrec_encode_fused(const float* embeddings, const int64_t* ids, const int64_t* lengths, const float* pos_emb,
+                              const rails_sasrec_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int32_t dim,
+                              int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* out,
+                              void* stream);
 /* out[r] = normalise(x[row_index ? row_index[r] : r]); mode 0 LayerNorm (no affine), 1 x / max(||x||, eps).
  * output_postprocessors.py:38-85 + get_current_embeddings (modeling/sequential/utils.py:74-90). */
 int rails_rows_normalize(const float* x, int64_t ldx, const int64_t* row_index, int64_t rows, int32_t dim, int32_t mode, float eps,

@@ -832,9 +832,24 @@ int rails_gemm_f32(const float* a, int64_t lda, const float* w, int32_t w_is_nk,
   if (m < 0 || n < 0 || k <= 0) { set_error("gemm_f32: bad size"); return RAILS_EINVAL; }
   if (m == 0 || n == 0) return RAILS_OK;
   if (!a || !w || !c || lda < k || ldc < n || (residual && ldr < n)) { set_error("gemm_f32: NULL pointer or short stride"); return RAILS_EINVAL; }
-  if (act != 0 && act != 1) { set_error("gemm_f32: unknown activation %d", act); return RAILS_EINVAL; }
+  if (act < RAILS_ACT_NONE || act > RAILS_ACT_GELU) { set_error("gemm_f32: unknown activation %d", act); return RAILS_EINVAL; }
   if (lengths && (seq_len <= 0 || m % seq_len != 0)) { set_error("gemm_f32: rows are not batch * seq_len"); return RAILS_EINVAL; }
   return fail(gemm_f32(a, lda, w, w_is_nk ? 1 : 0, bias, residual, ldr, m, n, k, act, lengths, seq_len, c, ldc, (hipStream_t)stream), "gemm_f32");
+}
+
+int rails_gemm_f32_id_masked(const float* a, int64_t lda, const float* w, int32_t w_is_nk, const float* bias, const float* residual,
+                             int64_t ldr, int64_t m, int32_t n, int32_t k, int32_t act, const int64_t* row_ids, float* c, int64_t ldc,
+                             void* stream) {
+  g_err[0] = '\0';
+  if (m < 0 || n < 0 || k <= 0) { set_error("gemm_f32_id_masked: bad size"); return RAILS_EINVAL; }
+  if (m == 0 || n == 0) return RAILS_OK;
+  if (!a || !w || !c || !row_ids || lda < k || ldc < n || (residual && ldr < n)) {
+    set_error("gemm_f32_id_masked: NULL pointer or short stride");
+    return RAILS_EINVAL;
+  }
+  if (act < RAILS_ACT_NONE || act > RAILS_ACT_GELU) { set_error("gemm_f32_id_masked: unknown activation %d", act); return RAILS_EINVAL; }
+  return fail(gemm_f32(a, lda, w, w_is_nk ? 1 : 0, bias, residual, ldr, m, n, k, act, nullptr, 0, c, ldc, (hipStream_t)stream, row_ids),
+              "gemm_f32_id_masked");
 }
 
 int rails_mol_gate_combine(const float* logits, int64_t ld_logits, const float* pair_part, int64_t ld_pair, const float* query_part,
@@ -904,6 +919,46 @@ int rails_hstu_encode_fused(const float* embeddings, const int64_t* ids, const i
   const int r = hstu_encode_fused(embeddings, ids, lengths, buckets, pos_emb, layers, n_blocks, batch, seq_len, dim, heads, dqk, dv,
                                   num_buckets, postproc_mode, eps, out, (hipStream_t)stream);
   return r == kOk ? r : fail(r, "hstu_encode_fused");
+}
+
+// ---- SASRec query encoder, eval path ----
+int rails_sasrec_attention(const float* qkv, int64_t ld, int32_t batch, int32_t seq_len, int32_t dim, int32_t heads, float* out,
+                           void* stream) {
+  g_err[0] = '\0';
+  if (batch < 0 || seq_len < 0 || dim <= 0 || heads <= 0) { set_error("sasrec_attention: bad size"); return RAILS_EINVAL; }
+  if (dim % heads != 0) { set_error("sasrec_attention: dim %d is not a multiple of heads %d", dim, heads); return RAILS_EINVAL; }
+  if (dim / heads > 64) { set_error("sasrec_attention: head_dim = %d (supported: <= 64)", dim / heads); return RAILS_ENOTSUP; }
+  if (batch == 0 || seq_len == 0) return RAILS_OK;
+  if (!qkv || !out || ld < (int64_t)3 * dim) { set_error("sasrec_attention: NULL pointer or short stride"); return RAILS_EINVAL; }
+  const int r = sasrec_attention(qkv, ld, batch, seq_len, heads, dim / heads, out, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "sasrec_attention");
+}
+
+int rails_sasrec_fused_supported(int32_t seq_len, int32_t dim, int32_t heads, int32_t ffn_dim) {
+  return sasrec_fused_supported(seq_len, dim, heads, ffn_dim) ? 1 : 0;
+}
+
+int rails_sasrec_encode_fused(const float* embeddings, const int64_t* ids, const int64_t* lengths, const float* pos_emb,
+                              const rails_sasrec_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int32_t dim,
+                              int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* out,
+                              void* stream) {
+  g_err[0] = '\0';
+  if (batch < 0 || n_blocks < 0 || seq_len <= 0 || dim <= 0 || heads <= 0 || ffn_dim <= 0) { set_error("sasrec_encode_fused: bad size"); return RAILS_EINVAL; }
+  if (dim % heads != 0) { set_error("sasrec_encode_fused: dim %d is not a multiple of heads %d", dim, heads); return RAILS_EINVAL; }
+  if ((ffn_act != RAILS_ACT_RELU && ffn_act != RAILS_ACT_GELU) || (postproc_mode != 0 && postproc_mode != 1)) {
+    set_error("sasrec_encode_fused: bad ffn_act %d or postproc_mode %d", ffn_act, postproc_mode);
+    return RAILS_EINVAL;
+  }
+  if (batch == 0) return RAILS_OK;
+  if (!embeddings || !ids || !lengths || !pos_emb || !out || (n_blocks > 0 && !layers)) { set_error("sasrec_encode_fused: NULL pointer"); return RAILS_EINVAL; }
+  if (!sasrec_fused_supported(seq_len, dim, heads, ffn_dim)) {
+    set_error("sasrec_encode_fused: seq_len %d, dim %d, heads %d, ffn_dim %d not supported (seq_len <= 64, dim <= 128, ffn_dim <= 128, "
+              "head_dim <= 64)", seq_len, dim, heads, ffn_dim);
+    return RAILS_ENOTSUP;
+  }
+  const int r = sasrec_encode_fused(embeddings, ids, lengths, pos_emb, layers, n_blocks, batch, seq_len, dim, heads, ffn_dim, ffn_act,
+                                    postproc_mode, eps, out, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "sasrec_encode_fused");
 }
 
 int rails_rows_normalize(const float* x, int64_t ldx, const int64_t* row_index, int64_t rows, int32_t dim, int32_t mode, float eps,

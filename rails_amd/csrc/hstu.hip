@@ -13,7 +13,7 @@
 // for exactness and few launches, not tuned):
 //   hstu_preprocess_kernel   x = [id != 0, n < len] * (emb * sqrt(D) + pos_emb[n])
 //   rows_layer_norm_kernel   y = LN(x) (no affine, biased variance), optionally * u         one wave per row
-//   gemm_f32_kernel          C = act(A W + bias) + residual, rows of padded positions zeroed;  v_mfma_f32_32x32x2_f32,
+//   gemm_f32_kernel          C = act(A W + bias) + residual, rows of padded positions (or of id 0) zeroed;  v_mfma_f32_32x32x2_f32,
 //                            one wave per 32 x 32 output tile, W given as (K, N) or as (N, K) (torch Linear)
 //   hstu_time_buckets_kernel the (B, N, N) time-bucket matrix of the relative bias, once per encode
 //   hstu_attention_kernel    a[b, i, h, :] = sum_{j <= i} silu(q_i . k_j + bias[b, i, j]) / N * v_j
@@ -107,10 +107,25 @@ struct GemmArgs {
   const float* A; int64_t lda;
   const float* W; int w_is_nk;          // 0: W[k * N + n]   1: W[n * K + k] (torch.nn.Linear.weight)
   const float* bias; const float* residual; int64_t ldr;
-  int64_t M; int N, K; int act;          // act 1: silu
+  int64_t M; int N, K; int act;          // act 1: silu, 2: relu, 3: gelu (erf)
   const int64_t* lengths; int seq_len;   // rows r = b * seq_len + n with n >= lengths[b] are written as zeros (nullable)
   float* C; int64_t ldc;
+  const int64_t* row_ids;                // rows r with row_ids[r] == 0 are written as zeros (nullable; SASRec's id mask)
 };
+
+// the epilogue both GEMM kernels share: act(acc + bias) + residual, then the row masks
+__device__ __forceinline__ float gemm_epilogue(const GemmArgs& g, int64_t m, int n, float v) {
+  if (g.act == 1) v = silu_fast(v);
+  else if (g.act == 2) v = v > 0.0f ? v : 0.0f;
+  else if (g.act == 3) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+  if (g.residual) v += g.residual[m * g.ldr + n];
+  if (g.lengths) {
+    const int64_t b = m / g.seq_len;
+    if (m - b * g.seq_len >= g.lengths[b]) v = 0.0f;
+  }
+  if (g.row_ids && g.row_ids[m] == 0) v = 0.0f;
+  return v;
+}
 
 // one wave per 32 x 32 tile of C; A rows on the MFMA row axis, output columns on the column axis.
 // A lane needs 16 consecutive k of ITS row (A, and W in the (N, K) layout): as 16 dword loads that is 16 instructions of
@@ -181,14 +196,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
   for (int r = 0; r < 16; ++r) {
     const int64_t m = m0 + acc_row(r, h);
     if (m >= g.M) continue;
-    float v = acc[r] + bias;
-    if (g.act == 1) v = silu_fast(v);
-    if (g.residual) v += g.residual[m * g.ldr + n];
-    if (g.lengths) {
-      const int64_t b = m / g.seq_len;
-      if (m - b * g.seq_len >= g.lengths[b]) v = 0.0f;
-    }
-    g.C[m * g.ldc + n] = v;
+    g.C[m * g.ldc + n] = gemm_epilogue(g, m, n, acc[r] + bias);
   }
 }
 
@@ -271,14 +279,7 @@ __global__ __launch_bounds__(256) void gemm_f32_tiled_kernel(GemmArgs g) {
   for (int r = 0; r < 16; ++r) {
     const int64_t m = m0 + wm * 32 + acc_row(r, h);
     if (m >= g.M) continue;
-    float v = acc[r] + bias;
-    if (g.act == 1) v = silu_fast(v);
-    if (g.residual) v += g.residual[m * g.ldr + n];
-    if (g.lengths) {
-      const int64_t b = m / g.seq_len;
-      if (m - b * g.seq_len >= g.lengths[b]) v = 0.0f;
-    }
-    g.C[m * g.ldc + n] = v;
+    g.C[m * g.ldc + n] = gemm_epilogue(g, m, n, acc[r] + bias);
   }
 }
 
@@ -817,9 +818,9 @@ int rows_normalize(const float* x, int64_t ldx, const int64_t* row_index, int64_
 }
 
 int gemm_f32(const float* A, int64_t lda, const float* W, int w_is_nk, const float* bias, const float* residual, int64_t ldr, int64_t M,
-             int N, int K, int act, const int64_t* lengths, int seq_len, float* C, int64_t ldc, hipStream_t stream) {
+             int N, int K, int act, const int64_t* lengths, int seq_len, float* C, int64_t ldc, hipStream_t stream, const int64_t* row_ids) {
   if (M == 0 || N == 0) return kOk;
-  GemmArgs g{A, lda, W, w_is_nk, bias, residual, ldr, M, N, K, act, lengths, seq_len, C, ldc};
+  GemmArgs g{A, lda, W, w_is_nk, bias, residual, ldr, M, N, K, act, lengths, seq_len, C, ldc, row_ids};
   // RAILS_GEMM: 0 / unset = choose, 1 = per-wave kernel, 2 = tiled kernel where its alignment conditions hold (measurement override)
   static const int forced = [] { const char* e = getenv("RAILS_GEMM"); return e ? atoi(e) : 0; }();
   const bool aligned = K % 32 == 0 && K >= 32 && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&

@@ -129,7 +129,8 @@ int rows_layer_norm(const float* x, int64_t ldx, int64_t rows, int D, float eps,
 int rows_normalize(const float* x, int64_t ldx, const int64_t* row_index, int64_t rows, int D, int mode, float eps, float* out,
                    hipStream_t stream);
 int gemm_f32(const float* A, int64_t lda, const float* W, int w_is_nk, const float* bias, const float* residual, int64_t ldr, int64_t M,
-             int N, int K, int act, const int64_t* lengths, int seq_len, float* C, int64_t ldc, hipStream_t stream);
+             int N, int K, int act, const int64_t* lengths, int seq_len, float* C, int64_t ldc, hipStream_t stream,
+             const int64_t* row_ids = nullptr);
 int gate_combine(const float* y, int64_t ldy, const float* gqi, int64_t ldq, const float* gq, const float* gi, int64_t rows, int X, int L,
                  int gi_per_row, int glu_silu, int renorm, float eps, float* out, float* pi_out, hipStream_t stream);
 int glu_gate(const float* t, int64_t ldt, int64_t rows, int F, int kind, float* out, hipStream_t stream);
@@ -142,6 +143,11 @@ bool hstu_fused_supported(int N, int D, int H, int dqk, int dv, int num_buckets)
 int hstu_encode_fused(const float* emb, const int64_t* ids, const int64_t* lengths, const unsigned char* buckets, const float* pos_emb,
                       const void* layers, int n_blocks, int B, int N, int D, int H, int dqk, int dv, int num_buckets, int mode,
                       float eps, float* out, hipStream_t stream);
+// ---- SASRec query encoder, eval path (sasrec.hip) ----
+int sasrec_attention(const float* qkv, int64_t ld, int B, int N, int H, int hd, float* out, hipStream_t stream);
+bool sasrec_fused_supported(int N, int D, int H, int F);
+int sasrec_encode_fused(const float* emb, const int64_t* ids, const int64_t* lengths, const float* pos_emb, const void* layers, int n_blocks,
+                        int B, int N, int D, int H, int F, int act, int mode, float eps, float* out, hipStream_t stream);
 int select_keys(const unsigned long long* keys, int rows, int keys_per_row, int k, float* out_scores, int64_t* out_pos,
                 hipStream_t stream);
 int bf16_rows_kth(const unsigned short* rows16, int64_t ld, int n_rows, int n, int r, float* thr, hipStream_t stream);

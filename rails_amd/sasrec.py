@@ -1,0 +1,259 @@
+"""SASRec query encoder, eval path -- the other encoder of the paper's configs (`train_fn.main_module = "SASRec"`).
+
+Mirror of modeling/sequential/sasrec.py:SASRec for inference: the reference's constructor call, its parameter / buffer names
+(`attention_layers.{i}.in_proj_weight` ..., `forward_layers.{i}._conv1d.{0,3}.*`, `_attn_mask`), so that `load_state_dict` of a
+reference checkpoint works unchanged, and its `get_item_embeddings` / `forward` / `encode` signatures.  Every floating-point
+operation runs in the HIP kernels of csrc/sasrec.hip and csrc/hstu.hip through the C ABI (rails_hstu_preprocess,
+rails_rows_layer_norm, rails_gemm_f32, rails_sasrec_attention, rails_gemm_f32_id_masked, rails_rows_normalize; or the single-launch
+rails_sasrec_encode_fused); torch only holds the parameters and moves rows (embedding lookup).
+
+The reference's quirks are kept: the id mask (ids != 0) is the only mask -- rows past `past_lengths` with a nonzero id are valid
+rows of forward(), and a masked position is still a key of every later query (its key / value row is the in-projection bias).
+
+Not supported (raises): training mode, CPU tensors.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib
+from .engine import _on_device, _ptr, _stream
+from .hstu import (HSTU, L2NormEmbeddingPostprocessor, LayerNormEmbeddingPostprocessor,
+                   LearnablePositionalEmbeddingInputFeaturesPreprocessor, LocalEmbeddingModule)
+
+BLOCK_LN_EPS = 1e-8     # F.layer_norm(..., eps=1e-8) inside every block (sasrec.py:195-212)
+_ACT = {"relu": _lib.RAILS_ACT_RELU, "gelu": _lib.RAILS_ACT_GELU}
+
+
+class _MultiheadAttention(torch.nn.Module):
+    """Parameter holder with torch.nn.MultiheadAttention's state_dict (embed_dim == kdim == vdim, bias, no bias_k / bias_v)."""
+
+    def __init__(self, dim: int, num_heads: int) -> None:
+        super().__init__()
+        if dim % num_heads != 0:
+            raise ValueError(f"embedding_dim {dim} must be divisible by num_heads {num_heads}")
+        self.embed_dim, self.num_heads = dim, num_heads
+        self.in_proj_weight = torch.nn.Parameter(torch.empty(3 * dim, dim))
+        self.in_proj_bias = torch.nn.Parameter(torch.zeros(3 * dim))
+        self.out_proj = torch.nn.Linear(dim, dim)
+        torch.nn.init.xavier_normal_(self.in_proj_weight)
+        torch.nn.init.xavier_normal_(self.out_proj.weight)
+
+
+class _FeedForward(torch.nn.Module):
+    """StandardAttentionFF's parameters: `_conv1d` = [Conv1d(D, F, 1), act, Dropout, Conv1d(F, D, 1), Dropout]."""
+
+    def __init__(self, dim: int, hidden_dim: int, activation_fn: str) -> None:
+        super().__init__()
+        self._conv1d = torch.nn.Sequential(
+            torch.nn.Conv1d(dim, hidden_dim, kernel_size=1),
+            torch.nn.GELU() if activation_fn == "gelu" else torch.nn.ReLU(),
+            torch.nn.Dropout(p=0.0),
+            torch.nn.Conv1d(hidden_dim, dim, kernel_size=1),
+            torch.nn.Dropout(p=0.0),
+        )
+
+
+class SASRec(torch.nn.Module):
+    """encode(past_lengths (B,), past_ids (B, N), past_embeddings (B, N, D), past_payloads) -> (B, D);
+    forward(...) -> (B, N, D).  N must equal max_sequence_len + max_output_len."""
+
+    def __init__(self, max_sequence_len: int, max_output_len: int, embedding_dim: int, num_blocks: int, num_heads: int,
+                 ffn_hidden_dim: int, ffn_activation_fn: str = "relu", *args, **kwargs) -> None:
+        """Two signatures:
+          the reference's (modeling/sequential/sasrec.py) -- ..., ffn_activation_fn, ffn_dropout_rate, embedding_module,
+            similarity_module, input_features_preproc_module, output_postproc_module, activation_checkpoint=False,
+            verbose=False -- with rails_amd's LocalEmbeddingModule / LearnablePositionalEmbeddingInputFeaturesPreprocessor /
+            {L2Norm,LayerNorm}EmbeddingPostprocessor (or any objects with the same attributes);
+          the compact one -- ..., ffn_activation_fn="relu", num_items, similarity_module=None, output_postproc="layer_norm",
+            eps=1e-6."""
+        super().__init__()
+        reference_style = "embedding_module" in kwargs or (len(args) >= 2 and isinstance(args[1], torch.nn.Module))
+        if reference_style:
+            names = ["ffn_dropout_rate", "embedding_module", "similarity_module", "input_features_preproc_module",
+                     "output_postproc_module", "activation_checkpoint", "verbose"]
+            a = dict(activation_checkpoint=False, verbose=False)
+        else:
+            names = ["num_items", "similarity_module", "output_postproc", "eps"]
+            a = dict(similarity_module=None, output_postproc="layer_norm", eps=1e-6)
+        if len(args) > len(names):
+            raise TypeError(f"SASRec() takes at most {7 + len(names)} positional arguments")
+        a.update(dict(zip(names, args)))
+        for key, v in kwargs.items():
+            if key not in names:
+                raise TypeError(f"SASRec() got an unexpected keyword argument '{key}'")
+            a[key] = v
+        missing = [n for n in names if n not in a]
+        if missing:
+            raise TypeError(f"SASRec() missing required arguments: {missing}")
+        if ffn_activation_fn not in _ACT:
+            raise ValueError(f"Invalid activation_fn {ffn_activation_fn}")
+        if reference_style:
+            emb_mod, pre_mod, post_mod = a["embedding_module"], a["input_features_preproc_module"], a["output_postproc_module"]
+            if not hasattr(emb_mod, "_item_emb") or not hasattr(pre_mod, "_pos_emb"):
+                raise NotImplementedError("SASRec needs a LocalEmbeddingModule-like embedding_module (`_item_emb`) and a "
+                                          "LearnablePositionalEmbeddingInputFeaturesPreprocessor-like preprocessor (`_pos_emb`)")
+            output_postproc = getattr(post_mod, "mode", None) or {"l2": "l2_norm", "ln": "layer_norm"}.get(post_mod.debug_str())
+            eps = float(getattr(post_mod, "_eps", 1e-6))
+        else:
+            output_postproc, eps = a["output_postproc"], a["eps"]
+        if output_postproc not in ("layer_norm", "l2_norm"):
+            raise ValueError(f"Unknown output_postproc {output_postproc}")
+        self._ndp_module = a["similarity_module"]
+        self._embedding_dim = embedding_dim
+        self._seq = max_sequence_len + max_output_len
+        self._max_sequence_length = self._seq
+        self._num_blocks, self._num_heads = num_blocks, num_heads
+        self._ffn_hidden_dim, self._ffn_activation_fn = ffn_hidden_dim, ffn_activation_fn
+        self._postproc, self._eps = output_postproc, eps
+        if reference_style:
+            self._embedding_module, self._input_features_preproc, self._output_postproc = emb_mod, pre_mod, post_mod
+        else:
+            self._embedding_module = LocalEmbeddingModule(a["num_items"], embedding_dim)
+            self._input_features_preproc = LearnablePositionalEmbeddingInputFeaturesPreprocessor(self._seq, embedding_dim)
+            self._output_postproc = (LayerNormEmbeddingPostprocessor(embedding_dim, eps) if output_postproc == "layer_norm"
+                                     else L2NormEmbeddingPostprocessor(embedding_dim, eps))
+        self.attention_layers = torch.nn.ModuleList([_MultiheadAttention(embedding_dim, num_heads) for _ in range(num_blocks)])
+        self.forward_layers = torch.nn.ModuleList([_FeedForward(embedding_dim, ffn_hidden_dim, ffn_activation_fn) for _ in range(num_blocks)])
+        self.register_buffer("_attn_mask", torch.triu(torch.ones((self._seq, self._seq), dtype=torch.bool), diagonal=1))
+        self.use_fused_kernel = True    # short sequences: the whole encoder in one launch (falls back when it does not fit)
+        self._fused_ptrs = None
+
+    # ---- reference API ------------------------------------------------------------------------------------------
+    def get_item_embeddings(self, item_ids: torch.Tensor) -> torch.Tensor:
+        return self._embedding_module._item_emb(item_ids)       # a row gather
+
+    def debug_str(self) -> str:
+        return (f"SASRec-d{self._embedding_dim}-b{self._num_blocks}-h{self._num_heads}-{self._input_features_preproc.debug_str()}-"
+                f"{self._output_postproc.debug_str()}-ffn{self._ffn_hidden_dim}-{self._ffn_activation_fn}")
+
+    def forward(self, past_lengths, past_ids, past_embeddings, past_payloads: Optional[Dict[str, torch.Tensor]] = None,
+                batch_id=None) -> torch.Tensor:
+        """(B, N, D) postprocessed sequence embeddings (sasrec.py generate_user_embeddings).  Lengths play no part here, as in the
+        reference: every position with a nonzero id is a valid row."""
+        self._check(past_ids, past_embeddings)
+        self._check_device(past_embeddings)
+        x = self._run_layers(past_ids, past_embeddings)
+        B, N, D = past_embeddings.shape
+        return self._normalize(x, None).view(B, N, D)
+
+    def encode(self, past_lengths, past_ids, past_embeddings, past_payloads: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+        """(B, D): the postprocessed embedding at position past_lengths - 1 (modeling/sequential/utils.py:74-90).  Lengths follow
+        HSTU's policy (HSTU._lengths): host lengths outside [1, N] raise, device lengths are clamped and counted
+        (HSTU.length_violations())."""
+        self._check(past_ids, past_embeddings)
+        B, N = past_ids.shape
+        dev = past_embeddings.device
+        lengths = HSTU._lengths(past_lengths, dev, N)
+        self._check_device(past_embeddings)
+        if self.use_fused_kernel:
+            out = self._encode_fused(lengths, past_ids, past_embeddings)
+            if out is not None:
+                return out
+        x = self._run_layers(past_ids, past_embeddings)
+        rows = torch.arange(B, device=dev, dtype=torch.int64) * N + (lengths - 1)
+        return self._normalize(x, rows)
+
+    # ---- HIP path ------------------------------------------------------------------------------------------------
+    def _check(self, past_ids, past_embeddings) -> None:
+        if self.training:
+            raise NotImplementedError("rails_amd.SASRec is eval-only: call .eval()")
+        B, N = past_ids.shape
+        if N != self._seq or past_embeddings.shape != (B, N, self._embedding_dim):
+            raise ValueError(f"expected past_ids (B, {self._seq}) and past_embeddings (B, {self._seq}, {self._embedding_dim}), "
+                             f"got {tuple(past_ids.shape)} and {tuple(past_embeddings.shape)}")
+
+    @staticmethod
+    def _check_device(past_embeddings) -> None:
+        if not past_embeddings.is_cuda:
+            raise RuntimeError("rails_amd.SASRec runs on the GPU only (no CPU fallback)")
+
+    def _layer_tensors(self, dev):
+        """Per block: fp32 contiguous in_proj_weight, in_proj_bias, out_proj weight / bias, conv1 weight / bias, conv2 weight / bias
+        (Conv1d weights (out, in, 1) read as (out, in) Linear weights)."""
+        out = []
+        for att, ff in zip(self.attention_layers, self.forward_layers):
+            c1, c2 = ff._conv1d[0], ff._conv1d[3]
+            out.append([t.detach().to(device=dev, dtype=torch.float32).contiguous()
+                        for t in (att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias,
+                                  c1.weight, c1.bias, c2.weight, c2.bias)])
+        return out
+
+    def _encode_fused(self, lengths, past_ids, past_embeddings) -> Optional[torch.Tensor]:
+        """Single-launch encoder (rails_sasrec_encode_fused).  None when the geometry does not fit (the per-layer kernels then run)."""
+        lib = _lib.load()
+        B, N = past_ids.shape
+        D, H, F = self._embedding_dim, self._num_heads, self._ffn_hidden_dim
+        if not lib.rails_sasrec_fused_supported(N, D, H, F):
+            return None
+        dev = past_embeddings.device
+        tensors = self._layer_tensors(dev)   # kept alive until the launch is enqueued
+        rows = [[t.data_ptr() for t in layer] for layer in tensors]
+        key = tuple(p for r in rows for p in r)
+        if self._fused_ptrs is None or self._fused_ptrs[0] != key:
+            self._fused_ptrs = (key, torch.tensor(rows, dtype=torch.int64).to(dev))
+        ltab = self._fused_ptrs[1]
+        ids = past_ids.to(device=dev, dtype=torch.int64).contiguous()
+        emb = past_embeddings.detach().to(dtype=torch.float32).contiguous()
+        pos = self._input_features_preproc._pos_emb.weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _lib.check(lib.rails_sasrec_encode_fused(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(pos), _ptr(ltab), self._num_blocks, B, N, D, H, F,
+                                                     _ACT[self._ffn_activation_fn], 0 if self._postproc == "layer_norm" else 1,
+                                                     C.c_float(self._eps), _ptr(out), _stream()), "rails_sasrec_encode_fused")
+        return out
+
+    def _normalize(self, x2d: torch.Tensor, rows: Optional[torch.Tensor]) -> torch.Tensor:
+        lib = _lib.load()
+        n = x2d.shape[0] if rows is None else rows.numel()
+        out = torch.empty((n, x2d.shape[1]), dtype=torch.float32, device=x2d.device)
+        with _on_device(x2d.device):
+            _lib.check(lib.rails_rows_normalize(_ptr(x2d), x2d.stride(0), _ptr(rows) if rows is not None else None, n, x2d.shape[1],
+                                                0 if self._postproc == "layer_norm" else 1, C.c_float(self._eps), _ptr(out), _stream()),
+                       "rails_rows_normalize")
+        return out
+
+    def _run_layers(self, past_ids, past_embeddings) -> torch.Tensor:
+        """The block stack on the (B * N, D) rows; returns the last block's output (before the postprocessor)."""
+        lib = _lib.load()
+        dev = past_embeddings.device
+        B, N = past_ids.shape
+        D, H, F = self._embedding_dim, self._num_heads, self._ffn_hidden_dim
+        M = B * N
+        eps = C.c_float(BLOCK_LN_EPS)
+        act = _ACT[self._ffn_activation_fn]
+        layers = self._layer_tensors(dev)    # fp32 copies must outlive the launches that read them
+        ids = past_ids.to(device=dev, dtype=torch.int64).contiguous()
+        emb = past_embeddings.detach().to(dtype=torch.float32).contiguous()
+        pos = self._input_features_preproc._pos_emb.weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        full = torch.full((B,), N, dtype=torch.int64, device=dev)   # the mask is ids != 0 alone
+        x = torch.empty((M, D), dtype=torch.float32, device=dev)
+        qn = torch.empty((M, D), dtype=torch.float32, device=dev)
+        qkv = torch.empty((M, 3 * D), dtype=torch.float32, device=dev)
+        att = torch.empty((M, D), dtype=torch.float32, device=dev)
+        y = torch.empty((M, D), dtype=torch.float32, device=dev)
+        hid = torch.empty((M, F), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            st = _stream()
+            _lib.check(lib.rails_hstu_preprocess(_ptr(emb), _ptr(ids), _ptr(full), _ptr(pos), B, N, D, C.c_float(float(D) ** 0.5), _ptr(x), st),
+                       "rails_hstu_preprocess")
+            for w_in, b_in, w_o, b_o, w1, b1, w2, b2 in layers:
+                # Q = LN(x);  q = Q W_q^T + b_q;  [k | v] = x W_kv^T + b_kv  (no row mask: masked rows are keys too)
+                _lib.check(lib.rails_rows_layer_norm(_ptr(x), D, M, D, eps, None, 0, _ptr(qn), D, st), "rails_rows_layer_norm")
+                _lib.check(lib.rails_gemm_f32(_ptr(qn), D, _ptr(w_in), 1, _ptr(b_in), None, 0, M, D, D, 0, None, 0, _ptr(qkv), 3 * D, st),
+                           "rails_gemm_f32")
+                _lib.check(lib.rails_gemm_f32(_ptr(x), D, w_in.data_ptr() + 4 * D * D, 1, b_in.data_ptr() + 4 * D, None, 0, M, 2 * D, D, 0, None, 0,
+                                              qkv.data_ptr() + 4 * D, 3 * D, st), "rails_gemm_f32")
+                _lib.check(lib.rails_sasrec_attention(_ptr(qkv), 3 * D, B, N, D, H, _ptr(att), st), "rails_sasrec_attention")
+                # y = Q + a W_o^T + b_o;  z = LN(y);  x = (act(z W_1^T + b_1) W_2^T + b_2 + z) * (ids != 0)
+                _lib.check(lib.rails_gemm_f32(_ptr(att), D, _ptr(w_o), 1, _ptr(b_o), _ptr(qn), D, M, D, D, 0, None, 0, _ptr(y), D, st), "rails_gemm_f32")
+                _lib.check(lib.rails_rows_layer_norm(_ptr(y), D, M, D, eps, None, 0, _ptr(qn), D, st), "rails_rows_layer_norm")
+                _lib.check(lib.rails_gemm_f32(_ptr(qn), D, _ptr(w1), 1, _ptr(b1), None, 0, M, F, D, act, None, 0, _ptr(hid), F, st), "rails_gemm_f32")
+                _lib.check(lib.rails_gemm_f32_id_masked(_ptr(hid), F, _ptr(w2), 1, _ptr(b2), _ptr(qn), D, M, D, F, 0, _ptr(ids), _ptr(x), D, st),
+                           "rails_gemm_f32_id_masked")
+        return x
+
+    length_violations = staticmethod(HSTU.length_violations)
