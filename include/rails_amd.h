@@ -39,9 +39,10 @@ extern "C" {
  * are new, rails_mol_score_indexed_rows gained cand_counts, the component table became item-group-major (rails_mol_component_build
  * gained n_total / first_item, rails_mol_component_topk its out_of_range flag, rails_mol_component_topk_capacity is new);
  * 10: rails_topk_candidates_filtered, rails_rerank_topk_filtered / rails_rerank_workspace_bytes and rails_mol_coarse_topk_capacity are new;
- * 11: the SASRec encoder entries rails_sasrec_* and rails_gemm_f32_id_masked are new, rails_gemm_f32 gained act 2 (relu) / 3 (gelu)).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
+ * 11: the SASRec encoder entries rails_sasrec_* and rails_gemm_f32_id_masked are new, rails_gemm_f32 gained act 2 (relu) / 3 (gelu);
+ * 12: the HSTU cached-decoding entries rails_hstu_decode[_supported] and struct rails_hstu_decode_layer are new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
-#define RAILS_ABI_VERSION 11
+#define RAILS_ABI_VERSION 12
 int rails_abi_version(void);
 
 #define RAILS_OK 0
@@ -501,7 +502,7 @@ int rails_filter_seen_ids(const int64_t* top_ids, const float* top_scores, int32
                           float* out_scores, void* stream);
 
 /* ---- HSTU query encoder, eval path -----------------------------------
- * The step upstream of the retrieval path: modeling/sequential/hstu.py (HSTU.encode with no cache / delta path), without
+ * The step upstream of the retrieval path: modeling/sequential/hstu.py (HSTU.encode; its cache / delta path is rails_hstu_decode), without
  * fbgemm-gpu.  All tensors are fp32 and padded: (batch, seq_len, ...) with `lengths[b]` valid positions per row; rows at
  * positions >= lengths[b] are held at zero, which is what the reference's jagged layout amounts to.
  * rails_amd/hstu.py chains these per layer; a non-Python host would do the same. */
@@ -576,6 +577,36 @@ int rails_hstu_encode_fused(const float* embeddings, const int64_t* ids, const i
                             const float* pos_emb, const rails_hstu_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len,
                             int32_t dim, int32_t heads, int32_t dqk, int32_t dv, int32_t num_buckets, int32_t postproc_mode, float eps,
                             float* out, void* stream);
+/* Cached incremental decoding (HSTU.encode / generate_user_embeddings with delta_x_offsets and cache, hstu.py:144-213,
+ * :276-433): ONE launch re-encodes one row per sequence, position positions[b] < lengths[b], through all n_blocks layers
+ * against the K / V of every other position held in the cache, and writes that row's v, q, k and layer output into the cache
+ * in place.  The jagged row of sequence b is sum_{b' < b} lengths[b'] + positions[b], derived from the lengths (no caller
+ * offsets).  Per layer the cache is the reference's (v, padded_q, padded_k, outputs): v (cache_rows, heads * dv) and outputs
+ * (cache_rows, dim) jagged, q / k (batch, seq_len, heads * dqk) padded; every layer's v / outputs have the same cache_rows.
+ * Inputs: embeddings (batch, seq_len, dim) and ids (batch, seq_len) are read at row positions[b] only; timestamps
+ * (batch, seq_len) or NULL (no bias); thresholds as for rails_hstu_time_buckets; pos_emb (>= seq_len, dim); linear_act
+ * RAILS_ACT_NONE / RAILS_ACT_SILU (the uvqk activation).  out (batch, dim): the postprocessed last layer's outputs row at
+ * lengths[b] - 1 (the cached row when positions[b] < lengths[b] - 1, as the reference returns).  A sequence whose length lies
+ * outside [1, seq_len], whose position lies outside [0, length), or whose rows fall outside cache_rows is left alone: no cache
+ * row is written and its out row is NaN.  `layers`: DEVICE array of n_blocks rails_hstu_decode_layer entries, ts_w / pos_w NULL for a
+ * layer without relative bias.  dim <= 1024, dqk and dv <= 32, num_buckets <= 255 and an LDS bound, checked by
+ * rails_hstu_decode_supported; RAILS_ENOTSUP otherwise. */
+typedef struct rails_hstu_decode_layer {
+  const float* uvqk;   /* parameters as in rails_hstu_layer */
+  const float* o_w;
+  const float* o_b;
+  const float* ts_w;
+  const float* pos_w;
+  float* v;            /* (cache_rows, heads * dv) */
+  float* q;            /* (batch, seq_len, heads * dqk) */
+  float* k;            /* (batch, seq_len, heads * dqk) */
+  float* outputs;      /* (cache_rows, dim) */
+} rails_hstu_decode_layer;
+int rails_hstu_decode_supported(int32_t seq_len, int32_t dim, int32_t heads, int32_t dqk, int32_t dv, int32_t num_buckets);
+int rails_hstu_decode(const float* embeddings, const int64_t* ids, const int64_t* positions, const int64_t* lengths,
+                      const int64_t* timestamps, const int64_t* thresholds, const float* pos_emb, const rails_hstu_decode_layer* layers,
+                      int32_t n_blocks, int32_t batch, int32_t seq_len, int64_t cache_rows, int32_t dim, int32_t heads, int32_t dqk,
+                      int32_t dv, int32_t num_buckets, int32_t linear_act, int32_t postproc_mode, float eps, float* out, void* stream);
 /* ---- SASRec query encoder, eval path ----------------------------------------------------------------------------------
  * modeling/sequential/sasrec.py (SASRec.encode / forward, dropout off).  The per-layer route: rails_hstu_preprocess with every
  * length = seq_len (x = (ids != 0) * (emb * sqrt(dim) + pos_emb)), then per block rails_rows_layer_norm (eps 1e-8),

@@ -21,6 +21,7 @@
 //                            register r, which IS the B operand of the K-step {row(r,0), row(r,1)} of O^T += V^T P^T
 //   rows_normalize_kernel    LayerNorm or L2 normalisation of selected rows (the postprocessor + get_current_embeddings)
 //   hstu_fused_kernel        the whole encoder in one launch for seq_len <= 64: one workgroup per sequence, all in LDS
+//   hstu_decode_kernel       cached incremental decoding: one row per sequence through every layer against the cached K / V
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -945,6 +946,322 @@ int hstu_attention(const float* uvqk, int64_t ld, int B, int N, int H, int dqk, 
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
   }
   hipLaunchKernelGGL(hstu_attention_kernel, dim3((N + 31) / 32, H, B), dim3(64), lds, stream, a);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cached incremental decoding (hstu.py:144-213, :276-433 with delta_x_offsets): ONE launch for the whole stack, one workgroup
+// per sequence.  Sequence b re-encodes the single row at position p = positions[b] (jagged row r = sum_{b' < b} lengths[b'] + p,
+// derived here from the lengths, so no caller-supplied offset can steer a write) against the K / V the cache holds for every
+// other position:
+//   x = [id != 0] (emb * sqrt(D) + pos_emb[p]);  per layer:  y = act(LN(x) Wuvqk) -> u | v | q | k, written into the cache's
+//   v[r], q[b, p], k[b, p];  a_h = sum_{j <= p} silu(q_h . k_hj + pos_w[N-1+j-p] + ts_w[bucket(ts[min(p+1, N-1)] - ts[j])]) / N v_hj
+//   with key p taken from this row;  x = Wo (u * LN(a)) + bo + x, written into the cache's outputs[r].
+// The result is the postprocessed last layer's outputs row at lengths[b] - 1: this row when p == lengths[b] - 1, otherwise the
+// cached row (which this launch never writes).  The row's x, LN(x), y and a live in LDS; the weights stream from L2, which serves
+// them to every sequence (eight waves: enough loads in flight to stream them; four waves were latency-bound at 200 us per ML-20M
+// layer).  One wave per head walks the keys j < p, one key per lane.  Nothing is bounded by N.
+// A sequence whose length, position or derived row falls outside [1, N], [0, length) or the cache's rows writes no cache row and
+// gets a NaN result row.
+// ---------------------------------------------------------------------------------------------
+constexpr int kDecThreads = 512;
+constexpr int kDecWaves = kDecThreads / 64;
+constexpr int kDecMaxDim = 1024;
+constexpr int kDecMaxHead = 32;       // dqk, dv
+constexpr int kDecLdsBytes = 60 * 1024;   // dynamic LDS; stays under the 64 KiB a launch gets without opting in
+
+struct DecodeLayer {                  // mirrors rails_hstu_decode_layer
+  const float* uvqk; const float* o_w; const float* o_b; const float* ts_w; const float* pos_w;
+  float* v; float* q; float* k; float* outputs;
+};
+static_assert(sizeof(DecodeLayer) == sizeof(rails_hstu_decode_layer), "DecodeLayer mirrors rails_hstu_decode_layer field for field");
+
+struct DecodeArgs {
+  const float* emb; const int64_t* ids; const int64_t* positions; const int64_t* lengths; const int64_t* ts; const int64_t* thresholds;
+  const float* pos_emb; const DecodeLayer* layers; int n_blocks;
+  int B, N; int64_t cache_rows; int D, H, dqk, dv, num_buckets, act, mode;
+  float eps;
+  float* out;
+};
+
+static size_t hstu_decode_lds_bytes(int D, int H, int dqk, int dv, int num_buckets) {
+  const size_t HV = (size_t)H * dv, W = 2 * (size_t)H * (dv + dqk);
+  const size_t part = W > 4 * (size_t)kDecThreads ? W : 4 * (size_t)kDecThreads;
+  return sizeof(int64_t) * (size_t)num_buckets + sizeof(float) * (2 * (size_t)D + W + HV + kDecWaves + part);
+}
+
+// sum over the workgroup; every thread gets the total.  red: kDecWaves floats of LDS
+__device__ __forceinline__ float dec_block_sum(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.0f;
+#pragma unroll
+  for (int w = 0; w < kDecWaves; ++w) s += red[w];
+  return s;
+}
+
+// dst[i] = LN(src)[i] (no affine, biased variance) [* mul[i]]; src == dst allowed
+__device__ __forceinline__ void dec_layer_norm(const float* src, float* dst, const float* mul, int n, float eps, float* red) {
+  float s = 0.0f;
+  for (int i = threadIdx.x; i < n; i += kDecThreads) s += src[i];
+  const float mean = dec_block_sum(s, red) / (float)n;
+  float v = 0.0f;
+  for (int i = threadIdx.x; i < n; i += kDecThreads) { const float c = src[i] - mean; v = __builtin_fmaf(c, c, v); }
+  const float rstd = 1.0f / sqrtf(dec_block_sum(v, red) / (float)n + eps);
+  for (int i = threadIdx.x; i < n; i += kDecThreads) {
+    float y = (src[i] - mean) * rstd;
+    if (mul) y *= mul[i];
+    dst[i] = y;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kDecThreads) void hstu_decode_kernel(DecodeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dec_smem[];
+  const int N = a.N, D = a.D, H = a.H, dqk = a.dqk, dv = a.dv;
+  const int HV = H * dv, HQ = H * dqk, W = 2 * (HV + HQ);
+  int64_t* thr = reinterpret_cast<int64_t*>(dec_smem);          // [num_buckets]
+  float* xs = reinterpret_cast<float*>(thr + a.num_buckets);    // [D]  the row's residual stream
+  float* xn = xs + D;                                           // [D]  LN(x)
+  float* ys = xn + D;                                           // [W]  u | v | q | k
+  float* as = ys + W;                                           // [HV] attention, then u * LN(attention)
+  float* red = as + HV;                                         // [kDecWaves]
+  float* part = red + kDecWaves;                                // [max(W, 4 * threads)]  k-slice partial sums of the uvqk GEMV
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // ---- the jagged row: offset = sum of the preceding lengths (each must lie in [0, N])
+  long long off = 0;
+  int bad = 0;
+  for (int i = tid; i < b; i += kDecThreads) {
+    const int64_t l = a.lengths[i];
+    bad |= (l < 0 || l > N);
+    off += l;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { off += __shfl_xor(off, o, 64); bad |= __shfl_xor(bad, o, 64); }
+  __shared__ long long off_s[kDecWaves];
+  __shared__ int bad_s[kDecWaves];
+  if (lane == 0) { off_s[wave] = off; bad_s[wave] = bad; }
+  __syncthreads();
+  off = 0; bad = 0;
+#pragma unroll
+  for (int w = 0; w < kDecWaves; ++w) { off += off_s[w]; bad |= bad_s[w]; }
+  const int64_t len = a.lengths[b], p = a.positions[b];
+  if (bad || len < 1 || len > N || p < 0 || p >= len || off + len > a.cache_rows) {
+    for (int i = tid; i < D; i += kDecThreads) a.out[(int64_t)b * D + i] = __builtin_nanf("");
+    return;
+  }
+  const int64_t row = off + p;                                  // jagged row of the delta: < cache_rows
+  const int64_t prow = (int64_t)b * N + p;                      // padded row of the delta: < B * N
+  const int pi = (int)p;
+
+  // ---- prologue: thresholds to LDS; x = the preprocessed input row
+  if (a.ts)
+    for (int i = tid; i < a.num_buckets; i += kDecThreads) thr[i] = a.thresholds[i];
+  const bool keep = a.ids[prow] != 0;
+  const float scale = sqrtf((float)D);
+  for (int i = tid; i < D; i += kDecThreads) xs[i] = keep ? a.emb[prow * D + i] * scale + a.pos_emb[(int64_t)pi * D + i] : 0.0f;
+  __syncthreads();
+  const float inv_n = 1.0f / (float)N;
+  const int64_t tq = a.ts ? a.ts[(int64_t)b * N + (pi + 1 < N ? pi + 1 : N - 1)] : 0;
+
+  for (int blk = 0; blk < a.n_blocks; ++blk) {
+    const DecodeLayer L = a.layers[blk];
+    const bool biased = a.ts != nullptr && L.ts_w != nullptr;
+    // ---- y = act(LN(x) Wuvqk).  Rows of the weight are 16-byte aligned (the usual case): a thread owns four adjacent columns and one
+    // of S = threads / (W / 4) interleaved k slices, with four partial sums (float4 loads, four rows in flight per thread); the slices
+    // are added in order through LDS.  Otherwise a thread per column with eight partial sums (k mod 8).  One long fma chain per
+    // column was measured 4x further from float64 than the fp32 oracle on an ML-20M row; both orders here stay below it.
+    dec_layer_norm(xs, xn, nullptr, D, a.eps, red);
+    if ((W & 3) == 0 && (reinterpret_cast<uintptr_t>(L.uvqk) & 15) == 0) {
+      const int G = W >> 2;
+      const int S = G >= kDecThreads ? 1 : kDecThreads / G;
+      for (int t = tid; t < G * S; t += kDecThreads) {
+        const int g = t % G, sl = t / G;
+        const float* wg = L.uvqk + 4 * g;
+        float acc[4][4] = {};
+        int k = sl;
+        for (; k + 3 * S < D; k += 4 * S) {
+          float4 w4[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) w4[u] = *reinterpret_cast<const float4*>(wg + (int64_t)(k + u * S) * W);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float xv = xn[k + u * S];
+            acc[u][0] = __builtin_fmaf(xv, w4[u].x, acc[u][0]);
+            acc[u][1] = __builtin_fmaf(xv, w4[u].y, acc[u][1]);
+            acc[u][2] = __builtin_fmaf(xv, w4[u].z, acc[u][2]);
+            acc[u][3] = __builtin_fmaf(xv, w4[u].w, acc[u][3]);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+          if (k + u * S < D) {
+            const float4 w4 = *reinterpret_cast<const float4*>(wg + (int64_t)(k + u * S) * W);
+            const float xv = xn[k + u * S];
+            acc[u][0] = __builtin_fmaf(xv, w4.x, acc[u][0]);
+            acc[u][1] = __builtin_fmaf(xv, w4.y, acc[u][1]);
+            acc[u][2] = __builtin_fmaf(xv, w4.z, acc[u][2]);
+            acc[u][3] = __builtin_fmaf(xv, w4.w, acc[u][3]);
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) part[sl * W + 4 * g + e] = (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]);
+      }
+      __syncthreads();
+      for (int c = tid; c < W; c += kDecThreads) {
+        float v = part[c];
+        for (int sl = 1; sl < S; ++sl) v += part[sl * W + c];
+        ys[c] = a.act == 1 ? silu_fast(v) : v;
+      }
+    } else {
+      for (int c = tid; c < W; c += kDecThreads) {
+        const float* wc = L.uvqk + c;
+        float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        int k = 0;
+        for (; k + 8 <= D; k += 8) {
+          float w8[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) w8[u] = wc[(int64_t)(k + u) * W];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) acc[u] = __builtin_fmaf(xn[k + u], w8[u], acc[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 7; ++u)
+          if (k + u < D) acc[u] = __builtin_fmaf(xn[k + u], wc[(int64_t)(k + u) * W], acc[u]);
+        const float v = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+        ys[c] = a.act == 1 ? silu_fast(v) : v;
+      }
+    }
+    __syncthreads();
+    // ---- the delta row's v, q, k into the cache
+    for (int i = tid; i < HV; i += kDecThreads) L.v[row * HV + i] = ys[HV + i];
+    for (int i = tid; i < HQ; i += kDecThreads) {
+      L.q[prow * HQ + i] = ys[2 * HV + i];
+      L.k[prow * HQ + i] = ys[2 * HV + HQ + i];
+    }
+    // ---- attention row p: one wave per head, one key per lane; keys j < p from the cache, key p from LDS
+    for (int head = wave; head < H; head += kDecWaves) {
+      float qv[kDecMaxHead], acc[kDecMaxHead];
+#pragma unroll
+      for (int d = 0; d < kDecMaxHead; ++d) { qv[d] = d < dqk ? ys[2 * HV + head * dqk + d] : 0.0f; acc[d] = 0.0f; }
+      auto weight = [&](int j, float s) {
+        if (biased) {
+          long long dt = tq - a.ts[(int64_t)b * N + j];
+          if (dt < 0) dt = -dt;
+          int lo = 0, hi = a.num_buckets;
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (thr[mid] <= dt) lo = mid + 1; else hi = mid;
+          }
+          s += L.pos_w[N - 1 + j - pi] + L.ts_w[lo];
+        }
+        return silu_fast(s) * inv_n;
+      };
+      for (int j = lane; j < pi; j += 64) {
+        const float* kr = L.k + ((int64_t)b * N + j) * HQ + head * dqk;
+        const float* vr = L.v + (off + j) * HV + head * dv;
+        float s = 0.0f;
+#pragma unroll
+        for (int d = 0; d < kDecMaxHead; ++d)
+          if (d < dqk) s = __builtin_fmaf(qv[d], kr[d], s);
+        const float w = weight(j, s);
+#pragma unroll
+        for (int d = 0; d < kDecMaxHead; ++d)
+          if (d < dv) acc[d] = __builtin_fmaf(w, vr[d], acc[d]);
+      }
+      if (lane == 0) {
+        float s = 0.0f;
+#pragma unroll
+        for (int d = 0; d < kDecMaxHead; ++d)
+          if (d < dqk) s = __builtin_fmaf(qv[d], ys[2 * HV + HQ + head * dqk + d], s);
+        const float w = weight(pi, s);
+#pragma unroll
+        for (int d = 0; d < kDecMaxHead; ++d)
+          if (d < dv) acc[d] = __builtin_fmaf(w, ys[HV + head * dv + d], acc[d]);
+      }
+#pragma unroll
+      for (int d = 0; d < kDecMaxHead; ++d) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[d] += __shfl_xor(acc[d], o, 64);
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int d = 0; d < kDecMaxHead; ++d)
+          if (d < dv) as[head * dv + d] = acc[d];
+      }
+    }
+    __syncthreads();
+    // ---- o_input = u * LN(a);  x = Wo o_input + bo + x: one wave per output column (a row of the torch Linear weight)
+    dec_layer_norm(as, as, ys, HV, a.eps, red);
+    for (int n0 = 4 * wave; n0 < D; n0 += 4 * kDecWaves) {       // four rows per wave at a time: four loads in flight per lane
+      float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int k = lane; k < HV; k += 64) {
+        const float av = as[k];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n0 + r < D) s[r] = __builtin_fmaf(av, L.o_w[(int64_t)(n0 + r) * HV + k], s[r]);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[r] += __shfl_xor(s[r], o, 64);
+        if (lane == 0 && n0 + r < D) xs[n0 + r] = s[r] + L.o_b[n0 + r] + xs[n0 + r];
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < D; i += kDecThreads) L.outputs[row * D + i] = xs[i];
+  }
+
+  // ---- postprocessor on the last layer's outputs row at len - 1 (the cached row, never written by this launch, when p < len - 1):
+  // one wave, the arithmetic of rows_normalize_kernel step for step, so that a stale row gives the prefill's result bit for bit
+  if (wave != 0) return;
+  const float* xr = p == len - 1 ? xs : a.layers[a.n_blocks - 1].outputs + (off + len - 1) * D;
+  float* o = a.out + (int64_t)b * D;
+  if (a.mode == 0) {
+    float sm = 0.0f;
+    for (int k = lane; k < D; k += 64) sm += xr[k];
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) sm += __shfl_xor(sm, s, 64);
+    const float mean = sm / (float)D;
+    float v = 0.0f;
+    for (int k = lane; k < D; k += 64) { const float c = xr[k] - mean; v = __builtin_fmaf(c, c, v); }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+    const float rstd = 1.0f / sqrtf(v / (float)D + a.eps);
+    for (int k = lane; k < D; k += 64) o[k] = (xr[k] - mean) * rstd;
+  } else {
+    float v = 0.0f;
+    for (int k = lane; k < D; k += 64) v = __builtin_fmaf(xr[k], xr[k], v);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+    const float nrm = fmaxf(sqrtf(v), a.eps);
+    for (int k = lane; k < D; k += 64) o[k] = xr[k] / nrm;
+  }
+}
+
+bool hstu_decode_supported(int N, int D, int H, int dqk, int dv, int num_buckets) {
+  if (N < 1 || D < 1 || D > kDecMaxDim || H < 1 || dqk < 1 || dqk > kDecMaxHead || dv < 1 || dv > kDecMaxHead) return false;
+  if (num_buckets < 0 || num_buckets > 255 || H > 4096) return false;
+  return hstu_decode_lds_bytes(D, H, dqk, dv, num_buckets) <= (size_t)kDecLdsBytes;
+}
+
+int hstu_decode(const float* emb, const int64_t* ids, const int64_t* positions, const int64_t* lengths, const int64_t* ts,
+                const int64_t* thresholds, const float* pos_emb, const void* layers, int n_blocks, int B, int N, int64_t cache_rows, int D,
+                int H, int dqk, int dv, int num_buckets, int act, int mode, float eps, float* out, hipStream_t stream) {
+  if (B == 0) return kOk;
+  if (!hstu_decode_supported(N, D, H, dqk, dv, num_buckets)) {
+    set_error("hstu_decode: seq_len %d, dim %d, heads %d, dqk %d, dv %d, %d buckets not supported (dim <= %d, dqk and dv <= %d, "
+              "<= 255 buckets, %d bytes of LDS)", N, D, H, dqk, dv, num_buckets, kDecMaxDim, kDecMaxHead, kDecLdsBytes);
+    return kErrUnsupported;
+  }
+  DecodeArgs a{emb, ids, positions, lengths, ts, thresholds, pos_emb, static_cast<const DecodeLayer*>(layers), n_blocks, B, N, cache_rows,
+               D, H, dqk, dv, ts ? num_buckets : 0, act, mode, eps, out};
+  const size_t lds = hstu_decode_lds_bytes(D, H, dqk, dv, a.num_buckets);
+  hipLaunchKernelGGL(hstu_decode_kernel, dim3(B), dim3(kDecThreads), lds, stream, a);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -143,6 +143,10 @@ bool hstu_fused_supported(int N, int D, int H, int dqk, int dv, int num_buckets)
 int hstu_encode_fused(const float* emb, const int64_t* ids, const int64_t* lengths, const unsigned char* buckets, const float* pos_emb,
                       const void* layers, int n_blocks, int B, int N, int D, int H, int dqk, int dv, int num_buckets, int mode,
                       float eps, float* out, hipStream_t stream);
+bool hstu_decode_supported(int N, int D, int H, int dqk, int dv, int num_buckets);
+int hstu_decode(const float* emb, const int64_t* ids, const int64_t* positions, const int64_t* lengths, const int64_t* ts,
+                const int64_t* thresholds, const float* pos_emb, const void* layers, int n_blocks, int B, int N, int64_t cache_rows, int D,
+                int H, int dqk, int dv, int num_buckets, int act, int mode, float eps, float* out, hipStream_t stream);
 // ---- SASRec query encoder, eval path (sasrec.hip) ----
 int sasrec_attention(const float* qkv, int64_t ld, int B, int N, int H, int hd, float* out, hipStream_t stream);
 bool sasrec_fused_supported(int N, int D, int H, int F);

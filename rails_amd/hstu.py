@@ -7,13 +7,18 @@ rows at positions >= length held at zero.  Every floatin
 of csrc/hstu.hip through the C ABI (rails_hstu_preprocess, rails_hstu_time_buckets, rails_rows_layer_norm, rails_gemm_f32,
 rails_hstu_attention, rails_rows_normalize); torch only holds the parameters and moves rows (embedding lookup).
 
-Not supported (raises): training mode, the cache / delta_x_offsets decoding path (hstu.py:163-186), `concat_ua`,
-`normalization="softmax_rel_bias"`, `linear_activation` other than "silu" / "none".
+Cached incremental decoding (hstu.py:144-213, :276-433, :665-803): `encode` / `generate_user_embeddings` with
+`return_cache_states=True` return the reference's per-layer states (v, padded_q, padded_k, outputs); passing them back as `cache`
+with `delta_x_offsets = (jagged_rows, positions)` re-encodes one row per sequence against the cached K / V of the others in one
+launch of rails_hstu_decode and updates the cache in place.
+
+Not supported (raises): training mode, `concat_ua`, `normalization="softmax_rel_bias"`, `linear_activation` other than
+"silu" / "none", autocast / non-fp32 caches, more than one delta row per sequence.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -21,6 +26,7 @@ from . import _lib
 from .engine import _on_device, _ptr, _stream
 
 TIMESTAMPS_KEY = "timestamps"
+CacheState = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]   # (v, padded_q, padded_k, outputs) of one layer
 
 
 def _bucket_thresholds(num_buckets: int, max_dt: int = 1 << 62) -> torch.Tensor:
@@ -214,6 +220,7 @@ class HSTU(torch.nn.Module):
                              for _ in range(num_blocks)])
         self.use_fused_kernel = True    # short sequences: the whole encoder in one launch (falls back when it does not fit)
         self._fused_ptrs = None
+        self._decode_ptrs = None
         self.register_buffer("_attn_mask", torch.triu(torch.ones((self._seq, self._seq), dtype=torch.bool), diagonal=1))
         self.register_buffer("_bucket_thresholds", _bucket_thresholds(num_buckets), persistent=False)
 
@@ -230,9 +237,20 @@ class HSTU(torch.nn.Module):
 
     def encode(self, past_lengths, past_ids, past_embeddings, past_payloads: Dict[str, torch.Tensor], delta_x_offsets=None, cache=None,
                return_cache_states: bool = False) -> torch.Tensor:
-        """(B, D): the postprocessed embedding at position past_lengths - 1 (hstu.py:741-803)."""
-        if delta_x_offsets is not None or cache is not None or return_cache_states:
-            raise NotImplementedError("the cached / incremental decoding path is not built")
+        """(B, D): the postprocessed embedding at position past_lengths - 1 (hstu.py:741-803).
+        return_cache_states=True: (current embeddings, per-layer states) -- the per-layer route runs (the fused kernel keeps its
+        intermediates in LDS).  delta_x_offsets = (jagged_rows (B,), positions (B,)) with `cache`: re-encode one row per sequence
+        (rails_hstu_decode), updating the cache in place; the result is the last layer's cached outputs row at past_lengths - 1, as
+        in the reference (a delta at an earlier position leaves it as it was).  A `cache` without delta_x_offsets is ignored."""
+        if delta_x_offsets is not None:
+            cur, states, _ = self._decode(past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache)
+            return (cur, states) if return_cache_states else cur
+        if return_cache_states:
+            states = []
+            x = self._run_layers(past_lengths, past_ids, past_embeddings, past_payloads, states=states)
+            B, N, D = x.shape
+            rows = torch.arange(B, device=x.device, dtype=torch.int64) * N + (self._lengths(past_lengths, x.device, N) - 1)
+            return self._normalize(x.view(B * N, D), rows), states
         if self.use_fused_kernel:
             out = self._encode_fused(past_lengths, past_ids, past_embeddings, past_payloads)
             if out is not None:
@@ -241,6 +259,30 @@ class HSTU(torch.nn.Module):
         B, N, D = x.shape
         rows = torch.arange(B, device=x.device, dtype=torch.int64) * N + (self._lengths(past_lengths, x.device, N) - 1)
         return self._normalize(x.view(B * N, D), rows)
+
+    def generate_user_embeddings(self, past_lengths, past_ids, past_embeddings, past_payloads: Dict[str, torch.Tensor], delta_x_offsets=None,
+                                 cache=None, return_cache_states: bool = False) -> Tuple[torch.Tensor, List[CacheState]]:
+        """(postprocessed (B, N, D), states) as hstu.py:665-703: the states list is [] unless return_cache_states.  With
+        delta_x_offsets and cache the (B, N, D) is the last layer's cached outputs (updated in place) padded and postprocessed."""
+        if delta_x_offsets is None:
+            states: Optional[list] = [] if return_cache_states else None
+            x = self._run_layers(past_lengths, past_ids, past_embeddings, past_payloads, min_len=0, states=states)
+            B, N, D = x.shape
+            return self._normalize(x.view(B * N, D), None).view(B, N, D), (states if return_cache_states else [])
+        _, states, lengths = self._decode(past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache)
+        B, N = past_ids.shape
+        D = self._embedding_dim
+        out = states[-1][3]
+        dev = out.device
+        # the jagged outputs padded to (B, N, D): rows at positions >= length are zero rows (data movement only)
+        padded = torch.zeros((B * N, D), dtype=torch.float32, device=dev)
+        pos = torch.arange(N, device=dev).unsqueeze(0)
+        valid = pos < lengths.unsqueeze(1)
+        starts = torch.cumsum(lengths, 0) - lengths
+        src = (starts.unsqueeze(1) + pos).clamp(max=max(out.shape[0] - 1, 0))
+        padded[valid.view(-1)] = out[src[valid]]
+        y = self._normalize(padded, None).view(B, N, D)
+        return y, (states if return_cache_states else [])
 
     def _encode_fused(self, past_lengths, past_ids, past_embeddings, past_payloads) -> Optional[torch.Tensor]:
         """Single-launch encoder for short sequences (rails_hstu_encode_fused): one workgroup per sequence, everything in LDS.
@@ -311,7 +353,11 @@ class HSTU(torch.nn.Module):
         lengths = lengths.to(device=dev)
         # sync-free, but not silent: out-of-range lengths are counted in a sticky device counter (HSTU.length_violations() reads it at a
         # moment of the caller's choosing -- end of an eval pass, a stats call), then clamped
-        bad = ((lengths < min_len) | (lengths > N)).sum()
+        HSTU._count_violations(dev, ((lengths < min_len) | (lengths > N)).sum())
+        return lengths.clamp(min=min_len, max=N).contiguous()
+
+    @staticmethod
+    def _count_violations(dev, bad: torch.Tensor) -> None:
         # The counter is replaced, not updated in place: a tensor created under torch.inference_mode() is an inference tensor for ever, and an
         # in-place update of it from a later no_grad / grad-mode caller raises.  (The sum below is a tensor of whichever mode the CALLER is in;
         # a value made outside inference mode takes part in inference-mode arithmetic without complaint, the other way round does not -- so the
@@ -320,7 +366,6 @@ class HSTU(torch.nn.Module):
             with torch.inference_mode(False), torch.no_grad():
                 prev = HSTU._violations.get(dev)
                 HSTU._violations[dev] = (bad.clone() if prev is None else prev + bad.clone())
-        return lengths.clamp(min=min_len, max=N).contiguous()
 
     _violations: dict = {}
 
@@ -340,7 +385,7 @@ class HSTU(torch.nn.Module):
                        "rails_rows_normalize")
         return out
 
-    def _run_layers(self, past_lengths, past_ids, past_embeddings, past_payloads, min_len: int = 1) -> torch.Tensor:
+    def _run_layers(self, past_lengths, past_ids, past_embeddings, past_payloads, min_len: int = 1, states: Optional[list] = None) -> torch.Tensor:
         if self.training:
             raise NotImplementedError("rails_amd.HSTU is eval-only: call .eval()")
         if not past_embeddings.is_cuda:
@@ -372,6 +417,10 @@ class HSTU(torch.nn.Module):
         att = torch.empty((M, H * dv), dtype=torch.float32, device=dev)
         oin = torch.empty((M, H * dv), dtype=torch.float32, device=dev)
         thr = self._bucket_thresholds.to(dev)
+        if states is not None:   # the reference's cache states: flat indices of the jagged rows (one host read of the lengths)
+            lh = lengths.cpu()
+            jag = (torch.arange(B).unsqueeze(1) * N + torch.arange(N).unsqueeze(0))[torch.arange(N).unsqueeze(0) < lh.unsqueeze(1)].to(dev)
+            HV, HQ = H * dv, H * dqk
         has_bias = ts is not None and any(l._rel_attn_bias is not None for l in self._hstu._attention_layers)
         buckets = torch.empty((B, N, N), dtype=torch.uint8, device=dev) if has_bias else None
         with _on_device(dev):
@@ -398,4 +447,116 @@ class HSTU(torch.nn.Module):
                 _lib.check(lib.rails_gemm_f32(_ptr(oin), H * dv, _ptr(f32(layer._o.weight)), 1, _ptr(f32(layer._o.bias)), _ptr(x2), D, M, D, H * dv,
                                               0, _ptr(lengths), N, _ptr(xn), D, st), "rails_gemm_f32")
                 x = xn
+                if states is not None:   # (v jagged, padded_q, padded_k, outputs jagged); mm rows past the lengths are zero
+                    states.append((mm[jag, HV: 2 * HV].contiguous(), mm[:, 2 * HV: 2 * HV + HQ].contiguous().view(B, N, HQ),
+                                   mm[:, 2 * HV + HQ: 2 * HV + 2 * HQ].contiguous().view(B, N, HQ), xn.view(M, D)[jag]))
         return x
+
+    # ---- cached incremental decoding ------------------------------------------------------------------------------
+    def _decode_rows(self, delta_x_offsets, lengths: torch.Tensor, past_lengths: torch.Tensor, dev, B: int, N: int) -> torch.Tensor:
+        """The delta positions (B,) int64 on the device.  Host-resident offsets (or STRICT_DEVICE_LENGTHS) are checked: jagged_rows[b]
+        must be x_offsets[b] + positions[b] with 0 <= positions[b] < lengths[b].  Device-resident ones are checked on the device without
+        a sync: violations are counted in length_violations() and the position is clamped into [0, length).  The kernel derives the
+        jagged row from the lengths and the position, so the caller's rows never address a write."""
+        if not isinstance(delta_x_offsets, (tuple, list)) or len(delta_x_offsets) != 2:
+            raise ValueError("delta_x_offsets must be a pair (jagged_rows (B,), positions (B,))")
+        rows_in, pos_in = (torch.as_tensor(t) for t in delta_x_offsets)
+        if rows_in.shape != (B,) or pos_in.shape != (B,) or rows_in.dtype not in (torch.int32, torch.int64) or pos_in.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"delta_x_offsets must hold two int32 / int64 tensors of shape ({B},)")
+        if not (rows_in.is_cuda and pos_in.is_cuda) or HSTU.STRICT_DEVICE_LENGTHS:
+            lh, r, p = past_lengths.to(dtype=torch.int64).cpu(), rows_in.to(dtype=torch.int64).cpu(), pos_in.to(dtype=torch.int64).cpu()
+            off = torch.cumsum(lh, 0) - lh
+            if bool(((p < 0) | (p >= lh)).any()):
+                b = int(((p < 0) | (p >= lh)).nonzero()[0])
+                raise ValueError(f"delta position {int(p[b])} of sequence {b} is outside [0, {int(lh[b])})")
+            if not torch.equal(r, off + p):
+                b = int((r != off + p).nonzero()[0])
+                raise ValueError(f"delta jagged row {int(r[b])} of sequence {b} is not x_offsets[b] + position = {int(off[b] + p[b])}")
+            return p.to(device=dev).contiguous()
+        r, p = rows_in.to(device=dev, dtype=torch.int64), pos_in.to(device=dev, dtype=torch.int64)
+        off = torch.cumsum(lengths, 0) - lengths
+        HSTU._count_violations(dev, ((p < 0) | (p >= lengths) | (r != off + p)).sum())
+        return torch.minimum(p.clamp(min=0), lengths - 1).contiguous()
+
+    def _check_cache(self, cache, B: int, N: int, dev, lengths_host: Optional[torch.Tensor]) -> int:
+        """Host-side checks of the per-layer states; returns the jagged row count they share."""
+        H, dqk, dv, D = self._num_heads, self._dqk, self._dv, self._embedding_dim
+        layers = self._hstu._attention_layers
+        if cache is None:
+            raise ValueError("delta_x_offsets needs the cache states of an earlier call (return_cache_states=True)")
+        if not isinstance(cache, (list, tuple)) or len(cache) != len(layers):
+            raise ValueError(f"cache must hold one (v, padded_q, padded_k, outputs) state per layer: {len(layers)}, "
+                             f"got {len(cache) if isinstance(cache, (list, tuple)) else type(cache).__name__}")
+        rows = None
+        for i, state in enumerate(cache):
+            if not isinstance(state, (list, tuple)) or len(state) != 4:
+                raise ValueError(f"cache[{i}] must be a 4-tuple (v, padded_q, padded_k, outputs)")
+            for name, t in zip(("v", "padded_q", "padded_k", "outputs"), state):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                    raise ValueError(f"cache[{i}] {name} must be a contiguous float32 tensor on {dev}")
+            v, q, k, out = state
+            if rows is None:
+                rows = v.shape[0] if v.dim() == 2 else -1
+            if v.shape != (rows, H * dv) or out.shape != (rows, D):
+                raise ValueError(f"cache[{i}]: v {tuple(v.shape)} / outputs {tuple(out.shape)} must be ({rows}, {H * dv}) / ({rows}, {D})")
+            for name, t in (("padded_q", q), ("padded_k", k)):
+                if t.numel() != B * N * H * dqk or t.shape[-1] != H * dqk:
+                    raise ValueError(f"cache[{i}] {name} {tuple(t.shape)} must be ({B}, {N}, {H * dqk})")
+        if lengths_host is not None and rows != int(lengths_host.sum()):
+            raise ValueError(f"the cache holds {rows} jagged rows, the lengths sum to {int(lengths_host.sum())}")
+        if rows < B:
+            raise ValueError(f"the cache holds {rows} jagged rows for {B} sequences")
+        return rows
+
+    def _decode(self, past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache):
+        """One rails_hstu_decode launch -> ((B, D) current embeddings, the cache's own states, the device lengths)."""
+        if self.training:
+            raise NotImplementedError("rails_amd.HSTU is eval-only: call .eval()")
+        if not past_embeddings.is_cuda:
+            raise RuntimeError("rails_amd.HSTU runs on the GPU only (no CPU fallback)")
+        lib = _lib.load()
+        dev = past_embeddings.device
+        B, N = past_ids.shape
+        D, H, dqk, dv = self._embedding_dim, self._num_heads, self._dqk, self._dv
+        if N != self._seq or past_embeddings.shape != (B, N, D):
+            raise ValueError(f"expected past_ids (B, {self._seq}) and past_embeddings (B, {self._seq}, {D})")
+        if not lib.rails_hstu_decode_supported(N, D, H, dqk, dv, self._num_buckets):
+            raise NotImplementedError(f"cached decoding supports dim <= 1024, dqk <= 32, dv <= 32 and <= 255 buckets within its LDS bound "
+                                      f"(got dim {D}, {H} heads, dqk {dqk}, dv {dv}, {self._num_buckets} buckets)")
+        # host-side checks of the cache's row count whenever the lengths or the offsets are on the host (the latter read the lengths anyway)
+        host_check = not past_lengths.is_cuda or HSTU.STRICT_DEVICE_LENGTHS or not (
+            isinstance(delta_x_offsets, (tuple, list)) and all(isinstance(t, torch.Tensor) and t.is_cuda for t in delta_x_offsets))
+        lengths = self._lengths(past_lengths, dev, N)
+        rows = self._check_cache(cache, B, N, dev, past_lengths.to(dtype=torch.int64).cpu() if host_check else None)
+        positions = self._decode_rows(delta_x_offsets, lengths, past_lengths, dev, B, N)
+        keep = []
+
+        def f32(t):
+            t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+            keep.append(t)
+            return t
+
+        ids = past_ids.to(device=dev, dtype=torch.int64).contiguous()
+        emb = f32(past_embeddings)
+        ts = past_payloads.get(TIMESTAMPS_KEY) if past_payloads else None
+        if ts is not None:
+            ts = ts.to(device=dev, dtype=torch.int64).contiguous()
+        table = []
+        for layer, (v, q, k, out) in zip(self._hstu._attention_layers, cache):
+            rb = layer._rel_attn_bias
+            bias = (f32(rb._ts_w).data_ptr(), f32(rb._pos_w).data_ptr()) if (rb is not None and ts is not None) else (0, 0)
+            table.append([f32(layer._uvqk).data_ptr(), f32(layer._o.weight).data_ptr(), f32(layer._o.bias).data_ptr(), *bias,
+                          v.data_ptr(), q.data_ptr(), k.data_ptr(), out.data_ptr()])
+        key = tuple(p for r in table for p in r)
+        if self._decode_ptrs is None or self._decode_ptrs[0] != key:
+            self._decode_ptrs = (key, torch.tensor(table, dtype=torch.int64).to(dev))
+        thr = self._bucket_thresholds.to(dev)
+        res = torch.empty((B, D), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _lib.check(lib.rails_hstu_decode(_ptr(emb), _ptr(ids), _ptr(positions), _ptr(lengths), _ptr(ts), _ptr(thr) if ts is not None else None,
+                                             _ptr(f32(self._input_features_preproc._pos_emb.weight)), _ptr(self._decode_ptrs[1]), len(table), B, N,
+                                             rows, D, H, dqk, dv, self._num_buckets, 1 if self._linear_activation == "silu" else 0,
+                                             0 if self._postproc == "layer_norm" else 1, C.c_float(self._eps), _ptr(res), _stream()),
+                       "rails_hstu_decode")
+        states = [(v, q.view(B, N, H * dqk), k.view(B, N, H * dqk), out) for v, q, k, out in cache]
+        return res, states, lengths
