@@ -40,9 +40,11 @@ extern "C" {
  * gained n_total / first_item, rails_mol_component_topk its out_of_range flag, rails_mol_component_topk_capacity is new);
  * 10: rails_topk_candidates_filtered, rails_rerank_topk_filtered / rails_rerank_workspace_bytes and rails_mol_coarse_topk_capacity are new;
  * 11: the SASRec encoder entries rails_sasrec_* and rails_gemm_f32_id_masked are new, rails_gemm_f32 gained act 2 (relu) / 3 (gelu);
- * 12: the HSTU cached-decoding entries rails_hstu_decode[_supported] and struct rails_hstu_decode_layer are new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
+ * 12: the HSTU cached-decoding entries rails_hstu_decode[_supported] and struct rails_hstu_decode_layer are new;
+ * 13: the SASRec cached-decoding entries rails_sasrec_decode[_supported] / rails_sasrec_decode_workspace_floats and struct
+ * rails_sasrec_decode_layer are new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
-#define RAILS_ABI_VERSION 12
+#define RAILS_ABI_VERSION 13
 int rails_abi_version(void);
 
 #define RAILS_OK 0
@@ -638,6 +640,35 @@ int rails_sasrec_encode_fused(const float* embeddings, const int64_t* ids, const
                               const rails_sasrec_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int32_t dim,
                               int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* out,
                               void* stream);
+/* Cached incremental decoding (SASRec.encode with cache=): for every sequence b, p = lengths[b] - 1 is re-encoded through all
+ * n_blocks blocks against the key / value rows 0..p-1 of each block's cache, and the block's fresh k / v row is written to cache
+ * row p in place (rows > p are neither read nor written).  Causal attention and the per-row id mask make this exact: out equals
+ * the encode of the updated sequence up to fp32 summation order.  embeddings (batch, seq_len, dim) and ids (batch, seq_len) are
+ * read at row p only; pos_emb (>= seq_len, dim); out (batch, dim) the postprocessed row p (postproc_mode / eps as
+ * rails_sasrec_encode_fused).  A length outside [1, seq_len] is clamped into it (the caller validates).  `layers`: HOST array of
+ * n_blocks rails_sasrec_decode_layer, each cache k / v a dense (batch, seq_len, dim) float32 device array holding the
+ * in-projection's key / value rows (bias included) of the block's input.  work: device scratch of
+ * rails_sasrec_decode_workspace_floats(batch, dim, ffn_dim) floats.  5 * n_blocks + 1 launches on `stream`, every output column
+ * split across workgroups.  rails_sasrec_decode_supported: seq_len <= 2048, dim and ffn_dim <= 1024,
+ * head_dim <= 64; RAILS_ENOTSUP otherwise. */
+typedef struct rails_sasrec_decode_layer {
+  const float* in_proj_weight;   /* parameters as in rails_sasrec_layer */
+  const float* in_proj_bias;
+  const float* out_proj_weight;
+  const float* out_proj_bias;
+  const float* conv1_weight;
+  const float* conv1_bias;
+  const float* conv2_weight;
+  const float* conv2_bias;
+  float* k;                      /* (batch, seq_len, dim) */
+  float* v;                      /* (batch, seq_len, dim) */
+} rails_sasrec_decode_layer;
+int rails_sasrec_decode_supported(int32_t seq_len, int32_t dim, int32_t heads, int32_t ffn_dim);
+int64_t rails_sasrec_decode_workspace_floats(int32_t batch, int32_t dim, int32_t ffn_dim);
+int rails_sasrec_decode(const float* embeddings, const int64_t* ids, const int64_t* lengths, const float* pos_emb,
+                        const rails_sasrec_decode_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int32_t dim,
+                        int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* work, float* out,
+                        void* stream);
 /* out[r] = normalise(x[row_index ? row_index[r] : r]); mode 0 LayerNorm (no affine), 1 x / max(||x||, eps).
  * output_postprocessors.py:38-85 + get_current_embeddings (modeling/sequential/utils.py:74-90). */
 int rails_rows_normalize(const float* x, int64_t ldx, const int64_t* row_index, int64_t rows, int32_t dim, int32_t mode, float eps,

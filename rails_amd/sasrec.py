@@ -10,6 +10,11 @@ rails_sasrec_encode_fused); torch only holds the parameters and moves rows (embe
 The reference's quirks are kept: the id mask (ids != 0) is the only mask -- rows past `past_lengths` with a nonzero id are valid
 rows of forward(), and a masked position is still a key of every later query (its key / value row is the in-projection bias).
 
+Cached incremental decoding (encode with `cache=`): a prefill with return_cache_states=True also returns every
+block's key / value rows; a decode step re-encodes row lengths - 1 of every sequence against them in rails_sasrec_decode (5 launches
+per block over the whole batch) and writes that row's k / v into the cache in place.  The attention is strictly causal and the id
+mask is per row, so the step equals encode() of the updated sequence up to fp32 summation order.
+
 Not supported (raises): training mode, CPU tensors.
 """
 from __future__ import annotations
@@ -121,6 +126,7 @@ class SASRec(torch.nn.Module):
         self.register_buffer("_attn_mask", torch.triu(torch.ones((self._seq, self._seq), dtype=torch.bool), diagonal=1))
         self.use_fused_kernel = True    # short sequences: the whole encoder in one launch (falls back when it does not fit)
         self._fused_ptrs = None
+        self._decode_ptrs = None        # (pointer key, ctypes rails_sasrec_decode_layer table) of the last decode step
 
     # ---- reference API ------------------------------------------------------------------------------------------
     def get_item_embeddings(self, item_ids: torch.Tensor) -> torch.Tensor:
@@ -140,15 +146,30 @@ class SASRec(torch.nn.Module):
         B, N, D = past_embeddings.shape
         return self._normalize(x, None).view(B, N, D)
 
-    def encode(self, past_lengths, past_ids, past_embeddings, past_payloads: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+    def encode(self, past_lengths, past_ids, past_embeddings, past_payloads: Optional[Dict[str, torch.Tensor]] = None, cache=None,
+               return_cache_states: bool = False):
         """(B, D): the postprocessed embedding at position past_lengths - 1 (modeling/sequential/utils.py:74-90).  Lengths follow
         HSTU's policy (HSTU._lengths): host lengths outside [1, N] raise, device lengths are clamped and counted
-        (HSTU.length_violations())."""
+        (HSTU.length_violations()).
+
+        return_cache_states=True without a cache (prefill): (emb, cache) from the per-layer route, emb bitwise that of
+        use_fused_kernel=False; cache[i] = (k, v), contiguous float32 (B, N, D): block i's in-projection key / value rows of its input.
+        With a cache (decode step): row p = past_lengths - 1 of every sequence is re-encoded through every block against cache rows
+        0..p-1 and its k / v written to cache row p in place (rows > p untouched); only past_ids / past_embeddings at row p are read.
+        Returns the (B, D) embedding of row p, or (emb, cache) with return_cache_states=True -- the same tensors, updated."""
+        if cache is not None:
+            out = self._decode(past_lengths, past_ids, past_embeddings, cache)
+            return (out, cache) if return_cache_states else out
         self._check(past_ids, past_embeddings)
         B, N = past_ids.shape
         dev = past_embeddings.device
         lengths = HSTU._lengths(past_lengths, dev, N)
         self._check_device(past_embeddings)
+        if return_cache_states:   # the per-layer route: the fused kernel keeps K / V in LDS
+            states = []
+            x = self._run_layers(past_ids, past_embeddings, states)
+            rows = torch.arange(B, device=dev, dtype=torch.int64) * N + (lengths - 1)
+            return self._normalize(x, rows), states
         if self.use_fused_kernel:
             out = self._encode_fused(lengths, past_ids, past_embeddings)
             if out is not None:
@@ -216,8 +237,9 @@ class SASRec(torch.nn.Module):
                        "rails_rows_normalize")
         return out
 
-    def _run_layers(self, past_ids, past_embeddings) -> torch.Tensor:
-        """The block stack on the (B * N, D) rows; returns the last block's output (before the postprocessor)."""
+    def _run_layers(self, past_ids, past_embeddings, states: Optional[list] = None) -> torch.Tensor:
+        """The block stack on the (B * N, D) rows; returns the last block's output (before the postprocessor).  `states`: a list
+        that receives each block's (k, v) rows as contiguous (B, N, D) copies."""
         lib = _lib.load()
         dev = past_embeddings.device
         B, N = past_ids.shape
@@ -247,6 +269,8 @@ class SASRec(torch.nn.Module):
                            "rails_gemm_f32")
                 _lib.check(lib.rails_gemm_f32(_ptr(x), D, w_in.data_ptr() + 4 * D * D, 1, b_in.data_ptr() + 4 * D, None, 0, M, 2 * D, D, 0, None, 0,
                                               qkv.data_ptr() + 4 * D, 3 * D, st), "rails_gemm_f32")
+                if states is not None:
+                    states.append((qkv[:, D:2 * D].reshape(B, N, D).contiguous(), qkv[:, 2 * D:].reshape(B, N, D).contiguous()))
                 _lib.check(lib.rails_sasrec_attention(_ptr(qkv), 3 * D, B, N, D, H, _ptr(att), st), "rails_sasrec_attention")
                 # y = Q + a W_o^T + b_o;  z = LN(y);  x = (act(z W_1^T + b_1) W_2^T + b_2 + z) * (ids != 0)
                 _lib.check(lib.rails_gemm_f32(_ptr(att), D, _ptr(w_o), 1, _ptr(b_o), _ptr(qn), D, M, D, D, 0, None, 0, _ptr(y), D, st), "rails_gemm_f32")
@@ -255,5 +279,66 @@ class SASRec(torch.nn.Module):
                 _lib.check(lib.rails_gemm_f32_id_masked(_ptr(hid), F, _ptr(w2), 1, _ptr(b2), _ptr(qn), D, M, D, F, 0, _ptr(ids), _ptr(x), D, st),
                            "rails_gemm_f32_id_masked")
         return x
+
+    # ---- cached incremental decoding ------------------------------------------------------------------------------
+    def _check_cache(self, cache, B: int, N: int, dev) -> None:
+        """Host-side checks of the per-block (k, v) states: no device read."""
+        D = self._embedding_dim
+        if not isinstance(cache, (list, tuple)) or len(cache) != self._num_blocks:
+            raise ValueError(f"cache must hold one (k, v) pair per block: {self._num_blocks}, "
+                             f"got {len(cache) if isinstance(cache, (list, tuple)) else type(cache).__name__}")
+        for i, state in enumerate(cache):
+            if not isinstance(state, (list, tuple)) or len(state) != 2:
+                raise ValueError(f"cache[{i}] must be a pair (k, v)")
+            for name, t in zip("kv", state):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                    raise ValueError(f"cache[{i}] {name} must be a contiguous float32 tensor on {dev}")
+                if t.shape != (B, N, D):
+                    raise ValueError(f"cache[{i}] {name} {tuple(t.shape)} must be ({B}, {N}, {D})")
+
+    def _decode_table(self, cache, dev):
+        """The HOST array of rails_sasrec_decode_layer (ten pointers per block), cached on the module while the parameters and the
+        cache tensors stay where they are.  Parameters that are not float32 contiguous on `dev` are converted on every call (the
+        copies are returned so that they outlive the launches)."""
+        params = []
+        for att, ff in zip(self.attention_layers, self.forward_layers):
+            c1, c2 = ff._conv1d[0], ff._conv1d[3]
+            params.append((att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias, c1.weight, c1.bias, c2.weight, c2.bias))
+        direct = all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for layer in params for t in layer)
+        keep = params if direct else self._layer_tensors(dev)
+        key = tuple(t.data_ptr() for layer in keep for t in layer) + tuple(t.data_ptr() for state in cache for t in state)
+        if not direct or self._decode_ptrs is None or self._decode_ptrs[0] != key:
+            ptrs = [p for layer, (k, v) in zip(keep, cache) for p in [t.data_ptr() for t in layer] + [k.data_ptr(), v.data_ptr()]]
+            self._decode_ptrs = (key, (C.c_void_p * len(ptrs))(*ptrs))
+        return self._decode_ptrs[1], keep
+
+    def _decode(self, past_lengths, past_ids, past_embeddings, cache) -> torch.Tensor:
+        """One decode step (rails_sasrec_decode) -> (B, D); the cache is updated in place.  With device-resident lengths nothing
+        here reads the device."""
+        self._check(past_ids, past_embeddings)
+        self._check_device(past_embeddings)
+        lib = _lib.load()
+        B, N = past_ids.shape
+        D, H, F = self._embedding_dim, self._num_heads, self._ffn_hidden_dim
+        if not lib.rails_sasrec_decode_supported(N, D, H, F):
+            raise NotImplementedError(f"cached decoding supports seq_len <= 2048, embedding_dim and ffn_hidden_dim <= 1024 and head_dim <= 64 "
+                                      f"(got seq_len {N}, embedding_dim {D}, {H} heads, ffn_hidden_dim {F})")
+        dev = past_embeddings.device
+        self._check_cache(cache, B, N, dev)
+        lengths = HSTU._lengths(past_lengths, dev, N)
+        table, keep = self._decode_table(cache, dev)
+        ids = past_ids.to(device=dev, dtype=torch.int64).contiguous()
+        emb = past_embeddings.detach().to(dtype=torch.float32).contiguous()
+        pos = self._input_features_preproc._pos_emb.weight.detach()
+        if pos.dtype != torch.float32 or not pos.is_contiguous() or pos.device != dev:
+            pos = pos.to(device=dev, dtype=torch.float32).contiguous()
+        work = torch.empty(lib.rails_sasrec_decode_workspace_floats(B, D, F), dtype=torch.float32, device=dev)
+        out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _lib.check(lib.rails_sasrec_decode(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(pos), table, self._num_blocks, B, N, D, H, F,
+                                               _ACT[self._ffn_activation_fn], 0 if self._postproc == "layer_norm" else 1, C.c_float(self._eps),
+                                               _ptr(work), _ptr(out), _stream()), "rails_sasrec_decode")
+        del keep
+        return out
 
     length_violations = staticmethod(HSTU.length_violations)
