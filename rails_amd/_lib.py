@@ -85,6 +85,38 @@ class MolWeights(C.Structure):
     ]
 
 
+# the encoders' per-layer pointer tables (rails_hstu_encode_fused, rails_hstu_decode, rails_sasrec_encode_fused, rails_sasrec_decode)
+class HstuLayer(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("uvqk", "o_w", "o_b", "ts_w", "pos_w")]
+
+
+class HstuDecodeLayer(C.Structure):
+    _fields_ = HstuLayer._fields_ + [(name, C.c_void_p) for name in ("v", "q", "k", "outputs")]
+
+
+class SasrecLayer(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("in_proj_weight", "in_proj_bias", "out_proj_weight", "out_proj_bias",
+                                                "conv1_weight", "conv1_bias", "conv2_weight", "conv2_bias")]
+
+
+class SasrecDecodeLayer(C.Structure):
+    _fields_ = SasrecLayer._fields_ + [("k", C.c_void_p), ("v", C.c_void_p)]
+
+
+def layer_table(struct, layers, device=None, cached=None):
+    """(key, table): an array of `struct`, one entry per layer, its fields the data pointers of that layer's tensors in declaration
+    order (None, or fields past the end of a row: NULL).  device None: a host ctypes array; otherwise a tensor on `device` holding
+    its bytes.  `cached`, the (key, table) of an earlier call, is returned as it is while the pointers are the same."""
+    key = tuple(tuple(0 if t is None else t.data_ptr() for t in layer) for layer in layers)
+    if cached is not None and cached[0] == key:
+        return cached
+    table = (struct * len(key))(*(struct(*ptrs) for ptrs in key))
+    if device is not None:
+        import torch
+        table = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(device)
+    return key, table
+
+
 # name -> (restype, argtypes): one entry per declaration in include/rails_amd.h
 _SHAPE_P = C.POINTER(MolShape)
 _WEIGHTS_P = C.POINTER(MolWeights)

@@ -25,18 +25,13 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "encoder_device.h"
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
 namespace mol {
 
 typedef float hf32x16 __attribute__((ext_vector_type(16)));
-
-// silu on the hardware transcendentals (v_exp_f32 = 2^x, v_rcp_f32; ~1 ulp each) instead of expf + an IEEE division (~50
-// instructions per element: the attention kernels were VALU-bound on it); the scoring kernel does the same.
-__device__ __forceinline__ float silu_fast(float v) {
-  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
-}
 
 __global__ void hstu_preprocess_kernel(const float* __restrict__ emb, const int64_t* __restrict__ ids,
                                        const int64_t* __restrict__ lengths, const float* __restrict__ pos_emb, int B, int N,
@@ -117,8 +112,8 @@ struct GemmArgs {
 // the epilogue both GEMM kernels share: act(acc + bias) + residual, then the row masks
 __device__ __forceinline__ float gemm_epilogue(const GemmArgs& g, int64_t m, int n, float v) {
   if (g.act == 1) v = silu_fast(v);
-  else if (g.act == 2) v = v > 0.0f ? v : 0.0f;
-  else if (g.act == 3) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+  else if (g.act == 2) v = relu(v);
+  else if (g.act == 3) v = gelu_erf(v);
   if (g.residual) v += g.residual[m * g.ldr + n];
   if (g.lengths) {
     const int64_t b = m / g.seq_len;
@@ -992,8 +987,7 @@ static size_t hstu_decode_lds_bytes(int D, int H, int dqk, int dv, int num_bucke
 
 // sum over the workgroup; every thread gets the total.  red: kDecWaves floats of LDS
 __device__ __forceinline__ float dec_block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "encoder_device.h"
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
@@ -51,18 +52,6 @@ struct KvDecArgs {
 __device__ __forceinline__ int dec_pos(const int64_t* lengths, int b, int N) {
   const int64_t len = lengths[b];
   return len < 1 ? 0 : len > N ? N - 1 : (int)len - 1;   // the host validates or clamps; never a row outside the cache
-}
-
-__device__ __forceinline__ float dec_act(float v, int act) {   // rails_gemm_f32's codes
-  if (act == RAILS_ACT_RELU) return v > 0.0f ? v : 0.0f;
-  return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));       // GELU (erf), as torch.nn.GELU()
-}
-
-// sum over the 64 lanes of a wave
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // C[r][col] = sum_k A[r][k] W[col][k] for the rows of a tile and one column per lane.  MODE: 0 in-projection (A = x; the q columns
@@ -208,7 +197,7 @@ __global__ __launch_bounds__(kDecThreads) void kvdec_rows_kernel(KvDecArgs a) {
     } else if (MODE == 1) {
       a.y[(int64_t)b * D + col] = v + a.qn[(int64_t)b * D + col];
     } else if (MODE == 2) {
-      a.h[(int64_t)b * a.F + col] = dec_act(v, a.act);
+      a.h[(int64_t)b * a.F + col] = ffn_act(v, a.act);
     } else {
       const float o = v + a.z[(int64_t)b * D + col];
       const int p = dec_pos(a.lengths, b, N);

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "encoder_device.h"
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
@@ -170,11 +171,6 @@ constexpr int kSasThreads = 256;   // one wave per SIMD: a lane may use the whol
 constexpr int kSasWaves = kSasThreads / 64;
 constexpr int kSasRows = 64;
 constexpr int kSasMaxDim = 128;   // D and F
-
-__device__ __forceinline__ float ffn_act(float v, int act) {   // the codes of rails_gemm_f32's act
-  if (act == RAILS_ACT_RELU) return v > 0.0f ? v : 0.0f;
-  return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));       // GELU (erf), as torch.nn.GELU()
-}
 
 // C (64 x n_cols) = A (64 x K) W^T, W a torch Linear / Conv1d(k=1) weight (n_cols, K); v_mfma_f32_32x32x2_f32, one wave per 32 x 32
 // tile.  aop(row, k) yields the A operand (k < K); epi(row, col, acc) consumes a finished element (col < n_cols).

@@ -25,9 +25,8 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
+from ._encoder import Encoder, parse_args
 from .engine import _on_device, _ptr, _stream
-from .hstu import (HSTU, L2NormEmbeddingPostprocessor, LayerNormEmbeddingPostprocessor,
-                   LearnablePositionalEmbeddingInputFeaturesPreprocessor, LocalEmbeddingModule)
 
 BLOCK_LN_EPS = 1e-8     # F.layer_norm(..., eps=1e-8) inside every block (sasrec.py:195-212)
 _ACT = {"relu": _lib.RAILS_ACT_RELU, "gelu": _lib.RAILS_ACT_GELU}
@@ -62,9 +61,14 @@ class _FeedForward(torch.nn.Module):
         )
 
 
-class SASRec(torch.nn.Module):
+class SASRec(Encoder):
     """encode(past_lengths (B,), past_ids (B, N), past_embeddings (B, N, D), past_payloads) -> (B, D);
     forward(...) -> (B, N, D).  N must equal max_sequence_len + max_output_len."""
+
+    NAME = "SASRec"
+    _SIGNATURES = ((["ffn_dropout_rate", "embedding_module", "similarity_module", "input_features_preproc_module", "output_postproc_module",
+                     "activation_checkpoint", "verbose"], dict(activation_checkpoint=False, verbose=False)),
+                   (["num_items", "similarity_module", "output_postproc", "eps"], dict(similarity_module=None, output_postproc="layer_norm", eps=1e-6)))
 
     def __init__(self, max_sequence_len: int, max_output_len: int, embedding_dim: int, num_blocks: int, num_heads: int,
                  ffn_hidden_dim: int, ffn_activation_fn: str = "relu", *args, **kwargs) -> None:
@@ -75,63 +79,18 @@ class SASRec(torch.nn.Module):
             {L2Norm,LayerNorm}EmbeddingPostprocessor (or any objects with the same attributes);
           the compact one -- ..., ffn_activation_fn="relu", num_items, similarity_module=None, output_postproc="layer_norm",
             eps=1e-6."""
-        super().__init__()
         reference_style = "embedding_module" in kwargs or (len(args) >= 2 and isinstance(args[1], torch.nn.Module))
-        if reference_style:
-            names = ["ffn_dropout_rate", "embedding_module", "similarity_module", "input_features_preproc_module",
-                     "output_postproc_module", "activation_checkpoint", "verbose"]
-            a = dict(activation_checkpoint=False, verbose=False)
-        else:
-            names = ["num_items", "similarity_module", "output_postproc", "eps"]
-            a = dict(similarity_module=None, output_postproc="layer_norm", eps=1e-6)
-        if len(args) > len(names):
-            raise TypeError(f"SASRec() takes at most {7 + len(names)} positional arguments")
-        a.update(dict(zip(names, args)))
-        for key, v in kwargs.items():
-            if key not in names:
-                raise TypeError(f"SASRec() got an unexpected keyword argument '{key}'")
-            a[key] = v
-        missing = [n for n in names if n not in a]
-        if missing:
-            raise TypeError(f"SASRec() missing required arguments: {missing}")
+        a = parse_args("SASRec", args, kwargs, reference_style, *self._SIGNATURES)
         if ffn_activation_fn not in _ACT:
             raise ValueError(f"Invalid activation_fn {ffn_activation_fn}")
-        if reference_style:
-            emb_mod, pre_mod, post_mod = a["embedding_module"], a["input_features_preproc_module"], a["output_postproc_module"]
-            if not hasattr(emb_mod, "_item_emb") or not hasattr(pre_mod, "_pos_emb"):
-                raise NotImplementedError("SASRec needs a LocalEmbeddingModule-like embedding_module (`_item_emb`) and a "
-                                          "LearnablePositionalEmbeddingInputFeaturesPreprocessor-like preprocessor (`_pos_emb`)")
-            output_postproc = getattr(post_mod, "mode", None) or {"l2": "l2_norm", "ln": "layer_norm"}.get(post_mod.debug_str())
-            eps = float(getattr(post_mod, "_eps", 1e-6))
-        else:
-            output_postproc, eps = a["output_postproc"], a["eps"]
-        if output_postproc not in ("layer_norm", "l2_norm"):
-            raise ValueError(f"Unknown output_postproc {output_postproc}")
-        self._ndp_module = a["similarity_module"]
-        self._embedding_dim = embedding_dim
-        self._seq = max_sequence_len + max_output_len
-        self._max_sequence_length = self._seq
-        self._num_blocks, self._num_heads = num_blocks, num_heads
+        seq = max_sequence_len + max_output_len
+        super().__init__(a, reference_style, seq, embedding_dim, num_blocks, num_heads)
+        self._max_sequence_length = seq
         self._ffn_hidden_dim, self._ffn_activation_fn = ffn_hidden_dim, ffn_activation_fn
-        self._postproc, self._eps = output_postproc, eps
-        if reference_style:
-            self._embedding_module, self._input_features_preproc, self._output_postproc = emb_mod, pre_mod, post_mod
-        else:
-            self._embedding_module = LocalEmbeddingModule(a["num_items"], embedding_dim)
-            self._input_features_preproc = LearnablePositionalEmbeddingInputFeaturesPreprocessor(self._seq, embedding_dim)
-            self._output_postproc = (LayerNormEmbeddingPostprocessor(embedding_dim, eps) if output_postproc == "layer_norm"
-                                     else L2NormEmbeddingPostprocessor(embedding_dim, eps))
         self.attention_layers = torch.nn.ModuleList([_MultiheadAttention(embedding_dim, num_heads) for _ in range(num_blocks)])
         self.forward_layers = torch.nn.ModuleList([_FeedForward(embedding_dim, ffn_hidden_dim, ffn_activation_fn) for _ in range(num_blocks)])
-        self.register_buffer("_attn_mask", torch.triu(torch.ones((self._seq, self._seq), dtype=torch.bool), diagonal=1))
-        self.use_fused_kernel = True    # short sequences: the whole encoder in one launch (falls back when it does not fit)
-        self._fused_ptrs = None
-        self._decode_ptrs = None        # (pointer key, ctypes rails_sasrec_decode_layer table) of the last decode step
 
     # ---- reference API ------------------------------------------------------------------------------------------
-    def get_item_embeddings(self, item_ids: torch.Tensor) -> torch.Tensor:
-        return self._embedding_module._item_emb(item_ids)       # a row gather
-
     def debug_str(self) -> str:
         return (f"SASRec-d{self._embedding_dim}-b{self._num_blocks}-h{self._num_heads}-{self._input_features_preproc.debug_str()}-"
                 f"{self._output_postproc.debug_str()}-ffn{self._ffn_hidden_dim}-{self._ffn_activation_fn}")
@@ -141,7 +100,6 @@ class SASRec(torch.nn.Module):
         """(B, N, D) postprocessed sequence embeddings (sasrec.py generate_user_embeddings).  Lengths play no part here, as in the
         reference: every position with a nonzero id is a valid row."""
         self._check(past_ids, past_embeddings)
-        self._check_device(past_embeddings)
         x = self._run_layers(past_ids, past_embeddings)
         B, N, D = past_embeddings.shape
         return self._normalize(x, None).view(B, N, D)
@@ -149,8 +107,8 @@ class SASRec(torch.nn.Module):
     def encode(self, past_lengths, past_ids, past_embeddings, past_payloads: Optional[Dict[str, torch.Tensor]] = None, cache=None,
                return_cache_states: bool = False):
         """(B, D): the postprocessed embedding at position past_lengths - 1 (modeling/sequential/utils.py:74-90).  Lengths follow
-        HSTU's policy (HSTU._lengths): host lengths outside [1, N] raise, device lengths are clamped and counted
-        (HSTU.length_violations()).
+        the encoders' policy (Encoder._lengths): host lengths outside [1, N] raise, device lengths are clamped and
+        counted (length_violations()).
 
         return_cache_states=True without a cache (prefill): (emb, cache) from the per-layer route, emb bitwise that of
         use_fused_kernel=False; cache[i] = (k, v), contiguous float32 (B, N, D): block i's in-projection key / value rows of its input.
@@ -160,48 +118,28 @@ class SASRec(torch.nn.Module):
         if cache is not None:
             out = self._decode(past_lengths, past_ids, past_embeddings, cache)
             return (out, cache) if return_cache_states else out
-        self._check(past_ids, past_embeddings)
-        B, N = past_ids.shape
-        dev = past_embeddings.device
-        lengths = HSTU._lengths(past_lengths, dev, N)
+        self._check(past_ids, past_embeddings, device=False)
+        N = past_ids.shape[1]
+        lengths = self._lengths(past_lengths, past_embeddings.device, N)
         self._check_device(past_embeddings)
         if return_cache_states:   # the per-layer route: the fused kernel keeps K / V in LDS
             states = []
             x = self._run_layers(past_ids, past_embeddings, states)
-            rows = torch.arange(B, device=dev, dtype=torch.int64) * N + (lengths - 1)
-            return self._normalize(x, rows), states
+            return self._normalize(x, self._last_rows(lengths, N)), states
         if self.use_fused_kernel:
             out = self._encode_fused(lengths, past_ids, past_embeddings)
             if out is not None:
                 return out
         x = self._run_layers(past_ids, past_embeddings)
-        rows = torch.arange(B, device=dev, dtype=torch.int64) * N + (lengths - 1)
-        return self._normalize(x, rows)
+        return self._normalize(x, self._last_rows(lengths, N))
 
     # ---- HIP path ------------------------------------------------------------------------------------------------
-    def _check(self, past_ids, past_embeddings) -> None:
-        if self.training:
-            raise NotImplementedError("rails_amd.SASRec is eval-only: call .eval()")
-        B, N = past_ids.shape
-        if N != self._seq or past_embeddings.shape != (B, N, self._embedding_dim):
-            raise ValueError(f"expected past_ids (B, {self._seq}) and past_embeddings (B, {self._seq}, {self._embedding_dim}), "
-                             f"got {tuple(past_ids.shape)} and {tuple(past_embeddings.shape)}")
-
-    @staticmethod
-    def _check_device(past_embeddings) -> None:
-        if not past_embeddings.is_cuda:
-            raise RuntimeError("rails_amd.SASRec runs on the GPU only (no CPU fallback)")
-
-    def _layer_tensors(self, dev):
-        """Per block: fp32 contiguous in_proj_weight, in_proj_bias, out_proj weight / bias, conv1 weight / bias, conv2 weight / bias
-        (Conv1d weights (out, in, 1) read as (out, in) Linear weights)."""
-        out = []
+    def _block_params(self):
+        """Per block, in rails_sasrec_layer's order: in_proj_weight, in_proj_bias, out_proj weight / bias, conv1 weight / bias, conv2
+        weight / bias (Conv1d weights (out, in, 1) read as (out, in) Linear weights)."""
         for att, ff in zip(self.attention_layers, self.forward_layers):
             c1, c2 = ff._conv1d[0], ff._conv1d[3]
-            out.append([t.detach().to(device=dev, dtype=torch.float32).contiguous()
-                        for t in (att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias,
-                                  c1.weight, c1.bias, c2.weight, c2.bias)])
-        return out
+            yield (att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias, c1.weight, c1.bias, c2.weight, c2.bias)
 
     def _encode_fused(self, lengths, past_ids, past_embeddings) -> Optional[torch.Tensor]:
         """Single-launch encoder (rails_sasrec_encode_fused).  None when the geometry does not fit (the per-layer kernels then run)."""
@@ -211,30 +149,17 @@ class SASRec(torch.nn.Module):
         if not lib.rails_sasrec_fused_supported(N, D, H, F):
             return None
         dev = past_embeddings.device
-        tensors = self._layer_tensors(dev)   # kept alive until the launch is enqueued
-        rows = [[t.data_ptr() for t in layer] for layer in tensors]
-        key = tuple(p for r in rows for p in r)
-        if self._fused_ptrs is None or self._fused_ptrs[0] != key:
-            self._fused_ptrs = (key, torch.tensor(rows, dtype=torch.int64).to(dev))
-        ltab = self._fused_ptrs[1]
+        keep = []   # copies staged to fp32 live until the launch is enqueued
+        f32 = self._f32(dev, keep)
+        self._fused_ptrs = _lib.layer_table(_lib.SasrecLayer, [[f32(t) for t in p] for p in self._block_params()], dev, self._fused_ptrs)
         ids = past_ids.to(device=dev, dtype=torch.int64).contiguous()
-        emb = past_embeddings.detach().to(dtype=torch.float32).contiguous()
-        pos = self._input_features_preproc._pos_emb.weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        emb = f32(past_embeddings)
+        pos = f32(self._input_features_preproc._pos_emb.weight)
         out = torch.empty((B, D), dtype=torch.float32, device=dev)
         with _on_device(dev):
-            _lib.check(lib.rails_sasrec_encode_fused(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(pos), _ptr(ltab), self._num_blocks, B, N, D, H, F,
-                                                     _ACT[self._ffn_activation_fn], 0 if self._postproc == "layer_norm" else 1,
-                                                     C.c_float(self._eps), _ptr(out), _stream()), "rails_sasrec_encode_fused")
-        return out
-
-    def _normalize(self, x2d: torch.Tensor, rows: Optional[torch.Tensor]) -> torch.Tensor:
-        lib = _lib.load()
-        n = x2d.shape[0] if rows is None else rows.numel()
-        out = torch.empty((n, x2d.shape[1]), dtype=torch.float32, device=x2d.device)
-        with _on_device(x2d.device):
-            _lib.check(lib.rails_rows_normalize(_ptr(x2d), x2d.stride(0), _ptr(rows) if rows is not None else None, n, x2d.shape[1],
-                                                0 if self._postproc == "layer_norm" else 1, C.c_float(self._eps), _ptr(out), _stream()),
-                       "rails_rows_normalize")
+            _lib.check(lib.rails_sasrec_encode_fused(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(pos), _ptr(self._fused_ptrs[1]), self._num_blocks,
+                                                     B, N, D, H, F, _ACT[self._ffn_activation_fn], self._postproc_mode, C.c_float(self._eps),
+                                                     _ptr(out), _stream()), "rails_sasrec_encode_fused")
         return out
 
     def _run_layers(self, past_ids, past_embeddings, states: Optional[list] = None) -> torch.Tensor:
@@ -247,10 +172,12 @@ class SASRec(torch.nn.Module):
         M = B * N
         eps = C.c_float(BLOCK_LN_EPS)
         act = _ACT[self._ffn_activation_fn]
-        layers = self._layer_tensors(dev)    # fp32 copies must outlive the launches that read them
+        keep = []   # fp32 copies must outlive the launches that read them
+        f32 = self._f32(dev, keep)
+        layers = [[f32(t) for t in p] for p in self._block_params()]
         ids = past_ids.to(device=dev, dtype=torch.int64).contiguous()
-        emb = past_embeddings.detach().to(dtype=torch.float32).contiguous()
-        pos = self._input_features_preproc._pos_emb.weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        emb = f32(past_embeddings)
+        pos = f32(self._input_features_preproc._pos_emb.weight)
         full = torch.full((B,), N, dtype=torch.int64, device=dev)   # the mask is ids != 0 alone
         x = torch.empty((M, D), dtype=torch.float32, device=dev)
         qn = torch.empty((M, D), dtype=torch.float32, device=dev)
@@ -296,27 +223,10 @@ class SASRec(torch.nn.Module):
                 if t.shape != (B, N, D):
                     raise ValueError(f"cache[{i}] {name} {tuple(t.shape)} must be ({B}, {N}, {D})")
 
-    def _decode_table(self, cache, dev):
-        """The HOST array of rails_sasrec_decode_layer (ten pointers per block), cached on the module while the parameters and the
-        cache tensors stay where they are.  Parameters that are not float32 contiguous on `dev` are converted on every call (the
-        copies are returned so that they outlive the launches)."""
-        params = []
-        for att, ff in zip(self.attention_layers, self.forward_layers):
-            c1, c2 = ff._conv1d[0], ff._conv1d[3]
-            params.append((att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias, c1.weight, c1.bias, c2.weight, c2.bias))
-        direct = all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for layer in params for t in layer)
-        keep = params if direct else self._layer_tensors(dev)
-        key = tuple(t.data_ptr() for layer in keep for t in layer) + tuple(t.data_ptr() for state in cache for t in state)
-        if not direct or self._decode_ptrs is None or self._decode_ptrs[0] != key:
-            ptrs = [p for layer, (k, v) in zip(keep, cache) for p in [t.data_ptr() for t in layer] + [k.data_ptr(), v.data_ptr()]]
-            self._decode_ptrs = (key, (C.c_void_p * len(ptrs))(*ptrs))
-        return self._decode_ptrs[1], keep
-
     def _decode(self, past_lengths, past_ids, past_embeddings, cache) -> torch.Tensor:
         """One decode step (rails_sasrec_decode) -> (B, D); the cache is updated in place.  With device-resident lengths nothing
         here reads the device."""
         self._check(past_ids, past_embeddings)
-        self._check_device(past_embeddings)
         lib = _lib.load()
         B, N = past_ids.shape
         D, H, F = self._embedding_dim, self._num_heads, self._ffn_hidden_dim
@@ -325,20 +235,18 @@ class SASRec(torch.nn.Module):
                                       f"(got seq_len {N}, embedding_dim {D}, {H} heads, ffn_hidden_dim {F})")
         dev = past_embeddings.device
         self._check_cache(cache, B, N, dev)
-        lengths = HSTU._lengths(past_lengths, dev, N)
-        table, keep = self._decode_table(cache, dev)
+        lengths = self._lengths(past_lengths, dev, N)
+        keep = []   # fp32 copies must outlive the launches that read them
+        f32 = self._f32(dev, keep)
+        self._decode_ptrs = _lib.layer_table(_lib.SasrecDecodeLayer, [[f32(t) for t in p] + [k, v] for p, (k, v) in zip(self._block_params(), cache)],
+                                             None, self._decode_ptrs)   # a HOST array
         ids = past_ids.to(device=dev, dtype=torch.int64).contiguous()
-        emb = past_embeddings.detach().to(dtype=torch.float32).contiguous()
-        pos = self._input_features_preproc._pos_emb.weight.detach()
-        if pos.dtype != torch.float32 or not pos.is_contiguous() or pos.device != dev:
-            pos = pos.to(device=dev, dtype=torch.float32).contiguous()
+        emb = f32(past_embeddings)
+        pos = f32(self._input_features_preproc._pos_emb.weight)
         work = torch.empty(lib.rails_sasrec_decode_workspace_floats(B, D, F), dtype=torch.float32, device=dev)
         out = torch.empty((B, D), dtype=torch.float32, device=dev)
         with _on_device(dev):
-            _lib.check(lib.rails_sasrec_decode(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(pos), table, self._num_blocks, B, N, D, H, F,
-                                               _ACT[self._ffn_activation_fn], 0 if self._postproc == "layer_norm" else 1, C.c_float(self._eps),
-                                               _ptr(work), _ptr(out), _stream()), "rails_sasrec_decode")
-        del keep
+            _lib.check(lib.rails_sasrec_decode(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(pos), self._decode_ptrs[1], self._num_blocks, B, N, D, H,
+                                               F, _ACT[self._ffn_activation_fn], self._postproc_mode, C.c_float(self._eps), _ptr(work), _ptr(out),
+                                               _stream()), "rails_sasrec_decode")
         return out
-
-    length_violations = staticmethod(HSTU.length_violations)

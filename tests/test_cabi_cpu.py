@@ -35,6 +35,14 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
 def test_struct_layout_matches_header(lib):
     assert C.sizeof(_lib.MolShape) == 20 * 4
     assert C.sizeof(_lib.MolWeights) == 8 * (4 + 4 + 4 + 12 + 2)  # 26 pointer-sized fields
+    # the encoders' per-layer tables: every field a pointer, named and ordered as in the header
+    header = open(os.path.join(ROOT, "include", "rails_amd.h")).read()
+    for struct, name in ((_lib.HstuLayer, "rails_hstu_layer"), (_lib.HstuDecodeLayer, "rails_hstu_decode_layer"),
+                         (_lib.SasrecLayer, "rails_sasrec_layer"), (_lib.SasrecDecodeLayer, "rails_sasrec_decode_layer")):
+        body = re.search(r"typedef struct " + name + r"\s*\{(.*?)\}\s*" + name + ";", header, re.S).group(1)
+        fields = re.findall(r"\*\s*(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+        assert [f for f, _ in struct._fields_] == fields, name
+        assert C.sizeof(struct) == 8 * len(fields), name
 
 
 def test_size_helpers_and_validation(lib):

@@ -153,6 +153,30 @@ def test_device_lengths_are_clamped_counted_and_never_read_back():
     assert R.distance(cur.cpu(), S.encoder64(f, ids=I[1], lengths=clamped)[1]) <= tolerance(f)
 
 
+def test_strict_device_lengths_is_sasrecs_own_flag(monkeypatch):
+    """SASRec.STRICT_DEVICE_LENGTHS = True makes device-resident lengths outside [1, N] raise as host lengths do, on both encode routes
+    and on a decode step, before anything is launched."""
+    from rails_amd import SASRec
+
+    f = R.load("amzn-books")
+    m = build(f, dev())
+    N = f["cfg"]["N"]
+    L, I = chain(f)
+    _, cache = prefill(m, L[1].to(dev()), I[1])
+    bad = L[1].clone()
+    bad[2] = N + 7
+    Ld, ids = bad.to(dev()), I[1].to(dev())
+    monkeypatch.setattr(SASRec, "STRICT_DEVICE_LENGTHS", True)
+    with torch.inference_mode():
+        emb = m.get_item_embeddings(ids)
+        for fused in (True, False):
+            m.use_fused_kernel = fused
+            with pytest.raises(ValueError, match="past_lengths"):
+                m.encode(Ld, ids, emb, {})
+        with pytest.raises(ValueError, match="past_lengths"):
+            m.encode(Ld, ids, emb, {}, cache=cache)
+
+
 # ----------------------------------------------------------------------------------------------------------------------------
 # shapes beyond the fixtures
 # ----------------------------------------------------------------------------------------------------------------------------
