@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: queries/sec of exact MoL top-k (BASELINE.json metric) on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, the W warm-up and K timed steps of the dense fp32 path and of the proved exact
+path (the one `value` reports when it qualifies), the output dump, the JSON line.  --full adds everything else the line can carry, each
+after the headline regions: the run without the seen-id filter, the f16x3 / f16-exact / f16x3-exact legs, the B = 1 / 8 and accuracy-protocol
+matrix, the other workloads, the weight-scale sweep, the full-shard legs, the CPU baseline, HR parity against the CPU oracle chain, the
+two-pass recall and coarse-scan roofline, and the sharded path's phase timings, pipelined rate and in-run checks.  The --no-* options
+trim a --full run.
 
 Workload (config.workload): amzn-books HSTU+MoL 8x8x32, N = 695 762 items, B = 32 queries per batch --
 the configuration BASELINE.json's target is quoted on (">=10x the reference CPU queries/sec on amzn-books
@@ -668,10 +675,13 @@ def main() -> None:
                          "was proved and the output is identical to the dense fp32 path's (else, and with 'fp32-dense', `value` = the dense fp32 kernels)")
     ap.add_argument("--pipeline", action="store_true",
                     help="N > 1: time the steps with batch i's all-gather + merge + filter overlapped with batch i+1's prologue + scoring "
-                         "(ShardedTopK.submit / result, two streams); without it the pipelined rate is still reported next to `value`")
+                         "(ShardedTopK.submit / result, two streams); without it, --full still reports the pipelined rate next to `value`")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the run, write what the path reported as `value` returned in its last timed step (top_k_ids as float64, "
                          "top_k_scores as float32) to DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every secondary measurement and check (see the module docstring); a plain run times "
+                         "the headline alone.  The --no-* options trim a --full run")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -779,7 +789,7 @@ def main() -> None:
 
     last_outputs = {}   # leg -> (top_k_ids, top_k_scores) of its last timed step, copied to the host after the timed region (--dump-outputs)
     recall_info = None
-    if two_pass and not args.no_recall:
+    if two_pass and args.full and not args.no_recall:
         # north_star: config 5 "with recall@k vs exact reported".  Untimed, BEFORE the timed module exists (one index per rank at a
         # time: a full shard's is 160 GB): the same two-pass module on planted-structure weights against exact brute force over the
         # whole (sharded) corpus -- every item scored by the fp32 kernels, exact local top-k, the same all-gather + merge.
@@ -913,7 +923,7 @@ def main() -> None:
         last_outputs["headline"] = host_copy(last_out)
 
         sharded_info = None
-        if sharded and not two_pass:
+        if sharded and not two_pass and args.full:
             # what carried the exchange, where a step's time goes (events on the launch stream, unpipelined), and the pipelined rate
             pe = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in range(args.steps)]
             for i in range(args.steps):
@@ -1006,7 +1016,7 @@ def main() -> None:
                 "pipelined": {"ms_per_step": float(tpp.item()) / args.steps * 1e3, "value": B * args.steps / float(tpp.item()), "unit": "queries/s",
                               "output_equal_to_unpipelined": equal, "headline_uses_it": bool(pipelined_headline)},
             }
-        if sharded and two_pass:
+        if sharded and two_pass and args.full:
             # the approximate mode has no unsharded twin to equal (K' per shard); what the line can carry is that every rank ends with
             # the same (ids, score bits), plus the recall measurement above
             fin_i, fin_s = step()
@@ -1020,7 +1030,7 @@ def main() -> None:
                             "exchange": "one all_gather_into_tensor of (B, 2k') int64 per batch" + (" (host-staged: test hook)" if test_backend else " on device tensors")}
         per_step_ms = [ev_step[i].elapsed_time(ev_step[i + 1]) for i in range(args.steps)]
         two_pass_pipelined = None
-        if two_pass:
+        if two_pass and args.full:
             # MoLAvgTopK.submit / result: batch i + 1 is enqueued before the host looks at batch i's verdict word (the fused scan's
             # candidate counts), so that look costs the GPU nothing; same launches, same output
             ref_out = step()
@@ -1042,7 +1052,8 @@ def main() -> None:
             two_pass_pipelined = {"ms_per_step": p_elapsed / args.steps * 1e3, "value": B * args.steps / p_elapsed, "unit": "queries/s",
                                   "output_equal_to_unpipelined": equal, "headline_uses_it": bool(pipelined_headline),
                                   "what": "two batches submitted ahead of the one whose result is taken: the host reads a batch's verdict word while the GPU runs the next ones, whose short launches run under its table scan"}
-        if two_pass:
+        score_ms = None       # two-pass: the coarse scan's own timing below is a --full measurement
+        if two_pass and args.full:
             # the dominant kernel chain of this mode is the fused coarse top-K' (HBM-bound scan of the bf16 table):
             # timed on its own, on the launch stream, after the step timing
             table = local._table()
@@ -1069,31 +1080,33 @@ def main() -> None:
                 e1.record()
                 torch.cuda.synchronize()
                 score_ms_bf16 = e0.elapsed_time(e1) / args.steps
-        else:
+        elif not two_pass:
             score_ms = sum(a.elapsed_time(b) for a, b in zip(ev0, ev1)) / args.steps
 
-        # the same step without the seen-id filter (k' = k, invalid_ids = None), timed the same way
-        # after the headline region
-        def step_nofilter():
-            out_ids, out_scores, _ = cand.get_top_k_outputs(q, k, kw, topk_mod, None)
-            return out_ids
+        nofilter_elapsed = None
+        if args.full:
+            # the same step without the seen-id filter (k' = k, invalid_ids = None), timed the same way
+            # after the headline region
+            def step_nofilter():
+                out_ids, out_scores, _ = cand.get_top_k_outputs(q, k, kw, topk_mod, None)
+                return out_ids
 
-        for _ in range(args.warmup):
-            step_nofilter()
-        if sharded:
-            dist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step_nofilter()
-        torch.cuda.synchronize()
-        if sharded:
-            dist.barrier()
-        nofilter_elapsed = time.perf_counter() - t0
-        if sharded:
-            tn = torch.tensor([nofilter_elapsed], dtype=torch.float64, device="cpu" if test_backend else dev)
-            dist.all_reduce(tn, op=dist.ReduceOp.MAX)
-            nofilter_elapsed = float(tn.item())
+            for _ in range(args.warmup):
+                step_nofilter()
+            if sharded:
+                dist.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step_nofilter()
+            torch.cuda.synchronize()
+            if sharded:
+                dist.barrier()
+            nofilter_elapsed = time.perf_counter() - t0
+            if sharded:
+                tn = torch.tensor([nofilter_elapsed], dtype=torch.float64, device="cpu" if test_backend else dev)
+                dist.all_reduce(tn, op=dist.ReduceOp.MAX)
+                nofilter_elapsed = float(tn.item())
 
         # ---- the PROVED exact path (the module's default): same step through the module API, same protocol (W warm-up steps, K timed steps
         #      between barrier + synchronize), the first-pass launch bracketed by events on its stream.  Its output must equal the dense
@@ -1165,7 +1178,7 @@ def main() -> None:
                 # N > 1: the same K steps with batch i + 1 submitted before batch i's result is taken (ShardedTopK.submit / result): the plain call
                 # waits on the host for the global verdict behind its one all-gather; with a batch in flight that wait costs the GPU nothing
                 p_pipe = None
-                if sharded and not two_pass and hasattr(topk_mod, "submit"):
+                if sharded and not two_pass and hasattr(topk_mod, "submit") and (args.full or args.pipeline):
                     pp_out = run_pipelined(2)
                     pp_equal = bool(torch.equal(pp_out[0], ref_ids) and torch.equal(pp_out[1], ref_scores))
                     pp_before = dict(mod_stats())
@@ -1213,7 +1226,7 @@ def main() -> None:
     # ---- opt-in precision mode "f16x3" (same API, same index, same 1e-4 bar), timed the same
     #      way AFTER the headline region so it cannot perturb it.  Reported separately; `value` stays the exact-fp32 path.
     fast = None
-    if not args.no_fast_path and not two_pass:
+    if args.full and not args.no_fast_path and not two_pass:
         with torch.inference_mode():
             # the exact-fp32 logits to compare with (the fused headline step does not write them)
             eng.score_dense(eng.query_pack(q, kw.get("user_ids"))[0], B, local._index, out=logits)
@@ -1269,7 +1282,7 @@ def main() -> None:
     #      fp32 kernels re-score them, the result is verified to be the fp32 path's (rails_amd/topk_modules.py _forward_rescored).
     #      Through the module API, compared bit for bit with the headline path's output, timed the same way.  Reported separately.
     exact_fast = None
-    if not args.no_fast_path and not two_pass:
+    if args.full and not args.no_fast_path and not two_pass:
         exact_fast = {}
         for mode, what in (("f16-exact", "one-product f16 scoring of the whole index (logits ~1e-2 off)"), ("f16x3-exact", "f16x3 scoring of the whole index")):
             with torch.inference_mode():
@@ -1336,7 +1349,7 @@ def main() -> None:
         elapsed = float(t.item())
     n_shard = hi - lo
     flops_alg = B * n_shard * flops_per_pair(cfg)
-    achieved = flops_alg / (score_ms * 1e-3) / 1e12
+    achieved = None if score_ms is None else flops_alg / (score_ms * 1e-3) / 1e12
 
     if rank == 0:
         traffic = None
@@ -1366,7 +1379,7 @@ def main() -> None:
                 "global_batch": B, "k": k, "k_prime": kp, "seen_id_width": width, "n_items": N,
                 "parallelism": f"item-shard x{world}" if sharded else "single GPU",
             },
-            "roofline": {
+            "roofline": None if score_ms is None else {      # (a plain two-pass run: the coarse scan is timed with --full only)
                 "kernel": "mol_score_kernel",
                 "bound": "mfma",
                 "achieved": achieved,
@@ -1442,16 +1455,19 @@ def main() -> None:
                     "peak_note": "2500 TFLOP/s dense f16 MFMA / 3 MFMAs per algorithmic product block; issued-MFMA rate = 3 x achieved",
                 }
             out["proved"] = leg
-        out["without_seen_id_filter"] = {"value": B * args.steps / nofilter_elapsed, "unit": "queries/s",
-                                         "ms_per_step": nofilter_elapsed / args.steps * 1e3, "k": k}
+        if nofilter_elapsed is not None:
+            out["without_seen_id_filter"] = {"value": B * args.steps / nofilter_elapsed, "unit": "queries/s",
+                                             "ms_per_step": nofilter_elapsed / args.steps * 1e3, "k": k}
         if two_pass:
-            gbps = coarse_table_bytes / (score_ms * 1e-3) / 1e9
             out["metric"] = "queries/sec, MoL two-pass approximate top-k over N items (get_top_k_outputs: coarse top-K' + MoL rerank + id map + seen-id filter)"
             out["config"]["workload"] = (f"{args.workload} MoL {cfg.query_dot_product_groups}x{cfg.item_dot_product_groups}x{cfg.dot_product_dimension}, "
                                          f"N={N} items, two-pass MoLAvgTopK, K'={args.two_pass} per shard")
             out["config"]["avg_top_k_per_shard"] = args.two_pass
-            out["pipelined"] = two_pass_pipelined
             out["scaling"] = "weak" if args.workload.startswith("synthetic") and not args.items else "strong"
+        if two_pass_pipelined is not None:
+            out["pipelined"] = two_pass_pipelined
+        if two_pass and score_ms is not None:     # --full: the fused coarse top-K' timed on its own
+            gbps = coarse_table_bytes / (score_ms * 1e-3) / 1e9
             out["roofline"] = {
                 "kernel": ("coarse_scan_i8_kernel (fused coarse top-K': sample pass + select pass over the int8 copy of the table, fired tiles from the bf16 table + key selection)"
                            if score_ms_bf16 is not None else "coarse_scan_kernel (fused coarse top-K': sample pass + select pass + key selection)"),
@@ -1478,35 +1494,35 @@ def main() -> None:
             out["fast_path"] = fast
         if exact_fast is not None:
             out["exact_fast_path"] = exact_fast
-        if not sharded and not two_pass and not args.no_matrix:
+        if args.full and not sharded and not two_pass and not args.no_matrix:
             # the other points of the reference's protocol on this workload -- small batches (B = 1 is the
             # HBM-bound end: one index pass per query) and the accuracy protocol (k = 2500 -> k' = 2561, no truncation)
             out["matrix"] = measurement_matrix(mol, X, ids, q, kw, inv, cfg, hi - lo, min(args.steps, 10), dev)
-        if not sharded and args.workload == "amzn-books" and not args.no_other_workloads:
+        if args.full and not sharded and args.workload == "amzn-books" and not args.no_other_workloads:
             # the two smaller real-dataset shapes of BASELINE.json (configs 1 and 2): fixed per-batch costs dominate there
             out["other_workloads"] = [quick_workload(n, B, k, kp, 10, dev, precision=pr) for n in ("ml-20m", "ml-1m") for pr in ("fp32", "proved", "f16x3", "f16-exact")]
             # BASELINE config 4 (16x16x64, 100 M items 8-way): a 400 k-item sub-range of one shard -- the kernels are linear in N
             out["other_workloads"] += [quick_workload("synthetic-16x16x64", B, k, kp, 5, dev, items=400_000, precision=pr) for pr in ("fp32", "proved", "f16x3", "f16-exact")]
-        if not sharded and not two_pass and not args.no_weights_sweep and args.precision == "proved":
+        if args.full and not sharded and not two_pass and not args.no_weights_sweep and args.precision == "proved":
             try:
                 out["weights_scale_sweep"] = weights_scale_sweep(cfg, weights, X, ids, q, kw, inv, k, kp, min(args.steps, 10), dev)
             except Exception as e:   # noqa: BLE001 -- a secondary leg must not take the headline line down with it
                 out["weights_scale_sweep"] = [{"skipped": f"{type(e).__name__}: {e}"[:300]}]
                 torch.cuda.empty_cache()
-        if not sharded and args.workload == "amzn-books" and not args.no_other_workloads and not args.no_full_shards:
+        if args.full and not sharded and args.workload == "amzn-books" and not args.no_other_workloads and not args.no_full_shards:
             try:
                 out["full_shards"] = full_shard_legs(B, k, dev)
             except Exception as e:   # noqa: BLE001 -- a secondary leg must not take the headline line down with it (e.g. a smaller device)
                 out["full_shards"] = [{"skipped": f"{type(e).__name__}: {e}"[:300]}]
                 torch.cuda.empty_cache()
         shared = None
-        if not sharded and not args.no_cpu_baseline and not two_pass:   # the CPU baseline is the exact path
+        if args.full and not sharded and not args.no_cpu_baseline and not two_pass:   # the CPU baseline is the exact path
             cb = cpu_baseline(cfg, weights, q_cpu, uid_cpu, N, min(args.cpu_sample_items or N, N), kp)
             oracle_topk = cb.pop("_oracle_topk")
             out["cpu_baseline"] = cb
             if oracle_topk is not None and kp == 200 and k == 120:
                 shared = (q_cpu, uid_cpu, N, oracle_topk)
-        if not sharded and not two_pass and not args.no_hr_parity:
+        if args.full and not sharded and not two_pass and not args.no_hr_parity:
             # the quality half of the metric + the reference's own CSV line (eval_from_checkpoint.py:507-515; BatchTimeMs = this run's step)
             hp = hr_parity_leg(cfg, weights, mol, B, 120, 200, dev, shared=shared,    # the harness's own timing-protocol constants (data/eval.py:128-130)
                                exact_mode="proved" if (proved is not None and proved["qualifies"]) else "dense")

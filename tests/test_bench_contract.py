@@ -130,9 +130,32 @@ def test_dump_outputs_writes_float_arrays_within_the_size_cap(tmp_path, monkeypa
     assert np.array_equal(runs[0]["top_k_ids.npy"].astype(np.int64), ids.numpy()[rows]) and np.array_equal(runs[0]["top_k_scores.npy"], scores.numpy()[rows])
 
 
+# what only --full measures or checks: a plain run carries none of it
+FULL_ONLY = {"without_seen_id_filter", "fast_path", "exact_fast_path", "matrix", "other_workloads", "weights_scale_sweep", "full_shards",
+             "cpu_baseline", "hr_parity", "reference_csv", "sharded", "recall", "pipelined"}
+
+
+@pytest.mark.gpu
+def test_live_plain_bench_line_is_the_headline_alone(tmp_path):
+    """A plain run (no --full): the contract fields, the proved path as `value` beside the dense fp32 one, the dump of the leg `value`
+    reports, and none of the secondary legs."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    check_line(d, expect_cpu_baseline=False)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and not (FULL_ONLY & set(d)), FULL_ONLY & set(d)
+    pr = d["proved"]
+    assert pr["is_headline"] is True and pr["output_identical_to_fp32_path"] is True and pr["proved_calls"] == pr["timed_calls"] == 3
+    assert d["value"] == pr["value"] and d["fp32_dense"]["value"] < d["value"] and d["dump_outputs"]["leg"] == "proved"
+    assert sorted(os.listdir(tmp_path / "dump")) == ["top_k_ids.npy", "top_k_scores.npy"]
+
+
 @pytest.mark.gpu
 def test_live_bench_line(tmp_path):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-fast-path", "--no-matrix",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-fast-path", "--no-matrix",
                           "--no-other-workloads", "--no-weights-sweep", "--dump-outputs", str(tmp_path / "dump")],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -166,7 +166,7 @@ def test_bench_one_rank_exchange_over_rccl():
         env.pop(v, None)
     env["RAILS_BENCH_TEST_ONE_RANK_EXCHANGE"] = "1"
     env["MASTER_PORT"] = str(_free_port())
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--no-other-workloads", "--items", "200000"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -200,7 +200,7 @@ def _bench_two_ranks(*extra):
         env.pop(v, None)
     if torch.cuda.device_count() < 2:
         env["RAILS_BENCH_TEST_BACKEND"] = "gloo"     # both ranks on GPU 0; the message is staged through the host
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--no-other-workloads", *extra], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

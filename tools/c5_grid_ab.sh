@@ -5,7 +5,7 @@ timeout 600 python tools/fuzz_fused_scans.py > $O/fuzz.txt 2>&1; tail -1 $O/fuzz
 for G in 2048 768 1024 1536 4096; do
   export RAILS_SCAN_GRID=$G
   for B in 32 128; do
-    timeout 900 python bench.py --workload synthetic-8x8x32 --two-pass 1000 --device-table --batch $B --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --steps 10 --warmup 2 > $O/g${G}_b$B.json 2> $O/g${G}_b$B.err
+    timeout 900 python bench.py --full --workload synthetic-8x8x32 --two-pass 1000 --device-table --batch $B --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --steps 10 --warmup 2 > $O/g${G}_b$B.json 2> $O/g${G}_b$B.err
     echo "grid $G B=$B $(python -c "import json,sys; print(json.load(open('$O/g${G}_b$B.json'))['ms_per_step'])")"
   done
 done

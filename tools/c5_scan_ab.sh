@@ -6,7 +6,7 @@ timeout 600 python tools/fuzz_fused_scans.py > $O/fuzz.txt 2>&1; tail -2 $O/fuzz
 for lib in default $(ls rails_amd/_ab/ 2>/dev/null); do
   [ $lib = default ] && unset RAILS_AMD_LIBRARY || export RAILS_AMD_LIBRARY=$PWD/rails_amd/_ab/$lib
   for B in 32 128; do
-    timeout 900 python bench.py --workload synthetic-8x8x32 --two-pass 1000 --device-table --batch $B --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --steps 10 --warmup 2 > $O/${lib}_b$B.json 2> $O/${lib}_b$B.err
+    timeout 900 python bench.py --full --workload synthetic-8x8x32 --two-pass 1000 --device-table --batch $B --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --steps 10 --warmup 2 > $O/${lib}_b$B.json 2> $O/${lib}_b$B.err
     echo "$lib B=$B $(python -c "import json,sys; print(json.load(open('$O/${lib}_b$B.json'))['ms_per_step'])")"
   done
 done

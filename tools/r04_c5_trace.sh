@@ -1,5 +1,5 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; O=gpurun_out/c5trace; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python bench.py --workload synthetic-8x8x32 --two-pass 1000 --device-table --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --no-recall --steps 20 --warmup 3 > $O/out.json 2> $O/err.txt
+rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python bench.py --full --workload synthetic-8x8x32 --two-pass 1000 --device-table --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --no-recall --steps 20 --warmup 3 > $O/out.json 2> $O/err.txt
 python - <<'PY'
 import csv,glob
 f=glob.glob('gpurun_out/c5trace/*kernel_trace.csv')+glob.glob('gpurun_out/c5trace/*/*kernel_trace.csv')

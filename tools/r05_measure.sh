@@ -3,9 +3,9 @@
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r05_${1:-final}; mkdir -p $O
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 # the headline step alone under rocprofv3 (every launch of the proved step at B = 32)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_headline -o r05 -- python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --no-hr-parity > $O/bench_headline_under_profiler.json 2> $O/prof_headline.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_headline -o r05 -- python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --no-hr-parity > $O/bench_headline_under_profiler.json 2> $O/prof_headline.err
 f=$(find $O/prof_headline -name '*kernel_stats.csv' | head -1); cp "$f" $O/kernel_stats_headline.csv; python tools/kernel_stats_top.py "$f" 24 > $O/kernel_stats_headline_top.txt; rm -rf $O/prof_headline
 # HBM traffic and SQ counters of the first-pass kernel (f16x3), separate --pmc passes
 bash tools/pmc_traffic.sh $O/pmc_traffic_f16x3 --workload amzn-books --batch 32 --precision f16x3 > $O/pmc_traffic_f16x3_summary.txt 2>&1

@@ -21,7 +21,7 @@ for n in ("_absorb_state", "_proved_eps", "_bound_from_weights", "_proved_applie
     wrap(rails_amd.MoLBruteForceTopK, n)
 wrap(MM.MoLSimilarity, "engine")
 wrap(rails_amd.CandidateIndex, "get_top_k_outputs", 4e-3)
-sys.argv = ["bench.py", "--steps", "10", "--warmup", "3", "--no-other-workloads", "--no-cpu-baseline", "--no-hr-parity"]
+sys.argv = ["bench.py", "--full", "--steps", "10", "--warmup", "3", "--no-other-workloads", "--no-cpu-baseline", "--no-hr-parity"]
 try:
     bench.main()
 finally:

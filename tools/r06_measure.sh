@@ -3,9 +3,9 @@
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r06_${1:-final}; mkdir -p $O
-( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/bench_wall.txt; echo "bench rc=$?"; tail -3 $O/bench_wall.txt
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/bench_wall.txt; echo "bench rc=$?"; tail -3 $O/bench_wall.txt
 # the headline step alone under rocprofv3 (every launch of the proved step at B = 32)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_headline -o r06 -- python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --no-hr-parity --no-weights-sweep > $O/bench_headline_under_profiler.json 2> $O/prof_headline.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_headline -o r06 -- python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-matrix --no-other-workloads --no-fast-path --no-hr-parity --no-weights-sweep > $O/bench_headline_under_profiler.json 2> $O/prof_headline.err
 f=$(find $O/prof_headline -name '*kernel_stats.csv' | head -1); cp "$f" $O/kernel_stats_headline.csv; python tools/kernel_stats_top.py "$f" 24 > $O/kernel_stats_headline_top.txt; rm -rf $O/prof_headline
 # timelines of the proved step (launch order, kernel time incl. its dispatch gap): C3, B = 8, C2 (ML-20M), an R = 8 shard
 cd /tmp
@@ -25,5 +25,5 @@ rm -rf $O/tl_c3 $O/tl_b8 $O/tl_c2 $O/tl_r8
   for R in 8 4 2; do python tools/shard_step_profile.py --world $R --precision proved-global; python tools/shard_step_profile.py --world $R --precision proved-global --pipeline; python tools/shard_step_profile.py --world $R; done; } 2>&1 | grep -v amdgpu | cut -c1-220 > $O/step_times.txt
 python tools/algorithms_bench.py --workload amzn-books > $O/algorithms_amzn_books.json 2> /dev/null
 # the sharded path of bench.py in a process group of ONE rank over backend nccl (RCCL's all-gather / all-reduce / barrier on device tensors, exchange stream, merge + global verdict)
-RAILS_BENCH_TEST_ONE_RANK_EXCHANGE=1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-workloads --no-matrix --no-hr-parity --no-weights-sweep > $O/bench_one_rank_rccl.json 2> $O/bench_one_rank_rccl.err; echo "one-rank rccl bench rc=$?"
+RAILS_BENCH_TEST_ONE_RANK_EXCHANGE=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-workloads --no-matrix --no-hr-parity --no-weights-sweep > $O/bench_one_rank_rccl.json 2> $O/bench_one_rank_rccl.err; echo "one-rank rccl bench rc=$?"
 ( time timeout 1500 python -m pytest tests -m gpu -q ) > $O/gpu_tests.txt 2>&1; echo "gpu tests rc=$?"; tail -5 $O/gpu_tests.txt
