@@ -10,7 +10,7 @@ import os
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# RAILS_AMD_LIBRARY: load another build of the same library (e.g. the phase-stamp debug build of tools/query_phases.sh)
+# RAILS_AMD_LIBRARY: load another build of the same library (e.g. the parent commit's, for an A/B run in one place)
 LIB_PATH = os.environ.get("RAILS_AMD_LIBRARY") or os.path.join(_HERE, "librails_amd.so")
 
 RAILS_ABI_VERSION = 13  # include/rails_amd.h

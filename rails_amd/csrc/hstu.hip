@@ -546,13 +546,6 @@ __global__ __launch_bounds__(256) void hstu_attention_wg_kernel(AttnArgs a) {
 // 16 waves: phase work is dealt tile-wise (t = wave, wave + 16, ...).  LDS rows use odd strides (conflict-free column
 // walks).  Same arithmetic as the multi-kernel kernels except the K order inside the GEMMs (pairs 2s, 2s+1).
 // ---------------------------------------------------------------------------------------------
-#ifdef RAILS_HSTU_PHASES   // tools/hstu_phases.sh: wall-clock stamps (100 MHz) of sequence 0, block 1
-__device__ long long g_hphase[8];
-#define RAILS_HPHASE(i) do { if (blockIdx.x == 0 && threadIdx.x == 0 && blk == 1) g_hphase[i] = (long long)wall_clock64(); } while (0)
-#else
-#define RAILS_HPHASE(i)
-#endif
-
 struct FusedLayer { const float* uvqk; const float* o_w; const float* o_b; const float* ts_w; const float* pos_w; };
 
 struct FusedArgs {
@@ -627,11 +620,9 @@ __global__ __launch_bounds__(kFusedThreads) void hstu_fused_kernel(FusedArgs a) 
       for (int i = tid; i < 2 * N - 1; i += kFusedThreads) pos_s[i] = L.pos_w[i];
       for (int i = tid; i <= a.num_buckets; i += kFusedThreads) tsw_s[i] = L.ts_w[i];
     }
-    RAILS_HPHASE(0);
     // ---- LN1: A[row][:D] = layer_norm(X[row])
     fused_layer_norm_rows(X, XS, A, AS, nullptr, 0, D, a.eps, wave, lane);
     __syncthreads();
-    RAILS_HPHASE(1);
     // ---- GEMM uvqk: Y = silu(A[:, :D] Wuvqk), rows >= len zero
     for (int t = wave; t < 2 * (W / 32); t += kFusedWaves) {
       const int mt = t / (W / 32), nt = t - mt * (W / 32);
@@ -655,7 +646,6 @@ __global__ __launch_bounds__(kFusedThreads) void hstu_fused_kernel(FusedArgs a) 
       }
     }
     __syncthreads();
-    RAILS_HPHASE(2);
     // ---- attention: A[i][head*dv + d] = sum_{j <= i} silu(q_i . k_j + bias) / N * v_j
     for (int t = wave; t < 2 * H; t += kFusedWaves) {
       const int head = t % H, qt = t / H;
@@ -695,11 +685,9 @@ __global__ __launch_bounds__(kFusedThreads) void hstu_fused_kernel(FusedArgs a) 
       }
     }
     __syncthreads();
-    RAILS_HPHASE(3);
     // ---- LN2 * u: A[row][:HV] = layer_norm(A[row][:HV]) * Y[row][:HV]
     fused_layer_norm_rows(A, AS, A, AS, Y, YS, HV, a.eps, wave, lane);
     __syncthreads();
-    RAILS_HPHASE(4);
     // ---- GEMM o: X = A[:, :HV] Wo^T + bo + X, rows >= len zero
     for (int t = wave; t < 2 * (D / 32); t += kFusedWaves) {
       const int mt = t / (D / 32), nt = t - mt * (D / 32);
@@ -724,7 +712,6 @@ __global__ __launch_bounds__(kFusedThreads) void hstu_fused_kernel(FusedArgs a) 
       }
     }
     __syncthreads();
-    RAILS_HPHASE(5);
   }
   // ---- postprocessor on row len - 1
   if (wave == 0) {
@@ -1259,11 +1246,4 @@ int hstu_decode(const float* emb, const int64_t* ids, const int64_t* positions, 
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
-#ifdef RAILS_HSTU_PHASES
-}  // namespace mol
-extern "C" int rails_debug_hstu_phases(long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(mol::g_hphase), sizeof(long long) * 8) == hipSuccess ? 0 : -1;
-}
-namespace mol {
-#endif
 }  // namespace mol

@@ -66,18 +66,11 @@ constexpr int kScanThreads = 256;
 constexpr int kSampleMaxQT = 4;       // query tiles (of 32) a sample launch keeps running maxima for: B <= 128
 constexpr int kSelectMaxRows = 512;   // query rows of a select launch (its workgroup flush keeps a counter per row in LDS)
 constexpr int kSampleGrid = 256;      // workgroups of a sample launch: 1 024 waves -> 32 768 maxima per query, one row_select launch
-#ifndef RAILS_SCAN_NT
-#define RAILS_SCAN_NT 1   // the select scan of a single query tile (B <= 32) reads the table with non-temporal loads -- each byte is used once:
-                          // 125 M x 32 bf16, B = 32: 1 388 -> 1 315 us (5.8 -> 6.1 TB/s); with four query tiles (B = 128) the scan is no longer
-                          // bound by the reads and the hint costs 1.5 %, so those launches keep the default policy
-#endif
-#ifndef RAILS_SCAN_WAVES
-#define RAILS_SCAN_WAVES 3   // waves per SIMD the select scan is compiled for (168 VGPRs; 3 over 2: 3.07 -> 2.87 ms per config-5 step at B = 128,
-                           // nothing at B = 32); the store modes hold sixteen addresses per tile and keep 2
-#endif
-#ifndef RAILS_SCAN_TU
-#define RAILS_SCAN_TU 0   // item tiles per trip of the scan (0: by d)
-#endif
+// The select scan of a single query tile (B <= 32) reads the table with non-temporal loads -- each byte is used once: 125 M x 32 bf16,
+// B = 32: 1 388 -> 1 315 us (5.8 -> 6.1 TB/s); with four query tiles (B = 128) the scan is no longer bound by the reads and the hint
+// costs 1.5 %, so those launches keep the default policy.
+constexpr int kScanWaves = 3;   // waves per SIMD the select scan is compiled for (168 VGPRs; 3 over 2: 3.07 -> 2.87 ms per config-5 step at B = 128,
+                                // nothing at B = 32); the store modes hold sixteen addresses per tile and keep 2
 
 struct CoarseScanArgs {
   const float* eq; int B, PQ, d, avg;
@@ -87,7 +80,6 @@ struct CoarseScanArgs {
   // candidate lists -- is q * groups + m.  groups = 1, comp = 0: the coarse pass of MoLAvgTopK.
   int groups, comp; int64_t group_stride;
   int stage_cap;                        // kScanSelect: entries of the workgroup's LDS list of hits (set by launch_coarse_scan)
-  int no_hits;                          // RAILS_COMP_DEBUG=1 (measurement): the select scan with every threshold at +inf -- its cost without candidates
   const unsigned short* qfrag;          // the queries' A fragments, made once by workgroup 0 of the sample scan (NULL: every workgroup makes them from eq)
   const unsigned short* table; int64_t n;
   float* scores; int64_t ld;            // kScanAll: scores[b * ld + item]
@@ -122,7 +114,7 @@ constexpr int kStage = 128;   // entries per wave (2 KiB)
 __device__ __forceinline__ void append_candidate(unsigned long long* keys, unsigned int* counts, int cap, int sub,
                                                  unsigned int orow, unsigned long long key) {
   const int subcap = cap / kSubLists;
-  const unsigned int slot = counts ? atomicAdd(&counts[(int64_t)orow * kSubLists + sub], 1u) : 0u;   // (counts == NULL: RAILS_COMP_DEBUG=2, a measurement of the path without its atomics)
+  const unsigned int slot = atomicAdd(&counts[(int64_t)orow * kSubLists + sub], 1u);
   if (slot < (unsigned int)subcap) keys[(int64_t)orow * cap + sub * subcap + slot] = key;
 }
 __device__ __forceinline__ void stage_push(volatile StageEntry* st, unsigned int* cnt, unsigned long long* keys,
@@ -151,27 +143,6 @@ __device__ __forceinline__ void stage_flush_mixed(volatile StageEntry* st, volat
   if (lane == 0) *cnt = 0u;
 }
 
-// The same staging with the wave's fill count in a scalar register (component scans, round 6: a hit every few blocks): no LDS atomic and no
-// LDS read on the way -- slots from a ballot's prefix count, the entries written and forgotten; the flush reads them back (DS operations of a
-// wave execute in issue order).  `sel` lanes append (key, orow, sub).
-__device__ __forceinline__ void stage_push_reg(volatile StageEntry* st, unsigned int& staged, bool sel, unsigned long long key, unsigned int orow, int sub,
-                                               unsigned long long* keys, unsigned int* counts, int cap, int lane) {
-  const unsigned long long m = __ballot(sel);
-  if (m == 0ull) return;
-  const unsigned int slot = staged + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
-  if (sel) {
-    if (slot < (unsigned int)kStage) { st[slot].key = key; st[slot].orow = orow; st[slot].pad = (unsigned int)sub; }
-    else append_candidate(keys, counts, cap, sub, orow, key);      // list full: straight to global
-  }
-  staged += (unsigned int)__popcll(m);
-}
-__device__ __forceinline__ void stage_flush_reg(volatile StageEntry* st, unsigned int& staged, int lane, unsigned long long* keys, unsigned int* counts, int cap,
-                                                unsigned int at_least) {
-  if (staged < at_least || staged == 0u) return;      // wave-uniform
-  const unsigned int n = staged < (unsigned int)kStage ? staged : (unsigned int)kStage;
-  for (unsigned int e = lane; e < n; e += 64) append_candidate(keys, counts, cap, (int)st[e].pad, st[e].orow, st[e].key);
-  staged = 0u;
-}
 
 // Pre-test of the select scan: the accumulator STARTS at minus the pre-test bound of its (query row, register), so "some score of
 // this lane reaches its bound" is "some accumulator has a clear sign bit" -- an unsigned minimum over the sixteen registers (seven
@@ -223,8 +194,8 @@ __device__ __forceinline__ void component_query_element(const float* __restrict_
 }
 __device__ __forceinline__ void quantise_query(const unsigned short* qfrag, int DC, int d, int q, signed char* q8, float* qmeta);   // int8 pre-filter, below
 
-template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>   // DC = d / 16 K chunks; NT: non-temporal table loads; QTS: query tiles a sample launch keeps maxima for; COMP: the component scans' select / sample blocks
-__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu((MODE == kScanSelect && !COMP) ? RAILS_SCAN_WAVES : 2, (MODE == kScanSelect && !COMP) ? RAILS_SCAN_WAVES : 2))) void coarse_scan_kernel(CoarseScanArgs a) {
+template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>   // DC = d / 16 K chunks; NT: non-temporal table loads; QTS: query tiles a sample launch keeps maxima for; COMP: the component scans' sample block
+__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MODE == kScanSelect ? kScanWaves : 2, MODE == kScanSelect ? kScanWaves : 2))) void coarse_scan_kernel(CoarseScanArgs a) {
   MOL_RUN_IF(a.run_if);
   extern __shared__ __attribute__((aligned(16))) unsigned short qfrag[];   // [n_qt][DC][64 lanes][8] bf16, then thr
   const int d = a.d, B = a.comp ? a.B * a.PQ : a.B;      // B: query ROWS from here on
@@ -232,12 +203,11 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu((M
   const unsigned short* const table = a.table + (int64_t)gm * a.group_stride;
   const int n_qt = (B + 31) / 32;
   float* thr_s = reinterpret_cast<float*>(qfrag + (size_t)n_qt * DC * 64 * 8);   // [n_qt * 32]
-  __shared__ StageEntry stage_s[COMP ? kScanThreads / 64 : 1][COMP ? kStage : 1];      // (the per-wave lists of the COMP select block)
   __shared__ unsigned int stage_n[kScanThreads / 64];
   __shared__ float acc_s[MODE == kScanSelect ? (kScanThreads / 64) * 16 * 64 : 1];   // a fired tile's scores, per wave
   // The select scan's appends (round 6).  A hit used to take its slot from a device-scope atomic on counts[row][tile % 16]: with few query
   // rows (MoLAvgTopK: 32 rows = 512 counters) the ~500 k appends of K' = 4 000 queue up on the same addresses -- 257 us of a scan that takes 46
-  // without the atomics and 10 without candidates (tools/r06_probe_t.sh).  Now a workgroup keeps ALL its hits in one LDS list (wg_stage, LDS
+  // without the atomics and 10 without candidates (round-6 measurement builds).  Now a workgroup keeps ALL its hits in one LDS list (wg_stage, LDS
   // cursor; a.stage_cap entries behind the thresholds in dynamic LDS: 1 024 where that leaves three workgroups per CU, else 512) and flushes
   // once, at its end: the entries of a row are counted (LDS), ONE device-scope atomic per (row, workgroup) reserves their slots in sub-list
   // blockIdx.x % 16, and the keys go out.  Entries beyond the list take their slots one by one as before.
@@ -259,7 +229,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu((M
   float* ntlo_s = thr_s + n_qt * 32;                                              // [n_qt * 32]: minus the pre-test bound
   if constexpr (MODE == kScanSelect)
     for (int i = threadIdx.x; i < n_qt * 32; i += kScanThreads) {
-      const float thr = (i < B && !a.no_hits) ? a.thr[((int64_t)i * groups + gm) * a.thr_stride] : INFINITY;
+      const float thr = i < B ? a.thr[((int64_t)i * groups + gm) * a.thr_stride] : INFINITY;
       thr_s[i] = thr;
       ntlo_s[i] = -coarse_unorderable(coarse_orderable(thr) - 0x10000u);
     }
@@ -286,7 +256,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu((M
   // the next trip are issued before the current one is scored, so a wave always has a trip of table bytes in flight (with one
   // trip per wave and two waves per SIMD only 4 MB of the chip's reads were outstanding: 4.6 TB/s by Little's law).
   constexpr int TU = (MODE == kScanSample && QTS > kSampleMaxQT) ? (DC <= 2 ? 2 : 1)      // eight row tiles of running maxima are 128 registers: shorter trips
-                     : (MODE == kScanSelect && RAILS_SCAN_TU > 0) ? RAILS_SCAN_TU : (MODE == kScanAll ? (DC <= 4 ? 2 : 1) : (DC <= 2 ? 4 : (DC <= 4 ? 2 : 1)));   // the score stores of kScanAll hold 16 addresses per tile
+                     : (MODE == kScanAll ? (DC <= 4 ? 2 : 1) : (DC <= 2 ? 4 : (DC <= 4 ? 2 : 1)));   // the score stores of kScanAll hold 16 addresses per tile
   struct Trip {
     bf16x8 Bv[TU][DC];
     int64_t item[TU];
@@ -388,7 +358,6 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu((M
 #pragma unroll
       for (int r = 0; r < 16; ++r) mx[qt][r] = -INFINITY;
   }
-  unsigned int staged = 0u;      // COMP select: entries in this wave's stage (wave-uniform)
   auto score_trip = [&](int64_t w0, const Trip& T) {
     if constexpr (MODE == kScanSample) {
 #pragma unroll
@@ -427,46 +396,6 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu((M
 #pragma unroll
               for (int r = 0; r < 16; ++r) mx[qt][r] = fmaxf(mx[qt][r], acc[r] + pen);
             }
-          }
-        }
-      }
-      return;
-    }
-    if constexpr (COMP && MODE == kScanSelect) {
-      // Component scans: 256 query rows (eight row tiles walk over every trip) and a candidate in every fifth to fifteenth block.
-      unsigned long long in_m[TU];      // lanes whose item of tile u is inside the corpus (all of them but on a ragged last tile)
-#pragma unroll
-      for (int u = 0; u < TU; ++u) in_m[u] = __ballot(T.in[u]);
-      for (int qt = 0; qt < n_qt; ++qt) {
-        if (n_qt > 1) load_query_tile(qt, A, ntlo);
-#pragma unroll
-        for (int u = 0; u < TU; ++u) {
-          // pre-test as in the coarse scan (accumulator started at minus the bound, one sign test over the sixteen registers: 9 VALU
-          // instructions per block; sixteen compares into scalar masks measured 2.2 x the whole scan's time) ...
-          cf32x16 pre = ntlo;
-#pragma unroll
-          for (int c = 0; c < DC; ++c) pre = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[c], T.Bv[u][c], pre, 0, 0, 0);
-          if (__any(any_sign_clear(pre))) {
-            // ... and a block that fires (one in five to fifteen here, where the coarse scan's fire once in a hundred) is scored again from
-            // zero -- the materialising path's bits -- and walked register by register through the compares' scalar lane masks: no trip
-            // through LDS to index a register, no LDS counter, no second look at the thresholds
-            cf32x16 acc = {0};
-#pragma unroll
-            for (int c = 0; c < DC; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[c], T.Bv[u][c], acc, 0, 0, 0);
-            const int64_t t = (w0 + u) * step;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const unsigned long long mk = __builtin_amdgcn_fcmpf(acc[r], -ntlo[r], 3 /* oge */) & in_m[u];
-              if (mk != 0ull) {      // scalar
-                const float sc = bf16_rn(acc[r]);     // an un-rounded sum at or above the bound may round up to the threshold
-                const float thr = coarse_unorderable(coarse_orderable(-ntlo[r]) + 0x10000u);
-                const int q = qt * 32 + acc_row(r, h);
-                const bool keep = T.in[u] && acc[r] >= -ntlo[r] && sc >= thr && q < B;
-                stage_push_reg(stage_s[wave], staged, keep, ((unsigned long long)coarse_orderable(sc) << 32) | (unsigned int)(~(unsigned int)T.item[u]),
-                               (unsigned int)(q * groups + gm), (int)(t % kSubLists), a.keys, a.counts, a.cap, lane);
-              }
-            }
-            stage_flush_reg(stage_s[wave], staged, lane, a.keys, a.counts, a.cap, 64u);
           }
         }
       }
@@ -519,8 +448,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu((M
     w0 = w1;
   }
   }
-  if constexpr (MODE == kScanSelect && COMP) stage_flush_reg(stage_s[wave], staged, lane, a.keys, a.counts, a.cap, 1u);
-  else if constexpr (MODE == kScanSelect) {
+  if constexpr (MODE == kScanSelect) {
     __syncthreads();                                   // every wave is through its tiles: the list is complete
     const unsigned int n_st = wg_n < (unsigned int)kWgStage ? wg_n : (unsigned int)kWgStage;
     if (n_st > 0u) {                                   // workgroup-uniform
@@ -532,7 +460,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu((M
       __syncthreads();
       for (int r = threadIdx.x; r < rows_wg; r += kScanThreads) {
         const unsigned int c = row_cnt_s[r];
-        if (c) row_base_s[r] = a.counts ? atomicAdd(&a.counts[((int64_t)r * groups + gm) * kSubLists + sub], c) : 0u;   // (counts == NULL: RAILS_COMP_DEBUG=2)
+        if (c) row_base_s[r] = atomicAdd(&a.counts[((int64_t)r * groups + gm) * kSubLists + sub], c);
       }
       __syncthreads();
       for (unsigned int e = threadIdx.x; e < n_st; e += kScanThreads) {
@@ -575,8 +503,8 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
   const int64_t n_work = (n_tiles + step - 1) / step;
   constexpr int tu = MODE != kScanSelect ? 2 : 4;   // tiles per trip at d = 32 (fewer at larger d: then some waves get no trip)
   int64_t grid = (n_work + 4 * tu - 1) / (4 * tu);
-  static const int64_t grid_cap = [] { const char* e = getenv("RAILS_SCAN_GRID"); const int64_t v = e ? atoll(e) : 0; return v > 0 ? v : (int64_t)2048; }();
-  const int64_t cap_g = (grid_cap + groups - 1) / groups;   // 2048 workgroups over all groups: 8 workgroups of 4 waves per CU
+  constexpr int64_t kGridCap = 2048;
+  const int64_t cap_g = (kGridCap + groups - 1) / groups;   // 2048 workgroups over all groups: 8 workgroups of 4 waves per CU
   if (grid > cap_g) grid = cap_g;
   const bool wide = a.comp && n_qt > kSampleMaxQT;
   if (MODE == kScanSelect && n_qt * 32 > kSelectMaxRows) { set_error("coarse select scan: %d query rows exceed %d", rows, kSelectMaxRows); return kErrUnsupported; }
@@ -614,20 +542,9 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
         }
       }
     }
-    if constexpr (MODE == kScanSelect) {
-      // RAILS_COMP_SELECT=1 (measurement): the select block that walks a fired block's registers by the compares' scalar masks.  Measured at
-      // amzn-books, B = 32, k_g = 5, stride 4: 198 us (116 without candidates, at two waves per SIMD) against 162 (96) for the coarse scan's
-      // own block at three waves -- the default
-      static const bool comp_block = [] { const char* e = getenv("RAILS_COMP_SELECT"); return e && atoi(e) == 1; }();
-      if (a.comp && comp_block) {
-        switch (dc) {
-          case 2: return fire(&coarse_scan_kernel<2, MODE, NT, kSampleMaxQT, true>);
-          case 4: return fire(&coarse_scan_kernel<4, MODE, NT, kSampleMaxQT, true>);
-          case 8: return fire(&coarse_scan_kernel<8, MODE, NT, kSampleMaxQT, true>);
-          default: return false;
-        }
-      }
-    }
+    // (The component scans select with the coarse scan's own block.  A block of their own that walked a fired block's registers by the
+    // compares' scalar masks measured slower at amzn-books, B = 32, k_g = 5, stride 4: 198 us (116 without candidates, at two waves per
+    // SIMD) against 162 (96) at three waves.)
     switch (dc) {
       case 2: return fire(&coarse_scan_kernel<2, MODE, NT>);
       case 4: return fire(&coarse_scan_kernel<4, MODE, NT>);
@@ -636,7 +553,7 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
     }
   };
   bool known;
-  if constexpr (MODE == kScanSelect && RAILS_SCAN_NT != 0) known = n_qt == 1 ? go(std::true_type{}) : go(std::false_type{});
+  if constexpr (MODE == kScanSelect) known = n_qt == 1 ? go(std::true_type{}) : go(std::false_type{});
   else known = go(std::false_type{});
   if (!known) { set_error("coarse scan: d = %d (supported: 32, 64, 128)", a.d); return kErrUnsupported; }
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
@@ -677,9 +594,6 @@ struct CoarseTopkPlan { int stride, r, cap; bool sample16; int64_t n_sample; siz
 
 static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
-#ifndef RAILS_SAMPLE16
-#define RAILS_SAMPLE16 1   // 0: fp32 threshold samples (measurement)
-#endif
 // group_max: the sample is the coarse scan's block of per-wave running maxima (kScanSample above) instead of every sampled score
 // comp_rows > 0: the plan of the component scans (B = all B * P_Q * P_X rows; comp_rows = the B * P_Q query rows of one item group): a denser
 // sample (the threshold's Poisson noise sets how many candidates the select scan appends: ~k + 6 sqrt(k stride) per row, and the appends are
@@ -697,8 +611,7 @@ static bool coarse_topk_plan(int B, int64_t n, int k_prime, CoarseTopkPlan* p, b
   if (stride < 64) stride = 64;
   if (stride > 256) stride = 256;
   if (comp_rows > 0) {
-    static const int forced = [] { const char* e = getenv("RAILS_COMP_STRIDE"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 256 ? v : 0; }();   // measurement override
-    stride = forced ? forced : 4;      // sample + select scan at amzn-books, B = 32, k_g = 5 (round-6 kernels before the COMP select block): 16 -> 42 + 228 us, 4 -> 81 + 162, 1 -> 237 + 136
+    stride = 4;      // sample + select scan at amzn-books, B = 32, k_g = 5 (round-6 kernels): 16 -> 42 + 228 us, 4 -> 81 + 162, 1 -> 237 + 136
   }
   // Corpora of a few million items (round 6): the sample is cheap there (a 64 k-item sample of a 45 MB table is microseconds), and what the
   // step pays for is every candidate beyond K' -- appended by the scan, loaded and ranked by the key selection.  m = 64 expected hits and the
@@ -761,7 +674,7 @@ static bool coarse_topk_plan(int B, int64_t n, int k_prime, CoarseTopkPlan* p, b
   p->off_keys = o; o += align256(sizeof(unsigned long long) * (size_t)B * cap);
   // the sample holds bf16 values: kept as 16-bit patterns where the selection of its r-th largest reads them (B * n_sample
   // elements written by the sample scan and read back once: 0.5 GB per batch of 128 on a 125 M-item shard as fp32)
-  p->sample16 = (RAILS_SAMPLE16 || group_max) && topk_bf16_source_ok(B, p->n_sample, r);
+  p->sample16 = topk_bf16_source_ok(B, p->n_sample, r);
   if (group_max && !p->sample16) return false;
   p->off_sample = o; o += align256((p->sample16 ? sizeof(unsigned short) : sizeof(float)) * (size_t)B * p->n_sample);
   p->off_top_s = o; o += align256(sizeof(float) * (size_t)B * r);
@@ -854,12 +767,8 @@ int coarse_prefilter_build(const Shape& s, const void* table, int64_t n, void* p
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
-#ifndef RAILS_SCAN8_WAVES
-#define RAILS_SCAN8_WAVES 3
-#endif
-#ifndef RAILS_SCAN8_TU
-#define RAILS_SCAN8_TU 8      // KiB of int8 table per wave and trip (tiles of d = 32)
-#endif
+constexpr int kScan8Waves = 3;
+constexpr int kScan8TripKiB = 8;   // KiB of int8 table per wave and trip (tiles of d = 32)
 typedef int ci32x4 __attribute__((ext_vector_type(4)));
 typedef int ci32x16 __attribute__((ext_vector_type(16)));
 
@@ -885,7 +794,7 @@ struct CoarseI8Args {
 };
 
 template <int DC8, bool NT>   // DC8 = d / 32 K chunks of the int8 MFMA; NT: non-temporal table loads
-__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(RAILS_SCAN8_WAVES, RAILS_SCAN8_WAVES))) void coarse_scan_i8_kernel(CoarseI8Args a) {
+__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(kScan8Waves, kScan8Waves))) void coarse_scan_i8_kernel(CoarseI8Args a) {
   constexpr int DC = 2 * DC8;
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // bf16 fragments, int8 fragments, thr, thr_lo, integer starts
   const int d = a.d, B = a.B;
@@ -919,7 +828,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(RA
   const int x = lane & 31, h = lane >> 5;
   const int64_t n_tiles = (a.n + 31) >> 5;
   const int64_t gw = (int64_t)blockIdx.x * (kScanThreads / 64) + wave, n_waves = (int64_t)gridDim.x * (kScanThreads / 64);
-  constexpr int TU = RAILS_SCAN8_TU / DC8;   // item tiles per trip: 8 KiB of table per wave in flight
+  constexpr int TU = kScan8TripKiB / DC8;   // item tiles per trip: 8 KiB of table per wave in flight
   struct Trip { ci32x4 Bq[TU][DC8]; };
   auto load_trip = [&](int64_t w0, Trip& T) {
 #pragma unroll
@@ -1044,10 +953,9 @@ static int launch_coarse_scan_i8(const CoarseI8Args& a, hipStream_t stream) {
   const size_t lds = coarse_scan_i8_lds(a.B, a.d);
   if (lds > 48 * 1024) { set_error("coarse int8 scan: batch %d x d %d does not fit LDS", a.B, a.d); return kErrUnsupported; }
   const int64_t n_tiles = (a.n + 31) >> 5;
-  const int tu = RAILS_SCAN8_TU / dc8;
+  const int tu = kScan8TripKiB / dc8;
   int64_t grid = (n_tiles + 4 * tu - 1) / (4 * tu);
-  static const int64_t grid_cap = [] { const char* e = getenv("RAILS_SCAN8_GRID"); const int64_t v = e ? atoll(e) : 0; return v > 0 ? v : (int64_t)2048; }();
-  if (grid > grid_cap) grid = grid_cap;
+  if (grid > 2048) grid = 2048;
   if (grid < 1) return kOk;
   auto go = [&](auto nt) {
     constexpr bool NT = decltype(nt)::value;
@@ -1058,7 +966,7 @@ static int launch_coarse_scan_i8(const CoarseI8Args& a, hipStream_t stream) {
       default: return false;
     }
   };
-  const bool known = (RAILS_SCAN_NT != 0 && n_qt == 1) ? go(std::true_type{}) : go(std::false_type{});
+  const bool known = n_qt == 1 ? go(std::true_type{}) : go(std::false_type{});
   if (!known) { set_error("coarse int8 scan: d = %d (supported: 32, 64, 128)", a.d); return kErrUnsupported; }
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
@@ -1126,9 +1034,6 @@ int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* tab
     a.qfrag = frag; a.qfrag_out = nullptr; a.zero_words = nullptr; a.n_zero = 0; a.zero_flag = nullptr; a.q8_out = nullptr; a.qmeta_out = nullptr;
     a.scores16 = nullptr; a.ld = 0; a.stride = 1;
     a.thr = top_s + (p.r - 1); a.thr_stride = p.r; a.keys = keys; a.cap = p.cap; a.counts = counts;
-    static const int dbg = [] { const char* e = getenv("RAILS_COMP_DEBUG"); return e ? atoi(e) : 0; }();
-    a.no_hits = dbg & 1;
-    if (dbg & 2) a.counts = nullptr;      // (measurement: the appends without their global atomics -- wrong results)
     rc = launch_coarse_scan<kScanSelect>(a, stream);
   }
   if (rc != kOk) return rc;
@@ -1227,11 +1132,7 @@ int component_topk(const Shape& s, const float* eq, int B, const void* table, in
   a.qfrag = frag; a.qfrag_out = nullptr; a.zero_words = nullptr; a.n_zero = 0; a.zero_flag = nullptr;
   a.scores16 = nullptr; a.ld = 0; a.stride = 1;
   a.thr = top_s; a.thr_stride = 1; a.keys = keys; a.cap = p.cap; a.counts = counts;
-  static const int dbg = [] { const char* e = getenv("RAILS_COMP_DEBUG"); return e ? atoi(e) : 0; }();
-  a.no_hits = dbg & 1;
-  if (dbg & 2) a.counts = nullptr;
   rc = launch_coarse_scan<kScanSelect>(a, stream);
-  a.counts = counts;
   if (rc != kOk) return rc;
   return select_sublists(keys, counts, rows, p.cap, kSubLists, k_group, out_scores, out_pos, out_counts, out_flag, stream);
 }

@@ -24,11 +24,9 @@
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
-#ifndef RAILS_BATCHED_PROLOGUE_BYTES
-#define RAILS_BATCHED_PROLOGUE_BYTES (1300 * 1024)   // query-side weights per query beyond which the batched (MFMA) kernels take over
-#endif
-
 namespace mol {
+
+constexpr size_t kBatchedPrologueBytes = 1300 * 1024;   // query-side weights per query beyond which the batched (MFMA) kernels take over
 
 constexpr int kQueryThreads = 1024;  // 16 waves: the prologue is a chain of small dense layers, latency-bound
 
@@ -405,12 +403,6 @@ __global__ __launch_bounds__(kQueryThreads) void query_group_kernel(QueryArgs a,
 // ---------------------------------------------------------------------------------------------
 typedef float qf32x16 __attribute__((ext_vector_type(16)));
 
-#ifdef RAILS_QUERY_PHASES   // tools/query_phases.sh: wall-clock stamps (100 MHz) of P1's workgroup (0, 0)
-__device__ long long g_qphase[8];
-#define RAILS_QPHASE(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_qphase[i] = (long long)wall_clock64(); } while (0)
-#else
-#define RAILS_QPHASE(i)
-#endif
 constexpr int kP1Threads = 512;    // 8 waves: K split eight ways (one macro step per wave up to D = 256)
 constexpr int kP2Threads = 1024;   // 16 waves: K split sixteen ways (one macro step per wave at QH = 512)
 constexpr int kP3Threads = 1024;
@@ -512,7 +504,6 @@ __device__ __forceinline__ void p1_gemm_block(const QueryArgs& a, int tile, int 
   const int c0 = (is_glu ? block : block - nglu) * 32;
   // biases of this thread's two output elements (same column): loaded now so that the round trip (a first touch of
   // that tensor since the scoring kernel streamed the corpus: TLB miss included) overlaps the operand loads
-  RAILS_QPHASE(0);
   const int tcc = threadIdx.x & 31;
   const float bias_l = is_glu ? a.w.q_glu_b[c0 + tcc] : a.w.gq_b1[c0 + tcc];
   const float bias_r = is_glu ? a.w.q_glu_b[QH + c0 + tcc] : 0.0f;
@@ -549,14 +540,12 @@ __device__ __forceinline__ void p1_gemm_block(const QueryArgs& a, int tile, int 
       if (is_glu) accr = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], br[s], accr, 0, 0, 0);
     }
   }
-  RAILS_QPHASE(1);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     part[0][wave][acc_row(r, h)][col] = accl[r];
     part[1][wave][acc_row(r, h)][col] = accr[r];
   }
   __syncthreads();
-  RAILS_QPHASE(2);
   for (int e = threadIdx.x; e < 1024; e += kP1Threads) {
     const int rr = e >> 5, cc = e & 31;
     const int64_t bb = (int64_t)tile * 32 + rr;
@@ -569,7 +558,6 @@ __device__ __forceinline__ void p1_gemm_block(const QueryArgs& a, int tile, int 
       hq_out[bb * a.Hq + c0 + cc] = silu_precise(l);
     }
   }
-  RAILS_QPHASE(3);
 }
 
 __global__ __launch_bounds__(kP1Threads) void query_p1_kernel(QueryArgs a, float* __restrict__ glu_out, float* __restrict__ hq_out) {
@@ -684,7 +672,7 @@ int query_prologue(const Shape& s, const Weights& w, const float* q, const int64
   // The per-query kernel streams every weight matrix through one CU per query (~150 GB/s of L2 each); the batched
   // kernels read them once but pay three dependent launches (~8 us each).  Crossover ~1.3 MB of weights per query.
   const size_t weight_bytes = sizeof(float) * ((size_t)a.D * 2 * a.QH + (size_t)(a.PQ - a.n_uid) * a.d * a.QH + (size_t)a.Hq * a.D + (size_t)L * a.Hq);
-  const bool use_batched = forced == 2 || (forced == 0 && weight_bytes > (size_t)RAILS_BATCHED_PROLOGUE_BYTES);
+  const bool use_batched = forced == 2 || (forced == 0 && weight_bytes > kBatchedPrologueBytes);
   if (batched_ok && use_batched && !(forced == 0 && a.QH > 0 && B <= 64)) {
     // scratch rows behind the fragment pack (rails_mol_query_pack_floats counts them)
     const int64_t bt = (int64_t)(B + 31) / 32 * 32;
@@ -720,9 +708,3 @@ int query_prologue(const Shape& s, const Weights& w, const float* q, const int64
 }
 
 }  // namespace mol
-
-#ifdef RAILS_QUERY_PHASES
-extern "C" int rails_debug_query_phases(long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(mol::g_qphase), sizeof(long long) * 8) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -13,10 +13,7 @@ namespace mol {
 struct WsFp32 {
   static constexpr int CE = 4, OPV = 1;
   static constexpr int kW1Stream = 0;
-#ifndef RAILS_WS_PD1
-#define RAILS_WS_PD1 2
-#endif
-  static constexpr int PD1 = RAILS_WS_PD1;  // GEMM1 chunks (16 MFMAs = 1024 cycles each) requested ahead: L2 latency with the tile touched a unit earlier
+  static constexpr int PD1 = 2;  // GEMM1 chunks (16 MFMAs = 1024 cycles each) requested ahead: L2 latency with the tile touched a unit earlier
   static constexpr int PD2 = 1, PD3 = 1;    // a chunk is 8 MFMAs = 512 cycles: one chunk ahead covers the LDS latency
   struct Op { float4 v; };
   __device__ __forceinline__ void init() {}
@@ -150,13 +147,11 @@ template <int PQ, int PX, int DD, int H>
 static int launch_score(const ScoreArgs& a, int n_cu, hipStream_t stream) {
   using U = Fp32Unit;
   const int variant = choose_variant<PQ, PX, DD, H>(a, n_cu);
-  if ((variant == 2 || variant == 4 || variant == 5) && a.per_row) { set_error("staged scoring kernel does not do per-row candidates"); return kErrUnsupported; }
+  if ((variant == 2 || variant == 5) && a.per_row) { set_error("staged scoring kernel does not do per-row candidates"); return kErrUnsupported; }
   switch (variant) {
-    case 1: return launch_kernel<U, PQ, PX, DD, H, 8, false>(a, n_cu, stream);
-    case 2: return launch_kernel<U, PQ, PX, DD, H, 8, true>(a, n_cu, stream);
-    case 3: return launch_kernel<U, PQ, PX, DD, H, 4, false>(a, n_cu, stream);
-    case 4: return launch_kernel<U, PQ, PX, DD, H, 4, true>(a, n_cu, stream);
-    case 5: return launch_staged1<U, PQ, PX, DD, H, 8>(a, n_cu, stream);
+    case 1: return launch_kernel<U, PQ, PX, DD, H, false>(a, n_cu, stream);
+    case 2: return launch_kernel<U, PQ, PX, DD, H, true>(a, n_cu, stream);
+    case 5: return launch_staged1<U, PQ, PX, DD, H>(a, n_cu, stream);
     default: set_error("unknown RAILS_SCORE_VARIANT %d", variant); return kErrInvalid;
   }
 }
@@ -212,11 +207,4 @@ int score_launch(const Shape& s, const ScoreArgs& a, int n_cu, hipStream_t strea
   return kErrUnsupported;
 }
 
-#ifdef RAILS_WS_PHASES
-}  // namespace mol
-extern "C" int rails_debug_ws_phases(long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(mol::g_ws_phase), sizeof(long long) * 16) == hipSuccess ? 0 : -1;
-}
-namespace mol {
-#endif
 }  // namespace mol

@@ -17,7 +17,7 @@
 //  * one wave's stream is software-pipelined so that MFMAs always have independent VALU work next to them:
 //      stage X(q)   GEMM2 of query q       ||  softmax/mixture epilogue of query q-1 (+ the operand split of cl)
 //      stage Y(q)   GEMM3 K-step s         ||  silu + operand split of K-step s+1
-//    Two waves per SIMD (or one with 512 registers) fill what is left.
+//    Two waves per SIMD fill what is left.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -35,18 +35,6 @@
 #ifndef RAILS_F16_SINGLE
 #define RAILS_F16_SINGLE 0
 #endif
-#ifndef RAILS_F16_TIGHT_PF
-#define RAILS_F16_TIGHT_PF 2   // epilogue operand ring depth of the TIGHT stream
-#endif
-// Round-6 latency experiments on the TIGHT stream (8x8x32 at two waves per SIMD; A/B builds, tools/r06_f16_pipe_ab.sh; results: DESIGN.md 7.1):
-//   RAILS_F16_TIGHT_YPIPE = 1  stage Y: silu + operand split of K-step s + 1 in the scheduling region of K-step s's MFMAs (both operand slots live)
-//   RAILS_F16_TIGHT_XPIPE = 1  stage X: the cl operand split of K-step s + 1 in the region of K-step s's MFMAs (a second operand slot)
-#ifndef RAILS_F16_TIGHT_YPIPE
-#define RAILS_F16_TIGHT_YPIPE 0
-#endif
-#ifndef RAILS_F16_TIGHT_XPIPE
-#define RAILS_F16_TIGHT_XPIPE 0
-#endif
 
 namespace mol {
 #if RAILS_F16_SINGLE
@@ -54,6 +42,8 @@ inline namespace f16x1 {
 #else
 inline namespace f16x3 {
 #endif
+
+constexpr int kF16TightLimit = 200;   // accumulator registers of a unit above which the 8-wave build takes the TIGHT stream
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
@@ -83,33 +73,9 @@ __device__ __forceinline__ void static_for(F&& f) {
   [&]<int... I>(std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, N>{});
 }
 
-// RAILS_F16_ABLATE (debug builds, tools/f16_ablation.sh): 1 = no MFMAs, 2 = no transcendentals, 3 = no VALU arithmetic at all --
-// wrong results, used to price each instruction class in situ
-#ifndef RAILS_F16_ABLATE
-#define RAILS_F16_ABLATE 0
-#endif
-__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
-#if RAILS_F16_ABLATE == 1
-  asm volatile("" : "+v"(c) : "v"(a), "v"(b));
-  return c;
-#else
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-#endif
-}
-__device__ __forceinline__ float f_exp2(float x) {
-#if RAILS_F16_ABLATE >= 2
-  return x * x;
-#else
-  return __builtin_amdgcn_exp2f(x);
-#endif
-}
-__device__ __forceinline__ float f_rcp(float x) {
-#if RAILS_F16_ABLATE >= 2
-  return x + 0.5f;
-#else
-  return __builtin_amdgcn_rcpf(x);
-#endif
-}
+__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ float f_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+__device__ __forceinline__ float f_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float swap32(float v) { return __shfl_xor(v, 32, 64); }
 
 // two fp32 values -> packed f16 hi (round toward zero) and packed f16 lo (the fp32 remainder x - hi, exact, RTZ to f16):
@@ -117,11 +83,6 @@ __device__ __forceinline__ float swap32(float v) { return __shfl_xor(v, 32, 64);
 // `m1` is -1.0 in a VGPR the compiler cannot see through: fma(fpext(h), m1, x) then selects v_fma_mix_f32 (a visible -1.0 is
 // folded into cvt + sub, two instructions), and unlike inline asm the instruction stays visible to the scheduler.
 __device__ __forceinline__ void split_pair(float x0, float x1, float m1, unsigned& hi, unsigned& lo) {
-#if RAILS_F16_ABLATE == 3
-  hi = __builtin_bit_cast(unsigned, x0);
-  lo = __builtin_bit_cast(unsigned, x1);
-  return;
-#endif
   typedef _Float16 h2v __attribute__((ext_vector_type(2)));
   const h2v h = __builtin_bit_cast(h2v, __builtin_amdgcn_cvt_pkrtz(x0, x1));
 #if RAILS_F16_SINGLE
@@ -148,12 +109,8 @@ __device__ __forceinline__ void split8(const float (&x)[8], float m1, h8& hi, h8
 }
 // t / (1 + 2^t) on the -log2e-prescaled argument (mol_layout.h): exp2, add, rcp, mul
 __device__ __forceinline__ float nsilu(float t) {
-#if RAILS_F16_ABLATE == 3
-  return t;
-#else
   const float e = f_exp2(t) + 1.0f;
   return t * f_rcp(e);
-#endif
 }
 
 // Views of the split gate pack (rails_mol_pack_gate_weights with precision f16x3): [W1 hi][W1 lo][W2 hi][W2 lo][b1][b2], the whole
@@ -183,16 +140,15 @@ struct SplitPack {
 // GEMM1 on pre-split operands: eq = [ks][hi|lo][lane] h8 (query pack), tEx = [m][ks][hi|lo][lane] h8 (tile, LDS or HBM).
 // Item groups in chunks of <= 8 (their B fragments of a K-step are fetched together); inside a chunk the products are
 // outermost so that consecutive MFMAs go to different accumulators.
-// BULK: no fences between chunks -- the compiler then requests the whole tile up front (PX * d / 4 registers), which is what a
-// wave that fetches its tile straight from HBM wants (one round trip per unit instead of one per chunk) and what only a
-// one-wave-per-SIMD build has the registers for.
-template <class G, int PX, int DD, bool BULK_ = false, bool PIPE = false>
+// BULK: no fences between chunks -- the compiler then requests the whole tile up front (PX * d / 4 registers): one memory round trip
+// per unit instead of one per chunk.
+template <class G, int PX, int DD, bool PIPE = false>
 __device__ __forceinline__ void gemm1_presplit(f32x16 (&D1)[PX], const h8* __restrict__ eq, const h8* tEx, int lane) {
   // PIPE (independent waves at two per SIMD, operands straight from memory): the one-product build reads only the hi fragments --
-  // half the registers -- so it can request its whole tile up front like BULK (B = 1: 0.127 -> 0.110 ms); the three-product build cannot
+  // half the registers -- so it can request its whole tile up front, BULK (B = 1: 0.127 -> 0.110 ms); the three-product build cannot
   // (tile = 128 registers next to 128 of accumulators) and keeps one round trip per K-step (its hi fragments alone one step ahead
   // measured 2-6 % SLOWER at B = 1 ... 16).
-  constexpr bool BULK = BULK_ || (PIPE && RAILS_F16_SINGLE != 0 && PX * (DD / 16) * 4 <= 64);
+  constexpr bool BULK = PIPE && RAILS_F16_SINGLE != 0 && PX * (DD / 16) * 4 <= 64;
   static_assert(DD % 16 == 0, "f16x3 GEMM1 walks K in steps of 16");
   static_assert(PX <= 8, "the register-resident unit holds all item groups of a K-step at once");
   constexpr int MC = PX;
@@ -423,9 +379,6 @@ template <class G>
 struct XState {
   WSlots<1> ws;
   h8 bh, bl;         // current K-step's cl operand, split right before the K-step's first MFMA
-#if RAILS_F16_TIGHT_XPIPE
-  h8 bh2, bl2;       // the next K-step's, split one region ahead
-#endif
 };
 template <class G, class WP>
 __device__ __forceinline__ void init_d2(f32x16 (&D2)[G::TH], const WP& w, int hi) {
@@ -512,13 +465,6 @@ __device__ __forceinline__ void y_end(const YS& st, f32x16 (&D3)[G::TL]) {
   }
 }
 
-#ifdef RAILS_F16_PHASES   // tools/f16_phases.sh: shader-clock stamps of workgroup 0 / wave 0's units (the last one stays)
-static __device__ long long g_f16_phase[32];
-#define F16_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0 && item0 == 32 * 20 * (int64_t)gridDim.x) g_f16_phase[i] = (long long)clock64(); } while (0)
-#else
-#define F16_STAMP(i)
-#endif
-
 // OVERLAP: stage X of query Q+1 carries the epilogue of query Q (needs D2 and D3 of two queries live at once).
 // TIGHT:   the accumulators alone fill the register budget (8x8x32 at two waves per SIMD: 224 of 256): no operand double
 //          buffering in stage Y and no pinned order -- the compiler's own schedule fits without spilling, a pinned one does not.
@@ -532,9 +478,9 @@ struct F16Unit {
   template <class G, int NW>
   static __device__ __forceinline__ void stage(const ScoreArgs& p, float* smem) { SplitPack<G>::template stage<NW>(p, smem); }
 
-  template <class G, int PX, int DD, bool BULK = false, int PIPE = 0>   // PIPE > 1 (the fp32 unit's register ring) means "none" here
+  template <class G, int PX, int DD, int PIPE = 0>   // PIPE > 1 (the fp32 unit's register ring) means "none" here
   static __device__ __forceinline__ void gemm1(f32x16 (&D1)[PX], const float* __restrict__ eq, const float4* tEx, int lane) {
-    gemm1_presplit<G, PX, DD, BULK, (PIPE == 1)>(D1, reinterpret_cast<const h8*>(eq), reinterpret_cast<const h8*>(tEx), lane);
+    gemm1_presplit<G, PX, DD, (PIPE == 1)>(D1, reinterpret_cast<const h8*>(eq), reinterpret_cast<const h8*>(tEx), lane);
   }
 
   template <class G, int PX>
@@ -567,7 +513,7 @@ struct F16Unit {
     };
 
     f32x16 D2[G::TH];
-    Epi<G, (TIGHT ? RAILS_F16_TIGHT_PF : 8), NONE> ep;   // TIGHT has no registers to spare for a deeper operand ring (and its epilogue is not fenced: the compiler hoists)
+    Epi<G, (TIGHT ? 2 : 8), NONE> ep;   // TIGHT has no registers to spare for a deeper operand ring (and its epilogue is not fenced: the compiler hoists)
     XState<G> xs;
     YState<G, 1> ys;
     auto stage_x_alone = [&](auto qc) {   // GEMM2 with nothing to hide it under but the operand splits
@@ -575,21 +521,6 @@ struct F16Unit {
       init_d2<G>(D2, w, hi);
       x_begin<G>(xs, w, lane);
       if constexpr (TIGHT) {
-#if RAILS_F16_TIGHT_XPIPE
-        cl_split<G, PX, Q * G::RPQ, 0>(D1, w, xs.bh, xs.bl);
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<G::E / 8>([&](auto kc) {
-          constexpr int KS = decltype(kc)::value;
-          if constexpr (KS + 1 < G::E / 8) cl_split<G, PX, Q * G::RPQ, KS + 1>(D1, w, xs.bh2, xs.bl2);
-          static_for<3 * G::TH>([&](auto ic) {
-            constexpr int I = 3 * G::TH * KS + decltype(ic)::value;
-            seq_mfma<XSeq<G>, I>(D2, xs.ws, xs.bh, xs.bl, [&](bool hi_part, int f) { return (hi_part ? w.w1hi : w.w1lo)[f * 64 + lane]; });
-          });
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (KS + 1 < G::E / 8) { xs.bh = xs.bh2; xs.bl = xs.bl2; }
-        });
-        return;
-#endif
         static_for<G::E / 8>([&](auto kc) {
           static_for<3 * G::TH>([&](auto ic) { x_mfma<G, PX, Q * G::RPQ, 3 * G::TH * decltype(kc)::value + decltype(ic)::value>(D1, D2, xs, w, lane); });
           __builtin_amdgcn_sched_barrier(0);
@@ -601,18 +532,6 @@ struct F16Unit {
     auto stage_y = [&](auto qc) {         // silu of K-step 0 exposed, then GEMM3 || silu of the following K-steps
       y_begin<G>(ep.D3, ys, w, lane, hi);
       if constexpr (TIGHT) {
-#if RAILS_F16_TIGHT_YPIPE
-        static_for<4>([&](auto sc) { silu_slice<G, decltype(sc)::value>(D2, ys, w); });
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<NYS>([&](auto kc) {
-          constexpr int KS = decltype(kc)::value;
-          if constexpr (KS + 1 < NYS) static_for<4>([&](auto sc) { silu_slice<G, 4 * (KS + 1) + decltype(sc)::value>(D2, ys, w); });   // into slot (KS + 1) & 1
-          static_for<3 * G::TL>([&](auto ic) { y_mfma<G, 3 * G::TL * KS + decltype(ic)::value>(ep.D3, ys, w, lane); });
-          __builtin_amdgcn_sched_barrier(0);
-        });
-        y_end<G>(ys, ep.D3);
-        return;
-#endif
         static_for<NYS>([&](auto kc) {
           constexpr int KS = decltype(kc)::value;
           static_for<4>([&](auto sc) { silu_slice<G, 4 * KS + decltype(sc)::value>(D2, ys, w); });
@@ -643,29 +562,22 @@ struct F16Unit {
         constexpr int Q = decltype(qc)::value;
         const int q = g * G::QT + Q;
         if (q < p.B && (only < 0 || q == only)) {
-          F16_STAMP(4 * Q);
           stage_x_alone(qc);
-          F16_STAMP(4 * Q + 1);
           ep.reset(gq_of(q), tGi, lane);
           stage_y(qc);
-          F16_STAMP(4 * Q + 2);
           store(qc, q, epilogue_alone(qc));
-          F16_STAMP(4 * Q + 3);
         }
       });
       return;
     }
     // shared corpus: all QT queries of the group in one straight-line stream;
     // stage X of query Q+1 carries the epilogue of query Q between its MFMAs
-    F16_STAMP(0);
     stage_x_alone(std::integral_constant<int, 0>{});
-    F16_STAMP(1);
     static_for<G::QT>([&](auto qc) {
       constexpr int Q = decltype(qc)::value;
       const int q = g * G::QT + Q;
       ep.reset(gq_of(q), tGi, lane);
       stage_y(qc);
-      F16_STAMP(2 + 2 * Q);
       if constexpr (Q + 1 < G::QT) {
         init_d2<G>(D2, w, hi);
         x_begin<G>(xs, w, lane);
@@ -675,7 +587,6 @@ struct F16Unit {
       } else {
         store(qc, q, epilogue_alone(qc));
       }
-      F16_STAMP(3 + 2 * Q);
     });
   }
 };

@@ -54,7 +54,7 @@ __device__ __forceinline__ float xor32(float v) { return __shfl_xor(v, 32, 64); 
 // SS: float4 stride between consecutive fragment slots of `tEx` as the lane sees them -- 64 in a tile (slot s of lane l at tEx[64 s + l]); 2 in
 // the row-major copy of the index (rails_mol_index_rows_build: item i's slot s, half h at rows[i * RP + 2 s + h]; the rows kernel hands the
 // unit the per-lane pointer row + h - lane, so that tEx[2 s + l] lands there).  Same values, same order, same bits.
-template <class G, int PX, int DD, bool BULK = false, int PIPE = 0, int SS = 64>
+template <class G, int PX, int DD, int PIPE = 0, int SS = 64>
 __device__ __forceinline__ void gemm1(f32x16 (&D1)[PX], const float4* __restrict__ eq, const float4* tEx, int lane) {
 #pragma unroll
   for (int m = 0; m < PX; ++m)
@@ -137,9 +137,8 @@ __device__ __forceinline__ void gemm1(f32x16 (&D1)[PX], const float4* __restrict
       D1[m] = mfma32(a.w, b.w, D1[m]);
     }
     // keep the operand fetches of later K-chunks below this chunk's MFMAs: left alone, the scheduler hoists
-    // every read of the tile to the top (128 live registers) and spills.  BULK (one wave per SIMD, tile straight from HBM)
-    // wants exactly that hoist: one memory round trip per unit instead of one per chunk.
-    if constexpr (!BULK) asm volatile("" ::: "memory");
+    // every read of the tile to the top (128 live registers) and spills
+    asm volatile("" ::: "memory");
   }
 }
 
@@ -287,9 +286,9 @@ struct Fp32UnitImpl {
   static constexpr int kLdsWeightFloats = G::kWpackFloats;
   template <class G, int NW>
   static __device__ __forceinline__ void stage(const ScoreArgs& p, float* smem) { stage_weights<G, NW>(p, smem); }
-  template <class G, int PX, int DD, bool BULK = false, int PIPE = 0>
+  template <class G, int PX, int DD, int PIPE = 0>
   static __device__ __forceinline__ void gemm1(f32x16 (&D1)[PX], const float* __restrict__ eq, const float4* tEx, int lane) {
-    mol::gemm1<G, PX, DD, BULK, PIPE, SS>(D1, reinterpret_cast<const float4*>(eq), tEx, lane);
+    mol::gemm1<G, PX, DD, PIPE, SS>(D1, reinterpret_cast<const float4*>(eq), tEx, lane);
   }
   // All queries of one unit, each at its own static register offset (no register rotation).
   // `only` >= 0 restricts the unit to that query (per-row candidates).

@@ -27,23 +27,14 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // -- which drains the wave's DMA pieces (vmcnt(0)) -- before its first weight read, and the staged shells issue their first tile's DMA
 // right behind this, so the two round trips run side by side instead of one after the other (a copy through registers waits for its
 // loads before it can store; small corpora are one round of tiles: every microsecond of prologue is on the critical path).
-#ifndef RAILS_STAGE_DMA
-#define RAILS_STAGE_DMA 1
-#endif
 template <class G, int NW>
 __device__ __forceinline__ void stage_weights(const ScoreArgs& p, float* smem) {
-#if RAILS_STAGE_DMA
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   constexpr int kPieces = G::kWpackFloats / 256;
   for (int piece = wave; piece < kPieces; piece += NW)
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.wpack + piece * 256 + lane * 4),
                                      (__attribute__((address_space(3))) void*)(smem + piece * 256), 16, 0, 0);
   for (int i = kPieces * 256 + threadIdx.x; i < G::kWpackFloats; i += NW * 64) smem[i] = p.wpack[i];
-#else
-  const float4* src = reinterpret_cast<const float4*>(p.wpack);
-  float4* dst = reinterpret_cast<float4*>(smem);
-  for (int i = threadIdx.x; i < G::kWpackFloats / 4; i += NW * 64) dst[i] = src[i];
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -100,10 +91,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_direct_kernel(Score
     const float4* tGi = tEx + G::kTileExFloats / 4;
     const float* eq = p.eqfrag + (int64_t)g * G::kEqGroupFloats;
     f32x16 D1[PX];
-#ifndef RAILS_DIRECT_PIPE
-#define RAILS_DIRECT_PIPE 1
-#endif
-    U::template gemm1<G, PX, DD, (NW == 4), ((NW == 8 && RAILS_DIRECT_PIPE != 0) ? 1 : 0)>(D1, eq, tEx, lane);   // one wave per SIMD: the whole tile requested up front; two: one K-chunk ahead
+    U::template gemm1<G, PX, DD, 1>(D1, eq, tEx, lane);   // two waves per SIMD: one K-chunk requested ahead
     // (Measured three times and not kept: an L2 touch of this wave's next tile from here -- untracked asm loads in rounds 1 and 3,
     // ordinary loads consumed at the end of the unit in round 3: B = 1 ... 8 all 2-5 % slower.  What does help these shells is the
     // K-chunk lookahead inside GEMM1, above.  An early touch of THIS tile's gate rows, read at the head of the epilogue, changed nothing
@@ -153,7 +141,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_rows_kernel(ScoreAr
     const float4* tGi = tEx + 2 * (G::kTileExFloats / 256);            // the Ex slots, two float4 each
     const float* eq = p.eqfrag + (int64_t)(row / G::QT) * G::kEqGroupFloats;
     f32x16 D1[PX];
-    UR::template gemm1<G, PX, DD, false, 1>(D1, eq, tEx, lane);
+    UR::template gemm1<G, PX, DD, 1>(D1, eq, tEx, lane);
     UR::template queries<G, PX>(D1, p, row / G::QT, row, (int64_t)tile * kTileItems, smem, tGi, lane, hi, x);
   }
 }
@@ -172,6 +160,8 @@ __device__ __forceinline__ void dma_floats(const float* __restrict__ src, float*
         (__attribute__((address_space(3))) void*)(lds + piece * 256), 16, 0, 0);
   }
 }
+
+constexpr int kStagedPipe = 0;   // GEMM1 one K-chunk ahead with the tile in LDS: measured no difference (6.34 ms either way)
 
 template <class U, int PQ, int PX, int DD, int H, int NW>
 __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged_kernel(ScoreArgs p) {
@@ -200,10 +190,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged_kernel(Score
     for (int g = wave; g < p.n_groups; g += NW) {
       const float* eq = p.eqfrag + (int64_t)g * G::kEqGroupFloats;
       f32x16 D1[PX];
-#ifndef RAILS_STAGED_PIPE
-#define RAILS_STAGED_PIPE 0   // GEMM1 one K-chunk ahead with the tile in LDS: measured no difference (6.34 ms either way)
-#endif
-      U::template gemm1<G, PX, DD, false, RAILS_STAGED_PIPE>(D1, eq, tEx, lane);
+      U::template gemm1<G, PX, DD, kStagedPipe>(D1, eq, tEx, lane);
       U::template queries<G, PX>(D1, p, g, -1, tile * kTileItems, smem, tGi, lane, hi, x);
     }
   }
@@ -220,6 +207,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged_kernel(Score
 // nsub = grid / leftover workgroups that split its query groups (group = sub + nsub * wave), so the round runs one unit
 // per SIMD instead of two on a few CUs (ML-20M: 853 tiles on 256 CUs -> 3 full rounds + 85 leftover tiles x 3 workgroups).
 // ---------------------------------------------------------------------------------------------
+// GEMM1 K-chunks in flight: a ring of three -- ML-20M 64 x 221 184 2.820 -> 2.765 ms, B = 32 0.200 -> 0.194 ms (one ahead: 2.780);
+// ML-1M 0.030 ms either way
+constexpr int kStaged1Pipe = 3;
+
 template <class U, int PQ, int PX, int DD, int H, int NW>
 __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged1_kernel(ScoreArgs p) {
   using G = Geo<PQ, PX, DD, H>;
@@ -269,12 +260,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged1_kernel(Scor
       const bool has = gi_idx < cnt;
       const int g = off + stride * gi_idx;
       f32x16 D1[PX];
-#ifndef RAILS_STAGED1_PIPE
-#define RAILS_STAGED1_PIPE 3   // a ring of three K-chunks: ML-20M 64 x 221 184 2.820 -> 2.765 ms, B = 32 0.200 -> 0.194 ms (one ahead: 2.780); ML-1M 0.030 ms either way
-#endif
-      // the ring costs PIPE * (PX + 1) float4 registers: built where that is <= 16 and K is deeper than the ring (4 x 128 shapes); elsewhere none (8 x 32 would spill)
-      constexpr int kPipe = (RAILS_STAGED1_PIPE > 1 && (RAILS_STAGED1_PIPE * (PX + 1) > 16 || DD / 8 <= RAILS_STAGED1_PIPE)) ? 0 : RAILS_STAGED1_PIPE;
-      if (has) U::template gemm1<G, PX, DD, false, kPipe>(D1, p.eqfrag + (int64_t)g * G::kEqGroupFloats, tEx, lane);
+      // the ring costs kStaged1Pipe * (PX + 1) float4 registers: built where that is <= 16 and K is deeper than the ring (4 x 128 shapes); elsewhere none (8 x 32 would spill)
+      constexpr int kPipe = (kStaged1Pipe * (PX + 1) > 16 || DD / 8 <= kStaged1Pipe) ? 0 : kStaged1Pipe;
+      if (has) U::template gemm1<G, PX, DD, kPipe>(D1, p.eqfrag + (int64_t)g * G::kEqGroupFloats, tEx, lane);
       if (it == n_it - 1) {
         __syncthreads();   // every wave is past its last GEMM1 of this tile: the Ex buffer is free
         if (i + 1 < mine) {
@@ -289,24 +277,23 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged1_kernel(Scor
 }
 
 // ---- launch helpers ----------------------------------------------------------------------------------------------
-// RAILS_SCORE_VARIANT: 0 = pick automatically; 1 / 2 = force direct / staged with 8 waves (2 per SIMD);
-// 3 / 4 = direct / staged with 4 waves (1 per SIMD, 512 registers); 5 = staged with a single Ex buffer (8 waves);
-// 6 = staged with a single Ex buffer, 4 waves
+// RAILS_SCORE_VARIANT: 0 = pick automatically; 1 / 2 = force direct / staged; 5 = staged with a single Ex buffer
+// (7 = the small-unit shell, mol_score.hip).  Every shell runs kScoreWaves = 8 waves (2 per SIMD).
 inline int score_variant() {
   const char* e = getenv("RAILS_SCORE_VARIANT");
   return e ? atoi(e) : 0;
 }
 
-template <class U, int PQ, int PX, int DD, int H, int NW, bool STAGED>
+template <class U, int PQ, int PX, int DD, int H, bool STAGED>
 static int launch_kernel(const ScoreArgs& a, int n_cu, hipStream_t stream) {
   using G = Geo<PQ, PX, DD, H>;
+  constexpr int NW = kScoreWaves;
   constexpr size_t lds = ((size_t)U::template kLdsWeightFloats<G> + (STAGED ? 2 * (size_t)G::kTileFloats : 0)) * sizeof(float);
   if constexpr (lds > 160 * 1024) {
     set_error("staged scoring kernel needs %zu B of LDS", lds);
     return kErrUnsupported;
   } else {
     if (a.dry_run) return kOk;
-    const int wg_per_cu = (NW == 4 && lds <= 80 * 1024) ? 2 : 1;
     int64_t grid;
     if (STAGED) {
       grid = a.n_tiles;
@@ -314,7 +301,7 @@ static int launch_kernel(const ScoreArgs& a, int n_cu, hipStream_t stream) {
       const int64_t n_units = a.per_row ? (int64_t)a.B * a.n_tiles : a.n_tiles * a.n_groups;
       grid = n_units;   // fewer units than wave slots: one unit per workgroup first (wave-major remainder mapping)
     }
-    if (grid > (int64_t)n_cu * wg_per_cu) grid = (int64_t)n_cu * wg_per_cu;
+    if (grid > (int64_t)n_cu) grid = (int64_t)n_cu;
     if (grid < 1) return kOk;
     auto go = [&](auto kernel) {
       static DynLdsOnce once;   // one per kernel (the lambda is instantiated per kernel type)
@@ -326,7 +313,7 @@ static int launch_kernel(const ScoreArgs& a, int n_cu, hipStream_t stream) {
       if (a.cand_pos) { set_error("indexed candidates need the independent-wave shell"); return kErrUnsupported; }
       return go(&mol_score_staged_kernel<U, PQ, PX, DD, H, NW>);
     } else {
-      if constexpr (U::kIndexedCandidates && NW == 8) {
+      if constexpr (U::kIndexedCandidates) {
         if constexpr (std::is_same_v<U, Fp32Unit>) {
           if (a.cand_pos && a.irows) return go(&mol_score_rows_kernel<Fp32UnitRows, PQ, PX, DD, H, NW>);
         }
@@ -338,9 +325,10 @@ static int launch_kernel(const ScoreArgs& a, int n_cu, hipStream_t stream) {
   }
 }
 
-template <class U, int PQ, int PX, int DD, int H, int NW>
+template <class U, int PQ, int PX, int DD, int H>
 static int launch_staged1(const ScoreArgs& a, int n_cu, hipStream_t stream) {
   using G = Geo<PQ, PX, DD, H>;
+  constexpr int NW = kScoreWaves;
   constexpr size_t lds = ((size_t)U::template kLdsWeightFloats<G> + (size_t)G::kTileExFloats + 2 * (size_t)G::kTileGiFloats) * sizeof(float);
   if constexpr (lds > 160 * 1024) {
     set_error("single-buffer staged scoring kernel needs %zu B of LDS", lds);

@@ -30,27 +30,11 @@
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
-#ifndef RAILS_SMALL_ABL
-#define RAILS_SMALL_ABL 0
-#endif
-#ifndef RAILS_SMALL_NW
-#define RAILS_SMALL_NW 8      // waves per workgroup
-#endif
-#ifndef RAILS_SMALL_WGCU
-#define RAILS_SMALL_WGCU 2    // workgroups per CU: NW * WGCU / 4 waves per SIMD
-#endif
-#ifndef RAILS_SMALL_ASM
-#define RAILS_SMALL_ASM 1     // 1: the unit's operand loads are pinned inline-asm requests with hand-counted vmcnt waits
-#endif
-#ifndef RAILS_SMALL_HD
-#define RAILS_SMALL_HD 0      // GEMM1 load rounds in flight; 0: what fits ~40 registers (8x8x32: 1, P_X = 4: 2)
-#endif
-#ifndef RAILS_SMALL_IL
-#define RAILS_SMALL_IL 2
-#endif
-
 namespace mol {
 namespace {
+
+constexpr int kSmallWaves = 8;      // waves per workgroup
+constexpr int kSmallWgPerCu = 2;    // workgroups per CU: kSmallWaves * kSmallWgPerCu / 4 waves per SIMD
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -75,7 +59,7 @@ __device__ __forceinline__ float4 ld16(const float4* __restrict__ p) {
 }
 __device__ __forceinline__ float4 ld_pair(const float4* __restrict__ p) { return swap_pair(ld16(p)); }
 
-// Loads the compiler cannot move (RAILS_SMALL_ASM): left to itself it sinks a unit's operand loads towards their uses -- and, vmcnt
+// Loads the compiler cannot move: left to itself it sinks a unit's operand loads towards their uses -- and, vmcnt
 // being in order, puts late requests in front of waits for early ones -- so a unit pays two or three memory round trips where one
 // would do.  These are issued exactly where written; vm_wait<N>() waits until at most N requests are outstanding and ties the
 // registers it covers (a use cannot be scheduled above it).  The compiler's own loads (query fragments, gate weights via LDS) only
@@ -123,7 +107,7 @@ __device__ __forceinline__ float query_mlp16(const f32x4 (&D1)[PX], const float4
   }
   // v_mfma_f32_16x16x4_f32 issues every 32 cycles but a dependent one (same accumulator) only after 40: consecutive MFMAs go to
   // IL different accumulators
-  constexpr int IL = RAILS_SMALL_IL;
+  constexpr int IL = 2;
 #pragma unroll
   for (int mc = 0; mc < PX / 2; ++mc) {
 #pragma unroll
@@ -148,11 +132,7 @@ __device__ __forceinline__ float query_mlp16(const f32x4 (&D1)[PX], const float4
 #pragma unroll
     for (int r = 0; r < 4; r += 2) {
       const f32x2 tv = {D2[t][r], D2[t][r + 1]};
-#if RAILS_SMALL_ABL & 1   // timing ablation only: wrong results
-      const f32x2 h = tv;
-#else
       const f32x2 h = tv * pk_sig(tv);
-#endif
       D2[t][r] = h.x;
       D2[t][r + 1] = h.y;
     }
@@ -203,11 +183,7 @@ __device__ __forceinline__ float query_mlp16(const f32x4 (&D1)[PX], const float4
         mn = fminf(mn, fminf(u0, u1));
       } else {
         const f32x2 t2 = pk_fma2(f32x2{gqv[o][0], gqv[o][1]}, f32x2{giv[o][0], giv[o][1]}, f32x2{D3[mm][2 * o], D3[mm][2 * o + 1]});
-#if RAILS_SMALL_ABL & 2
-        const f32x2 u = t2;
-#else
         const f32x2 u = t2 * pk_sig(t2);
-#endif
         D3[mm][2 * o] = u.x;
         D3[mm][2 * o + 1] = u.y;
         mn = fminf(mn, fminf(u.x, u.y));
@@ -222,11 +198,7 @@ __device__ __forceinline__ float query_mlp16(const f32x4 (&D1)[PX], const float4
   for (int m = 0; m < PX; ++m)
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-#if RAILS_SMALL_ABL & 2
-      const float ex = mn - D3[m / 2][2 * (m & 1) + b];
-#else
       const float ex = __builtin_amdgcn_exp2f(mn - D3[m / 2][2 * (m & 1) + b]);
-#endif
       den = den + ex;
       num = __builtin_fmaf(ex, D1[m][2 * Q + b], num);
     }
@@ -239,7 +211,7 @@ __device__ __forceinline__ float query_mlp16(const f32x4 (&D1)[PX], const float4
 }
 
 template <int PX, int DD, int H, int NW>
-__global__ __launch_bounds__(NW * 64, NW * RAILS_SMALL_WGCU / 4) void mol_score_small_kernel(ScoreArgs p) {
+__global__ __launch_bounds__(NW * 64, NW * kSmallWgPerCu / 4) void mol_score_small_kernel(ScoreArgs p) {
   using G = Geo16<PX, DD, H>;
   MOL_RUN_IF(p.run_if);
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -288,7 +260,6 @@ __global__ __launch_bounds__(NW * 64, NW * RAILS_SMALL_WGCU / 4) void mol_score_
 
     // GEMM1.  Rounds of two packed chunks (four K-steps) per item group; the loads of round r + HD are issued when round r's
     // registers have been consumed (HD rounds in flight), the item gate rows of the unit behind the last round's.
-#if RAILS_SMALL_ASM
     // every round (up to ~80 registers of them) requested up front, the item gate rows into the first registers a round frees
     constexpr int R = G::KC / 2, NL = PX + 1, HD = (80 / (4 * NL) < R ? 80 / (4 * NL) : R), NG = PX / 2;
     f32x4 ring[HD][NL], gir[NG];
@@ -341,44 +312,6 @@ __global__ __launch_bounds__(NW * 64, NW * RAILS_SMALL_WGCU / 4) void mol_score_
     vm_wait<0, NG>(gir);
 #pragma unroll
     for (int mm = 0; mm < NG; ++mm) gi[mm] = make_float4(gir[mm][0], gir[mm][1], gir[mm][2], gir[mm][3]);
-#else
-    constexpr int R = G::KC / 2, kHdFit = 40 / (4 * (PX + 1)) > 0 ? 40 / (4 * (PX + 1)) : 1;   // rounds in flight that fit ~40 registers
-    constexpr int kHdWant = RAILS_SMALL_HD > 0 ? RAILS_SMALL_HD : kHdFit, HD = kHdWant < R ? kHdWant : R;
-    float4 ra[HD], rb[HD][PX], gi[PX / 2];
-#pragma unroll
-    for (int r = 0; r < HD; ++r) {
-      ra[r] = ld16(eq + 2 * r * 64);
-#pragma unroll
-      for (int m = 0; m < PX; ++m) rb[r][m] = ld16(tEx + (m * G::KC + 2 * r) * 64);
-    }
-    f32x4 D1[PX];
-#pragma unroll
-    for (int m = 0; m < PX; ++m) D1[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int r = 0; r < R; ++r) {   // chunks 2r (x, z) and 2r + 1 (y, w): four K-steps
-      const float4 a = swap_pair(ra[r % HD]);
-      float4 b[PX];
-#pragma unroll
-      for (int m = 0; m < PX; ++m) b[m] = swap_pair(rb[r % HD][m]);
-      if (r + HD < R) {
-        ra[r % HD] = ld16(eq + 2 * (r + HD) * 64);
-#pragma unroll
-        for (int m = 0; m < PX; ++m) rb[r % HD][m] = ld16(tEx + (m * G::KC + 2 * (r + HD)) * 64);
-      }
-      if (r == R - 1) {   // the item gate rows, behind the last round's requests: in flight under this round and the first query's MLP
-#pragma unroll
-        for (int mm = 0; mm < PX / 2; ++mm) gi[mm] = ld16(tGi + 2 * mm * 64);
-      }
-#pragma unroll
-      for (int m = 0; m < PX; ++m) D1[m] = mfma16(a.x, b[m].x, D1[m]);
-#pragma unroll
-      for (int m = 0; m < PX; ++m) D1[m] = mfma16(a.z, b[m].z, D1[m]);
-#pragma unroll
-      for (int m = 0; m < PX; ++m) D1[m] = mfma16(a.y, b[m].y, D1[m]);
-#pragma unroll
-      for (int m = 0; m < PX; ++m) D1[m] = mfma16(a.w, b[m].w, D1[m]);
-    }
-#endif
     if (!staged) {   // wave-uniform; every wave of the workgroup passes exactly one of the two barriers
       __syncthreads();   // drains this wave's DMA pieces (vmcnt(0)) and meets the others
       staged = true;
@@ -400,7 +333,7 @@ __global__ __launch_bounds__(NW * 64, NW * RAILS_SMALL_WGCU / 4) void mol_score_
 template <int PX, int DD, int H>
 int launch_small(const ScoreArgs& a, int n_cu, hipStream_t stream) {
   using G = Geo16<PX, DD, H>;
-  constexpr int NW = RAILS_SMALL_NW, kWgPerCu = RAILS_SMALL_WGCU;
+  constexpr int NW = kSmallWaves, kWgPerCu = kSmallWgPerCu;
   constexpr size_t lds = (size_t)G::kPackFloats * sizeof(float);
   static_assert(kWgPerCu * lds <= 160 * 1024, "workgroups per CU");
   if (a.per_row || a.cand_pos || a.split) { set_error("the small-unit kernel scores a shared corpus densely in fp32 only"); return kErrUnsupported; }

@@ -68,13 +68,6 @@ __device__ __forceinline__ float ws_xor32(float v) { return __shfl_xor(v, 32, 64
 // barrier -- at 6 k cycles per unit (one-product build) that is the HBM latency exposed twice per unit.
 __device__ __forceinline__ void ws_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-#ifdef RAILS_WS_PHASES   // tools/wsplit_phases.sh: shader-clock stamps of workgroup 0 / wave 0, second unit
-static __device__ long long g_ws_phase[16];
-#define WS_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0 && it == 1) g_ws_phase[i] = (long long)clock64(); } while (0)
-#else
-#define WS_STAMP(i)
-#endif
-
 template <class P, int PQ, int PX, int DD, int H>
 struct WsGeo {
   using G = Geo<PQ, PX, DD, H>;
@@ -251,7 +244,6 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
     const float* tile_ptr = tile_base(cur);
     const WsBuf tileb(tile_ptr, (unsigned)(G::kTileFloats * sizeof(float)));
     const WsBuf eqb(p.eqfrag + (int64_t)cur.g * G::kEqGroupFloats, (unsigned)(G::kEqGroupFloats * sizeof(float)));
-    WS_STAMP(0);
     const unsigned un = u + stride;
     Unit nxt{};
     if (un < n_units) nxt = decode(un);
@@ -282,7 +274,6 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
         P::template mma_a<MW>(D1w, a[c % (PD1 + 1)], b[c % (PD1 + 1)]);
       });
     }
-    WS_STAMP(1);
     if constexpr (UPPER) {   // max |cl| over this wave's logits of (query = lane half, item): accumulator registers [Q RPQ, (Q + 1) RPQ) are query Q
       float cq[QT];
 #pragma unroll
@@ -304,7 +295,6 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
       P::st(sCl + ((Q * NC2 + wave * NC2W + c) * OPV) * 64, lane, o);
     });
     ws_barrier();   // B1: every wave's cl chunks are in LDS; every wave is done with the previous unit's hid and partials
-    WS_STAMP(2);
     if (have_prev && wave == (it & 3)) combine_store(prev, (it - 1) & 1);
     // Memory requests that nothing waits for soon go HERE, behind the barrier: vector-memory results return in order, so in
     // phase 1 they sat in front of GEMM1's operand loads and every chunk waited for their HBM misses (GEMM1 at half rate).
@@ -354,7 +344,6 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
         else P::template mma_a<QT>(D2, w1s[c - NC2R], ring[c % (PD + 1)]);
       });
     }
-    WS_STAMP(3);
     // hid' = t / (1 + 2^t) = -log2e * silu(pre), then the tile's hidden values as B-operand chunks -> LDS
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -369,7 +358,6 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
     for (int ec = 0; ec < EW / 4; ++ec) sGi[(wave * (EW / 4) + ec) * 64 + lane] = gi[ec];
     __builtin_amdgcn_sched_barrier(0);
     ws_barrier();   // B2: the whole hidden layer of both queries is in LDS; every wave is done with the cl chunks
-    WS_STAMP(4);
 
     // the unit after next: L2 touch
     if (un + stride < n_units) touch(decode(un + stride));
@@ -411,7 +399,6 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
       gemm3_begin(Q0{});
       ws_static_for<NC3>([&](auto cc) { gemm3_chunk(Q0{}, cc); });
       __builtin_amdgcn_sched_barrier(0);
-      WS_STAMP(7);
       EpiT ep;
       const auto a0 = epi_args(Q0{});
       ep.begin(a0.cl_own, a0.gi_own, a0.gq4);
@@ -423,10 +410,8 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
         ws_static_for<s1 - s0>([&](auto sc) { ep.template slice<0, s0 + decltype(sc)::value>(D3[0], D1w, a0.cl_own, a0.gi_own, a0.gq4, p.combine_none); });
         __builtin_amdgcn_sched_barrier(0);
       });
-      WS_STAMP(8);
       ep.template end<0>(D3[0], D1w, a0.cl_own, pmn[0], pden[0], pnum[0]);
       __builtin_amdgcn_sched_barrier(0);
-      WS_STAMP(9);
       // next unit: request the first GEMM1 chunks now (L2 hits: touched a unit ago), behind the register peak of the overlapped
       // part and one gate + softmax pass ahead of their use
       if (un < n_units) prefetch_first(nxt);
@@ -439,7 +424,6 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
       ep.template end<1>(D3[1], D1w, a1.cl_own, pmn[1], pden[1], pnum[1]);
       __builtin_amdgcn_sched_barrier(0);
     }
-    WS_STAMP(5);
     // partial softmax state of (query = lane half, item) -> LDS; both lane halves hold the wave's totals
     sPart[(wave * 3 + 0) * 64 + lane] = hi ? pmn[1] : pmn[0];
     sPart[(wave * 3 + 1) * 64 + lane] = hi ? pden[1] : pden[0];
@@ -447,7 +431,6 @@ __global__ __launch_bounds__(256, 1) void mol_score_wsplit_kernel(ScoreArgs p) {
     prev = cur;
     have_prev = true;
     cur = nxt;
-    WS_STAMP(6);
   }
   if (have_prev) {
     __syncthreads();   // also drains the uncounted touch loads before the wave ends

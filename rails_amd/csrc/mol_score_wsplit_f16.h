@@ -19,19 +19,13 @@ template <bool NONE>
 struct WsF16T {
   static constexpr int CE = 8;
   static constexpr int OPV = RAILS_F16_SINGLE ? 1 : 2;
-#ifndef RAILS_WS16_W1STREAM
-#define RAILS_WS16_W1STREAM 4
-#endif
-  static constexpr int kW1Stream = RAILS_F16_SINGLE ? 0 : RAILS_WS16_W1STREAM;   // f16x3: 256 registers of weights; 32 of them re-read per unit
+  static constexpr int kW1Stream = RAILS_F16_SINGLE ? 0 : 4;   // f16x3: 256 registers of weights; 32 of them re-read per unit
   // prefetch distances in chunks.  A chunk of f16x3 is 12 (GEMM1) / 6 MFMAs = 384 / 192 cycles, of the one-product build a third
   // of that; L2 latency ~ 800 cycles, LDS ~ 130-200.
 #if RAILS_F16_SINGLE
   static constexpr int PD1 = 3, PD2 = 4, PD3 = 4;   // (PD1 = 4, all of GEMM1 a phase ahead, measured slower: 20 buffer loads cost ~1 k cycles of issue in the gate pass)
 #else
-#ifndef RAILS_WS16_PD1
-#define RAILS_WS16_PD1 1   // 2 spills (26 registers over with 256 of weights)
-#endif
-  static constexpr int PD1 = RAILS_WS16_PD1, PD2 = 2, PD3 = 2;
+  static constexpr int PD1 = 1, PD2 = 2, PD3 = 2;   // (PD1 = 2: 2 spills, 26 registers over with 256 of weights)
 #endif
   struct Op {
     h8 hi;

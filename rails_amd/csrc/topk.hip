@@ -461,7 +461,7 @@ __global__ __launch_bounds__(kHistThreads) void compact_kernel(const float* __re
 // atomic per wave accumulates them in a rotating counter set, one barrier, one LDS read per lane and a ballot pick the
 // digit.  Elements are dealt to threads in small runs, so for untied data only about -1024 ln(1 - k/1024) of them pass
 // (~220 for k = 200); they are compacted (per-thread counts, one wave scan and one LDS atomic per wave) and sorted as
-// 64-bit keys, which settles ties by position.  Measured phases for n = 27278, k = 200 (tools/row_select_phases.hip):
+// 64-bit keys, which settles ties by position.  Measured phases for n = 27278, k = 200:
 // see DESIGN.md section 3.3.
 // General path (k > 512, heavy ties, adversarial layouts that overflow the candidate buffer): radix bisection of the
 // k-th largest key, two bits per step, first over the 32 score bits and -- only if the k-th score is tied -- on over the
@@ -471,13 +471,6 @@ constexpr int kRowMaxK = 4096;
 constexpr int kRowMaxN = 48 * kRowThreads;
 constexpr int kRowFastK = 512;
 constexpr int kRowCandCap = 4096;   // candidate keys the fast path may hand to the sort
-
-#ifdef RAILS_TOPK_PHASES   // tools/row_select_phases.hip: wall-clock stamps (100 MHz) of workgroup 0's phases
-__device__ long long g_phase[16];
-#define RAILS_PHASE(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_phase[i] = (long long)wall_clock64(); } while (0)
-#else
-#define RAILS_PHASE(i)
-#endif
 
 constexpr int kFuseMaxK = 512;    // candidates per row the fused seen-id filter stages in LDS
 constexpr int kFuseMaxW = 256;    // seen ids per row
@@ -670,7 +663,6 @@ __global__ __launch_bounds__(kRowThreads) void row_select_kernel(const RowSelect
   unsigned int lo[KEYS ? VPT : 1];
   int cnt;
   unsigned int begin = 0u;
-  RAILS_PHASE(0);
   if constexpr (KEYS) {
     cnt = a.keys_per_row;
     const unsigned long long* src = a.keys_in + (int64_t)row * cnt;
@@ -730,7 +722,6 @@ __global__ __launch_bounds__(kRowThreads) void row_select_kernel(const RowSelect
   radix_init<kRowThreads>(rsh);
   for (int i = tid; i < lds_keys; i += kRowThreads) keys[i] = 0ull;
   __syncthreads();
-  RAILS_PHASE(1);
 
   int it = 0;   // rotating counter set: step `it` accumulates into ctr[it % 3] and clears ctr[(it + 1) % 3] before its barrier
   auto emit = [&](unsigned long long kv, int j) {
@@ -822,20 +813,14 @@ __global__ __launch_bounds__(kRowThreads) void row_select_kernel(const RowSelect
       L |= (unsigned int)__popcll(ok) << shift;
       ++it;
     }
-    RAILS_PHASE(2);
     compact([&](int j) { return v[j] >= L; });
     __syncthreads();
-    RAILS_PHASE(3);
     const unsigned int m_ge = cursor;
     if (m_ge <= (unsigned int)lds_keys) {
       int npad = 2;
       while (npad < (int)m_ge) npad <<= 1;
       emit_sorted(npad);
       finish();
-      RAILS_PHASE(4);
-#ifdef RAILS_TOPK_PHASES
-      if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) g_phase[5] = m_ge;
-#endif
       return;
     }
     __syncthreads();                       // everyone has read the cursor: start over on the general path
@@ -906,12 +891,11 @@ static bool two_level_plan_at(int64_t n, int k, int64_t max_chunk, int* chunks, 
 // where what counts is how many launches they are (2 instead of 10: ~40 us of every MoLAvgTopK call with K' >= 1 000 at amzn-books size)
 static bool two_level_plan(int64_t n, int k, int* chunks, int64_t* chunk, int rows = 1 << 30, int max_k = 512) {
   if (k > max_k) return false;
-  // first-level chunk size: RAILS_ROW_CHUNK (measurement override), else the largest a workgroup holds in registers -- half of that
+  // first-level chunk size: the largest a workgroup holds in registers -- half of that
   // for up to eight rows, where 49 152-element chunks leave most of the chip idle (695 762 elements: 1 row 29 -> 27 us, 4 rows
   // 37 -> 31, 8 rows 37 -> 32; from 32 rows on smaller chunks only add second-level work: 63 -> 75 us).  A plan that does not work
   // out with the smaller chunks is retried with the full ones, so feasibility does not depend on the row count.
-  static const int64_t forced = [] { const char* e = getenv("RAILS_ROW_CHUNK"); const int64_t v = e ? atoll(e) : 0; return v >= 4096 && v <= kRowMaxN ? v / 4 * 4 : (int64_t)0; }();
-  const int64_t first = forced ? forced : (rows <= 8 ? (int64_t)kRowMaxN / 2 : (int64_t)kRowMaxN);
+  const int64_t first = rows <= 8 ? (int64_t)kRowMaxN / 2 : (int64_t)kRowMaxN;
   if (two_level_plan_at(n, k, first, chunks, chunk)) return true;
   return first != kRowMaxN && two_level_plan_at(n, k, kRowMaxN, chunks, chunk);
 }
@@ -961,7 +945,7 @@ int topk(const float* scores, int64_t ld, int rows, int64_t n, int k, const int6
   if (ids_index && n > kSortCap) { set_error("topk: ids_index needs n <= %d", kSortCap); return kErrUnsupported; }
   // k > 512 of a short row: when the k winners fill the same power of two of sort slots as the whole row would (k = 3 200 of 3 200,
   // 2 561 of 4 096), selecting first buys nothing -- the row is sorted whole (n = 3 200 = k: 52 -> 41 us per 32 rows; k = 1 000 of
-  // 3 200 stays on the selection: 28 vs 41 us; tools/r04_topk_bigk_ab.sh)
+  // 3 200 stays on the selection: 28 vs 41 us)
   const bool sort_whole = k > kRowFastK && n <= kSortCap && next_pow2((int)n) <= next_pow2(k) && !scores16 && !f_invalid;
   // candidate rows (ids through ids_index): the register-resident selection up to 8 192 candidates (16 per thread spills), the seen-id filter fused where asked
   // (round 6: the union of a Naive / Comb rerank, 6 400-7 400 candidates of which get_top_k_outputs wants k + |seen| <= 512)
@@ -1021,8 +1005,8 @@ int topk(const float* scores, int64_t ld, int rows, int64_t n, int k, const int6
 
   if (hipMemsetAsync(ws, 0, state_bytes, stream) != hipSuccess) return kErrLaunch;   // state + histograms
   // enough workgroups to fill the chip (four per CU), at least 8K elements each
-  static const int radix_wgs = [] { const char* e = getenv("RAILS_RADIX_WGS"); const int v = e ? atoi(e) : 0; return v >= 64 && v <= 16384 ? v : 1024; }();   // workgroups per launch (override for measurements): 512 / 1024 / 2048 / 4096 -> 135 / 131 / 140 / 147 us at k' = 2561, 32 x 695 762 (fewer per-workgroup histogram merges)
-  int64_t chunks = (radix_wgs + rows - 1) / rows;
+  constexpr int kRadixWgs = 1024;   // workgroups per launch: 512 / 1024 / 2048 / 4096 -> 135 / 131 / 140 / 147 us at k' = 2561, 32 x 695 762 (fewer per-workgroup histogram merges)
+  int64_t chunks = (kRadixWgs + rows - 1) / rows;
   const int64_t max_chunks = (n + 8191) / 8192;
   if (chunks > max_chunks) chunks = max_chunks;
   if (chunks < 1) chunks = 1;
@@ -2186,11 +2170,6 @@ __global__ __launch_bounds__(kRowThreads) void cand_single_kernel(const float* _
                            &wg_base, &wg_cursor);
 }
 
-static int cand_single_max() {
-  static const int v = [] { const char* e = getenv("RAILS_CAND_SINGLE_MAX"); const int x = e ? atoi(e) : -1; return x >= 0 ? x : kCandSingleMax; }();
-  return v;
-}
-
 int candidates_select(const float* scores, int64_t ld, int rows, int64_t n, int cap, float lo, float hi, void* ws, int64_t* out_pos, float* out_approx,
                       int64_t cand_ld, int n_cu, hipStream_t stream) {
   if (rows <= 0 || n <= 0) return kOk;
@@ -2199,12 +2178,11 @@ int candidates_select(const float* scores, int64_t ld, int rows, int64_t n, int 
   if (!(hi > lo)) { set_error("candidates_select: empty score range"); return kErrInvalid; }
   const float scale = (float)kCandBins / (hi - lo);
   const CandWs w = cand_ws(ws, rows);
-  if (n <= cand_single_max()) {
+  if (n <= kCandSingleMax) {
     hipLaunchKernelGGL(cand_single_kernel, dim3(rows), dim3(kRowThreads), 0, stream, scores, ld, n, lo, scale, (unsigned int)cap, w, out_pos, out_approx, cand_ld);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
   }
-  static const int cand_wgs = [] { const char* e = getenv("RAILS_CAND_WGS"); const int v = e ? atoi(e) : 0; return v >= 64 && v <= 16384 ? v : 0; }();
-  const int target = cand_wgs ? cand_wgs : 2 * (n_cu > 0 ? n_cu : 256);      // 128 / 256 / 384 / 512 / 1024 / 2048 workgroups at 32 x 695 762: hist 26.9 / 19.3 / - / 18.2 / 20.9 / 31.5 us
+  const int target = 2 * (n_cu > 0 ? n_cu : 256);      // 128 / 256 / 384 / 512 / 1024 / 2048 workgroups at 32 x 695 762: hist 26.9 / 19.3 / - / 18.2 / 20.9 / 31.5 us
   int64_t chunks = (target + rows - 1) / rows;
   const int64_t max_chunks = (n + 8191) / 8192;
   if (chunks > max_chunks) chunks = max_chunks;
@@ -2230,7 +2208,6 @@ struct CandFinishArgs {
   const int64_t* f_invalid; int f_width, f_k; int64_t* f_out_ids; float* f_out_scores;   // optional seen-id filter over the k winners
   float* state; float* state_host;           // verdict state (rails_rescore_verdict's layout); state_host: optional mirror in pinned host memory
   int clean_hist;                            // the selection was the two-launch one: its global histograms are zeroed here
-  int debug;                                 // RAILS_FINISH_DEBUG (measurements): 1 = no verdict commit, 2 = no host mirror, 4 = no sort
   int64_t* msg;                              // sharded form: (rows, 2k + 2) message [k score words | k ids | m | err], no verdict here
 };
 
@@ -2295,8 +2272,7 @@ __global__ __launch_bounds__(kSortThreads) void cand_finish_kernel(const CandFin
     if (tid == 0) { a.w.counts[row] = 0u; a.w.flags[row] = 0u; }
   }
   __syncthreads();
-  if (a.debug & 4) {
-  } else if (npad <= kSortThreads) {
+  if (npad <= kSortThreads) {
     unsigned long long kv = tid < npad ? keys[tid] : 0ull;
     kv = block_sort_desc(kv, npad, keys + npad);
     __syncthreads();
@@ -2345,7 +2321,7 @@ __global__ __launch_bounds__(kSortThreads) void cand_finish_kernel(const CandFin
     __syncthreads();
     filter_from_lds<kSortThreads>(f_id, f_sc, k, f_inv, a.f_width, a.f_k, a.f_out_ids + (int64_t)row * a.f_k, a.f_out_scores + (int64_t)row * a.f_k, f_scratch);
   }
-  if (!(a.debug & 1)) verdict_commit(a.w.call, row, rows, fail, bad, err, gap, grd, a.default_eps, a.safety, a.state, (a.debug & 2) ? nullptr : a.state_host, &s_last);
+  verdict_commit(a.w.call, row, rows, fail, bad, err, gap, grd, a.default_eps, a.safety, a.state, a.state_host, &s_last);
 }
 
 int candidates_finish(const float* exact, int64_t ld, const float* approx, const int64_t* pos, int64_t cand_ld, int cap, void* ws, const int64_t* ids,
@@ -2369,9 +2345,7 @@ int candidates_finish(const float* exact, int64_t ld, const float* approx, const
   a.out_scores = out_scores; a.out_ids = out_ids;
   a.f_invalid = f_invalid; a.f_width = f_width; a.f_k = f_k; a.f_out_ids = f_out_ids; a.f_out_scores = f_out_scores;
   a.state = state; a.state_host = state_host; a.msg = msg;
-  static const int debug = [] { const char* e = getenv("RAILS_FINISH_DEBUG"); return e ? atoi(e) : 0; }();
-  a.debug = debug;
-  a.clean_hist = n_items > cand_single_max() ? 1 : 0;
+  a.clean_hist = n_items > kCandSingleMax ? 1 : 0;
   const size_t lds = (size_t)(npad <= kSortThreads ? 3 * npad : npad) * sizeof(unsigned long long);
   hipLaunchKernelGGL(cand_finish_kernel, dim3(rows), dim3(kSortThreads), lds, stream, a);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;

@@ -344,8 +344,8 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
         B = query_embeddings.size(0)
         per_shard = -(-self._n_total // max(self._world, 1))
         # (the 4 GiB logit policy: the first pass wants the whole (B, N_shard) matrix -- beyond it every rank alike takes the per-shard path, which chunks)
-        if (not self._global_proof(query_embeddings) or not MoLBruteForceTopK.speculation_pays(B, per_shard) or B * per_shard * 4 > MoLBruteForceTopK.MAX_LOGIT_BYTES
-                or not MoLBruteForceTopK.FUSED_TAIL):
+        if (not self._global_proof(query_embeddings) or not MoLBruteForceTopK.speculation_pays(B, per_shard)
+                or B * per_shard * 4 > MoLBruteForceTopK.MAX_LOGIT_BYTES):
             return super().submit(query_embeddings, k, sorted, **kwargs)
         if k > self._n_total:
             raise RuntimeError(f"selected index k out of range (k={k}, n={self._n_total})")

@@ -367,7 +367,7 @@ class MoLBruteForceTopK(MoLTopKModule):
             ex = eng.exact
             if not (not self.speculation_pays(B, N) and self._mol_module.engine() is not eng and eng.dense_precision == "f16x3"
                     and self._index32 is not None and self._index32_engine is ex):
-                if not (self.FUSED_TAIL and eng.dense_precision == "f16x3" and k <= k_prime <= N):
+                if not (eng.dense_precision == "f16x3" and k <= k_prime <= N):
                     return None
                 # the proved flow: the filter runs inside its finish launch (and inside the redo's selection)
                 r = self._forward_rescored(query_embeddings, k_prime, _seen=(invalid_ids, k), **kwargs)
@@ -477,7 +477,7 @@ class MoLBruteForceTopK(MoLTopKModule):
                     parts.append(self._forward_rescored(query_embeddings[b0 : b0 + rows], k, **kw))
                 return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
             return self._forward_fp32_dense(query_embeddings, k, **kwargs)   # one row is too long: fp32, in corpus chunks
-        if (eps_proved is not None and self.FUSED_TAIL and self.DEVICE_VERDICT and self._index32 is not None and self._index32_engine is ex):
+        if (eps_proved is not None and self.DEVICE_VERDICT and self._index32 is not None and self._index32_engine is ex):
             return self._forward_proved(query_embeddings, k, kc, eps_proved, upper, _seen, **kwargs)
         # one prologue writes the query pack in both formats: f16 hi/lo for the first pass, fp32 for the re-scoring
         n_q = eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), B)
@@ -573,7 +573,6 @@ class MoLBruteForceTopK(MoLTopKModule):
     # fp32 re-scoring of the counted candidates -> rails_candidates_finish (sort, top-k, verdict, seen-id filter, calibration state written
     # to the device AND straight into pinned host memory) -> the dense redo under the verdict's launch predicate: 8-9 launches where the
     # exact-kc selection + separate verdict / filter / state copy took 19 (amzn-books B = 32: 0.19 -> ~0.1 ms behind the first pass).
-    FUSED_TAIL = __import__("os").environ.get("RAILS_FUSED_TAIL", "1") != "0"
     _cand = None          # {(B, cap): [workspace, positions, first-pass scores, fp32 scores]}
     _cand_dirty = False
 

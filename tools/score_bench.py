@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """A/B harness for the scoring kernel: interleaved rounds of every variant in ONE process
 (cdna_hip_programming.md section 5.4 rule 24), median/min ms and TFLOP/s per variant, max |diff| vs variant 0.
-Variants are selected by the RAILS_SCORE_VARIANT env var read at launch time by librails_amd.so; a trailing "n" (e.g. "2n")
-also sets RAILS_F16_OVERLAP=0 (f16x3 kernels without the cross-query overlap of stage X).
+Variants are selected by the RAILS_SCORE_VARIANT env var read at launch time by librails_amd.so: 0 (the dispatcher's choice), 1, 2, 5
+(the shells of mol_score_shell.h) and 7 (the small-unit shell).
   python tools/score_bench.py --variants 0,1,2 --workload amzn-books --batch 32 --rounds 7
 """
 import argparse
@@ -66,8 +66,7 @@ def main():
             score = lambda qp, b, idx, out=None: eng.score_dense_upper(qp, b, idx, poly, out=out)      # noqa: E731
 
         def select(v):
-            os.environ["RAILS_SCORE_VARIANT"] = v.rstrip("n")
-            os.environ["RAILS_F16_OVERLAP"] = "0" if v.endswith("n") else "1"
+            os.environ["RAILS_SCORE_VARIANT"] = v
 
         for v in variants:
             select(v)
