@@ -42,9 +42,10 @@ extern "C" {
  * 11: the SASRec encoder entries rails_sasrec_* and rails_gemm_f32_id_masked are new, rails_gemm_f32 gained act 2 (relu) / 3 (gelu);
  * 12: the HSTU cached-decoding entries rails_hstu_decode[_supported] and struct rails_hstu_decode_layer are new;
  * 13: the SASRec cached-decoding entries rails_sasrec_decode[_supported] / rails_sasrec_decode_workspace_floats and struct
- * rails_sasrec_decode_layer are new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
+ * rails_sasrec_decode_layer are new;
+ * 14: the IVF-Flat component index rails_ivf_* (MoLNaiveTopK use_faiss=True) is new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
-#define RAILS_ABI_VERSION 13
+#define RAILS_ABI_VERSION 14
 int rails_abi_version(void);
 
 #define RAILS_OK 0
@@ -310,6 +311,51 @@ int32_t rails_mol_component_topk_capacity(const rails_mol_shape* shape, int32_t 
 int rails_mol_component_topk(const rails_mol_shape* shape, const float* eq, int32_t batch, const void* table, int64_t n_items,
                              int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
                              int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* stream);
+/* ---- IVF-Flat index over the item components (MoLNaiveTopK use_faiss=True) ------------------------------------------
+ * Replaces the per-item-group faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) of rails/indexing/mol_top_k.py:176-199
+ * and its search (:223-238): one independent index per item group m < P_X over the fp16-rounded components fp16(Ex[:, m, :]).
+ * d in {32, 64, 128}, nlist <= 4096 (RAILS_ENOTSUP otherwise); n_items < nlist is RAILS_EINVAL.
+ * The build entries read the components from exactly one source (the other NULL): `index`, an fp32-format item index, or `components16`,
+ * the (P_X, n_items, d) fp16 table rails_ivf_components16_build writes chunk by chunk (for callers whose index is in a split-f16 format).
+ *   centroids  (P_X, nlist, d) fp32, unit norm after training;
+ *   vectors    (P_X, n_items, d) fp16 in list order;  positions (P_X, n_items) int32 item positions alongside (ascending inside a list);
+ *   offsets    (P_X, nlist + 1) int32: list l of group m is [offsets[m][l], offsets[m][l + 1]).
+ * rails_ivf_components16_build: components16[m][first_item + x][:] = fp16(Ex[x, m, :]) for the n_items items of an fp32-format index (chunk).
+ * rails_ivf_train: spherical Lloyd k-means, `iters` iterations on the sample items sample_positions[0..n_sample) (drawn by the caller);
+ * init != 0 first sets centroids to the first nlist sample items.  Assignment by the largest fp32 inner product (ties to the lower list),
+ * per-list means summed in sample order, an empty list takes the largest list's centroid (ties to the lower id) and both are perturbed by
+ * +-1/1024 per dimension, then every centroid is l2-normalised.  Deterministic: no float atomics.
+ * rails_ivf_assign: assign[m][x] = the list of item x in group m, as training assigns (n_items * P_X int32).
+ * rails_ivf_build_lists: assigns every item and writes vectors / positions / offsets with a stable counting sort.
+ * workspace of both: rails_ivf_build_workspace_bytes(n_items, nlist, n_sample) bytes (n_sample = 0 for the list build). */
+size_t rails_ivf_build_workspace_bytes(const rails_mol_shape* shape, int64_t n_items, int32_t nlist, int32_t n_sample);
+int rails_ivf_components16_build(const rails_mol_shape* shape, const float* index, int64_t n_items, void* components16, int64_t n_total,
+                                 int64_t first_item, void* stream);
+int rails_ivf_train(const rails_mol_shape* shape, const float* index, const void* components16, int64_t n_items, const int32_t* sample_positions,
+                    int32_t n_sample, int32_t nlist, int32_t iters, int32_t init, float* centroids, void* workspace, size_t workspace_bytes, void* stream);
+int rails_ivf_assign(const rails_mol_shape* shape, const float* index, const void* components16, int64_t n_items, int32_t nlist,
+                     const float* centroids, int32_t* assign, void* stream);
+int rails_ivf_build_lists(const rails_mol_shape* shape, const float* index, const void* components16, int64_t n_items, int32_t nlist,
+                          const float* centroids, void* vectors, int32_t* positions, int32_t* offsets, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* HOST pointers: offsets is a host copy of the built offsets.  *max_probes = the probe capacity the short-list rule needs (the fewest
+ * lists of any group whose sizes reach k_per_group, at least nprobe); *max_list = the largest list.  Both go to rails_ivf_search. */
+int rails_ivf_plan(const rails_mol_shape* shape, const int32_t* offsets, int32_t nlist, int32_t nprobe, int32_t k_per_group, int32_t* max_probes,
+                   int32_t* max_list);
+/* out_positions (batch, P_Q * P_X * k_per_group) int64, row (b * P_Q + i) * P_X + m holding the k_per_group best items of group m for query
+ * component eq[b, i, :] (eq: (batch, P_Q, d) fp32) by fp32 inner product with the fp16 vectors, best first (score desc, position asc),
+ * among the nprobe lists of the best centroid scores (ties to the lower list).  Where those lists hold fewer than k_per_group items the
+ * search goes on into further lists in centroid-score order until they do (FAISS returns -1 there); NaN scores rank last.  Three
+ * launches per slice of 1024 / P_Q queries: centroid scores, the scan of each probed list for all its probes, the merge.
+ * unfilled (optional, an int32 in device memory, zeroed by the call): raised when some row found fewer than k_per_group items, which
+ * only a max_probes below rails_ivf_plan's can cause; such slots hold position 0.
+ * nprobe <= min(64, nlist), k_per_group <= 128 (RAILS_ENOTSUP otherwise); 0 workspace bytes: arguments outside the limits. */
+size_t rails_ivf_search_workspace_bytes(const rails_mol_shape* shape, int32_t batch, int32_t nlist, int32_t nprobe, int32_t max_probes,
+                                        int32_t max_list, int32_t k_per_group);
+int rails_ivf_search(const rails_mol_shape* shape, const float* eq, int32_t batch, const float* centroids, const void* vectors,
+                     const int32_t* positions, const int32_t* offsets, int64_t n_items, int32_t nlist, int32_t nprobe, int32_t max_probes,
+                     int32_t max_list, int32_t k_per_group, void* workspace, size_t workspace_bytes, int64_t* out_positions, int32_t* unfilled,
+                     void* stream);
 /* torch.sort(indices, dim=1) on (rows, n) int64, n <= 16384 (mol_top_k.py:257, :515); in == out allowed. */
 int rails_sort_rows_i64(const int64_t* in, int32_t rows, int32_t n, int64_t* out, void* stream);
 /* scores[r][j] = fill where sorted_idx[r][j] == sorted_idx[r][j-1] (mol_top_k.py:277-284, :535-542). */

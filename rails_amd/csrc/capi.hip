@@ -3,6 +3,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
@@ -1042,6 +1044,94 @@ int rails_rows_normalize(const float* x, int64_t ldx, const int64_t* row_index, 
   if (rows == 0) return RAILS_OK;
   if (!x || !out || ldx < dim) { set_error("rows_normalize: NULL pointer or short stride"); return RAILS_EINVAL; }
   return fail(rows_normalize(x, ldx, row_index, rows, dim, mode, eps, out, (hipStream_t)stream), "rows_normalize");
+}
+
+size_t rails_ivf_build_workspace_bytes(const rails_mol_shape* s, int64_t n_items, int32_t nlist, int32_t n_sample) {
+  if (!shape_ok(s) || n_items < 0 || nlist <= 0 || n_sample < 0) return 0;
+  return ivf_build_workspace_bytes(*s, n_items, nlist, n_sample);
+}
+
+static int ivf_source(const rails_mol_shape* s, const float* index, const void* components16, int64_t n_items, int32_t nlist, const char* what) {
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  if ((index != nullptr) == (components16 != nullptr)) { set_error("%s: pass exactly one of index and components16", what); return RAILS_EINVAL; }
+  return ivf_check(*s, n_items, nlist, index != nullptr);
+}
+
+int rails_ivf_components16_build(const rails_mol_shape* s, const float* index, int64_t n_items, void* components16, int64_t n_total,
+                                 int64_t first_item, void* stream) {
+  g_err[0] = '\0';
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  if (s->dot_product_dimension % 8 != 0) { set_error("ivf_components16_build: d must be a multiple of 8"); return RAILS_ENOTSUP; }
+  if (n_items < 0 || first_item < 0 || first_item + n_items > n_total) { set_error("ivf_components16_build: items [%lld, %lld) outside a table of %lld", (long long)first_item, (long long)(first_item + n_items), (long long)n_total); return RAILS_EINVAL; }
+  if (n_items == 0) return RAILS_OK;
+  if (!index || !components16) { set_error("ivf_components16_build: NULL pointer"); return RAILS_EINVAL; }
+  if (is_split(*s)) { set_error("ivf_components16_build: needs an fp32-format item index (build one with precision = RAILS_PRECISION_FP32)"); return RAILS_ENOTSUP; }
+  return fail(ivf_components16(*s, index, n_items, components16, n_total, first_item, (hipStream_t)stream), "ivf_components16_build");
+}
+
+int rails_ivf_train(const rails_mol_shape* s, const float* index, const void* components16, int64_t n_items, const int32_t* sample_positions,
+                    int32_t n_sample, int32_t nlist, int32_t iters, int32_t init, float* centroids, void* workspace, size_t workspace_bytes, void* stream) {
+  g_err[0] = '\0';
+  const int c = ivf_source(s, index, components16, n_items, nlist, "ivf_train");
+  if (c != kOk) return c;
+  if (n_sample < nlist || n_sample > n_items || iters < 0) {
+    set_error("ivf_train: n_sample = %d outside [nlist = %d, n_items = %lld] or iters = %d < 0", n_sample, nlist, (long long)n_items, iters);
+    return RAILS_EINVAL;
+  }
+  if (!sample_positions || !centroids || !workspace) { set_error("ivf_train: NULL pointer"); return RAILS_EINVAL; }
+  return fail(ivf_train(*s, index, components16, n_items, sample_positions, n_sample, nlist, iters, init, centroids, workspace, workspace_bytes,
+                        (hipStream_t)stream), "ivf_train");
+}
+
+int rails_ivf_assign(const rails_mol_shape* s, const float* index, const void* components16, int64_t n_items, int32_t nlist, const float* centroids,
+                     int32_t* assign, void* stream) {
+  g_err[0] = '\0';
+  const int c = ivf_source(s, index, components16, n_items, nlist, "ivf_assign");
+  if (c != kOk) return c;
+  if (!centroids || !assign) { set_error("ivf_assign: NULL pointer"); return RAILS_EINVAL; }
+  return fail(ivf_assign(*s, index, components16, n_items, nlist, centroids, assign, (hipStream_t)stream), "ivf_assign");
+}
+
+int rails_ivf_build_lists(const rails_mol_shape* s, const float* index, const void* components16, int64_t n_items, int32_t nlist, const float* centroids,
+                          void* vectors, int32_t* positions, int32_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+  g_err[0] = '\0';
+  const int c = ivf_source(s, index, components16, n_items, nlist, "ivf_build_lists");
+  if (c != kOk) return c;
+  if (!centroids || !vectors || !positions || !offsets || !workspace) { set_error("ivf_build_lists: NULL pointer"); return RAILS_EINVAL; }
+  return fail(ivf_build_lists(*s, index, components16, n_items, nlist, centroids, vectors, positions, offsets, workspace, workspace_bytes,
+                              (hipStream_t)stream), "ivf_build_lists");
+}
+
+int rails_ivf_plan(const rails_mol_shape* s, const int32_t* offsets, int32_t nlist, int32_t nprobe, int32_t k_per_group, int32_t* max_probes,
+                   int32_t* max_list) {
+  g_err[0] = '\0';
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  if (!offsets || !max_probes || !max_list || nlist <= 0 || nprobe <= 0 || k_per_group <= 0) { set_error("ivf_plan: bad argument"); return RAILS_EINVAL; }
+  int mp = 0, ml = 0;
+  ivf_plan(offsets, s->item_dot_product_groups, nlist, std::min(nprobe, nlist), k_per_group, &mp, &ml);
+  *max_probes = mp;
+  *max_list = ml;
+  return RAILS_OK;
+}
+
+size_t rails_ivf_search_workspace_bytes(const rails_mol_shape* s, int32_t batch, int32_t nlist, int32_t nprobe, int32_t max_probes, int32_t max_list,
+                                        int32_t k_per_group) {
+  if (!shape_ok(s) || batch <= 0 || ivf_search_check(*s, nlist, nprobe, max_probes, max_list, k_per_group, INT64_MAX) != kOk) return 0;
+  return ivf_search_workspace_bytes(*s, batch, nlist, nprobe, max_probes, max_list, k_per_group);
+}
+
+int rails_ivf_search(const rails_mol_shape* s, const float* eq, int32_t batch, const float* centroids, const void* vectors, const int32_t* positions,
+                     const int32_t* offsets, int64_t n_items, int32_t nlist, int32_t nprobe, int32_t max_probes, int32_t max_list, int32_t k_per_group,
+                     void* workspace, size_t workspace_bytes, int64_t* out_positions, int32_t* unfilled, void* stream) {
+  g_err[0] = '\0';
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  if (batch < 0) { set_error("ivf_search: negative batch"); return RAILS_EINVAL; }
+  const int c = ivf_search_check(*s, nlist, nprobe, max_probes, max_list, k_per_group, n_items);
+  if (c != kOk) return c;
+  if (batch == 0) return RAILS_OK;
+  if (!eq || !centroids || !vectors || !positions || !offsets || !workspace || !out_positions) { set_error("ivf_search: NULL pointer"); return RAILS_EINVAL; }
+  return fail(ivf_search(*s, eq, batch, centroids, vectors, positions, offsets, n_items, nlist, nprobe, max_probes, max_list, k_per_group, workspace,
+                         workspace_bytes, out_positions, unfilled, (hipStream_t)stream), "ivf_search");
 }
 
 }  // extern "C"

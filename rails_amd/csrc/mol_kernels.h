@@ -175,6 +175,22 @@ int rerank_topk_filtered(const float* scores, int64_t ld, int rows, int n_cand, 
                          const int64_t* invalid, int width, int k, void* ws, size_t ws_bytes, int64_t* out_ids, float* out_scores, int32_t* flag,
                          hipStream_t stream);
 
+// ---- IVF-Flat index over the item components (ivf.hip) ----
+int ivf_check(const Shape& s, int64_t n, int nlist, bool from_index);
+int ivf_components16(const Shape& s, const float* ipack, int64_t n, void* table, int64_t n_total, int64_t first, hipStream_t st);
+size_t ivf_build_workspace_bytes(const Shape& s, int64_t n, int nlist, int S);
+int ivf_train(const Shape& s, const float* ipack, const void* comp16, int64_t n, const int32_t* sample_pos, int S, int nlist, int iters, int init, float* cent,
+              void* ws, size_t ws_bytes, hipStream_t st);
+int ivf_assign(const Shape& s, const float* ipack, const void* comp16, int64_t n, int nlist, const float* cent, int32_t* assign, hipStream_t st);
+int ivf_build_lists(const Shape& s, const float* ipack, const void* comp16, int64_t n, int nlist, const float* cent, void* vectors, int32_t* positions, int32_t* offsets,
+                    void* ws, size_t ws_bytes, hipStream_t st);
+int ivf_search_check(const Shape& s, int nlist, int nprobe, int max_probes, int max_list, int k, int64_t n);
+size_t ivf_search_workspace_bytes(const Shape& s, int B, int nlist, int nprobe, int max_probes, int max_list, int k);
+int ivf_search(const Shape& s, const float* eq, int B, const float* cent, const void* vectors, const int32_t* positions, const int32_t* offsets,
+               int64_t n, int nlist, int nprobe, int max_probes, int max_list, int k, void* ws, size_t ws_bytes, int64_t* out, int32_t* unfilled,
+               hipStream_t st);
+void ivf_plan(const int32_t* offsets, int G, int nlist, int nprobe, int k, int* max_probes, int* max_list);
+
 int hash_item_table(unsigned long long seed, int64_t first_item, int64_t n_items, int dim, float scale, float* out, hipStream_t stream);
 int mips_pack_items(const float* items, int64_t n, int D, float* out, hipStream_t stream);
 int mips_score(const float* q, int B, int D, const float* ifrag, int64_t n, float* qfrag_ws, float* logits, int64_t ld,

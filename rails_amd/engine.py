@@ -628,6 +628,133 @@ class MolEngine:
         return int(self.lib.rails_mol_component_topk_capacity(C.byref(self.shape), int(batch), int(n), int(k_group)))
 
 
+class IvfIndex:
+    """IVF-Flat index over the item components (include/rails_amd.h rails_ivf_*): one index per item group, trained by spherical Lloyd
+    k-means on a seeded sample of the fp16-rounded components and searched in three launches -- the native counterpart of the FAISS
+    branch of MoLNaiveTopK (reference rails/indexing/mol_top_k.py:176-239).  Where the probed lists hold fewer than k_per_group items the
+    search goes on into further lists in centroid-score order (FAISS returns -1 there)."""
+
+    COMPONENT_CHUNK = 1 << 20     # items per temporary fp32-format index chunk where the engine's own index is in a split-f16 format
+
+    def __init__(self, engine: MolEngine, index: MolIndex, nlist: int = 100, nprobe: int = 1, iters: int = 10, seed: int = 1234,
+                 items: Optional[torch.Tensor] = None):
+        """items: the raw (N, D) item embeddings; needed only where `engine` is not an fp32 engine: the fp16 components are then cut from
+        temporary fp32-format index chunks of COMPONENT_CHUNK items (the same values as the fp32 engine's), as the component table is."""
+        self.lib = engine.lib
+        spec = engine.spec
+        self.groups, self.d = spec.item_dot_product_groups, spec.dot_product_dimension
+        self.query_groups = spec.query_dot_product_groups
+        self.n_items, self.nlist = index.n_items, int(nlist)
+        if self.nlist < 1 or self.nlist > 4096:
+            raise NotImplementedError(f"IvfIndex: nlist = {self.nlist} outside [1, 4096]")
+        self._nprobe = int(nprobe)
+        self._check_nprobe(self._nprobe)
+        shape = self._shape = engine._fp32_shape
+        n, dev = self.n_items, index.buf.device
+        if n < self.nlist:
+            raise ValueError(f"IvfIndex: {n} items cannot fill nlist = {self.nlist} lists")
+        G, d = self.groups, self.d
+        src_index, comp16 = index.buf, None
+        if engine.precision != "fp32":
+            if items is None:
+                raise ValueError("IvfIndex: a non-fp32 engine needs the raw item embeddings to cut the fp32 components from")
+            items = _f32c(items)
+            comp16 = torch.empty((G, n, d), dtype=torch.float16, device=dev)
+            chunk = self.COMPONENT_CHUNK
+            tmp = torch.empty(self.lib.rails_mol_index_floats(C.byref(shape), min(chunk, n)), dtype=torch.float32, device=dev)
+            with _on_device(dev):
+                for lo in range(0, n, chunk):
+                    m = min(chunk, n - lo)
+                    _lib.check(self.lib.rails_mol_index_build(C.byref(shape), C.byref(engine.weights), _ptr(items[lo : lo + m]), m, _ptr(tmp), _stream()),
+                               "rails_mol_index_build")
+                    _lib.check(self.lib.rails_ivf_components16_build(C.byref(shape), _ptr(tmp), m, _ptr(comp16), n, lo, _stream()),
+                               "rails_ivf_components16_build")
+            del tmp
+            src_index = None
+        # the sample: a seeded permutation of the items, its first min(N, 256 nlist); the first nlist of it start the centroids
+        gen = torch.Generator().manual_seed(int(seed))
+        n_sample = min(n, 256 * self.nlist)
+        sample = torch.randperm(n, generator=gen)[:n_sample].to(torch.int32).to(dev)
+        self._centroids = torch.empty((G, self.nlist, d), dtype=torch.float32, device=dev)
+        self._vectors = torch.empty((G, n, d), dtype=torch.float16, device=dev)
+        self._positions = torch.empty((G, n), dtype=torch.int32, device=dev)
+        self._offsets = torch.empty((G, self.nlist + 1), dtype=torch.int32, device=dev)
+        ws = torch.empty(max(self.lib.rails_ivf_build_workspace_bytes(C.byref(shape), n, self.nlist, n_sample), 1), dtype=torch.uint8, device=dev)
+        with _on_device(dev):
+            _lib.check(self.lib.rails_ivf_train(C.byref(shape), _ptr(src_index), _ptr(comp16), n, _ptr(sample), n_sample, self.nlist, int(iters), 1,
+                                                _ptr(self._centroids), _ptr(ws), ws.numel(), _stream()), "rails_ivf_train")
+            _lib.check(self.lib.rails_ivf_build_lists(C.byref(shape), _ptr(src_index), _ptr(comp16), n, self.nlist, _ptr(self._centroids),
+                                                      _ptr(self._vectors), _ptr(self._positions), _ptr(self._offsets), _ptr(ws), ws.numel(), _stream()),
+                       "rails_ivf_build_lists")
+        del ws, comp16
+        self._offsets_host = self._offsets.cpu().contiguous()
+        self._plans: Dict[Tuple[int, int], Tuple[int, int]] = {}
+        self._ws: Optional[torch.Tensor] = None
+        self._unfilled = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    # read-only views of the index (tests and tools)
+    centroids = property(lambda self: self._centroids, doc="(P_X, nlist, d) fp32 unit-norm centroids")
+    vectors = property(lambda self: self._vectors, doc="(P_X, N, d) fp16 components in list order")
+    positions = property(lambda self: self._positions, doc="(P_X, N) int32 item positions alongside `vectors`")
+    offsets = property(lambda self: self._offsets, doc="(P_X, nlist + 1) int32 list starts")
+    nprobe = property(lambda self: self._nprobe, doc="lists probed per query component when search() is not told otherwise")
+
+    def _check_nprobe(self, nprobe: int) -> None:
+        if nprobe < 1 or nprobe > min(64, self.nlist):
+            raise NotImplementedError(f"IvfIndex: nprobe = {nprobe} outside [1, min(64, nlist = {self.nlist})]")
+
+    def _plan(self, nprobe: int, k: int) -> Tuple[int, int]:
+        key = (nprobe, k)
+        p = self._plans.get(key)
+        if p is None:
+            mp, ml = C.c_int32(0), C.c_int32(0)
+            _lib.check(self.lib.rails_ivf_plan(C.byref(self._shape), C.c_void_p(self._offsets_host.data_ptr()), self.nlist, nprobe, k,
+                                               C.byref(mp), C.byref(ml)), "rails_ivf_plan")
+            p = self._plans[key] = (mp.value, ml.value)
+        return p
+
+    def search(self, eq: torch.Tensor, k_per_group: int, nprobe: Optional[int] = None, out: Optional[torch.Tensor] = None,
+               check: bool = False) -> torch.Tensor:
+        """eq (B, P_Q, d) fp32 query components -> (B, P_Q * P_X * k_per_group) int64 item positions, row-major over (query group,
+        item group, rank) as MoLNaiveTopK's exhaustive candidates.  check: wait for the call and raise if some row found fewer than
+        k_per_group items (which the probe plan rules out)."""
+        nprobe = self._nprobe if nprobe is None else int(nprobe)
+        self._check_nprobe(nprobe)
+        k = int(k_per_group)
+        if k < 1 or k > 128:
+            raise NotImplementedError(f"IvfIndex: k_per_group = {k} outside [1, 128]")
+        if k > self.n_items:
+            raise RuntimeError(f"selected index k out of range (k={k}, n={self.n_items})")
+        if eq.dim() != 3 or eq.shape[1] != self.query_groups or eq.shape[2] != self.d:
+            raise ValueError(f"IvfIndex.search: eq must be (B, {self.query_groups}, {self.d}), got {tuple(eq.shape)}")
+        B = eq.shape[0]
+        dev = self._centroids.device
+        if eq.device != dev:
+            raise ValueError(f"IvfIndex.search: eq is on {eq.device}, the index on {dev}")
+        eq = _f32c(eq)
+        max_probes, max_list = self._plan(nprobe, k)
+        ws_bytes = self.lib.rails_ivf_search_workspace_bytes(C.byref(self._shape), max(B, 1), self.nlist, nprobe, max_probes, max_list, k)
+        if ws_bytes == 0:
+            raise NotImplementedError(f"rails_ivf_search_workspace_bytes: {_lib.last_error()}")
+        if self._ws is None or self._ws.numel() < ws_bytes:
+            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        shape_out = (B, self.query_groups * self.groups * k)
+        if out is None:
+            out = torch.empty(shape_out, dtype=torch.int64, device=dev)
+        elif tuple(out.shape) != shape_out or out.dtype != torch.int64 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"IvfIndex.search: out must be a contiguous int64 {shape_out} tensor on {dev}")
+        with _on_device(dev):
+            _lib.check(self.lib.rails_ivf_search(C.byref(self._shape), _ptr(eq), B, _ptr(self._centroids), _ptr(self._vectors), _ptr(self._positions),
+                                                 _ptr(self._offsets), self.n_items, self.nlist, nprobe, max_probes, max_list, k, _ptr(self._ws),
+                                                 self._ws.numel(), _ptr(out), _ptr(self._unfilled), _stream()), "rails_ivf_search")
+        if check and B > 0 and int(self._unfilled.item()) != 0:
+            raise RuntimeError("IvfIndex.search: some row found fewer than k_per_group items")
+        return out
+
+    def list_sizes(self) -> torch.Tensor:
+        """(P_X, nlist) int64 list sizes (host)."""
+        return (self._offsets_host[:, 1:] - self._offsets_host[:, :-1]).to(torch.int64)
+
 def sort_rows(idx: torch.Tensor) -> torch.Tensor:
     """Ascending sort of every row of an int64 (rows, n) tensor, n <= 16384 (torch.sort(dim=1) values)."""
     lib = _lib.load()
