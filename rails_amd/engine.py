@@ -397,6 +397,13 @@ class MolEngine:
                                                               _ptr(out_other), _stream()), "rails_mol_query_prologue_both")
         return out, out_other
 
+    def gate_rows(self, qpack: torch.Tensor, batch: int) -> torch.Tensor:
+        """The batch's gq' rows (batch * num_logits floats) inside an fp32 query pack: they sit behind the Eq fragments, which take
+        32 * d floats per block of 32 / P_Q queries (the verdict kernels check the bound's gate guard on them)."""
+        s = self.spec
+        off = (batch + 32 // s.query_dot_product_groups - 1) // (32 // s.query_dot_product_groups) * 32 * s.dot_product_dimension
+        return qpack[off : off + batch * s.num_logits]
+
     # ---- scoring ------------------------------------------------------------------------------
     def score_dense(self, qpack: torch.Tensor, batch: int, index: MolIndex, out: Optional[torch.Tensor] = None,
                     run_if: Optional[torch.Tensor] = None) -> torch.Tensor:

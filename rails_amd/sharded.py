@@ -93,29 +93,45 @@ class ShardedTopK(TopKModule):
             local_topk = lambda q, k, **kw: self._local_module(q, k=k, **kw)  # noqa: E731
             self._local_topk_is_module = True
         else:
+            self._local_module = None
             self._n_local = int(item_ids_shard.numel())
             self._local_topk_is_module = False
         self._local_topk = local_topk
         self._merge = merge if merge is not None else _hip_merge
-        self._xstream = None     # exchange stream (all-gather + merge), created on first GPU use
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         with self._inline():     # a plain call has no neighbouring batch to overlap with (MoLAvgTopK.submit)
             return self.result(self.submit(query_embeddings, k, sorted, **kwargs))
 
+    # The exchange (all-gather + merge) runs on the caller's stream.  On a second stream, concurrently with the next batch's scoring, it was
+    # measured through the real module in a one-rank nccl group (tools/r06_shard_rccl_probe.py, 8-way shard, profiles/r06_shard_rccl_probe.txt):
+    # the two stream hand-overs per step cost more than the overlap gains (0.474 against 0.455 ms for the plain call); with everything on the
+    # caller's stream, submit / result two batches ahead keeps the device queue full across the host's look at the verdict with no hand-over.
     _plain_call = False
-    EXCHANGE_STREAM = False    # True: submit / result run the exchange (all-gather + merge) on a second stream, concurrently with the next batch's
-                               # scoring.  Measured through the real module in a one-rank nccl group (tools/r06_shard_rccl_probe.py, 8-way shard):
-                               # the two stream hand-overs per step cost more than the overlap gains (0.474 against 0.455 ms for the plain call); with
-                               # everything on the caller's stream, submit / result two batches ahead keeps the device queue full across the host's look
-                               # at the verdict with no hand-over at all.
+
+    def _join_submit(self, device, ready) -> None:
+        """result() of an explicit submit() may be called on another stream than the one submit() ran on: wait for its event there
+        (a plain call's exchange follows on the very stream of its submit)."""
+        if not self._plain_call and ready is not None:
+            torch.cuda.current_stream(device).wait_event(ready)
+
+    def _all_gather_rows(self, msg: torch.Tensor) -> torch.Tensor:
+        """(B, W) -> (world * B, W), rank-major: concatenated along dim 0, the layout both RCCL and gloo accept for all_gather_into_tensor.
+        Device tensors on a gloo group (test setups only) are staged through the host."""
+        if msg.is_cuda and dist.get_backend(self._group) == "gloo":
+            host = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype)
+            dist.all_gather_into_tensor(host, msg.cpu(), group=self._group)
+            return host.to(msg.device)
+        out = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype, device=msg.device)
+        dist.all_gather_into_tensor(out, msg, group=self._group)
+        return out
 
     @contextlib.contextmanager
     def _inline(self):
         """A plain forward / forward_filtered: there is no neighbouring batch to overlap with, so the local module stays on the caller's stream
         (MoLAvgTopK.inline_calls) and so does the exchange -- every hand-over between streams is an event the GPU waits 5-12 us for (round 6:
         two of them per step on an 8-way shard's 0.44 ms)."""
-        local = getattr(self, "_local_module", None)
+        local = self._local_module
         saved = self._plain_call
         self._plain_call = True
         try:
@@ -133,7 +149,7 @@ class ShardedTopK(TopKModule):
         if k > self._n_total:
             raise RuntimeError(f"selected index k out of range (k={k}, n={self._n_total})")
         k_local = min(k, self._n_local)
-        local = getattr(self, "_local_module", None)
+        local = self._local_module
         spec = None   # a local module with its own submit / result (MoLAvgTopK): its speculative output travels on, verified in result()
         if k_local > 0 and local is not None and hasattr(local, "submit") and self._local_topk_is_module:
             spec = local.submit(query_embeddings, k_local, **kwargs)
@@ -165,7 +181,7 @@ class ShardedTopK(TopKModule):
         (rails_merge_candidates_filtered) -> (top_k_ids (B, k), top_k_scores (B, k)), or None when the sizes are outside the fused path
         or the merge is not the HIP one (the caller then composes forward + filter_seen_ids: same bits)."""
         if not self._exchange:
-            local = getattr(self, "_local_module", None)
+            local = self._local_module
             return local.forward_filtered(query_embeddings, k_prime, invalid_ids, k, **kwargs) if hasattr(local, "forward_filtered") else None
         if not (query_embeddings.is_cuda and self._merge is _hip_merge and E.merge_filter_fusable(k_prime, invalid_ids.shape[1], k)) or k_prime > self._n_total:
             return None
@@ -194,46 +210,20 @@ class ShardedTopK(TopKModule):
         if seen is not None and not (msg.is_cuda and on_gpu):
             raise RuntimeError("result(seen=...) needs the HIP merge")
         if not msg.is_cuda:
-            gathered = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype)
-            dist.all_gather_into_tensor(gathered, msg, group=self._group)
+            gathered = self._all_gather_rows(msg)
             all_s, all_ids = unpack_candidates(gathered.view(self._world, msg.shape[0], msg.shape[1]), k)
             ms, mi = self._merge(all_s, all_ids, k)
             return ms.to(dtype), mi
-        cur = torch.cuda.current_stream(msg.device)
-        plain = self._plain_call or not self.EXCHANGE_STREAM
-        if plain:
-            side = cur
-            if not self._plain_call and ready is not None:
-                cur.wait_event(ready)      # submit() may have run on another stream than the one result() is called on
+        self._join_submit(msg.device, ready)
+        gathered = self._all_gather_rows(msg)
+        if on_gpu and seen is not None:   # one kernel: rank-major candidates -> exact top-k -> seen-id filter
+            mi, ms = E.merge_candidates_filtered(gathered, self._world, k, k, seen[0], seen[1])
+        elif on_gpu:   # one kernel: rank-major candidates -> exact top-k (scores, ids)
+            ms, mi = E.merge_candidates(gathered, self._world, k, k)
         else:
-            if self._xstream is None:
-                self._xstream = torch.cuda.Stream(msg.device)
-            side = self._xstream
-            side.wait_event(ready)
-            msg.record_stream(side)
-        with (contextlib.nullcontext() if plain else torch.cuda.stream(side)):
-            # concatenated-along-dim-0 output: the layout both RCCL and gloo accept for all_gather_into_tensor
-            if dist.get_backend(self._group) == "gloo":   # test setups only: stage through the host
-                host = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype)
-                dist.all_gather_into_tensor(host, msg.cpu(), group=self._group)
-                gathered = host.to(msg.device)
-            else:
-                gathered = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype, device=msg.device)
-                dist.all_gather_into_tensor(gathered, msg, group=self._group)
-            if on_gpu and seen is not None:   # one kernel: rank-major candidates -> exact top-k -> seen-id filter
-                mi, ms = E.merge_candidates_filtered(gathered, self._world, k, k, seen[0], seen[1])
-                if not plain:
-                    seen[0].record_stream(side)
-            elif on_gpu:   # one kernel: rank-major candidates -> exact top-k (scores, ids)
-                ms, mi = E.merge_candidates(gathered, self._world, k, k)
-            else:
-                all_s, all_ids = unpack_candidates(gathered.view(self._world, msg.shape[0], msg.shape[1]), k)
-                ms, mi = self._merge(all_s, all_ids, k)
-            ms = ms.to(dtype)
-        if not plain:
-            cur.wait_stream(side)
-            ms.record_stream(cur)
-            mi.record_stream(cur)
+            all_s, all_ids = unpack_candidates(gathered.view(self._world, msg.shape[0], msg.shape[1]), k)
+            ms, mi = self._merge(all_s, all_ids, k)
+        ms = ms.to(dtype)
         if seen is not None:
             return mi, ms
         return ms, mi
@@ -269,6 +259,29 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
     PAD_DECAY_CALLS = 64          # after this many consecutive proved calls a doubled candidate margin is halved again
     VERDICT_TIMEOUT_S = 120.0
 
+    def __init__(self, *args, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self._gp_collectives = 0      # all-gathers of the global proof issued so far (exchange_info)
+        self._gp_reset(None, None)
+
+    def _gp_reset(self, eng, device) -> None:
+        """The whole state of the global proof, for one binding of the local module (eng None: not decided yet, no device buffers)."""
+        self._gp_engine = eng
+        self._gp_on = False
+        self._gp_eps: Optional[float] = None
+        self._gp_guard_limit: Optional[float] = None
+        self._gp_state = self._gp_host = self._gp_host_f = self._gp_host_i = self._gp_call = None
+        if eng is not None:
+            self._gp_state = torch.zeros(8, dtype=torch.float32, device=device)
+            self._gp_host = torch.zeros(8, dtype=torch.float32).pin_memory()
+            self._gp_host_f = self._gp_host.numpy()                         # views of the same pinned words: a poll is a plain memory read,
+            self._gp_host_i = self._gp_host.view(torch.int32).numpy()       # not a tensor index + conversion (2-3 us each, between the batches)
+            self._gp_call = torch.zeros(8 + 4 * 256, dtype=torch.int32, device=device)      # arrival counter + one 16-byte word per row
+        self._gp_issued = 0           # verdicts enqueued so far (the host mirror's call counter reaches it when the last one has landed)
+        self._gp_pad = 1
+        self._gp_streak = 0
+        self._gp_stats = {"calls": 0, "fallbacks": 0, "proved_calls": 0, "bound_violations": 0}
+
     def _make_local_module(self, mol_module, item_embeddings_shard, item_ids_shard) -> TopKModule:
         # the size-dependent choices of the proved flow (one eps or per-pair bounds, candidate margins) are made for the SHARD size every rank
         # computes alike -- the last shard may be shorter, and ranks must agree on the form of the bound
@@ -283,62 +296,37 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
         dist.all_reduce(t, op=op, group=self._group)
         return t
 
-    def _all_gather_rows(self, msg: torch.Tensor) -> torch.Tensor:
-        self._gp_collectives = getattr(self, "_gp_collectives", 0) + 1
-        if msg.is_cuda and dist.get_backend(self._group) == "gloo":
-            host = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype)
-            dist.all_gather_into_tensor(host, msg.cpu(), group=self._group)
-            return host.to(msg.device)
-        out = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype, device=msg.device)
-        dist.all_gather_into_tensor(out, msg, group=self._group)
-        return out
-
     def _global_proof(self, query_embeddings: torch.Tensor) -> bool:
         """Decided collectively, once per binding of the local module (all ranks reach this at the same call)."""
-        local = getattr(self, "_local_module", None)
+        local = self._local_module
         if not (self.GLOBAL_PROOF and self._exchange and dist.is_initialized() and isinstance(local, MoLBruteForceTopK) and self._local_topk_is_module
                 and self._merge is _hip_merge and query_embeddings.is_cuda):
             return False
         eng = local._bind()
-        if getattr(self, "_gp_engine", None) is not eng:
+        if self._gp_engine is not eng:
             from . import f16x3_bound as FB
 
             mine = local.shard_can_speculate()
             flags = torch.tensor([1.0 if mine else 0.0, -(local._gi_abs_max() if mine else 0.0)], dtype=torch.float32, device=query_embeddings.device)
             flags = self._all_reduce(flags, dist.ReduceOp.MIN)          # min of the flags, max of max |gi| (negated)
+            self._gp_reset(eng, query_embeddings.device)
             self._gp_on = bool(flags[0].item() > 0.5)
             gi_max = -float(flags[1].item())
             self._gp_guard_limit = min(FB.GATE_GUARD / gi_max, 3.0e38) if gi_max > 0.0 else 3.0e38
-            self._gp_engine = eng
             self._gp_eps = local._proved_eps() if self._gp_on else None
-            self._gp_state = torch.zeros(8, dtype=torch.float32, device=query_embeddings.device)
-            self._gp_host = torch.zeros(8, dtype=torch.float32).pin_memory()
-            self._gp_host_f = self._gp_host.numpy()                         # views of the same pinned words: a poll is a plain memory read,
-            self._gp_host_i = self._gp_host.view(torch.int32).numpy()       # not a tensor index + conversion (2-3 us each, between the batches)
-            self._gp_call = torch.zeros(8 + 4 * 256, dtype=torch.int32, device=query_embeddings.device)      # arrival counter + one 16-byte word per row
-            self._gp_issued = 0           # verdicts enqueued so far (the host mirror's call counter reaches it when the last one has landed)
-            self._gp_pad = 1
-            self._gp_streak = 0
-            self._gp_stats = {"calls": 0, "fallbacks": 0, "proved_calls": 0, "bound_violations": 0}
         return self._gp_on
 
     def stats(self) -> dict:
         """Counters of the global proof (calls, proved_calls, fallbacks, bound_violations, kc per rank) merged over the local module's."""
         local = self._local_module
         out = local.stats()
-        if getattr(self, "_gp_on", False):
+        if self._gp_on:
             out.update(self._gp_stats)
             out["global_proof"] = True
         return out
 
     def _kc_local(self, k: int) -> int:
-        upper = self._local_module._upper_poly() is not None       # per-pair upper bounds: more items can reach the k-th score (topk_modules._forward_rescored)
-        floor, per_k = self._local_module._per_pair_pad() if upper else MoLBruteForceTopK.PAD_ONE_EPS
-        total = k + max(floor, per_k * k) * self._gp_pad
-        per = -(-total // self._world)
-        kc = per + int(4.0 * per ** 0.5) + 32
-        kc = (kc + E.TILE_ITEMS - 1) // E.TILE_ITEMS * E.TILE_ITEMS
-        return max(1, min(kc, 16384, self._n_local))
+        return self._local_module.shard_candidate_count(k, self._gp_pad, self._world)
 
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
         B = query_embeddings.size(0)
@@ -367,41 +355,20 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
         local = self._local_module
         sp = local._engine.spec
         B = query_embeddings.size(0)
-        off = (B + 32 // sp.query_dot_product_groups - 1) // (32 // sp.query_dot_product_groups) * 32 * sp.dot_product_dimension
-        gq = qpack32[off : off + B * sp.num_logits]
-        cur = torch.cuda.current_stream(msg.device)
-        plain = self._plain_call or not self.EXCHANGE_STREAM          # the exchange stays on the caller's stream (always for a plain call: _inline)
-        if plain:
-            side = cur
-            if not self._plain_call and ready is not None:
-                cur.wait_event(ready)      # submit() may have run on another stream than the one result() is called on
-        else:
-            if self._xstream is None:
-                self._xstream = torch.cuda.Stream(msg.device)
-            side = self._xstream
-            side.wait_event(ready)
-            for t in (msg, qpack32):
-                t.record_stream(side)
+        gq = local._engine.gate_rows(qpack32, B)
+        self._join_submit(msg.device, ready)
         fuse = seen is not None and E.merge_filter_fusable(k, seen[0].shape[1], seen[1])
         if self._gp_call.numel() < 8 + 4 * B:
             self._gp_call = torch.zeros(8 + 4 * B, dtype=torch.int32, device=msg.device)
-        with (contextlib.nullcontext() if plain else torch.cuda.stream(side)):
-            # ONE exchange: the (B, 2k + 2) messages carry every rank's top-k, the best first-pass score it left outside its candidates and the
-            # largest |fp32 - first pass| it saw; merge, verdict and the seen-id filter are one launch behind it
-            gathered = self._all_gather_rows(msg)
-            if fuse and not plain:
-                seen[0].record_stream(side)
-            out = E.merge_candidates_verdict(gathered, self._world, k, k, self._gp_eps, 1.0, gq, sp.num_logits, self._gp_guard_limit, self._gp_state,
-                                             self._gp_host, self._gp_call, seen if fuse else None)
-            if seen is not None and not fuse:
-                if not plain:
-                    seen[0].record_stream(side)
-                out = E.filter_seen_ids(out[1], out[0], seen[0], seen[1])
+        # ONE exchange: the (B, 2k + 2) messages carry every rank's top-k, the best first-pass score it left outside its candidates and the
+        # largest |fp32 - first pass| it saw; merge, verdict and the seen-id filter are one launch behind it
+        gathered = self._all_gather_rows(msg)
+        self._gp_collectives += 1
+        out = E.merge_candidates_verdict(gathered, self._world, k, k, self._gp_eps, 1.0, gq, sp.num_logits, self._gp_guard_limit, self._gp_state,
+                                         self._gp_host, self._gp_call, seen if fuse else None)
+        if seen is not None and not fuse:
+            out = E.filter_seen_ids(out[1], out[0], seen[0], seen[1])
         self._gp_issued += 1
-        if not plain:
-            cur.wait_stream(side)
-            out[0].record_stream(cur)
-            out[1].record_stream(cur)
         # Every rank computes the verdict from the same gathered bytes, so all of them raise or clear REDO alike; the host reads it from the pinned
         # mirror the merge kernel writes (with submit / result pipelining batch i + 1 is already enqueued: the device does not idle) and only a
         # failed verdict -- crowded scores, a skewed shard, a violated guard -- costs more: the dense fp32 kernels over the shards and their
@@ -459,7 +426,7 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
     def exchange_info(self) -> dict:
         info = super().exchange_info()
         info["collectives_per_proved_step"] = 1
-        info["collectives_issued"] = getattr(self, "_gp_collectives", 0)
+        info["collectives_issued"] = self._gp_collectives
         return info
 
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
@@ -502,16 +469,6 @@ class ShardedMoLAvgTopK(ShardedTopK):
     def _make_local_module(self, mol_module, item_embeddings_shard, item_ids_shard) -> TopKModule:
         return MoLAvgTopK(mol_module, item_embeddings_shard, item_ids_shard, avg_top_k=min(self._avg_top_k, int(item_ids_shard.numel())))
 
-    def _gather(self, msg: torch.Tensor) -> torch.Tensor:
-        """(B, W) -> (world * B, W), rank-major (host-staged only for device tensors on a gloo group: test setups)."""
-        if msg.is_cuda and dist.get_backend(self._group) == "gloo":
-            host = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype)
-            dist.all_gather_into_tensor(host, msg.cpu(), group=self._group)
-            return host.to(msg.device)
-        out = torch.empty((self._world * msg.shape[0], msg.shape[1]), dtype=msg.dtype, device=msg.device)
-        dist.all_gather_into_tensor(out, msg, group=self._group)
-        return out
-
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
         if k_prime > self._avg_top_k or (self._global and self._exchange):
             return None   # forward's own checks / the global-K' exchange: the caller composes forward + filter_seen_ids
@@ -536,7 +493,7 @@ class ShardedMoLAvgTopK(ShardedTopK):
             cpos = torch.empty((B, 0), dtype=torch.int64, device=dev)
         on_gpu = cs.is_cuda and self._merge is _hip_merge
         msg = E.pack_candidates(cs, cpos, K) if on_gpu else pack_candidates(cs.float(), cpos, K)
-        gathered = self._gather(msg)
+        gathered = self._all_gather_rows(msg)
         # (2) the global coarse top-K' (same total order on every rank: score desc, global position asc)
         if on_gpu and self._world * K <= 16384:   # one kernel (its lists are sorted in LDS)
             _, gpos = E.merge_candidates(gathered, self._world, K, K)
@@ -555,7 +512,7 @@ class ShardedMoLAvgTopK(ShardedTopK):
             s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
             ids = torch.full((B, k), -1, dtype=torch.int64, device=dev)
         msg2 = E.pack_candidates(s, ids, k) if on_gpu else pack_candidates(s.float(), ids, k)
-        gathered2 = self._gather(msg2)
+        gathered2 = self._all_gather_rows(msg2)
         if on_gpu:
             ms, mi = E.merge_candidates(gathered2, self._world, k, k)
         else:

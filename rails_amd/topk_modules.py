@@ -14,7 +14,7 @@ fused scoring -> exact top-k -> id gather, all HIP.
 from __future__ import annotations
 
 import abc
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import math
 
@@ -60,6 +60,8 @@ class MoLTopKModule(TopKModule):
         self._call_eng: Optional[E.MolEngine] = None
         self._index: Optional[E.MolIndex] = None
         self._scratch: Dict[tuple, torch.Tensor] = {}   # internal buffers recycled across calls (never returned)
+        self._no_fused = False        # True: the fused scans are off (the redo of a call whose scan verdict failed; tests)
+        self._flag_free: list = []    # pinned verdict words ready for reuse (_pinned_word)
         self._bind()
 
     def _buf(self, tag: str, numel: int, dtype: torch.dtype) -> torch.Tensor:
@@ -110,29 +112,53 @@ class MoLTopKModule(TopKModule):
         qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"))
         return eng.score_dense(qpack, query_embeddings.size(0), self._index)
 
-    def _all_logits_scratch(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
-        """Same, into recycled internal buffers (the result is consumed by the top-k before the next call)."""
-        eng = self._bind()
+    def _all_logits_scratch(self, query_embeddings: torch.Tensor, _eng=None, _index=None, _tag: str = "qpack", _private: bool = False, **kwargs) -> torch.Tensor:
+        """Same, into recycled internal buffers (the result is consumed by the top-k before the next call).  _eng / _index: another engine
+        over its own index (the fp32 companion of the exact modes; its pack has its own `_tag`); _private: fresh buffers (the audit's side
+        stream must not share the scratch of the call it checks)."""
+        eng = _eng if _eng is not None else self._bind()
+        index = _index if _index is not None else self._index
         B = query_embeddings.size(0)
-        n_q = eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), B)
-        qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), out=self._buf("qpack", n_q, torch.float32))
-        logits = self._buf("logits", B * self._index.n_items, torch.float32).view(B, self._index.n_items)
-        return eng.score_dense(qpack, B, self._index, out=logits)
+        pack = logits = None
+        if not _private:
+            pack = self._buf(_tag, eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), B), torch.float32)
+            logits = self._buf("logits", B * index.n_items, torch.float32).view(B, index.n_items)
+        qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), out=pack)
+        return eng.score_dense(qpack, B, index, out=logits)
 
+    def _dense_topk(self, query_embeddings: torch.Tensor, k: int, seen=None, sorted: bool = True, _private: bool = False, **kwargs):
+        """Dense fp32 logits into scratch (_all_logits_scratch and its options) + exact top-k -> (scores, ids); with seen = (invalid_ids, k_out)
+        the seen-id filter runs inside the selection launch (rails_topk_filtered) -> (ids (B, k_out), scores (B, k_out))."""
+        logits = self._all_logits_scratch(query_embeddings, _private=_private, **kwargs)
+        ws = None if _private else self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(logits.shape[0], logits.shape[1], k), torch.uint8)
+        if seen is not None:
+            ids, scores = E.topk_filtered(logits, k, self._ids_flat, seen[0], seen[1], workspace=ws)
+            return ids, scores.to(query_embeddings.dtype)
+        scores, ids = E.topk(logits, k, ids=self._ids_flat, sorted=sorted, workspace=ws)
+        return scores.to(query_embeddings.dtype), ids
 
-    def _score_at(self, eng, qpack: torch.Tensor, batch: int, positions: torch.Tensor) -> torch.Tensor:
-        """(B, K) full-MoL logits of per-row candidates given as VALID positions of this module's index.  fp32 engines read the
-        candidates in place (rails_mol_score_indexed: no gathered copy, one launch; the same bits as gather + score_candidates);
-        the f16 builds, which have no indexed instantiation, gather a per-row index of the candidates first."""
+    @staticmethod
+    def _score_positions(eng, qpack: torch.Tensor, batch: int, index, rows, positions: torch.Tensor) -> torch.Tensor:
+        """(B, K) full-MoL logits of per-row candidates given as VALID positions of `index`, whichever way is cheapest -- same bits each way.
+        fp32 engines read the candidates in place (rails_mol_score_indexed: no gathered copy, one launch; the same bits as gather +
+        score_candidates): from `rows`, the row-major copy of the index, where there is one (a candidate's bytes in whole cache lines: half
+        the time of the tile-packed reads), else from the tile-packed index (any K: the kernel masks the ragged last tile); the f16 builds,
+        which have no indexed instantiation, gather a per-row index of the candidates first (the 256-logit team kernel).
+        rows: the copy, None, or a function of the engine that yields one of the two (asked only where the copy can be read)."""
         K = positions.shape[1]
         if eng.score_indexed_supported(batch, K):
-            rows = self._index_rows(eng)
-            if rows is not None:           # the row-major copy: a candidate's bytes in whole cache lines (half the time of the tile-packed reads; same bits)
-                return eng.score_indexed_rows(qpack, batch, rows, self._index.n_items, positions)
-            return eng.score_indexed(qpack, batch, self._index, positions)   # any K: the kernel masks the ragged last tile
-        cand, kp = eng.gather_index(self._index, positions)
+            if callable(rows):
+                rows = rows(eng)
+            if rows is not None:
+                return eng.score_indexed_rows(qpack, batch, rows, index.n_items, positions)
+            return eng.score_indexed(qpack, batch, index, positions)
+        cand, kp = eng.gather_index(index, positions)
         return eng.score_candidates(qpack, batch, cand, kp)[:, :K]
 
+    def _score_at(self, eng, qpack: torch.Tensor, batch: int, positions: torch.Tensor) -> torch.Tensor:
+        """_score_positions over this module's own index (the rerank of the approximate algorithms); the row-major copy is built at the
+        first call that can read it."""
+        return self._score_positions(eng, qpack, batch, self._index, self._index_rows, positions)
 
     RERANK_ROWS_COPY_MAX_BYTES = 8 << 30     # fp32 indexes up to this size get a row-major copy for the candidate re-scoring of the rerank paths (0: never)
     _rows_cache = None
@@ -151,6 +177,50 @@ class MoLTopKModule(TopKModule):
                 rows = eng.build_index_rows(self._index)
         self._rows_cache = (eng, self._index, rows)
         return rows
+
+
+class BoundPolicy(NamedTuple):
+    """How one MoLBruteForceTopK bounds |first pass - fp32| under one set of parameters: decided once per engine (MoLBruteForceTopK.bound_policy,
+    a pure function of the pair-gate weights, the shape, the policy corpus size and the library's shape queries), read by everything else.
+      base          the module's own engine the record belongs to (new parameters -> a new engine -> a new record)
+      proved        the default mode's choice for `base`: bind the split-f16 engine (_proved_applies) or stay dense; None: not decided
+      terms         f16x3_bound.first_pass_bound's breakdown, {"eps": inf} where a guard of the bound fails; None: not evaluated (yet)
+      kind          "eps"    one a-priori eps for every pair, where it is at most PROVED_MAX_EPS;
+                    "upper"  a per-pair bound, quadratic in the pair's largest |cross logit|, added to the first-pass logit by the kernel itself
+                             (f16x3_bound.upper_bound_poly, rails_mol_score_dense_upper): where one eps is too coarse, or the corpus is small,
+                             and the shape has the kernel;
+                    None     neither (infinite bound, or too coarse without the kernel): the module runs the dense fp32 kernels
+      poly          (ub2, ub1, ub0) when the engine's form is per-pair, else None
+      any_poly      the same polynomial when the shape has the UPPER build at all: calls for PER_PAIR_MIN_K results or more take it
+      eps_of_c      upper_bound_poly's samples of eps against the largest |cross logit| (reported by rigorous_eps)
+      eps           what the verdict compares with (with_guard): 0.0 under per-pair bounds, inf when the bound is; None: no a-priori bound in
+                    use (the one-product first pass, the dense modes)
+      guard_limit   GATE_GUARD / max |gi| over the corpus: the bound's one data-dependent hypothesis, checked per batch by the verdict"""
+
+    base: object = None
+    proved: Optional[bool] = None
+    terms: Optional[Dict[str, float]] = None
+    kind: Optional[str] = None
+    poly: Optional[Tuple[float, float, float]] = None
+    any_poly: Optional[Tuple[float, float, float]] = None
+    eps_of_c: Optional[Dict[str, float]] = None
+    eps: Optional[float] = None
+    guard_limit: Optional[float] = None
+
+    def with_guard(self, gi_abs_max: float) -> "BoundPolicy":
+        """The record with the verdict's eps and the guard limit filled in, given max |gi| over the corpus.  eps: the a-priori bound rounded UP
+        to a float32 (the verdict compares in fp32: gap = fl(e_k - m) > eps, one rounding of relative 2^-24 on a gap of at most 2 / tau --
+        covered by the 2^-16 relative slack added here); 0.0 where the first pass writes upper bounds of the fp32 logits (the verdict is
+        e_k > m itself -- strict: ties with an outsider are redone); inf when an item gate is not finite."""
+        from . import f16x3_bound as FB
+
+        if self.poly is not None:
+            eps = 0.0
+        else:
+            eps32 = torch.tensor(float(self.terms["eps"]) * (1.0 + 2.0 ** -16), dtype=torch.float32)
+            eps = float(torch.nextafter(eps32, torch.tensor(float("inf"))))
+        limit = min(FB.GATE_GUARD / gi_abs_max, 3.0e38) if gi_abs_max > 0.0 else 3.0e38
+        return self._replace(eps=eps if math.isfinite(gi_abs_max) else math.inf, guard_limit=limit)
 
 
 class MoLBruteForceTopK(MoLTopKModule):
@@ -182,7 +252,7 @@ class MoLBruteForceTopK(MoLTopKModule):
         self._state_direct = False    # True: the verdict state reaches the host through the finish kernel's own stores (no copy, no event)
         self._pause_left = 0
         self.exact_mode: str = exact_mode or self.EXACT_MODE
-        self._proved_choice = None    # (fp32 engine the choice was made for, precision to bind or None)
+        self._policy = BoundPolicy()  # the bound on |first pass - fp32| for the current parameters (one record per engine)
         self._gate_guard_limit: Optional[float] = None
         self._ok_event = None
         self._probe_n = -1
@@ -228,12 +298,15 @@ class MoLBruteForceTopK(MoLTopKModule):
     def _engine_for_bind(self) -> E.MolEngine:
         mol = self._mol_module
         base = mol.engine()
+        pol = self._policy
+        if pol.base is not base:      # new parameters (or another precision): nothing decided, nothing evaluated yet
+            pol = self._policy = BoundPolicy(base=base)
         if self.exact_mode != "proved" or base.precision != "fp32" or base.exact is not None:
             return base
-        if self._proved_choice is None or self._proved_choice[0] is not base:
-            self._proved_choice = (base, "f16x3-exact" if self._proved_applies(base) else None)
-        want = self._proved_choice[1]
-        return mol.engine(want, _params_as_checked=True) if want else base     # (the second look at the same parameters in the same breath)
+        if pol.proved is None:
+            ok = self._proved_applies(base)
+            pol = self._policy = self._policy._replace(proved=ok)
+        return mol.engine("f16x3-exact", _params_as_checked=True) if pol.proved else base     # (the second look at the same parameters in the same breath)
 
     def _proved_applies(self, base: E.MolEngine) -> bool:
         spec, N = base.spec, self._item_embeddings.shape[1]
@@ -241,7 +314,7 @@ class MoLBruteForceTopK(MoLTopKModule):
             return False
         if not base.lib.rails_mol_shape_supported(E.C.byref(spec.to_c("f16x3"))):
             return False
-        if self._bound_kind(spec, base.lib) is None:
+        if self._evaluated(spec, base.lib).kind is None:
             return False
         from . import arith_check
 
@@ -254,81 +327,91 @@ class MoLBruteForceTopK(MoLTopKModule):
         held = self._index.buf.numel() * 4 if self._index is not None else 0     # a rebind: the old index is dropped first
         return free + held > 2 * need + min(32 * N * 4, self.MAX_LOGIT_BYTES) + (1 << 30)
 
-    def _bound_from_weights(self, spec) -> Dict[str, float]:
-        """rails_amd/f16x3_bound.py for this module's pair-gate weights; {"eps": inf} where a guard of the bound fails."""
+    def _evaluated(self, spec, lib) -> BoundPolicy:
+        """The current record with the bound evaluated: f16x3_bound runs here, once per engine (float64 work on weight-sized tensors)."""
+        pol = self._policy
+        if pol.terms is None:
+            pol = self._policy = self.bound_policy(self._mol_module, spec, lib, self._policy_items())._replace(base=pol.base, proved=pol.proved)
+        return pol
+
+    @classmethod
+    def bound_policy(cls, mol_module, spec, lib, policy_items: int) -> BoundPolicy:
+        """rails_amd/f16x3_bound.py for this module's pair-gate weights and the form the proved flow takes from it (BoundPolicy.kind): a pure
+        function of the weights, the shape, `policy_items` and the library's query for the UPPER build -- no GPU."""
         from . import f16x3_bound as FB
 
-        if (not spec.dot_product_l2_norm or spec.gating_combination_type != "glu_silu" or spec.gating_qi_hidden_dim <= 0
-                or not (spec.gating_query_fn and spec.gating_item_fn)):
-            return {"eps": math.inf}
-        g = self._mol_module._gating_fn._qi_partial_module
-        lin = [m for m in g.modules() if isinstance(m, torch.nn.Linear)]
-        if len(lin) != 2:
-            return {"eps": math.inf}
-        zeros = lambda n: torch.zeros(n)
-        b1 = lin[0].bias if lin[0].bias is not None else zeros(lin[0].out_features)
-        b2 = lin[1].bias if lin[1].bias is not None else zeros(lin[1].out_features)
-        return FB.first_pass_bound(lin[0].weight, b1, lin[1].weight, b2, spec.temperature, spec.dot_product_dimension,
-                                   spec.query_dot_product_groups, spec.item_dot_product_groups)
+        terms, args = {"eps": math.inf}, None
+        if (spec.dot_product_l2_norm and spec.gating_combination_type == "glu_silu" and spec.gating_qi_hidden_dim > 0
+                and spec.gating_query_fn and spec.gating_item_fn):
+            lin = [m for m in mol_module._gating_fn._qi_partial_module.modules() if isinstance(m, torch.nn.Linear)]
+            if len(lin) == 2:
+                b1 = lin[0].bias if lin[0].bias is not None else torch.zeros(lin[0].out_features)
+                b2 = lin[1].bias if lin[1].bias is not None else torch.zeros(lin[1].out_features)
+                args = (lin[0].weight, b1, lin[1].weight, b2, spec.temperature, spec.dot_product_dimension, spec.query_dot_product_groups,
+                        spec.item_dot_product_groups)
+                terms = FB.first_pass_bound(*args)
+        eps = float(terms.get("eps", math.inf))
+        per_pair_ok = eps <= cls.PROVED_MAX_EPS_PER_PAIR and bool(lib.rails_mol_score_dense_upper_supported(E.C.byref(spec.to_c("f16x3"))))
+        if per_pair_ok and (eps > cls.PROVED_MAX_EPS or policy_items <= cls.PER_PAIR_MAX_ITEMS):
+            kind = "upper"
+        else:
+            kind = "eps" if eps <= cls.PROVED_MAX_EPS else None
+        poly = any_poly = eps_of_c = None
+        if kind is not None and per_pair_ok:
+            res = FB.upper_bound_poly(*args)
+            any_poly, eps_of_c = res["poly"], res.get("eps_of_c")
+            poly = any_poly if kind == "upper" else None
+        return BoundPolicy(terms=terms, kind=kind, poly=poly, any_poly=any_poly, eps_of_c=eps_of_c)
 
-    def _bound_kind(self, spec, lib) -> Optional[str]:
-        """How the proved flow bounds |first pass - fp32| for this shape and these weights:
-          "eps"    one a-priori eps for every pair (f16x3_bound.first_pass_bound), where it is at most PROVED_MAX_EPS;
-          "upper"  a per-pair bound, quadratic in the pair's largest |cross logit|, added to the first-pass logit by the kernel itself
-                   (f16x3_bound.upper_bound_poly, rails_mol_score_dense_upper): where one eps is too coarse and the shape has the kernel;
-          None     neither (infinite bound, or too coarse without the kernel): the module runs the dense fp32 kernels."""
-        eps = self._bound_from_weights(spec).get("eps", math.inf)
-        small = self._policy_items() <= self.PER_PAIR_MAX_ITEMS
-        if (eps > self.PROVED_MAX_EPS or small) and eps <= self.PROVED_MAX_EPS_PER_PAIR and lib.rails_mol_score_dense_upper_supported(E.C.byref(spec.to_c("f16x3"))):
-            return "upper"
-        if eps <= self.PROVED_MAX_EPS:
-            return "eps"
-        return None
+    def _bound_from_weights(self, spec) -> Dict[str, float]:
+        """The bound's term dictionary for this module's pair-gate weights; {"eps": inf} where a guard of the bound fails."""
+        return self._evaluated(spec, E._lib.load()).terms
 
     def _policy_items(self) -> int:
         """The corpus size the size-dependent choices of the proved flow are made for: this module's own, or -- set by the item-sharded wrapper,
         the same on every rank -- the shard size (ranks must agree on the form of the bound)."""
         return int(self.bound_kind_items or self._item_embeddings.shape[1])
 
-    def _per_pair_pad(self) -> Tuple[int, int]:
-        return self.PAD_PER_PAIR_SMALL if self._policy_items() <= self.PER_PAIR_MAX_ITEMS else self.PAD_PER_PAIR
+    @classmethod
+    def candidate_count(cls, k: int, per_pair: bool, policy_items: int, pad_scale: int = 1, world: Optional[int] = None,
+                        n_local: Optional[int] = None, single: bool = False) -> int:
+        """How many candidates per query a speculative call re-scores: k + a margin (PAD_ONE_EPS / PAD_PER_PAIR / PAD_PER_PAIR_SMALL by the form
+        of the bound and the policy corpus size, times `pad_scale`, which failed verdicts double), rounded up to whole tiles, at most 16 384.
+          world, n_local   the item-sharded proof: the candidates within eps of the GLOBAL k-th score spread evenly over the shards, so each of
+                           `world` ranks takes its share + 4 sqrt(share) + 32, at most its `n_local` items (rails_amd/sharded.py)
+          single           the one-product first pass, which has no a-priori bound (the monitored flow; per_pair and policy_items do not
+                           apply): k / 2 beyond k, at least 128; up to k = 384 at most 512 -- rails_topk's two-launch path ends there,
+                           beyond it a selection costs five reads of the logits"""
+        tile = E.TILE_ITEMS
+        if single:
+            kc = (k + max(128, k // 2) * pad_scale + tile - 1) // tile * tile
+            return min(kc, 512) if k <= 384 else kc
+        floor, per_k = cls.PAD_ONE_EPS if not per_pair else cls.PAD_PER_PAIR_SMALL if policy_items <= cls.PER_PAIR_MAX_ITEMS else cls.PAD_PER_PAIR
+        total = k + max(floor, per_k * k) * pad_scale
+        if world is None:
+            return min((total + tile - 1) // tile * tile, 16384)
+        if n_local is None:
+            raise ValueError("candidate_count: world needs n_local")
+        per = -(-total // world)
+        kc = per + int(4.0 * per ** 0.5) + 32
+        return max(1, min((kc + tile - 1) // tile * tile, 16384, n_local))
+
+    def shard_candidate_count(self, k: int, pad_scale: int, world: int) -> int:
+        """candidate_count for this module as one of `world` shards (the form of the bound and the margins follow the policy corpus size
+        every rank computes alike)."""
+        return self.candidate_count(k, self._policy.poly is not None, self._policy_items(), pad_scale, world=world, n_local=self.num_items)
 
     def _upper_poly(self, k: Optional[int] = None) -> Optional[Tuple[float, float, float]]:
-        """(ub2, ub1, ub0) when the bound engine's first pass writes per-pair UPPER BOUNDS of the fp32 logits (_bound_kind "upper"), else None.
+        """(ub2, ub1, ub0) when the bound engine's first pass writes per-pair UPPER BOUNDS of the fp32 logits (BoundPolicy.kind "upper"), else None.
         With k: also for a CALL of an engine whose form is the one eps, when the call wants PER_PAIR_MIN_K results or more -- the candidates a
         large k needs under one eps (k' = 2 561 on amzn-books: 10 272) cost more to re-score and sort than the UPPER build adds to the first pass
         (3.19 -> 2.9 ms per batch); the verdict of such a call runs with eps = 0 on the same state."""
-        eng = self._engine
-        c = self._upper_poly_cache
-        if c is None or c[0] is not eng:
-            c = self._upper_poly_fill(eng)
-        if c[1] is not None or k is None or k < self.PER_PAIR_MIN_K:
-            return c[1]
-        return c[2]
-
-    def _upper_poly_fill(self, eng):
-        """-> (engine, the polynomial if the engine's form is per-pair, the polynomial if the shape has the UPPER build at all)"""
-        poly = any_poly = None
-        kind = self._bound_kind(eng.spec, eng.lib) if (eng.exact is not None and eng.dense_precision == "f16x3") else None
-        if kind is not None and eng.score_dense_upper_supported() and self._bound_from_weights(eng.spec).get("eps", math.inf) <= self.PROVED_MAX_EPS_PER_PAIR:
-            from . import f16x3_bound as FB
-
-            lin = [m for m in self._mol_module._gating_fn._qi_partial_module.modules() if isinstance(m, torch.nn.Linear)]
-            sp = eng.spec
-            zeros = lambda n: torch.zeros(n)      # noqa: E731
-            res = FB.upper_bound_poly(lin[0].weight, lin[0].bias if lin[0].bias is not None else zeros(lin[0].out_features), lin[1].weight,
-                                      lin[1].bias if lin[1].bias is not None else zeros(lin[1].out_features), sp.temperature, sp.dot_product_dimension,
-                                      sp.query_dot_product_groups, sp.item_dot_product_groups)
-            any_poly = res["poly"]
-            self._upper_poly_info = res
-            if kind == "upper":
-                poly = any_poly
-        self._upper_poly_cache = (eng, poly, any_poly)
-        return self._upper_poly_cache
+        pol = self._policy
+        if pol.poly is not None or k is None or k < self.PER_PAIR_MIN_K:
+            return pol.poly
+        return pol.any_poly
 
     PER_PAIR_MIN_K = 1024         # calls for at least this many results take per-pair bounds whatever the engine's form (see _upper_poly)
-    _upper_poly_cache = None
-    _upper_poly_info = None
 
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus -- of the module's OWN precision (the proved mode's internal split-f16
@@ -347,10 +430,7 @@ class MoLBruteForceTopK(MoLTopKModule):
         B, N = query_embeddings.size(0), self._index.n_items
         if B * N * 4 > self.MAX_LOGIT_BYTES and k <= self.CHUNK_ITEMS:
             return self._forward_chunked(query_embeddings, k, **kwargs)
-        logits = self._all_logits_scratch(query_embeddings, **kwargs)
-        ws = self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(logits.shape[0], logits.shape[1], k), torch.uint8)
-        scores, ids = E.topk(logits, k, ids=self._ids_flat, sorted=sorted, workspace=ws)
-        return scores.to(query_embeddings.dtype), ids
+        return self._dense_topk(query_embeddings, k, sorted=sorted, **kwargs)
 
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
         """CandidateIndex.get_top_k_outputs' body for this module: top-k' + id map + seen-id filter with the filter fused into the final
@@ -361,29 +441,21 @@ class MoLBruteForceTopK(MoLTopKModule):
         B, N = query_embeddings.size(0), self._index.n_items
         if B * N * 4 > self.MAX_LOGIT_BYTES or not E.topk_filter_fusable(N, k_prime, invalid_ids.shape[1], k):
             return None
-        if eng.exact is not None:
+        ex = eng.exact
+        if ex is None:
+            return self._dense_topk(query_embeddings, k_prime, seen=(invalid_ids, k), **kwargs)
+        if (not self.speculation_pays(B, N) and self._mol_module.engine() is not eng and eng.dense_precision == "f16x3"
+                and self._index32 is not None and self._index32_engine is ex):
             # the default mode's small calls (speculation_pays) run the dense fp32 kernels (_forward_rescored): keep the filter fused into their
             # selection launch as the plain fp32 module does
-            ex = eng.exact
-            if not (not self.speculation_pays(B, N) and self._mol_module.engine() is not eng and eng.dense_precision == "f16x3"
-                    and self._index32 is not None and self._index32_engine is ex):
-                if not (eng.dense_precision == "f16x3" and k <= k_prime <= N):
-                    return None
-                # the proved flow: the filter runs inside its finish launch (and inside the redo's selection)
-                r = self._forward_rescored(query_embeddings, k_prime, _seen=(invalid_ids, k), **kwargs)
-                if r[0] == "filtered":
-                    return r[1], r[2]
-                return E.filter_seen_ids(r[1], r[0], invalid_ids, k)
-            n_q = ex.lib.rails_mol_query_pack_floats(E.C.byref(ex.shape), B)
-            qpack32, _, _ = ex.query_pack(query_embeddings, kwargs.get("user_ids"), out=self._buf("qpack32", n_q, torch.float32))
-            logits = ex.score_dense(qpack32, B, self._index32, out=self._buf("logits", B * N, torch.float32).view(B, N))
-            ws = self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(B, N, k_prime), torch.uint8)
-            ids, scores = E.topk_filtered(logits, k_prime, self._ids_flat, invalid_ids, k, workspace=ws)
-            return ids, scores.to(query_embeddings.dtype)
-        logits = self._all_logits_scratch(query_embeddings, **kwargs)
-        ws = self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(B, N, k_prime), torch.uint8)
-        ids, scores = E.topk_filtered(logits, k_prime, self._ids_flat, invalid_ids, k, workspace=ws)
-        return ids, scores.to(query_embeddings.dtype)
+            return self._dense_topk(query_embeddings, k_prime, seen=(invalid_ids, k), _eng=ex, _index=self._index32, _tag="qpack32", **kwargs)
+        if not (eng.dense_precision == "f16x3" and k <= k_prime <= N):
+            return None
+        # the proved flow: the filter runs inside its finish launch (and inside the redo's selection)
+        r = self._forward_rescored(query_embeddings, k_prime, _seen=(invalid_ids, k), **kwargs)
+        if r[0] == "filtered":
+            return r[1], r[2]
+        return E.filter_seen_ids(r[1], r[0], invalid_ids, k)
 
     MAX_LOGIT_BYTES = 4 << 30      # larger (B, N) logit matrices are never materialised: the corpus is scored in chunks
     CHUNK_ITEMS = 1 << 23          # 8 Mi items per chunk (a multiple of the tile): 1 GiB of logits at B = 32
@@ -419,56 +491,37 @@ class MoLBruteForceTopK(MoLTopKModule):
     RESCORE_EPS_PER_INV_TEMPERATURE_F16X1 = 7.5e-3
 
     def _forward_rescored(self, query_embeddings: torch.Tensor, k: int, _seen=None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The fp32 brute-force result -- same scores, same ids, same tie order -- at the f16x3 kernel's speed.
-          1. f16x3 logits s16 over the whole index; the top Kc = k + max(64, k/4) of them (rounded up to whole tiles) are the
-             candidates, m = the smallest candidate's s16.  Every other item has s16 <= m.
-          2. the candidates are gathered from the dense fp32 index (kept next to the f16x3 one when memory allows; otherwise
-             their raw rows go through the fp32 index build) and scored by the fp32 kernel: e32, their exact fp32 logits (the
-             same arithmetic per (query, item) pair as the dense fp32 path, hence the same bits).
-          3. rails_rescore_select: top-k of e32 by (score desc, corpus position asc) -- the dense path's total order.
-        The result is the dense fp32 top-k iff no item outside the candidates can reach the k-th exact score e_k, i.e. iff
-        e_k > m + eps where |s16 - s32| <= eps.  Step 3 returns e_k - m per row and the largest |e32 - s16| over the row's Kc
-        candidates and 32 more items drawn at random from the whole corpus; eps is the calibrated default or SAFETY x the largest
-        such error this module has seen, whichever is larger.  A row that does not clear eps -> the call is redone on the dense
-        fp32 index (and later calls take more candidates).  One (B x 8)-byte device-to-host copy per call."""
+        """The router of the exact modes: the fp32 brute-force result -- same scores, same ids, same tie order -- by the dense fp32 kernels, the
+        proved flow (_forward_proved) or the monitored flow (_forward_monitored), a slice of the batch at a time under the 4 GiB logit policy."""
         eng = self._bind()
-        ex = eng.exact
         self._absorb_state()
         B, N = query_embeddings.size(0), self._index.n_items
         if k > N:
             raise RuntimeError(f"selected index k out of range (k={k}, n={N})")
-        single = eng.dense_precision == "f16x1"
         # The bound on |first pass - fp32|: A PRIORI for the f16x3 first pass (rails_amd/f16x3_bound.py: the call is then PROVED to
         # return the dense fp32 result whenever its verdict clears); monitored and empirical for the one-product first pass, whose a-priori
-        # bound is vacuous.  A module whose a-priori bound is infinite (a guard fails) does not speculate.
-        eps_proved = None if single else self._proved_eps()
-        upper = None if single else self._upper_poly(k)         # per-pair upper bounds instead of one eps (then the verdict's eps is 0)
-        if upper is not None and eps_proved is not None and math.isfinite(eps_proved) and self._upper_poly() is None:
-            eps_proved = 0.0          # a large-k call of an engine whose own form is the one eps
-        if eps_proved is not None and not math.isfinite(eps_proved):
-            self.rescore_stats["unprovable_calls"] = self.rescore_stats.get("unprovable_calls", 0) + 1
-            return self._forward_fp32_dense(query_embeddings, k, **kwargs)
-        if eps_proved is not None and not self.speculation_pays(query_embeddings.size(0), self._index.n_items) and self._mol_module.engine() is not eng:
-            # too few (query, item) pairs for the first pass to save what the verification costs (PROVED_MIN_PAIRS) -- the default mode takes
-            # the dense kernels there (an explicit "f16x3-exact" precision keeps speculating)
-            return self._forward_fp32_dense(query_embeddings, k, **kwargs)
-        if eps_proved is not None:
-            # candidates: every item within eps of the k-th score must be among them.  amzn-books, eps = 0.9-1.0: 470-680 items at k = 200,
-            # 6 000-7 500 at k = 2 561 (128 queries; profiles/r05_proved_candidate_census.json); rails_topk costs the same 80-90 us from
-            # 544 to 1 536 candidates per row of 700 k scores, so the margin starts generous.  A failed verdict doubles it
-            # (per-pair upper bounds on a 12.5 M-item shard of 16x16x64: 730-900 items can reach the 200-th score; tools/r05_c4_census.py)
-            floor, per_k = self._per_pair_pad() if upper is not None else self.PAD_ONE_EPS
-            pad = max(floor, per_k * k) * self._pad_scale
-            kc = min((k + pad + E.TILE_ITEMS - 1) // E.TILE_ITEMS * E.TILE_ITEMS, 16384)
-        else:
-            pad = (max(128, k // 2) if single else max(64, k // 4)) * self._pad_scale
-            kc = (k + pad + E.TILE_ITEMS - 1) // E.TILE_ITEMS * E.TILE_ITEMS
-            if k <= 384:
-                kc = min(kc, 512)       # rails_topk's two-launch path ends at k = 512; beyond it a selection costs five reads of the logits
-        oversize = B * N * 4 > self.MAX_LOGIT_BYTES      # the 4 GiB logit policy comes first: no route below may materialise (B, N)
+        # bound is vacuous (eps None).  A module whose a-priori bound is infinite (a guard fails) does not speculate.
+        eps = self._policy.eps
+        upper = None
+        if eps is not None:
+            if not math.isfinite(eps):
+                self.rescore_stats["unprovable_calls"] = self.rescore_stats.get("unprovable_calls", 0) + 1
+                return self._forward_fp32_dense(query_embeddings, k, **kwargs)
+            if not self.speculation_pays(B, N) and self._mol_module.engine() is not eng:
+                # too few (query, item) pairs for the first pass to save what the verification costs (PROVED_MIN_PAIRS) -- the default mode takes
+                # the dense kernels there (an explicit "f16x3-exact" precision keeps speculating)
+                return self._forward_fp32_dense(query_embeddings, k, **kwargs)
+            upper = self._upper_poly(k)       # per-pair upper bounds instead of one eps (then the verdict's eps is 0)
+            if upper is not None and self._policy.poly is None:
+                eps = 0.0                     # a large-k call of an engine whose own form is the one eps
+        # candidates: every item within eps of the k-th score must be among them.  amzn-books, eps = 0.9-1.0: 470-680 items at k = 200,
+        # 6 000-7 500 at k = 2 561 (128 queries; profiles/r05_proved_candidate_census.json); rails_topk costs the same 80-90 us from
+        # 544 to 1 536 candidates per row of 700 k scores, so the margin starts generous.  A failed verdict doubles it
+        # (per-pair upper bounds on a 12.5 M-item shard of 16x16x64: 730-900 items can reach the 200-th score; tools/r05_c4_census.py)
+        kc = self.candidate_count(k, upper is not None, self._policy_items(), self._pad_scale, single=eps is None)
         if kc >= N or k == 0 or kc > 16384 or k + E.TILE_ITEMS > kc or N > 0xFFFFFFFF or N < self.SPECULATE_MIN_ITEMS or self._speculation_paused():
             return self._forward_fp32_dense(query_embeddings, k, **kwargs)
-        if oversize:                              # the speculative pass wants the whole (B, N) s16 matrix
+        if B * N * 4 > self.MAX_LOGIT_BYTES:      # the 4 GiB logit policy: the speculative pass wants the whole (B, N) first-pass matrix
             rows = self.MAX_LOGIT_BYTES // (N * 4)
             if rows >= 1:                         # ... of a slice of the batch at a time (per-row payloads are sliced with it)
                 parts = []
@@ -477,14 +530,15 @@ class MoLBruteForceTopK(MoLTopKModule):
                     parts.append(self._forward_rescored(query_embeddings[b0 : b0 + rows], k, **kw))
                 return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
             return self._forward_fp32_dense(query_embeddings, k, **kwargs)   # one row is too long: fp32, in corpus chunks
-        if (eps_proved is not None and self.DEVICE_VERDICT and self._index32 is not None and self._index32_engine is ex):
-            return self._forward_proved(query_embeddings, k, kc, eps_proved, upper, _seen, **kwargs)
-        # one prologue writes the query pack in both formats: f16 hi/lo for the first pass, fp32 for the re-scoring
-        n_q = eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), B)
-        qpack16, qpack32 = eng.query_pack_both(query_embeddings, kwargs.get("user_ids"), self._buf("qpack", n_q, torch.float32),
-                                               self._buf("qpack32", n_q, torch.float32))
+        if eps is not None and self._index32 is not None and self._index32_engine is eng.exact:
+            return self._forward_proved(query_embeddings, k, kc, eps, upper, _seen, **kwargs)
+        return self._forward_monitored(query_embeddings, k, kc, eps, upper, **kwargs)
+
+    def _first_pass(self, eng, qpack16: torch.Tensor, B: int, upper, bias: bool = True) -> torch.Tensor:
+        """The first pass over the whole index into the recycled (B, N) buffer: upper bounds of the fp32 logits with `upper`, else the
+        first-pass logits themselves.  bias: apply the tests' planted error (speculate_for_shard does not)."""
+        N = self._index.n_items
         s16 = self._buf("logits", B * N, torch.float32).view(B, N)
-        ws = self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(B, N, kc), torch.uint8)
         hook = self._first_pass_hook        # measurement only (bench.py: events around the dominant launch, on its stream)
         if hook is not None:
             hook(0)
@@ -494,47 +548,68 @@ class MoLBruteForceTopK(MoLTopKModule):
             eng.score_dense(qpack16, B, self._index, out=s16)
         if hook is not None:
             hook(1)
-        if self._debug_first_pass_bias is not None:   # tests only: (positions, delta) -- the first pass is made to under-score these items
+        if bias and self._debug_first_pass_bias is not None:   # tests only: (positions, delta) -- the first pass is made to under-score these items
             s16[:, self._debug_first_pass_bias[0]] -= self._debug_first_pass_bias[1]
+        return s16
+
+    def _query_packs(self, eng, query_embeddings: torch.Tensor, **kwargs):
+        """One prologue writes the query pack in both formats: f16 hi/lo for the first pass, fp32 for the re-scoring."""
+        n_q = eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), query_embeddings.size(0))
+        return eng.query_pack_both(query_embeddings, kwargs.get("user_ids"), self._buf("qpack", n_q, torch.float32), self._buf("qpack32", n_q, torch.float32))
+
+    def _forward_monitored(self, query_embeddings: torch.Tensor, k: int, kc: int, eps_proved: Optional[float], upper, **kwargs):
+        """The older speculate / verify flow: what serves the one-product first pass ("f16-exact", eps_proved None) and the f16x3 first pass
+        without a resident fp32 index.
+          1. first-pass logits s16 over the whole index; the top kc of them are the candidates, m = the smallest candidate's s16.  Every
+             other item has s16 <= m.
+          2. the candidates are scored by the fp32 kernel from the dense fp32 index (kept next to the first-pass one when memory allows;
+             otherwise their raw rows go through the fp32 index build): e32, their exact fp32 logits (the same arithmetic per (query, item)
+             pair as the dense fp32 path, hence the same bits).
+          3. rails_rescore_select: top-k of e32 by (score desc, corpus position asc) -- the dense path's total order.
+        The result is the dense fp32 top-k iff no item outside the candidates can reach the k-th exact score e_k, i.e. iff
+        e_k > m + eps where |s16 - s32| <= eps.  Step 3 returns e_k - m per row and the largest |e32 - s16| over the row's candidates, and,
+        for the one-product pass, over 64 more items: 32 drawn at random from the whole corpus and 32 of the highest-norm ones; its eps is
+        the calibrated default or SAFETY x the largest such error this module has seen, whichever is larger.  A row that does not clear eps
+        -> the call is redone on the dense fp32 kernels (and later calls take more candidates)."""
+        eng = self._engine
+        ex = eng.exact
+        B, N = query_embeddings.size(0), self._index.n_items
+        single = eps_proved is None
+        qpack16, qpack32 = self._query_packs(eng, query_embeddings, **kwargs)
+        s16 = self._first_pass(eng, qpack16, B, upper)
+        ws = self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(B, N, kc), torch.uint8)
         c16, pos = E.topk(s16, kc, workspace=ws)
         # two more tiles per query of probes (random + highest-norm items), re-scored too, so that the MONITORED bound |s16 - s32| <= eps is
         # watched outside the candidates as well (the a-priori bound needs no watching: the candidates' own errors are still compared
         # with it, and one above it is reported as a violation of the arithmetic model)
-        if eps_proved is None:
+        if single:
             pos = torch.cat([pos, *self._probes(B, N)], dim=1)
-        if self._index32 is not None and B * pos.shape[1] <= self.INDEXED_MAX_CANDIDATES and ex.score_indexed_supported(B, pos.shape[1]):
-            # (_rescore_candidates below is this branch + the gather fallback, for the sharded flow)
+        if self._index32 is not None:
             # read the candidates in place from the fp32 index: one launch less and no gathered copy.  A candidate's 1 280 bytes are 80
             # pieces of 16 bytes in the tile-packed index, each in its own cache line, whoever fetches them -- the gather kernel paid
             # that amplification AND wrote and re-read the copy.  Measured with the GEMM1 lookahead of the independent-wave kernels in
-            # (tools/indexed_rescore_probe.py, amzn-books, `f16-exact`): k' = 200  B = 8 / 32 / 128: 0.501 / 1.59 / 5.81 -> 0.494 /
-            # 1.59 / 5.76 ms; k' = 2561: 0.631 / 1.93 / 6.88 -> 0.610 / 1.835 / 6.55 ms.  (Before the lookahead the in-place reads cost
-            # more than the copy beyond B x Kc = 1024 candidates: B = 32 1.65 -> 1.69 ms; INDEXED_MAX_CANDIDATES keeps the switch.)
-            e32 = self._rescore(ex, qpack32, B, pos)
-        else:
-            if self._index32 is not None:
-                cand, _ = ex.gather_index(self._index32, pos)
-            else:
-                cand = ex.build_index(self._item_embeddings[0].index_select(0, pos.reshape(-1)))
+            # (amzn-books, `f16-exact`): k' = 200  B = 8 / 32 / 128: 0.501 / 1.59 / 5.81 -> 0.494 / 1.59 / 5.76 ms; k' = 2561: 0.631 /
+            # 1.93 / 6.88 -> 0.610 / 1.835 / 6.55 ms (docs/HISTORY.md section 3.3)
+            e32 = self._score_positions(ex, qpack32, B, self._index32, self._rows32, pos)
+        else:     # no resident fp32 index: the candidates' raw rows go through the fp32 index build
+            cand = ex.build_index(self._item_embeddings[0].index_select(0, pos.reshape(-1)))
             e32 = ex.score_candidates(qpack32, B, cand, pos.shape[1])
         scores, ids, _, stats = E.rescore_select(e32, c16, pos, self._ids_flat, N, k, approx_dense=s16, one_sided=upper is not None)
         self.rescore_stats["calls"] += 1
         self.rescore_stats["kc"] = kc
-        # The bound eps on |s16 - s32|: never below the calibrated default, and SAFETY x the largest error this module has seen on its
-        # candidates and probes (this call included) -- a model whose weights make the first pass coarser widens its own margin
-        # instead of failing the monitor forever.  The row passes when its k-th exact score clears the best non-candidate by eps.
-        default = (self.RESCORE_EPS_PER_INV_TEMPERATURE_F16X1 if single else self.RESCORE_EPS_PER_INV_TEMPERATURE) / eng.spec.temperature
-        safety = self.SAFETY_F16X1 if single else self.SAFETY_F16X3
-        guard, guard_limit = None, 0.0
-        if eps_proved is not None:
+        if single:
+            # The bound eps on |s16 - s32|: never below the calibrated default, and SAFETY x the largest error this module has seen on its
+            # candidates and probes (this call included) -- a model whose weights make the first pass coarser widens its own margin
+            # instead of failing the monitor forever.  The row passes when its k-th exact score clears the best non-candidate by eps.
+            default, safety = self.RESCORE_EPS_PER_INV_TEMPERATURE_F16X1 / eng.spec.temperature, self.SAFETY_F16X1
+            guard, guard_limit = None, 0.0
+        else:
             # eps = the a-priori bound (safety 1: an observed error above it -- a violation of the model -- still widens the margin); the
-            # one data-dependent hypothesis of the bound, max |gq'| max |gi| <= gate_guard, is checked by the verdict kernel on the
-            # batch's gq' rows (behind the Eq fragments in the fp32 query pack)
+            # one data-dependent hypothesis of the bound, max |gq'| max |gi| <= gate_guard, is checked on the batch's gq' rows
             default, safety = eps_proved, 1.0
-            sp = eng.spec
-            off = (B + 32 // sp.query_dot_product_groups - 1) // (32 // sp.query_dot_product_groups) * 32 * sp.dot_product_dimension
-            guard, guard_limit = qpack32[off : off + B * sp.num_logits], self._gate_guard_limit
-        if self._index32 is not None and self._index32_engine is ex and self.DEVICE_VERDICT:
+            guard, guard_limit = eng.gate_rows(qpack32, B), self._gate_guard_limit
+        if self._index32 is not None:
+            # (the one-product first pass only: with a resident fp32 index the f16x3 pass takes the proved flow)
             # Verdict and fallback ON THE DEVICE: rails_rescore_verdict folds the row stats into the calibration state and writes the
             # REDO flag; the dense fp32 pass and its top-k are enqueued behind it under that flag as their launch predicate (no-ops
             # unless the verification failed) and overwrite (scores, ids).  The host never waits; it looks at a snapshot of the
@@ -546,9 +621,10 @@ class MoLBruteForceTopK(MoLTopKModule):
             E.topk(l32, k, ids=self._ids_flat, workspace=ws, out=(scores, ids), run_if=redo)
             self._state_host.copy_(state, non_blocking=True)
             self._state_event.record()
-            self._state_pending = (k, kc)
+            self._state_pending = (k, kc, upper is not None)
             self._state_direct = False
         else:
+            # no resident fp32 index: the host reads the verdict (one event spin per call)
             err, gap = self._read_stats(stats)
             if err == err and err != float("inf"):
                 self._err_seen = max(err, self._err_seen)   # never forgotten: a rare outlier keeps the margin wide until the engine changes
@@ -558,10 +634,10 @@ class MoLBruteForceTopK(MoLTopKModule):
                 gmax = float(guard.abs().max())
                 self.rescore_stats["guard_max"] = max(self.rescore_stats.get("guard_max", 0.0), gmax)
                 good = gmax <= guard_limit
-            if eps_proved is not None:
+            if not single:
                 self._count_proved(1 if good else 0)
             self.rescore_stats["eps"] = eps
-            self._note_verdict(good, k, kc)
+            self._note_verdict(good, k, kc, upper is not None)
             if not good:
                 return self._forward_fp32_dense(query_embeddings, k, **kwargs)
         if self.audit_every > 0 and self.rescore_stats["calls"] % self.audit_every == 0:
@@ -603,37 +679,29 @@ class MoLBruteForceTopK(MoLTopKModule):
         hi = c + ((upper[0] * c + upper[1]) * c + upper[2] if upper is not None else 0.0)
         return -c, hi
 
-    def _forward_proved(self, query_embeddings: torch.Tensor, k: int, kc: int, eps_proved: float, upper, seen, **kwargs):
-        eng = self._engine
-        ex = eng.exact
-        B, N = query_embeddings.size(0), self._index.n_items
-        sp = eng.spec
-        n_q = eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), B)
-        qpack16, qpack32 = eng.query_pack_both(query_embeddings, kwargs.get("user_ids"), self._buf("qpack", n_q, torch.float32),
-                                               self._buf("qpack32", n_q, torch.float32))
-        s16 = self._buf("logits", B * N, torch.float32).view(B, N)
-        hook = self._first_pass_hook        # measurement only (bench.py: events around the dominant launch, on its stream)
-        if hook is not None:
-            hook(0)
-        if upper is not None:
-            eng.score_dense_upper(qpack16, B, self._index, upper, out=s16)
-        else:
-            eng.score_dense(qpack16, B, self._index, out=s16)
-        if hook is not None:
-            hook(1)
-        if self._debug_first_pass_bias is not None:   # tests only: (positions, delta) -- the first pass is made to under-score these items
-            s16[:, self._debug_first_pass_bias[0]] -= self._debug_first_pass_bias[1]
-        cap = min(kc, N)
+    def _select_and_rescore(self, ex, qpack32: torch.Tensor, B: int, s16: torch.Tensor, cap: int, upper):
+        """Threshold selection of at most `cap` candidates per row by first-pass score + their fp32 logits
+        -> (workspace with the rows' counts, positions, first-pass scores, fp32 scores)."""
         ws, pos, a16, e32 = self._cand_buffers(B, cap)
         self._cand_dirty = True
         lo, hi = self._score_range(upper)
         E.candidates_select(s16, cap, lo, hi, ws, pos, a16)
         if self._rows32 is not None and ex.score_indexed_supported(B, cap):
-            ex.score_indexed_rows(qpack32, B, self._rows32, N, pos, counts=ws, out=e32)
-        else:
-            e32 = self._rescore(ex, qpack32, B, pos)       # every slot (the slots past a row's count hold earlier candidates: valid positions, ignored below)
-        off = (B + 32 // sp.query_dot_product_groups - 1) // (32 // sp.query_dot_product_groups) * 32 * sp.dot_product_dimension
-        guard = qpack32[off : off + B * sp.num_logits]
+            ex.score_indexed_rows(qpack32, B, self._rows32, s16.shape[1], pos, counts=ws, out=e32)
+        else:      # every slot (the slots past a row's count hold earlier candidates: valid positions, ignored by the finish)
+            e32 = self._score_positions(ex, qpack32, B, self._index32, self._rows32, pos)
+        return ws, pos, a16, e32
+
+    def _forward_proved(self, query_embeddings: torch.Tensor, k: int, kc: int, eps_proved: float, upper, seen, **kwargs):
+        eng = self._engine
+        ex = eng.exact
+        B, N = query_embeddings.size(0), self._index.n_items
+        sp = eng.spec
+        qpack16, qpack32 = self._query_packs(eng, query_embeddings, **kwargs)
+        s16 = self._first_pass(eng, qpack16, B, upper)
+        cap = min(kc, N)
+        ws, pos, a16, e32 = self._select_and_rescore(ex, qpack32, B, s16, cap, upper)
+        guard = eng.gate_rows(qpack32, B)
         state = self._state()
         fuse = seen is not None and k <= 512 and seen[0].shape[1] <= 256 and E.topk_filter_fusable(N, k, seen[0].shape[1], seen[1])
         scores, ids, f_i, f_s = E.candidates_finish(e32, a16, pos, cap, ws, self._ids_flat, N, k, eps_proved, 1.0, upper is not None, guard, sp.num_logits,
@@ -649,7 +717,7 @@ class MoLBruteForceTopK(MoLTopKModule):
             E.topk_filtered(l32, k, self._ids_flat, seen[0], seen[1], workspace=tws, out=(f_i, f_s), run_if=redo)
         else:
             E.topk(l32, k, ids=self._ids_flat, workspace=tws, out=(scores, ids), run_if=redo)
-        self._state_pending = (k, kc)
+        self._state_pending = (k, kc, upper is not None)
         self._state_direct = True
         if fuse:
             return "filtered", f_i, f_s.to(query_embeddings.dtype)
@@ -662,8 +730,9 @@ class MoLBruteForceTopK(MoLTopKModule):
         """True iff this (local) module is bound in proved mode with both index formats resident: what ShardedMoLBruteForceTopK needs from
         EVERY rank before it runs the global proof."""
         eng = self._bind()
+        eps = self._policy.eps
         return eng.exact is not None and eng.dense_precision == "f16x3" and self._index32 is not None and self._index32_engine is eng.exact \
-            and self._proved_eps() is not None and math.isfinite(self._proved_eps())
+            and eps is not None and math.isfinite(eps)
 
     def speculate_for_shard(self, query_embeddings: torch.Tensor, k: int, kc: int, **kwargs):
         """The proved flow on THIS shard without a verdict: first pass over the shard, threshold selection of at most kc candidates by first-pass
@@ -677,11 +746,10 @@ class MoLBruteForceTopK(MoLTopKModule):
         ex = eng.exact
         B, N = query_embeddings.size(0), self._index.n_items
         dev = query_embeddings.device
+        # an fp32 pack of its own: with submit / result pipelining the verdict of batch i reads its gate rows while batch i + 1's prologue runs
         n_q = eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), B)
-        # packs of their own: with submit / result pipelining the verdict of batch i reads its gate rows while batch i + 1's prologue runs
-        qpack16 = self._buf("qpack", n_q, torch.float32)
-        qpack32 = torch.empty(n_q, dtype=torch.float32, device=dev)
-        eng.query_pack_both(query_embeddings, kwargs.get("user_ids"), qpack16, qpack32)
+        qpack16, qpack32 = eng.query_pack_both(query_embeddings, kwargs.get("user_ids"), self._buf("qpack", n_q, torch.float32),
+                                               torch.empty(n_q, dtype=torch.float32, device=dev))
         msg = torch.empty((B, 2 * k + 2), dtype=torch.int64, device=dev)
         if N == 0:      # an empty shard still takes part in the exchange: nothing to offer, nothing left outside
             msg[:, :k] = int(torch.tensor(float("-inf")).view(torch.int32)) & 0xFFFFFFFF
@@ -690,25 +758,11 @@ class MoLBruteForceTopK(MoLTopKModule):
             msg[:, 2 * k + 1] = 0
             return msg, qpack32
         cap = min(max(kc, 1), N)
-        s16 = self._buf("logits", B * N, torch.float32).view(B, N)
-        hook = self._first_pass_hook
-        if hook is not None:
-            hook(0)
-        upper = self._upper_poly()
-        if upper is not None:
-            eng.score_dense_upper(qpack16, B, self._index, upper, out=s16)
-        else:
-            eng.score_dense(qpack16, B, self._index, out=s16)
-        if hook is not None:
-            hook(1)
-        ws, pos, a16, e32 = self._cand_buffers(B, cap)
-        self._cand_dirty = True
-        lo, hi = self._score_range(upper)
-        E.candidates_select(s16, cap, lo, hi, ws, pos, a16)
-        if self._rows32 is not None and ex.score_indexed_supported(B, cap):
-            ex.score_indexed_rows(qpack32, B, self._rows32, N, pos, counts=ws, out=e32)
-        else:
-            e32 = self._rescore(ex, qpack32, B, pos)
+        upper = self._policy.poly
+        # bias=False: the tests' planted first-pass error is NOT applied here -- the sharded forced-failure test plants its failure through the
+        # global proof's eps instead
+        s16 = self._first_pass(eng, qpack16, B, upper, bias=False)
+        ws, pos, a16, e32 = self._select_and_rescore(ex, qpack32, B, s16, cap, upper)
         E.candidates_finish(e32, a16, pos, cap, ws, self._ids_flat, N, k, 0.0, 1.0, upper is not None, None, 0, 0.0, None, None, msg=msg)
         self._cand_dirty = False
         self.rescore_stats["calls"] += 1
@@ -718,28 +772,16 @@ class MoLBruteForceTopK(MoLTopKModule):
     ROWS_COPY_MAX_BYTES = 8 << 30      # the row-major copy of the fp32 index is kept for indexes up to this size (0: never)
     _rows32 = None
 
-    def _rescore(self, ex: E.MolEngine, qpack32: torch.Tensor, B: int, pos: torch.Tensor) -> torch.Tensor:
-        """fp32 logits of per-row candidates `pos` (positions of the resident fp32 index), whichever way is cheapest here -- same bits each way:
-        in place from the row-major copy, in place from the tile-packed index, or gathered tiles (the 256-logit team kernel)."""
-        if ex.score_indexed_supported(B, pos.shape[1]):
-            if self._rows32 is not None:
-                return ex.score_indexed_rows(qpack32, B, self._rows32, self._index32.n_items, pos)
-            return ex.score_indexed(qpack32, B, self._index32, pos)
-        cand, _ = ex.gather_index(self._index32, pos)
-        return ex.score_candidates(qpack32, B, cand, pos.shape[1])
-
-    INDEXED_MAX_CANDIDATES = 1 << 30   # rails_mol_score_indexed instead of gather + score_candidates up to this many (B x Kc) candidates (was 1024)
-    DEVICE_VERDICT = True     # False: the host reads the verdict (one event spin per call) -- kept for deployments without a resident fp32 index
-
-    def _note_verdict(self, good: bool, k: int, kc: int) -> None:
+    def _note_verdict(self, good: bool, k: int, kc: int, per_pair: bool) -> None:
         self._recent.append(good)
         if not good:
             self.rescore_stats["fallbacks"] += 1
-            if self._in_proved_mode():
-                if kc < 16384:
-                    self._pad_scale *= 2      # proved mode: the candidates must cover everything within eps of the k-th score
-            elif self._pad_scale < 4 and not (k <= 384 and kc >= 512):
-                self._pad_scale *= 2          # crowded scores or a coarse first pass: more candidates from the next call on
+            # crowded scores or a coarse first pass: more candidates from the next call on, while doubling the margin still yields more of
+            # them (candidate_count's caps).  Proved mode: the candidates must cover everything within eps of the k-th score, whatever it
+            # takes; the monitored margin stops at four times its start
+            proved = self._in_proved_mode()
+            if (proved or self._pad_scale < 4) and self.candidate_count(k, per_pair, self._policy_items(), self._pad_scale * 2, single=not proved) > kc:
+                self._pad_scale *= 2
 
     def _state(self) -> torch.Tensor:
         if self._verdict_state is None:
@@ -778,44 +820,21 @@ class MoLBruteForceTopK(MoLTopKModule):
         self._err_seen = max(self._err_seen, float(h[0]))
         self.rescore_stats["eps"] = float(h[2])
         self.rescore_stats["guard_max"] = max(self.rescore_stats.get("guard_max", 0.0), float(h[7]))
-        k, kc = self._state_pending
+        k, kc, per_pair = self._state_pending
         self._state_pending = None
         for i in range(new_calls):
-            self._note_verdict(i >= new_redone, k, kc)
+            self._note_verdict(i >= new_redone, k, kc, per_pair)
         if self._in_proved_mode():
             self._count_proved(new_calls - new_redone)
 
     _first_pass_hook = None
-    _proved_eps_cache = None      # (engine, eps as the float32 handed to the verdict or None: monitored mode)
 
     def _in_proved_mode(self) -> bool:
-        c = self._proved_eps_cache
-        return c is not None and c[0] is self._engine and c[1] is not None and self._engine.dense_precision != "f16x1"
+        return self._policy.eps is not None
 
     def _proved_eps(self) -> Optional[float]:
-        """The a-priori bound for the bound engine, rounded UP to a float32 (the verdict compares in fp32: gap = fl(e_k - m) > eps, one
-        rounding of relative 2^-24 on a gap of at most 2 / tau -- covered by the 2^-16 relative slack added here), or inf when a
-        guard fails.  Computed once per engine; also fixes the device-side guard limit GATE_GUARD / max |gi| from the item index."""
-        eng = self._engine
-        if self._proved_eps_cache is not None and self._proved_eps_cache[0] is eng:
-            return self._proved_eps_cache[1]
-        from . import f16x3_bound as FB
-
-        eps = float(self._bound_from_weights(eng.spec).get("eps", math.inf))
-        if math.isfinite(eps):
-            if self._upper_poly() is not None:
-                eps = 0.0          # the first pass writes upper bounds of the fp32 logits: the verdict is e_k > m itself (strict: ties with an outsider are redone)
-            else:
-                eps32 = torch.tensor(eps * (1.0 + 2.0 ** -16), dtype=torch.float32)
-                eps = float(torch.nextafter(eps32, torch.tensor(float("inf"))))
-            gi_max = self._gi_abs_max()
-            self._gate_guard_limit = min(FB.GATE_GUARD / gi_max, 3.0e38) if gi_max > 0.0 else 3.0e38
-            if not math.isfinite(gi_max):
-                eps = math.inf
-        self._proved_eps_cache = (eng, eps)
-        self.rescore_stats["proved_calls"] = 0
-        self.rescore_stats["bound_violations"] = 0
-        return eps
+        """The eps the verdicts of the bound engine compare with (BoundPolicy.eps); None for the one-product first pass and the dense modes."""
+        return self._policy.eps
 
     def _gi_abs_max(self) -> float:
         """max |gi| over the corpus, from the item-gate rows of the tile-packed index (fp32 in both formats; padding rows are zero).
@@ -836,7 +855,7 @@ class MoLBruteForceTopK(MoLTopKModule):
 
     def _count_proved(self, n_clear: int) -> None:
         """Calls whose verdict cleared count as PROVED while no observed |first pass - fp32| has exceeded the a-priori bound."""
-        eps = self._proved_eps_cache[1]
+        eps = self._policy.eps
         if self._err_seen > eps:
             self.rescore_stats["bound_violations"] = self.rescore_stats.get("bound_violations", 0) + 1
             return
@@ -864,29 +883,23 @@ class MoLBruteForceTopK(MoLTopKModule):
                                 eps_rigorous itself and a cleared call is proved, not merely monitored.
           eps_default           the calibrated empirical eps of the monitored modes, for comparison."""
         eng = self._bind()
-        cached = getattr(self, "_rig_cache", None)
-        if cached is not None and cached[0] is eng:
-            return cached[1]
         single = eng.dense_precision == "f16x1"
         inv_tau = 1.0 / float(eng.spec.temperature)
         default = (self.RESCORE_EPS_PER_INV_TEMPERATURE_F16X1 if single else self.RESCORE_EPS_PER_INV_TEMPERATURE) * inv_tau
         if single:
-            out = {"eps_rigorous": 2.0 * inv_tau, "eps_default": default, "eps_rigorous_usable": False}
-        else:
-            terms = self._bound_from_weights(eng.spec)
-            bound = float(terms.get("eps", math.inf))
-            out = {"eps_rigorous": bound, "eps_default": default, "eps_rigorous_usable": bool(math.isfinite(bound) and eng.exact is not None),
-                   "eps_rigorous_terms": {k: v for k, v in terms.items() if k != "eps"}}
-            if eng.exact is not None and self._item_embeddings.is_cuda:
-                from . import arith_check
+            return {"eps_rigorous": 2.0 * inv_tau, "eps_default": default, "eps_rigorous_usable": False}
+        pol = self._evaluated(eng.spec, eng.lib)
+        bound = float(pol.terms.get("eps", math.inf))
+        out = {"eps_rigorous": bound, "eps_default": default, "eps_rigorous_usable": bool(math.isfinite(bound) and eng.exact is not None),
+               "eps_rigorous_terms": {k: v for k, v in pol.terms.items() if k != "eps"}}
+        if eng.exact is not None and self._item_embeddings.is_cuda:
+            from . import arith_check
 
-                out["arithmetic_model_on_device"] = arith_check.report(self._item_embeddings.device)     # H1-H3 re-measured on this device (worst error / bound)
-            if eng.exact is not None and self._upper_poly() is not None:
-                # one eps for every pair is too coarse for this shape: the first pass adds a per-pair bound (quadratic in the pair's largest
-                # |cross logit|) to its logit and the verdict compares upper bounds with exact scores, eps = 0
-                info = self._upper_poly_info or {}
-                out.update({"bound_kind": "per-pair upper bound", "upper_bound_poly": list(self._upper_poly()), "eps_of_max_abs_cl": info.get("eps_of_c")})
-        self._rig_cache = (eng, out)
+            out["arithmetic_model_on_device"] = arith_check.report(self._item_embeddings.device)     # H1-H3 re-measured on this device (worst error / bound)
+        if eng.exact is not None and pol.poly is not None:
+            # one eps for every pair is too coarse for this shape: the first pass adds a per-pair bound (quadratic in the pair's largest
+            # |cross logit|) to its logit and the verdict compares upper bounds with exact scores, eps = 0
+            out.update({"bound_kind": "per-pair upper bound", "upper_bound_poly": list(pol.poly), "eps_of_max_abs_cl": pol.eps_of_c})
         return out
 
     # Shadow audit: every AUDIT_EVERY-th verified call is ALSO run on the dense fp32 path and compared bit for bit; the counts are in
@@ -917,8 +930,7 @@ class MoLBruteForceTopK(MoLTopKModule):
             self.rescore_stats["mismatches"] = int(self._audit_bad.item())
         return dict(self.rescore_stats)
 
-    SAFETY_F16X3 = 8.0      # eps >= SAFETY x the running maximum of |s16 - s32| over the re-scored candidates and probes
-    SAFETY_F16X1 = 3.0
+    SAFETY_F16X1 = 3.0      # eps >= SAFETY x the running maximum of |s16 - s32| over the re-scored candidates and probes
 
     # Speculation pays on large corpora only: below SPECULATE_MIN_ITEMS the fixed cost of the verification (~0.1 ms) exceeds what
     # the faster first pass saves (ML-20M, 27 278 items: fp32 step 0.26 ms; amzn-books shape at 16 384 items: 0.19 against 0.21 ms of GPU time,
@@ -1017,12 +1029,7 @@ class MoLBruteForceTopK(MoLTopKModule):
         B, N = query_embeddings.size(0), self._index.n_items
         have32 = self._index32 is not None and self._index32_engine is ex
         if have32 and B * N * 4 <= self.MAX_LOGIT_BYTES:
-            n_q = ex.lib.rails_mol_query_pack_floats(E.C.byref(ex.shape), B)
-            qpack32, _, _ = ex.query_pack(query_embeddings, kwargs.get("user_ids"), out=None if _private else self._buf("qpack32", n_q, torch.float32))
-            out = None if _private else self._buf("logits", B * N, torch.float32).view(B, N)
-            ws = None if _private else self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(B, N, k), torch.uint8)
-            scores, ids = E.topk(ex.score_dense(qpack32, B, self._index32, out=out), k, ids=self._ids_flat, workspace=ws)
-            return scores.to(query_embeddings.dtype), ids
+            return self._dense_topk(query_embeddings, k, _eng=ex, _index=self._index32, _tag="qpack32", _private=_private, **kwargs)
         if have32:
             return self._forward_chunked(query_embeddings, k, _engine=ex, _index=self._index32, **kwargs)
         # no resident fp32 index: temporary per-chunk indexes (CHUNK_ITEMS rows at a time), merged like _forward_chunked
@@ -1048,6 +1055,18 @@ class MoLBruteForceTopK(MoLTopKModule):
             self._recent.clear()
             self._verdict_state = None
             self._state_pending = None
+            if eng.dense_precision == "f16x3":
+                self.rescore_stats["proved_calls"] = 0
+                self.rescore_stats["bound_violations"] = 0
+        if eng.exact is not None and self._policy.eps is None and eng.dense_precision == "f16x3":
+            # the bound for this engine, once: its form, the eps handed to the verdict and the device-side guard limit GATE_GUARD / max |gi|
+            pol = self._evaluated(eng.spec, eng.lib)
+            if math.isfinite(float(pol.terms.get("eps", math.inf))):
+                pol = pol.with_guard(self._gi_abs_max())
+                self._gate_guard_limit = pol.guard_limit
+            else:
+                pol = pol._replace(eps=math.inf)
+            self._policy = pol
         if eng.exact is not None and self._index32_engine is not eng.exact and self.keep_dense_fp32_index is not False:
             # precision "f16x3-exact": a dense fp32 index next to the f16x3 one makes the candidates a gather (10 us) instead of
             # an index build of their raw rows (160 us), and is the fallback's index.  Same bytes again; skipped (None) when
@@ -1070,12 +1089,12 @@ class MoLBruteForceTopK(MoLTopKModule):
 def _pinned_word(module) -> torch.Tensor:
     """One int32 in pinned host memory, zeroed on the device by the first launch of the call that takes it.  A word goes back to the module's
     free list only when its verdict has been read (_release_words): a call of many slices, or several batches in flight, never share one."""
-    free = module.__dict__.setdefault("_flag_free", [])
+    free = module._flag_free
     return free.pop() if free else torch.zeros(1, dtype=torch.int32).pin_memory()
 
 
 def _release_words(module, words) -> None:
-    free = module.__dict__.setdefault("_flag_free", [])
+    free = module._flag_free
     for w in words:
         if not w.is_cuda and len(free) < 64:
             free.append(w)
@@ -1121,7 +1140,7 @@ class MoLAvgTopK(MoLTopKModule):
             return True
         if self.DEVICE_REDO_BYTES <= 0 or self.DEVICE_REDO_FREE_FRACTION <= 0.0:     # tests: "as if it did not fit"
             return False
-        memo = self.__dict__.setdefault("_redo_fit_memo", {})
+        memo = self._redo_fit_memo
         if nbytes not in memo:
             free, _ = torch.cuda.mem_get_info(self._item_embeddings.device)
             memo[nbytes] = nbytes <= self.DEVICE_REDO_FREE_FRACTION * free
@@ -1141,6 +1160,9 @@ class MoLAvgTopK(MoLTopKModule):
         self._verdict_pool: list = []
         self._side_streams = None
         self._side_turn = 0
+        self._prefilter_calls = 0                 # scans that looked at the int8 copy (the schedule of its statistics check)
+        self._prefilter_pending = None            # (pinned copy of the header's counts, its event) on its way to the host
+        self._redo_fit_memo: Dict[int, bool] = {} # _device_redo_fits by buffer size
 
     OVERLAP_BATCHES = True            # submit(): speculative calls alternate between two streams of the module (see submit)
     PREFILTER_MIN_ITEMS = 4_000_000   # the int8 copy of the coarse table pays where the streaming pass is bound by HBM reads
@@ -1166,8 +1188,8 @@ class MoLAvgTopK(MoLTopKModule):
             # both copies.  The select scans keep (fired, tested) counts in the header; looked at now and then -- WITHOUT a host wait:
             # the 16 bytes are copied to pinned memory behind the launches already enqueued and read by a later call, once the copy
             # has landed (a blocking read here stalled the submit / result pipeline on call 3 and on every 64th call)
-            self._prefilter_calls = getattr(self, "_prefilter_calls", 0) + 1
-            pend = getattr(self, "_prefilter_pending", None)
+            self._prefilter_calls += 1
+            pend = self._prefilter_pending
             first, every = self.PREFILTER_CHECK_CALLS
             if pend is not None:
                 if pend[1].query():
@@ -1214,7 +1236,7 @@ class MoLAvgTopK(MoLTopKModule):
         # large corpora: fused scan + threshold select, no (B, N) score matrix (16 GB per 125 M-item shard at B = 32).
         # Same scores and the same exact top-K' as the materialising path below -- when every query's candidate count
         # landed inside [K', capacity]; the check costs one 128-byte device-to-host copy.
-        if n >= self.fused_coarse_min_items and self._avg_top_k <= 4096 and not getattr(self, "_no_fused", False):
+        if n >= self.fused_coarse_min_items and self._avg_top_k <= 4096 and not self._no_fused:
             on_device = self._device_redo_fits(eq.shape[0] * n * 4, n)
             # a verdict the HOST reads (no device redo, the caller defers the look): the word lives in pinned host memory and the kernels write it
             # there themselves -- no 4-byte copy behind the call's last launch (round 6, as the component scans)
@@ -1384,7 +1406,44 @@ class MoLAvgTopK(MoLTopKModule):
 
 
 class _ComponentCandidates:
-    """Per-component candidate generation shared by MoLNaiveTopK and MoLCombTopK."""
+    """Per-component candidate generation, the rerank of the union and the two-attempt forward shared by MoLNaiveTopK and MoLCombTopK, which
+    supply _candidates(eq, pending) -> (B, _union_width()) positions.  Mixed in BEFORE the MoL base class: its forward / forward_filtered are
+    the modules' own."""
+
+    fused_component_min_items = 262144     # below this the (B * P_Q * P_X, N) component scores are small and one launch chain shorter
+    NO_FILTER_FUSION = False               # tests: True keeps the seen-id filter out of the selection launch
+
+    def __init__(self, **kwargs) -> None:
+        super().__init__(**kwargs)
+        self._comp_engine = None
+        self._comp_table = None
+
+    def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """All the union's candidates ranked, whatever `k` is, as the reference does."""
+        scores, ids = self._ranked(query_embeddings, sorted, None, kwargs)
+        return scores.to(query_embeddings.dtype), ids
+
+    def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
+        """CandidateIndex.get_top_k_outputs' body (the module returns all its candidates whatever k_prime is, the filter keeps the first k unseen):
+        -> (top_k_ids, top_k_scores), or None where the filter does not fit the selection launch (_filter_inside)."""
+        seen = self._filter_inside(self._union_width(), invalid_ids, k)
+        if seen is None:
+            return None
+        ids, scores = self._ranked(query_embeddings, True, seen, kwargs)
+        return ids, scores.to(query_embeddings.dtype)
+
+    def _ranked(self, query_embeddings: torch.Tensor, sorted: bool, seen, kwargs):
+        eng = self._bind()
+        qpack, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
+        for attempt in range(2):     # speculate on the fused scans, verify after everything is enqueued
+            pending: list = []
+            all_indices = self._candidates(eq, pending)
+            out = self._rerank_union(qpack, query_embeddings.size(0), all_indices, sorted, seen, pending)
+            if _verdicts_clear(pending, self):
+                break
+            self._no_fused = True
+        self._no_fused = False
+        return out
 
     UNION_CAP = 16384          # candidates per query the rerank sorts and ranks in one workgroup's LDS (rails_sort_rows_i64 / rails_topk)
     UNION_HARD_CAP = 1 << 20   # beyond UNION_CAP (16x16x64 with k_per_group >= 75: 256 * 75 = 19 200) the two integer / float sorts of the
@@ -1399,7 +1458,7 @@ class _ComponentCandidates:
 
     def _component_table(self) -> torch.Tensor:
         eng = self._bind()
-        if getattr(self, "_comp_engine", None) is not eng:
+        if self._comp_engine is not eng:
             self._comp_engine = eng
             self._comp_table = eng.build_component_table(self._index, self._item_embeddings[0])
         return self._comp_table
@@ -1419,7 +1478,7 @@ class _ComponentCandidates:
             return torch.cat([self._component_topk(eq[b0 : b0 + max_b], k_per_group, pending) for b0 in range(0, eq.shape[0], max_b)], dim=0)
         # large corpora: fused scan + threshold select, no (B*P_Q*P_X, N) score matrix (5.7 GB at amzn-books, B = 32);
         # identical to the materialising path below whenever every row's candidate count is inside [k, capacity]
-        if n >= getattr(self, "fused_component_min_items", 262144) and not getattr(self, "_no_fused", False):
+        if n >= self.fused_component_min_items and not self._no_fused:
             rows = eq.shape[0] * eng.spec.query_dot_product_groups * eng.spec.item_dot_product_groups
             on_device = rows * n * 4 <= MoLAvgTopK.DEVICE_REDO_BYTES
             if on_device:
@@ -1449,7 +1508,7 @@ class _ComponentCandidates:
         list are the first k unseen of its top k + width -- at most `width` scored candidates are seen, and a masked duplicate (-32767.0)
         outranks a scored one only where fewer than k + width scored ones exist, in both forms alike.  -> (invalid_ids, k) where
         rails_topk_candidates_filtered takes the sizes, else None (the caller ranks everything and filters after)."""
-        if invalid_ids is None or invalid_ids.dim() != 2 or getattr(self, "NO_FILTER_FUSION", False):
+        if invalid_ids is None or invalid_ids.dim() != 2 or self.NO_FILTER_FUSION:
             return None
         width = invalid_ids.shape[1]
         if not E.topk_candidates_filterable(n_candidates, min(k + width, n_candidates), width, k):
@@ -1469,7 +1528,7 @@ class _ComponentCandidates:
         eng = self._bind()
         big = all_indices.shape[1] > self.UNION_CAP
         word = next((b for b in (pending or []) if not b.is_cuda), None)
-        if seen is not None and word is not None and self.UNSORTED_RERANK and not getattr(self, "_no_fused", False):
+        if seen is not None and word is not None and self.UNSORTED_RERANK and not self._no_fused:
             invalid_ids, k_out = seen
             pos = all_indices.to(torch.int64).contiguous()
             scores = self._score_at(eng, qpack, batch, pos)
@@ -1488,7 +1547,7 @@ class _ComponentCandidates:
         return E.topk_candidates(scores, k, sorted_idx, self._ids_flat)
 
 
-class MoLNaiveTopK(MoLTopKModule, _ComponentCandidates):
+class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
     """Reference rails/indexing/mol_top_k.py:133-293.  Returns (B, P_Q * P_X * k_per_group) columns whatever `k` is, as the reference does.
     use_faiss=True (the reference's FAISS-GPU branch, :176-239): the per-group candidates come from a native IVF-Flat index
     (engine.IvfIndex) built at the first call -- nlist lists per item group, nprobe of them searched per query component -- instead of the
@@ -1530,35 +1589,12 @@ class MoLNaiveTopK(MoLTopKModule, _ComponentCandidates):
             return self.ivf_index().search(eq, self._k_per_group, nprobe=self.nprobe)
         return self._component_topk(eq, self._k_per_group, pending)
 
-    def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        scores, ids = self._ranked(query_embeddings, sorted, None, kwargs)
-        return scores.to(query_embeddings.dtype), ids
-
-    def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
-        """CandidateIndex.get_top_k_outputs' body (the module returns all its candidates whatever k_prime is, the filter keeps the first k unseen):
-        -> (top_k_ids, top_k_scores), or None where the filter does not fit the selection launch (_filter_inside)."""
+    def _union_width(self) -> int:
         mol = self._mol_module
-        seen = self._filter_inside(mol._query_dot_product_groups * mol._item_dot_product_groups * self._k_per_group, invalid_ids, k)
-        if seen is None:
-            return None
-        ids, scores = self._ranked(query_embeddings, True, seen, kwargs)
-        return ids, scores.to(query_embeddings.dtype)
-
-    def _ranked(self, query_embeddings: torch.Tensor, sorted: bool, seen, kwargs):
-        eng = self._bind()
-        qpack, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
-        for attempt in range(2):     # speculate on the fused scans, verify after everything is enqueued
-            pending: list = []
-            all_indices = self._candidates(eq, pending)
-            out = self._rerank_union(qpack, query_embeddings.size(0), all_indices, sorted, seen, pending)
-            if _verdicts_clear(pending, self):
-                break
-            self._no_fused = True
-        self._no_fused = False
-        return out
+        return mol._query_dot_product_groups * mol._item_dot_product_groups * self._k_per_group
 
 
-class MoLCombTopK(MoLAvgTopK, _ComponentCandidates):
+class MoLCombTopK(_ComponentCandidates, MoLAvgTopK):
     """Reference rails/indexing/mol_top_k.py:432-551: per-component candidates + the averaged-query coarse
     candidates, reranked together.  Returns (B, P_Q * P_X * k_per_group + avg_top_k) columns."""
 
@@ -1567,32 +1603,14 @@ class MoLCombTopK(MoLAvgTopK, _ComponentCandidates):
         self._k_per_group: int = k_per_group
         self._check_union_size(mol_module._query_dot_product_groups * mol_module._item_dot_product_groups * k_per_group + avg_top_k)
 
-    def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        scores, ids = self._ranked(query_embeddings, sorted, None, kwargs)
-        return scores.to(query_embeddings.dtype), ids
-
-    def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
-        """As MoLNaiveTopK.forward_filtered, over the component candidates + the averaged-query candidates."""
+    def _union_width(self) -> int:
         mol = self._mol_module
-        seen = self._filter_inside(mol._query_dot_product_groups * mol._item_dot_product_groups * self._k_per_group + self._avg_top_k, invalid_ids, k)
-        if seen is None:
-            return None
-        ids, scores = self._ranked(query_embeddings, True, seen, kwargs)
-        return ids, scores.to(query_embeddings.dtype)
+        return mol._query_dot_product_groups * mol._item_dot_product_groups * self._k_per_group + self._avg_top_k
 
-    def _ranked(self, query_embeddings: torch.Tensor, sorted: bool, seen, kwargs):
-        eng = self._bind()
-        qpack, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
-        for attempt in range(2):
-            pending: list = []
-            comp = self._component_topk(eq, self._k_per_group, pending)
-            avg_idx = self._coarse_topk_from_eq(eq, average_queries=True, pending=pending)
-            out = self._rerank_union(qpack, query_embeddings.size(0), torch.cat([comp, avg_idx], dim=1), sorted, seen, pending)
-            if _verdicts_clear(pending, self):
-                break
-            self._no_fused = True
-        self._no_fused = False
-        return out
+    def _candidates(self, eq: torch.Tensor, pending: list) -> torch.Tensor:
+        comp = self._component_topk(eq, self._k_per_group, pending)
+        avg_idx = self._coarse_topk_from_eq(eq, average_queries=True, pending=pending)
+        return torch.cat([comp, avg_idx], dim=1)
 
 
 class MIPSTopKModule(TopKModule):

@@ -1687,7 +1687,7 @@ def test_f16x3_exact_ties_and_forced_fallback(dev, mode):
         assert bool((r_s[:, 0] == r_s[:, 7]).all())           # the ties are real
         before = tk.stats()["fallbacks"]
         if mode == "f16x3-exact":     # the verdicts run on the a-priori bound: make it absurd
-            tk._proved_eps_cache = (tk._engine, 1.0e9)
+            tk._policy = tk._policy._replace(eps=1.0e9)
         else:
             tk.RESCORE_EPS_PER_INV_TEMPERATURE_F16X1 = float("inf")
         s, i = tk(q, k=204)

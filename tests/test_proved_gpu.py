@@ -320,6 +320,7 @@ def test_proved_mode_is_the_default_and_equals_dense_fp32(dev, workload, N, B, k
             # 16x16x64: one a-priori eps (3.0 logit units) is beyond PROVED_MAX_EPS -> the first pass writes per-pair upper bounds instead
             per_pair = cfg.num_logits > 64 or N <= rails_amd.MoLBruteForceTopK.PER_PAIR_MAX_ITEMS      # ... and small corpora take them whatever their eps
             assert (tk._upper_poly() is not None) == per_pair
+            assert tk._policy.kind == ("upper" if per_pair else "eps")      # (27 278 items: "upper", with the library's own shape query)
             for _ in range(3):
                 s, i = tk(q, k=k, **kw)
                 assert torch.equal(s, r_s) and torch.equal(i, r_i)
