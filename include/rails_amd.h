@@ -43,9 +43,10 @@ extern "C" {
  * 12: the HSTU cached-decoding entries rails_hstu_decode[_supported] and struct rails_hstu_decode_layer are new;
  * 13: the SASRec cached-decoding entries rails_sasrec_decode[_supported] / rails_sasrec_decode_workspace_floats and struct
  * rails_sasrec_decode_layer are new;
- * 14: the IVF-Flat component index rails_ivf_* (MoLNaiveTopK use_faiss=True) is new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
+ * 14: the IVF-Flat component index rails_ivf_* (MoLNaiveTopK use_faiss=True) is new;
+ * 15: the shape-generic fp32 scoring route rails_mol_generic_* is new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
-#define RAILS_ABI_VERSION 14
+#define RAILS_ABI_VERSION 15
 int rails_abi_version(void);
 
 #define RAILS_OK 0
@@ -208,6 +209,32 @@ int rails_mol_score_dense_upper(const rails_mol_shape* shape, const float* gate_
 int rails_mol_score_candidates(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack,
                                int32_t batch, const float* cand_index, int64_t n_cand, float* logits,
                                int64_t ld, void* stream);
+/* ---- The shape-generic scoring route: runtime-shape exact-fp32 kernels for the MoL shapes rails_mol_shape_supported refuses.
+ * Envelope: precision RAILS_PRECISION_FP32, a pair gate with a hidden layer (1 <= gating_qi_hidden_dim <= 512),
+ * P_Q * P_X <= 256, dot_product_dimension <= 256, and whatever the query prologue (64 KiB of LDS) and the index build (160 KiB)
+ * take; every variant axis of the fused route (GLU / Linear projections, uid tables, both gating combinations, l2 norm on / off).
+ * The route has its own packs (row-major, see rails_amd/csrc/mol_generic.h): a generic index, query pack or gate pack is not
+ * interchangeable with the fused route's.  Eq, Ex, gq and gi are computed by the fused route's own prologue / index-build
+ * arithmetic.  A pair's logit has the same bits whatever the batch, the row, the item position, n_items, and whether
+ * rails_mol_generic_score_dense or rails_mol_generic_score_candidates scored it.  A shape the fused route supports is accepted too
+ * (the caller decides the route; the two routes agree to rounding, not bit for bit).
+ * rails_mol_generic_supported and the three size helpers answer without a device. */
+int rails_mol_generic_supported(const rails_mol_shape* shape);
+size_t rails_mol_generic_gate_pack_floats(const rails_mol_shape* shape);
+size_t rails_mol_generic_index_floats(const rails_mol_shape* shape, int64_t n_items);   /* whole tiles of 32 items, stored back to back */
+size_t rails_mol_generic_query_pack_floats(const rails_mol_shape* shape, int32_t batch);
+int rails_mol_generic_pack_gate_weights(const rails_mol_shape* shape, const rails_mol_weights* w, float* gate_pack, void* stream);
+int rails_mol_generic_index_build(const rails_mol_shape* shape, const rails_mol_weights* w, const float* items, int64_t n_items, float* index,
+                                  void* stream);
+int rails_mol_generic_index_unpack(const rails_mol_shape* shape, const float* index, int64_t n_items, float* ex_out, float* gi_out, void* stream);
+int rails_mol_generic_query_prologue(const rails_mol_shape* shape, const rails_mol_weights* w, const float* queries, const int64_t* user_ids,
+                                     int32_t batch, float* query_pack, float* eq_out, float* gq_out, void* stream);
+/* logits[b * ld + x] for x < n_items; run_if as in rails_mol_score_dense */
+int rails_mol_generic_score_dense(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch, const float* index,
+                                  int64_t n_items, float* logits, int64_t ld, const int32_t* run_if, void* stream);
+/* per-row candidates: candidate j of row b is item b * n_cand + j of `cand_index` (a generic index of batch * n_cand items; any n_cand) */
+int rails_mol_generic_score_candidates(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch,
+                                       const float* cand_index, int64_t n_cand, float* logits, int64_t ld, const int32_t* run_if, void* stream);
 /* Per-row candidates scored IN PLACE: logits[b][j] = MoL(query b, item positions[b][j]) with the item operands read straight from the
  * shared index -- rails_mol_index_gather + rails_mol_score_candidates without the gathered copy and its launch (same arithmetic per
  * pair, same bits).  Exact-fp32 shapes on the independent-wave shell (rails_mol_score_indexed_supported != 0); the 256-logit shape

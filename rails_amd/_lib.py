@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RAILS_AMD_LIBRARY: load another build of the same library (e.g. the parent commit's, for an A/B run in one place)
 LIB_PATH = os.environ.get("RAILS_AMD_LIBRARY") or os.path.join(_HERE, "librails_amd.so")
 
-RAILS_ABI_VERSION = 14  # include/rails_amd.h
+RAILS_ABI_VERSION = 15  # include/rails_amd.h
 RAILS_OK = 0
 RAILS_EINVAL = -22
 RAILS_ENOTSUP = -95
@@ -164,6 +164,26 @@ PROTOTYPES = {
     "rails_mol_score_candidates": (
         C.c_int,
         [_SHAPE_P, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    # the shape-generic fp32 scoring route (same argument lists as the fused counterparts; score_candidates also takes run_if)
+    "rails_mol_generic_supported": (C.c_int, [_SHAPE_P]),
+    "rails_mol_generic_gate_pack_floats": (C.c_size_t, [_SHAPE_P]),
+    "rails_mol_generic_index_floats": (C.c_size_t, [_SHAPE_P, C.c_int64]),
+    "rails_mol_generic_query_pack_floats": (C.c_size_t, [_SHAPE_P, C.c_int32]),
+    "rails_mol_generic_pack_gate_weights": (C.c_int, [_SHAPE_P, _WEIGHTS_P, C.c_void_p, C.c_void_p]),
+    "rails_mol_generic_index_build": (C.c_int, [_SHAPE_P, _WEIGHTS_P, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_mol_generic_index_unpack": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rails_mol_generic_query_prologue": (
+        C.c_int,
+        [_SHAPE_P, _WEIGHTS_P, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "rails_mol_generic_score_dense": (
+        C.c_int,
+        [_SHAPE_P, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    ),
+    "rails_mol_generic_score_candidates": (
+        C.c_int,
+        [_SHAPE_P, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     ),
     "rails_mips_index_floats": (C.c_size_t, [C.c_int32, C.c_int64]),
     "rails_mips_index_build": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),

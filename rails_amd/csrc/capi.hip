@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "mol_generic.h"
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
@@ -78,6 +79,53 @@ static bool shape_supported(const Shape* s) {
               "(built: 8x4x64, 8x4x128, 8x8x32, 16x16x64 with 128)",
               s->query_dot_product_groups, s->item_dot_product_groups, s->dot_product_dimension,
               s->gating_qi_hidden_dim);
+    return false;
+  }
+  return true;
+}
+
+// The generic route's envelope (mol_generic.h): answered without a device.
+static bool generic_supported(const Shape* s) {
+  if (!shape_ok(s)) return false;
+  if (s->precision != RAILS_PRECISION_FP32) {
+    set_error("the generic scoring route is exact fp32 only (precision RAILS_PRECISION_FP32), got precision %d", s->precision);
+    return false;
+  }
+  if (s->gating_qi_hidden_dim <= 0) {
+    set_error("the generic scoring route needs a pair gate with a hidden layer (gating_qi_hidden_dim >= 1)");
+    return false;
+  }
+  if (s->gating_qi_hidden_dim > kGenericMaxH) {
+    set_error("the generic scoring route takes gating_qi_hidden_dim <= %d, got %d", kGenericMaxH, s->gating_qi_hidden_dim);
+    return false;
+  }
+  if ((int64_t)s->query_dot_product_groups * s->item_dot_product_groups > kGenericMaxL) {
+    set_error("the generic scoring route takes P_Q * P_X <= %d, got %dx%d = %lld", kGenericMaxL, s->query_dot_product_groups,
+              s->item_dot_product_groups, (long long)s->query_dot_product_groups * s->item_dot_product_groups);
+    return false;
+  }
+  if (s->dot_product_dimension > kGenericMaxD) {
+    set_error("the generic scoring route takes dot_product_dimension <= %d, got %d", kGenericMaxD, s->dot_product_dimension);
+    return false;
+  }
+  if (s->gating_combination != RAILS_COMBINE_GLU_SILU && s->gating_combination != RAILS_COMBINE_NONE) {
+    set_error("gating_combination must be RAILS_COMBINE_GLU_SILU or RAILS_COMBINE_NONE, got %d", s->gating_combination);
+    return false;
+  }
+  if (s->gating_combination == RAILS_COMBINE_GLU_SILU && (!s->gating_has_query || !s->gating_has_item)) {
+    set_error("gating_combination glu_silu needs the query-only and the item-only gate part (the reference multiplies them)");
+    return false;
+  }
+  if ((s->gating_has_query && s->gating_query_hidden_dim <= 0) || (s->gating_has_item && s->gating_item_hidden_dim <= 0)) {
+    set_error("gating hidden dims must be > 0 for the gate parts that exist");
+    return false;
+  }
+  if (index_build_lds_bytes(*s) > kIndexBuildMaxLds) {
+    set_error("index build needs %zu B of LDS (> 160 KiB) for this shape", index_build_lds_bytes(*s));
+    return false;
+  }
+  if (query_prologue_lds_bytes(*s) > kQueryPrologueMaxLds) {
+    set_error("query prologue needs %zu B of LDS (> 64 KiB) for this shape", query_prologue_lds_bytes(*s));
     return false;
   }
   return true;
@@ -366,6 +414,98 @@ int rails_mol_score_indexed_rows(const rails_mol_shape* s, const float* gate_pac
 int rails_mol_score_candidates(const rails_mol_shape* s, const float* gate_pack, const float* query_pack, int32_t batch,
                                const float* cand_index, int64_t n_cand, float* logits, int64_t ld, void* stream) {
   return score_common(s, gate_pack, query_pack, batch, cand_index, n_cand, logits, ld, 1, stream, "score_candidates");
+}
+
+// ---- the shape-generic scoring route (mol_generic.hip) ----
+int rails_mol_generic_supported(const rails_mol_shape* shape) { g_err[0] = '\0'; return generic_supported(shape) ? 1 : 0; }
+
+size_t rails_mol_generic_gate_pack_floats(const rails_mol_shape* s) { return generic_supported(s) ? gen_gate_pack_floats(*s) : 0; }
+
+size_t rails_mol_generic_index_floats(const rails_mol_shape* s, int64_t n_items) {
+  if (!generic_supported(s) || n_items < 0) return 0;
+  return (size_t)(num_tiles(n_items) * 32 * gen_item_floats(*s));
+}
+
+size_t rails_mol_generic_query_pack_floats(const rails_mol_shape* s, int32_t batch) {
+  if (!generic_supported(s) || batch < 0) return 0;
+  return (size_t)batch * (size_t)gen_query_floats(*s);
+}
+
+int rails_mol_generic_pack_gate_weights(const rails_mol_shape* s, const rails_mol_weights* w, float* gate_pack, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (!w || !gate_pack || !w->gqi_w1 || !w->gqi_b1 || !w->gqi_w2 || !w->gqi_b2) { set_error("generic_pack_gate_weights: NULL pointer"); return RAILS_EINVAL; }
+  return fail(generic_pack_gate_weights(*s, *w, gate_pack, (hipStream_t)stream), "generic_pack_gate_weights");
+}
+
+int rails_mol_generic_index_build(const rails_mol_shape* s, const rails_mol_weights* w, const float* items, int64_t n_items, float* index,
+                                  void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (n_items < 0) { set_error("generic_index_build: n_items < 0"); return RAILS_EINVAL; }
+  if (n_items == 0) return RAILS_OK;
+  if (!w || !items || !index || !w->i_proj_w || !w->i_proj_b || (s->gating_has_item && (!w->gi_w1 || !w->gi_b1 || !w->gi_w2)) ||
+      (s->item_hidden_dim > 0 && (!w->i_glu_w || !w->i_glu_b))) {
+    set_error("generic_index_build: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  const int r = index_build_plain(*s, *w, items, n_items, index, gen_item_floats(*s), gen_dp(*s), gen_lq(*s), (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "generic_index_build");
+}
+
+int rails_mol_generic_index_unpack(const rails_mol_shape* s, const float* index, int64_t n_items, float* ex_out, float* gi_out, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (n_items <= 0 || (!ex_out && !gi_out)) return RAILS_OK;
+  if (!index) { set_error("generic_index_unpack: NULL index"); return RAILS_EINVAL; }
+  return fail(generic_index_unpack(*s, index, n_items, ex_out, gi_out, (hipStream_t)stream), "generic_index_unpack");
+}
+
+int rails_mol_generic_query_prologue(const rails_mol_shape* s, const rails_mol_weights* w, const float* queries, const int64_t* user_ids,
+                                     int32_t batch, float* query_pack, float* eq_out, float* gq_out, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (batch < 0) { set_error("generic_query_prologue: batch < 0"); return RAILS_EINVAL; }
+  if (batch == 0) return RAILS_OK;
+  if (!w || !queries || !query_pack || !w->q_proj_w || !w->q_proj_b || (s->query_hidden_dim > 0 && (!w->q_glu_w || !w->q_glu_b)) ||
+      (s->gating_has_query && (!w->gq_w1 || !w->gq_b1 || !w->gq_w2))) {
+    set_error("generic_query_prologue: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  if (s->num_uid_tables > 0) {
+    if (!user_ids) { set_error("generic_query_prologue: user_ids is required when num_uid_tables > 0"); return RAILS_EINVAL; }
+    for (int t = 0; t < s->num_uid_tables; ++t)
+      if (!w->uid_table[t] || w->uid_hash_size[t] <= 0) { set_error("generic_query_prologue: uid table %d missing", t); return RAILS_EINVAL; }
+  }
+  const int r = query_prologue_plain(*s, *w, queries, user_ids, batch, query_pack, gen_query_floats(*s), gen_dp(*s), eq_out, gq_out, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "generic_query_prologue");
+}
+
+static int generic_score_common(const rails_mol_shape* s, const float* gate_pack, const float* query_pack, int32_t batch, const float* index,
+                                int64_t n_items, float* logits, int64_t ld, int per_row, const int32_t* run_if, void* stream, const char* what) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (batch < 0 || n_items < 0) { set_error("%s: negative size", what); return RAILS_EINVAL; }
+  if (batch == 0 || n_items == 0) return RAILS_OK;
+  if (!gate_pack || !query_pack || !index || !logits) { set_error("%s: NULL pointer", what); return RAILS_EINVAL; }
+  if (ld < n_items) { set_error("%s: ld (%lld) < n_items (%lld)", what, (long long)ld, (long long)n_items); return RAILS_EINVAL; }
+  const int cu = compute_units();
+  if (cu <= 0) { set_error("%s: no HIP device", what); return RAILS_ELAUNCH; }
+  GenericScoreArgs a{};
+  a.wpack = gate_pack; a.qpack = query_pack; a.ipack = index; a.logits = logits; a.ld = ld; a.n_items = n_items; a.B = batch;
+  a.per_row = per_row; a.run_if = run_if;
+  const int r = generic_score(*s, a, cu, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, what);
+}
+
+int rails_mol_generic_score_dense(const rails_mol_shape* s, const float* gate_pack, const float* query_pack, int32_t batch, const float* index,
+                                  int64_t n_items, float* logits, int64_t ld, const int32_t* run_if, void* stream) {
+  return generic_score_common(s, gate_pack, query_pack, batch, index, n_items, logits, ld, 0, run_if, stream, "generic_score_dense");
+}
+
+int rails_mol_generic_score_candidates(const rails_mol_shape* s, const float* gate_pack, const float* query_pack, int32_t batch,
+                                       const float* cand_index, int64_t n_cand, float* logits, int64_t ld, const int32_t* run_if, void* stream) {
+  return generic_score_common(s, gate_pack, query_pack, batch, cand_index, n_cand, logits, ld, 1, run_if, stream, "generic_score_candidates");
 }
 
 size_t rails_mips_index_floats(int32_t dim, int64_t n_items) {

@@ -1,0 +1,52 @@
+// The shape-generic fp32 scoring route (mol_generic.hip): runtime-shape kernels for the MoL shapes that have no fused kernel.
+//
+// Layouts (all fp32, row-major, padded to the kernels' vector width):
+//   item index   per item  [P_X][dp] Ex (dp = d rounded up to 8, pad = 0), then [Lq] gi (Lq = L rounded up to 4, pad = 0);
+//                the buffer holds a whole number of 32-item tiles, rows beyond n_items are zeros
+//   query pack   per query [P_Q][dp] Eq / tau (pad = 0), then [Lq] gq
+//   gate pack    W1 and W2 in the A-operand order of v_mfma_f32_32x32x2_f32 (zero-padded to Hp = H rounded up to 32 and
+//                Lp = L rounded up to 32), then b1 [Hp], b2 [Lp]
+// Eq, Ex, gq and gi are computed by the prologue / index-build kernels of the fused route (mol_query.hip, mol_index.hip), which
+// only write them in this layout instead of fragment order: the same values on both routes.
+#pragma once
+#include "mol_kernels.h"
+
+namespace mol {
+
+constexpr int kGenericMaxL = 256, kGenericMaxD = 256, kGenericMaxH = 512;
+
+inline int gen_dp(const Shape& s) { return (s.dot_product_dimension + 7) / 8 * 8; }
+inline int gen_lq(const Shape& s) { return (num_logits(s) + 3) / 4 * 4; }
+inline int gen_lp(const Shape& s) { return (num_logits(s) + 31) / 32 * 32; }
+inline int gen_hp(const Shape& s) { return (s.gating_qi_hidden_dim + 31) / 32 * 32; }
+inline int64_t gen_item_floats(const Shape& s) { return (int64_t)s.item_dot_product_groups * gen_dp(s) + gen_lq(s); }
+inline int64_t gen_query_floats(const Shape& s) { return (int64_t)s.query_dot_product_groups * gen_dp(s) + gen_lq(s); }
+inline size_t gen_gate_pack_floats(const Shape& s) { return 2 * (size_t)gen_hp(s) * gen_lp(s) + gen_hp(s) + gen_lp(s); }
+
+// LDS of the prologue / index-build kernels for a shape (the limits the generic route inherits from them)
+size_t index_build_lds_bytes(const Shape& s);
+size_t query_prologue_lds_bytes(const Shape& s);
+constexpr size_t kQueryPrologueMaxLds = 64 * 1024;
+constexpr size_t kIndexBuildMaxLds = 160 * 1024;
+
+// mol_index.hip / mol_query.hip: the fused route's arithmetic, written row-major (`ld` floats per item / query)
+int index_build_plain(const Shape& s, const Weights& w, const float* items, int64_t n, float* out, int64_t ld, int dp, int lq, hipStream_t stream);
+int query_prologue_plain(const Shape& s, const Weights& w, const float* q, const int64_t* user_ids, int B, float* qpack, int64_t ld, int dp,
+                         float* eq_out, float* gq_out, hipStream_t stream);
+
+struct GenericScoreArgs {
+  const float* wpack;
+  const float* qpack;
+  const float* ipack;
+  float* logits;
+  int64_t ld;
+  int64_t n_items;      // shared corpus: items of the index; per-row candidates: candidates per row
+  int B;
+  int per_row;          // 1: candidate j of row b is item row b * n_items + j
+  const int32_t* run_if;
+};
+int generic_pack_gate_weights(const Shape& s, const Weights& w, float* wpack, hipStream_t stream);
+int generic_index_unpack(const Shape& s, const float* ipack, int64_t n, float* ex, float* gi, hipStream_t stream);
+int generic_score(const Shape& s, const GenericScoreArgs& a, int n_cu, hipStream_t stream);
+
+}  // namespace mol

@@ -8,6 +8,7 @@
 // fetch of the hot loop is one contiguous 1 KiB per wave.
 #include <hip/hip_runtime.h>
 
+#include "mol_generic.h"
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
@@ -185,6 +186,11 @@ struct BuildArgs {
   int D, PQ, PX, d, Hi;
   int l2norm;
   float eps;
+  // generic route (mol_generic.h): the same values written row-major instead of in fragment order -- item x at plain + x * plain_ld
+  // as [PX][dp] Ex then [lq] gi, pads zero; NULL = fragment order into ipack
+  float* plain;
+  int64_t plain_ld;
+  int dp, lq;
 };
 
 __device__ __forceinline__ void dense_cols(const float* __restrict__ W, const float* __restrict__ bias, int col0,
@@ -280,8 +286,18 @@ __global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a)
       ns[x * mpc + mg] = a.l2norm ? fmaxf(sqrtf(ss), a.eps) : 1.0f;
     }
     __syncthreads();
+    if (a.plain) {   // row-major: the same quotient, any d
+      const int cols = groups * a.dp;
+      for (int i = threadIdx.x; i < kTileItems * cols; i += kBuildThreads) {
+        const int x = i / cols, c = i - x * cols;
+        const int mg = c / a.dp, k = c - mg * a.dp;
+        float v = 0.0f;
+        if (k < d && item0 + x < a.n) v = cs[x * cs_ld + mg * d + k] / ns[x * mpc + mg];
+        a.plain[(item0 + x) * a.plain_ld + (m0 + mg) * a.dp + k] = v;
+      }
+    }
     // fragment order: Ex slot (m, c8, lane)[j] = Ex[x = lane&31][m][kdim_of(4*c8 + j, lane>>5)]
-    const int slots = groups * (d / 8) * 64;
+    const int slots = a.plain ? 0 : groups * (d / 8) * 64;
     for (int i = threadIdx.x; i < slots; i += kBuildThreads) {
       const int lane = i & 63, c8 = (i >> 6) % (d / 8), mg = (i >> 6) / (d / 8);
       const int x = lane & 31, hi = lane >> 5;
@@ -305,6 +321,13 @@ __global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a)
     for (int i = threadIdx.x; i < kTileItems * L; i += kBuildThreads) cs[(i / L) * cs_ld + i % L] = 0.0f;
   }
   __syncthreads();
+  if (a.plain) {
+    for (int i = threadIdx.x; i < kTileItems * a.lq; i += kBuildThreads) {
+      const int x = i / a.lq, l = i - x * a.lq;
+      a.plain[(item0 + x) * a.plain_ld + PX * a.dp + l] = (l < L && item0 + x < a.n) ? cs[x * cs_ld + l] : 0.0f;
+    }
+    return;
+  }
   for (int i = threadIdx.x; i < (L / 8) * 64; i += kBuildThreads) {
     const int lane = i & 63, ec = i >> 6;
     const int x = lane & 31, hi = lane >> 5;
@@ -326,7 +349,10 @@ static size_t build_lds_bytes(const Shape& s) {
   return sizeof(float) * (size_t)kTileItems * ((s.item_embedding_dim + 1) + (hi_w + 1) + cs_ld + mpc + (ih + 1));
 }
 
-int index_build(const Shape& s, const Weights& w, const float* items, int64_t n, float* ipack, hipStream_t stream) {
+size_t index_build_lds_bytes(const Shape& s) { return build_lds_bytes(s); }
+
+static int index_build_launch(const Shape& s, const Weights& w, const float* items, int64_t n, float* ipack, float* plain, int64_t plain_ld,
+                              int dp, int lq, hipStream_t stream) {
   const int64_t tiles = num_tiles(n);
   if (tiles == 0) return kOk;
   BuildArgs a;
@@ -336,6 +362,7 @@ int index_build(const Shape& s, const Weights& w, const float* items, int64_t n,
   a.gluw = w.i_glu_w; a.glub = w.i_glu_b; a.IH = s.item_hidden_dim > 0 ? s.item_hidden_dim : 0; a.glu_kind = s.item_nonlinearity;
   a.has_gate = s.gating_has_item;
   a.l2norm = s.dot_product_l2_norm; a.eps = s.eps;
+  a.plain = plain; a.plain_ld = plain_ld; a.dp = dp; a.lq = lq;
   const size_t lds = build_lds_bytes(s);
   if (lds > 160 * 1024) { set_error("index build needs %zu B of LDS (> 160 KiB) for this shape", lds); return kErrUnsupported; }
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&index_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -343,6 +370,14 @@ int index_build(const Shape& s, const Weights& w, const float* items, int64_t n,
     return kErrLaunch;
   hipLaunchKernelGGL(index_build_kernel, dim3((unsigned)tiles), dim3(kBuildThreads), lds, stream, a);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int index_build(const Shape& s, const Weights& w, const float* items, int64_t n, float* ipack, hipStream_t stream) {
+  return index_build_launch(s, w, items, n, ipack, nullptr, 0, 0, 0, stream);
+}
+
+int index_build_plain(const Shape& s, const Weights& w, const float* items, int64_t n, float* out, int64_t ld, int dp, int lq, hipStream_t stream) {
+  return index_build_launch(s, w, items, n, nullptr, out, ld, dp, lq, stream);
 }
 
 // ---- precision f16x3: the Ex fragments of a tile, fp32 -> f16 hi/lo, in place ---------------------------------------

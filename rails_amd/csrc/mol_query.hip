@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include "mol_generic.h"
 #include "mol_kernels.h"
 #include "mol_layout.h"
 
@@ -46,6 +47,11 @@ struct QueryArgs {
   float* eqfrag2;   // optional second pack in the OTHER format (fp32 <-> f16 hi/lo), same values: the verified fast modes need both
   float* gqfrag2;
   int has_gate;   // 0: no query-only gate part -> gq = 0
+  // generic route (mol_generic.h; per-query kernel only): the same values row-major instead of in fragment order -- query b at
+  // gen + b * gen_ld as [PQ][gen_dp] Eq / tau then gq (the pads are zeroed by the host); NULL = fragment order
+  float* gen;
+  int64_t gen_ld;
+  int gen_dp;
 };
 
 // One element of a query group's Eq fragment: K index s of lane half hi, accumulator row `row` (= qj*P_Q + p).
@@ -198,7 +204,7 @@ __device__ __forceinline__ float glu_act(const QueryArgs& a, float l, float r) {
 __global__ __launch_bounds__(kQueryThreads) void query_prologue_kernel(QueryArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int D = a.D, d = a.d, PQ = a.PQ, L = a.PQ * a.PX, QH = a.QH;
-  const int QT = 32 / PQ;
+  const int QT = PQ <= 32 ? 32 / PQ : 1;   // (the generic route takes P_Q > 32 and never uses the fragment addresses)
   float* qs = smem;             // [D]
   float* glu = qs + D;          // [2*QH] then [QH]
   float* eqs = glu + 2 * QH;    // [PQ*d]
@@ -234,6 +240,13 @@ __global__ __launch_bounds__(kQueryThreads) void query_prologue_kernel(QueryArgs
       for (int i = threadIdx.x; i < L; i += kQueryThreads) gqs[i] = 0.0f;
     }
     __syncthreads();
+    if (a.gen) {
+      for (int i = threadIdx.x; i < L; i += kQueryThreads) {
+        if (a.gq_out) a.gq_out[(int64_t)b * L + i] = gqs[i];
+        a.gen[(int64_t)b * a.gen_ld + PQ * a.gen_dp + i] = gqs[i];
+      }
+      return;
+    }
     for (int i = threadIdx.x; i < L; i += kQueryThreads) {
       if (a.gq_out) a.gq_out[(int64_t)b * L + i] = gqs[i];
       // gqfrag[b][hi][e] = gq[b][logit_of(e, hi)]
@@ -277,6 +290,7 @@ __global__ __launch_bounds__(kQueryThreads) void query_prologue_kernel(QueryArgs
     const int p = i / d, k = i - p * d;
     const float v = eqs[i] / inv[p];
     if (a.eq_out) a.eq_out[(int64_t)b * PQ * d + i] = v;
+    if (a.gen) { a.gen[(int64_t)b * a.gen_ld + p * a.gen_dp + k] = v / a.temperature; continue; }   // carries 1/tau, as the fragments do
     // EqFrag[g][sc][lane][j] = Eq[g*QT + row/PQ][row%PQ][kdim_of(4sc + j, hi)], lane = hi*32 + row
     const int hi = k / (d / 2), s = k - hi * (d / 2);
     eq_frag_store(eqf, s, hi, qj * PQ + p, v / a.temperature, a.split);  // fragment copy carries 1/tau
@@ -664,6 +678,7 @@ int query_prologue(const Shape& s, const Weights& w, const float* q, const int64
   a.eqfrag2 = qpack_other;
   a.gqfrag2 = qpack_other ? qpack_other + (int64_t)n_groups * 32 * a.d : nullptr;
   a.eq_out = eq_out; a.gq_out = gq_out;
+  a.gen = nullptr; a.gen_ld = 0; a.gen_dp = 0;
   const int L = a.PQ * a.PX;
   // RAILS_PROLOGUE: 0 / unset = choose, 1 = per-query kernel, 2 = batched (MFMA) kernels, 3 = split per-query kernels (measurement override)
   const char* forced_env = getenv("RAILS_PROLOGUE");   // read per call: tests and A/B runs switch it in-process
@@ -704,6 +719,34 @@ int query_prologue(const Shape& s, const Weights& w, const float* q, const int64
   }
   const size_t lds = sizeof(float) * (size_t)(a.D + 2 * a.QH + a.PQ * a.d + a.Hq + a.PQ * a.PX + a.PQ);
   hipLaunchKernelGGL(query_prologue_kernel, dim3(n_groups * QT, 2), dim3(kQueryThreads), lds, stream, a);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+
+size_t query_prologue_lds_bytes(const Shape& s) {
+  const int QH = s.query_hidden_dim > 0 ? s.query_hidden_dim : 0, Hq = s.gating_has_query ? s.gating_query_hidden_dim : 0;
+  return sizeof(float) * ((size_t)s.query_embedding_dim + 2 * (size_t)QH + (size_t)s.query_dot_product_groups * s.dot_product_dimension + Hq +
+                          (size_t)num_logits(s) + s.query_dot_product_groups);
+}
+
+// The per-query kernel (one arithmetic for every batch size) writing the generic route's row-major pack.
+int query_prologue_plain(const Shape& s, const Weights& w, const float* q, const int64_t* user_ids, int B, float* qpack, int64_t ld, int dp,
+                         float* eq_out, float* gq_out, hipStream_t stream) {
+  if (B <= 0) return kOk;
+  QueryArgs a;
+  a.q = q; a.user_ids = user_ids; a.w = w; a.B = B;
+  a.D = s.query_embedding_dim; a.PQ = s.query_dot_product_groups; a.PX = s.item_dot_product_groups;
+  a.d = s.dot_product_dimension; a.QH = s.query_hidden_dim > 0 ? s.query_hidden_dim : 0; a.Hq = s.gating_has_query ? s.gating_query_hidden_dim : 0;
+  a.has_gate = s.gating_has_query;
+  a.n_uid = s.num_uid_tables; a.glu = s.query_nonlinearity; a.l2norm = s.dot_product_l2_norm; a.eps = s.eps; a.temperature = s.temperature;
+  a.split = 0;
+  a.eqfrag = nullptr; a.gqfrag = nullptr; a.eqfrag2 = nullptr; a.gqfrag2 = nullptr;
+  a.eq_out = eq_out; a.gq_out = gq_out;
+  a.gen = qpack; a.gen_ld = ld; a.gen_dp = dp;
+  const size_t lds = query_prologue_lds_bytes(s);
+  if (lds > kQueryPrologueMaxLds) { set_error("query prologue needs %zu B of LDS (> 64 KiB) for this shape", lds); return kErrUnsupported; }
+  if (hipMemsetAsync(qpack, 0, sizeof(float) * (size_t)B * (size_t)ld, stream) != hipSuccess) return kErrLaunch;
+  hipLaunchKernelGGL(query_prologue_kernel, dim3(B, 2), dim3(kQueryThreads), lds, stream, a);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -212,21 +212,36 @@ class MolIndex:
 class MolEngine:
     """One MoL module's weights bound to the HIP kernels."""
 
-    def __init__(self, spec: MolShapeSpec, weights: Dict[str, torch.Tensor], precision: Optional[str] = None):
+    def __init__(self, spec: MolShapeSpec, weights: Dict[str, torch.Tensor], precision: Optional[str] = None, route: Optional[str] = None):
+        """route: None -- the fused kernels where rails_mol_shape_supported says so, else the shape-generic fp32 kernels
+        (rails_mol_generic_*); "generic" -- the generic kernels whatever the shape.  By shape and precision alone, never by size."""
         self.lib = _lib.load()
         self.spec = spec
         precision = precision or default_precision()
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        if route not in (None, "generic"):
+            raise ValueError(f"route must be None or 'generic', got {route!r}")
+        self.route = "fused"
         self.precision = {"f16x3-exact": "f16x3", "f16-exact": "f16x3", "f16x1": "f16x3"}.get(precision, precision)   # format of the packs
-        self.exact: Optional["MolEngine"] = MolEngine(spec, weights, "fp32") if precision.endswith("-exact") else None
         self.shape = spec.to_c(self.precision)
+        if route == "generic":
+            if not self.lib.rails_mol_generic_supported(C.byref(self.shape)):
+                raise NotImplementedError(_lib.last_error())
+            self.route = "generic"
+        elif not self.lib.rails_mol_shape_supported(C.byref(self.shape)):
+            # the fused check's message stays where it names the reason itself (a hidden-layer-free pair gate, a bad combination);
+            # "no fused scoring kernel" is the one the generic route answers
+            fused_msg = _lib.last_error()
+            if not self.lib.rails_mol_generic_supported(C.byref(self.shape)):
+                generic_msg = _lib.last_error()
+                raise NotImplementedError(fused_msg if not fused_msg.startswith("no fused scoring kernel") else f"{fused_msg}; {generic_msg}")
+            self.route = "generic"
+        self.exact: Optional["MolEngine"] = MolEngine(spec, weights, "fp32") if precision.endswith("-exact") else None
         # the shape the DENSE pass is launched with: the one-product kernels for "f16-exact" / "f16x1" (same packs, lo halves ignored)
         self.dense_precision = "f16x1" if precision in ("f16-exact", "f16x1") else self.precision
         self.dense_shape = spec.to_c(self.dense_precision)
         self._fp32_shape = spec.to_c("fp32")     # for the derived bf16 tables, which are cut from an fp32-format index
-        if not self.lib.rails_mol_shape_supported(C.byref(self.shape)):
-            raise NotImplementedError(_lib.last_error())
         self._keep = []  # fp32 contiguous device tensors the weight struct points into
         w = _lib.MolWeights()
         for key, field in spec.weight_fields().items():
@@ -250,13 +265,29 @@ class MolEngine:
         self.device = self._keep[0].device
         if self.precision == "f16x3":
             self._check_f16_range(weights)
-        n = self.lib.rails_mol_gate_pack_floats(C.byref(self.shape))
+        generic = self.route == "generic"
+        n = (self.lib.rails_mol_generic_gate_pack_floats if generic else self.lib.rails_mol_gate_pack_floats)(C.byref(self.shape))
         self.gate_pack = torch.empty(n, dtype=torch.float32, device=self.device)
         with _on_device(self.device):
+            if generic:
+                _lib.check(self.lib.rails_mol_generic_pack_gate_weights(C.byref(self.shape), C.byref(self.weights), _ptr(self.gate_pack), _stream()),
+                           "rails_mol_generic_pack_gate_weights")
+                return
             _lib.check(
                 self.lib.rails_mol_pack_gate_weights(C.byref(self.shape), C.byref(self.weights), _ptr(self.gate_pack), _stream()),
                 "rails_mol_pack_gate_weights",
             )
+
+    def _name(self, name: str) -> str:
+        """Name of the entry point `rails_mol_<name>` of this engine's route (also the label of its error messages)."""
+        return ("rails_mol_generic_" if self.route == "generic" else "rails_mol_") + name
+
+    def _fn(self, name: str):
+        return getattr(self.lib, self._name(name))
+
+    def _fused_only(self, what: str) -> None:
+        if self.route == "generic":
+            raise NotImplementedError(f"{what} is not built on the generic scoring route")
 
     def _check_f16_range(self, weights: Dict[str, torch.Tensor]) -> None:
         """precision='f16x3' keeps cl, hid and the gate weights as f16 hi + lo.  Small values are safe (f16 subnormals are
@@ -281,12 +312,12 @@ class MolEngine:
             raise ValueError(f"item_embeddings must be (N, {self.spec.item_embedding_dim}), got {tuple(items.shape)}")
         items = _f32c(items)
         n = items.shape[0]
-        floats = self.lib.rails_mol_index_floats(C.byref(self.shape), n)
+        floats = self._fn("index_floats")(C.byref(self.shape), n)
         buf = torch.empty(floats, dtype=torch.float32, device=items.device)
         with _on_device(items.device):
             _lib.check(
-                self.lib.rails_mol_index_build(C.byref(self.shape), C.byref(self.weights), _ptr(items), n, _ptr(buf), _stream()),
-                "rails_mol_index_build",
+                self._fn("index_build")(C.byref(self.shape), C.byref(self.weights), _ptr(items), n, _ptr(buf), _stream()),
+                self._name("index_build"),
             )
         return MolIndex(buf, n)
 
@@ -296,13 +327,14 @@ class MolEngine:
         gi = torch.empty((index.n_items, s.num_logits), dtype=torch.float32, device=index.buf.device) if want_gi else None
         with _on_device(index.buf.device):
             _lib.check(
-                self.lib.rails_mol_index_unpack(C.byref(self.shape), _ptr(index.buf), index.n_items, _ptr(ex), _ptr(gi), _stream()),
-                "rails_mol_index_unpack",
+                self._fn("index_unpack")(C.byref(self.shape), _ptr(index.buf), index.n_items, _ptr(ex), _ptr(gi), _stream()),
+                self._name("index_unpack"),
             )
         return ex, gi
 
     def build_index_rows(self, index: MolIndex) -> torch.Tensor:
         """Row-major copy of an exact-fp32 index (include/rails_amd.h rails_mol_index_rows_build): what score_indexed_rows reads candidates from."""
+        self._fused_only("the row-major index copy")
         floats = self.lib.rails_mol_index_rows_floats(C.byref(self.shape), index.n_items)
         if floats == 0:
             raise NotImplementedError("the row-major index copy exists for exact-fp32 indexes only")
@@ -315,6 +347,7 @@ class MolEngine:
                            counts: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """score_indexed with the candidates read from the row-major copy: whole cache lines per candidate, same bits.
         counts: per-row candidate counts (int32 on the device; candidates_select's): only the first counts[b] logits of row b are written."""
+        self._fused_only("score_indexed_rows")
         if positions.dtype != torch.int64 or positions.device != rows.device or not positions.is_contiguous():
             positions = positions.to(device=rows.device, dtype=torch.int64).contiguous()
         n_cand = positions.shape[1]
@@ -330,6 +363,7 @@ class MolEngine:
 
     def gather_index(self, index: MolIndex, cand_idx: torch.Tensor) -> Tuple[MolIndex, int]:
         """cand_idx: (rows, K) int64 positions -> per-row tile-packed index, K padded to a multiple of 32."""
+        self._fused_only("gather_index")
         _require_device(cand_idx, "candidate indices")
         rows, K = cand_idx.shape
         Kp = (K + TILE_ITEMS - 1) // TILE_ITEMS * TILE_ITEMS
@@ -362,21 +396,22 @@ class MolEngine:
             if uid.numel() != B:
                 # the reference fails in torch.cat on the same mismatch (query_embeddings_fns.py:206-216)
                 raise RuntimeError(f"Sizes of tensors must match: user_ids has {tuple(uid.shape)} for a batch of {B} queries")
-        n = self.lib.rails_mol_query_pack_floats(C.byref(self.shape), B)
+        n = self._fn("query_pack_floats")(C.byref(self.shape), B)
         pack = out if out is not None and out.numel() == n and out.device == q.device else torch.empty(n, dtype=torch.float32, device=q.device)
         s = self.spec
         eq = torch.empty((B, s.query_dot_product_groups, s.dot_product_dimension), dtype=torch.float32, device=q.device) if want_plain else None
         gq = torch.empty((B, s.num_logits), dtype=torch.float32, device=q.device) if want_plain else None
         with _on_device(q.device):
             _lib.check(
-                self.lib.rails_mol_query_prologue(C.byref(self.shape), C.byref(self.weights), _ptr(q), _ptr(uid), B, _ptr(pack), _ptr(eq), _ptr(gq), _stream()),
-                "rails_mol_query_prologue",
+                self._fn("query_prologue")(C.byref(self.shape), C.byref(self.weights), _ptr(q), _ptr(uid), B, _ptr(pack), _ptr(eq), _ptr(gq), _stream()),
+                self._name("query_prologue"),
             )
         return pack, eq, gq
 
     def query_pack_both(self, q: torch.Tensor, user_ids: Optional[torch.Tensor], out: torch.Tensor, out_other: torch.Tensor):
         """One prologue, two packs: `out` in this engine's format, `out_other` in the other one (for the fp32 companion of a
         verified fast mode).  Both must hold rails_mol_query_pack_floats floats."""
+        self._fused_only("query_pack_both")
         _require_device(q, "query_embeddings")
         if q.dim() != 2 or q.shape[1] != self.spec.query_embedding_dim:
             raise ValueError(f"query_embeddings must be (B, {self.spec.query_embedding_dim}), got {tuple(q.shape)}")
@@ -400,6 +435,7 @@ class MolEngine:
     def gate_rows(self, qpack: torch.Tensor, batch: int) -> torch.Tensor:
         """The batch's gq' rows (batch * num_logits floats) inside an fp32 query pack: they sit behind the Eq fragments, which take
         32 * d floats per block of 32 / P_Q queries (the verdict kernels check the bound's gate guard on them)."""
+        self._fused_only("gate_rows")
         s = self.spec
         off = (batch + 32 // s.query_dot_product_groups - 1) // (32 // s.query_dot_product_groups) * 32 * s.dot_product_dimension
         return qpack[off : off + batch * s.num_logits]
@@ -412,13 +448,15 @@ class MolEngine:
             out = torch.empty((batch, index.n_items), dtype=torch.float32, device=index.buf.device)
         with _on_device(index.buf.device):
             _lib.check(
-                self.lib.rails_mol_score_dense(C.byref(self.dense_shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(index.buf), index.n_items, _ptr(out), out.stride(0), _pred(run_if), _stream()),
-                "rails_mol_score_dense",
+                self._fn("score_dense")(C.byref(self.dense_shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(index.buf), index.n_items, _ptr(out), out.stride(0), _pred(run_if), _stream()),
+                self._name("score_dense"),
             )
         return out
 
     def score_dense_upper_supported(self) -> bool:
         """True iff this engine's dense precision has the upper-bound first pass (include/rails_amd.h rails_mol_score_dense_upper)."""
+        if self.route == "generic":
+            return False
         memo = self.__dict__
         if "_upper_ok" not in memo:
             memo["_upper_ok"] = bool(self.lib.rails_mol_score_dense_upper_supported(C.byref(self.dense_shape)))
@@ -428,6 +466,7 @@ class MolEngine:
                           run_if: Optional[torch.Tensor] = None) -> torch.Tensor:
         """f16x3 logit + (ub2 c + ub1) c + ub0 per pair, c = the pair's largest |cross logit|: an upper bound of the fp32 logit when `poly` is
         f16x3_bound.upper_bound_poly's (ub2, ub1, ub0)."""
+        self._fused_only("the upper-bound first pass")
         if out is None:
             out = torch.empty((batch, index.n_items), dtype=torch.float32, device=index.buf.device)
         with _on_device(index.buf.device):
@@ -439,6 +478,8 @@ class MolEngine:
         return out
 
     def score_indexed_supported(self, batch: int, n_cand: int) -> bool:
+        if self.route == "generic":
+            return False
         key = (int(batch), int(n_cand))
         memo = self.__dict__.setdefault("_indexed_ok", {})     # a dry run of the launch per call otherwise: host time of every rerank
         if key not in memo:
@@ -448,6 +489,7 @@ class MolEngine:
     def score_indexed(self, qpack: torch.Tensor, batch: int, index: MolIndex, positions: torch.Tensor) -> torch.Tensor:
         """(B, n_cand) logits of per-row candidates given as positions of `index` (all inside the index):
         gather_index + score_candidates without the gathered copy (include/rails_amd.h rails_mol_score_indexed)."""
+        self._fused_only("score_indexed")
         positions = positions.to(device=index.buf.device, dtype=torch.int64).contiguous()
         n_cand = positions.shape[1]
         out = torch.empty((batch, n_cand), dtype=torch.float32, device=index.buf.device)
@@ -462,6 +504,11 @@ class MolEngine:
     def score_candidates(self, qpack: torch.Tensor, batch: int, cand_index: MolIndex, n_cand_padded: int) -> torch.Tensor:
         out = torch.empty((batch, n_cand_padded), dtype=torch.float32, device=cand_index.buf.device)
         with _on_device(cand_index.buf.device):
+            if self.route == "generic":
+                _lib.check(self.lib.rails_mol_generic_score_candidates(C.byref(self.shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(cand_index.buf),
+                                                                       n_cand_padded, _ptr(out), out.stride(0), None, _stream()),
+                           "rails_mol_generic_score_candidates")
+                return out
             _lib.check(
                 self.lib.rails_mol_score_candidates(C.byref(self.shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(cand_index.buf), n_cand_padded, _ptr(out), out.stride(0), _stream()),
                 "rails_mol_score_candidates",
@@ -473,6 +520,7 @@ class MolEngine:
     def _derived_table(self, fn_name: str, row_elems: int, index: MolIndex, items: Optional[torch.Tensor]) -> torch.Tensor:
         """A bf16 table cut from the fp32 Ex of the index.  In f16x3 precision the index only holds Ex to 22 bits, so the
         table is cut from temporary fp32-format index chunks rebuilt from `items` (same values as the fp32 engine's)."""
+        self._fused_only("the coarse / component tables")
         fn = getattr(self.lib, fn_name)
         n, dev = index.n_items, index.buf.device
         table = torch.empty(n * row_elems, dtype=torch.bfloat16, device=dev)
@@ -647,6 +695,7 @@ class IvfIndex:
                  items: Optional[torch.Tensor] = None):
         """items: the raw (N, D) item embeddings; needed only where `engine` is not an fp32 engine: the fp16 components are then cut from
         temporary fp32-format index chunks of COMPONENT_CHUNK items (the same values as the fp32 engine's), as the component table is."""
+        engine._fused_only("the IVF-Flat index")
         self.lib = engine.lib
         spec = engine.spec
         self.groups, self.d = spec.item_dot_product_groups, spec.dot_product_dimension

@@ -327,6 +327,9 @@ class MoLSimilarity(SimilarityModule):
         self._extra_engines: Dict[str, tuple] = {}
         # None -> RAILS_PRECISION or "fp32" (exact fp32 MFMA, the parity path); "f16x3" -> opt-in split-f16 gate MLP
         self.precision: Optional[str] = None
+        # None -> the fused kernels where the shape has them, the shape-generic fp32 kernels otherwise; "generic" sends a fused shape
+        # through the generic kernels too (tests and measurements: the two routes agree to rounding, not bit for bit)
+        self.route: Optional[str] = None
 
     # ---- binding the parameters to the HIP engine -----------------------------------------------
     def shape_spec(self) -> MolShapeSpec:
@@ -391,19 +394,19 @@ class MoLSimilarity(SimilarityModule):
                 # the caller has just asked for the module's own engine (same thread, nothing in between): the parameters are those of
                 # _engine_key, and this precision's engine was built from the same ones -- no second walk over the 27 tensors
                 return hit[1]
-            key = (precision,) + tuple((v.data_ptr(), _version(v)) for v in plist)
+            key = ((precision, self.route),) + tuple((v.data_ptr(), _version(v)) for v in plist)
             if hit is None or hit[0] != key:
                 params = dict(self.state_dict(keep_vars=True))
                 self._param_list = list(params.values())
-                key = (precision,) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
-                hit = self._extra_engines[precision] = (key, MolEngine(self.shape_spec(), params, precision=precision))
+                key = ((precision, self.route),) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
+                hit = self._extra_engines[precision] = (key, MolEngine(self.shape_spec(), params, precision=precision, route=self.route))
             return hit[1]
-        key = (self.precision,) + tuple((v.data_ptr(), _version(v)) for v in plist)
+        key = ((self.precision, self.route),) + tuple((v.data_ptr(), _version(v)) for v in plist)
         if self._engine is None or key != self._engine_key:
             params = dict(self.state_dict(keep_vars=True))
             self._param_list = list(params.values())
-            key = (self.precision,) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
-            self._engine = MolEngine(self.shape_spec(), params, precision=self.precision)
+            key = ((self.precision, self.route),) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
+            self._engine = MolEngine(self.shape_spec(), params, precision=self.precision, route=self.route)
             self._engine_key = key
         return self._engine
 
@@ -448,7 +451,7 @@ class MoLSimilarity(SimilarityModule):
         else:
             if Bp != B:
                 raise RuntimeError(f"item_embeddings.shape[0] must be 1 or B={B}, got {Bp}")
-            Xp = (X + 31) // 32 * 32
+            Xp = X if eng.route == "generic" else (X + 31) // 32 * 32     # (the generic kernels take any number of candidates per row)
             items = item_embeddings
             if Xp != X:
                 items = torch.nn.functional.pad(items, (0, 0, 0, Xp - X))

@@ -121,7 +121,7 @@ class MoLTopKModule(TopKModule):
         B = query_embeddings.size(0)
         pack = logits = None
         if not _private:
-            pack = self._buf(_tag, eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), B), torch.float32)
+            pack = self._buf(_tag, eng._fn("query_pack_floats")(E.C.byref(eng.shape), B), torch.float32)
             logits = self._buf("logits", B * index.n_items, torch.float32).view(B, index.n_items)
         qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), out=pack)
         return eng.score_dense(qpack, B, index, out=logits)
@@ -177,6 +177,14 @@ class MoLTopKModule(TopKModule):
                 rows = eng.build_index_rows(self._index)
         self._rows_cache = (eng, self._index, rows)
         return rows
+
+
+def _refuse_generic_route(mol_module: MoLSimilarity, what: str) -> None:
+    """The approximate algorithms need the coarse / component tables and the in-place candidate re-scoring, which the generic scoring
+    route does not have: refuse at construction, before any build."""
+    if mol_module.engine().route == "generic":
+        raise NotImplementedError(f"{what} is not built on the generic scoring route (this MoL shape has no fused scoring kernel); "
+                                  "MoLBruteForceTopK runs it")
 
 
 class BoundPolicy(NamedTuple):
@@ -301,8 +309,8 @@ class MoLBruteForceTopK(MoLTopKModule):
         pol = self._policy
         if pol.base is not base:      # new parameters (or another precision): nothing decided, nothing evaluated yet
             pol = self._policy = BoundPolicy(base=base)
-        if self.exact_mode != "proved" or base.precision != "fp32" or base.exact is not None:
-            return base
+        if self.exact_mode != "proved" or base.precision != "fp32" or base.exact is not None or base.route == "generic":
+            return base       # (the generic scoring route has the dense fp32 pass only)
         if pol.proved is None:
             ok = self._proved_applies(base)
             pol = self._policy = self._policy._replace(proved=ok)
@@ -468,7 +476,7 @@ class MoLBruteForceTopK(MoLTopKModule):
         eng = _engine if _engine is not None else self._bind()
         index = _index if _index is not None else self._index
         B, N, C = query_embeddings.size(0), index.n_items, self.CHUNK_ITEMS
-        n_q = eng.lib.rails_mol_query_pack_floats(E.C.byref(eng.shape), B)
+        n_q = eng._fn("query_pack_floats")(E.C.byref(eng.shape), B)
         qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), out=self._buf("qpack", n_q, torch.float32))
         buf = self._buf("logits_chunk", B * min(C, N), torch.float32)
         ws = self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(B, min(C, N), min(k, C)), torch.uint8)
@@ -1151,6 +1159,7 @@ class MoLAvgTopK(MoLTopKModule):
     which are then scored with the full MoL and cut to k.  Spans keep the reference's profiler names."""
 
     def __init__(self, mol_module: MoLSimilarity, item_embeddings: torch.Tensor, item_ids: torch.Tensor, avg_top_k: int) -> None:
+        _refuse_generic_route(mol_module, type(self).__name__)
         super().__init__(mol_module=mol_module, item_embeddings=item_embeddings, item_ids=item_ids)
         self._avg_top_k: int = avg_top_k
         self.fused_coarse_min_items: int = 262144    # below this the (B, N) scores are small and one launch chain shorter
@@ -1555,6 +1564,7 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
 
     def __init__(self, mol_module: MoLSimilarity, item_embeddings: torch.Tensor, item_ids: torch.Tensor, k_per_group: int, use_faiss: bool = False,
                  *, nlist: int = 100, nprobe: int = 1, iters: int = 10, seed: int = 1234) -> None:
+        _refuse_generic_route(mol_module, type(self).__name__)
         super().__init__(mol_module=mol_module, item_embeddings=item_embeddings, item_ids=item_ids)
         self._k_per_group: int = k_per_group
         self._use_faiss: bool = bool(use_faiss)
