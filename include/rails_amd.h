@@ -44,7 +44,9 @@ extern "C" {
  * 13: the SASRec cached-decoding entries rails_sasrec_decode[_supported] / rails_sasrec_decode_workspace_floats and struct
  * rails_sasrec_decode_layer are new;
  * 14: the IVF-Flat component index rails_ivf_* (MoLNaiveTopK use_faiss=True) is new;
- * 15: the shape-generic fp32 scoring route rails_mol_generic_* is new).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
+ * 15: the shape-generic fp32 scoring route rails_mol_generic_* is new; the candidate-key entry points rails_group_keys_* of the item-sharded
+ * MoLNaiveTopK / MoLCombTopK were added under 15 as well: no struct and no existing entry point changed, so callers built against the
+ * earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
 #define RAILS_ABI_VERSION 15
 int rails_abi_version(void);
@@ -470,6 +472,40 @@ int rails_merge_candidates_verdict(const int64_t* gathered, int32_t n_ranks, int
                                    const float* guard_values, int32_t guard_per_row, float guard_limit, float* state, float* state_host,
                                    void* call_ws, const int64_t* invalid_ids, int32_t width, int32_t f_k, int64_t* out_ids, float* out_scores,
                                    void* stream);
+
+/* ---- candidate keys of the item-sharded MoLNaiveTopK / MoLCombTopK, global form (rails_amd/sharded.py; no counterpart in the reference) ----
+ * The per-group component scores and the coarse scores are bf16 values carried in fp32, so ONE 64-bit key holds a candidate:
+ *   bits 63..48  the order-preserving 16-bit image of the score: with h = the upper 16 bits of the fp32 word (the bf16 value; the
+ *                lower 16 bits are not looked at), h | 0x8000 for a clear sign bit and ~h for a set one
+ *   bits 47..0   2^48 - 1 - global position
+ * so a LARGER unsigned key is the BETTER candidate and equal scores order by ascending global position.  This is rails_topk's total
+ * order restricted to bf16: rails_topk compares the same image of the whole fp32 word (u | 0x80000000 / ~u), a bit-pattern order in
+ * which +0 ranks above -0, +inf above every finite score, a NaN with a clear sign bit above +inf and a NaN with a set sign bit below
+ * -inf; nothing is special-cased, here or there.  Key 0 is the pad: no candidate (a real candidate could only produce it as the
+ * all-ones NaN at position 2^48 - 1).
+ *
+ * rails_group_keys_pack (one launch): scores / positions (rows, k_local), positions local in [0, n_local) (a negative one is written
+ * as a pad) -> keys (rows, k_slots), k_slots >= k_local, the columns from k_local on padded with key 0.  The order of a row is kept, so
+ * rows sorted best-first (what the scans and rails_topk leave) give descending keys.  offset = global position of the shard's item 0;
+ * offset < 0 or offset + n_local > 2^48 is RAILS_EINVAL before any launch. */
+int rails_group_keys_pack(const float* scores, const int64_t* positions, int32_t rows, int32_t k_local, int64_t offset, int64_t n_local,
+                          int32_t k_slots, uint64_t* keys, void* stream);
+/* 1 iff rails_group_keys_merge_own takes n_ranks lists of k keys per row (n_ranks * k <= 16384, the limit of rails_merge_candidates);
+ * answers without a device. */
+int rails_group_keys_supported(int32_t n_ranks, int32_t k);
+/* rails_group_keys_merge_own (one launch): gathered = n_ranks messages in rank order, as an all-gather leaves them; the keys of rank r,
+ * row b are gathered[r * rank_stride + b * k + j], j < k (rank_stride >= rows * k, in keys: a message may carry more than these rows).
+ * Per row the best k of the n_ranks * k keys are selected (every list descending: merged by rank counting, one binary search per other
+ * list; lists that are not descending are sorted in LDS instead) and per kept key, best first, two things are written:
+ *   out_global[b * k + j]   the global position, -1 for a pad                                  (optional: may be NULL)
+ *   out_local[(b / rows_per_out_row) * out_ld + out_col + (b % rows_per_out_row) * k + j]
+ *                           position - lo where lo <= position < hi (this rank's items), else -1
+ * so that the per-group rows of one query (rows_per_out_row = P_Q * P_X) and, in a second call, its coarse row (rows_per_out_row = 1,
+ * out_col = P_Q * P_X * k_group) fill one (B, W) union buffer of row stride out_ld directly.  Equal keys (overlapping shards, pads)
+ * keep rank order.  RAILS_ENOTSUP where rails_group_keys_supported is 0. */
+int rails_group_keys_merge_own(const uint64_t* gathered, int32_t n_ranks, int64_t rank_stride, int32_t rows, int32_t k, int64_t lo, int64_t hi,
+                               int64_t* out_global, int64_t* out_local, int64_t out_ld, int64_t out_col, int32_t rows_per_out_row,
+                               void* stream);
 
 /* Finish of a speculate-then-verify brute-force top-k (precision "f16x3-exact"; no counterpart in the reference, whose
  * MoLBruteForceTopK scores everything in one precision, mol_top_k.py:84-130).  Per row: n_cand entries with their exact fp32

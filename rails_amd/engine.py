@@ -1268,6 +1268,57 @@ def merge_candidates(gathered: torch.Tensor, n_ranks: int, k: int, k_out: int) -
     return out_s, out_i
 
 
+def group_keys_supported(n_ranks: int, k: int) -> bool:
+    """sizes rails_group_keys_merge_own takes (n_ranks * k <= 16384); answers without a device"""
+    return bool(_lib.load().rails_group_keys_supported(int(n_ranks), int(k)))
+
+
+def group_keys_pack(scores: torch.Tensor, positions: torch.Tensor, offset: int, n_local: int, k_slots: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(rows, k_local) bf16-valued fp32 scores + int64 local positions in [0, n_local) -> (rows, k_slots) int64 holding the 64-bit candidate
+    keys (score image << 48 | 2^48 - 1 - (position + offset); key 0 pads), one launch (include/rails_amd.h rails_group_keys_pack).
+    out: a contiguous int64 tensor of rows * k_slots elements to write into (a slice of a larger message)."""
+    lib = _lib.load()
+    _require_device(scores, "scores")
+    rows, kl = scores.shape
+    scores, positions = _f32c(scores), positions.to(torch.int64).contiguous()
+    if out is None:
+        out = torch.empty((rows, k_slots), dtype=torch.int64, device=scores.device)
+    elif out.dtype != torch.int64 or out.numel() != rows * k_slots or not out.is_contiguous() or out.device != scores.device:
+        raise ValueError("group_keys_pack: out must be a contiguous int64 tensor of rows * k_slots elements on the scores' device")
+    with _on_device(scores.device):
+        _lib.check(lib.rails_group_keys_pack(_ptr(scores), _ptr(positions), rows, kl, int(offset), int(n_local), int(k_slots), _ptr(out), _stream()),
+                   "rails_group_keys_pack")
+    return out
+
+
+def group_keys_merge_own(gathered: torch.Tensor, n_ranks: int, rows: int, k: int, lo: int, hi: int, out_local: Optional[torch.Tensor] = None,
+                         out_col: int = 0, rows_per_out_row: int = 1, want_global: bool = False, rank_stride: Optional[int] = None):
+    """gathered: int64 keys of n_ranks ranks in rank order, rank r's (rows, k) block starting at element r * rank_stride (default rows * k)
+    -> the global top-k of every row as THIS rank's local positions (position - lo inside [lo, hi), -1 elsewhere and for pads), one launch
+    (include/rails_amd.h rails_group_keys_merge_own).  out_local: a contiguous (B, W) int64 union buffer, row b of the keys going to
+    out_local[b // rows_per_out_row, out_col + (b % rows_per_out_row) * k : ...]; default a fresh (rows, k).
+    -> out_local, or (out_local, global positions (rows, k)) with want_global."""
+    lib = _lib.load()
+    _require_device(gathered, "gathered keys")
+    if gathered.dtype != torch.int64 or not gathered.is_contiguous():
+        raise ValueError("group_keys_merge_own: gathered must be a contiguous int64 tensor")
+    stride = rows * k if rank_stride is None else int(rank_stride)
+    if gathered.numel() < (n_ranks - 1) * stride + rows * k:
+        raise ValueError("group_keys_merge_own: gathered is shorter than n_ranks messages")
+    dev = gathered.device
+    if out_local is None:
+        out_local = torch.empty((rows, k), dtype=torch.int64, device=dev)
+        out_col, rows_per_out_row = 0, 1
+    elif (out_local.dtype != torch.int64 or out_local.dim() != 2 or not out_local.is_contiguous() or out_local.device != dev
+          or out_local.shape[0] * rows_per_out_row < rows):
+        raise ValueError("group_keys_merge_own: out_local must be a contiguous int64 (ceil(rows / rows_per_out_row), W) tensor on the keys' device")
+    out_g = torch.empty((rows, k), dtype=torch.int64, device=dev) if want_global else None
+    with _on_device(dev):
+        _lib.check(lib.rails_group_keys_merge_own(_ptr(gathered), int(n_ranks), stride, int(rows), int(k), int(lo), int(hi), _ptr(out_g), _ptr(out_local),
+                                                  out_local.shape[1], int(out_col), int(rows_per_out_row), _stream()), "rails_group_keys_merge_own")
+    return (out_local, out_g) if want_global else out_local
+
+
 def merge_filter_fusable(k_prime: int, width: int, k: int) -> bool:
     return 0 < k <= k_prime <= 512 and 0 <= width <= 256
 

@@ -18,6 +18,10 @@ ShardedMoLAvgTopK(global_k_prime=True) is the single-device algorithm itself on 
 one more all-gather first exchanges every shard's coarse top-K' (coarse score bits | global position), every rank
 selects the GLOBAL coarse top-K' with the same total order (score desc, global position asc), reranks only its own
 members of it, and the usual merge follows.  Bit-identical to MoLAvgTopK(avg_top_k = K') over the whole corpus.
+
+ShardedMoLNaiveTopK / ShardedMoLCombTopK shard the per-component candidate generators the same two ways: per shard (the single-device
+module on every shard, one all-gather) and, with global_candidates=True, the single-device algorithm itself -- the ranks exchange their
+per-group (and coarse) candidate lists as 64-bit keys, every rank selects the global lists and reranks its own members of the union.
 """
 from __future__ import annotations
 
@@ -29,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from . import engine as E
-from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, TopKModule
+from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule
 
 
 def shard_bounds(n_items: int, world_size: int, rank: int) -> Tuple[int, int]:
@@ -519,3 +523,242 @@ class ShardedMoLAvgTopK(ShardedTopK):
             all_s, all_i = unpack_candidates(gathered2.view(self._world, B, 2 * k), k)
             ms, mi = self._merge(all_s, all_i, k)
         return ms.to(query_embeddings.dtype), mi
+
+
+# ---- per-component candidates on an item-sharded corpus ---------------------------------------------------------------------------------
+# The component scores and the coarse scores are bf16 values, so one 64-bit key carries a candidate (include/rails_amd.h rails_group_keys_*):
+#   bits 63..48  order-preserving image of the bf16 score (h | 0x8000 for a clear sign bit, ~h for a set one: rails_topk's order cut to 16 bits --
+#                +0 above -0, NaNs with a clear sign bit above +inf, with a set one below -inf)
+#   bits 47..0   2^48 - 1 - global position
+# A larger UNSIGNED key is better; equal scores order by ascending position; key 0 pads.  The tensors below hold the keys' bit patterns in int64.
+GROUP_KEY_POSITION_BITS = 48
+_POS_MASK = (1 << GROUP_KEY_POSITION_BITS) - 1
+_SIGN64 = -(1 << 63)
+
+
+def pack_group_keys(scores: torch.Tensor, positions: torch.Tensor, offset: int, k_slots: int, n_local: Optional[int] = None) -> torch.Tensor:
+    """The torch restatement of rails_group_keys_pack: (rows, k_local) bf16-valued fp32 scores + int64 local positions -> (rows, k_slots)
+    int64 key bit patterns, padded with key 0 (negative positions pad too).  Global positions of 2^48 or more raise ValueError."""
+    rows, kl = scores.shape
+    if k_slots < kl:
+        raise ValueError(f"pack_group_keys: k_slots ({k_slots}) < k_local ({kl})")
+    bound = int(n_local) if n_local is not None else (int(positions.max()) + 1 if positions.numel() else 0)
+    if offset < 0 or offset + bound > (1 << GROUP_KEY_POSITION_BITS):
+        raise ValueError(f"pack_group_keys: global positions [{offset}, {offset + bound}) do not fit {GROUP_KEY_POSITION_BITS} bits")
+    h = (scores.float().contiguous().view(torch.int32).to(torch.int64) >> 16) & 0xFFFF
+    img = torch.where((h & 0x8000) != 0, ~h & 0xFFFF, h | 0x8000)
+    img = torch.where(img >= 0x8000, img - 0x10000, img)          # the upper 16 bits of a two's-complement word
+    keys = img * (1 << GROUP_KEY_POSITION_BITS) + (_POS_MASK - (positions.to(torch.int64) + offset))
+    keys = torch.where(positions < 0, torch.zeros_like(keys), keys)
+    if kl < k_slots:
+        keys = torch.cat([keys, keys.new_zeros((rows, k_slots - kl))], 1)
+    return keys
+
+
+def unpack_group_keys(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """keys (any shape, int64 bit patterns) -> (scores fp32, global positions).  A pad decodes to position -1 and to the score its bits
+    spell: the all-ones NaN, which rails_topk ranks below everything, -inf included."""
+    img = (keys >> GROUP_KEY_POSITION_BITS) & 0xFFFF
+    h = torch.where((img & 0x8000) != 0, img & 0x7FFF, ~img & 0xFFFF)
+    scores = ((h << 16) - ((h >> 15) << 32)).to(torch.int32).view(torch.float32)      # (the fp32 word as a two's-complement int32)
+    pos = _POS_MASK - (keys & _POS_MASK)
+    return scores, torch.where(keys == 0, torch.full_like(pos, -1), pos)
+
+
+def merge_group_keys_own(keys: torch.Tensor, lo: int, hi: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The torch restatement of rails_group_keys_merge_own: keys (R, rows, k) -> (global positions (rows, k), local positions (rows, k)):
+    the k largest unsigned keys of every row, best first; position - lo inside [lo, hi), -1 elsewhere and for pads."""
+    R, rows, k = keys.shape
+    flat = keys.permute(1, 0, 2).reshape(rows, R * k)
+    order = torch.sort(flat ^ _SIGN64, dim=1, descending=True, stable=True).values[:, :k] ^ _SIGN64     # unsigned order through the sign flip
+    _, gpos = unpack_group_keys(order)
+    return gpos, torch.where((gpos >= lo) & (gpos < hi), gpos - lo, torch.full_like(gpos, -1))
+
+
+class _ShardedComponentCandidates(ShardedTopK):
+    """What ShardedMoLNaiveTopK and ShardedMoLCombTopK share.  forward(q, k) -> (scores, ids) with min(k, W) columns, identical on every rank,
+    W = P_Q * P_X * k_per_group [+ avg_top_k] being the union width the single-device module returns.
+
+    Per-shard form (default): every rank runs the single-device module on its shard -- k_per_group (and avg_top_k) candidates PER SHARD --
+    keeps the first k columns of its ranking and the usual single all-gather + merge follows: weak scaling, a superset-quality variant that
+    equals the single-device module at one rank.
+    Global form (global_candidates=True): the single-device algorithm on the sharded corpus.  (1) local candidates with scores, verified (a
+    rank whose fused-scan verdict fails redoes ITS scan before it sends: the collectives do not depend on verdicts); (2) ONE all-gather of the
+    candidate keys -- Comb's group keys and coarse keys in one message, 8 bytes per candidate; (3) every rank selects the global top-k_per_group
+    of every (query group, item group) row (and the global coarse top-K') under (score desc, global position asc) and writes its own members of
+    the union as local positions, holes elsewhere (rails_group_keys_merge_own; beyond 16 384 keys per row: unpack + the general top-k);
+    (4) rerank of those with full MoL, duplicates masked as on one device; (5) the usual all-gather + merge of the local top-k.  Two collectives
+    per step.  The scores equal the first columns of the single-device ranking bit for bit, the ids wherever the score is above the duplicate
+    mark -32767.0.  THE MASKED TAIL (columns at -32767.0: second and later copies of a candidate several lists named) carries the ids of those
+    copies in ascending global position, rank by rank; it holds the same multiset of ids as the single-device tail, and the same order whenever
+    the shards are the contiguous split.
+
+    Out of scope: use_faiss=True (IVF lists are trained per shard: NotImplementedError); submit / result pipelining of the global form (its
+    forward is one synchronous chain; the per-shard form has ShardedTopK's); the generic scoring route (refused by the local modules)."""
+
+    def __init__(self, mol_module, item_embeddings_shard, item_ids_shard, n_items_total: int, *, global_candidates: bool, shard_offset: Optional[int],
+                 candidates_local, rerank_local, **kwargs) -> None:
+        self._global = bool(global_candidates)
+        if candidates_local is not None and "local_topk" not in kwargs:
+            kwargs["local_topk"] = lambda q, k, **kw: (_ for _ in ()).throw(RuntimeError("global_candidates path only"))   # noqa: E731
+        super().__init__(mol_module, item_embeddings_shard, item_ids_shard, n_items_total, **kwargs)
+        rank = dist.get_rank(self._group) if dist.is_initialized() else 0
+        self._offset = int(shard_offset) if shard_offset is not None else shard_bounds(n_items_total, self._world, rank)[0]
+        if self._global and self._exchange and shard_offset is not None:
+            # equal scores are ordered by global position, and the final merge breaks ties by rank: one order only for ascending disjoint ranges
+            spans = [None] * self._world
+            dist.all_gather_object(spans, (self._offset, self._offset + self._n_local), group=self._group)
+            if any(spans[r][1] > spans[r + 1][0] for r in range(self._world - 1)):
+                raise ValueError(f"global_candidates needs shard ranges that ascend with the rank without overlap, got {spans}")
+        if self._local_topk_is_module:        # the module ranks its whole union whatever k is: a shard's top-k are its first columns
+            self._local_topk = lambda q, k, **kw: tuple(t[:, :k] for t in self._local_module(q, k=k, **kw))  # noqa: E731
+            self._local_topk_is_module = False    # (MoLCombTopK inherits MoLAvgTopK's submit / result, which are not its forward: plain calls only)
+        self._candidates_local = candidates_local if candidates_local is not None else (lambda q, **kw: self._local_module.local_candidates(q, **kw))
+        self._rerank_local = rerank_local if rerank_local is not None else (lambda q, idx, k, **kw: self._local_module.rerank_union_masked(q, idx, k, **kw))
+        self._msg_keys = 0
+
+    # (rows per query of the group lists, k_per_group, K' or 0)
+    def _widths(self) -> Tuple[int, int, int]:
+        raise NotImplementedError
+
+    def union_width(self) -> int:
+        g, kg, kc = self._widths()
+        return g * kg + kc
+
+    def _check_k(self, k: int) -> int:
+        if k > self._n_total:
+            raise RuntimeError(f"selected index k out of range (k={k}, n={self._n_total})")
+        return min(k, self.union_width())
+
+    def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        kk = self._check_k(k)
+        if not (self._global and self._exchange):
+            if not self._exchange:       # one rank: the module's own ranking
+                s, ids = self._local_topk(query_embeddings, kk, **kwargs)
+                return s, ids
+            return super().forward(query_embeddings, kk, sorted, **kwargs)
+        return self._forward_global(query_embeddings, kk, **kwargs)
+
+    def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
+        if self._global and self._exchange:
+            raise NotImplementedError(f"{type(self).__name__}: submit / result pipelining of the global form is not built; call forward")
+        return super().submit(query_embeddings, k, sorted, **kwargs)
+
+    def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
+        if self._global and self._exchange:
+            return None      # the caller composes forward + filter_seen_ids: same bits
+        if not self._exchange or k_prime > self.union_width() or k_prime > self._n_total:
+            return None
+        return super().forward_filtered(query_embeddings, k_prime, invalid_ids, k, **kwargs)
+
+    def _forward_global(self, query_embeddings: torch.Tensor, kk: int, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        g, kg, kc = self._widths()
+        B = query_embeddings.size(0)
+        dev = query_embeddings.device
+        rows = B * g
+        W = g * kg + kc
+        if kg > self._n_total or kc > self._n_total:
+            raise RuntimeError(f"selected index k out of range (k={max(kg, kc)}, n={self._n_total})")
+        R, lo, hi = self._world, self._offset, self._offset + self._n_local
+        # (1) this shard's candidates with their scores, verified
+        if self._n_local > 0:
+            cand = self._candidates_local(query_embeddings, **kwargs)
+        else:
+            ef, ei = torch.empty((rows, 0), dtype=torch.float32, device=dev), torch.empty((rows, 0), dtype=torch.int64, device=dev)
+            cand = (ef, ei, ef[:B], ei[:B]) if kc else (ef, ei)
+        on_gpu = cand[0].is_cuda and self._merge is _hip_merge
+        # (2) ONE message per rank: [rows * k_g group keys | B * K' coarse keys], all-gathered in rank order
+        n_keys = rows * kg + B * kc
+        self._msg_keys = n_keys
+        if on_gpu:
+            msg = torch.empty(n_keys, dtype=torch.int64, device=dev)
+            E.group_keys_pack(cand[0], cand[1], lo, self._n_local, kg, out=msg[: rows * kg])
+            if kc:
+                E.group_keys_pack(cand[2], cand[3], lo, self._n_local, kc, out=msg[rows * kg :])
+        else:
+            parts = [pack_group_keys(cand[0].float(), cand[1], lo, kg, self._n_local).reshape(-1)]
+            if kc:
+                parts.append(pack_group_keys(cand[2].float(), cand[3], lo, kc, self._n_local).reshape(-1))
+            msg = torch.cat(parts)
+        gathered = self._all_gather_rows(msg.view(1, n_keys))            # (R, n_keys)
+        # (3) the global lists, as this rank's local positions in one (B, W) union buffer
+        union = torch.empty((B, W), dtype=torch.int64, device=gathered.device)
+        for first, n_rows, kx, col, per_row in ((0, rows, kg, 0, g), (rows * kg, B, kc, g * kg, 1)):
+            if kx == 0:
+                continue
+            block = gathered[:, first : first + n_rows * kx]
+            if on_gpu and E.group_keys_supported(R, kx):       # one launch
+                E.group_keys_merge_own(gathered.view(-1)[first:], R, n_rows, kx, lo, hi, out_local=union, out_col=col, rows_per_out_row=per_row,
+                                       rank_stride=n_keys)
+                continue
+            if on_gpu:       # long lists: unpack + the general top-k over the rank-major concatenation (same total order)
+                sc, gp = unpack_group_keys(block.reshape(R, n_rows, kx).permute(1, 0, 2).reshape(n_rows, R * kx))
+                _, gpos = E.topk(sc, kx, ids=gp)
+                local = torch.where((gpos >= lo) & (gpos < hi), gpos - lo, gpos.new_full((), -1))
+            else:
+                _, local = merge_group_keys_own(block.reshape(R, n_rows, kx), lo, hi)
+            union[:, col : col + per_row * kx] = local.view(B, per_row * kx)
+        # (4) full MoL on my members of the union, (5) the usual exchange of exact scores
+        if self._n_local > 0:
+            s, ids = self._rerank_local(query_embeddings, union, kk, **kwargs)
+        else:
+            s = torch.full((B, kk), float("-inf"), dtype=torch.float32, device=dev)
+            ids = torch.full((B, kk), -1, dtype=torch.int64, device=dev)
+        msg2 = E.pack_candidates(s, ids, kk) if on_gpu else pack_candidates(s.float(), ids, kk)
+        with self._inline():
+            return self.result(("pending", msg2, None, kk, on_gpu, query_embeddings.dtype, None))
+
+    def exchange_info(self) -> dict:
+        info = super().exchange_info()
+        glob = self._global and self._exchange
+        info["form"] = "global" if self._global else "per-shard"
+        info["collectives_per_step"] = 2 if glob else (1 if self._exchange else 0)
+        # the global form's first exchange: 8 bytes per candidate slot, (B * P_Q * P_X * k_g [+ B * K']) slots as of the last call
+        info["candidate_message_bytes"] = 8 * self._msg_keys if glob else 0
+        return info
+
+
+class ShardedMoLNaiveTopK(_ShardedComponentCandidates):
+    """MoLNaiveTopK on an item-sharded corpus; the two forms, the return value and what is out of scope: _ShardedComponentCandidates.
+    `candidates_local(q, **kw) -> (group scores, group local positions)`, both (B * P_Q * P_X, <= k_per_group), and
+    `rerank_local(q, local positions with -1 holes (B, W), k, **kw) -> (scores, ids)` default to the HIP module's local_candidates /
+    rerank_union_masked; the CPU test of the collective logic injects oracle callables (then `groups` = P_Q * P_X must be given)."""
+
+    def __init__(self, mol_module, item_embeddings_shard, item_ids_shard, n_items_total: int, k_per_group: int, global_candidates: bool = False,
+                 shard_offset: Optional[int] = None, use_faiss: bool = False, candidates_local=None, rerank_local=None, groups: Optional[int] = None,
+                 **kwargs) -> None:
+        if use_faiss:
+            raise NotImplementedError("ShardedMoLNaiveTopK: use_faiss=True is not built for a sharded corpus (IVF lists are trained per shard)")
+        self._k_per_group = int(k_per_group)
+        self._groups = int(groups) if groups is not None else mol_module._query_dot_product_groups * mol_module._item_dot_product_groups
+        super().__init__(mol_module, item_embeddings_shard, item_ids_shard, n_items_total, global_candidates=global_candidates, shard_offset=shard_offset,
+                         candidates_local=candidates_local, rerank_local=rerank_local, **kwargs)
+
+    def _make_local_module(self, mol_module, item_embeddings_shard, item_ids_shard) -> TopKModule:
+        return MoLNaiveTopK(mol_module, item_embeddings_shard, item_ids_shard, k_per_group=max(1, min(self._k_per_group, int(item_ids_shard.numel()))))
+
+    def _widths(self) -> Tuple[int, int, int]:
+        return self._groups, self._k_per_group, 0
+
+
+class ShardedMoLCombTopK(_ShardedComponentCandidates):
+    """MoLCombTopK on an item-sharded corpus: as ShardedMoLNaiveTopK, with the averaged-query coarse top-`avg_top_k` in the union
+    (`candidates_local` -> (group scores, group positions, coarse scores (B, <= K'), coarse positions)); in the global form the group keys and the
+    coarse keys travel in one message."""
+
+    def __init__(self, mol_module, item_embeddings_shard, item_ids_shard, n_items_total: int, avg_top_k: int, k_per_group: int,
+                 global_candidates: bool = False, shard_offset: Optional[int] = None, candidates_local=None, rerank_local=None,
+                 groups: Optional[int] = None, **kwargs) -> None:
+        self._k_per_group = int(k_per_group)
+        self._avg_top_k = int(avg_top_k)
+        self._groups = int(groups) if groups is not None else mol_module._query_dot_product_groups * mol_module._item_dot_product_groups
+        super().__init__(mol_module, item_embeddings_shard, item_ids_shard, n_items_total, global_candidates=global_candidates, shard_offset=shard_offset,
+                         candidates_local=candidates_local, rerank_local=rerank_local, **kwargs)
+
+    def _make_local_module(self, mol_module, item_embeddings_shard, item_ids_shard) -> TopKModule:
+        n = int(item_ids_shard.numel())
+        return MoLCombTopK(mol_module, item_embeddings_shard, item_ids_shard, avg_top_k=max(1, min(self._avg_top_k, n)),
+                           k_per_group=max(1, min(self._k_per_group, n)))
+
+    def _widths(self) -> Tuple[int, int, int]:
+        return self._groups, self._k_per_group, self._avg_top_k

@@ -1472,9 +1472,10 @@ class _ComponentCandidates:
             self._comp_table = eng.build_component_table(self._index, self._item_embeddings[0])
         return self._comp_table
 
-    def _component_topk(self, eq: torch.Tensor, k_per_group: int, pending: Optional[list] = None) -> torch.Tensor:
+    def _component_topk(self, eq: torch.Tensor, k_per_group: int, pending: Optional[list] = None, with_scores: bool = False):
         """-> (B, P_Q * P_X * k_per_group) positions: top k_per_group items of every (query group, item group) pair.
-        `pending`: deferred validity check of the fused scan, as in MoLAvgTopK._coarse_topk_from_eq."""
+        `pending`: deferred validity check of the fused scan, as in MoLAvgTopK._coarse_topk_from_eq.
+        with_scores: -> (scores, positions), both (B * P_Q * P_X, k_per_group), best first: the bf16 component scores as fp32."""
         eng = self._bind()
         table = self._component_table()      # (P_X, N, d), item-group-major
         n = table.shape[1]
@@ -1484,7 +1485,8 @@ class _ComponentCandidates:
         # registers (four at d = 128): batches beyond 256 (128) query rows go in slices
         max_b = max(1, (128 if eng.spec.dot_product_dimension >= 128 else 256) // eng.spec.query_dot_product_groups)
         if eq.shape[0] > max_b:
-            return torch.cat([self._component_topk(eq[b0 : b0 + max_b], k_per_group, pending) for b0 in range(0, eq.shape[0], max_b)], dim=0)
+            parts = [self._component_topk(eq[b0 : b0 + max_b], k_per_group, pending, with_scores) for b0 in range(0, eq.shape[0], max_b)]
+            return (torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)) if with_scores else torch.cat(parts, dim=0)
         # large corpora: fused scan + threshold select, no (B*P_Q*P_X, N) score matrix (5.7 GB at amzn-books, B = 32);
         # identical to the materialising path below whenever every row's candidate count is inside [k, capacity]
         if n >= self.fused_component_min_items and not self._no_fused:
@@ -1502,15 +1504,58 @@ class _ComponentCandidates:
                 if on_device:     # redo on the device under the flag, as in MoLAvgTopK._coarse_topk_from_eq
                     scores = eng.component_scores(eq, table, out=self._buf("component_all", rows * n, torch.float32).view(rows, n), run_if=flag)
                     E.topk(scores, k_per_group, out=(sc_c, pos), run_if=flag)
-                    return pos.view(eq.shape[0], -1)
+                    return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
                 if pending is not None:      # a device verdict word (1 = redo), read by the caller once everything is enqueued
                     pending.append(flag)
-                    return pos.view(eq.shape[0], -1)
+                    return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
                 if int(flag.item()) == 0:
-                    return pos.view(eq.shape[0], -1)
+                    return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
         scores = eng.component_scores(eq, table)
-        _, pos = E.topk(scores, k_per_group)
-        return pos.view(eq.shape[0], -1)
+        sc_c, pos = E.topk(scores, k_per_group)
+        return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
+
+    # ---- the two halves of _ranked on their own, for the item-sharded global form (sharded.ShardedMoLNaiveTopK / ShardedMoLCombTopK) -----------
+    def _candidates_scored(self, eq: torch.Tensor, pending: list):
+        """_candidates with the scores that ranked them: -> (group scores, group positions[, coarse scores, coarse positions])."""
+        raise NotImplementedError
+
+    def local_candidates(self, query_embeddings: torch.Tensor, **kwargs):
+        """Local candidates with scores: the per-group top-k_per_group of THIS module's items as (scores, positions), both
+        (B * P_Q * P_X, k_per_group), best first under (score desc, position asc) -- and for MoLCombTopK the averaged-query coarse top-K'
+        (scores, positions), both (B, K'), behind them.  Scores are the scans' bf16 values as fp32.  VERIFIED before it returns: the fused
+        scans are enqueued speculatively, their verdict words read once (the one host look of the single-device call), and a failed verdict
+        redoes the scans on the materialising path -- what comes back is exact."""
+        eng = self._bind()
+        _, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
+        for attempt in range(2):
+            pending: list = []
+            out = self._candidates_scored(eq, pending)
+            if _verdicts_clear(pending, self):
+                break
+            self._no_fused = True
+        self._no_fused = False
+        return out
+
+    def rerank_union_masked(self, query_embeddings: torch.Tensor, union_idx: torch.Tensor, k: int, **kwargs):
+        """Rerank a union with holes: union_idx (B, W) positions of this module's items, < 0 where a candidate is another shard's.  The same
+        chain as _rerank_union -- sort, full MoL, duplicates (the second and later copies of an owned position) masked with -32767.0 -- with
+        the holes scoring -inf, carrying id -1 and never counting as a duplicate of anything.  -> the top-min(k, W) (scores fp32, ids), ties by
+        position ascending.  No host synchronisation."""
+        eng = self._bind()
+        qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"))
+        W = union_idx.shape[1]
+        big = W > self.UNION_CAP
+        sorted_idx = torch.sort(union_idx.to(torch.int64), dim=1).values if big else E.sort_rows(union_idx)     # holes first
+        hole = sorted_idx < 0
+        safe = sorted_idx.clamp_min(0)                  # holes read item 0 and are overwritten below
+        scores = self._score_at(eng, qpack, query_embeddings.size(0), safe)
+        E.mask_sorted_duplicates(sorted_idx, scores, -32767.0)      # (on the unclamped positions: the first owned item 0 is no copy of a hole)
+        scores = torch.where(hole, scores.new_full((), float("-inf")), scores)
+        ids = torch.where(hole, sorted_idx.new_full((), -1), self._ids_flat[safe])
+        if big and min(k, W) > self.UNION_CAP:
+            vals, order = torch.sort(scores, dim=1, descending=True, stable=True)
+            return vals[:, : min(k, W)].contiguous(), torch.gather(ids, 1, order)[:, : min(k, W)].contiguous()
+        return E.topk(scores, min(k, W), ids=ids)
 
     def _filter_inside(self, n_candidates: int, invalid_ids: torch.Tensor, k: int):
         """get_top_k_outputs over a module that returns ALL its candidates ranked (masked duplicates last): the first k unseen entries of that
@@ -1599,6 +1644,11 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
             return self.ivf_index().search(eq, self._k_per_group, nprobe=self.nprobe)
         return self._component_topk(eq, self._k_per_group, pending)
 
+    def _candidates_scored(self, eq: torch.Tensor, pending: list):
+        if self._use_faiss:
+            raise NotImplementedError("MoLNaiveTopK: the IVF lists return no exhaustive per-group ranking to exchange (use_faiss=True)")
+        return self._component_topk(eq, self._k_per_group, pending, with_scores=True)
+
     def _union_width(self) -> int:
         mol = self._mol_module
         return mol._query_dot_product_groups * mol._item_dot_product_groups * self._k_per_group
@@ -1621,6 +1671,11 @@ class MoLCombTopK(_ComponentCandidates, MoLAvgTopK):
         comp = self._component_topk(eq, self._k_per_group, pending)
         avg_idx = self._coarse_topk_from_eq(eq, average_queries=True, pending=pending)
         return torch.cat([comp, avg_idx], dim=1)
+
+    def _candidates_scored(self, eq: torch.Tensor, pending: list):
+        gs, gp = self._component_topk(eq, self._k_per_group, pending, with_scores=True)
+        cs, cp = self._coarse_topk_from_eq(eq, average_queries=True, pending=pending, with_scores=True)
+        return gs, gp, cs, cp
 
 
 class MIPSTopKModule(TopKModule):

@@ -16,6 +16,9 @@ ap.add_argument("--world", type=int, default=8)
 ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--precision", default=None, help="fp32 (default) | f16x3 | f16x3-exact | f16-exact (the module's verified route, proved PER SHARD) | "
                                                  "proved-global (ShardedMoLBruteForceTopK's flow: one proof for all shards, its collectives replaced by copies)")
+ap.add_argument("--method", default=None, help="Naive5 | Naive100 | Comb5_200 | Comb100_1000: the per-rank step of ShardedMoLNaiveTopK / ShardedMoLCombTopK "
+                                              "instead (both forms), beside the single-device module on the whole corpus; medians of per-step event times")
+ap.add_argument("--json", default=None, help="with --method: append the medians to this JSON file (a list of records)")
 ap.add_argument("--pipeline", action="store_true", help="exchange (copy + merge + filter) of step i on a second stream, behind step i+1's scoring")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -32,6 +35,75 @@ mol = mol.to(dev).eval()
 if a.precision and a.precision != "proved-global":
     mol.precision = a.precision
 lo, hi = shard_bounds(N, a.world, 0)
+if a.method:
+    # ---- the candidate generators: rank 0's step in both forms, collectives replaced by device copies (no RCCL latency) -----------------
+    import json, re, statistics
+    from rails_amd.sharded import ShardedMoLCombTopK, ShardedMoLNaiveTopK
+    m = re.fullmatch(r"(Naive)(\d+)|(Comb)(\d+)_(\d+)", a.method)
+    kg, kc = (int(m.group(2)), 0) if m.group(1) else (int(m.group(4)), int(m.group(5)))
+    G = cfg.query_dot_product_groups * cfg.item_dot_product_groups
+    W, R, n_loc = G * kg + kc, a.world, hi - lo
+    Xall = torch.from_numpy(O.hash_item_table(1, 0, N, cfg.item_embedding_dim)).unsqueeze(0).to(dev)
+    ids_all = torch.arange(1, N + 1, dtype=torch.int64, device=dev).unsqueeze(0)
+    q = O.synthetic_queries(cfg, B).to(dev)
+    kk = min(kp, W)
+
+    def module(x, i):
+        if kc:
+            return rails_amd.MoLCombTopK(mol, x, i, avg_top_k=kc, k_per_group=kg)
+        return rails_amd.MoLNaiveTopK(mol, x, i, k_per_group=kg)
+
+    def median_ms(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(a.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record(); e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    with torch.inference_mode():
+        single = module(Xall, ids_all)
+        t_single = median_ms(lambda: single(q, k=kk))
+        del single
+        local = module(Xall[:, lo:hi], ids_all[:, lo:hi])
+        rows = B * G
+        n_keys = rows * kg + B * kc
+        shift = torch.arange(R, dtype=torch.int64, device=dev).view(R, 1) * n_loc       # rank r's copy names items r * n_loc further on
+
+        def finish(s, i):
+            gathered = E.pack_candidates(s, i, kk).repeat(R, 1)
+            return E.merge_candidates(gathered, R, kk, kk)
+
+        def per_shard():
+            s, i = local(q, k=kk)
+            return finish(s[:, :kk], i[:, :kk])
+
+        def global_form():
+            cand = local.local_candidates(q)
+            msg = torch.empty(n_keys, dtype=torch.int64, device=dev)
+            E.group_keys_pack(cand[0], cand[1], lo, n_loc, kg, out=msg[: rows * kg])
+            if kc:
+                E.group_keys_pack(cand[2], cand[3], lo, n_loc, kc, out=msg[rows * kg :])
+            gathered = (msg.view(1, n_keys) - shift).contiguous()                         # stands for the all-gather
+            union = torch.empty((B, W), dtype=torch.int64, device=dev)
+            for first, n_rows, kx, col, per_row in ((0, rows, kg, 0, G), (rows * kg, B, kc, G * kg, 1)):
+                if kx:
+                    E.group_keys_merge_own(gathered.view(-1)[first:], R, n_rows, kx, lo, hi, out_local=union, out_col=col, rows_per_out_row=per_row,
+                                           rank_stride=n_keys)
+            return finish(*local.rerank_union_masked(q, union, kk))
+
+        t_per, t_glob = median_ms(per_shard), median_ms(global_form)
+    rec = {"method": a.method, "world": R, "shard_items": n_loc, "batch": B, "k": kk, "union_width": W, "steps": a.steps,
+           "single_device_whole_corpus_ms": round(t_single, 4), "per_shard_form_ms": round(t_per, 4), "global_form_ms": round(t_glob, 4),
+           "candidate_message_bytes": 8 * n_keys, "note": "rank 0's step on one GPU, collectives replaced by device copies (no RCCL latency); medians"}
+    print(json.dumps(rec))
+    if a.json:
+        old = json.load(open(a.json)) if os.path.exists(a.json) else []
+        json.dump(old + [rec], open(a.json, "w"), indent=1)
+    sys.exit(0)
 X = torch.from_numpy(O.hash_item_table(1, lo, hi - lo, cfg.item_embedding_dim)).unsqueeze(0).to(dev)
 ids = torch.arange(lo + 1, hi + 1, dtype=torch.int64, device=dev).unsqueeze(0)
 q = O.synthetic_queries(cfg, B).to(dev)
