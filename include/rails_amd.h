@@ -160,6 +160,14 @@ size_t rails_mol_index_floats(const rails_mol_shape* shape, int64_t n_items);
  * of every item into `index` in tile/fragment order. */
 int rails_mol_index_build(const rails_mol_shape* shape, const rails_mol_weights* w, const float* items,
                           int64_t n_items, float* index, void* stream);
+/* In-place update of an existing index of n_items items (added under ABI 15: no struct and no existing entry point changed): item j of
+ * `items` (n_new, D_i) is built and stored at slot positions[j] (int64, device memory) -- rails_mol_index_build's kernel with scatter stores,
+ * one launch, no temporary index; fp32 fragments or, under a split precision, the f16 hi / lo halves.  An item's values do not depend on its
+ * slot or its neighbours: the index equals the one rails_mol_index_build makes of the updated table, bit for bit.  positions must be unique
+ * and inside [0, n_items) (the caller checks; a position outside is skipped, duplicates leave either item).  Touches n_new items' bytes only.
+ * To append, grow the buffer to rails_mol_index_floats(n_items + n_new) (old bytes copied, the rest zero) and update the new positions. */
+int rails_mol_index_update(const rails_mol_shape* shape, const rails_mol_weights* w, const float* items, int64_t n_new, const int64_t* positions,
+                           float* index, int64_t n_items, void* stream);
 /* Inverse view for accessors/tests: plain Ex (n_items, P_X, d) and/or gi (n_items, L); either may be NULL.
  * Mirrors MoLSimilarity.get_item_component_embeddings (similarity_fn.py:294-339). */
 int rails_mol_index_unpack(const rails_mol_shape* shape, const float* index, int64_t n_items, float* ex_out,
@@ -228,6 +236,9 @@ size_t rails_mol_generic_query_pack_floats(const rails_mol_shape* shape, int32_t
 int rails_mol_generic_pack_gate_weights(const rails_mol_shape* shape, const rails_mol_weights* w, float* gate_pack, void* stream);
 int rails_mol_generic_index_build(const rails_mol_shape* shape, const rails_mol_weights* w, const float* items, int64_t n_items, float* index,
                                   void* stream);
+/* rails_mol_index_update for the generic route's row-major index */
+int rails_mol_generic_index_update(const rails_mol_shape* shape, const rails_mol_weights* w, const float* items, int64_t n_new, const int64_t* positions,
+                                   float* index, int64_t n_items, void* stream);
 int rails_mol_generic_index_unpack(const rails_mol_shape* shape, const float* index, int64_t n_items, float* ex_out, float* gi_out, void* stream);
 int rails_mol_generic_query_prologue(const rails_mol_shape* shape, const rails_mol_weights* w, const float* queries, const int64_t* user_ids,
                                      int32_t batch, float* query_pack, float* eq_out, float* gq_out, void* stream);
@@ -250,6 +261,9 @@ int rails_mol_score_indexed_supported(const rails_mol_shape* shape, int32_t batc
  * use rails_mol_score_indexed). */
 size_t rails_mol_index_rows_floats(const rails_mol_shape* shape, int64_t n_items);
 int rails_mol_index_rows_build(const rails_mol_shape* shape, const float* index, int64_t n_items, float* index_rows, void* stream);
+/* The rows of n_new positions copied again from the (already updated) index; nothing else is read or written. */
+int rails_mol_index_rows_update(const rails_mol_shape* shape, const float* index, int64_t n_items, const int64_t* positions, int64_t n_new,
+                                float* index_rows, void* stream);
 /* cand_counts (optional, may be NULL): row b has cand_counts[b] <= n_cand candidates (rails_candidates_select's counts): only logits[b][0 .. cand_counts[b])
  * are written, the tiles past them are skipped. */
 int rails_mol_score_indexed_rows(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch, const float* index_rows,
@@ -281,6 +295,11 @@ int rails_dot_rowwise(const float* queries, const float* items, int64_t n_querie
  * rails_topk and reranks with rails_mol_index_gather + rails_mol_score_candidates. */
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* shape, int64_t n_items);   /* 2*d bytes per item */
 int rails_mol_coarse_build(const rails_mol_shape* shape, const float* index, int64_t n_items, void* table, void* stream);
+/* The rows of n_new positions (int64, device memory, unique, inside [0, n_items)) of an existing table, with rails_mol_coarse_build's arithmetic.
+ * src_index is an fp32-format index: src_in_place != 0 -- the index the table belongs to, update j reads item positions[j]; 0 -- an index of the
+ * n_new updated items alone (what a split-precision caller builds from their raw rows), update j reads item j.  2 d bytes written per update. */
+int rails_mol_coarse_update(const rails_mol_shape* shape, const float* src_index, int32_t src_in_place, const int64_t* positions, int64_t n_new,
+                            void* table, int64_t n_items, void* stream);
 /* eq: plain (batch, P_Q, d) fp32 from rails_mol_query_prologue's eq_out.  average_queries 0: sum over P_Q
  * (forward), 1: mean over P_Q (topk_ids).  scores[b * ld + x]. */
 int rails_mol_coarse_score(const rails_mol_shape* shape, const float* eq, int32_t batch, int32_t average_queries,
@@ -327,6 +346,9 @@ int rails_mol_coarse_prefilter_build(const rails_mol_shape* shape, const void* t
 size_t rails_mol_component_table_bytes(const rails_mol_shape* shape, int64_t n_items);   /* 2 * P_X * d bytes per item */
 int rails_mol_component_build(const rails_mol_shape* shape, const float* index, int64_t n_items, void* table, int64_t n_total, int64_t first_item,
                               void* stream);
+/* The rows of n_new positions in every item group of an existing table of n_total items (arguments as rails_mol_coarse_update). */
+int rails_mol_component_update(const rails_mol_shape* shape, const float* src_index, int32_t src_in_place, const int64_t* positions, int64_t n_new,
+                               void* table, int64_t n_total, void* stream);
 int rails_mol_component_score(const rails_mol_shape* shape, const float* eq, int32_t batch, const void* table,
                               int64_t n_items, float* scores, int64_t ld, const int32_t* run_if, void* stream);
 /* Fused scoring + exact top-k_group of every (query group, item group) row, without the (rows, n_items) score matrix:

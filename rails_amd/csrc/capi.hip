@@ -192,6 +192,33 @@ int rails_mol_index_build(const rails_mol_shape* s, const rails_mol_weights* w, 
   return r == kOk ? r : fail(r, "index_build");
 }
 
+static bool build_weights_ok(const rails_mol_shape* s, const rails_mol_weights* w) {
+  return w && w->i_proj_w && w->i_proj_b && !(s->gating_has_item && (!w->gi_w1 || !w->gi_b1 || !w->gi_w2)) &&
+         !(s->item_hidden_dim > 0 && (!w->i_glu_w || !w->i_glu_b));
+}
+
+int rails_mol_index_update(const rails_mol_shape* s, const rails_mol_weights* w, const float* items, int64_t n_new, const int64_t* positions,
+                           float* index, int64_t n_items, void* stream) {
+  g_err[0] = '\0';
+  if (!shape_supported(s)) return RAILS_ENOTSUP;
+  if (n_new < 0 || n_items < 0) { set_error("index_update: negative size"); return RAILS_EINVAL; }
+  if (n_new == 0) return RAILS_OK;
+  if (!items || !positions || !index || !build_weights_ok(s, w)) { set_error("index_update: NULL pointer"); return RAILS_EINVAL; }
+  const int r = index_update(*s, *w, items, n_new, positions, index, n_items, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "index_update");
+}
+
+int rails_mol_index_rows_update(const rails_mol_shape* s, const float* index, int64_t n_items, const int64_t* positions, int64_t n_new, float* rows,
+                                void* stream) {
+  g_err[0] = '\0';
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  if (is_split(*s)) { set_error("index_rows_update: exact-fp32 index only"); return RAILS_ENOTSUP; }
+  if (n_new < 0 || n_items < 0) { set_error("index_rows_update: negative size"); return RAILS_EINVAL; }
+  if (n_new == 0) return RAILS_OK;
+  if (!index || !positions || !rows) { set_error("index_rows_update: NULL pointer"); return RAILS_EINVAL; }
+  return fail(index_rows_update(*s, index, n_items, positions, n_new, rows, (hipStream_t)stream), "index_rows_update");
+}
+
 int rails_mol_index_unpack(const rails_mol_shape* s, const float* index, int64_t n_items, float* ex_out, float* gi_out,
                            void* stream) {
   g_err[0] = '\0';
@@ -453,6 +480,17 @@ int rails_mol_generic_index_build(const rails_mol_shape* s, const rails_mol_weig
   return r == kOk ? r : fail(r, "generic_index_build");
 }
 
+int rails_mol_generic_index_update(const rails_mol_shape* s, const rails_mol_weights* w, const float* items, int64_t n_new, const int64_t* positions,
+                                   float* index, int64_t n_items, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (n_new < 0 || n_items < 0) { set_error("generic_index_update: negative size"); return RAILS_EINVAL; }
+  if (n_new == 0) return RAILS_OK;
+  if (!items || !positions || !index || !build_weights_ok(s, w)) { set_error("generic_index_update: NULL pointer"); return RAILS_EINVAL; }
+  const int r = index_update_plain(*s, *w, items, n_new, positions, index, n_items, gen_item_floats(*s), gen_dp(*s), gen_lq(*s), (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "generic_index_update");
+}
+
 int rails_mol_generic_index_unpack(const rails_mol_shape* s, const float* index, int64_t n_items, float* ex_out, float* gi_out, void* stream) {
   g_err[0] = '\0';
   if (!generic_supported(s)) return RAILS_ENOTSUP;
@@ -566,6 +604,32 @@ int rails_mol_coarse_build(const rails_mol_shape* s, const float* index, int64_t
 size_t rails_mol_coarse_prefilter_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s)) return 0;
   return coarse_prefilter_bytes(*s, n_items);
+}
+
+static int table_update_check(const rails_mol_shape* s, const float* src, const int64_t* positions, int64_t n_new, void* table, int64_t n_items,
+                              const char* what) {
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  if (s->dot_product_dimension % 8 != 0) { set_error("%s: d must be a multiple of 8", what); return RAILS_ENOTSUP; }
+  if (n_new < 0 || n_items < 0) { set_error("%s: negative size", what); return RAILS_EINVAL; }
+  if (n_new > 0 && (!src || !positions || !table)) { set_error("%s: NULL pointer", what); return RAILS_EINVAL; }
+  if (is_split(*s)) { set_error("%s: needs an fp32-format item index (build one with precision = RAILS_PRECISION_FP32)", what); return RAILS_ENOTSUP; }
+  return RAILS_OK;
+}
+
+int rails_mol_coarse_update(const rails_mol_shape* s, const float* src_index, int32_t src_in_place, const int64_t* positions, int64_t n_new, void* table,
+                            int64_t n_items, void* stream) {
+  g_err[0] = '\0';
+  const int c = table_update_check(s, src_index, positions, n_new, table, n_items, "coarse_update");
+  if (c != RAILS_OK || n_new == 0) return c;
+  return fail(coarse_update(*s, src_index, src_in_place ? 1 : 0, positions, n_new, table, n_items, (hipStream_t)stream), "coarse_update");
+}
+
+int rails_mol_component_update(const rails_mol_shape* s, const float* src_index, int32_t src_in_place, const int64_t* positions, int64_t n_new, void* table,
+                               int64_t n_total, void* stream) {
+  g_err[0] = '\0';
+  const int c = table_update_check(s, src_index, positions, n_new, table, n_total, "component_update");
+  if (c != RAILS_OK || n_new == 0) return c;
+  return fail(component_update(*s, src_index, src_in_place ? 1 : 0, positions, n_new, table, n_total, (hipStream_t)stream), "component_update");
 }
 
 int rails_mol_coarse_prefilter_build(const rails_mol_shape* s, const void* table, int64_t n_items, void* prefilter, void* stream) {

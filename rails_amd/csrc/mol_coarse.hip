@@ -43,6 +43,26 @@ __global__ void coarse_build_kernel(const float* __restrict__ ipack, int64_t n, 
   table[i] = bf16_bits(bf16_rn(acc) / (float)PX);
 }
 
+// The rows of `m` positions of an existing table: update u reads item (src_in_place ? pos[u] : u) of the fp32-format index `src` and writes
+// table row pos[u] -- coarse_build_kernel's arithmetic, 2 d bytes per update.
+__global__ void coarse_update_kernel(const float* __restrict__ src, int src_in_place, const int64_t* __restrict__ pos, int64_t m, int64_t n, int PQ, int PX, int d,
+                                     unsigned short* __restrict__ table) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m * d) return;
+  const int64_t u = i / d;
+  const int dd = (int)(i - u * d);
+  const int64_t p = pos[u];
+  if (p < 0 || p >= n) return;
+  const int64_t item = src_in_place ? p : u;
+  const int64_t tile = item >> 5;
+  const int x = (int)(item & 31);
+  const float* tEx = src + tile * (int64_t)(kTileItems * (PX * d + PQ * PX));
+  const int hi = dd / (d / 2), s = dd - hi * (d / 2);
+  float acc = 0.0f;
+  for (int g = 0; g < PX; ++g) acc += bf16_rn(tEx[((g * (d / 8) + (s >> 2)) * 64 + hi * 32 + x) * 4 + (s & 3)]);
+  table[p * d + dd] = bf16_bits(bf16_rn(acc) / (float)PX);
+}
+
 // ---- the coarse scan (bf16 MFMA) ------------------------------------------------------------------------------
 // 2*d*B flops against 2*d bytes per item: at B = 32 that is 2048 flop per 64-byte item -- 6x what the VALU can stream at
 // HBM rate, nothing for the bf16 MFMA.  A wave takes tiles of 32 items: v_mfma_f32_32x32x16_bf16 with the 32 queries of a
@@ -568,6 +588,15 @@ int coarse_build(const Shape& s, const float* ipack, int64_t n, void* table, hip
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
+int coarse_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream) {
+  const int d = s.dot_product_dimension;
+  const int64_t total = m * d;
+  if (total <= 0) return kOk;
+  hipLaunchKernelGGL(coarse_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, src_in_place, positions, m, n,
+                     s.query_dot_product_groups, s.item_dot_product_groups, d, static_cast<unsigned short*>(table));
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
 int coarse_score(const Shape& s, const float* eq, int B, int avg, const void* table, int64_t n, float* scores, int64_t ld,
                  hipStream_t stream, const int32_t* run_if) {
   if (B <= 0 || n <= 0) return kOk;
@@ -1074,6 +1103,34 @@ int component_build(const Shape& s, const float* ipack, int64_t n, void* table, 
   hipLaunchKernelGGL(component_build_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, ipack, n,
                      s.query_dot_product_groups, s.item_dot_product_groups, s.dot_product_dimension, n_total, first,
                      static_cast<unsigned short*>(table));
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+// The rows of `m` positions in every item group of an existing table of n_total items (component_build_kernel's values; source item as in
+// coarse_update_kernel): 2 P_X d bytes per update, one row per group.
+__global__ void component_update_kernel(const float* __restrict__ src, int src_in_place, const int64_t* __restrict__ pos, int64_t m, int PQ, int PX, int d,
+                                        int64_t n_total, unsigned short* __restrict__ table) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int row = PX * d;
+  if (i >= m * row) return;
+  const int64_t u = i / row;
+  const int rem = (int)(i - u * row);
+  const int g = rem / d, dd = rem - g * d;
+  const int64_t p = pos[u];
+  if (p < 0 || p >= n_total) return;
+  const int64_t item = src_in_place ? p : u;
+  const int64_t tile = item >> 5;
+  const int x = (int)(item & 31);
+  const float* tEx = src + tile * (int64_t)(kTileItems * (PX * d + PQ * PX));
+  const int hi = dd / (d / 2), s = dd - hi * (d / 2);
+  table[((int64_t)g * n_total + p) * d + dd] = bf16_bits(tEx[((g * (d / 8) + (s >> 2)) * 64 + hi * 32 + x) * 4 + (s & 3)]);
+}
+
+int component_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n_total, hipStream_t stream) {
+  const int64_t total = m * s.item_dot_product_groups * s.dot_product_dimension;
+  if (total <= 0) return kOk;
+  hipLaunchKernelGGL(component_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, src_in_place, positions, m,
+                     s.query_dot_product_groups, s.item_dot_product_groups, s.dot_product_dimension, n_total, static_cast<unsigned short*>(table));
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -31,6 +31,8 @@ constexpr size_t kIndexBuildMaxLds = 160 * 1024;
 
 // mol_index.hip / mol_query.hip: the fused route's arithmetic, written row-major (`ld` floats per item / query)
 int index_build_plain(const Shape& s, const Weights& w, const float* items, int64_t n, float* out, int64_t ld, int dp, int lq, hipStream_t stream);
+int index_update_plain(const Shape& s, const Weights& w, const float* items, int64_t n, const int64_t* positions, float* out, int64_t n_index, int64_t ld,
+                       int dp, int lq, hipStream_t stream);
 int query_prologue_plain(const Shape& s, const Weights& w, const float* q, const int64_t* user_ids, int B, float* qpack, int64_t ld, int dp,
                          float* eq_out, float* gq_out, hipStream_t stream);
 

@@ -191,6 +191,11 @@ struct BuildArgs {
   float* plain;
   int64_t plain_ld;
   int dp, lq;
+  // scatter mode (index_update_kernel): input item j is written to slot pos[j] of an existing index of n_index items instead of slot j of a
+  // new one; split: Ex goes out as f16 hi / lo halves (index_split_kernel's layout) straight from the registers
+  const int64_t* pos;
+  int64_t n_index;
+  int split;
 };
 
 __device__ __forceinline__ void dense_cols(const float* __restrict__ W, const float* __restrict__ bias, int col0,
@@ -217,8 +222,10 @@ __device__ __forceinline__ void dense_cols(const float* __restrict__ W, const fl
   }
 }
 
-__global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+// SCATTER: the stores of the update path.  Everything before a store is the same instruction sequence per item whatever its slot (a thread's
+// accumulators are one per item, walked in the same k order), so an item's bits do not depend on where it is stored or on its neighbours.
+template <bool SCATTER>
+__device__ __forceinline__ void index_build_body(const BuildArgs& a, float* smem) {
   const int D = a.D, d = a.d, PX = a.PX, L = a.PQ * a.PX, Hi = a.Hi;
   const int mpc = (kBuildThreads / d) > 0 ? (kBuildThreads / d) : 1;  // component groups per column chunk
   const int chunk_cols = mpc * d;
@@ -232,8 +239,15 @@ __global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a)
   float* gs = ns + kTileItems * mpc;         // [32][IH+1] GLU hidden layer of the item projection (item_hidden_dim > 0)
   const int64_t tile = blockIdx.x;
   const int64_t item0 = tile * kTileItems;
-  float* tEx = a.ipack + tile * (int64_t)(kTileItems * (PX * d + L));
+  const int64_t tile_fl = (int64_t)(kTileItems * (PX * d + L));
+  float* tEx = SCATTER ? a.ipack : a.ipack + tile * tile_fl;
   float* tGi = tEx + kTileItems * PX * d;
+  // scatter: where item x of this workgroup goes (-1: past the input, or a position outside the index -- nothing is stored)
+  auto dest = [&](int x) -> int64_t {
+    if (item0 + x >= a.n) return -1;
+    const int64_t p = a.pos[item0 + x];
+    return (p >= 0 && p < a.n_index) ? p : -1;
+  };
 
   for (int i = threadIdx.x; i < kTileItems * D; i += kBuildThreads) {
     const int x = i / D, k = i - x * D;
@@ -293,11 +307,39 @@ __global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a)
         const int mg = c / a.dp, k = c - mg * a.dp;
         float v = 0.0f;
         if (k < d && item0 + x < a.n) v = cs[x * cs_ld + mg * d + k] / ns[x * mpc + mg];
-        a.plain[(item0 + x) * a.plain_ld + (m0 + mg) * a.dp + k] = v;
+        if constexpr (SCATTER) {
+          const int64_t p = dest(x);
+          if (p >= 0) a.plain[p * a.plain_ld + (m0 + mg) * a.dp + k] = v;
+        } else {
+          a.plain[(item0 + x) * a.plain_ld + (m0 + mg) * a.dp + k] = v;
+        }
+      }
+    }
+    if constexpr (SCATTER) {
+      if (!a.plain && a.split) {
+        // split-f16 format: a lane's chunks (2ks, 2ks + 1) of an item group are its 8 k-values of K = 16 step ks; they go out as the 8 hi
+        // halves (chunk 2ks) and the 8 lo halves (chunk 2ks + 1) -- what index_split_kernel makes of the fp32 fragments
+        const int pairs = groups * (d / 16) * 64;
+        for (int i = threadIdx.x; i < pairs; i += kBuildThreads) {
+          const int lane = i & 63, ks = (i >> 6) % (d / 16), mg = (i >> 6) / (d / 16);
+          const int x = lane & 31, hi = lane >> 5;
+          const int64_t p = dest(x);
+          if (p < 0) continue;
+          const float nv = ns[x * mpc + mg];
+          unsigned short hb[8], lb[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) split_f16(cs[x * cs_ld + mg * d + kdim_of(8 * ks + j, hi, d)] / nv, hb[j], lb[j]);
+          uint4 H, Lo;
+          H.x = hb[0] | (unsigned)hb[1] << 16; H.y = hb[2] | (unsigned)hb[3] << 16; H.z = hb[4] | (unsigned)hb[5] << 16; H.w = hb[6] | (unsigned)hb[7] << 16;
+          Lo.x = lb[0] | (unsigned)lb[1] << 16; Lo.y = lb[2] | (unsigned)lb[3] << 16; Lo.z = lb[4] | (unsigned)lb[5] << 16; Lo.w = lb[6] | (unsigned)lb[7] << 16;
+          uint4* o = reinterpret_cast<uint4*>(tEx + (p >> 5) * tile_fl) + ((m0 + mg) * (d / 8) + 2 * ks) * 64 + hi * 32 + (int)(p & 31);
+          o[0] = H;
+          o[64] = Lo;
+        }
       }
     }
     // fragment order: Ex slot (m, c8, lane)[j] = Ex[x = lane&31][m][kdim_of(4*c8 + j, lane>>5)]
-    const int slots = a.plain ? 0 : groups * (d / 8) * 64;
+    const int slots = (a.plain || (SCATTER && a.split)) ? 0 : groups * (d / 8) * 64;
     for (int i = threadIdx.x; i < slots; i += kBuildThreads) {
       const int lane = i & 63, c8 = (i >> 6) % (d / 8), mg = (i >> 6) / (d / 8);
       const int x = lane & 31, hi = lane >> 5;
@@ -306,8 +348,13 @@ __global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a)
       float* ov = reinterpret_cast<float*>(&o);
 #pragma unroll
       for (int j = 0; j < 4; ++j) ov[j] = cs[x * cs_ld + mg * d + kdim_of(4 * c8 + j, hi, d)] / nv;
-      if (item0 + x >= a.n) o = make_float4(0.f, 0.f, 0.f, 0.f);
-      reinterpret_cast<float4*>(tEx)[((m0 + mg) * (d / 8) + c8) * 64 + lane] = o;
+      if constexpr (SCATTER) {
+        const int64_t p = dest(x);
+        if (p >= 0) reinterpret_cast<float4*>(tEx + (p >> 5) * tile_fl)[((m0 + mg) * (d / 8) + c8) * 64 + hi * 32 + (int)(p & 31)] = o;
+      } else {
+        if (item0 + x >= a.n) o = make_float4(0.f, 0.f, 0.f, 0.f);
+        reinterpret_cast<float4*>(tEx)[((m0 + mg) * (d / 8) + c8) * 64 + lane] = o;
+      }
     }
     __syncthreads();
   }
@@ -324,7 +371,13 @@ __global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a)
   if (a.plain) {
     for (int i = threadIdx.x; i < kTileItems * a.lq; i += kBuildThreads) {
       const int x = i / a.lq, l = i - x * a.lq;
-      a.plain[(item0 + x) * a.plain_ld + PX * a.dp + l] = (l < L && item0 + x < a.n) ? cs[x * cs_ld + l] : 0.0f;
+      const float v = (l < L && item0 + x < a.n) ? cs[x * cs_ld + l] : 0.0f;
+      if constexpr (SCATTER) {
+        const int64_t p = dest(x);
+        if (p >= 0) a.plain[p * a.plain_ld + PX * a.dp + l] = v;
+      } else {
+        a.plain[(item0 + x) * a.plain_ld + PX * a.dp + l] = v;
+      }
     }
     return;
   }
@@ -335,9 +388,25 @@ __global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a)
     float* ov = reinterpret_cast<float*>(&o);
 #pragma unroll
     for (int j = 0; j < 4; ++j) ov[j] = cs[x * cs_ld + logit_of(4 * ec + j, hi, a.PQ, PX)];
-    if (item0 + x >= a.n) o = make_float4(0.f, 0.f, 0.f, 0.f);
-    reinterpret_cast<float4*>(tGi)[ec * 64 + lane] = o;
+    if constexpr (SCATTER) {
+      const int64_t p = dest(x);
+      if (p >= 0) reinterpret_cast<float4*>(tGi + (p >> 5) * tile_fl)[ec * 64 + hi * 32 + (int)(p & 31)] = o;
+    } else {
+      if (item0 + x >= a.n) o = make_float4(0.f, 0.f, 0.f, 0.f);
+      reinterpret_cast<float4*>(tGi)[ec * 64 + lane] = o;
+    }
   }
+}
+
+__global__ __launch_bounds__(kBuildThreads) void index_build_kernel(BuildArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  index_build_body<false>(a, smem);
+}
+
+// The positions-aware build of the update path: one workgroup per 32 INPUT items, each stored at its own position of an existing index.
+__global__ __launch_bounds__(kBuildThreads) void index_update_kernel(BuildArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  index_build_body<true>(a, smem);
 }
 
 static size_t build_lds_bytes(const Shape& s) {
@@ -352,7 +421,7 @@ static size_t build_lds_bytes(const Shape& s) {
 size_t index_build_lds_bytes(const Shape& s) { return build_lds_bytes(s); }
 
 static int index_build_launch(const Shape& s, const Weights& w, const float* items, int64_t n, float* ipack, float* plain, int64_t plain_ld,
-                              int dp, int lq, hipStream_t stream) {
+                              int dp, int lq, hipStream_t stream, const int64_t* pos = nullptr, int64_t n_index = 0) {
   const int64_t tiles = num_tiles(n);
   if (tiles == 0) return kOk;
   BuildArgs a;
@@ -363,13 +432,25 @@ static int index_build_launch(const Shape& s, const Weights& w, const float* ite
   a.has_gate = s.gating_has_item;
   a.l2norm = s.dot_product_l2_norm; a.eps = s.eps;
   a.plain = plain; a.plain_ld = plain_ld; a.dp = dp; a.lq = lq;
+  a.pos = pos; a.n_index = n_index; a.split = (pos && !plain && is_split(s)) ? 1 : 0;
   const size_t lds = build_lds_bytes(s);
   if (lds > 160 * 1024) { set_error("index build needs %zu B of LDS (> 160 KiB) for this shape", lds); return kErrUnsupported; }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&index_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)lds) != hipSuccess)
-    return kErrLaunch;
-  hipLaunchKernelGGL(index_build_kernel, dim3((unsigned)tiles), dim3(kBuildThreads), lds, stream, a);
+  if (a.split && s.dot_product_dimension % 16 != 0) { set_error("precision f16x3 needs dot_product_dimension % 16 == 0"); return kErrUnsupported; }
+  const void* fn = pos ? reinterpret_cast<const void*>(&index_update_kernel) : reinterpret_cast<const void*>(&index_build_kernel);
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return kErrLaunch;
+  if (pos) hipLaunchKernelGGL(index_update_kernel, dim3((unsigned)tiles), dim3(kBuildThreads), lds, stream, a);
+  else hipLaunchKernelGGL(index_build_kernel, dim3((unsigned)tiles), dim3(kBuildThreads), lds, stream, a);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+// items[j] -> slot positions[j] of an index of n_index items, in the index's own format (fp32 fragments, or f16 hi / lo under a split shape)
+int index_update(const Shape& s, const Weights& w, const float* items, int64_t n, const int64_t* positions, float* ipack, int64_t n_index, hipStream_t stream) {
+  return index_build_launch(s, w, items, n, ipack, nullptr, 0, 0, 0, stream, positions, n_index);
+}
+
+int index_update_plain(const Shape& s, const Weights& w, const float* items, int64_t n, const int64_t* positions, float* out, int64_t n_index, int64_t ld,
+                       int dp, int lq, hipStream_t stream) {
+  return index_build_launch(s, w, items, n, nullptr, out, ld, dp, lq, stream, positions, n_index);
 }
 
 int index_build(const Shape& s, const Weights& w, const float* items, int64_t n, float* ipack, hipStream_t stream) {
@@ -473,6 +554,27 @@ int index_rows_build(const Shape& s, const float* ipack, int64_t n, float* rows,
   const int64_t total = n * rp;
   hipLaunchKernelGGL(index_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const float4*>(ipack), n, rp, tile_f4,
                      reinterpret_cast<float4*>(rows));
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+// the rows of `m` positions refreshed from the (already updated) index: m * rp float4, nothing else is touched
+__global__ void index_rows_update_kernel(const float4* __restrict__ ipack, int64_t n, const int64_t* __restrict__ pos, int64_t m, int rp, int tile_f4,
+                                         float4* __restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m * rp) return;
+  const int64_t u = i / rp;
+  const int64_t item = pos[u];
+  if (item < 0 || item >= n) return;
+  const int j = (int)(i - u * rp), slot = j >> 1, h = j & 1;
+  rows[item * rp + j] = ipack[(item >> 5) * tile_f4 + slot * 64 + h * 32 + (item & 31)];
+}
+
+int index_rows_update(const Shape& s, const float* ipack, int64_t n, const int64_t* positions, int64_t m, float* rows, hipStream_t stream) {
+  if (m <= 0) return kOk;
+  const int tile_f4 = (int)(tile_floats(s) / 4), rp = tile_f4 / 32;
+  const int64_t total = m * rp;
+  hipLaunchKernelGGL(index_rows_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const float4*>(ipack), n, positions, m,
+                     rp, tile_f4, reinterpret_cast<float4*>(rows));
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -101,6 +101,11 @@ int pack_gate_weights(const Shape& s, const Weights& w, float* wpack, hipStream_
 int index_build(const Shape& s, const Weights& w, const float* items, int64_t n, float* ipack, hipStream_t stream);
 int index_unpack(const Shape& s, const float* ipack, int64_t n, float* ex, float* gi, hipStream_t stream);
 int index_rows_build(const Shape& s, const float* ipack, int64_t n, float* rows, hipStream_t stream);
+// in-place updates (rails_mol_*_update): items / rows of `positions` only
+int index_update(const Shape& s, const Weights& w, const float* items, int64_t n, const int64_t* positions, float* ipack, int64_t n_index, hipStream_t stream);
+int index_rows_update(const Shape& s, const float* ipack, int64_t n, const int64_t* positions, int64_t m, float* rows, hipStream_t stream);
+int coarse_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream);
+int component_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n_total, hipStream_t stream);
 // fp32 Ex fragments of a freshly built index -> f16 hi/lo fragments, in place (precision f16x3)
 int index_split_inplace(const Shape& s, float* ipack, int64_t n, hipStream_t stream);
 int index_gather(const Shape& s, const float* ipack, int64_t n, const int64_t* idx, int64_t rows, int64_t n_cand,

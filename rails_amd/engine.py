@@ -343,6 +343,60 @@ class MolEngine:
             _lib.check(self.lib.rails_mol_index_rows_build(C.byref(self.shape), _ptr(index.buf), index.n_items, _ptr(rows), _stream()), "rails_mol_index_rows_build")
         return rows
 
+    # ---- in-place updates (MoLTopKModule.update_items / append_items): every method touches the updated positions' bytes only ----------------
+    def update_index(self, index: MolIndex, positions: torch.Tensor, items: torch.Tensor) -> None:
+        """items (M, D_i) -> slots positions (M,) int64 on the device, unique and inside [0, index.n_items) (the caller has checked), of `index`
+        in its own format (rails_mol_index_update / rails_mol_generic_index_update): the bits build_index gives the updated table."""
+        _require_device(items, "item_embeddings")
+        if items.dim() != 2 or items.shape[1] != self.spec.item_embedding_dim or positions.shape != (items.shape[0],) or positions.dtype != torch.int64:
+            raise ValueError(f"update_index takes (M, {self.spec.item_embedding_dim}) items and (M,) int64 positions, got {tuple(items.shape)} and {tuple(positions.shape)}")
+        items, positions = _f32c(items), positions.contiguous()
+        with _on_device(index.buf.device):
+            _lib.check(self._fn("index_update")(C.byref(self.shape), C.byref(self.weights), _ptr(items), items.shape[0], _ptr(positions), _ptr(index.buf),
+                                                index.n_items, _stream()), self._name("index_update"))
+
+    def update_index_rows(self, index: MolIndex, rows: torch.Tensor, positions: torch.Tensor) -> None:
+        """The row-major copy's rows at `positions`, from the updated index."""
+        positions = positions.contiguous()
+        with _on_device(index.buf.device):
+            _lib.check(self.lib.rails_mol_index_rows_update(C.byref(self.shape), _ptr(index.buf), index.n_items, _ptr(positions), positions.numel(), _ptr(rows),
+                                                            _stream()), "rails_mol_index_rows_update")
+
+    def update_source(self, index: MolIndex, items: torch.Tensor) -> Tuple[torch.Tensor, int]:
+        """What the bf16 tables' updates are cut from -> (fp32-format index, read in place?): the (updated) index itself for fp32 engines; in
+        f16x3 precision, whose index holds Ex to 22 bits, a temporary fp32-format index of the M updated rows alone (as _derived_table's chunks)."""
+        self._fused_only("the coarse / component tables")
+        if self.precision == "fp32":
+            return index.buf, 1
+        items = _f32c(items)
+        m = items.shape[0]
+        tmp = torch.empty(self.lib.rails_mol_index_floats(C.byref(self._fp32_shape), m), dtype=torch.float32, device=items.device)
+        with _on_device(items.device):
+            _lib.check(self.lib.rails_mol_index_build(C.byref(self._fp32_shape), C.byref(self.weights), _ptr(items), m, _ptr(tmp), _stream()), "rails_mol_index_build")
+        return tmp, 0
+
+    def update_coarse_table(self, table: torch.Tensor, positions: torch.Tensor, source: Tuple[torch.Tensor, int]) -> None:
+        """Rows `positions` of a build_coarse_table table from update_source's pair."""
+        positions = positions.contiguous()
+        with _on_device(table.device):
+            _lib.check(self.lib.rails_mol_coarse_update(C.byref(self._fp32_shape), _ptr(source[0]), source[1], _ptr(positions), positions.numel(), _ptr(table),
+                                                        table.shape[0], _stream()), "rails_mol_coarse_update")
+
+    def update_component_table(self, table: torch.Tensor, positions: torch.Tensor, source: Tuple[torch.Tensor, int]) -> None:
+        """Rows `positions` of every item group of a build_component_table table (P_X, N, d)."""
+        positions = positions.contiguous()
+        with _on_device(table.device):
+            _lib.check(self.lib.rails_mol_component_update(C.byref(self._fp32_shape), _ptr(source[0]), source[1], _ptr(positions), positions.numel(), _ptr(table),
+                                                           table.shape[1], _stream()), "rails_mol_component_update")
+
+    def grow_index(self, index: MolIndex, n_new: int) -> None:
+        """`index` with room for n_new more items, IN PLACE (the same object: caches keyed on it stay valid): the old bytes copied, the rest zero
+        (what the padding slots of a fresh index hold).  The new slots are filled by update_index."""
+        n = index.n_items + n_new
+        buf = torch.zeros(self._fn("index_floats")(C.byref(self.shape), n), dtype=torch.float32, device=index.buf.device)
+        buf[: index.buf.numel()].copy_(index.buf)
+        index.buf, index.n_items = buf, n
+
     def score_indexed_rows(self, qpack: torch.Tensor, batch: int, rows: torch.Tensor, n_items: int, positions: torch.Tensor,
                            counts: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """score_indexed with the candidates read from the row-major copy: whole cache lines per candidate, same bits.

@@ -42,6 +42,14 @@ def shard_bounds(n_items: int, world_size: int, rank: int) -> Tuple[int, int]:
     return lo, min(n_items, lo + per)
 
 
+def route_update_positions(global_positions: torch.Tensor, lo: int, hi: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Global -> local routing of an update on the shard that owns the global positions [lo, hi): -> (local positions, rows), `rows` being the
+    indices into the update (its embedding / id rows) that fall inside the shard, in the order given; everything else is another shard's."""
+    p = global_positions.reshape(-1).to(torch.int64)
+    rows = torch.nonzero((p >= lo) & (p < hi)).reshape(-1)
+    return p[rows] - lo, rows
+
+
 def pack_candidates(scores: torch.Tensor, ids: torch.Tensor, k: int) -> torch.Tensor:
     """(B, k_local) fp32 scores + int64 ids -> one (B, 2k) int64 message (score bits | ids); rows shorter than
     k are padded with -inf / id -1 so every rank sends the same size."""
@@ -232,6 +240,45 @@ class ShardedTopK(TopKModule):
             return mi, ms
         return ms, mi
 
+    # ---- in-place corpus changes (topk_modules.MoLTopKModule.update_items) ----------------------------------------------------------
+    def shard_range(self) -> Tuple[int, int]:
+        """[lo, hi): the global positions this rank owns."""
+        lo = getattr(self, "_offset", None)
+        if lo is None:
+            rank = dist.get_rank(self._group) if dist.is_initialized() else 0
+            lo = shard_bounds(self._n_total, self._world, rank)[0]
+        return int(lo), int(lo) + self._n_local
+
+    def update_items(self, global_positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
+        """MoLTopKModule.update_items on an item-sharded corpus, called ALIKE on every rank with GLOBAL positions ((M,) int64, unique, inside
+        [0, n_items_total)): each rank applies the positions inside its shard range to its local module (route_update_positions) and ignores the
+        rest.  No collective is issued (what the ranks agree on collectively -- the global proof's guard -- is agreed again at the next call)."""
+        local = self._local_module
+        if local is None or not hasattr(local, "update_items"):
+            raise NotImplementedError(f"{type(self).__name__}.update_items needs the HIP local module")
+        emb = item_embeddings[0] if torch.is_tensor(item_embeddings) and item_embeddings.dim() == 3 and item_embeddings.shape[0] == 1 else item_embeddings
+        if not torch.is_tensor(emb) or emb.dim() != 2:
+            raise ValueError("item_embeddings must be (M, D) or (1, M, D)")
+        host = local._checked_positions(global_positions, emb.shape[0], self._n_total).cpu()
+        if item_ids is not None and (not torch.is_tensor(item_ids) or item_ids.numel() != emb.shape[0]):
+            raise ValueError(f"item_ids must hold {emb.shape[0]} ids")
+        if emb.shape[0] == 0:
+            return
+        lo, hi = self.shard_range()
+        local_pos, rows = route_update_positions(host, lo, hi)
+        if rows.numel():
+            pick = rows.to(emb.device)
+            local.update_items(local_pos, emb.index_select(0, pick), None if item_ids is None else item_ids.reshape(-1).index_select(0, rows.to(item_ids.device)))
+        else:
+            local._update_rows_arg(emb, None if item_ids is None else item_ids.reshape(-1))       # the same argument errors on every rank
+        self._after_local_update()
+
+    def _after_local_update(self) -> None:
+        pass
+
+    def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
+        raise NotImplementedError(f"{type(self).__name__}.append_items: growing an item-sharded corpus would move the shard bounds; build the shards again")
+
     def exchange_info(self) -> dict:
         """What carried the exchange: backend of the process group and its size (bench.py reports it)."""
         if not dist.is_initialized():
@@ -285,6 +332,10 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
         self._gp_pad = 1
         self._gp_streak = 0
         self._gp_stats = {"calls": 0, "fallbacks": 0, "proved_calls": 0, "bound_violations": 0}
+
+    def _after_local_update(self) -> None:
+        # the global proof's guard limit comes from max |gi| over every shard: decided again, collectively, at the next call (every rank alike)
+        self._gp_reset(None, None)
 
     def _make_local_module(self, mol_module, item_embeddings_shard, item_ids_shard) -> TopKModule:
         # the size-dependent choices of the proved flow (one eps or per-pair bounds, candidate margins) are made for the SHARD size every rank

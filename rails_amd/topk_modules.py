@@ -106,6 +106,141 @@ class MoLTopKModule(TopKModule):
         finally:
             self._call_eng = outer
 
+    # ---- in-place corpus changes ---------------------------------------------------------------------------------
+    # After any sequence of update_items / append_items the module holds what a module freshly constructed from the resulting table, the
+    # resulting ids and the same mol_module holds -- every derived buffer bit for bit -- and answers alike.  Per-item index values depend on
+    # the item's own row alone (one workgroup computes 32 items with one accumulator per item), so an update recomputes the changed items
+    # and nothing else: O(M) bytes per held buffer.  Whole passes over the corpus: the int8 pre-filter (one scale for the whole table:
+    # rebuilt from the updated coarse table) and the proved mode's max |gi| (metadata of the bound); append_items also copies what it grows.
+    # Both calls are issued on the current stream, behind everything already enqueued there; the module's own side streams (submit()'s, the
+    # audit's) are JOINED first: handles outstanding from submit() keep the results of the corpus they were submitted against.
+    def update_items(self, positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
+        """Replace the items at `positions` ((M,) int64, CPU or device: POSITIONS 0 .. N-1 of this module's corpus, not ids; unique) by the rows of
+        `item_embeddings` ((M, D) or (1, M, D), on the module's device, the table's dtype) and, when given, their ids by `item_ids` ((M,) or
+        (1, M)).  The rows are written INTO the item table (and the ids into the id tensor) the module borrowed at construction: the caller's
+        tensors change too.  Every derived buffer the module holds is then brought up to date at those positions only; one not built yet stays
+        unbuilt.  ValueError before any launch for bad shapes / dtypes / positions (the uniqueness check costs one device sync when the
+        positions live on the device).  M = 0 is a no-op."""
+        self._check_updatable("update_items")
+        emb, ids = self._update_rows_arg(item_embeddings, item_ids)
+        pos = self._checked_positions(positions, emb.shape[0], self.num_items)
+        if emb.shape[0] == 0:
+            return
+        with torch.inference_mode():
+            self._join_side_streams()
+            eng = self._bind()
+            pos = pos.to(self._item_embeddings.device)
+            self._item_embeddings[0].index_copy_(0, pos, emb)
+            if ids is not None:
+                own = self._item_ids[0] if self._item_ids.dim() == 2 else self._item_ids
+                own.index_copy_(0, pos.to(own.device), ids.to(device=own.device, dtype=own.dtype))
+                if self._ids_flat.data_ptr() != own.data_ptr():
+                    self._ids_flat.index_copy_(0, pos, ids.to(device=pos.device, dtype=torch.int64))
+            self._refresh(eng, pos, emb)
+            self._after_update(eng)
+
+    def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
+        """Grow the corpus from N to N + M items, the new ones at positions N .. N + M - 1.  Every held buffer is grown with device copies and the
+        new range goes through update_items' kernels: no old item is recomputed -- unless the larger corpus makes the module choose another
+        engine (the default exact mode turning proved at 16 384 items: the split-f16 index a fresh module of N + M items holds is then built,
+        as for a fresh module).  Everything a fresh module decides from N is decided again for N + M.  From this call on the module OWNS its item
+        table and ids (the caller's tensors are no longer written)."""
+        self._check_updatable("append_items")
+        if item_ids is None:
+            raise ValueError("append_items needs the ids of the new items")
+        emb, ids = self._update_rows_arg(item_embeddings, item_ids)
+        m = emb.shape[0]
+        if m == 0:
+            return
+        with torch.inference_mode():
+            self._join_side_streams()
+            eng = self._bind()
+            n, dev = self.num_items, self._item_embeddings.device
+            self._item_embeddings = torch.cat([self._item_embeddings, emb.unsqueeze(0)], dim=1)
+            self._item_ids = torch.cat([self._item_ids.reshape(1, -1), ids.reshape(1, -1).to(device=self._item_ids.device, dtype=self._item_ids.dtype)], dim=1)
+            self._ids_flat = torch.cat([self._ids_flat, ids.to(device=dev, dtype=torch.int64)])
+            self._grow(eng, m)
+            self._refresh(eng, torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
+            self._after_append(eng)
+
+    def _check_updatable(self, what: str) -> None:
+        """Modules whose state cannot follow an in-place change refuse here, before anything is touched."""
+
+    def _update_rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor]):
+        table = self._item_embeddings
+        emb = item_embeddings
+        if not torch.is_tensor(emb):
+            raise ValueError("item_embeddings must be a tensor")
+        if emb.dim() == 3 and emb.shape[0] == 1:
+            emb = emb[0]
+        if emb.dim() != 2 or emb.shape[1] != table.shape[2]:
+            raise ValueError(f"item_embeddings must be (M, {table.shape[2]}) or (1, M, {table.shape[2]}), got {tuple(item_embeddings.shape)}")
+        if table.is_cuda:
+            E._require_device(emb, "item_embeddings")
+        if emb.device != table.device or emb.dtype != table.dtype:
+            raise ValueError(f"item_embeddings must be {table.dtype} on {table.device}, got {emb.dtype} on {emb.device}")
+        ids = None
+        if item_ids is not None:
+            if (not torch.is_tensor(item_ids) or item_ids.dtype != self._item_ids.dtype or item_ids.numel() != emb.shape[0]
+                    or not (item_ids.dim() == 1 or (item_ids.dim() == 2 and item_ids.shape[0] == 1))):
+                raise ValueError(f"item_ids must be ({emb.shape[0]},) or (1, {emb.shape[0]}) {self._item_ids.dtype}")
+            ids = item_ids.reshape(-1)
+        return emb, ids
+
+    @staticmethod
+    def _checked_positions(positions: torch.Tensor, m: int, n: int) -> torch.Tensor:
+        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or tuple(positions.shape) != (m,):
+            raise ValueError(f"positions must be ({m},) int64")
+        if m:
+            host = positions.cpu()      # (the one sync of a device tensor)
+            if int(host.min()) < 0 or int(host.max()) >= n:
+                raise ValueError(f"positions must lie in [0, {n})")
+            if torch.unique(host).numel() != m:
+                raise ValueError("positions must be unique")
+        return positions
+
+    def _join_side_streams(self) -> None:
+        if not self._item_embeddings.is_cuda:
+            return
+        cur = torch.cuda.current_stream(self._item_embeddings.device)
+        for side in list(getattr(self, "_side_streams", None) or ()) + [getattr(self, "_audit_stream", None)]:
+            if side is not None:
+                cur.wait_stream(side)
+
+    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        """Every held buffer at positions `pos` (device), whose raw rows are `emb`; subclasses add theirs behind this one's."""
+        self._upd_source = None
+        eng.update_index(self._index, pos, emb)
+        c = self._rows_cache
+        if c is not None and c[0] is eng and c[1] is self._index and c[2] is not None:
+            eng.update_index_rows(self._index, c[2], pos)
+
+    def _table_source(self, eng, emb: torch.Tensor):
+        """engine.update_source, once per update (the coarse and the component table share it)."""
+        if self._upd_source is None:
+            self._upd_source = eng.update_source(self._index, emb)
+        return self._upd_source
+
+    def _grow(self, eng, m: int) -> None:
+        """Room for m more items in every held buffer (old bytes copied; the new range is written by _refresh)."""
+        c = self._rows_cache
+        held = c is not None and c[0] is eng and c[1] is self._index
+        eng.grow_index(self._index, m)
+        if held and c[2] is not None:
+            rows = torch.empty(eng.lib.rails_mol_index_rows_floats(E.C.byref(eng.shape), self._index.n_items), dtype=torch.float32, device=c[2].device)
+            rows[: c[2].numel()].copy_(c[2])
+            self._rows_cache = (eng, self._index, rows)
+        else:
+            self._rows_cache = None      # not held (or refused for its size): decided again at the next rerank, as for a fresh module
+        self._scratch.clear()            # recycled buffers sized by N
+
+    def _after_update(self, eng) -> None:
+        self._upd_source = None
+
+    def _after_append(self, eng) -> None:
+        self._upd_source = None
+        self._bind()
+
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus."""
         eng = self._bind()
@@ -162,6 +297,7 @@ class MoLTopKModule(TopKModule):
 
     RERANK_ROWS_COPY_MAX_BYTES = 8 << 30     # fp32 indexes up to this size get a row-major copy for the candidate re-scoring of the rerank paths (0: never)
     _rows_cache = None
+    _upd_source = None
 
     def _index_rows(self, eng) -> Optional[torch.Tensor]:
         """The row-major copy of this module's fp32 index (rails_mol_index_rows_build), built at the first rerank; None where it does not apply
@@ -777,6 +913,44 @@ class MoLBruteForceTopK(MoLTopKModule):
         self.rescore_stats["kc"] = kc
         return msg, qpack32
 
+    # ---- in-place corpus changes: the proved mode's companions -----------------------------------------------------------------------
+    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        super()._refresh(eng, pos, emb)
+        ex = eng.exact
+        if ex is not None and self._index32 is not None and self._index32_engine is ex:
+            ex.update_index(self._index32, pos, emb)
+            if self._rows32 is not None:
+                ex.update_index_rows(self._index32, self._rows32, pos)
+        self._risk_pool = self._risk_rows = None      # (the monitored flow's probes follow the raw rows' norms: drawn again at the next call)
+
+    def _grow(self, eng, m: int) -> None:
+        super()._grow(eng, m)
+        ex = eng.exact
+        if ex is not None and self._index32 is not None and self._index32_engine is ex:
+            ex.grow_index(self._index32, m)
+            if self._rows32 is not None:
+                rows = torch.empty(ex.lib.rails_mol_index_rows_floats(E.C.byref(ex.shape), self._index32.n_items), dtype=torch.float32, device=self._rows32.device)
+                rows[: self._rows32.numel()].copy_(self._rows32)
+                self._rows32 = rows
+
+    def _after_update(self, eng) -> None:
+        """The bound's one corpus-dependent figure, GATE_GUARD / max |gi|, as a fresh module reads it at its first bind: one pass over the item-gate
+        rows of the index (N * L floats; an old maximum may have belonged to a replaced item)."""
+        super()._after_update(eng)
+        pol = self._policy
+        if eng.exact is not None and eng.dense_precision == "f16x3" and pol.eps is not None and pol.terms is not None and math.isfinite(float(pol.terms.get("eps", math.inf))):
+            pol = pol.with_guard(self._gi_abs_max())
+            self._gate_guard_limit = pol.guard_limit
+            self._policy = pol
+
+    def _after_append(self, eng) -> None:
+        """Proved or dense, the form of the bound, the margins: decided for N + M items as at construction (_bind: a changed choice of engine builds
+        that engine's indexes from the table, the same choice keeps the grown ones and re-reads the guard)."""
+        self._policy = BoundPolicy()
+        self._gate_guard_limit = None
+        self._probe_pool = None
+        super()._after_append(eng)
+
     ROWS_COPY_MAX_BYTES = 8 << 30      # the row-major copy of the fp32 index is kept for indexes up to this size (0: never)
     _rows32 = None
 
@@ -1184,6 +1358,26 @@ class MoLAvgTopK(MoLTopKModule):
             self._coarse_prefilter = eng.build_coarse_prefilter(self._coarse_table) if self._coarse_table.shape[0] >= self.PREFILTER_MIN_ITEMS else None
         return self._coarse_table
 
+    # ---- in-place corpus changes: the coarse table and its int8 copy ------------------------------------------------------------------
+    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        super()._refresh(eng, pos, emb)
+        if self._coarse_engine is eng and self._coarse_table is not None:
+            eng.update_coarse_table(self._coarse_table, pos, self._table_source(eng, emb))
+            # the int8 copy has ONE scale for the whole table: rebuilt from the updated table (one streaming pass over N rows, the one O(N) step
+            # of an update), with its statistics and their check schedule as for a fresh table -- a copy dropped for its statistics comes back
+            self._coarse_prefilter = eng.build_coarse_prefilter(self._coarse_table) if self._coarse_table.shape[0] >= self.PREFILTER_MIN_ITEMS else None
+            self._prefilter_calls = 0
+            self._prefilter_pending = None
+
+    def _grow(self, eng, m: int) -> None:
+        super()._grow(eng, m)
+        self._redo_fit_memo.clear()
+        if self._coarse_engine is eng and self._coarse_table is not None:
+            old = self._coarse_table
+            table = torch.empty((old.shape[0] + m, old.shape[1]), dtype=old.dtype, device=old.device)
+            table[: old.shape[0]].copy_(old)
+            self._coarse_table = table
+
     PREFILTER_MAX_FIRED = 0.35        # fraction of (tile, query tile) blocks passing the integer bound beyond which the copy is dropped
     PREFILTER_CHECK_CALLS = (2, 64)   # the header's statistics are read (16 bytes, one sync) after this many calls, then every so many
 
@@ -1472,6 +1666,20 @@ class _ComponentCandidates:
             self._comp_table = eng.build_component_table(self._index, self._item_embeddings[0])
         return self._comp_table
 
+    # ---- in-place corpus changes: the component table (item-group-major: one row per group and position, group stride N) -----------------
+    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        super()._refresh(eng, pos, emb)
+        if self._comp_engine is eng and self._comp_table is not None:
+            eng.update_component_table(self._comp_table, pos, self._table_source(eng, emb))
+
+    def _grow(self, eng, m: int) -> None:
+        super()._grow(eng, m)
+        if self._comp_engine is eng and self._comp_table is not None:
+            old = self._comp_table
+            table = torch.empty((old.shape[0], old.shape[1] + m, old.shape[2]), dtype=old.dtype, device=old.device)
+            table[:, : old.shape[1]].copy_(old)
+            self._comp_table = table
+
     def _component_topk(self, eq: torch.Tensor, k_per_group: int, pending: Optional[list] = None, with_scores: bool = False):
         """-> (B, P_Q * P_X * k_per_group) positions: top k_per_group items of every (query group, item group) pair.
         `pending`: deferred validity check of the fused scan, as in MoLAvgTopK._coarse_topk_from_eq.
@@ -1629,6 +1837,11 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
                 raise NotImplementedError(f"MoLNaiveTopK: use_faiss=True takes dot_product_dimension in {{32, 64, 128}}, got {mol_module._dot_product_dimension}")
             if self.num_items < self._ivf_args["nlist"]:
                 raise ValueError(f"MoLNaiveTopK: {self.num_items} items cannot fill nlist = {nlist} lists")
+
+    def _check_updatable(self, what: str) -> None:
+        if self._use_faiss:
+            raise NotImplementedError(f"MoLNaiveTopK.{what}: the IVF index (use_faiss=True) is trained on the corpus -- its lists and centroids do not follow "
+                                      "an in-place change; construct the module again")
 
     def ivf_index(self) -> E.IvfIndex:
         """The IVF index of use_faiss=True, built at first use and rebuilt when _bind() yields a new engine (as _component_table)."""
