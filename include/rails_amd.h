@@ -236,6 +236,8 @@ size_t rails_mol_generic_query_pack_floats(const rails_mol_shape* shape, int32_t
 int rails_mol_generic_pack_gate_weights(const rails_mol_shape* shape, const rails_mol_weights* w, float* gate_pack, void* stream);
 int rails_mol_generic_index_build(const rails_mol_shape* shape, const rails_mol_weights* w, const float* items, int64_t n_items, float* index,
                                   void* stream);
+/* rails_mol_index_clear_tail for the generic route's row-major index (rows n_items .. end of the last tile) */
+int rails_mol_generic_index_clear_tail(const rails_mol_shape* shape, float* index, int64_t n_items, void* stream);
 /* rails_mol_index_update for the generic route's row-major index */
 int rails_mol_generic_index_update(const rails_mol_shape* shape, const rails_mol_weights* w, const float* items, int64_t n_new, const int64_t* positions,
                                    float* index, int64_t n_items, void* stream);
@@ -261,6 +263,10 @@ int rails_mol_score_indexed_supported(const rails_mol_shape* shape, int32_t batc
  * use rails_mol_score_indexed). */
 size_t rails_mol_index_rows_floats(const rails_mol_shape* shape, int64_t n_items);
 int rails_mol_index_rows_build(const rails_mol_shape* shape, const float* index, int64_t n_items, float* index_rows, void* stream);
+/* An index that was CUT to n_items items (its first rails_mol_index_floats(shape, n_items) floats kept): the slots n_items .. end of the last tile
+ * are set to zero, what rails_mol_index_build leaves there -- the cut index is then the bytes of a fresh build of its first n_items items.  Either
+ * index format (fp32, split-f16); touches one tile; nothing to do when n_items is a multiple of 32.  The row-major copy has no padding. */
+int rails_mol_index_clear_tail(const rails_mol_shape* shape, float* index, int64_t n_items, void* stream);
 /* The rows of n_new positions copied again from the (already updated) index; nothing else is read or written. */
 int rails_mol_index_rows_update(const rails_mol_shape* shape, const float* index, int64_t n_items, const int64_t* positions, int64_t n_new,
                                 float* index_rows, void* stream);
@@ -278,6 +284,14 @@ int rails_mol_score_indexed(const rails_mol_shape* shape, const float* gate_pack
  * (rails/similarities/dot_product_similarity_fn.py:48-54).  fp32. */
 size_t rails_mips_index_floats(int32_t dim, int64_t n_items);          /* tile-packed copy of the (n, dim) table */
 int rails_mips_index_build(const float* items, int64_t n_items, int32_t dim, float* index, void* stream);
+/* In-place changes of a built index (additions under ABI 15).  rails_mips_index_update: rails_mips_index_build's stores with scatter addressing --
+ * item j of `items` (n_new, dim) goes to slot positions[j] (int64, device memory, unique) of an index of n_items items; a position outside
+ * [0, n_items) is skipped.  No arithmetic: the slot holds the bytes a fresh build of the changed table holds.  rails_mips_index_gather_rows: the
+ * inverse read, rows (n_rows, dim) = the items at `positions` as the index holds them (a position outside the index reads zeros).
+ * rails_mips_index_clear_tail: as rails_mol_index_clear_tail, for an index cut to n_items items. */
+int rails_mips_index_update(const float* items, int64_t n_new, int32_t dim, const int64_t* positions, float* index, int64_t n_items, void* stream);
+int rails_mips_index_gather_rows(const float* index, int64_t n_items, int32_t dim, const int64_t* positions, int64_t n_rows, float* rows, void* stream);
+int rails_mips_index_clear_tail(float* index, int64_t n_items, int32_t dim, void* stream);
 size_t rails_mips_query_ws_floats(int32_t dim, int32_t batch);         /* scratch for the packed queries */
 int rails_mips_score(const float* queries, int32_t batch, int32_t dim, const float* index, int64_t n_items,
                      float* query_ws, float* logits, int64_t ld, void* stream);

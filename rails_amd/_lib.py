@@ -149,6 +149,8 @@ PROTOTYPES = {
     "rails_mol_index_update": (C.c_int, [_SHAPE_P, _WEIGHTS_P, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rails_mol_generic_index_update": (C.c_int, [_SHAPE_P, _WEIGHTS_P, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rails_mol_index_rows_update": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_mol_index_clear_tail": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rails_mol_generic_index_clear_tail": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int64, C.c_void_p]),
     "rails_mol_coarse_update": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "rails_mol_component_update": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "rails_mol_index_rows_floats": (C.c_size_t, [_SHAPE_P, C.c_int64]),
@@ -192,6 +194,9 @@ PROTOTYPES = {
     ),
     "rails_mips_index_floats": (C.c_size_t, [C.c_int32, C.c_int64]),
     "rails_mips_index_build": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rails_mips_index_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rails_mips_index_gather_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_mips_index_clear_tail": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "rails_mips_query_ws_floats": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rails_mips_score": (
         C.c_int,

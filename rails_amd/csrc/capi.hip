@@ -219,6 +219,15 @@ int rails_mol_index_rows_update(const rails_mol_shape* s, const float* index, in
   return fail(index_rows_update(*s, index, n_items, positions, n_new, rows, (hipStream_t)stream), "index_rows_update");
 }
 
+int rails_mol_index_clear_tail(const rails_mol_shape* s, float* index, int64_t n_items, void* stream) {
+  g_err[0] = '\0';
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  if (n_items < 0) { set_error("index_clear_tail: n_items < 0"); return RAILS_EINVAL; }
+  if (n_items % 32 == 0) return RAILS_OK;
+  if (!index) { set_error("index_clear_tail: NULL pointer"); return RAILS_EINVAL; }
+  return fail(tile_clear_tail(index, n_items, tile_floats(*s), (hipStream_t)stream), "index_clear_tail");
+}
+
 int rails_mol_index_unpack(const rails_mol_shape* s, const float* index, int64_t n_items, float* ex_out, float* gi_out,
                            void* stream) {
   g_err[0] = '\0';
@@ -480,6 +489,15 @@ int rails_mol_generic_index_build(const rails_mol_shape* s, const rails_mol_weig
   return r == kOk ? r : fail(r, "generic_index_build");
 }
 
+int rails_mol_generic_index_clear_tail(const rails_mol_shape* s, float* index, int64_t n_items, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (n_items < 0) { set_error("generic_index_clear_tail: n_items < 0"); return RAILS_EINVAL; }
+  if (n_items % 32 == 0) return RAILS_OK;
+  if (!index) { set_error("generic_index_clear_tail: NULL pointer"); return RAILS_EINVAL; }
+  return fail(rows_clear_tail(index, n_items, gen_item_floats(*s), (hipStream_t)stream), "generic_index_clear_tail");
+}
+
 int rails_mol_generic_index_update(const rails_mol_shape* s, const rails_mol_weights* w, const float* items, int64_t n_new, const int64_t* positions,
                                    float* index, int64_t n_items, void* stream) {
   g_err[0] = '\0';
@@ -557,6 +575,30 @@ int rails_mips_index_build(const float* items, int64_t n_items, int32_t dim, flo
   if (n_items == 0) return RAILS_OK;
   if (!items || !index) { set_error("mips_index_build: NULL pointer"); return RAILS_EINVAL; }
   return fail(mips_pack_items(items, n_items, dim, index, (hipStream_t)stream), "mips_index_build");
+}
+
+int rails_mips_index_update(const float* items, int64_t n_new, int32_t dim, const int64_t* positions, float* index, int64_t n_items, void* stream) {
+  g_err[0] = '\0';
+  if (dim <= 0 || n_new < 0 || n_items < 0) { set_error("mips_index_update: bad size"); return RAILS_EINVAL; }
+  if (n_new == 0) return RAILS_OK;
+  if (!items || !positions || !index) { set_error("mips_index_update: NULL pointer"); return RAILS_EINVAL; }
+  return fail(mips_update_items(items, n_new, dim, positions, index, n_items, (hipStream_t)stream), "mips_index_update");
+}
+
+int rails_mips_index_gather_rows(const float* index, int64_t n_items, int32_t dim, const int64_t* positions, int64_t n_rows, float* rows, void* stream) {
+  g_err[0] = '\0';
+  if (dim <= 0 || n_rows < 0 || n_items < 0) { set_error("mips_index_gather_rows: bad size"); return RAILS_EINVAL; }
+  if (n_rows == 0) return RAILS_OK;
+  if (!index || !positions || !rows) { set_error("mips_index_gather_rows: NULL pointer"); return RAILS_EINVAL; }
+  return fail(mips_gather_rows(index, n_items, dim, positions, n_rows, rows, (hipStream_t)stream), "mips_index_gather_rows");
+}
+
+int rails_mips_index_clear_tail(float* index, int64_t n_items, int32_t dim, void* stream) {
+  g_err[0] = '\0';
+  if (dim <= 0 || n_items < 0) { set_error("mips_index_clear_tail: bad size"); return RAILS_EINVAL; }
+  if (n_items % 32 == 0) return RAILS_OK;
+  if (!index) { set_error("mips_index_clear_tail: NULL pointer"); return RAILS_EINVAL; }
+  return fail(tile_clear_tail(index, n_items, 32 * (int64_t)((dim + 7) / 8 * 8), (hipStream_t)stream), "mips_index_clear_tail");
 }
 
 size_t rails_mips_query_ws_floats(int32_t dim, int32_t batch) {

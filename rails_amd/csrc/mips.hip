@@ -17,7 +17,11 @@ namespace mol {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // items (n, D) row-major -> tiles of 32 items, [sc in Dp/8][lane][4]: lane (x, hi) holds X[x][hi*Dp/2 + 4sc + j]
-__global__ void mips_pack_items_kernel(const float* __restrict__ items, int64_t n, int D, int Dp, float* __restrict__ out) {
+// SCATTER (mips_update_items_kernel): one workgroup per 32 INPUT items, item j stored at slot pos[j] of an existing index of n_index items
+// (a position outside it: nothing is stored).  The same loads and the same values as the build; only the address of the store differs.
+template <bool SCATTER>
+__device__ __forceinline__ void mips_pack_body(const float* __restrict__ items, int64_t n, int D, int Dp, float* __restrict__ out,
+                                               const int64_t* __restrict__ pos, int64_t n_index) {
   const int64_t tile = blockIdx.x;
   const int per_tile = kTileItems * Dp;
   for (int i = threadIdx.x; i < per_tile; i += blockDim.x) {
@@ -25,8 +29,52 @@ __global__ void mips_pack_items_kernel(const float* __restrict__ items, int64_t 
     const int x = lane & 31, hi = lane >> 5;
     const int k = hi * (Dp / 2) + 4 * sc + j;
     const int64_t item = tile * kTileItems + x;
-    out[tile * per_tile + i] = (item < n && k < D) ? items[item * D + k] : 0.0f;
+    const float v = (item < n && k < D) ? items[item * D + k] : 0.0f;
+    if constexpr (SCATTER) {
+      if (item >= n) continue;
+      const int64_t p = pos[item];
+      if (p >= 0 && p < n_index) out[(p >> 5) * per_tile + (sc * 64 + hi * 32 + (int)(p & 31)) * 4 + j] = v;
+    } else {
+      out[tile * per_tile + i] = v;
+    }
   }
+}
+
+__global__ void mips_pack_items_kernel(const float* __restrict__ items, int64_t n, int D, int Dp, float* __restrict__ out) {
+  mips_pack_body<false>(items, n, D, Dp, out, nullptr, 0);
+}
+
+__global__ void mips_update_items_kernel(const float* __restrict__ items, int64_t n, int D, int Dp, float* __restrict__ out,
+                                         const int64_t* __restrict__ pos, int64_t n_index) {
+  mips_pack_body<true>(items, n, D, Dp, out, pos, n_index);
+}
+
+// the inverse read, for m positions: rows[u][k] = X[pos[u]][k] as the index holds it (fp32 copies: exact); a position outside the index reads 0
+__global__ void mips_gather_rows_kernel(const float* __restrict__ index, int64_t n_index, const int64_t* __restrict__ pos, int64_t m, int D, int Dp,
+                                        float* __restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m * D) return;
+  const int64_t u = i / D;
+  const int k = (int)(i - u * D);
+  const int64_t p = pos[u];
+  const int hi = k >= Dp / 2 ? 1 : 0, r = k - hi * (Dp / 2);
+  const int sc = r >> 2, j = r & 3;
+  rows[i] = (p >= 0 && p < n_index) ? index[(p >> 5) * (int64_t)(kTileItems * Dp) + (sc * 64 + hi * 32 + (int)(p & 31)) * 4 + j] : 0.0f;
+}
+
+int mips_update_items(const float* items, int64_t n, int D, const int64_t* positions, float* out, int64_t n_index, hipStream_t stream) {
+  const int Dp = (D + 7) / 8 * 8;
+  const int64_t tiles = num_tiles(n);
+  if (tiles == 0) return kOk;
+  hipLaunchKernelGGL(mips_update_items_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, items, n, D, Dp, out, positions, n_index);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int mips_gather_rows(const float* index, int64_t n_index, int D, const int64_t* positions, int64_t m, float* rows, hipStream_t stream) {
+  const int Dp = (D + 7) / 8 * 8;
+  if (m <= 0) return kOk;
+  hipLaunchKernelGGL(mips_gather_rows_kernel, dim3((unsigned)((m * D + 255) / 256)), dim3(256), 0, stream, index, n_index, positions, m, D, Dp, rows);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
 // queries (B, D) -> groups of 32 rows, [g][sc][lane][4]: lane (row, hi) holds q[g*32 + row][hi*Dp/2 + 4sc + j]

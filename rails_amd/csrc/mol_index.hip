@@ -578,6 +578,36 @@ int index_rows_update(const Shape& s, const float* ipack, int64_t n, const int64
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
+// ---- the padding of the last tile, restored after an index was cut to fewer items (MoLTopKModule.remove_items, MipsIndex.shrink) ----------
+// Slots first .. 31 of ONE tile of a tile-packed format -> zero, what a fresh build leaves in the padding of its last tile.  The MoL index
+// formats (fp32 fragments, split-f16) and the MIPS index are all [chunk][64 lanes] x 16 bytes with the item slot in lane & 31.
+__global__ void tile_clear_tail_kernel(float4* __restrict__ tile, int tile_f4, int first) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < tile_f4 && (i & 31) >= first) tile[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// row-major formats (the generic route's index): floats [lo, hi) -> zero
+__global__ void floats_clear_kernel(float* __restrict__ p, int64_t lo, int64_t hi) {
+  const int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < hi) p[i] = 0.0f;
+}
+
+int tile_clear_tail(float* index, int64_t n, int64_t tile_fl, hipStream_t stream) {
+  const int first = (int)(n % kTileItems);
+  if (n <= 0 || first == 0) return kOk;       // the last tile is full: no padding
+  const int tile_f4 = (int)(tile_fl / 4);
+  hipLaunchKernelGGL(tile_clear_tail_kernel, dim3((unsigned)((tile_f4 + 255) / 256)), dim3(256), 0, stream,
+                     reinterpret_cast<float4*>(index + (num_tiles(n) - 1) * tile_fl), tile_f4, first);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int rows_clear_tail(float* index, int64_t n, int64_t ld, hipStream_t stream) {
+  const int64_t lo = n * ld, hi = num_tiles(n) * kTileItems * ld;
+  if (n <= 0 || hi <= lo) return kOk;
+  hipLaunchKernelGGL(floats_clear_kernel, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, stream, index, lo, hi);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
 // ---- gather: rows x n_cand candidate positions -> a tile-packed index of their own -----------------
 __global__ void index_gather_kernel(const float4* __restrict__ ipack, int64_t n, const int64_t* __restrict__ idx,
                                     int64_t tiles_per_row, int64_t n_cand, int tile_f4, float4* __restrict__ out) {

@@ -104,6 +104,10 @@ int index_rows_build(const Shape& s, const float* ipack, int64_t n, float* rows,
 // in-place updates (rails_mol_*_update): items / rows of `positions` only
 int index_update(const Shape& s, const Weights& w, const float* items, int64_t n, const int64_t* positions, float* ipack, int64_t n_index, hipStream_t stream);
 int index_rows_update(const Shape& s, const float* ipack, int64_t n, const int64_t* positions, int64_t m, float* rows, hipStream_t stream);
+// the padding slots (n .. end of the last tile) of an index that was cut to n items -> zero, as a fresh build leaves them: tile-packed formats
+// (tile_fl floats per tile, the item slot in lane & 31 of every 16-byte piece: MoL fp32 / split-f16, MIPS) and row-major ones (ld floats per row)
+int tile_clear_tail(float* index, int64_t n, int64_t tile_fl, hipStream_t stream);
+int rows_clear_tail(float* index, int64_t n, int64_t ld, hipStream_t stream);
 int coarse_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream);
 int component_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n_total, hipStream_t stream);
 // fp32 Ex fragments of a freshly built index -> f16 hi/lo fragments, in place (precision f16x3)
@@ -198,6 +202,9 @@ void ivf_plan(const int32_t* offsets, int G, int nlist, int nprobe, int k, int* 
 
 int hash_item_table(unsigned long long seed, int64_t first_item, int64_t n_items, int dim, float scale, float* out, hipStream_t stream);
 int mips_pack_items(const float* items, int64_t n, int D, float* out, hipStream_t stream);
+// items[j] -> slot positions[j] of an index of n_index items (mips_pack_items' stores, scatter addressing); rows of m positions read back
+int mips_update_items(const float* items, int64_t n, int D, const int64_t* positions, float* out, int64_t n_index, hipStream_t stream);
+int mips_gather_rows(const float* index, int64_t n_index, int D, const int64_t* positions, int64_t m, float* rows, hipStream_t stream);
 int mips_score(const float* q, int B, int D, const float* ifrag, int64_t n, float* qfrag_ws, float* logits, int64_t ld,
                int n_cu, hipStream_t stream);
 

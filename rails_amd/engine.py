@@ -397,6 +397,16 @@ class MolEngine:
         buf[: index.buf.numel()].copy_(index.buf)
         index.buf, index.n_items = buf, n
 
+    def shrink_index(self, index: MolIndex, n_items: int) -> None:
+        """`index` cut to its first n_items items, IN PLACE (the same object, as grow_index): a buffer of index_floats(n_items) with the whole tiles
+        copied and the slots past n_items of the new last tile zero (rails_mol_index_clear_tail) -- the bytes of a fresh build of those items."""
+        if not 0 < n_items <= index.n_items:
+            raise ValueError(f"shrink_index: {n_items} items outside (0, {index.n_items}]")
+        buf = index.buf[: self._fn("index_floats")(C.byref(self.shape), n_items)].clone()
+        with _on_device(buf.device):
+            _lib.check(self._fn("index_clear_tail")(C.byref(self.shape), _ptr(buf), n_items, _stream()), self._name("index_clear_tail"))
+        index.buf, index.n_items = buf, n_items
+
     def score_indexed_rows(self, qpack: torch.Tensor, batch: int, rows: torch.Tensor, n_items: int, positions: torch.Tensor,
                            counts: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """score_indexed with the candidates read from the row-major copy: whole cache lines per candidate, same bits.
@@ -900,6 +910,43 @@ class MipsIndex:
         self.buf = torch.empty(lib.rails_mips_index_floats(self.dim, self.n_items), dtype=torch.float32, device=items.device)
         with _on_device(items.device):
             _lib.check(lib.rails_mips_index_build(_ptr(items), self.n_items, self.dim, _ptr(self.buf), _stream()), "rails_mips_index_build")
+
+    # ---- in-place changes (MIPSBruteForceTopK.update_items / append_items / remove_items): the bytes of a fresh build of the changed table ----
+    def update(self, positions: torch.Tensor, items: torch.Tensor) -> None:
+        """items (M, D) -> slots positions (M,) int64 on the device, unique (rails_mips_index_update: the build's stores, scatter addressing)."""
+        _require_device(items, "item_embeddings")
+        if items.dim() != 2 or items.shape[1] != self.dim or positions.shape != (items.shape[0],) or positions.dtype != torch.int64:
+            raise ValueError(f"update takes (M, {self.dim}) items and (M,) int64 positions, got {tuple(items.shape)} and {tuple(positions.shape)}")
+        items, positions = _f32c(items), positions.to(self.buf.device).contiguous()
+        with _on_device(self.buf.device):
+            _lib.check(_lib.load().rails_mips_index_update(_ptr(items), items.shape[0], self.dim, _ptr(positions), _ptr(self.buf), self.n_items, _stream()),
+                       "rails_mips_index_update")
+
+    def rows(self, positions: torch.Tensor) -> torch.Tensor:
+        """(M, D) fp32: the items at `positions` as the index holds them (the module keeps no raw table; fp32 copies, so the round trip is exact)."""
+        positions = positions.to(self.buf.device).contiguous()
+        out = torch.empty((positions.numel(), self.dim), dtype=torch.float32, device=self.buf.device)
+        with _on_device(self.buf.device):
+            _lib.check(_lib.load().rails_mips_index_gather_rows(_ptr(self.buf), self.n_items, self.dim, _ptr(positions), positions.numel(), _ptr(out), _stream()),
+                       "rails_mips_index_gather_rows")
+        return out
+
+    def grow(self, m: int) -> None:
+        """Room for m more items: the old bytes copied, the rest zero (the padding of a fresh index); the new slots are filled by update()."""
+        n = self.n_items + m
+        buf = torch.zeros(_lib.load().rails_mips_index_floats(self.dim, n), dtype=torch.float32, device=self.buf.device)
+        buf[: self.buf.numel()].copy_(self.buf)
+        self.buf, self.n_items = buf, n
+
+    def shrink(self, n_new: int) -> None:
+        """Cut to the first n_new items: whole tiles copied, the slots past n_new of the new last tile zero (rails_mips_index_clear_tail)."""
+        if not 0 < n_new <= self.n_items:
+            raise ValueError(f"shrink: {n_new} items outside (0, {self.n_items}]")
+        lib = _lib.load()
+        buf = self.buf[: lib.rails_mips_index_floats(self.dim, n_new)].clone()
+        with _on_device(buf.device):
+            _lib.check(lib.rails_mips_index_clear_tail(_ptr(buf), n_new, self.dim, _stream()), "rails_mips_index_clear_tail")
+        self.buf, self.n_items = buf, n_new
 
     def score(self, q: torch.Tensor) -> torch.Tensor:
         """(B, D) -> (B, N) fp32 dot products (reference rails/indexing/mips_top_k.py:72)."""

@@ -279,6 +279,9 @@ class ShardedTopK(TopKModule):
     def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
         raise NotImplementedError(f"{type(self).__name__}.append_items: growing an item-sharded corpus would move the shard bounds; build the shards again")
 
+    def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError(f"{type(self).__name__}.remove_items: shrinking an item-sharded corpus would move the shard bounds; build the shards again")
+
     def exchange_info(self) -> dict:
         """What carried the exchange: backend of the process group and its size (bench.py reports it)."""
         if not dist.is_initialized():

@@ -44,6 +44,48 @@ class TopKModule(torch.nn.Module):
         """-> (top_k_scores (B, k), top_k_ids (B, k))."""
 
 
+def _rows_arg(item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], dim: int, dtype: torch.dtype, device: torch.device, ids_dtype: torch.dtype):
+    """The rows (and ids) argument of update_items / append_items against a table of `dim` columns, `dtype`, on `device` -> ((M, dim) rows, (M,) ids
+    or None); ValueError for anything else."""
+    emb = item_embeddings
+    if not torch.is_tensor(emb):
+        raise ValueError("item_embeddings must be a tensor")
+    if emb.dim() == 3 and emb.shape[0] == 1:
+        emb = emb[0]
+    if emb.dim() != 2 or emb.shape[1] != dim:
+        raise ValueError(f"item_embeddings must be (M, {dim}) or (1, M, {dim}), got {tuple(item_embeddings.shape)}")
+    if device.type == "cuda":
+        E._require_device(emb, "item_embeddings")
+    if emb.device != device or emb.dtype != dtype:
+        raise ValueError(f"item_embeddings must be {dtype} on {device}, got {emb.dtype} on {emb.device}")
+    ids = None
+    if item_ids is not None:
+        if (not torch.is_tensor(item_ids) or item_ids.dtype != ids_dtype or item_ids.numel() != emb.shape[0]
+                or not (item_ids.dim() == 1 or (item_ids.dim() == 2 and item_ids.shape[0] == 1))):
+            raise ValueError(f"item_ids must be ({emb.shape[0]},) or (1, {emb.shape[0]}) {ids_dtype}")
+        ids = item_ids.reshape(-1)
+    return emb, ids
+
+
+def removal_plan(positions: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The one rule of remove_items: removing `positions` ((M,) int64 on the CPU, unique, inside [0, n)) from a table of n
+    rows leaves N' = n - M rows -- rows 0 .. N' - 1 with the HOLES (the removed positions below N', ascending) filled from the MOVERS (the surviving
+    positions at or above N', ascending), the i-th mover's row and id at the i-th hole; nothing else moves.  -> (holes, movers), CPU int64, of one
+    length.  Pure host arithmetic in O(M log M): the tail N' .. n - 1 has M positions.  ValueError for a wrong dtype or shape, a position out of
+    range, a duplicate, or N' < 1."""
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 1 or positions.is_cuda:
+        raise ValueError("positions must be a 1-d int64 tensor on the CPU")
+    m = positions.numel()
+    MoLTopKModule._checked_positions(positions, m, n)
+    n_new = n - m
+    if n_new < 1:
+        raise ValueError(f"removing {m} of {n} items would leave none")
+    order = torch.sort(positions).values
+    tail_kept = torch.ones(m, dtype=torch.bool)
+    tail_kept[order[order >= n_new] - n_new] = False
+    return order[order < n_new], n_new + torch.nonzero(tail_kept).reshape(-1)
+
+
 class MoLTopKModule(TopKModule):
     """Common state of the MoL top-k modules (reference mol_top_k.py:29-81): borrows `item_embeddings`
     (1, N, D) and `item_ids` (1, N); owns the packed index."""
@@ -107,12 +149,12 @@ class MoLTopKModule(TopKModule):
             self._call_eng = outer
 
     # ---- in-place corpus changes ---------------------------------------------------------------------------------
-    # After any sequence of update_items / append_items the module holds what a module freshly constructed from the resulting table, the
+    # After any sequence of update_items / append_items / remove_items the module holds what a module freshly constructed from the resulting table, the
     # resulting ids and the same mol_module holds -- every derived buffer bit for bit -- and answers alike.  Per-item index values depend on
     # the item's own row alone (one workgroup computes 32 items with one accumulator per item), so an update recomputes the changed items
     # and nothing else: O(M) bytes per held buffer.  Whole passes over the corpus: the int8 pre-filter (one scale for the whole table:
     # rebuilt from the updated coarse table) and the proved mode's max |gi| (metadata of the bound); append_items also copies what it grows.
-    # Both calls are issued on the current stream, behind everything already enqueued there; the module's own side streams (submit()'s, the
+    # All three calls are issued on the current stream, behind everything already enqueued there; the module's own side streams (submit()'s, the
     # audit's) are JOINED first: handles outstanding from submit() keep the results of the corpus they were submitted against.
     def update_items(self, positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
         """Replace the items at `positions` ((M,) int64, CPU or device: POSITIONS 0 .. N-1 of this module's corpus, not ids; unique) by the rows of
@@ -163,29 +205,53 @@ class MoLTopKModule(TopKModule):
             self._refresh(eng, torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
             self._after_append(eng)
 
+    def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
+        """Shrink the corpus from N to N' = N - M items: the items at `positions` ((M,) int64, CPU or device: POSITIONS, not ids; unique) go, and the
+        holes they leave below N' are filled from the tail (removal_plan: O(M) rows move, every other item keeps its position).  -> `moved`, a CPU
+        int64 tensor of rows [from, to], for callers that keep positions.  A mover's bytes at its new position are what update_items writes there;
+        every held buffer is then cut to what a fresh module of N' items holds, and everything a fresh module decides from N is decided again for
+        N' (the default exact mode turns dense below 16 384 items: the module then holds a fresh dense module's buffers and nothing more).  From
+        this call on the module OWNS its item table and ids; the caller's tensors are not written.  ValueError before anything is touched (one
+        device sync when the positions live on the device).  M = 0 is a no-op."""
+        self._check_updatable("remove_items")
+        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 1:
+            raise ValueError("positions must be (M,) int64")
+        n = self.num_items
+        holes, movers = removal_plan(positions.cpu(), n)      # (the one sync of a device tensor)
+        moved = torch.stack([movers, holes], dim=1)
+        m = positions.numel()
+        if m == 0:
+            return moved
+        with torch.inference_mode():
+            self._join_side_streams()
+            eng = self._bind()
+            n_new, dev = n - m, self._item_embeddings.device
+            h, mv = holes.to(dev), movers.to(dev)
+            emb = self._item_embeddings[0].index_select(0, mv)
+            table = self._item_embeddings[:, :n_new].clone()
+            table[0].index_copy_(0, h, emb)
+            own = self._item_ids.reshape(1, -1)
+            ids = own[:, :n_new].clone()
+            ids[0].index_copy_(0, h.to(own.device), own[0].index_select(0, mv.to(own.device)))
+            flat = self._ids_flat[:n_new].clone()
+            flat.index_copy_(0, h, self._ids_flat.index_select(0, mv))
+            self._item_embeddings, self._item_ids, self._ids_flat = table, ids, flat
+            self._forget_corpus_choices()
+            if self._engine_for_bind() is eng:
+                self._shrink(eng, n_new)
+                if holes.numel():
+                    self._refresh(eng, h, emb)
+            else:       # another engine for N' items: its buffers are built from the table, as at construction
+                self._drop_derived()
+            self._after_remove(eng)
+        return moved
+
     def _check_updatable(self, what: str) -> None:
         """Modules whose state cannot follow an in-place change refuse here, before anything is touched."""
 
     def _update_rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor]):
         table = self._item_embeddings
-        emb = item_embeddings
-        if not torch.is_tensor(emb):
-            raise ValueError("item_embeddings must be a tensor")
-        if emb.dim() == 3 and emb.shape[0] == 1:
-            emb = emb[0]
-        if emb.dim() != 2 or emb.shape[1] != table.shape[2]:
-            raise ValueError(f"item_embeddings must be (M, {table.shape[2]}) or (1, M, {table.shape[2]}), got {tuple(item_embeddings.shape)}")
-        if table.is_cuda:
-            E._require_device(emb, "item_embeddings")
-        if emb.device != table.device or emb.dtype != table.dtype:
-            raise ValueError(f"item_embeddings must be {table.dtype} on {table.device}, got {emb.dtype} on {emb.device}")
-        ids = None
-        if item_ids is not None:
-            if (not torch.is_tensor(item_ids) or item_ids.dtype != self._item_ids.dtype or item_ids.numel() != emb.shape[0]
-                    or not (item_ids.dim() == 1 or (item_ids.dim() == 2 and item_ids.shape[0] == 1))):
-                raise ValueError(f"item_ids must be ({emb.shape[0]},) or (1, {emb.shape[0]}) {self._item_ids.dtype}")
-            ids = item_ids.reshape(-1)
-        return emb, ids
+        return _rows_arg(item_embeddings, item_ids, table.shape[2], table.dtype, table.device, self._item_ids.dtype)
 
     @staticmethod
     def _checked_positions(positions: torch.Tensor, m: int, n: int) -> torch.Tensor:
@@ -234,10 +300,33 @@ class MoLTopKModule(TopKModule):
             self._rows_cache = None      # not held (or refused for its size): decided again at the next rerank, as for a fresh module
         self._scratch.clear()            # recycled buffers sized by N
 
+    def _shrink(self, eng, n_new: int) -> None:
+        """Every held buffer cut to n_new items, with a fresh build's padding (the holes below n_new are written by _refresh behind this)."""
+        c = self._rows_cache
+        held = c is not None and c[0] is eng and c[1] is self._index
+        eng.shrink_index(self._index, n_new)
+        if held and c[2] is not None:       # (the row-major copy has no padding: n_new whole rows)
+            self._rows_cache = (eng, self._index, c[2][: eng.lib.rails_mol_index_rows_floats(E.C.byref(eng.shape), n_new)].clone())
+        else:
+            self._rows_cache = None      # as in _grow: decided again at the next rerank
+        self._scratch.clear()            # recycled buffers sized by N
+
+    def _forget_corpus_choices(self) -> None:
+        """What the module decided from the corpus size, to be decided again (subclasses that decide something)."""
+
+    def _drop_derived(self) -> None:
+        """The engine changes with the corpus size: nothing derived under the old one stays (_bind builds the new engine's index from the table)."""
+        self._rows_cache = None
+        self._scratch.clear()
+
     def _after_update(self, eng) -> None:
         self._upd_source = None
 
     def _after_append(self, eng) -> None:
+        self._upd_source = None
+        self._bind()
+
+    def _after_remove(self, eng) -> None:
         self._upd_source = None
         self._bind()
 
@@ -951,6 +1040,24 @@ class MoLBruteForceTopK(MoLTopKModule):
         self._probe_pool = None
         super()._after_append(eng)
 
+    def _shrink(self, eng, n_new: int) -> None:
+        super()._shrink(eng, n_new)
+        ex = eng.exact
+        if ex is not None and self._index32 is not None and self._index32_engine is ex:
+            ex.shrink_index(self._index32, n_new)
+            if self._rows32 is not None:
+                self._rows32 = self._rows32[: ex.lib.rails_mol_index_rows_floats(E.C.byref(ex.shape), n_new)].clone()
+
+    def _forget_corpus_choices(self) -> None:
+        """Proved or dense, the form of the bound, the margins, max |gi|, the probes: all decided or drawn again for N' items (_bind)."""
+        self._policy = BoundPolicy()
+        self._gate_guard_limit = None
+        self._probe_pool = self._risk_pool = self._risk_rows = None
+
+    def _drop_derived(self) -> None:
+        super()._drop_derived()
+        self._index32 = self._rows32 = self._index32_engine = None      # (a fresh dense module holds neither; a proved one builds both in _bind)
+
     ROWS_COPY_MAX_BYTES = 8 << 30      # the row-major copy of the fp32 index is kept for indexes up to this size (0: never)
     _rows32 = None
 
@@ -1378,6 +1485,23 @@ class MoLAvgTopK(MoLTopKModule):
             table[: old.shape[0]].copy_(old)
             self._coarse_table = table
 
+    def _shrink(self, eng, n_new: int) -> None:
+        super()._shrink(eng, n_new)
+        self._redo_fit_memo.clear()
+        if self._coarse_engine is eng and self._coarse_table is not None:
+            self._coarse_table = self._coarse_table[:n_new].clone()
+            self._coarse_prefilter = None      # one scale for the whole table: rebuilt from the shrunk table in _after_remove
+
+    def _after_remove(self, eng) -> None:
+        super()._after_remove(eng)
+        if self._coarse_engine is eng and self._coarse_table is not None:
+            # the int8 copy as a fresh module of N' items has it: rebuilt whole while N' is still at the threshold (by _refresh where holes were
+            # filled, else here), dropped below it; statistics and their check schedule start again
+            if self._coarse_prefilter is None and self._coarse_table.shape[0] >= self.PREFILTER_MIN_ITEMS:
+                self._coarse_prefilter = eng.build_coarse_prefilter(self._coarse_table)
+            self._prefilter_calls = 0
+            self._prefilter_pending = None
+
     PREFILTER_MAX_FIRED = 0.35        # fraction of (tile, query tile) blocks passing the integer bound beyond which the copy is dropped
     PREFILTER_CHECK_CALLS = (2, 64)   # the header's statistics are read (16 bytes, one sync) after this many calls, then every so many
 
@@ -1680,6 +1804,11 @@ class _ComponentCandidates:
             table[:, : old.shape[1]].copy_(old)
             self._comp_table = table
 
+    def _shrink(self, eng, n_new: int) -> None:
+        super()._shrink(eng, n_new)
+        if self._comp_engine is eng and self._comp_table is not None:
+            self._comp_table = self._comp_table[:, :n_new].clone(memory_format=torch.contiguous_format)      # re-laid to group stride n_new
+
     def _component_topk(self, eq: torch.Tensor, k_per_group: int, pending: Optional[list] = None, with_scores: bool = False):
         """-> (B, P_Q * P_X * k_per_group) positions: top k_per_group items of every (query group, item group) pair.
         `pending`: deferred validity check of the fused scan, as in MoLAvgTopK._coarse_topk_from_eq.
@@ -1908,6 +2037,7 @@ class MIPSBruteForceTopK(MIPSTopKModule):
         if item_embeddings.dim() != 3 or item_embeddings.shape[0] != 1:
             raise ValueError(f"item_embeddings must be (1, N, D), got {tuple(item_embeddings.shape)}")
         del self._item_embeddings
+        self._table_dtype = item_embeddings.dtype      # (what update_items / append_items take; the index holds fp32 copies)
         self._index = E.MipsIndex(item_embeddings[0])
         self._ids_flat = item_ids.reshape(-1).to(device=item_embeddings.device, dtype=torch.int64).contiguous()
 
@@ -1915,6 +2045,72 @@ class MIPSBruteForceTopK(MIPSTopKModule):
         logits = self._index.score(query_embeddings)
         scores, ids = E.topk(logits, k, ids=self._ids_flat, sorted=sorted)
         return scores.to(query_embeddings.dtype), ids
+
+    # ---- in-place corpus changes: the MoL modules' three calls, same signatures, validation and tail-fill rule ------
+    # The module keeps the tile-packed copy and the ids only: after any sequence of the calls _index.buf and _ids_flat are what a fresh module
+    # built from the resulting table and ids holds (rails_mips_index_update stores the build's bytes at the positions; no arithmetic).  Rows
+    # are fp32 in the index whatever the table's dtype was, so a mover's row read back from it is what a fresh build would convert again.
+    @property
+    def num_items(self) -> int:
+        return self._index.n_items
+
+    def _rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor]):
+        return _rows_arg(item_embeddings, item_ids, self._index.dim, self._table_dtype, self._index.buf.device, self._item_ids.dtype)
+
+    def update_items(self, positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
+        """MoLTopKModule.update_items.  The raw table is not kept, so only the borrowed id tensor is written in place."""
+        emb, ids = self._rows_arg(item_embeddings, item_ids)
+        pos = MoLTopKModule._checked_positions(positions, emb.shape[0], self.num_items)
+        if emb.shape[0] == 0:
+            return
+        with torch.inference_mode():
+            pos = pos.to(self._index.buf.device)
+            self._index.update(pos, emb)
+            if ids is not None:
+                own = self._item_ids[0] if self._item_ids.dim() == 2 else self._item_ids
+                own.index_copy_(0, pos.to(own.device), ids.to(device=own.device, dtype=own.dtype))
+                if self._ids_flat.data_ptr() != own.data_ptr():
+                    self._ids_flat.index_copy_(0, pos, ids.to(device=pos.device, dtype=torch.int64))
+
+    def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
+        """MoLTopKModule.append_items: the new items at positions N .. N + M - 1; from this call on the module owns its ids."""
+        if item_ids is None:
+            raise ValueError("append_items needs the ids of the new items")
+        emb, ids = self._rows_arg(item_embeddings, item_ids)
+        m = emb.shape[0]
+        if m == 0:
+            return
+        with torch.inference_mode():
+            n, dev = self.num_items, self._index.buf.device
+            self._item_ids = torch.cat([self._item_ids.reshape(1, -1), ids.reshape(1, -1).to(device=self._item_ids.device, dtype=self._item_ids.dtype)], dim=1)
+            self._ids_flat = torch.cat([self._ids_flat, ids.to(device=dev, dtype=torch.int64)])
+            self._index.grow(m)
+            self._index.update(torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
+
+    def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
+        """MoLTopKModule.remove_items (removal_plan's rule) -> `moved`, CPU int64 rows [from, to].  The movers' rows are read back from the index."""
+        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 1:
+            raise ValueError("positions must be (M,) int64")
+        n = self.num_items
+        holes, movers = removal_plan(positions.cpu(), n)
+        moved = torch.stack([movers, holes], dim=1)
+        m = positions.numel()
+        if m == 0:
+            return moved
+        with torch.inference_mode():
+            n_new, dev = n - m, self._index.buf.device
+            h, mv = holes.to(dev), movers.to(dev)
+            rows = self._index.rows(mv)
+            own = self._item_ids.reshape(1, -1)
+            ids = own[:, :n_new].clone()
+            ids[0].index_copy_(0, h.to(own.device), own[0].index_select(0, mv.to(own.device)))
+            flat = self._ids_flat[:n_new].clone()
+            flat.index_copy_(0, h, self._ids_flat.index_select(0, mv))
+            self._item_ids, self._ids_flat = ids, flat
+            self._index.shrink(n_new)
+            if holes.numel():
+                self._index.update(h, rows)
+        return moved
 
 
 class CandidateIndex(object):
