@@ -43,7 +43,7 @@ __device__ __forceinline__ unsigned short f2h(float f) { return __builtin_bit_ca
 __device__ __forceinline__ float4 index_quad(const float* ipack, int64_t item, int PQ, int PX, int d, int m, int q) {
   const int hi = q >= d / 8, c = q - hi * (d / 8);
   const float* tEx = ipack + (item >> 5) * (int64_t)(kTileItems * (PX * d + PQ * PX));
-  return *reinterpret_cast<const float4*>(tEx + ((m * (d / 8) + c) * 64 + hi * 32 + (int)(item & 31)) * 4);
+  return *reinterpret_cast<const float4*>(tEx + ex_slot(d, (int)(item & 31), m, c, hi) * 4);
 }
 
 // dims 4q .. 4q+3 of the fp16-rounded component, as fp16 bits

@@ -26,41 +26,38 @@ __device__ __forceinline__ float bf16_rn(float x) {
 __device__ __forceinline__ unsigned short bf16_bits(float x) { return (unsigned short)(__float_as_uint(bf16_rn(x)) >> 16); }
 __device__ __forceinline__ float bf16_to_f32(unsigned short b) { return __uint_as_float(((unsigned int)b) << 16); }
 
-// one thread per (item, d): reads the tile-packed index, writes table[item][dd] row-major bf16
-__global__ void coarse_build_kernel(const float* __restrict__ ipack, int64_t n, int PQ, int PX, int d,
-                                    unsigned short* __restrict__ table) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * d) return;
-  const int64_t item = i / d;
-  const int dd = (int)(i - item * d);
-  const int64_t tile = item >> 5;
-  const int x = (int)(item & 31);
-  const float* tEx = ipack + tile * (int64_t)(kTileItems * (PX * d + PQ * PX));
-  // Ex slot (m, c8, lane)[j] holds Ex[x][m][hi*d/2 + 4*c8 + j], lane = hi*32 + x
-  const int hi = dd / (d / 2), s = dd - hi * (d / 2);
-  float acc = 0.0f;
-  for (int m = 0; m < PX; ++m) acc += bf16_rn(tEx[((m * (d / 8) + (s >> 2)) * 64 + hi * 32 + x) * 4 + (s & 3)]);
-  table[i] = bf16_bits(bf16_rn(acc) / (float)PX);
+// Work item u of a derived-table kernel: the build form reads item u of the fp32-format index `src` and writes row first + u; the update form
+// (AT_POSITIONS) writes row p = pos[u] of an existing table of n rows from item (src_in_place ? p : u) -- false, nothing to write, for p outside.
+template <bool AT_POSITIONS>
+__device__ __forceinline__ bool table_work_item(int64_t u, const int64_t* __restrict__ pos, int src_in_place, int64_t n, int64_t first, int64_t& item, int64_t& row) {
+  row = AT_POSITIONS ? pos[u] : first + u;
+  if (AT_POSITIONS && (row < 0 || row >= n)) return false;
+  item = AT_POSITIONS && src_in_place ? row : u;
+  return true;
 }
 
-// The rows of `m` positions of an existing table: update u reads item (src_in_place ? pos[u] : u) of the fp32-format index `src` and writes
-// table row pos[u] -- coarse_build_kernel's arithmetic, 2 d bytes per update.
-__global__ void coarse_update_kernel(const float* __restrict__ src, int src_in_place, const int64_t* __restrict__ pos, int64_t m, int64_t n, int PQ, int PX, int d,
-                                     unsigned short* __restrict__ table) {
+// one thread per (work item, dd): reads the tile-packed index, writes table[row][dd] row-major bf16
+template <bool AT_POSITIONS>
+__device__ __forceinline__ void coarse_table_body(const float* __restrict__ src, int src_in_place, const int64_t* __restrict__ pos, int64_t m, int64_t n, int PQ, int PX, int d,
+                                                  unsigned short* __restrict__ table) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m * d) return;
   const int64_t u = i / d;
   const int dd = (int)(i - u * d);
-  const int64_t p = pos[u];
-  if (p < 0 || p >= n) return;
-  const int64_t item = src_in_place ? p : u;
-  const int64_t tile = item >> 5;
+  int64_t item, row;
+  if (!table_work_item<AT_POSITIONS>(u, pos, src_in_place, n, 0, item, row)) return;
   const int x = (int)(item & 31);
-  const float* tEx = src + tile * (int64_t)(kTileItems * (PX * d + PQ * PX));
-  const int hi = dd / (d / 2), s = dd - hi * (d / 2);
+  const float* tEx = src + (item >> 5) * (int64_t)(kTileItems * (PX * d + PQ * PX));
   float acc = 0.0f;
-  for (int g = 0; g < PX; ++g) acc += bf16_rn(tEx[((g * (d / 8) + (s >> 2)) * 64 + hi * 32 + x) * 4 + (s & 3)]);
-  table[p * d + dd] = bf16_bits(bf16_rn(acc) / (float)PX);
+  for (int g = 0; g < PX; ++g) acc += bf16_rn(tEx[ex_offset(d, x, g, dd)]);
+  table[AT_POSITIONS ? row * d + dd : i] = bf16_bits(bf16_rn(acc) / (float)PX);      // (the build's i IS row * d + dd)
+}
+__global__ void coarse_build_kernel(const float* __restrict__ ipack, int64_t n, int PQ, int PX, int d, unsigned short* __restrict__ table) {
+  coarse_table_body<false>(ipack, 1, nullptr, n, n, PQ, PX, d, table);
+}
+__global__ void coarse_update_kernel(const float* __restrict__ src, int src_in_place, const int64_t* __restrict__ pos, int64_t m, int64_t n, int PQ, int PX, int d,
+                                     unsigned short* __restrict__ table) {
+  coarse_table_body<true>(src, src_in_place, pos, m, n, PQ, PX, d, table);
 }
 
 // ---- the coarse scan (bf16 MFMA) ------------------------------------------------------------------------------
@@ -580,20 +577,19 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
 }
 
 int coarse_build(const Shape& s, const float* ipack, int64_t n, void* table, hipStream_t stream) {
-  const int d = s.dot_product_dimension;
-  const int64_t total = n * d;
-  if (total == 0) return kOk;
-  hipLaunchKernelGGL(coarse_build_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, ipack, n,
-                     s.query_dot_product_groups, s.item_dot_product_groups, d, static_cast<unsigned short*>(table));
-  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+  if (n * s.dot_product_dimension == 0) return kOk;
+  return coarse_update(s, ipack, 1, nullptr, n, table, n, stream);
 }
 
+// positions == NULL: the build of an m-row table
 int coarse_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream) {
-  const int d = s.dot_product_dimension;
+  const int PQ = s.query_dot_product_groups, PX = s.item_dot_product_groups, d = s.dot_product_dimension;
   const int64_t total = m * d;
   if (total <= 0) return kOk;
-  hipLaunchKernelGGL(coarse_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, src_in_place, positions, m, n,
-                     s.query_dot_product_groups, s.item_dot_product_groups, d, static_cast<unsigned short*>(table));
+  const dim3 grid((unsigned)((total + 255) / 256));
+  unsigned short* t = static_cast<unsigned short*>(table);
+  if (positions) hipLaunchKernelGGL(coarse_update_kernel, grid, dim3(256), 0, stream, src, src_in_place, positions, m, n, PQ, PX, d, t);
+  else hipLaunchKernelGGL(coarse_build_kernel, grid, dim3(256), 0, stream, src, m, PQ, PX, d, t);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -1082,55 +1078,44 @@ int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* tab
 // tile) of every tile and took sixteen compares per block (0.40-0.57 ms per batch of 32 at amzn-books: 0.07 of the 356 MB table's HBM
 // time); the table is item-group-major so that a wave streams one group's rows back to back.
 // ---------------------------------------------------------------------------------------------
+// one thread per (work item, item group g, dd): row (table_work_item) of group g of a table of n_total items
+template <bool AT_POSITIONS>
+__device__ __forceinline__ void component_table_body(const float* __restrict__ src, int src_in_place, const int64_t* __restrict__ pos, int64_t m, int PQ, int PX, int d,
+                                                     int64_t n_total, int64_t first, unsigned short* __restrict__ table) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per_item = PX * d;
+  if (i >= m * per_item) return;
+  const int64_t u = i / per_item;
+  const int rem = (int)(i - u * per_item);
+  const int g = rem / d, dd = rem - g * d;
+  int64_t item, row;
+  if (!table_work_item<AT_POSITIONS>(u, pos, src_in_place, n_total, first, item, row)) return;
+  const int x = (int)(item & 31);
+  const float* tEx = src + (item >> 5) * (int64_t)(kTileItems * (PX * d + PQ * PX));
+  table[((int64_t)g * n_total + row) * d + dd] = bf16_bits(tEx[ex_offset(d, x, g, dd)]);
+}
 __global__ void component_build_kernel(const float* __restrict__ ipack, int64_t n, int PQ, int PX, int d, int64_t n_total, int64_t first,
                                        unsigned short* __restrict__ table) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int row = PX * d;
-  if (i >= n * row) return;
-  const int64_t item = i / row;
-  const int rem = (int)(i - item * row);
-  const int m = rem / d, dd = rem - m * d;
-  const int64_t tile = item >> 5;
-  const int x = (int)(item & 31);
-  const float* tEx = ipack + tile * (int64_t)(kTileItems * (PX * d + PQ * PX));
-  const int hi = dd / (d / 2), s = dd - hi * (d / 2);
-  table[((int64_t)m * n_total + first + item) * d + dd] = bf16_bits(tEx[((m * (d / 8) + (s >> 2)) * 64 + hi * 32 + x) * 4 + (s & 3)]);
+  component_table_body<false>(ipack, 1, nullptr, n, PQ, PX, d, n_total, first, table);
 }
-
-int component_build(const Shape& s, const float* ipack, int64_t n, void* table, int64_t n_total, int64_t first, hipStream_t stream) {
-  const int64_t total = n * s.item_dot_product_groups * s.dot_product_dimension;
-  if (total == 0) return kOk;
-  hipLaunchKernelGGL(component_build_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, ipack, n,
-                     s.query_dot_product_groups, s.item_dot_product_groups, s.dot_product_dimension, n_total, first,
-                     static_cast<unsigned short*>(table));
-  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
-}
-
-// The rows of `m` positions in every item group of an existing table of n_total items (component_build_kernel's values; source item as in
-// coarse_update_kernel): 2 P_X d bytes per update, one row per group.
 __global__ void component_update_kernel(const float* __restrict__ src, int src_in_place, const int64_t* __restrict__ pos, int64_t m, int PQ, int PX, int d,
                                         int64_t n_total, unsigned short* __restrict__ table) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int row = PX * d;
-  if (i >= m * row) return;
-  const int64_t u = i / row;
-  const int rem = (int)(i - u * row);
-  const int g = rem / d, dd = rem - g * d;
-  const int64_t p = pos[u];
-  if (p < 0 || p >= n_total) return;
-  const int64_t item = src_in_place ? p : u;
-  const int64_t tile = item >> 5;
-  const int x = (int)(item & 31);
-  const float* tEx = src + tile * (int64_t)(kTileItems * (PX * d + PQ * PX));
-  const int hi = dd / (d / 2), s = dd - hi * (d / 2);
-  table[((int64_t)g * n_total + p) * d + dd] = bf16_bits(tEx[((g * (d / 8) + (s >> 2)) * 64 + hi * 32 + x) * 4 + (s & 3)]);
+  component_table_body<true>(src, src_in_place, pos, m, PQ, PX, d, n_total, 0, table);
+}
+int component_build(const Shape& s, const float* ipack, int64_t n, void* table, int64_t n_total, int64_t first, hipStream_t stream) {
+  if (n * s.item_dot_product_groups * s.dot_product_dimension == 0) return kOk;
+  return component_update(s, ipack, 1, nullptr, n, table, n_total, stream, first);
 }
 
-int component_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n_total, hipStream_t stream) {
-  const int64_t total = m * s.item_dot_product_groups * s.dot_product_dimension;
+// positions == NULL: the build of rows first .. first + m - 1
+int component_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n_total, hipStream_t stream, int64_t first) {
+  const int PQ = s.query_dot_product_groups, PX = s.item_dot_product_groups, d = s.dot_product_dimension;
+  const int64_t total = m * PX * d;
   if (total <= 0) return kOk;
-  hipLaunchKernelGGL(component_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, src_in_place, positions, m,
-                     s.query_dot_product_groups, s.item_dot_product_groups, s.dot_product_dimension, n_total, static_cast<unsigned short*>(table));
+  const dim3 grid((unsigned)((total + 255) / 256));
+  unsigned short* t = static_cast<unsigned short*>(table);
+  if (positions) hipLaunchKernelGGL(component_update_kernel, grid, dim3(256), 0, stream, src, src_in_place, positions, m, PQ, PX, d, n_total, t);
+  else hipLaunchKernelGGL(component_build_kernel, grid, dim3(256), 0, stream, src, m, PQ, PX, d, n_total, first, t);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

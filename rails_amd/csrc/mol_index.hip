@@ -540,41 +540,38 @@ int index_unpack(const Shape& s, const float* ipack, int64_t n, float* ex, float
 // ---- row-major copy of an fp32 index: item i's fragment slot s, lane half h (one float4) at rows[i * RP + 2 s + h], RP = floats per item / 4.
 // A candidate's operands are then RP consecutive float4 (amzn-books: 1 280 B in ten 128-byte lines) instead of RP pieces of 16 B each in a line
 // of its own across the tile (8 x read amplification when candidates are re-scored in place: rails_mol_score_indexed_rows).
-__global__ void index_rows_kernel(const float4* __restrict__ ipack, int64_t n, int rp, int tile_f4, float4* __restrict__ rows) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * rp) return;
-  const int64_t item = i / rp;
-  const int j = (int)(i - item * rp), slot = j >> 1, h = j & 1;
-  rows[i] = ipack[(item >> 5) * tile_f4 + slot * 64 + h * 32 + (item & 31)];
-}
-
-int index_rows_build(const Shape& s, const float* ipack, int64_t n, float* rows, hipStream_t stream) {
-  if (n <= 0) return kOk;
-  const int tile_f4 = (int)(tile_floats(s) / 4), rp = tile_f4 / 32;
-  const int64_t total = n * rp;
-  hipLaunchKernelGGL(index_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const float4*>(ipack), n, rp, tile_f4,
-                     reinterpret_cast<float4*>(rows));
-  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
-}
-
-// the rows of `m` positions refreshed from the (already updated) index: m * rp float4, nothing else is touched
-__global__ void index_rows_update_kernel(const float4* __restrict__ ipack, int64_t n, const int64_t* __restrict__ pos, int64_t m, int rp, int tile_f4,
-                                         float4* __restrict__ rows) {
+// One thread per float4: work item u is item u (the build: all m = n rows), or (AT_POSITIONS) item pos[u] of the already updated index -- nothing for a
+// position outside [0, n), and nothing but the m rows is touched.
+template <bool AT_POSITIONS>
+__device__ __forceinline__ void index_rows_body(const float4* __restrict__ ipack, int64_t n, const int64_t* __restrict__ pos, int64_t m, int rp, int tile_f4,
+                                                float4* __restrict__ rows) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m * rp) return;
   const int64_t u = i / rp;
-  const int64_t item = pos[u];
-  if (item < 0 || item >= n) return;
+  const int64_t item = AT_POSITIONS ? pos[u] : u;
+  if (AT_POSITIONS && (item < 0 || item >= n)) return;
   const int j = (int)(i - u * rp), slot = j >> 1, h = j & 1;
-  rows[item * rp + j] = ipack[(item >> 5) * tile_f4 + slot * 64 + h * 32 + (item & 31)];
+  rows[AT_POSITIONS ? item * rp + j : i] = ipack[(item >> 5) * tile_f4 + slot * 64 + h * 32 + (item & 31)];      // (the build's i IS item * rp + j)
+}
+__global__ void index_rows_kernel(const float4* __restrict__ ipack, int64_t n, int rp, int tile_f4, float4* __restrict__ rows) {
+  index_rows_body<false>(ipack, n, nullptr, n, rp, tile_f4, rows);
+}
+__global__ void index_rows_update_kernel(const float4* __restrict__ ipack, int64_t n, const int64_t* __restrict__ pos, int64_t m, int rp, int tile_f4,
+                                         float4* __restrict__ rows) {
+  index_rows_body<true>(ipack, n, pos, m, rp, tile_f4, rows);
+}
+int index_rows_build(const Shape& s, const float* ipack, int64_t n, float* rows, hipStream_t stream) {
+  return index_rows_update(s, ipack, n, nullptr, n, rows, stream);
 }
 
+// positions == NULL: the build (m = n)
 int index_rows_update(const Shape& s, const float* ipack, int64_t n, const int64_t* positions, int64_t m, float* rows, hipStream_t stream) {
   if (m <= 0) return kOk;
   const int tile_f4 = (int)(tile_floats(s) / 4), rp = tile_f4 / 32;
-  const int64_t total = m * rp;
-  hipLaunchKernelGGL(index_rows_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const float4*>(ipack), n, positions, m,
-                     rp, tile_f4, reinterpret_cast<float4*>(rows));
+  const dim3 grid((unsigned)((m * rp + 255) / 256));
+  const float4* in = reinterpret_cast<const float4*>(ipack);
+  if (positions) hipLaunchKernelGGL(index_rows_update_kernel, grid, dim3(256), 0, stream, in, n, positions, m, rp, tile_f4, reinterpret_cast<float4*>(rows));
+  else hipLaunchKernelGGL(index_rows_kernel, grid, dim3(256), 0, stream, in, n, rp, tile_f4, reinterpret_cast<float4*>(rows));
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

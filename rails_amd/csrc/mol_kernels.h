@@ -109,7 +109,8 @@ int index_rows_update(const Shape& s, const float* ipack, int64_t n, const int64
 int tile_clear_tail(float* index, int64_t n, int64_t tile_fl, hipStream_t stream);
 int rows_clear_tail(float* index, int64_t n, int64_t ld, hipStream_t stream);
 int coarse_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream);
-int component_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n_total, hipStream_t stream);
+int component_update(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int64_t m, void* table, int64_t n_total, hipStream_t stream,
+                     int64_t first = 0);   // positions == NULL: component_build's rows first .. first + m - 1
 // fp32 Ex fragments of a freshly built index -> f16 hi/lo fragments, in place (precision f16x3)
 int index_split_inplace(const Shape& s, float* ipack, int64_t n, hipStream_t stream);
 int index_gather(const Shape& s, const float* ipack, int64_t n, const int64_t* idx, int64_t rows, int64_t n_cand,

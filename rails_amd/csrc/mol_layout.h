@@ -92,6 +92,15 @@ MOL_HD int kdim_of(int s, int hi, int DD) { return hi * (DD / 2) + s; }
 MOL_HD int reg_of_row(int i) { return (i & 3) + 4 * (i >> 3); }
 MOL_HD int half_of_row(int i) { return (i >> 2) & 1; }
 
+// The fp32 fragment format of the item index: tiles of kTileItems items, kTileItems * (P_X * d + P_Q * P_X) floats each, Ex then gi.  A tile's Ex is
+// [m < P_X][c < d / 8][lane < 64] float4: lane = 32 hi + x holds Ex[x][m][kdim_of(4 c + j, hi, d) = hi * d / 2 + 4 c + j], j < 4, of the tile's item x.
+// ex_slot: the float4 index of (x, m, c, hi) inside a tile; ex_offset: the float offset of Ex[x][m][dd].
+MOL_HD int ex_slot(int d, int x, int m, int c, int hi) { return (m * (d / 8) + c) * 64 + hi * 32 + x; }
+MOL_HD int ex_offset(int d, int x, int m, int dd) {
+  const int hi = dd / (d / 2), s = dd - hi * (d / 2);
+  return ex_slot(d, x, m, s >> 2, hi) * 4 + (s & 3);
+}
+
 // ---- small-unit layout: v_mfma_f32_16x16x4_f32, unit = 2 queries x 16 items (mol_score_small.h; P_Q = 8 only) -----------------
 // Accumulator register i (0..3) of lane group g = lane >> 4 holds row 4g + i of item column lane & 15; as the B operand of the
 // next GEMM, register i is one K = 4 step with k = g.  fp32 MFMA is an fmaf chain in k order, and the small kernel must return the

@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from . import engine as E
-from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule
+from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule, _checked_positions
 
 
 def shard_bounds(n_items: int, world_size: int, rank: int) -> Tuple[int, int]:
@@ -259,7 +259,7 @@ class ShardedTopK(TopKModule):
         emb = item_embeddings[0] if torch.is_tensor(item_embeddings) and item_embeddings.dim() == 3 and item_embeddings.shape[0] == 1 else item_embeddings
         if not torch.is_tensor(emb) or emb.dim() != 2:
             raise ValueError("item_embeddings must be (M, D) or (1, M, D)")
-        host = local._checked_positions(global_positions, emb.shape[0], self._n_total).cpu()
+        host = _checked_positions(global_positions, emb.shape[0], self._n_total).cpu()
         if item_ids is not None and (not torch.is_tensor(item_ids) or item_ids.numel() != emb.shape[0]):
             raise ValueError(f"item_ids must hold {emb.shape[0]} ids")
         if emb.shape[0] == 0:

@@ -44,9 +44,11 @@ class TopKModule(torch.nn.Module):
         """-> (top_k_scores (B, k), top_k_ids (B, k))."""
 
 
-def _rows_arg(item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], dim: int, dtype: torch.dtype, device: torch.device, ids_dtype: torch.dtype):
+def _rows_arg(item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], dim: int, dtype: torch.dtype, device: torch.device, ids_dtype: torch.dtype, appending: bool = False):
     """The rows (and ids) argument of update_items / append_items against a table of `dim` columns, `dtype`, on `device` -> ((M, dim) rows, (M,) ids
     or None); ValueError for anything else."""
+    if appending and item_ids is None:
+        raise ValueError("append_items needs the ids of the new items")
     emb = item_embeddings
     if not torch.is_tensor(emb):
         raise ValueError("item_embeddings must be a tensor")
@@ -67,6 +69,49 @@ def _rows_arg(item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], d
     return emb, ids
 
 
+def _checked_positions(positions: torch.Tensor, m: int, n: int) -> torch.Tensor:
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or tuple(positions.shape) != (m,):
+        raise ValueError(f"positions must be ({m},) int64")
+    if m:
+        host = positions.cpu()      # (the one sync of a device tensor)
+        if int(host.min()) < 0 or int(host.max()) >= n:
+            raise ValueError(f"positions must lie in [0, {n})")
+        if torch.unique(host).numel() != m:
+            raise ValueError("positions must be unique")
+    return positions
+
+
+def _removal_arg(positions: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """remove_items' positions against n items -> removal_plan's (holes, movers) and `moved`, CPU int64 rows [from, to]."""
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 1:
+        raise ValueError("positions must be (M,) int64")
+    holes, movers = removal_plan(positions.cpu(), n)      # (the one sync of a device tensor)
+    return holes, movers, torch.stack([movers, holes], dim=1)
+
+
+def _write_ids(item_ids: torch.Tensor, flat: torch.Tensor, pos: torch.Tensor, ids: torch.Tensor) -> None:
+    """update_items: `ids` at positions `pos` (on flat's device) of the borrowed id tensor, (1, N) or (N,), and of `flat`, its int64 copy (or that very storage)."""
+    own = item_ids[0] if item_ids.dim() == 2 else item_ids
+    own.index_copy_(0, pos.to(own.device), ids.to(device=own.device, dtype=own.dtype))
+    if flat.data_ptr() != own.data_ptr():
+        flat.index_copy_(0, pos, ids.to(device=pos.device, dtype=torch.int64))
+
+
+def _append_ids(item_ids: torch.Tensor, flat: torch.Tensor, ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """append_items: `ids` behind both -> new ((1, N + M) item_ids, flat)."""
+    return (torch.cat([item_ids.reshape(1, -1), ids.reshape(1, -1).to(device=item_ids.device, dtype=item_ids.dtype)], dim=1),
+            torch.cat([flat, ids.to(device=flat.device, dtype=torch.int64)]))
+
+
+def _remove_ids(item_ids: torch.Tensor, flat: torch.Tensor, n_new: int, holes: torch.Tensor, movers: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """remove_items: both cut to n_new, the movers' ids in the holes (both on flat's device) -> new ((1, n_new) item_ids, flat)."""
+    own = item_ids.reshape(1, -1)
+    ids, new_flat = own[:, :n_new].clone(), flat[:n_new].clone()
+    ids[0].index_copy_(0, holes.to(own.device), own[0].index_select(0, movers.to(own.device)))
+    new_flat.index_copy_(0, holes, flat.index_select(0, movers))
+    return ids, new_flat
+
+
 def removal_plan(positions: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """The one rule of remove_items: removing `positions` ((M,) int64 on the CPU, unique, inside [0, n)) from a table of n
     rows leaves N' = n - M rows -- rows 0 .. N' - 1 with the HOLES (the removed positions below N', ascending) filled from the MOVERS (the surviving
@@ -76,7 +121,7 @@ def removal_plan(positions: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.T
     if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 1 or positions.is_cuda:
         raise ValueError("positions must be a 1-d int64 tensor on the CPU")
     m = positions.numel()
-    MoLTopKModule._checked_positions(positions, m, n)
+    _checked_positions(positions, m, n)
     n_new = n - m
     if n_new < 1:
         raise ValueError(f"removing {m} of {n} items would leave none")
@@ -165,7 +210,7 @@ class MoLTopKModule(TopKModule):
         positions live on the device).  M = 0 is a no-op."""
         self._check_updatable("update_items")
         emb, ids = self._update_rows_arg(item_embeddings, item_ids)
-        pos = self._checked_positions(positions, emb.shape[0], self.num_items)
+        pos = _checked_positions(positions, emb.shape[0], self.num_items)
         if emb.shape[0] == 0:
             return
         with torch.inference_mode():
@@ -174,10 +219,7 @@ class MoLTopKModule(TopKModule):
             pos = pos.to(self._item_embeddings.device)
             self._item_embeddings[0].index_copy_(0, pos, emb)
             if ids is not None:
-                own = self._item_ids[0] if self._item_ids.dim() == 2 else self._item_ids
-                own.index_copy_(0, pos.to(own.device), ids.to(device=own.device, dtype=own.dtype))
-                if self._ids_flat.data_ptr() != own.data_ptr():
-                    self._ids_flat.index_copy_(0, pos, ids.to(device=pos.device, dtype=torch.int64))
+                _write_ids(self._item_ids, self._ids_flat, pos, ids)
             self._refresh(eng, pos, emb)
             self._after_update(eng)
 
@@ -188,9 +230,7 @@ class MoLTopKModule(TopKModule):
         as for a fresh module).  Everything a fresh module decides from N is decided again for N + M.  From this call on the module OWNS its item
         table and ids (the caller's tensors are no longer written)."""
         self._check_updatable("append_items")
-        if item_ids is None:
-            raise ValueError("append_items needs the ids of the new items")
-        emb, ids = self._update_rows_arg(item_embeddings, item_ids)
+        emb, ids = self._update_rows_arg(item_embeddings, item_ids, appending=True)
         m = emb.shape[0]
         if m == 0:
             return
@@ -199,8 +239,7 @@ class MoLTopKModule(TopKModule):
             eng = self._bind()
             n, dev = self.num_items, self._item_embeddings.device
             self._item_embeddings = torch.cat([self._item_embeddings, emb.unsqueeze(0)], dim=1)
-            self._item_ids = torch.cat([self._item_ids.reshape(1, -1), ids.reshape(1, -1).to(device=self._item_ids.device, dtype=self._item_ids.dtype)], dim=1)
-            self._ids_flat = torch.cat([self._ids_flat, ids.to(device=dev, dtype=torch.int64)])
+            self._item_ids, self._ids_flat = _append_ids(self._item_ids, self._ids_flat, ids)
             self._grow(eng, m)
             self._refresh(eng, torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
             self._after_append(eng)
@@ -214,11 +253,8 @@ class MoLTopKModule(TopKModule):
         this call on the module OWNS its item table and ids; the caller's tensors are not written.  ValueError before anything is touched (one
         device sync when the positions live on the device).  M = 0 is a no-op."""
         self._check_updatable("remove_items")
-        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 1:
-            raise ValueError("positions must be (M,) int64")
         n = self.num_items
-        holes, movers = removal_plan(positions.cpu(), n)      # (the one sync of a device tensor)
-        moved = torch.stack([movers, holes], dim=1)
+        holes, movers, moved = _removal_arg(positions, n)
         m = positions.numel()
         if m == 0:
             return moved
@@ -230,12 +266,8 @@ class MoLTopKModule(TopKModule):
             emb = self._item_embeddings[0].index_select(0, mv)
             table = self._item_embeddings[:, :n_new].clone()
             table[0].index_copy_(0, h, emb)
-            own = self._item_ids.reshape(1, -1)
-            ids = own[:, :n_new].clone()
-            ids[0].index_copy_(0, h.to(own.device), own[0].index_select(0, mv.to(own.device)))
-            flat = self._ids_flat[:n_new].clone()
-            flat.index_copy_(0, h, self._ids_flat.index_select(0, mv))
-            self._item_embeddings, self._item_ids, self._ids_flat = table, ids, flat
+            self._item_ids, self._ids_flat = _remove_ids(self._item_ids, self._ids_flat, n_new, h, mv)
+            self._item_embeddings = table
             self._forget_corpus_choices()
             if self._engine_for_bind() is eng:
                 self._shrink(eng, n_new)
@@ -249,21 +281,9 @@ class MoLTopKModule(TopKModule):
     def _check_updatable(self, what: str) -> None:
         """Modules whose state cannot follow an in-place change refuse here, before anything is touched."""
 
-    def _update_rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor]):
+    def _update_rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], appending: bool = False):
         table = self._item_embeddings
-        return _rows_arg(item_embeddings, item_ids, table.shape[2], table.dtype, table.device, self._item_ids.dtype)
-
-    @staticmethod
-    def _checked_positions(positions: torch.Tensor, m: int, n: int) -> torch.Tensor:
-        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or tuple(positions.shape) != (m,):
-            raise ValueError(f"positions must be ({m},) int64")
-        if m:
-            host = positions.cpu()      # (the one sync of a device tensor)
-            if int(host.min()) < 0 or int(host.max()) >= n:
-                raise ValueError(f"positions must lie in [0, {n})")
-            if torch.unique(host).numel() != m:
-                raise ValueError("positions must be unique")
-        return positions
+        return _rows_arg(item_embeddings, item_ids, table.shape[2], table.dtype, table.device, self._item_ids.dtype, appending)
 
     def _join_side_streams(self) -> None:
         if not self._item_embeddings.is_cuda:
@@ -2054,46 +2074,37 @@ class MIPSBruteForceTopK(MIPSTopKModule):
     def num_items(self) -> int:
         return self._index.n_items
 
-    def _rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor]):
-        return _rows_arg(item_embeddings, item_ids, self._index.dim, self._table_dtype, self._index.buf.device, self._item_ids.dtype)
+    def _rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], appending: bool = False):
+        return _rows_arg(item_embeddings, item_ids, self._index.dim, self._table_dtype, self._index.buf.device, self._item_ids.dtype, appending)
 
     def update_items(self, positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
         """MoLTopKModule.update_items.  The raw table is not kept, so only the borrowed id tensor is written in place."""
         emb, ids = self._rows_arg(item_embeddings, item_ids)
-        pos = MoLTopKModule._checked_positions(positions, emb.shape[0], self.num_items)
+        pos = _checked_positions(positions, emb.shape[0], self.num_items)
         if emb.shape[0] == 0:
             return
         with torch.inference_mode():
             pos = pos.to(self._index.buf.device)
             self._index.update(pos, emb)
             if ids is not None:
-                own = self._item_ids[0] if self._item_ids.dim() == 2 else self._item_ids
-                own.index_copy_(0, pos.to(own.device), ids.to(device=own.device, dtype=own.dtype))
-                if self._ids_flat.data_ptr() != own.data_ptr():
-                    self._ids_flat.index_copy_(0, pos, ids.to(device=pos.device, dtype=torch.int64))
+                _write_ids(self._item_ids, self._ids_flat, pos, ids)
 
     def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
         """MoLTopKModule.append_items: the new items at positions N .. N + M - 1; from this call on the module owns its ids."""
-        if item_ids is None:
-            raise ValueError("append_items needs the ids of the new items")
-        emb, ids = self._rows_arg(item_embeddings, item_ids)
+        emb, ids = self._rows_arg(item_embeddings, item_ids, appending=True)
         m = emb.shape[0]
         if m == 0:
             return
         with torch.inference_mode():
             n, dev = self.num_items, self._index.buf.device
-            self._item_ids = torch.cat([self._item_ids.reshape(1, -1), ids.reshape(1, -1).to(device=self._item_ids.device, dtype=self._item_ids.dtype)], dim=1)
-            self._ids_flat = torch.cat([self._ids_flat, ids.to(device=dev, dtype=torch.int64)])
+            self._item_ids, self._ids_flat = _append_ids(self._item_ids, self._ids_flat, ids)
             self._index.grow(m)
             self._index.update(torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
 
     def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
         """MoLTopKModule.remove_items (removal_plan's rule) -> `moved`, CPU int64 rows [from, to].  The movers' rows are read back from the index."""
-        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 1:
-            raise ValueError("positions must be (M,) int64")
         n = self.num_items
-        holes, movers = removal_plan(positions.cpu(), n)
-        moved = torch.stack([movers, holes], dim=1)
+        holes, movers, moved = _removal_arg(positions, n)
         m = positions.numel()
         if m == 0:
             return moved
@@ -2101,12 +2112,7 @@ class MIPSBruteForceTopK(MIPSTopKModule):
             n_new, dev = n - m, self._index.buf.device
             h, mv = holes.to(dev), movers.to(dev)
             rows = self._index.rows(mv)
-            own = self._item_ids.reshape(1, -1)
-            ids = own[:, :n_new].clone()
-            ids[0].index_copy_(0, h.to(own.device), own[0].index_select(0, mv.to(own.device)))
-            flat = self._ids_flat[:n_new].clone()
-            flat.index_copy_(0, h, self._ids_flat.index_select(0, mv))
-            self._item_ids, self._ids_flat = ids, flat
+            self._item_ids, self._ids_flat = _remove_ids(self._item_ids, self._ids_flat, n_new, h, mv)
             self._index.shrink(n_new)
             if holes.numel():
                 self._index.update(h, rows)

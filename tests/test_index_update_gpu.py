@@ -321,3 +321,43 @@ def test_refusals_and_validation(dev):
             ivf.append_items(rows, torch.tensor([1, 2, 3], device=dev))
         same(ivf(q, k=10), first, "the IVF module after the refusals")
         assert ivf.num_items == n and torch.equal(X, snap["table"][0])
+
+
+@pytest.mark.parametrize("config", ["amzn-books", "synthetic-16x16x64"])       # 8x8x32 and 16x16x64: P_X and d both differ
+def test_derived_tables_build_at_an_offset_and_update_equal_the_build(config, dev):
+    """The engine and C entry points of the derived buffers directly, N = 70 (two full tiles and a ragged one of 6), fp32 engine: the build
+    into a table at an offset -- _derived_table's chunked arm, which the modules only reach from 2^20 items on -- and the update from both
+    forms of update_source, against the one-call build, bit for bit."""
+    cfg = O.CONFIGS[config]
+    n, px, d = 70, cfg.item_dot_product_groups, cfg.dot_product_dimension
+    bits = lambda t: t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+    eng = build_module(cfg, O.synthetic_weights(cfg, seed=1), dev, precision="fp32").engine()
+    assert eng.precision == "fp32" and eng.route != "generic"
+    with torch.inference_mode():
+        X = table(cfg, n, 17, dev)
+        index, head, tail = eng.build_index(X), eng.build_index(X[:64]), eng.build_index(X[64:])
+        shape, lib = E.C.byref(eng.shape), eng.lib
+        # (a) one call against two calls into one table, the second at item 64
+        coarse, comp = eng.build_coarse_table(index), eng.build_component_table(index)
+        coarse2 = torch.full((n, d), -1, dtype=torch.int16, device=dev).view(torch.bfloat16)
+        comp2 = torch.full((px, n, d), -1, dtype=torch.int16, device=dev).view(torch.bfloat16)
+        with E._on_device(dev):
+            for part, m, first in ((head, 64, 0), (tail, 6, 64)):
+                E._lib.check(lib.rails_mol_component_build(shape, E._ptr(part.buf), m, E._ptr(comp2), n, first, E._stream()), "rails_mol_component_build")
+                E._lib.check(lib.rails_mol_coarse_build(shape, E._ptr(part.buf), m, E.C.c_void_p(coarse2.data_ptr() + 2 * first * d), E._stream()),
+                             "rails_mol_coarse_build")
+        assert torch.equal(bits(comp2), bits(comp)), "component table built in two parts"
+        assert torch.equal(bits(coarse2), bits(coarse)), "coarse table built in two parts"
+        # (b), (c) every row updated in a fixed shuffled order, from the index in place and from a temporary index of the rows in that order
+        perm = torch.randperm(n, generator=torch.Generator().manual_seed(5)).to(dev)
+        for what, source in (("in place", (index.buf, 1)), ("temporary index", (eng.build_index(X[perm]).buf, 0))):
+            coarse3, comp3 = torch.full_like(bits(coarse), -1).view(torch.bfloat16), torch.full_like(bits(comp), -1).view(torch.bfloat16)
+            eng.update_coarse_table(coarse3, perm, source)
+            eng.update_component_table(comp3, perm, source)
+            assert torch.equal(bits(coarse3), bits(coarse)), f"coarse table updated from the source {what}"
+            assert torch.equal(bits(comp3), bits(comp)), f"component table updated from the source {what}"
+        # (d) the row-major copy
+        rows = eng.build_index_rows(index)
+        rows2 = torch.full_like(bits(rows), -1).view(torch.float32)
+        eng.update_index_rows(index, rows2, perm)
+        assert torch.equal(bits(rows2), bits(rows)), "row-major copy updated at every position"
