@@ -296,6 +296,31 @@ size_t rails_mips_query_ws_floats(int32_t dim, int32_t batch);         /* scratc
 int rails_mips_score(const float* queries, int32_t batch, int32_t dim, const float* index, int64_t n_items,
                      float* query_ws, float* logits, int64_t ld, void* stream);
 
+/* ---- item id -> position map (additions under ABI 15) ------------------------------------------
+ * What lets a caller address the corpus of a top-k module by item id (positions_of, update_items_by_id, remove_items_by_id, upsert_items).
+ * An open-addressing table with linear probing in device memory: int64 keys[slots], then int32 values[slots]; slots a power of two.
+ * INT64_MIN marks an EMPTY slot and INT64_MIN + 1 an ERASED one (a tombstone; an insert never reuses it): both are reserved, an id equal to
+ * either is counted and not stored.  The home slot of an id is mix(id) & (slots - 1), mix the splitmix64 step of the hashed item tables
+ * below, on the id as an unsigned 64-bit word (arithmetic mod 2^64):
+ *   z = id + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  mix = z ^ (z >> 31)
+ * -- a bijection (odd multipliers, xor-shifts).  One thread per id; every probe loop ends within `slots` steps.  Which key lands in which
+ * slot depends on the order the atomic claims win in: the contract is on lookups, not on the table's bytes.
+ * slots: the smallest power of two >= 4 * max(n_items, 1), so a fresh table has load <= 1/4; RAILS_EINVAL for n_items < 0 or >= 2^31 (values
+ *   are int32 positions).  bytes: 12 * slots; 0 when slots is not a power of two in [1, 2^33].
+ * clear: every slot EMPTY.
+ * insert: ids[u] (int64, device) -> positions[u] (int64, device), or first + u when positions is NULL.  flags (3 x int32, device, ADDED to):
+ *   [0] ids already in the table or given twice in the call (the table keeps one entry), [1] reserved ids or positions outside [0, 2^31),
+ *   [2] inserts that found no slot in a full table.
+ * erase: the key becomes ERASED; *missing (int32, device, ADDED to) counts the ids that were absent (or given a second time).
+ * lookup: positions_out[u] (int64, device) = the position of ids[u], -1 where absent.
+ * All four return RAILS_EINVAL before any launch for a NULL pointer, slots not a power of two, m < 0 or first + m > 2^31; m = 0 is a no-op. */
+int64_t rails_id_map_slots(int64_t n_items);
+size_t rails_id_map_bytes(int64_t slots);
+int rails_id_map_clear(void* map, int64_t slots, void* stream);
+int rails_id_map_insert(void* map, int64_t slots, const int64_t* ids, const int64_t* positions, int64_t first, int64_t m, int32_t* flags, void* stream);
+int rails_id_map_erase(void* map, int64_t slots, const int64_t* ids, int64_t m, int32_t* missing, void* stream);
+int rails_id_map_lookup(const void* map, int64_t slots, const int64_t* ids, int64_t m, int64_t* positions_out, void* stream);
+
 /* Per-row candidates: out[bq * n_cand + x] = <queries[bq], items[bq / r][x]> for queries (n_queries, dim) and items
  * (n_queries / r, n_cand, dim) -- the two bmm branches of DotProductSimilarity.forward
  * (rails/similarities/dot_product_similarity_fn.py:55-68). */

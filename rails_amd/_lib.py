@@ -202,6 +202,12 @@ PROTOTYPES = {
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     ),
+    "rails_id_map_slots": (C.c_int64, [C.c_int64]),
+    "rails_id_map_bytes": (C.c_size_t, [C.c_int64]),
+    "rails_id_map_clear": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "rails_id_map_insert": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_id_map_erase": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_id_map_lookup": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "rails_dot_rowwise": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],

@@ -627,6 +627,52 @@ int rails_dot_rowwise(const float* queries, const float* items, int64_t n_querie
   return fail(dot_rowwise(queries, items, n_queries, n_cand, dim, r, out, (hipStream_t)stream), "dot_rowwise");
 }
 
+// ---- item id -> position map (id_map.hip) ----
+static bool id_map_slots_ok(int64_t slots) { return slots >= 1 && slots <= (1LL << 33) && (slots & (slots - 1)) == 0; }
+
+// the checks the four entry points share, before any launch: 1 = launch, 0 = nothing to do, < 0 = the error code
+static int id_map_args(const char* what, bool pointers, int64_t slots, int64_t m, int64_t first = 0) {
+  g_err[0] = '\0';
+  if (!id_map_slots_ok(slots)) { set_error("%s: slots = %lld is not a power of two in [1, 2^33]", what, (long long)slots); return RAILS_EINVAL; }
+  if (m < 0 || first < 0 || first > (1LL << 31) || m > (1LL << 31) - first) {
+    set_error("%s: m = %lld ids from position %lld: sizes must be >= 0 and positions below 2^31", what, (long long)m, (long long)first);
+    return RAILS_EINVAL;
+  }
+  if (m == 0) return 0;
+  if (!pointers) { set_error("%s: NULL pointer", what); return RAILS_EINVAL; }
+  return 1;
+}
+
+int64_t rails_id_map_slots(int64_t n_items) {
+  g_err[0] = '\0';
+  if (n_items < 0 || n_items >= (1LL << 31)) { set_error("id_map_slots: n_items = %lld outside [0, 2^31)", (long long)n_items); return RAILS_EINVAL; }
+  int64_t slots = 4;
+  while (slots < 4 * n_items) slots <<= 1;
+  return slots;
+}
+
+size_t rails_id_map_bytes(int64_t slots) { return id_map_slots_ok(slots) ? (size_t)slots * 12 : 0; }
+
+int rails_id_map_clear(void* map, int64_t slots, void* stream) {
+  const int go = id_map_args("id_map_clear", map != nullptr, slots, 1);
+  return go <= 0 ? go : fail(id_map_clear(map, slots, (hipStream_t)stream), "id_map_clear");
+}
+
+int rails_id_map_insert(void* map, int64_t slots, const int64_t* ids, const int64_t* positions, int64_t first, int64_t m, int32_t* flags, void* stream) {
+  const int go = id_map_args("id_map_insert", map && ids && flags, slots, m, positions ? 0 : first);
+  return go <= 0 ? go : fail(id_map_insert(map, slots, ids, positions, first, m, flags, (hipStream_t)stream), "id_map_insert");
+}
+
+int rails_id_map_erase(void* map, int64_t slots, const int64_t* ids, int64_t m, int32_t* missing, void* stream) {
+  const int go = id_map_args("id_map_erase", map && ids && missing, slots, m);
+  return go <= 0 ? go : fail(id_map_erase(map, slots, ids, m, missing, (hipStream_t)stream), "id_map_erase");
+}
+
+int rails_id_map_lookup(const void* map, int64_t slots, const int64_t* ids, int64_t m, int64_t* positions_out, void* stream) {
+  const int go = id_map_args("id_map_lookup", map && ids && positions_out, slots, m);
+  return go <= 0 ? go : fail(id_map_lookup(map, slots, ids, m, positions_out, (hipStream_t)stream), "id_map_lookup");
+}
+
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s) || n_items < 0) return 0;
   return (size_t)n_items * (size_t)s->dot_product_dimension * 2;

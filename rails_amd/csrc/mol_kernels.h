@@ -209,6 +209,12 @@ int mips_gather_rows(const float* index, int64_t n_index, int D, const int64_t* 
 int mips_score(const float* q, int B, int D, const float* ifrag, int64_t n, float* qfrag_ws, float* logits, int64_t ld,
                int n_cu, hipStream_t stream);
 
+// ---- item id -> position map (id_map.hip): int64 keys[slots] then int32 values[slots], slots a power of two ----
+int id_map_clear(void* map, int64_t slots, hipStream_t stream);
+int id_map_insert(void* map, int64_t slots, const int64_t* ids, const int64_t* positions, int64_t first, int64_t m, int32_t* flags, hipStream_t stream);
+int id_map_erase(void* map, int64_t slots, const int64_t* ids, int64_t m, int32_t* missing, hipStream_t stream);
+int id_map_lookup(const void* map, int64_t slots, const int64_t* ids, int64_t m, int64_t* positions_out, hipStream_t stream);
+
 int dot_rowwise(const float* q, const float* items, int64_t Bq, int X, int D, int r, float* out, hipStream_t stream);
 
 size_t topk_workspace_bytes(int rows, int64_t n, int k);

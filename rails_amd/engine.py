@@ -963,6 +963,124 @@ class MipsIndex:
         return out
 
 
+# ---- item id -> position map (rails_id_map_*) ---------------------------------------------------
+ID_MAP_RESERVED = (-(1 << 63), -(1 << 63) + 1)      # EMPTY and ERASED: no item may carry these ids
+
+
+def _ids_arg(ids: torch.Tensor, device: torch.device, what: str = "item_ids") -> torch.Tensor:
+    if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.dim() != 1:
+        raise ValueError(f"{what} must be (M,) int64")
+    return ids.to(device).contiguous()
+
+
+def id_map_slots(n_items: int) -> int:
+    slots = _lib.load().rails_id_map_slots(n_items)
+    if slots < 0:
+        _lib.check(int(slots), "rails_id_map_slots")
+    return int(slots)
+
+
+def id_map_new(slots: int, device: torch.device) -> torch.Tensor:
+    """An empty table of `slots` slots (int64 keys, then int32 values) as one uint8 tensor."""
+    lib = _lib.load()
+    table = torch.empty(lib.rails_id_map_bytes(slots), dtype=torch.uint8, device=device)
+    with _on_device(table.device):
+        _lib.check(lib.rails_id_map_clear(_ptr(table), slots, _stream()), "rails_id_map_clear")
+    return table
+
+
+def id_map_insert(table: torch.Tensor, slots: int, ids: torch.Tensor, positions: Optional[torch.Tensor], first: int, flags: torch.Tensor) -> None:
+    """ids (M,) int64 -> positions (M,) int64, or first + u for None; flags (>= 3,) int32 on the device is added to: [0] present already or twice in
+    the call, [1] reserved, [2] no slot."""
+    ids = _ids_arg(ids, table.device)
+    if positions is not None:
+        positions = _ids_arg(positions, table.device, "positions")
+        if positions.numel() != ids.numel():
+            raise ValueError(f"{ids.numel()} ids but {positions.numel()} positions")
+    with _on_device(table.device):
+        _lib.check(_lib.load().rails_id_map_insert(_ptr(table), slots, _ptr(ids), _ptr(positions), first, ids.numel(), _ptr(flags), _stream()),
+                   "rails_id_map_insert")
+
+
+def id_map_erase(table: torch.Tensor, slots: int, ids: torch.Tensor, missing: torch.Tensor) -> None:
+    """The keys of ids (M,) int64 become tombstones; missing (1,) int32 on the device is added to for every absent id."""
+    ids = _ids_arg(ids, table.device)
+    with _on_device(table.device):
+        _lib.check(_lib.load().rails_id_map_erase(_ptr(table), slots, _ptr(ids), ids.numel(), _ptr(missing), _stream()), "rails_id_map_erase")
+
+
+def id_map_lookup(table: torch.Tensor, slots: int, ids: torch.Tensor) -> torch.Tensor:
+    """(M,) int64 positions on the table's device, -1 where the id is absent."""
+    ids = _ids_arg(ids, table.device)
+    out = torch.empty(ids.numel(), dtype=torch.int64, device=table.device)
+    with _on_device(table.device):
+        _lib.check(_lib.load().rails_id_map_lookup(_ptr(table), slots, _ptr(ids), ids.numel(), _ptr(out), _stream()), "rails_id_map_lookup")
+    return out
+
+
+class ItemIdMap:
+    """The id -> position map of one corpus: the device table, the live and tombstone counts (host integers: upper bounds of the slots in
+    use) and four device counters -- [0] duplicates, [1] reserved ids, [2] inserts without a slot, [3] erased ids that were absent.
+
+    Tombstones are never reused, so the slots in use only grow: before any launch that would take live + tombstones + incoming past
+    slots / 2, insert builds the table again, at rails_id_map_slots(n) slots, from `ids_flat` -- the ids, in position order, that the map
+    is to hold once the call in progress is done (a module passes its own id tensor, written before the map is told).  The kernels' "no
+    slot" counter cannot be reached through this class.  insert / erase launch and return; take_flags() reads and clears the counters (one
+    sync) and is how a caller learns that the ids it fed were not what the map expected."""
+
+    def __init__(self, device: torch.device):
+        self.device = torch.device(device)
+        self.table: Optional[torch.Tensor] = None
+        self.slots = self.live = self.tombstones = self.rebuilds = 0
+        with torch.inference_mode(False):     # (an ordinary tensor: cleared in place from inside and outside inference mode)
+            self.flags = torch.zeros(4, dtype=torch.int32, device=self.device)
+
+    def build(self, ids_flat: torch.Tensor) -> None:
+        """A fresh table holding ids_flat[p] -> p.  ValueError, naming the count, for ids that repeat or are reserved (the map is then empty)."""
+        ids = _ids_arg(ids_flat, self.device, "ids_flat")
+        self.slots = id_map_slots(ids.numel())
+        self.table = id_map_new(self.slots, self.device)
+        self.live, self.tombstones = ids.numel(), 0
+        self.flags.zero_()
+        id_map_insert(self.table, self.slots, ids, None, 0, self.flags)
+        dup, reserved, _, _ = self.take_flags()
+        if dup or reserved:
+            self.table, self.slots, self.live = None, 0, 0
+            raise ValueError(f"the corpus cannot be addressed by id: {dup} of its {ids.numel()} item ids repeat an earlier one and {reserved} are reserved "
+                             f"values ({ID_MAP_RESERVED[0]}, {ID_MAP_RESERVED[1]})")
+
+    def rebuild(self, ids_flat: torch.Tensor) -> None:
+        """build(), counted: what insert does instead of letting the load pass 1/2."""
+        self.rebuilds += 1
+        self.build(ids_flat)
+
+    def insert(self, ids: torch.Tensor, positions: torch.Tensor, ids_flat: torch.Tensor) -> None:
+        m = ids.numel()
+        if self.table is None or self.live + self.tombstones + m > self.slots // 2:
+            self.rebuild(ids_flat)      # holds `ids` at `positions` already
+            return
+        id_map_insert(self.table, self.slots, ids, positions, 0, self.flags)
+        self.live += m
+
+    def erase(self, ids: torch.Tensor) -> None:
+        m = ids.numel()
+        id_map_erase(self.table, self.slots, ids, self.flags[3:])
+        self.live -= m
+        self.tombstones += m
+
+    def lookup(self, ids: torch.Tensor) -> torch.Tensor:
+        return id_map_lookup(self.table, self.slots, ids)
+
+    def take_flags(self) -> Tuple[int, int, int, int]:
+        host = self.flags.tolist()      # (one sync)
+        if any(host):
+            self.flags.zero_()
+        return tuple(host)
+
+    def info(self) -> Dict[str, int]:
+        return {"slots": self.slots, "live": self.live, "tombstones": self.tombstones, "rebuilds": self.rebuilds}
+
+
 def dot_rowwise(q: torch.Tensor, items: torch.Tensor) -> torch.Tensor:
     """q (Bq, D), items (B_I, X, D) with Bq a multiple of B_I -> (Bq, X): <q[bq], items[bq // r][x]>."""
     lib = _lib.load()

@@ -131,7 +131,112 @@ def removal_plan(positions: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.T
     return order[order < n_new], n_new + torch.nonzero(tail_kept).reshape(-1)
 
 
-class MoLTopKModule(TopKModule):
+def upsert_plan(found: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The host rule of upsert_items: `found` ((M,) int64 on the CPU) is where each given id sits in the corpus, -1 where it is absent ->
+    (update_rows, update_positions, append_rows): the rows of the argument that replace the items at update_positions, and the rows that are
+    appended -- both in the order given, so the i-th appended row lands at position N + i."""
+    present = found >= 0
+    rows = torch.arange(found.numel(), dtype=torch.int64)
+    return rows[present], found[present], rows[~present]
+
+
+def _by_id_arg(item_ids: torch.Tensor, what: str) -> torch.Tensor:
+    if (not torch.is_tensor(item_ids) or item_ids.is_floating_point() or item_ids.is_complex() or item_ids.dtype == torch.bool
+            or not (item_ids.dim() == 1 or (item_ids.dim() == 2 and item_ids.shape[0] == 1))):
+        raise ValueError(f"{what}: item_ids must be an (M,) or (1, M) integer tensor")
+    return item_ids.reshape(-1).to(torch.int64)
+
+
+class _ItemsById:
+    """The corpus addressed by item id, shared by MoLTopKModule and MIPSBruteForceTopK: a device-resident id -> position
+    map (engine.ItemIdMap) in front of update_items / append_items / remove_items, which stay the only code that edits the corpus.  The map is
+    built from the module's ids at the first by-id call -- ValueError, naming the count, when two items share an id or one carries a reserved
+    value (INT64_MIN, INT64_MIN + 1); the module is then exactly what it was and the by-position calls keep working.  From then on the
+    by-position calls keep the map in step (at the price of one small read-back per call); a module that never makes a by-id call never
+    builds one.  Out of scope: the sharded wrappers (their ranks own slices of the corpus) and an order-preserving compaction --
+    remove_items_by_id fills holes from the tail, as remove_items does."""
+
+    _id_map: Optional[E.ItemIdMap] = None
+
+    def _live_id_map(self) -> E.ItemIdMap:
+        m = self._id_map
+        if m is None:
+            m = E.ItemIdMap(self._ids_flat.device)
+            m.build(self._ids_flat)
+            self._id_map = m
+        return m
+
+    def positions_of(self, item_ids: torch.Tensor) -> torch.Tensor:
+        """(M,) int64 on the module's device: the position of each id of `item_ids` ((M,) or (1, M), CPU or device), -1 where the corpus has no
+        such item.  Read-only; works on every module, the IVF one included."""
+        ids = _by_id_arg(item_ids, "positions_of")
+        with torch.inference_mode():
+            return self._live_id_map().lookup(ids)
+
+    def _resolved(self, item_ids: torch.Tensor, what: str, absent_ok: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (ids (M,) int64 as given, their positions on the CPU); ValueError for an id given twice or, unless absent_ok, an unknown one."""
+        ids = _by_id_arg(item_ids, what)
+        found = self.positions_of(ids).cpu()      # (the one sync)
+        twice = ids.numel() - torch.unique(ids.cpu()).numel()
+        if twice:
+            raise ValueError(f"{what}: {twice} of the {ids.numel()} item ids repeat an earlier one")
+        unknown = int((found < 0).sum())
+        if unknown and not absent_ok:
+            raise ValueError(f"{what}: {unknown} of the {ids.numel()} item ids are not in the corpus")
+        return ids, found
+
+    def update_items_by_id(self, item_ids: torch.Tensor, item_embeddings: torch.Tensor, new_item_ids: Optional[torch.Tensor] = None) -> None:
+        """update_items for the items that carry `item_ids` ((M,) or (1, M)); `new_item_ids`, when given, renames them (two items may swap ids in
+        one call).  ValueError before anything is touched for an unknown id or an id given twice, naming how many (one device sync)."""
+        self._check_updatable("update_items_by_id")
+        _, found = self._resolved(item_ids, "update_items_by_id")
+        self.update_items(found, item_embeddings, new_item_ids)
+
+    def remove_items_by_id(self, item_ids: torch.Tensor) -> torch.Tensor:
+        """remove_items for the items that carry `item_ids` -> its `moved`.  Positions are not stable under removal (holes are filled from the
+        tail, no order-preserving compaction): ask positions_of again afterwards."""
+        self._check_updatable("remove_items_by_id")
+        _, found = self._resolved(item_ids, "remove_items_by_id")
+        return self.remove_items(found)
+
+    def upsert_items(self, item_ids: torch.Tensor, item_embeddings: torch.Tensor) -> None:
+        """The items of `item_ids` that the corpus holds are updated in place (update_items); the others are appended in the order given
+        (append_items: the module then owns its table and ids).  ValueError before anything is touched for an id given twice."""
+        self._check_updatable("upsert_items")
+        ids, found = self._resolved(item_ids, "upsert_items", absent_ok=True)
+        emb, _ = self._update_rows_arg(item_embeddings, None)
+        if emb.shape[0] != ids.numel():
+            raise ValueError(f"upsert_items: {ids.numel()} item ids but {emb.shape[0]} rows")
+        upd, pos, app = upsert_plan(found)
+        if upd.numel():
+            self.update_items(pos, emb.index_select(0, upd.to(emb.device)))
+        if app.numel():
+            self.append_items(emb.index_select(0, app.to(emb.device)), ids.index_select(0, app.to(ids.device)).to(self._item_ids.dtype))
+
+    def _ids_at(self, pos: torch.Tensor) -> Optional[torch.Tensor]:
+        """The ids at `pos` (device) for a live map -- read BEFORE a by-position call overwrites or moves them."""
+        return None if self._id_map is None else self._ids_flat.index_select(0, pos)
+
+    def _id_map_step(self, gone: Optional[torch.Tensor], ids: Optional[torch.Tensor], pos: Optional[torch.Tensor]) -> None:
+        """A live map follows a by-position call: the ids `gone` erased in one launch, then `ids` inserted at `pos` in a second (a batch may
+        swap ids between positions).  Called with self._ids_flat already what the call leaves.  An id the map did not expect (a duplicate
+        among the new ids, most likely) drops the map: the next by-id call builds it again and raises what a fresh module would."""
+        m = self._id_map
+        if m is None:
+            return
+        try:
+            if gone is not None and gone.numel():
+                m.erase(gone)
+            if ids is not None and ids.numel():
+                m.insert(ids.to(device=self._ids_flat.device, dtype=torch.int64), pos, self._ids_flat)
+            ok = not any(m.take_flags())
+        except ValueError:
+            ok = False
+        if not ok:
+            self._id_map = None
+
+
+class MoLTopKModule(_ItemsById, TopKModule):
     """Common state of the MoL top-k modules (reference mol_top_k.py:29-81): borrows `item_embeddings`
     (1, N, D) and `item_ids` (1, N); owns the packed index."""
 
@@ -219,7 +324,9 @@ class MoLTopKModule(TopKModule):
             pos = pos.to(self._item_embeddings.device)
             self._item_embeddings[0].index_copy_(0, pos, emb)
             if ids is not None:
+                old = self._ids_at(pos)
                 _write_ids(self._item_ids, self._ids_flat, pos, ids)
+                self._id_map_step(old, ids, pos)
             self._refresh(eng, pos, emb)
             self._after_update(eng)
 
@@ -240,6 +347,7 @@ class MoLTopKModule(TopKModule):
             n, dev = self.num_items, self._item_embeddings.device
             self._item_embeddings = torch.cat([self._item_embeddings, emb.unsqueeze(0)], dim=1)
             self._item_ids, self._ids_flat = _append_ids(self._item_ids, self._ids_flat, ids)
+            self._id_map_step(None, ids, torch.arange(n, n + m, dtype=torch.int64, device=dev))
             self._grow(eng, m)
             self._refresh(eng, torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
             self._after_append(eng)
@@ -266,7 +374,10 @@ class MoLTopKModule(TopKModule):
             emb = self._item_embeddings[0].index_select(0, mv)
             table = self._item_embeddings[:, :n_new].clone()
             table[0].index_copy_(0, h, emb)
+            gone, moving = self._ids_at(positions.to(dev)), self._ids_at(mv)
             self._item_ids, self._ids_flat = _remove_ids(self._item_ids, self._ids_flat, n_new, h, mv)
+            if gone is not None:
+                self._id_map_step(torch.cat([gone, moving]), moving, h)
             self._item_embeddings = table
             self._forget_corpus_choices()
             if self._engine_for_bind() is eng:
@@ -2049,7 +2160,7 @@ class MIPSTopKModule(TopKModule):
         self._item_ids: torch.Tensor = item_ids
 
 
-class MIPSBruteForceTopK(MIPSTopKModule):
+class MIPSBruteForceTopK(_ItemsById, MIPSTopKModule):
     """Dot-product brute force (reference rails/indexing/mips_top_k.py:41-81): MFMA scan + exact top-k, all HIP."""
 
     def __init__(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
@@ -2077,6 +2188,11 @@ class MIPSBruteForceTopK(MIPSTopKModule):
     def _rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], appending: bool = False):
         return _rows_arg(item_embeddings, item_ids, self._index.dim, self._table_dtype, self._index.buf.device, self._item_ids.dtype, appending)
 
+    _update_rows_arg = _rows_arg
+
+    def _check_updatable(self, what: str) -> None:
+        """Nothing this module holds refuses an in-place change (MoLTopKModule._check_updatable)."""
+
     def update_items(self, positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
         """MoLTopKModule.update_items.  The raw table is not kept, so only the borrowed id tensor is written in place."""
         emb, ids = self._rows_arg(item_embeddings, item_ids)
@@ -2087,7 +2203,9 @@ class MIPSBruteForceTopK(MIPSTopKModule):
             pos = pos.to(self._index.buf.device)
             self._index.update(pos, emb)
             if ids is not None:
+                old = self._ids_at(pos)
                 _write_ids(self._item_ids, self._ids_flat, pos, ids)
+                self._id_map_step(old, ids, pos)
 
     def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
         """MoLTopKModule.append_items: the new items at positions N .. N + M - 1; from this call on the module owns its ids."""
@@ -2098,6 +2216,7 @@ class MIPSBruteForceTopK(MIPSTopKModule):
         with torch.inference_mode():
             n, dev = self.num_items, self._index.buf.device
             self._item_ids, self._ids_flat = _append_ids(self._item_ids, self._ids_flat, ids)
+            self._id_map_step(None, ids, torch.arange(n, n + m, dtype=torch.int64, device=dev))
             self._index.grow(m)
             self._index.update(torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
 
@@ -2112,7 +2231,10 @@ class MIPSBruteForceTopK(MIPSTopKModule):
             n_new, dev = n - m, self._index.buf.device
             h, mv = holes.to(dev), movers.to(dev)
             rows = self._index.rows(mv)
+            gone, moving = self._ids_at(positions.to(dev)), self._ids_at(mv)
             self._item_ids, self._ids_flat = _remove_ids(self._item_ids, self._ids_flat, n_new, h, mv)
+            if gone is not None:
+                self._id_map_step(torch.cat([gone, moving]), moving, h)
             self._index.shrink(n_new)
             if holes.numel():
                 self._index.update(h, rows)
