@@ -45,8 +45,8 @@ extern "C" {
  * rails_sasrec_decode_layer are new;
  * 14: the IVF-Flat component index rails_ivf_* (MoLNaiveTopK use_faiss=True) is new;
  * 15: the shape-generic fp32 scoring route rails_mol_generic_* is new; the candidate-key entry points rails_group_keys_* of the item-sharded
- * MoLNaiveTopK / MoLCombTopK were added under 15 as well: no struct and no existing entry point changed, so callers built against the
- * earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
+ * MoLNaiveTopK / MoLCombTopK and the list edit rails_ivf_lists_edit[_workspace_bytes] of the IVF index were added under 15 as well: no struct
+ * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
 #define RAILS_ABI_VERSION 15
 int rails_abi_version(void);
@@ -428,6 +428,28 @@ int rails_ivf_assign(const rails_mol_shape* shape, const float* index, const voi
 int rails_ivf_build_lists(const rails_mol_shape* shape, const float* index, const void* components16, int64_t n_items, int32_t nlist,
                           const float* centroids, void* vectors, int32_t* positions, int32_t* offsets, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* Lists that follow an in-place change of the corpus under FROZEN centroids (FAISS IndexIVFFlat.add / remove_ids: the centroids are read,
+ * never written).  rails_ivf_lists_edit reads the old lists of n_old entries per group -- every position 0 .. n_old - 1 once, as
+ * rails_ivf_build_lists leaves them -- and writes FRESH buffers of n_new entries (no output may alias an input):
+ *   dropped    every old entry whose position is >= n_keep or is one of positions[0..m) (device int64, unique; m may be 0);
+ *   inserted   one entry per element of positions: its list by the assignment of rails_ivf_assign (the same kernel body: fma order and tie
+ *              rule of a full assignment), its fp16 vector cut from the fp32-format index `source_index` -- item positions[j] when
+ *              src_in_place != 0, item j otherwise (an index of the m new rows alone);
+ *   order      every list ascending by position; new_offsets (P_X, nlist + 1).
+ * The outputs are bit for bit what rails_ivf_build_lists writes from the resulting table with the same centroids, provided the result
+ * holds every position 0 .. n_new - 1 once.  n_new is the caller's (host arithmetic), and must be exactly
+ *   n_new = min(n_old, n_keep) - #{p in positions : p < min(n_old, n_keep)} + m.
+ * An n_new above min(n_old, n_keep) + m is RAILS_EINVAL; any other wrong n_new cannot be told from the arguments and gives undefined list
+ * CONTENTS (too small: entries are dropped; too large: the tail slots are not written) -- never a write outside the n_new entries.
+ * Launches: drop mask, indexed assignment, one rails_sort_rows_i64 row per group over the inserted entries' (list, position) keys (hence
+ * m <= 16384: RAILS_ENOTSUP beyond, rebuild with rails_ivf_build_lists), count / prefix / scan of the kept old slots in tiles of 4096, move,
+ * insert, offsets.  Deterministic; no float atomics.  workspace: rails_ivf_lists_edit_workspace_bytes(shape, n_old, nlist, m) bytes, a pure host
+ * function of its arguments; 0 with rails_last_error set: nlist outside [1, 4096], m outside [0, 16384], n_old outside [1, 2^31). */
+size_t rails_ivf_lists_edit_workspace_bytes(const rails_mol_shape* shape, int64_t n_old, int32_t nlist, int64_t m);
+int rails_ivf_lists_edit(const rails_mol_shape* shape, const float* source_index, int32_t src_in_place, const int64_t* positions, int64_t m,
+                         int64_t n_keep, int32_t nlist, const float* centroids, const void* old_vectors, const int32_t* old_positions,
+                         const int32_t* old_offsets, int64_t n_old, void* new_vectors, int32_t* new_positions, int32_t* new_offsets, int64_t n_new,
+                         void* workspace, size_t workspace_bytes, void* stream);
 /* HOST pointers: offsets is a host copy of the built offsets.  *max_probes = the probe capacity the short-list rule needs (the fewest
  * lists of any group whose sizes reach k_per_group, at least nprobe); *max_list = the largest list.  Both go to rails_ivf_search. */
 int rails_ivf_plan(const rails_mol_shape* shape, const int32_t* offsets, int32_t nlist, int32_t nprobe, int32_t k_per_group, int32_t* max_probes,

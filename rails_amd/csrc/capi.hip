@@ -1394,6 +1394,35 @@ int rails_ivf_build_lists(const rails_mol_shape* s, const float* index, const vo
                               (hipStream_t)stream), "ivf_build_lists");
 }
 
+size_t rails_ivf_lists_edit_workspace_bytes(const rails_mol_shape* s, int64_t n_old, int32_t nlist, int64_t m) {
+  g_err[0] = '\0';
+  if (!shape_ok(s) || ivf_lists_edit_check(*s, n_old, nlist, m) != kOk) return 0;
+  return ivf_lists_edit_workspace_bytes(*s, n_old, (int)m);
+}
+
+int rails_ivf_lists_edit(const rails_mol_shape* s, const float* source_index, int32_t src_in_place, const int64_t* positions, int64_t m, int64_t n_keep,
+                         int32_t nlist, const float* centroids, const void* old_vectors, const int32_t* old_positions, const int32_t* old_offsets,
+                         int64_t n_old, void* new_vectors, int32_t* new_positions, int32_t* new_offsets, int64_t n_new, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  g_err[0] = '\0';
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  const int c = ivf_lists_edit_check(*s, n_old, nlist, m);
+  if (c != kOk) return c;
+  if (is_split(*s)) { set_error("ivf_lists_edit: needs an fp32-format item index (build one with precision = RAILS_PRECISION_FP32)"); return RAILS_ENOTSUP; }
+  if (n_keep < 0 || n_new < 1 || n_new > std::min(n_old, n_keep) + m || n_new > 0x7fffffffLL) {
+    set_error("ivf_lists_edit: n_new = %lld outside [1, min(n_old = %lld, n_keep = %lld) + m = %lld]", (long long)n_new, (long long)n_old, (long long)n_keep,
+              (long long)m);
+    return RAILS_EINVAL;
+  }
+  if (!old_vectors || !old_positions || !old_offsets || !new_vectors || !new_positions || !new_offsets || !workspace ||
+      (m > 0 && (!source_index || !positions || !centroids))) {
+    set_error("ivf_lists_edit: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  return fail(ivf_lists_edit(*s, source_index, src_in_place ? 1 : 0, positions, (int)m, n_keep, nlist, centroids, old_vectors, old_positions, old_offsets,
+                             n_old, new_vectors, new_positions, new_offsets, n_new, workspace, workspace_bytes, (hipStream_t)stream), "ivf_lists_edit");
+}
+
 int rails_ivf_plan(const rails_mol_shape* s, const int32_t* offsets, int32_t nlist, int32_t nprobe, int32_t k_per_group, int32_t* max_probes,
                    int32_t* max_list) {
   g_err[0] = '\0';

@@ -122,17 +122,24 @@ __global__ void mol_ivf_init_kernel(const unsigned short* __restrict__ x16, int 
   cent[i] = h2f(x16[((int64_t)m * S + l) * d + dd]);
 }
 
-// assign[m][p] = argmax_l <x_p, c_l> (fp32, dims in order; ties to the lower l).  Block: 256 points of one group; the centroids
-// pass through LDS in chunks (every lane reads the same centroid: broadcast).
-template <int D>
-__global__ __launch_bounds__(256) void mol_ivf_assign_kernel(Src src, int64_t n, const float* __restrict__ cent, int nlist,
-                                                             int32_t* __restrict__ assign) {
+// key of one inserted entry of a list edit: (list, position) order, the row of the edit's source in the low bits (positions are unique, so
+// the row never decides an order)
+constexpr int kEditMax = 16384;        // inserted entries per list edit: one rails_sort_rows_i64 row
+__device__ __forceinline__ int64_t edit_key(int list, int64_t pos, int row) { return ((int64_t)list << 45) | ((pos & 0x7fffffffLL) << 14) | (int64_t)row; }
+
+// argmax_l <x_p, c_l> (fp32, dims in order; ties to the lower l) of 256 points of one group per block; the centroids pass through LDS in
+// chunks (every lane reads the same centroid: broadcast).  One body, two addressing modes: point p is item p of `src` and its list goes
+// to assign[m][p]; or (kIndexed) point p is entry p of a list edit -- item pos[p] of the fp32-format index `src` (src_in_place) or its
+// item p -- and edit_key(list, pos[p], p) goes to keys[m][p].
+template <int D, bool kIndexed>
+__device__ __forceinline__ void ivf_assign_body(const Src& src, int64_t n, const float* __restrict__ cent, int nlist, int32_t* __restrict__ assign,
+                                                int src_in_place, const int64_t* __restrict__ pos, int64_t* __restrict__ keys) {
   constexpr int kChunk = 8192 / D;
   __shared__ float4 sc[kChunk * D / 4];
   const int m = blockIdx.y;
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   float x[D];
-  if (p < n) load_point<D>(src, m, n, p, x);
+  if (p < n) load_point<D>(src, m, n, kIndexed && src_in_place ? pos[p] : p, x);
   else
     for (int j = 0; j < D; ++j) x[j] = 0.0f;
   float best = -INFINITY;
@@ -156,7 +163,22 @@ __global__ __launch_bounds__(256) void mol_ivf_assign_kernel(Src src, int64_t n,
       if (acc > best) { best = acc; arg = l0 + c; }
     }
   }
-  if (p < n) assign[(int64_t)m * n + p] = arg;
+  if (p < n) {
+    if (kIndexed) keys[(int64_t)m * n + p] = edit_key(arg, pos[p], (int)p);
+    else assign[(int64_t)m * n + p] = arg;
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void mol_ivf_assign_kernel(Src src, int64_t n, const float* __restrict__ cent, int nlist,
+                                                             int32_t* __restrict__ assign) {
+  ivf_assign_body<D, false>(src, n, cent, nlist, assign, 1, nullptr, nullptr);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void mol_ivf_assign_indexed_kernel(Src src, int src_in_place, const int64_t* __restrict__ pos, int64_t m_ins,
+                                                                     const float* __restrict__ cent, int nlist, int64_t* __restrict__ keys) {
+  ivf_assign_body<D, true>(src, m_ins, cent, nlist, nullptr, src_in_place, pos, keys);
 }
 
 // hist[m][l][t] = #{items of tile t in list l}
@@ -308,6 +330,154 @@ __global__ __launch_bounds__(256) void mol_ivf_finish_kernel(float* __restrict__
     if (lane < d) r[lane] = a * inv;
     if (lane + 64 < d) r[lane + 64] = b * inv;
   }
+}
+
+// ---- list edit kernels (frozen centroids) ------------------------------------------------------------------------------------------
+// The lists after an edit = the kept old entries and the inserted ones, merged in (list, position) order.  A kept old slot s moves to
+// K[s] + (inserted entries before it); sorted inserted entry j goes to j + K[s*], s* its lower bound among the old slots of its list.
+
+// number of keys[0..m) below `key` (keys ascending)
+__device__ __forceinline__ int keys_below(const int64_t* __restrict__ keys, int m, int64_t key) {
+  int lo = 0, hi = m;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// an old entry stays: its position is below n_lim = min(n_old, n_keep) and is not replaced by the edit
+__device__ __forceinline__ bool edit_kept(int p, int64_t n_lim, const unsigned char* __restrict__ drop) { return p >= 0 && p < n_lim && drop[p] == 0; }
+
+// drop[p] = 1 for the edit's positions inside the old corpus (drop is zeroed before)
+__global__ void mol_ivf_edit_mask_kernel(const int64_t* __restrict__ pos, int m, int64_t n_old, unsigned char* __restrict__ drop) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const int64_t p = pos[j];
+  if (p >= 0 && p < n_old) drop[p] = 1;
+}
+
+// counts[g][t] = kept slots of tile t (kSortTile old slots) of group g
+__global__ __launch_bounds__(256) void mol_ivf_edit_count_kernel(const int32_t* __restrict__ old_pos, int64_t n_old, int64_t n_lim,
+                                                                 const unsigned char* __restrict__ drop, int tiles, int32_t* __restrict__ counts) {
+  __shared__ int wsum[4];
+  const int g = blockIdx.y, t = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t lo = (int64_t)t * kSortTile, hi = min(n_old, lo + kSortTile);
+  int c = 0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) c += edit_kept(old_pos[(int64_t)g * n_old + i], n_lim, drop) ? 1 : 0;
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) wsum[wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) counts[(int64_t)g * tiles + t] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// K[g][s] = kept slots of group g before old slot s (s <= n_old), from the tiles' exclusive prefix sums `base`
+__global__ __launch_bounds__(256) void mol_ivf_edit_scan_kernel(const int32_t* __restrict__ old_pos, int64_t n_old, int64_t n_lim,
+                                                                const unsigned char* __restrict__ drop, int tiles, const int32_t* __restrict__ base,
+                                                                int32_t* __restrict__ K) {
+  __shared__ int wcount[4];
+  const int g = blockIdx.y, t = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t lo = (int64_t)t * kSortTile, hi = min(n_old, lo + kSortTile);
+  int32_t* Kg = K + (int64_t)g * (n_old + 1);
+  int carry = base[(int64_t)g * tiles + t];
+  for (int64_t i0 = lo; i0 < hi; i0 += 256) {          // (uniform trip count: lo and hi are the block's)
+    const int64_t i = i0 + threadIdx.x;
+    const bool kept = i < hi && edit_kept(old_pos[(int64_t)g * n_old + i], n_lim, drop);
+    const unsigned long long b = __ballot(kept);
+    __syncthreads();
+    if (lane == 0) wcount[wave] = (int)__popcll(b);
+    __syncthreads();
+    int before = (int)__popcll(b & ((1ull << lane) - 1ull)), total = 0;
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) before += wcount[w];
+      total += wcount[w];
+    }
+    if (i < hi) Kg[i] = carry + before;
+    carry += total;
+  }
+  if (t == tiles - 1 && threadIdx.x == 0) Kg[n_old] = carry;
+}
+
+// Move: block = 256 old slots of one group.  Every kept slot finds its list (the last l with old_off[l] <= s) and its new slot, writes
+// its position there; then the block copies the vectors 16 bytes per lane.
+template <int D>
+__global__ __launch_bounds__(256) void mol_ivf_edit_move_kernel(const unsigned short* __restrict__ old_vec, const int32_t* __restrict__ old_pos,
+                                                                const int32_t* __restrict__ old_off, int64_t n_old, int64_t n_lim, int nlist,
+                                                                const unsigned char* __restrict__ drop, const int32_t* __restrict__ K,
+                                                                const int64_t* __restrict__ keys, int m_ins, unsigned short* __restrict__ new_vec,
+                                                                int32_t* __restrict__ new_pos, int64_t n_new) {
+  __shared__ int dst[256];
+  const int g = blockIdx.y;
+  const int64_t s0 = (int64_t)blockIdx.x * 256, s = s0 + threadIdx.x;
+  int to = -1;
+  if (s < n_old) {
+    const int p = old_pos[(int64_t)g * n_old + s];
+    if (edit_kept(p, n_lim, drop)) {
+      const int32_t* off = old_off + (int64_t)g * (nlist + 1);
+      int lo = 0, hi = nlist;                           // off[lo] <= s < off[hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= s) lo = mid;
+        else hi = mid;
+      }
+      const int64_t t = (int64_t)K[(int64_t)g * (n_old + 1) + s] + keys_below(keys + (int64_t)g * m_ins, m_ins, edit_key(lo, p, 0));
+      if (t < n_new) {                                  // (always, for the n_new of the header's formula)
+        to = (int)t;
+        new_pos[(int64_t)g * n_new + t] = p;
+      }
+    }
+  }
+  dst[threadIdx.x] = to;
+  __syncthreads();
+  constexpr int C = D / 8;
+  const uint4* src = reinterpret_cast<const uint4*>(old_vec) + ((int64_t)g * n_old + s0) * C;
+  uint4* out = reinterpret_cast<uint4*>(new_vec) + (int64_t)g * n_new * C;
+  for (int i = threadIdx.x; i < 256 * C; i += 256) {
+    const int r = i / C, c = i - r * C;
+    if (dst[r] >= 0) out[(int64_t)dst[r] * C + c] = src[(int64_t)r * C + c];
+  }
+}
+
+// Insert: one lane per sorted inserted entry (list, position, row): its position and its fp16 vector, cut from the fp32-format index
+// `src` (item `position` when src_in_place, else item `row`), at slot j + K[s*].
+template <int D>
+__global__ __launch_bounds__(256) void mol_ivf_edit_insert_kernel(const float* __restrict__ src, int src_in_place, int PQ, int PX,
+                                                                  const int64_t* __restrict__ keys, int m_ins, const int32_t* __restrict__ old_pos,
+                                                                  const int32_t* __restrict__ old_off, int64_t n_old, int nlist,
+                                                                  const int32_t* __restrict__ K, unsigned short* __restrict__ new_vec,
+                                                                  int32_t* __restrict__ new_pos, int64_t n_new) {
+  const int g = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= m_ins) return;
+  const int64_t key = keys[(int64_t)g * m_ins + j];
+  const int l = (int)(key >> 45), row = (int)(key & (kEditMax - 1));
+  const int p = (int)((key >> 14) & 0x7fffffffLL);
+  if (l < 0 || l >= nlist) return;
+  const int32_t* off = old_off + (int64_t)g * (nlist + 1);
+  int64_t lo = max(0, off[l]), hi = min(n_old, (int64_t)off[l + 1]);
+  while (lo < hi) {                                     // old positions ascend inside a list, dropped entries included
+    const int64_t mid = (lo + hi) >> 1;
+    if (old_pos[(int64_t)g * n_old + mid] < p) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t t = (int64_t)j + K[(int64_t)g * (n_old + 1) + lo];
+  if (t >= n_new) return;                               // (never, for the n_new of the header's formula)
+  new_pos[(int64_t)g * n_new + t] = p;
+  const int64_t item = src_in_place ? p : row;
+  uint2* out = reinterpret_cast<uint2*>(new_vec + ((int64_t)g * n_new + t) * D);
+#pragma unroll
+  for (int q = 0; q < D / 4; ++q) out[q] = index_quad16(src, item, PQ, PX, D, g, q);
+}
+
+// new_off[g][l] = kept slots before old list l + inserted entries of lower lists; new_off[g][nlist] = n_new
+__global__ void mol_ivf_edit_offsets_kernel(const int32_t* __restrict__ old_off, int nlist, int G, int64_t n_old, const int32_t* __restrict__ K,
+                                            const int64_t* __restrict__ keys, int m_ins, int64_t n_new, int32_t* __restrict__ new_off) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= G * (nlist + 1)) return;
+  const int g = i / (nlist + 1), l = i - g * (nlist + 1);
+  if (l == nlist) { new_off[i] = (int32_t)n_new; return; }
+  const int64_t s = min(n_old, (int64_t)max(0, old_off[i]));
+  new_off[i] = K[(int64_t)g * (n_old + 1) + s] + keys_below(keys + (int64_t)g * m_ins, m_ins, edit_key(l, 0, 0));
 }
 
 // ---- search kernels ------------------------------------------------------------------------------------------------------------
@@ -660,6 +830,87 @@ int ivf_build_lists(const Shape& s, const float* ipack, const void* comp16, int6
   const Src src{static_cast<const unsigned short*>(comp16), ipack, s.query_dot_product_groups, G};
   if (assign_points(src, G, n, d, cent, nlist, w.assign, st) != kOk) return kErrLaunch;
   return counting_sort(src, G, n, d, nlist, w.assign, w.hist, offsets, positions, static_cast<unsigned short*>(vectors), st);
+}
+
+// edit workspace: drop mask | keys as assigned | keys sorted | K | tile counts | the tile prefix's offsets (each 256-byte aligned)
+struct EditWs {
+  unsigned char* drop;
+  int64_t *keys_in, *keys;
+  int32_t *K, *counts, *ends;
+};
+
+static size_t edit_ws_layout(int G, int64_t n_old, int m, char* base, EditWs* w) {
+  const size_t sz[6] = {align256((size_t)n_old), align256((size_t)G * m * 8), align256((size_t)G * m * 8), align256((size_t)G * (n_old + 1) * 4),
+                        align256((size_t)G * sort_tiles(n_old) * 4), align256((size_t)G * 2 * 4)};
+  size_t o = 0;
+  char* p[6];
+  for (int i = 0; i < 6; ++i) { p[i] = base ? base + o : nullptr; o += sz[i]; }
+  if (w) {
+    w->drop = reinterpret_cast<unsigned char*>(p[0]);
+    w->keys_in = reinterpret_cast<int64_t*>(p[1]);
+    w->keys = reinterpret_cast<int64_t*>(p[2]);
+    w->K = reinterpret_cast<int32_t*>(p[3]);
+    w->counts = reinterpret_cast<int32_t*>(p[4]);
+    w->ends = reinterpret_cast<int32_t*>(p[5]);
+  }
+  return o;
+}
+
+int ivf_lists_edit_check(const Shape& s, int64_t n_old, int nlist, int64_t m) {
+  if (!d_ok(s.dot_product_dimension)) {
+    set_error("ivf_lists_edit: d = %d outside the supported dot_product_dimension in {32, 64, 128}", s.dot_product_dimension);
+    return kErrUnsupported;
+  }
+  if (nlist < 1 || nlist > kMaxNlist) { set_error("ivf_lists_edit: nlist = %d outside [1, %d]", nlist, kMaxNlist); return kErrUnsupported; }
+  if (m < 0 || m > kEditMax) { set_error("ivf_lists_edit: %lld inserted entries outside [0, %d] (rebuild the lists instead)", (long long)m, kEditMax); return kErrUnsupported; }
+  if (n_old < 1 || n_old > 0x7fffffffLL) { set_error("ivf_lists_edit: %lld old entries outside [1, 2^31)", (long long)n_old); return kErrInvalid; }
+  return kOk;
+}
+
+size_t ivf_lists_edit_workspace_bytes(const Shape& s, int64_t n_old, int m) {
+  return edit_ws_layout(s.item_dot_product_groups, n_old, m, nullptr, nullptr);
+}
+
+int ivf_lists_edit(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int m, int64_t n_keep, int nlist, const float* cent,
+                   const void* old_vectors, const int32_t* old_positions, const int32_t* old_offsets, int64_t n_old, void* new_vectors,
+                   int32_t* new_positions, int32_t* new_offsets, int64_t n_new, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int G = s.item_dot_product_groups, d = s.dot_product_dimension, PQ = s.query_dot_product_groups;
+  EditWs w;
+  if (edit_ws_layout(G, n_old, m, static_cast<char*>(ws), &w) > ws_bytes) { set_error("ivf_lists_edit: workspace too small"); return kErrNoMem; }
+  const int64_t n_lim = std::min(n_old, std::max<int64_t>(n_keep, 0));
+  const int tiles = (int)sort_tiles(n_old);
+  const unsigned short* ov = static_cast<const unsigned short*>(old_vectors);
+  unsigned short* nv = static_cast<unsigned short*>(new_vectors);
+  if (hipMemsetAsync(w.drop, 0, (size_t)n_old, st) != hipSuccess) return kErrLaunch;
+  if (m > 0) {
+    hipLaunchKernelGGL(mol_ivf_edit_mask_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, positions, m, n_old, w.drop);
+    const Src source{nullptr, src, PQ, G};
+    by_d(d, [&](auto DC) {
+      constexpr int D = decltype(DC)::value;
+      hipLaunchKernelGGL(mol_ivf_assign_indexed_kernel<D>, dim3((unsigned)((m + 255) / 256), (unsigned)G), dim3(256), 0, st, source, src_in_place, positions,
+                         (int64_t)m, cent, nlist, w.keys_in);
+      return kOk;
+    });
+    if (launch_ok() != kOk) return kErrLaunch;
+    const int r = sort_rows_i64(w.keys_in, G, m, w.keys, st);
+    if (r != kOk) return r;
+  }
+  hipLaunchKernelGGL(mol_ivf_edit_count_kernel, dim3((unsigned)tiles, (unsigned)G), dim3(256), 0, st, old_positions, n_old, n_lim, w.drop, tiles, w.counts);
+  hipLaunchKernelGGL(mol_ivf_prefix_kernel, dim3((unsigned)G), dim3(1024), 0, st, w.counts, 1, tiles, n_old, w.ends);      // one "list" per group: counts -> tile bases
+  hipLaunchKernelGGL(mol_ivf_edit_scan_kernel, dim3((unsigned)tiles, (unsigned)G), dim3(256), 0, st, old_positions, n_old, n_lim, w.drop, tiles, w.counts, w.K);
+  by_d(d, [&](auto DC) {
+    constexpr int D = decltype(DC)::value;
+    hipLaunchKernelGGL(mol_ivf_edit_move_kernel<D>, dim3((unsigned)((n_old + 255) / 256), (unsigned)G), dim3(256), 0, st, ov, old_positions, old_offsets, n_old,
+                       n_lim, nlist, w.drop, w.K, w.keys, m, nv, new_positions, n_new);
+    if (m > 0)
+      hipLaunchKernelGGL(mol_ivf_edit_insert_kernel<D>, dim3((unsigned)((m + 255) / 256), (unsigned)G), dim3(256), 0, st, src, src_in_place, PQ, G, w.keys, m,
+                         old_positions, old_offsets, n_old, nlist, w.K, nv, new_positions, n_new);
+    return kOk;
+  });
+  const int no = G * (nlist + 1);
+  hipLaunchKernelGGL(mol_ivf_edit_offsets_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, st, old_offsets, nlist, G, n_old, w.K, w.keys, m, n_new,
+                     new_offsets);
+  return launch_ok();
 }
 
 int ivf_search_check(const Shape& s, int nlist, int nprobe, int max_probes, int max_list, int k, int64_t n) {

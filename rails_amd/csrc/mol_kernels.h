@@ -194,6 +194,11 @@ int ivf_train(const Shape& s, const float* ipack, const void* comp16, int64_t n,
 int ivf_assign(const Shape& s, const float* ipack, const void* comp16, int64_t n, int nlist, const float* cent, int32_t* assign, hipStream_t st);
 int ivf_build_lists(const Shape& s, const float* ipack, const void* comp16, int64_t n, int nlist, const float* cent, void* vectors, int32_t* positions, int32_t* offsets,
                     void* ws, size_t ws_bytes, hipStream_t st);
+int ivf_lists_edit_check(const Shape& s, int64_t n_old, int nlist, int64_t m);
+size_t ivf_lists_edit_workspace_bytes(const Shape& s, int64_t n_old, int m);
+int ivf_lists_edit(const Shape& s, const float* src, int src_in_place, const int64_t* positions, int m, int64_t n_keep, int nlist, const float* cent,
+                   const void* old_vectors, const int32_t* old_positions, const int32_t* old_offsets, int64_t n_old, void* new_vectors,
+                   int32_t* new_positions, int32_t* new_offsets, int64_t n_new, void* ws, size_t ws_bytes, hipStream_t st);
 int ivf_search_check(const Shape& s, int nlist, int nprobe, int max_probes, int max_list, int k, int64_t n);
 size_t ivf_search_workspace_bytes(const Shape& s, int B, int nlist, int nprobe, int max_probes, int max_list, int k);
 int ivf_search(const Shape& s, const float* eq, int B, const float* cent, const void* vectors, const int32_t* positions, const int32_t* offsets,

@@ -747,20 +747,38 @@ class MolEngine:
         return int(self.lib.rails_mol_component_topk_capacity(C.byref(self.shape), int(batch), int(n), int(k_group)))
 
 
+def ivf_edited_size(n_old: int, n_keep: int, positions=None, *, m: Optional[int] = None, below: Optional[int] = None) -> int:
+    """Entries per group after IvfIndex.edit (include/rails_amd.h rails_ivf_lists_edit): the old lists hold each of 0 .. n_old - 1 once, so
+    n_new = min(n_old, n_keep) - #{p in positions : p < min(n_old, n_keep)} + m.  Either `positions` (unique ints: a host tensor, an array
+    or a list) or, where they live on the device, their number `m` and the count `below` of those under min(n_old, n_keep)."""
+    lim = min(int(n_old), int(n_keep))
+    if positions is not None:
+        pos = [int(p) for p in (positions.tolist() if hasattr(positions, "tolist") else positions)]
+        m, below = len(pos), sum(1 for p in pos if p < lim)
+    if m is None or below is None or not 0 <= below <= min(m, lim):
+        raise ValueError("ivf_edited_size: give positions, or m and 0 <= below <= min(m, min(n_old, n_keep))")
+    return lim - int(below) + int(m)
+
+
 class IvfIndex:
     """IVF-Flat index over the item components (include/rails_amd.h rails_ivf_*): one index per item group, trained by spherical Lloyd
     k-means on a seeded sample of the fp16-rounded components and searched in three launches -- the native counterpart of the FAISS
     branch of MoLNaiveTopK (reference rails/indexing/mol_top_k.py:176-239).  Where the probed lists hold fewer than k_per_group items the
-    search goes on into further lists in centroid-score order (FAISS returns -1 there)."""
+    search goes on into further lists in centroid-score order (FAISS returns -1 there).  edit() makes the lists follow an in-place change
+    of the corpus under FROZEN centroids (FAISS IndexIVFFlat.add / remove_ids): the centroids are never written again."""
 
     COMPONENT_CHUNK = 1 << 20     # items per temporary fp32-format index chunk where the engine's own index is in a split-f16 format
+    EDIT_MAX = 16384              # inserted entries one rails_ivf_lists_edit call takes (one rails_sort_rows_i64 row); beyond: edit() rebuilds the lists
 
     def __init__(self, engine: MolEngine, index: MolIndex, nlist: int = 100, nprobe: int = 1, iters: int = 10, seed: int = 1234,
-                 items: Optional[torch.Tensor] = None):
+                 items: Optional[torch.Tensor] = None, centroids: Optional[torch.Tensor] = None):
         """items: the raw (N, D) item embeddings; needed only where `engine` is not an fp32 engine: the fp16 components are then cut from
-        temporary fp32-format index chunks of COMPONENT_CHUNK items (the same values as the fp32 engine's), as the component table is."""
+        temporary fp32-format index chunks of COMPONENT_CHUNK items (the same values as the fp32 engine's), as the component table is.
+        centroids: a (P_X, nlist, d) fp32 tensor on the index's device -- the lists are built from a COPY of it and nothing is trained (no
+        sample, no Lloyd iterations); ValueError for another shape, dtype or device."""
         engine._fused_only("the IVF-Flat index")
         self.lib = engine.lib
+        self._engine, self._index = engine, index
         spec = engine.spec
         self.groups, self.d = spec.item_dot_product_groups, spec.dot_product_dimension
         self.query_groups = spec.query_dot_product_groups
@@ -774,43 +792,115 @@ class IvfIndex:
         if n < self.nlist:
             raise ValueError(f"IvfIndex: {n} items cannot fill nlist = {self.nlist} lists")
         G, d = self.groups, self.d
-        src_index, comp16 = index.buf, None
-        if engine.precision != "fp32":
-            if items is None:
-                raise ValueError("IvfIndex: a non-fp32 engine needs the raw item embeddings to cut the fp32 components from")
-            items = _f32c(items)
-            comp16 = torch.empty((G, n, d), dtype=torch.float16, device=dev)
-            chunk = self.COMPONENT_CHUNK
-            tmp = torch.empty(self.lib.rails_mol_index_floats(C.byref(shape), min(chunk, n)), dtype=torch.float32, device=dev)
-            with _on_device(dev):
-                for lo in range(0, n, chunk):
-                    m = min(chunk, n - lo)
-                    _lib.check(self.lib.rails_mol_index_build(C.byref(shape), C.byref(engine.weights), _ptr(items[lo : lo + m]), m, _ptr(tmp), _stream()),
-                               "rails_mol_index_build")
-                    _lib.check(self.lib.rails_ivf_components16_build(C.byref(shape), _ptr(tmp), m, _ptr(comp16), n, lo, _stream()),
-                               "rails_ivf_components16_build")
-            del tmp
-            src_index = None
-        # the sample: a seeded permutation of the items, its first min(N, 256 nlist); the first nlist of it start the centroids
-        gen = torch.Generator().manual_seed(int(seed))
-        n_sample = min(n, 256 * self.nlist)
-        sample = torch.randperm(n, generator=gen)[:n_sample].to(torch.int32).to(dev)
-        self._centroids = torch.empty((G, self.nlist, d), dtype=torch.float32, device=dev)
+        if centroids is not None:
+            if (not torch.is_tensor(centroids) or tuple(centroids.shape) != (G, self.nlist, d) or centroids.dtype != torch.float32
+                    or centroids.device != dev):
+                raise ValueError(f"IvfIndex: centroids must be a ({G}, {self.nlist}, {d}) float32 tensor on {dev}")
+        if engine.precision != "fp32" and items is None:
+            raise ValueError("IvfIndex: a non-fp32 engine needs the raw item embeddings to cut the fp32 components from")
+        src_index, comp16 = self._source(items)
         self._vectors = torch.empty((G, n, d), dtype=torch.float16, device=dev)
         self._positions = torch.empty((G, n), dtype=torch.int32, device=dev)
         self._offsets = torch.empty((G, self.nlist + 1), dtype=torch.int32, device=dev)
-        ws = torch.empty(max(self.lib.rails_ivf_build_workspace_bytes(C.byref(shape), n, self.nlist, n_sample), 1), dtype=torch.uint8, device=dev)
-        with _on_device(dev):
-            _lib.check(self.lib.rails_ivf_train(C.byref(shape), _ptr(src_index), _ptr(comp16), n, _ptr(sample), n_sample, self.nlist, int(iters), 1,
-                                                _ptr(self._centroids), _ptr(ws), ws.numel(), _stream()), "rails_ivf_train")
-            _lib.check(self.lib.rails_ivf_build_lists(C.byref(shape), _ptr(src_index), _ptr(comp16), n, self.nlist, _ptr(self._centroids),
-                                                      _ptr(self._vectors), _ptr(self._positions), _ptr(self._offsets), _ptr(ws), ws.numel(), _stream()),
-                       "rails_ivf_build_lists")
-        del ws, comp16
+        if centroids is not None:
+            self._centroids = centroids.detach().clone(memory_format=torch.contiguous_format)
+            self._build_lists(src_index, comp16)
+        else:
+            # the sample: a seeded permutation of the items, its first min(N, 256 nlist); the first nlist of it start the centroids
+            gen = torch.Generator().manual_seed(int(seed))
+            n_sample = min(n, 256 * self.nlist)
+            sample = torch.randperm(n, generator=gen)[:n_sample].to(torch.int32).to(dev)
+            self._centroids = torch.empty((G, self.nlist, d), dtype=torch.float32, device=dev)
+            ws = torch.empty(max(self.lib.rails_ivf_build_workspace_bytes(C.byref(shape), n, self.nlist, n_sample), 1), dtype=torch.uint8, device=dev)
+            with _on_device(dev):
+                _lib.check(self.lib.rails_ivf_train(C.byref(shape), _ptr(src_index), _ptr(comp16), n, _ptr(sample), n_sample, self.nlist, int(iters), 1,
+                                                    _ptr(self._centroids), _ptr(ws), ws.numel(), _stream()), "rails_ivf_train")
+            self._build_lists(src_index, comp16, ws)
+            del ws
+        del comp16
         self._offsets_host = self._offsets.cpu().contiguous()
         self._plans: Dict[Tuple[int, int], Tuple[int, int]] = {}
         self._ws: Optional[torch.Tensor] = None
         self._unfilled = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _source(self, items: Optional[torch.Tensor]):
+        """What the components of the whole corpus are read from -> (fp32-format index buffer, None), or on a split-f16 engine (None, the
+        (P_X, N, d) fp16 table cut from temporary fp32-format index chunks of `items`)."""
+        engine, index, shape = self._engine, self._index, self._shape
+        if engine.precision == "fp32":
+            return index.buf, None
+        n, dev = index.n_items, index.buf.device
+        items = _f32c(items)
+        comp16 = torch.empty((self.groups, n, self.d), dtype=torch.float16, device=dev)
+        chunk = self.COMPONENT_CHUNK
+        tmp = torch.empty(self.lib.rails_mol_index_floats(C.byref(shape), min(chunk, n)), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            for lo in range(0, n, chunk):
+                m = min(chunk, n - lo)
+                _lib.check(self.lib.rails_mol_index_build(C.byref(shape), C.byref(engine.weights), _ptr(items[lo : lo + m]), m, _ptr(tmp), _stream()),
+                           "rails_mol_index_build")
+                _lib.check(self.lib.rails_ivf_components16_build(C.byref(shape), _ptr(tmp), m, _ptr(comp16), n, lo, _stream()),
+                           "rails_ivf_components16_build")
+        return None, comp16
+
+    def _build_lists(self, src_index, comp16, ws: Optional[torch.Tensor] = None) -> None:
+        """vectors / positions / offsets (allocated for n items) of the n items of the source, by the centroids held."""
+        n, dev = self._positions.shape[1], self._centroids.device
+        if ws is None:
+            ws = torch.empty(max(self.lib.rails_ivf_build_workspace_bytes(C.byref(self._shape), n, self.nlist, 0), 1), dtype=torch.uint8, device=dev)
+        with _on_device(dev):
+            _lib.check(self.lib.rails_ivf_build_lists(C.byref(self._shape), _ptr(src_index), _ptr(comp16), n, self.nlist, _ptr(self._centroids),
+                                                      _ptr(self._vectors), _ptr(self._positions), _ptr(self._offsets), _ptr(ws), ws.numel(), _stream()),
+                       "rails_ivf_build_lists")
+
+    def edit(self, positions: torch.Tensor, source: Optional[Tuple[torch.Tensor, int]], n_keep: int, items: Optional[torch.Tensor] = None) -> None:
+        """The lists follow an in-place change of the corpus; the centroids stay bit for bit what they were.  Every old entry whose position
+        is >= n_keep or in `positions` ((M,) int64 on the device, unique, may be empty) is dropped; one entry per element of `positions` is
+        inserted -- its list by the assignment kernel's own body against the frozen centroids, its fp16 vector cut from `source`
+        (MolEngine.update_source's pair; None with M = 0).  Afterwards vectors / positions / offsets are what rails_ivf_build_lists writes
+        from the resulting corpus with these centroids.  PRECONDITION (MoLTopKModule's hooks keep it): the engine's index this object was
+        built from already holds the resulting corpus when edit() is called -- updated, grown or cut -- and `items`, needed on a split-f16
+        engine only, is the resulting raw table of as many rows.  The edit kernel reads the inserted items from it; more than EDIT_MAX
+        positions do not go through the kernel at all: the lists are rebuilt from that index (`positions`, `source` and `n_keep` are then
+        not read), with the same result.  One small read-back: the number of replaced entries and the new offsets."""
+        dev = self._centroids.device
+        m, n_old, n_keep = int(positions.numel()), self.n_items, int(n_keep)
+        lim = min(n_old, n_keep)
+        if m and (positions.dtype != torch.int64 or positions.dim() != 1 or positions.device != dev):
+            raise ValueError(f"IvfIndex.edit: positions must be an (M,) int64 tensor on {dev}")
+        if m > self.EDIT_MAX:
+            n_new = self._index.n_items
+            if n_new < self.nlist:
+                raise ValueError(f"IvfIndex: {n_new} items cannot fill nlist = {self.nlist} lists")
+            if self._engine.precision != "fp32" and items is None:
+                raise ValueError("IvfIndex.edit: a non-fp32 engine needs the raw item embeddings to rebuild the lists from")
+            src_index, comp16 = self._source(items)
+            self._vectors = self._positions = None      # (freed before the new ones are allocated)
+            self._vectors = torch.empty((self.groups, n_new, self.d), dtype=torch.float16, device=dev)
+            self._positions = torch.empty((self.groups, n_new), dtype=torch.int32, device=dev)
+            self._build_lists(src_index, comp16)
+        else:
+            positions = positions.contiguous()
+            n_new = ivf_edited_size(n_old, n_keep, m=m, below=int((positions < lim).sum()) if m else 0)
+            if n_new < self.nlist:
+                raise ValueError(f"IvfIndex: {n_new} items cannot fill nlist = {self.nlist} lists")
+            ws_bytes = self.lib.rails_ivf_lists_edit_workspace_bytes(C.byref(self._shape), n_old, self.nlist, m)
+            if ws_bytes == 0:
+                raise NotImplementedError(f"rails_ivf_lists_edit_workspace_bytes: {_lib.last_error()}")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            vectors = torch.empty((self.groups, n_new, self.d), dtype=torch.float16, device=dev)
+            pos_new = torch.empty((self.groups, n_new), dtype=torch.int32, device=dev)
+            offsets = torch.empty_like(self._offsets)
+            src, in_place = source if m else (None, 1)
+            with _on_device(dev):
+                _lib.check(self.lib.rails_ivf_lists_edit(C.byref(self._shape), _ptr(src), int(in_place), _ptr(positions) if m else None, m, n_keep, self.nlist,
+                                                         _ptr(self._centroids), _ptr(self._vectors), _ptr(self._positions), _ptr(self._offsets), n_old,
+                                                         _ptr(vectors), _ptr(pos_new), _ptr(offsets), n_new, _ptr(ws), ws.numel(), _stream()),
+                           "rails_ivf_lists_edit")
+            self._vectors, self._positions, self._offsets = vectors, pos_new, offsets
+        self.n_items = n_new
+        self._offsets_host = self._offsets.cpu().contiguous()
+        self._plans.clear()
 
     # read-only views of the index (tests and tools)
     centroids = property(lambda self: self._centroids, doc="(P_X, nlist, d) fp32 unit-norm centroids")

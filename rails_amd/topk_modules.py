@@ -2073,14 +2073,24 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
     """Reference rails/indexing/mol_top_k.py:133-293.  Returns (B, P_Q * P_X * k_per_group) columns whatever `k` is, as the reference does.
     use_faiss=True (the reference's FAISS-GPU branch, :176-239): the per-group candidates come from a native IVF-Flat index
     (engine.IvfIndex) built at the first call -- nlist lists per item group, nprobe of them searched per query component -- instead of the
-    exhaustive component scan; nlist / nprobe / iters / seed (keyword-only, not in the reference's signature) default to FAISS's values."""
+    exhaustive component scan; nlist / nprobe / iters / seed (keyword-only, not in the reference's signature) default to FAISS's values.
+    ivf_centroids: a (P_X, nlist, d) fp32 tensor on the module's device -- the index is built from a copy of it, nothing is trained.
+    frozen_centroids=True (use_faiss=True only) opts in to the in-place corpus API: update_items / append_items /
+    remove_items and the by-id calls edit the lists under the centroids the index has, which are never written again -- as FAISS's
+    IndexIVFFlat.add / remove_ids.  The contract is NOT "equals a freshly constructed module" (a fresh module trains new centroids): after any
+    sequence of calls the lists are bit for bit what rails_ivf_build_lists writes from the resulting table with THOSE centroids.  Recall may
+    drift as the corpus moves away from them: watch ivf_index().list_sizes(), and construct the module again to retrain."""
 
     def __init__(self, mol_module: MoLSimilarity, item_embeddings: torch.Tensor, item_ids: torch.Tensor, k_per_group: int, use_faiss: bool = False,
-                 *, nlist: int = 100, nprobe: int = 1, iters: int = 10, seed: int = 1234) -> None:
+                 *, nlist: int = 100, nprobe: int = 1, iters: int = 10, seed: int = 1234, frozen_centroids: bool = False,
+                 ivf_centroids: Optional[torch.Tensor] = None) -> None:
         _refuse_generic_route(mol_module, type(self).__name__)
         super().__init__(mol_module=mol_module, item_embeddings=item_embeddings, item_ids=item_ids)
         self._k_per_group: int = k_per_group
         self._use_faiss: bool = bool(use_faiss)
+        self._frozen_centroids: bool = bool(frozen_centroids)
+        if self._frozen_centroids and not self._use_faiss:
+            raise ValueError("MoLNaiveTopK: frozen_centroids=True applies to the IVF index of use_faiss=True only")
         self._ivf_args = dict(nlist=int(nlist), nprobe=int(nprobe), iters=int(iters), seed=int(seed))
         self.nprobe: int = int(nprobe)      # lists searched per query component; may be changed between calls (the index stays)
         self._ivf: Optional[E.IvfIndex] = None
@@ -2097,11 +2107,45 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
                 raise NotImplementedError(f"MoLNaiveTopK: use_faiss=True takes dot_product_dimension in {{32, 64, 128}}, got {mol_module._dot_product_dimension}")
             if self.num_items < self._ivf_args["nlist"]:
                 raise ValueError(f"MoLNaiveTopK: {self.num_items} items cannot fill nlist = {nlist} lists")
+        if ivf_centroids is not None:
+            want = (mol_module._item_dot_product_groups, self._ivf_args["nlist"], mol_module._dot_product_dimension)
+            if (not torch.is_tensor(ivf_centroids) or tuple(ivf_centroids.shape) != want or ivf_centroids.dtype != torch.float32
+                    or ivf_centroids.device != item_embeddings.device):
+                raise ValueError(f"MoLNaiveTopK: ivf_centroids must be a {want} float32 tensor on {item_embeddings.device}")
+            self._ivf_args["centroids"] = ivf_centroids.detach().clone()      # (the caller's tensor is never aliased)
 
     def _check_updatable(self, what: str) -> None:
-        if self._use_faiss:
+        if self._use_faiss and not self._frozen_centroids:
             raise NotImplementedError(f"MoLNaiveTopK.{what}: the IVF index (use_faiss=True) is trained on the corpus -- its lists and centroids do not follow "
-                                      "an in-place change; construct the module again")
+                                      "an in-place change; construct the module again (or with frozen_centroids=True: the lists then follow under the "
+                                      "centroids the index has)")
+
+    # ---- in-place corpus changes under frozen centroids: the lists of a held index follow, behind the base class's buffers ----------------
+    def _ivf_held(self, eng) -> Optional[E.IvfIndex]:
+        return self._ivf if self._ivf is not None and self._ivf_engine is eng else None
+
+    def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
+        if self._use_faiss and self._frozen_centroids and torch.is_tensor(positions) and positions.dim() == 1:
+            left = self.num_items - positions.numel()
+            if 0 < left < self._ivf_args["nlist"]:      # (the constructor's refusal, before anything is touched; left < 1 is removal_plan's)
+                raise ValueError(f"MoLNaiveTopK: {left} items cannot fill nlist = {self._ivf_args['nlist']} lists")
+        return super().remove_items(positions)
+
+    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        super()._refresh(eng, pos, emb)
+        ivf = self._ivf_held(eng)
+        if ivf is not None:       # update: replaced in place; append: positions the old lists do not hold; remove: the holes
+            ivf.edit(pos, self._table_source(eng, emb), n_keep=self.num_items, items=self._item_embeddings[0])
+
+    def _shrink(self, eng, n_new: int) -> None:
+        super()._shrink(eng, n_new)
+        ivf = self._ivf_held(eng)
+        if ivf is not None:       # a pure truncation
+            ivf.edit(torch.empty(0, dtype=torch.int64, device=self._item_embeddings.device), None, n_keep=n_new)
+
+    def _drop_derived(self) -> None:
+        super()._drop_derived()
+        self._ivf = self._ivf_engine = None
 
     def ivf_index(self) -> E.IvfIndex:
         """The IVF index of use_faiss=True, built at first use and rebuilt when _bind() yields a new engine (as _component_table)."""
