@@ -192,6 +192,20 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+def resized(t: torch.Tensor, n: int, dim: int = 0, zero: bool = False) -> torch.Tensor:
+    """A fresh contiguous copy of `t` with n entries along `dim` (the one resize of the in-place corpus API): the first n when that cuts (or
+    keeps) it, else all of `t` with room behind it -- zeros where the buffer has padding a fresh build leaves zero, else unwritten (the caller
+    writes every new entry)."""
+    old = t.shape[dim]
+    if n <= old:
+        return t.narrow(dim, 0, n).clone(memory_format=torch.contiguous_format)
+    shape = list(t.shape)
+    shape[dim] = n
+    out = (torch.zeros if zero else torch.empty)(shape, dtype=t.dtype, device=t.device)
+    out.narrow(dim, 0, old).copy_(t)
+    return out
+
+
 class MolIndex:
     """Tile-packed item index: Ex (l2-normalised component embeddings) + gi (item gate) per item."""
 
@@ -389,22 +403,17 @@ class MolEngine:
             _lib.check(self.lib.rails_mol_component_update(C.byref(self._fp32_shape), _ptr(source[0]), source[1], _ptr(positions), positions.numel(), _ptr(table),
                                                            table.shape[1], _stream()), "rails_mol_component_update")
 
-    def grow_index(self, index: MolIndex, n_new: int) -> None:
-        """`index` with room for n_new more items, IN PLACE (the same object: caches keyed on it stay valid): the old bytes copied, the rest zero
-        (what the padding slots of a fresh index hold).  The new slots are filled by update_index."""
-        n = index.n_items + n_new
-        buf = torch.zeros(self._fn("index_floats")(C.byref(self.shape), n), dtype=torch.float32, device=index.buf.device)
-        buf[: index.buf.numel()].copy_(index.buf)
-        index.buf, index.n_items = buf, n
-
-    def shrink_index(self, index: MolIndex, n_items: int) -> None:
-        """`index` cut to its first n_items items, IN PLACE (the same object, as grow_index): a buffer of index_floats(n_items) with the whole tiles
-        copied and the slots past n_items of the new last tile zero (rails_mol_index_clear_tail) -- the bytes of a fresh build of those items."""
-        if not 0 < n_items <= index.n_items:
-            raise ValueError(f"shrink_index: {n_items} items outside (0, {index.n_items}]")
-        buf = index.buf[: self._fn("index_floats")(C.byref(self.shape), n_items)].clone()
-        with _on_device(buf.device):
-            _lib.check(self._fn("index_clear_tail")(C.byref(self.shape), _ptr(buf), n_items, _stream()), self._name("index_clear_tail"))
+    def resize_index(self, index: MolIndex, n_items: int) -> None:
+        """`index` resized to n_items items, IN PLACE (the same object: caches keyed on it stay valid): a buffer of index_floats(n_items) with the
+        whole tiles copied and zeros beyond them (what the padding slots of a fresh index hold); cut, the slots past n_items of the new last
+        tile are set to zero (rails_mol_index_clear_tail).  New slots are filled by update_index."""
+        if n_items < 1:
+            raise ValueError(f"resize_index: {n_items} items")
+        shrinking = n_items < index.n_items
+        buf = resized(index.buf, self._fn("index_floats")(C.byref(self.shape), n_items), zero=True)
+        if shrinking:
+            with _on_device(buf.device):
+                _lib.check(self._fn("index_clear_tail")(C.byref(self.shape), _ptr(buf), n_items, _stream()), self._name("index_clear_tail"))
         index.buf, index.n_items = buf, n_items
 
     def score_indexed_rows(self, qpack: torch.Tensor, batch: int, rows: torch.Tensor, n_items: int, positions: torch.Tensor,
@@ -1021,22 +1030,18 @@ class MipsIndex:
                        "rails_mips_index_gather_rows")
         return out
 
-    def grow(self, m: int) -> None:
-        """Room for m more items: the old bytes copied, the rest zero (the padding of a fresh index); the new slots are filled by update()."""
-        n = self.n_items + m
-        buf = torch.zeros(_lib.load().rails_mips_index_floats(self.dim, n), dtype=torch.float32, device=self.buf.device)
-        buf[: self.buf.numel()].copy_(self.buf)
-        self.buf, self.n_items = buf, n
-
-    def shrink(self, n_new: int) -> None:
-        """Cut to the first n_new items: whole tiles copied, the slots past n_new of the new last tile zero (rails_mips_index_clear_tail)."""
-        if not 0 < n_new <= self.n_items:
-            raise ValueError(f"shrink: {n_new} items outside (0, {self.n_items}]")
+    def resize(self, n_items: int) -> None:
+        """To n_items items, as MolEngine.resize_index: whole tiles copied, zeros beyond them; cut, the slots past n_items of the new last tile
+        are set to zero (rails_mips_index_clear_tail).  New slots are filled by update()."""
+        if n_items < 1:
+            raise ValueError(f"resize: {n_items} items")
         lib = _lib.load()
-        buf = self.buf[: lib.rails_mips_index_floats(self.dim, n_new)].clone()
-        with _on_device(buf.device):
-            _lib.check(lib.rails_mips_index_clear_tail(_ptr(buf), n_new, self.dim, _stream()), "rails_mips_index_clear_tail")
-        self.buf, self.n_items = buf, n_new
+        shrinking = n_items < self.n_items
+        buf = resized(self.buf, lib.rails_mips_index_floats(self.dim, n_items), zero=True)
+        if shrinking:
+            with _on_device(buf.device):
+                _lib.check(lib.rails_mips_index_clear_tail(_ptr(buf), n_items, self.dim, _stream()), "rails_mips_index_clear_tail")
+        self.buf, self.n_items = buf, n_items
 
     def score(self, q: torch.Tensor) -> torch.Tensor:
         """(B, D) -> (B, N) fp32 dot products (reference rails/indexing/mips_top_k.py:72)."""

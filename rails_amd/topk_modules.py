@@ -14,7 +14,7 @@ fused scoring -> exact top-k -> id gather, all HIP.
 from __future__ import annotations
 
 import abc
-from typing import Dict, NamedTuple, Optional, Tuple
+from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import math
 
@@ -236,7 +236,158 @@ class _ItemsById:
             self._id_map = None
 
 
-class MoLTopKModule(_ItemsById, TopKModule):
+IN_PLACE, CONCATENATED, CUT_AND_FILLED = "in place", "concatenated", "cut and filled"
+
+
+class CorpusEdit(NamedTuple):
+    """One in-place change of the corpus -- what update_items / append_items / remove_items hand to _CorpusEdits._apply."""
+    n_new: int                                  # items afterwards
+    positions: torch.Tensor                     # (M',) int64 on the device: the positions to rewrite; ids that are inserted go to these too
+    rows: Optional[torch.Tensor]                # their raw rows; None: the rows at `movers`, read before the write
+    how: str                                    # table and ids written IN_PLACE, CONCATENATED, or CUT_AND_FILLED from `movers`
+    ids: Optional[torch.Tensor] = None          # ids to insert at `positions`; None: the ids are not edited (the movers' ids, when cut and filled)
+    gone: Optional[torch.Tensor] = None         # device positions whose ids a live id map erases first (read before the write)
+    movers: Optional[torch.Tensor] = None       # CUT_AND_FILLED: device positions, the i-th of them moves to the i-th of `positions`
+
+
+class Held(NamedTuple):
+    """One derived buffer of a module under a corpus edit: everything the edit flow knows about it.  Functions of (module, engine, ...); a
+    module class lists its own in _HELD, next to the code that builds the buffer lazily, and holds those of its bases before them."""
+    attrs: Tuple[str, ...]                      # the attributes that hold it (None = not built)
+    held: Callable[..., bool]                   # (tk, eng): built, and under this engine?  Not held: the edit leaves it alone -- unbuilt stays unbuilt
+    resize: Optional[Callable[..., None]]       # (tk, eng, n_new): to n_new items, with a fresh build's padding; new entries are written by refresh
+    refresh: Optional[Callable[..., None]]      # (tk, eng, pos, rows): the entries at device positions `pos`, whose raw rows are `rows`
+    drop: Optional[Callable[..., None]]         # (tk): the corpus size chose another engine -- nothing derived under the old one stays
+    settle: Optional[Callable[..., None]] = None    # (tk, eng): after the edit, resized or not
+
+
+class _CorpusEdits(_ItemsById):
+    """The in-place corpus API, shared by MoLTopKModule and MIPSBruteForceTopK: the three calls describe themselves as a
+    CorpusEdit and _apply is the one flow that carries it out, over the class's list of held buffers.  After any sequence of the calls the
+    module holds what a module freshly constructed from the resulting table and ids holds -- every derived buffer bit for bit -- and answers
+    alike.  All three are issued on the current stream, behind everything already enqueued there; the module's own side streams are JOINED
+    first: handles outstanding from submit() keep the results of the corpus they were submitted against.
+    A module supplies num_items, _row_format, _rows_at and _HELD; one with a raw table _write_table; one with a choice of engines _bind,
+    _engine_for_bind, _join_side_streams and _forget_corpus_choices."""
+
+    _HELD: Tuple[Held, ...] = ()
+    _upd_source = None
+
+    @classmethod
+    def _held_buffers(cls) -> Tuple[Held, ...]:
+        """Base classes' buffers first: the order of the launches (the index, its row copy, the fp32 companion and its row copy, the tables
+        with the pre-filter behind the coarse one, the IVF lists)."""
+        return tuple(h for k in reversed(cls.__mro__) for h in k.__dict__.get("_HELD", ()))
+
+    def update_items(self, positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
+        """Replace the items at `positions` ((M,) int64, CPU or device: POSITIONS 0 .. N-1 of this module's corpus, not ids; unique) by the rows of
+        `item_embeddings` ((M, D) or (1, M, D), on the module's device, the table's dtype) and, when given, their ids by `item_ids` ((M,) or
+        (1, M)).  The rows are written INTO the item table (and the ids into the id tensor) the module borrowed at construction: the caller's
+        tensors change too (a module that keeps no raw table writes the ids alone).  Every derived buffer the module holds is then brought up
+        to date at those positions only; one not built yet stays unbuilt.  ValueError before any launch for bad shapes / dtypes / positions
+        (the uniqueness check costs one device sync when the positions live on the device).  M = 0 is a no-op."""
+        self._check_updatable("update_items")
+        emb, ids = self._update_rows_arg(item_embeddings, item_ids)
+        pos = _checked_positions(positions, emb.shape[0], self.num_items)
+        if emb.shape[0]:
+            pos = pos.to(self._ids_flat.device)
+            self._apply(CorpusEdit(self.num_items, pos, emb, IN_PLACE, ids=ids, gone=None if ids is None else pos))
+
+    def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
+        """Grow the corpus from N to N + M items, the new ones at positions N .. N + M - 1.  Every held buffer is grown with device copies and the
+        new range goes through update_items' kernels: no old item is recomputed -- unless the larger corpus makes the module choose another
+        engine (the default exact mode turning proved at 16 384 items: what was derived under the old one is dropped and the new engine's
+        buffers are built from the table, as for a fresh module).  Everything a fresh module decides from N is decided again for N + M.  From
+        this call on the module OWNS its item table and ids (the caller's tensors are no longer written)."""
+        self._check_updatable("append_items")
+        emb, ids = self._update_rows_arg(item_embeddings, item_ids, appending=True)
+        n, m = self.num_items, emb.shape[0]
+        if m:
+            self._apply(CorpusEdit(n + m, torch.arange(n, n + m, dtype=torch.int64, device=self._ids_flat.device), emb, CONCATENATED, ids=ids))
+
+    def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
+        """Shrink the corpus from N to N' = N - M items: the items at `positions` ((M,) int64, CPU or device: POSITIONS, not ids; unique) go, and the
+        holes they leave below N' are filled from the tail (removal_plan: O(M) rows move, every other item keeps its position).  -> `moved`, a CPU
+        int64 tensor of rows [from, to], for callers that keep positions.  A mover's bytes at its new position are what update_items writes there;
+        every held buffer is then cut to what a fresh module of N' items holds, and everything a fresh module decides from N is decided again for
+        N' (the default exact mode turns dense below 16 384 items: the module then holds a fresh dense module's buffers and nothing more).  From
+        this call on the module OWNS its item table and ids; the caller's tensors are not written.  ValueError before anything is touched (one
+        device sync when the positions live on the device).  M = 0 is a no-op."""
+        n = self.num_items
+        self._check_updatable("remove_items", n - positions.numel() if torch.is_tensor(positions) and positions.dim() == 1 else None)
+        holes, movers, moved = _removal_arg(positions, n)
+        if positions.numel():
+            dev = self._ids_flat.device
+            self._apply(CorpusEdit(n - positions.numel(), holes.to(dev), None, CUT_AND_FILLED, gone=positions.to(dev), movers=movers.to(dev)))
+        return moved
+
+    def _apply(self, e: CorpusEdit) -> None:
+        """The one edit flow.  The ids about to be overwritten or moved are read BEFORE the write; what was decided from the corpus size is
+        forgotten BEFORE the engine for n_new items is asked for; resize comes before refresh; a removal without holes refreshes nothing."""
+        with torch.inference_mode():
+            self._join_side_streams()
+            eng = self._bind()
+            n, pos, rows, ids = self.num_items, e.positions, e.rows, e.ids
+            gone = None if e.gone is None else self._ids_at(e.gone)
+            if e.how == CUT_AND_FILLED:
+                rows, ids = self._rows_at(e.movers), self._ids_at(e.movers)
+                if ids is not None:       # (the movers' ids are erased too, and come back at the holes)
+                    gone = torch.cat([gone, ids])
+            self._write_table(e, pos, rows)
+            if e.how == CUT_AND_FILLED:
+                self._item_ids, self._ids_flat = _remove_ids(self._item_ids, self._ids_flat, e.n_new, pos, e.movers)
+            elif e.how == CONCATENATED:
+                self._item_ids, self._ids_flat = _append_ids(self._item_ids, self._ids_flat, ids)
+            elif ids is not None:
+                _write_ids(self._item_ids, self._ids_flat, pos, ids)
+            if ids is not None:
+                self._id_map_step(gone, ids, pos)
+            held, resize = self._held_buffers(), e.n_new != n
+            if resize:
+                self._forget_corpus_choices()
+            if not resize or self._engine_for_bind() is eng:
+                self._upd_source = None
+                for h in held:
+                    if resize and h.resize is not None and h.held(self, eng):
+                        h.resize(self, eng, e.n_new)
+                for h in held:
+                    if pos.numel() and h.refresh is not None and h.held(self, eng):
+                        h.refresh(self, eng, pos, rows)
+                self._upd_source = None
+            else:       # another engine for n_new items: its buffers are built from the table, as at construction
+                for h in held:
+                    if h.drop is not None:
+                        h.drop(self)
+            if resize:
+                self._bind()
+            for h in held:
+                if h.settle is not None and h.held(self, eng):
+                    h.settle(self, eng)
+
+    def _update_rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], appending: bool = False):
+        dim, dtype = self._row_format()
+        return _rows_arg(item_embeddings, item_ids, dim, dtype, self._ids_flat.device, self._item_ids.dtype, appending)
+
+    def _check_updatable(self, what: str, n_left: Optional[int] = None) -> None:
+        """The single refusal point: modules whose state cannot follow an in-place change (or a removal down to n_left items) raise here,
+        before anything is touched."""
+
+    def _write_table(self, e: CorpusEdit, pos: torch.Tensor, rows: torch.Tensor) -> None:
+        """The raw item table as the edit leaves it (a module that keeps none: nothing)."""
+
+    def _join_side_streams(self) -> None:
+        pass
+
+    def _bind(self):
+        return None
+
+    _engine_for_bind = _bind       # (no choice of engines)
+
+    def _forget_corpus_choices(self) -> None:
+        """What the module decided from the corpus size, to be decided again (subclasses that decide something)."""
+
+
+class MoLTopKModule(_CorpusEdits, TopKModule):
     """Common state of the MoL top-k modules (reference mol_top_k.py:29-81): borrows `item_embeddings`
     (1, N, D) and `item_ids` (1, N); owns the packed index."""
 
@@ -298,103 +449,26 @@ class MoLTopKModule(_ItemsById, TopKModule):
         finally:
             self._call_eng = outer
 
-    # ---- in-place corpus changes ---------------------------------------------------------------------------------
-    # After any sequence of update_items / append_items / remove_items the module holds what a module freshly constructed from the resulting table, the
-    # resulting ids and the same mol_module holds -- every derived buffer bit for bit -- and answers alike.  Per-item index values depend on
-    # the item's own row alone (one workgroup computes 32 items with one accumulator per item), so an update recomputes the changed items
-    # and nothing else: O(M) bytes per held buffer.  Whole passes over the corpus: the int8 pre-filter (one scale for the whole table:
-    # rebuilt from the updated coarse table) and the proved mode's max |gi| (metadata of the bound); append_items also copies what it grows.
-    # All three calls are issued on the current stream, behind everything already enqueued there; the module's own side streams (submit()'s, the
-    # audit's) are JOINED first: handles outstanding from submit() keep the results of the corpus they were submitted against.
-    def update_items(self, positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
-        """Replace the items at `positions` ((M,) int64, CPU or device: POSITIONS 0 .. N-1 of this module's corpus, not ids; unique) by the rows of
-        `item_embeddings` ((M, D) or (1, M, D), on the module's device, the table's dtype) and, when given, their ids by `item_ids` ((M,) or
-        (1, M)).  The rows are written INTO the item table (and the ids into the id tensor) the module borrowed at construction: the caller's
-        tensors change too.  Every derived buffer the module holds is then brought up to date at those positions only; one not built yet stays
-        unbuilt.  ValueError before any launch for bad shapes / dtypes / positions (the uniqueness check costs one device sync when the
-        positions live on the device).  M = 0 is a no-op."""
-        self._check_updatable("update_items")
-        emb, ids = self._update_rows_arg(item_embeddings, item_ids)
-        pos = _checked_positions(positions, emb.shape[0], self.num_items)
-        if emb.shape[0] == 0:
-            return
-        with torch.inference_mode():
-            self._join_side_streams()
-            eng = self._bind()
-            pos = pos.to(self._item_embeddings.device)
-            self._item_embeddings[0].index_copy_(0, pos, emb)
-            if ids is not None:
-                old = self._ids_at(pos)
-                _write_ids(self._item_ids, self._ids_flat, pos, ids)
-                self._id_map_step(old, ids, pos)
-            self._refresh(eng, pos, emb)
-            self._after_update(eng)
+    # ---- in-place corpus changes (_CorpusEdits): the raw table, and the buffers every MoL module holds ------------------------------------------
+    # Per-item index values depend on the item's own row alone (one workgroup computes 32 items with one accumulator per item), so an update
+    # recomputes the changed items and nothing else: O(M) bytes per held buffer.  Whole passes over the corpus: the int8 pre-filter (one scale
+    # for the whole table: rebuilt from the updated coarse table) and the proved mode's max |gi| (metadata of the bound); a resize also copies
+    # what it resizes.
+    def _row_format(self) -> Tuple[int, torch.dtype]:
+        return self._item_embeddings.shape[2], self._item_embeddings.dtype
 
-    def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
-        """Grow the corpus from N to N + M items, the new ones at positions N .. N + M - 1.  Every held buffer is grown with device copies and the
-        new range goes through update_items' kernels: no old item is recomputed -- unless the larger corpus makes the module choose another
-        engine (the default exact mode turning proved at 16 384 items: the split-f16 index a fresh module of N + M items holds is then built,
-        as for a fresh module).  Everything a fresh module decides from N is decided again for N + M.  From this call on the module OWNS its item
-        table and ids (the caller's tensors are no longer written)."""
-        self._check_updatable("append_items")
-        emb, ids = self._update_rows_arg(item_embeddings, item_ids, appending=True)
-        m = emb.shape[0]
-        if m == 0:
-            return
-        with torch.inference_mode():
-            self._join_side_streams()
-            eng = self._bind()
-            n, dev = self.num_items, self._item_embeddings.device
-            self._item_embeddings = torch.cat([self._item_embeddings, emb.unsqueeze(0)], dim=1)
-            self._item_ids, self._ids_flat = _append_ids(self._item_ids, self._ids_flat, ids)
-            self._id_map_step(None, ids, torch.arange(n, n + m, dtype=torch.int64, device=dev))
-            self._grow(eng, m)
-            self._refresh(eng, torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
-            self._after_append(eng)
+    def _rows_at(self, pos: torch.Tensor) -> torch.Tensor:
+        return self._item_embeddings[0].index_select(0, pos)
 
-    def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
-        """Shrink the corpus from N to N' = N - M items: the items at `positions` ((M,) int64, CPU or device: POSITIONS, not ids; unique) go, and the
-        holes they leave below N' are filled from the tail (removal_plan: O(M) rows move, every other item keeps its position).  -> `moved`, a CPU
-        int64 tensor of rows [from, to], for callers that keep positions.  A mover's bytes at its new position are what update_items writes there;
-        every held buffer is then cut to what a fresh module of N' items holds, and everything a fresh module decides from N is decided again for
-        N' (the default exact mode turns dense below 16 384 items: the module then holds a fresh dense module's buffers and nothing more).  From
-        this call on the module OWNS its item table and ids; the caller's tensors are not written.  ValueError before anything is touched (one
-        device sync when the positions live on the device).  M = 0 is a no-op."""
-        self._check_updatable("remove_items")
-        n = self.num_items
-        holes, movers, moved = _removal_arg(positions, n)
-        m = positions.numel()
-        if m == 0:
-            return moved
-        with torch.inference_mode():
-            self._join_side_streams()
-            eng = self._bind()
-            n_new, dev = n - m, self._item_embeddings.device
-            h, mv = holes.to(dev), movers.to(dev)
-            emb = self._item_embeddings[0].index_select(0, mv)
-            table = self._item_embeddings[:, :n_new].clone()
-            table[0].index_copy_(0, h, emb)
-            gone, moving = self._ids_at(positions.to(dev)), self._ids_at(mv)
-            self._item_ids, self._ids_flat = _remove_ids(self._item_ids, self._ids_flat, n_new, h, mv)
-            if gone is not None:
-                self._id_map_step(torch.cat([gone, moving]), moving, h)
+    def _write_table(self, e: CorpusEdit, pos: torch.Tensor, rows: torch.Tensor) -> None:
+        if e.how == IN_PLACE:
+            self._item_embeddings[0].index_copy_(0, pos, rows)
+        elif e.how == CONCATENATED:
+            self._item_embeddings = torch.cat([self._item_embeddings, rows.unsqueeze(0)], dim=1)
+        else:
+            table = self._item_embeddings[:, : e.n_new].clone()
+            table[0].index_copy_(0, pos, rows)
             self._item_embeddings = table
-            self._forget_corpus_choices()
-            if self._engine_for_bind() is eng:
-                self._shrink(eng, n_new)
-                if holes.numel():
-                    self._refresh(eng, h, emb)
-            else:       # another engine for N' items: its buffers are built from the table, as at construction
-                self._drop_derived()
-            self._after_remove(eng)
-        return moved
-
-    def _check_updatable(self, what: str) -> None:
-        """Modules whose state cannot follow an in-place change refuse here, before anything is touched."""
-
-    def _update_rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], appending: bool = False):
-        table = self._item_embeddings
-        return _rows_arg(item_embeddings, item_ids, table.shape[2], table.dtype, table.device, self._item_ids.dtype, appending)
 
     def _join_side_streams(self) -> None:
         if not self._item_embeddings.is_cuda:
@@ -404,62 +478,33 @@ class MoLTopKModule(_ItemsById, TopKModule):
             if side is not None:
                 cur.wait_stream(side)
 
-    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
-        """Every held buffer at positions `pos` (device), whose raw rows are `emb`; subclasses add theirs behind this one's."""
-        self._upd_source = None
-        eng.update_index(self._index, pos, emb)
-        c = self._rows_cache
-        if c is not None and c[0] is eng and c[1] is self._index and c[2] is not None:
-            eng.update_index_rows(self._index, c[2], pos)
-
     def _table_source(self, eng, emb: torch.Tensor):
-        """engine.update_source, once per update (the coarse and the component table share it)."""
+        """engine.update_source, once per edit (the coarse table, the component table and the IVF lists share it)."""
         if self._upd_source is None:
             self._upd_source = eng.update_source(self._index, emb)
         return self._upd_source
 
-    def _grow(self, eng, m: int) -> None:
-        """Room for m more items in every held buffer (old bytes copied; the new range is written by _refresh)."""
+    def _rows_held(self, eng) -> bool:
         c = self._rows_cache
-        held = c is not None and c[0] is eng and c[1] is self._index
-        eng.grow_index(self._index, m)
-        if held and c[2] is not None:
-            rows = torch.empty(eng.lib.rails_mol_index_rows_floats(E.C.byref(eng.shape), self._index.n_items), dtype=torch.float32, device=c[2].device)
-            rows[: c[2].numel()].copy_(c[2])
-            self._rows_cache = (eng, self._index, rows)
-        else:
-            self._rows_cache = None      # not held (or refused for its size): decided again at the next rerank, as for a fresh module
-        self._scratch.clear()            # recycled buffers sized by N
+        return c is not None and c[0] is eng and c[1] is self._index
 
-    def _shrink(self, eng, n_new: int) -> None:
-        """Every held buffer cut to n_new items, with a fresh build's padding (the holes below n_new are written by _refresh behind this)."""
-        c = self._rows_cache
-        held = c is not None and c[0] is eng and c[1] is self._index
-        eng.shrink_index(self._index, n_new)
-        if held and c[2] is not None:       # (the row-major copy has no padding: n_new whole rows)
-            self._rows_cache = (eng, self._index, c[2][: eng.lib.rails_mol_index_rows_floats(E.C.byref(eng.shape), n_new)].clone())
-        else:
-            self._rows_cache = None      # as in _grow: decided again at the next rerank
-        self._scratch.clear()            # recycled buffers sized by N
+    def _rows_resize(self, eng, n_new: int) -> None:
+        rows = self._rows_cache[2]      # None: refused for its size -- decided again at the next rerank, as for a fresh module
+        self._rows_cache = None if rows is None else (eng, self._index, E.resized(rows, eng.lib.rails_mol_index_rows_floats(E.C.byref(eng.shape), n_new)))
 
-    def _forget_corpus_choices(self) -> None:
-        """What the module decided from the corpus size, to be decided again (subclasses that decide something)."""
+    def _rows_refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        if self._rows_cache[2] is not None:
+            eng.update_index_rows(self._index, self._rows_cache[2], pos)
 
-    def _drop_derived(self) -> None:
-        """The engine changes with the corpus size: nothing derived under the old one stays (_bind builds the new engine's index from the table)."""
+    def _rows_drop(self) -> None:
         self._rows_cache = None
-        self._scratch.clear()
 
-    def _after_update(self, eng) -> None:
-        self._upd_source = None
-
-    def _after_append(self, eng) -> None:
-        self._upd_source = None
-        self._bind()
-
-    def _after_remove(self, eng) -> None:
-        self._upd_source = None
-        self._bind()
+    _HELD = (
+        Held(("_index",), lambda tk, eng: True, lambda tk, eng, n: eng.resize_index(tk._index, n),
+             lambda tk, eng, pos, emb: eng.update_index(tk._index, pos, emb), None),       # (never dropped: _bind builds the new engine's over it)
+        Held(("_rows_cache",), _rows_held, _rows_resize, _rows_refresh, _rows_drop),
+        Held(("_scratch",), lambda tk, eng: True, lambda tk, eng, n: tk._scratch.clear(), None, lambda tk: tk._scratch.clear()),   # recycled buffers sized by N
+    )
 
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus."""
@@ -517,7 +562,6 @@ class MoLTopKModule(_ItemsById, TopKModule):
 
     RERANK_ROWS_COPY_MAX_BYTES = 8 << 30     # fp32 indexes up to this size get a row-major copy for the candidate re-scoring of the rerank paths (0: never)
     _rows_cache = None
-    _upd_source = None
 
     def _index_rows(self, eng) -> Optional[torch.Tensor]:
         """The row-major copy of this module's fp32 index (rails_mol_index_rows_build), built at the first rerank; None where it does not apply
@@ -1133,61 +1177,41 @@ class MoLBruteForceTopK(MoLTopKModule):
         self.rescore_stats["kc"] = kc
         return msg, qpack32
 
-    # ---- in-place corpus changes: the proved mode's companions -----------------------------------------------------------------------
-    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
-        super()._refresh(eng, pos, emb)
-        ex = eng.exact
-        if ex is not None and self._index32 is not None and self._index32_engine is ex:
-            ex.update_index(self._index32, pos, emb)
-            if self._rows32 is not None:
-                ex.update_index_rows(self._index32, self._rows32, pos)
-        self._risk_pool = self._risk_rows = None      # (the monitored flow's probes follow the raw rows' norms: drawn again at the next call)
+    # ---- in-place corpus changes: the proved mode's companions (built in _bind) ---------------------------------------------------------
+    def _index32_held(self, eng) -> bool:
+        return eng.exact is not None and self._index32 is not None and self._index32_engine is eng.exact
 
-    def _grow(self, eng, m: int) -> None:
-        super()._grow(eng, m)
-        ex = eng.exact
-        if ex is not None and self._index32 is not None and self._index32_engine is ex:
-            ex.grow_index(self._index32, m)
-            if self._rows32 is not None:
-                rows = torch.empty(ex.lib.rails_mol_index_rows_floats(E.C.byref(ex.shape), self._index32.n_items), dtype=torch.float32, device=self._rows32.device)
-                rows[: self._rows32.numel()].copy_(self._rows32)
-                self._rows32 = rows
+    def _rows32_resize(self, eng, n_new: int) -> None:
+        self._rows32 = E.resized(self._rows32, eng.exact.lib.rails_mol_index_rows_floats(E.C.byref(eng.exact.shape), n_new))
 
-    def _after_update(self, eng) -> None:
-        """The bound's one corpus-dependent figure, GATE_GUARD / max |gi|, as a fresh module reads it at its first bind: one pass over the item-gate
-        rows of the index (N * L floats; an old maximum may have belonged to a replaced item)."""
-        super()._after_update(eng)
+    def _index32_drop(self) -> None:
+        self._index32 = self._rows32 = self._index32_engine = None      # (a fresh dense module holds neither; a proved one builds both in _bind)
+
+    def _bound_refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        """The monitored flow's probes follow the raw rows' norms: drawn again at the next call.  The bound's one corpus-dependent figure,
+        GATE_GUARD / max |gi|, as a fresh module reads it at its first bind: one pass over the item-gate rows of the index (N * L floats; an
+        old maximum may have belonged to a replaced item) -- under a policy that stands; one forgotten with the corpus size is evaluated,
+        guard and all, by the _bind() that ends the edit."""
+        self._risk_pool = self._risk_rows = None
         pol = self._policy
         if eng.exact is not None and eng.dense_precision == "f16x3" and pol.eps is not None and pol.terms is not None and math.isfinite(float(pol.terms.get("eps", math.inf))):
             pol = pol.with_guard(self._gi_abs_max())
             self._gate_guard_limit = pol.guard_limit
             self._policy = pol
 
-    def _after_append(self, eng) -> None:
-        """Proved or dense, the form of the bound, the margins: decided for N + M items as at construction (_bind: a changed choice of engine builds
-        that engine's indexes from the table, the same choice keeps the grown ones and re-reads the guard)."""
-        self._policy = BoundPolicy()
-        self._gate_guard_limit = None
-        self._probe_pool = None
-        super()._after_append(eng)
-
-    def _shrink(self, eng, n_new: int) -> None:
-        super()._shrink(eng, n_new)
-        ex = eng.exact
-        if ex is not None and self._index32 is not None and self._index32_engine is ex:
-            ex.shrink_index(self._index32, n_new)
-            if self._rows32 is not None:
-                self._rows32 = self._rows32[: ex.lib.rails_mol_index_rows_floats(E.C.byref(ex.shape), n_new)].clone()
+    _HELD = (
+        Held(("_index32",), _index32_held, lambda tk, eng, n: eng.exact.resize_index(tk._index32, n),
+             lambda tk, eng, pos, emb: eng.exact.update_index(tk._index32, pos, emb), _index32_drop),
+        Held(("_rows32",), lambda tk, eng: tk._index32_held(eng) and tk._rows32 is not None, _rows32_resize,
+             lambda tk, eng, pos, emb: eng.exact.update_index_rows(tk._index32, tk._rows32, pos), None),      # (dropped with _index32)
+        Held(("_policy", "_gate_guard_limit"), lambda tk, eng: True, None, _bound_refresh, None),
+    )
 
     def _forget_corpus_choices(self) -> None:
-        """Proved or dense, the form of the bound, the margins, max |gi|, the probes: all decided or drawn again for N' items (_bind)."""
+        """Proved or dense, the form of the bound, the margins, max |gi|, the probes: all decided or drawn again for the new size (_bind)."""
         self._policy = BoundPolicy()
         self._gate_guard_limit = None
         self._probe_pool = self._risk_pool = self._risk_rows = None
-
-    def _drop_derived(self) -> None:
-        super()._drop_derived()
-        self._index32 = self._rows32 = self._index32_engine = None      # (a fresh dense module holds neither; a proved one builds both in _bind)
 
     ROWS_COPY_MAX_BYTES = 8 << 30      # the row-major copy of the fp32 index is kept for indexes up to this size (0: never)
     _rows32 = None
@@ -1597,41 +1621,33 @@ class MoLAvgTopK(MoLTopKModule):
         return self._coarse_table
 
     # ---- in-place corpus changes: the coarse table and its int8 copy ------------------------------------------------------------------
-    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
-        super()._refresh(eng, pos, emb)
-        if self._coarse_engine is eng and self._coarse_table is not None:
-            eng.update_coarse_table(self._coarse_table, pos, self._table_source(eng, emb))
-            # the int8 copy has ONE scale for the whole table: rebuilt from the updated table (one streaming pass over N rows, the one O(N) step
-            # of an update), with its statistics and their check schedule as for a fresh table -- a copy dropped for its statistics comes back
-            self._coarse_prefilter = eng.build_coarse_prefilter(self._coarse_table) if self._coarse_table.shape[0] >= self.PREFILTER_MIN_ITEMS else None
-            self._prefilter_calls = 0
-            self._prefilter_pending = None
+    # The int8 copy has ONE scale for the whole table: rebuilt whole from the edited table (one streaming pass over N rows, the one O(N) step of
+    # an update) while N is at the threshold, dropped below it, with its statistics and their check schedule as for a fresh table -- a copy
+    # dropped for its statistics comes back.  After a removal that left no holes nothing is refreshed: the copy is then rebuilt as the edit settles.
+    def _coarse_held(self, eng) -> bool:
+        return self._coarse_engine is eng and self._coarse_table is not None
 
-    def _grow(self, eng, m: int) -> None:
-        super()._grow(eng, m)
-        self._redo_fit_memo.clear()
-        if self._coarse_engine is eng and self._coarse_table is not None:
-            old = self._coarse_table
-            table = torch.empty((old.shape[0] + m, old.shape[1]), dtype=old.dtype, device=old.device)
-            table[: old.shape[0]].copy_(old)
-            self._coarse_table = table
+    def _coarse_resize(self, eng, n_new: int) -> None:
+        self._coarse_table, self._coarse_prefilter = E.resized(self._coarse_table, n_new), None
 
-    def _shrink(self, eng, n_new: int) -> None:
-        super()._shrink(eng, n_new)
-        self._redo_fit_memo.clear()
-        if self._coarse_engine is eng and self._coarse_table is not None:
-            self._coarse_table = self._coarse_table[:n_new].clone()
-            self._coarse_prefilter = None      # one scale for the whole table: rebuilt from the shrunk table in _after_remove
+    def _coarse_refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        eng.update_coarse_table(self._coarse_table, pos, self._table_source(eng, emb))
+        self._coarse_prefilter = None
+        self._coarse_settle(eng)
 
-    def _after_remove(self, eng) -> None:
-        super()._after_remove(eng)
-        if self._coarse_engine is eng and self._coarse_table is not None:
-            # the int8 copy as a fresh module of N' items has it: rebuilt whole while N' is still at the threshold (by _refresh where holes were
-            # filled, else here), dropped below it; statistics and their check schedule start again
-            if self._coarse_prefilter is None and self._coarse_table.shape[0] >= self.PREFILTER_MIN_ITEMS:
-                self._coarse_prefilter = eng.build_coarse_prefilter(self._coarse_table)
-            self._prefilter_calls = 0
-            self._prefilter_pending = None
+    def _coarse_settle(self, eng) -> None:
+        if self._coarse_prefilter is None and self._coarse_table.shape[0] >= self.PREFILTER_MIN_ITEMS:
+            self._coarse_prefilter = eng.build_coarse_prefilter(self._coarse_table)
+        self._prefilter_calls = 0
+        self._prefilter_pending = None
+
+    def _coarse_drop(self) -> None:
+        self._coarse_engine = self._coarse_table = self._coarse_prefilter = None
+
+    _HELD = (
+        Held(("_coarse_table", "_coarse_prefilter"), _coarse_held, _coarse_resize, _coarse_refresh, _coarse_drop, _coarse_settle),
+        Held(("_redo_fit_memo",), lambda tk, eng: True, lambda tk, eng, n: tk._redo_fit_memo.clear(), None, lambda tk: tk._redo_fit_memo.clear()),
+    )
 
     PREFILTER_MAX_FIRED = 0.35        # fraction of (tile, query tile) blocks passing the integer bound beyond which the copy is dropped
     PREFILTER_CHECK_CALLS = (2, 64)   # the header's statistics are read (16 bytes, one sync) after this many calls, then every so many
@@ -1921,24 +1937,15 @@ class _ComponentCandidates:
             self._comp_table = eng.build_component_table(self._index, self._item_embeddings[0])
         return self._comp_table
 
-    # ---- in-place corpus changes: the component table (item-group-major: one row per group and position, group stride N) -----------------
-    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
-        super()._refresh(eng, pos, emb)
-        if self._comp_engine is eng and self._comp_table is not None:
-            eng.update_component_table(self._comp_table, pos, self._table_source(eng, emb))
+    # ---- in-place corpus changes: the component table (item-group-major: one row per group and position; a resize re-lays it to group stride n_new)
+    def _comp_drop(self) -> None:
+        self._comp_engine = self._comp_table = None
 
-    def _grow(self, eng, m: int) -> None:
-        super()._grow(eng, m)
-        if self._comp_engine is eng and self._comp_table is not None:
-            old = self._comp_table
-            table = torch.empty((old.shape[0], old.shape[1] + m, old.shape[2]), dtype=old.dtype, device=old.device)
-            table[:, : old.shape[1]].copy_(old)
-            self._comp_table = table
-
-    def _shrink(self, eng, n_new: int) -> None:
-        super()._shrink(eng, n_new)
-        if self._comp_engine is eng and self._comp_table is not None:
-            self._comp_table = self._comp_table[:, :n_new].clone(memory_format=torch.contiguous_format)      # re-laid to group stride n_new
+    _HELD = (
+        Held(("_comp_table",), lambda tk, eng: tk._comp_engine is eng and tk._comp_table is not None,
+             lambda tk, eng, n: setattr(tk, "_comp_table", E.resized(tk._comp_table, n, dim=1)),
+             lambda tk, eng, pos, emb: eng.update_component_table(tk._comp_table, pos, tk._table_source(eng, emb)), _comp_drop),
+    )
 
     def _component_topk(self, eq: torch.Tensor, k_per_group: int, pending: Optional[list] = None, with_scores: bool = False):
         """-> (B, P_Q * P_X * k_per_group) positions: top k_per_group items of every (query group, item group) pair.
@@ -2114,38 +2121,26 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
                 raise ValueError(f"MoLNaiveTopK: ivf_centroids must be a {want} float32 tensor on {item_embeddings.device}")
             self._ivf_args["centroids"] = ivf_centroids.detach().clone()      # (the caller's tensor is never aliased)
 
-    def _check_updatable(self, what: str) -> None:
+    def _check_updatable(self, what: str, n_left: Optional[int] = None) -> None:
         if self._use_faiss and not self._frozen_centroids:
             raise NotImplementedError(f"MoLNaiveTopK.{what}: the IVF index (use_faiss=True) is trained on the corpus -- its lists and centroids do not follow "
                                       "an in-place change; construct the module again (or with frozen_centroids=True: the lists then follow under the "
                                       "centroids the index has)")
+        if self._use_faiss and n_left is not None and 0 < n_left < self._ivf_args["nlist"]:      # (the constructor's refusal; n_left < 1 is removal_plan's)
+            raise ValueError(f"MoLNaiveTopK: {n_left} items cannot fill nlist = {self._ivf_args['nlist']} lists")
 
-    # ---- in-place corpus changes under frozen centroids: the lists of a held index follow, behind the base class's buffers ----------------
-    def _ivf_held(self, eng) -> Optional[E.IvfIndex]:
-        return self._ivf if self._ivf is not None and self._ivf_engine is eng else None
+    # ---- in-place corpus changes under frozen centroids: the lists of a held index follow, behind every other buffer -----------------------
+    def _ivf_resize(self, eng, n_new: int) -> None:
+        if n_new < self._ivf.n_items:       # a pure truncation; growth is a no-op (refresh inserts the positions the old lists do not hold)
+            self._ivf.edit(torch.empty(0, dtype=torch.int64, device=self._item_embeddings.device), None, n_keep=n_new)
 
-    def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
-        if self._use_faiss and self._frozen_centroids and torch.is_tensor(positions) and positions.dim() == 1:
-            left = self.num_items - positions.numel()
-            if 0 < left < self._ivf_args["nlist"]:      # (the constructor's refusal, before anything is touched; left < 1 is removal_plan's)
-                raise ValueError(f"MoLNaiveTopK: {left} items cannot fill nlist = {self._ivf_args['nlist']} lists")
-        return super().remove_items(positions)
+    def _ivf_refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
+        self._ivf.edit(pos, self._table_source(eng, emb), n_keep=self.num_items, items=self._item_embeddings[0])
 
-    def _refresh(self, eng, pos: torch.Tensor, emb: torch.Tensor) -> None:
-        super()._refresh(eng, pos, emb)
-        ivf = self._ivf_held(eng)
-        if ivf is not None:       # update: replaced in place; append: positions the old lists do not hold; remove: the holes
-            ivf.edit(pos, self._table_source(eng, emb), n_keep=self.num_items, items=self._item_embeddings[0])
-
-    def _shrink(self, eng, n_new: int) -> None:
-        super()._shrink(eng, n_new)
-        ivf = self._ivf_held(eng)
-        if ivf is not None:       # a pure truncation
-            ivf.edit(torch.empty(0, dtype=torch.int64, device=self._item_embeddings.device), None, n_keep=n_new)
-
-    def _drop_derived(self) -> None:
-        super()._drop_derived()
+    def _ivf_drop(self) -> None:
         self._ivf = self._ivf_engine = None
+
+    _HELD = (Held(("_ivf",), lambda tk, eng: tk._ivf is not None and tk._ivf_engine is eng, _ivf_resize, _ivf_refresh, _ivf_drop),)
 
     def ivf_index(self) -> E.IvfIndex:
         """The IVF index of use_faiss=True, built at first use and rebuilt when _bind() yields a new engine (as _component_table)."""
@@ -2204,7 +2199,7 @@ class MIPSTopKModule(TopKModule):
         self._item_ids: torch.Tensor = item_ids
 
 
-class MIPSBruteForceTopK(_ItemsById, MIPSTopKModule):
+class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
     """Dot-product brute force (reference rails/indexing/mips_top_k.py:41-81): MFMA scan + exact top-k, all HIP."""
 
     def __init__(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
@@ -2221,68 +2216,22 @@ class MIPSBruteForceTopK(_ItemsById, MIPSTopKModule):
         scores, ids = E.topk(logits, k, ids=self._ids_flat, sorted=sorted)
         return scores.to(query_embeddings.dtype), ids
 
-    # ---- in-place corpus changes: the MoL modules' three calls, same signatures, validation and tail-fill rule ------
+    # ---- in-place corpus changes (_CorpusEdits): the MoL modules' three calls -------------------------------------------------------------
     # The module keeps the tile-packed copy and the ids only: after any sequence of the calls _index.buf and _ids_flat are what a fresh module
-    # built from the resulting table and ids holds (rails_mips_index_update stores the build's bytes at the positions; no arithmetic).  Rows
-    # are fp32 in the index whatever the table's dtype was, so a mover's row read back from it is what a fresh build would convert again.
+    # built from the resulting table and ids holds (rails_mips_index_update stores the build's bytes at the positions; no arithmetic).  There
+    # is no raw table to write (update_items writes the borrowed ids alone) and no choice of engines.  Rows are fp32 in the index whatever
+    # the table's dtype was, so a mover's row read back from it is what a fresh build would convert again.
     @property
     def num_items(self) -> int:
         return self._index.n_items
 
-    def _rows_arg(self, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor], appending: bool = False):
-        return _rows_arg(item_embeddings, item_ids, self._index.dim, self._table_dtype, self._index.buf.device, self._item_ids.dtype, appending)
+    def _row_format(self) -> Tuple[int, torch.dtype]:
+        return self._index.dim, self._table_dtype
 
-    _update_rows_arg = _rows_arg
+    def _rows_at(self, pos: torch.Tensor) -> torch.Tensor:
+        return self._index.rows(pos)
 
-    def _check_updatable(self, what: str) -> None:
-        """Nothing this module holds refuses an in-place change (MoLTopKModule._check_updatable)."""
-
-    def update_items(self, positions: torch.Tensor, item_embeddings: torch.Tensor, item_ids: Optional[torch.Tensor] = None) -> None:
-        """MoLTopKModule.update_items.  The raw table is not kept, so only the borrowed id tensor is written in place."""
-        emb, ids = self._rows_arg(item_embeddings, item_ids)
-        pos = _checked_positions(positions, emb.shape[0], self.num_items)
-        if emb.shape[0] == 0:
-            return
-        with torch.inference_mode():
-            pos = pos.to(self._index.buf.device)
-            self._index.update(pos, emb)
-            if ids is not None:
-                old = self._ids_at(pos)
-                _write_ids(self._item_ids, self._ids_flat, pos, ids)
-                self._id_map_step(old, ids, pos)
-
-    def append_items(self, item_embeddings: torch.Tensor, item_ids: torch.Tensor) -> None:
-        """MoLTopKModule.append_items: the new items at positions N .. N + M - 1; from this call on the module owns its ids."""
-        emb, ids = self._rows_arg(item_embeddings, item_ids, appending=True)
-        m = emb.shape[0]
-        if m == 0:
-            return
-        with torch.inference_mode():
-            n, dev = self.num_items, self._index.buf.device
-            self._item_ids, self._ids_flat = _append_ids(self._item_ids, self._ids_flat, ids)
-            self._id_map_step(None, ids, torch.arange(n, n + m, dtype=torch.int64, device=dev))
-            self._index.grow(m)
-            self._index.update(torch.arange(n, n + m, dtype=torch.int64, device=dev), emb)
-
-    def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
-        """MoLTopKModule.remove_items (removal_plan's rule) -> `moved`, CPU int64 rows [from, to].  The movers' rows are read back from the index."""
-        n = self.num_items
-        holes, movers, moved = _removal_arg(positions, n)
-        m = positions.numel()
-        if m == 0:
-            return moved
-        with torch.inference_mode():
-            n_new, dev = n - m, self._index.buf.device
-            h, mv = holes.to(dev), movers.to(dev)
-            rows = self._index.rows(mv)
-            gone, moving = self._ids_at(positions.to(dev)), self._ids_at(mv)
-            self._item_ids, self._ids_flat = _remove_ids(self._item_ids, self._ids_flat, n_new, h, mv)
-            if gone is not None:
-                self._id_map_step(torch.cat([gone, moving]), moving, h)
-            self._index.shrink(n_new)
-            if holes.numel():
-                self._index.update(h, rows)
-        return moved
+    _HELD = (Held(("_index",), lambda tk, eng: True, lambda tk, eng, n: tk._index.resize(n), lambda tk, eng, pos, emb: tk._index.update(pos, emb), None),)
 
 
 class CandidateIndex(object):

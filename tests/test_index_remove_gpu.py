@@ -232,13 +232,13 @@ def test_remove_before_the_first_call_and_between_submits(dev):
         U.equals_fresh(tk, make, X, ids, q, aux, "avg removal between submits")
 
 
-def mips_equals_fresh(tk, X, ids, q, what):
+def mips_equals_fresh(tk, X, ids, q, what, ks=(10, 200)):
     fresh = rails_amd.MIPSBruteForceTopK(X.clone().unsqueeze(0), ids.clone().unsqueeze(0))
     assert tk.num_items == X.shape[0]
     U.same(tk._index.buf, fresh._index.buf, f"{what}: index")
     U.same(tk._ids_flat, fresh._ids_flat, f"{what}: ids")
     out = {}
-    for k in (10, 200):
+    for k in ks:
         out[k] = tk(q, k=k)
         U.same(out[k], fresh(q, k=k), f"{what}: forward {k}")
     return out

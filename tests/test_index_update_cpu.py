@@ -78,3 +78,41 @@ def test_positions_outside_every_shard_are_ignored():
     assert local.tolist() == [2] and rows.tolist() == [4]
     local, rows = route_update_positions(torch.tensor([1, 2]), 4, 4)                 # an empty shard
     assert local.numel() == 0 and rows.numel() == 0
+
+
+HELD_READS = {      # what tests/test_index_update_gpu.py::held reads of each module class, beside the table and the ids
+    "MoLBruteForceTopK": {"_index", "_rows_cache", "_index32", "_rows32"},
+    "MoLAvgTopK": {"_index", "_rows_cache", "_coarse_table", "_coarse_prefilter"},
+    "MoLNaiveTopK": {"_index", "_rows_cache", "_comp_table"},
+    "MoLCombTopK": {"_index", "_rows_cache", "_coarse_table", "_coarse_prefilter", "_comp_table"},
+    "MIPSBruteForceTopK": {"_index"},
+}
+CORPUS = {"_item_embeddings", "_item_ids", "_ids_flat"}      # written by the edit flow itself
+
+
+def test_the_held_buffer_lists_name_what_the_gpu_tests_compare():
+    """The edit flow resizes, refreshes and drops what a class lists in _HELD and nothing else: every attribute the GPU tests' held() compares
+    with a fresh module's is named by the list of every class that has it, so a buffer added later cannot be forgotten by the flow."""
+    from unittest import mock
+
+    import rails_amd
+    from tests.test_index_update_gpu import held
+
+    class Probe:
+        def __init__(self):
+            self.read = set()
+
+        def __getattr__(self, name):
+            self.read.add(name)
+            return mock.MagicMock()
+
+    probe = Probe()
+    held(probe)
+    assert probe.read == CORPUS.union(*HELD_READS.values()), "held() reads an attribute this test does not assign to a class"
+    for name, reads in HELD_READS.items():
+        cls = getattr(rails_amd, name)
+        listed = {a for h in cls._held_buffers() for a in h.attrs}
+        assert reads <= listed, (name, sorted(reads - listed))
+    assert [h.attrs[0] for h in rails_amd.MoLCombTopK._held_buffers() if h.refresh is not None] == ["_index", "_rows_cache", "_coarse_table", "_comp_table"]
+    assert [h.attrs[0] for h in rails_amd.MoLBruteForceTopK._held_buffers() if h.refresh is not None] == ["_index", "_rows_cache", "_index32", "_rows32", "_policy"]
+    assert [h.attrs[0] for h in rails_amd.MoLNaiveTopK._held_buffers() if h.refresh is not None] == ["_index", "_rows_cache", "_comp_table", "_ivf"]

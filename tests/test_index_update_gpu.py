@@ -281,6 +281,72 @@ def test_update_before_the_first_call_and_between_calls(module, dev):
         equals_fresh(tk, make, X, ids, q, aux, f"{module} update between calls")
 
 
+SMALL_MAKERS = {      # (the MAKERS' candidate counts exceed a corpus of 61 items)
+    "brute": lambda mol, x, i: rails_amd.MoLBruteForceTopK(mol, x, i),
+    "comb": lambda mol, x, i: rails_amd.MoLCombTopK(mol, x, i, avg_top_k=16, k_per_group=1),
+    "mips": lambda mol, x, i: rails_amd.MIPSBruteForceTopK(x, i),
+}
+
+
+@pytest.mark.parametrize("module", ["brute", "comb", "mips"])
+def test_the_three_calls_and_a_by_id_call_interleaved(module, dev):
+    """One module through append_items, remove_items, upsert_items and update_items in a row -- one code path for all of them -- at sizes
+    where every tile count changes: 70 items (two full tiles and a ragged one) -> 101 -> 61 (the removal takes tail positions and cuts a tile
+    boundary) -> 67 (half of the upserted ids present, half absent; the id map is live from here on) -> the last tile updated, ids included.
+    Every derived buffer is built before the first edit (the first comparison makes every call); a fresh module after each step."""
+    from tests import test_index_remove_gpu as R      # (imports this module: not at the top)
+
+    cfg, mol, _, aux = setup_route("brute", "default", dev)
+    make = lambda x, i: SMALL_MAKERS[module](mol, x, i)      # noqa: E731
+    with torch.inference_mode():
+        if module == "mips":
+            q = (torch.randn(B, cfg.item_embedding_dim, generator=torch.Generator().manual_seed(15)) * 0.05).to(dev)
+            check = lambda what: R.mips_equals_fresh(tk, X, ids, q, what, ks=(5, 10))      # noqa: E731
+        else:
+            q = O.synthetic_queries(cfg, B, seed=15).to(dev)
+            check = lambda what: equals_fresh(tk, make, X, ids, q, aux, f"{module}: {what}", ks=(5, 10))      # noqa: E731
+        X, ids = table(cfg, 70, 61, dev), ids_of(70, dev)
+        tk = make(X.clone().unsqueeze(0), ids.clone().unsqueeze(0))
+        check("70 items as built")
+        if module == "comb":
+            assert tk._coarse_table is not None and tk._comp_table is not None and tk._rows_cache[2] is not None
+        e, ei = table(cfg, 31, 62, dev, first=1_000), ids_of(31, dev, first=70)
+        tk.append_items(e, ei)
+        X, ids = torch.cat([X, e]), torch.cat([ids, ei])
+        check("appended to 101")
+        pos = torch.cat([torch.arange(92, 101), torch.arange(0, 62, 2)])      # the last nine and every other one of the rest: 40
+        X, ids, moved = R.after_removal(X, ids, pos)
+        assert torch.equal(tk.remove_items(pos), moved) and X.shape[0] == 61
+        check("removed to 61")
+        at = torch.tensor([3, 60, 31, 32, 0, 17], device=dev)
+        absent = ids_of(6, dev, first=5_000)
+        rows = table(cfg, 12, 63, dev, first=2_000)
+        tk.upsert_items(torch.stack([ids[at], absent], dim=1).reshape(-1), rows)      # present and absent ids alternate
+        X[at] = rows[0::2]
+        X, ids = torch.cat([X, rows[1::2]]), torch.cat([ids, absent])
+        check("upserted to 67")
+        p, r, i = torch.tensor([66, 64, 65], device=dev), table(cfg, 3, 64, dev, first=3_000), ids_of(3, dev, first=9_000)
+        tk.update_items(p, r, i)
+        X[p], ids[p] = r, i
+        check("last tile updated")
+        assert torch.equal(tk.positions_of(ids), torch.arange(67, device=dev)), "the id map followed every call since the upsert"
+
+
+def test_append_over_the_engine_threshold_holds_what_a_fresh_module_holds(dev):
+    """16 380 + 8 items cross the 16 384-item rule of the default exact mode: append_items looks first, drops what it held under the dense
+    engine and builds the proved one's buffers from the table -- the set of held buffers and their bits are a fresh module's."""
+    cfg, mol, make, aux = setup_route("brute", "default", dev)
+    with torch.inference_mode():
+        full, full_ids = table(cfg, 16_388, 18, dev), ids_of(16_388, dev)
+        q = O.synthetic_queries(cfg, B, seed=16).to(dev)
+        tk = make(full[:16_380].clone().unsqueeze(0), full_ids[:16_380].clone().unsqueeze(0))
+        calls(tk, q, full_ids[:16_380], full[:16_380], aux)
+        assert tk._bind().exact is None and tk._index32 is None
+        tk.append_items(full[16_380:], full_ids[16_380:])
+        assert tk._bind().exact is not None and tk._index32 is not None
+        equals_fresh(tk, make, full, full_ids, q, aux, "16 388 items")
+
+
 def test_refusals_and_validation(dev):
     cfg, mol, make, aux = setup_route("brute", "default", dev)
     n, D = 20_000, cfg.item_embedding_dim
