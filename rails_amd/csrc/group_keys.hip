@@ -3,12 +3,13 @@
 // every row, written as THIS rank's local positions (holes elsewhere) straight into the union buffer the rerank reads.
 //   key = (order-preserving 16-bit image of the bf16 score) << 48 | (2^48 - 1 - global position)        key 0 = pad
 // A larger unsigned key is the better candidate; equal scores order by ascending global position.  The score image is rails_topk's
-// (topk.hip orderable(): u | sign bit for a clear sign, ~u for a set one) cut to the upper 16 bits of the fp32 word, so +0 > -0,
+// (topk_keys.h orderable(): u | sign bit for a clear sign, ~u for a set one) cut to the upper 16 bits of the fp32 word, so +0 > -0,
 // +inf above every finite score, a NaN with a clear sign bit above +inf, a NaN with a set sign bit below -inf -- a plain bit-pattern
 // order with no special case, exactly as rails_topk ranks the same values.  (include/rails_amd.h rails_group_keys_*)
 #include <hip/hip_runtime.h>
 
 #include "mol_kernels.h"
+#include "topk_keys.h"
 
 namespace mol {
 
@@ -66,51 +67,15 @@ __global__ __launch_bounds__(kGroupKeyThreads) void group_keys_merge_own_kernel(
     if (out_global) out_global[(int64_t)row * k + slot] = pos;
     out_local[local_base + slot] = (pos >= lo && pos < hi) ? pos - lo : (int64_t)-1;
   };
-  bool bad = false;
-  for (int i = threadIdx.x; i + 1 < count; i += kGroupKeyThreads)
-    if ((i + 1) % k != 0 && gk_keys[i] < gk_keys[i + 1]) bad = true;
-  if (bad) unsorted = 1;
-  __syncthreads();
-  if (!unsorted) {
+  if (sorted_lists_check<kGroupKeyThreads>(gk_keys, count, k, &unsorted)) {
     for (int i = threadIdx.x; i < count; i += kGroupKeyThreads) {
-      const unsigned long long kv = gk_keys[i];
-      const int r = i / k, j = i - r * k;
-      int rank = j;
-      for (int o = 0; o < R && rank < k; ++o) {
-        if (o == r) continue;
-        const unsigned long long* list = gk_keys + o * k;   // descending
-        const bool ties_first = o < r;                      // an equal key of a lower rank precedes this one
-        int a = 0, b = k;
-        while (a < b) {                                     // first index whose key does not precede kv
-          const int mid = (a + b) >> 1;
-          const unsigned long long x = list[mid];
-          if (x > kv || (ties_first && x == kv)) a = mid + 1; else b = mid;
-        }
-        rank += a;
-      }
-      if (rank < k) emit(kv, rank);
+      const int rank = sorted_lists_rank<true>(gk_keys, R, k, i, k);   // an equal key of a lower rank precedes this one
+      if (rank < k) emit(gk_keys[i], rank);
     }
     return;
   }
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (npad >> 1); t += kGroupKeyThreads) {
-        const int a = ((t & ~(stride - 1)) << 1) | (t & (stride - 1));
-        const int b = a | stride;
-        const bool desc = ((a & size) == 0);
-        const unsigned long long x = gk_keys[a], y = gk_keys[b];
-        if ((x < y) == desc) { gk_keys[a] = y; gk_keys[b] = x; }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_desc<kGroupKeyThreads>(gk_keys, npad);
   for (int j = threadIdx.x; j < k; j += kGroupKeyThreads) emit(gk_keys[j], j);
-}
-
-static int npad_of(int count) {
-  int n = 2;
-  while (n < count) n <<= 1;
-  return n;
 }
 
 }  // namespace mol
@@ -160,7 +125,7 @@ int rails_group_keys_merge_own(const uint64_t* gathered, int32_t n_ranks, int64_
     set_error("group_keys_merge_own: cannot reserve LDS");
     return kErrLaunch;
   }
-  const int npad = npad_of(n_ranks * k);
+  const int npad = next_pow2(n_ranks * k, 2);
   hipLaunchKernelGGL(group_keys_merge_own_kernel, dim3(rows), dim3(kGroupKeyThreads), npad * sizeof(unsigned long long), (hipStream_t)stream,
                      reinterpret_cast<const unsigned long long*>(gathered), n_ranks, rank_stride, k, npad, lo, hi, out_global, out_local, out_ld,
                      out_col, rows_per_out_row);

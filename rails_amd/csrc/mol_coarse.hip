@@ -14,6 +14,7 @@
 #include "mol_kernels.h"
 #include <utility>
 #include "mol_layout.h"
+#include "topk_keys.h"
 
 namespace mol {
 
@@ -111,14 +112,6 @@ struct CoarseScanArgs {
   unsigned int* counts;                 // kScanSelect: counts[b * kSubLists + sub], candidates seen (may exceed the sub-list)
   const int32_t* run_if;                // launch predicate (mol_kernels.h); set for the materialising scan only
 };
-
-__device__ __forceinline__ unsigned int coarse_orderable(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float coarse_unorderable(unsigned int k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 
 // Append path of the select scans.  A hit's slot comes from a device-scope atomic whose result takes ~2 us to return;
 // issued one by one inside the scan they serialise (a wave of the component scan met ~40 per tile: 2 ms for a 0.1 ms
@@ -248,7 +241,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
     for (int i = threadIdx.x; i < n_qt * 32; i += kScanThreads) {
       const float thr = i < B ? a.thr[((int64_t)i * groups + gm) * a.thr_stride] : INFINITY;
       thr_s[i] = thr;
-      ntlo_s[i] = -coarse_unorderable(coarse_orderable(thr) - 0x10000u);
+      ntlo_s[i] = -unorderable(orderable(thr) - 0x10000u);
     }
   __syncthreads();
   if constexpr (MODE == kScanSample) {
@@ -345,7 +338,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
             const float thr = thr_s[q];
             const float sc = bf16_rn(mine[r * 64]);   // an un-rounded sum at or above the bound may round up to thr
             if (q < B && sc >= thr) {
-              const unsigned long long key = ((unsigned long long)coarse_orderable(sc) << 32) | (unsigned int)(~(unsigned int)item);
+              const unsigned long long key = make_key(sc, (unsigned int)item);
               const unsigned int i = atomicAdd(&wg_n, 1u);   // LDS
               if (i < (unsigned int)kWgStage) { wg_stage[i].key = key; wg_stage[i].orow = (unsigned int)q; }
               else append_candidate(a.keys, a.counts, a.cap, (int)(blockIdx.x % kSubLists), (unsigned int)(q * groups + gm), key);   // list full: one by one
@@ -837,7 +830,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(kS
   for (int i = threadIdx.x; i < n_qt * DC8 * 64; i += kScanThreads) reinterpret_cast<ci32x4*>(q8)[i] = reinterpret_cast<const ci32x4*>(a.q8)[i];
   for (int i = threadIdx.x; i < n_qt * 32; i += kScanThreads) {
     const float thr = i < B ? a.thr[(int64_t)i * a.thr_stride] : INFINITY;
-    const float tlo = coarse_unorderable(coarse_orderable(thr) - 0x10000u);
+    const float tlo = unorderable(orderable(thr) - 0x10000u);
     const float s = a.hdr->scale, sq = a.qmeta[2 * i], l1 = a.qmeta[2 * i + 1];
     const float eps = 1.002f * (0.5f * s * l1 + 0.5f * sq * a.hdr->x1max + 0.75f * s * sq * (float)d);
     float bound = floorf((tlo - eps) / (s * sq)) - 2.0f;          // integer dot products below it cannot reach thr
@@ -904,7 +897,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(kS
           const float sc = bf16_rn(mine[r * 64]);
           if (q < B && sc >= thr_s[q])
             stage_push(stage_s[wave], &stage_n[wave], a.keys, a.counts, a.cap, (int)(tile % kSubLists), (unsigned int)q,
-                       ((unsigned long long)coarse_orderable(sc) << 32) | (unsigned int)(~(unsigned int)item));
+                       make_key(sc, (unsigned int)item));
         }
       }
     }

@@ -4,9 +4,8 @@
 // MoLBruteForceTopK.forward (rails/indexing/mol_top_k.py:123-130), and the row-wise masking of
 // CandidateIndex.get_top_k_outputs (indexing/candidate_index.py:154-178).
 //
-// Every score becomes a 64-bit key  (orderable(score) << 32) | ~position : all keys of a row are
-// distinct, so "the k largest keys" is a unique set and its descending order is "score descending,
-// then position ascending" -- the deterministic tie rule that makes 1/2/4/8-GPU results identical.
+// Every score becomes a 64-bit key whose descending order is "score descending, then position ascending"; the key format and the
+// in-LDS sorts of the kernels below are in topk_keys.h.
 //
 //   n <= 1024   one workgroup per row bitonic-sorts the whole row in LDS (also n <= 16384 with k > 4096).
 //   n <= 49152  (k <= 4096) row_select_kernel: one workgroup per row holds the row in registers (<= 48 scores per thread).
@@ -26,11 +25,11 @@
 #include <stdlib.h>
 
 #include "mol_kernels.h"
+#include "topk_keys.h"
 
 namespace mol {
 
 constexpr int kSortCap = 16384;       // 64-bit keys in 128 KiB of LDS
-constexpr int kSortThreads = 1024;
 constexpr int kHistThreads = 512;
 constexpr int kRadixPasses = 3;
 constexpr int kBins = 2048;
@@ -45,13 +44,6 @@ struct SelectState {       // one per row, lives in the workspace
   unsigned int pad;
 };
 
-__device__ __forceinline__ unsigned int orderable(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unorderable(unsigned int k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 // The id written for column `pos` of row `row`: ids[ids_row_stride * row + pos], the position itself without an id table, or --
 // with ids_index (the rows are candidate lists, ids_index[row][pos] the candidate's position in the corpus) -- ids[ids_index[row][pos]]
 // resp. that corpus position (torch.gather + the id lookup of rails/indexing/mol_top_k.py:379-382 inside the selection's launch).
@@ -62,123 +54,6 @@ __device__ __forceinline__ int64_t map_id(const int64_t* __restrict__ ids, int64
     return ids ? ids[ids_row_stride * row + at] : at;
   }
   return ids ? ids[ids_row_stride * row + pos] : (int64_t)pos;
-}
-__device__ __forceinline__ unsigned long long make_key(float score, unsigned int pos) {
-  return ((unsigned long long)orderable(score) << 32) | (unsigned int)(~pos);
-}
-
-// ---- block bitonic sort, one key per thread (npad <= 1024) ----------------------------------------------------
-// Thread i holds key i.  Compare-exchange partners at distance < 64 sit in the same wavefront and are exchanged with
-// ds_bpermute (no barrier); only the distances >= 64 go through LDS (one barrier each, double-buffered): 3 barriers for
-// 256 keys, 10 for 1024, against 36 / 55 barrier-separated LDS passes for the plain loop (~0.4 us each with 16 waves).
-// Returns the key of descending rank threadIdx.x.  `buf` needs 2 * npad entries; all threads of the block must call.
-__device__ __forceinline__ unsigned long long block_sort_desc(unsigned long long key, int npad, unsigned long long* buf) {
-  const int i = threadIdx.x;
-  int flip = 0;
-  for (int size = 2; size <= npad; size <<= 1) {
-    const bool desc = (i & size) == 0;
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      unsigned long long other;
-      if (stride >= 64) {
-        unsigned long long* b = buf + flip * npad;
-        flip ^= 1;
-        if (i < npad) b[i] = key;
-        __syncthreads();
-        other = i < npad ? b[i ^ stride] : 0ull;
-      } else {
-        other = __shfl_xor(key, stride, 64);
-      }
-      const bool lower = (i & stride) == 0;
-      const bool take_max = lower == desc;
-      const unsigned long long mx = key > other ? key : other, mn = key > other ? other : key;
-      key = take_max ? mx : mn;
-    }
-  }
-  return key;
-}
-
-// ---- more keys than threads: KPT = npad / 1024 keys per thread (npad = 2048 .. 16384) --------------------------------
-// Thread t holds the keys of LDS slots [t * KPT, (t + 1) * KPT).  Compare-exchange distances below KPT stay inside the
-// thread, distances below 64 * KPT are one ds_bpermute per key inside the wavefront, only the rest go through LDS (two
-// barriers each, `keys` itself is the exchange buffer): 10 LDS steps of 78 for 4096 keys, where the plain loop took a
-// barrier-separated LDS pass for every step (39 us per 4096-key row).
-// In: keys[0, npad) in LDS, visible to all threads.  Out: the same, sorted descending, visible to all threads.
-template <int KPT>
-__device__ __forceinline__ void block_sort_desc_multi(unsigned long long* keys) {
-  constexpr int npad = KPT * kSortThreads;
-  const int t = threadIdx.x;
-  unsigned long long key[KPT];
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) key[j] = keys[t * KPT + j];
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride >= KPT; stride >>= 1) {
-      unsigned long long other[KPT];
-      if (stride >= 64 * KPT) {
-        __syncthreads();                       // every thread is done reading the previous exchange
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) keys[t * KPT + j] = key[j];
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) other[j] = keys[(t * KPT + j) ^ stride];
-      } else {
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) other[j] = __shfl_xor(key[j], stride / KPT, 64);
-      }
-#pragma unroll
-      for (int j = 0; j < KPT; ++j) {
-        const int e = t * KPT + j;
-        const bool take_max = ((e & stride) == 0) == ((e & size) == 0);
-        const unsigned long long mx = key[j] > other[j] ? key[j] : other[j], mn = key[j] > other[j] ? other[j] : key[j];
-        key[j] = take_max ? mx : mn;
-      }
-    }
-#pragma unroll
-    for (int s = KPT / 2; s > 0; s >>= 1) {
-      if (s < size) {
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-          if ((j & s) == 0) {
-            const bool desc = (((t * KPT + j) & size) == 0);
-            const unsigned long long a = key[j], b = key[j | s];
-            const bool sw = (a < b) == desc;
-            key[j] = sw ? b : a;
-            key[j | s] = sw ? a : b;
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) keys[t * KPT + j] = key[j];
-  __syncthreads();
-}
-
-// ---- block rank (64 <= npad <= 512 keys in LDS, zero-padded, distinct) ------------------------------------------
-// A key's descending rank is the number of larger keys.  The 1024 threads split into 1024/npad parts; thread (c, part)
-// counts the keys of its slice that exceed key c (broadcast 16-byte LDS reads, no conflicts) and adds the count to
-// rank_buf[c].  Two barriers and ~npad^2/2048 LDS reads per thread, against the 36-45 dependent shuffle steps of the
-// bitonic network (5.6 us -> ~1.5 us for the ~220 candidates of a k = 200 selection).  Afterwards every thread with
-// part 0 holds (key c, rank of key c).
-__device__ __forceinline__ void block_rank_desc(const unsigned long long* keys, int npad, unsigned int* rank_buf,
-                                                unsigned long long& mine, unsigned int& rank, bool& owner) {
-  const int tid = threadIdx.x;
-  const int c = tid & (npad - 1), part = tid / npad;
-  const int span = npad / ((int)blockDim.x / npad);      // keys per slice (>= 4 for npad >= 64 at 1024 threads)
-  if (tid < npad) rank_buf[tid] = 0u;
-  __syncthreads();
-  mine = keys[c];
-  unsigned int cnt = 0;
-  const ulonglong2* p = reinterpret_cast<const ulonglong2*>(keys + part * span);
-  for (int i = 0; i < span / 2; ++i) {
-    const ulonglong2 x = p[i];
-    cnt += x.x > mine ? 1u : 0u;
-    cnt += x.y > mine ? 1u : 0u;
-  }
-  if (cnt) atomicAdd(&rank_buf[c], cnt);
-  __syncthreads();
-  rank = rank_buf[c];
-  owner = part == 0;
 }
 
 // ---- LDS bitonic sort (descending) + emit ------------------------------------------------------
@@ -215,41 +90,17 @@ __global__ __launch_bounds__(kSortThreads) void sort_emit_kernel(const float* __
     unsigned long long kv; unsigned int rank; bool owner;
     block_rank_desc(keys, npad, reinterpret_cast<unsigned int*>(keys + npad), kv, rank, owner);
     if (owner && kv != 0ull && rank < (unsigned int)k) {
-      const unsigned int pos = ~(unsigned int)(kv & 0xFFFFFFFFull);
-      out_scores[(int64_t)row * k + rank] = unorderable((unsigned int)(kv >> 32));
-      out_ids[(int64_t)row * k + rank] = map_id(ids, ids_row_stride, ids_index, ids_index_ld, row, pos);
+      out_scores[(int64_t)row * k + rank] = unorderable(key_score(kv));
+      out_ids[(int64_t)row * k + rank] = map_id(ids, ids_row_stride, ids_index, ids_index_ld, row, key_pos(kv));
     }
     return;
   }
-  if (npad <= kSortThreads) {   // one key per thread, sorted mostly in registers; keys[npad, 3 npad) is the exchange buffer
-    unsigned long long kv = (int)threadIdx.x < npad ? keys[threadIdx.x] : 0ull;
-    kv = block_sort_desc(kv, npad, keys + npad);
-    __syncthreads();
-    if ((int)threadIdx.x < npad) keys[threadIdx.x] = kv;
-    __syncthreads();
-  } else if (npad == 2 * kSortThreads) block_sort_desc_multi<2>(keys);
-  else if (npad == 4 * kSortThreads) block_sort_desc_multi<4>(keys);
-  else if (npad == 8 * kSortThreads) block_sort_desc_multi<8>(keys);
-  else if (npad == 16 * kSortThreads) block_sort_desc_multi<16>(keys);
-  else
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (npad >> 1); t += kSortThreads) {
-        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1));
-        const int hi2 = lo | stride;
-        const bool desc = ((lo & size) == 0);
-        const unsigned long long a = keys[lo], b = keys[hi2];
-        if ((a < b) == desc) { keys[lo] = b; keys[hi2] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  lds_sort_desc(keys, npad);   // npad is a power of two <= kSortCap (sort_slots, on the host); npad <= 1024: keys[npad, 3 npad) is the exchange buffer
   for (int j = threadIdx.x; j < k; j += kSortThreads) {
     const unsigned long long kv = keys[j];   // j >= count: padding key 0, sorts below everything at the next level
     if (out_scores) {
-      const unsigned int pos = ~(unsigned int)(kv & 0xFFFFFFFFull);
-      out_scores[(int64_t)row * k + j] = unorderable((unsigned int)(kv >> 32));
-      out_ids[(int64_t)row * k + j] = map_id(ids, ids_row_stride, ids_index, ids_index_ld, row, pos);
+      out_scores[(int64_t)row * k + j] = unorderable(key_score(kv));
+      out_ids[(int64_t)row * k + j] = map_id(ids, ids_row_stride, ids_index, ids_index_ld, row, key_pos(kv));
     } else {
       keys_out[row * keys_ld + (int64_t)blockIdx.y * k + j] = kv;
     }
@@ -357,7 +208,7 @@ __global__ __launch_bounds__(kTieThreads) void tie_resolve_kernel(const float* _
   __shared__ unsigned int wave_cnt[kTieThreads / 64];
   const int row = blockIdx.x;
   if (st[row].done) return;
-  const unsigned int target = (unsigned int)(st[row].prefix >> 32);
+  const unsigned int target = key_score(st[row].prefix);
   const unsigned int need = st[row].need;
   const float* rowp = scores + (int64_t)row * ld;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -375,7 +226,7 @@ __global__ __launch_bounds__(kTieThreads) void tie_resolve_kernel(const float* _
     }
     const unsigned int rank = before + (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));  // 0-based among matches
     if (match && rank == need - 1) {
-      st[row].prefix = ((unsigned long long)target << 32) | (unsigned int)(~(unsigned int)i);
+      st[row].prefix = ((unsigned long long)target << 32) | (unsigned int)(~(unsigned int)i);   // make_key of the matched element, from its score word
       st[row].done = 1u;
     }
     running += total;
@@ -726,8 +577,8 @@ __global__ __launch_bounds__(kRowThreads) void row_select_kernel(const RowSelect
   int it = 0;   // rotating counter set: step `it` accumulates into ctr[it % 3] and clears ctr[(it + 1) % 3] before its barrier
   auto emit = [&](unsigned long long kv, int j) {
     if (a.out_scores) {
-      const unsigned int pos = ~(unsigned int)(kv & 0xFFFFFFFFull);
-      const float sc = unorderable((unsigned int)(kv >> 32));
+      const unsigned int pos = key_pos(kv);
+      const float sc = unorderable(key_score(kv));
       int64_t id;
       if constexpr (IDX) id = map_id(a.ids, a.ids_row_stride, a.ids_index, a.ids_index_ld, row, pos);
       else id = a.ids ? a.ids[a.ids_row_stride * row + pos] : (int64_t)pos;
@@ -751,6 +602,8 @@ __global__ __launch_bounds__(kRowThreads) void row_select_kernel(const RowSelect
       if (tid < k) emit(kv, tid);
       return;
     }
+    // lds_bitonic_desc<kRowThreads>(keys, npad), written out: through the helper the compiler encodes two branches of this kernel
+    // differently (profiles/topk_keys_isa.txt), and this kernel's code is held fixed
     for (int size = 2; size <= npad; size <<= 1) {
       for (int stride = size >> 1; stride > 0; stride >>= 1) {
         for (int t = tid; t < (npad >> 1); t += kRowThreads) {
@@ -817,9 +670,7 @@ __global__ __launch_bounds__(kRowThreads) void row_select_kernel(const RowSelect
     __syncthreads();
     const unsigned int m_ge = cursor;
     if (m_ge <= (unsigned int)lds_keys) {
-      int npad = 2;
-      while (npad < (int)m_ge) npad <<= 1;
-      emit_sorted(npad);
+      emit_sorted(next_pow2((int)m_ge, 2));
       finish();
       return;
     }
@@ -838,9 +689,7 @@ __global__ __launch_bounds__(kRowThreads) void row_select_kernel(const RowSelect
   RadixSel sel;
   radix_select<VPT>(hi_of, lo_of, (unsigned int)k, rsh, sel);
   compact([&](int j) { return radix_selected(v[j], low_of(j), sel); });
-  int npad = 2;
-  while (npad < k) npad <<= 1;
-  emit_sorted(npad);
+  emit_sorted(next_pow2(k, 2));
   finish();
 }
 
@@ -854,10 +703,7 @@ static int launch_row_select_t(const RowSelectArgs& a, int rows, int chunks, hip
 // elements = per-workgroup element count (chunk size, or keys per row)
 template <bool KEYS>
 static int launch_row_select(RowSelectArgs a, int rows, int chunks, int elements, hipStream_t stream) {
-  int lds_keys = 2;
-  while (lds_keys < a.k) lds_keys <<= 1;
-  if (a.k <= kRowFastK) lds_keys = kRowCandCap;     // room for the pre-filtered candidates
-  a.lds_keys = lds_keys;
+  a.lds_keys = a.k <= kRowFastK ? kRowCandCap : next_pow2(a.k, 2);     // kRowCandCap: room for the pre-filtered candidates
   if (elements <= 4 * kRowThreads) return launch_row_select_t<4, KEYS>(a, rows, chunks, stream);
   if (elements <= 8 * kRowThreads) return launch_row_select_t<8, KEYS>(a, rows, chunks, stream);
   if (elements <= 16 * kRowThreads) return launch_row_select_t<16, KEYS>(a, rows, chunks, stream);
@@ -900,8 +746,6 @@ static bool two_level_plan(int64_t n, int k, int* chunks, int64_t* chunk, int ro
   return first != kRowMaxN && two_level_plan_at(n, k, kRowMaxN, chunks, chunk);
 }
 
-static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 size_t topk_workspace_bytes(int rows, int64_t n, int k) {
@@ -912,6 +756,12 @@ size_t topk_workspace_bytes(int rows, int64_t n, int k) {
   b += align_up(sizeof(unsigned long long) * (size_t)rows * next_pow2(k < 2 ? 2 : k), 256);   // npad candidate slots per row
   const size_t two_level = sizeof(unsigned long long) * (size_t)rows * 24 * 1024;
   return b > two_level ? b : two_level;
+}
+
+// sort_emit_kernel's npad for `count` keys: a power of two in [2, kSortCap], the only sizes lds_sort_desc sorts; 0 (and the error set) beyond
+static int sort_slots(int64_t count) {
+  if (count > kSortCap) { set_error("topk: %lld keys exceed the in-LDS sort capacity (%d)", (long long)count, kSortCap); return 0; }
+  return next_pow2((int)count, 2);
 }
 
 static int ensure_sort_lds() {
@@ -955,9 +805,7 @@ int topk(const float* scores, int64_t ld, int rows, int64_t n, int k, const int6
     a.scores = scores; a.ld = ld; a.n = n; a.k = k; a.chunk = n; a.ids = ids; a.ids_row_stride = ids_row_stride; a.out_scores = out_scores; a.out_ids = out_ids;
     a.ids_index = ids_index; a.ids_index_ld = ids_index_ld;
     a.f_invalid = f_invalid; a.f_width = f_width; a.f_k = f_k;
-    int lds_keys = 2;                                   // as launch_row_select sets it
-    while (lds_keys < a.k) lds_keys <<= 1;
-    a.lds_keys = a.k <= kRowFastK ? kRowCandCap : lds_keys;
+    a.lds_keys = a.k <= kRowFastK ? kRowCandCap : next_pow2(a.k, 2);   // as launch_row_select sets it
     if (n <= 4 * kRowThreads) return launch_row_select_t<4, false, true>(a, rows, 1, stream);
     return launch_row_select_t<8, false, true>(a, rows, 1, stream);
   }
@@ -987,13 +835,16 @@ int topk(const float* scores, int64_t ld, int rows, int64_t n, int k, const int6
     }
   }
   if (n <= kSortCap) {
-    const int npad = next_pow2((int)n < 2 ? 2 : (int)n);
+    const int npad = sort_slots(n);
+    if (!npad) return kErrUnsupported;
     hipLaunchKernelGGL(sort_emit_kernel, dim3(rows), dim3(kSortThreads), (npad <= kSortThreads ? 3 * npad : npad) * sizeof(unsigned long long), stream,
                        scores, ld, n, n, (const unsigned long long*)nullptr, (int64_t)0, 0, k, npad, ids, ids_row_stride,
                        out_scores, out_ids, (unsigned long long*)nullptr, (int64_t)0, pred, (const SelectState*)nullptr, ids_index, ids_index_ld);
     return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
   }
   if (ws_bytes < topk_workspace_bytes(rows, n, k)) { set_error("top-k workspace too small"); return kErrNoMem; }
+  const int npad = sort_slots(k);
+  if (!npad) return kErrUnsupported;
   char* base = static_cast<char*>(ws);
   SelectState* st = reinterpret_cast<SelectState*>(base);
   base += align_up(sizeof(SelectState) * (size_t)rows, 256);
@@ -1011,7 +862,6 @@ int topk(const float* scores, int64_t ld, int rows, int64_t n, int k, const int6
   if (chunks > max_chunks) chunks = max_chunks;
   if (chunks < 1) chunks = 1;
   const int64_t chunk = (n + chunks - 1) / chunks;
-  const int npad = next_pow2(k < 2 ? 2 : k);
   for (int pass = 0; pass < kRadixPasses; ++pass) {
     hipLaunchKernelGGL(hist_kernel, dim3((unsigned)chunks, rows), dim3(kHistThreads), 0, stream, scores, ld, n, st, hist, pass,
                        chunk, pred);
@@ -1129,16 +979,15 @@ __global__ __launch_bounds__(kRowThreads) void sublist_select_kernel(const SubSe
   }
   __syncthreads();
   auto emit = [&](unsigned long long kv, int j) {
-    a.out_scores[(int64_t)row * k + j] = kv ? unorderable((unsigned int)(kv >> 32)) : -INFINITY;
-    a.out_pos[(int64_t)row * k + j] = kv ? (int64_t)(~(unsigned int)(kv & 0xFFFFFFFFull)) : 0;   // an unfilled slot names item 0 (such a row is redone by the caller)
+    a.out_scores[(int64_t)row * k + j] = kv ? unorderable(key_score(kv)) : -INFINITY;
+    a.out_pos[(int64_t)row * k + j] = kv ? (int64_t)key_pos(kv) : 0;   // an unfilled slot names item 0 (such a row is redone by the caller)
   };
   if (npad <= kRowThreads) {
     unsigned long long kv = tid < npad ? skeys[tid] : 0ull;
     kv = block_sort_desc(kv, npad, skeys + npad);
     if (tid < k) emit(kv, tid);
   } else {
-    if (npad == 2 * kRowThreads) block_sort_desc_multi<2>(skeys);
-    else block_sort_desc_multi<4>(skeys);
+    lds_sort_desc_wide<kRowMaxK / kRowThreads>(skeys, npad);
     for (int j = tid; j < k; j += kRowThreads) emit(skeys[j], j);
   }
 }
@@ -1185,8 +1034,8 @@ __global__ __launch_bounds__(kSmallThreads) void sublist_rank_kernel(const SubSe
     for (int j = 0; j < held / 2; ++j) { const ulonglong2 x = p2[j]; rank += x.x > mine ? 1 : 0; rank += x.y > mine ? 1 : 0; }
     if (held & 1) rank += skeys[held - 1] > mine ? 1 : 0;
     if (rank < k) {
-      a.out_scores[(int64_t)row * k + rank] = unorderable((unsigned int)(mine >> 32));
-      a.out_pos[(int64_t)row * k + rank] = (int64_t)(~(unsigned int)(mine & 0xFFFFFFFFull));
+      a.out_scores[(int64_t)row * k + rank] = unorderable(key_score(mine));
+      a.out_pos[(int64_t)row * k + rank] = (int64_t)key_pos(mine);
     }
   }
   for (int j = held + tid; j < k; j += kSmallThreads) {     // a row with fewer than k candidates (redone by the caller): defined filler
@@ -1501,17 +1350,17 @@ __global__ __launch_bounds__(kSortThreads) void merge_candidates_kernel(const in
     if (i < count) {
       const int r = i / k, j = i - r * k;
       const unsigned int bits = (unsigned int)(unsigned long long)gathered[((int64_t)r * rows + row) * msg_ld + j];
-      kv = ((unsigned long long)orderable(__uint_as_float(bits)) << 32) | (unsigned int)(~(unsigned int)i);
+      kv = make_key(__uint_as_float(bits), (unsigned int)i);
     }
     keys[i] = kv;
   }
   __syncthreads();
   auto emit = [&](unsigned long long kv, int slot) {
-    const unsigned int pos = ~(unsigned int)(kv & 0xFFFFFFFFull);
+    const unsigned int pos = key_pos(kv);
     const int r = (int)(pos / (unsigned int)k), jj = (int)(pos - (unsigned int)r * (unsigned int)k);
-    const float sc = unorderable((unsigned int)(kv >> 32));
+    const float sc = unorderable(key_score(kv));
     const int64_t id = gathered[((int64_t)r * rows + row) * msg_ld + k + jj];
-    if (slot == k_out - 1) s_kth = (unsigned int)(kv >> 32);
+    if (slot == k_out - 1) s_kth = key_score(kv);
     if (fuse) { f_sc[slot] = sc; f_id[slot] = id; }
     else { out_scores[(int64_t)row * k_out + slot] = sc; out_ids[(int64_t)row * k_out + slot] = id; }
   };
@@ -1543,43 +1392,15 @@ __global__ __launch_bounds__(kSortThreads) void merge_candidates_kernel(const in
     __syncthreads();
     filter_from_lds<kSortThreads>(f_id, f_sc, k_out, f_inv, f_width, f_k, out_ids + (int64_t)row * f_k, out_scores + (int64_t)row * f_k, f_scratch);
   };
-  bool bad = false;
-  for (int i = threadIdx.x; i + 1 < count; i += kSortThreads)
-    if ((i + 1) % k != 0 && keys[i] < keys[i + 1]) bad = true;
-  if (bad) unsorted = 1;
-  __syncthreads();
-  if (!unsorted) {
+  if (sorted_lists_check<kSortThreads>(keys, count, k, &unsorted)) {
     for (int i = threadIdx.x; i < count; i += kSortThreads) {
-      const unsigned long long kv = keys[i];
-      const int r = i / k, j = i - r * k;
-      int rank = j;
-      for (int o = 0; o < R && rank < k_out; ++o) {
-        if (o == r) continue;
-        const unsigned long long* list = keys + o * k;   // descending
-        int lo = 0, hi = k;
-        while (lo < hi) {                                // first index whose key is < kv  = #keys > kv
-          const int mid = (lo + hi) >> 1;
-          if (list[mid] > kv) lo = mid + 1; else hi = mid;
-        }
-        rank += lo;
-      }
-      if (rank < k_out) emit(kv, rank);
+      const int rank = sorted_lists_rank<false>(keys, R, k, i, k_out);
+      if (rank < k_out) emit(keys[i], rank);
     }
     finish();
     return;
   }
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (npad >> 1); t += kSortThreads) {
-        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1));
-        const int hi2 = lo | stride;
-        const bool desc = ((lo & size) == 0);
-        const unsigned long long a = keys[lo], b = keys[hi2];
-        if ((a < b) == desc) { keys[lo] = b; keys[hi2] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_desc<kSortThreads>(keys, npad);
   for (int j = threadIdx.x; j < k_out; j += kSortThreads) emit(keys[j], j);
   finish();
 }
@@ -1650,7 +1471,7 @@ __global__ __launch_bounds__(kSortThreads) void rescore_select_kernel(const floa
       float a;
       if (i < n_ranked) {
         a = approx[(int64_t)row * n_ranked + i];
-        kv = ((unsigned long long)orderable(e) << 32) | (unsigned int)(~(unsigned int)pos);
+        kv = make_key(e, (unsigned int)pos);
         mn = fminf(mn, a);
       } else {
         a = approx_dense[(int64_t)row * ld_dense + pos];
@@ -1669,29 +1490,18 @@ __global__ __launch_bounds__(kSortThreads) void rescore_select_kernel(const floa
   }
   if ((threadIdx.x & 63) == 0) { red_min[threadIdx.x >> 6] = mn; red_err[threadIdx.x >> 6] = err; red_nan[threadIdx.x >> 6] = bad; }
   __syncthreads();
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (npad >> 1); t += kSortThreads) {
-        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1));
-        const int hi2 = lo | stride;
-        const bool desc = ((lo & size) == 0);
-        const unsigned long long a = keys[lo], b = keys[hi2];
-        if ((a < b) == desc) { keys[lo] = b; keys[hi2] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_desc<kSortThreads>(keys, npad);
   for (int j = threadIdx.x; j < k; j += kSortThreads) {
     const unsigned long long kv = keys[j];
-    const int64_t pos = (int64_t)(~(unsigned int)(kv & 0xFFFFFFFFull));
-    out_scores[(int64_t)row * k + j] = unorderable((unsigned int)(kv >> 32));
+    const int64_t pos = (int64_t)key_pos(kv);
+    out_scores[(int64_t)row * k + j] = unorderable(key_score(kv));
     out_ids[(int64_t)row * k + j] = ids ? ids[pos] : pos;
   }
   if (threadIdx.x == 0) {
     float m = INFINITY, er = 0.0f;
     int b = 0;
     for (int w = 0; w < kSortThreads / 64; ++w) { m = fminf(m, red_min[w]); er = fmaxf(er, red_err[w]); b |= red_nan[w]; }
-    const float kth = unorderable((unsigned int)(keys[k - 1] >> 32));
+    const float kth = unorderable(key_score(keys[k - 1]));
     if (ok) ok[row] = (!b && kth > m + margin_eps) ? 1 : 0;
     if (stats) { stats[2 * row] = er; stats[2 * row + 1] = kth - m; }   // largest |exact - approx| seen, and the margin the row has
   }
@@ -1797,28 +1607,14 @@ __global__ __launch_bounds__(kSortThreads) void sort_rows_i64_kernel(const int64
     for (int i = threadIdx.x; i < npad; i += kSortThreads)
       keys[i] = i < n ? ~((unsigned long long)in[(int64_t)row * n + i] ^ 0x8000000000000000ull) : 0ull;      // padding sorts last
     __syncthreads();
-    if (npad == 2 * kSortThreads) block_sort_desc_multi<2>(keys);
-    else if (npad == 4 * kSortThreads) block_sort_desc_multi<4>(keys);
-    else if (npad == 8 * kSortThreads) block_sort_desc_multi<8>(keys);
-    else block_sort_desc_multi<16>(keys);
+    lds_sort_desc_wide(keys, npad);
     for (int i = threadIdx.x; i < n; i += kSortThreads) out[(int64_t)row * n + i] = (int64_t)(~keys[i] ^ 0x8000000000000000ull);
     return;
   }
   for (int i = threadIdx.x; i < npad; i += kSortThreads)
     keys[i] = i < n ? ((unsigned long long)in[(int64_t)row * n + i] ^ 0x8000000000000000ull) : ~0ull;  // signed order
   __syncthreads();
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (npad >> 1); t += kSortThreads) {
-        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1));
-        const int hi2 = lo | stride;
-        const bool asc = ((lo & size) == 0);
-        const unsigned long long a = keys[lo], b = keys[hi2];
-        if ((a > b) == asc) { keys[lo] = b; keys[hi2] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_asc<kSortThreads>(keys, npad);
   for (int i = threadIdx.x; i < n; i += kSortThreads) out[(int64_t)row * n + i] = (int64_t)(keys[i] ^ 0x8000000000000000ull);
 }
 
@@ -2240,7 +2036,7 @@ __global__ __launch_bounds__(kSortThreads) void cand_finish_kernel(const CandFin
       p = a.pos[(int64_t)row * a.cand_ld + i];
     }
     if (i < (int)c) {
-      kv = ((unsigned long long)orderable(e) << 32) | (unsigned int)(~(unsigned int)p);
+      kv = make_key(e, (unsigned int)p);
       mn = fminf(mn, ap);
       const float dd = a.one_sided ? fmaxf(e - ap, 0.0f) : fabsf(e - ap);
       bad |= !(dd == dd) || !(e == e) || !(ap == ap);
@@ -2272,16 +2068,7 @@ __global__ __launch_bounds__(kSortThreads) void cand_finish_kernel(const CandFin
     if (tid == 0) { a.w.counts[row] = 0u; a.w.flags[row] = 0u; }
   }
   __syncthreads();
-  if (npad <= kSortThreads) {
-    unsigned long long kv = tid < npad ? keys[tid] : 0ull;
-    kv = block_sort_desc(kv, npad, keys + npad);
-    __syncthreads();
-    if (tid < npad) keys[tid] = kv;
-    __syncthreads();
-  } else if (npad == 2 * kSortThreads) block_sort_desc_multi<2>(keys);
-  else if (npad == 4 * kSortThreads) block_sort_desc_multi<4>(keys);
-  else if (npad == 8 * kSortThreads) block_sort_desc_multi<8>(keys);
-  else block_sort_desc_multi<16>(keys);
+  lds_sort_desc(keys, npad);   // npad <= 1024: keys[npad, 3 npad) is the exchange buffer
   mn = INFINITY; err = 0.0f; grd = 0.0f; bad = 0;
   for (int wv = 0; wv < kSortThreads / 64; ++wv) { mn = fminf(mn, red_min[wv]); err = fmaxf(err, red_err[wv]); grd = fmaxf(grd, red_grd[wv]); bad |= red_bad[wv]; }
   const bool whole_row = (int64_t)c >= a.n_items;          // every item of the row is a candidate: nothing is left outside
@@ -2292,8 +2079,8 @@ __global__ __launch_bounds__(kSortThreads) void cand_finish_kernel(const CandFin
     int64_t* m = a.msg + (int64_t)row * (2 * k + 2);
     for (int j = tid; j < k; j += kSortThreads) {
       const unsigned long long kv = j < (int)c ? keys[j] : 0ull;
-      const int64_t p = (int64_t)(~(unsigned int)(kv & 0xFFFFFFFFull));
-      const float sc = kv ? unorderable((unsigned int)(kv >> 32)) : -INFINITY;
+      const int64_t p = (int64_t)key_pos(kv);
+      const float sc = kv ? unorderable(key_score(kv)) : -INFINITY;
       m[j] = (int64_t)(unsigned long long)__float_as_uint(sc);
       m[k + j] = kv ? (a.ids ? a.ids[p] : p) : -1;
     }
@@ -2305,15 +2092,15 @@ __global__ __launch_bounds__(kSortThreads) void cand_finish_kernel(const CandFin
   }
   for (int j = tid; j < k; j += kSortThreads) {
     const unsigned long long kv = keys[j];
-    const int64_t p = (int64_t)(~(unsigned int)(kv & 0xFFFFFFFFull));
-    const float sc = unorderable((unsigned int)(kv >> 32));
+    const int64_t p = (int64_t)key_pos(kv);
+    const float sc = unorderable(key_score(kv));
     const int64_t id = a.ids ? a.ids[p < a.n_items ? p : 0] : p;
     a.out_scores[(int64_t)row * k + j] = sc;
     a.out_ids[(int64_t)row * k + j] = id;
     if (fuse && j < kFuseMaxK) { f_sc[j] = sc; f_id[j] = id; }
   }
   // the row's verdict: its k-th fp32 score must clear the best first-pass score left outside the candidates by eps
-  const float kth = (int)c >= k ? unorderable((unsigned int)(keys[k - 1] >> 32)) : -INFINITY;
+  const float kth = (int)c >= k ? unorderable(key_score(keys[k - 1])) : -INFINITY;
   const float gap = kth - mn;
   const float eps = fmaxf(a.default_eps, a.safety * fmaxf(seen_before, bad ? 0.0f : err));
   const int fail = bad || (int)c < k || !(gap > eps);

@@ -170,7 +170,9 @@ def test_f7_full_size(name, dev, precision):
                                       (2, 40960, 4096), (2, 40961, 100), (2, 9000, 5000), (2, 3883, 3883),
                                       # two-level (per-chunk winners, then their winners): 2 .. 74 chunks
                                       (4, 695762, 200), (3, 86971, 200), (2, 3000000, 200), (3, 81921, 512),
-                                      (2, 3400000, 200), (1, 4500000, 200), (2, 49152, 300), (2, 49153, 300)])
+                                      (2, 3400000, 200), (1, 4500000, 200), (2, 49152, 300), (2, 49153, 300),
+                                      # the in-LDS sort at 8 keys per thread (the whole row, 8 192 slots) and at 2 (the radix path's 2 048 candidate slots)
+                                      (2, 5000, 4500), (2, 200000, 1500)])
 def test_topk_matches_deterministic_rule(dev, rows, n, k):
     g = torch.Generator().manual_seed(rows * 1000003 + n)
     scores = torch.randn((rows, n), generator=g)
@@ -1107,8 +1109,15 @@ def test_naive_and_comb_filter_inside_the_selection_equals_the_full_ranking(dev,
                 assert torch.equal(got2[0], want2[0]) and torch.equal(got2[1], want2[1])
 
 
-def test_sort_rows_and_duplicate_mask(dev):
+@pytest.mark.parametrize("n", [1, 2, 64, 777, 1024, 1025, 2049, 4097, 8193, 16384])
+def test_sort_rows_and_duplicate_mask(dev, n):
+    """Rows of 1 .. 1 024 values take the plain network (2 .. 1 024 slots), longer ones the register sort at 2, 4, 8 and 16 keys per thread."""
     g = torch.Generator().manual_seed(1)
+    if n != 777:
+        idx = torch.randint(-(1 << 40), 1 << 40, (3, n), generator=g)
+        idx[:, n // 2] = idx[:, 0]                                         # a repeated value
+        assert torch.equal(E.sort_rows(idx.to(dev)).cpu(), torch.sort(idx, dim=1)[0])
+        return
     idx = torch.randint(-50, 3000, (7, 777), generator=g)
     out = E.sort_rows(idx.to(dev)).cpu()
     assert torch.equal(out, torch.sort(idx, dim=1)[0])
