@@ -45,7 +45,8 @@ extern "C" {
  * rails_sasrec_decode_layer are new;
  * 14: the IVF-Flat component index rails_ivf_* (MoLNaiveTopK use_faiss=True) is new;
  * 15: the shape-generic fp32 scoring route rails_mol_generic_* is new; the candidate-key entry points rails_group_keys_* of the item-sharded
- * MoLNaiveTopK / MoLCombTopK and the list edit rails_ivf_lists_edit[_workspace_bytes] of the IVF index were added under 15 as well: no struct
+ * MoLNaiveTopK / MoLCombTopK, the list edit rails_ivf_lists_edit[_workspace_bytes] of the IVF index and the item masks rails_item_mask_* /
+ * rails_scores_mask were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
 #define RAILS_ABI_VERSION 15
@@ -320,6 +321,33 @@ int rails_id_map_clear(void* map, int64_t slots, void* stream);
 int rails_id_map_insert(void* map, int64_t slots, const int64_t* ids, const int64_t* positions, int64_t first, int64_t m, int32_t* flags, void* stream);
 int rails_id_map_erase(void* map, int64_t slots, const int64_t* ids, int64_t m, int32_t* missing, void* stream);
 int rails_id_map_lookup(const void* map, int64_t slots, const int64_t* ids, int64_t m, int64_t* positions_out, void* stream);
+
+/* ---- item masks: a top-k call restricted to a subset of the corpus (added under ABI 15: new entries only) -----------------------
+ * No counterpart in the reference: CandidateIndex.apply_object_filter ("general per batch filters", indexing/candidate_index.py) raises
+ * NotImplementedError there.  A mask is `rows` rows of rails_item_mask_words of n 32-bit words; bit i % 32 of word i / 32 of a row is
+ * item i (1 = the item may be returned) and the unused high bits of a row's last word are zero.  1 <= n < 2^31, 1 <= rows <= 2^24. */
+int64_t rails_item_mask_words(int64_t n);                 /* ceil(n / 32) */
+int64_t rails_item_mask_tile_items(void);                 /* items per tile of the compaction below (8 192) */
+/* mask_u8 (rows, n) bool bytes with row stride ld (non-zero = set) -> words (rows, words-of-n), every word written, and counts[r] = set
+ * bits of row r.  One wave ballot per 64 items; two launches. */
+int rails_item_mask_pack(const uint8_t* mask_u8, int64_t ld, int32_t rows, int64_t n, uint32_t* words, int32_t* counts, void* stream);
+/* ONE row, zeroed by the caller: the bits at positions[0 .. m) are set (a 32-bit atomic OR each; repeats are harmless).  The caller
+ * checks the positions against [0, n) beforehand; the kernel skips one outside it. */
+int rails_item_mask_set(const int64_t* positions, int64_t m, int64_t n, uint32_t* words, void* stream);
+/* counts[r] = set bits of row r among its first n */
+int rails_item_mask_count(const uint32_t* words, int32_t rows, int64_t n, int32_t* counts, void* stream);
+/* Stable compaction: out[r * out_ld + j] = the j-th set position of row r, ascending, for j < counts[r]; the slots from counts[r] to
+ * out_ld hold 0; set positions beyond out_ld are dropped (the caller passes out_ld >= the largest count).  Per-tile popcounts, an
+ * exclusive 64-bit scan of every row's tile counts, the write, the padding: four launches, rows of any length.  `workspace`:
+ * rails_item_mask_positions_workspace_bytes bytes, uninitialised. */
+size_t rails_item_mask_positions_workspace_bytes(int32_t rows, int64_t n);
+int rails_item_mask_positions(const uint32_t* words, int32_t rows, int64_t n, int64_t* out, int64_t out_ld, void* workspace, size_t workspace_bytes,
+                              void* stream);
+/* In place: scores[b * ld + x] = fill for x < n wherever bit first_item + x of row b's mask is clear (row b of the mask starts at
+ * words + b * words_row_stride; words_row_stride = 0: one row shared by every b).  The mask rows hold at least first_item + n bits.
+ * Entries whose bit is set are neither read nor written: their bits stay, NaN payloads included.  run_if: the launch predicate. */
+int rails_scores_mask(float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const uint32_t* words, int64_t words_row_stride,
+                      float fill, const int32_t* run_if, void* stream);
 
 /* Per-row candidates: out[bq * n_cand + x] = <queries[bq], items[bq / r][x]> for queries (n_queries, dim) and items
  * (n_queries / r, n_cand, dim) -- the two bmm branches of DotProductSimilarity.forward

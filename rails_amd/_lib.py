@@ -208,6 +208,14 @@ PROTOTYPES = {
     "rails_id_map_insert": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "rails_id_map_erase": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "rails_id_map_lookup": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_item_mask_words": (C.c_int64, [C.c_int64]),
+    "rails_item_mask_tile_items": (C.c_int64, []),
+    "rails_item_mask_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rails_item_mask_set": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_item_mask_count": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_item_mask_positions_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "rails_item_mask_positions": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rails_scores_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "rails_dot_rowwise": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],

@@ -673,6 +673,68 @@ int rails_id_map_lookup(const void* map, int64_t slots, const int64_t* ids, int6
   return go <= 0 ? go : fail(id_map_lookup(map, slots, ids, m, positions_out, (hipStream_t)stream), "id_map_lookup");
 }
 
+// ---- item masks (item_mask.hip) ----
+// the checks the entry points share, before any launch: 1 = launch, < 0 = the error code
+static int item_mask_args(const char* what, bool pointers, int64_t rows, int64_t n) {
+  g_err[0] = '\0';
+  if (rows < 1 || rows > (1 << 24) || n < 1 || n >= (1LL << 31)) {
+    set_error("%s: rows = %lld, n = %lld: rows must lie in [1, 2^24] and n in [1, 2^31)", what, (long long)rows, (long long)n);
+    return RAILS_EINVAL;
+  }
+  if (!pointers) { set_error("%s: NULL pointer", what); return RAILS_EINVAL; }
+  return 1;
+}
+
+int64_t rails_item_mask_words(int64_t n) { return n < 0 ? 0 : item_mask_words(n); }
+
+int64_t rails_item_mask_tile_items(void) { return item_mask_tile_bits(); }
+
+int rails_item_mask_pack(const uint8_t* mask, int64_t ld, int32_t rows, int64_t n, uint32_t* words, int32_t* counts, void* stream) {
+  const int go = item_mask_args("item_mask_pack", mask && words && counts, rows, n);
+  if (go <= 0) return go;
+  if (ld < n) { set_error("item_mask_pack: ld = %lld < n = %lld", (long long)ld, (long long)n); return RAILS_EINVAL; }
+  return fail(item_mask_pack(mask, ld, rows, n, words, counts, (hipStream_t)stream), "item_mask_pack");
+}
+
+int rails_item_mask_set(const int64_t* positions, int64_t m, int64_t n, uint32_t* words, void* stream) {
+  const int go = item_mask_args("item_mask_set", words && (positions || m == 0), 1, n);
+  if (go <= 0) return go;
+  if (m < 0) { set_error("item_mask_set: m < 0"); return RAILS_EINVAL; }
+  if (m == 0) return RAILS_OK;
+  return fail(item_mask_set(positions, m, n, words, (hipStream_t)stream), "item_mask_set");
+}
+
+int rails_item_mask_count(const uint32_t* words, int32_t rows, int64_t n, int32_t* counts, void* stream) {
+  const int go = item_mask_args("item_mask_count", words && counts, rows, n);
+  return go <= 0 ? go : fail(item_mask_count(words, rows, n, counts, (hipStream_t)stream), "item_mask_count");
+}
+
+size_t rails_item_mask_positions_workspace_bytes(int32_t rows, int64_t n) {
+  return rows < 1 || n < 1 || n >= (1LL << 31) ? 0 : item_mask_positions_workspace_bytes(rows, n);
+}
+
+int rails_item_mask_positions(const uint32_t* words, int32_t rows, int64_t n, int64_t* out, int64_t out_ld, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  const int go = item_mask_args("item_mask_positions", words && workspace && (out || out_ld == 0), rows, n);
+  if (go <= 0) return go;
+  if (out_ld < 0) { set_error("item_mask_positions: out_ld < 0"); return RAILS_EINVAL; }
+  if (workspace_bytes < item_mask_positions_workspace_bytes(rows, n)) { set_error("item_mask_positions: workspace too small"); return RAILS_ENOMEM; }
+  return fail(item_mask_positions(words, rows, n, out, out_ld, workspace, (hipStream_t)stream), "item_mask_positions");
+}
+
+int rails_scores_mask(float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const uint32_t* words, int64_t words_row_stride, float fill,
+                      const int32_t* run_if, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || n < 0 || ld < n || first_item < 0 || words_row_stride < 0 || first_item + n >= (1LL << 31)) {
+    set_error("scores_mask: bad size (rows = %d, n = %lld, ld = %lld, first_item = %lld)", rows, (long long)n, (long long)ld, (long long)first_item);
+    return RAILS_EINVAL;
+  }
+  if (rows == 0 || n == 0) return RAILS_OK;
+  if (!scores || !words) { set_error("scores_mask: NULL pointer"); return RAILS_EINVAL; }
+  if (words_row_stride != 0 && words_row_stride < item_mask_words(first_item + n)) { set_error("scores_mask: the mask rows are shorter than first_item + n bits"); return RAILS_EINVAL; }
+  return fail(scores_mask(scores, ld, rows, n, first_item, words, words_row_stride, fill, run_if, (hipStream_t)stream), "scores_mask");
+}
+
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s) || n_items < 0) return 0;
   return (size_t)n_items * (size_t)s->dot_product_dimension * 2;

@@ -1,0 +1,240 @@
+// Item masks (rails_item_mask_*, rails_scores_mask): a top-k call restricted to a subset of the corpus.
+//
+// A mask is `rows` bit rows of ceil(n / 32) 32-bit words each: bit i % 32 of word i / 32 is item i (little-endian), the unused high bits
+// of a row's last word are ZERO -- every kernel here keeps that invariant and none relies on it for its bounds.
+//   pack        bool bytes -> words: one wave ballot per 64 items, lanes 0 and 32 store the two words
+//   set         positions -> bits of one zeroed row, a 32-bit atomic OR per position
+//   count       per-row popcount, one workgroup per row
+//   positions   STABLE compaction of a row's set bits into its ascending position list, in tiles of kTileBits items:
+//                 1. per-tile popcounts  2. exclusive scan of a row's tile counts (64-bit, one workgroup per row, looping)
+//                 3. every tile writes its positions behind its offset  4. the slots past the row's count are set to 0
+//   scores_mask scores[b][x] = fill where bit first_item + x of row b's mask is clear; kept entries are neither read nor written
+// All plain C++ with vector stores, no LDS beyond the 4-word reductions, every loop grid-strided with 64-bit indices (rows of 125 M bits).
+#include <hip/hip_runtime.h>
+
+#include "mol_kernels.h"
+
+namespace mol {
+
+namespace {
+
+typedef unsigned int u32;
+typedef unsigned long long u64;
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kTileWords = kThreads;               // one word per thread
+constexpr int64_t kTileBits = 32 * kTileWords;     // 8 192 items per compaction tile
+constexpr unsigned kMaxGrid = 1u << 16;
+
+inline unsigned grid_for(int64_t blocks) { return (unsigned)(blocks < 1 ? 1 : blocks > (int64_t)kMaxGrid ? (int64_t)kMaxGrid : blocks); }
+
+// the word `w` of a row of n bits with the bits at or past n cleared
+__device__ __forceinline__ u32 live_bits(u32 word, int64_t w, int64_t n) {
+  const int64_t left = n - w * 32;
+  return left >= 32 ? word : left <= 0 ? 0u : word & ((1u << (int)left) - 1u);
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// sum over the workgroup, returned to every thread (two barriers: `part` may be reused at once)
+__device__ __forceinline__ int block_sum(int v, int* part) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int s = 0;
+  for (int w = 0; w < kWaves; ++w) s += part[w];
+  __syncthreads();
+  return s;
+}
+
+// exclusive prefix sum over the workgroup in thread order; *total: the workgroup's sum
+__device__ __forceinline__ int block_scan_excl(int v, int* part, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += up;
+  }
+  if (lane == 63) part[wave] = inc;
+  __syncthreads();
+  int before = 0, all = 0;
+  for (int w = 0; w < kWaves; ++w) {
+    if (w < wave) before += part[w];
+    all += part[w];
+  }
+  __syncthreads();
+  *total = all;
+  return before + inc - v;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kThreads) item_mask_pack_kernel(const unsigned char* __restrict__ mask, int64_t ld, int rows, int64_t n, int64_t n_words,
+                                                                 u32* __restrict__ words) {
+  const int64_t chunks = (n + kThreads - 1) / kThreads, total = chunks * rows;
+  for (int64_t c = blockIdx.x; c < total; c += gridDim.x) {
+    const int64_t row = c / chunks, ch = c - row * chunks;
+    const int64_t i = ch * kThreads + threadIdx.x;
+    const bool set = i < n && mask[row * ld + i] != 0;
+    const u64 b = __ballot(set);
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (ch * kThreads + (threadIdx.x & ~63)) >> 5;      // the first of this wave's two words
+    if (lane == 0 && w < n_words) words[row * n_words + w] = (u32)b;
+    if (lane == 32 && w + 1 < n_words) words[row * n_words + w + 1] = (u32)(b >> 32);
+  }
+}
+
+__global__ void item_mask_set_kernel(const int64_t* __restrict__ positions, int64_t m, int64_t n, u32* __restrict__ words) {
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < m; u += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = positions[u];
+    if (p >= 0 && p < n) atomicOr(words + (p >> 5), 1u << (int)(p & 31));
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) item_mask_count_kernel(const u32* __restrict__ words, int64_t n, int64_t n_words, int32_t* __restrict__ counts) {
+  __shared__ int part[kWaves];
+  const int64_t row = blockIdx.x;
+  int c = 0;
+  for (int64_t w = threadIdx.x; w < n_words; w += kThreads) c += __popc(live_bits(words[row * n_words + w], w, n));
+  c = block_sum(c, part);
+  if (threadIdx.x == 0) counts[row] = c;
+}
+
+// ws[row * tiles + t] = set bits of tile t of the row
+__global__ void __launch_bounds__(kThreads) item_mask_tile_counts_kernel(const u32* __restrict__ words, int rows, int64_t n, int64_t n_words, int64_t tiles,
+                                                                        int64_t* __restrict__ ws) {
+  __shared__ int part[kWaves];
+  const int64_t total = tiles * rows;
+  for (int64_t c = blockIdx.x; c < total; c += gridDim.x) {
+    const int64_t row = c / tiles, t = c - row * tiles;
+    const int64_t w = t * kTileWords + threadIdx.x;
+    const int bits = w < n_words ? __popc(live_bits(words[row * n_words + w], w, n)) : 0;
+    const int s = block_sum(bits, part);
+    if (threadIdx.x == 0) ws[c] = s;
+  }
+}
+
+// in place: a row's tile counts -> their exclusive prefix sums; ws[rows * tiles + row] = the row's total
+__global__ void __launch_bounds__(kThreads) item_mask_tile_scan_kernel(int rows, int64_t tiles, int64_t* __restrict__ ws) {
+  __shared__ int part[kWaves];
+  const int64_t row = blockIdx.x;
+  int64_t* counts = ws + row * tiles;
+  int64_t running = 0;
+  for (int64_t base = 0; base < tiles; base += kThreads) {
+    const int64_t t = base + threadIdx.x;
+    const int v = t < tiles ? (int)counts[t] : 0;      // at most kTileBits
+    int all;
+    const int excl = block_scan_excl(v, part, &all);
+    if (t < tiles) counts[t] = running + excl;
+    running += all;
+  }
+  if (threadIdx.x == 0) ws[(int64_t)rows * tiles + row] = running;
+}
+
+__global__ void __launch_bounds__(kThreads) item_mask_tile_write_kernel(const u32* __restrict__ words, int rows, int64_t n, int64_t n_words, int64_t tiles,
+                                                                       const int64_t* __restrict__ ws, int64_t* __restrict__ out, int64_t out_ld) {
+  __shared__ int part[kWaves];
+  const int64_t total = tiles * rows;
+  for (int64_t c = blockIdx.x; c < total; c += gridDim.x) {
+    const int64_t row = c / tiles, t = c - row * tiles;
+    const int64_t w = t * kTileWords + threadIdx.x;
+    u32 word = w < n_words ? live_bits(words[row * n_words + w], w, n) : 0u;
+    int all;
+    int64_t slot = ws[c] + block_scan_excl(__popc(word), part, &all);
+    int64_t* dst = out + row * out_ld;
+    while (word) {
+      const int bit = __ffs((int)word) - 1;
+      if (slot < out_ld) dst[slot] = w * 32 + bit;
+      ++slot;
+      word &= word - 1;
+    }
+  }
+}
+
+__global__ void item_mask_pad_kernel(int rows, int64_t tiles, const int64_t* __restrict__ ws, int64_t* __restrict__ out, int64_t out_ld) {
+  const int64_t total = out_ld * rows;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = i / out_ld, slot = i - row * out_ld;
+    if (slot >= ws[(int64_t)rows * tiles + row]) out[i] = 0;
+  }
+}
+
+constexpr int kMaskPerThread = 4;
+
+__global__ void __launch_bounds__(kThreads) scores_mask_kernel(float* __restrict__ scores, int64_t ld, int rows, int64_t n, int64_t first_item,
+                                                              const u32* __restrict__ words, int64_t words_row_stride, float fill,
+                                                              const int32_t* __restrict__ run_if) {
+  MOL_RUN_IF(run_if);
+  constexpr int64_t kChunk = (int64_t)kThreads * kMaskPerThread;
+  const int64_t chunks = (n + kChunk - 1) / kChunk, total = chunks * rows;
+  for (int64_t c = blockIdx.x; c < total; c += gridDim.x) {
+    const int64_t row = c / chunks, ch = c - row * chunks;
+    const u32* mrow = words + row * words_row_stride;
+    float* srow = scores + row * ld;
+#pragma unroll
+    for (int j = 0; j < kMaskPerThread; ++j) {
+      const int64_t x = ch * kChunk + (int64_t)j * kThreads + threadIdx.x;
+      if (x < n) {
+        const int64_t bit = first_item + x;
+        if (((mrow[bit >> 5] >> (int)(bit & 31)) & 1u) == 0u) srow[x] = fill;
+      }
+    }
+  }
+}
+
+static inline int launched() { return hipGetLastError() == hipSuccess ? kOk : kErrLaunch; }
+
+int64_t item_mask_words(int64_t n) { return (n + 31) / 32; }
+
+int item_mask_count(const void* words, int rows, int64_t n, int32_t* counts, hipStream_t stream) {
+  hipLaunchKernelGGL(item_mask_count_kernel, dim3((unsigned)rows), dim3(kThreads), 0, stream, (const u32*)words, n, item_mask_words(n), counts);
+  return launched();
+}
+
+int item_mask_pack(const unsigned char* mask, int64_t ld, int rows, int64_t n, void* words, int32_t* counts, hipStream_t stream) {
+  const int64_t chunks = (n + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(item_mask_pack_kernel, dim3(grid_for(chunks * rows)), dim3(kThreads), 0, stream, mask, ld, rows, n, item_mask_words(n), (u32*)words);
+  if (launched() != kOk) return kErrLaunch;
+  return item_mask_count(words, rows, n, counts, stream);
+}
+
+int item_mask_set(const int64_t* positions, int64_t m, int64_t n, void* words, hipStream_t stream) {
+  hipLaunchKernelGGL(item_mask_set_kernel, dim3(grid_for((m + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, positions, m, n, (u32*)words);
+  return launched();
+}
+
+int64_t item_mask_tile_bits() { return kTileBits; }
+
+size_t item_mask_positions_workspace_bytes(int rows, int64_t n) {
+  const int64_t tiles = (item_mask_words(n) + kTileWords - 1) / kTileWords;
+  return (size_t)(tiles + 1) * (size_t)rows * sizeof(int64_t);
+}
+
+int item_mask_positions(const void* words, int rows, int64_t n, int64_t* out, int64_t out_ld, void* workspace, hipStream_t stream) {
+  const int64_t n_words = item_mask_words(n), tiles = (n_words + kTileWords - 1) / kTileWords;
+  int64_t* ws = (int64_t*)workspace;
+  const u32* w = (const u32*)words;
+  hipLaunchKernelGGL(item_mask_tile_counts_kernel, dim3(grid_for(tiles * rows)), dim3(kThreads), 0, stream, w, rows, n, n_words, tiles, ws);
+  if (launched() != kOk) return kErrLaunch;
+  hipLaunchKernelGGL(item_mask_tile_scan_kernel, dim3((unsigned)rows), dim3(kThreads), 0, stream, rows, tiles, ws);
+  if (launched() != kOk) return kErrLaunch;
+  if (out_ld == 0) return kOk;
+  hipLaunchKernelGGL(item_mask_tile_write_kernel, dim3(grid_for(tiles * rows)), dim3(kThreads), 0, stream, w, rows, n, n_words, tiles, ws, out, out_ld);
+  if (launched() != kOk) return kErrLaunch;
+  hipLaunchKernelGGL(item_mask_pad_kernel, dim3(grid_for((out_ld * rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, rows, tiles, ws, out, out_ld);
+  return launched();
+}
+
+int scores_mask(float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const void* words, int64_t words_row_stride, float fill,
+                const int32_t* run_if, hipStream_t stream) {
+  const int64_t chunks = (n + (int64_t)kThreads * kMaskPerThread - 1) / ((int64_t)kThreads * kMaskPerThread);
+  hipLaunchKernelGGL(scores_mask_kernel, dim3(grid_for(chunks * rows)), dim3(kThreads), 0, stream, scores, ld, rows, n, first_item, (const u32*)words,
+                     words_row_stride, fill, run_if);
+  return launched();
+}
+
+}  // namespace mol

@@ -220,6 +220,17 @@ int id_map_insert(void* map, int64_t slots, const int64_t* ids, const int64_t* p
 int id_map_erase(void* map, int64_t slots, const int64_t* ids, int64_t m, int32_t* missing, hipStream_t stream);
 int id_map_lookup(const void* map, int64_t slots, const int64_t* ids, int64_t m, int64_t* positions_out, hipStream_t stream);
 
+// ---- item masks (item_mask.hip): rows of ceil(n / 32) 32-bit words, bit i % 32 of word i / 32 is item i, high bits of the last word zero ----
+int64_t item_mask_words(int64_t n);
+int64_t item_mask_tile_bits();
+int item_mask_pack(const unsigned char* mask, int64_t ld, int rows, int64_t n, void* words, int32_t* counts, hipStream_t stream);
+int item_mask_set(const int64_t* positions, int64_t m, int64_t n, void* words, hipStream_t stream);
+int item_mask_count(const void* words, int rows, int64_t n, int32_t* counts, hipStream_t stream);
+size_t item_mask_positions_workspace_bytes(int rows, int64_t n);
+int item_mask_positions(const void* words, int rows, int64_t n, int64_t* out, int64_t out_ld, void* workspace, hipStream_t stream);
+int scores_mask(float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const void* words, int64_t words_row_stride, float fill,
+                const int32_t* run_if, hipStream_t stream);
+
 int dot_rowwise(const float* q, const float* items, int64_t Bq, int X, int D, int r, float* out, hipStream_t stream);
 
 size_t topk_workspace_bytes(int rows, int64_t n, int k);

@@ -1176,6 +1176,159 @@ class ItemIdMap:
         return {"slots": self.slots, "live": self.live, "tombstones": self.tombstones, "rebuilds": self.rebuilds}
 
 
+# ---- item masks (rails_item_mask_*, rails_scores_mask) ---------------------
+def item_mask_words(n_items: int) -> int:
+    return (int(n_items) + 31) // 32
+
+
+def check_item_mask(mask_items: int, mask_rows: int, shared: bool, kept_min: int, n_items: int, batch: Optional[int], k: Optional[int]) -> None:
+    """The pure checks of a masked call, made before any launch: a mask of `mask_items` items (`mask_rows` rows, shared by the batch or one per
+    query row, its smallest row keeping `kept_min`) against a module of `n_items` items, a batch of `batch` rows and a call for k results
+    (None: not checked).  ValueError for a mask of another corpus size or another batch; for k beyond the kept items what k > N raises."""
+    if mask_items != n_items:
+        raise ValueError(f"item_mask covers {mask_items} items but the module holds {n_items}: a mask is by position -- build a new one after "
+                         "append_items / remove_items (mask_of_ids does it from ids)")
+    if not shared and batch is not None and mask_rows != batch:
+        raise ValueError(f"item_mask has {mask_rows} rows but the batch has {batch}")
+    if k is not None and k > kept_min:
+        raise RuntimeError(f"selected index k out of range (k={k}, n={kept_min})")
+
+
+class ItemMask:
+    """Which items a top-k call may return (item_mask= of MoLBruteForceTopK / MIPSBruteForceTopK): by POSITION, tied to n_items.
+      ItemMask(mask)        mask: bool device tensor (N,) -- shared by the batch -- or (B, N) -- one row per query row; True = may be returned
+      ItemMask.from_positions(n_items, positions, device)   a shared mask with exactly those positions set
+    Holds `words` (rows, ceil(N / 32)) int32 -- bit i % 32 of word i / 32 is item i, the unused high bits of the last word zero --, `counts`
+    (rows,) int32 on the device, n_items, rows, shared, and the host integers kept_min / kept_max from ONE read-back at construction: a
+    reused mask costs a call no host sync.  positions(): the set positions per row, ascending, computed at first use and kept."""
+
+    def __init__(self, mask: torch.Tensor):
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or mask.dim() not in (1, 2) or mask.shape[-1] < 1 or mask.shape[0] < 1:
+            raise ValueError("item_mask must be a bool tensor (N,) or (B, N)")
+        _require_device(mask, "item_mask")
+        shared = mask.dim() == 1
+        m2 = mask.reshape(1, -1) if shared else mask
+        rows, n = m2.shape
+        if m2.stride(1) != 1 or (rows > 1 and m2.stride(0) < n):
+            m2 = m2.contiguous()
+        words = torch.empty((rows, item_mask_words(n)), dtype=torch.int32, device=mask.device)
+        counts = torch.empty(rows, dtype=torch.int32, device=mask.device)
+        with _on_device(mask.device):
+            _lib.check(_lib.load().rails_item_mask_pack(_ptr(m2), m2.stride(0) if rows > 1 else n, rows, n, _ptr(words), _ptr(counts), _stream()),
+                       "rails_item_mask_pack")
+        self._init(words, counts, n, shared, counts.cpu())      # (the one sync)
+
+    def _init(self, words: torch.Tensor, counts: torch.Tensor, n_items: int, shared: bool, counts_host: torch.Tensor) -> None:
+        self.words, self.counts, self.n_items, self.shared = words, counts, int(n_items), bool(shared)
+        self.rows = words.shape[0]
+        self._counts_host = counts_host
+        self.kept_min, self.kept_max = int(counts_host.min()), int(counts_host.max())
+        self._positions: Optional[torch.Tensor] = None
+        self._slots: Optional["ItemMask"] = None
+        self._expanded: Optional[torch.Tensor] = None
+
+    @classmethod
+    def from_positions(cls, n_items: int, positions, device) -> "ItemMask":
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"item_mask must live on the GPU: rails_amd runs its path in HIP kernels only and has no CPU fallback (got {device})")
+        pos = torch.as_tensor(positions)
+        if pos.dtype != torch.int64 or pos.dim() != 1:
+            raise ValueError("positions must be (M,) int64")
+        n_items = int(n_items)
+        if n_items < 1:
+            raise ValueError(f"a mask of {n_items} items")
+        if pos.numel():
+            lo, hi = torch.aminmax(pos)      # (a sync when the positions live on the device; the construction reads the count back anyway)
+            if int(lo) < 0 or int(hi) >= n_items:
+                raise ValueError(f"positions must lie in [0, {n_items})")
+        pos = pos.to(device).contiguous()
+        lib = _lib.load()
+        words = torch.zeros((1, item_mask_words(n_items)), dtype=torch.int32, device=device)
+        counts = torch.empty(1, dtype=torch.int32, device=device)
+        with _on_device(device):
+            _lib.check(lib.rails_item_mask_set(_ptr(pos), pos.numel(), n_items, _ptr(words), _stream()), "rails_item_mask_set")
+            _lib.check(lib.rails_item_mask_count(_ptr(words), 1, n_items, _ptr(counts), _stream()), "rails_item_mask_count")
+        self = cls.__new__(cls)
+        self._init(words, counts, n_items, True, counts.cpu())
+        return self
+
+    def check(self, n_items: int, batch: Optional[int] = None, k: Optional[int] = None) -> None:
+        check_item_mask(self.n_items, self.rows, self.shared, self.kept_min, n_items, batch, k)
+
+    def positions(self) -> torch.Tensor:
+        """(rows, kept_max) int64: each row's set positions ascending, the slots past counts[r] hold 0 (rails_item_mask_positions)."""
+        if self._positions is None:
+            lib = _lib.load()
+            out = torch.empty((self.rows, self.kept_max), dtype=torch.int64, device=self.words.device)
+            ws_bytes = lib.rails_item_mask_positions_workspace_bytes(self.rows, self.n_items)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.words.device)
+            with _on_device(self.words.device):
+                _lib.check(lib.rails_item_mask_positions(_ptr(self.words), self.rows, self.n_items, _ptr(out) if self.kept_max else None, self.kept_max,
+                                                         _ptr(ws), ws_bytes, _stream()), "rails_item_mask_positions")
+            self._positions = out
+        return self._positions
+
+    def positions_for(self, batch: int) -> torch.Tensor:
+        """positions() as (batch, kept_max) contiguous rows, one per query row: a shared mask's row repeated (kept for the last batch size)."""
+        pos = self.positions()
+        if not self.shared or batch == 1:
+            return pos
+        c = self._expanded
+        if c is None or c.shape[0] != batch:
+            c = self._expanded = pos.expand(batch, -1).contiguous()
+        return c
+
+    def ragged(self) -> bool:
+        return self.kept_min != self.kept_max
+
+    def slot_mask(self) -> "ItemMask":
+        """The mask of the SLOTS of positions(): bit j of row r is set iff j < counts[r] -- what clears the scores of a ragged row's padding
+        slots (rails_scores_mask on the (rows, kept_max) candidate scores).  Built at first use and kept."""
+        if self._slots is None:
+            self._slots = ItemMask(torch.arange(self.kept_max, device=self.words.device).unsqueeze(0) < self.counts.unsqueeze(1))
+        return self._slots
+
+    def rows_slice(self, b0: int, b1: int) -> "ItemMask":
+        """The mask of the batch rows b0 .. b1 - 1 (the 4 GiB logit policy slices the batch); a shared mask is its own slice.  No sync."""
+        if self.shared:
+            return self
+        b0, b1 = max(0, int(b0)), min(self.rows, int(b1))
+        if b0 >= b1:
+            raise ValueError(f"rows_slice: no rows in [{b0}, {b1})")
+        if b0 == 0 and b1 == self.rows:
+            return self
+        part = ItemMask.__new__(ItemMask)
+        part._init(self.words[b0:b1], self.counts[b0:b1], self.n_items, False, self._counts_host[b0:b1])
+        if self._positions is not None:
+            part._positions = self._positions[b0:b1, : part.kept_max].contiguous()
+        return part
+
+
+def as_item_mask(item_mask) -> ItemMask:
+    """item_mask= as given: an ItemMask, or a bool tensor packed for this call (one sync: keep an ItemMask to avoid it)."""
+    return item_mask if isinstance(item_mask, ItemMask) else ItemMask(item_mask)
+
+
+def scores_mask(scores: torch.Tensor, mask: ItemMask, first_item: int = 0, fill: float = float("-inf"), run_if: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place: scores[b, x] = fill wherever item first_item + x is not in row b's mask (rails_scores_mask); kept entries are not touched.
+    scores (rows, n) fp32 with unit column stride; a per-row mask has one row per row of scores."""
+    _require_device(scores, "scores")
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError("scores must be (rows, n) fp32 with contiguous rows")
+    rows, n = scores.shape
+    if first_item < 0 or first_item + n > mask.n_items:
+        raise ValueError(f"scores_mask: items [{first_item}, {first_item + n}) are not inside a mask of {mask.n_items} items")
+    if not mask.shared and mask.rows != rows:
+        raise ValueError(f"scores_mask: the mask has {mask.rows} rows but scores has {rows}")
+    if mask.words.device != scores.device:
+        raise ValueError("scores_mask: the mask and the scores live on different devices")
+    with _on_device(scores.device):
+        _lib.check(_lib.load().rails_scores_mask(_ptr(scores), scores.stride(0) if rows > 1 else max(n, scores.stride(0)), rows, n, first_item, _ptr(mask.words),
+                                                 0 if mask.shared else mask.words.stride(0), float(fill), _pred(run_if), _stream()), "rails_scores_mask")
+    return scores
+
+
 def dot_rowwise(q: torch.Tensor, items: torch.Tensor) -> torch.Tensor:
     """q (Bq, D), items (B_I, X, D) with Bq a multiple of B_I -> (Bq, X): <q[bq], items[bq // r][x]>."""
     lib = _lib.load()

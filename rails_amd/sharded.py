@@ -33,7 +33,9 @@ import torch
 import torch.distributed as dist
 
 from . import engine as E
-from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule, _checked_positions
+from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule, _checked_positions, refuse_item_mask
+
+_MASK_WHY = "a mask is by position of ONE corpus and the sharded wrappers split theirs over the ranks (out of scope, DESIGN section 3.13)"
 
 
 def shard_bounds(n_items: int, world_size: int, rank: int) -> Tuple[int, int]:
@@ -112,6 +114,7 @@ class ShardedTopK(TopKModule):
         self._merge = merge if merge is not None else _hip_merge
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         with self._inline():     # a plain call has no neighbouring batch to overlap with (MoLAvgTopK.submit)
             return self.result(self.submit(query_embeddings, k, sorted, **kwargs))
 
@@ -158,6 +161,7 @@ class ShardedTopK(TopKModule):
     # it with the next batch's scoring").  Same kernels, same order of arithmetic: the output is bit-equal to forward's.
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
         """Local scoring + local top-k + pack on the current stream -> handle for result()."""
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         if k > self._n_total:
             raise RuntimeError(f"selected index k out of range (k={k}, n={self._n_total})")
         k_local = min(k, self._n_local)
@@ -192,6 +196,7 @@ class ShardedTopK(TopKModule):
         """CandidateIndex.get_top_k_outputs' body for the sharded modules: the seen-id filter runs inside the merge launch
         (rails_merge_candidates_filtered) -> (top_k_ids (B, k), top_k_scores (B, k)), or None when the sizes are outside the fused path
         or the merge is not the HIP one (the caller then composes forward + filter_seen_ids: same bits)."""
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         if not self._exchange:
             local = self._local_module
             return local.forward_filtered(query_embeddings, k_prime, invalid_ids, k, **kwargs) if hasattr(local, "forward_filtered") else None
@@ -387,6 +392,7 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
         return self._local_module.shard_candidate_count(k, self._gp_pad, self._world)
 
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         B = query_embeddings.size(0)
         per_shard = -(-self._n_total // max(self._world, 1))
         # (the 4 GiB logit policy: the first pass wants the whole (B, N_shard) matrix -- beyond it every rank alike takes the per-shard path, which chunks)
@@ -488,6 +494,7 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
         return info
 
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         if self._exchange and self._global_proof(query_embeddings) and MoLBruteForceTopK.speculation_pays(query_embeddings.size(0), -(-self._n_total // self._world)) and k_prime <= self._n_total:
             with self._inline():
                 return self.result(self.submit(query_embeddings, k_prime, **kwargs), seen=(invalid_ids, k))
@@ -528,11 +535,13 @@ class ShardedMoLAvgTopK(ShardedTopK):
         return MoLAvgTopK(mol_module, item_embeddings_shard, item_ids_shard, avg_top_k=min(self._avg_top_k, int(item_ids_shard.numel())))
 
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         if k_prime > self._avg_top_k or (self._global and self._exchange):
             return None   # forward's own checks / the global-K' exchange: the caller composes forward + filter_seen_ids
         return super().forward_filtered(query_embeddings, k_prime, invalid_ids, k, **kwargs)
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         if k > self._avg_top_k:
             raise ValueError(f"avg_top_k ({self._avg_top_k}) must be larger than k ({k})")
         if not self._global or not self._exchange:
@@ -685,6 +694,7 @@ class _ShardedComponentCandidates(ShardedTopK):
         return min(k, self.union_width())
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         kk = self._check_k(k)
         if not (self._global and self._exchange):
             if not self._exchange:       # one rank: the module's own ranking
@@ -694,11 +704,13 @@ class _ShardedComponentCandidates(ShardedTopK):
         return self._forward_global(query_embeddings, kk, **kwargs)
 
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         if self._global and self._exchange:
             raise NotImplementedError(f"{type(self).__name__}: submit / result pipelining of the global form is not built; call forward")
         return super().submit(query_embeddings, k, sorted, **kwargs)
 
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
+        refuse_item_mask(self, kwargs, _MASK_WHY)
         if self._global and self._exchange:
             return None      # the caller composes forward + filter_seen_ids: same bits
         if not self._exchange or k_prime > self.union_width() or k_prime > self._n_total:

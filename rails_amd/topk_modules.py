@@ -185,6 +185,23 @@ class _ItemsById:
             raise ValueError(f"{what}: {unknown} of the {ids.numel()} item ids are not in the corpus")
         return ids, found
 
+    def mask_of_ids(self, item_ids: torch.Tensor) -> E.ItemMask:
+        """The shared item mask that keeps exactly the items carrying `item_ids` ((M,) or (1, M)), resolved through the live
+        id map.  ValueError for an unknown id or an id given twice, as update_items_by_id.  A mask is by position: after remove_items (which moves
+        rows) or append_items, ask again."""
+        _, found = self._resolved(item_ids, "mask_of_ids")
+        return E.ItemMask.from_positions(self.num_items, found, self._ids_flat.device)
+
+    def _take_item_mask(self, kwargs: dict, batch: int, k: Optional[int]) -> Optional[E.ItemMask]:
+        """item_mask= of a call, taken OUT of its kwargs: None, or the ItemMask (a bool tensor is packed: one sync) checked against this module,
+        the batch and k before any launch (engine.check_item_mask)."""
+        m = kwargs.pop("item_mask", None)
+        if m is None:
+            return None
+        m = E.as_item_mask(m)
+        m.check(self.num_items, batch, k)
+        return m
+
     def update_items_by_id(self, item_ids: torch.Tensor, item_embeddings: torch.Tensor, new_item_ids: Optional[torch.Tensor] = None) -> None:
         """update_items for the items that carry `item_ids` ((M,) or (1, M)); `new_item_ids`, when given, renames them (two items may swap ids in
         one call).  ValueError before anything is touched for an unknown id or an id given twice, naming how many (one device sync)."""
@@ -508,6 +525,7 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
 
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus."""
+        refuse_item_mask(self, kwargs)
         eng = self._bind()
         qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"))
         return eng.score_dense(qpack, query_embeddings.size(0), self._index)
@@ -526,10 +544,13 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
         qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), out=pack)
         return eng.score_dense(qpack, B, index, out=logits)
 
-    def _dense_topk(self, query_embeddings: torch.Tensor, k: int, seen=None, sorted: bool = True, _private: bool = False, **kwargs):
+    def _dense_topk(self, query_embeddings: torch.Tensor, k: int, seen=None, sorted: bool = True, _private: bool = False, _mask=None, **kwargs):
         """Dense fp32 logits into scratch (_all_logits_scratch and its options) + exact top-k -> (scores, ids); with seen = (invalid_ids, k_out)
-        the seen-id filter runs inside the selection launch (rails_topk_filtered) -> (ids (B, k_out), scores (B, k_out))."""
+        the seen-id filter runs inside the selection launch (rails_topk_filtered) -> (ids (B, k_out), scores (B, k_out)).  _mask: the logits
+        of the items outside this ItemMask are set to -inf before the selection (the dense strategy of a masked call)."""
         logits = self._all_logits_scratch(query_embeddings, _private=_private, **kwargs)
+        if _mask is not None:
+            E.scores_mask(logits, _mask)
         ws = None if _private else self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(logits.shape[0], logits.shape[1], k), torch.uint8)
         if seen is not None:
             ids, scores = E.topk_filtered(logits, k, self._ids_flat, seen[0], seen[1], workspace=ws)
@@ -577,6 +598,26 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
                 rows = eng.build_index_rows(self._index)
         self._rows_cache = (eng, self._index, rows)
         return rows
+
+
+def refuse_item_mask(module, kwargs, why: str = "its candidates are generated inside the fused scans, and masking their result afterwards is not the "
+                                               "contract of a masked call") -> None:
+    """item_mask= is built on the exact modules only: every other module refuses it by name, before any launch."""
+    if kwargs.get("item_mask") is not None:
+        name = type(module).__name__ + (" (IVF, use_faiss=True)" if getattr(module, "_use_faiss", False) else "")
+        raise NotImplementedError(f"{name} takes no item_mask: {why}; MoLBruteForceTopK and MIPSBruteForceTopK take it")
+
+
+def mask_strategy(kept_max: int, n_items: int, sparse_max: int, factor: int, positions_scorable: bool) -> str:
+    """How a masked call runs, from the largest row count of the mask alone -- pure host arithmetic:
+      "sparse"  the kept positions are the candidates: scored in place, ranked by rails_topk_candidates; nothing outside the mask is scored.
+                Where at most `sparse_max` items are kept per row (never more than the 16 384 candidates one ranking launch takes), the kept
+                items are at most 1 / `factor` of the corpus, and the engine can score positions in place (`positions_scorable`: the fused
+                fp32 kernels -- not the generic route, not the split-f16 builds);
+      "dense"   everything is scored as without a mask, the cleared entries of the (B, N) matrix are set to -inf, the usual selection follows."""
+    if positions_scorable and 1 <= kept_max <= min(int(sparse_max), 16384) and factor * kept_max <= n_items:
+        return "sparse"
+    return "dense"
 
 
 def _refuse_generic_route(mol_module: MoLSimilarity, what: str) -> None:
@@ -823,16 +864,90 @@ class MoLBruteForceTopK(MoLTopKModule):
 
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus -- of the module's OWN precision (the proved mode's internal split-f16
-        engine is not the module's precision: its fp32 companion answers)."""
+        engine is not the module's precision: its fp32 companion answers).  item_mask=: the columns outside the mask hold -inf."""
         eng = self._bind()
+        mask = self._take_item_mask(kwargs, query_embeddings.size(0), None)
         if eng.exact is not None and self._mol_module.engine() is not eng:
             ex = eng.exact
             qpack, _, _ = ex.query_pack(query_embeddings, kwargs.get("user_ids"))
-            return ex.score_dense(qpack, query_embeddings.size(0), self._dense_fp32_index())
-        return super().all_logits(query_embeddings, **kwargs)
+            logits = ex.score_dense(qpack, query_embeddings.size(0), self._dense_fp32_index())
+        else:
+            logits = super().all_logits(query_embeddings, **kwargs)
+        return logits if mask is None else E.scores_mask(logits, mask)
+
+    # ---- item_mask=: a call restricted to a subset of the corpus (DESIGN section 3.13) ------------------------------------------------------
+    # The call equals the same call on a module freshly constructed from the kept rows and their ids, bit for bit (scores are per item and
+    # position-independent, ties break by position, and the kept items keep their order).  Two strategies, chosen on the host from the mask's
+    # largest row count (mask_strategy): SPARSE scores the kept positions alone; DENSE scores everything as without a mask and sets the cleared
+    # entries of the (B, N) matrix to -inf before the selection -- on every arm: _dense_topk, the corpus chunks, the proved flow's first pass
+    # and its redo.  Rows whose k-th kept score is -inf or NaN tie with cleared entries: the contract is stated for finite scores.
+    MASK_SPARSE_MAX = 16384       # rows keeping at most this many items may take the sparse strategy (never more than rails_topk_candidates ranks)
+    MASK_SPARSE_FACTOR = 4        # ... when they keep at most 1 / this of the corpus.  Measured (profiles/item_mask.json, B = 32, k' = 261): sparse / dense
+                                  # step time 0.44 at N = 32 768 and 0.65 at N = 65 536 with N / 4 kept, 1.02 with N / 3, 1.22 with N / 2: the crossover
+                                  # lies at a third of the corpus, 4 is the smallest whole factor at which sparse wins
+    MASK_PROVED_MIN_KEPT = 16384  # the proved flow runs masked where every row keeps MORE than this: at least as many as a call has candidates
+                                  # (candidate_count's cap), so every selected candidate is a kept item; other masks take the dense fp32 kernels
+
+    def _mask_scorer(self, eng):
+        """(engine, index, row-major copy or a function yielding it) that scores corpus positions in place in the module's own fp32 arithmetic --
+        _score_positions' arguments -- or None where there is none: the generic route, the split-f16 precisions (no indexed instantiation), an
+        exact mode without its resident fp32 index."""
+        if eng.route == "generic":
+            return None
+        if eng.exact is not None:
+            if self._index32 is None or self._index32_engine is not eng.exact:
+                return None
+            return eng.exact, self._index32, self._rows32
+        if eng.precision != "fp32":
+            return None
+        return eng, self._index, self._index_rows
+
+    def _masked(self, eng, mask: E.ItemMask, count: bool = True) -> str:
+        """The strategy of this masked call; counted in rescore_stats (stats()["masked_sparse_calls" / "masked_dense_calls"])."""
+        how = mask_strategy(mask.kept_max, self.num_items, self.MASK_SPARSE_MAX, self.MASK_SPARSE_FACTOR, self._mask_scorer(eng) is not None)
+        if count:
+            key = f"masked_{how}_calls"
+            self.rescore_stats[key] = self.rescore_stats.get(key, 0) + 1
+        return how
+
+    def _forward_sparse(self, eng, query_embeddings: torch.Tensor, k: int, mask: E.ItemMask, seen, **kwargs):
+        """The sparse strategy: the kept positions of every row are its candidates (ItemMask.positions, ascending: the order of a fresh module
+        of the kept rows), scored in place by the fp32 kernels (_score_positions: the dense kernels' bits) and ranked by rails_topk_candidates
+        (score desc, candidate column asc) -> (scores, ids); seen = (invalid_ids, k_out): the seen-id filter inside that launch where the
+        sizes fit, behind it otherwise -> (ids, scores).  A ragged per-row mask pads short rows with position 0: those slots are set to -inf."""
+        ex, index, rows = self._mask_scorer(eng)
+        B = query_embeddings.size(0)
+        pos = mask.positions_for(B)
+        K = pos.shape[1]
+        qpack, _, _ = ex.query_pack(query_embeddings, kwargs.get("user_ids"))
+        if mask.ragged():
+            copy = (rows(ex) if callable(rows) else rows) if ex.score_indexed_supported(B, K) else None
+            if copy is not None:      # the tiles past a row's count are skipped
+                scores = ex.score_indexed_rows(qpack, B, copy, index.n_items, pos, counts=mask.counts)
+            else:
+                scores = self._score_positions(ex, qpack, B, index, None, pos)
+            E.scores_mask(scores, mask.slot_mask())
+        else:
+            scores = self._score_positions(ex, qpack, B, index, rows, pos)
+        if seen is not None:
+            invalid_ids, k_out = seen
+            if E.topk_candidates_filterable(K, k, invalid_ids.shape[1], k_out):
+                ids, s = E.topk_candidates_filtered(scores, k, pos, self._ids_flat, invalid_ids, k_out)
+            else:
+                s, ids = E.topk_candidates(scores, k, pos, self._ids_flat)
+                ids, s = E.filter_seen_ids(ids, s, invalid_ids, k_out)
+            return ids, s.to(query_embeddings.dtype)
+        s, ids = E.topk_candidates(scores, k, pos, self._ids_flat)
+        return s.to(query_embeddings.dtype), ids
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """item_mask= (an engine.ItemMask, or a bool tensor (N,) / (B, N) packed for this call): only items inside the mask are returned."""
         eng = self._bind()
+        mask = self._take_item_mask(kwargs, query_embeddings.size(0), k)
+        if mask is not None:
+            if self._masked(eng, mask) == "sparse":
+                return self._forward_sparse(eng, query_embeddings, k, mask, None, **kwargs)
+            kwargs["_mask"] = mask
         if eng.exact is not None:
             return self._forward_rescored(query_embeddings, k, **kwargs)
         B, N = query_embeddings.size(0), self._index.n_items
@@ -847,8 +962,15 @@ class MoLBruteForceTopK(MoLTopKModule):
         filter_seen_ids: same bits)."""
         eng = self._bind()
         B, N = query_embeddings.size(0), self._index.n_items
+        mask = self._take_item_mask(kwargs, B, k_prime)
+        if mask is not None and k <= k_prime and self._masked(eng, mask, count=False) == "sparse":
+            self._masked(eng, mask)
+            return self._forward_sparse(eng, query_embeddings, k_prime, mask, (invalid_ids, k), **kwargs)
         if B * N * 4 > self.MAX_LOGIT_BYTES or not E.topk_filter_fusable(N, k_prime, invalid_ids.shape[1], k):
             return None
+        if mask is not None:
+            self._masked(eng, mask)
+            kwargs["_mask"] = mask
         ex = eng.exact
         if ex is None:
             return self._dense_topk(query_embeddings, k_prime, seen=(invalid_ids, k), **kwargs)
@@ -868,11 +990,13 @@ class MoLBruteForceTopK(MoLTopKModule):
     MAX_LOGIT_BYTES = 4 << 30      # larger (B, N) logit matrices are never materialised: the corpus is scored in chunks
     CHUNK_ITEMS = 1 << 23          # 8 Mi items per chunk (a multiple of the tile): 1 GiB of logits at B = 32
 
-    def _forward_chunked(self, query_embeddings: torch.Tensor, k: int, _engine=None, _index=None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _forward_chunked(self, query_embeddings: torch.Tensor, k: int, _engine=None, _index=None, _mask=None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """Exact top-k of a corpus whose (B, N) logits would not fit comfortably (a 125 M-item shard at B = 32 is 16 GB): score
         CHUNK_ITEMS at a time into one recycled buffer, keep each chunk's top-k, merge.  Same result as the one-pass path bit for
         bit: chunks are position ranges in order and every list is sorted (score desc, position asc), so the final top-k over
-        the chunk-major concatenation breaks ties by position as well (the item-sharded merge's argument, rails_amd/sharded.py)."""
+        the chunk-major concatenation breaks ties by position as well (the item-sharded merge's argument, rails_amd/sharded.py).
+        _mask: every chunk's logits are masked at its offset (a chunk may keep fewer than k items: its list then ends in -inf entries, which
+        the merge ranks below every kept item of the other chunks)."""
         eng = _engine if _engine is not None else self._bind()
         index = _index if _index is not None else self._index
         B, N, C = query_embeddings.size(0), index.n_items, self.CHUNK_ITEMS
@@ -884,6 +1008,8 @@ class MoLBruteForceTopK(MoLTopKModule):
         for lo in range(0, N, C):
             n = min(C, N - lo)
             logits = eng.score_dense(qpack, B, index.items(lo, lo + n), out=buf[: B * n].view(B, n))
+            if _mask is not None:
+                E.scores_mask(logits, _mask, first_item=lo)
             s, p = E.topk(logits, min(k, n), workspace=ws)
             part_s.append(s)
             part_p.append(p + lo)
@@ -898,9 +1024,13 @@ class MoLBruteForceTopK(MoLTopKModule):
     # (tools/single_f16_probe.py) -> default eps = 0.15 on logits in [-20, 20], twice the candidate margin of the f16x3 first pass
     RESCORE_EPS_PER_INV_TEMPERATURE_F16X1 = 7.5e-3
 
-    def _forward_rescored(self, query_embeddings: torch.Tensor, k: int, _seen=None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _forward_rescored(self, query_embeddings: torch.Tensor, k: int, _seen=None, _mask=None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """The router of the exact modes: the fp32 brute-force result -- same scores, same ids, same tie order -- by the dense fp32 kernels, the
-        proved flow (_forward_proved) or the monitored flow (_forward_monitored), a slice of the batch at a time under the 4 GiB logit policy."""
+        proved flow (_forward_proved) or the monitored flow (_forward_monitored), a slice of the batch at a time under the 4 GiB logit policy.
+        _mask (the dense strategy of a masked call) travels with every arm; the proved flow takes it where every row keeps more than
+        MASK_PROVED_MIN_KEPT items, the dense fp32 kernels otherwise (and instead of the monitored flow)."""
+        if _mask is not None:
+            kwargs["_mask"] = _mask
         eng = self._bind()
         self._absorb_state()
         B, N = query_embeddings.size(0), self._index.n_items
@@ -935,10 +1065,15 @@ class MoLBruteForceTopK(MoLTopKModule):
                 parts = []
                 for b0 in range(0, B, rows):
                     kw = {key: (v[b0 : b0 + rows] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kwargs.items()}
+                    if _mask is not None:
+                        kw["_mask"] = _mask.rows_slice(b0, b0 + rows)
                     parts.append(self._forward_rescored(query_embeddings[b0 : b0 + rows], k, **kw))
                 return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
             return self._forward_fp32_dense(query_embeddings, k, **kwargs)   # one row is too long: fp32, in corpus chunks
-        if eps is not None and self._index32 is not None and self._index32_engine is eng.exact:
+        proved = eps is not None and self._index32 is not None and self._index32_engine is eng.exact
+        if _mask is not None and not (proved and _mask.kept_min > self.MASK_PROVED_MIN_KEPT):
+            return self._forward_fp32_dense(query_embeddings, k, **kwargs)
+        if proved:
             return self._forward_proved(query_embeddings, k, kc, eps, upper, _seen, **kwargs)
         return self._forward_monitored(query_embeddings, k, kc, eps, upper, **kwargs)
 
@@ -1100,13 +1235,19 @@ class MoLBruteForceTopK(MoLTopKModule):
             e32 = self._score_positions(ex, qpack32, B, self._index32, self._rows32, pos)
         return ws, pos, a16, e32
 
-    def _forward_proved(self, query_embeddings: torch.Tensor, k: int, kc: int, eps_proved: float, upper, seen, **kwargs):
+    def _forward_proved(self, query_embeddings: torch.Tensor, k: int, kc: int, eps_proved: float, upper, seen, _mask=None, **kwargs):
+        """_mask (every row keeps more than MASK_PROVED_MIN_KEPT >= kc items): the first-pass matrix -- scores, or upper bounds -- is masked
+        before the selection, so every candidate is a kept item (the cleared entries sit in the lowest bin, below the threshold bin), m and
+        the verdict are those of the kept corpus and the proof is that of a module built from the kept rows; the redo's dense logits are
+        masked under the redo's own launch predicate."""
         eng = self._engine
         ex = eng.exact
         B, N = query_embeddings.size(0), self._index.n_items
         sp = eng.spec
         qpack16, qpack32 = self._query_packs(eng, query_embeddings, **kwargs)
         s16 = self._first_pass(eng, qpack16, B, upper)
+        if _mask is not None:
+            E.scores_mask(s16, _mask)
         cap = min(kc, N)
         ws, pos, a16, e32 = self._select_and_rescore(ex, qpack32, B, s16, cap, upper)
         guard = eng.gate_rows(qpack32, B)
@@ -1120,6 +1261,8 @@ class MoLBruteForceTopK(MoLTopKModule):
         # the redo: the dense fp32 kernels behind the verdict, no-ops unless it failed (the host never waits)
         redo = state.view(torch.int32)[1:2]
         l32 = ex.score_dense(qpack32, B, self._index32, out=s16, run_if=redo)
+        if _mask is not None:
+            E.scores_mask(l32, _mask, run_if=redo)
         tws = self._buf("topk_ws", E._lib.load().rails_topk_workspace_bytes(B, N, k), torch.uint8)
         if fuse:
             E.topk_filtered(l32, k, self._ids_flat, seen[0], seen[1], workspace=tws, out=(f_i, f_s), run_if=redo)
@@ -1130,7 +1273,7 @@ class MoLBruteForceTopK(MoLTopKModule):
         if fuse:
             return "filtered", f_i, f_s.to(query_embeddings.dtype)
         if self.audit_every > 0 and self.rescore_stats["calls"] % self.audit_every == 0:
-            self._audit(query_embeddings, k, scores, ids, **kwargs)
+            self._audit(query_embeddings, k, scores, ids, _mask=_mask, **kwargs)      # (the audit's reference call is masked alike)
         return scores.to(query_embeddings.dtype), ids
 
     # ---- the proved flow split for an item-sharded corpus (rails_amd/sharded.py) --------------------------------------------------
@@ -1464,7 +1607,7 @@ class MoLBruteForceTopK(MoLTopKModule):
             self._index32, self._index32_engine = ex.build_index(self._item_embeddings[0]), ex
         return self._index32
 
-    def _forward_fp32_dense(self, query_embeddings: torch.Tensor, k: int, _private: bool = False, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _forward_fp32_dense(self, query_embeddings: torch.Tensor, k: int, _private: bool = False, _mask=None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """The exact-fp32 brute force of this module's corpus (fallback of a failed verification, small corpora, the audit).
         Same policies as the plain fp32 module: never more than MAX_LOGIT_BYTES of logits (corpus chunks beyond that), and with
         keep_dense_fp32_index False -- or when _bind declined the second index for lack of memory -- no resident fp32 index either:
@@ -1473,9 +1616,9 @@ class MoLBruteForceTopK(MoLTopKModule):
         B, N = query_embeddings.size(0), self._index.n_items
         have32 = self._index32 is not None and self._index32_engine is ex
         if have32 and B * N * 4 <= self.MAX_LOGIT_BYTES:
-            return self._dense_topk(query_embeddings, k, _eng=ex, _index=self._index32, _tag="qpack32", _private=_private, **kwargs)
+            return self._dense_topk(query_embeddings, k, _eng=ex, _index=self._index32, _tag="qpack32", _private=_private, _mask=_mask, **kwargs)
         if have32:
-            return self._forward_chunked(query_embeddings, k, _engine=ex, _index=self._index32, **kwargs)
+            return self._forward_chunked(query_embeddings, k, _engine=ex, _index=self._index32, _mask=_mask, **kwargs)
         # no resident fp32 index: temporary per-chunk indexes (CHUNK_ITEMS rows at a time), merged like _forward_chunked
         C = min(self.CHUNK_ITEMS, max(1, self.MAX_LOGIT_BYTES // (4 * max(B, 1))))
         C = max(E.TILE_ITEMS, C // E.TILE_ITEMS * E.TILE_ITEMS)
@@ -1484,7 +1627,10 @@ class MoLBruteForceTopK(MoLTopKModule):
         for lo in range(0, N, C):
             n = min(C, N - lo)
             idx = ex.build_index(self._item_embeddings[0, lo : lo + n])
-            s_, p_ = E.topk(ex.score_dense(qpack32, B, idx), min(k, n))
+            logits = ex.score_dense(qpack32, B, idx)
+            if _mask is not None:
+                E.scores_mask(logits, _mask, first_item=lo)
+            s_, p_ = E.topk(logits, min(k, n))
             part_s.append(s_)
             part_p.append(p_ + lo)
             del idx
@@ -1767,6 +1913,7 @@ class MoLAvgTopK(MoLTopKModule):
     # joined to the caller's stream only by result() -- read them through result(), never through the handle, and do not drop a handle
     # without calling result() (ShardedTopK.submit, which needs the scores earlier, waits on the handle's event explicitly).
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
+        refuse_item_mask(self, kwargs)
         if k > self._avg_top_k:  # the reference raises after doing the work (mol_top_k.py:383-386)
             raise ValueError(f"avg_top_k ({self._avg_top_k}) must be larger than k ({k})")
         # Calls that will be speculative (the (B, N) redo buffer does not fit: large shards) alternate between two streams of the
@@ -1839,6 +1986,7 @@ class MoLAvgTopK(MoLTopKModule):
         """CandidateIndex.get_top_k_outputs' body: forward(k_prime) + the seen-id filter, with the filter enqueued BEFORE the host looks
         at the scan's verdict word (it then runs while the host is on its way back) -> (top_k_ids, top_k_scores); None where this
         does not apply (subclasses with their own forward, k_prime beyond K': the caller composes the two calls)."""
+        refuse_item_mask(self, kwargs)
         if type(self).forward is not MoLAvgTopK.forward or k_prime > self._avg_top_k or k_prime < k:
             return None
         with self.inline_calls():
@@ -1907,6 +2055,7 @@ class _ComponentCandidates:
         return ids, scores.to(query_embeddings.dtype)
 
     def _ranked(self, query_embeddings: torch.Tensor, sorted: bool, seen, kwargs):
+        refuse_item_mask(self, kwargs)
         eng = self._bind()
         qpack, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
         for attempt in range(2):     # speculate on the fused scans, verify after everything is enqueued
@@ -2212,7 +2361,12 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
         self._ids_flat = item_ids.reshape(-1).to(device=item_embeddings.device, dtype=torch.int64).contiguous()
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """item_mask= (an engine.ItemMask or a bool tensor (N,) / (B, N)): only items inside the mask are returned -- the
+        dense strategy: the score matrix of the items outside it is set to -inf before the selection."""
+        mask = self._take_item_mask(kwargs, query_embeddings.size(0), k)
         logits = self._index.score(query_embeddings)
+        if mask is not None:
+            E.scores_mask(logits, mask)
         scores, ids = E.topk(logits, k, ids=self._ids_flat, sorted=sorted)
         return scores.to(query_embeddings.dtype), ids
 
