@@ -640,7 +640,7 @@ int rails_range_flag_i32(const int32_t* values, int32_t n, int32_t lo, int32_t h
 /* Verdict of a speculate-then-verify call, on the device: from the row_stats of rails_rescore_select (rows x 2 floats) and the
  * caller's calibration state (8 floats in device memory, zero-initialised once):
  *   state[0]  largest |first pass - fp32| ever observed (updated here; never decreases)
- *   state[1]  REDO flag, an int32 (written here): 1 iff some row's margin <= eps or a NaN was seen, eps = max(default_eps, safety * state[0])
+ *   state[1]  REDO flag, an int32 (written here): 1 iff some row's margin <= eps or a NaN or an infinite error was seen (a bad call: state[0] keeps its value), eps = max(default_eps, safety * state[0])
  *   state[2]  eps   state[3] / state[4]  this call's largest error / smallest margin   state[5] / state[6]  calls / redone calls so far
  *   state[7]  largest |guard value| ever observed
  * guard_values (optional, may be NULL): guard_count floats whose magnitudes must not exceed guard_limit for the caller's bound on
