@@ -45,8 +45,9 @@ extern "C" {
  * rails_sasrec_decode_layer are new;
  * 14: the IVF-Flat component index rails_ivf_* (MoLNaiveTopK use_faiss=True) is new;
  * 15: the shape-generic fp32 scoring route rails_mol_generic_* is new; the candidate-key entry points rails_group_keys_* of the item-sharded
- * MoLNaiveTopK / MoLCombTopK, the list edit rails_ivf_lists_edit[_workspace_bytes] of the IVF index and the item masks rails_item_mask_* /
- * rails_scores_mask were added under 15 as well: no struct
+ * MoLNaiveTopK / MoLCombTopK, the list edit rails_ivf_lists_edit[_workspace_bytes] of the IVF index, the item masks rails_item_mask_* /
+ * rails_scores_mask and the hidden-item entries rails_item_mask_clear / rails_mol_coarse_topk_visible / rails_mol_component_topk_visible
+ * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
 #define RAILS_ABI_VERSION 15
@@ -334,6 +335,9 @@ int rails_item_mask_pack(const uint8_t* mask_u8, int64_t ld, int32_t rows, int64
 /* ONE row, zeroed by the caller: the bits at positions[0 .. m) are set (a 32-bit atomic OR each; repeats are harmless).  The caller
  * checks the positions against [0, n) beforehand; the kernel skips one outside it. */
 int rails_item_mask_set(const int64_t* positions, int64_t m, int64_t n, uint32_t* words, void* stream);
+/* The counterpart (added under ABI 15): the bits at positions[0 .. m) of ONE row are cleared (a 32-bit atomic AND-NOT each; repeats are
+ * harmless), every other bit stays.  What hide_items does to a module's visibility row. */
+int rails_item_mask_clear(const int64_t* positions, int64_t m, int64_t n, uint32_t* words, void* stream);
 /* counts[r] = set bits of row r among its first n */
 int rails_item_mask_count(const uint32_t* words, int32_t rows, int64_t n, int32_t* counts, void* stream);
 /* Stable compaction: out[r * out_ld + j] = the j-th set position of row r, ascending, for j < counts[r]; the slots from counts[r] to
@@ -391,6 +395,16 @@ int rails_mol_coarse_topk(const rails_mol_shape* shape, const float* eq, int32_t
                           const void* table, int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes,
                           float* out_scores, int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range,
                           void* prefilter, void* stream);
+/* The same over the VISIBLE items only (added under ABI 15; hidden items, no counterpart in the reference): visible_words is one mask row
+ * of rails_item_mask_words(n_items) words in device memory, bit set = the item may be returned, shared by the batch.  The sample scan
+ * keeps hidden items out of the per-group maxima and the streaming pass drops them from the candidate lists, so the outputs are those of
+ * rails_mol_coarse_score + rails_scores_mask(fill = -inf) + rails_topk under the same counts check (counts count visible candidates).
+ * The call launches the scans' visible kernels; visible_words == NULL is rails_mol_coarse_topk itself, launch for launch.  With a
+ * pre-filter the int8 pass is kept for d <= 64; at d = 128 the pass reads the bf16 table (same outputs). */
+int rails_mol_coarse_topk_visible(const rails_mol_shape* shape, const float* eq, int32_t batch, int32_t average_queries,
+                                  const void* table, int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes,
+                                  float* out_scores, int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range,
+                                  void* prefilter, const uint32_t* visible_words, void* stream);
 /* Optional int8 pre-filter of rails_mol_coarse_topk's streaming pass (no counterpart in the reference; it changes what the pass
  * READS, not what it returns): a copy of the coarse table as int8 with one scale (256-byte header + d bytes per item).  With it the
  * streaming pass reads the int8 copy, one int8 MFMA per 32 items, against a per-query integer bound that no item reaching the
@@ -429,6 +443,11 @@ int32_t rails_mol_component_topk_capacity(const rails_mol_shape* shape, int32_t 
 int rails_mol_component_topk(const rails_mol_shape* shape, const float* eq, int32_t batch, const void* table, int64_t n_items,
                              int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
                              int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* stream);
+/* The same over the visible items only (added under ABI 15): visible_words as for rails_mol_coarse_topk_visible, shared by every row. */
+int rails_mol_component_topk_visible(const rails_mol_shape* shape, const float* eq, int32_t batch, const void* table, int64_t n_items,
+                                     int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
+                                     int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, const uint32_t* visible_words,
+                                     void* stream);
 /* ---- IVF-Flat index over the item components (MoLNaiveTopK use_faiss=True) ------------------------------------------
  * Replaces the per-item-group faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) of rails/indexing/mol_top_k.py:176-199
  * and its search (:223-238): one independent index per item group m < P_X over the fp16-rounded components fp16(Ex[:, m, :]).

@@ -212,6 +212,7 @@ PROTOTYPES = {
     "rails_item_mask_tile_items": (C.c_int64, []),
     "rails_item_mask_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rails_item_mask_set": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rails_item_mask_clear": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "rails_item_mask_count": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "rails_item_mask_positions_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "rails_item_mask_positions": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -226,6 +227,8 @@ PROTOTYPES = {
     "rails_mol_coarse_topk_capacity": (C.c_int32, [C.c_int32, C.c_int64, C.c_int32]),
     "rails_mol_coarse_topk": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                         C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rails_mol_coarse_topk_visible": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                                C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rails_mol_coarse_prefilter_bytes": (C.c_size_t, [_SHAPE_P, C.c_int64]),
     "rails_mol_coarse_prefilter_build": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "rails_mol_coarse_score": (
@@ -238,6 +241,8 @@ PROTOTYPES = {
     "rails_mol_component_topk_workspace_bytes": (C.c_size_t, [_SHAPE_P, C.c_int32, C.c_int64, C.c_int32]),
     "rails_mol_component_topk": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rails_mol_component_topk_visible": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rails_ivf_build_workspace_bytes": (C.c_size_t, [_SHAPE_P, C.c_int64, C.c_int32, C.c_int32]),
     "rails_ivf_components16_build": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "rails_ivf_train": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,

@@ -704,6 +704,14 @@ int rails_item_mask_set(const int64_t* positions, int64_t m, int64_t n, uint32_t
   return fail(item_mask_set(positions, m, n, words, (hipStream_t)stream), "item_mask_set");
 }
 
+int rails_item_mask_clear(const int64_t* positions, int64_t m, int64_t n, uint32_t* words, void* stream) {
+  const int go = item_mask_args("item_mask_clear", words && (positions || m == 0), 1, n);
+  if (go <= 0) return go;
+  if (m < 0) { set_error("item_mask_clear: m < 0"); return RAILS_EINVAL; }
+  if (m == 0) return RAILS_OK;
+  return fail(item_mask_clear(positions, m, n, words, (hipStream_t)stream), "item_mask_clear");
+}
+
 int rails_item_mask_count(const uint32_t* words, int32_t rows, int64_t n, int32_t* counts, void* stream) {
   const int go = item_mask_args("item_mask_count", words && counts, rows, n);
   return go <= 0 ? go : fail(item_mask_count(words, rows, n, counts, (hipStream_t)stream), "item_mask_count");
@@ -802,6 +810,14 @@ int32_t rails_mol_coarse_topk_capacity(int32_t batch, int64_t n_items, int32_t k
 int rails_mol_coarse_topk(const rails_mol_shape* s, const float* eq, int32_t batch, int32_t average_queries, const void* table,
                           int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes, float* out_scores,
                           int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* prefilter, void* stream) {
+  return rails_mol_coarse_topk_visible(s, eq, batch, average_queries, table, n_items, k_prime, workspace, workspace_bytes, out_scores, out_positions,
+                                       out_counts, out_of_range, prefilter, nullptr, stream);
+}
+
+int rails_mol_coarse_topk_visible(const rails_mol_shape* s, const float* eq, int32_t batch, int32_t average_queries, const void* table,
+                                  int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes, float* out_scores,
+                                  int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* prefilter,
+                                  const uint32_t* visible_words, void* stream) {
   g_err[0] = '\0';
   if (!shape_ok(s)) return RAILS_EINVAL;
   if (batch < 0 || n_items < 0 || k_prime < 0) { set_error("coarse_topk: negative size"); return RAILS_EINVAL; }
@@ -811,7 +827,7 @@ int rails_mol_coarse_topk(const rails_mol_shape* s, const float* eq, int32_t bat
   const int cu = compute_units();
   if (cu <= 0) { set_error("coarse_topk: no HIP device"); return RAILS_ELAUNCH; }
   const int r = coarse_topk(*s, eq, batch, average_queries ? 1 : 0, table, n_items, k_prime, workspace, workspace_bytes,
-                            out_scores, out_positions, out_counts, out_of_range, prefilter, cu, (hipStream_t)stream);
+                            out_scores, out_positions, out_counts, out_of_range, prefilter, cu, (hipStream_t)stream, visible_words);
   return r == kOk ? r : fail(r, "coarse_topk");
 }
 
@@ -857,6 +873,14 @@ int32_t rails_mol_component_topk_capacity(const rails_mol_shape* s, int32_t batc
 int rails_mol_component_topk(const rails_mol_shape* s, const float* eq, int32_t batch, const void* table, int64_t n_items,
                              int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
                              int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* stream) {
+  return rails_mol_component_topk_visible(s, eq, batch, table, n_items, k_group, workspace, workspace_bytes, out_scores, out_positions, out_counts,
+                                          out_of_range, nullptr, stream);
+}
+
+int rails_mol_component_topk_visible(const rails_mol_shape* s, const float* eq, int32_t batch, const void* table, int64_t n_items,
+                                     int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
+                                     int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, const uint32_t* visible_words,
+                                     void* stream) {
   g_err[0] = '\0';
   if (!shape_ok(s)) return RAILS_EINVAL;
   if (batch < 0 || n_items < 0 || k_group < 0) { set_error("component_topk: negative size"); return RAILS_EINVAL; }
@@ -866,7 +890,7 @@ int rails_mol_component_topk(const rails_mol_shape* s, const float* eq, int32_t 
   const int cu = compute_units();
   if (cu <= 0) { set_error("component_topk: no HIP device"); return RAILS_ELAUNCH; }
   const int r = component_topk(*s, eq, batch, table, n_items, k_group, workspace, workspace_bytes, out_scores, out_positions,
-                               out_counts, out_of_range, cu, (hipStream_t)stream);
+                               out_counts, out_of_range, cu, (hipStream_t)stream, visible_words);
   return r == kOk ? r : fail(r, "component_topk");
 }
 

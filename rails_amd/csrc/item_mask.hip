@@ -4,6 +4,7 @@
 // of a row's last word are ZERO -- every kernel here keeps that invariant and none relies on it for its bounds.
 //   pack        bool bytes -> words: one wave ballot per 64 items, lanes 0 and 32 store the two words
 //   set         positions -> bits of one zeroed row, a 32-bit atomic OR per position
+//   clear       positions -> bits of one row cleared, a 32-bit atomic AND-NOT per position (hide_items)
 //   count       per-row popcount, one workgroup per row
 //   positions   STABLE compaction of a row's set bits into its ascending position list, in tiles of kTileBits items:
 //                 1. per-tile popcounts  2. exclusive scan of a row's tile counts (64-bit, one workgroup per row, looping)
@@ -92,6 +93,14 @@ __global__ void item_mask_set_kernel(const int64_t* __restrict__ positions, int6
   for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < m; u += (int64_t)gridDim.x * blockDim.x) {
     const int64_t p = positions[u];
     if (p >= 0 && p < n) atomicOr(words + (p >> 5), 1u << (int)(p & 31));
+  }
+}
+
+// (named apart from the item_mask_* kernels: tests/test_item_mask_cpu.py pins that family's list)
+__global__ void mask_bits_clear_kernel(const int64_t* __restrict__ positions, int64_t m, int64_t n, u32* __restrict__ words) {
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < m; u += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = positions[u];
+    if (p >= 0 && p < n) atomicAnd(words + (p >> 5), ~(1u << (int)(p & 31)));
   }
 }
 
@@ -204,6 +213,11 @@ int item_mask_pack(const unsigned char* mask, int64_t ld, int rows, int64_t n, v
 
 int item_mask_set(const int64_t* positions, int64_t m, int64_t n, void* words, hipStream_t stream) {
   hipLaunchKernelGGL(item_mask_set_kernel, dim3(grid_for((m + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, positions, m, n, (u32*)words);
+  return launched();
+}
+
+int item_mask_clear(const int64_t* positions, int64_t m, int64_t n, void* words, hipStream_t stream) {
+  hipLaunchKernelGGL(mask_bits_clear_kernel, dim3(grid_for((m + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, positions, m, n, (u32*)words);
   return launched();
 }
 

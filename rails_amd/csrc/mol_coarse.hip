@@ -111,7 +111,8 @@ struct CoarseScanArgs {
   unsigned long long* keys; int cap;    // kScanSelect: keys[b * cap + sub * (cap / kSubLists) + slot]
   unsigned int* counts;                 // kScanSelect: counts[b * kSubLists + sub], candidates seen (may exceed the sub-list)
   const int32_t* run_if;                // launch predicate (mol_kernels.h); set for the materialising scan only
-};
+  const unsigned int* visible;          // hidden items: one row of ItemMask words over the n items, bit set = visible; read by the
+};                                      // HIDDEN instantiations only (coarse_scan_visible_kernel), which the launch picks when it is not NULL
 
 // Append path of the select scans.  A hit's slot comes from a device-scope atomic whose result takes ~2 us to return;
 // issued one by one inside the scan they serialise (a wave of the component scan met ~40 per tile: 2 ms for a 0.1 ms
@@ -204,8 +205,13 @@ __device__ __forceinline__ void component_query_element(const float* __restrict_
 }
 __device__ __forceinline__ void quantise_query(const unsigned short* qfrag, int DC, int d, int q, signed char* q8, float* qmeta);   // int8 pre-filter, below
 
-template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>   // DC = d / 16 K chunks; NT: non-temporal table loads; QTS: query tiles a sample launch keeps maxima for; COMP: the component scans' sample block
-__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MODE == kScanSelect ? kScanWaves : 2, MODE == kScanSelect ? kScanWaves : 2))) void coarse_scan_kernel(CoarseScanArgs a) {
+// HIDDEN: a.visible holds one visibility word per tile of 32 items (a tile starts at a multiple of 32), lane column x
+// tests bit x.  The sample scan keeps a hidden item's score out of the running maxima -- else the threshold sits above the visible K'-th
+// score and the call falls to its redo --, the select scan's pre-test is unchanged (a hidden item may fire a tile) and keep_candidates clears
+// the hit mask of a hidden column.  The word's address is wave-uniform.  HIDDEN = false is the scan as it was, under its own symbols.
+template <int DC, int MODE, bool NT, int QTS, bool COMP, bool HIDDEN>   // DC = d / 16 K chunks; NT: non-temporal table loads; QTS: query tiles a sample launch keeps maxima for; COMP: the component scans' sample block
+__device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
+  static_assert(!HIDDEN || MODE != kScanAll, "the materialising scan is masked behind it (rails_scores_mask)");
   MOL_RUN_IF(a.run_if);
   extern __shared__ __attribute__((aligned(16))) unsigned short qfrag[];   // [n_qt][DC][64 lanes][8] bf16, then thr
   const int d = a.d, B = a.comp ? a.B * a.PQ : a.B;      // B: query ROWS from here on
@@ -271,6 +277,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
     bf16x8 Bv[TU][DC];
     int64_t item[TU];
     bool in[TU];
+    unsigned int vis[HIDDEN ? TU : 1];      // HIDDEN: the tiles' visibility words (0 for a tile past the end)
   };
   auto load_trip = [&](int64_t w0, Trip& T) {
 #pragma unroll
@@ -279,6 +286,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
       T.in[u] = (w0 + u) < n_work && item < a.n;
       if (!T.in[u]) item = a.n - 1;
       T.item[u] = item;
+      if constexpr (HIDDEN) T.vis[u] = (w0 + u) < n_work ? a.visible[(w0 + u) * step] : 0u;      // (tile (w0 + u) * step < n_tiles = the row's words)
       const unsigned short* rowp = table + item * d + 8 * h;
 #pragma unroll
       for (int c = 0; c < DC; ++c) {
@@ -305,15 +313,18 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
       bf16x8 Bu[DC];
       int64_t item = 0;
       bool in = false;
+      unsigned int vis = ~0u;
       // constant indices from the front end on, so that the trip stays in registers
       auto pick = [&]<int V, int... C>(std::integral_constant<int, V>, std::integer_sequence<int, C...>) {
         item = T.item[V];
         in = T.in[V];
+        if constexpr (HIDDEN) vis = T.vis[V];
         ((Bu[C] = T.Bv[V][C]), ...);
       };
       [&]<int... V>(std::integer_sequence<int, V...>) {
         ((u == V ? pick(std::integral_constant<int, V>{}, std::make_integer_sequence<int, DC>{}) : (void)0), ...);
       }(std::make_integer_sequence<int, TU>{});
+      if (HIDDEN && vis == 0u) continue;      // wave-uniform: nothing of a wholly hidden tile is kept
       cf32x16 acc = {0};
 #pragma unroll
       for (int c = 0; c < DC; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[c], Bu[c], acc, 0, 0, 0);
@@ -326,6 +337,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
 #pragma unroll
       for (int r = 0; r < 16; ++r) mask |= acc[r] >= -ntlo[r] ? 1u << r : 0u;   // -ntlo = the bf16 value just below the threshold
       if (!in) mask = 0u;
+      if (HIDDEN && !((vis >> x) & 1u)) mask = 0u;      // a hidden item is no candidate
       if (__any(mask != 0u)) {
         float* mine = acc_s + (wave * 16) * 64 + lane;
 #pragma unroll
@@ -380,6 +392,10 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
             bool whole = w0 + TU <= n_work;
 #pragma unroll
             for (int u = 0; u < TU; ++u) whole = whole && T.in[u];
+            if constexpr (HIDDEN) {      // ... and wholly visible: both tiles' words are full (a tile with a hidden item takes the masked maxima below)
+#pragma unroll
+              for (int u = 0; u < TU; ++u) whole = whole && T.vis[u] == ~0u;
+            }
             if (__all(whole)) {
               static_assert(TU == 1 || TU % 2 == 0, "tile pairs");
 #pragma unroll
@@ -402,7 +418,9 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
 #pragma unroll
             for (int c = 0; c < DC; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[c], T.Bv[u][c], acc, 0, 0, 0);
             if (w0 + u < n_work) {                                   // a trip past the end holds the last row again: not a sample
-              const float pen = T.in[u] ? 0.0f : -INFINITY;          // nor are the columns past the end of a ragged last tile
+              bool live = T.in[u];                                   // nor are the columns past the end of a ragged last tile
+              if constexpr (HIDDEN) live = live && ((T.vis[u] >> x) & 1u);   // nor a hidden item
+              const float pen = live ? 0.0f : -INFINITY;
 #pragma unroll
               for (int r = 0; r < 16; ++r) mx[qt][r] = fmaxf(mx[qt][r], acc[r] + pen);
             }
@@ -490,6 +508,21 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MO
   }
 }
 
+#define MOL_COARSE_SCAN_ATTRS __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MODE == kScanSelect ? kScanWaves : 2, MODE == kScanSelect ? kScanWaves : 2)))
+template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>
+MOL_COARSE_SCAN_ATTRS void coarse_scan_kernel(CoarseScanArgs a) { coarse_scan_body<DC, MODE, NT, QTS, COMP, false>(a); }
+template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>      // sample and select scans that honour a.visible
+MOL_COARSE_SCAN_ATTRS void coarse_scan_visible_kernel(CoarseScanArgs a) { coarse_scan_body<DC, MODE, NT, QTS, COMP, true>(a); }
+#undef MOL_COARSE_SCAN_ATTRS
+// the kernel of a launch: the visible form where the caller passed visibility words (never for the materialising scan)
+template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>
+static auto scan_kernel_for(bool hidden) -> void (*)(CoarseScanArgs) {
+  if constexpr (MODE != kScanAll) {
+    if (hidden) return &coarse_scan_visible_kernel<DC, MODE, NT, QTS, COMP>;
+  }
+  return &coarse_scan_kernel<DC, MODE, NT, QTS, COMP>;
+}
+
 constexpr int kSampleMaxQTComp = 8;   // ... and of a component sample launch: B * P_Q <= 256 query rows
 
 template <int MODE>
@@ -526,9 +559,10 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
   CoarseScanArgs b = a;
   b.groups = groups;
   b.stage_cap = stage_cap;
+  const bool hidden = MODE != kScanAll && a.visible != nullptr;
   auto go = [&](auto nt) {
     constexpr bool NT = decltype(nt)::value;
-    auto fire = [&](auto kernel) {
+    auto fire = [&](void (*kernel)(CoarseScanArgs)) {
       if (lds > 48 * 1024 &&
           hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
         return false;
@@ -539,15 +573,15 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
       if (a.comp) {      // the component sample: up to eight row tiles of running maxima, two tiles per v_max3
         if (wide) {
           switch (dc) {      // (d = 128 keeps four row tiles: eight would spill -- component_max_rows)
-            case 2: return fire(&coarse_scan_kernel<2, MODE, NT, kSampleMaxQTComp, true>);
-            case 4: return fire(&coarse_scan_kernel<4, MODE, NT, kSampleMaxQTComp, true>);
+            case 2: return fire(scan_kernel_for<2, MODE, NT, kSampleMaxQTComp, true>(hidden));
+            case 4: return fire(scan_kernel_for<4, MODE, NT, kSampleMaxQTComp, true>(hidden));
             default: return false;
           }
         }
         switch (dc) {
-          case 2: return fire(&coarse_scan_kernel<2, MODE, NT, kSampleMaxQT, true>);
-          case 4: return fire(&coarse_scan_kernel<4, MODE, NT, kSampleMaxQT, true>);
-          case 8: return fire(&coarse_scan_kernel<8, MODE, NT, kSampleMaxQT, true>);
+          case 2: return fire(scan_kernel_for<2, MODE, NT, kSampleMaxQT, true>(hidden));
+          case 4: return fire(scan_kernel_for<4, MODE, NT, kSampleMaxQT, true>(hidden));
+          case 8: return fire(scan_kernel_for<8, MODE, NT, kSampleMaxQT, true>(hidden));
           default: return false;
         }
       }
@@ -556,9 +590,9 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
     // compares' scalar masks measured slower at amzn-books, B = 32, k_g = 5, stride 4: 198 us (116 without candidates, at two waves per
     // SIMD) against 162 (96) at three waves.)
     switch (dc) {
-      case 2: return fire(&coarse_scan_kernel<2, MODE, NT>);
-      case 4: return fire(&coarse_scan_kernel<4, MODE, NT>);
-      case 8: return fire(&coarse_scan_kernel<8, MODE, NT>);
+      case 2: return fire(scan_kernel_for<2, MODE, NT>(hidden));
+      case 4: return fire(scan_kernel_for<4, MODE, NT>(hidden));
+      case 8: return fire(scan_kernel_for<8, MODE, NT>(hidden));
       default: return false;
     }
   };
@@ -809,10 +843,12 @@ struct CoarseI8Args {
   const unsigned short* table; const signed char* table8; PrefilterHeader* hdr; int64_t n; int B, d;
   const float* thr; int64_t thr_stride;
   unsigned long long* keys; int cap; unsigned int* counts;
+  const unsigned int* visible;   // hidden items: one row of ItemMask words (read by coarse_scan_i8_visible_kernel only)
 };
 
-template <int DC8, bool NT>   // DC8 = d / 32 K chunks of the int8 MFMA; NT: non-temporal table loads
-__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(kScan8Waves, kScan8Waves))) void coarse_scan_i8_kernel(CoarseI8Args a) {
+// HIDDEN: the integer pre-test is unchanged; a fired tile reads and keeps its VISIBLE suspects only (bit x of the tile's word, as in coarse_scan_body)
+template <int DC8, bool NT, bool HIDDEN>   // DC8 = d / 32 K chunks of the int8 MFMA; NT: non-temporal table loads
+__device__ __forceinline__ void coarse_scan_i8_body(const CoarseI8Args& a) {
   constexpr int DC = 2 * DC8;
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // bf16 fragments, int8 fragments, thr, thr_lo, integer starts
   const int d = a.d, B = a.B;
@@ -866,6 +902,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(kS
   // item, so the other columns of the tile cannot hold a candidate of this query tile -- 64 B of bf16 table per suspect instead of
   // the tile's 2 KiB (the fired tiles' rows were 0.65 GB of the launch's 4.65 GB).
   auto exact_tile = [&](int qt, int64_t tile, bool need) {
+    if constexpr (HIDDEN) need = need && ((a.visible[tile] >> x) & 1u);      // (tile < n_tiles = the row's words; a wave-uniform address)
     int64_t item = tile * 32 + x;
     const bool in = item < a.n;
     if (!in) item = a.n - 1;
@@ -957,6 +994,13 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(kS
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&a.hdr->scanned, (unsigned long long)(n_tiles * n_qt));
 }
 
+#define MOL_COARSE_I8_ATTRS __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(kScan8Waves, kScan8Waves)))
+template <int DC8, bool NT>
+MOL_COARSE_I8_ATTRS void coarse_scan_i8_kernel(CoarseI8Args a) { coarse_scan_i8_body<DC8, NT, false>(a); }
+template <int DC8, bool NT>      // the scan that honours a.visible; d = 32 and 64 (the d = 128 body spills: such calls take the bf16 select scan)
+MOL_COARSE_I8_ATTRS void coarse_scan_i8_visible_kernel(CoarseI8Args a) { coarse_scan_i8_body<DC8, NT, true>(a); }
+#undef MOL_COARSE_I8_ATTRS
+
 // dynamic LDS of the int8 select scan: the queries' bf16 fragments, their int8 fragments and three bound rows per query tile
 static size_t coarse_scan_i8_lds(int B, int d) {
   const int n_qt = (B + 31) / 32, dc8 = d / 32;
@@ -977,6 +1021,13 @@ static int launch_coarse_scan_i8(const CoarseI8Args& a, hipStream_t stream) {
   if (grid < 1) return kOk;
   auto go = [&](auto nt) {
     constexpr bool NT = decltype(nt)::value;
+    if (a.visible) {
+      switch (dc8) {
+        case 1: hipLaunchKernelGGL((coarse_scan_i8_visible_kernel<1, NT>), dim3((unsigned)grid), dim3(kScanThreads), lds, stream, a); return true;
+        case 2: hipLaunchKernelGGL((coarse_scan_i8_visible_kernel<2, NT>), dim3((unsigned)grid), dim3(kScanThreads), lds, stream, a); return true;
+        default: return false;
+      }
+    }
     switch (dc8) {
       case 1: hipLaunchKernelGGL((coarse_scan_i8_kernel<1, NT>), dim3((unsigned)grid), dim3(kScanThreads), lds, stream, a); return true;
       case 2: hipLaunchKernelGGL((coarse_scan_i8_kernel<2, NT>), dim3((unsigned)grid), dim3(kScanThreads), lds, stream, a); return true;
@@ -1012,12 +1063,13 @@ int range_flag(const int32_t* v, int n, int lo, int hi, int32_t* flag, hipStream
 
 int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* table, int64_t n, int k_prime, void* ws,
                 size_t ws_bytes, float* out_scores, int64_t* out_pos, int32_t* out_counts, int32_t* out_flag, void* prefilter, int n_cu,
-                hipStream_t stream) {
+                hipStream_t stream, const uint32_t* visible) {
   CoarseTopkPlan p;
   if (!coarse_topk_plan(B, n, k_prime, &p, true)) { set_error("coarse_topk: unsupported size (B = %d, K' = %d, n = %lld)", B, k_prime, (long long)n); return kErrUnsupported; }
   if (n >= (1ll << 32)) { set_error("coarse_topk: n does not fit 32-bit positions; shard the corpus"); return kErrUnsupported; }
   if (ws_bytes < p.total) { set_error("coarse_topk: workspace too small"); return kErrNoMem; }
   if (prefilter && !coarse_scan_i8_fits(B, s.dot_product_dimension)) prefilter = nullptr;   // decided BEFORE anything is enqueued: the bf16 select scan, same output
+  if (prefilter && visible && s.dot_product_dimension > 64) prefilter = nullptr;            // (no visible form of the d = 128 int8 scan: same output again)
   char* base = static_cast<char*>(ws);
   unsigned int* counts = reinterpret_cast<unsigned int*>(base);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + p.off_keys);
@@ -1031,7 +1083,7 @@ int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* tab
   // not zeroed: the key selection reads the filled slots only.
   CoarseScanArgs a{};
   a.eq = eq; a.B = B; a.PQ = s.query_dot_product_groups; a.d = s.dot_product_dimension; a.avg = avg; a.groups = 1;
-  a.table = static_cast<const unsigned short*>(table); a.n = n;
+  a.table = static_cast<const unsigned short*>(table); a.n = n; a.visible = visible;
   a.qfrag_out = frag; a.zero_words = counts; a.n_zero = B * kSubLists; a.zero_flag = out_flag;
   signed char* q8 = reinterpret_cast<signed char*>(base + p.off_q8);
   float* qmeta = reinterpret_cast<float*>(base + p.off_qmeta);
@@ -1046,7 +1098,7 @@ int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* tab
     i8.qfrag = frag; i8.q8 = q8; i8.qmeta = qmeta;
     i8.table = static_cast<const unsigned short*>(table); i8.hdr = static_cast<PrefilterHeader*>(prefilter);   // the header's two statistics words are updated
     i8.table8 = static_cast<const signed char*>(prefilter) + kPrefilterHeader; i8.n = n; i8.B = B; i8.d = a.d;
-    i8.thr = top_s + (p.r - 1); i8.thr_stride = p.r; i8.keys = keys; i8.cap = p.cap; i8.counts = counts;
+    i8.thr = top_s + (p.r - 1); i8.thr_stride = p.r; i8.keys = keys; i8.cap = p.cap; i8.counts = counts; i8.visible = visible;
     rc = launch_coarse_scan_i8(i8, stream);
   } else {
     a.qfrag = frag; a.qfrag_out = nullptr; a.zero_words = nullptr; a.n_zero = 0; a.zero_flag = nullptr; a.q8_out = nullptr; a.qmeta_out = nullptr;
@@ -1142,7 +1194,7 @@ size_t component_topk_workspace_bytes(const Shape& s, int B, int64_t n, int k_gr
 }
 
 int component_topk(const Shape& s, const float* eq, int B, const void* table, int64_t n, int k_group, void* ws, size_t ws_bytes,
-                   float* out_scores, int64_t* out_pos, int32_t* out_counts, int32_t* out_flag, int n_cu, hipStream_t stream) {
+                   float* out_scores, int64_t* out_pos, int32_t* out_counts, int32_t* out_flag, int n_cu, hipStream_t stream, const uint32_t* visible) {
   const int rows = B * s.query_dot_product_groups * s.item_dot_product_groups;
   CoarseTopkPlan p;
   if (B * s.query_dot_product_groups > component_max_rows(s) || !coarse_topk_plan(rows, n, k_group, &p, true, B * s.query_dot_product_groups)) { set_error("component_topk: unsupported size (batch = %d, k = %d, n = %lld)", B, k_group, (long long)n); return kErrUnsupported; }
@@ -1157,6 +1209,7 @@ int component_topk(const Shape& s, const float* eq, int B, const void* table, in
   unsigned short* frag = reinterpret_cast<unsigned short*>(base + p.off_qfrag);
   CoarseScanArgs a;
   component_args(s, eq, B, table, n, &a);
+  a.visible = visible;
   a.qfrag_out = frag; a.zero_words = counts; a.n_zero = rows * kSubLists; a.zero_flag = out_flag;
   a.scores16 = sample; a.ld = p.n_sample; a.stride = p.stride;
   int rc = launch_coarse_scan<kScanSample>(a, stream);

@@ -652,14 +652,17 @@ class MolEngine:
         return pre
 
     def coarse_topk(self, eq: torch.Tensor, table: torch.Tensor, average_queries: bool, k_prime: int, with_flag: bool = False,
-                    prefilter: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None):
+                    prefilter: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None, visible: Optional[torch.Tensor] = None):
         """Fused coarse scoring + exact top-K' (no (B, N) score matrix).  -> (scores (B, K'), positions (B, K'), counts (B,)
         int32) or None when the sizes are unsupported.  The result is exact iff K' <= counts[b] <= capacity for every b
         (see include/rails_amd.h); the caller checks and falls back to coarse_scores + topk otherwise.  with_flag: a fourth
         element, a device int32 that is 1 iff some count is out of range (written by the call's own launches) -- or `flag`, the caller's own
         int32 word (device or PINNED HOST memory: the kernels store through the device-visible address, no copy is needed to read it).
-        prefilter: build_coarse_prefilter(table) -- same outputs, the streaming pass reads the int8 copy."""
+        prefilter: build_coarse_prefilter(table) -- same outputs, the streaming pass reads the int8 copy.
+        visible: the visibility words of a hidden set (one ItemMask row over the n items, bit set = visible): the top-K' of the visible items
+        alone, through the scans' visible kernels (rails_mol_coarse_topk_visible); None: rails_mol_coarse_topk, launch for launch."""
         B, n = eq.shape[0], table.shape[0]
+        _check_visible_words(visible, n, table.device)
         memo = self.__dict__.setdefault("_coarse_ws_bytes", {})
         if (B, n, k_prime) not in memo:
             memo[(B, n, k_prime)] = self.lib.rails_mol_coarse_topk_workspace_bytes(C.byref(self.shape), B, n, k_prime)
@@ -688,11 +691,19 @@ class MolEngine:
         else:
             with_flag = True
         with _on_device(dev):
-            _lib.check(
-                self.lib.rails_mol_coarse_topk(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
-                                               _ptr(ws), ws_bytes, _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag) if with_flag else None, _ptr(prefilter), _stream()),
-                "rails_mol_coarse_topk",
-            )
+            if visible is None:
+                _lib.check(
+                    self.lib.rails_mol_coarse_topk(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
+                                                   _ptr(ws), ws_bytes, _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag) if with_flag else None, _ptr(prefilter), _stream()),
+                    "rails_mol_coarse_topk",
+                )
+            else:
+                _lib.check(
+                    self.lib.rails_mol_coarse_topk_visible(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
+                                                           _ptr(ws), ws_bytes, _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag) if with_flag else None,
+                                                           _ptr(prefilter), _ptr(visible), _stream()),
+                    "rails_mol_coarse_topk_visible",
+                )
         return (out_s, out_p, counts[:B], flag) if with_flag else (out_s, out_p, counts[:B])
 
     @staticmethod
@@ -725,11 +736,14 @@ class MolEngine:
             )
         return out
 
-    def component_topk(self, eq: torch.Tensor, table: torch.Tensor, k_group: int, flag: Optional[torch.Tensor] = None):
+    def component_topk(self, eq: torch.Tensor, table: torch.Tensor, k_group: int, flag: Optional[torch.Tensor] = None,
+                       visible: Optional[torch.Tensor] = None):
         """Fused component scoring + exact top-k_group per (b, i, m) row (no (rows, N) score matrix).
         -> (scores (rows, k_group), positions (rows, k_group), counts (rows,) int32) or None when unsupported; exact iff
-        k_group <= counts <= component_topk_capacity for every row -- `flag` (an int32 device scalar, zeroed by the call) is raised otherwise."""
+        k_group <= counts <= component_topk_capacity for every row -- `flag` (an int32 device scalar, zeroed by the call) is raised otherwise.
+        visible: as for coarse_topk (rails_mol_component_topk_visible), shared by every row."""
         B, n = eq.shape[0], table.shape[1]
+        _check_visible_words(visible, n, table.device)
         ws_bytes = self.lib.rails_mol_component_topk_workspace_bytes(C.byref(self.shape), B, n, k_group)
         if ws_bytes == 0:
             return None
@@ -745,11 +759,18 @@ class MolEngine:
         out_p = torch.empty((rows, k_group), dtype=torch.int64, device=dev)
         counts = torch.empty((rows,), dtype=torch.int32, device=dev)
         with _on_device(dev):
-            _lib.check(
-                self.lib.rails_mol_component_topk(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
-                                                  _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag), _stream()),
-                "rails_mol_component_topk",
-            )
+            if visible is None:
+                _lib.check(
+                    self.lib.rails_mol_component_topk(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
+                                                      _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag), _stream()),
+                    "rails_mol_component_topk",
+                )
+            else:
+                _lib.check(
+                    self.lib.rails_mol_component_topk_visible(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
+                                                              _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag), _ptr(visible), _stream()),
+                    "rails_mol_component_topk_visible",
+                )
         return out_s, out_p, counts
 
     def component_topk_capacity(self, batch: int, n: int, k_group: int) -> int:
@@ -1303,6 +1324,68 @@ class ItemMask:
         if self._positions is not None:
             part._positions = self._positions[b0:b1, : part.kept_max].contiguous()
         return part
+
+
+def _check_visible_words(visible: Optional[torch.Tensor], n_items: int, device: torch.device) -> None:
+    """The visibility row a scan reads one word per 32-item tile of: exactly the words of n_items, on the table's device -- checked before any launch."""
+    if visible is None:
+        return
+    if (not torch.is_tensor(visible) or visible.dtype != torch.int32 or visible.numel() != item_mask_words(n_items) or not visible.is_contiguous()
+            or visible.device != device):
+        raise ValueError(f"visible must be the {item_mask_words(n_items)} contiguous int32 mask words of {n_items} items on {device}")
+
+
+def last_word_mask(n_items: int) -> int:
+    """The live bits of the last word of a row of n_items bits, as the int32 that holds them (the unused high bits of a row are zero)."""
+    live = n_items - 32 * (item_mask_words(n_items) - 1)
+    v = (1 << live) - 1
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def visibility_row(n_items: int, device) -> torch.Tensor:
+    """(1, words) int32 on `device`: the row in which every one of n_items items is visible."""
+    words = torch.full((1, item_mask_words(n_items)), -1, dtype=torch.int32, device=device)
+    words[0, -1] = last_word_mask(n_items)
+    return words
+
+
+def visibility_edit(words: torch.Tensor, n_items: int, positions: torch.Tensor, visible: bool) -> Tuple[torch.Tensor, int]:
+    """A COPY of the visibility row `words` with the bits at `positions` (device int64, inside [0, n_items)) set (visible) or cleared (hidden:
+    rails_item_mask_clear), and its number of set bits (rails_item_mask_count; the one read-back).  The row given is not written: launches
+    already enqueued against it keep what they were submitted against."""
+    lib = _lib.load()
+    out = words.clone()
+    counts = torch.empty(1, dtype=torch.int32, device=words.device)
+    fn, name = (lib.rails_item_mask_set, "rails_item_mask_set") if visible else (lib.rails_item_mask_clear, "rails_item_mask_clear")
+    with _on_device(words.device):
+        _lib.check(fn(_ptr(positions), positions.numel(), n_items, _ptr(out), _stream()), name)
+        _lib.check(lib.rails_item_mask_count(_ptr(out), 1, n_items, _ptr(counts), _stream()), "rails_item_mask_count")
+    return out, int(counts.cpu()[0])
+
+
+def visibility_count(words: torch.Tensor, n_items: int) -> int:
+    counts = torch.empty(1, dtype=torch.int32, device=words.device)
+    with _on_device(words.device):
+        _lib.check(_lib.load().rails_item_mask_count(_ptr(words), 1, n_items, _ptr(counts), _stream()), "rails_item_mask_count")
+    return int(counts.cpu()[0])
+
+
+def item_mask_of_words(words: torch.Tensor, n_items: int, kept: int) -> ItemMask:
+    """The shared ItemMask over an existing (1, words) row that keeps `kept` items (no launch, no sync)."""
+    m = ItemMask.__new__(ItemMask)
+    m._init(words, torch.full((1,), kept, dtype=torch.int32, device=words.device), n_items, True, torch.tensor([kept], dtype=torch.int32))
+    return m
+
+
+def item_mask_and(mask: ItemMask, visible: ItemMask) -> ItemMask:
+    """mask AND the shared row `visible`, row by row: what a call with item_mask= returns from a module with a hidden set (one sync: the counts)."""
+    words = torch.bitwise_and(mask.words, visible.words).contiguous()
+    counts = torch.empty(mask.rows, dtype=torch.int32, device=words.device)
+    with _on_device(words.device):
+        _lib.check(_lib.load().rails_item_mask_count(_ptr(words), mask.rows, mask.n_items, _ptr(counts), _stream()), "rails_item_mask_count")
+    m = ItemMask.__new__(ItemMask)
+    m._init(words, counts, mask.n_items, mask.shared, counts.cpu())
+    return m
 
 
 def as_item_mask(item_mask) -> ItemMask:

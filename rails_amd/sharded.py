@@ -287,6 +287,29 @@ class ShardedTopK(TopKModule):
     def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError(f"{type(self).__name__}.remove_items: shrinking an item-sharded corpus would move the shard bounds; build the shards again")
 
+    # ---- hidden items: not built on the item-sharded wrappers -------------------------------------------------------
+    def _refuse_hidden(self, what: str):
+        raise NotImplementedError(f"{type(self).__name__}.{what}: a hidden set is not built on the item-sharded wrappers (every rank would have to hold its "
+                                  "slice of one set, and the global candidate counts would have to follow it); the single-device modules take it")
+
+    def hide_items(self, positions: torch.Tensor) -> None:
+        self._refuse_hidden("hide_items")
+
+    def unhide_items(self, positions: torch.Tensor) -> None:
+        self._refuse_hidden("unhide_items")
+
+    def hide_items_by_id(self, item_ids: torch.Tensor) -> None:
+        self._refuse_hidden("hide_items_by_id")
+
+    def unhide_items_by_id(self, item_ids: torch.Tensor) -> None:
+        self._refuse_hidden("unhide_items_by_id")
+
+    def hidden_positions(self) -> torch.Tensor:
+        self._refuse_hidden("hidden_positions")
+
+    def compact(self) -> torch.Tensor:
+        self._refuse_hidden("compact")
+
     def exchange_info(self) -> dict:
         """What carried the exchange: backend of the process group and its size (bench.py reports it)."""
         if not dist.is_initialized():

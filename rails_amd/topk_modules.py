@@ -131,6 +131,51 @@ def removal_plan(positions: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.T
     return order[order < n_new], n_new + torch.nonzero(tail_kept).reshape(-1)
 
 
+def visibility_after_removal(words: torch.Tensor, n_new: int, holes: torch.Tensor, movers: torch.Tensor) -> torch.Tensor:
+    """remove_items on a visibility row: visibility belongs to the position, so the i-th mover's bit -- read BEFORE the cut --
+    goes to the i-th hole and the row is cut to the words of n_new items, the unused high bits of its last word zero.  words: (1, W) or (W,) int32
+    ItemMask words; holes / movers: removal_plan's, int64 on the words' device.  -> (1, words of n_new) int32.  Pure tensor arithmetic, on
+    whichever device the row lives (tested on the CPU against a numpy model): holes are unique, so the per-word sums below are ORs."""
+    flat = words.reshape(-1)
+    n_words = (int(n_new) + 31) // 32
+    moved = (flat.index_select(0, movers >> 5).to(torch.int64) >> (movers & 31)) & 1
+    w = flat[:n_words].to(torch.int64) & 0xFFFFFFFF
+    hole_bit = torch.ones_like(holes) << (holes & 31)
+    cleared = torch.zeros(n_words, dtype=torch.int64, device=flat.device).index_add_(0, holes >> 5, hole_bit)
+    filled = torch.zeros(n_words, dtype=torch.int64, device=flat.device).index_add_(0, holes >> 5, hole_bit * moved)
+    w = (w & ~cleared) | filled
+    live = int(n_new) - 32 * (n_words - 1)
+    w[-1] &= (1 << live) - 1
+    return torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32).reshape(1, -1)
+
+
+def visibility_after_append(words: torch.Tensor, n: int, n_new: int) -> torch.Tensor:
+    """append_items on a visibility row: the row grown to the words of n_new items, the new items n .. n_new - 1 visible.  Pure tensor arithmetic."""
+    n_words = (int(n_new) + 31) // 32
+    w = torch.zeros(n_words, dtype=torch.int64, device=words.device)
+    w[: words.numel()] = words.reshape(-1).to(torch.int64) & 0xFFFFFFFF
+    first = torch.arange(n_words, dtype=torch.int64, device=words.device) * 32
+    lo, hi = (n - first).clamp(0, 32), (n_new - first).clamp(0, 32)      # the new items of word j are its bits lo .. hi - 1
+    w |= ((torch.ones_like(first) << hi) - 1) & ~((torch.ones_like(first) << lo) - 1)
+    return torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32).reshape(1, -1)
+
+
+def hidden_scan_route(n_items: int, num_visible: int, k: int, min_visible_fraction: float = 0.5) -> str:
+    """Which route a candidate scan of a module with a hidden set takes -- pure host arithmetic:
+      "fused"         the fused scan over the visible items (the scans' visible kernels), guarded by its count check and redo as ever;
+      "materialised"  the scores of every item, the hidden columns set to -inf, the usual selection.
+    The fused scan's threshold is the r-th largest of the sample's per-group maxima, and a group whose sampled items are all hidden
+    contributes -inf.  The plan of n_items sizes the sample for at least 4 r groups, each of which may hold a single sampled item; with a
+    fraction v = num_visible / n_items of the items visible, such a plan keeps ~4 r v finite maxima.  v >= 1/2 leaves 2 r of them -- r to
+    spare, sqrt(r) standard deviations of the binomial count -- and the visible sample is then the same 1-in-stride sample of the visible
+    corpus that the plan's rank r was chosen for: the threshold sits below the visible k-th score and ~r stride visible items above it, as
+    without a hidden set.  Below that fraction the threshold may be -inf or too high on every call, every call would pay the scan AND its
+    redo, and the materialising route is taken directly.  (k beyond num_visible has been refused before.)"""
+    if num_visible < k:
+        raise RuntimeError(f"selected index k out of range (k={k}, n={num_visible})")
+    return "fused" if num_visible >= min_visible_fraction * n_items else "materialised"
+
+
 def upsert_plan(found: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The host rule of upsert_items: `found` ((M,) int64 on the CPU) is where each given id sits in the corpus, -1 where it is absent ->
     (update_rows, update_positions, append_rows): the rows of the argument that replace the items at update_positions, and the rows that are
@@ -196,11 +241,21 @@ class _ItemsById:
         """item_mask= of a call, taken OUT of its kwargs: None, or the ItemMask (a bool tensor is packed: one sync) checked against this module,
         the batch and k before any launch (engine.check_item_mask)."""
         m = kwargs.pop("item_mask", None)
+        vis = self._visible_mask()
         if m is None:
-            return None
+            if vis is not None:      # the hidden set acts as a shared mask of every call (DESIGN section 3.14)
+                vis.check(self.num_items, batch, k)
+            return vis
         m = E.as_item_mask(m)
-        m.check(self.num_items, batch, k)
-        return m
+        if vis is None:
+            m.check(self.num_items, batch, k)
+            return m
+        m.check(self.num_items, batch, None)
+        c = self._and_mask_cache      # the AND of the two, kept per (mask object, hidden-set version): one sync when it is first built
+        if c is None or c[0] is not m or c[1] != self._hidden_version:
+            c = self._and_mask_cache = (m, self._hidden_version, E.item_mask_and(m, vis))
+        c[2].check(self.num_items, batch, k)
+        return c[2]
 
     def update_items_by_id(self, item_ids: torch.Tensor, item_embeddings: torch.Tensor, new_item_ids: Optional[torch.Tensor] = None) -> None:
         """update_items for the items that carry `item_ids` ((M,) or (1, M)); `new_item_ids`, when given, renames them (two items may swap ids in
@@ -338,6 +393,114 @@ class _CorpusEdits(_ItemsById):
             self._apply(CorpusEdit(n - positions.numel(), holes.to(dev), None, CUT_AND_FILLED, gone=positions.to(dev), movers=movers.to(dev)))
         return moved
 
+    # ---- hidden items: a persistent, module-level set of items no call returns ---------------------------------------
+    # State: one row of visibility words in the ItemMask layout (bit set = visible, the unused high bits of the last word zero), None while
+    # nothing is hidden -- such a module runs exactly the launches of one that never heard of hiding.  A module with hidden set H answers every
+    # call as a module freshly constructed from the visible rows and their ids would (scores and ids bit for bit; positions, where a call returns
+    # positions, are this module's).  Visibility belongs to the POSITION: update_items leaves it, append_items adds visible items,
+    # remove_items moves a mover's bit to its hole (visibility_after_removal).  num_hidden / num_visible are host integers from the one
+    # read-back of the hide / unhide / remove call -- a query call never syncs for them.
+    _visible: Optional[torch.Tensor] = None
+    _num_hidden: int = 0
+    _hidden_version: int = 0
+    _visible_mask_cache = None
+    _and_mask_cache = None
+
+    @property
+    def num_hidden(self) -> int:
+        return self._num_hidden
+
+    @property
+    def num_visible(self) -> int:
+        return self.num_items - self._num_hidden
+
+    def hide_items(self, positions: torch.Tensor) -> None:
+        """The items at `positions` ((M,) int64, CPU or device: POSITIONS, checked as update_items checks them) are returned by no call from now on,
+        until unhide_items; hiding a hidden item again is harmless.  Nothing is moved or copied but the visibility row (N / 8 bytes).  ValueError
+        before anything is touched for bad positions, or if no item would stay visible.  M = 0 is a no-op."""
+        self._set_visibility(positions, False, "hide_items")
+
+    def unhide_items(self, positions: torch.Tensor) -> None:
+        """The items at `positions` are visible again (those that were visible stay so)."""
+        self._set_visibility(positions, True, "unhide_items")
+
+    def hide_items_by_id(self, item_ids: torch.Tensor) -> None:
+        """hide_items for the items that carry `item_ids`, through the live id map; unknown or repeated ids are refused as in update_items_by_id."""
+        self._check_hideable("hide_items_by_id")
+        _, found = self._resolved(item_ids, "hide_items_by_id")
+        self.hide_items(found)
+
+    def unhide_items_by_id(self, item_ids: torch.Tensor) -> None:
+        self._check_hideable("unhide_items_by_id")
+        _, found = self._resolved(item_ids, "unhide_items_by_id")
+        self.unhide_items(found)
+
+    def hidden_positions(self) -> torch.Tensor:
+        """(num_hidden,) int64 on the module's device, ascending: the hand-off of the hidden set (it is not part of state_dict)."""
+        self._check_hideable("hidden_positions")
+        dev = self._ids_flat.device
+        if self._visible is None:
+            return torch.empty(0, dtype=torch.int64, device=dev)
+        with torch.inference_mode():
+            inv = torch.bitwise_not(self._visible)
+            inv[0, -1] &= E.last_word_mask(self.num_items)
+            return E.item_mask_of_words(inv, self.num_items, self._num_hidden).positions()[0]
+
+    def compact(self) -> torch.Tensor:
+        """remove_items(hidden_positions()): the hidden items leave the corpus for good -> remove_items' `moved`.  Afterwards nothing is hidden."""
+        self._check_hideable("compact")
+        return self.remove_items(self.hidden_positions())
+
+    def _check_hideable(self, what: str) -> None:
+        """The refusal point of the hidden set: modules whose candidate generation cannot honour it raise here, before anything is touched."""
+
+    def _set_visibility(self, positions: torch.Tensor, visible: bool, what: str) -> None:
+        self._check_hideable(what)
+        if not torch.is_tensor(positions) or positions.dim() != 1:
+            raise ValueError("positions must be (M,) int64")
+        n = self.num_items
+        pos = _checked_positions(positions, positions.numel(), n)
+        if not pos.numel() or (visible and self._visible is None):
+            return
+        with torch.inference_mode():
+            self._join_side_streams()      # handles outstanding from submit() keep the corpus they were submitted against
+            dev = self._ids_flat.device
+            words = self._visible if self._visible is not None else E.visibility_row(n, dev)
+            words, kept = E.visibility_edit(words, n, pos.to(dev), visible)      # a copy: the row in use is not written
+            if kept < 1:
+                raise ValueError(f"{what}: hiding these {pos.numel()} positions would leave none of the {n} items visible")
+            self._visibility_is(words, n - kept)
+
+    def _visibility_is(self, words: Optional[torch.Tensor], num_hidden: int) -> None:
+        """The new state; a row without a hidden item is dropped, so that unhiding everything restores the launches of a module that never hid."""
+        self._visible = words if num_hidden else None
+        self._num_hidden = int(num_hidden)
+        self._hidden_version += 1
+        self._visible_mask_cache = self._and_mask_cache = None
+
+    def _visible_mask(self) -> Optional[E.ItemMask]:
+        """The hidden set as a shared ItemMask (what rails_scores_mask and the exact modules' masked strategies take); None: nothing hidden."""
+        if self._visible is None:
+            return None
+        m = self._visible_mask_cache
+        if m is None:
+            m = self._visible_mask_cache = E.item_mask_of_words(self._visible, self.num_items, self.num_visible)
+        return m
+
+    def _check_k_visible(self, k: int) -> None:
+        if self._visible is not None and k > self.num_visible:
+            raise RuntimeError(f"selected index k out of range (k={k}, n={self.num_visible})")
+
+    def _visibility_step(self, e: CorpusEdit, n: int) -> None:
+        """The visibility row follows an edit (called by _apply with the movers still where they were)."""
+        if self._visible is None:
+            return
+        if e.how == CONCATENATED:
+            self._visibility_is(visibility_after_append(self._visible, n, e.n_new), self._num_hidden)
+        elif e.how == CUT_AND_FILLED:
+            words = visibility_after_removal(self._visible, e.n_new, e.positions, e.movers)
+            self._visibility_is(words, e.n_new - E.visibility_count(words, e.n_new))      # (one read-back, inside the removal)
+
     def _apply(self, e: CorpusEdit) -> None:
         """The one edit flow.  The ids about to be overwritten or moved are read BEFORE the write; what was decided from the corpus size is
         forgotten BEFORE the engine for n_new items is asked for; resize comes before refresh; a removal without holes refreshes nothing."""
@@ -359,6 +522,7 @@ class _CorpusEdits(_ItemsById):
                 _write_ids(self._item_ids, self._ids_flat, pos, ids)
             if ids is not None:
                 self._id_map_step(gone, ids, pos)
+            self._visibility_step(e, n)
             held, resize = self._held_buffers(), e.n_new != n
             if resize:
                 self._forget_corpus_choices()
@@ -526,6 +690,11 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus."""
         refuse_item_mask(self, kwargs)
+        logits = self._raw_logits(query_embeddings, **kwargs)
+        vis = self._visible_mask()      # hidden columns hold -inf
+        return logits if vis is None else E.scores_mask(logits, vis)
+
+    def _raw_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         eng = self._bind()
         qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"))
         return eng.score_dense(qpack, query_embeddings.size(0), self._index)
@@ -872,8 +1041,8 @@ class MoLBruteForceTopK(MoLTopKModule):
             qpack, _, _ = ex.query_pack(query_embeddings, kwargs.get("user_ids"))
             logits = ex.score_dense(qpack, query_embeddings.size(0), self._dense_fp32_index())
         else:
-            logits = super().all_logits(query_embeddings, **kwargs)
-        return logits if mask is None else E.scores_mask(logits, mask)
+            logits = self._raw_logits(query_embeddings, **kwargs)
+        return logits if mask is None else E.scores_mask(logits, mask)      # (a hidden set is part of `mask`: _take_item_mask)
 
     # ---- item_mask=: a call restricted to a subset of the corpus ------------------------------------------------------
     # The call equals the same call on a module freshly constructed from the kept rows and their ids, bit for bit (scores are per item and
@@ -1755,6 +1924,7 @@ class MoLAvgTopK(MoLTopKModule):
         self._prefilter_pending = None            # (pinned copy of the header's counts, its event) on its way to the host
         self._redo_fit_memo: Dict[int, bool] = {} # _device_redo_fits by buffer size
 
+    HIDDEN_FUSED_MIN_VISIBLE = 0.5    # hidden_scan_route: the visible fraction below which a scan of a module with a hidden set is materialised directly
     OVERLAP_BATCHES = True            # submit(): speculative calls alternate between two streams of the module (see submit)
     PREFILTER_MIN_ITEMS = 4_000_000   # the int8 copy of the coarse table pays where the streaming pass is bound by HBM reads
 
@@ -1850,18 +2020,24 @@ class MoLAvgTopK(MoLTopKModule):
         n = table.shape[0]
         if self._avg_top_k > n:
             raise RuntimeError(f"selected index k out of range (k={self._avg_top_k}, n={n})")
+        self._check_k_visible(self._avg_top_k)
+        # a hidden set: the fused scan runs its visible kernels; every materialised score matrix -- the direct route of a
+        # mostly hidden corpus, the predicated redo, the redo after a failed verdict -- has its hidden columns set to -inf before the selection
+        vis = self._visible_mask()
+        fused_ok = vis is None or hidden_scan_route(n, self.num_visible, self._avg_top_k, self.HIDDEN_FUSED_MIN_VISIBLE) == "fused"
         if eq.shape[0] > 128:   # the scan keeps ceil(B / 32) query tiles in LDS: larger batches go in slices
             parts = [self._coarse_topk_from_eq(eq[b0 : b0 + 128], average_queries, pending, with_scores) for b0 in range(0, eq.shape[0], 128)]
             return (torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)) if with_scores else torch.cat(parts, dim=0)
         # large corpora: fused scan + threshold select, no (B, N) score matrix (16 GB per 125 M-item shard at B = 32).
         # Same scores and the same exact top-K' as the materialising path below -- when every query's candidate count
         # landed inside [K', capacity]; the check costs one 128-byte device-to-host copy.
-        if n >= self.fused_coarse_min_items and self._avg_top_k <= 4096 and not self._no_fused:
+        if n >= self.fused_coarse_min_items and self._avg_top_k <= 4096 and not self._no_fused and fused_ok:
             on_device = self._device_redo_fits(eq.shape[0] * n * 4, n)
             # a verdict the HOST reads (no device redo, the caller defers the look): the word lives in pinned host memory and the kernels write it
             # there themselves -- no 4-byte copy behind the call's last launch (round 6, as the component scans)
             word = _pinned_word(self) if (not on_device and pending is not None) else None
-            fused = eng.coarse_topk(eq, table, average_queries, self._avg_top_k, with_flag=True, prefilter=self._prefilter(), flag=word)
+            fused = eng.coarse_topk(eq, table, average_queries, self._avg_top_k, with_flag=True, prefilter=self._prefilter(), flag=word,
+                                    visible=self._visible)
             if fused is not None:
                 # bad: 1 iff some row's candidate count is outside [K', capacity] -- raised by the call's key-selection launch
                 sc, idx, counts, bad = fused
@@ -1870,6 +2046,8 @@ class MoLAvgTopK(MoLTopKModule):
                     # predicate and overwrite (sc, idx) -- no-ops unless a count was out of range; nothing for the host to wait
                     # for (the (B, N) score buffer is recycled across calls)
                     coarse = eng.coarse_scores(eq, table, average_queries, out=self._buf("coarse_all", eq.shape[0] * n, torch.float32).view(eq.shape[0], n), run_if=bad)
+                    if vis is not None:
+                        E.scores_mask(coarse, vis, run_if=bad)
                     E.topk(coarse, self._avg_top_k, out=(sc, idx), run_if=bad)
                     return (sc, idx) if with_scores else idx
                 if pending is not None:      # the caller reads the verdict word after it has enqueued everything that follows
@@ -1878,6 +2056,8 @@ class MoLAvgTopK(MoLTopKModule):
                 if int(bad.item()) == 0:
                     return (sc, idx) if with_scores else idx
         coarse = eng.coarse_scores(eq, table, average_queries)
+        if vis is not None:
+            E.scores_mask(coarse, vis)
         sc, idx = E.topk(coarse, self._avg_top_k)
         return (sc, idx) if with_scores else idx
 
@@ -2032,6 +2212,7 @@ class _ComponentCandidates:
     supply _candidates(eq, pending) -> (B, _union_width()) positions.  Mixed in BEFORE the MoL base class: its forward / forward_filtered are
     the modules' own."""
 
+    HIDDEN_FUSED_MIN_VISIBLE = 0.5         # hidden_scan_route's fraction (as MoLAvgTopK's)
     fused_component_min_items = 262144     # below this the (B * P_Q * P_X, N) component scores are small and one launch chain shorter
     NO_FILTER_FUSION = False               # tests: True keeps the seen-id filter out of the selection launch
 
@@ -2105,6 +2286,9 @@ class _ComponentCandidates:
         n = table.shape[1]
         if k_per_group > n:
             raise RuntimeError(f"selected index k out of range (k={k_per_group}, n={n})")
+        self._check_k_visible(k_per_group)
+        vis = self._visible_mask()      # a hidden set: as in MoLAvgTopK._coarse_topk_from_eq
+        fused_ok = vis is None or hidden_scan_route(n, self.num_visible, k_per_group, self.HIDDEN_FUSED_MIN_VISIBLE) == "fused"
         # the component scans keep the fragments of all B * P_Q query rows in LDS and (the fused form) eight row tiles of running maxima in
         # registers (four at d = 128): batches beyond 256 (128) query rows go in slices
         max_b = max(1, (128 if eng.spec.dot_product_dimension >= 128 else 256) // eng.spec.query_dot_product_groups)
@@ -2113,7 +2297,7 @@ class _ComponentCandidates:
             return (torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)) if with_scores else torch.cat(parts, dim=0)
         # large corpora: fused scan + threshold select, no (B*P_Q*P_X, N) score matrix (5.7 GB at amzn-books, B = 32);
         # identical to the materialising path below whenever every row's candidate count is inside [k, capacity]
-        if n >= self.fused_component_min_items and not self._no_fused:
+        if n >= self.fused_component_min_items and not self._no_fused and fused_ok:
             rows = eq.shape[0] * eng.spec.query_dot_product_groups * eng.spec.item_dot_product_groups
             on_device = rows * n * 4 <= MoLAvgTopK.DEVICE_REDO_BYTES
             if on_device:
@@ -2122,11 +2306,13 @@ class _ComponentCandidates:
                 # the verdict word in pinned host memory, written by the kernels themselves: the caller spins on an event and reads it (no 4-byte
                 # copy launch, no blocking .item(): ~30 us of every Naive / Comb call at amzn-books)
                 flag = _pinned_word(self)
-            fused = eng.component_topk(eq, table, k_per_group, flag)
+            fused = eng.component_topk(eq, table, k_per_group, flag, visible=self._visible)
             if fused is not None:
                 sc_c, pos, counts = fused
                 if on_device:     # redo on the device under the flag, as in MoLAvgTopK._coarse_topk_from_eq
                     scores = eng.component_scores(eq, table, out=self._buf("component_all", rows * n, torch.float32).view(rows, n), run_if=flag)
+                    if vis is not None:
+                        E.scores_mask(scores, vis, run_if=flag)
                     E.topk(scores, k_per_group, out=(sc_c, pos), run_if=flag)
                     return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
                 if pending is not None:      # a device verdict word (1 = redo), read by the caller once everything is enqueued
@@ -2135,6 +2321,8 @@ class _ComponentCandidates:
                 if int(flag.item()) == 0:
                     return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
         scores = eng.component_scores(eq, table)
+        if vis is not None:
+            E.scores_mask(scores, vis)
         sc_c, pos = E.topk(scores, k_per_group)
         return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
 
@@ -2277,6 +2465,12 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
                                       "centroids the index has)")
         if self._use_faiss and n_left is not None and 0 < n_left < self._ivf_args["nlist"]:      # (the constructor's refusal; n_left < 1 is removal_plan's)
             raise ValueError(f"MoLNaiveTopK: {n_left} items cannot fill nlist = {self._ivf_args['nlist']} lists")
+
+    def _check_hideable(self, what: str) -> None:
+        if self._use_faiss:
+            raise NotImplementedError(f"MoLNaiveTopK.{what}: the IVF index (use_faiss=True{', frozen_centroids=True' if self._frozen_centroids else ''}) searches "
+                                      "its lists without a visibility test -- a hidden set is not built for it; remove_items (under frozen_centroids=True) "
+                                      "deletes for good, and the exhaustive MoLNaiveTopK takes hide_items")
 
     # ---- in-place corpus changes under frozen centroids: the lists of a held index follow, behind every other buffer -----------------------
     def _ivf_resize(self, eng, n_new: int) -> None:
