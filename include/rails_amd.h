@@ -46,7 +46,9 @@ extern "C" {
  * 14: the IVF-Flat component index rails_ivf_* (MoLNaiveTopK use_faiss=True) is new;
  * 15: the shape-generic fp32 scoring route rails_mol_generic_* is new; the candidate-key entry points rails_group_keys_* of the item-sharded
  * MoLNaiveTopK / MoLCombTopK, the list edit rails_ivf_lists_edit[_workspace_bytes] of the IVF index, the item masks rails_item_mask_* /
- * rails_scores_mask and the hidden-item entries rails_item_mask_clear / rails_mol_coarse_topk_visible / rails_mol_component_topk_visible
+ * rails_scores_mask, the hidden-item entries rails_item_mask_clear / rails_mol_coarse_topk_visible / rails_mol_component_topk_visible and the
+ * item-tag entries rails_item_tags_effective / rails_item_tags_count / rails_item_mask_from_tags / rails_scores_mask_tags / rails_mol_coarse_topk_tagged /
+ * rails_mol_component_topk_tagged / rails_mol_scan_plan
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -353,6 +355,28 @@ int rails_item_mask_positions(const uint32_t* words, int32_t rows, int64_t n, in
 int rails_scores_mask(float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const uint32_t* words, int64_t words_row_stride,
                       float fill, const int32_t* run_if, void* stream);
 
+/* ---- item tags (added under ABI 15; no counterpart in the reference) ------------------------------
+ * One 32-bit word of attributes per item, bit j = the item carries attribute j; a call carries one ALLOW word per query row (or one for the
+ * whole batch) and row b may return item x iff tags[x] & allowed[b] != 0.  Every kernel reads the EFFECTIVE tags: the word of a hidden
+ * item is 0, so a hidden item matches no word.  All arrays live in device memory. */
+/* eff_out[i] = tags[i] where bit i of the visibility row (rails_item_mask_words(n) words, bit set = visible) is set, else 0. */
+int rails_item_tags_effective(const uint32_t* tags, const uint32_t* visible_words, int64_t n, uint32_t* eff_out, void* stream);
+/* counts_out[j] = the number of items i < n with eff_tags[i] & words[j] != 0, for j < n_words (at most 65 536): how many items each allow
+ * word keeps.  One workgroup per word; the caller reads a count back once and keeps it. */
+int rails_item_tags_count(const uint32_t* eff_tags, int64_t n, const uint32_t* words, int32_t n_words, int32_t* counts_out, void* stream);
+/* The item mask of a tag filter: bit i of row r of words_out (`rows` rows of rails_item_mask_words(n) words, the unused high bits zero) is
+ * set iff eff_tags[i] & allowed[r] != 0 -- packed with one wave ballot per 64 items, as rails_item_mask_pack packs bool bytes --, and
+ * counts_out[r] = the row's set bits.  What the exact modules hand to their masked strategies. */
+int rails_item_mask_from_tags(const uint32_t* eff_tags, int64_t n, const uint32_t* allowed, int32_t rows, uint32_t* words_out, int32_t* counts_out,
+                              void* stream);
+/* rails_scores_mask with the tag test in place of a mask bit.  In place: scores[r * ld + x] = fill for x < n wherever
+ * eff_tags[first_item + x] & allowed[r / rows_per_allowed] == 0; kept entries are neither read nor written.  eff_tags holds at least
+ * first_item + n words, allowed at least ceil(rows / rows_per_allowed).  rows_per_allowed maps the rows of a matrix with several rows per
+ * query (the B * P_Q * P_X rows of the component scores: P_Q * P_X) to batch rows; rows_per_allowed = rows: one word for all.
+ * run_if: the launch predicate. */
+int rails_scores_mask_tags(float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const uint32_t* eff_tags, const uint32_t* allowed,
+                           int32_t rows_per_allowed, float fill, const int32_t* run_if, void* stream);
+
 /* Per-row candidates: out[bq * n_cand + x] = <queries[bq], items[bq / r][x]> for queries (n_queries, dim) and items
  * (n_queries / r, n_cand, dim) -- the two bmm branches of DotProductSimilarity.forward
  * (rails/similarities/dot_product_similarity_fn.py:55-68). */
@@ -405,6 +429,22 @@ int rails_mol_coarse_topk_visible(const rails_mol_shape* shape, const float* eq,
                                   const void* table, int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes,
                                   float* out_scores, int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range,
                                   void* prefilter, const uint32_t* visible_words, void* stream);
+/* The same with a PER-ROW filter by item tags (added under ABI 15): eff_tags holds the effective 32-bit tag word of each of the n_items items
+ * (0 for a hidden item, rails_item_tags_effective), allowed one allow word per query b < batch; row b may return item x iff
+ * eff_tags[x] & allowed[b] != 0.  The sample scan lets a score into row b's group maxima only where the test holds, the streaming pass
+ * appends only such candidates (counts count them), so the outputs are those of rails_mol_coarse_score + rails_scores_mask_tags(fill =
+ * -inf) + rails_topk under the same counts check.  The call launches the scans' tagged kernels; eff_tags == NULL is rails_mol_coarse_topk
+ * itself, launch for launch.  With a pre-filter the int8 pass is kept for d <= 64 (its tagged kernel reads a fired tile's tag words and keeps
+ * a row's allowed suspects only); at d = 128 the pass reads the bf16 table (same outputs), as for rails_mol_coarse_topk_visible. */
+int rails_mol_coarse_topk_tagged(const rails_mol_shape* shape, const float* eq, int32_t batch, int32_t average_queries,
+                                 const void* table, int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes,
+                                 float* out_scores, int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range,
+                                 void* prefilter, const uint32_t* eff_tags, const uint32_t* allowed, void* stream);
+/* The numbers of the plan behind rails_mol_coarse_topk (comp_rows = 0, rows = batch) or rails_mol_component_topk (rows = batch * P_Q * P_X,
+ * comp_rows = batch * P_Q) that the routing rule of a tagged call needs (added under ABI 15): out4 = {stride, r, G, s} -- the sample visits
+ * every stride-th tile of 32 items, the threshold is the r-th largest of G per-group maxima and a group holds about s sampled items (G
+ * counted for the d = 32 trip of four tiles: a lower bound at larger d).  Returns 1, or 0 where the sizes have no plan.  Host arithmetic. */
+int32_t rails_mol_scan_plan(int32_t rows, int64_t n_items, int32_t k, int32_t comp_rows, int32_t* out4);
 /* Optional int8 pre-filter of rails_mol_coarse_topk's streaming pass (no counterpart in the reference; it changes what the pass
  * READS, not what it returns): a copy of the coarse table as int8 with one scale (256-byte header + d bytes per item).  With it the
  * streaming pass reads the int8 copy, one int8 MFMA per 32 items, against a per-query integer bound that no item reaching the
@@ -448,6 +488,13 @@ int rails_mol_component_topk_visible(const rails_mol_shape* shape, const float* 
                                      int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
                                      int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, const uint32_t* visible_words,
                                      void* stream);
+/* The same with a per-row filter by item tags (added under ABI 15): eff_tags / allowed as for rails_mol_coarse_topk_tagged, allowed[b] shared
+ * by the P_Q * P_X rows of query b.  The tagged sample keeps four row tiles of maxima: batch * P_Q <= 128 query rows (RAILS_ENOTSUP beyond;
+ * the caller slices the batch).  eff_tags == NULL is rails_mol_component_topk itself. */
+int rails_mol_component_topk_tagged(const rails_mol_shape* shape, const float* eq, int32_t batch, const void* table, int64_t n_items,
+                                    int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
+                                    int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, const uint32_t* eff_tags,
+                                    const uint32_t* allowed, void* stream);
 /* ---- IVF-Flat index over the item components (MoLNaiveTopK use_faiss=True) ------------------------------------------
  * Replaces the per-item-group faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) of rails/indexing/mol_top_k.py:176-199
  * and its search (:223-238): one independent index per item group m < P_X over the fp16-rounded components fp16(Ex[:, m, :]).

@@ -743,6 +743,38 @@ int rails_scores_mask(float* scores, int64_t ld, int32_t rows, int64_t n, int64_
   return fail(scores_mask(scores, ld, rows, n, first_item, words, words_row_stride, fill, run_if, (hipStream_t)stream), "scores_mask");
 }
 
+int rails_item_tags_effective(const uint32_t* tags, const uint32_t* visible_words, int64_t n, uint32_t* eff_out, void* stream) {
+  const int go = item_mask_args("item_tags_effective", tags && visible_words && eff_out, 1, n);
+  return go <= 0 ? go : fail(item_tags_effective(tags, visible_words, n, eff_out, (hipStream_t)stream), "item_tags_effective");
+}
+
+int rails_item_tags_count(const uint32_t* eff_tags, int64_t n, const uint32_t* words, int32_t n_words, int32_t* counts_out, void* stream) {
+  g_err[0] = '\0';
+  if (n_words == 0) return RAILS_OK;
+  if (n_words < 0 || n_words > (1 << 16)) { set_error("item_tags_count: n_words = %d outside [0, 65536]", n_words); return RAILS_EINVAL; }
+  const int go = item_mask_args("item_tags_count", eff_tags && words && counts_out, 1, n);
+  return go <= 0 ? go : fail(item_tags_count(eff_tags, n, words, n_words, counts_out, (hipStream_t)stream), "item_tags_count");
+}
+
+int rails_item_mask_from_tags(const uint32_t* eff_tags, int64_t n, const uint32_t* allowed, int32_t rows, uint32_t* words_out, int32_t* counts_out,
+                              void* stream) {
+  const int go = item_mask_args("item_mask_from_tags", eff_tags && allowed && words_out && counts_out, rows, n);
+  return go <= 0 ? go : fail(item_mask_from_tags(eff_tags, n, allowed, rows, words_out, counts_out, (hipStream_t)stream), "item_mask_from_tags");
+}
+
+int rails_scores_mask_tags(float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const uint32_t* eff_tags, const uint32_t* allowed,
+                           int32_t rows_per_allowed, float fill, const int32_t* run_if, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || n < 0 || ld < n || first_item < 0 || first_item + n >= (1LL << 31)) {
+    set_error("scores_mask_tags: bad size (rows = %d, n = %lld, ld = %lld, first_item = %lld)", rows, (long long)n, (long long)ld, (long long)first_item);
+    return RAILS_EINVAL;
+  }
+  if (rows == 0 || n == 0) return RAILS_OK;
+  if (!scores || !eff_tags || !allowed) { set_error("scores_mask_tags: NULL pointer"); return RAILS_EINVAL; }
+  if (rows_per_allowed < 1) { set_error("scores_mask_tags: rows_per_allowed = %d < 1", rows_per_allowed); return RAILS_EINVAL; }
+  return fail(scores_mask_tags(scores, ld, rows, n, first_item, eff_tags, allowed, rows_per_allowed, fill, run_if, (hipStream_t)stream), "scores_mask_tags");
+}
+
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s) || n_items < 0) return 0;
   return (size_t)n_items * (size_t)s->dot_product_dimension * 2;
@@ -807,6 +839,11 @@ int32_t rails_mol_coarse_topk_capacity(int32_t batch, int64_t n_items, int32_t k
   return batch > 0 ? coarse_topk_capacity(batch, n_items, k_prime) : 0;
 }
 
+static int coarse_topk_entry(const rails_mol_shape* s, const float* eq, int32_t batch, int32_t average_queries, const void* table,
+                             int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes, float* out_scores,
+                             int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* prefilter,
+                             const uint32_t* visible_words, const uint32_t* eff_tags, const uint32_t* allowed, void* stream);
+
 int rails_mol_coarse_topk(const rails_mol_shape* s, const float* eq, int32_t batch, int32_t average_queries, const void* table,
                           int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes, float* out_scores,
                           int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* prefilter, void* stream) {
@@ -818,6 +855,23 @@ int rails_mol_coarse_topk_visible(const rails_mol_shape* s, const float* eq, int
                                   int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes, float* out_scores,
                                   int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* prefilter,
                                   const uint32_t* visible_words, void* stream) {
+  return coarse_topk_entry(s, eq, batch, average_queries, table, n_items, k_prime, workspace, workspace_bytes, out_scores, out_positions, out_counts,
+                           out_of_range, prefilter, visible_words, nullptr, nullptr, stream);
+}
+
+int rails_mol_coarse_topk_tagged(const rails_mol_shape* s, const float* eq, int32_t batch, int32_t average_queries, const void* table,
+                                 int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes, float* out_scores,
+                                 int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* prefilter,
+                                 const uint32_t* eff_tags, const uint32_t* allowed, void* stream) {
+  if (eff_tags && !allowed) { g_err[0] = '\0'; set_error("coarse_topk_tagged: eff_tags without allowed"); return RAILS_EINVAL; }
+  return coarse_topk_entry(s, eq, batch, average_queries, table, n_items, k_prime, workspace, workspace_bytes, out_scores, out_positions, out_counts,
+                           out_of_range, prefilter, nullptr, eff_tags, eff_tags ? allowed : nullptr, stream);
+}
+
+static int coarse_topk_entry(const rails_mol_shape* s, const float* eq, int32_t batch, int32_t average_queries, const void* table,
+                             int64_t n_items, int32_t k_prime, void* workspace, size_t workspace_bytes, float* out_scores,
+                             int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* prefilter,
+                             const uint32_t* visible_words, const uint32_t* eff_tags, const uint32_t* allowed, void* stream) {
   g_err[0] = '\0';
   if (!shape_ok(s)) return RAILS_EINVAL;
   if (batch < 0 || n_items < 0 || k_prime < 0) { set_error("coarse_topk: negative size"); return RAILS_EINVAL; }
@@ -827,7 +881,7 @@ int rails_mol_coarse_topk_visible(const rails_mol_shape* s, const float* eq, int
   const int cu = compute_units();
   if (cu <= 0) { set_error("coarse_topk: no HIP device"); return RAILS_ELAUNCH; }
   const int r = coarse_topk(*s, eq, batch, average_queries ? 1 : 0, table, n_items, k_prime, workspace, workspace_bytes,
-                            out_scores, out_positions, out_counts, out_of_range, prefilter, cu, (hipStream_t)stream, visible_words);
+                            out_scores, out_positions, out_counts, out_of_range, prefilter, cu, (hipStream_t)stream, visible_words, eff_tags, allowed);
   return r == kOk ? r : fail(r, "coarse_topk");
 }
 
@@ -870,6 +924,11 @@ int32_t rails_mol_component_topk_capacity(const rails_mol_shape* s, int32_t batc
   return component_topk_capacity(*s, batch, n_items, k_group);
 }
 
+static int component_topk_entry(const rails_mol_shape* s, const float* eq, int32_t batch, const void* table, int64_t n_items,
+                                int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
+                                int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, const uint32_t* visible_words,
+                                const uint32_t* eff_tags, const uint32_t* allowed, void* stream);
+
 int rails_mol_component_topk(const rails_mol_shape* s, const float* eq, int32_t batch, const void* table, int64_t n_items,
                              int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
                              int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, void* stream) {
@@ -881,6 +940,28 @@ int rails_mol_component_topk_visible(const rails_mol_shape* s, const float* eq, 
                                      int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
                                      int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, const uint32_t* visible_words,
                                      void* stream) {
+  return component_topk_entry(s, eq, batch, table, n_items, k_group, workspace, workspace_bytes, out_scores, out_positions, out_counts, out_of_range,
+                              visible_words, nullptr, nullptr, stream);
+}
+
+int rails_mol_component_topk_tagged(const rails_mol_shape* s, const float* eq, int32_t batch, const void* table, int64_t n_items,
+                                    int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
+                                    int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, const uint32_t* eff_tags,
+                                    const uint32_t* allowed, void* stream) {
+  if (eff_tags && !allowed) { g_err[0] = '\0'; set_error("component_topk_tagged: eff_tags without allowed"); return RAILS_EINVAL; }
+  return component_topk_entry(s, eq, batch, table, n_items, k_group, workspace, workspace_bytes, out_scores, out_positions, out_counts, out_of_range,
+                              nullptr, eff_tags, eff_tags ? allowed : nullptr, stream);
+}
+
+int32_t rails_mol_scan_plan(int32_t rows, int64_t n_items, int32_t k, int32_t comp_rows, int32_t* out4) {
+  if (!out4 || rows < 1 || n_items < 1 || k < 1 || comp_rows < 0) return 0;
+  return scan_plan_numbers(rows, n_items, k, comp_rows, out4);
+}
+
+static int component_topk_entry(const rails_mol_shape* s, const float* eq, int32_t batch, const void* table, int64_t n_items,
+                                int32_t k_group, void* workspace, size_t workspace_bytes, float* out_scores,
+                                int64_t* out_positions, int32_t* out_counts, int32_t* out_of_range, const uint32_t* visible_words,
+                                const uint32_t* eff_tags, const uint32_t* allowed, void* stream) {
   g_err[0] = '\0';
   if (!shape_ok(s)) return RAILS_EINVAL;
   if (batch < 0 || n_items < 0 || k_group < 0) { set_error("component_topk: negative size"); return RAILS_EINVAL; }
@@ -890,7 +971,7 @@ int rails_mol_component_topk_visible(const rails_mol_shape* s, const float* eq, 
   const int cu = compute_units();
   if (cu <= 0) { set_error("component_topk: no HIP device"); return RAILS_ELAUNCH; }
   const int r = component_topk(*s, eq, batch, table, n_items, k_group, workspace, workspace_bytes, out_scores, out_positions,
-                               out_counts, out_of_range, cu, (hipStream_t)stream, visible_words);
+                               out_counts, out_of_range, cu, (hipStream_t)stream, visible_words, eff_tags, allowed);
   return r == kOk ? r : fail(r, "component_topk");
 }
 

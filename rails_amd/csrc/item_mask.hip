@@ -10,6 +10,8 @@
 //                 1. per-tile popcounts  2. exclusive scan of a row's tile counts (64-bit, one workgroup per row, looping)
 //                 3. every tile writes its positions behind its offset  4. the slots past the row's count are set to 0
 //   scores_mask scores[b][x] = fill where bit first_item + x of row b's mask is clear; kept entries are neither read nor written
+//   item tags    effective tags, kept counts per allow word, a filter's mask rows, scores[r][x] = fill where item x carries
+//               no bit of row r's allow word
 // All plain C++ with vector stores, no LDS beyond the 4-word reductions, every loop grid-strided with 64-bit indices (rows of 125 M bits).
 #include <hip/hip_runtime.h>
 
@@ -195,13 +197,97 @@ __global__ void __launch_bounds__(kThreads) scores_mask_kernel(float* __restrict
   }
 }
 
+// ---- item tags: one 32-bit word of attributes per item; row b of a call may return item x iff eff[x] & allowed[b] != 0.
+// (Named apart from the item_mask_* / scores_mask kernels: tests/test_item_mask_cpu.py pins that family's list.)  Plain C++, vector stores,
+// grid-strided loops with 64-bit indices; every index is tested against n before it is used.
+
+// eff[i] = tags[i] where bit i of the visibility row is set, else 0: a hidden item carries no attribute
+__global__ void __launch_bounds__(kThreads) item_tags_effective_kernel(const u32* __restrict__ tags, const u32* __restrict__ visible, int64_t n,
+                                                                      u32* __restrict__ eff) {
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
+    eff[i] = ((visible[i >> 5] >> (int)(i & 31)) & 1u) ? tags[i] : 0u;
+}
+
+// counts[j] = #{i < n : eff[i] & words[j] != 0}: one workgroup per word (a count is read back once per new word and cached by the caller)
+__global__ void __launch_bounds__(kThreads) item_tags_count_kernel(const u32* __restrict__ eff, int64_t n, const u32* __restrict__ words,
+                                                                  int32_t* __restrict__ counts) {
+  __shared__ int part[kWaves];
+  const u32 word = words[blockIdx.x];
+  int c = 0;
+  for (int64_t i = threadIdx.x; i < n; i += kThreads) c += (eff[i] & word) != 0u;
+  c = block_sum(c, part);
+  if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// the ItemMask rows of a tag filter: bit i of row r = (eff[i] & allowed[r]) != 0, packed with a ballot as item_mask_pack_kernel packs bool bytes
+__global__ void __launch_bounds__(kThreads) item_tags_to_mask_kernel(const u32* __restrict__ eff, int64_t n, int64_t n_words, const u32* __restrict__ allowed,
+                                                                    int rows, u32* __restrict__ words) {
+  const int64_t chunks = (n + kThreads - 1) / kThreads, total = chunks * rows;
+  for (int64_t c = blockIdx.x; c < total; c += gridDim.x) {
+    const int64_t row = c / chunks, ch = c - row * chunks;
+    const int64_t i = ch * kThreads + threadIdx.x;
+    const bool set = i < n && (eff[i] & allowed[row]) != 0u;
+    const u64 b = __ballot(set);
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (ch * kThreads + (threadIdx.x & ~63)) >> 5;      // the first of this wave's two words
+    if (lane == 0 && w < n_words) words[row * n_words + w] = (u32)b;
+    if (lane == 32 && w + 1 < n_words) words[row * n_words + w + 1] = (u32)(b >> 32);
+  }
+}
+
+// scores_mask_kernel's shape with a tag test in place of the mask bit: row r of the matrix belongs to allow word r / rows_per_allowed
+__global__ void __launch_bounds__(kThreads) scores_tags_fill_kernel(float* __restrict__ scores, int64_t ld, int rows, int64_t n, int64_t first_item,
+                                                                   const u32* __restrict__ eff, const u32* __restrict__ allowed, int rows_per_allowed,
+                                                                   float fill, const int32_t* __restrict__ run_if) {
+  MOL_RUN_IF(run_if);
+  constexpr int64_t kChunk = (int64_t)kThreads * kMaskPerThread;
+  const int64_t chunks = (n + kChunk - 1) / kChunk, total = chunks * rows;
+  for (int64_t c = blockIdx.x; c < total; c += gridDim.x) {
+    const int64_t row = c / chunks, ch = c - row * chunks;
+    const u32 allow = allowed[row / rows_per_allowed];
+    float* srow = scores + row * ld;
+#pragma unroll
+    for (int j = 0; j < kMaskPerThread; ++j) {
+      const int64_t x = ch * kChunk + (int64_t)j * kThreads + threadIdx.x;
+      if (x < n && (eff[first_item + x] & allow) == 0u) srow[x] = fill;
+    }
+  }
+}
+
 static inline int launched() { return hipGetLastError() == hipSuccess ? kOk : kErrLaunch; }
+
+int item_tags_effective(const void* tags, const void* visible, int64_t n, void* eff, hipStream_t stream) {
+  hipLaunchKernelGGL(item_tags_effective_kernel, dim3(grid_for((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, (const u32*)tags, (const u32*)visible,
+                     n, (u32*)eff);
+  return launched();
+}
+
+int item_tags_count(const void* eff, int64_t n, const void* words, int n_words, int32_t* counts, hipStream_t stream) {
+  hipLaunchKernelGGL(item_tags_count_kernel, dim3((unsigned)n_words), dim3(kThreads), 0, stream, (const u32*)eff, n, (const u32*)words, counts);
+  return launched();
+}
+
+int scores_mask_tags(float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const void* eff, const void* allowed, int rows_per_allowed,
+                     float fill, const int32_t* run_if, hipStream_t stream) {
+  const int64_t chunks = (n + (int64_t)kThreads * kMaskPerThread - 1) / ((int64_t)kThreads * kMaskPerThread);
+  hipLaunchKernelGGL(scores_tags_fill_kernel, dim3(grid_for(chunks * rows)), dim3(kThreads), 0, stream, scores, ld, rows, n, first_item, (const u32*)eff,
+                     (const u32*)allowed, rows_per_allowed, fill, run_if);
+  return launched();
+}
 
 int64_t item_mask_words(int64_t n) { return (n + 31) / 32; }
 
 int item_mask_count(const void* words, int rows, int64_t n, int32_t* counts, hipStream_t stream) {
   hipLaunchKernelGGL(item_mask_count_kernel, dim3((unsigned)rows), dim3(kThreads), 0, stream, (const u32*)words, n, item_mask_words(n), counts);
   return launched();
+}
+
+int item_mask_from_tags(const void* eff, int64_t n, const void* allowed, int rows, void* words, int32_t* counts, hipStream_t stream) {
+  const int64_t chunks = (n + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(item_tags_to_mask_kernel, dim3(grid_for(chunks * rows)), dim3(kThreads), 0, stream, (const u32*)eff, n, item_mask_words(n),
+                     (const u32*)allowed, rows, (u32*)words);
+  if (launched() != kOk) return kErrLaunch;
+  return item_mask_count(words, rows, n, counts, stream);
 }
 
 int item_mask_pack(const unsigned char* mask, int64_t ld, int rows, int64_t n, void* words, int32_t* counts, hipStream_t stream) {

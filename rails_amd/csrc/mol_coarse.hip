@@ -114,6 +114,13 @@ struct CoarseScanArgs {
   const unsigned int* visible;          // hidden items: one row of ItemMask words over the n items, bit set = visible; read by the
 };                                      // HIDDEN instantiations only (coarse_scan_visible_kernel), which the launch picks when it is not NULL
 
+// Item tags, the extra argument of the tagged kernels alone -- CoarseScanArgs and the kernels that take only it stay as they are.
+struct ScanTagArgs {
+  const unsigned int* tags;             // the EFFECTIVE tag word of each of the n items (0: hidden, or no attribute)
+  const unsigned int* allowed;          // one allow word per batch row b < a.B: row b may return item x iff tags[x] & allowed[b] != 0
+};
+constexpr int kVisAll = 0, kVisWords = 1, kVisTags = 2;      // the visibility form of a scan body: none, a.visible's words, per-row tags
+
 // Append path of the select scans.  A hit's slot comes from a device-scope atomic whose result takes ~2 us to return;
 // issued one by one inside the scan they serialise (a wave of the component scan met ~40 per tile: 2 ms for a 0.1 ms
 // scan).  Hits are therefore staged in a per-wave LDS list (LDS atomic cursor) and flushed once per tile, one entry per
@@ -209,9 +216,16 @@ __device__ __forceinline__ void quantise_query(const unsigned short* qfrag, int 
 // tests bit x.  The sample scan keeps a hidden item's score out of the running maxima -- else the threshold sits above the visible K'-th
 // score and the call falls to its redo --, the select scan's pre-test is unchanged (a hidden item may fire a tile) and keep_candidates clears
 // the hit mask of a hidden column.  The word's address is wave-uniform.  HIDDEN = false is the scan as it was, under its own symbols.
-template <int DC, int MODE, bool NT, int QTS, bool COMP, bool HIDDEN>   // DC = d / 16 K chunks; NT: non-temporal table loads; QTS: query tiles a sample launch keeps maxima for; COMP: the component scans' sample block
-__device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
-  static_assert(!HIDDEN || MODE != kScanAll, "the materialising scan is masked behind it (rails_scores_mask)");
+// TAGGED (VIS = kVisTags): the PER-ROW form.  load_trip fetches the effective tag word of each lane column's item (0 for a
+// tile past the end and the columns past a ragged end), the workgroup keeps the allow word of every query ROW in LDS behind everything
+// else (in component mode query row q belongs to batch row q / P_Q).  The sample scan lets score (row r, column x) into the running maximum
+// only where the column's word meets row r's allow word -- the sixteen allow words of a query tile sit in registers as ntlo does, and the
+// component block's whole-trip v_max3 path is not taken --; keep_candidates skips a tile whose 32 words are all 0 and keeps a hit of row q
+// only if tag & allow_s[q] != 0.  The pre-test is unchanged.
+template <int DC, int MODE, bool NT, int QTS, bool COMP, int VIS>   // DC = d / 16 K chunks; NT: non-temporal table loads; QTS: query tiles a sample launch keeps maxima for; COMP: the component scans' sample block
+__device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a, const ScanTagArgs& tg) {
+  constexpr bool HIDDEN = VIS == kVisWords, TAGGED = VIS == kVisTags;
+  static_assert(VIS == kVisAll || MODE != kScanAll, "the materialising scan is masked behind it (rails_scores_mask, rails_scores_mask_tags)");
   MOL_RUN_IF(a.run_if);
   extern __shared__ __attribute__((aligned(16))) unsigned short qfrag[];   // [n_qt][DC][64 lanes][8] bf16, then thr
   const int d = a.d, B = a.comp ? a.B * a.PQ : a.B;      // B: query ROWS from here on
@@ -232,6 +246,10 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
   unsigned int* const row_base_s = row_cnt_s + n_qt * 32;                                     // [n_qt * 32]
   StageEntry* const wg_stage = reinterpret_cast<StageEntry*>(row_base_s + n_qt * 32);        // [a.stage_cap], 16-byte aligned (every part is a multiple of 128 bytes)
   __shared__ unsigned int wg_n;
+  // TAGGED: the rows' allow words, behind the last thing the mode keeps in dynamic LDS (launch_coarse_scan sizes it)
+  unsigned int* const allow_s = MODE == kScanSelect ? reinterpret_cast<unsigned int*>(wg_stage + kWgStage) : reinterpret_cast<unsigned int*>(thr_s + 2 * n_qt * 32);
+  if constexpr (TAGGED)
+    for (int i = threadIdx.x; i < n_qt * 32; i += kScanThreads) allow_s[i] = i < B ? tg.allowed[a.comp ? i / a.PQ : i] : 0u;
   if (threadIdx.x < kScanThreads / 64) stage_n[threadIdx.x] = 0u;
   if (threadIdx.x == 0) wg_n = 0u;
   if (a.qfrag) {   // 16 bytes per thread and step instead of P_Q dependent loads per element (2 048 workgroups each made them)
@@ -278,6 +296,7 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
     int64_t item[TU];
     bool in[TU];
     unsigned int vis[HIDDEN ? TU : 1];      // HIDDEN: the tiles' visibility words (0 for a tile past the end)
+    unsigned int tag[TAGGED ? TU : 1];      // TAGGED: the tag word of this lane column's item (0 past the end)
   };
   auto load_trip = [&](int64_t w0, Trip& T) {
 #pragma unroll
@@ -287,6 +306,7 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
       if (!T.in[u]) item = a.n - 1;
       T.item[u] = item;
       if constexpr (HIDDEN) T.vis[u] = (w0 + u) < n_work ? a.visible[(w0 + u) * step] : 0u;      // (tile (w0 + u) * step < n_tiles = the row's words)
+      if constexpr (TAGGED) T.tag[u] = T.in[u] ? tg.tags[item] : 0u;                            // (in: the tile is inside the launch and item < n)
       const unsigned short* rowp = table + item * d + 8 * h;
 #pragma unroll
       for (int c = 0; c < DC; ++c) {
@@ -295,12 +315,17 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
       }
     }
   };
+  unsigned int allow_r[TAGGED && MODE == kScanSample ? 16 : 1];      // TAGGED sample scan: the allow words of the current query tile's sixteen rows
   auto load_query_tile = [&](int qt, bf16x8 (&A)[DC], cf32x16& ntlo) {
 #pragma unroll
     for (int c = 0; c < DC; ++c) A[c] = *reinterpret_cast<const bf16x8*>(qfrag + (((size_t)qt * DC + c) * 64 + lane) * 8);
     if constexpr (MODE == kScanSelect) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) ntlo[r] = ntlo_s[qt * 32 + acc_row(r, h)];
+    }
+    if constexpr (TAGGED && MODE == kScanSample) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) allow_r[r] = allow_s[qt * 32 + acc_row(r, h)];
     }
   };
   // Select mode, the rare part (K'/N of the scores pass, a few percent of the tiles at shard scale): the tiles of the trip whose
@@ -313,18 +338,20 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
       bf16x8 Bu[DC];
       int64_t item = 0;
       bool in = false;
-      unsigned int vis = ~0u;
+      unsigned int vis = ~0u, tag = ~0u;
       // constant indices from the front end on, so that the trip stays in registers
       auto pick = [&]<int V, int... C>(std::integral_constant<int, V>, std::integer_sequence<int, C...>) {
         item = T.item[V];
         in = T.in[V];
         if constexpr (HIDDEN) vis = T.vis[V];
+        if constexpr (TAGGED) tag = T.tag[V];
         ((Bu[C] = T.Bv[V][C]), ...);
       };
       [&]<int... V>(std::integer_sequence<int, V...>) {
         ((u == V ? pick(std::integral_constant<int, V>{}, std::make_integer_sequence<int, DC>{}) : (void)0), ...);
       }(std::make_integer_sequence<int, TU>{});
       if (HIDDEN && vis == 0u) continue;      // wave-uniform: nothing of a wholly hidden tile is kept
+      if (TAGGED && !__any(tag != 0u)) continue;      // wave-uniform too: no item of the tile carries an attribute
       cf32x16 acc = {0};
 #pragma unroll
       for (int c = 0; c < DC; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[c], Bu[c], acc, 0, 0, 0);
@@ -338,6 +365,7 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
       for (int r = 0; r < 16; ++r) mask |= acc[r] >= -ntlo[r] ? 1u << r : 0u;   // -ntlo = the bf16 value just below the threshold
       if (!in) mask = 0u;
       if (HIDDEN && !((vis >> x) & 1u)) mask = 0u;      // a hidden item is no candidate
+      if (TAGGED && tag == 0u) mask = 0u;               // nor is one that no row may return (the per-row test follows in the rare loop)
       if (__any(mask != 0u)) {
         float* mine = acc_s + (wave * 16) * 64 + lane;
 #pragma unroll
@@ -349,7 +377,7 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
             const int q = qt * 32 + acc_row(r, h);
             const float thr = thr_s[q];
             const float sc = bf16_rn(mine[r * 64]);   // an un-rounded sum at or above the bound may round up to thr
-            if (q < B && sc >= thr) {
+            if (q < B && sc >= thr && (!TAGGED || (tag & allow_s[q]) != 0u)) {      // TAGGED: row q may return the item
               const unsigned long long key = make_key(sc, (unsigned int)item);
               const unsigned int i = atomicAdd(&wg_n, 1u);   // LDS
               if (i < (unsigned int)kWgStage) { wg_stage[i].key = key; wg_stage[i].orow = (unsigned int)q; }
@@ -386,7 +414,7 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
       for (int qt = 0; qt < QTS; ++qt) {
         if (qt < n_qt) {
           if (n_qt > 1) load_query_tile(qt, A, ntlo);
-          if constexpr (COMP) {
+          if constexpr (COMP && !TAGGED) {
             // whole trips inside the corpus (all but a wave's last): the maxima of two tiles per v_max3 -- 8 VALU instructions per block
             // instead of 32 (an add and a max per score), which is what bounds this launch at 256 query rows
             bool whole = w0 + TU <= n_work;
@@ -420,9 +448,14 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
             if (w0 + u < n_work) {                                   // a trip past the end holds the last row again: not a sample
               bool live = T.in[u];                                   // nor are the columns past the end of a ragged last tile
               if constexpr (HIDDEN) live = live && ((T.vis[u] >> x) & 1u);   // nor a hidden item
+              if constexpr (TAGGED) {                                // per ROW: the column's word against each row's allow word (0 where !in)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx[qt][r] = fmaxf(mx[qt][r], (T.tag[u] & allow_r[r]) != 0u ? acc[r] : -INFINITY);
+              } else {
               const float pen = live ? 0.0f : -INFINITY;
 #pragma unroll
               for (int r = 0; r < 16; ++r) mx[qt][r] = fmaxf(mx[qt][r], acc[r] + pen);
+              }
             }
           }
         }
@@ -510,9 +543,11 @@ __device__ __forceinline__ void coarse_scan_body(const CoarseScanArgs& a) {
 
 #define MOL_COARSE_SCAN_ATTRS __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(MODE == kScanSelect ? kScanWaves : 2, MODE == kScanSelect ? kScanWaves : 2)))
 template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>
-MOL_COARSE_SCAN_ATTRS void coarse_scan_kernel(CoarseScanArgs a) { coarse_scan_body<DC, MODE, NT, QTS, COMP, false>(a); }
+MOL_COARSE_SCAN_ATTRS void coarse_scan_kernel(CoarseScanArgs a) { coarse_scan_body<DC, MODE, NT, QTS, COMP, kVisAll>(a, ScanTagArgs{}); }
 template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>      // sample and select scans that honour a.visible
-MOL_COARSE_SCAN_ATTRS void coarse_scan_visible_kernel(CoarseScanArgs a) { coarse_scan_body<DC, MODE, NT, QTS, COMP, true>(a); }
+MOL_COARSE_SCAN_ATTRS void coarse_scan_visible_kernel(CoarseScanArgs a) { coarse_scan_body<DC, MODE, NT, QTS, COMP, kVisWords>(a, ScanTagArgs{}); }
+template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>      // sample and select scans that honour per-row allow words (tg)
+MOL_COARSE_SCAN_ATTRS void coarse_scan_tagged_kernel(CoarseScanArgs a, ScanTagArgs tg) { coarse_scan_body<DC, MODE, NT, QTS, COMP, kVisTags>(a, tg); }
 #undef MOL_COARSE_SCAN_ATTRS
 // the kernel of a launch: the visible form where the caller passed visibility words (never for the materialising scan)
 template <int DC, int MODE, bool NT = false, int QTS = kSampleMaxQT, bool COMP = false>
@@ -525,8 +560,19 @@ static auto scan_kernel_for(bool hidden) -> void (*)(CoarseScanArgs) {
 
 constexpr int kSampleMaxQTComp = 8;   // ... and of a component sample launch: B * P_Q <= 256 query rows
 
+// the tagged kernel of a launch: the sample and select scans at d = 32 / 64 / 128 with up to kSampleMaxQT query tiles of
+// running maxima -- the component sample's eight-tile block already holds 128 registers of maxima and is not built with sixteen allow words
+// on top: component calls beyond 32 * kSampleMaxQT query rows are sliced by the caller
+template <int DC, int MODE, bool NT>
+static auto tagged_kernel_for(bool comp) -> void (*)(CoarseScanArgs, ScanTagArgs) {
+  if constexpr (MODE == kScanSample) {
+    if (comp) return &coarse_scan_tagged_kernel<DC, MODE, NT, kSampleMaxQT, true>;
+  }
+  return &coarse_scan_tagged_kernel<DC, MODE, NT>;
+}
+
 template <int MODE>
-static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
+static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream, const ScanTagArgs* tg = nullptr) {
   const int rows = a.comp ? a.B * a.PQ : a.B;
   const int groups = a.groups > 0 ? a.groups : 1;
   const int n_qt = (rows + 31) / 32;
@@ -540,6 +586,7 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
     stage_cap = (lds + 1024 * sizeof(StageEntry) + 17 * 1024) * 3 <= 156 * 1024 ? 1024 : 512;
     lds += (size_t)stage_cap * sizeof(StageEntry);
   }
+  if (tg) lds += (size_t)n_qt * 32 * sizeof(unsigned int);      // the rows' allow words, behind everything else
   if (lds > 96 * 1024) { set_error("coarse scan: %d query rows x d %d do not fit LDS", rows, a.d); return kErrUnsupported; }
   const int64_t n_tiles = (a.n + 31) >> 5;
   const int64_t step = MODE == kScanSample ? a.stride : 1;
@@ -562,6 +609,23 @@ static int launch_coarse_scan(const CoarseScanArgs& a, hipStream_t stream) {
   const bool hidden = MODE != kScanAll && a.visible != nullptr;
   auto go = [&](auto nt) {
     constexpr bool NT = decltype(nt)::value;
+    if constexpr (MODE != kScanAll) {
+      if (tg) {
+        if (wide) return false;
+        void (*kernel)(CoarseScanArgs, ScanTagArgs) = nullptr;
+        switch (dc) {
+          case 2: kernel = tagged_kernel_for<2, MODE, NT>(a.comp != 0); break;
+          case 4: kernel = tagged_kernel_for<4, MODE, NT>(a.comp != 0); break;
+          case 8: kernel = tagged_kernel_for<8, MODE, NT>(a.comp != 0); break;
+          default: return false;
+        }
+        if (lds > 48 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
+          return false;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid, (unsigned)groups), dim3(kScanThreads), lds, stream, b, *tg);
+        return true;
+      }
+    }
     auto fire = [&](void (*kernel)(CoarseScanArgs)) {
       if (lds > 48 * 1024 &&
           hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
@@ -847,8 +911,12 @@ struct CoarseI8Args {
 };
 
 // HIDDEN: the integer pre-test is unchanged; a fired tile reads and keeps its VISIBLE suspects only (bit x of the tile's word, as in coarse_scan_body)
-template <int DC8, bool NT, bool HIDDEN>   // DC8 = d / 32 K chunks of the int8 MFMA; NT: non-temporal table loads
-__device__ __forceinline__ void coarse_scan_i8_body(const CoarseI8Args& a) {
+// TAGGED (VIS = kVisTags): the integer pre-test is unchanged as well; a fired tile fetches the effective tag word of each lane
+// column's item, `need` is narrowed to the columns whose word is not 0, and the rolled loop keeps a hit of row q only if tag & allow_s[q] != 0
+// (the rows' allow words sit in LDS behind the integer bounds: coarse_scan_i8_lds)
+template <int DC8, bool NT, int VIS>   // DC8 = d / 32 K chunks of the int8 MFMA; NT: non-temporal table loads
+__device__ __forceinline__ void coarse_scan_i8_body(const CoarseI8Args& a, const ScanTagArgs& tg) {
+  constexpr bool HIDDEN = VIS == kVisWords, TAGGED = VIS == kVisTags;
   constexpr int DC = 2 * DC8;
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];   // bf16 fragments, int8 fragments, thr, thr_lo, integer starts
   const int d = a.d, B = a.B;
@@ -858,6 +926,9 @@ __device__ __forceinline__ void coarse_scan_i8_body(const CoarseI8Args& a) {
   float* thr_s = reinterpret_cast<float*>(q8 + (size_t)n_qt * DC8 * 64 * 16);             // [n_qt * 32]
   float* tlo_s = thr_s + n_qt * 32;                                                        // the bf16 value below thr
   int* nb_s = reinterpret_cast<int*>(tlo_s + n_qt * 32);                                   // minus the integer bound
+  unsigned int* allow_s = reinterpret_cast<unsigned int*>(nb_s + n_qt * 32);               // TAGGED: the rows' allow words
+  if constexpr (TAGGED)
+    for (int i = threadIdx.x; i < n_qt * 32; i += kScanThreads) allow_s[i] = i < B ? tg.allowed[i] : 0u;
   __shared__ StageEntry stage_s[kScanThreads / 64][kStage];
   __shared__ unsigned int stage_n[kScanThreads / 64];
   __shared__ float acc_s[(kScanThreads / 64) * 16 * 64];
@@ -906,6 +977,11 @@ __device__ __forceinline__ void coarse_scan_i8_body(const CoarseI8Args& a) {
     int64_t item = tile * 32 + x;
     const bool in = item < a.n;
     if (!in) item = a.n - 1;
+    unsigned int tag = ~0u;
+    if constexpr (TAGGED) {      // (a coalesced 128-byte load per fired tile; 0 for the columns past a ragged end)
+      tag = in ? tg.tags[item] : 0u;
+      need = need && tag != 0u;
+    }
     const unsigned short* rowp = a.table + item * d + 8 * h;
     bf16x8 Bu[DC];
 #pragma unroll
@@ -932,7 +1008,7 @@ __device__ __forceinline__ void coarse_scan_i8_body(const CoarseI8Args& a) {
           mask &= mask - 1u;
           const int q = qt * 32 + acc_row(r, h);
           const float sc = bf16_rn(mine[r * 64]);
-          if (q < B && sc >= thr_s[q])
+          if (q < B && sc >= thr_s[q] && (!TAGGED || (tag & allow_s[q]) != 0u))      // TAGGED: row q may return the item
             stage_push(stage_s[wave], &stage_n[wave], a.keys, a.counts, a.cap, (int)(tile % kSubLists), (unsigned int)q,
                        make_key(sc, (unsigned int)item));
         }
@@ -996,23 +1072,26 @@ __device__ __forceinline__ void coarse_scan_i8_body(const CoarseI8Args& a) {
 
 #define MOL_COARSE_I8_ATTRS __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(kScan8Waves, kScan8Waves)))
 template <int DC8, bool NT>
-MOL_COARSE_I8_ATTRS void coarse_scan_i8_kernel(CoarseI8Args a) { coarse_scan_i8_body<DC8, NT, false>(a); }
+MOL_COARSE_I8_ATTRS void coarse_scan_i8_kernel(CoarseI8Args a) { coarse_scan_i8_body<DC8, NT, kVisAll>(a, ScanTagArgs{}); }
 template <int DC8, bool NT>      // the scan that honours a.visible; d = 32 and 64 (the d = 128 body spills: such calls take the bf16 select scan)
-MOL_COARSE_I8_ATTRS void coarse_scan_i8_visible_kernel(CoarseI8Args a) { coarse_scan_i8_body<DC8, NT, true>(a); }
+MOL_COARSE_I8_ATTRS void coarse_scan_i8_visible_kernel(CoarseI8Args a) { coarse_scan_i8_body<DC8, NT, kVisWords>(a, ScanTagArgs{}); }
+template <int DC8, bool NT>      // the scan that honours per-row allow words (tg); d = 32 and 64, as the visible form
+MOL_COARSE_I8_ATTRS void coarse_scan_i8_tagged_kernel(CoarseI8Args a, ScanTagArgs tg) { coarse_scan_i8_body<DC8, NT, kVisTags>(a, tg); }
 #undef MOL_COARSE_I8_ATTRS
 
 // dynamic LDS of the int8 select scan: the queries' bf16 fragments, their int8 fragments and three bound rows per query tile
-static size_t coarse_scan_i8_lds(int B, int d) {
+// (tagged: a fourth row, the allow words)
+static size_t coarse_scan_i8_lds(int B, int d, bool tagged = false) {
   const int n_qt = (B + 31) / 32, dc8 = d / 32;
-  return (size_t)n_qt * (2 * dc8 * 1024 + dc8 * 1024 + 3 * 32 * 4);
+  return (size_t)n_qt * (2 * dc8 * 1024 + dc8 * 1024 + (tagged ? 4 : 3) * 32 * 4);
 }
 // d = 128 with 97..128 queries needs 50 688 B, over the 48 KiB a launch gets without opting in: coarse_topk() then runs the bf16 select
 // scan, whose output is the same bit for bit (the pre-filter only decides WHICH tiles are scored from the bf16 table)
-static bool coarse_scan_i8_fits(int B, int d) { return (d == 32 || d == 64 || d == 128) && coarse_scan_i8_lds(B, d) <= 48 * 1024; }
+static bool coarse_scan_i8_fits(int B, int d, bool tagged = false) { return (d == 32 || d == 64 || d == 128) && coarse_scan_i8_lds(B, d, tagged) <= 48 * 1024; }
 
-static int launch_coarse_scan_i8(const CoarseI8Args& a, hipStream_t stream) {
+static int launch_coarse_scan_i8(const CoarseI8Args& a, hipStream_t stream, const ScanTagArgs* tg = nullptr) {
   const int n_qt = (a.B + 31) / 32, dc8 = a.d / 32;
-  const size_t lds = coarse_scan_i8_lds(a.B, a.d);
+  const size_t lds = coarse_scan_i8_lds(a.B, a.d, tg != nullptr);
   if (lds > 48 * 1024) { set_error("coarse int8 scan: batch %d x d %d does not fit LDS", a.B, a.d); return kErrUnsupported; }
   const int64_t n_tiles = (a.n + 31) >> 5;
   const int tu = kScan8TripKiB / dc8;
@@ -1021,6 +1100,13 @@ static int launch_coarse_scan_i8(const CoarseI8Args& a, hipStream_t stream) {
   if (grid < 1) return kOk;
   auto go = [&](auto nt) {
     constexpr bool NT = decltype(nt)::value;
+    if (tg) {
+      switch (dc8) {
+        case 1: hipLaunchKernelGGL((coarse_scan_i8_tagged_kernel<1, NT>), dim3((unsigned)grid), dim3(kScanThreads), lds, stream, a, *tg); return true;
+        case 2: hipLaunchKernelGGL((coarse_scan_i8_tagged_kernel<2, NT>), dim3((unsigned)grid), dim3(kScanThreads), lds, stream, a, *tg); return true;
+        default: return false;
+      }
+    }
     if (a.visible) {
       switch (dc8) {
         case 1: hipLaunchKernelGGL((coarse_scan_i8_visible_kernel<1, NT>), dim3((unsigned)grid), dim3(kScanThreads), lds, stream, a); return true;
@@ -1063,13 +1149,16 @@ int range_flag(const int32_t* v, int n, int lo, int hi, int32_t* flag, hipStream
 
 int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* table, int64_t n, int k_prime, void* ws,
                 size_t ws_bytes, float* out_scores, int64_t* out_pos, int32_t* out_counts, int32_t* out_flag, void* prefilter, int n_cu,
-                hipStream_t stream, const uint32_t* visible) {
+                hipStream_t stream, const uint32_t* visible, const uint32_t* tags, const uint32_t* allowed) {
   CoarseTopkPlan p;
+  if (tags && (visible || !allowed)) { set_error("coarse_topk: tags come with allow words and without visibility words (the effective tags hold the hidden set)"); return kErrUnsupported; }
+  const ScanTagArgs tga{tags, allowed};
+  const ScanTagArgs* tg = tags ? &tga : nullptr;
   if (!coarse_topk_plan(B, n, k_prime, &p, true)) { set_error("coarse_topk: unsupported size (B = %d, K' = %d, n = %lld)", B, k_prime, (long long)n); return kErrUnsupported; }
   if (n >= (1ll << 32)) { set_error("coarse_topk: n does not fit 32-bit positions; shard the corpus"); return kErrUnsupported; }
   if (ws_bytes < p.total) { set_error("coarse_topk: workspace too small"); return kErrNoMem; }
-  if (prefilter && !coarse_scan_i8_fits(B, s.dot_product_dimension)) prefilter = nullptr;   // decided BEFORE anything is enqueued: the bf16 select scan, same output
-  if (prefilter && visible && s.dot_product_dimension > 64) prefilter = nullptr;            // (no visible form of the d = 128 int8 scan: same output again)
+  if (prefilter && !coarse_scan_i8_fits(B, s.dot_product_dimension, tg != nullptr)) prefilter = nullptr;   // decided BEFORE anything is enqueued: the bf16 select scan, same output
+  if (prefilter && (visible || tg) && s.dot_product_dimension > 64) prefilter = nullptr;    // (no visible or tagged form of the d = 128 int8 scan: same output again)
   char* base = static_cast<char*>(ws);
   unsigned int* counts = reinterpret_cast<unsigned int*>(base);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + p.off_keys);
@@ -1089,7 +1178,7 @@ int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* tab
   float* qmeta = reinterpret_cast<float*>(base + p.off_qmeta);
   if (prefilter) { a.q8_out = q8; a.qmeta_out = qmeta; }
   a.scores16 = sample; a.ld = p.n_sample; a.stride = p.stride;
-  int rc = launch_coarse_scan<kScanSample>(a, stream);
+  int rc = launch_coarse_scan<kScanSample>(a, stream, tg);
   if (rc != kOk) return rc;
   rc = topk(nullptr, p.n_sample, B, p.n_sample, p.r, nullptr, 0, top_s, top_i, base + p.off_ws, p.topk_ws, n_cu, stream, nullptr, 0, 0, sample);
   if (rc != kOk) return rc;
@@ -1099,12 +1188,12 @@ int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* tab
     i8.table = static_cast<const unsigned short*>(table); i8.hdr = static_cast<PrefilterHeader*>(prefilter);   // the header's two statistics words are updated
     i8.table8 = static_cast<const signed char*>(prefilter) + kPrefilterHeader; i8.n = n; i8.B = B; i8.d = a.d;
     i8.thr = top_s + (p.r - 1); i8.thr_stride = p.r; i8.keys = keys; i8.cap = p.cap; i8.counts = counts; i8.visible = visible;
-    rc = launch_coarse_scan_i8(i8, stream);
+    rc = launch_coarse_scan_i8(i8, stream, tg);
   } else {
     a.qfrag = frag; a.qfrag_out = nullptr; a.zero_words = nullptr; a.n_zero = 0; a.zero_flag = nullptr; a.q8_out = nullptr; a.qmeta_out = nullptr;
     a.scores16 = nullptr; a.ld = 0; a.stride = 1;
     a.thr = top_s + (p.r - 1); a.thr_stride = p.r; a.keys = keys; a.cap = p.cap; a.counts = counts;
-    rc = launch_coarse_scan<kScanSelect>(a, stream);
+    rc = launch_coarse_scan<kScanSelect>(a, stream, tg);
   }
   if (rc != kOk) return rc;
   return select_sublists(keys, counts, B, p.cap, kSubLists, k_prime, out_scores, out_pos, out_counts, out_flag, stream);
@@ -1194,9 +1283,17 @@ size_t component_topk_workspace_bytes(const Shape& s, int B, int64_t n, int k_gr
 }
 
 int component_topk(const Shape& s, const float* eq, int B, const void* table, int64_t n, int k_group, void* ws, size_t ws_bytes,
-                   float* out_scores, int64_t* out_pos, int32_t* out_counts, int32_t* out_flag, int n_cu, hipStream_t stream, const uint32_t* visible) {
+                   float* out_scores, int64_t* out_pos, int32_t* out_counts, int32_t* out_flag, int n_cu, hipStream_t stream, const uint32_t* visible,
+                   const uint32_t* tags, const uint32_t* allowed) {
   const int rows = B * s.query_dot_product_groups * s.item_dot_product_groups;
   CoarseTopkPlan p;
+  if (tags && (visible || !allowed)) { set_error("component_topk: tags come with allow words and without visibility words"); return kErrUnsupported; }
+  if (tags && B * s.query_dot_product_groups > 32 * kSampleMaxQT) {      // (the tagged sample keeps four row tiles of maxima)
+    set_error("component_topk: %d query rows exceed the %d of the tagged scans; slice the batch", B * s.query_dot_product_groups, 32 * kSampleMaxQT);
+    return kErrUnsupported;
+  }
+  const ScanTagArgs tga{tags, allowed};
+  const ScanTagArgs* tg = tags ? &tga : nullptr;
   if (B * s.query_dot_product_groups > component_max_rows(s) || !coarse_topk_plan(rows, n, k_group, &p, true, B * s.query_dot_product_groups)) { set_error("component_topk: unsupported size (batch = %d, k = %d, n = %lld)", B, k_group, (long long)n); return kErrUnsupported; }
   if (n >= (1ll << 32)) { set_error("component_topk: n does not fit 32-bit positions; shard the corpus"); return kErrUnsupported; }
   if (ws_bytes < p.total) { set_error("component_topk: workspace too small"); return kErrNoMem; }
@@ -1212,7 +1309,7 @@ int component_topk(const Shape& s, const float* eq, int B, const void* table, in
   a.visible = visible;
   a.qfrag_out = frag; a.zero_words = counts; a.n_zero = rows * kSubLists; a.zero_flag = out_flag;
   a.scores16 = sample; a.ld = p.n_sample; a.stride = p.stride;
-  int rc = launch_coarse_scan<kScanSample>(a, stream);
+  int rc = launch_coarse_scan<kScanSample>(a, stream, tg);
   if (rc != kOk) return rc;
   (void)top_i; (void)n_cu;
   rc = bf16_rows_kth(sample, p.n_sample, rows, (int)p.n_sample, p.r, top_s, stream);      // thr[row] = the r-th largest of the row's maxima
@@ -1220,9 +1317,23 @@ int component_topk(const Shape& s, const float* eq, int B, const void* table, in
   a.qfrag = frag; a.qfrag_out = nullptr; a.zero_words = nullptr; a.n_zero = 0; a.zero_flag = nullptr;
   a.scores16 = nullptr; a.ld = 0; a.stride = 1;
   a.thr = top_s; a.thr_stride = 1; a.keys = keys; a.cap = p.cap; a.counts = counts;
-  rc = launch_coarse_scan<kScanSelect>(a, stream);
+  rc = launch_coarse_scan<kScanSelect>(a, stream, tg);
   if (rc != kOk) return rc;
   return select_sublists(keys, counts, rows, p.cap, kSubLists, k_group, out_scores, out_pos, out_counts, out_flag, stream);
+}
+
+// The numbers of a call's plan that the tagged routing rule needs: out = {stride, r, G, s} -- the sample visits every stride-th
+// tile, the threshold is the r-th largest of G per-(wave, lane column) maxima that hold sampled items, and a maximum is taken over about s
+// sampled items.  comp_rows = 0: the coarse plan of `rows` = B queries; else the component plan (rows = B * P_Q * P_X, comp_rows = B * P_Q).
+int scan_plan_numbers(int rows, int64_t n, int k, int comp_rows, int32_t* out) {
+  CoarseTopkPlan p;
+  if (!coarse_topk_plan(rows, n, k, &p, true, comp_rows)) return 0;
+  const int64_t n_tiles = (n + 31) >> 5, n_work = (n_tiles + p.stride - 1) / p.stride;
+  const int64_t waves = p.n_sample / 32;                          // the waves of the sample launch
+  const int64_t trips = (n_work + 3) / 4;                          // (coarse_topk_plan's count: a wave's trip is up to four tiles)
+  const int64_t busy = trips < waves ? trips : waves;              // waves that see a tile
+  out[0] = p.stride; out[1] = p.r; out[2] = (int32_t)(busy * 32); out[3] = (int32_t)((n_work + busy - 1) / busy);
+  return 1;
 }
 
 int component_topk_capacity(const Shape& s, int B, int64_t n, int k_group) {

@@ -124,13 +124,15 @@ size_t coarse_topk_workspace_bytes(const Shape& s, int B, int64_t n, int k_prime
 int coarse_topk_capacity(int B, int64_t n, int k_prime);
 int coarse_topk(const Shape& s, const float* eq, int B, int avg, const void* table, int64_t n, int k_prime, void* ws,
                 size_t ws_bytes, float* out_scores, int64_t* out_pos, int32_t* out_counts, int32_t* out_flag, void* prefilter, int n_cu,
-                hipStream_t stream, const uint32_t* visible = nullptr);      // visible: the hidden set's ItemMask row (the scans' visible kernels)
+                hipStream_t stream, const uint32_t* visible = nullptr,       // visible: the hidden set's ItemMask row (the scans' visible kernels)
+                const uint32_t* tags = nullptr, const uint32_t* allowed = nullptr);      // tags / allowed: effective item tags and one allow word per query (the tagged kernels)
 size_t coarse_prefilter_bytes(const Shape& s, int64_t n);
 int coarse_prefilter_build(const Shape& s, const void* table, int64_t n, void* prefilter, hipStream_t stream);
 size_t component_topk_workspace_bytes(const Shape& s, int B, int64_t n, int k_group);
 int component_topk(const Shape& s, const float* eq, int B, const void* table, int64_t n, int k_group, void* ws, size_t ws_bytes,
                    float* out_scores, int64_t* out_pos, int32_t* out_counts, int32_t* out_flag, int n_cu, hipStream_t stream,
-                   const uint32_t* visible = nullptr);
+                   const uint32_t* visible = nullptr, const uint32_t* tags = nullptr, const uint32_t* allowed = nullptr);
+int scan_plan_numbers(int rows, int64_t n, int k, int comp_rows, int32_t* out);      // {stride, r, groups of maxima, sampled items per group}; 0: no plan
 int component_topk_capacity(const Shape& s, int B, int64_t n, int k_group);
 // ---- HSTU query encoder, eval path (hstu.hip) ----
 int hstu_preprocess(const float* emb, const int64_t* ids, const int64_t* lengths, const float* pos_emb, int B, int N, int D,
@@ -228,6 +230,12 @@ int item_mask_pack(const unsigned char* mask, int64_t ld, int rows, int64_t n, v
 int item_mask_set(const int64_t* positions, int64_t m, int64_t n, void* words, hipStream_t stream);
 int item_mask_clear(const int64_t* positions, int64_t m, int64_t n, void* words, hipStream_t stream);
 int item_mask_count(const void* words, int rows, int64_t n, int32_t* counts, hipStream_t stream);
+// item tags: eff = one 32-bit word per item, 0 for a hidden item; allowed = one word per query row (or one for all)
+int item_tags_effective(const void* tags, const void* visible, int64_t n, void* eff, hipStream_t stream);
+int item_tags_count(const void* eff, int64_t n, const void* words, int n_words, int32_t* counts, hipStream_t stream);
+int item_mask_from_tags(const void* eff, int64_t n, const void* allowed, int rows, void* words, int32_t* counts, hipStream_t stream);
+int scores_mask_tags(float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const void* eff, const void* allowed, int rows_per_allowed,
+                     float fill, const int32_t* run_if, hipStream_t stream);
 size_t item_mask_positions_workspace_bytes(int rows, int64_t n);
 int item_mask_positions(const void* words, int rows, int64_t n, int64_t* out, int64_t out_ld, void* workspace, hipStream_t stream);
 int scores_mask(float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const void* words, int64_t words_row_stride, float fill,

@@ -9,7 +9,7 @@ import ctypes as C
 import dataclasses
 import math
 import os
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -652,7 +652,8 @@ class MolEngine:
         return pre
 
     def coarse_topk(self, eq: torch.Tensor, table: torch.Tensor, average_queries: bool, k_prime: int, with_flag: bool = False,
-                    prefilter: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None, visible: Optional[torch.Tensor] = None):
+                    prefilter: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None, visible: Optional[torch.Tensor] = None,
+                    tags: Optional["TagFilter"] = None):
         """Fused coarse scoring + exact top-K' (no (B, N) score matrix).  -> (scores (B, K'), positions (B, K'), counts (B,)
         int32) or None when the sizes are unsupported.  The result is exact iff K' <= counts[b] <= capacity for every b
         (see include/rails_amd.h); the caller checks and falls back to coarse_scores + topk otherwise.  with_flag: a fourth
@@ -660,9 +661,12 @@ class MolEngine:
         int32 word (device or PINNED HOST memory: the kernels store through the device-visible address, no copy is needed to read it).
         prefilter: build_coarse_prefilter(table) -- same outputs, the streaming pass reads the int8 copy.
         visible: the visibility words of a hidden set (one ItemMask row over the n items, bit set = visible): the top-K' of the visible items
-        alone, through the scans' visible kernels (rails_mol_coarse_topk_visible); None: rails_mol_coarse_topk, launch for launch."""
+        alone, through the scans' visible kernels (rails_mol_coarse_topk_visible); None: rails_mol_coarse_topk, launch for launch.
+        tags: a TagFilter (allowed_tags= resolved): row b's top-K' of the items it may return, through the scans' tagged
+        kernels (rails_mol_coarse_topk_tagged); its effective tags hold the hidden set, so `visible` is not passed with it."""
         B, n = eq.shape[0], table.shape[0]
         _check_visible_words(visible, n, table.device)
+        _check_tag_filter(tags, n, B, table.device, visible)
         memo = self.__dict__.setdefault("_coarse_ws_bytes", {})
         if (B, n, k_prime) not in memo:
             memo[(B, n, k_prime)] = self.lib.rails_mol_coarse_topk_workspace_bytes(C.byref(self.shape), B, n, k_prime)
@@ -691,7 +695,14 @@ class MolEngine:
         else:
             with_flag = True
         with _on_device(dev):
-            if visible is None:
+            if tags is not None:
+                _lib.check(
+                    self.lib.rails_mol_coarse_topk_tagged(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
+                                                          _ptr(ws), ws_bytes, _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag) if with_flag else None,
+                                                          _ptr(prefilter), _ptr(tags.eff), _ptr(tags.allowed_for(B)), _stream()),
+                    "rails_mol_coarse_topk_tagged",
+                )
+            elif visible is None:
                 _lib.check(
                     self.lib.rails_mol_coarse_topk(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
                                                    _ptr(ws), ws_bytes, _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag) if with_flag else None, _ptr(prefilter), _stream()),
@@ -737,13 +748,18 @@ class MolEngine:
         return out
 
     def component_topk(self, eq: torch.Tensor, table: torch.Tensor, k_group: int, flag: Optional[torch.Tensor] = None,
-                       visible: Optional[torch.Tensor] = None):
+                       visible: Optional[torch.Tensor] = None, tags: Optional["TagFilter"] = None):
         """Fused component scoring + exact top-k_group per (b, i, m) row (no (rows, N) score matrix).
         -> (scores (rows, k_group), positions (rows, k_group), counts (rows,) int32) or None when unsupported; exact iff
         k_group <= counts <= component_topk_capacity for every row -- `flag` (an int32 device scalar, zeroed by the call) is raised otherwise.
-        visible: as for coarse_topk (rails_mol_component_topk_visible), shared by every row."""
+        visible: as for coarse_topk (rails_mol_component_topk_visible), shared by every row.
+        tags: as for coarse_topk (rails_mol_component_topk_tagged), the P_Q * P_X rows of a query share its allow word; at most
+        TAGGED_COMPONENT_ROWS query rows (B * P_Q) per call -- None beyond, as for any unsupported size."""
         B, n = eq.shape[0], table.shape[1]
         _check_visible_words(visible, n, table.device)
+        _check_tag_filter(tags, n, B, table.device, visible)
+        if tags is not None and B * self.spec.query_dot_product_groups > TAGGED_COMPONENT_ROWS:
+            return None
         ws_bytes = self.lib.rails_mol_component_topk_workspace_bytes(C.byref(self.shape), B, n, k_group)
         if ws_bytes == 0:
             return None
@@ -759,7 +775,14 @@ class MolEngine:
         out_p = torch.empty((rows, k_group), dtype=torch.int64, device=dev)
         counts = torch.empty((rows,), dtype=torch.int32, device=dev)
         with _on_device(dev):
-            if visible is None:
+            if tags is not None:
+                _lib.check(
+                    self.lib.rails_mol_component_topk_tagged(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
+                                                             _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag), _ptr(tags.eff), _ptr(tags.allowed_for(B)),
+                                                             _stream()),
+                    "rails_mol_component_topk_tagged",
+                )
+            elif visible is None:
                 _lib.check(
                     self.lib.rails_mol_component_topk(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
                                                       _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag), _stream()),
@@ -1409,6 +1432,126 @@ def scores_mask(scores: torch.Tensor, mask: ItemMask, first_item: int = 0, fill:
     with _on_device(scores.device):
         _lib.check(_lib.load().rails_scores_mask(_ptr(scores), scores.stride(0) if rows > 1 else max(n, scores.stride(0)), rows, n, first_item, _ptr(mask.words),
                                                  0 if mask.shared else mask.words.stride(0), float(fill), _pred(run_if), _stream()), "rails_scores_mask")
+    return scores
+
+
+# ---- item tags (rails_item_tags_*, rails_item_mask_from_tags, rails_scores_mask_tags) ---------------------
+def tag_word_i32(word: int) -> int:
+    """A 32-bit tag word as the int32 that holds its bit pattern."""
+    return word - (1 << 32) if word >= 1 << 31 else word
+
+
+def item_tags_effective(tags: torch.Tensor, visible_words: torch.Tensor, n_items: int) -> torch.Tensor:
+    """(N,) int32: tags[i] where bit i of the visibility row is set, 0 where the item is hidden (rails_item_tags_effective) -- the one array
+    every tag kernel reads: a hidden item is an item that carries no attribute."""
+    eff = torch.empty_like(tags)
+    with _on_device(tags.device):
+        _lib.check(_lib.load().rails_item_tags_effective(_ptr(tags), _ptr(visible_words), n_items, _ptr(eff), _stream()), "rails_item_tags_effective")
+    return eff
+
+
+def item_tags_counts(eff: torch.Tensor, words: Sequence[int]) -> List[int]:
+    """How many items each allow word keeps: counts[j] = #{i : eff[i] & words[j] != 0} (rails_item_tags_count: one launch, ONE read-back)."""
+    w = torch.tensor([tag_word_i32(int(v)) for v in words], dtype=torch.int32).to(eff.device)
+    counts = torch.empty(len(words), dtype=torch.int32, device=eff.device)
+    with _on_device(eff.device):
+        _lib.check(_lib.load().rails_item_tags_count(_ptr(eff), eff.numel(), _ptr(w), len(words), _ptr(counts), _stream()), "rails_item_tags_count")
+    return [int(c) for c in counts.cpu()]
+
+
+TAGGED_COMPONENT_ROWS = 128      # query rows (B * P_Q) one rails_mol_component_topk_tagged call takes: four row tiles of running maxima
+
+
+def scan_plan(rows: int, n_items: int, k: int, comp_rows: int = 0) -> Optional[Tuple[int, int, int, int]]:
+    """(stride, r, G, s) of the plan behind the fused coarse top-K' (comp_rows = 0, rows = B) or the fused component top-k (rows = B * P_Q * P_X,
+    comp_rows = B * P_Q): every stride-th tile is sampled, the threshold is the r-th largest of G group maxima of about s sampled items each
+    (rails_mol_scan_plan; host arithmetic, no device).  None where the sizes have no plan."""
+    out = (C.c_int32 * 4)()
+    if not _lib.load().rails_mol_scan_plan(int(rows), int(n_items), int(k), int(comp_rows), out):
+        return None
+    return tuple(int(v) for v in out)
+
+
+def _check_tag_filter(tags, n_items: int, batch: int, device: torch.device, visible) -> None:
+    """The filter a tagged scan reads: the effective tags of exactly n_items items on the table's device, one allow word for the batch or one per
+    row, and no visibility row beside it -- checked before any launch."""
+    if tags is None:
+        return
+    if not isinstance(tags, TagFilter) or tags.n_items != n_items or tags.eff.device != device or tags.rows not in (1, batch):
+        raise ValueError(f"tags must be a TagFilter over the {n_items} items on {device} with 1 or {batch} allow words")
+    if visible is not None:
+        raise ValueError("tags and visible in one call: the filter's effective tags already hold the hidden set")
+
+
+class TagFilter:
+    """allowed_tags= of one call, resolved against a module's tags: `words` (one allow word shared by the batch, or one per query row, host
+    integers), `kept` (how many items each row may return, host integers), `eff` (the module's effective tags, (N,) int32) and `allowed` (the
+    words as int32 on the device).  Row b may return item x iff eff[x] & words[b] != 0.  Built by the module, which caches it per tuple of
+    words: a repeated filter costs a call neither a copy nor a sync."""
+
+    def __init__(self, eff: torch.Tensor, words: Tuple[int, ...], kept: Tuple[int, ...], allowed: Optional[torch.Tensor] = None, stamp=None):
+        self.eff, self.words, self.kept, self.stamp = eff, tuple(words), tuple(kept), stamp
+        self.n_items = eff.numel()
+        self.rows = len(self.words)
+        self.kept_min = min(self.kept)
+        self.allowed = allowed if allowed is not None else torch.tensor([tag_word_i32(w) for w in self.words], dtype=torch.int32).to(eff.device)
+        self._mask: Optional[ItemMask] = None
+        self._per_row: Optional[torch.Tensor] = None
+
+    def allowed_for(self, batch: int) -> torch.Tensor:
+        """The allow words as one int32 per query row of a batch (what the tagged scans read); a shared word is repeated, kept for the last batch size."""
+        if self.rows == batch:
+            return self.allowed
+        c = self._per_row
+        if c is None or c.numel() != batch:
+            c = self._per_row = self.allowed.expand(batch).contiguous()
+        return c
+
+    def rows_slice(self, b0: int, b1: int) -> "TagFilter":
+        """The filter of the batch rows b0 .. b1 - 1; a shared word is its own slice."""
+        if self.rows == 1:
+            return self
+        return TagFilter(self.eff, self.words[b0:b1], self.kept[b0:b1], self.allowed[b0:b1], self.stamp)
+
+    def item_mask(self) -> ItemMask:
+        """The filter as an ItemMask (rails_item_mask_from_tags: a shared row for one word, else one row per query row) -- what the exact
+        modules' masked strategies take.  No sync (the counts are the filter's).  A SHARED word's mask (N / 8 bytes) is built at first use and kept
+        with the filter; a per-row filter's (B N / 8 bytes: 500 MB per batch of 32 on a 125 M-item shard, times the filters a module caches) is
+        built for the call and let go -- a caller with one steady per-row filter on a large corpus keeps an ItemMask and passes item_mask=."""
+        if self._mask is not None:
+            return self._mask
+        n = self.n_items
+        words = torch.empty((self.rows, item_mask_words(n)), dtype=torch.int32, device=self.eff.device)
+        counts = torch.empty(self.rows, dtype=torch.int32, device=self.eff.device)
+        with _on_device(self.eff.device):
+            _lib.check(_lib.load().rails_item_mask_from_tags(_ptr(self.eff), n, _ptr(self.allowed), self.rows, _ptr(words), _ptr(counts), _stream()),
+                       "rails_item_mask_from_tags")
+        m = ItemMask.__new__(ItemMask)
+        m._init(words, counts, n, self.rows == 1, torch.tensor(self.kept, dtype=torch.int32))
+        if self.rows == 1:
+            self._mask = m
+        return m
+
+
+def scores_mask_tags(scores: torch.Tensor, filt: TagFilter, first_item: int = 0, fill: float = float("-inf"),
+                     run_if: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place: scores[r, x] = fill wherever item first_item + x carries no bit of the allow word of row r's query (rails_scores_mask_tags); kept
+    entries are neither read nor written.  scores (rows, n) fp32 with unit column stride, rows a multiple of the filter's rows: consecutive
+    blocks of rows / filt.rows rows share an allow word (the component matrix has P_Q * P_X rows per query; a shared word covers every row)."""
+    _require_device(scores, "scores")
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError("scores must be (rows, n) fp32 with contiguous rows")
+    rows, n = scores.shape
+    if first_item < 0 or first_item + n > filt.n_items:
+        raise ValueError(f"scores_mask_tags: items [{first_item}, {first_item + n}) are not inside the {filt.n_items} tagged items")
+    if rows % filt.rows:
+        raise ValueError(f"scores_mask_tags: {rows} rows of scores against {filt.rows} allow words")
+    if filt.eff.device != scores.device:
+        raise ValueError("scores_mask_tags: the tags and the scores live on different devices")
+    with _on_device(scores.device):
+        _lib.check(_lib.load().rails_scores_mask_tags(_ptr(scores), scores.stride(0) if rows > 1 else max(n, scores.stride(0)), rows, n, first_item,
+                                                      _ptr(filt.eff), _ptr(filt.allowed), rows // filt.rows, float(fill), _pred(run_if), _stream()),
+                   "rails_scores_mask_tags")
     return scores
 
 

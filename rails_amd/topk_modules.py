@@ -176,6 +176,86 @@ def hidden_scan_route(n_items: int, num_visible: int, k: int, min_visible_fracti
     return "fused" if num_visible >= min_visible_fraction * n_items else "materialised"
 
 
+def tags_after_append(tags: torch.Tensor, n: int, n_new: int) -> torch.Tensor:
+    """append_items on a tag row: the (n,) int32 row grown to n_new words, the new items n .. n_new - 1 carrying no
+    attribute (0: they match no filtered call until set_item_tags(..., positions) tags them).  Pure tensor arithmetic."""
+    out = torch.zeros(int(n_new), dtype=torch.int32, device=tags.device)
+    out[:n] = tags[:n]
+    return out
+
+
+def tags_after_removal(tags: torch.Tensor, n_new: int, holes: torch.Tensor, movers: torch.Tensor) -> torch.Tensor:
+    """remove_items on a tag row: tags belong to the position, so the i-th mover's word -- read BEFORE the cut -- goes to the i-th hole and the
+    row is cut to n_new words.  holes / movers: removal_plan's, int64 on the row's device.  Pure tensor arithmetic (a copy: the row given is
+    not written)."""
+    out = tags[: int(n_new)].clone()
+    if holes.numel():
+        out.index_copy_(0, holes, tags.index_select(0, movers))
+    return out
+
+
+def parse_allowed_tags(allowed_tags, batch: int) -> Tuple[int, ...]:
+    """allowed_tags= as given -> its allow words as host integers: (word,) for a Python int (shared by the batch), else one per query row from
+    a sequence or an integer tensor of shape (batch,) (a device tensor is copied to the host: one sync).  ValueError for anything else, a
+    word of 0 (it would match nothing) or one outside 32 bits.  Pure host code."""
+    if isinstance(allowed_tags, bool):
+        raise ValueError("allowed_tags must be an int, or a sequence / integer tensor of one word per query row")
+    if isinstance(allowed_tags, int):
+        words = (allowed_tags,)
+    else:
+        if torch.is_tensor(allowed_tags):
+            if allowed_tags.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or allowed_tags.dim() != 1:
+                raise ValueError("allowed_tags must be an int, or a sequence / integer tensor of one word per query row")
+            values = allowed_tags.cpu().tolist()
+        else:
+            try:
+                values = list(allowed_tags)
+            except TypeError:
+                raise ValueError("allowed_tags must be an int, or a sequence / integer tensor of one word per query row") from None
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in values):
+            raise ValueError("allowed_tags must hold integers")
+        if len(values) != batch:
+            raise ValueError(f"allowed_tags has {len(values)} words but the batch has {batch} rows")
+        words = tuple(values)
+    for w in words:
+        if w == 0:
+            raise ValueError("allowed_tags: a word of 0 allows no item")
+        if not 0 < w < 1 << 32:
+            raise ValueError(f"allowed_tags: {w} is not a 32-bit word (values lie in [1, 2^32))")
+    return words
+
+
+def tagged_scan_route(plan: Optional[Tuple[int, int, int, int]], kept_min: int, n_items: int, k: int, min_groups: float = 2.0) -> str:
+    """Which route a candidate scan under allowed_tags= takes -- pure host arithmetic, beside hidden_scan_route:
+      "fused"         the fused scan through its tagged kernels, guarded by its count check and redo as ever;
+      "materialised"  the scores of every item, the entries a row may not return set to -inf, the usual selection.
+    plan = (stride, r, G, s) of the call (engine.scan_plan; None: the sizes have no fused plan): the threshold is the r-th largest of G
+    per-group maxima of s sampled items each.  How many candidates pass the threshold does not depend on the kept fraction -- a row's k best
+    kept items fall into the 1-in-stride sample as any k items do --, what a small fraction v = kept_min / n_items breaks is the number of
+    FINITE maxima the threshold is ranked from: a group keeps one iff at least one of its s sampled items is kept, 1 - (1 - v)^s of them in
+    expectation (items kept at random).  Fused iff the least-kept row of the batch still expects min_groups * r finite maxima:
+    G (1 - (1 - v)^s) >= 2 r, r to spare as in hidden_scan_route -- whose v >= 1/2 this is for a plan of G = 4 r groups of one item.  A wrong
+    guess costs the redo, never the result.  (k beyond kept_min is what a fresh module of kept_min items raises.)"""
+    if kept_min < k:
+        raise RuntimeError(f"selected index k out of range (k={k}, n={kept_min})")
+    if plan is None:
+        return "materialised"
+    _, r, groups, per_group = plan
+    v = min(1.0, kept_min / float(n_items))
+    return "fused" if groups * (1.0 - (1.0 - v) ** per_group) >= min_groups * r else "materialised"
+
+
+def refuse_allowed_tags(module, kwargs, why: str) -> None:
+    """allowed_tags= where it is not built: refused by the class's name, before any launch."""
+    if kwargs.get("allowed_tags") is not None:
+        raise NotImplementedError(f"{type(module).__name__} takes no allowed_tags: {why}")
+
+
+def _tag_ks(module) -> Tuple[int, ...]:
+    """The sizes a candidate-generating module selects per row: each must fit the items a filtered row may return."""
+    return tuple(k for k in (getattr(module, "_avg_top_k", None), getattr(module, "_k_per_group", None)) if k is not None)
+
+
 def upsert_plan(found: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The host rule of upsert_items: `found` ((M,) int64 on the CPU) is where each given id sits in the corpus, -1 where it is absent ->
     (update_rows, update_positions, append_rows): the rows of the argument that replace the items at update_positions, and the rows that are
@@ -241,6 +321,13 @@ class _ItemsById:
         """item_mask= of a call, taken OUT of its kwargs: None, or the ItemMask (a bool tensor is packed: one sync) checked against this module,
         the batch and k before any launch (engine.check_item_mask)."""
         m = kwargs.pop("item_mask", None)
+        if kwargs.get("allowed_tags") is not None:      # a tag filter (DESIGN section 3.15) becomes the call's mask: the hidden set is inside its tags
+            if m is not None:
+                raise ValueError("allowed_tags= and item_mask= in one call: combining the two is not built; fold one into the other")
+            tagged = self._take_allowed_tags(kwargs, batch, ()).item_mask()
+            tagged.check(self.num_items, batch, k)
+            return tagged
+        kwargs.pop("allowed_tags", None)
         vis = self._visible_mask()
         if m is None:
             if vis is not None:      # the hidden set acts as a shared mask of every call (DESIGN section 3.14)
@@ -501,6 +588,142 @@ class _CorpusEdits(_ItemsById):
             words = visibility_after_removal(self._visible, e.n_new, e.positions, e.movers)
             self._visibility_is(words, e.n_new - E.visibility_count(words, e.n_new))      # (one read-back, inside the removal)
 
+    # ---- item tags: one 32-bit word of attributes per item, and allowed_tags= on the calls --------------------------------
+    # State: an owned (N,) int32 tensor of bit patterns, None until set_item_tags -- such a module runs exactly the launches it ran before.  Bit j
+    # set = the item carries attribute j.  A call with allowed_tags= returns, in row b, only items x with tags[x] & allowed[b] != 0 that are
+    # not hidden, and equals row b of the same call on a module freshly built from those rows and their ids.  An item with word 0 matches no
+    # filtered call and stays visible to unfiltered ones.  Tags belong to the POSITION: update_items leaves them, append_items adds words
+    # of 0, remove_items moves a mover's word to its hole (tags_after_append / tags_after_removal).  The kernels read one array, the
+    # EFFECTIVE tags (a hidden item's word is 0), cached per (tags, hidden set); the kept count of every distinct allow word is read back once
+    # and cached with it, so a repeated filter costs a call no sync.
+    _tags: Optional[torch.Tensor] = None
+    _tags_version: int = 0
+    _tag_cache = None              # (stamp, effective tags, {word: kept count}, {words: TagFilter})
+    TAG_FILTERS_KEPT = 64          # resolved filters kept per module (a per-row filter holds B words on the device)
+
+    @property
+    def item_tags(self) -> Optional[torch.Tensor]:
+        """The (N,) int32 tag words on the module's device (bit patterns: a word with bit 31 set reads negative), or None while no tags are
+        set.  The hand-off of the tags -- they are not part of state_dict; set_item_tags takes this tensor back as it is."""
+        return self._tags
+
+    def set_item_tags(self, tags: torch.Tensor, positions: Optional[torch.Tensor] = None) -> None:
+        """One tag word per item.  tags: (N,) -- every item -- or (M,) with positions ((M,) int64, CPU or device, unique POSITIONS); int64 values
+        in [0, 2^32), or int32 taken as the bit patterns themselves (what item_tags returns); on the module's device.  A call with positions on
+        a module without tags builds the row with every other item at 0.  ValueError before anything is touched for a wrong shape, dtype,
+        device, value or position (the value check of int64 tags and the position check cost one sync each).  The stored tensor is the
+        module's own: neither argument is aliased, and a row already handed to enqueued launches is not written."""
+        n = self.num_items
+        dev = self._ids_flat.device
+        if not torch.is_tensor(tags) or tags.dim() != 1 or tags.dtype not in (torch.int32, torch.int64):
+            raise ValueError("tags must be an (N,) or (M,) int32 / int64 tensor")
+        if tags.device != dev:
+            raise ValueError(f"tags must live on the module's device {dev}, got {tags.device}")
+        m = tags.numel()
+        if positions is None:
+            if m != n:
+                raise ValueError(f"tags has {m} words but the module holds {n} items (pass positions to tag a subset)")
+        else:
+            positions = _checked_positions(positions, m, n)
+        if tags.dtype == torch.int64 and m:
+            lo, hi = torch.aminmax(tags)
+            if int(lo) < 0 or int(hi) >= 1 << 32:
+                raise ValueError("tags must lie in [0, 2^32)")
+        with torch.inference_mode():
+            self._join_side_streams()
+            if tags.dtype == torch.int64:
+                tags = torch.where(tags >= 1 << 31, tags - (1 << 32), tags).to(torch.int32)
+            if positions is None:
+                row = tags.clone()
+            else:
+                row = torch.zeros(n, dtype=torch.int32, device=dev) if self._tags is None else self._tags.clone()
+                row.index_copy_(0, positions.to(dev), tags)
+            self._tags_are(row)
+
+    def _tags_are(self, row: Optional[torch.Tensor]) -> None:
+        self._tags = row
+        self._tags_version += 1
+        self._tag_cache = None
+
+    def _tags_step(self, e: CorpusEdit, n: int) -> None:
+        """The tag row follows an edit (called by _apply)."""
+        if self._tags is None:
+            return
+        if e.how == CONCATENATED:
+            self._tags_are(tags_after_append(self._tags, n, e.n_new))
+        elif e.how == CUT_AND_FILLED:
+            self._tags_are(tags_after_removal(self._tags, e.n_new, e.positions, e.movers))
+
+    TAGGED_FUSED_MIN_GROUPS = 2.0     # tagged_scan_route: the expected finite group maxima, in units of the plan's rank r, below which a tagged scan is materialised directly
+
+    def allowed_tags_route(self, allowed_tags, batch: int) -> str:
+        """The route the candidate scans of a call with this allowed_tags= take, e.g. "coarse: fused" or "component: fused, coarse: materialised"
+        (tools/item_tags_bench.py records it per cell); "item mask" on the exact modules, which hand the filter to their masked strategies."""
+        tags = self._take_allowed_tags({"allowed_tags": allowed_tags}, batch, ())
+        eng, parts = self._bind(), []
+        if getattr(self, "_k_per_group", None) is not None and not getattr(self, "_use_faiss", False):
+            fused = self.num_items >= self.fused_component_min_items and self._tagged_route(eng, tags, batch, self.num_items, self._k_per_group, True) == "fused"
+            parts.append("component: " + ("fused" if fused else "materialised"))
+        if getattr(self, "_avg_top_k", None) is not None:
+            fused = (self.num_items >= self.fused_coarse_min_items and self._avg_top_k <= 4096
+                     and self._tagged_route(eng, tags, batch, self.num_items, self._avg_top_k, False) == "fused")
+            parts.append("coarse: " + ("fused" if fused else "materialised"))
+        return ", ".join(parts) if parts else "item mask"
+
+    def _tagged_route(self, eng, tags: E.TagFilter, batch: int, n: int, k: int, component: bool) -> str:
+        """tagged_scan_route for one scan of this module: the plan of the call as the scan will be sliced (host arithmetic, memoised per size)."""
+        if component:
+            pq, px = eng.spec.query_dot_product_groups, eng.spec.item_dot_product_groups
+            b = min(batch, max(1, E.TAGGED_COMPONENT_ROWS // pq))
+            key = (b * pq * px, n, k, b * pq)
+        else:
+            key = (min(batch, 128), n, k, 0)
+        memo = self.__dict__.setdefault("_scan_plans", {})
+        if key not in memo:
+            if len(memo) > 64:
+                memo.clear()
+            memo[key] = E.scan_plan(*key)
+        return tagged_scan_route(memo[key], tags.kept_min, n, k, self.TAGGED_FUSED_MIN_GROUPS)
+
+    def _check_taggable(self, what: str) -> None:
+        """The refusal point of allowed_tags=: modules whose candidate generation cannot honour it raise here, before any launch."""
+
+    def _tag_state(self):
+        stamp = (self._tags_version, self._hidden_version, self.num_items)
+        c = self._tag_cache
+        if c is None or c[0] != stamp:
+            eff = self._tags if self._visible is None else E.item_tags_effective(self._tags, self._visible, self.num_items)
+            c = self._tag_cache = (stamp, eff, {}, {})
+        return c
+
+    def _take_allowed_tags(self, kwargs: dict, batch: int, ks: Tuple[int, ...]) -> Optional[E.TagFilter]:
+        """allowed_tags= of a call, taken OUT of its kwargs: None, or the resolved E.TagFilter -- validated against this module, the batch and the
+        sizes `ks` the call selects (avg_top_k, k_per_group, k) before any launch.  An E.TagFilter given (a call handing its own filter on) is
+        returned as it is while the module's tags, hidden set and size are the ones it was resolved against."""
+        a = kwargs.pop("allowed_tags", None)
+        if a is None:
+            return None
+        self._check_taggable("allowed_tags")
+        if self._tags is None:
+            raise ValueError(f"{type(self).__name__}: allowed_tags= on a module without tags (set_item_tags first)")
+        stamp, eff, counts, filters = self._tag_state()
+        if isinstance(a, E.TagFilter) and a.stamp == stamp and a.rows in (1, batch):
+            filt = a
+        else:
+            words = a.words if isinstance(a, E.TagFilter) else parse_allowed_tags(a, batch)
+            filt = filters.get(words)
+            if filt is None:
+                new = [w for w in dict.fromkeys(words) if w not in counts]
+                if new:      # one launch and one read-back per call that brings new words
+                    counts.update(zip(new, E.item_tags_counts(eff, new)))
+                if len(filters) >= self.TAG_FILTERS_KEPT:
+                    filters.clear()
+                filt = filters[words] = E.TagFilter(eff, words, tuple(counts[w] for w in words), stamp=stamp)
+        for k in ks:
+            if k is not None and k > filt.kept_min:
+                raise RuntimeError(f"selected index k out of range (k={k}, n={filt.kept_min})")
+        return filt
+
     def _apply(self, e: CorpusEdit) -> None:
         """The one edit flow.  The ids about to be overwritten or moved are read BEFORE the write; what was decided from the corpus size is
         forgotten BEFORE the engine for n_new items is asked for; resize comes before refresh; a removal without holes refreshes nothing."""
@@ -523,6 +746,7 @@ class _CorpusEdits(_ItemsById):
             if ids is not None:
                 self._id_map_step(gone, ids, pos)
             self._visibility_step(e, n)
+            self._tags_step(e, n)
             held, resize = self._held_buffers(), e.n_new != n
             if resize:
                 self._forget_corpus_choices()
@@ -690,7 +914,10 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus."""
         refuse_item_mask(self, kwargs)
+        tags = self._take_allowed_tags(kwargs, query_embeddings.size(0), ())
         logits = self._raw_logits(query_embeddings, **kwargs)
+        if tags is not None:            # allowed_tags=: a row's disallowed columns hold -inf (the hidden ones are among them)
+            return E.scores_mask_tags(logits, tags)
         vis = self._visible_mask()      # hidden columns hold -inf
         return logits if vis is None else E.scores_mask(logits, vis)
 
@@ -2003,12 +2230,14 @@ class MoLAvgTopK(MoLTopKModule):
         return {"fired": fired, "tested": tested, "fraction": fired / tested if tested else 0.0}
 
     def _coarse_topk(self, query_embeddings: torch.Tensor, average_queries: bool, pending: Optional[list] = None, **kwargs):
+        tags = self._take_allowed_tags(kwargs, query_embeddings.size(0), (self._avg_top_k,))      # (before any launch)
         eng = self._bind()
         table = self._table()
         qpack, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
-        return qpack, self._coarse_topk_from_eq(eq, average_queries, pending)
+        return qpack, self._coarse_topk_from_eq(eq, average_queries, pending, tags=tags)
 
-    def _coarse_topk_from_eq(self, eq: torch.Tensor, average_queries: bool, pending: Optional[list] = None, with_scores: bool = False):
+    def _coarse_topk_from_eq(self, eq: torch.Tensor, average_queries: bool, pending: Optional[list] = None, with_scores: bool = False,
+                             tags: Optional[E.TagFilter] = None):
         """(B, P_Q, d) query components -> (B, avg_top_k) positions of the coarse top-K', best first
         (with_scores: -> (scores, positions), the bf16 coarse scores as fp32).
         The fused scan's result is exact iff every row collected between K' and `capacity` candidates.  With `pending` (a
@@ -2025,8 +2254,14 @@ class MoLAvgTopK(MoLTopKModule):
         # mostly hidden corpus, the predicated redo, the redo after a failed verdict -- has its hidden columns set to -inf before the selection
         vis = self._visible_mask()
         fused_ok = vis is None or hidden_scan_route(n, self.num_visible, self._avg_top_k, self.HIDDEN_FUSED_MIN_VISIBLE) == "fused"
+        # allowed_tags=: the fused scan runs its tagged kernels where the plan-aware rule expects enough finite group maxima
+        # for the least-kept row; every materialised score matrix has the entries a row may not return (a hidden item's included: the effective
+        # tags) set to -inf before the selection
+        if tags is not None:
+            fused_ok = self._tagged_route(eng, tags, eq.shape[0], n, self._avg_top_k, False) == "fused"
         if eq.shape[0] > 128:   # the scan keeps ceil(B / 32) query tiles in LDS: larger batches go in slices
-            parts = [self._coarse_topk_from_eq(eq[b0 : b0 + 128], average_queries, pending, with_scores) for b0 in range(0, eq.shape[0], 128)]
+            parts = [self._coarse_topk_from_eq(eq[b0 : b0 + 128], average_queries, pending, with_scores, None if tags is None else tags.rows_slice(b0, b0 + 128))
+                     for b0 in range(0, eq.shape[0], 128)]
             return (torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)) if with_scores else torch.cat(parts, dim=0)
         # large corpora: fused scan + threshold select, no (B, N) score matrix (16 GB per 125 M-item shard at B = 32).
         # Same scores and the same exact top-K' as the materialising path below -- when every query's candidate count
@@ -2036,8 +2271,8 @@ class MoLAvgTopK(MoLTopKModule):
             # a verdict the HOST reads (no device redo, the caller defers the look): the word lives in pinned host memory and the kernels write it
             # there themselves -- no 4-byte copy behind the call's last launch (round 6, as the component scans)
             word = _pinned_word(self) if (not on_device and pending is not None) else None
-            fused = eng.coarse_topk(eq, table, average_queries, self._avg_top_k, with_flag=True, prefilter=self._prefilter(), flag=word,
-                                    visible=self._visible)
+            fused = eng.coarse_topk(eq, table, average_queries, self._avg_top_k, with_flag=True, prefilter=self._prefilter(),
+                                    flag=word, visible=None if tags is not None else self._visible, tags=tags)
             if fused is not None:
                 # bad: 1 iff some row's candidate count is outside [K', capacity] -- raised by the call's key-selection launch
                 sc, idx, counts, bad = fused
@@ -2046,7 +2281,9 @@ class MoLAvgTopK(MoLTopKModule):
                     # predicate and overwrite (sc, idx) -- no-ops unless a count was out of range; nothing for the host to wait
                     # for (the (B, N) score buffer is recycled across calls)
                     coarse = eng.coarse_scores(eq, table, average_queries, out=self._buf("coarse_all", eq.shape[0] * n, torch.float32).view(eq.shape[0], n), run_if=bad)
-                    if vis is not None:
+                    if tags is not None:
+                        E.scores_mask_tags(coarse, tags, run_if=bad)
+                    elif vis is not None:
                         E.scores_mask(coarse, vis, run_if=bad)
                     E.topk(coarse, self._avg_top_k, out=(sc, idx), run_if=bad)
                     return (sc, idx) if with_scores else idx
@@ -2056,7 +2293,9 @@ class MoLAvgTopK(MoLTopKModule):
                 if int(bad.item()) == 0:
                     return (sc, idx) if with_scores else idx
         coarse = eng.coarse_scores(eq, table, average_queries)
-        if vis is not None:
+        if tags is not None:
+            E.scores_mask_tags(coarse, tags)
+        elif vis is not None:
             E.scores_mask(coarse, vis)
         sc, idx = E.topk(coarse, self._avg_top_k)
         return (sc, idx) if with_scores else idx
@@ -2094,6 +2333,8 @@ class MoLAvgTopK(MoLTopKModule):
     # without calling result() (ShardedTopK.submit, which needs the scores earlier, waits on the handle's event explicitly).
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
         refuse_item_mask(self, kwargs)
+        if kwargs.get("allowed_tags") is not None:      # allowed_tags=, resolved and checked before any launch; the handle and a
+            kwargs["allowed_tags"] = self._take_allowed_tags(kwargs, query_embeddings.size(0), (self._avg_top_k,))      # redo carry the resolved filter
         if k > self._avg_top_k:  # the reference raises after doing the work (mol_top_k.py:383-386)
             raise ValueError(f"avg_top_k ({self._avg_top_k}) must be larger than k ({k})")
         # Calls that will be speculative (the (B, N) redo buffer does not fit: large shards) alternate between two streams of the
@@ -2187,6 +2428,8 @@ class MoLAvgTopK(MoLTopKModule):
 
     def coarse_candidates(self, query_embeddings: torch.Tensor, **kwargs):
         """Pass 1 on this module's items: -> (coarse scores (B, K'), positions (B, K')), best first (ties by position)."""
+        refuse_allowed_tags(self, kwargs, "coarse_candidates is the item-sharded wrappers' hand-off, and a tag filter is not built on them; forward, submit "
+                            "and topk_ids take it")
         eng = self._bind()
         _, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
         return self._coarse_topk_from_eq(eq, False, None, with_scores=True)
@@ -2237,11 +2480,12 @@ class _ComponentCandidates:
 
     def _ranked(self, query_embeddings: torch.Tensor, sorted: bool, seen, kwargs):
         refuse_item_mask(self, kwargs)
+        tags = self._take_allowed_tags(kwargs, query_embeddings.size(0), _tag_ks(self))      # allowed_tags=, before any launch
         eng = self._bind()
         qpack, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
         for attempt in range(2):     # speculate on the fused scans, verify after everything is enqueued
             pending: list = []
-            all_indices = self._candidates(eq, pending)
+            all_indices = self._candidates(eq, pending) if tags is None else self._candidates(eq, pending, tags)
             out = self._rerank_union(qpack, query_embeddings.size(0), all_indices, sorted, seen, pending)
             if _verdicts_clear(pending, self):
                 break
@@ -2277,7 +2521,8 @@ class _ComponentCandidates:
              lambda tk, eng, pos, emb: eng.update_component_table(tk._comp_table, pos, tk._table_source(eng, emb)), _comp_drop),
     )
 
-    def _component_topk(self, eq: torch.Tensor, k_per_group: int, pending: Optional[list] = None, with_scores: bool = False):
+    def _component_topk(self, eq: torch.Tensor, k_per_group: int, pending: Optional[list] = None, with_scores: bool = False,
+                        tags: Optional[E.TagFilter] = None):
         """-> (B, P_Q * P_X * k_per_group) positions: top k_per_group items of every (query group, item group) pair.
         `pending`: deferred validity check of the fused scan, as in MoLAvgTopK._coarse_topk_from_eq.
         with_scores: -> (scores, positions), both (B * P_Q * P_X, k_per_group), best first: the bf16 component scores as fp32."""
@@ -2289,11 +2534,16 @@ class _ComponentCandidates:
         self._check_k_visible(k_per_group)
         vis = self._visible_mask()      # a hidden set: as in MoLAvgTopK._coarse_topk_from_eq
         fused_ok = vis is None or hidden_scan_route(n, self.num_visible, k_per_group, self.HIDDEN_FUSED_MIN_VISIBLE) == "fused"
+        if tags is not None:            # allowed_tags=: as in MoLAvgTopK._coarse_topk_from_eq
+            fused_ok = self._tagged_route(eng, tags, eq.shape[0], n, k_per_group, True) == "fused"
         # the component scans keep the fragments of all B * P_Q query rows in LDS and (the fused form) eight row tiles of running maxima in
         # registers (four at d = 128): batches beyond 256 (128) query rows go in slices
         max_b = max(1, (128 if eng.spec.dot_product_dimension >= 128 else 256) // eng.spec.query_dot_product_groups)
+        if tags is not None and fused_ok:      # (the tagged sample keeps four row tiles at every d: its eight-tile form would spill)
+            max_b = max(1, E.TAGGED_COMPONENT_ROWS // eng.spec.query_dot_product_groups)
         if eq.shape[0] > max_b:
-            parts = [self._component_topk(eq[b0 : b0 + max_b], k_per_group, pending, with_scores) for b0 in range(0, eq.shape[0], max_b)]
+            parts = [self._component_topk(eq[b0 : b0 + max_b], k_per_group, pending, with_scores, None if tags is None else tags.rows_slice(b0, b0 + max_b))
+                     for b0 in range(0, eq.shape[0], max_b)]
             return (torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)) if with_scores else torch.cat(parts, dim=0)
         # large corpora: fused scan + threshold select, no (B*P_Q*P_X, N) score matrix (5.7 GB at amzn-books, B = 32);
         # identical to the materialising path below whenever every row's candidate count is inside [k, capacity]
@@ -2306,12 +2556,14 @@ class _ComponentCandidates:
                 # the verdict word in pinned host memory, written by the kernels themselves: the caller spins on an event and reads it (no 4-byte
                 # copy launch, no blocking .item(): ~30 us of every Naive / Comb call at amzn-books)
                 flag = _pinned_word(self)
-            fused = eng.component_topk(eq, table, k_per_group, flag, visible=self._visible)
+            fused = eng.component_topk(eq, table, k_per_group, flag, visible=None if tags is not None else self._visible, tags=tags)
             if fused is not None:
                 sc_c, pos, counts = fused
                 if on_device:     # redo on the device under the flag, as in MoLAvgTopK._coarse_topk_from_eq
                     scores = eng.component_scores(eq, table, out=self._buf("component_all", rows * n, torch.float32).view(rows, n), run_if=flag)
-                    if vis is not None:
+                    if tags is not None:
+                        E.scores_mask_tags(scores, tags, run_if=flag)
+                    elif vis is not None:
                         E.scores_mask(scores, vis, run_if=flag)
                     E.topk(scores, k_per_group, out=(sc_c, pos), run_if=flag)
                     return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
@@ -2321,7 +2573,9 @@ class _ComponentCandidates:
                 if int(flag.item()) == 0:
                     return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
         scores = eng.component_scores(eq, table)
-        if vis is not None:
+        if tags is not None:            # (P_Q * P_X rows of the matrix per query row share its allow word)
+            E.scores_mask_tags(scores, tags)
+        elif vis is not None:
             E.scores_mask(scores, vis)
         sc_c, pos = E.topk(scores, k_per_group)
         return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
@@ -2337,6 +2591,8 @@ class _ComponentCandidates:
         (scores, positions), both (B, K'), behind them.  Scores are the scans' bf16 values as fp32.  VERIFIED before it returns: the fused
         scans are enqueued speculatively, their verdict words read once (the one host look of the single-device call), and a failed verdict
         redoes the scans on the materialising path -- what comes back is exact."""
+        refuse_allowed_tags(self, kwargs, "local_candidates is the item-sharded wrappers' hand-off, and a tag filter is not built on them; forward and "
+                            "get_top_k_outputs take it")
         eng = self._bind()
         _, eq, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"), want_plain=True)
         for attempt in range(2):
@@ -2494,10 +2750,16 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
             self._ivf_engine = eng
         return self._ivf
 
-    def _candidates(self, eq: torch.Tensor, pending: list) -> torch.Tensor:
+    def _candidates(self, eq: torch.Tensor, pending: list, tags: Optional[E.TagFilter] = None) -> torch.Tensor:
         if self._use_faiss:       # exact by construction over the probed lists: nothing to verify, nothing added to `pending`
             return self.ivf_index().search(eq, self._k_per_group, nprobe=self.nprobe)
-        return self._component_topk(eq, self._k_per_group, pending)
+        # (tags travel as a keyword only when there are any: tests/test_gpu_parity.py swaps _component_topk for a stand-in of the (eq, k, pending) form)
+        return self._component_topk(eq, self._k_per_group, pending, **({} if tags is None else {"tags": tags}))
+
+    def _check_taggable(self, what: str) -> None:
+        if self._use_faiss:
+            raise NotImplementedError(f"MoLNaiveTopK takes no {what}: the IVF index (use_faiss=True{', frozen_centroids=True' if self._frozen_centroids else ''}) "
+                                      "searches its lists without a tag test -- a tag filter is not built for it; the exhaustive MoLNaiveTopK takes it")
 
     def _candidates_scored(self, eq: torch.Tensor, pending: list):
         if self._use_faiss:
@@ -2522,9 +2784,9 @@ class MoLCombTopK(_ComponentCandidates, MoLAvgTopK):
         mol = self._mol_module
         return mol._query_dot_product_groups * mol._item_dot_product_groups * self._k_per_group + self._avg_top_k
 
-    def _candidates(self, eq: torch.Tensor, pending: list) -> torch.Tensor:
-        comp = self._component_topk(eq, self._k_per_group, pending)
-        avg_idx = self._coarse_topk_from_eq(eq, average_queries=True, pending=pending)
+    def _candidates(self, eq: torch.Tensor, pending: list, tags: Optional[E.TagFilter] = None) -> torch.Tensor:
+        comp = self._component_topk(eq, self._k_per_group, pending, **({} if tags is None else {"tags": tags}))      # (as in MoLNaiveTopK._candidates)
+        avg_idx = self._coarse_topk_from_eq(eq, average_queries=True, pending=pending, tags=tags)
         return torch.cat([comp, avg_idx], dim=1)
 
     def _candidates_scored(self, eq: torch.Tensor, pending: list):
