@@ -149,8 +149,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_rows_kernel(ScoreAr
 // ---------------------------------------------------------------------------------------------
 // Kernel B ("staged"): the workgroup's waves share one item tile per step.  The tile is copied
 // HBM -> LDS by LDS-DMA (global_load_lds, 1 KiB per wave-instruction, no registers) one tile ahead of
-// its use, double buffered, so each tile is read from HBM exactly once per batch and its latency is
-// hidden behind a whole tile of MFMA work.  One barrier per tile.
+// its use, double buffered, so each tile is read from HBM exactly once per batch.  One barrier per tile.
+// The DMA of tile t + 1 is issued behind the first GEMM1 of tile t (see the kernel): the first wait it can hold up is
+// the first read of the tile's gate part, one GEMM2 later; from there to the next barrier its latency is hidden.
 // ---------------------------------------------------------------------------------------------
 template <int NW>
 __device__ __forceinline__ void dma_floats(const float* __restrict__ src, float* lds, int n_floats, int wave, int lane) {
@@ -163,6 +164,17 @@ __device__ __forceinline__ void dma_floats(const float* __restrict__ src, float*
 
 constexpr int kStagedPipe = 0;   // GEMM1 one K-chunk ahead with the tile in LDS: measured no difference (6.34 ms either way)
 
+// This lane's index within its wave, computed where it is asked for and opaque to the compiler.  The staged kernels ask once per part of
+// a unit (GEMM1, the prefetch, the gate MLP): every lane-dependent address of the tile loop (LDS fragment offsets, the Eq / gq / logits
+// pointers, the DMA source) is then built where it is used from wave-uniform bases in SGPRs and this one register -- a handful of VALU instructions.  Derived from
+// threadIdx they are loop invariants, which the compiler hoists into VGPR pairs, spills (the unit's accumulators leave no room for
+// them) and reloads at the top of every tile, in front of GEMM1's first loads.
+__device__ __forceinline__ int lane_now() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
 template <class U, int PQ, int PX, int DD, int H, int NW>
 __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged_kernel(ScoreArgs p) {
   using G = Geo<PQ, PX, DD, H>;
@@ -172,27 +184,41 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged_kernel(Score
   float* tiles = smem + U::template kLdsWeightFloats<G>;  // two tile buffers
   U::template stage<G, NW>(p, smem);
 
-  const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int hi = lane >> 5, x = lane & 31;
-  const int64_t first = blockIdx.x;
-  if (first < p.n_tiles) dma_floats<NW>(p.ipack + first * (int64_t)G::kTileFloats, tiles, G::kTileFloats, wave, lane);
+  // tile counters in 32 bits (the launcher refuses more tiles): a 64-bit loop bound is compared on the VALU, from a VGPR pair
+  const int n_tiles = (int)p.n_tiles, grid = (int)gridDim.x, first = (int)blockIdx.x;
+  if (first < n_tiles) dma_floats<NW>(p.ipack + first * (int64_t)G::kTileFloats, tiles, G::kTileFloats, wave, threadIdx.x & 63);
   int cur = 0;
-  int64_t it = 0;
-  for (int64_t tile = first; tile < p.n_tiles; tile += gridDim.x, cur ^= 1, ++it) {
+  for (int tile = first; tile < n_tiles; tile += grid, cur ^= 1) {
     // (1) my pieces of `tile` have landed (vmcnt(0)); (2) barrier: every wave's pieces have, and every wave
     // is done with the previous tile, so the other buffer may be overwritten
     __syncthreads();
-    const int64_t next = tile + gridDim.x;
-    if (next < p.n_tiles) dma_floats<NW>(p.ipack + next * (int64_t)G::kTileFloats, tiles + (cur ^ 1) * G::kTileFloats, G::kTileFloats, wave, lane);
     const float4* tEx = reinterpret_cast<const float4*>(tiles + cur * G::kTileFloats);
     const float4* tGi = tEx + G::kTileExFloats / 4;
+    // The next tile's DMA goes out BEHIND the first GEMM1 of this tile, not in front of it: vector-memory results return in order and
+    // the DMA pieces count in vmcnt, so a GEMM1 whose Eq loads are queued behind them starts only when the whole next tile has
+    // arrived from HBM -- with all eight waves waiting at the same moment, right after the barrier.  Behind GEMM1 the first wait that
+    // the DMA can hold up is the unit's first read of the tile's gate rows, a GEMM2 later (the compiler drains vmcnt before an LDS read
+    // that may alias a DMA in flight).  The other buffer is free from the barrier on; the next barrier's vmcnt(0) sees the pieces land.
+    bool prefetch = tile + grid < n_tiles;
+    auto issue_prefetch = [&] {
+      __builtin_amdgcn_sched_barrier(0);   // not hoisted above the GEMM1 behind which it stands
+      asm volatile("" ::: "memory");
+      dma_floats<NW>(p.ipack + (tile + grid) * (int64_t)G::kTileFloats, tiles + (cur ^ 1) * G::kTileFloats, G::kTileFloats, wave, lane_now());
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      prefetch = false;
+    };
     for (int g = wave; g < p.n_groups; g += NW) {
       const float* eq = p.eqfrag + (int64_t)g * G::kEqGroupFloats;
       f32x16 D1[PX];
-      U::template gemm1<G, PX, DD, kStagedPipe>(D1, eq, tEx, lane);
-      U::template queries<G, PX>(D1, p, g, -1, tile * kTileItems, smem, tGi, lane, hi, x);
+      // the lane index anew for each part of a unit: no address of one part stays live (or spilled) across another
+      U::template gemm1<G, PX, DD, kStagedPipe>(D1, eq, tEx, lane_now());
+      if (prefetch) issue_prefetch();
+      const int lane = lane_now();
+      U::template queries<G, PX>(D1, p, g, -1, (int64_t)tile * kTileItems, smem, tGi, lane, lane >> 5, lane & 31);
     }
+    if (prefetch) issue_prefetch();   // a wave without a query group (fewer groups than waves) still moves its pieces
   }
 }
 
@@ -222,7 +248,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged1_kernel(Scor
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int hi = lane >> 5, x = lane & 31;
   const int64_t grid = gridDim.x, b = blockIdx.x;
   const int64_t rounds = p.n_tiles / grid;
   const int64_t left = p.n_tiles - rounds * grid;
@@ -262,16 +287,21 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mol_score_staged1_kernel(Scor
       f32x16 D1[PX];
       // the ring costs kStaged1Pipe * (PX + 1) float4 registers: built where that is <= 16 and K is deeper than the ring (4 x 128 shapes); elsewhere none (8 x 32 would spill)
       constexpr int kPipe = (kStaged1Pipe * (PX + 1) > 16 || DD / 8 <= kStaged1Pipe) ? 0 : kStaged1Pipe;
-      if (has) U::template gemm1<G, PX, DD, kPipe>(D1, p.eqfrag + (int64_t)g * G::kEqGroupFloats, tEx, lane);
+      // (the lane index anew for each part of a unit, as in mol_score_staged_kernel: no lane-dependent address is carried from tile to tile)
+      if (has) U::template gemm1<G, PX, DD, kPipe>(D1, p.eqfrag + (int64_t)g * G::kEqGroupFloats, tEx, lane_now());
       if (it == n_it - 1) {
         __syncthreads();   // every wave is past its last GEMM1 of this tile: the Ex buffer is free
-        if (i + 1 < mine) {
+        if (i + 1 < mine) {   // behind the tile's last GEMM1 already: no GEMM1 operand load queues behind these pieces
           const float* tn = p.ipack + tile_of(i + 1) * (int64_t)G::kTileFloats;
-          dma_floats<NW>(tn, sEx, G::kTileExFloats, wave, lane);
-          dma_floats<NW>(tn + G::kTileExFloats, sGi + (cur ^ 1) * G::kTileGiFloats, G::kTileGiFloats, wave, lane);
+          const int l = lane_now();
+          dma_floats<NW>(tn, sEx, G::kTileExFloats, wave, l);
+          dma_floats<NW>(tn + G::kTileExFloats, sGi + (cur ^ 1) * G::kTileGiFloats, G::kTileGiFloats, wave, l);
         }
       }
-      if (has) U::template queries<G, PX>(D1, p, g, -1, tile * kTileItems, smem, tGi, lane, hi, x);
+      if (has) {
+        const int l = lane_now();
+        U::template queries<G, PX>(D1, p, g, -1, tile * kTileItems, smem, tGi, l, l >> 5, l & 31);
+      }
     }
   }
 }
@@ -311,6 +341,7 @@ static int launch_kernel(const ScoreArgs& a, int n_cu, hipStream_t stream) {
     };
     if constexpr (STAGED) {
       if (a.cand_pos) { set_error("indexed candidates need the independent-wave shell"); return kErrUnsupported; }
+      if (a.n_tiles + grid > 0x7fffffff) { set_error("staged scoring kernel counts tiles in 32 bits"); return kErrUnsupported; }
       return go(&mol_score_staged_kernel<U, PQ, PX, DD, H, NW>);
     } else {
       if constexpr (U::kIndexedCandidates) {
