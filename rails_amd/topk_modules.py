@@ -256,6 +256,38 @@ def _tag_ks(module) -> Tuple[int, ...]:
     return tuple(k for k in (getattr(module, "_avg_top_k", None), getattr(module, "_k_per_group", None)) if k is not None)
 
 
+class Restriction(NamedTuple):
+    """What a call may return when that is not every item: the module's hidden set or the call's resolved allowed_tags=
+    (section 3.15; its effective tags hold the hidden set).  Which of the two it is stays in here.  Built once per call by
+    _CorpusEdits._restriction -- None for a call with neither, which runs the unrestricted launches and nothing more."""
+    hidden: Optional[E.ItemMask]                # the hidden set as a shared mask over the visibility row; None under a tag filter
+    tags: Optional[E.TagFilter]
+    count: int                                  # items the least-kept row may return (num_visible, or the filter's kept_min): every k is checked against it
+
+    @classmethod
+    def of(cls, hidden: Optional[E.ItemMask], tags: Optional[E.TagFilter]) -> Optional["Restriction"]:
+        return None if hidden is None and tags is None else cls(hidden, tags, (hidden if tags is None else tags).kept_min)
+
+    def launch_kwargs(self) -> dict:
+        """What a fused scan takes beside its plain arguments: its visible kernels' row, or its tagged kernels' filter -- never both."""
+        return {"visible": self.hidden.words} if self.tags is None else {"tags": self.tags}
+
+    def mask(self, scores: torch.Tensor, run_if: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """In place: -inf in every entry of a materialised score matrix that its row may not return (the rows of one query share its rule)."""
+        if self.tags is None:
+            return E.scores_mask(scores, self.hidden, run_if=run_if)
+        return E.scores_mask_tags(scores, self.tags, run_if=run_if)
+
+    def rows_slice(self, b0: int, b1: int) -> "Restriction":      # (the batch rows b0 .. b1 - 1; the hidden set is every row's)
+        return self if self.tags is None else Restriction.of(None, self.tags.rows_slice(b0, b1))
+
+    def allows_fused(self, module, component: bool, batch: int, n: int, k: int) -> bool:
+        """The rule of the restriction's kind on whether a fused scan's sampled threshold is expected to hold (a wrong guess costs the redo)."""
+        if self.tags is None:
+            return hidden_scan_route(n, self.count, k, module.HIDDEN_FUSED_MIN_VISIBLE) == "fused"
+        return tagged_scan_route(module._scan_plan(component, batch, n, k), self.count, n, k, module.TAGGED_FUSED_MIN_GROUPS) == "fused"
+
+
 def upsert_plan(found: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The host rule of upsert_items: `found` ((M,) int64 on the CPU) is where each given id sits in the corpus, -1 where it is absent ->
     (update_rows, update_positions, append_rows): the rows of the argument that replace the items at update_positions, and the rows that are
@@ -574,9 +606,9 @@ class _CorpusEdits(_ItemsById):
             m = self._visible_mask_cache = E.item_mask_of_words(self._visible, self.num_items, self.num_visible)
         return m
 
-    def _check_k_visible(self, k: int) -> None:
-        if self._visible is not None and k > self.num_visible:
-            raise RuntimeError(f"selected index k out of range (k={k}, n={self.num_visible})")
+    def _restriction(self, tags: Optional[E.TagFilter] = None) -> Optional[Restriction]:
+        """(the hidden set, the call's resolved allowed_tags=) as the one value the candidate scans and all_logits deal with; None: neither."""
+        return Restriction.of(None if tags is not None else self._visible_mask(), tags)
 
     def _visibility_step(self, e: CorpusEdit, n: int) -> None:
         """The visibility row follows an edit (called by _apply with the movers still where they were)."""
@@ -654,26 +686,31 @@ class _CorpusEdits(_ItemsById):
         elif e.how == CUT_AND_FILLED:
             self._tags_are(tags_after_removal(self._tags, e.n_new, e.positions, e.movers))
 
+    HIDDEN_FUSED_MIN_VISIBLE = 0.5    # hidden_scan_route: the visible fraction below which a scan of a module with a hidden set is materialised directly
     TAGGED_FUSED_MIN_GROUPS = 2.0     # tagged_scan_route: the expected finite group maxima, in units of the plan's rank r, below which a tagged scan is materialised directly
 
     def allowed_tags_route(self, allowed_tags, batch: int) -> str:
         """The route the candidate scans of a call with this allowed_tags= take, e.g. "coarse: fused" or "component: fused, coarse: materialised"
         (tools/item_tags_bench.py records it per cell); "item mask" on the exact modules, which hand the filter to their masked strategies."""
-        tags = self._take_allowed_tags({"allowed_tags": allowed_tags}, batch, ())
-        eng, parts = self._bind(), []
-        if getattr(self, "_k_per_group", None) is not None and not getattr(self, "_use_faiss", False):
-            fused = self.num_items >= self.fused_component_min_items and self._tagged_route(eng, tags, batch, self.num_items, self._k_per_group, True) == "fused"
-            parts.append("component: " + ("fused" if fused else "materialised"))
-        if getattr(self, "_avg_top_k", None) is not None:
-            fused = (self.num_items >= self.fused_coarse_min_items and self._avg_top_k <= 4096
-                     and self._tagged_route(eng, tags, batch, self.num_items, self._avg_top_k, False) == "fused")
-            parts.append("coarse: " + ("fused" if fused else "materialised"))
+        restr = self._restriction(self._take_allowed_tags({"allowed_tags": allowed_tags}, batch, ()))
+        scans = (("component", True, None if getattr(self, "_use_faiss", False) else getattr(self, "_k_per_group", None)),
+                 ("coarse", False, getattr(self, "_avg_top_k", None)))
+        parts = [f"{name}: " + ("fused" if all(self._scan_route(component, batch, self.num_items, k, restr)) else "materialised")
+                 for name, component, k in scans if k is not None]
         return ", ".join(parts) if parts else "item mask"
 
-    def _tagged_route(self, eng, tags: E.TagFilter, batch: int, n: int, k: int, component: bool) -> str:
-        """tagged_scan_route for one scan of this module: the plan of the call as the scan will be sliced (host arithmetic, memoised per size)."""
+    def _scan_route(self, component: bool, batch: int, n: int, k: int, restr: Optional[Restriction]) -> Tuple[bool, bool]:
+        """The one route decision of the candidate scans (the component scan, or the coarse one) -> (eligible, allowed).  eligible: the sizes are
+        the fused scan's (fused_*_min_items; the fused coarse selection holds K' <= 4096).  allowed: the restriction's rule, hidden_scan_route or
+        tagged_scan_route, expects the fused scan's threshold to hold.  Fused iff both; the component scan sizes its slices by `allowed` alone."""
+        eligible = n >= self.fused_component_min_items if component else (n >= self.fused_coarse_min_items and k <= 4096)
+        return eligible, restr is None or restr.allows_fused(self, component, batch, n, k)
+
+    def _scan_plan(self, component: bool, batch: int, n: int, k: int) -> Optional[Tuple[int, int, int, int]]:
+        """E.scan_plan of one scan's call as it will be sliced under a tag filter (host arithmetic, memoised per size)."""
         if component:
-            pq, px = eng.spec.query_dot_product_groups, eng.spec.item_dot_product_groups
+            spec = self._bind().spec
+            pq, px = spec.query_dot_product_groups, spec.item_dot_product_groups
             b = min(batch, max(1, E.TAGGED_COMPONENT_ROWS // pq))
             key = (b * pq * px, n, k, b * pq)
         else:
@@ -683,7 +720,7 @@ class _CorpusEdits(_ItemsById):
             if len(memo) > 64:
                 memo.clear()
             memo[key] = E.scan_plan(*key)
-        return tagged_scan_route(memo[key], tags.kept_min, n, k, self.TAGGED_FUSED_MIN_GROUPS)
+        return memo[key]
 
     def _check_taggable(self, what: str) -> None:
         """The refusal point of allowed_tags=: modules whose candidate generation cannot honour it raise here, before any launch."""
@@ -916,10 +953,8 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
         refuse_item_mask(self, kwargs)
         tags = self._take_allowed_tags(kwargs, query_embeddings.size(0), ())
         logits = self._raw_logits(query_embeddings, **kwargs)
-        if tags is not None:            # allowed_tags=: a row's disallowed columns hold -inf (the hidden ones are among them)
-            return E.scores_mask_tags(logits, tags)
-        vis = self._visible_mask()      # hidden columns hold -inf
-        return logits if vis is None else E.scores_mask(logits, vis)
+        restr = self._restriction(tags)      # the columns a row may not return -- disallowed by allowed_tags=, or hidden -- hold -inf
+        return logits if restr is None else restr.mask(logits)
 
     def _raw_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         eng = self._bind()
@@ -2080,28 +2115,83 @@ def _pinned_word(module) -> torch.Tensor:
 
 
 def _release_words(module, words) -> None:
-    free = module._flag_free
-    for w in words:
-        if not w.is_cuda and len(free) < 64:
-            free.append(w)
+    module._flag_free.extend(words[: max(0, 64 - len(module._flag_free))])
 
 
-def _verdicts_clear(pending: list, module=None) -> bool:
+def _verdicts_clear(pending: list, module) -> bool:
     """pending: int32 verdict words of fused scans (1 = a candidate count left its range), read after everything that depends on them is
-    enqueued.  Words in PINNED HOST memory (the component scans write theirs there: the kernels store through the device-visible address)
-    are read after a spin on an event -- no copy launch, no blocking sync (a blocking read parks the thread on an interrupt whose wake-up
-    costs 20-100 us of idle GPU per batch); device words cost one synchronising read each."""
+    enqueued.  They live in PINNED HOST memory (the kernels store through the device-visible address) and are read after a spin on an event -- no
+    copy launch, no blocking sync (a blocking read parks the thread on an interrupt whose wake-up costs 20-100 us of idle GPU per batch)."""
     if not pending:
         return True
-    if any(not b.is_cuda for b in pending) and torch.cuda.is_available():
+    if torch.cuda.is_available():
         ev = torch.cuda.Event()
         ev.record()
         while not ev.query():
             pass
-    clear = all(int(b.item() if b.is_cuda else b.numpy()[0]) == 0 for b in pending)     # (pinned words: a plain memory read through the numpy view)
-    if module is not None:
-        _release_words(module, pending)
-    return clear
+    _release_words(module, pending)
+    return all(int(b.numpy()[0]) == 0 for b in pending)     # (a plain memory read through the numpy view)
+
+
+class CandidateScan(NamedTuple):
+    """One candidate scan as _speculative_scan runs it: what differs between the coarse scan and the component scans, and nothing else."""
+    n: int                                      # items scanned
+    k: int                                      # selected per row of the score matrix
+    rows_per_query: int                         # rows of the score matrix per batch row
+    route: Callable[..., Tuple[bool, bool]]     # (batch, restriction) -> the module's _scan_route for this scan: (eligible, allowed)
+    width: Callable[[bool], int]                # (allowed) -> batch rows one call takes: the scans keep the query rows in LDS, wider batches go in slices
+    launch: Callable                            # (eq, flag, **Restriction.launch_kwargs()) -> (scores, positions, the verdict word), or None: sizes without a plan
+    scores: Callable[..., torch.Tensor]         # (eq, out=None, run_if=None) -> the materialised (rows, n) scores
+    redo_buffer: str                            # _buf tag of the recycled (rows, n) matrix of a redo on the device
+    redo_on_device: Callable[[int], bool]       # (batch) -> the redo is enqueued behind the fused launch, under its verdict word
+    device_flag: Callable[[], Optional[torch.Tensor]]   # the verdict word of a call the host does not defer; None: the launcher's own
+    shaped: Callable[..., torch.Tensor]         # (positions, batch) -> the positions as the scan's caller takes them
+
+
+def _speculative_scan(tk, scan: CandidateScan, eq: torch.Tensor, restr: Optional[Restriction], pending: Optional[list] = None, with_scores: bool = False):
+    """The one flow of the candidate scans: eq (B, P_Q, d) -> scan.shaped(positions) (with_scores: -> (scores, positions)), the exact top-k of every
+    row among the items `restr` lets it return.  The fused scan (no score matrix: 16 GB per 125 M-item shard at B = 32) is exact iff every row
+    collected between k and `capacity` candidates; its launches raise a verdict word otherwise, and one of three things follows:
+      the redo ON THE DEVICE: scorer, mask and top-k are enqueued under that word as their launch predicate and overwrite the outputs -- no-ops
+        unless a count was out of range, nothing for the host to wait for;
+      a DEFERRED verdict (`pending`, a list): the word lives in pinned host memory, where the kernels write it themselves (no copy launch); it is
+        appended, the positions are returned at once, and the caller reads it (_verdicts_clear, MoLAvgTopK.result) after it has enqueued all
+        that depends on them -- speculate, then verify: the GPU never waits for the host in mid-pipeline;
+      else the word is read here (one 4-byte D2H copy), and a failed verdict takes the materialising path of every scan that is not fused."""
+    n, k, batch = scan.n, scan.k, eq.shape[0]
+    for limit in (n,) if restr is None else (n, restr.count):
+        if k > limit:
+            raise RuntimeError(f"selected index k out of range (k={k}, n={limit})")
+    eligible, allowed = scan.route(batch, restr)
+    width = scan.width(allowed)
+    if batch > width:
+        parts = [_speculative_scan(tk, scan, eq[b0 : b0 + width], None if restr is None else restr.rows_slice(b0, b0 + width), pending, with_scores)
+                 for b0 in range(0, batch, width)]
+        return (torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)) if with_scores else torch.cat(parts, dim=0)
+    if eligible and allowed and not tk._no_fused:
+        on_device = scan.redo_on_device(batch)
+        # a word goes back to the free list when its verdict has been read -- or here, when no launch took it
+        word = _pinned_word(tk) if (not on_device and pending is not None) else None
+        fused = scan.launch(eq, scan.device_flag() if word is None else word, **({} if restr is None else restr.launch_kwargs()))
+        if fused is None:
+            _release_words(tk, () if word is None else (word,))
+        else:
+            sc, pos, bad = fused
+            if on_device:      # (the (rows, n) score buffer is recycled across calls)
+                rows = batch * scan.rows_per_query
+                scores = scan.scores(eq, out=tk._buf(scan.redo_buffer, rows * n, torch.float32).view(rows, n), run_if=bad)
+                if restr is not None:
+                    restr.mask(scores, run_if=bad)
+                E.topk(scores, k, out=(sc, pos), run_if=bad)
+            elif pending is not None:
+                pending.append(bad)
+            if on_device or pending is not None or int(bad.item()) == 0:
+                return (sc, pos) if with_scores else scan.shaped(pos, batch)
+    scores = scan.scores(eq)
+    if restr is not None:
+        restr.mask(scores)
+    sc, pos = E.topk(scores, k)
+    return (sc, pos) if with_scores else scan.shaped(pos, batch)
 
 
 class MoLAvgTopK(MoLTopKModule):
@@ -2144,14 +2234,12 @@ class MoLAvgTopK(MoLTopKModule):
         self._coarse_engine = None
         self._coarse_table = None
         self._coarse_prefilter = None
-        self._verdict_pool: list = []
         self._side_streams = None
         self._side_turn = 0
         self._prefilter_calls = 0                 # scans that looked at the int8 copy (the schedule of its statistics check)
         self._prefilter_pending = None            # (pinned copy of the header's counts, its event) on its way to the host
         self._redo_fit_memo: Dict[int, bool] = {} # _device_redo_fits by buffer size
 
-    HIDDEN_FUSED_MIN_VISIBLE = 0.5    # hidden_scan_route: the visible fraction below which a scan of a module with a hidden set is materialised directly
     OVERLAP_BATCHES = True            # submit(): speculative calls alternate between two streams of the module (see submit)
     PREFILTER_MIN_ITEMS = 4_000_000   # the int8 copy of the coarse table pays where the streaming pass is bound by HBM reads
 
@@ -2240,65 +2328,22 @@ class MoLAvgTopK(MoLTopKModule):
                              tags: Optional[E.TagFilter] = None):
         """(B, P_Q, d) query components -> (B, avg_top_k) positions of the coarse top-K', best first
         (with_scores: -> (scores, positions), the bf16 coarse scores as fp32).
-        The fused scan's result is exact iff every row collected between K' and `capacity` candidates.  With `pending` (a
-        list) the check is DEFERRED: the positions are returned at once, the scan's device verdict word (1 = out of range) is
-        appended, and the caller reads it after it has enqueued everything that depends on the positions (speculate, then
-        verify: the GPU never waits for the host in mid-pipeline).  Without it the check is made here (one 4-byte D2H copy)."""
-        eng = self._bind()
-        table = self._table()
+        The coarse scan's entry to _speculative_scan, which holds the flow: `pending` (a list) DEFERS the fused scan's verdict to the caller."""
+        eng, table, k = self._bind(), self._table(), self._avg_top_k
         n = table.shape[0]
-        if self._avg_top_k > n:
-            raise RuntimeError(f"selected index k out of range (k={self._avg_top_k}, n={n})")
-        self._check_k_visible(self._avg_top_k)
-        # a hidden set (DESIGN section 3.14): the fused scan runs its visible kernels; every materialised score matrix -- the direct route of a
-        # mostly hidden corpus, the predicated redo, the redo after a failed verdict -- has its hidden columns set to -inf before the selection
-        vis = self._visible_mask()
-        fused_ok = vis is None or hidden_scan_route(n, self.num_visible, self._avg_top_k, self.HIDDEN_FUSED_MIN_VISIBLE) == "fused"
-        # allowed_tags= (DESIGN section 3.15): the fused scan runs its tagged kernels where the plan-aware rule expects enough finite group maxima
-        # for the least-kept row; every materialised score matrix has the entries a row may not return (a hidden item's included: the effective
-        # tags) set to -inf before the selection
-        if tags is not None:
-            fused_ok = self._tagged_route(eng, tags, eq.shape[0], n, self._avg_top_k, False) == "fused"
-        if eq.shape[0] > 128:   # the scan keeps ceil(B / 32) query tiles in LDS: larger batches go in slices
-            parts = [self._coarse_topk_from_eq(eq[b0 : b0 + 128], average_queries, pending, with_scores, None if tags is None else tags.rows_slice(b0, b0 + 128))
-                     for b0 in range(0, eq.shape[0], 128)]
-            return (torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)) if with_scores else torch.cat(parts, dim=0)
-        # large corpora: fused scan + threshold select, no (B, N) score matrix (16 GB per 125 M-item shard at B = 32).
-        # Same scores and the same exact top-K' as the materialising path below -- when every query's candidate count
-        # landed inside [K', capacity]; the check costs one 128-byte device-to-host copy.
-        if n >= self.fused_coarse_min_items and self._avg_top_k <= 4096 and not self._no_fused and fused_ok:
-            on_device = self._device_redo_fits(eq.shape[0] * n * 4, n)
-            # a verdict the HOST reads (no device redo, the caller defers the look): the word lives in pinned host memory and the kernels write it
-            # there themselves -- no 4-byte copy behind the call's last launch (round 6, as the component scans)
-            word = _pinned_word(self) if (not on_device and pending is not None) else None
-            fused = eng.coarse_topk(eq, table, average_queries, self._avg_top_k, with_flag=True, prefilter=self._prefilter(),
-                                    flag=word, visible=None if tags is not None else self._visible, tags=tags)
-            if fused is not None:
-                # bad: 1 iff some row's candidate count is outside [K', capacity] -- raised by the call's key-selection launch
-                sc, idx, counts, bad = fused
-                if on_device:
-                    # the redo ON THE DEVICE: the materialising scan and its top-K' are enqueued under that flag as their launch
-                    # predicate and overwrite (sc, idx) -- no-ops unless a count was out of range; nothing for the host to wait
-                    # for (the (B, N) score buffer is recycled across calls)
-                    coarse = eng.coarse_scores(eq, table, average_queries, out=self._buf("coarse_all", eq.shape[0] * n, torch.float32).view(eq.shape[0], n), run_if=bad)
-                    if tags is not None:
-                        E.scores_mask_tags(coarse, tags, run_if=bad)
-                    elif vis is not None:
-                        E.scores_mask(coarse, vis, run_if=bad)
-                    E.topk(coarse, self._avg_top_k, out=(sc, idx), run_if=bad)
-                    return (sc, idx) if with_scores else idx
-                if pending is not None:      # the caller reads the verdict word after it has enqueued everything that follows
-                    pending.append(bad)
-                    return (sc, idx) if with_scores else idx
-                if int(bad.item()) == 0:
-                    return (sc, idx) if with_scores else idx
-        coarse = eng.coarse_scores(eq, table, average_queries)
-        if tags is not None:
-            E.scores_mask_tags(coarse, tags)
-        elif vis is not None:
-            E.scores_mask(coarse, vis)
-        sc, idx = E.topk(coarse, self._avg_top_k)
-        return (sc, idx) if with_scores else idx
+
+        def launch(eq, flag, **restriction):
+            out = eng.coarse_topk(eq, table, average_queries, k, with_flag=True, prefilter=self._prefilter(), flag=flag, **restriction)
+            return None if out is None else (out[0], out[1], out[3])
+
+        scan = CandidateScan(
+            n=n, k=k, rows_per_query=1, route=lambda batch, restr: self._scan_route(False, batch, n, k, restr),
+            width=lambda allowed: 128,      # the scan keeps ceil(B / 32) query tiles in LDS
+            launch=launch, scores=lambda eq, out=None, run_if=None: eng.coarse_scores(eq, table, average_queries, out=out, run_if=run_if),
+            redo_buffer="coarse_all", redo_on_device=lambda batch: self._device_redo_fits(batch * n * 4, n),
+            device_flag=lambda: None,       # the tail of the launch's own counts
+            shaped=lambda pos, batch: pos)
+        return _speculative_scan(self, scan, eq, self._restriction(tags), pending, with_scores)
 
     def rerank(self, qpack: torch.Tensor, batch: int, cand_idx: torch.Tensor, k: int):
         """Full MoL on per-row candidates (positions, (B, K')) -> exact top-min(k, K') among them."""
@@ -2307,7 +2352,7 @@ class MoLAvgTopK(MoLTopKModule):
         return E.topk_candidates(scores, min(k, cand_idx.shape[1]), cand_idx, self._ids_flat)
 
     def _enqueue(self, query_embeddings: torch.Tensor, k: int, pending: list, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        """One pass of forward's launches; the device verdicts of the fused scan (int32 words, 1 = redo) are appended to `pending`."""
+        """One pass of forward's launches; the verdict words of the fused scan (int32 in pinned host memory, 1 = redo) are appended to `pending`."""
         # the reference's four profiler spans (mol_top_k.py:350-382), around the launches that do the same work here (entered only
         # under a profiler: a span costs ~9 us of host time, four of them more than the GPU needs for the launches they bracket)
         span = torch.profiler.record_function if torch.autograd._profiler_enabled() else (lambda name: contextlib.nullcontext())
@@ -2325,7 +2370,7 @@ class MoLAvgTopK(MoLTopKModule):
     # ---- two-stage form of forward ---------------------------------------------------------------------------------------------
     # The fused coarse scan is exact unless a candidate count left its range (heavy ties at the threshold), which only the device
     # knows when the launches are enqueued.  forward() = result(submit()): submit enqueues the whole call on that assumption and
-    # copies the scan's verdict word to pinned host memory behind it; result waits for THAT copy (not for the stream), and redoes
+    # records an event behind it; result waits for THAT event (not for the stream) to read the scan's verdict word, and redoes
     # the call on the materialising path in the rare other case.  A caller with the next batch at hand calls submit(batch i + 1)
     # before result(batch i): the host's look at the verdict then costs the GPU nothing (bench.py --two-pass reports both rates).
     # The handle submit() returns is OPAQUE: the tensors inside it may still be in flight on a stream of the module's own and are
@@ -2355,15 +2400,7 @@ class MoLAvgTopK(MoLTopKModule):
         pending: list = []
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()), self.one_bind():
             scores, ids = self._enqueue(query_embeddings, k, pending, **kwargs)
-            if not pending:
-                host = None
-            elif all(not bad.is_cuda for bad in pending):
-                host = list(pending)           # already in pinned host memory (written by the scans themselves): nothing to copy
-            else:
-                pool = self._verdict_pool      # pinned words go back to the pool in result(): no host allocation per call
-                host = pool.pop() if pool and pool[-1].numel() == len(pending) else torch.empty(len(pending), dtype=torch.int32, pin_memory=True)
-                for j, bad in enumerate(pending):
-                    host[j : j + 1].copy_(bad, non_blocking=True)
+            host = list(pending) or None       # the verdict words, in pinned host memory (written by the scans themselves): nothing to copy
             done = torch.cuda.Event() if (pending or side is not None) else None
             if done is not None:
                 done.record()
@@ -2384,13 +2421,8 @@ class MoLAvgTopK(MoLTopKModule):
         if host is not None:
             while not done.query():      # spin: the word is microseconds away, and a blocking wait parks the thread on an interrupt whose
                 pass                     # wake-up costs 50-100 us of GPU idle per batch (see MoLBruteForceTopK._read_stats)
-            if isinstance(host, list):
-                redo = any(int(w.numpy()[0]) != 0 for w in host)
-                _release_words(self, host)
-            else:
-                redo = int(host.max()) != 0
-                if len(self._verdict_pool) < 8:
-                    self._verdict_pool.append(host)
+            redo = any(int(w.numpy()[0]) != 0 for w in host)
+            _release_words(self, host)
         if not redo:
             return scores, ids
         self._no_fused = True      # redo this call on the materialising path
@@ -2455,7 +2487,6 @@ class _ComponentCandidates:
     supply _candidates(eq, pending) -> (B, _union_width()) positions.  Mixed in BEFORE the MoL base class: its forward / forward_filtered are
     the modules' own."""
 
-    HIDDEN_FUSED_MIN_VISIBLE = 0.5         # hidden_scan_route's fraction (as MoLAvgTopK's)
     fused_component_min_items = 262144     # below this the (B * P_Q * P_X, N) component scores are small and one launch chain shorter
     NO_FILTER_FUSION = False               # tests: True keeps the seen-id filter out of the selection launch
 
@@ -2524,61 +2555,28 @@ class _ComponentCandidates:
     def _component_topk(self, eq: torch.Tensor, k_per_group: int, pending: Optional[list] = None, with_scores: bool = False,
                         tags: Optional[E.TagFilter] = None):
         """-> (B, P_Q * P_X * k_per_group) positions: top k_per_group items of every (query group, item group) pair.
-        `pending`: deferred validity check of the fused scan, as in MoLAvgTopK._coarse_topk_from_eq.
+        The component scan's entry to _speculative_scan, which holds the flow: `pending` (a list) DEFERS the fused scan's verdict to the caller.
         with_scores: -> (scores, positions), both (B * P_Q * P_X, k_per_group), best first: the bf16 component scores as fp32."""
-        eng = self._bind()
-        table = self._component_table()      # (P_X, N, d), item-group-major
-        n = table.shape[1]
-        if k_per_group > n:
-            raise RuntimeError(f"selected index k out of range (k={k_per_group}, n={n})")
-        self._check_k_visible(k_per_group)
-        vis = self._visible_mask()      # a hidden set: as in MoLAvgTopK._coarse_topk_from_eq
-        fused_ok = vis is None or hidden_scan_route(n, self.num_visible, k_per_group, self.HIDDEN_FUSED_MIN_VISIBLE) == "fused"
-        if tags is not None:            # allowed_tags=: as in MoLAvgTopK._coarse_topk_from_eq
-            fused_ok = self._tagged_route(eng, tags, eq.shape[0], n, k_per_group, True) == "fused"
-        # the component scans keep the fragments of all B * P_Q query rows in LDS and (the fused form) eight row tiles of running maxima in
-        # registers (four at d = 128): batches beyond 256 (128) query rows go in slices
-        max_b = max(1, (128 if eng.spec.dot_product_dimension >= 128 else 256) // eng.spec.query_dot_product_groups)
-        if tags is not None and fused_ok:      # (the tagged sample keeps four row tiles at every d: its eight-tile form would spill)
-            max_b = max(1, E.TAGGED_COMPONENT_ROWS // eng.spec.query_dot_product_groups)
-        if eq.shape[0] > max_b:
-            parts = [self._component_topk(eq[b0 : b0 + max_b], k_per_group, pending, with_scores, None if tags is None else tags.rows_slice(b0, b0 + max_b))
-                     for b0 in range(0, eq.shape[0], max_b)]
-            return (torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)) if with_scores else torch.cat(parts, dim=0)
-        # large corpora: fused scan + threshold select, no (B*P_Q*P_X, N) score matrix (5.7 GB at amzn-books, B = 32);
-        # identical to the materialising path below whenever every row's candidate count is inside [k, capacity]
-        if n >= self.fused_component_min_items and not self._no_fused and fused_ok:
-            rows = eq.shape[0] * eng.spec.query_dot_product_groups * eng.spec.item_dot_product_groups
-            on_device = rows * n * 4 <= MoLAvgTopK.DEVICE_REDO_BYTES
-            if on_device:
-                flag = self._buf("redo_flag_c", 1, torch.int32)      # (zeroed by the call's first launch)
-            else:
-                # the verdict word in pinned host memory, written by the kernels themselves: the caller spins on an event and reads it (no 4-byte
-                # copy launch, no blocking .item(): ~30 us of every Naive / Comb call at amzn-books)
-                flag = _pinned_word(self)
-            fused = eng.component_topk(eq, table, k_per_group, flag, visible=None if tags is not None else self._visible, tags=tags)
-            if fused is not None:
-                sc_c, pos, counts = fused
-                if on_device:     # redo on the device under the flag, as in MoLAvgTopK._coarse_topk_from_eq
-                    scores = eng.component_scores(eq, table, out=self._buf("component_all", rows * n, torch.float32).view(rows, n), run_if=flag)
-                    if tags is not None:
-                        E.scores_mask_tags(scores, tags, run_if=flag)
-                    elif vis is not None:
-                        E.scores_mask(scores, vis, run_if=flag)
-                    E.topk(scores, k_per_group, out=(sc_c, pos), run_if=flag)
-                    return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
-                if pending is not None:      # a device verdict word (1 = redo), read by the caller once everything is enqueued
-                    pending.append(flag)
-                    return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
-                if int(flag.item()) == 0:
-                    return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
-        scores = eng.component_scores(eq, table)
-        if tags is not None:            # (P_Q * P_X rows of the matrix per query row share its allow word)
-            E.scores_mask_tags(scores, tags)
-        elif vis is not None:
-            E.scores_mask(scores, vis)
-        sc_c, pos = E.topk(scores, k_per_group)
-        return (sc_c, pos) if with_scores else pos.view(eq.shape[0], -1)
+        eng, table = self._bind(), self._component_table()      # (P_X, N, d), item-group-major
+        n, k = table.shape[1], k_per_group
+        pq, px = eng.spec.query_dot_product_groups, eng.spec.item_dot_product_groups
+        # the scans keep the fragments of all B * P_Q query rows in LDS and (the fused form) eight row tiles of running maxima in registers (four
+        # at d = 128): 256 (128) query rows per call; the tagged sample keeps four row tiles at every d (its eight-tile form would spill)
+        plain_rows = 128 if eng.spec.dot_product_dimension >= 128 else 256
+
+        def launch(eq, flag, **restriction):      # (flag: zeroed by the call's first launch)
+            out = eng.component_topk(eq, table, k, flag, **restriction)
+            return None if out is None else (out[0], out[1], flag)
+
+        scan = CandidateScan(
+            n=n, k=k, rows_per_query=pq * px, route=lambda batch, restr: self._scan_route(True, batch, n, k, restr),
+            width=lambda allowed: max(1, (E.TAGGED_COMPONENT_ROWS if tags is not None and allowed else plain_rows) // pq),
+            launch=launch, scores=lambda eq, out=None, run_if=None: eng.component_scores(eq, table, out=out, run_if=run_if),
+            # (the limit is MoLAvgTopK's, read from the class: MoLNaiveTopK is no Avg module; 5.7 GB of scores at amzn-books, B = 32, leave the verdict to the host)
+            redo_buffer="component_all", redo_on_device=lambda batch: batch * pq * px * n * 4 <= MoLAvgTopK.DEVICE_REDO_BYTES,
+            device_flag=lambda: self._buf("redo_flag_c", 1, torch.int32),
+            shaped=lambda pos, batch: pos.view(batch, -1))
+        return _speculative_scan(self, scan, eq, self._restriction(tags), pending, with_scores)
 
     # ---- the two halves of _ranked on their own, for the item-sharded global form (sharded.ShardedMoLNaiveTopK / ShardedMoLCombTopK) -----------
     def _candidates_scored(self, eq: torch.Tensor, pending: list):
@@ -2649,7 +2647,7 @@ class _ComponentCandidates:
         fewer than k + width distinct positions raises the same word and the call is redone on the sorted form."""
         eng = self._bind()
         big = all_indices.shape[1] > self.UNION_CAP
-        word = next((b for b in (pending or []) if not b.is_cuda), None)
+        word = pending[0] if pending else None
         if seen is not None and word is not None and self.UNSORTED_RERANK and not self._no_fused:
             invalid_ids, k_out = seen
             pos = all_indices.to(torch.int64).contiguous()
