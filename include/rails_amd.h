@@ -48,7 +48,8 @@ extern "C" {
  * MoLNaiveTopK / MoLCombTopK, the list edit rails_ivf_lists_edit[_workspace_bytes] of the IVF index, the item masks rails_item_mask_* /
  * rails_scores_mask, the hidden-item entries rails_item_mask_clear / rails_mol_coarse_topk_visible / rails_mol_component_topk_visible and the
  * item-tag entries rails_item_tags_effective / rails_item_tags_count / rails_item_mask_from_tags / rails_scores_mask_tags / rails_mol_coarse_topk_tagged /
- * rails_mol_component_topk_tagged / rails_mol_scan_plan
+ * rails_mol_component_topk_tagged / rails_mol_scan_plan and the filtered-list entries rails_ivf_list_words / rails_ivf_list_counts /
+ * rails_ivf_plan_filtered / rails_ivf_search_filtered
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -562,6 +563,32 @@ int rails_ivf_search(const rails_mol_shape* shape, const float* eq, int32_t batc
                      const int32_t* positions, const int32_t* offsets, int64_t n_items, int32_t nlist, int32_t nprobe, int32_t max_probes,
                      int32_t max_list, int32_t k_per_group, void* workspace, size_t workspace_bytes, int64_t* out_positions, int32_t* unfilled,
                      void* stream);
+/* ---- filtered lists: the hidden set and allowed_tags inside the list scan (added under ABI 15: new entries only) -----
+ * A filtered search returns, in the rows of query b, only items x with word(x) & allowed[b] != 0, and equals the plain search of an index built
+ * with the same centroids from the kept items alone (positions mapped through the kept rows): the short-list rule counts a list's ELIGIBLE
+ * entries, the scan drops the others before they are offered (their vectors are not read), the merge is rails_ivf_search's.
+ * rails_ivf_list_words: list_words[m][slot] = word(positions[m][slot]) over the (groups, n_items) list entries, where word(x) = eff_tags[x]
+ * (rails_item_tags_effective's array) or, with visible_words (one mask row of the corpus) instead, 0xffffffff for a visible item and 0 for a
+ * hidden one.  Exactly one of the two is given.  One launch.
+ * rails_ivf_list_counts: counts[r][m][l] = #{slot in list l of group m : list_words[m][slot] & allowed[r] != 0}, r < count_rows
+ * ((count_rows, groups, nlist) int32).  One workgroup per (list, group), no atomics.
+ * rails_ivf_plan_filtered: HOST pointers.  *max_probes = the probe capacity the short-list rule needs over every (row, group) of a host copy
+ * of counts: the fewest lists whose counts reach k_per_group (nlist where they never do), at least nprobe, at most nlist.
+ * rails_ivf_search_filtered: rails_ivf_search plus list_words, allowed (one word per BATCH row), counts and count_rows (1: one row of counts
+ * shared by the batch; else batch).  list_words == NULL is rails_ivf_search itself.  max_list stays rails_ivf_plan's (the scan walks whole
+ * lists); max_probes, the segments and the workspace only size the work.  A row whose eligible items are fewer than k_per_group raises
+ * *unfilled: callers check the kept counts on the host first. */
+int rails_ivf_list_words(const int32_t* positions, int32_t groups, int64_t n_items, const uint32_t* eff_tags, const uint32_t* visible_words,
+                         uint32_t* list_words, void* stream);
+int rails_ivf_list_counts(const uint32_t* list_words, const int32_t* offsets, int32_t groups, int64_t n_items, int32_t nlist, const uint32_t* allowed,
+                          int32_t count_rows, int32_t* counts, void* stream);
+int rails_ivf_plan_filtered(const int32_t* counts, int32_t count_rows, int32_t groups, int32_t nlist, int32_t nprobe, int32_t k_per_group,
+                            int32_t* max_probes);
+int rails_ivf_search_filtered(const rails_mol_shape* shape, const float* eq, int32_t batch, const float* centroids, const void* vectors,
+                              const int32_t* positions, const int32_t* offsets, int64_t n_items, int32_t nlist, int32_t nprobe, int32_t max_probes,
+                              int32_t max_list, int32_t k_per_group, void* workspace, size_t workspace_bytes, int64_t* out_positions,
+                              int32_t* unfilled, const uint32_t* list_words, const uint32_t* allowed, const int32_t* counts, int32_t count_rows,
+                              void* stream);
 /* torch.sort(indices, dim=1) on (rows, n) int64, n <= 16384 (mol_top_k.py:257, :515); in == out allowed. */
 int rails_sort_rows_i64(const int64_t* in, int32_t rows, int32_t n, int64_t* out, void* stream);
 /* scores[r][j] = fill where sorted_idx[r][j] == sorted_idx[r][j-1] (mol_top_k.py:277-284, :535-542). */

@@ -1622,4 +1622,58 @@ int rails_ivf_search(const rails_mol_shape* s, const float* eq, int32_t batch, c
                          workspace_bytes, out_positions, unfilled, (hipStream_t)stream), "ivf_search");
 }
 
+
+int rails_ivf_list_words(const int32_t* positions, int32_t groups, int64_t n_items, const uint32_t* eff_tags, const uint32_t* visible_words,
+                         uint32_t* list_words, void* stream) {
+  g_err[0] = '\0';
+  if (groups < 1 || n_items < 1 || n_items > 0x7fffffffLL) { set_error("ivf_list_words: groups = %d or n_items = %lld outside [1, 2^31)", groups, (long long)n_items); return RAILS_EINVAL; }
+  if (!positions || !list_words || (eff_tags == nullptr) == (visible_words == nullptr)) {
+    set_error("ivf_list_words: NULL pointer, or not exactly one of eff_tags and visible_words");
+    return RAILS_EINVAL;
+  }
+  return fail(ivf_list_words(positions, groups, n_items, eff_tags, visible_words, list_words, (hipStream_t)stream), "ivf_list_words");
+}
+
+int rails_ivf_list_counts(const uint32_t* list_words, const int32_t* offsets, int32_t groups, int64_t n_items, int32_t nlist, const uint32_t* allowed,
+                          int32_t count_rows, int32_t* counts, void* stream) {
+  g_err[0] = '\0';
+  if (groups < 1 || n_items < 1 || n_items > 0x7fffffffLL || nlist < 1 || nlist > 4096 || count_rows < 1) {
+    set_error("ivf_list_counts: groups = %d, n_items = %lld, nlist = %d or count_rows = %d outside the limits", groups, (long long)n_items, nlist, count_rows);
+    return RAILS_EINVAL;
+  }
+  if (!list_words || !offsets || !allowed || !counts) { set_error("ivf_list_counts: NULL pointer"); return RAILS_EINVAL; }
+  return fail(ivf_list_counts(list_words, offsets, groups, n_items, nlist, allowed, count_rows, counts, (hipStream_t)stream), "ivf_list_counts");
+}
+
+int rails_ivf_plan_filtered(const int32_t* counts, int32_t count_rows, int32_t groups, int32_t nlist, int32_t nprobe, int32_t k_per_group,
+                            int32_t* max_probes) {
+  g_err[0] = '\0';
+  if (!counts || !max_probes || count_rows < 1 || groups < 1 || nlist <= 0 || nprobe <= 0 || k_per_group <= 0) { set_error("ivf_plan_filtered: bad argument"); return RAILS_EINVAL; }
+  *max_probes = ivf_plan_filtered(counts, count_rows, groups, nlist, std::min(nprobe, nlist), k_per_group);
+  return RAILS_OK;
+}
+
+int rails_ivf_search_filtered(const rails_mol_shape* s, const float* eq, int32_t batch, const float* centroids, const void* vectors, const int32_t* positions,
+                              const int32_t* offsets, int64_t n_items, int32_t nlist, int32_t nprobe, int32_t max_probes, int32_t max_list,
+                              int32_t k_per_group, void* workspace, size_t workspace_bytes, int64_t* out_positions, int32_t* unfilled,
+                              const uint32_t* list_words, const uint32_t* allowed, const int32_t* counts, int32_t count_rows, void* stream) {
+  if (!list_words)
+    return rails_ivf_search(s, eq, batch, centroids, vectors, positions, offsets, n_items, nlist, nprobe, max_probes, max_list, k_per_group, workspace,
+                            workspace_bytes, out_positions, unfilled, stream);
+  g_err[0] = '\0';
+  if (!shape_ok(s)) return RAILS_EINVAL;
+  if (batch < 0) { set_error("ivf_search_filtered: negative batch"); return RAILS_EINVAL; }
+  const int c = ivf_search_check(*s, nlist, nprobe, max_probes, max_list, k_per_group, n_items);
+  if (c != kOk) return c;
+  if (batch == 0) return RAILS_OK;
+  if (!eq || !centroids || !vectors || !positions || !offsets || !workspace || !out_positions || !allowed || !counts) {
+    set_error("ivf_search_filtered: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  if (count_rows != 1 && count_rows != batch) { set_error("ivf_search_filtered: count_rows = %d is neither 1 nor batch = %d", count_rows, batch); return RAILS_EINVAL; }
+  return fail(ivf_search_filtered(*s, eq, batch, centroids, vectors, positions, offsets, n_items, nlist, nprobe, max_probes, max_list, k_per_group, workspace,
+                                  workspace_bytes, out_positions, unfilled, list_words, allowed, counts, count_rows, (hipStream_t)stream),
+              "ivf_search_filtered");
+}
+
 }  // extern "C"

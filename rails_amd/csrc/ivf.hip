@@ -13,6 +13,9 @@
 //              nprobe in coarse-score order while the probed lists hold fewer than k items), scan (one workgroup per
 //              (m, list, segment): the rows that probe the list find it there, so each probed list is read once per call), merge
 //              (the partial top-k of every probe and segment -> k positions per row).  Tie rule everywhere: score desc, position asc.
+//   filtered   the same three launches with the hidden set / a per-row tag filter INSIDE them: the filter gathered into list order once
+//              (list words beside the positions), the eligible entries counted per (row, group, list); the coarse rule then counts eligible
+//              entries, the scan offers eligible entries only -- the result is the plain search of the lists without the others.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -529,10 +532,13 @@ struct WaveTopK {
 
 // Coarse: one workgroup per row (b, i, m).  Scores every centroid, then takes lists best-first until nprobe are taken and they hold at
 // least k items (the short-list rule), at most max_probes.  probes[row][r] (-1 beyond), nprob[row].
-template <int D>
-__global__ __launch_bounds__(256) void mol_ivf_coarse_kernel(const float* __restrict__ eq, int G, const float* __restrict__ cent, int nlist,
-                                                             const int32_t* __restrict__ offsets, int nprobe, int k, int max_probes,
-                                                             int32_t* __restrict__ probes, int32_t* __restrict__ nprob, int32_t* __restrict__ unfilled) {
+// kFiltered ("filtered lists"): the rule counts the items the row's filter keeps in a list -- counts[r][m][l], r = 0 for
+// a filter shared by the batch (count_rows == 1), else the row's query b = qrow / PQ -- where the plain kernel counts the list's entries.
+template <int D, bool kFiltered>
+__device__ __forceinline__ void ivf_coarse_body(const float* __restrict__ eq, int G, const float* __restrict__ cent, int nlist,
+                                                const int32_t* __restrict__ offsets, int nprobe, int k, int max_probes, int32_t* __restrict__ probes,
+                                                int32_t* __restrict__ nprob, int32_t* __restrict__ unfilled, const int32_t* __restrict__ counts,
+                                                int count_rows, int PQ) {
   __shared__ float sc[kMaxNlist];
   __shared__ float rv[4];
   __shared__ int ri[4];
@@ -557,7 +563,7 @@ __global__ __launch_bounds__(256) void mol_ivf_coarse_kernel(const float* __rest
     }
     sc[l] = acc != acc ? -INFINITY : acc;       // a NaN query still takes lists (in id order): every row gets k items
   }
-  const int32_t* off = offsets + (int64_t)m * (nlist + 1);
+  const int32_t* off = kFiltered ? counts + ((int64_t)(count_rows == 1 ? 0 : qrow / PQ) * G + m) * nlist : offsets + (int64_t)m * (nlist + 1);
   int32_t* out = probes + (int64_t)row * max_probes;
   int taken = 0;
   int64_t held = 0;
@@ -581,7 +587,7 @@ __global__ __launch_bounds__(256) void mol_ivf_coarse_kernel(const float* __rest
     for (int w = 1; w < 4; ++w)
       if (rv[w] > vL || (rv[w] == vL && ri[w] < L)) { vL = rv[w]; L = ri[w]; }
     if (L >= nlist) break;                                 // every list taken (cannot happen with max_probes <= nlist)
-    held += off[L + 1] - off[L];
+    held += kFiltered ? off[L] : off[L + 1] - off[L];
     if (tid == 0) { out[taken] = L; sc[L] = NAN; }
     ++taken;
     __syncthreads();
@@ -591,14 +597,33 @@ __global__ __launch_bounds__(256) void mol_ivf_coarse_kernel(const float* __rest
   if (tid == 0) nprob[row] = taken;
 }
 
+template <int D>
+__global__ __launch_bounds__(256) void mol_ivf_coarse_kernel(const float* __restrict__ eq, int G, const float* __restrict__ cent, int nlist,
+                                                             const int32_t* __restrict__ offsets, int nprobe, int k, int max_probes,
+                                                             int32_t* __restrict__ probes, int32_t* __restrict__ nprob, int32_t* __restrict__ unfilled) {
+  ivf_coarse_body<D, false>(eq, G, cent, nlist, offsets, nprobe, k, max_probes, probes, nprob, unfilled, nullptr, 1, 1);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void mol_ivf_coarse_filtered_kernel(const float* __restrict__ eq, int G, const float* __restrict__ cent, int nlist,
+                                                                      const int32_t* __restrict__ counts, int count_rows, int PQ, int nprobe, int k,
+                                                                      int max_probes, int32_t* __restrict__ probes, int32_t* __restrict__ nprob,
+                                                                      int32_t* __restrict__ unfilled) {
+  ivf_coarse_body<D, true>(eq, G, cent, nlist, nullptr, nprobe, k, max_probes, probes, nprob, unfilled, counts, count_rows, PQ);
+}
+
 // Scan: workgroup (segment, list, group).  Collects the probes of this list (at most one per query row), then each wave runs one
 // probe over the segment's items at a time: fp32 dot of the query with the fp16 vectors (dims in order), running top-k.
 // part_s / part_p [(row * max_probes + r) * n_seg + seg][k].
-template <int D, int KS>
-__global__ __launch_bounds__(256) void mol_ivf_scan_kernel(const float* __restrict__ eq, int qrows, int G, int nlist, const unsigned short* __restrict__ vec16,
-                                                           const int32_t* __restrict__ pos, const int32_t* __restrict__ offsets, int64_t n,
-                                                           const int32_t* __restrict__ probes, int max_probes, int seg_items, int n_seg, int k,
-                                                           float* __restrict__ part_s, int32_t* __restrict__ part_p) {
+// kFiltered: an entry whose word in list_words (the filter in list order, beside `pos`) shares no bit with the allow word of the probe's query
+// (allowed[slot / max_probes / G / PQ], wave-uniform) is not offered, and its vector is not read; a segment without an eligible entry leaves
+// the sentinels (-inf, 0x7fffffff), which the merge never takes.
+template <int D, int KS, bool kFiltered>
+__device__ __forceinline__ void ivf_scan_body(const float* __restrict__ eq, int qrows, int G, int nlist, const unsigned short* __restrict__ vec16,
+                                              const int32_t* __restrict__ pos, const int32_t* __restrict__ offsets, int64_t n,
+                                              const int32_t* __restrict__ probes, int max_probes, int seg_items, int n_seg, int k,
+                                              float* __restrict__ part_s, int32_t* __restrict__ part_p, const uint32_t* __restrict__ list_words,
+                                              const uint32_t* __restrict__ allowed, int PQ) {
   __shared__ int match[kSliceRows];
   __shared__ int n_match;
   const int seg = blockIdx.x, l = blockIdx.y, m = blockIdx.z;
@@ -623,10 +648,13 @@ __global__ __launch_bounds__(256) void mol_ivf_scan_kernel(const float* __restri
     float x[D];
 #pragma unroll
     for (int t = 0; t < D; ++t) x[t] = q[t];
+    uint32_t aw = 0;
+    if (kFiltered) aw = allowed[slot / max_probes / G / PQ];
     WaveTopK<KS> top;
     for (int i0 = s0; i0 < s1; i0 += 64) {
       const int i = i0 + lane;
-      const bool valid = i < s1;
+      bool valid = i < s1;
+      if (kFiltered) valid = valid && (list_words[base + i] & aw) != 0u;
       float acc = 0.0f;
       int p = 0;
       if (valid) {
@@ -649,6 +677,70 @@ __global__ __launch_bounds__(256) void mol_ivf_scan_kernel(const float* __restri
     const int64_t o = ((int64_t)slot * n_seg + seg) * k;
     if (lane < k) { part_s[o + lane] = top.s0; part_p[o + lane] = top.p0; }
     if (KS == 2 && 64 + lane < k) { part_s[o + 64 + lane] = top.s1; part_p[o + 64 + lane] = top.p1; }
+  }
+}
+
+template <int D, int KS>
+__global__ __launch_bounds__(256) void mol_ivf_scan_kernel(const float* __restrict__ eq, int qrows, int G, int nlist, const unsigned short* __restrict__ vec16,
+                                                           const int32_t* __restrict__ pos, const int32_t* __restrict__ offsets, int64_t n,
+                                                           const int32_t* __restrict__ probes, int max_probes, int seg_items, int n_seg, int k,
+                                                           float* __restrict__ part_s, int32_t* __restrict__ part_p) {
+  ivf_scan_body<D, KS, false>(eq, qrows, G, nlist, vec16, pos, offsets, n, probes, max_probes, seg_items, n_seg, k, part_s, part_p, nullptr, nullptr, 1);
+}
+
+template <int D, int KS>
+__global__ __launch_bounds__(256) void mol_ivf_scan_filtered_kernel(const float* __restrict__ eq, int qrows, int G, int nlist,
+                                                                    const unsigned short* __restrict__ vec16, const int32_t* __restrict__ pos,
+                                                                    const int32_t* __restrict__ offsets, int64_t n, const int32_t* __restrict__ probes,
+                                                                    int max_probes, int seg_items, int n_seg, int k, float* __restrict__ part_s,
+                                                                    int32_t* __restrict__ part_p, const uint32_t* __restrict__ list_words,
+                                                                    const uint32_t* __restrict__ allowed, int PQ) {
+  ivf_scan_body<D, KS, true>(eq, qrows, G, nlist, vec16, pos, offsets, n, probes, max_probes, seg_items, n_seg, k, part_s, part_p, list_words, allowed, PQ);
+}
+
+// ---- the filter in list order (filtered lists) ---------------------------------------------------------------------------------------
+
+// list_words[m][slot] = word(pos[m][slot]): the item's effective tag word, or (no tags) all ones for a visible item and 0 for a hidden one
+__global__ void mol_ivf_list_words_kernel(const int32_t* __restrict__ pos, int64_t total, int64_t n, const uint32_t* __restrict__ eff,
+                                          const uint32_t* __restrict__ visible, uint32_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int p = pos[i];
+  uint32_t w = 0u;
+  if (p >= 0 && p < n) w = eff ? eff[p] : (((visible[p >> 5] >> (p & 31)) & 1u) ? 0xffffffffu : 0u);
+  out[i] = w;
+}
+
+// counts[r][m][l] = entries of list l of group m whose word shares a bit with allowed[r].  One workgroup per (list, group); 64 allow words at
+// a time sit in LDS, every 64-entry chunk of the list is tested against each (ballot + popcount, the sum kept by the lane of the word's
+// index); the four waves' sums meet in LDS.  No atomics.
+__global__ __launch_bounds__(256) void mol_ivf_list_counts_kernel(const uint32_t* __restrict__ list_words, const int32_t* __restrict__ offsets, int64_t n,
+                                                                  int nlist, int G, const uint32_t* __restrict__ allowed, int R,
+                                                                  int32_t* __restrict__ counts) {
+  __shared__ uint32_t aw[64];
+  __shared__ int wsum[4][64];
+  const int l = blockIdx.x, m = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t* off = offsets + (int64_t)m * (nlist + 1);
+  const int lb = off[l], size = off[l + 1] - lb;
+  const uint32_t* lw = list_words + (int64_t)m * n + lb;
+  for (int r0 = 0; r0 < R; r0 += 64) {                  // (uniform trip counts: R and size are the block's)
+    const int nr = min(64, R - r0);
+    __syncthreads();
+    if (tid < 64) aw[tid] = tid < nr ? allowed[r0 + tid] : 0u;
+    __syncthreads();
+    int cnt = 0;
+    for (int i0 = wave * 64; i0 < size; i0 += 256) {
+      const int i = i0 + lane;
+      const uint32_t w = i < size ? lw[i] : 0u;
+      for (int j = 0; j < nr; ++j) {
+        const int c = (int)__popcll(__ballot((w & aw[j]) != 0u));
+        if (lane == j) cnt += c;
+      }
+    }
+    wsum[wave][lane] = cnt;
+    __syncthreads();
+    if (tid < nr) counts[((int64_t)(r0 + tid) * G + m) * nlist + l] = wsum[0][tid] + wsum[1][tid] + wsum[2][tid] + wsum[3][tid];
   }
 }
 
@@ -940,6 +1032,15 @@ size_t ivf_search_workspace_bytes(const Shape& s, int B, int nlist, int nprobe, 
 int ivf_search(const Shape& s, const float* eq, int B, const float* cent, const void* vectors, const int32_t* positions, const int32_t* offsets,
                int64_t n, int nlist, int nprobe, int max_probes, int max_list, int k, void* ws, size_t ws_bytes, int64_t* out, int32_t* unfilled,
                hipStream_t st) {
+  return ivf_search_filtered(s, eq, B, cent, vectors, positions, offsets, n, nlist, nprobe, max_probes, max_list, k, ws, ws_bytes, out, unfilled, nullptr,
+                             nullptr, nullptr, 1, st);
+}
+
+// list_words == NULL: the plain search (the three launches of ivf_search, the kernels it always ran).  Else allowed holds one word per batch row
+// and counts (count_rows, G, nlist) the eligible entries per list: one row shared by the batch, or one per batch row.
+int ivf_search_filtered(const Shape& s, const float* eq, int B, const float* cent, const void* vectors, const int32_t* positions, const int32_t* offsets,
+                        int64_t n, int nlist, int nprobe, int max_probes, int max_list, int k, void* ws, size_t ws_bytes, int64_t* out, int32_t* unfilled,
+                        const uint32_t* list_words, const uint32_t* allowed, const int32_t* counts, int count_rows, hipStream_t st) {
   const int PQ = s.query_dot_product_groups, G = s.item_dot_product_groups, d = s.dot_product_dimension;
   if (ivf_search_workspace_bytes(s, B, nlist, nprobe, max_probes, max_list, k) > ws_bytes) { set_error("ivf_search: workspace too small"); return kErrNoMem; }
   const SearchGeo g = search_geo(B, PQ, G, nlist, nprobe, max_list);
@@ -958,9 +1059,21 @@ int ivf_search(const Shape& s, const float* eq, int B, const float* cent, const 
     int64_t* outs = out + (int64_t)b0 * PQ * G * k;
     by_d(d, [&](auto DC) {
       constexpr int D = decltype(DC)::value;
+      const dim3 grid((unsigned)g.n_seg, (unsigned)nlist, (unsigned)G);
+      if (list_words) {
+        const int32_t* cs = counts + (count_rows == 1 ? 0 : (int64_t)b0 * G * nlist);
+        hipLaunchKernelGGL(mol_ivf_coarse_filtered_kernel<D>, dim3((unsigned)rows), dim3(256), 0, st, eqs, G, cent, nlist, cs, count_rows, PQ, nprobe, k,
+                           max_probes, probes, nprob, b0 == 0 ? unfilled : nullptr);
+        if (k > 64)
+          hipLaunchKernelGGL((mol_ivf_scan_filtered_kernel<D, 2>), grid, dim3(256), 0, st, eqs, qrows, G, nlist, v16, positions, offsets, n, probes,
+                             max_probes, g.seg_items, g.n_seg, k, part_s, part_p, list_words, allowed + b0, PQ);
+        else
+          hipLaunchKernelGGL((mol_ivf_scan_filtered_kernel<D, 1>), grid, dim3(256), 0, st, eqs, qrows, G, nlist, v16, positions, offsets, n, probes,
+                             max_probes, g.seg_items, g.n_seg, k, part_s, part_p, list_words, allowed + b0, PQ);
+        return kOk;
+      }
       hipLaunchKernelGGL(mol_ivf_coarse_kernel<D>, dim3((unsigned)rows), dim3(256), 0, st, eqs, G, cent, nlist, offsets, nprobe, k, max_probes, probes, nprob,
                          b0 == 0 ? unfilled : nullptr);
-      const dim3 grid((unsigned)g.n_seg, (unsigned)nlist, (unsigned)G);
       if (k > 64)
         hipLaunchKernelGGL((mol_ivf_scan_kernel<D, 2>), grid, dim3(256), 0, st, eqs, qrows, G, nlist, v16, positions, offsets, n, probes, max_probes,
                            g.seg_items, g.n_seg, k, part_s, part_p);
@@ -999,6 +1112,38 @@ void ivf_plan(const int32_t* offsets, int G, int nlist, int nprobe, int k, int* 
   }
   *max_probes = std::min(mp, nlist);
   *max_list = ml;
+}
+
+int ivf_list_words(const int32_t* positions, int G, int64_t n, const uint32_t* eff, const uint32_t* visible, uint32_t* list_words, hipStream_t st) {
+  const int64_t total = (int64_t)G * n;
+  hipLaunchKernelGGL(mol_ivf_list_words_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, positions, total, n, eff, visible, list_words);
+  return launch_ok();
+}
+
+int ivf_list_counts(const uint32_t* list_words, const int32_t* offsets, int G, int64_t n, int nlist, const uint32_t* allowed, int R, int32_t* counts,
+                    hipStream_t st) {
+  hipLaunchKernelGGL(mol_ivf_list_counts_kernel, dim3((unsigned)nlist, (unsigned)G), dim3(256), 0, st, list_words, offsets, n, nlist, G, allowed, R, counts);
+  return launch_ok();
+}
+
+// host: ivf_plan's probe capacity over the eligible counts of every (row, group): the fewest lists whose counts reach k (every list where they
+// never do), at least nprobe
+int ivf_plan_filtered(const int32_t* counts, int R, int G, int nlist, int nprobe, int k) {
+  int mp = nprobe;
+  std::vector<int> sz(nlist);
+  for (int64_t rm = 0; rm < (int64_t)R * G && mp < nlist; ++rm) {
+    const int32_t* c = counts + rm * nlist;
+    std::copy(c, c + nlist, sz.begin());
+    std::sort(sz.begin(), sz.end());
+    int64_t held = 0;
+    int need = nlist;
+    for (int l = 0; l < nlist; ++l) {
+      held += sz[l];
+      if (held >= k) { need = l + 1; break; }
+    }
+    mp = std::max(mp, need);
+  }
+  return std::min(mp, nlist);
 }
 
 }  // namespace mol

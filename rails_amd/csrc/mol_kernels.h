@@ -208,6 +208,14 @@ int ivf_search(const Shape& s, const float* eq, int B, const float* cent, const 
                int64_t n, int nlist, int nprobe, int max_probes, int max_list, int k, void* ws, size_t ws_bytes, int64_t* out, int32_t* unfilled,
                hipStream_t st);
 void ivf_plan(const int32_t* offsets, int G, int nlist, int nprobe, int k, int* max_probes, int* max_list);
+// filtered lists: the filter in list order, the eligible entries per (row, group, list), the probe capacity they need, and the search over them
+int ivf_list_words(const int32_t* positions, int G, int64_t n, const uint32_t* eff, const uint32_t* visible, uint32_t* list_words, hipStream_t st);
+int ivf_list_counts(const uint32_t* list_words, const int32_t* offsets, int G, int64_t n, int nlist, const uint32_t* allowed, int R, int32_t* counts,
+                    hipStream_t st);
+int ivf_plan_filtered(const int32_t* counts, int R, int G, int nlist, int nprobe, int k);
+int ivf_search_filtered(const Shape& s, const float* eq, int B, const float* cent, const void* vectors, const int32_t* positions, const int32_t* offsets,
+                        int64_t n, int nlist, int nprobe, int max_probes, int max_list, int k, void* ws, size_t ws_bytes, int64_t* out, int32_t* unfilled,
+                        const uint32_t* list_words, const uint32_t* allowed, const int32_t* counts, int count_rows, hipStream_t st);
 
 int hash_item_table(unsigned long long seed, int64_t first_item, int64_t n_items, int dim, float scale, float* out, hipStream_t stream);
 int mips_pack_items(const float* items, int64_t n, int D, float* out, hipStream_t stream);

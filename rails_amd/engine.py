@@ -813,6 +813,20 @@ def ivf_edited_size(n_old: int, n_keep: int, positions=None, *, m: Optional[int]
     return lim - int(below) + int(m)
 
 
+class IvfFilterPlan:
+    """What IvfIndex keeps per filter while the lists and the filter stay what they are: the eligible entries per (row, group, list) on the device
+    (`counts`, (count_rows, P_X, nlist) int32 -- rails_ivf_list_counts), their ONE read-back (`counts_host`), the items each row keeps (`kept`,
+    host integers) and the probe capacity per (nprobe, k_per_group) (rails_ivf_plan_filtered).  `key` is the filter itself: the TagFilter, or the
+    visibility row of a hidden-only call."""
+
+    def __init__(self, key, allowed: torch.Tensor, counts: torch.Tensor):
+        self.key, self.allowed, self.counts = key, allowed, counts
+        self.count_rows = counts.shape[0]
+        self.counts_host = counts.cpu().contiguous()
+        self.kept = tuple(int(v) for v in self.counts_host[:, 0, :].sum(dim=1))       # (every group's lists hold every item once)
+        self.max_probes: Dict[Tuple[int, int], int] = {}
+
+
 class IvfIndex:
     """IVF-Flat index over the item components (include/rails_amd.h rails_ivf_*): one index per item group, trained by spherical Lloyd
     k-means on a seeded sample of the fp16-rounded components and searched in three launches -- the native counterpart of the FAISS
@@ -822,6 +836,8 @@ class IvfIndex:
 
     COMPONENT_CHUNK = 1 << 20     # items per temporary fp32-format index chunk where the engine's own index is in a split-f16 format
     EDIT_MAX = 16384              # inserted entries one rails_ivf_lists_edit call takes (one rails_sort_rows_i64 row); beyond: edit() rebuilds the lists
+    FILTER_WS_CAP = 256 << 20     # bytes of search workspace a filtered call stays under by slicing its batch (the part buffers grow with max_probes)
+    FILTER_PLANS_KEPT = 64        # filters whose counts and plans are kept (a per-row filter's counts hold B * P_X * nlist int32)
 
     def __init__(self, engine: MolEngine, index: MolIndex, nlist: int = 100, nprobe: int = 1, iters: int = 10, seed: int = 1234,
                  items: Optional[torch.Tensor] = None, centroids: Optional[torch.Tensor] = None):
@@ -875,6 +891,10 @@ class IvfIndex:
         self._plans: Dict[Tuple[int, int], Tuple[int, int]] = {}
         self._ws: Optional[torch.Tensor] = None
         self._unfilled = torch.zeros(1, dtype=torch.int32, device=dev)
+        # filtered lists: nothing is allocated until a search is given a filter
+        self._list_words: Optional[Tuple[torch.Tensor, torch.Tensor]] = None       # (the filter's source array, the words in list order)
+        self._filter_plans: Dict[int, IvfFilterPlan] = {}
+        self._all_ones: Optional[torch.Tensor] = None                               # the allow word of a hidden-only call, one per batch row
 
     def _source(self, items: Optional[torch.Tensor]):
         """What the components of the whole corpus are read from -> (fp32-format index buffer, None), or on a split-f16 engine (None, the
@@ -954,6 +974,8 @@ class IvfIndex:
         self.n_items = n_new
         self._offsets_host = self._offsets.cpu().contiguous()
         self._plans.clear()
+        self._list_words = None       # the words sit beside `positions`: other lists, other words, counts and plans
+        self._filter_plans.clear()
 
     # read-only views of the index (tests and tools)
     centroids = property(lambda self: self._centroids, doc="(P_X, nlist, d) fp32 unit-norm centroids")
@@ -976,11 +998,110 @@ class IvfIndex:
             p = self._plans[key] = (mp.value, ml.value)
         return p
 
+    # ---- filtered lists: the hidden set / allowed_tags inside the list scan ---------------------------------------------------------------
+    def list_words(self, filter) -> torch.Tensor:
+        """(P_X, N) int32: the filter in list order, beside `positions` (rails_ivf_list_words: one gather launch) -- the effective tag word of
+        every entry for a TagFilter, all ones / 0 for a visible / hidden entry for a visibility row.  Kept until the lists change (edit()) or
+        another source array comes: the module makes a new one whenever its hidden set or its tags change, and only then."""
+        src = filter.eff if isinstance(filter, TagFilter) else filter
+        c = self._list_words
+        if c is None or c[0] is not src:
+            dev, n = self._centroids.device, self.n_items
+            if isinstance(filter, TagFilter):
+                ok = filter.n_items == n and src.device == dev
+            else:
+                ok = (torch.is_tensor(src) and src.dtype == torch.int32 and src.numel() == item_mask_words(n) and src.is_contiguous() and src.device == dev)
+            if not ok:
+                raise ValueError(f"IvfIndex.search: filter must be a TagFilter over the {n} items on {dev}, or their int32 visibility row")
+            words = torch.empty((self.groups, n), dtype=torch.int32, device=dev)
+            tagged = isinstance(filter, TagFilter)
+            with _on_device(dev):
+                _lib.check(self.lib.rails_ivf_list_words(_ptr(self._positions), self.groups, n, _ptr(src) if tagged else None, None if tagged else _ptr(src),
+                                                         _ptr(words), _stream()), "rails_ivf_list_words")
+            c = self._list_words = (src, words)
+            self._filter_plans.clear()
+        return c[1]
+
+    def filter_plan(self, filter) -> IvfFilterPlan:
+        """The counts of `filter` over the lists as they are: one launch and ONE read-back the first time a filter is seen, nothing afterwards."""
+        words = self.list_words(filter)
+        p = self._filter_plans.get(id(filter))
+        if p is None or p.key is not filter:
+            dev = self._centroids.device
+            if isinstance(filter, TagFilter):
+                allowed = filter.allowed
+            else:
+                allowed = torch.full((1,), -1, dtype=torch.int32, device=dev)      # one word shared by the batch: one row of counts
+            counts = torch.empty((allowed.numel(), self.groups, self.nlist), dtype=torch.int32, device=dev)
+            with _on_device(dev):
+                _lib.check(self.lib.rails_ivf_list_counts(_ptr(words), _ptr(self._offsets), self.groups, self.n_items, self.nlist, _ptr(allowed),
+                                                          allowed.numel(), _ptr(counts), _stream()), "rails_ivf_list_counts")
+            if len(self._filter_plans) >= self.FILTER_PLANS_KEPT:
+                self._filter_plans.clear()
+            p = self._filter_plans[id(filter)] = IvfFilterPlan(filter, allowed, counts)
+        return p
+
+    def _filtered_max_probes(self, plan: IvfFilterPlan, nprobe: int, k: int) -> int:
+        mp = plan.max_probes.get((nprobe, k))
+        if mp is None:
+            out = C.c_int32(0)
+            _lib.check(self.lib.rails_ivf_plan_filtered(C.c_void_p(plan.counts_host.data_ptr()), plan.count_rows, self.groups, self.nlist, nprobe, k,
+                                                        C.byref(out)), "rails_ivf_plan_filtered")
+            mp = plan.max_probes[(nprobe, k)] = out.value
+        return mp
+
+    def _search_filtered(self, eq: torch.Tensor, k: int, nprobe: int, out: torch.Tensor, filter, check: bool) -> None:
+        """The refusals are the twin's own -- an index of the kept items alone -- before any search launch; the batch is cut so that the
+        workspace of one call stays under FILTER_WS_CAP."""
+        B, dev = eq.shape[0], self._centroids.device
+        plan = self.filter_plan(filter)
+        if plan.count_rows not in (1, B):
+            raise ValueError(f"IvfIndex.search: the filter has {plan.count_rows} allow words, the batch {B} rows")
+        kept = min(plan.kept)
+        if kept < self.nlist:
+            raise ValueError(f"IvfIndex: {kept} items cannot fill nlist = {self.nlist} lists")
+        if k > kept:
+            raise RuntimeError(f"selected index k out of range (k={k}, n={kept})")
+        if B == 0:
+            return
+        max_probes, max_list = self._filtered_max_probes(plan, nprobe, k), self._plan(nprobe, k)[1]
+        if isinstance(filter, TagFilter):
+            allowed = filter.allowed_for(B)
+        else:
+            if self._all_ones is None or self._all_ones.numel() < B:
+                self._all_ones = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            allowed = self._all_ones
+        step = B
+        while True:
+            ws_bytes = self.lib.rails_ivf_search_workspace_bytes(C.byref(self._shape), step, self.nlist, nprobe, max_probes, max_list, k)
+            if ws_bytes == 0:
+                raise NotImplementedError(f"rails_ivf_search_workspace_bytes: {_lib.last_error()}")
+            if ws_bytes <= self.FILTER_WS_CAP or step == 1:
+                break
+            step = (step + 1) // 2
+        if self._ws is None or self._ws.numel() < ws_bytes:
+            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        with _on_device(dev):
+            for b0 in range(0, B, step):
+                b1 = min(B, b0 + step)
+                counts = plan.counts if plan.count_rows == 1 else plan.counts[b0:b1]
+                _lib.check(self.lib.rails_ivf_search_filtered(C.byref(self._shape), _ptr(eq[b0:b1]), b1 - b0, _ptr(self._centroids), _ptr(self._vectors),
+                                                              _ptr(self._positions), _ptr(self._offsets), self.n_items, self.nlist, nprobe, max_probes,
+                                                              max_list, k, _ptr(self._ws), self._ws.numel(), _ptr(out[b0:b1]),
+                                                              _ptr(self._unfilled), _ptr(self.list_words(filter)), _ptr(allowed[b0:b1]),
+                                                              _ptr(counts), plan.count_rows if plan.count_rows == 1 else b1 - b0, _stream()),
+                           "rails_ivf_search_filtered")
+                if check and int(self._unfilled.item()) != 0:      # (every call zeroes the word: it is read per slice)
+                    raise RuntimeError("IvfIndex.search: some row found fewer than k_per_group items")
+
     def search(self, eq: torch.Tensor, k_per_group: int, nprobe: Optional[int] = None, out: Optional[torch.Tensor] = None,
-               check: bool = False) -> torch.Tensor:
+               check: bool = False, filter=None) -> torch.Tensor:
         """eq (B, P_Q, d) fp32 query components -> (B, P_Q * P_X * k_per_group) int64 item positions, row-major over (query group,
         item group, rank) as MoLNaiveTopK's exhaustive candidates.  check: wait for the call and raise if some row found fewer than
-        k_per_group items (which the probe plan rules out)."""
+        k_per_group items (which the probe plan rules out).
+        filter: a TagFilter (row b returns only items x with eff[x] & words[b] != 0), or the module's (1, words) int32 visibility row (no row
+        returns a hidden item).  Row b then equals, position for position through the kept rows, the plain search of an index built with these
+        centroids from the items row b keeps.  ValueError where a row keeps fewer than nlist items, RuntimeError where fewer than k_per_group."""
         nprobe = self._nprobe if nprobe is None else int(nprobe)
         self._check_nprobe(nprobe)
         k = int(k_per_group)
@@ -995,17 +1116,22 @@ class IvfIndex:
         if eq.device != dev:
             raise ValueError(f"IvfIndex.search: eq is on {eq.device}, the index on {dev}")
         eq = _f32c(eq)
+        shape_out = (B, self.query_groups * self.groups * k)
+        if out is not None and (tuple(out.shape) != shape_out or out.dtype != torch.int64 or not out.is_contiguous() or out.device != dev):
+            raise ValueError(f"IvfIndex.search: out must be a contiguous int64 {shape_out} tensor on {dev}")
+        if filter is not None:
+            if out is None:
+                out = torch.empty(shape_out, dtype=torch.int64, device=dev)
+            self._search_filtered(eq, k, nprobe, out, filter, check)
+            return out
         max_probes, max_list = self._plan(nprobe, k)
         ws_bytes = self.lib.rails_ivf_search_workspace_bytes(C.byref(self._shape), max(B, 1), self.nlist, nprobe, max_probes, max_list, k)
         if ws_bytes == 0:
             raise NotImplementedError(f"rails_ivf_search_workspace_bytes: {_lib.last_error()}")
         if self._ws is None or self._ws.numel() < ws_bytes:
             self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        shape_out = (B, self.query_groups * self.groups * k)
         if out is None:
             out = torch.empty(shape_out, dtype=torch.int64, device=dev)
-        elif tuple(out.shape) != shape_out or out.dtype != torch.int64 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"IvfIndex.search: out must be a contiguous int64 {shape_out} tensor on {dev}")
         with _on_device(dev):
             _lib.check(self.lib.rails_ivf_search(C.byref(self._shape), _ptr(eq), B, _ptr(self._centroids), _ptr(self._vectors), _ptr(self._positions),
                                                  _ptr(self._offsets), self.n_items, self.nlist, nprobe, max_probes, max_list, k, _ptr(self._ws),

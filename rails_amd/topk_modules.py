@@ -2677,11 +2677,17 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
     remove_items and the by-id calls edit the lists under the centroids the index has, which are never written again -- as FAISS's
     IndexIVFFlat.add / remove_ids.  The contract is NOT "equals a freshly constructed module" (a fresh module trains new centroids): after any
     sequence of calls the lists are bit for bit what rails_ivf_build_lists writes from the resulting table with THOSE centroids.  Recall may
-    drift as the corpus moves away from them: watch ivf_index().list_sizes(), and construct the module again to retrain."""
+    drift as the corpus moves away from them: watch ivf_index().list_sizes(), and construct the module again to retrain.
+    filtered_lists=True (use_faiss=True only; independent of frozen_centroids) opts in to the hidden set and the item tags (DESIGN sections
+    3.14 and 3.15) INSIDE the list scan: hide_items / unhide_items and their by-id forms, hidden_positions, set_item_tags and allowed_tags= on
+    forward, get_top_k_outputs and all_logits; compact() is a removal and needs frozen_centroids=True as well.  Row b of a call equals row b of
+    the same call on MoLNaiveTopK(mol, X[keep_b], ids[keep_b], k_per_group, use_faiss=True, ivf_centroids=<these centroids>, ...), keep_b the
+    items row b may return; a row that keeps fewer than nlist items is that module's ValueError, fewer than k_per_group its RuntimeError.
+    The index keeps one more int32 per list entry (P_X * 4 bytes per item) from the first filtered call on.  item_mask= stays refused."""
 
     def __init__(self, mol_module: MoLSimilarity, item_embeddings: torch.Tensor, item_ids: torch.Tensor, k_per_group: int, use_faiss: bool = False,
                  *, nlist: int = 100, nprobe: int = 1, iters: int = 10, seed: int = 1234, frozen_centroids: bool = False,
-                 ivf_centroids: Optional[torch.Tensor] = None) -> None:
+                 ivf_centroids: Optional[torch.Tensor] = None, filtered_lists: bool = False) -> None:
         _refuse_generic_route(mol_module, type(self).__name__)
         super().__init__(mol_module=mol_module, item_embeddings=item_embeddings, item_ids=item_ids)
         self._k_per_group: int = k_per_group
@@ -2689,6 +2695,9 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
         self._frozen_centroids: bool = bool(frozen_centroids)
         if self._frozen_centroids and not self._use_faiss:
             raise ValueError("MoLNaiveTopK: frozen_centroids=True applies to the IVF index of use_faiss=True only")
+        self._filtered_lists: bool = bool(filtered_lists)
+        if self._filtered_lists and not self._use_faiss:
+            raise ValueError("MoLNaiveTopK: filtered_lists=True applies to the IVF index of use_faiss=True only")
         self._ivf_args = dict(nlist=int(nlist), nprobe=int(nprobe), iters=int(iters), seed=int(seed))
         self.nprobe: int = int(nprobe)      # lists searched per query component; may be changed between calls (the index stays)
         self._ivf: Optional[E.IvfIndex] = None
@@ -2721,7 +2730,7 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
             raise ValueError(f"MoLNaiveTopK: {n_left} items cannot fill nlist = {self._ivf_args['nlist']} lists")
 
     def _check_hideable(self, what: str) -> None:
-        if self._use_faiss:
+        if self._use_faiss and not getattr(self, "_filtered_lists", False):
             raise NotImplementedError(f"MoLNaiveTopK.{what}: the IVF index (use_faiss=True{', frozen_centroids=True' if self._frozen_centroids else ''}) searches "
                                       "its lists without a visibility test -- a hidden set is not built for it; remove_items (under frozen_centroids=True) "
                                       "deletes for good, and the exhaustive MoLNaiveTopK takes hide_items")
@@ -2750,12 +2759,14 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
 
     def _candidates(self, eq: torch.Tensor, pending: list, tags: Optional[E.TagFilter] = None) -> torch.Tensor:
         if self._use_faiss:       # exact by construction over the probed lists: nothing to verify, nothing added to `pending`
-            return self.ivf_index().search(eq, self._k_per_group, nprobe=self.nprobe)
+            # filtered_lists: the call's tag filter, else the hidden set, goes INTO the list scan (a module without the flag holds neither)
+            filt = (tags if tags is not None else self._visible) if self._filtered_lists else None
+            return self.ivf_index().search(eq, self._k_per_group, nprobe=self.nprobe, filter=filt)
         # (tags travel as a keyword only when there are any: tests/test_gpu_parity.py swaps _component_topk for a stand-in of the (eq, k, pending) form)
         return self._component_topk(eq, self._k_per_group, pending, **({} if tags is None else {"tags": tags}))
 
     def _check_taggable(self, what: str) -> None:
-        if self._use_faiss:
+        if self._use_faiss and not getattr(self, "_filtered_lists", False):
             raise NotImplementedError(f"MoLNaiveTopK takes no {what}: the IVF index (use_faiss=True{', frozen_centroids=True' if self._frozen_centroids else ''}) "
                                       "searches its lists without a tag test -- a tag filter is not built for it; the exhaustive MoLNaiveTopK takes it")
 

@@ -4,6 +4,10 @@ algorithms_bench.py timing protocol (3 warm-ups + 20 timed get_top_k_outputs cal
 index build time, list-size imbalance, ms per call for B in {1, 8, 32} x nprobe in {1, 4, 16} next to MoLNaiveTopK5 at the same B,
 and overlap@10 / @120 with MoLNaiveTopK5 and MoLBruteForceTopK.  Prints one JSON document.
   python tools/ivf_bench.py [--batches 1,8,32] [--nprobes 1,4,16]
+--filtered: the filtered-lists leg instead (MoLNaiveTopK(use_faiss=True, filtered_lists=True)): B in {1, 8, 32} x
+nprobe in {1, 4}, the same protocol, ms per call with nothing hidden and no tags (the plain search of the same module, in the same run),
+with a random 10 % / 50 % of the corpus hidden, and with per-row allowed_tags keeping 10 % / 1 % (ten distinct words cycled over the
+rows).  Writes profiles/ivf_filtered.json.
 """
 import argparse
 import gc, json, os, sys, time
@@ -16,6 +20,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batches", default="1,8,32")
 ap.add_argument("--nprobes", default="1,4,16")
 ap.add_argument("--nlist", type=int, default=100)
+ap.add_argument("--filtered", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg_key, N, width = bench.WORKLOADS["amzn-books"]
@@ -34,15 +39,16 @@ model = type("M", (), {"_ndp_module": mol})()
 cand = rails_amd.CandidateIndex(ids=ids, embeddings=X)
 
 
-def timed(tk, q, inv):
+def timed(tk, q, inv, aux=None):
+    aux = aux or {}
     for _ in range(3):
-        out_ids, _, _ = cand.get_top_k_outputs(q, k, {}, tk, inv, truncate_k_prime_to=kp)
+        out_ids, _, _ = cand.get_top_k_outputs(q, k, aux, tk, inv, truncate_k_prime_to=kp)
     torch.cuda.synchronize()
     gc.collect()
     ts = []
     for _ in range(20):
         t0 = time.perf_counter()
-        out_ids, _, _ = cand.get_top_k_outputs(q, k, {}, tk, inv, truncate_k_prime_to=kp)
+        out_ids, _, _ = cand.get_top_k_outputs(q, k, aux, tk, inv, truncate_k_prime_to=kp)
         torch.cuda.synchronize()
         ts.append((time.perf_counter() - t0) * 1e3)
     return out_ids.cpu(), {"ms_avg": sum(ts) / len(ts), "ms_min": min(ts), "ms_median": sorted(ts)[len(ts) // 2]}
@@ -52,7 +58,47 @@ def overlap(x, y, kk):
     return sum(len(set(r.tolist()) & set(s.tolist())) for r, s in zip(x[:, :kk], y[:, :kk])) / (x.shape[0] * kk)
 
 
+def filtered_leg():
+    """Every cell beside the same module's unfiltered call of the same (B, nprobe), timed in the same run."""
+    doc = {"workload": f"amzn-books {cfg.query_dot_product_groups}x{cfg.item_dot_product_groups}x{cfg.dot_product_dimension}, N={N}, k={k}, k'={kp}, "
+                       f"k_per_group={kg}, nlist={a.nlist}, MoLNaiveTopK(use_faiss=True, filtered_lists=True)",
+           "protocol": "3 warm-ups + 20 timed get_top_k_outputs calls, wall clock with device sync (tools/algorithms_bench.py)",
+           "tags": "bits 0-9 each on a random 10 % of the items, bits 10-19 each on a random 1 %; row b of a batch allows bit (b % 10) of the fraction's ten",
+           "rows": []}
+    gen = torch.Generator().manual_seed(7)
+    tags = torch.zeros(N, dtype=torch.int64)
+    for bit in range(20):
+        tags[torch.randperm(N, generator=gen)[: N // (10 if bit < 10 else 100)]] |= 1 << bit
+    order = torch.randperm(N, generator=gen)
+    with torch.inference_mode():
+        tk = rails_amd.MoLNaiveTopK(mol, X, ids, k_per_group=kg, use_faiss=True, nlist=a.nlist, filtered_lists=True)
+        tk.ivf_index()
+        tk.set_item_tags(tags.to(dev))
+        for B in (1, 8, 32):
+            q = O.synthetic_queries(cfg, B).to(dev)
+            inv = torch.zeros((B, width), dtype=torch.int64, device=dev)
+            for p in (1, 4):
+                tk.nprobe = p
+                row = {"B": B, "nprobe": p, "unfiltered": timed(tk, q, inv)[1]}
+                for share in (10, 50):
+                    hide = order[: N * share // 100]
+                    tk.hide_items(hide)
+                    row[f"hidden_{share}pct"] = timed(tk, q, inv)[1]
+                    tk.unhide_items(hide)
+                for share, first in ((10, 0), (1, 10)):
+                    words = [1 << (first + b % 10) for b in range(B)]
+                    row[f"tags_per_row_{share}pct"] = timed(tk, q, inv, {"allowed_tags": words})[1]
+                doc["rows"].append(row)
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ivf_filtered.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+    print(json.dumps(doc, indent=1))
+
+
 gc.disable()
+if a.filtered:
+    filtered_leg()
+    sys.exit(0)
 out = {"workload": f"amzn-books {cfg.query_dot_product_groups}x{cfg.item_dot_product_groups}x{cfg.dot_product_dimension}, N={N}, k={k}, k'={kp}, "
                    f"k_per_group={kg}, nlist={a.nlist}",
        "protocol": "3 warm-ups + 20 timed get_top_k_outputs calls, wall clock with device sync (tools/algorithms_bench.py)",
