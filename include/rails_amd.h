@@ -49,7 +49,7 @@ extern "C" {
  * rails_scores_mask, the hidden-item entries rails_item_mask_clear / rails_mol_coarse_topk_visible / rails_mol_component_topk_visible and the
  * item-tag entries rails_item_tags_effective / rails_item_tags_count / rails_item_mask_from_tags / rails_scores_mask_tags / rails_mol_coarse_topk_tagged /
  * rails_mol_component_topk_tagged / rails_mol_scan_plan and the filtered-list entries rails_ivf_list_words / rails_ivf_list_counts /
- * rails_ivf_plan_filtered / rails_ivf_search_filtered
+ * rails_ivf_plan_filtered / rails_ivf_search_filtered and the group-collapse entries rails_topk_collapse / rails_scores_group_max / rails_topk_keys
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -637,6 +637,32 @@ size_t rails_rerank_workspace_bytes(int32_t rows, int32_t n_cand);
 int rails_rerank_topk_filtered(const float* scores, int64_t ld, int32_t rows, int32_t n_cand, int32_t k_prime, const int64_t* positions,
                                const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, void* workspace, size_t workspace_bytes,
                                int64_t* out_ids, float* out_scores, int32_t* out_of_range, void* stream);
+
+/* ---- collapsing by item group (added under ABI 15; no counterpart in the reference) ------------------------------
+ * At most one result per item group.  Every entry point takes DENSE group ranks: group_ranks[x] is an int32 in [0, n_groups) for each of the
+ * n_items positions, equal for the items of one group, and an ungrouped item has a rank of its own (n_groups <= n_items).  ids: the id table
+ * by position, NULL = a position is its own id.  invalid_ids: (rows, width) seen ids per row, unread when width == 0. */
+/* The walk.  Row b holds a ranked list of `depth` entries (scores[b * ld + j], positions[b * depth + j]) that the caller guarantees to be in
+ * key order (score descending, position ascending).  An entry is eligible iff its position lies in [0, n_items), its score is above -inf
+ * and its id is not among the row's invalid_ids; the outputs are the first k eligible entries whose rank no earlier eligible entry of the
+ * list has -- scores as given, positions, ids -- with (-inf, -1, -1) behind them where the list holds fewer than k.  out_counts[b]: how
+ * many such entries the WHOLE list holds; *out_of_range (int32, device-visible, zeroed by the caller; may be pinned host memory) is set to 1
+ * when some row holds fewer than k, and is usable as a run_if predicate.  One workgroup per row, one launch; 1 <= depth <= 16 384. */
+int rails_topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const int32_t* group_ranks,
+                        int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, float* out_scores,
+                        int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, void* stream);
+/* The per-group maxima of a score matrix: for every FINITE scores[b * ld + x], x < n, whose id is not among row b's invalid_ids,
+ * table[b * n_groups + group_ranks[first_item + x]] = max(itself, key) with key = (orderable(score) << 32) | ~(first_item + x), the selection
+ * key of rails_topk: afterwards a slot holds the key of its group's best eligible item under (score desc, position asc), 0 where the group
+ * has none.  -inf entries (what rails_scores_mask* write) are skipped.  clear_table != 0: the (rows, n_groups) table is zeroed first, so a
+ * chunked caller passes 1 with its first chunk and 0 after.  first_item + n < 2^32, width <= 4096, rows <= 65 535. */
+int rails_scores_group_max(const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const int32_t* group_ranks, int64_t n_groups,
+                           uint64_t* table, int32_t clear_table, const int64_t* ids, const int64_t* invalid_ids, int32_t width, void* stream);
+/* The k largest keys of every row of such a table, descending, decoded: out_scores / out_positions / out_ids (rows, k), (-inf, -1, -1) where a
+ * row has fewer than k non-zero keys; out_counts[b]: the row's non-zero keys.  The keys of a row are distinct, so there are no ties.  An MSD
+ * radix selection over rows of any length, one workgroup per row; k <= 512. */
+int rails_topk_keys(const uint64_t* table, int32_t rows, int64_t n_groups, int32_t k, const int64_t* ids, float* out_scores, int64_t* out_positions,
+                    int64_t* out_ids, int32_t* out_counts, void* stream);
 
 /* CandidateIndex.get_top_k_outputs' selection in ONE chain (reference indexing/candidate_index.py:149-175 after
  * rails/indexing/mol_top_k.py:123-130): exact top-k' of every row with the id map, then the seen-id filter of

@@ -1082,6 +1082,45 @@ int rails_rerank_topk_filtered(const float* scores, int64_t ld, int32_t rows, in
   return r == kOk ? r : fail(r, "rerank_topk_filtered");
 }
 
+int rails_topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const int32_t* group_ranks,
+                        int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, float* out_scores,
+                        int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || depth < 0 || k < 0 || width < 0 || n_items < 0) { set_error("topk_collapse: negative size"); return RAILS_EINVAL; }
+  if (rows == 0 || k == 0) return RAILS_OK;
+  if (!scores || !positions || !group_ranks || !out_scores || !out_positions || !out_ids || !out_counts || !out_of_range || (width > 0 && !invalid_ids)) {
+    set_error("topk_collapse: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  if (ld < depth) { set_error("topk_collapse: ld < depth"); return RAILS_EINVAL; }
+  const int r = topk_collapse(scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k, out_scores, out_positions, out_ids,
+                              out_counts, out_of_range, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "topk_collapse");
+}
+
+int rails_scores_group_max(const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const int32_t* group_ranks, int64_t n_groups,
+                           uint64_t* table, int32_t clear_table, const int64_t* ids, const int64_t* invalid_ids, int32_t width, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || n < 0 || first_item < 0 || n_groups < 0 || width < 0) { set_error("scores_group_max: negative size"); return RAILS_EINVAL; }
+  if (rows == 0 || n_groups == 0) return RAILS_OK;
+  if (!table || (n > 0 && (!scores || !group_ranks)) || (width > 0 && !invalid_ids)) { set_error("scores_group_max: NULL pointer"); return RAILS_EINVAL; }
+  if (ld < n) { set_error("scores_group_max: ld < n"); return RAILS_EINVAL; }
+  const int r = scores_group_max(scores, ld, rows, n, first_item, group_ranks, n_groups, reinterpret_cast<unsigned long long*>(table), clear_table, ids,
+                                 invalid_ids, width, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "scores_group_max");
+}
+
+int rails_topk_keys(const uint64_t* table, int32_t rows, int64_t n_groups, int32_t k, const int64_t* ids, float* out_scores, int64_t* out_positions,
+                    int64_t* out_ids, int32_t* out_counts, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || n_groups < 0 || k < 0) { set_error("topk_keys: negative size"); return RAILS_EINVAL; }
+  if (rows == 0 || k == 0) return RAILS_OK;
+  if (!table || !out_scores || !out_positions || !out_ids || !out_counts) { set_error("topk_keys: NULL pointer"); return RAILS_EINVAL; }
+  const int r = topk_keys(reinterpret_cast<const unsigned long long*>(table), rows, n_groups, k, ids, out_scores, out_positions, out_ids, out_counts,
+                          (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "topk_keys");
+}
+
 int rails_topk_filter_fusable(int64_t n, int32_t k_prime, int32_t width, int32_t k) { return topk_can_fuse_filter(n, k_prime, width, k) ? 1 : 0; }
 
 int rails_topk_filtered(const float* scores, int64_t ld, int32_t rows, int64_t n, int32_t k_prime, const int64_t* ids, int64_t ids_row_stride,

@@ -1,0 +1,270 @@
+// Collapsing a ranked list by item group: at most one result per group.  Three kernels:
+//   collapse_walk_kernel   one workgroup per row over a ranked list of D (score, position) entries in key order: the first k entries whose
+//                          group has not occurred earlier in the list, the seen-id filter inside (rails_topk_collapse)
+//   group_max_kernel       streams a (rows, n) score matrix: table[row][rank] = max over the group's eligible items of the topk_keys.h key
+//                          (rails_scores_group_max) -- the exact fallback where one group owns the head of the ranking
+//   topk_keys_kernel       the k largest keys of every row of that table, by MSD radix selection, decoded (rails_topk_keys)
+// The kernels see DENSE group ranks (int32 in [0, G), every ungrouped item a rank of its own), never the callers' sparse keys.
+#include "mol_kernels.h"
+#include "topk_keys.h"
+
+namespace mol {
+
+constexpr int kCollapseThreads = kSortThreads;       // 1024: the in-LDS sorts' workgroup
+constexpr int kCollapseMaxDepth = 16384;             // entries of one ranked list: what lds_sort_desc sorts
+constexpr int kSeenTile = 256;                       // seen ids held in LDS at a time
+
+// block-wide exclusive scan of one int per thread (shuffle scan inside each wave, the wave totals through LDS); `total`: the sum.
+// All threads call; two barriers.
+template <int NT>
+__device__ __forceinline__ int collapse_exclusive_scan(int v, int* totals, int& total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+  if (lane == 63) totals[wv] = inc;
+  __syncthreads();
+  int base = 0;
+  total = 0;
+#pragma unroll
+  for (int t = 0; t < NT / 64; ++t) { const int tv = totals[t]; if (t < wv) base += tv; total += tv; }
+  __syncthreads();
+  return base + inc - v;
+}
+
+// ---- the walk ----------------------------------------------------------------------------------------------------
+// Entry j of a row is ELIGIBLE iff its position is one of the corpus, its score is above -inf (what the masks write) and its id is not in
+// the row's seen set.  An eligible entry SURVIVES iff no eligible entry before it has its group rank.  "First occurrence" is found by a sort,
+// not a hash table: the key (rank + 1, ~j) of every eligible entry (0: not eligible, the padding of topk_keys.h) is sorted descending in LDS,
+// which puts the entries of one rank side by side with the smallest j first -- the head of every run survives.  A prefix scan over the
+// survivor flags in list order compacts the first k.  Deterministic, order-preserving, no probe loops.
+// LDS: sort_slots keys | depth survivor bytes (dynamic), one tile of seen ids and the scan's wave totals (static).
+__global__ __launch_bounds__(kCollapseThreads) void collapse_walk_kernel(
+    const float* __restrict__ scores, int64_t ld, const int64_t* __restrict__ positions, int depth, int npad, int sort_slots,
+    const int32_t* __restrict__ ranks, int64_t n_items, const int64_t* __restrict__ ids, const int64_t* __restrict__ invalid, int width, int k,
+    float* __restrict__ out_scores, int64_t* __restrict__ out_pos, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_counts,
+    int32_t* __restrict__ out_of_range) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+  unsigned char* surv = reinterpret_cast<unsigned char*>(keys + sort_slots);      // [depth]
+  __shared__ int64_t seen[kSeenTile];
+  __shared__ int wave_tot[kCollapseThreads / 64];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* srow = scores + (int64_t)row * ld;
+  const int64_t* prow = positions + (int64_t)row * depth;
+
+  for (int j = tid; j < depth; j += kCollapseThreads) {
+    const int64_t p = prow[j];
+    surv[j] = (p >= 0 && p < n_items && srow[j] > -INFINITY) ? 1 : 0;
+  }
+  for (int w0 = 0; w0 < width; w0 += kSeenTile) {       // the seen-id filter, a tile of the row's seen ids at a time
+    const int wn = width - w0 < kSeenTile ? width - w0 : kSeenTile;
+    __syncthreads();
+    if (tid < wn) seen[tid] = invalid[(int64_t)row * width + w0 + tid];
+    __syncthreads();
+    for (int j = tid; j < depth; j += kCollapseThreads) {
+      if (!surv[j]) continue;
+      const int64_t p = prow[j];
+      const int64_t id = ids != nullptr ? ids[p] : p;
+      bool hit = false;
+      for (int w = 0; w < wn; ++w) hit |= (seen[w] == id);
+      if (hit) surv[j] = 0;
+    }
+  }
+  __syncthreads();
+  for (int j = tid; j < npad; j += kCollapseThreads) {
+    unsigned long long kv = 0ull;
+    if (j < depth && surv[j]) kv = ((unsigned long long)((unsigned int)ranks[prow[j]] + 1u) << 32) | (unsigned int)(~(unsigned int)j);
+    keys[j] = kv;
+  }
+  __syncthreads();
+  for (int j = tid; j < depth; j += kCollapseThreads) surv[j] = 0;
+  lds_sort_desc(keys, npad);                            // (ends with a barrier)
+  for (int i = tid; i < npad; i += kCollapseThreads) {
+    const unsigned long long kv = keys[i];
+    if (kv != 0ull && (i == 0 || (keys[i - 1] >> 32) != (kv >> 32))) surv[~(unsigned int)(kv & 0xFFFFFFFFull)] = 1;
+  }
+  __syncthreads();
+  // the first k survivors in list order: a contiguous segment of the list per thread
+  const int seg = (depth + kCollapseThreads - 1) / kCollapseThreads;
+  const int s0 = tid * seg < depth ? tid * seg : depth, s1 = s0 + seg < depth ? s0 + seg : depth;
+  int c = 0;
+  for (int j = s0; j < s1; ++j) c += surv[j];
+  int total;
+  int o = collapse_exclusive_scan<kCollapseThreads>(c, wave_tot, total);
+  for (int j = s0; j < s1 && o < k; ++j) {
+    if (!surv[j]) continue;
+    const int64_t p = prow[j];
+    out_scores[(int64_t)row * k + o] = srow[j];
+    out_pos[(int64_t)row * k + o] = p;
+    out_ids[(int64_t)row * k + o] = ids != nullptr ? ids[p] : p;
+    ++o;
+  }
+  for (int e = total + tid; e < k; e += kCollapseThreads) {      // a short row: the rest is empty
+    out_scores[(int64_t)row * k + e] = -INFINITY;
+    out_pos[(int64_t)row * k + e] = -1;
+    out_ids[(int64_t)row * k + e] = -1;
+  }
+  if (tid == 0) {
+    out_counts[row] = total;
+    if (total < k) *out_of_range = 1;                   // every writer stores the same value
+  }
+}
+
+int topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int rows, int depth, const int32_t* ranks, int64_t n_items,
+                  const int64_t* ids, const int64_t* invalid, int width, int k, float* out_scores, int64_t* out_pos, int64_t* out_ids,
+                  int32_t* out_counts, int32_t* out_of_range, hipStream_t stream) {
+  if (rows <= 0 || k <= 0) return kOk;
+  if (depth < 1 || depth > kCollapseMaxDepth) {
+    set_error("topk_collapse: depth = %d outside [1, %d]", depth, kCollapseMaxDepth);
+    return kErrUnsupported;
+  }
+  const int npad = next_pow2(depth, kSortThreads);
+  const int sort_slots = npad <= kSortThreads ? 3 * npad : npad;      // lds_sort_desc's exchange buffer
+  const int lds = sort_slots * (int)sizeof(unsigned long long) + (depth + 15) / 16 * 16;
+  static DynLdsOnce once;
+  if (ensure_dyn_lds(once, reinterpret_cast<const void*>(&collapse_walk_kernel), kCollapseMaxDepth * ((int)sizeof(unsigned long long) + 1)) != kOk)
+    return kErrLaunch;
+  hipLaunchKernelGGL(collapse_walk_kernel, dim3(rows), dim3(kCollapseThreads), lds, stream, scores, ld, positions, depth, npad, sort_slots, ranks,
+                     n_items, ids, invalid, width, k, out_scores, out_pos, out_ids, out_counts, out_of_range);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+// ---- the exact fallback: per-group maxima of a score matrix ---------------------------------------------------------------------------
+// table[row][rank[first_item + x]] = max(., make_key(score, first_item + x)) for every FINITE entry x < n of the row whose id is not in the
+// row's seen set: afterwards a group's slot holds the key of its best eligible item under (score desc, position asc), 0 where it has none.
+// A slot only grows, so an entry whose key does not beat a plain read of its slot is dropped before its id is looked up -- after the first
+// few items of a group, most are.  One workgroup per (chunk of kGroupMaxChunk columns, row); the row's seen ids sit in LDS.
+constexpr int kGroupMaxThreads = 256;
+constexpr int kGroupMaxChunk = 4096;
+constexpr int kGroupMaxSeen = 4096;      // seen ids per row
+
+__global__ __launch_bounds__(kGroupMaxThreads) void group_max_kernel(const float* __restrict__ scores, int64_t ld, int64_t n, int64_t first_item,
+                                                                    const int32_t* __restrict__ ranks, int64_t n_groups,
+                                                                    unsigned long long* __restrict__ table, const int64_t* __restrict__ ids,
+                                                                    const int64_t* __restrict__ invalid, int width) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long gm_seen[];      // [width]
+  const int row = blockIdx.y, tid = threadIdx.x;
+  for (int w = tid; w < width; w += kGroupMaxThreads) gm_seen[w] = (unsigned long long)invalid[(int64_t)row * width + w];
+  __syncthreads();
+  const int64_t begin = (int64_t)blockIdx.x * kGroupMaxChunk;
+  const int64_t end = begin + kGroupMaxChunk < n ? begin + kGroupMaxChunk : n;
+  const float* srow = scores + (int64_t)row * ld;
+  unsigned long long* trow = table + (int64_t)row * n_groups;
+  for (int64_t x = begin + tid; x < end; x += kGroupMaxThreads) {
+    const float s = srow[x];
+    if (!(fabsf(s) < INFINITY)) continue;               // -inf (masked), +inf, NaN
+    const int64_t p = first_item + x;
+    const int32_t r = ranks[p];
+    if (r < 0 || r >= n_groups) continue;
+    const unsigned long long kv = make_key(s, (unsigned int)p);
+    if (kv <= __atomic_load_n(&trow[r], __ATOMIC_RELAXED)) continue;
+    if (width > 0) {
+      const unsigned long long id = (unsigned long long)(ids != nullptr ? ids[p] : p);
+      bool hit = false;
+      for (int w = 0; w < width; ++w) hit |= (gm_seen[w] == id);
+      if (hit) continue;
+    }
+    atomicMax(&trow[r], kv);
+  }
+}
+
+int scores_group_max(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,
+                     unsigned long long* table, int clear_table, const int64_t* ids, const int64_t* invalid, int width, hipStream_t stream) {
+  if (rows <= 0 || n_groups <= 0) return kOk;
+  if (width > kGroupMaxSeen) { set_error("scores_group_max: width = %d beyond %d seen ids per row", width, kGroupMaxSeen); return kErrUnsupported; }
+  if (first_item + n > 0xFFFFFFFFll) { set_error("scores_group_max: positions beyond 32 bits"); return kErrUnsupported; }
+  if (rows > 65535) { set_error("scores_group_max: more than 65 535 rows"); return kErrUnsupported; }
+  if (clear_table && hipMemsetAsync(table, 0, sizeof(unsigned long long) * (size_t)rows * (size_t)n_groups, stream) != hipSuccess) return kErrLaunch;
+  if (n <= 0) return kOk;
+  const unsigned int blocks = (unsigned int)((n + kGroupMaxChunk - 1) / kGroupMaxChunk);
+  hipLaunchKernelGGL(group_max_kernel, dim3(blocks, rows), dim3(kGroupMaxThreads), sizeof(unsigned long long) * (size_t)width, stream, scores, ld, n,
+                     first_item, ranks, n_groups, table, ids, invalid, width);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+// ---- top-k of a key table -------------------------------------------------------------------------------------------
+// One workgroup per row.  The keys of a row are distinct (a key holds its position), zeros aside, so "the kk largest" (kk = min(k, non-zero
+// keys)) is the set of keys >= the kk-th largest, found by MSD radix selection -- eight passes of one byte, a 256-bin LDS histogram of the keys
+// that match the prefix so far (sublist_select_kernel's scheme over a row of any length) -- and collected in a ninth pass, sorted in LDS
+// (lds_sort_desc) and decoded with the codec of topk_keys.h.
+constexpr int kKeysThreads = kSortThreads;
+constexpr int kKeysMaxK = 512;
+
+__global__ __launch_bounds__(kKeysThreads) void topk_keys_kernel(const unsigned long long* __restrict__ table, int64_t n_groups, int k,
+                                                                const int64_t* __restrict__ ids, float* __restrict__ out_scores,
+                                                                int64_t* __restrict__ out_pos, int64_t* __restrict__ out_ids,
+                                                                int32_t* __restrict__ out_counts) {
+  __shared__ __attribute__((aligned(16))) unsigned long long sel[3 * kKeysThreads];      // the winners + lds_sort_desc's exchange buffer
+  __shared__ unsigned int hist[256];
+  __shared__ unsigned int nonzero, taken;
+  __shared__ unsigned long long s_prefix;
+  __shared__ unsigned int s_remaining;
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const unsigned long long* trow = table + (int64_t)row * n_groups;
+  if (tid == 0) { nonzero = 0u; taken = 0u; s_prefix = 0ull; }
+  __syncthreads();
+  unsigned int nz = 0u;
+  for (int64_t g = tid; g < n_groups; g += kKeysThreads) nz += trow[g] != 0ull ? 1u : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nz += (unsigned int)__shfl_xor((int)nz, o, 64);
+  if ((tid & 63) == 0 && nz) atomicAdd(&nonzero, nz);
+  __syncthreads();
+  const unsigned int kk = nonzero < (unsigned int)k ? nonzero : (unsigned int)k;
+  if (tid == 0) s_remaining = kk;
+  for (int i = tid; i < kKeysThreads; i += kKeysThreads) sel[i] = 0ull;
+  __syncthreads();
+  if (kk > 0u) {
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      if (tid < 256) hist[tid] = 0u;
+      __syncthreads();
+      const unsigned long long prefix = s_prefix;
+      const unsigned long long hi_mask = shift == 56 ? 0ull : ~0ull << (shift + 8);
+      for (int64_t g = tid; g < n_groups; g += kKeysThreads) {
+        const unsigned long long kv = trow[g];
+        if (kv != 0ull && (kv & hi_mask) == prefix) atomicAdd(&hist[(unsigned int)(kv >> shift) & 255u], 1u);
+      }
+      __syncthreads();
+      if (tid == 0) {                                   // the byte whose bin holds the remaining-th largest matching key
+        unsigned int rem = s_remaining, above = 0u;
+        int d = 255;
+        for (; d > 0; --d) {
+          if (above + hist[d] >= rem) break;
+          above += hist[d];
+        }
+        s_remaining = rem - above;
+        s_prefix = prefix | ((unsigned long long)d << shift);
+      }
+      __syncthreads();
+    }
+    const unsigned long long threshold = s_prefix;      // the kk-th largest key itself
+    for (int64_t g = tid; g < n_groups; g += kKeysThreads) {
+      const unsigned long long kv = trow[g];
+      if (kv != 0ull && kv >= threshold) {
+        const unsigned int slot = atomicAdd(&taken, 1u);
+        if (slot < (unsigned int)kKeysThreads) sel[slot] = kv;
+      }
+    }
+    __syncthreads();
+    lds_sort_desc(sel, kKeysThreads);
+  }
+  for (int e = tid; e < k; e += kKeysThreads) {
+    const unsigned long long kv = sel[e];
+    const bool real = kv != 0ull;
+    const int64_t p = real ? (int64_t)key_pos(kv) : -1;
+    out_scores[(int64_t)row * k + e] = real ? unorderable(key_score(kv)) : -INFINITY;
+    out_pos[(int64_t)row * k + e] = p;
+    out_ids[(int64_t)row * k + e] = real ? (ids != nullptr ? ids[p] : p) : -1;
+  }
+  if (tid == 0) out_counts[row] = (int32_t)nonzero;
+}
+
+int topk_keys(const unsigned long long* table, int rows, int64_t n_groups, int k, const int64_t* ids, float* out_scores, int64_t* out_pos,
+              int64_t* out_ids, int32_t* out_counts, hipStream_t stream) {
+  if (rows <= 0 || k <= 0) return kOk;
+  if (k > kKeysMaxK) { set_error("topk_keys: k = %d beyond %d", k, kKeysMaxK); return kErrUnsupported; }
+  if (n_groups < 1) { set_error("topk_keys: no groups"); return kErrInvalid; }
+  hipLaunchKernelGGL(topk_keys_kernel, dim3(rows), dim3(kKeysThreads), 0, stream, table, n_groups, k, ids, out_scores, out_pos, out_ids, out_counts);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+}  // namespace mol

@@ -188,6 +188,15 @@ int rerank_topk_filtered(const float* scores, int64_t ld, int rows, int n_cand, 
                          const int64_t* invalid, int width, int k, void* ws, size_t ws_bytes, int64_t* out_ids, float* out_scores, int32_t* flag,
                          hipStream_t stream);
 
+// ---- collapsing by item group (collapse.hip) ----
+int topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int rows, int depth, const int32_t* ranks, int64_t n_items,
+                  const int64_t* ids, const int64_t* invalid, int width, int k, float* out_scores, int64_t* out_pos, int64_t* out_ids,
+                  int32_t* out_counts, int32_t* out_of_range, hipStream_t stream);
+int scores_group_max(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,
+                     unsigned long long* table, int clear_table, const int64_t* ids, const int64_t* invalid, int width, hipStream_t stream);
+int topk_keys(const unsigned long long* table, int rows, int64_t n_groups, int k, const int64_t* ids, float* out_scores, int64_t* out_pos,
+              int64_t* out_ids, int32_t* out_counts, hipStream_t stream);
+
 // ---- IVF-Flat index over the item components (ivf.hip) ----
 int ivf_check(const Shape& s, int64_t n, int nlist, bool from_index);
 int ivf_components16(const Shape& s, const float* ipack, int64_t n, void* table, int64_t n_total, int64_t first, hipStream_t st);

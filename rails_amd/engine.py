@@ -1869,6 +1869,92 @@ def rerank_topk_filtered(scores: torch.Tensor, k_prime: int, positions: torch.Te
     return out_i, out_s
 
 
+COLLAPSE_MAX_LIST = 16384      # entries of one ranked list rails_topk_collapse walks
+COLLAPSE_MAX_K = 512           # rails_topk_keys' k
+COLLAPSE_MAX_SEEN = 4096       # rails_scores_group_max's seen ids per row
+
+
+def _seen_arg(invalid_ids: Optional[torch.Tensor], rows: int, device) -> Tuple[Optional[torch.Tensor], int]:
+    if invalid_ids is None:
+        return None, 0
+    inv = invalid_ids.to(device=device, dtype=torch.int64).contiguous()
+    if inv.dim() != 2 or inv.shape[0] != rows:
+        raise ValueError("invalid_ids must be (rows, width)")
+    return (inv, inv.shape[1]) if inv.shape[1] else (None, 0)
+
+
+def topk_collapse(scores: torch.Tensor, positions: torch.Tensor, ranks: torch.Tensor, k: int, ids: Optional[torch.Tensor],
+                  invalid_ids: Optional[torch.Tensor], flag: torch.Tensor):
+    """The walk of a collapsed top-k (include/rails_amd.h rails_topk_collapse): scores / positions (rows, D) in key order, ranks the (N,) int32
+    dense group ranks -> (scores (rows, k), positions, ids, counts (rows,) int32).  `flag` (int32, zeroed by the caller; device or pinned host
+    memory) is raised when a row's list holds fewer than k distinct eligible groups."""
+    lib = _lib.load()
+    _require_device(scores, "scores")
+    if scores.dtype != torch.float32 or scores.stride(1) != 1:
+        scores = _f32c(scores)
+    rows, depth = scores.shape
+    positions = positions.to(device=scores.device, dtype=torch.int64).contiguous()
+    if positions.shape != (rows, depth):
+        raise ValueError("positions must be (rows, depth) like scores")
+    if ranks.dtype != torch.int32 or ranks.dim() != 1 or ranks.device != scores.device or not ranks.is_contiguous():
+        raise ValueError("ranks must be a contiguous (N,) int32 tensor on the scores' device")
+    if flag.dtype != torch.int32 or not (flag.is_cuda or flag.is_pinned()):
+        raise ValueError("flag must be an int32 tensor on the device or in pinned host memory")
+    if ids is not None:
+        ids = ids.to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
+    inv, width = _seen_arg(invalid_ids, rows, scores.device)
+    out_s = torch.empty((rows, k), dtype=torch.float32, device=scores.device)
+    out_p = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
+    out_i = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
+    counts = torch.empty(rows, dtype=torch.int32, device=scores.device)
+    with _on_device(scores.device):
+        _lib.check(lib.rails_topk_collapse(_ptr(scores), scores.stride(0), _ptr(positions), rows, depth, _ptr(ranks), ranks.numel(), _ptr(ids), _ptr(inv),
+                                           width, k, _ptr(out_s), _ptr(out_p), _ptr(out_i), _ptr(counts), _ptr(flag), _stream()), "rails_topk_collapse")
+    return out_s, out_p, out_i, counts
+
+
+def scores_group_max(scores: torch.Tensor, ranks: torch.Tensor, table: torch.Tensor, first_item: int = 0, clear: bool = True,
+                     ids: Optional[torch.Tensor] = None, invalid_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place on `table` ((rows, G) int64 holding the 64-bit keys): the per-group maxima of the (rows, n) score matrix whose column x is
+    item first_item + x (include/rails_amd.h rails_scores_group_max).  clear: zero the table first."""
+    lib = _lib.load()
+    _require_device(scores, "scores")
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError("scores must be a (rows, n) float32 matrix with unit column stride")
+    rows, n = scores.shape
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[0] != rows or not table.is_contiguous() or table.device != scores.device:
+        raise ValueError("table must be a contiguous (rows, G) int64 tensor on the scores' device")
+    if ranks.dtype != torch.int32 or ranks.dim() != 1 or ranks.device != scores.device or not ranks.is_contiguous() or ranks.numel() < first_item + n:
+        raise ValueError("ranks must be a contiguous int32 tensor of at least first_item + n entries on the scores' device")
+    if ids is not None:
+        ids = ids.to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
+    inv, width = _seen_arg(invalid_ids, rows, scores.device)
+    with _on_device(scores.device):
+        _lib.check(lib.rails_scores_group_max(_ptr(scores), scores.stride(0), rows, n, int(first_item), _ptr(ranks), table.shape[1], _ptr(table),
+                                              1 if clear else 0, _ptr(ids), _ptr(inv), width, _stream()), "rails_scores_group_max")
+    return table
+
+
+def topk_keys(table: torch.Tensor, k: int, ids: Optional[torch.Tensor] = None):
+    """The k largest keys of every row of a group-maxima table, decoded (include/rails_amd.h rails_topk_keys) -> (scores (rows, k), positions,
+    ids, counts (rows,) int32: the row's non-zero keys)."""
+    lib = _lib.load()
+    _require_device(table, "table")
+    if table.dtype != torch.int64 or table.dim() != 2 or not table.is_contiguous():
+        raise ValueError("table must be a contiguous (rows, G) int64 tensor")
+    rows, groups = table.shape
+    if ids is not None:
+        ids = ids.to(device=table.device, dtype=torch.int64).reshape(-1).contiguous()
+    out_s = torch.empty((rows, k), dtype=torch.float32, device=table.device)
+    out_p = torch.empty((rows, k), dtype=torch.int64, device=table.device)
+    out_i = torch.empty((rows, k), dtype=torch.int64, device=table.device)
+    counts = torch.empty(rows, dtype=torch.int32, device=table.device)
+    with _on_device(table.device):
+        _lib.check(lib.rails_topk_keys(_ptr(table), rows, groups, k, _ptr(ids), _ptr(out_s), _ptr(out_p), _ptr(out_i), _ptr(counts), _stream()),
+                   "rails_topk_keys")
+    return out_s, out_p, out_i, counts
+
+
 def topk_filter_fusable(n: int, k_prime: int, width: int, k: int) -> bool:
     return bool(_lib.load().rails_topk_filter_fusable(int(n), int(k_prime), int(width), int(k)))
 

@@ -194,6 +194,34 @@ def tags_after_removal(tags: torch.Tensor, n_new: int, holes: torch.Tensor, move
     return out
 
 
+def groups_after_append(groups: torch.Tensor, n: int, n_new: int) -> torch.Tensor:
+    """append_items on a group-key row: the (n,) int32 row grown to n_new keys, the new items n .. n_new - 1 ungrouped
+    (-1: they collapse with nothing until set_item_groups(..., positions) keys them).  Pure tensor arithmetic."""
+    out = torch.full((int(n_new),), -1, dtype=torch.int32, device=groups.device)
+    out[:n] = groups[:n]
+    return out
+
+
+def groups_after_removal(groups: torch.Tensor, n_new: int, holes: torch.Tensor, movers: torch.Tensor) -> torch.Tensor:
+    """remove_items on a group-key row: keys belong to the position, so the i-th mover's key -- read BEFORE the cut -- goes to the i-th hole and
+    the row is cut to n_new keys (tags_after_removal's rule; a copy: the row given is not written)."""
+    return tags_after_removal(groups, n_new, holes, movers)
+
+
+GROUP_KEY_LIMIT = (1 << 31) - 1      # group keys lie in [-1, GROUP_KEY_LIMIT)
+
+
+def group_ranks(groups: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """The dense ranks the collapse kernels read: groups, an (N,) integer row of keys >= 0 or -1 (ungrouped) ->
+    ((N,) int32 ranks in [0, G), G): equal keys get equal ranks, every ungrouped item a rank of its own, so G <= N.  A function of the row
+    alone -- the ranks of keyed items follow the order of their keys, the ungrouped ones follow in position order -- so an edit chain and a
+    fresh module of the resulting row agree.  Integer plumbing in torch ops, on whichever device the row lives (one sync for G)."""
+    g = groups.to(torch.int64)
+    surrogate = torch.where(g < 0, GROUP_KEY_LIMIT + torch.arange(g.numel(), dtype=torch.int64, device=g.device), g)
+    uniq, inverse = torch.unique(surrogate, return_inverse=True)
+    return inverse.to(torch.int32).contiguous(), int(uniq.numel())
+
+
 def parse_allowed_tags(allowed_tags, batch: int) -> Tuple[int, ...]:
     """allowed_tags= as given -> its allow words as host integers: (word,) for a Python int (shared by the batch), else one per query row from
     a sequence or an integer tensor of shape (batch,) (a device tensor is copied to the host: one sync).  ValueError for anything else, a
@@ -249,6 +277,15 @@ def refuse_allowed_tags(module, kwargs, why: str) -> None:
     """allowed_tags= where it is not built: refused by the class's name, before any launch."""
     if kwargs.get("allowed_tags") is not None:
         raise NotImplementedError(f"{type(module).__name__} takes no allowed_tags: {why}")
+
+
+def refuse_collapse_groups(module, kwargs, what: Optional[str] = None) -> None:
+    """collapse_groups=True where it is not built -- the item-sharded wrappers, the hand-off calls they use, and the calls
+    that return no ranked ids (all_logits, topk_ids): refused by the class's name, before any launch."""
+    if kwargs.get("collapse_groups"):
+        name = type(module).__name__ + ("" if what is None else "." + what)
+        raise NotImplementedError(f"{name} takes no collapse_groups: collapsing by item group is built on the single-device modules' forward, "
+                                  "forward_filtered, submit and get_top_k_outputs only")
 
 
 def _tag_ks(module) -> Tuple[int, ...]:
@@ -352,6 +389,11 @@ class _ItemsById:
     def _take_item_mask(self, kwargs: dict, batch: int, k: Optional[int]) -> Optional[E.ItemMask]:
         """item_mask= of a call, taken OUT of its kwargs: None, or the ItemMask (a bool tensor is packed: one sync) checked against this module,
         the batch and k before any launch (engine.check_item_mask)."""
+        if "_resolved_mask" in kwargs:      # a collapsed call (DESIGN section 3.16) resolved its mask once and hands it to every arm it runs
+            m = kwargs.pop("_resolved_mask")
+            if m is not None:
+                m.check(self.num_items, batch, k)
+            return m
         m = kwargs.pop("item_mask", None)
         if kwargs.get("allowed_tags") is not None:      # a tag filter (DESIGN section 3.15) becomes the call's mask: the hidden set is inside its tags
             if m is not None:
@@ -686,6 +728,115 @@ class _CorpusEdits(_ItemsById):
         elif e.how == CUT_AND_FILLED:
             self._tags_are(tags_after_removal(self._tags, e.n_new, e.positions, e.movers))
 
+    # ---- item groups: one group key per item, and collapse_groups=True on the calls ------------------------------------
+    # State: an owned (N,) int32 row of keys (>= 0, or -1: ungrouped), None until set_item_groups -- such a module runs exactly the launches it
+    # ran before.  A call with collapse_groups=True returns, per row, the first k items of the row's ranking (score desc, position asc, over the
+    # items the row may return and has not seen) whose key is -1 or differs from the key of every earlier item of that ranking: each group is
+    # represented by its best eligible item.  Keys belong to the POSITION and follow edits as tags do (groups_after_append / groups_after_removal).
+    # The kernels read the DENSE ranks of the keys (group_ranks), computed once per row and kept.
+    _groups: Optional[torch.Tensor] = None
+    _group_rank_cache = None       # (ranks (N,) int32, G) of the current row
+    COLLAPSE_DEPTH_FACTOR = 2      # the exact modules' first walk looks at this many times k + width ranked items ...
+    COLLAPSE_MAX_DEPTH = 4096      # ... and a walk that found too few groups doubles its depth up to this; beyond it the group-maxima pass answers
+
+    @property
+    def item_groups(self) -> Optional[torch.Tensor]:
+        """The (N,) int32 group keys on the module's device, or None while no groups are set.  The hand-off of the keys -- they are not part of
+        state_dict; set_item_groups takes this tensor back as it is."""
+        return self._groups
+
+    def set_item_groups(self, groups: torch.Tensor, positions: Optional[torch.Tensor] = None) -> None:
+        """One group key per item.  groups: (N,) -- every item -- or (M,) with positions ((M,) int64, CPU or device, unique POSITIONS); int32 or
+        int64 values in [-1, 2^31 - 1), -1 = ungrouped; on the module's device.  A call with positions on a module without groups builds the
+        row with every other item at -1.  ValueError before anything is touched for a wrong shape, dtype, device, value or position (the
+        value check and the position check cost one sync each).  The stored row is the module's own: neither argument is aliased."""
+        self._check_collapsible("set_item_groups")
+        n = self.num_items
+        dev = self._ids_flat.device
+        if not torch.is_tensor(groups) or groups.dim() != 1 or groups.dtype not in (torch.int32, torch.int64):
+            raise ValueError("groups must be an (N,) or (M,) int32 / int64 tensor")
+        if groups.device != dev:
+            raise ValueError(f"groups must live on the module's device {dev}, got {groups.device}")
+        m = groups.numel()
+        if positions is None:
+            if m != n:
+                raise ValueError(f"groups has {m} keys but the module holds {n} items (pass positions to key a subset)")
+        else:
+            positions = _checked_positions(positions, m, n)
+        if m:
+            lo, hi = torch.aminmax(groups)
+            if int(lo) < -1 or int(hi) >= GROUP_KEY_LIMIT:
+                raise ValueError("groups must lie in [-1, 2^31 - 1)")
+        with torch.inference_mode():
+            self._join_side_streams()
+            keys = groups.to(torch.int32)
+            if positions is None:
+                row = keys.clone()
+            else:
+                row = torch.full((n,), -1, dtype=torch.int32, device=dev) if self._groups is None else self._groups.clone()
+                row.index_copy_(0, positions.to(dev), keys)
+            self._groups_are(row)
+
+    def clear_item_groups(self) -> None:
+        """No item carries a group key any more: collapse_groups=True is refused again, every other call is what it was."""
+        self._groups_are(None)
+
+    def _groups_are(self, row: Optional[torch.Tensor]) -> None:
+        self._groups = row
+        self._group_rank_cache = None
+
+    def _groups_step(self, e: CorpusEdit, n: int) -> None:
+        """The group-key row follows an edit (called by _apply)."""
+        if self._groups is None:
+            return
+        if e.how == CONCATENATED:
+            self._groups_are(groups_after_append(self._groups, n, e.n_new))
+        elif e.how == CUT_AND_FILLED:
+            self._groups_are(groups_after_removal(self._groups, e.n_new, e.positions, e.movers))
+
+    def _dense_group_ranks(self) -> Tuple[torch.Tensor, int]:
+        c = self._group_rank_cache
+        if c is None:
+            with torch.inference_mode():
+                c = self._group_rank_cache = group_ranks(self._groups)
+        return c
+
+    def _check_collapsible(self, what: str) -> None:
+        """The refusal point of the item groups: modules whose candidate generation cannot honour them raise here, before anything is touched."""
+
+    def _take_collapse(self, kwargs: dict) -> bool:
+        """collapse_groups= of a call, taken OUT of its kwargs and checked against this module before any launch."""
+        if not kwargs.pop("collapse_groups", False):
+            return False
+        self._check_collapsible("collapse_groups")
+        if self._groups is None:
+            raise ValueError(f"{type(self).__name__}: collapse_groups=True on a module without groups (set_item_groups first)")
+        return True
+
+    def collapse_stats(self) -> dict:
+        """Which path answered the collapsed calls so far: calls, walk_redos (depth doublings), fallbacks (exact group-maxima passes)."""
+        return dict(self.__dict__.setdefault("_collapse_stats", {"calls": 0, "walk_redos": 0, "fallbacks": 0}))
+
+    @contextlib.contextmanager
+    def _positions_as_ids(self):
+        """Inside this block every call of the module returns POSITIONS where it returns ids: the id table is swapped for 0 .. N - 1, so whichever
+        arm ranks the call (the proved flow, the dense kernels, the chunks, the sparse masked strategy, a rerank) hands the collapse walk the
+        positions it needs without a second form of each arm.  It works because every arm reads self._ids_flat when it launches, and it is
+        module state while it lasts: code that runs inside the block must not keep anything derived from the id table -- build the id map
+        (only the by-id calls do, never a query call), cache a gathered id tensor, capture a graph -- and a module is driven by one thread at a
+        time, as everywhere else in this file (the scratch buffers and pinned words are per module too).  The block holds one query call and
+        nothing else: _collapsed_exact's forward, _collapsed_candidates' submit / result."""
+        n = self.num_items
+        c = self.__dict__.get("_position_ids")
+        if c is None or c.numel() != n or c.device != self._ids_flat.device:
+            c = self._position_ids = torch.arange(n, dtype=torch.int64, device=self._ids_flat.device)
+        saved = self._ids_flat
+        self._ids_flat = c
+        try:
+            yield
+        finally:
+            self._ids_flat = saved
+
     HIDDEN_FUSED_MIN_VISIBLE = 0.5    # hidden_scan_route: the visible fraction below which a scan of a module with a hidden set is materialised directly
     TAGGED_FUSED_MIN_GROUPS = 2.0     # tagged_scan_route: the expected finite group maxima, in units of the plan's rank r, below which a tagged scan is materialised directly
 
@@ -784,6 +935,7 @@ class _CorpusEdits(_ItemsById):
                 self._id_map_step(gone, ids, pos)
             self._visibility_step(e, n)
             self._tags_step(e, n)
+            self._groups_step(e, n)
             held, resize = self._held_buffers(), e.n_new != n
             if resize:
                 self._forget_corpus_choices()
@@ -950,6 +1102,7 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
 
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus."""
+        refuse_collapse_groups(self, kwargs, "all_logits")
         refuse_item_mask(self, kwargs)
         tags = self._take_allowed_tags(kwargs, query_embeddings.size(0), ())
         logits = self._raw_logits(query_embeddings, **kwargs)
@@ -1296,6 +1449,7 @@ class MoLBruteForceTopK(MoLTopKModule):
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus -- of the module's OWN precision (the proved mode's internal split-f16
         engine is not the module's precision: its fp32 companion answers).  item_mask=: the columns outside the mask hold -inf."""
+        refuse_collapse_groups(self, kwargs, "all_logits")
         eng = self._bind()
         mask = self._take_item_mask(kwargs, query_embeddings.size(0), None)
         if eng.exact is not None and self._mol_module.engine() is not eng:
@@ -1372,7 +1526,10 @@ class MoLBruteForceTopK(MoLTopKModule):
         return s.to(query_embeddings.dtype), ids
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        """item_mask= (an engine.ItemMask, or a bool tensor (N,) / (B, N) packed for this call): only items inside the mask are returned."""
+        """item_mask= (an engine.ItemMask, or a bool tensor (N,) / (B, N) packed for this call): only items inside the mask are returned.
+        collapse_groups=True: at most one item per group of set_item_groups."""
+        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
+            return _collapsed_exact(self, query_embeddings, k, None, kwargs)
         eng = self._bind()
         mask = self._take_item_mask(kwargs, query_embeddings.size(0), k)
         if mask is not None:
@@ -1390,7 +1547,11 @@ class MoLBruteForceTopK(MoLTopKModule):
         """CandidateIndex.get_top_k_outputs' body for this module: top-k' + id map + seen-id filter with the filter fused into the final
         selection launch (rails_topk_filtered on the dense logits) -> (top_k_ids (B, k), top_k_scores (B, k)),
         or None when the sizes / the precision route are outside the fused path (the caller then composes forward +
-        filter_seen_ids: same bits)."""
+        filter_seen_ids: same bits).  collapse_groups=True never returns None: the seen ids go to the collapse walk (a filter behind the
+        collapse would drop a group whose best item is seen instead of promoting its next member)."""
+        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
+            scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs)
+            return ids, scores
         eng = self._bind()
         B, N = query_embeddings.size(0), self._index.n_items
         mask = self._take_item_mask(kwargs, B, k_prime)
@@ -1417,6 +1578,23 @@ class MoLBruteForceTopK(MoLTopKModule):
         if r[0] == "filtered":
             return r[1], r[2]
         return E.filter_seen_ids(r[1], r[0], invalid_ids, k)
+
+    def _own_score_chunks(self, query_embeddings: torch.Tensor, mask: Optional[E.ItemMask], **kwargs):
+        """all_logits' scores -- the module's OWN precision, -inf outside `mask` -- as (first item, (B, n) matrix) pieces: the whole corpus
+        where the logit policy lets it be materialised, CHUNK_ITEMS at a time otherwise (the collapse fallback consumes each before the next)."""
+        eng = self._bind()
+        if eng.exact is not None and self._mol_module.engine() is not eng:
+            eng, index = eng.exact, self._dense_fp32_index()
+        else:
+            index = self._index
+        B, N = query_embeddings.size(0), index.n_items
+        C = N if B * N * 4 <= self.MAX_LOGIT_BYTES else min(N, self.CHUNK_ITEMS)
+        qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"))
+        for lo in range(0, N, C):
+            logits = eng.score_dense(qpack, B, index if C == N else index.items(lo, min(N, lo + C)))
+            if mask is not None:
+                E.scores_mask(logits, mask, first_item=lo)
+            yield lo, logits
 
     MAX_LOGIT_BYTES = 4 << 30      # larger (B, N) logit matrices are never materialised: the corpus is scored in chunks
     CHUNK_ITEMS = 1 << 23          # 8 Mi items per chunk (a multiple of the tile): 1 GiB of logits at B = 32
@@ -2194,6 +2372,129 @@ def _speculative_scan(tk, scan: CandidateScan, eq: torch.Tensor, restr: Optional
     return (sc, pos) if with_scores else scan.shaped(pos, batch)
 
 
+class CollapseWalk(NamedTuple):
+    """One enqueued walk of a collapsed call: its outputs and the pinned verdict word the host reads behind them."""
+    scores: torch.Tensor
+    positions: torch.Tensor
+    ids: torch.Tensor
+    counts: torch.Tensor
+    word: torch.Tensor
+
+    def clear(self, tk) -> bool:
+        return _verdicts_clear([self.word], tk)
+
+
+def _collapse_count(tk, key: str) -> None:
+    stats = tk.__dict__.setdefault("_collapse_stats", {"calls": 0, "walk_redos": 0, "fallbacks": 0})
+    stats[key] += 1
+
+
+def _too_few_groups(k: int, counts: torch.Tensor) -> RuntimeError:
+    return RuntimeError(f"selected index k out of range (k={k}, n={int(counts.min())}: the distinct eligible groups of the row with the fewest)")
+
+
+def _collapse_walk(tk, scores: torch.Tensor, positions: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor]) -> CollapseWalk:
+    """The one walk launch (rails_topk_collapse) behind a ranked list of POSITIONS in key order; the seen-id filter runs inside it."""
+    ranks, _ = tk._dense_group_ranks()
+    word = _pinned_word(tk)
+    word.zero_()      # (a word on the free list has been read: nothing in flight writes it)
+    return CollapseWalk(*E.topk_collapse(scores, positions, ranks, k, tk._ids_flat, invalid_ids, word), word)
+
+
+def _collapsed_exact(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The collapsed call of an exact module -> (scores, ids).  The module's ordinary ranked top-D BY POSITION, through the
+    arm it would take anyway with the call's mask / hidden set / tags -- the seen ids are NOT handed to it: a seen item must not represent its
+    group, so they go to the walk --, then the walk; a walk that found fewer than k groups doubles D up to COLLAPSE_MAX_DEPTH, and beyond that
+    the exact fallback answers: the group maxima of the materialised scores (_collapse_fallback).  Correctness never depends on the depths:
+    the first k first-occurrences of the top-D are those of the whole ranking whenever the top-D holds k of them."""
+    width = 0 if invalid_ids is None else invalid_ids.shape[1]
+    if k > E.COLLAPSE_MAX_K or width > E.COLLAPSE_MAX_SEEN:      # (the fallback's sizes: it must be there for every call the walks may fail on)
+        raise NotImplementedError(f"{type(tk).__name__}: collapse_groups=True takes k <= {E.COLLAPSE_MAX_K} and up to {E.COLLAPSE_MAX_SEEN} seen ids per "
+                                  f"row (what its exact group-maxima pass selects and filters), got k = {k}, width = {width}")
+    _collapse_count(tk, "calls")
+    B, n = query_embeddings.size(0), tk.num_items
+    # the call's mask -- item_mask= (a bool tensor is packed here: its one sync), allowed_tags=, the hidden set -- is resolved ONCE; every
+    # forward of the loop and the fallback take the resolved ItemMask as it is (_take_item_mask's _resolved_mask)
+    kwargs = dict(kwargs)
+    mask = tk._take_item_mask(kwargs, B, k)
+    kwargs["_resolved_mask"] = mask
+    bound = n if mask is None else mask.kept_min
+    if k > bound:
+        raise RuntimeError(f"selected index k out of range (k={k}, n={bound})")
+    depth = min(bound, tk.COLLAPSE_DEPTH_FACTOR * (k + width), E.COLLAPSE_MAX_LIST)
+    while depth >= k:
+        with tk._positions_as_ids():
+            scores, positions = tk.forward(query_embeddings, depth, **dict(kwargs))
+        walk = _collapse_walk(tk, scores, positions, k, invalid_ids)
+        if walk.clear(tk):
+            return walk.scores.to(query_embeddings.dtype), walk.ids
+        deeper = min(2 * depth, bound, tk.COLLAPSE_MAX_DEPTH, E.COLLAPSE_MAX_LIST)
+        if deeper <= depth:
+            break
+        depth = deeper
+        _collapse_count(tk, "walk_redos")
+    del kwargs["_resolved_mask"]
+    return _collapse_fallback(tk, query_embeddings, k, invalid_ids, mask, kwargs)
+
+
+def _collapse_fallback(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], mask: Optional[E.ItemMask],
+                       kw: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exact fallback of a collapsed call: dense scores of the module's own precision, the call's mask written into them, their per-group
+    maxima as 64-bit keys (rails_scores_group_max, per corpus chunk under the logit policy, the seen-id filter inside) and the top-k of the
+    (B, G) key table (rails_topk_keys) -- a slice of the batch at a time where that table would exceed the same policy.  A row with fewer than k
+    non-empty groups is the RuntimeError of a call for more than there is.  mask: the call's resolved mask; kw: its other keyword arguments.
+    (k and the seen-id width were checked against the pass's limits by _collapsed_exact, before any launch.)"""
+    _collapse_count(tk, "fallbacks")
+    B = query_embeddings.size(0)
+    ranks, groups = tk._dense_group_ranks()
+    rows = max(1, min(B, int(getattr(tk, "MAX_LOGIT_BYTES", 4 << 30)) // (groups * 8)))
+    parts = []
+    for b0 in range(0, B, rows):
+        b1 = min(B, b0 + rows)
+        part_kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kw.items()}
+        part_mask = mask if mask is None or mask.shared else mask.rows_slice(b0, b1)
+        table = torch.empty((b1 - b0, groups), dtype=torch.int64, device=query_embeddings.device)
+        first = True
+        for lo, logits in tk._own_score_chunks(query_embeddings[b0:b1], part_mask, **part_kw):
+            E.scores_group_max(logits, ranks, table, first_item=lo, clear=first, ids=tk._ids_flat, invalid_ids=None if invalid_ids is None else invalid_ids[b0:b1])
+            first = False
+        parts.append(E.topk_keys(table, k, tk._ids_flat))
+    scores, ids, counts = (torch.cat([p[i] for p in parts], 0) for i in (0, 2, 3))
+    if int(counts.min()) < k:      # (the one read-back of the fallback)
+        raise _too_few_groups(k, counts)
+    return scores.to(query_embeddings.dtype), ids
+
+
+def _collapsed_candidates(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], n_ranked: int, kwargs: dict):
+    """The collapsed call of an approximate module -> a handle for _collapsed_candidates_result.  The walk runs over the module's own ranked
+    candidate list -- forward's, by position, in its sorted form, all n_ranked of it -- in place of the final cut to k.  No doubling and no
+    fallback: the depth is the list's, and too few distinct groups among the candidates is the RuntimeError.  A list longer than the walk takes
+    is refused here, before any launch."""
+    n_list = n_ranked if n_ranked else tk._union_width()
+    if n_list > E.COLLAPSE_MAX_LIST:
+        raise NotImplementedError(f"{type(tk).__name__}: collapse_groups=True walks ranked lists of up to {E.COLLAPSE_MAX_LIST} candidates per query, this "
+                                  f"module ranks {n_list}")
+    _collapse_count(tk, "calls")
+    with tk._positions_as_ids(), getattr(tk, "inline_calls", contextlib.nullcontext)():
+        inner = MoLAvgTopK.submit(tk, query_embeddings, n_ranked, **dict(kwargs)) if n_ranked else None
+        ranked = inner[1:3] if inner is not None else tk.forward(query_embeddings, k, **dict(kwargs))
+    return (tk, inner, _collapse_walk(tk, ranked[0], ranked[1], k, invalid_ids), k, invalid_ids, query_embeddings.dtype)
+
+
+def _collapsed_candidates_result(handle) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (scores, ids); owns the redo of the candidate scan (MoLAvgTopK.result's) and the look at the walk's verdict."""
+    tk, inner, walk, k, invalid_ids, dtype = handle
+    if inner is not None:
+        with tk._positions_as_ids():
+            scores, positions = MoLAvgTopK.result(tk, inner)
+        if scores is not inner[1]:      # the scan was redone on the materialising path: walk its list instead
+            walk.clear(tk)
+            walk = _collapse_walk(tk, scores, positions, k, invalid_ids)
+    if not walk.clear(tk):
+        raise _too_few_groups(k, walk.counts)
+    return walk.scores.to(dtype), walk.ids
+
+
 class MoLAvgTopK(MoLTopKModule):
     DEVICE_REDO_BYTES = 1 << 30   # materialised score matrices up to this size are kept as the device-side redo buffer of a fused scan;
                                   # beyond it (a 125 M-item shard: 16 GB) the counts are read on the host after the call is enqueued --
@@ -2377,6 +2678,8 @@ class MoLAvgTopK(MoLTopKModule):
     # joined to the caller's stream only by result() -- read them through result(), never through the handle, and do not drop a handle
     # without calling result() (ShardedTopK.submit, which needs the scores earlier, waits on the handle's event explicitly).
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
+        if "collapse_groups" in kwargs and self._take_collapse(kwargs):      # (the walk over the reranked candidates; result owns the redo)
+            return ("collapsed", self._collapse_enqueue(query_embeddings, k, None, kwargs))
         refuse_item_mask(self, kwargs)
         if kwargs.get("allowed_tags") is not None:      # allowed_tags=, resolved and checked before any launch; the handle and a
             kwargs["allowed_tags"] = self._take_allowed_tags(kwargs, query_embeddings.size(0), (self._avg_top_k,))      # redo carry the resolved filter
@@ -2408,7 +2711,17 @@ class MoLAvgTopK(MoLTopKModule):
             return ("final", scores, ids)
         return ("speculative", scores, ids, host, done, query_embeddings, k, kwargs, side)
 
+    def _collapse_enqueue(self, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict):
+        """The collapsed call over this module's own ranked list: MoLAvgTopK's avg_top_k reranked candidates; a subclass with its own forward
+        (MoLCombTopK) has that forward rank its union."""
+        own = type(self).forward is MoLAvgTopK.forward
+        if own and k > self._avg_top_k:
+            raise ValueError(f"avg_top_k ({self._avg_top_k}) must be larger than k ({k})")
+        return _collapsed_candidates(self, query_embeddings, k, invalid_ids, self._avg_top_k if own else 0, kwargs)
+
     def result(self, handle) -> Tuple[torch.Tensor, torch.Tensor]:
+        if handle[0] == "collapsed":
+            return _collapsed_candidates_result(handle[1])
         if handle[0] == "final":
             return handle[1], handle[2]
         _, scores, ids, host, done, query_embeddings, k, kwargs, side = handle
@@ -2438,7 +2751,11 @@ class MoLAvgTopK(MoLTopKModule):
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
         """CandidateIndex.get_top_k_outputs' body: forward(k_prime) + the seen-id filter, with the filter enqueued BEFORE the host looks
         at the scan's verdict word (it then runs while the host is on its way back) -> (top_k_ids, top_k_scores); None where this
-        does not apply (subclasses with their own forward, k_prime beyond K': the caller composes the two calls)."""
+        does not apply (subclasses with their own forward, k_prime beyond K': the caller composes the two calls).  collapse_groups=True never
+        returns None: the seen ids go to the collapse walk."""
+        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
+            scores, ids = _collapsed_candidates_result(self._collapse_enqueue(query_embeddings, k, invalid_ids, kwargs))
+            return ids, scores
         refuse_item_mask(self, kwargs)
         if type(self).forward is not MoLAvgTopK.forward or k_prime > self._avg_top_k or k_prime < k:
             return None
@@ -2460,6 +2777,7 @@ class MoLAvgTopK(MoLTopKModule):
 
     def coarse_candidates(self, query_embeddings: torch.Tensor, **kwargs):
         """Pass 1 on this module's items: -> (coarse scores (B, K'), positions (B, K')), best first (ties by position)."""
+        refuse_collapse_groups(self, kwargs, "coarse_candidates")
         refuse_allowed_tags(self, kwargs, "coarse_candidates is the item-sharded wrappers' hand-off, and a tag filter is not built on them; forward, submit "
                             "and topk_ids take it")
         eng = self._bind()
@@ -2479,6 +2797,7 @@ class MoLAvgTopK(MoLTopKModule):
 
     def topk_ids(self, query_embeddings: torch.Tensor, sorted: bool = True, **kwargs) -> torch.Tensor:
         """Coarse candidates only, with the P_Q-averaged query (reference mol_top_k.py:398-429) -> positions."""
+        refuse_collapse_groups(self, kwargs, "topk_ids")
         return self._coarse_topk(query_embeddings, average_queries=True, **kwargs)[1]
 
 
@@ -2496,13 +2815,20 @@ class _ComponentCandidates:
         self._comp_table = None
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        """All the union's candidates ranked, whatever `k` is, as the reference does."""
+        """All the union's candidates ranked, whatever `k` is, as the reference does.  collapse_groups=True: the first k
+        of that ranking with at most one item per group of set_item_groups -- k columns."""
+        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
+            return _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, None, 0, kwargs))
         scores, ids = self._ranked(query_embeddings, sorted, None, kwargs)
         return scores.to(query_embeddings.dtype), ids
 
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
         """CandidateIndex.get_top_k_outputs' body (the module returns all its candidates whatever k_prime is, the filter keeps the first k unseen):
-        -> (top_k_ids, top_k_scores), or None where the filter does not fit the selection launch (_filter_inside)."""
+        -> (top_k_ids, top_k_scores), or None where the filter does not fit the selection launch (_filter_inside).  collapse_groups=True never
+        returns None: the seen ids go to the collapse walk, over the sorted form of the ranking."""
+        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
+            scores, ids = _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, invalid_ids, 0, kwargs))
+            return ids, scores
         seen = self._filter_inside(self._union_width(), invalid_ids, k)
         if seen is None:
             return None
@@ -2589,6 +2915,7 @@ class _ComponentCandidates:
         (scores, positions), both (B, K'), behind them.  Scores are the scans' bf16 values as fp32.  VERIFIED before it returns: the fused
         scans are enqueued speculatively, their verdict words read once (the one host look of the single-device call), and a failed verdict
         redoes the scans on the materialising path -- what comes back is exact."""
+        refuse_collapse_groups(self, kwargs, "local_candidates")
         refuse_allowed_tags(self, kwargs, "local_candidates is the item-sharded wrappers' hand-off, and a tag filter is not built on them; forward and "
                             "get_top_k_outputs take it")
         eng = self._bind()
@@ -2765,6 +3092,11 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
         # (tags travel as a keyword only when there are any: tests/test_gpu_parity.py swaps _component_topk for a stand-in of the (eq, k, pending) form)
         return self._component_topk(eq, self._k_per_group, pending, **({} if tags is None else {"tags": tags}))
 
+    def _check_collapsible(self, what: str) -> None:
+        if self._use_faiss:
+            raise NotImplementedError(f"MoLNaiveTopK (IVF, use_faiss=True) takes no {what}: collapsing by item group is not built on the IVF index; the "
+                                      "exhaustive MoLNaiveTopK takes it")
+
     def _check_taggable(self, what: str) -> None:
         if self._use_faiss and not getattr(self, "_filtered_lists", False):
             raise NotImplementedError(f"MoLNaiveTopK takes no {what}: the IVF index (use_faiss=True{', frozen_centroids=True' if self._frozen_centroids else ''}) "
@@ -2824,16 +3156,32 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
         self._table_dtype = item_embeddings.dtype      # (what update_items / append_items take; the index holds fp32 copies)
         self._index = E.MipsIndex(item_embeddings[0])
         self._ids_flat = item_ids.reshape(-1).to(device=item_embeddings.device, dtype=torch.int64).contiguous()
+        self._flag_free: list = []    # pinned verdict words ready for reuse (_pinned_word: the collapse walk's)
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """item_mask= (an engine.ItemMask or a bool tensor (N,) / (B, N)): only items inside the mask are returned -- the
-        dense strategy: the score matrix of the items outside it is set to -inf before the selection."""
+        dense strategy: the score matrix of the items outside it is set to -inf before the selection.  collapse_groups=True (section 3.16): at
+        most one item per group of set_item_groups."""
+        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
+            return _collapsed_exact(self, query_embeddings, k, None, kwargs)
         mask = self._take_item_mask(kwargs, query_embeddings.size(0), k)
         logits = self._index.score(query_embeddings)
         if mask is not None:
             E.scores_mask(logits, mask)
         scores, ids = E.topk(logits, k, ids=self._ids_flat, sorted=sorted)
         return scores.to(query_embeddings.dtype), ids
+
+    def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
+        """CandidateIndex.get_top_k_outputs' body under collapse_groups=True -> (top_k_ids, top_k_scores): the seen ids go to the collapse walk.
+        None for every other call (the caller composes forward + filter_seen_ids, as it always has)."""
+        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
+            scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs)
+            return ids, scores
+        return None
+
+    def _own_score_chunks(self, query_embeddings: torch.Tensor, mask: Optional[E.ItemMask], **kwargs):
+        logits = self._index.score(query_embeddings)
+        yield 0, logits if mask is None else E.scores_mask(logits, mask)
 
     # ---- in-place corpus changes (_CorpusEdits): the MoL modules' three calls -------------------------------------------------------------
     # The module keeps the tile-packed copy and the ids only: after any sequence of the calls _index.buf and _ids_flat are what a fresh module

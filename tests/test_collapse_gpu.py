@@ -1,0 +1,595 @@
+"""GPU: collapse_groups=True.  The reference of every module-level case is tests/_collapse_ref.py's collapse_walk applied to
+the module's OWN all_logits(...) of the same call arguments (MIPSBruteForceTopK: its score matrix), ordered on the host by (score desc, position
+asc) in exact integer arithmetic; the comparison is torch.equal on ids and on scores, every row of every case.  The approximate modules are
+compared with collapse_walk over their own forward(q, k = all candidates) ranking.  The three kernels are also driven on their own, on
+hand-built lists and exact inputs."""
+import pytest
+import torch
+
+import rails_amd
+from oracle import mol_oracle as O
+from rails_amd import engine as E
+from tests import _collapse_ref as CR
+from tests import test_index_update_gpu as U
+from tests._fixtures import Fixture
+from tests.test_generic_route_gpu import CASES as GENERIC, build_module
+
+pytestmark = pytest.mark.gpu
+N = 4096 + 37          # a ragged last tile
+NEG_INF = float("-inf")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def aux_of(cfg, batch, dev):
+    return {"user_ids": (torch.arange(batch, dtype=torch.int64) * 7919 - 5).to(dev)} if cfg.uid_embedding_hash_sizes else {}
+
+
+def setup(dev, batch, name="c3_books", n=N, precision=None, seed=7, **kw):
+    """-> (tk, q, aux, X, ids) of a MoLBruteForceTopK over n hashed rows with the fixture's weights."""
+    if name in GENERIC:
+        cfg, w, _ = GENERIC[name]
+    else:
+        fx = Fixture(name)
+        cfg, w = fx.cfg, fx.weights
+    mol = build_module(cfg, w, dev, precision=precision)
+    X, ids = U.table(cfg, n, seed, dev), U.ids_of(n, dev)
+    tk = rails_amd.MoLBruteForceTopK(mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0), **kw)
+    return tk, O.synthetic_queries(cfg, batch, seed=5).to(dev), aux_of(cfg, batch, dev), X, ids
+
+
+def layout_a(n, g):
+    """random keys, mean group size 4, a tenth of the items ungrouped"""
+    keys = torch.randint(0, n // 4, (n,), generator=g)
+    keys[torch.randperm(n, generator=g)[: n // 10]] = -1
+    return keys
+
+
+def layout_c(logits_row0, n, g):
+    """one giant group (key 0) owning the top 60 % of row 0's ranking; layout (a), shifted past key 0, elsewhere"""
+    keys = layout_a(n, g)
+    keys[keys >= 0] += 1
+    keys[CR.key_order(logits_row0)[: n * 6 // 10]] = 0
+    return keys
+
+
+def logits_of(tk, q, kw):
+    if isinstance(tk, rails_amd.MIPSBruteForceTopK):
+        kw = dict(kw)
+        mask = tk._take_item_mask(kw, q.shape[0], None)
+        logits = tk._index.score(q)
+        return logits if mask is None else E.scores_mask(logits, mask)
+    return tk.all_logits(q, **kw)
+
+
+def check(tk, q, k, kw, what, invalid=None, want_raise=False):
+    """One collapsed call -- forward, or get_top_k_outputs when there are invalid ids -- against the reference; -> (scores, ids)."""
+    keys, ids = tk.item_groups.cpu(), tk._ids_flat.cpu()
+    want = CR.collapsed_topk(logits_of(tk, q, kw), keys, invalid, ids, k)
+    call_kw = dict(kw, collapse_groups=True)
+
+    def call():
+        if invalid is None:
+            return tk(q, k=k, **call_kw)
+        cand = rails_amd.CandidateIndex(ids=tk._ids_flat.reshape(1, -1), embeddings=None)
+        got_ids, got_scores, _ = cand.get_top_k_outputs(q, k, call_kw, tk, invalid)
+        return got_scores, got_ids
+
+    if want is None or want_raise:
+        assert want is None, what
+        with pytest.raises(RuntimeError, match="out of range"):
+            call()
+        return None
+    scores, got_ids = call()
+    assert scores.shape == (q.shape[0], k) and got_ids.shape == (q.shape[0], k), what
+    assert torch.equal(got_ids.cpu(), want[1]), what
+    assert torch.equal(scores.float().cpu().view(torch.int32), want[0].view(torch.int32)), what
+    return scores, got_ids
+
+
+def both_paths(tk, q, k, kw, what, invalid=None):
+    """the walk path as the module takes it, then the exact fallback forced (a walk of depth 0 never answers): same expected output"""
+    check(tk, q, k, kw, what + ", walk", invalid)
+    before = tk.collapse_stats()["fallbacks"]
+    tk.COLLAPSE_DEPTH_FACTOR = 0
+    try:
+        check(tk, q, k, kw, what + ", forced fallback", invalid)
+    finally:
+        del tk.COLLAPSE_DEPTH_FACTOR
+    assert tk.collapse_stats()["fallbacks"] == before + 1, what
+
+
+def seen_of(tk, q, kw, dev, width=61):
+    """(B, width) invalid ids holding, per row, the reference representatives of its three best groups, then ids nobody returns"""
+    keys, ids = tk.item_groups.cpu(), tk._ids_flat.cpu()
+    logits = logits_of(tk, q, kw).cpu()
+    rows = []
+    for b in range(q.shape[0]):
+        _, _, top = CR.collapse_walk(logits[b], CR.key_order(logits[b]), keys, None, ids, 3)
+        rows.append(torch.tensor(top + [-7 - j for j in range(width - len(top))], dtype=torch.int64))
+    return torch.stack(rows).to(dev)
+
+
+def dense_mode(tk):
+    """exact_mode="dense": the module's own fp32 engine over its own index, no companion engine"""
+    assert tk.exact_mode == "dense" and tk._bind().exact is None and tk._bind().precision == "fp32"
+    return tk
+
+
+@pytest.mark.parametrize("mode", ["dense", "default"])
+@pytest.mark.parametrize("batch", [5, 37])
+def test_layouts(batch, mode, dev):
+    g = torch.Generator().manual_seed(81)
+    with torch.inference_mode():
+        tk, q, aux, X, ids = setup(dev, batch, **({"exact_mode": "dense"} if mode == "dense" else {}))
+        if mode == "dense":
+            dense_mode(tk)
+        assert tk.item_groups is None and tk.collapse_stats() == {"calls": 0, "walk_redos": 0, "fallbacks": 0}
+        plain = {k: tk(q, k=k, **aux) for k in (1, 10, 200)}
+        # (a) random groups
+        tk.set_item_groups(layout_a(N, g).to(dev))
+        assert tk.item_groups.dtype == torch.int32 and tk.item_groups.shape == (N,)
+        for k in (1, 10, 200):
+            both_paths(tk, q, k, aux, f"(a), B = {batch}, k = {k}")
+        for k in (1, 10, 200):      # a module with groups answers a call without the argument as before
+            U.same(tk(q, k=k, **aux), plain[k], f"plain call with groups set, k = {k}")
+            U.same(tk(q, k=k, collapse_groups=False, **aux), plain[k], f"collapse_groups=False, k = {k}")
+        # (b) everything ungrouped: the plain call
+        tk.set_item_groups(torch.full((N,), -1, dtype=torch.int32, device=dev))
+        for k in (1, 10, 200):
+            got = check(tk, q, k, aux, f"(b), B = {batch}, k = {k}")
+            U.same(got, plain[k], f"(b) against the plain call, k = {k}")
+        # (f) sparse large keys against their dense relabelling
+        sparse = torch.tensor([(1 << 31) - 2, 0, 7, 1 << 20, (1 << 31) - 3, 99])
+        dense = torch.randint(0, 6, (N,), generator=g)
+        tk.set_item_groups(sparse[dense].to(dev))
+        got_sparse = check(tk, q, 5, aux, "(f) sparse keys")
+        tk.set_item_groups(dense.to(torch.int32).to(dev))
+        U.same(check(tk, q, 5, aux, "(f) dense keys"), got_sparse, "(f)")
+        check(tk, q, 7, aux, "(f) seven of six groups", want_raise=True)
+        tk.clear_item_groups()
+        assert tk.item_groups is None
+        with pytest.raises(ValueError, match="without groups"):
+            tk(q, k=3, collapse_groups=True, **aux)
+        U.same(tk(q, k=10, **aux), plain[10], "plain call after clear_item_groups")
+
+
+def test_a_giant_group_doubles_the_depth_and_the_fallback_answers(dev):
+    g = torch.Generator().manual_seed(82)
+    with torch.inference_mode():
+        tk, q, aux, X, ids = setup(dev, 5, exact_mode="dense")
+        dense_mode(tk)
+        tk.set_item_groups(layout_c(tk.all_logits(q, **aux)[0], N, g).to(dev))
+        for k in (1, 10, 200):
+            before = tk.collapse_stats()
+            check(tk, q, k, aux, f"(c) walk, k = {k}")
+            after = tk.collapse_stats()
+            if k > 1:      # (k = 1: the giant group's best item IS row 0's first result)
+                assert after["walk_redos"] > before["walk_redos"] and after["fallbacks"] == before["fallbacks"], (k, before, after)
+            tk.COLLAPSE_MAX_DEPTH = 64
+            try:
+                check(tk, q, k, aux, f"(c) COLLAPSE_MAX_DEPTH = 64, k = {k}")
+            finally:
+                del tk.COLLAPSE_MAX_DEPTH
+            if k > 1:
+                assert tk.collapse_stats()["fallbacks"] > after["fallbacks"], k
+        # (d) one group for the whole corpus
+        tk.set_item_groups(torch.zeros(N, dtype=torch.int64, device=dev))
+        s1, i1 = check(tk, q, 1, aux, "(d) k = 1")
+        U.same((s1, i1), tk(q, k=1, **aux), "(d): the top item")
+        fb = tk.collapse_stats()["fallbacks"]
+        check(tk, q, 2, aux, "(d) k = 2", want_raise=True)
+        assert tk.collapse_stats()["fallbacks"] == fb + 1      # raised only after the exact fallback established it
+
+
+def test_all_scores_tie(dev):
+    """(e) a corpus of identical rows: only the position tie rule decides, on the walk and on the forced fallback"""
+    g = torch.Generator().manual_seed(83)
+    with torch.inference_mode():
+        tk, q, aux, X, ids = setup(dev, 5)
+        tk.update_items(torch.arange(N), X[:1].expand(N, -1).contiguous())
+        logits = tk.all_logits(q, **aux)
+        assert bool((logits == logits[:, :1]).all())
+        tk.set_item_groups(layout_a(N, g).to(dev))
+        for k in (1, 10, 200):
+            both_paths(tk, q, k, aux, f"(e) k = {k}")
+
+
+def surfaces(tk, q, aux, dev, what, sparse_ok=True):
+    """forward and get_top_k_outputs under the seen ids, allowed_tags=, item_mask= (shared and per row; the sparse and the dense strategy) and a
+    hidden set -- on whichever path the module's constants select."""
+    g = torch.Generator().manual_seed(84)
+    n, batch = tk.num_items, q.shape[0]
+    check(tk, q, 10, aux, what + ": forward")
+    seen = seen_of(tk, q, aux, dev)
+    got = check(tk, q, 10, aux, what + ": seen ids", seen)
+    assert not bool((got[1].unsqueeze(2) == seen.unsqueeze(1)).any())      # (the next members of the seen representatives' groups: the reference's rows, compared above)
+    tags =(torch.ones(n, dtype=torch.int64) << torch.randint(0, 4, (n,), generator=g)).to(dev)
+    tk.set_item_tags(tags)
+    allowed = [(0b0111, 0b1010, 0b1111, 0b0001)[b % 4] for b in range(batch)]
+    kw = dict(aux, allowed_tags=allowed)
+    check(tk, q, 10, kw, what + ": seen ids + allowed_tags", seen_of(tk, q, kw, dev))
+    dense_shared = torch.rand(n, generator=g) < 0.6
+    sparse_shared = torch.zeros(n, dtype=torch.bool)
+    sparse_shared[torch.randperm(n, generator=g)[:1000]] = True
+    per_row = torch.rand(batch, n, generator=g) < 0.6
+    sparse_rows = torch.rand(batch, n, generator=g) < 0.2
+    for name, m in (("dense shared", dense_shared), ("sparse shared", sparse_shared), ("dense per row", per_row), ("sparse per row", sparse_rows)):
+        mask = E.ItemMask(m.to(dev))
+        kw = dict(aux, item_mask=mask)
+        if hasattr(tk, "_masked") and sparse_ok:
+            assert tk._masked(tk._bind(), mask, count=False) == name.split()[0], name
+        check(tk, q, 10, kw, f"{what}: seen ids + {name} mask", seen_of(tk, q, kw, dev))
+    tk.hide_items(torch.randperm(n, generator=g)[: n // 3])
+    check(tk, q, 10, aux, what + ": hidden set", seen_of(tk, q, aux, dev))
+    tk.unhide_items(tk.hidden_positions())
+
+
+@pytest.mark.parametrize("mode", ["dense", "default"])
+@pytest.mark.parametrize("layout", ["a", "c forced fallback"])
+def test_call_surfaces(layout, mode, dev):
+    g = torch.Generator().manual_seed(85)
+    with torch.inference_mode():
+        tk, q, aux, X, ids = setup(dev, 5, **({"exact_mode": "dense"} if mode == "dense" else {}))
+        if mode == "dense":
+            dense_mode(tk)
+        if layout == "a":
+            tk.set_item_groups(layout_a(N, g).to(dev))
+        else:
+            tk.set_item_groups(layout_c(tk.all_logits(q, **aux)[0], N, g).to(dev))
+            tk.COLLAPSE_MAX_DEPTH = 64
+        surfaces(tk, q, aux, dev, layout)
+        if layout != "a":
+            assert tk.collapse_stats()["fallbacks"] > 0
+
+
+ROUTES = {
+    "proved": dict(n=16384 + 37, batch=32),
+    "f16x3": dict(precision="f16x3"),
+    "c4_16x16x64": dict(name="c4_16x16x64"),
+    "generic g_4x4x64": dict(name="g_4x4x64"),
+    "chunked": dict(),
+}
+
+
+@pytest.mark.parametrize("route", sorted(ROUTES))
+def test_routes(route, dev):
+    g = torch.Generator().manual_seed(86)
+    with torch.inference_mode():
+        spec = dict(ROUTES[route])
+        batch, n = spec.pop("batch", 5), spec.get("n", N)
+        tk, q, aux, X, ids = setup(dev, batch, **spec)
+        if route == "chunked":
+            tk.CHUNK_ITEMS, tk.MAX_LOGIT_BYTES = 1024, batch * 1024 * 4
+        if route == "generic g_4x4x64":
+            assert tk._bind().route == "generic"
+        tk.set_item_groups(layout_a(n, g).to(dev))
+        proved = tk.stats().get("proved_calls", 0)
+        for k in (1, 10, 200):
+            check(tk, q, k, aux, f"{route}, k = {k}")
+        if route == "proved":      # the ranked top-D came from the proved flow, and its verdicts cleared
+            st = tk.stats()
+            assert tk.exact_mode == "proved" and tk._bind().exact is not None
+            assert st["proved_calls"] > proved and st["bound_violations"] == 0, st
+        seen = seen_of(tk, q, aux, dev)
+        both_paths(tk, q, 10, aux, f"{route}: seen ids", seen)
+        tk.set_item_groups(layout_c(tk.all_logits(q, **aux)[0], n, g).to(dev))
+        tk.COLLAPSE_MAX_DEPTH = 64
+        check(tk, q, 10, aux, f"{route}: (c), forced fallback", seen_of(tk, q, aux, dev))
+        assert tk.collapse_stats()["fallbacks"] >= 2
+
+
+def test_mips(dev):
+    g = torch.Generator().manual_seed(87)
+    with torch.inference_mode():
+        X = torch.randn(N, 48, generator=g).to(dev)
+        ids = U.ids_of(N, dev)
+        q = torch.randn(5, 48, generator=g).to(dev)
+        tk = rails_amd.MIPSBruteForceTopK(X.clone().unsqueeze(0), ids.clone().unsqueeze(0))
+        plain = tk(q, k=10)
+        tk.set_item_groups(layout_a(N, g).to(dev))
+        for k in (1, 10, 200):
+            both_paths(tk, q, k, {}, f"mips, k = {k}")
+        surfaces(tk, q, {}, dev, "mips (a)")
+        U.same(tk(q, k=10), plain, "mips: plain call with groups set")
+        tk.set_item_groups(layout_c(tk._index.score(q)[0], N, g).to(dev))
+        tk.COLLAPSE_MAX_DEPTH = 64
+        surfaces(tk, q, {}, dev, "mips (c), forced fallback")
+        assert tk.collapse_stats()["fallbacks"] > 0
+
+
+APPROX = {
+    "avg": lambda mol, x, i: rails_amd.MoLAvgTopK(mol, x, i, avg_top_k=256),
+    "naive": lambda mol, x, i: rails_amd.MoLNaiveTopK(mol, x, i, k_per_group=5),
+    "comb": lambda mol, x, i: rails_amd.MoLCombTopK(mol, x, i, avg_top_k=256, k_per_group=5),
+}
+
+
+@pytest.mark.parametrize("min_items", [0, 1 << 62])
+@pytest.mark.parametrize("kind", sorted(APPROX))
+def test_approximate_modules_collapse_their_own_ranking(kind, min_items, dev):
+    g = torch.Generator().manual_seed(88)
+    with torch.inference_mode():
+        fx = Fixture("c3_books")
+        mol = build_module(fx.cfg, fx.weights, dev)
+        X, ids = U.table(fx.cfg, N, 7, dev), U.ids_of(N, dev)
+        q, aux = O.synthetic_queries(fx.cfg, 5, seed=5).to(dev), aux_of(fx.cfg, 5, dev)
+        tk = APPROX[kind](mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0))
+        tk.fused_coarse_min_items = tk.fused_component_min_items = min_items
+        ranked_s, ranked_i = tk(q, k=256, **aux)      # all candidates, ranked: MoLAvgTopK's avg_top_k; the union whatever k is
+        plain = tk(q, k=10, **aux)
+        keys = layout_a(N, g)
+        tk.set_item_groups(keys.to(dev))
+        pos_of_id = {int(i): p for p, i in enumerate(ids.cpu().tolist())}
+        cand = rails_amd.CandidateIndex(ids=ids.reshape(1, -1), embeddings=None)
+
+        def want(k, invalid):
+            rows_s, rows_i = [], []
+            for b in range(5):
+                s, i = ranked_s[b].float().cpu(), ranked_i[b].cpu()
+                real = s != -32767.0      # (a masked duplicate of the union is no candidate)
+                order = [pos_of_id[int(x)] for x in i[real].tolist()]
+                by_pos = torch.full((N,), NEG_INF)
+                by_pos[torch.tensor(order)] = s[real]
+                out_s, _, out_i = CR.collapse_walk(by_pos, order, keys, None if invalid is None else invalid[b].cpu(), ids.cpu(), k)
+                if len(out_i) < k:      # fewer than k groups among this row's candidates: the call raises
+                    return None
+                rows_s.append(torch.tensor(out_s))
+                rows_i.append(torch.tensor(out_i))
+            return torch.stack(rows_s), torch.stack(rows_i)
+
+        for k in (1, 10, 200):      # (k = 200 consumes most of a list of 256 to 576 candidates)
+            expected = want(k, None)
+            if expected is None:
+                with pytest.raises(RuntimeError, match="out of range"):
+                    tk(q, k=k, collapse_groups=True, **aux)
+                continue
+            s, i = tk(q, k=k, collapse_groups=True, **aux)
+            assert s.shape == (5, k) and torch.equal(i.cpu(), expected[1]) and torch.equal(s.float().cpu(), expected[0]), (kind, k)
+        assert want(10, None) is not None
+        seen = torch.cat([want(3, None)[1], torch.full((5, 58), -9)], dim=1).to(dev)
+        gi, gs, _ = cand.get_top_k_outputs(q, 10, dict(aux, collapse_groups=True), tk, seen)
+        ws, wi = want(10, seen)
+        assert torch.equal(gi.cpu(), wi) and torch.equal(gs.float().cpu(), ws), kind
+        if kind != "naive":
+            h = tk.submit(q, 10, collapse_groups=True, **aux)
+            s, i = tk.result(h)
+            ws, wi = want(10, None)
+            assert torch.equal(i.cpu(), wi) and torch.equal(s.float().cpu(), ws), kind
+        U.same(tk(q, k=10, **aux), plain, f"{kind}: plain call with groups set")
+        tk.set_item_groups(torch.zeros(N, dtype=torch.int32, device=dev))
+        with pytest.raises(RuntimeError, match="out of range"):
+            tk(q, k=2, collapse_groups=True, **aux)
+        assert tk.collapse_stats()["fallbacks"] == 0 and tk.collapse_stats()["walk_redos"] == 0
+
+
+def test_groups_follow_a_chain_of_edits(dev):
+    """update -> append (new items -1, then keyed by positions) -> remove across a tile boundary -> hide -> by-id remove -> compact; after each
+    step the collapsed call equals a fresh module's of the resulting table, ids and key row, and item_groups is that row."""
+    g = torch.Generator().manual_seed(89)
+    with torch.inference_mode():
+        tk, q, aux, X, ids = setup(dev, 5)
+        cfg = Fixture("c3_books").cfg
+        mol = tk.mol_module
+        keys = layout_a(N, g).to(torch.int32).to(dev)
+        tk.set_item_groups(keys)
+        seen = seen_of(tk, q, aux, dev)
+        cand = lambda t: rails_amd.CandidateIndex(ids=t._ids_flat.reshape(1, -1), embeddings=None)      # noqa: E731
+
+        def agree(step, hidden=None):
+            assert torch.equal(tk.item_groups, keys) and tk.num_items == X.shape[0] == keys.numel(), step
+            fresh = rails_amd.MoLBruteForceTopK(mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0))
+            fresh.set_item_groups(keys)
+            if hidden is not None:
+                fresh.hide_items(hidden)
+            for k in (10, 200):
+                U.same(tk(q, k=k, collapse_groups=True, **aux), fresh(q, k=k, collapse_groups=True, **aux), f"{step}: forward, k = {k}")
+            kw = dict(aux, collapse_groups=True)
+            U.same(cand(tk).get_top_k_outputs(q, 10, kw, tk, seen)[:2], cand(fresh).get_top_k_outputs(q, 10, kw, fresh, seen)[:2], f"{step}: seen ids")
+            check(tk, q, 10, aux, f"{step}: against the reference", seen)
+
+        pos = U.positions_for(N, g, extra=100).to(dev)                       # update: the keys stay
+        rows = U.table(cfg, pos.numel(), 21, dev, first=5_000_000)
+        tk.update_items(pos, rows)
+        X[pos] = rows
+        agree("update")
+        new_rows, new_ids = U.table(cfg, 40, 22, dev, first=6_000_000), U.ids_of(40, dev, first=N + 1000)      # append: -1, then keyed by positions
+        tk.append_items(new_rows, new_ids)
+        X, ids, keys = torch.cat([X, new_rows]), torch.cat([ids, new_ids]), torch.cat([keys, torch.full((40,), -1, dtype=torch.int32, device=dev)])
+        agree("append")
+        some = torch.arange(N, N + 20)
+        tk.set_item_groups(torch.arange(20, dtype=torch.int64, device=dev) % 3, positions=some)
+        keys[some.to(dev)] = (torch.arange(20, device=dev) % 3).to(torch.int32)
+        agree("set_item_groups(..., positions)")
+
+        def removed(gone):
+            nonlocal X, ids, keys
+            n = X.shape[0]
+            holes, movers = rails_amd.topk_modules.removal_plan(gone.cpu(), n)
+            n_new = n - gone.numel()
+            X2, ids2, keys2 = X[:n_new].clone(), ids[:n_new].clone(), keys[:n_new].clone()
+            X2[holes.to(dev)], ids2[holes.to(dev)], keys2[holes.to(dev)] = X[movers.to(dev)], ids[movers.to(dev)], keys[movers.to(dev)]
+            X, ids, keys = X2, ids2, keys2
+
+        n = X.shape[0]
+        gone = torch.cat([torch.arange(4090, 4102), torch.randperm(4000, generator=g)[:50], torch.tensor([n - 1, n - 3])])      # remove across a tile boundary
+        tk.remove_items(gone)
+        removed(gone)
+        agree("remove")
+        hide = torch.randperm(X.shape[0], generator=g)[:300]                   # hide
+        tk.hide_items(hide)
+        agree("hide", hide)
+        by_id = ids[torch.randperm(X.shape[0], generator=g)[:30].to(dev)]
+        by_id = by_id[~torch.isin(by_id, ids[hide.to(dev)])]                   # by-id remove (of visible items)
+        gone = tk.positions_of(by_id).cpu()
+        hidden_ids = ids[hide.to(dev)]
+        tk.remove_items_by_id(by_id)
+        removed(gone)
+        agree("remove by id", tk.positions_of(hidden_ids).cpu())
+        gone = tk.hidden_positions().cpu()                                     # compact
+        tk.compact()
+        removed(gone)
+        agree("compact")
+
+
+def test_refusals_come_before_any_launch(dev):
+    g = torch.Generator().manual_seed(90)
+    with torch.inference_mode():
+        fx = Fixture("c3_books")
+        mol = build_module(fx.cfg, fx.weights, dev)
+        X, ids = U.table(fx.cfg, N, 7, dev), U.ids_of(N, dev)
+        q, aux = O.synthetic_queries(fx.cfg, 5, seed=5).to(dev), aux_of(fx.cfg, 5, dev)
+        tk = rails_amd.MoLBruteForceTopK(mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0))
+        cand = rails_amd.CandidateIndex(ids=ids.reshape(1, -1), embeddings=None)
+        with pytest.raises(ValueError, match="without groups"):
+            tk(q, k=3, collapse_groups=True, **aux)
+        with pytest.raises(ValueError, match="without groups"):
+            cand.get_top_k_outputs(q, 3, dict(aux, collapse_groups=True), tk, ids[:5].reshape(5, 1))
+        keys = layout_a(N, g)
+        for bad, kw in ((keys.float().to(dev), {}), (keys[:-1].to(dev), {}), (keys, {}), (keys.to(dev).reshape(1, -1), {}),
+                        (torch.full((N,), -2, device=dev), {}), (torch.full((N,), (1 << 31) - 1, device=dev), {}),
+                        (keys[:3].to(dev), {"positions": torch.tensor([0, 1, 1])}), (keys[:3].to(dev), {"positions": torch.tensor([0, 1, N])}),
+                        (keys[:3].to(dev), {"positions": torch.tensor([0, 1])})):
+            with pytest.raises(ValueError):
+                tk.set_item_groups(bad, **kw)
+            assert tk.item_groups is None
+        tk.set_item_groups(keys.to(dev))
+        for call, name in ((lambda: tk.all_logits(q, collapse_groups=True, **aux), "all_logits"),
+                           (lambda: APPROX["avg"](mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0)).topk_ids(q, collapse_groups=True, **aux), "topk_ids")):
+            with pytest.raises(NotImplementedError, match=name + " takes no collapse_groups"):
+                call()
+        calls = tk.collapse_stats()["calls"]
+        with pytest.raises(NotImplementedError, match="k <= 512"):      # the limits of the exact fallback, before the first walk
+            tk(q, k=513, collapse_groups=True, **aux)
+        with pytest.raises(NotImplementedError, match="seen ids"):
+            cand.get_top_k_outputs(q, 3, dict(aux, collapse_groups=True), tk, torch.zeros((5, 4097), dtype=torch.int64, device=dev))
+        wide = rails_amd.MoLNaiveTopK(mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0), k_per_group=300)      # a union of 19 200 candidates
+        wide.set_item_groups(keys.to(dev))
+        with pytest.raises(NotImplementedError, match="19200"):
+            wide(q, k=3, collapse_groups=True, **aux)
+        assert tk.collapse_stats()["calls"] == calls and wide.collapse_stats()["calls"] == 0 and wide._comp_table is None      # (nothing launched)
+        tk.clear_item_groups()
+        ivf = rails_amd.MoLNaiveTopK(mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0), k_per_group=5, use_faiss=True, nlist=8)
+        with pytest.raises(NotImplementedError, match="IVF"):
+            ivf.set_item_groups(keys.to(dev))
+        with pytest.raises(NotImplementedError, match="IVF"):
+            ivf(q, k=3, collapse_groups=True, **aux)
+        assert ivf._ivf is None      # (nothing was built, nothing launched)
+        naive = APPROX["naive"](mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0))
+        naive.set_item_groups(keys.to(dev))
+        for call in (naive.local_candidates, APPROX["comb"](mol, X.clone().unsqueeze(0), ids.clone().unsqueeze(0)).coarse_candidates):
+            with pytest.raises(NotImplementedError, match="collapse_groups"):
+                call(q, collapse_groups=True, **aux)
+        from rails_amd import sharded
+
+        class OneRank(sharded.ShardedMoLAvgTopK):
+            def __init__(self):      # (no process group: the refusal comes before anything of the wrapper is touched)
+                torch.nn.Module.__init__(self)
+
+        for call in (lambda w: w.forward(q, 3, collapse_groups=True), lambda w: w.forward_filtered(q, 4, ids[:5].reshape(5, 1), 3, collapse_groups=True)):
+            with pytest.raises(NotImplementedError, match="OneRank takes no collapse_groups"):
+                call(OneRank())
+
+
+# ---- the kernels on their own ----------------------------------------------------------------------------------------------------------
+def walk(scores, positions, ranks, k, ids, invalid, dev):
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = E.topk_collapse(scores.to(dev), positions.to(dev), ranks.to(torch.int32).to(dev), k, None if ids is None else ids.to(dev),
+                          None if invalid is None else invalid.to(dev), flag)
+    return tuple(t.cpu() for t in out) + (int(flag.item()),)
+
+
+@pytest.mark.parametrize("k", [1, 512])
+@pytest.mark.parametrize("depth", [1, 63, 64, 65, 4096, 8192, 16384])      # (8 192 and 16 384: the widest in-LDS sorts, the launch's LDS ceiling)
+def test_walk_kernel_on_hand_built_lists(depth, k, dev):
+    g = torch.Generator().manual_seed(91)
+    n = 20000
+    rows = 3
+    ids = torch.randperm(n, generator=g) * 5 + 2
+    positions = torch.stack([torch.randperm(n, generator=g)[:depth] for _ in range(rows)])
+    scores = torch.sort(torch.randint(-50, 50, (rows, depth), generator=g).float(), dim=1, descending=True).values
+    layouts = {
+        "one group": torch.zeros(n, dtype=torch.int64),
+        "all distinct": torch.randperm(n, generator=g),
+        "groups of ~3": torch.randint(0, n // 3, (n,), generator=g),
+    }
+    for name, ranks in layouts.items():
+        first = torch.stack([ids[positions[r, : min(depth, 40)]] for r in range(rows)])      # seen ids hit the first occurrences
+        pad = torch.full((rows, 40 - first.shape[1]), -3, dtype=torch.int64)
+        for invalid in (None, torch.cat([first, pad], dim=1)[:, torch.randperm(40, generator=g)], torch.cat([first, pad, pad, pad, pad, pad, pad, pad], dim=1)):
+            s, p, i, counts, flag = walk(scores, positions, ranks, k, ids, invalid, dev)
+            short = False
+            for r in range(rows):
+                by_pos = torch.full((n,), NEG_INF)
+                by_pos[positions[r]] = scores[r]
+                ws, wp, wi = CR.collapse_walk(by_pos, positions[r], ranks, None if invalid is None else invalid[r], ids, depth)
+                assert counts[r] == len(wp), (name, r)
+                m = min(k, len(wp))
+                short |= len(wp) < k
+                assert p[r, :m].tolist() == wp[:m] and i[r, :m].tolist() == wi[:m] and s[r, :m].tolist() == ws[:m], (name, r)
+                assert bool((p[r, m:] == -1).all()) and bool((i[r, m:] == -1).all()) and bool((s[r, m:] == NEG_INF).all()), (name, r)
+            assert flag == int(short), name
+    # entries that are not eligible by themselves: a position outside the corpus, a score of -inf
+    if depth >= 63:
+        ranks = layouts["all distinct"]
+        sc, ps = scores.clone(), positions.clone()
+        sc[:, 5], ps[:, 7], ps[:, 9] = NEG_INF, -1, n
+        s, p, i, counts, flag = walk(sc, ps, ranks, 1, None, None, dev)
+        assert counts.tolist() == [depth - 3] * rows and flag == 0 and torch.equal(p[:, 0], ps[:, 0]) and torch.equal(i, p)
+
+
+def scatter_max_reference(scores, ranks, groups, first_item, ids, invalid):
+    """the key table by torch: integer keys (orderable(score), ~position) as non-negative int64 pairs, scatter-max per (row, rank)"""
+    rows, n = scores.shape
+    bits = scores.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    ordered = torch.where(bits >= 1 << 31, 0xFFFFFFFF - bits, bits + (1 << 31))
+    pos = torch.arange(first_item, first_item + n)
+    ok = torch.isfinite(scores)
+    if invalid is not None:
+        ok &= ~(ids[pos].reshape(1, n, 1) == invalid.reshape(rows, 1, -1)).any(dim=2)
+    # (the 64-bit key does not fit a signed int64 compare: rank the (score, position) pairs by a 2^32-scaled double-free route -- two scatters)
+    best_s = torch.full((rows, groups), -1, dtype=torch.int64).scatter_reduce(1, ranks[pos].to(torch.int64).expand(rows, n), torch.where(ok, ordered, -1), "amax")
+    at_best = ok & (ordered == best_s.gather(1, ranks[pos].to(torch.int64).expand(rows, n)))
+    best_p = torch.full((rows, groups), 1 << 40, dtype=torch.int64).scatter_reduce(1, ranks[pos].to(torch.int64).expand(rows, n),
+                                                                                 torch.where(at_best, pos.expand(rows, n), 1 << 40), "amin")
+    return best_s, best_p      # (-1, 2^40) where the group has no eligible item
+
+
+@pytest.mark.parametrize("groups_kind", ["G = 1", "G = N", "groups of ~5"])
+def test_group_max_and_topk_keys_against_a_scatter_max_of_integer_keys(groups_kind, dev):
+    g = torch.Generator().manual_seed(92)
+    rows, n_total = 4, 9000 + 37
+    ranks = {"G = 1": torch.zeros(n_total, dtype=torch.int32), "G = N": torch.randperm(n_total, generator=g).to(torch.int32),
+             "groups of ~5": torch.randint(0, n_total // 5, (n_total,), generator=g).to(torch.int32)}[groups_kind]
+    groups = int(ranks.max()) + 1
+    ids = torch.randperm(n_total, generator=g) * 3 + 1
+    scores = torch.randint(-3, 4, (rows, n_total), generator=g).float()      # small integers: ties abound
+    scores[:, torch.randperm(n_total, generator=g)[:500]] = NEG_INF         # -inf columns
+    scores[1, :] = NEG_INF                                                  # ... and a row with nothing eligible
+    invalid = ids[torch.randint(0, n_total, (rows, 61), generator=g)]
+    for inv in (None, invalid):
+        table = torch.full((rows, groups), -1, dtype=torch.int64, device=dev)      # (garbage: the first chunk's launch clears it)
+        cuts = (0, 4096 + 5, n_total)                                           # two chunks: a first_item offset that is no multiple of anything
+        for lo, hi in zip(cuts, cuts[1:]):
+            E.scores_group_max(scores[:, lo:hi].contiguous().to(dev), ranks.to(dev), table, first_item=lo, clear=lo == 0, ids=ids.to(dev),
+                               invalid_ids=None if inv is None else inv.to(dev))
+        best_s, best_p = scatter_max_reference(scores, ranks, groups, 0, ids, inv)
+        t = table.cpu()
+        hi_word, lo_word = (t >> 32) & 0xFFFFFFFF, t & 0xFFFFFFFF
+        empty = best_s < 0
+        assert bool((t[empty] == 0).all()) and bool((hi_word[~empty] == best_s[~empty]).all()) and bool((0xFFFFFFFF - lo_word[~empty] == best_p[~empty]).all())
+        for k in (1, 10, 512):
+            s, p, i, counts = (x.cpu() for x in E.topk_keys(table, k, ids.to(dev)))
+            assert counts.tolist() == (~empty).sum(dim=1).tolist()
+            for r in range(rows):
+                live = torch.nonzero(~empty[r]).reshape(-1)
+                order = sorted(live.tolist(), key=lambda c: (-int(best_s[r, c]), int(best_p[r, c])))[:k]
+                m = len(order)
+                want_p = [int(best_p[r, c]) for c in order]
+                assert p[r, :m].tolist() == want_p and i[r, :m].tolist() == ids[want_p].tolist() if m else True
+                assert s[r, :m].tolist() == scores[r, want_p].tolist() if m else True
+                assert bool((p[r, m:] == -1).all()) and bool((i[r, m:] == -1).all()) and bool((s[r, m:] == NEG_INF).all())
