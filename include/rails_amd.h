@@ -50,6 +50,8 @@ extern "C" {
  * item-tag entries rails_item_tags_effective / rails_item_tags_count / rails_item_mask_from_tags / rails_scores_mask_tags / rails_mol_coarse_topk_tagged /
  * rails_mol_component_topk_tagged / rails_mol_scan_plan and the filtered-list entries rails_ivf_list_words / rails_ivf_list_counts /
  * rails_ivf_plan_filtered / rails_ivf_search_filtered and the group-collapse entries rails_topk_collapse / rails_scores_group_max / rails_topk_keys
+ * and the generic route's candidate entries rails_mol_generic_score_indexed / rails_mol_generic_table_width / rails_mol_generic_coarse_build /
+ * rails_mol_generic_coarse_update / rails_mol_generic_component_build / rails_mol_generic_component_update / rails_mol_generic_eq_pad
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -255,6 +257,28 @@ int rails_mol_generic_score_dense(const rails_mol_shape* shape, const float* gat
 /* per-row candidates: candidate j of row b is item b * n_cand + j of `cand_index` (a generic index of batch * n_cand items; any n_cand) */
 int rails_mol_generic_score_candidates(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch,
                                        const float* cand_index, int64_t n_cand, float* logits, int64_t ld, const int32_t* run_if, void* stream);
+/* per-row candidates scored IN PLACE on the shared generic index (rails_mol_score_indexed / rails_mol_score_indexed_rows for this route; the
+ * index is row-major already): candidate j of row b is item positions[b * n_cand + j] of `index`, clamped into [0, n_items); any n_cand >= 1.
+ * counts: NULL, or per-row live counts (int32 on the device): only logits[b * ld + j] for j < counts[b] are written, tiles of 32 candidates
+ * past the count are skipped.  A pair's logit has the bits rails_mol_generic_score_dense gives it. */
+int rails_mol_generic_score_indexed(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch, const float* index,
+                                    int64_t n_items, const int64_t* positions, int64_t n_cand, const int32_t* counts, float* logits, int64_t ld,
+                                    const int32_t* run_if, void* stream);
+/* The bf16 candidate tables of the two-pass algorithms from the generic index.  rails_mol_generic_table_width: the smallest of 32 / 64 / 128
+ * that is >= dot_product_dimension, 0 for d > 128 (no table; answered without a device).  Rows have that many columns, the columns d .. width
+ * exact zeros; the real columns carry rails_mol_coarse_build's / rails_mol_component_build's arithmetic, operation for operation.  The coarse
+ * table is (n_items, width), the component table item-group-major (P_X, n_items, width); the scans rails_mol_coarse_* / rails_mol_component_*
+ * run on them under a copy of the shape with dot_product_dimension = width, Eq padded alike (rails_mol_generic_eq_pad: (rows, d) fp32 ->
+ * (rows, width), zeros behind; rows = batch * P_Q).  The update forms rewrite rows positions[0 .. n_new) (those outside [0, n_items) are
+ * skipped) of a table of n_items rows from the index, which holds the new items already. */
+int32_t rails_mol_generic_table_width(const rails_mol_shape* shape);
+int rails_mol_generic_coarse_build(const rails_mol_shape* shape, const float* index, int64_t n_items, void* table, void* stream);
+int rails_mol_generic_coarse_update(const rails_mol_shape* shape, const float* index, const int64_t* positions, int64_t n_new, void* table,
+                                    int64_t n_items, void* stream);
+int rails_mol_generic_component_build(const rails_mol_shape* shape, const float* index, int64_t n_items, void* table, void* stream);
+int rails_mol_generic_component_update(const rails_mol_shape* shape, const float* index, const int64_t* positions, int64_t n_new, void* table,
+                                       int64_t n_items, void* stream);
+int rails_mol_generic_eq_pad(const rails_mol_shape* shape, const float* eq, int64_t rows, float* out, void* stream);
 /* Per-row candidates scored IN PLACE: logits[b][j] = MoL(query b, item positions[b][j]) with the item operands read straight from the
  * shared index -- rails_mol_index_gather + rails_mol_score_candidates without the gathered copy and its launch (same arithmetic per
  * pair, same bits).  Exact-fp32 shapes on the independent-wave shell (rails_mol_score_indexed_supported != 0); the 256-logit shape

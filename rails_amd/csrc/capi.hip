@@ -564,6 +564,80 @@ int rails_mol_generic_score_candidates(const rails_mol_shape* s, const float* ga
   return generic_score_common(s, gate_pack, query_pack, batch, cand_index, n_cand, logits, ld, 1, run_if, stream, "generic_score_candidates");
 }
 
+int rails_mol_generic_score_indexed(const rails_mol_shape* s, const float* gate_pack, const float* query_pack, int32_t batch, const float* index,
+                                    int64_t n_items, const int64_t* positions, int64_t n_cand, const int32_t* counts, float* logits, int64_t ld,
+                                    const int32_t* run_if, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (batch < 0 || n_items < 0 || n_cand < 0) { set_error("generic_score_indexed: negative size"); return RAILS_EINVAL; }
+  if (batch == 0 || n_cand == 0) return RAILS_OK;
+  if (n_items == 0) { set_error("generic_score_indexed: candidates of an empty index"); return RAILS_EINVAL; }
+  if (!gate_pack || !query_pack || !index || !positions || !logits) { set_error("generic_score_indexed: NULL pointer"); return RAILS_EINVAL; }
+  if (ld < n_cand) { set_error("generic_score_indexed: ld (%lld) < n_cand (%lld)", (long long)ld, (long long)n_cand); return RAILS_EINVAL; }
+  const int cu = compute_units();
+  if (cu <= 0) { set_error("generic_score_indexed: no HIP device"); return RAILS_ELAUNCH; }
+  GenericScoreArgs a{};
+  a.wpack = gate_pack; a.qpack = query_pack; a.ipack = index; a.logits = logits; a.ld = ld; a.n_items = n_cand; a.B = batch;
+  a.per_row = 0; a.run_if = run_if; a.cand_pos = positions; a.cand_count = counts; a.index_items = n_items;
+  const int r = generic_score(*s, a, cu, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "generic_score_indexed");
+}
+
+// ---- the bf16 candidate tables from the generic index (mol_coarse.hip) ----
+int32_t rails_mol_generic_table_width(const rails_mol_shape* s) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return 0;
+  const int w = gen_table_width(*s);
+  if (w == 0) set_error("the generic route's candidate tables take dot_product_dimension <= 128 (the widest bf16 scan), got %d", s->dot_product_dimension);
+  return w;
+}
+
+static int generic_table_check(const rails_mol_shape* s, const float* index, const int64_t* positions, bool update, int64_t m, void* table, int64_t n_items,
+                               const char* what) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (rails_mol_generic_table_width(s) == 0) return RAILS_ENOTSUP;
+  if (m < 0 || n_items < 0) { set_error("%s: negative size", what); return RAILS_EINVAL; }
+  if (m > 0 && (!index || !table || (update && !positions))) { set_error("%s: NULL pointer", what); return RAILS_EINVAL; }
+  return RAILS_OK;
+}
+
+int rails_mol_generic_coarse_build(const rails_mol_shape* s, const float* index, int64_t n_items, void* table, void* stream) {
+  const int c = generic_table_check(s, index, nullptr, false, n_items, table, n_items, "generic_coarse_build");
+  if (c != RAILS_OK || n_items == 0) return c;
+  return fail(generic_coarse_table(*s, index, nullptr, n_items, table, n_items, (hipStream_t)stream), "generic_coarse_build");
+}
+
+int rails_mol_generic_coarse_update(const rails_mol_shape* s, const float* index, const int64_t* positions, int64_t n_new, void* table, int64_t n_items,
+                                    void* stream) {
+  const int c = generic_table_check(s, index, positions, true, n_new, table, n_items, "generic_coarse_update");
+  if (c != RAILS_OK || n_new == 0) return c;
+  return fail(generic_coarse_table(*s, index, positions, n_new, table, n_items, (hipStream_t)stream), "generic_coarse_update");
+}
+
+int rails_mol_generic_component_build(const rails_mol_shape* s, const float* index, int64_t n_items, void* table, void* stream) {
+  const int c = generic_table_check(s, index, nullptr, false, n_items, table, n_items, "generic_component_build");
+  if (c != RAILS_OK || n_items == 0) return c;
+  return fail(generic_component_table(*s, index, nullptr, n_items, table, n_items, (hipStream_t)stream), "generic_component_build");
+}
+
+int rails_mol_generic_component_update(const rails_mol_shape* s, const float* index, const int64_t* positions, int64_t n_new, void* table, int64_t n_items,
+                                       void* stream) {
+  const int c = generic_table_check(s, index, positions, true, n_new, table, n_items, "generic_component_update");
+  if (c != RAILS_OK || n_new == 0) return c;
+  return fail(generic_component_table(*s, index, positions, n_new, table, n_items, (hipStream_t)stream), "generic_component_update");
+}
+
+int rails_mol_generic_eq_pad(const rails_mol_shape* s, const float* eq, int64_t rows, float* out, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (rails_mol_generic_table_width(s) == 0) return RAILS_ENOTSUP;
+  if (rows < 0) { set_error("generic_eq_pad: rows < 0"); return RAILS_EINVAL; }
+  if (rows == 0) return RAILS_OK;
+  if (!eq || !out) { set_error("generic_eq_pad: NULL pointer"); return RAILS_EINVAL; }
+  return fail(generic_eq_pad(*s, eq, rows, out, (hipStream_t)stream), "generic_eq_pad");
+}
+
 size_t rails_mips_index_floats(int32_t dim, int64_t n_items) {
   if (dim <= 0 || n_items < 0) return 0;
   return (size_t)num_tiles(n_items) * 32 * (size_t)((dim + 7) / 8 * 8);

@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "mol_kernels.h"
+#include "mol_generic.h"
 #include <utility>
 #include "mol_layout.h"
 #include "topk_keys.h"
@@ -59,6 +60,47 @@ __global__ void coarse_build_kernel(const float* __restrict__ ipack, int64_t n, 
 __global__ void coarse_update_kernel(const float* __restrict__ src, int src_in_place, const int64_t* __restrict__ pos, int64_t m, int64_t n, int PQ, int PX, int d,
                                      unsigned short* __restrict__ table) {
   coarse_table_body<true>(src, src_in_place, pos, m, n, PQ, PX, d, table);
+}
+
+// The same table from the generic route's row-major index ([P_X][dp] Ex then gi per item, `item_floats` floats; mol_generic.h): rows of
+// `width` = gen_table_width columns, the real columns by the arithmetic above, operation for operation, the columns d .. width exact zeros.
+// One thread per (work item, column); the update form's item is the row's own (the index is fp32 and already updated).
+template <bool AT_POSITIONS>
+__device__ __forceinline__ void generic_coarse_table_body(const float* __restrict__ src, const int64_t* __restrict__ pos, int64_t m, int64_t n, int PX, int d, int dp,
+                                                          int width, int64_t item_floats, unsigned short* __restrict__ table) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m * width) return;
+  const int64_t u = i / width;
+  const int dd = (int)(i - u * width);
+  int64_t item, row;
+  if (!table_work_item<AT_POSITIONS>(u, pos, 1, n, 0, item, row)) return;
+  unsigned short v = 0;
+  if (dd < d) {
+    const float* ex = src + item * item_floats + dd;
+    float acc = 0.0f;
+    for (int g = 0; g < PX; ++g) acc += bf16_rn(ex[g * dp]);
+    v = bf16_bits(bf16_rn(acc) / (float)PX);
+  }
+  table[row * width + dd] = v;
+}
+__global__ void generic_coarse_build_kernel(const float* __restrict__ ipack, int64_t n, int PX, int d, int dp, int width, int64_t item_floats,
+                                            unsigned short* __restrict__ table) {
+  generic_coarse_table_body<false>(ipack, nullptr, n, n, PX, d, dp, width, item_floats, table);
+}
+__global__ void generic_coarse_update_kernel(const float* __restrict__ ipack, const int64_t* __restrict__ pos, int64_t m, int64_t n, int PX, int d, int dp, int width,
+                                             int64_t item_floats, unsigned short* __restrict__ table) {
+  generic_coarse_table_body<true>(ipack, pos, m, n, PX, d, dp, width, item_floats, table);
+}
+
+int generic_coarse_table(const Shape& s, const float* ipack, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream) {
+  const int PX = s.item_dot_product_groups, d = s.dot_product_dimension, dp = gen_dp(s), width = gen_table_width(s);
+  const int64_t total = m * width;
+  if (total <= 0) return kOk;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  unsigned short* t = static_cast<unsigned short*>(table);
+  if (positions) hipLaunchKernelGGL(generic_coarse_update_kernel, grid, dim3(256), 0, stream, ipack, positions, m, n, PX, d, dp, width, gen_item_floats(s), t);
+  else hipLaunchKernelGGL(generic_coarse_build_kernel, grid, dim3(256), 0, stream, ipack, m, PX, d, dp, width, gen_item_floats(s), t);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
 // ---- the coarse scan (bf16 MFMA) ------------------------------------------------------------------------------
@@ -1250,6 +1292,40 @@ int component_update(const Shape& s, const float* src, int src_in_place, const i
   unsigned short* t = static_cast<unsigned short*>(table);
   if (positions) hipLaunchKernelGGL(component_update_kernel, grid, dim3(256), 0, stream, src, src_in_place, positions, m, PQ, PX, d, n_total, t);
   else hipLaunchKernelGGL(component_build_kernel, grid, dim3(256), 0, stream, src, m, PQ, PX, d, n_total, first, t);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+// The component table from the generic route's row-major index (as generic_coarse_table_body): (P_X, n_total, width), pad columns zeros.
+template <bool AT_POSITIONS>
+__device__ __forceinline__ void generic_component_table_body(const float* __restrict__ src, const int64_t* __restrict__ pos, int64_t m, int PX, int d, int dp, int width,
+                                                             int64_t item_floats, int64_t n_total, unsigned short* __restrict__ table) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per_item = PX * width;
+  if (i >= m * per_item) return;
+  const int64_t u = i / per_item;
+  const int rem = (int)(i - u * per_item);
+  const int g = rem / width, dd = rem - g * width;
+  int64_t item, row;
+  if (!table_work_item<AT_POSITIONS>(u, pos, 1, n_total, 0, item, row)) return;
+  table[((int64_t)g * n_total + row) * width + dd] = dd < d ? bf16_bits(src[item * item_floats + g * dp + dd]) : (unsigned short)0;
+}
+__global__ void generic_component_build_kernel(const float* __restrict__ ipack, int64_t n, int PX, int d, int dp, int width, int64_t item_floats,
+                                               unsigned short* __restrict__ table) {
+  generic_component_table_body<false>(ipack, nullptr, n, PX, d, dp, width, item_floats, n, table);
+}
+__global__ void generic_component_update_kernel(const float* __restrict__ ipack, const int64_t* __restrict__ pos, int64_t m, int PX, int d, int dp, int width,
+                                                int64_t item_floats, int64_t n_total, unsigned short* __restrict__ table) {
+  generic_component_table_body<true>(ipack, pos, m, PX, d, dp, width, item_floats, n_total, table);
+}
+
+int generic_component_table(const Shape& s, const float* ipack, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream) {
+  const int PX = s.item_dot_product_groups, d = s.dot_product_dimension, dp = gen_dp(s), width = gen_table_width(s);
+  const int64_t total = m * PX * width;
+  if (total <= 0) return kOk;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  unsigned short* t = static_cast<unsigned short*>(table);
+  if (positions) hipLaunchKernelGGL(generic_component_update_kernel, grid, dim3(256), 0, stream, ipack, positions, m, PX, d, dp, width, gen_item_floats(s), n, t);
+  else hipLaunchKernelGGL(generic_component_build_kernel, grid, dim3(256), 0, stream, ipack, m, PX, d, dp, width, gen_item_floats(s), t);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

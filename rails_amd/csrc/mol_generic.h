@@ -46,9 +46,27 @@ struct GenericScoreArgs {
   int B;
   int per_row;          // 1: candidate j of row b is item row b * n_items + j
   const int32_t* run_if;
+  // candidates scored in place (the indexed mode): candidate j of row b is item cand_pos[b * n_items + j] of the shared index `ipack` of
+  // index_items items, clamped into it; cand_count (optional): only the first cand_count[b] slots of row b are scored and written
+  const int64_t* cand_pos;
+  const int32_t* cand_count;
+  int64_t index_items;
 };
 int generic_pack_gate_weights(const Shape& s, const Weights& w, float* wpack, hipStream_t stream);
 int generic_index_unpack(const Shape& s, const float* ipack, int64_t n, float* ex, float* gi, hipStream_t stream);
 int generic_score(const Shape& s, const GenericScoreArgs& a, int n_cu, hipStream_t stream);
+
+// The bf16 candidate tables of the two-pass algorithms, cut from the generic index (mol_coarse.hip): rows of gen_table_width(s) columns,
+// the columns d .. width exact zeros, so that the bf16 scans run their d = 32 / 64 / 128 instantiations on them.  0: d > 128, no table.
+inline int gen_table_width(const Shape& s) {
+  const int d = s.dot_product_dimension;
+  return d <= 32 ? 32 : d <= 64 ? 64 : d <= 128 ? 128 : 0;
+}
+// positions == NULL: the build of an n-row table from the n items of `ipack`; else rows positions[0 .. m) of a table of n rows, each from the
+// item of the same position
+int generic_coarse_table(const Shape& s, const float* ipack, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream);
+int generic_component_table(const Shape& s, const float* ipack, const int64_t* positions, int64_t m, void* table, int64_t n, hipStream_t stream);
+// eq (rows, d) fp32 -> out (rows, width) fp32, the columns d .. width zeros
+int generic_eq_pad(const Shape& s, const float* eq, int64_t rows, float* out, hipStream_t stream);
 
 }  // namespace mol

@@ -15,7 +15,8 @@
 //
 // One arithmetic per pair: every contraction visits k in ascending order of its zero-padded axis, the softmax sums run in
 // ascending l per lane half and the two halves are added last (a commutative add), and nothing depends on the lane, the wave,
-// the batch, N, or on whether the pair came from a shared index or per-row candidates: same bits everywhere.
+// the batch, N, or on whether the pair came from a shared index, per-row candidates or positions of the shared index (the indexed
+// mode: the item row of a lane comes from a 64-bit position load at the head of the unit): same bits everywhere.
 // fp32 throughout, precise expf and true divisions.
 #include <hip/hip_runtime.h>
 
@@ -50,7 +51,9 @@ __device__ __forceinline__ float silu_exact(float v) { return v / (1.0f + expf(-
 // cl buffer of a wave: logit l of item x at ((l >> 2) * 32 + x) * 4 + (l & 3): four consecutive logits of an item are one float4
 __device__ __forceinline__ int cl_at(int l, int x) { return ((l >> 2) * 32 + x) * 4 + (l & 3); }
 
-template <int TL, bool RES>
+// IDX: the indexed mode (candidates scored in place on the shared index) -- an instantiation of its own, so that the dense and per-row
+// launches keep their registers; the item row address and the count test are all that differs.
+template <int TL, bool RES, bool IDX = false>
 __global__ __launch_bounds__(kGenThreads) void mol_generic_score_kernel(GenKernelArgs k) {
   MOL_RUN_IF(k.a.run_if);
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -75,101 +78,116 @@ __global__ __launch_bounds__(kGenThreads) void mol_generic_score_kernel(GenKerne
   for (int64_t u = blockIdx.x; u < k.units; u += gridDim.x) {
     const int b = (int)(u % k.a.B);
     const int64_t xi = (u / k.a.B) * kGenBlockItems + wave * 32 + x;
-    const bool valid = xi < k.a.n_items;
-    const int64_t row = (k.a.per_row ? (int64_t)b * k.a.n_items : 0) + (valid ? xi : k.a.n_items - 1);   // clamped: always a real row
+    bool valid = xi < k.a.n_items;
+    bool live = true;                                          // false: this wave's tile is past the row's count -- it only keeps the unit's barriers
+    int64_t row;
+    if constexpr (IDX) {
+      // this lane's item: one 64-bit load ahead of GEMM1, clamped into the index (a slot past the row's end reads the last slot's)
+      const int64_t cnt = k.a.cand_count ? (int64_t)k.a.cand_count[b] : k.a.n_items;
+      live = __builtin_amdgcn_readfirstlane((int)(xi - x < cnt)) != 0;      // (the same for the whole wave: a scalar branch, EXEC stays full)
+      const int64_t p = k.a.cand_pos[(int64_t)b * k.a.n_items + (valid ? xi : k.a.n_items - 1)];
+      row = p < 0 ? 0 : (p < k.a.index_items ? p : k.a.index_items - 1);
+      valid = valid && xi < cnt;
+    } else {
+      row = (k.a.per_row ? (int64_t)b * k.a.n_items : 0) + (valid ? xi : k.a.n_items - 1);   // clamped: always a real row
+    }
     const float* irow = k.a.ipack + row * k.item_floats;
     const float* qrow = k.a.qpack + (int64_t)b * k.query_floats;
 
-    // ---- GEMM1 -> cl in LDS
-    for (int p0 = 0; p0 < PQ; p0 += 32) {
-      const int p = p0 + x;                                  // this lane's A row
-      const float* arow = qrow + (p < PQ ? p : PQ - 1) * dp + 4 * hi;
-      for (int m = 0; m < PX; ++m) {
-        const float* brow = irow + m * dp + 4 * hi;
-        gf32x16 acc = {0};
-        for (int c = 0; c < dp; c += 8) {
-          float4 av = *reinterpret_cast<const float4*>(arow + c);
-          const float4 bv = *reinterpret_cast<const float4*>(brow + c);
-          if (p >= PQ) av = make_float4(0.f, 0.f, 0.f, 0.f);
-          acc = mfma4(av, bv, acc);
-        }
+    if (live) {
+      // ---- GEMM1 -> cl in LDS
+      for (int p0 = 0; p0 < PQ; p0 += 32) {
+        const int p = p0 + x;                                  // this lane's A row
+        const float* arow = qrow + (p < PQ ? p : PQ - 1) * dp + 4 * hi;
+        for (int m = 0; m < PX; ++m) {
+          const float* brow = irow + m * dp + 4 * hi;
+          gf32x16 acc = {0};
+          for (int c = 0; c < dp; c += 8) {
+            float4 av = *reinterpret_cast<const float4*>(arow + c);
+            const float4 bv = *reinterpret_cast<const float4*>(brow + c);
+            if (p >= PQ) av = make_float4(0.f, 0.f, 0.f, 0.f);
+            acc = mfma4(av, bv, acc);
+          }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int pr = p0 + acc_row(r, hi);
-          if (pr < PQ) cl[cl_at(pr * PX + m, x)] = acc[r];
+          for (int r = 0; r < 16; ++r) {
+            const int pr = p0 + acc_row(r, hi);
+            if (pr < PQ) cl[cl_at(pr * PX + m, x)] = acc[r];
+          }
         }
       }
     }
     __syncthreads();
 
-    // ---- pair gate: gqi = W2 silu(W1 cl + b1) + b2
-    gf32x16 out[TL];
+    if (live) {
+      // ---- pair gate: gqi = W2 silu(W1 cl + b1) + b2
+      gf32x16 out[TL];
 #pragma unroll
-    for (int v = 0; v < TL; ++v)
+      for (int v = 0; v < TL; ++v)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) out[v][r] = b2[32 * v + acc_row(r, hi)];
-    for (int t = 0; t < TH; ++t) {
-      gf32x16 h;
+        for (int r = 0; r < 16; ++r) out[v][r] = b2[32 * v + acc_row(r, hi)];
+      for (int t = 0; t < TH; ++t) {
+        gf32x16 h;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) h[r] = b1[32 * t + acc_row(r, hi)];
+        for (int r = 0; r < 16; ++r) h[r] = b1[32 * t + acc_row(r, hi)];
 #pragma unroll
-      for (int c = 0; c < Lp / 8; ++c) h = mfma4(w1((t * (Lp / 8) + c) * 64 + lane), cl4[(2 * c + hi) * 32 + x], h);
+        for (int c = 0; c < Lp / 8; ++c) h = mfma4(w1((t * (Lp / 8) + c) * 64 + lane), cl4[(2 * c + hi) * 32 + x], h);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) h[r] = silu_exact(h[r]);
+        for (int r = 0; r < 16; ++r) h[r] = silu_exact(h[r]);
+#pragma unroll
+        for (int v = 0; v < TL; ++v)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const float4 hv = make_float4(h[4 * g], h[4 * g + 1], h[4 * g + 2], h[4 * g + 3]);
+            out[v] = mfma4(w2(((t * TL + v) * 4 + g) * 64 + lane), hv, out[v]);
+          }
+      }
+
+      // ---- combine + softmax mixture: this lane holds logits l = 32 v + 8 g + 4 hi + j of item x
+      const float* gq = qrow + PQ * dp;
+      const float* gi = irow + PX * dp;
+      float mx = -INFINITY;
 #pragma unroll
       for (int v = 0; v < TL; ++v)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const float4 hv = make_float4(h[4 * g], h[4 * g + 1], h[4 * g + 2], h[4 * g + 3]);
-          out[v] = mfma4(w2(((t * TL + v) * 4 + g) * 64 + lane), hv, out[v]);
+          const int l0 = 32 * v + 8 * g + 4 * hi;
+          const int lc = l0 < k.Lq ? l0 : 0;                    // Lq is a multiple of 4: a float4 inside the row
+          const float4 q4 = *reinterpret_cast<const float4*>(gq + lc);
+          const float4 i4 = *reinterpret_cast<const float4*>(gi + lc);
+          const float qv[4] = {q4.x, q4.y, q4.z, q4.w}, iv[4] = {i4.x, i4.y, i4.z, i4.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float gqi = out[v][4 * g + j];
+            float w;
+            if (k.combine_none) w = (qv[j] + iv[j]) + gqi;
+            else w = silu_exact(__builtin_fmaf(qv[j], iv[j], gqi));
+            out[v][4 * g + j] = w;
+            if (l0 + j < L) mx = fmaxf(mx, w);
+          }
         }
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      float den = 0.0f, num = 0.0f;
+#pragma unroll
+      for (int v = 0; v < TL; ++v)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int l0 = 32 * v + 8 * g + 4 * hi;
+          const float4 c4 = cl4[(8 * v + 2 * g + hi) * 32 + x];
+          const float cv[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float e = l0 + j < L ? expf(out[v][4 * g + j] - mx) : 0.0f;
+            den += e;
+            num = __builtin_fmaf(e, cv[j], num);
+          }
+        }
+      den += __shfl_xor(den, 32, 64);
+      num += __shfl_xor(num, 32, 64);
+      // pi = e / den, then the eval-time renormalisation pi / clamp(sum pi, 1e-6) (similarity_fn.py:42-46)
+      const float rden = 1.0f / den;
+      const float res = (num * rden) / fmaxf(den * rden, 1e-6f);
+      if (valid && hi == 0) k.a.logits[(int64_t)b * k.a.ld + xi] = res;
     }
-
-    // ---- combine + softmax mixture: this lane holds logits l = 32 v + 8 g + 4 hi + j of item x
-    const float* gq = qrow + PQ * dp;
-    const float* gi = irow + PX * dp;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int v = 0; v < TL; ++v)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int l0 = 32 * v + 8 * g + 4 * hi;
-        const int lc = l0 < k.Lq ? l0 : 0;                    // Lq is a multiple of 4: a float4 inside the row
-        const float4 q4 = *reinterpret_cast<const float4*>(gq + lc);
-        const float4 i4 = *reinterpret_cast<const float4*>(gi + lc);
-        const float qv[4] = {q4.x, q4.y, q4.z, q4.w}, iv[4] = {i4.x, i4.y, i4.z, i4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float gqi = out[v][4 * g + j];
-          float w;
-          if (k.combine_none) w = (qv[j] + iv[j]) + gqi;
-          else w = silu_exact(__builtin_fmaf(qv[j], iv[j], gqi));
-          out[v][4 * g + j] = w;
-          if (l0 + j < L) mx = fmaxf(mx, w);
-        }
-      }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float den = 0.0f, num = 0.0f;
-#pragma unroll
-    for (int v = 0; v < TL; ++v)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int l0 = 32 * v + 8 * g + 4 * hi;
-        const float4 c4 = cl4[(8 * v + 2 * g + hi) * 32 + x];
-        const float cv[4] = {c4.x, c4.y, c4.z, c4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float e = l0 + j < L ? expf(out[v][4 * g + j] - mx) : 0.0f;
-          den += e;
-          num = __builtin_fmaf(e, cv[j], num);
-        }
-      }
-    den += __shfl_xor(den, 32, 64);
-    num += __shfl_xor(num, 32, 64);
-    // pi = e / den, then the eval-time renormalisation pi / clamp(sum pi, 1e-6) (similarity_fn.py:42-46)
-    const float rden = 1.0f / den;
-    const float res = (num * rden) / fmaxf(den * rden, 1e-6f);
-    if (valid && hi == 0) k.a.logits[(int64_t)b * k.a.ld + xi] = res;
     __syncthreads();   // the next unit's GEMM1 overwrites cl
   }
 }
@@ -237,13 +255,32 @@ int generic_index_unpack(const Shape& s, const float* ipack, int64_t n, float* e
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
+// Eq for the bf16 scans of the padded table width (mol_generic.h gen_table_width): a copy, the columns d .. width zeros
+__global__ void mol_generic_eq_pad_kernel(const float* __restrict__ eq, int64_t rows, int d, int width, float* __restrict__ out) {
+  const int64_t total = rows * width;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / width;
+    const int c = (int)(i - r * width);
+    out[i] = c < d ? eq[r * d + c] : 0.0f;
+  }
+}
+
+int generic_eq_pad(const Shape& s, const float* eq, int64_t rows, float* out, hipStream_t stream) {
+  const int width = gen_table_width(s);
+  if (rows <= 0 || width <= 0) return kOk;
+  int64_t blocks = (rows * width + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(mol_generic_eq_pad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, eq, rows, s.dot_product_dimension, width, out);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
 // ---- launch ---------------------------------------------------------------------------------------------------------------
 constexpr size_t kGenMaxLds = 160 * 1024;
 
-template <int TL, bool RES>
+template <int TL, bool RES, bool IDX>
 static int launch_generic(const GenKernelArgs& k, size_t lds, int grid, hipStream_t stream) {
   static DynLdsOnce once;
-  auto* fn = &mol_generic_score_kernel<TL, RES>;
+  auto* fn = &mol_generic_score_kernel<TL, RES, IDX>;
   // the bytes depend on the shape (L, and H when the weights are resident), not on the instantiation alone: opt in to the route's maximum
   if (ensure_dyn_lds(once, reinterpret_cast<const void*>(fn), (int)kGenMaxLds) != kOk) return kErrLaunch;
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kGenThreads), lds, stream, k);
@@ -252,7 +289,8 @@ static int launch_generic(const GenKernelArgs& k, size_t lds, int grid, hipStrea
 
 template <int TL>
 static int launch_generic_tl(const GenKernelArgs& k, bool res, size_t lds, int grid, hipStream_t stream) {
-  return res ? launch_generic<TL, true>(k, lds, grid, stream) : launch_generic<TL, false>(k, lds, grid, stream);
+  if (k.a.cand_pos) return res ? launch_generic<TL, true, true>(k, lds, grid, stream) : launch_generic<TL, false, true>(k, lds, grid, stream);
+  return res ? launch_generic<TL, true, false>(k, lds, grid, stream) : launch_generic<TL, false, false>(k, lds, grid, stream);
 }
 
 int generic_score(const Shape& s, const GenericScoreArgs& a, int n_cu, hipStream_t stream) {

@@ -226,9 +226,12 @@ class MolIndex:
 class MolEngine:
     """One MoL module's weights bound to the HIP kernels."""
 
-    def __init__(self, spec: MolShapeSpec, weights: Dict[str, torch.Tensor], precision: Optional[str] = None, route: Optional[str] = None):
+    def __init__(self, spec: MolShapeSpec, weights: Dict[str, torch.Tensor], precision: Optional[str] = None, route: Optional[str] = None,
+                 generic_candidates: bool = False):
         """route: None -- the fused kernels where rails_mol_shape_supported says so, else the shape-generic fp32 kernels
-        (rails_mol_generic_*); "generic" -- the generic kernels whatever the shape.  By shape and precision alone, never by size."""
+        (rails_mol_generic_*); "generic" -- the generic kernels whatever the shape.  By shape and precision alone, never by size.
+        generic_candidates: on the generic route, the engine is candidate-capable: candidates are scored in place on
+        the generic index and the bf16 coarse / component tables are cut from it at the padded width table_width; no effect on the fused route."""
         self.lib = _lib.load()
         self.spec = spec
         precision = precision or default_precision()
@@ -251,6 +254,16 @@ class MolEngine:
                 generic_msg = _lib.last_error()
                 raise NotImplementedError(fused_msg if not fused_msg.startswith("no fused scoring kernel") else f"{fused_msg}; {generic_msg}")
             self.route = "generic"
+        # candidate-capable: the opt-in of the generic route.  The bf16 scans then run under `scan_shape`, a copy of the shape whose
+        # dot_product_dimension is the tables' padded width (32 / 64 / 128; 0: d > 128, no tables -- the candidate modules refuse)
+        self.candidates = bool(generic_candidates) and self.route == "generic"
+        self.scan_shape = self.shape
+        self.table_width = spec.dot_product_dimension
+        if self.candidates:
+            self.table_width = int(self.lib.rails_mol_generic_table_width(C.byref(self.shape)))
+            if self.table_width:
+                self.scan_shape = spec.to_c(self.precision)
+                self.scan_shape.dot_product_dimension = self.table_width
         self.exact: Optional["MolEngine"] = MolEngine(spec, weights, "fp32") if precision.endswith("-exact") else None
         # the shape the DENSE pass is launched with: the one-product kernels for "f16-exact" / "f16x1" (same packs, lo halves ignored)
         self.dense_precision = "f16x1" if precision in ("f16-exact", "f16x1") else self.precision
@@ -302,6 +315,30 @@ class MolEngine:
     def _fused_only(self, what: str) -> None:
         if self.route == "generic":
             raise NotImplementedError(f"{what} is not built on the generic scoring route")
+
+    def _candidates_only(self, what: str) -> None:
+        """The candidate entries: the fused route, or the generic route bound with generic_candidates=True (and d <= 128 where tables are cut)."""
+        if self.route == "generic" and not self.candidates:
+            raise NotImplementedError(f"{what} is not built on the generic scoring route")
+
+    def _tables_only(self, what: str) -> None:
+        self._candidates_only(what)
+        if self.table_width == 0:
+            raise NotImplementedError(f"{what}: the generic route's bf16 tables take dot_product_dimension <= 128 (the widest bf16 scan), "
+                                      f"got d = {self.spec.dot_product_dimension}")
+
+    def _scan_eq(self, eq: torch.Tensor) -> torch.Tensor:
+        """Eq as the bf16 scans read it: (B, P_Q, table_width) fp32 contiguous -- the caller's tensor where d is the width already, else a
+        zero-padded copy (rails_mol_generic_eq_pad); a tensor of the padded width passes through."""
+        eq = _f32c(eq)
+        if eq.shape[-1] == self.table_width:
+            return eq
+        if not self.candidates or eq.shape[-1] != self.spec.dot_product_dimension:
+            raise ValueError(f"Eq must be (B, P_Q, {self.spec.dot_product_dimension}), got {tuple(eq.shape)}")
+        out = torch.empty(eq.shape[:-1] + (self.table_width,), dtype=torch.float32, device=eq.device)
+        with _on_device(eq.device):
+            _lib.check(self.lib.rails_mol_generic_eq_pad(C.byref(self.shape), _ptr(eq), eq.numel() // eq.shape[-1], _ptr(out), _stream()), "rails_mol_generic_eq_pad")
+        return out
 
     def _check_f16_range(self, weights: Dict[str, torch.Tensor]) -> None:
         """precision='f16x3' keeps cl, hid and the gate weights as f16 hi + lo.  Small values are safe (f16 subnormals are
@@ -379,8 +416,8 @@ class MolEngine:
     def update_source(self, index: MolIndex, items: torch.Tensor) -> Tuple[torch.Tensor, int]:
         """What the bf16 tables' updates are cut from -> (fp32-format index, read in place?): the (updated) index itself for fp32 engines; in
         f16x3 precision, whose index holds Ex to 22 bits, a temporary fp32-format index of the M updated rows alone (as _derived_table's chunks)."""
-        self._fused_only("the coarse / component tables")
-        if self.precision == "fp32":
+        self._tables_only("the coarse / component tables")
+        if self.precision == "fp32":      # (the generic route is fp32 only: its tables are always cut from the index in place)
             return index.buf, 1
         items = _f32c(items)
         m = items.shape[0]
@@ -393,6 +430,10 @@ class MolEngine:
         """Rows `positions` of a build_coarse_table table from update_source's pair."""
         positions = positions.contiguous()
         with _on_device(table.device):
+            if self.route == "generic":
+                _lib.check(self.lib.rails_mol_generic_coarse_update(C.byref(self.shape), _ptr(source[0]), _ptr(positions), positions.numel(), _ptr(table),
+                                                                    table.shape[0], _stream()), "rails_mol_generic_coarse_update")
+                return
             _lib.check(self.lib.rails_mol_coarse_update(C.byref(self._fp32_shape), _ptr(source[0]), source[1], _ptr(positions), positions.numel(), _ptr(table),
                                                         table.shape[0], _stream()), "rails_mol_coarse_update")
 
@@ -400,6 +441,10 @@ class MolEngine:
         """Rows `positions` of every item group of a build_component_table table (P_X, N, d)."""
         positions = positions.contiguous()
         with _on_device(table.device):
+            if self.route == "generic":
+                _lib.check(self.lib.rails_mol_generic_component_update(C.byref(self.shape), _ptr(source[0]), _ptr(positions), positions.numel(), _ptr(table),
+                                                                       table.shape[1], _stream()), "rails_mol_generic_component_update")
+                return
             _lib.check(self.lib.rails_mol_component_update(C.byref(self._fp32_shape), _ptr(source[0]), source[1], _ptr(positions), positions.numel(), _ptr(table),
                                                            table.shape[1], _stream()), "rails_mol_component_update")
 
@@ -420,13 +465,20 @@ class MolEngine:
                            counts: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """score_indexed with the candidates read from the row-major copy: whole cache lines per candidate, same bits.
         counts: per-row candidate counts (int32 on the device; candidates_select's): only the first counts[b] logits of row b are written."""
-        self._fused_only("score_indexed_rows")
+        self._candidates_only("score_indexed_rows")
         if positions.dtype != torch.int64 or positions.device != rows.device or not positions.is_contiguous():
             positions = positions.to(device=rows.device, dtype=torch.int64).contiguous()
         n_cand = positions.shape[1]
         if out is None:
             out = torch.empty((batch, n_cand), dtype=torch.float32, device=rows.device)
         with _on_device(rows.device):
+            if self.route == "generic":      # `rows` is the generic index itself: it is row-major already
+                _lib.check(
+                    self.lib.rails_mol_generic_score_indexed(C.byref(self.shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(rows), n_items, _ptr(positions),
+                                                             n_cand, _ptr(counts), _ptr(out), out.stride(0), None, _stream()),
+                    "rails_mol_generic_score_indexed",
+                )
+                return out
             _lib.check(
                 self.lib.rails_mol_score_indexed_rows(C.byref(self.shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(rows), n_items, _ptr(positions), n_cand,
                                                       _ptr(out), out.stride(0), _ptr(counts), _stream()),
@@ -552,7 +604,7 @@ class MolEngine:
 
     def score_indexed_supported(self, batch: int, n_cand: int) -> bool:
         if self.route == "generic":
-            return False
+            return self.candidates      # (the indexed mode of the generic kernel takes any batch and any n_cand >= 1)
         key = (int(batch), int(n_cand))
         memo = self.__dict__.setdefault("_indexed_ok", {})     # a dry run of the launch per call otherwise: host time of every rerank
         if key not in memo:
@@ -562,7 +614,9 @@ class MolEngine:
     def score_indexed(self, qpack: torch.Tensor, batch: int, index: MolIndex, positions: torch.Tensor) -> torch.Tensor:
         """(B, n_cand) logits of per-row candidates given as positions of `index` (all inside the index):
         gather_index + score_candidates without the gathered copy (include/rails_amd.h rails_mol_score_indexed)."""
-        self._fused_only("score_indexed")
+        self._candidates_only("score_indexed")
+        if self.route == "generic":
+            return self.score_indexed_rows(qpack, batch, index.buf, index.n_items, positions)
         positions = positions.to(device=index.buf.device, dtype=torch.int64).contiguous()
         n_cand = positions.shape[1]
         out = torch.empty((batch, n_cand), dtype=torch.float32, device=index.buf.device)
@@ -593,11 +647,16 @@ class MolEngine:
     def _derived_table(self, fn_name: str, row_elems: int, index: MolIndex, items: Optional[torch.Tensor]) -> torch.Tensor:
         """A bf16 table cut from the fp32 Ex of the index.  In f16x3 precision the index only holds Ex to 22 bits, so the
         table is cut from temporary fp32-format index chunks rebuilt from `items` (same values as the fp32 engine's)."""
-        self._fused_only("the coarse / component tables")
-        fn = getattr(self.lib, fn_name)
+        self._tables_only("the coarse / component tables")
         n, dev = index.n_items, index.buf.device
         table = torch.empty(n * row_elems, dtype=torch.bfloat16, device=dev)
         grouped = fn_name == "rails_mol_component_build"      # item-group-major table: a chunk of items writes a slice of every group
+        if self.route == "generic":      # the generic index is fp32 and row-major: one launch, rows of table_width columns (row_elems counts them)
+            fn_name = fn_name.replace("rails_mol_", "rails_mol_generic_")
+            with _on_device(dev):
+                _lib.check(getattr(self.lib, fn_name)(C.byref(self.shape), _ptr(index.buf), n, _ptr(table), _stream()), fn_name)
+            return table
+        fn = getattr(self.lib, fn_name)
         with _on_device(dev):
             if self.precision == "fp32":
                 if grouped:
@@ -621,20 +680,21 @@ class MolEngine:
         return table
 
     def build_coarse_table(self, index: MolIndex, items: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """(N, d) bf16 table of P_X-averaged component embeddings (reference mol_top_k.py:321-325)."""
-        d = self.spec.dot_product_dimension
+        """(N, d) bf16 table of P_X-averaged component embeddings (reference mol_top_k.py:321-325); on a candidate-capable generic engine
+        (N, table_width), the columns d .. table_width zeros."""
+        d = self.table_width
         return self._derived_table("rails_mol_coarse_build", d, index, items).view(index.n_items, d)
 
     def coarse_scores(self, eq: torch.Tensor, table: torch.Tensor, average_queries: bool, out: Optional[torch.Tensor] = None,
                       run_if: Optional[torch.Tensor] = None) -> torch.Tensor:
         """eq (B, P_Q, d) fp32 -> (B, N) fp32 holding bf16-rounded dot products (reference mol_top_k.py:351-354)."""
         B, n = eq.shape[0], table.shape[0]
-        eq = _f32c(eq)
+        eq = self._scan_eq(eq)
         if out is None:
             out = torch.empty((B, n), dtype=torch.float32, device=table.device)
         with _on_device(table.device):
             _lib.check(
-                self.lib.rails_mol_coarse_score(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, _ptr(out), out.stride(0), _pred(run_if), _stream()),
+                self.lib.rails_mol_coarse_score(C.byref(self.scan_shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, _ptr(out), out.stride(0), _pred(run_if), _stream()),
                 "rails_mol_coarse_score",
             )
         return out
@@ -642,13 +702,15 @@ class MolEngine:
     def build_coarse_prefilter(self, table: torch.Tensor) -> Optional[torch.Tensor]:
         """The int8 copy of a coarse table that lets coarse_topk's streaming pass read d instead of 2d bytes per item
         (include/rails_amd.h rails_mol_coarse_prefilter_build); None for shapes without one."""
+        if self.route == "generic":      # not built for the padded widths of the generic route
+            return None
         n = table.shape[0]
-        nbytes = self.lib.rails_mol_coarse_prefilter_bytes(C.byref(self.shape), n)
+        nbytes = self.lib.rails_mol_coarse_prefilter_bytes(C.byref(self.scan_shape), n)
         if nbytes == 0:
             return None
         pre = torch.empty(nbytes, dtype=torch.uint8, device=table.device)
         with _on_device(table.device):
-            _lib.check(self.lib.rails_mol_coarse_prefilter_build(C.byref(self.shape), _ptr(table), n, _ptr(pre), _stream()), "rails_mol_coarse_prefilter_build")
+            _lib.check(self.lib.rails_mol_coarse_prefilter_build(C.byref(self.scan_shape), _ptr(table), n, _ptr(pre), _stream()), "rails_mol_coarse_prefilter_build")
         return pre
 
     def coarse_topk(self, eq: torch.Tensor, table: torch.Tensor, average_queries: bool, k_prime: int, with_flag: bool = False,
@@ -669,18 +731,18 @@ class MolEngine:
         _check_tag_filter(tags, n, B, table.device, visible)
         memo = self.__dict__.setdefault("_coarse_ws_bytes", {})
         if (B, n, k_prime) not in memo:
-            memo[(B, n, k_prime)] = self.lib.rails_mol_coarse_topk_workspace_bytes(C.byref(self.shape), B, n, k_prime)
+            memo[(B, n, k_prime)] = self.lib.rails_mol_coarse_topk_workspace_bytes(C.byref(self.scan_shape), B, n, k_prime)
         ws_bytes = memo[(B, n, k_prime)]
         if ws_bytes == 0:
             return None
-        eq = _f32c(eq)
+        eq = self._scan_eq(eq)
         dev = table.device
         if prefilter is not None:
             # the C side indexes the int8 copy by this call's n and d, and the exactness argument assumes copy and scale belong to THIS
             # table: a buffer of another size or device (a stale copy of a rebuilt table) is refused
             want = memo.get(("prefilter", n))
             if want is None:
-                want = memo[("prefilter", n)] = self.lib.rails_mol_coarse_prefilter_bytes(C.byref(self.shape), n)
+                want = memo[("prefilter", n)] = self.lib.rails_mol_coarse_prefilter_bytes(C.byref(self.scan_shape), n)
             if prefilter.device != dev or prefilter.dtype != torch.uint8 or prefilter.numel() != want or not prefilter.is_contiguous():
                 raise ValueError(f"coarse_topk: the int8 pre-filter does not belong to this table ({prefilter.numel()} bytes on {prefilter.device}, "
                                  f"expected {want} on {dev}): rebuild it with build_coarse_prefilter(table)")
@@ -697,20 +759,20 @@ class MolEngine:
         with _on_device(dev):
             if tags is not None:
                 _lib.check(
-                    self.lib.rails_mol_coarse_topk_tagged(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
+                    self.lib.rails_mol_coarse_topk_tagged(C.byref(self.scan_shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
                                                           _ptr(ws), ws_bytes, _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag) if with_flag else None,
                                                           _ptr(prefilter), _ptr(tags.eff), _ptr(tags.allowed_for(B)), _stream()),
                     "rails_mol_coarse_topk_tagged",
                 )
             elif visible is None:
                 _lib.check(
-                    self.lib.rails_mol_coarse_topk(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
+                    self.lib.rails_mol_coarse_topk(C.byref(self.scan_shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
                                                    _ptr(ws), ws_bytes, _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag) if with_flag else None, _ptr(prefilter), _stream()),
                     "rails_mol_coarse_topk",
                 )
             else:
                 _lib.check(
-                    self.lib.rails_mol_coarse_topk_visible(C.byref(self.shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
+                    self.lib.rails_mol_coarse_topk_visible(C.byref(self.scan_shape), _ptr(eq), B, 1 if average_queries else 0, _ptr(table), n, k_prime,
                                                            _ptr(ws), ws_bytes, _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag) if with_flag else None,
                                                            _ptr(prefilter), _ptr(visible), _stream()),
                     "rails_mol_coarse_topk_visible",
@@ -729,20 +791,20 @@ class MolEngine:
     # ---- per-component candidates (MoLNaiveTopK / MoLCombTopK) -----------------------------------------
     def build_component_table(self, index: MolIndex, items: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(P_X, N, d) bf16 component embeddings (reference mol_top_k.py:61-73), item-group-major: the scans stream one group's rows back to back."""
-        px, d = self.spec.item_dot_product_groups, self.spec.dot_product_dimension
+        px, d = self.spec.item_dot_product_groups, self.table_width      # (the padded width on a candidate-capable generic engine, as the coarse table)
         return self._derived_table("rails_mol_component_build", px * d, index, items).view(px, index.n_items, d)
 
     def component_scores(self, eq: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None,
                          run_if: Optional[torch.Tensor] = None) -> torch.Tensor:
         """eq (B, P_Q, d) -> (B * P_Q * P_X, N) fp32 holding bf16 values, row (b * P_Q + i) * P_X + m."""
         B, n = eq.shape[0], table.shape[1]
-        eq = _f32c(eq)
+        eq = self._scan_eq(eq)
         rows = B * self.spec.query_dot_product_groups * self.spec.item_dot_product_groups
         if out is None:
             out = torch.empty((rows, n), dtype=torch.float32, device=table.device)
         with _on_device(table.device):
             _lib.check(
-                self.lib.rails_mol_component_score(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, _ptr(out), out.stride(0), _pred(run_if), _stream()),
+                self.lib.rails_mol_component_score(C.byref(self.scan_shape), _ptr(eq), B, _ptr(table), n, _ptr(out), out.stride(0), _pred(run_if), _stream()),
                 "rails_mol_component_score",
             )
         return out
@@ -760,10 +822,10 @@ class MolEngine:
         _check_tag_filter(tags, n, B, table.device, visible)
         if tags is not None and B * self.spec.query_dot_product_groups > TAGGED_COMPONENT_ROWS:
             return None
-        ws_bytes = self.lib.rails_mol_component_topk_workspace_bytes(C.byref(self.shape), B, n, k_group)
+        ws_bytes = self.lib.rails_mol_component_topk_workspace_bytes(C.byref(self.scan_shape), B, n, k_group)
         if ws_bytes == 0:
             return None
-        eq = _f32c(eq)
+        eq = self._scan_eq(eq)
         dev = table.device
         rows = B * self.spec.query_dot_product_groups * self.spec.item_dot_product_groups
         memo = self.__dict__.setdefault("_comp_ws", {})          # the workspace is recycled: 30-70 MB of candidate lists per call otherwise
@@ -777,27 +839,27 @@ class MolEngine:
         with _on_device(dev):
             if tags is not None:
                 _lib.check(
-                    self.lib.rails_mol_component_topk_tagged(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
+                    self.lib.rails_mol_component_topk_tagged(C.byref(self.scan_shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
                                                              _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag), _ptr(tags.eff), _ptr(tags.allowed_for(B)),
                                                              _stream()),
                     "rails_mol_component_topk_tagged",
                 )
             elif visible is None:
                 _lib.check(
-                    self.lib.rails_mol_component_topk(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
+                    self.lib.rails_mol_component_topk(C.byref(self.scan_shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
                                                       _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag), _stream()),
                     "rails_mol_component_topk",
                 )
             else:
                 _lib.check(
-                    self.lib.rails_mol_component_topk_visible(C.byref(self.shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
+                    self.lib.rails_mol_component_topk_visible(C.byref(self.scan_shape), _ptr(eq), B, _ptr(table), n, k_group, _ptr(ws), ws_bytes,
                                                               _ptr(out_s), _ptr(out_p), _ptr(counts), _ptr(flag), _ptr(visible), _stream()),
                     "rails_mol_component_topk_visible",
                 )
         return out_s, out_p, counts
 
     def component_topk_capacity(self, batch: int, n: int, k_group: int) -> int:
-        return int(self.lib.rails_mol_component_topk_capacity(C.byref(self.shape), int(batch), int(n), int(k_group)))
+        return int(self.lib.rails_mol_component_topk_capacity(C.byref(self.scan_shape), int(batch), int(n), int(k_group)))
 
 
 def ivf_edited_size(n_old: int, n_keep: int, positions=None, *, m: Optional[int] = None, below: Optional[int] = None) -> int:

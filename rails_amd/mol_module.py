@@ -330,6 +330,10 @@ class MoLSimilarity(SimilarityModule):
         # None -> the fused kernels where the shape has them, the shape-generic fp32 kernels otherwise; "generic" sends a fused shape
         # through the generic kernels too (tests and measurements: the two routes agree to rounding, not bit for bit)
         self.route: Optional[str] = None
+        # True -> an engine bound on the generic route is candidate-capable: candidates are scored in place on the generic index and the bf16
+        # coarse / component tables are cut from it, so MoLAvgTopK / MoLNaiveTopK / MoLCombTopK run there.  No effect on
+        # the fused route.  Part of the engine cache key, as `route` and `precision` are.
+        self.generic_candidates: bool = False
 
     # ---- binding the parameters to the HIP engine -----------------------------------------------
     def shape_spec(self) -> MolShapeSpec:
@@ -394,19 +398,19 @@ class MoLSimilarity(SimilarityModule):
                 # the caller has just asked for the module's own engine (same thread, nothing in between): the parameters are those of
                 # _engine_key, and this precision's engine was built from the same ones -- no second walk over the 27 tensors
                 return hit[1]
-            key = ((precision, self.route),) + tuple((v.data_ptr(), _version(v)) for v in plist)
+            key = ((precision, self.route, self.generic_candidates),) + tuple((v.data_ptr(), _version(v)) for v in plist)
             if hit is None or hit[0] != key:
                 params = dict(self.state_dict(keep_vars=True))
                 self._param_list = list(params.values())
-                key = ((precision, self.route),) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
-                hit = self._extra_engines[precision] = (key, MolEngine(self.shape_spec(), params, precision=precision, route=self.route))
+                key = ((precision, self.route, self.generic_candidates),) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
+                hit = self._extra_engines[precision] = (key, MolEngine(self.shape_spec(), params, precision=precision, route=self.route, generic_candidates=self.generic_candidates))
             return hit[1]
-        key = ((self.precision, self.route),) + tuple((v.data_ptr(), _version(v)) for v in plist)
+        key = ((self.precision, self.route, self.generic_candidates),) + tuple((v.data_ptr(), _version(v)) for v in plist)
         if self._engine is None or key != self._engine_key:
             params = dict(self.state_dict(keep_vars=True))
             self._param_list = list(params.values())
-            key = ((self.precision, self.route),) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
-            self._engine = MolEngine(self.shape_spec(), params, precision=self.precision, route=self.route)
+            key = ((self.precision, self.route, self.generic_candidates),) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
+            self._engine = MolEngine(self.shape_spec(), params, precision=self.precision, route=self.route, generic_candidates=self.generic_candidates)
             self._engine_key = key
         return self._engine
 

@@ -33,7 +33,9 @@ import torch
 import torch.distributed as dist
 
 from . import engine as E
-from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule, _checked_positions, refuse_allowed_tags, refuse_collapse_groups, refuse_item_mask
+from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule, _checked_positions, refuse_allowed_tags, refuse_collapse_groups, refuse_generic_candidates, refuse_item_mask
+
+_GENERIC_WHY = "the single-device module runs there, and ShardedMoLBruteForceTopK shards the exact pass"
 
 _TAGS_WHY = ("tags belong to the positions of ONE corpus and the sharded wrappers split theirs over the ranks: every rank would have to hold its slice "
              "of the tags and the global candidate counts would have to follow the filter (out of scope, DESIGN section 3.15); the single-device modules take it")
@@ -574,6 +576,7 @@ class ShardedMoLAvgTopK(ShardedTopK):
         self._rerank_local = rerank_local if rerank_local is not None else (lambda q, idx, k, **kw: self._local_module.rerank_masked(q, idx, k, **kw))
 
     def _make_local_module(self, mol_module, item_embeddings_shard, item_ids_shard) -> TopKModule:
+        refuse_generic_candidates(mol_module, "ShardedMoLAvgTopK", _GENERIC_WHY)
         return MoLAvgTopK(mol_module, item_embeddings_shard, item_ids_shard, avg_top_k=min(self._avg_top_k, int(item_ids_shard.numel())))
 
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
@@ -853,6 +856,7 @@ class ShardedMoLNaiveTopK(_ShardedComponentCandidates):
                          candidates_local=candidates_local, rerank_local=rerank_local, **kwargs)
 
     def _make_local_module(self, mol_module, item_embeddings_shard, item_ids_shard) -> TopKModule:
+        refuse_generic_candidates(mol_module, "ShardedMoLNaiveTopK", _GENERIC_WHY)
         return MoLNaiveTopK(mol_module, item_embeddings_shard, item_ids_shard, k_per_group=max(1, min(self._k_per_group, int(item_ids_shard.numel()))))
 
     def _widths(self) -> Tuple[int, int, int]:
@@ -874,6 +878,7 @@ class ShardedMoLCombTopK(_ShardedComponentCandidates):
                          candidates_local=candidates_local, rerank_local=rerank_local, **kwargs)
 
     def _make_local_module(self, mol_module, item_embeddings_shard, item_ids_shard) -> TopKModule:
+        refuse_generic_candidates(mol_module, "ShardedMoLCombTopK", _GENERIC_WHY)
         n = int(item_ids_shard.numel())
         return MoLCombTopK(mol_module, item_embeddings_shard, item_ids_shard, avg_top_k=max(1, min(self._avg_top_k, n)),
                            k_per_group=max(1, min(self._k_per_group, n)))

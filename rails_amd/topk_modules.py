@@ -1176,7 +1176,8 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
             return c[2]
         rows = None
         need = self._index.buf.numel() * 4
-        if getattr(eng, "precision", None) == "fp32" and self._index.buf.is_cuda and 0 < need <= self.RERANK_ROWS_COPY_MAX_BYTES:
+        # (the generic index is row-major itself: no copy, score_indexed reads it in place)
+        if getattr(eng, "precision", None) == "fp32" and getattr(eng, "route", None) != "generic" and self._index.buf.is_cuda and 0 < need <= self.RERANK_ROWS_COPY_MAX_BYTES:
             free, _ = torch.cuda.mem_get_info(self._index.buf.device)
             if free > 2 * need:
                 rows = eng.build_index_rows(self._index)
@@ -1206,10 +1207,26 @@ def mask_strategy(kept_max: int, n_items: int, sparse_max: int, factor: int, pos
 
 def _refuse_generic_route(mol_module: MoLSimilarity, what: str) -> None:
     """The approximate algorithms need the coarse / component tables and the in-place candidate re-scoring, which the generic scoring
-    route does not have: refuse at construction, before any build."""
-    if mol_module.engine().route == "generic":
+    route has on a candidate-capable engine only (MoLSimilarity.generic_candidates = True): refuse otherwise, at
+    construction, before any build -- and, on a candidate-capable engine, what the route still lacks, by name."""
+    eng = mol_module.engine()
+    if eng.route != "generic":
+        return
+    if not eng.candidates:
         raise NotImplementedError(f"{what} is not built on the generic scoring route (this MoL shape has no fused scoring kernel); "
-                                  "MoLBruteForceTopK runs it")
+                                  "MoLBruteForceTopK runs it.  Setting generic_candidates = True on the MoLSimilarity opts in to the "
+                                  "two-pass algorithms on this route")
+    if eng.table_width == 0:
+        raise NotImplementedError(f"{what} on the generic scoring route takes dot_product_dimension <= 128 (the widest bf16 candidate scan), "
+                                  f"got d = {eng.spec.dot_product_dimension}; MoLBruteForceTopK runs it")
+
+
+def refuse_generic_candidates(mol_module: MoLSimilarity, what: str, instead: str) -> None:
+    """What the two-pass algorithms still lack on the generic scoring route, a candidate-capable engine included:
+    refused by name, before any build or launch."""
+    if mol_module.engine().route == "generic":
+        raise NotImplementedError(f"{what} is not built on the generic scoring route (generic_candidates = True covers the single-device "
+                                  f"exhaustive algorithms); {instead}")
 
 
 class BoundPolicy(NamedTuple):
@@ -1475,10 +1492,10 @@ class MoLBruteForceTopK(MoLTopKModule):
 
     def _mask_scorer(self, eng):
         """(engine, index, row-major copy or a function yielding it) that scores corpus positions in place in the module's own fp32 arithmetic --
-        _score_positions' arguments -- or None where there is none: the generic route, the split-f16 precisions (no indexed instantiation), an
-        exact mode without its resident fp32 index."""
+        _score_positions' arguments -- or None where there is none: the generic route unless its engine is candidate-capable (the index is
+        then its own row-major copy), the split-f16 precisions (no indexed instantiation), an exact mode without its resident fp32 index."""
         if eng.route == "generic":
-            return None
+            return (eng, self._index, lambda e: self._index.buf) if eng.candidates else None
         if eng.exact is not None:
             if self._index32 is None or self._index32_engine is not eng.exact:
                 return None
@@ -2495,6 +2512,14 @@ def _collapsed_candidates_result(handle) -> Tuple[torch.Tensor, torch.Tensor]:
     return walk.scores.to(dtype), walk.ids
 
 
+def _generic_takes_no_groups(tk, what: str) -> None:
+    """Item groups on the approximate modules of the generic route: the collapse walk has not been tested there, so it is refused by name.
+    Read from the engine the module is bound to (the constructor bound one): no look at the model's parameters on this path."""
+    if (tk._call_eng or tk._engine).route == "generic":
+        raise NotImplementedError(f"{type(tk).__name__}: {what} is not built on the generic scoring route (generic_candidates = True covers the "
+                                  "single-device exhaustive algorithms without item groups); MoLBruteForceTopK collapses by item group on this route")
+
+
 class MoLAvgTopK(MoLTopKModule):
     DEVICE_REDO_BYTES = 1 << 30   # materialised score matrices up to this size are kept as the device-side redo buffer of a fused scan;
                                   # beyond it (a 125 M-item shard: 16 GB) the counts are read on the host after the call is enqueued --
@@ -2540,6 +2565,9 @@ class MoLAvgTopK(MoLTopKModule):
         self._prefilter_calls = 0                 # scans that looked at the int8 copy (the schedule of its statistics check)
         self._prefilter_pending = None            # (pinned copy of the header's counts, its event) on its way to the host
         self._redo_fit_memo: Dict[int, bool] = {} # _device_redo_fits by buffer size
+
+    def _check_collapsible(self, what: str) -> None:
+        _generic_takes_no_groups(self, what)
 
     OVERLAP_BATCHES = True            # submit(): speculative calls alternate between two streams of the module (see submit)
     PREFILTER_MIN_ITEMS = 4_000_000   # the int8 copy of the coarse table pays where the streaming pass is bound by HBM reads
@@ -2888,7 +2916,7 @@ class _ComponentCandidates:
         pq, px = eng.spec.query_dot_product_groups, eng.spec.item_dot_product_groups
         # the scans keep the fragments of all B * P_Q query rows in LDS and (the fused form) eight row tiles of running maxima in registers (four
         # at d = 128): 256 (128) query rows per call; the tagged sample keeps four row tiles at every d (its eight-tile form would spill)
-        plain_rows = 128 if eng.spec.dot_product_dimension >= 128 else 256
+        plain_rows = 128 if eng.table_width >= 128 else 256      # (the width the scans run at: d, or the generic route's padded width)
 
         def launch(eq, flag, **restriction):      # (flag: zeroed by the call's first launch)
             out = eng.component_topk(eq, table, k, flag, **restriction)
@@ -3016,6 +3044,8 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
                  *, nlist: int = 100, nprobe: int = 1, iters: int = 10, seed: int = 1234, frozen_centroids: bool = False,
                  ivf_centroids: Optional[torch.Tensor] = None, filtered_lists: bool = False) -> None:
         _refuse_generic_route(mol_module, type(self).__name__)
+        if use_faiss:
+            refuse_generic_candidates(mol_module, "MoLNaiveTopK: the IVF index (use_faiss=True)", "the exhaustive MoLNaiveTopK runs there")
         super().__init__(mol_module=mol_module, item_embeddings=item_embeddings, item_ids=item_ids)
         self._k_per_group: int = k_per_group
         self._use_faiss: bool = bool(use_faiss)
@@ -3093,6 +3123,7 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
         return self._component_topk(eq, self._k_per_group, pending, **({} if tags is None else {"tags": tags}))
 
     def _check_collapsible(self, what: str) -> None:
+        _generic_takes_no_groups(self, what)
         if self._use_faiss:
             raise NotImplementedError(f"MoLNaiveTopK (IVF, use_faiss=True) takes no {what}: collapsing by item group is not built on the IVF index; the "
                                       "exhaustive MoLNaiveTopK takes it")

@@ -5,6 +5,8 @@ generic route runs, and 8x8x32 / H = 128 forced through the generic route next t
 
 Warm-up launches first, then the median of per-launch device times (CUDA events around each launch, the stream drained before each).
   python tools/generic_route_bench.py [--out profiles/generic_route.json] [--items 695762] [--reps 15]
+--candidates: instead, MoLAvgTopK1000 / MoLNaiveTopK5 / MoLCombTopK5_200 on a candidate-capable generic engine (generic_candidates = True)
+against the same shape's brute-force step, 4x4x64 and 16x8x32 / H = 256, medians of 20 calls -> profiles/generic_candidates.json
 """
 import argparse
 import json
@@ -76,13 +78,66 @@ def measure(cfg, dev, route, n_items, reps):
     return out
 
 
+CANDIDATE_SHAPES = ("4x4x64_h128", "16x8x32_h256")
+CANDIDATE_ALGORITHMS = ("MoLAvgTopK1000", "MoLNaiveTopK5", "MoLCombTopK5_200")
+
+
+def measure_candidates(cfg, dev, n_items, reps):
+    """The two-pass algorithms on a candidate-capable generic engine (generic_candidates = True) against the same shape's brute-force step:
+    whole CandidateIndex.get_top_k_outputs calls (k = 200, no history), medians of `reps` calls."""
+    mol = module(cfg, dev)
+    mol.generic_candidates = True
+
+    class Model:      # what get_top_k_module reads
+        _ndp_module = mol
+
+    X = torch.from_numpy(O.hash_item_table(1, 0, n_items, cfg.item_embedding_dim)).unsqueeze(0).to(dev)
+    ids = torch.arange(n_items, dtype=torch.int64, device=dev).unsqueeze(0)
+    ci = rails_amd.CandidateIndex(ids=ids, embeddings=X)
+    out = {}
+    with torch.inference_mode():
+        eng = mol.engine()
+        out["route"], out["table_width"] = eng.route, eng.table_width
+        for name in ("MoLBruteForceTopK",) + CANDIDATE_ALGORITHMS:
+            tk = rails_amd.MoLBruteForceTopK(mol, X, ids, exact_mode="dense") if name == "MoLBruteForceTopK" else rails_amd.get_top_k_module(name, Model, X, ids)
+            row = {}
+            for B in (1, 32):
+                q = O.synthetic_queries(cfg, B, seed=2).to(dev)
+                med, lo, hi = median_ms(lambda: ci.get_top_k_outputs(q, 200, {}, tk, None), reps)
+                row[f"B{B}"] = {"top_k_step_ms": round(med, 4), "top_k_step_min_max_ms": [round(lo, 4), round(hi, 4)]}
+            out[name] = row
+            print(" ", name, json.dumps(row), flush=True)
+            del tk
+            torch.cuda.empty_cache()
+        for name in CANDIDATE_ALGORITHMS:
+            out[name]["brute_force_over_it"] = {b: round(out["MoLBruteForceTopK"][b]["top_k_step_ms"] / out[name][b]["top_k_step_ms"], 1) for b in ("B1", "B32")}
+    del ci, X
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--items", type=int, default=695762)
-    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--reps", type=int, default=None, help="timed calls per figure (default 15; 20 with --candidates)")
+    ap.add_argument("--candidates", action="store_true", help="time MoLAvgTopK1000 / MoLNaiveTopK5 / MoLCombTopK5_200 on the generic route "
+                    "(generic_candidates = True) against the brute-force step; default output profiles/generic_candidates.json")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.candidates:
+        reps = args.reps or 20
+        res = {"device": torch.cuda.get_device_name(0), "n_items": args.items, "k": 200, "reps": reps, "what": "median ms of whole "
+               "CandidateIndex.get_top_k_outputs calls, no history; brute force = MoLBruteForceTopK(exact_mode='dense') on the same engine", "shapes": {}}
+        for name in CANDIDATE_SHAPES:
+            print(name, flush=True)
+            res["shapes"][name] = measure_candidates(SHAPES[name], dev, args.items, reps)
+        print(json.dumps(res, indent=1))
+        with open(args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "generic_candidates.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
+    args.reps = args.reps or 15
     res = {"device": torch.cuda.get_device_name(0), "n_items": args.items, "k": 200, "reps": args.reps, "exact_mode": "dense", "shapes": {}}
     for name, cfg in SHAPES.items():
         res["shapes"][name] = measure(cfg, dev, None, args.items, args.reps)
