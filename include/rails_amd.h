@@ -52,6 +52,7 @@ extern "C" {
  * rails_ivf_plan_filtered / rails_ivf_search_filtered and the group-collapse entries rails_topk_collapse / rails_scores_group_max / rails_topk_keys
  * and the generic route's candidate entries rails_mol_generic_score_indexed / rails_mol_generic_table_width / rails_mol_generic_coarse_build /
  * rails_mol_generic_coarse_update / rails_mol_generic_component_build / rails_mol_generic_component_update / rails_mol_generic_eq_pad
+ * and the rank entries rails_scores_rank_keys / rails_scores_rank / rails_item_mask_clear_rows
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -401,6 +402,27 @@ int rails_item_mask_from_tags(const uint32_t* eff_tags, int64_t n, const uint32_
  * run_if: the launch predicate. */
 int rails_scores_mask_tags(float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const uint32_t* eff_tags, const uint32_t* allowed,
                            int32_t rows_per_allowed, float fill, const int32_t* run_if, void* stream);
+
+/* ---- exact ranks of given items (added under ABI 15: new entries only; no counterpart in the reference) ----------------------------
+ * The rank of target position x in row r of a (rows, n) fp32 score matrix with row stride ld, among the items the row may return:
+ *   rank = 1 + #{ eligible y : key(r, y) > key(r, x) },   key(r, y) = (orderable(scores[r * ld + y]) << 32) | ~y
+ * -- the selection key of rails_topk on the score's bit pattern (+-0, +-inf and NaN payloads rank as they do there; ties break by position
+ * ascending), so rank - 1 is the index at which x stands in the row's exhaustive rails_topk list.  Rank 0: "not ranked" -- the target is
+ * not a position of the matrix, or its own mask bit is clear.  1 <= t <= 64 targets per row and call, 1 <= rows <= 2^24 (rows = 0: nothing
+ * to do), 1 <= n < 2^31, ld >= n. */
+/* keys_out[r * t + j] = the key of position p = positions[r * t + j] read from row r, or 0 -- below every real key -- for p outside [0, n)
+ * (the -1 of an unknown id). */
+int rails_scores_rank_keys(const float* scores, int64_t ld, int32_t rows, int64_t n, const int64_t* positions, int32_t t, uint64_t* keys_out, void* stream);
+/* ranks_out[r * t + j] = the rank of the target whose key is keys[r * t + j], every entry written.  mask_words: the item-mask rows of
+ * rails_scores_mask (row r at mask_words + r * words_row_stride, words_row_stride = 0: one row shared by every r; otherwise at least
+ * rails_item_mask_words(n)), bit set = eligible; NULL: every item is eligible.  Three launches -- zero, count, finish --: the count reads
+ * every score once for all t targets of its row and adds integers, so the result does not depend on the order of arrival. */
+int rails_scores_rank(const float* scores, int64_t ld, int32_t rows, int64_t n, const uint64_t* keys, int32_t t, const uint32_t* mask_words,
+                      int64_t words_row_stride, int32_t* ranks_out, void* stream);
+/* rails_item_mask_clear per row: the bits at positions[r * m .. r * m + m) of row r (at words + r * words_row_stride, words_row_stride >=
+ * rails_item_mask_words(n)) are cleared, a 32-bit atomic AND-NOT each; positions outside [0, n) are skipped, repeats are harmless.  How a
+ * row's seen ids leave its mask.  m = 0 or rows = 0: nothing to do. */
+int rails_item_mask_clear_rows(const int64_t* positions, int32_t rows, int64_t m, int64_t n, uint32_t* words, int64_t words_row_stride, void* stream);
 
 /* Per-row candidates: out[bq * n_cand + x] = <queries[bq], items[bq / r][x]> for queries (n_queries, dim) and items
  * (n_queries / r, n_cand, dim) -- the two bmm branches of DotProductSimilarity.forward

@@ -849,6 +849,42 @@ int rails_scores_mask_tags(float* scores, int64_t ld, int32_t rows, int64_t n, i
   return fail(scores_mask_tags(scores, ld, rows, n, first_item, eff_tags, allowed, rows_per_allowed, fill, run_if, (hipStream_t)stream), "scores_mask_tags");
 }
 
+// ---- exact ranks of given items (rank.hip) ----
+static int rank_args(const char* what, bool pointers, int64_t rows, int64_t n, int64_t ld, int64_t t) {
+  const int go = item_mask_args(what, pointers, rows, n);
+  if (go <= 0) return go;
+  if (ld < n) { set_error("%s: ld = %lld < n = %lld", what, (long long)ld, (long long)n); return RAILS_EINVAL; }
+  if (t < 1 || t > 64) { set_error("%s: t = %lld targets per row outside [1, 64]", what, (long long)t); return RAILS_EINVAL; }
+  return 1;
+}
+
+int rails_scores_rank_keys(const float* scores, int64_t ld, int32_t rows, int64_t n, const int64_t* positions, int32_t t, uint64_t* keys_out, void* stream) {
+  g_err[0] = '\0';
+  if (rows == 0) return RAILS_OK;
+  const int go = rank_args("scores_rank_keys", scores && positions && keys_out, rows, n, ld, t);
+  return go <= 0 ? go : fail(scores_rank_keys(scores, ld, rows, n, positions, t, keys_out, (hipStream_t)stream), "scores_rank_keys");
+}
+
+int rails_scores_rank(const float* scores, int64_t ld, int32_t rows, int64_t n, const uint64_t* keys, int32_t t, const uint32_t* mask_words,
+                      int64_t words_row_stride, int32_t* ranks_out, void* stream) {
+  g_err[0] = '\0';
+  if (rows == 0) return RAILS_OK;
+  const int go = rank_args("scores_rank", scores && keys && ranks_out, rows, n, ld, t);
+  if (go <= 0) return go;
+  if (words_row_stride != 0 && words_row_stride < item_mask_words(n)) { set_error("scores_rank: the mask rows are shorter than n bits"); return RAILS_EINVAL; }
+  return fail(scores_rank(scores, ld, rows, n, keys, t, mask_words, words_row_stride, ranks_out, (hipStream_t)stream), "scores_rank");
+}
+
+int rails_item_mask_clear_rows(const int64_t* positions, int32_t rows, int64_t m, int64_t n, uint32_t* words, int64_t words_row_stride, void* stream) {
+  g_err[0] = '\0';
+  if (m < 0) { set_error("item_mask_clear_rows: m < 0"); return RAILS_EINVAL; }
+  if (rows == 0 || m == 0) return RAILS_OK;
+  const int go = item_mask_args("item_mask_clear_rows", positions && words, rows, n);
+  if (go <= 0) return go;
+  if (words_row_stride < item_mask_words(n)) { set_error("item_mask_clear_rows: the mask rows are shorter than n bits"); return RAILS_EINVAL; }
+  return fail(item_mask_clear_rows(positions, rows, m, n, words, words_row_stride, (hipStream_t)stream), "item_mask_clear_rows");
+}
+
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s) || n_items < 0) return 0;
   return (size_t)n_items * (size_t)s->dot_product_dimension * 2;

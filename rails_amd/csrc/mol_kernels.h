@@ -258,6 +258,12 @@ int item_mask_positions(const void* words, int rows, int64_t n, int64_t* out, in
 int scores_mask(float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const void* words, int64_t words_row_stride, float fill,
                 const int32_t* run_if, hipStream_t stream);
 
+// ---- exact ranks of given items (rank.hip): keys are the selection keys of topk_keys.h, masks the rows above ----
+int scores_rank_keys(const float* scores, int64_t ld, int rows, int64_t n, const int64_t* positions, int t, void* keys_out, hipStream_t stream);
+int scores_rank(const float* scores, int64_t ld, int rows, int64_t n, const void* keys, int t, const void* mask_words, int64_t words_row_stride,
+                int32_t* ranks_out, hipStream_t stream);
+int item_mask_clear_rows(const int64_t* positions, int rows, int64_t m, int64_t n, void* words, int64_t words_row_stride, hipStream_t stream);
+
 int dot_rowwise(const float* q, const float* items, int64_t Bq, int X, int D, int r, float* out, hipStream_t stream);
 
 size_t topk_workspace_bytes(int rows, int64_t n, int k);

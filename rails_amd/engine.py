@@ -1623,6 +1623,83 @@ def scores_mask(scores: torch.Tensor, mask: ItemMask, first_item: int = 0, fill:
     return scores
 
 
+# ---- exact ranks of given items (rails_scores_rank_keys, rails_scores_rank, rails_item_mask_clear_rows) ---------------------
+RANK_MAX_TARGETS = 64      # targets per row and launch (rails_scores_rank); scores_rank slices wider calls
+
+
+def scores_rank(scores: torch.Tensor, positions: torch.Tensor, mask: Optional[ItemMask] = None) -> torch.Tensor:
+    """(rows, t) int64: the rank of position positions[r, j] in row r of `scores` ((rows, n) fp32 with unit column stride) among the items of row
+    r's `mask` (None: all of them; an ItemMask, or its int32 words with one row for all or one per row) -- 1 + the number of eligible items whose selection key (score descending, then position ascending, on
+    the score's bits) is larger, so rank - 1 is the target's index in the row's exhaustive top-k list.  0: not ranked (a position outside
+    [0, n), such as the -1 of an unknown id, or a target outside the mask).  Every score is read once per RANK_MAX_TARGETS targets of its
+    row; no sync."""
+    _require_device(scores, "scores")
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError("scores must be (rows, n) fp32 with contiguous rows")
+    rows, n = scores.shape
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != rows:
+        raise ValueError(f"scores_rank: positions must be ({rows}, t) int64")
+    if positions.device != scores.device:
+        raise ValueError("scores_rank: the positions and the scores live on different devices")
+    mwords = None
+    if isinstance(mask, ItemMask):
+        if mask.n_items != n:
+            raise ValueError(f"scores_rank: {n} columns of scores against a mask of {mask.n_items} items")
+        mwords = mask.words
+    elif mask is not None:      # the words themselves (what item_mask_clear_rows edits: nobody has counted their bits)
+        if not torch.is_tensor(mask) or mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[1] < item_mask_words(n) or (mask.shape[1] > 1 and mask.stride(1) != 1):
+            raise ValueError(f"scores_rank: mask must be an ItemMask or its (rows, >= {item_mask_words(n)}) int32 words")
+        mwords = mask
+    if mwords is not None:
+        if mwords.shape[0] not in (1, rows):
+            raise ValueError(f"scores_rank: the mask has {mwords.shape[0]} rows but scores has {rows}")
+        if mwords.device != scores.device:
+            raise ValueError("scores_rank: the mask and the scores live on different devices")
+    t_all = positions.shape[1]
+    out = torch.empty((rows, t_all), dtype=torch.int64, device=scores.device)
+    if rows == 0 or t_all == 0:
+        return out
+    if n < 1:
+        raise ValueError("scores_rank: scores has no columns")
+    lib = _lib.load()
+    ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
+    words, stride = (None, 0) if mwords is None else (_ptr(mwords), 0 if mwords.shape[0] == 1 else mwords.stride(0))
+    with _on_device(scores.device):
+        for t0 in range(0, t_all, RANK_MAX_TARGETS):
+            pos = positions[:, t0 : t0 + RANK_MAX_TARGETS].contiguous()
+            t = pos.shape[1]
+            keys = torch.empty((rows, t), dtype=torch.int64, device=scores.device)      # (the 64-bit keys; never read as integers here)
+            ranks = torch.empty((rows, t), dtype=torch.int32, device=scores.device)
+            _lib.check(lib.rails_scores_rank_keys(_ptr(scores), ld, rows, n, _ptr(pos), t, _ptr(keys), _stream()), "rails_scores_rank_keys")
+            _lib.check(lib.rails_scores_rank(_ptr(scores), ld, rows, n, _ptr(keys), t, words, stride, _ptr(ranks), _stream()), "rails_scores_rank")
+            out[:, t0 : t0 + t] = ranks
+    return out
+
+
+def item_mask_clear_rows(words: torch.Tensor, positions: torch.Tensor, n_items: Optional[int] = None) -> torch.Tensor:
+    """In place: row r of `words` ((rows, >= words of n_items) int32 with unit column stride) loses the bits at positions[r, :] ((rows, m) int64);
+    positions outside [0, n_items) -- the -1 of an unknown id -- are skipped, repeats are harmless (rails_item_mask_clear_rows).  n_items
+    defaults to every bit of a row.  How a row's seen ids leave its mask; no sync."""
+    _require_device(words, "words")
+    if words.dim() != 2 or words.dtype != torch.int32 or (words.shape[1] > 1 and words.stride(1) != 1):
+        raise ValueError("words must be (rows, words) int32 with contiguous rows")
+    rows = words.shape[0]
+    n = 32 * words.shape[1] if n_items is None else int(n_items)
+    if n < 1 or item_mask_words(n) > words.shape[1]:
+        raise ValueError(f"item_mask_clear_rows: rows of {words.shape[1]} words do not hold {n} items")
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != rows:
+        raise ValueError(f"item_mask_clear_rows: positions must be ({rows}, m) int64")
+    if positions.device != words.device:
+        raise ValueError("item_mask_clear_rows: the positions and the words live on different devices")
+    if rows == 0 or positions.shape[1] == 0:
+        return words
+    pos = positions.contiguous()
+    with _on_device(words.device):
+        _lib.check(_lib.load().rails_item_mask_clear_rows(_ptr(pos), rows, pos.shape[1], n, _ptr(words), words.stride(0) if rows > 1 else max(words.shape[1], words.stride(0)),
+                                                          _stream()), "rails_item_mask_clear_rows")
+    return words
+
+
 # ---- item tags (rails_item_tags_*, rails_item_mask_from_tags, rails_scores_mask_tags; DESIGN section 3.15) ---------------------
 def tag_word_i32(word: int) -> int:
     """A 32-bit tag word as the int32 that holds its bit pattern."""

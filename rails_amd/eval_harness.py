@@ -81,9 +81,18 @@ def eval_metrics_v2_from_tensors(
     dtype: Optional[torch.dtype] = None,
     include_eval_time: bool = False,
     include_eval_top_k_ids: bool = False,
+    exact_ranks: bool = False,
 ) -> Dict[str, torch.Tensor]:
+    """exact_ranks (not in the reference): the target's rank comes from top_k_module.rank_of -- a count over all N scores -- instead of a search
+    of the top-MAX_K list: the same metric keys, uncapped (a target the row may not return, or one outside the corpus, ranks N + 1), so MRR
+    and HR at any k are exact.  The seen ids (filter_invalid_ids) leave a row's eligible set wherever the default path's filter removes them.  No top-k list exists on that path: include_eval_time / include_eval_top_k_ids with it raise ValueError."""
     if include_full_matrices:
         raise NotImplementedError("include_full_matrices is not supported (the (B, N) logit matrix is internal to the top-k modules)")
+    if exact_ranks:
+        if include_eval_time or include_eval_top_k_ids:
+            raise ValueError("exact_ranks=True computes no top-k list: include_eval_time and include_eval_top_k_ids need the default path")
+        if not hasattr(eval_state.top_k_module, "rank_of"):
+            raise NotImplementedError(f"exact_ranks=True: {type(eval_state.top_k_module).__name__} has no rank_of (MoLBruteForceTopK and MIPSBruteForceTopK do)")
     device = target_ids.device
     q = model.encode(
         past_lengths=seq_features.past_lengths,
@@ -119,7 +128,19 @@ def eval_metrics_v2_from_tensors(
             truncate_k_prime_to=truncate_k_prime_to,
         )
 
-    for mb in range(num_batches):
+    def ranks_of(mb: int) -> torch.Tensor:
+        sl = slice(mb * user_max_batch_size, (mb + 1) * user_max_batch_size)
+        payloads = {key: (v[sl] if torch.is_tensor(v) and v.dim() >= 1 and v.size(0) == n_rows else v)
+                    for key, v in seq_features.past_payloads.items()}
+        return eval_state.top_k_module.rank_of(q[sl, ...], target_ids[sl, :], invalid_ids=seq_features.past_ids[sl, :] if seen_leave else None, **payloads)
+
+    # Where the top-k' list cannot supply k unseen ids the default path's filter puts seen ids back, in list order (reference
+    # indexing/candidate_index.py:160-170): with k = N -- a corpus of at most MAX_K items -- every seen id returns to its place and the ranks are
+    # the unfiltered ones, so the exact path filters nothing there either.  (For MAX_K < N < MAX_K + the width of past_ids the default path puts
+    # back some of a row's seen ids; the exact path filters them all.)
+    seen_leave = filter_invalid_ids and k < eval_state.candidate_index.ids.size(1)
+
+    for mb in range(0 if exact_ranks else num_batches):
         if include_eval_time and random.random() < 0.1:  # time 10 % of the mini-batches: 3 warm-ups, 20 timed calls
             for _ in range(3):
                 call(mb)
@@ -132,11 +153,15 @@ def eval_metrics_v2_from_tensors(
         top_ids, top_prs, _ = call(mb)
         ids_all.append(top_ids)
         prs_all.append(top_prs)
-    eval_top_k_ids = ids_all[0] if num_batches == 1 else torch.cat(ids_all, dim=0)
+    if exact_ranks:
+        ranks = torch.cat([ranks_of(mb) for mb in range(num_batches)], dim=0)[:, 0]
+        eval_ranks = torch.where(ranks == 0, eval_state.candidate_index.ids.size(1) + 1, ranks)
+    else:
+        eval_top_k_ids = ids_all[0] if num_batches == 1 else torch.cat(ids_all, dim=0)
 
-    assert eval_top_k_ids.size(1) == k
-    _, rank_idx = torch.max(torch.cat([eval_top_k_ids, target_ids], dim=1) == target_ids, dim=1)
-    eval_ranks = torch.where(rank_idx == k, MAX_K + 1, rank_idx + 1)
+        assert eval_top_k_ids.size(1) == k
+        _, rank_idx = torch.max(torch.cat([eval_top_k_ids, target_ids], dim=1) == target_ids, dim=1)
+        eval_ranks = torch.where(rank_idx == k, MAX_K + 1, rank_idx + 1)
     zero = torch.zeros(1, dtype=torch.float32, device=device)
     output: Dict[str, torch.Tensor] = {}
     for kk in (1, 5, 10, 50, 100, 200):

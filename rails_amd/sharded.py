@@ -40,6 +40,8 @@ _GENERIC_WHY = "the single-device module runs there, and ShardedMoLBruteForceTop
 _TAGS_WHY = ("tags belong to the positions of ONE corpus and the sharded wrappers split theirs over the ranks: every rank would have to hold its slice "
              "of the tags and the global candidate counts would have to follow the filter (out of scope, DESIGN section 3.15); the single-device modules take it")
 _MASK_WHY = "a mask is by position of ONE corpus and the sharded wrappers split theirs over the ranks (out of scope, DESIGN section 3.13)"
+_RANK_WHY = ("the exact rank of an item is built on the single-device MoLBruteForceTopK: a sharded one would be a local count plus one sum all-reduce, "
+             "and needs the target's key on every rank (out of scope, DESIGN section 3.17)")
 
 
 def shard_bounds(n_items: int, world_size: int, rank: int) -> Tuple[int, int]:
@@ -296,6 +298,13 @@ class ShardedTopK(TopKModule):
 
     def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError(f"{type(self).__name__}.remove_items: shrinking an item-sharded corpus would move the shard bounds; build the shards again")
+
+    # ---- exact ranks: not built on the item-sharded wrappers ----------------------------------------------------------
+    def rank_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids=None, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}.rank_of: {_RANK_WHY}")
+
+    def rank_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids=None, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}.rank_of_positions: {_RANK_WHY}")
 
     # ---- hidden items: not built on the item-sharded wrappers -------------------------------------------------------
     def _refuse_hidden(self, what: str):

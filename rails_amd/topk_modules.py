@@ -817,6 +817,71 @@ class _CorpusEdits(_ItemsById):
         """Which path answered the collapsed calls so far: calls, walk_redos (depth doublings), fallbacks (exact group-maxima passes)."""
         return dict(self.__dict__.setdefault("_collapse_stats", {"calls": 0, "walk_redos": 0, "fallbacks": 0}))
 
+    # ---- rank_of: the exact rank of given items per query row (DESIGN section 3.17) ---------------------------------------------------------
+    # rank(b, x) = 1 + the number of items row b may return whose selection key (score descending, position ascending, on all_logits' bits)
+    # exceeds x's: the index of x in the row's exhaustive get_top_k_outputs list, plus one.  0: not ranked -- x is not in the corpus, is hidden,
+    # lies outside the call's item_mask= / allowed_tags=, or its id is among the row's invalid_ids.  Built on the exact modules, which supply
+    # _rank_scores; every other module refuses by name before any launch.
+    def _rank_scores(self, query_embeddings: torch.Tensor, **kwargs) -> Optional[torch.Tensor]:
+        """all_logits' (b, N) fp32 scores for these rows, unmasked (a recycled buffer will do: it is consumed before the next call); None on
+        the modules that have no exact rank."""
+        return None
+
+    def _refuse_rank_of(self, kwargs: dict, what: str) -> None:
+        if type(self)._rank_scores is _CorpusEdits._rank_scores:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: an approximate module ranks its candidates only; the exact rank of an item is "
+                                      "built on MoLBruteForceTopK (and MIPSBruteForceTopK) -- ask a MoLBruteForceTopK over the same corpus")
+        refuse_collapse_groups(self, kwargs, what)
+
+    def rank_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """(B, T) int64: the rank of the item carrying target_ids[b, j] ((B, T) integer ids, resolved through the live id map) for query row b;
+        0 where the corpus has no such item or the row may not return it.  invalid_ids (B, S): the row's seen ids, which leave its eligible
+        set (ids nobody has are ignored).  kwargs: what all_logits takes (user_ids, item_mask=, allowed_tags=)."""
+        self._refuse_rank_of(kwargs, "rank_of")
+        B = query_embeddings.size(0)
+        if not torch.is_tensor(target_ids) or target_ids.dim() != 2 or target_ids.shape[0] != B or target_ids.is_floating_point() or target_ids.dtype == torch.bool:
+            raise ValueError(f"rank_of: target_ids must be ({B}, T) integer ids")
+        positions = self.positions_of(target_ids.reshape(-1)).view(B, -1)
+        return self.rank_of_positions(query_embeddings, positions, invalid_ids, **kwargs)
+
+    def rank_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """rank_of for targets given as corpus POSITIONS ((B, T) int64; one outside [0, N), such as the -1 positions_of gives an unknown id, gets
+        rank 0)."""
+        self._refuse_rank_of(kwargs, "rank_of_positions")
+        B, N = query_embeddings.size(0), self.num_items
+        dev = self._ids_flat.device
+        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != B:
+            raise ValueError(f"rank_of_positions: positions must be ({B}, T) int64")
+        if invalid_ids is not None and (not torch.is_tensor(invalid_ids) or invalid_ids.dim() != 2 or invalid_ids.shape[0] != B
+                                        or invalid_ids.is_floating_point() or invalid_ids.dtype == torch.bool):
+            raise ValueError(f"rank_of_positions: invalid_ids must be ({B}, S) integer ids")
+        rows = int(getattr(self, "MAX_LOGIT_BYTES", 4 << 30)) // (N * 4)      # the logit policy: a slice of the batch at a time
+        if rows < 1:
+            raise NotImplementedError(f"{type(self).__name__}.rank_of: one row of {N} logits exceeds MAX_LOGIT_BYTES; a target's key must be read "
+                                      "from the matrix that is counted, and corpus chunks are not built")
+        bind = getattr(self, "one_bind", None)
+        with torch.inference_mode(), (bind() if bind is not None else contextlib.nullcontext()):
+            mask = self._take_item_mask(kwargs, B, None)      # the hidden set, allowed_tags= and item_mask= as one mask (its syncs are the call's only ones)
+            words = None if mask is None else mask.words
+            if invalid_ids is not None and invalid_ids.shape[1] > 0:
+                seen = self.positions_of(invalid_ids.reshape(-1)).view(B, -1)
+                # a per-row COPY of the mask (a shared row, or "every item", repeated), from which each row's seen positions are cleared
+                if words is None:
+                    words = E.visibility_row(N, dev).repeat(B, 1)
+                elif mask.shared:
+                    words = words.repeat(B, 1)
+                else:
+                    words = words.clone(memory_format=torch.contiguous_format)
+                E.item_mask_clear_rows(words, seen, N)
+            positions = positions.to(dev)
+            out = []
+            for b0 in range(0, B, rows):
+                b1 = min(B, b0 + rows)
+                kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kwargs.items()}
+                scores = self._rank_scores(query_embeddings[b0:b1], **kw)
+                out.append(E.scores_rank(scores, positions[b0:b1], None if words is None else words if words.shape[0] == 1 else words[b0:b1]))
+            return out[0] if len(out) == 1 else torch.cat(out, 0)
+
     @contextlib.contextmanager
     def _positions_as_ids(self):
         """Inside this block every call of the module returns POSITIONS where it returns ids: the id table is swapped for 0 .. N - 1, so whichever
@@ -1476,6 +1541,13 @@ class MoLBruteForceTopK(MoLTopKModule):
         else:
             logits = self._raw_logits(query_embeddings, **kwargs)
         return logits if mask is None else E.scores_mask(logits, mask)      # (a hidden set is part of `mask`: _take_item_mask)
+
+    def _rank_scores(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
+        """all_logits' scores -- the module's OWN precision: the fp32 companion in the exact modes -- unmasked, in the recycled logits buffer."""
+        eng = self._bind()
+        if eng.exact is not None and self._mol_module.engine() is not eng:
+            return self._all_logits_scratch(query_embeddings, _eng=eng.exact, _index=self._dense_fp32_index(), _tag="qpack32", **kwargs)
+        return self._all_logits_scratch(query_embeddings, **kwargs)
 
     # ---- item_mask=: a call restricted to a subset of the corpus (DESIGN section 3.13) ------------------------------------------------------
     # The call equals the same call on a module freshly constructed from the kept rows and their ids, bit for bit (scores are per item and
@@ -3209,6 +3281,9 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
             scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs)
             return ids, scores
         return None
+
+    def _rank_scores(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
+        return self._index.score(query_embeddings)
 
     def _own_score_chunks(self, query_embeddings: torch.Tensor, mask: Optional[E.ItemMask], **kwargs):
         logits = self._index.score(query_embeddings)
