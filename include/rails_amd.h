@@ -53,6 +53,7 @@ extern "C" {
  * and the generic route's candidate entries rails_mol_generic_score_indexed / rails_mol_generic_table_width / rails_mol_generic_coarse_build /
  * rails_mol_generic_coarse_update / rails_mol_generic_component_build / rails_mol_generic_component_update / rails_mol_generic_eq_pad
  * and the rank entries rails_scores_rank_keys / rails_scores_rank / rails_item_mask_clear_rows
+ * and the softmax entries rails_scores_lse[_workspace_bytes] / rails_scores_log_prob / rails_scores_gumbel
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -423,6 +424,32 @@ int rails_scores_rank(const float* scores, int64_t ld, int32_t rows, int64_t n, 
  * rails_item_mask_words(n)) are cleared, a 32-bit atomic AND-NOT each; positions outside [0, n) are skipped, repeats are harmless.  How a
  * row's seen ids leave its mask.  m = 0 or rows = 0: nothing to do. */
 int rails_item_mask_clear_rows(const int64_t* positions, int32_t rows, int64_t m, int64_t n, uint32_t* words, int64_t words_row_stride, void* stream);
+
+/* ---- softmax over the corpus (added under ABI 15: new entries only; no counterpart in the reference) ---------------------------------
+ * Over the eligible columns of row r of a (rows, n) fp32 score matrix with row stride ld (mask_words / words_row_stride as in
+ * rails_scores_rank: bit set = eligible, NULL = every column), with beta = inv_temperature, a finite fp32 > 0:
+ *   y(x) = fl32(x * beta),  Y = y(M) for M the largest eligible x,  S = sum over the eligible x of expf(y(x) - Y),
+ *   lse = fl32(Y + log S)  (the log, the add and every sum across lanes and workgroups in float64),  log_prob(x) = fl32(y(x) - lse).
+ * Special rows: nothing eligible, or -inf alone -> lse = -inf; any eligible NaN -> NaN; otherwise any eligible +inf -> +inf; an eligible
+ * -inf adds 0; one eligible finite entry -> lse = y.  0 <= rows <= 2^24 (rows = 0: nothing to do), 1 <= n < 2^31, ld >= n; rows may start
+ * at any 4-byte alignment.  RAILS_EINVAL for a NULL pointer, a size outside these or an inv_temperature that is not a finite number > 0. */
+/* lse_out[r], every entry written.  Two reads of the matrix (a row-maximum pass, then the sum with the known Y: no rescaling), per thread
+ * an fp32 chain of at most 16 terms, everything above it in float64 in a fixed order, no floating-point atomics: the same bits on every
+ * run.  workspace: rails_scores_lse_workspace_bytes(rows, n) bytes, 256-byte aligned (RAILS_ENOMEM if shorter). */
+size_t rails_scores_lse_workspace_bytes(int32_t rows, int64_t n);
+int rails_scores_lse(const float* scores, int64_t ld, int32_t rows, int64_t n, float inv_temperature, const uint32_t* mask_words, int64_t words_row_stride,
+                     void* workspace, size_t workspace_bytes, float* lse_out, void* stream);
+/* out[r * t + j] = fl32(y(scores[r * ld + p]) - lse[r]) for p = positions[r * t + j] when p lies inside [0, n) and is eligible, -inf
+ * otherwise.  Any t >= 1. */
+int rails_scores_log_prob(const float* scores, int64_t ld, int32_t rows, int64_t n, const int64_t* positions, int64_t t, float inv_temperature, const float* lse,
+                          const uint32_t* mask_words, int64_t words_row_stride, float* out, void* stream);
+/* Gumbel perturbation, out of place: out[r * out_ld + x] = fl32(y(x) + g(seed, first_row + r, x)) for eligible x, -inf for the others
+ * (out_ld >= n; out must not overlap scores).  g = -logf(-logf(u)), u = ((w >> 9) + 0.5) * 2^-23 in [2^-24, 1 - 2^-24], w = word 0 of
+ * Philox4x32-10 with counter (x, row & 0xFFFFFFFF, row >> 32, 0) and key (seed & 0xFFFFFFFF, seed >> 32), row = first_row + r >= 0: the noise
+ * of (seed, row, x) does not depend on how a batch is sliced, on the grid or on the alignment of a row.  The top-k of a perturbed row is a
+ * draw without replacement from softmax(scores / temperature) over the row's eligible columns, in draw order. */
+int rails_scores_gumbel(const float* scores, int64_t ld, int32_t rows, int64_t n, float inv_temperature, uint64_t seed, int64_t first_row,
+                        const uint32_t* mask_words, int64_t words_row_stride, float* out, int64_t out_ld, void* stream);
 
 /* Per-row candidates: out[bq * n_cand + x] = <queries[bq], items[bq / r][x]> for queries (n_queries, dim) and items
  * (n_queries / r, n_cand, dim) -- the two bmm branches of DotProductSimilarity.forward

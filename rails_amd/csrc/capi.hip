@@ -885,6 +885,51 @@ int rails_item_mask_clear_rows(const int64_t* positions, int32_t rows, int64_t m
   return fail(item_mask_clear_rows(positions, rows, m, n, words, words_row_stride, (hipStream_t)stream), "item_mask_clear_rows");
 }
 
+// ---- softmax over the corpus (softmax.hip) ----
+static int softmax_args(const char* what, bool pointers, int64_t rows, int64_t n, int64_t ld, float inv_temperature, int64_t words_row_stride) {
+  const int go = item_mask_args(what, pointers, rows, n);
+  if (go <= 0) return go;
+  if (ld < n) { set_error("%s: ld = %lld < n = %lld", what, (long long)ld, (long long)n); return RAILS_EINVAL; }
+  if (!(inv_temperature > 0.0f && inv_temperature <= 3.402823466e+38f)) { set_error("%s: inv_temperature = %g is not a finite number > 0", what, (double)inv_temperature); return RAILS_EINVAL; }
+  if (words_row_stride != 0 && words_row_stride < item_mask_words(n)) { set_error("%s: the mask rows are shorter than n bits", what); return RAILS_EINVAL; }
+  return 1;
+}
+
+size_t rails_scores_lse_workspace_bytes(int32_t rows, int64_t n) {
+  return rows > 0 && rows <= (1 << 24) && n > 0 && n < (1LL << 31) ? scores_lse_workspace_bytes(rows, n) : 0;
+}
+
+int rails_scores_lse(const float* scores, int64_t ld, int32_t rows, int64_t n, float inv_temperature, const uint32_t* mask_words, int64_t words_row_stride,
+                     void* workspace, size_t workspace_bytes, float* lse_out, void* stream) {
+  g_err[0] = '\0';
+  if (rows == 0) return RAILS_OK;
+  const int go = softmax_args("scores_lse", scores && workspace && lse_out, rows, n, ld, inv_temperature, words_row_stride);
+  if (go <= 0) return go;
+  if (workspace_bytes < scores_lse_workspace_bytes(rows, n)) { set_error("scores_lse: workspace too small"); return RAILS_ENOMEM; }
+  return fail(scores_lse(scores, ld, rows, n, inv_temperature, mask_words, words_row_stride, workspace, lse_out, (hipStream_t)stream), "scores_lse");
+}
+
+int rails_scores_log_prob(const float* scores, int64_t ld, int32_t rows, int64_t n, const int64_t* positions, int64_t t, float inv_temperature, const float* lse,
+                          const uint32_t* mask_words, int64_t words_row_stride, float* out, void* stream) {
+  g_err[0] = '\0';
+  if (rows == 0) return RAILS_OK;
+  const int go = softmax_args("scores_log_prob", scores && positions && lse && out, rows, n, ld, inv_temperature, words_row_stride);
+  if (go <= 0) return go;
+  if (t < 1) { set_error("scores_log_prob: t = %lld targets per row < 1", (long long)t); return RAILS_EINVAL; }
+  return fail(scores_log_prob(scores, ld, rows, n, positions, t, inv_temperature, lse, mask_words, words_row_stride, out, (hipStream_t)stream), "scores_log_prob");
+}
+
+int rails_scores_gumbel(const float* scores, int64_t ld, int32_t rows, int64_t n, float inv_temperature, uint64_t seed, int64_t first_row,
+                        const uint32_t* mask_words, int64_t words_row_stride, float* out, int64_t out_ld, void* stream) {
+  g_err[0] = '\0';
+  if (rows == 0) return RAILS_OK;
+  const int go = softmax_args("scores_gumbel", scores && out, rows, n, ld, inv_temperature, words_row_stride);
+  if (go <= 0) return go;
+  if (out_ld < n) { set_error("scores_gumbel: out_ld = %lld < n = %lld", (long long)out_ld, (long long)n); return RAILS_EINVAL; }
+  if (first_row < 0) { set_error("scores_gumbel: first_row < 0"); return RAILS_EINVAL; }
+  return fail(scores_gumbel(scores, ld, rows, n, inv_temperature, seed, first_row, mask_words, words_row_stride, out, out_ld, (hipStream_t)stream), "scores_gumbel");
+}
+
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s) || n_items < 0) return 0;
   return (size_t)n_items * (size_t)s->dot_product_dimension * 2;

@@ -264,6 +264,15 @@ int scores_rank(const float* scores, int64_t ld, int rows, int64_t n, const void
                 int32_t* ranks_out, hipStream_t stream);
 int item_mask_clear_rows(const int64_t* positions, int rows, int64_t m, int64_t n, void* words, int64_t words_row_stride, hipStream_t stream);
 
+// ---- softmax over the corpus (softmax.hip): beta = 1 / temperature, masks the rows above ----
+size_t scores_lse_workspace_bytes(int rows, int64_t n);
+int scores_lse(const float* scores, int64_t ld, int rows, int64_t n, float beta, const void* mask_words, int64_t words_row_stride, void* workspace,
+               float* lse_out, hipStream_t stream);
+int scores_log_prob(const float* scores, int64_t ld, int rows, int64_t n, const int64_t* positions, int64_t t, float beta, const float* lse,
+                    const void* mask_words, int64_t words_row_stride, float* out, hipStream_t stream);
+int scores_gumbel(const float* scores, int64_t ld, int rows, int64_t n, float beta, uint64_t seed, int64_t first_row, const void* mask_words,
+                  int64_t words_row_stride, float* out, int64_t out_ld, hipStream_t stream);
+
 int dot_rowwise(const float* q, const float* items, int64_t Bq, int X, int D, int r, float* out, hipStream_t stream);
 
 size_t topk_workspace_bytes(int rows, int64_t n, int k);

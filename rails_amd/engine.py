@@ -1627,6 +1627,27 @@ def scores_mask(scores: torch.Tensor, mask: ItemMask, first_item: int = 0, fill:
 RANK_MAX_TARGETS = 64      # targets per row and launch (rails_scores_rank); scores_rank slices wider calls
 
 
+def _row_mask_words(what: str, mask, scores: torch.Tensor) -> Optional[torch.Tensor]:
+    """The mask argument of the streaming passes over a (rows, n) score matrix (scores_rank, scores_lse, scores_log_prob, scores_gumbel) ->
+    its int32 words with one row for all or one per row, checked against `scores`; None: every item is eligible."""
+    rows, n = scores.shape
+    if mask is None:
+        return None
+    if isinstance(mask, ItemMask):
+        if mask.n_items != n:
+            raise ValueError(f"{what}: {n} columns of scores against a mask of {mask.n_items} items")
+        mwords = mask.words
+    else:      # the words themselves (what item_mask_clear_rows edits: nobody has counted their bits)
+        if not torch.is_tensor(mask) or mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[1] < item_mask_words(n) or (mask.shape[1] > 1 and mask.stride(1) != 1):
+            raise ValueError(f"{what}: mask must be an ItemMask or its (rows, >= {item_mask_words(n)}) int32 words")
+        mwords = mask
+    if mwords.shape[0] not in (1, rows):
+        raise ValueError(f"{what}: the mask has {mwords.shape[0]} rows but scores has {rows}")
+    if mwords.device != scores.device:
+        raise ValueError(f"{what}: the mask and the scores live on different devices")
+    return mwords
+
+
 def scores_rank(scores: torch.Tensor, positions: torch.Tensor, mask: Optional[ItemMask] = None) -> torch.Tensor:
     """(rows, t) int64: the rank of position positions[r, j] in row r of `scores` ((rows, n) fp32 with unit column stride) among the items of row
     r's `mask` (None: all of them; an ItemMask, or its int32 words with one row for all or one per row) -- 1 + the number of eligible items whose selection key (score descending, then position ascending, on
@@ -1641,20 +1662,7 @@ def scores_rank(scores: torch.Tensor, positions: torch.Tensor, mask: Optional[It
         raise ValueError(f"scores_rank: positions must be ({rows}, t) int64")
     if positions.device != scores.device:
         raise ValueError("scores_rank: the positions and the scores live on different devices")
-    mwords = None
-    if isinstance(mask, ItemMask):
-        if mask.n_items != n:
-            raise ValueError(f"scores_rank: {n} columns of scores against a mask of {mask.n_items} items")
-        mwords = mask.words
-    elif mask is not None:      # the words themselves (what item_mask_clear_rows edits: nobody has counted their bits)
-        if not torch.is_tensor(mask) or mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[1] < item_mask_words(n) or (mask.shape[1] > 1 and mask.stride(1) != 1):
-            raise ValueError(f"scores_rank: mask must be an ItemMask or its (rows, >= {item_mask_words(n)}) int32 words")
-        mwords = mask
-    if mwords is not None:
-        if mwords.shape[0] not in (1, rows):
-            raise ValueError(f"scores_rank: the mask has {mwords.shape[0]} rows but scores has {rows}")
-        if mwords.device != scores.device:
-            raise ValueError("scores_rank: the mask and the scores live on different devices")
+    mwords = _row_mask_words("scores_rank", mask, scores)
     t_all = positions.shape[1]
     out = torch.empty((rows, t_all), dtype=torch.int64, device=scores.device)
     if rows == 0 or t_all == 0:
@@ -1698,6 +1706,99 @@ def item_mask_clear_rows(words: torch.Tensor, positions: torch.Tensor, n_items: 
         _lib.check(_lib.load().rails_item_mask_clear_rows(_ptr(pos), rows, pos.shape[1], n, _ptr(words), words.stride(0) if rows > 1 else max(words.shape[1], words.stride(0)),
                                                           _stream()), "rails_item_mask_clear_rows")
     return words
+
+
+# ---- softmax over the corpus (rails_scores_lse, rails_scores_log_prob, rails_scores_gumbel) ---------------------------------
+def inv_temperature(temperature: float, what: str = "temperature") -> float:
+    """beta = fp32(1 / temperature) as the Python float that holds it; ValueError unless temperature is a finite number > 0 whose inverse is
+    a finite fp32 > 0."""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"{what}: temperature must be a finite number > 0, got {temperature!r}")
+    beta = C.c_float(1.0 / temperature).value      # (one rounding to nearest: numpy.float32(1.0 / temperature))
+    if not math.isfinite(beta) or beta <= 0:
+        raise ValueError(f"{what}: 1 / temperature is not a finite fp32 > 0 for temperature = {temperature!r}")
+    return beta
+
+
+def _softmax_args(what: str, scores: torch.Tensor, mask, temperature: float):
+    """The argument checks of scores_rank on the softmax passes -> (rows, n, ld, mask words pointer, their row stride, beta)."""
+    _require_device(scores, "scores")
+    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError("scores must be (rows, n) fp32 with contiguous rows")
+    beta = inv_temperature(temperature, what)
+    rows, n = scores.shape
+    mwords = _row_mask_words(what, mask, scores)
+    if rows > 0 and n < 1:
+        raise ValueError(f"{what}: scores has no columns")
+    ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
+    words, stride = (None, 0) if mwords is None else (_ptr(mwords), 0 if mwords.shape[0] == 1 else mwords.stride(0))
+    return rows, n, ld, words, stride, beta
+
+
+def scores_lse(scores: torch.Tensor, mask: Optional[ItemMask] = None, temperature: float = 1.0) -> torch.Tensor:
+    """(rows,) fp32: log sum exp(scores[r, x] / temperature) over the items x of row r's `mask` (as scores_rank takes it; None: all of them)
+    -- the normaliser of softmax(scores / temperature) over what the row may return (rails_scores_lse: two reads of the matrix, the same
+    bits on every run).  -inf for a row with nothing eligible (or -inf alone), NaN with an eligible NaN, otherwise +inf with an eligible
+    +inf.  No sync."""
+    rows, n, ld, words, stride, beta = _softmax_args("scores_lse", scores, mask, temperature)
+    out = torch.empty((rows,), dtype=torch.float32, device=scores.device)
+    if rows == 0:
+        return out
+    lib = _lib.load()
+    need = int(lib.rails_scores_lse_workspace_bytes(rows, n))
+    ws = torch.empty(need, dtype=torch.uint8, device=scores.device)
+    with _on_device(scores.device):
+        _lib.check(lib.rails_scores_lse(_ptr(scores), ld, rows, n, beta, words, stride, _ptr(ws), need, _ptr(out), _stream()), "rails_scores_lse")
+    return out
+
+
+def scores_log_prob(scores: torch.Tensor, positions: torch.Tensor, lse: torch.Tensor, mask: Optional[ItemMask] = None,
+                    temperature: float = 1.0) -> torch.Tensor:
+    """(rows, t) fp32: fl32(fl32(scores[r, p] / temperature) - lse[r]) for p = positions[r, j] -- the log-probability of item p under the
+    softmax whose normaliser scores_lse gave for the same mask and temperature --, -inf for a position outside [0, n) or outside row r's
+    `mask` (rails_scores_log_prob).  No sync."""
+    rows, n, ld, words, stride, beta = _softmax_args("scores_log_prob", scores, mask, temperature)
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != rows:
+        raise ValueError(f"scores_log_prob: positions must be ({rows}, t) int64")
+    if not torch.is_tensor(lse) or lse.dtype != torch.float32 or lse.shape != (rows,):
+        raise ValueError(f"scores_log_prob: lse must be ({rows},) fp32")
+    if positions.device != scores.device or lse.device != scores.device:
+        raise ValueError("scores_log_prob: the positions, the lse and the scores live on different devices")
+    t = positions.shape[1]
+    out = torch.empty((rows, t), dtype=torch.float32, device=scores.device)
+    if rows == 0 or t == 0:
+        return out
+    pos, lse = positions.contiguous(), lse.contiguous()
+    with _on_device(scores.device):
+        _lib.check(_lib.load().rails_scores_log_prob(_ptr(scores), ld, rows, n, _ptr(pos), t, beta, _ptr(lse), words, stride, _ptr(out), _stream()),
+                   "rails_scores_log_prob")
+    return out
+
+
+def scores_gumbel(scores: torch.Tensor, seed: int, first_row: int = 0, mask: Optional[ItemMask] = None, temperature: float = 1.0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(rows, n) fp32, out of place: scores / temperature + Gumbel noise on the items of row r's `mask`, -inf on the others
+    (rails_scores_gumbel).  The top-k of a perturbed row draws k items without replacement from softmax(scores / temperature) over the
+    row's eligible items, in draw order.  The noise is a function of (seed, first_row + r, column) alone -- Philox4x32-10 --: slicing a batch
+    and passing each slice's first row reproduces the unsliced call.  seed: an int in [0, 2^64).  out: a (rows, n) fp32 tensor with
+    contiguous rows that does not overlap `scores`.  No sync."""
+    rows, n, ld, words, stride, beta = _softmax_args("scores_gumbel", scores, mask, temperature)
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"scores_gumbel: seed must be an int in [0, 2^64), got {seed!r}")
+    if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row < 1 << 62:
+        raise ValueError(f"scores_gumbel: first_row must be an int >= 0, got {first_row!r}")
+    if out is None:
+        out = torch.empty((rows, n), dtype=torch.float32, device=scores.device)
+    elif (not torch.is_tensor(out) or out.shape != (rows, n) or out.dtype != torch.float32 or out.device != scores.device
+          or (n > 1 and out.stride(1) != 1) or (rows > 1 and out.stride(0) < n)):
+        raise ValueError(f"scores_gumbel: out must be a ({rows}, {n}) fp32 tensor with contiguous rows on the scores' device")
+    if rows == 0:
+        return out
+    out_ld = out.stride(0) if rows > 1 else max(n, out.stride(0))
+    with _on_device(scores.device):
+        _lib.check(_lib.load().rails_scores_gumbel(_ptr(scores), ld, rows, n, beta, seed, first_row, words, stride, _ptr(out), out_ld, _stream()),
+                   "rails_scores_gumbel")
+    return out
 
 
 # ---- item tags (rails_item_tags_*, rails_item_mask_from_tags, rails_scores_mask_tags; DESIGN section 3.15) ---------------------
@@ -1841,6 +1942,9 @@ def _pred(flag: Optional[torch.Tensor]):
     if flag.dtype != torch.int32 or not flag.is_cuda or flag.numel() < 1:
         raise ValueError("the launch predicate is an int32 device tensor")
     return _ptr(flag)
+
+
+TOPK_MAX_K = 16384      # the largest k rails_topk takes (the 64-bit keys one workgroup sorts in LDS)
 
 
 def topk(scores: torch.Tensor, k: int, ids: Optional[torch.Tensor] = None, sorted: bool = True,

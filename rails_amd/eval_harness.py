@@ -82,10 +82,14 @@ def eval_metrics_v2_from_tensors(
     include_eval_time: bool = False,
     include_eval_top_k_ids: bool = False,
     exact_ranks: bool = False,
+    nll: bool = False,
 ) -> Dict[str, torch.Tensor]:
     """exact_ranks (not in the reference): the target's rank comes from top_k_module.rank_of -- a count over all N scores -- instead of a search
     of the top-MAX_K list: the same metric keys, uncapped (a target the row may not return, or one outside the corpus, ranks N + 1), so MRR
-    and HR at any k are exact.  The seen ids (filter_invalid_ids) leave a row's eligible set wherever the default path's filter removes them.  No top-k list exists on that path: include_eval_time / include_eval_top_k_ids with it raise ValueError."""
+    and HR at any k are exact.  The seen ids (filter_invalid_ids) leave a row's eligible set wherever the default path's filter removes them.  No top-k list exists on that path: include_eval_time / include_eval_top_k_ids with it raise ValueError.
+    nll (not in the reference): adds output["nll"] = -top_k_module.log_prob_of(q, target_ids, ...)[:, 0], the target's negative log-likelihood
+    under the softmax over the items its row may return (the seen ids leave under the rule of exact_ranks; +inf for a target the row may not
+    return).  With or without exact_ranks; it costs one more dense pass over the corpus per mini-batch."""
     if include_full_matrices:
         raise NotImplementedError("include_full_matrices is not supported (the (B, N) logit matrix is internal to the top-k modules)")
     if exact_ranks:
@@ -93,6 +97,8 @@ def eval_metrics_v2_from_tensors(
             raise ValueError("exact_ranks=True computes no top-k list: include_eval_time and include_eval_top_k_ids need the default path")
         if not hasattr(eval_state.top_k_module, "rank_of"):
             raise NotImplementedError(f"exact_ranks=True: {type(eval_state.top_k_module).__name__} has no rank_of (MoLBruteForceTopK and MIPSBruteForceTopK do)")
+    if nll and not hasattr(eval_state.top_k_module, "log_prob_of"):
+        raise NotImplementedError(f"nll=True: {type(eval_state.top_k_module).__name__} has no log_prob_of (MoLBruteForceTopK and MIPSBruteForceTopK do)")
     device = target_ids.device
     q = model.encode(
         past_lengths=seq_features.past_lengths,
@@ -134,11 +140,19 @@ def eval_metrics_v2_from_tensors(
                     for key, v in seq_features.past_payloads.items()}
         return eval_state.top_k_module.rank_of(q[sl, ...], target_ids[sl, :], invalid_ids=seq_features.past_ids[sl, :] if seen_leave else None, **payloads)
 
+    def nll_of(mb: int) -> torch.Tensor:
+        sl = slice(mb * user_max_batch_size, (mb + 1) * user_max_batch_size)
+        payloads = {key: (v[sl] if torch.is_tensor(v) and v.dim() >= 1 and v.size(0) == n_rows else v)
+                    for key, v in seq_features.past_payloads.items()}
+        return -eval_state.top_k_module.log_prob_of(q[sl, ...], target_ids[sl, :], invalid_ids=seq_features.past_ids[sl, :] if seen_leave else None, **payloads)
+
     # Where the top-k' list cannot supply k unseen ids the default path's filter puts seen ids back, in list order (reference
     # indexing/candidate_index.py:160-170): with k = N -- a corpus of at most MAX_K items -- every seen id returns to its place and the ranks are
     # the unfiltered ones, so the exact path filters nothing there either.  (For MAX_K < N < MAX_K + the width of past_ids the default path puts
     # back some of a row's seen ids; the exact path filters them all.)
     seen_leave = filter_invalid_ids and k < eval_state.candidate_index.ids.size(1)
+    # (first: a module that refuses log_prob_of does so by name before the top-k work)
+    nll_values = torch.cat([nll_of(mb) for mb in range(num_batches)], dim=0)[:, 0] if nll else None
 
     for mb in range(0 if exact_ranks else num_batches):
         if include_eval_time and random.random() < 0.1:  # time 10 % of the mini-batches: 3 warm-ups, 20 timed calls
@@ -169,6 +183,8 @@ def eval_metrics_v2_from_tensors(
     for kk in (1, 5, 10, 50, 100, 200, 500, 1000):
         output[f"hr@{kk}"] = eval_ranks <= kk
     output["mrr"] = 1.0 / eval_ranks
+    if nll:
+        output["nll"] = nll_values
     if include_eval_time:
         output["eval_time"] = eval_time_all
     if include_eval_top_k_ids:

@@ -42,6 +42,8 @@ _TAGS_WHY = ("tags belong to the positions of ONE corpus and the sharded wrapper
 _MASK_WHY = "a mask is by position of ONE corpus and the sharded wrappers split theirs over the ranks (out of scope, DESIGN section 3.13)"
 _RANK_WHY = ("the exact rank of an item is built on the single-device MoLBruteForceTopK: a sharded one would be a local count plus one sum all-reduce, "
              "and needs the target's key on every rank (out of scope, DESIGN section 3.17)")
+_SOFTMAX_WHY = ("the softmax over the corpus is built on the single-device MoLBruteForceTopK: a sharded one would merge the shards' (max, sum) pairs, "
+                "which combine associatively, in one all-gather (out of scope, DESIGN section 3.18)")
 
 
 def shard_bounds(n_items: int, world_size: int, rank: int) -> Tuple[int, int]:
@@ -305,6 +307,22 @@ class ShardedTopK(TopKModule):
 
     def rank_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids=None, **kwargs):
         raise NotImplementedError(f"{type(self).__name__}.rank_of_positions: {_RANK_WHY}")
+
+    # ---- softmax over the corpus: not built on the item-sharded wrappers ----------------------------------------------
+    def _refuse_softmax(self, what: str):
+        raise NotImplementedError(f"{type(self).__name__}.{what}: {_SOFTMAX_WHY}")
+
+    def log_partition(self, query_embeddings: torch.Tensor, invalid_ids=None, temperature: float = 1.0, **kwargs):
+        self._refuse_softmax("log_partition")
+
+    def log_prob_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids=None, temperature: float = 1.0, **kwargs):
+        self._refuse_softmax("log_prob_of")
+
+    def log_prob_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids=None, temperature: float = 1.0, **kwargs):
+        self._refuse_softmax("log_prob_of_positions")
+
+    def sample_items(self, query_embeddings: torch.Tensor, num_samples: int, seed: int, temperature: float = 1.0, invalid_ids=None, **kwargs):
+        self._refuse_softmax("sample_items")
 
     # ---- hidden items: not built on the item-sharded wrappers -------------------------------------------------------
     def _refuse_hidden(self, what: str):

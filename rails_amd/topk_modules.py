@@ -827,9 +827,9 @@ class _CorpusEdits(_ItemsById):
         the modules that have no exact rank."""
         return None
 
-    def _refuse_rank_of(self, kwargs: dict, what: str) -> None:
+    def _refuse_rank_of(self, kwargs: dict, what: str, thing: str = "the exact rank of an item") -> None:
         if type(self)._rank_scores is _CorpusEdits._rank_scores:
-            raise NotImplementedError(f"{type(self).__name__}.{what}: an approximate module ranks its candidates only; the exact rank of an item is "
+            raise NotImplementedError(f"{type(self).__name__}.{what}: an approximate module ranks its candidates only; {thing} is "
                                       "built on MoLBruteForceTopK (and MIPSBruteForceTopK) -- ask a MoLBruteForceTopK over the same corpus")
         refuse_collapse_groups(self, kwargs, what)
 
@@ -859,6 +859,18 @@ class _CorpusEdits(_ItemsById):
         if rows < 1:
             raise NotImplementedError(f"{type(self).__name__}.rank_of: one row of {N} logits exceeds MAX_LOGIT_BYTES; a target's key must be read "
                                       "from the matrix that is counted, and corpus chunks are not built")
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            positions = positions.to(dev)
+            out = [E.scores_rank(scores, positions[b0:b1], words) for b0, b1, scores, words in slices]
+            return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+    @contextlib.contextmanager
+    def _eligible_rows(self, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], kwargs: dict, rows: int):
+        """The host flow of the streaming passes over all_logits (rank_of, log_partition, log_prob_of, sample_items): inside the block (inference
+        mode, one bind) the value is a generator of (b0, b1, scores, words) over batch slices of at most `rows` rows -- scores: _rank_scores of
+        the slice (a recycled buffer: consumed before the next step), words: the eligible items of these rows as engine.scores_rank takes
+        them (None: every item)."""
+        B, N = query_embeddings.size(0), self.num_items
         bind = getattr(self, "one_bind", None)
         with torch.inference_mode(), (bind() if bind is not None else contextlib.nullcontext()):
             mask = self._take_item_mask(kwargs, B, None)      # the hidden set, allowed_tags= and item_mask= as one mask (its syncs are the call's only ones)
@@ -867,20 +879,98 @@ class _CorpusEdits(_ItemsById):
                 seen = self.positions_of(invalid_ids.reshape(-1)).view(B, -1)
                 # a per-row COPY of the mask (a shared row, or "every item", repeated), from which each row's seen positions are cleared
                 if words is None:
-                    words = E.visibility_row(N, dev).repeat(B, 1)
+                    words = E.visibility_row(N, self._ids_flat.device).repeat(B, 1)
                 elif mask.shared:
                     words = words.repeat(B, 1)
                 else:
                     words = words.clone(memory_format=torch.contiguous_format)
                 E.item_mask_clear_rows(words, seen, N)
-            positions = positions.to(dev)
-            out = []
-            for b0 in range(0, B, rows):
-                b1 = min(B, b0 + rows)
-                kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kwargs.items()}
-                scores = self._rank_scores(query_embeddings[b0:b1], **kw)
-                out.append(E.scores_rank(scores, positions[b0:b1], None if words is None else words if words.shape[0] == 1 else words[b0:b1]))
+
+            def slices():
+                for b0 in range(0, B, rows):
+                    b1 = min(B, b0 + rows)
+                    kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kwargs.items()}
+                    yield b0, b1, self._rank_scores(query_embeddings[b0:b1], **kw), None if words is None else words if words.shape[0] == 1 else words[b0:b1]
+
+            yield slices()
+
+    # ---- softmax over the corpus: log_partition, log_prob_of, sample_items -------------------------------------------------
+    # Over the items row b may return -- rank_of's eligible set -- with beta = fp32(1 / temperature): log_partition = log sum exp(logit * beta),
+    # log_prob_of = logit * beta - log_partition, sample_items = draws without replacement from that softmax (Gumbel top-k).  Built on
+    # _rank_scores like rank_of, with its refusals.
+    def _softmax_call(self, what: str, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], temperature: float, kwargs: dict,
+                      matrices: int = 1) -> int:
+        """The checks of a softmax call, before any launch -> the rows of a batch slice under the logit policy (`matrices` (b, N) matrices live)."""
+        self._refuse_rank_of(kwargs, what, "the softmax over every item of the corpus")
+        E.inv_temperature(temperature, f"{type(self).__name__}.{what}")
+        B, N = query_embeddings.size(0), self.num_items
+        if invalid_ids is not None and (not torch.is_tensor(invalid_ids) or invalid_ids.dim() != 2 or invalid_ids.shape[0] != B
+                                        or invalid_ids.is_floating_point() or invalid_ids.dtype == torch.bool):
+            raise ValueError(f"{what}: invalid_ids must be ({B}, S) integer ids")
+        rows = int(getattr(self, "MAX_LOGIT_BYTES", 4 << 30)) // (N * 4 * matrices)
+        if rows < 1:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: {'two rows' if matrices == 2 else 'one row'} of {N} logits exceed"
+                                      f"{'' if matrices == 2 else 's'} MAX_LOGIT_BYTES; the normaliser needs every item of a row, and corpus chunks are not built")
+        return rows
+
+    def log_partition(self, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, temperature: float = 1.0, **kwargs) -> torch.Tensor:
+        """(B,) fp32: log sum exp(logit / temperature) over the items query row b may return -- all_logits' bits, the hidden set, the call's
+        item_mask= / allowed_tags= and the row's invalid_ids honoured as rank_of honours them --, the normaliser that turns a score of
+        get_top_k_outputs into a log-probability.  -inf for a row that may return nothing.  One dense pass and two reads of its matrix."""
+        rows = self._softmax_call("log_partition", query_embeddings, invalid_ids, temperature, kwargs)
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            out = [E.scores_lse(scores, words, temperature) for _, _, scores, words in slices]
             return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+    def log_prob_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, temperature: float = 1.0,
+                    **kwargs) -> torch.Tensor:
+        """(B, T) fp32: the log-probability of the item carrying target_ids[b, j] under softmax(logits / temperature) over the items query row
+        b may return: fp32(logit * beta) - log_partition.  -inf where the corpus has no such item or the row may not return it."""
+        self._softmax_call("log_prob_of", query_embeddings, invalid_ids, temperature, kwargs)
+        B = query_embeddings.size(0)
+        if not torch.is_tensor(target_ids) or target_ids.dim() != 2 or target_ids.shape[0] != B or target_ids.is_floating_point() or target_ids.dtype == torch.bool:
+            raise ValueError(f"log_prob_of: target_ids must be ({B}, T) integer ids")
+        positions = self.positions_of(target_ids.reshape(-1)).view(B, -1)
+        return self.log_prob_of_positions(query_embeddings, positions, invalid_ids, temperature, **kwargs)
+
+    def log_prob_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None,
+                              temperature: float = 1.0, **kwargs) -> torch.Tensor:
+        """log_prob_of for targets given as corpus POSITIONS ((B, T) int64; one outside [0, N) gets -inf)."""
+        rows = self._softmax_call("log_prob_of_positions", query_embeddings, invalid_ids, temperature, kwargs)
+        B = query_embeddings.size(0)
+        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != B:
+            raise ValueError(f"log_prob_of_positions: positions must be ({B}, T) int64")
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            positions = positions.to(self._ids_flat.device)
+            out = [E.scores_log_prob(scores, positions[b0:b1], E.scores_lse(scores, words, temperature), words, temperature)
+                   for b0, b1, scores, words in slices]
+            return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+    def sample_items(self, query_embeddings: torch.Tensor, num_samples: int, seed: int, temperature: float = 1.0,
+                     invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(ids (B, S) int64, log_probs (B, S) fp32): S = num_samples items per query row drawn WITHOUT replacement from softmax(logits /
+        temperature) over the items the row may return, in draw order, each with its log-probability under that softmax (log_prob_of's
+        value; the probability of the FIRST draw).  Gumbel top-k: engine.scores_gumbel, then the exact top-k of the perturbed matrix.  A row
+        with fewer than S items of non-zero probability ends in (-1, -inf) entries.  seed: an int in [0, 2^64); the noise of (seed, batch row,
+        item position) does not depend on how the logit policy slices the batch.  Two (b, N) matrices live per slice."""
+        rows = self._softmax_call("sample_items", query_embeddings, invalid_ids, temperature, kwargs, matrices=2)
+        B, N = query_embeddings.size(0), self.num_items
+        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or not 1 <= num_samples <= min(N, E.TOPK_MAX_K):
+            raise ValueError(f"sample_items: num_samples must be an int in [1, {min(N, E.TOPK_MAX_K)}] (the corpus holds {N} items, the exact top-k "
+                             f"takes k <= {E.TOPK_MAX_K}), got {num_samples!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"sample_items: seed must be an int in [0, 2^64), got {seed!r}")
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            ids_out, lp_out = [], []
+            perturbed = torch.empty((min(rows, B), N), dtype=torch.float32, device=self._ids_flat.device)      # the second matrix, shared by the slices
+            for b0, b1, scores, words in slices:
+                noisy = E.scores_gumbel(scores, seed, b0, words, temperature, out=perturbed[: b1 - b0])
+                top, pos = E.topk(noisy, num_samples)
+                lp = E.scores_log_prob(scores, pos, E.scores_lse(scores, words, temperature), words, temperature)
+                drawn = top != float("-inf")      # (a perturbed -inf: an item outside the row's eligible set, or one of probability zero)
+                ids_out.append(torch.where(drawn, self._ids_flat[pos], -1))
+                lp_out.append(torch.where(drawn, lp, float("-inf")))
+            return (ids_out[0], lp_out[0]) if len(ids_out) == 1 else (torch.cat(ids_out, 0), torch.cat(lp_out, 0))
 
     @contextlib.contextmanager
     def _positions_as_ids(self):
