@@ -6,31 +6,15 @@
 //   topk_keys_kernel       the k largest keys of every row of that table, by MSD radix selection, decoded (rails_topk_keys)
 // The kernels see DENSE group ranks (int32 in [0, G), every ungrouped item a rank of its own), never the callers' sparse keys.
 #include "mol_kernels.h"
+#include "score_rows.h"
 #include "topk_keys.h"
+#include "wave_ops.h"
 
 namespace mol {
 
 constexpr int kCollapseThreads = kSortThreads;       // 1024: the in-LDS sorts' workgroup
 constexpr int kCollapseMaxDepth = 16384;             // entries of one ranked list: what lds_sort_desc sorts
 constexpr int kSeenTile = 256;                       // seen ids held in LDS at a time
-
-// block-wide exclusive scan of one int per thread (shuffle scan inside each wave, the wave totals through LDS); `total`: the sum.
-// All threads call; two barriers.
-template <int NT>
-__device__ __forceinline__ int collapse_exclusive_scan(int v, int* totals, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-  if (lane == 63) totals[wv] = inc;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-#pragma unroll
-  for (int t = 0; t < NT / 64; ++t) { const int tv = totals[t]; if (t < wv) base += tv; total += tv; }
-  __syncthreads();
-  return base + inc - v;
-}
 
 // ---- the walk ----------------------------------------------------------------------------------------------------
 // Entry j of a row is ELIGIBLE iff its position is one of the corpus, its score is above -inf (what the masks write) and its id is not in
@@ -90,7 +74,7 @@ __global__ __launch_bounds__(kCollapseThreads) void collapse_walk_kernel(
   int c = 0;
   for (int j = s0; j < s1; ++j) c += surv[j];
   int total;
-  int o = collapse_exclusive_scan<kCollapseThreads>(c, wave_tot, total);
+  int o = block_scan_excl<kCollapseThreads>(c, wave_tot, total);
   for (int j = s0; j < s1 && o < k; ++j) {
     if (!surv[j]) continue;
     const int64_t p = prow[j];
@@ -126,7 +110,7 @@ int topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int
     return kErrLaunch;
   hipLaunchKernelGGL(collapse_walk_kernel, dim3(rows), dim3(kCollapseThreads), lds, stream, scores, ld, positions, depth, npad, sort_slots, ranks,
                      n_items, ids, invalid, width, k, out_scores, out_pos, out_ids, out_counts, out_of_range);
-  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+  return launched();
 }
 
 // ---- the exact fallback: per-group maxima of a score matrix ---------------------------------------------------------------------------
@@ -179,7 +163,7 @@ int scores_group_max(const float* scores, int64_t ld, int rows, int64_t n, int64
   const unsigned int blocks = (unsigned int)((n + kGroupMaxChunk - 1) / kGroupMaxChunk);
   hipLaunchKernelGGL(group_max_kernel, dim3(blocks, rows), dim3(kGroupMaxThreads), sizeof(unsigned long long) * (size_t)width, stream, scores, ld, n,
                      first_item, ranks, n_groups, table, ids, invalid, width);
-  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+  return launched();
 }
 
 // ---- top-k of a key table -------------------------------------------------------------------------------------------
@@ -205,8 +189,7 @@ __global__ __launch_bounds__(kKeysThreads) void topk_keys_kernel(const unsigned 
   __syncthreads();
   unsigned int nz = 0u;
   for (int64_t g = tid; g < n_groups; g += kKeysThreads) nz += trow[g] != 0ull ? 1u : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) nz += (unsigned int)__shfl_xor((int)nz, o, 64);
+  nz = wave_sum(nz);
   if ((tid & 63) == 0 && nz) atomicAdd(&nonzero, nz);
   __syncthreads();
   const unsigned int kk = nonzero < (unsigned int)k ? nonzero : (unsigned int)k;
@@ -264,7 +247,7 @@ int topk_keys(const unsigned long long* table, int rows, int64_t n_groups, int k
   if (k > kKeysMaxK) { set_error("topk_keys: k = %d beyond %d", k, kKeysMaxK); return kErrUnsupported; }
   if (n_groups < 1) { set_error("topk_keys: no groups"); return kErrInvalid; }
   hipLaunchKernelGGL(topk_keys_kernel, dim3(rows), dim3(kKeysThreads), 0, stream, table, n_groups, k, ids, out_scores, out_pos, out_ids, out_counts);
-  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+  return launched();
 }
 
 }  // namespace mol

@@ -12,10 +12,12 @@
 //   scores_mask scores[b][x] = fill where bit first_item + x of row b's mask is clear; kept entries are neither read nor written
 //   item tags    effective tags, kept counts per allow word, a filter's mask rows, scores[r][x] = fill where item x carries
 //               no bit of row r's allow word
-// All plain C++ with vector stores, no LDS beyond the 4-word reductions, every loop grid-strided with 64-bit indices (rows of 125 M bits).
+// All plain C++ with vector stores, no LDS beyond the 4-word reductions (wave_ops.h), every loop grid-strided with 64-bit indices (rows of 125 M bits).
 #include <hip/hip_runtime.h>
 
 #include "mol_kernels.h"
+#include "score_rows.h"
+#include "wave_ops.h"
 
 namespace mol {
 
@@ -28,50 +30,11 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kTileWords = kThreads;               // one word per thread
 constexpr int64_t kTileBits = 32 * kTileWords;     // 8 192 items per compaction tile
-constexpr unsigned kMaxGrid = 1u << 16;
-
-inline unsigned grid_for(int64_t blocks) { return (unsigned)(blocks < 1 ? 1 : blocks > (int64_t)kMaxGrid ? (int64_t)kMaxGrid : blocks); }
 
 // the word `w` of a row of n bits with the bits at or past n cleared
 __device__ __forceinline__ u32 live_bits(u32 word, int64_t w, int64_t n) {
   const int64_t left = n - w * 32;
   return left >= 32 ? word : left <= 0 ? 0u : word & ((1u << (int)left) - 1u);
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// sum over the workgroup, returned to every thread (two barriers: `part` may be reused at once)
-__device__ __forceinline__ int block_sum(int v, int* part) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-  for (int w = 0; w < kWaves; ++w) s += part[w];
-  __syncthreads();
-  return s;
-}
-
-// exclusive prefix sum over the workgroup in thread order; *total: the workgroup's sum
-__device__ __forceinline__ int block_scan_excl(int v, int* part, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += up;
-  }
-  if (lane == 63) part[wave] = inc;
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wave) before += part[w];
-    all += part[w];
-  }
-  __syncthreads();
-  *total = all;
-  return before + inc - v;
 }
 
 }  // namespace
@@ -111,7 +74,7 @@ __global__ void __launch_bounds__(kThreads) item_mask_count_kernel(const u32* __
   const int64_t row = blockIdx.x;
   int c = 0;
   for (int64_t w = threadIdx.x; w < n_words; w += kThreads) c += __popc(live_bits(words[row * n_words + w], w, n));
-  c = block_sum(c, part);
+  c = block_sum<kThreads>(c, part);
   if (threadIdx.x == 0) counts[row] = c;
 }
 
@@ -124,7 +87,7 @@ __global__ void __launch_bounds__(kThreads) item_mask_tile_counts_kernel(const u
     const int64_t row = c / tiles, t = c - row * tiles;
     const int64_t w = t * kTileWords + threadIdx.x;
     const int bits = w < n_words ? __popc(live_bits(words[row * n_words + w], w, n)) : 0;
-    const int s = block_sum(bits, part);
+    const int s = block_sum<kThreads>(bits, part);
     if (threadIdx.x == 0) ws[c] = s;
   }
 }
@@ -139,7 +102,7 @@ __global__ void __launch_bounds__(kThreads) item_mask_tile_scan_kernel(int rows,
     const int64_t t = base + threadIdx.x;
     const int v = t < tiles ? (int)counts[t] : 0;      // at most kTileBits
     int all;
-    const int excl = block_scan_excl(v, part, &all);
+    const int excl = block_scan_excl<kThreads>(v, part, all);
     if (t < tiles) counts[t] = running + excl;
     running += all;
   }
@@ -155,7 +118,7 @@ __global__ void __launch_bounds__(kThreads) item_mask_tile_write_kernel(const u3
     const int64_t w = t * kTileWords + threadIdx.x;
     u32 word = w < n_words ? live_bits(words[row * n_words + w], w, n) : 0u;
     int all;
-    int64_t slot = ws[c] + block_scan_excl(__popc(word), part, &all);
+    int64_t slot = ws[c] + block_scan_excl<kThreads>(__popc(word), part, all);
     int64_t* dst = out + row * out_ld;
     while (word) {
       const int bit = __ffs((int)word) - 1;
@@ -215,7 +178,7 @@ __global__ void __launch_bounds__(kThreads) item_tags_count_kernel(const u32* __
   const u32 word = words[blockIdx.x];
   int c = 0;
   for (int64_t i = threadIdx.x; i < n; i += kThreads) c += (eff[i] & word) != 0u;
-  c = block_sum(c, part);
+  c = block_sum<kThreads>(c, part);
   if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
@@ -253,8 +216,6 @@ __global__ void __launch_bounds__(kThreads) scores_tags_fill_kernel(float* __res
     }
   }
 }
-
-static inline int launched() { return hipGetLastError() == hipSuccess ? kOk : kErrLaunch; }
 
 int item_tags_effective(const void* tags, const void* visible, int64_t n, void* eff, hipStream_t stream) {
   hipLaunchKernelGGL(item_tags_effective_kernel, dim3(grid_for((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, (const u32*)tags, (const u32*)visible,

@@ -20,14 +20,16 @@
 //   gumbel   out of place: out[r, x] = fl32(y(x) + g(seed, first_row + r, x)) for eligible x, -inf otherwise; g = -logf(-logf(u)),
 //            u = ((w >> 9) + 0.5) * 2^-23 (exact in fp32, inside [2^-24, 1 - 2^-24]), w = word 0 of Philox4x32-10 with counter
 //            (x, row & 0xFFFFFFFF, row >> 32, 0) and key (seed & 0xFFFFFFFF, seed >> 32): the noise depends on (seed, global row, x) alone
-// The row geometry of the order-independent passes (max, gumbel) is scores_rank_kernel's (rank.hip): head + aligned float4 body + tail, head
-// and tail peeled onto chunk 0, mask words loaded once per wave and handed to the lanes by shuffles, a grid-y loop over the rows.  Plain C++
-// with vector stores; every index is tested against n before it is used.
+// The order-independent passes (max, gumbel) run on the masked row walk of score_rows.h, which rank.hip shares; the sum keeps a walk of its
+// own and takes the constants and mask_bit from there, the wave sum from wave_ops.h.  Plain C++ with vector stores; every index is tested
+// against n before it is used.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "mol_kernels.h"
+#include "score_rows.h"
+#include "wave_ops.h"
 
 namespace mol {
 
@@ -36,52 +38,14 @@ namespace {
 typedef unsigned int u32;
 typedef unsigned long long u64;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kRowWalkThreads;
 constexpr int kWaves = kThreads / 64;
-constexpr int kIters = 4;                                   // 16-byte loads per thread: the fp32 chain of the sum has 4 * kIters = 16 terms
-constexpr int64_t kChunkVecs = (int64_t)kThreads * kIters;  // 1 024 float4 = 4 096 columns per workgroup
-constexpr unsigned kMaxGridY = 65535u;
-constexpr unsigned kMaxGrid = 1u << 16;
-
-inline unsigned grid_for(int64_t blocks) { return (unsigned)(blocks < 1 ? 1 : blocks > (int64_t)kMaxGrid ? (int64_t)kMaxGrid : blocks); }
-inline int64_t chunks_of(int64_t n) { return ((n + 3) / 4 + kChunkVecs - 1) / kChunkVecs; }      // (a row's aligned middle holds at most n / 4 float4)
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// a row as head + q aligned float4 + tail
-struct RowShape {
-  int64_t head, q, tail0;
-};
-
-__device__ __forceinline__ RowShape row_shape(const float* srow, int64_t n) {
-  const int64_t lead = (int64_t)((4u - (u32)(((uintptr_t)srow >> 2) & 3u)) & 3u);
-  RowShape s;
-  s.head = lead < n ? lead : n;
-  s.q = (n - s.head) >> 2;
-  s.tail0 = s.head + 4 * s.q;
-  return s;
-}
-
-// the mask bits of the four columns from x0, for the wave whose first column is xw (256 consecutive columns: at most 9 mask words, one load
-// per word, handed to the lanes by shuffles); every lane of the wave calls it
-__device__ __forceinline__ u32 wave_mask_bits(const u32* mrow, int64_t n_words, int64_t xw, int64_t x0, int lane) {
-  const int64_t wi = (xw >> 5) + lane;
-  const u32 wv = lane < 10 && wi < n_words ? mrow[wi] : 0u;
-  const int rel = (int)((x0 >> 5) - (xw >> 5));
-  const u32 lo = __shfl(wv, rel, 64), hi = __shfl(wv, rel + 1, 64);
-  return (u32)((((u64)hi << 32) | lo) >> (int)(x0 & 31)) & 0xFu;
-}
-
-__device__ __forceinline__ bool mask_bit(const u32* mrow, int64_t x) { return ((mrow[x >> 5] >> (int)(x & 31)) & 1u) != 0u; }
+constexpr int kIters = kRowWalkIters;      // the fp32 chain of the sum has 4 * kIters = 16 terms
 
 // NaN absorbs, otherwise the larger: commutative and associative, so any order of combination gives the same value
 __device__ __forceinline__ float max_or_nan(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b); }
 
 __device__ __forceinline__ float scaled(float x, float beta) { return __fmul_rn(x, beta); }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {      // xor butterfly: every lane ends with the same bits, in an order fixed by the lane ids
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 // word 0 of Philox4x32-10 (Salmon et al., SC'11) for counter (c0, c1, c2, 0) and key (k0, k1)
 __device__ __forceinline__ u32 philox4x32_10_word0(u32 c0, u32 c1, u32 c2, u32 k0, u32 k1) {
@@ -118,28 +82,18 @@ __global__ void __launch_bounds__(kThreads) scores_lse_max_kernel(const float* _
   for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
     const float* srow = scores + row * ld;
     const u32* mrow = MASKED ? words + row * words_row_stride : nullptr;
-    const RowShape rs = row_shape(srow, n);
     float m = -INFINITY;
-    const int64_t v0 = (int64_t)blockIdx.x * kChunkVecs;
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-      const int64_t vw = v0 + (int64_t)it * kThreads + wave * 64;
-      if (vw >= rs.q) break;                                           // (wave-uniform)
-      const int64_t v = vw + lane;
-      const int64_t xw = rs.head + 4 * vw, x0 = rs.head + 4 * v;
-      const u32 bits = MASKED ? wave_mask_bits(mrow, n_words, xw, x0, lane) : 0xFu;
-      if (v < rs.q) {
-        const float4 s = *reinterpret_cast<const float4*>(srow + x0);
-        if (bits & 1u) m = max_or_nan(m, s.x);
-        if (bits & 2u) m = max_or_nan(m, s.y);
-        if (bits & 4u) m = max_or_nan(m, s.z);
-        if (bits & 8u) m = max_or_nan(m, s.w);
-      }
-    }
-    if (blockIdx.x == 0 && tid < 8) {      // the peeled head (threads 0..3) and tail (threads 4..7): at most 3 columns each
-      const int64_t x = tid < 4 ? tid : rs.tail0 + (tid - 4);
-      if ((tid < 4 ? x < rs.head : x < n) && (!MASKED || mask_bit(mrow, x))) m = max_or_nan(m, srow[x]);
-    }
+    for_row_chunk<MASKED>(
+        srow, n, mrow, n_words,
+        [&](int64_t, float4 s, u32 bits) {
+          if (bits & 1u) m = max_or_nan(m, s.x);
+          if (bits & 2u) m = max_or_nan(m, s.y);
+          if (bits & 4u) m = max_or_nan(m, s.z);
+          if (bits & 8u) m = max_or_nan(m, s.w);
+        },
+        [&](int64_t, float s, bool keep) {
+          if (keep) m = max_or_nan(m, s);
+        });
     for (int d = 32; d > 0; d >>= 1) m = max_or_nan(m, __shfl_xor(m, d, 64));
     if (lane == 0) wave_max[wave] = m;
     __syncthreads();
@@ -183,7 +137,7 @@ __global__ void __launch_bounds__(kThreads) scores_lse_sum_kernel(const float* _
     const int64_t q = n >> 2;
     const bool aligned = (((uintptr_t)srow) & 15u) == 0u;      // (uniform over the row)
     float acc = 0.0f;      // the fp32 chain: at most 16 terms, each in [0, 1]
-    const int64_t v0 = (int64_t)blockIdx.x * kChunkVecs;
+    const int64_t v0 = (int64_t)blockIdx.x * kRowWalkChunkVecs;
 #pragma unroll
     for (int it = 0; it < kIters; ++it) {
       const int64_t vw = v0 + (int64_t)it * kThreads + wave * 64;      // the wave's first quad: 256 columns = 8 whole mask words
@@ -217,7 +171,7 @@ __global__ void __launch_bounds__(kThreads) scores_lse_sum_kernel(const float* _
       const int64_t x = 4 * q + tid;
       if (x < n && (!MASKED || mask_bit(mrow, x))) part += (double)expf(scaled(srow[x], beta) - Y);
     }
-    part = wave_sum_f64(part);
+    part = wave_sum(part);
     if (lane == 0) wave_part[wave] = part;
     __syncthreads();
     if (tid == 0) {
@@ -260,7 +214,6 @@ template <bool MASKED>
 __global__ void __launch_bounds__(kThreads) scores_gumbel_kernel(const float* __restrict__ scores, int64_t ld, int rows, int64_t n, float beta, u32 k0, u32 k1,
                                                                 int64_t first_row, const u32* __restrict__ words, int64_t words_row_stride, int64_t n_words,
                                                                 float* __restrict__ out, int64_t out_ld) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
     const float* srow = scores + row * ld;
     float* orow = out + row * out_ld;
@@ -269,44 +222,26 @@ __global__ void __launch_bounds__(kThreads) scores_gumbel_kernel(const float* __
     const bool out_aligned = (((uintptr_t)(orow + rs.head)) & 15u) == 0u;      // (uniform over the row: the body's stores are 16 bytes wide or scalar)
     const u64 grow = (u64)(first_row + row);
     const u32 r_lo = (u32)grow, r_hi = (u32)(grow >> 32);
-    const int64_t v0 = (int64_t)blockIdx.x * kChunkVecs;
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-      const int64_t vw = v0 + (int64_t)it * kThreads + wave * 64;
-      if (vw >= rs.q) break;                                           // (wave-uniform)
-      const int64_t v = vw + lane;
-      const int64_t xw = rs.head + 4 * vw, x0 = rs.head + 4 * v;
-      const u32 bits = MASKED ? wave_mask_bits(mrow, n_words, xw, x0, lane) : 0xFu;
-      if (v < rs.q) {
-        const float4 s = *reinterpret_cast<const float4*>(srow + x0);
-        const u32 p = (u32)x0;
-        float4 o;
-        o.x = (bits & 1u) ? scaled(s.x, beta) + gumbel_noise(p, r_lo, r_hi, k0, k1) : -INFINITY;
-        o.y = (bits & 2u) ? scaled(s.y, beta) + gumbel_noise(p + 1, r_lo, r_hi, k0, k1) : -INFINITY;
-        o.z = (bits & 4u) ? scaled(s.z, beta) + gumbel_noise(p + 2, r_lo, r_hi, k0, k1) : -INFINITY;
-        o.w = (bits & 8u) ? scaled(s.w, beta) + gumbel_noise(p + 3, r_lo, r_hi, k0, k1) : -INFINITY;
-        if (out_aligned) {
-          *reinterpret_cast<float4*>(orow + x0) = o;
-        } else {
-          orow[x0] = o.x;
-          orow[x0 + 1] = o.y;
-          orow[x0 + 2] = o.z;
-          orow[x0 + 3] = o.w;
-        }
-      }
-    }
-    if (blockIdx.x == 0 && tid < 8) {      // the peeled head (threads 0..3) and tail (threads 4..7): at most 3 columns each
-      const int64_t x = tid < 4 ? tid : rs.tail0 + (tid - 4);
-      if (tid < 4 ? x < rs.head : x < n)
-        orow[x] = (!MASKED || mask_bit(mrow, x)) ? scaled(srow[x], beta) + gumbel_noise((u32)x, r_lo, r_hi, k0, k1) : -INFINITY;
-    }
+    for_row_chunk<MASKED>(
+        srow, n, mrow, n_words,
+        [&](int64_t x0, float4 s, u32 bits) {
+          const u32 p = (u32)x0;
+          float4 o;
+          o.x = (bits & 1u) ? scaled(s.x, beta) + gumbel_noise(p, r_lo, r_hi, k0, k1) : -INFINITY;
+          o.y = (bits & 2u) ? scaled(s.y, beta) + gumbel_noise(p + 1, r_lo, r_hi, k0, k1) : -INFINITY;
+          o.z = (bits & 4u) ? scaled(s.z, beta) + gumbel_noise(p + 2, r_lo, r_hi, k0, k1) : -INFINITY;
+          o.w = (bits & 8u) ? scaled(s.w, beta) + gumbel_noise(p + 3, r_lo, r_hi, k0, k1) : -INFINITY;
+          if (out_aligned) {
+            *reinterpret_cast<float4*>(orow + x0) = o;
+          } else {
+            orow[x0] = o.x;
+            orow[x0 + 1] = o.y;
+            orow[x0 + 2] = o.z;
+            orow[x0 + 3] = o.w;
+          }
+        },
+        [&](int64_t x, float s, bool keep) { orow[x] = keep ? scaled(s, beta) + gumbel_noise((u32)x, r_lo, r_hi, k0, k1) : -INFINITY; });
   }
-}
-
-static inline int launched() { return hipGetLastError() == hipSuccess ? kOk : kErrLaunch; }
-
-static inline dim3 row_grid(int rows, int64_t n) {
-  return dim3((unsigned)chunks_of(n), (unsigned)((unsigned)rows < kMaxGridY ? (unsigned)rows : kMaxGridY));
 }
 
 // workspace: float64 partial sums (rows * chunks), fp32 partial maxima (rows * chunks), fp32 row maxima (rows), each 256-byte aligned
@@ -327,17 +262,12 @@ int scores_lse(const float* scores, int64_t ld, int rows, int64_t n, float beta,
   const u32* w = (const u32*)mask_words;
   const int64_t n_words = item_mask_words(n);
   const unsigned row_blocks = grid_for(((int64_t)rows + kThreads - 1) / kThreads);
-  if (w != nullptr)
-    hipLaunchKernelGGL((scores_lse_max_kernel<true>), grid, dim3(kThreads), 0, stream, scores, ld, rows, n, w, words_row_stride, n_words, part_max);
-  else
-    hipLaunchKernelGGL((scores_lse_max_kernel<false>), grid, dim3(kThreads), 0, stream, scores, ld, rows, n, w, words_row_stride, n_words, part_max);
+  launch_masked(w, scores_lse_max_kernel<true>, scores_lse_max_kernel<false>, grid, stream, scores, ld, rows, n, w, words_row_stride, n_words, part_max);
   if (launched() != kOk) return kErrLaunch;
   hipLaunchKernelGGL(scores_lse_rowmax_kernel, dim3(row_blocks), dim3(kThreads), 0, stream, part_max, (int64_t)rows, chunks, row_max);
   if (launched() != kOk) return kErrLaunch;
-  if (w != nullptr)
-    hipLaunchKernelGGL((scores_lse_sum_kernel<true>), grid, dim3(kThreads), 0, stream, scores, ld, rows, n, beta, w, words_row_stride, n_words, row_max, part_sum);
-  else
-    hipLaunchKernelGGL((scores_lse_sum_kernel<false>), grid, dim3(kThreads), 0, stream, scores, ld, rows, n, beta, w, words_row_stride, n_words, row_max, part_sum);
+  launch_masked(w, scores_lse_sum_kernel<true>, scores_lse_sum_kernel<false>, grid, stream, scores, ld, rows, n, beta, w, words_row_stride, n_words, row_max,
+                part_sum);
   if (launched() != kOk) return kErrLaunch;
   hipLaunchKernelGGL(scores_lse_finish_kernel, dim3(row_blocks), dim3(kThreads), 0, stream, row_max, part_sum, (int64_t)rows, chunks, beta, lse_out);
   return launched();
@@ -348,10 +278,8 @@ int scores_log_prob(const float* scores, int64_t ld, int rows, int64_t n, const 
   const int64_t total = (int64_t)rows * t;
   const dim3 grid(grid_for((total + kThreads - 1) / kThreads));
   const u32* w = (const u32*)mask_words;
-  if (w != nullptr)
-    hipLaunchKernelGGL((scores_log_prob_kernel<true>), grid, dim3(kThreads), 0, stream, scores, ld, n, positions, total, t, beta, lse, w, words_row_stride, out);
-  else
-    hipLaunchKernelGGL((scores_log_prob_kernel<false>), grid, dim3(kThreads), 0, stream, scores, ld, n, positions, total, t, beta, lse, w, words_row_stride, out);
+  launch_masked(w, scores_log_prob_kernel<true>, scores_log_prob_kernel<false>, grid, stream, scores, ld, n, positions, total, t, beta, lse, w, words_row_stride,
+                out);
   return launched();
 }
 
@@ -361,12 +289,8 @@ int scores_gumbel(const float* scores, int64_t ld, int rows, int64_t n, float be
   const u32* w = (const u32*)mask_words;
   const int64_t n_words = item_mask_words(n);
   const u32 k0 = (u32)seed, k1 = (u32)(seed >> 32);
-  if (w != nullptr)
-    hipLaunchKernelGGL((scores_gumbel_kernel<true>), grid, dim3(kThreads), 0, stream, scores, ld, rows, n, beta, k0, k1, first_row, w, words_row_stride, n_words,
-                       out, out_ld);
-  else
-    hipLaunchKernelGGL((scores_gumbel_kernel<false>), grid, dim3(kThreads), 0, stream, scores, ld, rows, n, beta, k0, k1, first_row, w, words_row_stride, n_words,
-                       out, out_ld);
+  launch_masked(w, scores_gumbel_kernel<true>, scores_gumbel_kernel<false>, grid, stream, scores, ld, rows, n, beta, k0, k1, first_row, w, words_row_stride,
+                n_words, out, out_ld);
   return launched();
 }
 

@@ -26,6 +26,7 @@
 
 #include "mol_kernels.h"
 #include "topk_keys.h"
+#include "wave_ops.h"
 
 namespace mol {
 
@@ -146,12 +147,7 @@ __global__ __launch_bounds__(64) void pick_bin_kernel(SelectState* __restrict__ 
   const int top = nb - 1 - lane * per;
   unsigned int mine = 0;
   for (int j = 0; j < per; ++j) mine += gh[top - j];
-  unsigned int incl = mine;  // inclusive prefix over lanes (lane 0 = top bins)
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned int v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
+  const unsigned int incl = wave_scan_incl(mine, lane);  // inclusive prefix over lanes (lane 0 = top bins)
   const unsigned int excl = incl - mine;
   if (excl < need && need <= incl) {   // exactly one lane (need <= total by construction: k <= n)
     unsigned int cum = excl;
@@ -329,24 +325,12 @@ constexpr int kFuseMaxW = 256;    // seen ids per row
 // The seen-id filter of the candidate index (reference indexing/candidate_index.py:149-175) over a row's k' selected candidates
 // held in LDS, best first: keep the first k NOT-seen ones in order; if fewer than k exist, back-fill with the earliest dropped
 // ones (seen, or beyond the first k) -- exactly what filter_seen_kernel does, one thread per candidate.  All threads of the
-// workgroup call it (NT threads, NT >= kp); `scratch` = NT / 64 + 2 ints.
+// workgroup call it (NT threads, NT >= kp) behind a barrier that orders their writes of id_s / sc_s / inv_s: id_s and inv_s are read before
+// the first barrier in here.  `scratch` = NT / 64 + 2 ints, used by nothing else.  Four barriers, two per scan.
 template <int NT>
 __device__ __forceinline__ void filter_from_lds(const int64_t* id_s, const float* sc_s, int kp, const int64_t* inv_s, int width, int k,
                                                 int64_t* __restrict__ out_ids, float* __restrict__ out_scores, int* scratch) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  auto block_scan = [&](int v, int& total) -> int {   // inclusive scan over the NT threads
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-    __syncthreads();
-    if (lane == 63) scratch[wv] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int t = 0; t < NT / 64; ++t) { const int tv = scratch[t]; if (t < wv) base += tv; total += tv; }
-    return base + inc;
-  };
+  const int tid = threadIdx.x;
   int ok = 0;
   int64_t id = 0;
   if (tid < kp) {
@@ -356,19 +340,19 @@ __device__ __forceinline__ void filter_from_lds(const int64_t* id_s, const float
     ok = seen ? 0 : 1;
   }
   int total_ok;
-  const int okc = block_scan(ok, total_ok);                 // not-seen candidates up to and including this one
+  const int okc = block_scan_excl<NT>(ok, scratch, total_ok) + ok;      // not-seen candidates up to and including this one
   const bool valid = ok && okc <= k;
   const int gap = k - (total_ok < k ? total_ok : k);
   int total_bad;
-  const int badc = block_scan(tid < kp && !valid ? 1 : 0, total_bad) - (tid < kp && !valid ? 1 : 0);   // dropped candidates before this one
-  if (tid < kp) {
-    int out_pos = -1;
-    if (valid) out_pos = (okc - 1) + (badc < gap ? badc : gap);
-    else if (badc + 1 <= gap) out_pos = (okc < k ? okc : k) + badc;
-    if (out_pos >= 0 && out_pos < k) {
-      out_ids[out_pos] = id;
-      out_scores[out_pos] = sc_s[tid];
-    }
+  const int badc = block_scan_excl<NT>(tid < kp && !valid ? 1 : 0, scratch, total_bad);      // dropped candidates before this one
+  // (every thread works its slot out, so that total_ok is summed up before the second scan reads its wave totals: with the sum left to a
+  // tid < kp branch behind it, both scans' totals stay in registers at once -- 6 more VGPRs for row_select_kernel, profiles/row_walk_and_scans_isa.txt)
+  int out_pos = -1;
+  if (valid) out_pos = (okc - 1) + (badc < gap ? badc : gap);
+  else if (badc + 1 <= gap) out_pos = (okc < k ? okc : k) + badc;
+  if (tid < kp && out_pos >= 0 && out_pos < k) {
+    out_ids[out_pos] = id;
+    out_scores[out_pos] = sc_s[tid];
   }
 }
 
@@ -627,12 +611,7 @@ __global__ __launch_bounds__(kRowThreads) void row_select_kernel(const RowSelect
     unsigned int c = 0;
 #pragma unroll
     for (int j = 0; j < VPT; ++j) c += (local_index(j) < cnt && pred(j)) ? 1u : 0u;
-    unsigned int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned int x = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += x;
-    }
+    const unsigned int incl = wave_scan_incl(c, lane);
     unsigned int base = 0;
     if (lane == 63 && incl) base = atomicAdd(&cursor, incl);
     base = (unsigned int)__shfl((int)base, 63, 64);
@@ -964,9 +943,7 @@ __global__ __launch_bounds__(kRowThreads) void sublist_select_kernel(const SubSe
     unsigned int c = 0u;
 #pragma unroll
     for (int j = 0; j < VPT; ++j) c += radix_selected(khi[j], klo[j], sel) ? 1u : 0u;
-    unsigned int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned int x = __shfl_up(incl, o, 64); if (lane >= o) incl += x; }
+    const unsigned int incl = wave_scan_incl(c, lane);
     unsigned int base = 0u;
     if (lane == 63 && incl) base = atomicAdd(&cursor, incl);
     base = (unsigned int)__shfl((int)base, 63, 64);
@@ -1189,24 +1166,9 @@ __global__ __launch_bounds__(kFilterThreads) void filter_seen_kernel(const int64
   const int s0 = threadIdx.x * seg, s1 = (s0 + seg < k_prime) ? s0 + seg : k_prime;
   int c = 0;
   for (int j = s0; j < s1; ++j) c += ok[j];
-  // block-wide exclusive scan of the per-thread counts: shuffle scan inside each wave, wave totals through LDS (a serial scan by
-  // thread 0 cost ~7 us of this kernel's 14)
-  auto block_exclusive_scan = [&](int v, int* totals, int& total) -> int {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-    if (lane == 63) totals[wv] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int t = 0; t < kFilterThreads / 64; ++t) { const int tv = totals[t]; if (t < wv) base += tv; total += tv; }
-    __syncthreads();
-    return base + inc - v;
-  };
+  // block-wide exclusive scan of the per-thread counts (a serial scan by thread 0 cost ~7 us of this kernel's 14)
   int tot;
-  seg_ok[threadIdx.x] = block_exclusive_scan(c, seg_bad, tot);
+  seg_ok[threadIdx.x] = block_scan_excl<kFilterThreads>(c, seg_bad, tot);
   if (threadIdx.x == 0) total_ok = tot;
   __syncthreads();
   const int n_valid = total_ok < k ? total_ok : k;   // valid = not seen and cumsum <= k
@@ -1218,7 +1180,7 @@ __global__ __launch_bounds__(kFilterThreads) void filter_seen_kernel(const int64
   __syncthreads();   // seg_bad served as the first scan's scratch
   {
     __shared__ int wave_tot[kFilterThreads / 64];
-    const int ex = block_exclusive_scan(c, wave_tot, tot);
+    const int ex = block_scan_excl<kFilterThreads>(c, wave_tot, tot);
     seg_bad[threadIdx.x] = ex;
   }
   __syncthreads();
@@ -1678,8 +1640,7 @@ __global__ __launch_bounds__(1024) void rerank_keys_kernel(const float* __restri
     keys[(int64_t)row * n + c] = first ? make_key(scores[(int64_t)row * ld + c], p) : 0ull;
     uniq += first ? 1u : 0u;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) uniq += (unsigned int)__shfl_xor((int)uniq, o, 64);
+  uniq = wave_sum(uniq);
   if ((tid & 63) == 0 && uniq) atomicAdd(&rr_tab[kRerankHash], uniq);
   __syncthreads();
   if (tid == 0 && rr_tab[kRerankHash] < (unsigned int)min_unique) *flag = 1;     // every writer stores the same value
@@ -1814,18 +1775,14 @@ __device__ __forceinline__ void cand_coarse_sums(const unsigned int* h, unsigned
 // bins >= b_t is <= cap (0 when the whole row fits; kCandBins -- nothing selected -- when the top fine bin alone holds more than cap).
 __device__ __forceinline__ int cand_pick(const unsigned int* coarse, const unsigned int* fine, unsigned int cap, int lane) {
   const unsigned int cc = coarse[kCandCoarse - 1 - lane];
-  unsigned int incl = cc;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned int v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+  const unsigned int incl = wave_scan_incl(cc, lane);
   const unsigned long long over = __ballot(incl > cap);
   if (over == 0ull) return 0;
   const int first = __ffsll((long long)over) - 1;
   const int cg = kCandCoarse - 1 - first;
   const unsigned int base = (unsigned int)__shfl((int)(incl - cc), first, 64);     // scores in the coarse bins above cg
   const unsigned int f = fine[cg * kCandPer + kCandPer - 1 - lane];
-  unsigned int incl2 = f;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned int v = __shfl_up(incl2, o, 64); if (lane >= o) incl2 += v; }
+  const unsigned int incl2 = wave_scan_incl(f, lane);
   const int fit = __popcll(__ballot(base + incl2 <= cap));                          // monotone in the lane: the top `fit` fine bins of cg fit
   return cg * kCandPer + kCandPer - fit;                                            // fit == 0: the first bin above cg
 }
@@ -1904,9 +1861,7 @@ __global__ __launch_bounds__(kCandThreads) void cand_hist_kernel(const float* __
   // row's count passes cap in c or above, so its threshold bin lies in a coarse bin >= c -- and every workgroup merges all of its bins >= its c.
   if (tid < 64) {
     const unsigned int cc = hc[kCandCoarse - 1 - lane];
-    unsigned int incl = cc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned int v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+    const unsigned int incl = wave_scan_incl(cc, lane);
     const unsigned long long over = __ballot(incl > cap);
     if (lane == 0) s_cut = over ? kCandCoarse - 1 - (__ffsll((long long)over) - 1) : 0;
   }

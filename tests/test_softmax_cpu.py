@@ -70,8 +70,10 @@ def test_entry_points_are_additions_under_abi_15(lib):
     for name in NAMES:
         assert re.search(r"\b" + name + r"\s*\(", header) and name in _lib.PROTOTYPES and getattr(lib, name) is not None, name
     assert "softmax.hip" in open(os.path.join(ROOT, "rails_amd", "csrc", "Makefile")).read()
-    src = open(os.path.join(ROOT, "rails_amd", "csrc", "softmax.hip")).read()
-    assert "atomicAdd" not in src and "__expf" not in src and "__logf" not in src      # no floating-point atomics, the accurate expf / log
+    for name in ("softmax.hip", "score_rows.h", "wave_ops.h"):      # the kernels, their row walk and their wave sum
+        src = open(os.path.join(ROOT, "rails_amd", "csrc", name)).read()
+        assert "atomicAdd" not in src and "__expf" not in src and "__logf" not in src, name      # no floating-point atomics, the accurate expf / log
+    assert '#include "score_rows.h"' in open(os.path.join(ROOT, "rails_amd", "csrc", "softmax.hip")).read()
     assert list(inspect.signature(E.scores_lse).parameters) == ["scores", "mask", "temperature"]
     assert list(inspect.signature(E.scores_log_prob).parameters) == ["scores", "positions", "lse", "mask", "temperature"]
     assert list(inspect.signature(E.scores_gumbel).parameters) == ["scores", "seed", "first_row", "mask", "temperature", "out"]
