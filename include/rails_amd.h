@@ -54,6 +54,7 @@ extern "C" {
  * rails_mol_generic_coarse_update / rails_mol_generic_component_build / rails_mol_generic_component_update / rails_mol_generic_eq_pad
  * and the rank entries rails_scores_rank_keys / rails_scores_rank / rails_item_mask_clear_rows
  * and the softmax entries rails_scores_lse[_workspace_bytes] / rails_scores_log_prob / rails_scores_gumbel
+ * and the range-search entries rails_scores_range_workspace_bytes / rails_scores_range_count / _write / _sort / _decode
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -450,6 +451,40 @@ int rails_scores_log_prob(const float* scores, int64_t ld, int32_t rows, int64_t
  * draw without replacement from softmax(scores / temperature) over the row's eligible columns, in draw order. */
 int rails_scores_gumbel(const float* scores, int64_t ld, int32_t rows, int64_t n, float inv_temperature, uint64_t seed, int64_t first_row,
                         const uint32_t* mask_words, int64_t words_row_stride, float* out, int64_t out_ld, void* stream);
+
+/* ---- range search over a score matrix (added under ABI 15: new entries only) -----------------------------------------------------------
+ * Which columns of row r of a (rows, n) fp32 score matrix with row stride ld meet the row's threshold, as a ragged result.  Column x is a
+ * HIT of row r when it is eligible (mask_words / words_row_stride as in rails_scores_rank: bit set = eligible, NULL = every column) and
+ *   v >= thresholds[r]    (an IEEE fp32 compare: false when either side is NaN)
+ * with v = scores[r * ld + x] when lse is NULL (the score form; inv_temperature is checked and not used) and
+ * v = fl32(fl32(scores[r * ld + x] * inv_temperature) - lse[r]) otherwise (the log-probability form: rails_scores_log_prob's value for the
+ * lse rails_scores_lse gave; one rounded multiply, not fused with the subtraction).  thresholds: rows fp32 values on the device.
+ * No atomics: the same bits on every run, whatever the alignment of a row.  Rows in [1, 2^24], n in [1, 2^31), ld >= n; rows = 0: nothing
+ * to do.  RAILS_EINVAL for a NULL pointer, a size outside these, an inv_temperature that is not a finite number > 0 or mask rows shorter
+ * than n bits; RAILS_ENOMEM for a workspace shorter than rails_scores_range_workspace_bytes(rows, n) (256-byte aligned); every refusal
+ * before any launch. */
+size_t rails_scores_range_workspace_bytes(int32_t rows, int64_t n);
+/* counts_out[r] = the hits of row r, lims_out[0] = 0, lims_out[r + 1] = lims_out[r] + counts_out[r] (rows + 1 entries).  One read of the
+ * matrix.  The workspace keeps the per-slot counts and offsets rails_scores_range_write needs: a row's hits are counted per slot, in
+ * position order [the unaligned head | every chunk of 4 096 aligned columns | the unaligned tail], then scanned by one workgroup. */
+int rails_scores_range_count(const float* scores, int64_t ld, int32_t rows, int64_t n, const float* thresholds, float inv_temperature, const float* lse,
+                             const uint32_t* mask_words, int64_t words_row_stride, void* workspace, size_t workspace_bytes, int64_t* counts_out,
+                             int64_t* lims_out, void* stream);
+/* After rails_scores_range_count with the same inputs and the workspace it filled: keys_out[lims[r] + j] = the 64-bit selection key
+ * ((orderable(score) << 32) | ~position) of row r's j-th hit in POSITION order.  One more read of the matrix.  capacity: the entries of
+ * keys_out (lims[rows] are written); every store is tested against it, and against the slot's count -- a pass that disagrees with its
+ * count (the inputs changed in between) writes nothing out of bounds and sets the int32 word at the start of the workspace's last 256
+ * bytes, which rails_scores_range_count zeroes.  capacity = 0: nothing to do. */
+int rails_scores_range_write(const float* scores, int64_t ld, int32_t rows, int64_t n, const float* thresholds, float inv_temperature, const float* lse,
+                             const uint32_t* mask_words, int64_t words_row_stride, void* workspace, size_t workspace_bytes, uint64_t* keys_out,
+                             int64_t capacity, void* stream);
+/* In place: keys[lims[r], lims[r + 1]) sorted descending for every row -- score descending, then position ascending, on the bit pattern: the
+ * row's exhaustive top-k order.  max_count: at least the largest row's count; it sizes the launch's LDS, and a row beyond it is left as it
+ * is.  RAILS_ENOTSUP for max_count > 16 384; max_count < 2: nothing to do. */
+int rails_scores_range_sort(uint64_t* keys, const int64_t* lims, int32_t rows, int32_t max_count, void* stream);
+/* scores_out[i] = the score of keys[i] (its bits), ids_out[i] = ids[position] (the position itself when ids is NULL; -1 for a position
+ * outside [0, n)), i < total.  total = 0: nothing to do. */
+int rails_scores_range_decode(const uint64_t* keys, int64_t total, const int64_t* ids, int64_t n, float* scores_out, int64_t* ids_out, void* stream);
 
 /* Per-row candidates: out[bq * n_cand + x] = <queries[bq], items[bq / r][x]> for queries (n_queries, dim) and items
  * (n_queries / r, n_cand, dim) -- the two bmm branches of DotProductSimilarity.forward

@@ -242,6 +242,13 @@ PROTOTYPES = {
                                         C.c_void_p, C.c_void_p]),
     "rails_scores_gumbel": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                       C.c_int64, C.c_void_p]),
+    "rails_scores_range_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "rails_scores_range_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rails_scores_range_write": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rails_scores_range_sort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "rails_scores_range_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rails_dot_rowwise": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],

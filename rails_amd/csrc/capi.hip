@@ -930,6 +930,53 @@ int rails_scores_gumbel(const float* scores, int64_t ld, int32_t rows, int64_t n
   return fail(scores_gumbel(scores, ld, rows, n, inv_temperature, seed, first_row, mask_words, words_row_stride, out, out_ld, (hipStream_t)stream), "scores_gumbel");
 }
 
+// ---- range search over a score matrix (range.hip) ----
+size_t rails_scores_range_workspace_bytes(int32_t rows, int64_t n) {
+  return rows > 0 && rows <= (1 << 24) && n > 0 && n < (1LL << 31) ? scores_range_workspace_bytes(rows, n) : 0;
+}
+
+int rails_scores_range_count(const float* scores, int64_t ld, int32_t rows, int64_t n, const float* thresholds, float inv_temperature, const float* lse,
+                             const uint32_t* mask_words, int64_t words_row_stride, void* workspace, size_t workspace_bytes, int64_t* counts_out,
+                             int64_t* lims_out, void* stream) {
+  g_err[0] = '\0';
+  if (rows == 0) return RAILS_OK;
+  const int go = softmax_args("scores_range_count", scores && thresholds && workspace && counts_out && lims_out, rows, n, ld, inv_temperature, words_row_stride);
+  if (go <= 0) return go;
+  if (workspace_bytes < scores_range_workspace_bytes(rows, n)) { set_error("scores_range_count: workspace too small"); return RAILS_ENOMEM; }
+  return fail(scores_range_count(scores, ld, rows, n, thresholds, inv_temperature, lse, mask_words, words_row_stride, workspace, counts_out, lims_out,
+                                 (hipStream_t)stream), "scores_range_count");
+}
+
+int rails_scores_range_write(const float* scores, int64_t ld, int32_t rows, int64_t n, const float* thresholds, float inv_temperature, const float* lse,
+                             const uint32_t* mask_words, int64_t words_row_stride, void* workspace, size_t workspace_bytes, uint64_t* keys_out,
+                             int64_t capacity, void* stream) {
+  g_err[0] = '\0';
+  if (capacity < 0) { set_error("scores_range_write: capacity < 0"); return RAILS_EINVAL; }
+  if (rows == 0 || capacity == 0) return RAILS_OK;
+  const int go = softmax_args("scores_range_write", scores && thresholds && workspace && keys_out, rows, n, ld, inv_temperature, words_row_stride);
+  if (go <= 0) return go;
+  if (workspace_bytes < scores_range_workspace_bytes(rows, n)) { set_error("scores_range_write: workspace too small"); return RAILS_ENOMEM; }
+  return fail(scores_range_write(scores, ld, rows, n, thresholds, inv_temperature, lse, mask_words, words_row_stride, workspace, keys_out, capacity,
+                                 (hipStream_t)stream), "scores_range_write");
+}
+
+int rails_scores_range_sort(uint64_t* keys, const int64_t* lims, int32_t rows, int32_t max_count, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || rows > (1 << 24) || max_count < 0) { set_error("scores_range_sort: rows = %d, max_count = %d", rows, max_count); return RAILS_EINVAL; }
+  if (max_count > kRangeSortMax) { set_error("scores_range_sort: max_count = %d beyond the %d keys one workgroup sorts", max_count, kRangeSortMax); return RAILS_ENOTSUP; }
+  if (rows == 0 || max_count < 2) return RAILS_OK;
+  if (!keys || !lims) { set_error("scores_range_sort: NULL pointer"); return RAILS_EINVAL; }
+  return fail(scores_range_sort(keys, lims, rows, max_count, (hipStream_t)stream), "scores_range_sort");
+}
+
+int rails_scores_range_decode(const uint64_t* keys, int64_t total, const int64_t* ids, int64_t n, float* scores_out, int64_t* ids_out, void* stream) {
+  g_err[0] = '\0';
+  if (total < 0 || n < 1 || n >= (1LL << 31)) { set_error("scores_range_decode: total = %lld, n = %lld", (long long)total, (long long)n); return RAILS_EINVAL; }
+  if (total == 0) return RAILS_OK;
+  if (!keys || !scores_out || !ids_out) { set_error("scores_range_decode: NULL pointer"); return RAILS_EINVAL; }
+  return fail(scores_range_decode(keys, total, ids, n, scores_out, ids_out, (hipStream_t)stream), "scores_range_decode");
+}
+
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s) || n_items < 0) return 0;
   return (size_t)n_items * (size_t)s->dot_product_dimension * 2;

@@ -273,6 +273,16 @@ int scores_log_prob(const float* scores, int64_t ld, int rows, int64_t n, const 
 int scores_gumbel(const float* scores, int64_t ld, int rows, int64_t n, float beta, uint64_t seed, int64_t first_row, const void* mask_words,
                   int64_t words_row_stride, float* out, int64_t out_ld, hipStream_t stream);
 
+// ---- range search over a score matrix (range.hip): lse == NULL is the score form; keys are the selection keys of topk_keys.h ----
+constexpr int kRangeSortMax = 16384;      // hits of one row scores_range_sort takes: what lds_sort_desc sorts
+size_t scores_range_workspace_bytes(int rows, int64_t n);
+int scores_range_count(const float* scores, int64_t ld, int rows, int64_t n, const float* thresholds, float beta, const float* lse, const void* mask_words,
+                       int64_t words_row_stride, void* workspace, int64_t* counts_out, int64_t* lims_out, hipStream_t stream);
+int scores_range_write(const float* scores, int64_t ld, int rows, int64_t n, const float* thresholds, float beta, const float* lse, const void* mask_words,
+                       int64_t words_row_stride, void* workspace, void* keys_out, int64_t capacity, hipStream_t stream);
+int scores_range_sort(void* keys, const int64_t* lims, int rows, int max_count, hipStream_t stream);
+int scores_range_decode(const void* keys, int64_t total, const int64_t* ids, int64_t n, float* scores_out, int64_t* ids_out, hipStream_t stream);
+
 int dot_rowwise(const float* q, const float* items, int64_t Bq, int X, int D, int r, float* out, hipStream_t stream);
 
 size_t topk_workspace_bytes(int rows, int64_t n, int k);

@@ -1802,6 +1802,91 @@ def scores_gumbel(scores: torch.Tensor, seed: int, first_row: int = 0, mask: Opt
 
 
 # ---- item tags (rails_item_tags_*, rails_item_mask_from_tags, rails_scores_mask_tags) ---------------------
+# ---- range search over a score matrix (rails_scores_range_count / _write / _sort / _decode) ------------------------------
+def range_thresholds(what: str, thresholds, rows: int, device) -> torch.Tensor:
+    """A call's threshold(s) -> (rows,) fp32 on `device`, converted to fp32 once, on the host side of the call: a Python number for every row
+    (NaN and +-inf included), or a (rows,) tensor of a real dtype."""
+    if torch.is_tensor(thresholds):
+        if thresholds.shape != (rows,) or thresholds.dtype == torch.bool or thresholds.is_complex():
+            raise ValueError(f"{what}: a threshold tensor must be ({rows},) real numbers, got {tuple(thresholds.shape)} {thresholds.dtype}")
+        return thresholds.to(device=device, dtype=torch.float32).contiguous()
+    if isinstance(thresholds, bool) or not isinstance(thresholds, (int, float)):
+        raise ValueError(f"{what}: the threshold must be a number or a ({rows},) tensor, got {thresholds!r}")
+    return torch.full((rows,), C.c_float(float(thresholds)).value, dtype=torch.float32, device=device)
+
+
+def _range_count(what: str, scores: torch.Tensor, thresholds, mask, temperature: float, lse: Optional[torch.Tensor]):
+    """The checks and the counting pass of scores_range_count / scores_range -> (the write pass' leading arguments, the tensors behind them,
+    counts, lims).  The caller of the write pass holds on to the tensors until it has launched: the workspace carries the slots' counts and
+    offsets from one pass to the other, and a freed block would be handed to the next allocation."""
+    rows, n, ld, words, stride, beta = _softmax_args(what, scores, mask, temperature)
+    if lse is None and beta != 1.0:
+        raise ValueError(f"{what}: temperature = {temperature!r} without lse: a score threshold is compared with the raw score")
+    if lse is not None:
+        if not torch.is_tensor(lse) or lse.dtype != torch.float32 or lse.shape != (rows,):
+            raise ValueError(f"{what}: lse must be ({rows},) fp32")
+        if lse.device != scores.device:
+            raise ValueError(f"{what}: the lse and the scores live on different devices")
+        lse = lse.contiguous()
+    thr = range_thresholds(what, thresholds, rows, scores.device)
+    counts = torch.empty((rows,), dtype=torch.int64, device=scores.device)
+    lims = torch.zeros((rows + 1,), dtype=torch.int64, device=scores.device)
+    if rows == 0:
+        return None, None, counts, lims
+    lib = _lib.load()
+    need = int(lib.rails_scores_range_workspace_bytes(rows, n))
+    ws = torch.empty(need, dtype=torch.uint8, device=scores.device)
+    args = (_ptr(scores), ld, rows, n, _ptr(thr), beta, _ptr(lse), words, stride, _ptr(ws), need)
+    with _on_device(scores.device):
+        _lib.check(lib.rails_scores_range_count(*args, _ptr(counts), _ptr(lims), _stream()), "rails_scores_range_count")
+    return args, (ws, thr, lse, scores), counts, lims
+
+
+def scores_range_count(scores: torch.Tensor, thresholds, mask: Optional[ItemMask] = None, temperature: float = 1.0,
+                       lse: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(rows,) int64: how many items of row r's `mask` (as scores_rank takes it; None: all of them) have v >= thresholds[r], an IEEE fp32
+    compare (false with a NaN on either side) -- v = scores[r, x] without `lse`, v = fl32(fl32(scores[r, x] / temperature) - lse[r]) with it
+    (scores_log_prob's value for the lse scores_lse gave).  thresholds: a number or a (rows,) tensor.  One read of the matrix; no sync."""
+    return _range_count("scores_range_count", scores, thresholds, mask, temperature, lse)[2]
+
+
+def scores_range(scores: torch.Tensor, thresholds, mask: Optional[ItemMask] = None, temperature: float = 1.0, lse: Optional[torch.Tensor] = None,
+                 ids: Optional[torch.Tensor] = None, sort: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(lims (rows + 1,) int64, scores (lims[rows],) fp32, ids (lims[rows],) int64): the items scores_range_count counts, row r's in
+    [lims[r], lims[r + 1]) -- the raw scores' bits and ids[position] (the positions themselves without `ids`, a (>= n,) int64 table).
+    sort=True: a row in selection-key order (score descending, then position ascending, on the bits), that is the row's exhaustive top-k
+    list without the items that miss; a row of more than RANGE_SORT_MAX hits raises ValueError after the count, before anything is written.
+    sort=False: position ascending, any count.  Two reads of the matrix, no atomics: the same bits on every run.  ONE sync: lims is read
+    back to size the result."""
+    if ids is not None:
+        if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.dim() != 1 or ids.shape[0] < scores.shape[-1] or ids.device != scores.device:
+            raise ValueError("scores_range: ids must be a (>= n,) int64 table on the scores' device")
+        ids = ids.contiguous()
+    args, held, _, lims = _range_count("scores_range", scores, thresholds, mask, temperature, lse)
+    rows, dev = scores.shape[0], scores.device
+    host = lims.cpu()      # (the call's one sync)
+    total = int(host[rows])
+    most = int((host[1:] - host[:-1]).max()) if rows > 0 else 0
+    if sort and most > RANGE_SORT_MAX:
+        row = int(torch.nonzero(host[1:] - host[:-1] == most)[0])      # (the first such row)
+        raise ValueError(f"scores_range: row {row} has {most} hits, more than the {RANGE_SORT_MAX} one sorted row takes; "
+                         "raise the threshold or call with sort=False (position order, any count)")
+    out_scores = torch.empty((total,), dtype=torch.float32, device=dev)
+    out_ids = torch.empty((total,), dtype=torch.int64, device=dev)
+    if total == 0:
+        return lims, out_scores, out_ids
+    lib = _lib.load()
+    keys = torch.empty((total,), dtype=torch.int64, device=dev)      # (the 64-bit keys; never read as integers here)
+    with _on_device(dev):
+        _lib.check(lib.rails_scores_range_write(*args, _ptr(keys), total, _stream()), "rails_scores_range_write")
+        if sort:
+            _lib.check(lib.rails_scores_range_sort(_ptr(keys), _ptr(lims), rows, most, _stream()), "rails_scores_range_sort")
+        _lib.check(lib.rails_scores_range_decode(_ptr(keys), total, _ptr(ids), scores.shape[1], _ptr(out_scores), _ptr(out_ids), _stream()),
+                   "rails_scores_range_decode")
+    del held
+    return lims, out_scores, out_ids
+
+
 def tag_word_i32(word: int) -> int:
     """A 32-bit tag word as the int32 that holds its bit pattern."""
     return word - (1 << 32) if word >= 1 << 31 else word
@@ -1945,6 +2030,7 @@ def _pred(flag: Optional[torch.Tensor]):
 
 
 TOPK_MAX_K = 16384      # the largest k rails_topk takes (the 64-bit keys one workgroup sorts in LDS)
+RANGE_SORT_MAX = TOPK_MAX_K      # hits of one row rails_scores_range_sort takes: the same sort
 
 
 def topk(scores: torch.Tensor, k: int, ids: Optional[torch.Tensor] = None, sorted: bool = True,

@@ -44,6 +44,8 @@ _RANK_WHY = ("the exact rank of an item is built on the single-device MoLBruteFo
              "and needs the target's key on every rank (out of scope, DESIGN section 3.17)")
 _SOFTMAX_WHY = ("the softmax over the corpus is built on the single-device MoLBruteForceTopK: a sharded one would merge the shards' (max, sum) pairs, "
                 "which combine associatively, in one all-gather (out of scope, DESIGN section 3.18)")
+_RANGE_WHY = ("the range search is built on the single-device MoLBruteForceTopK: a sharded one would gather the shards' ragged results and merge each "
+              "row's sorted runs (out of scope, DESIGN section 3.19)")
 
 
 def shard_bounds(n_items: int, world_size: int, rank: int) -> Tuple[int, int]:
@@ -323,6 +325,14 @@ class ShardedTopK(TopKModule):
 
     def sample_items(self, query_embeddings: torch.Tensor, num_samples: int, seed: int, temperature: float = 1.0, invalid_ids=None, **kwargs):
         self._refuse_softmax("sample_items")
+
+    # ---- range search: not built on the item-sharded wrappers -------------------------------------------------------------
+    def count_above(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0, invalid_ids=None, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}.count_above: {_RANGE_WHY}")
+
+    def range_search(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0, invalid_ids=None,
+                     sort: bool = True, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}.range_search: {_RANGE_WHY}")
 
     # ---- hidden items: not built on the item-sharded wrappers -------------------------------------------------------
     def _refuse_hidden(self, what: str):

@@ -972,6 +972,62 @@ class _CorpusEdits(_ItemsById):
                 lp_out.append(torch.where(drawn, lp, float("-inf")))
             return (ids_out[0], lp_out[0]) if len(ids_out) == 1 else (torch.cat(ids_out, 0), torch.cat(lp_out, 0))
 
+    # ---- range search: count_above, range_search ---------------------------------------------------------------------------
+    # Which items row b may return -- rank_of's eligible set -- meet the row's threshold, and how many: logit >= min_score on all_logits' bits,
+    # or log_prob_of's value >= min_log_prob.  An IEEE fp32 compare (NaN on either side: no hit).  Built on _rank_scores like rank_of, with its
+    # refusals.
+    def _range_call(self, what: str, query_embeddings: torch.Tensor, min_score, min_log_prob, temperature: float, invalid_ids: Optional[torch.Tensor],
+                    kwargs: dict) -> Tuple[int, torch.Tensor]:
+        """The checks of a range call, before any launch -> (the rows of a batch slice under the logit policy, the (B,) fp32 thresholds)."""
+        self._refuse_rank_of(kwargs, what, "a range search over every item of the corpus")
+        name = f"{type(self).__name__}.{what}"
+        if (min_score is None) == (min_log_prob is None):
+            raise ValueError(f"{name}: exactly one of min_score= and min_log_prob= is given, got {'both' if min_score is not None else 'neither'}")
+        if E.inv_temperature(temperature, name) != 1.0 and min_score is not None:
+            raise ValueError(f"{name}: temperature = {temperature!r} with min_score=: a score threshold is compared with the raw logit; "
+                             "temperature goes with min_log_prob=")
+        B, N = query_embeddings.size(0), self.num_items
+        if invalid_ids is not None and (not torch.is_tensor(invalid_ids) or invalid_ids.dim() != 2 or invalid_ids.shape[0] != B
+                                        or invalid_ids.is_floating_point() or invalid_ids.dtype == torch.bool):
+            raise ValueError(f"{what}: invalid_ids must be ({B}, S) integer ids")
+        rows = int(getattr(self, "MAX_LOGIT_BYTES", 4 << 30)) // (N * 4)
+        if rows < 1:
+            raise NotImplementedError(f"{name}: one row of {N} logits exceeds MAX_LOGIT_BYTES; a row is counted and written whole, and corpus "
+                                      "chunks are not built")
+        return rows, E.range_thresholds(name, min_score if min_score is not None else min_log_prob, B, self._ids_flat.device)
+
+    def count_above(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0,
+                    invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """(B,) int64: how many items query row b may return score at least its threshold -- logit >= min_score on all_logits' bits, or
+        log_prob_of's value (at `temperature`) >= min_log_prob; exactly one of the two, a number or a (B,) tensor.  The hidden set, the
+        call's item_mask= / allowed_tags= and the row's invalid_ids are honoured as rank_of honours them.  One dense pass and one read of its
+        matrix (three in the log-probability form: the normaliser first); no host sync beyond the mask's."""
+        rows, thr = self._range_call("count_above", query_embeddings, min_score, min_log_prob, temperature, invalid_ids, kwargs)
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            out = [E.scores_range_count(scores, thr[b0:b1], words, temperature, None if min_log_prob is None else E.scores_lse(scores, words, temperature))
+                   for b0, b1, scores, words in slices]
+            return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+    def range_search(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0,
+                     invalid_ids: Optional[torch.Tensor] = None, sort: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(lims (B + 1,) int64, scores (lims[B],) fp32, ids (lims[B],) int64): the items count_above counts, row b's in
+        [lims[b], lims[b + 1]) with their raw logits.  sort=True: each row in get_top_k_outputs' order (score descending, then position
+        ascending) -- that exhaustive ranking without the items that miss; a row of more than engine.RANGE_SORT_MAX hits raises ValueError.
+        sort=False: position ascending, any count.  One read-back of lims per batch slice of the logit policy, the call's only sync beyond
+        the mask's."""
+        rows, thr = self._range_call("range_search", query_embeddings, min_score, min_log_prob, temperature, invalid_ids, kwargs)
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            lims, scores_out, ids_out = [], [], []
+            for b0, b1, scores, words in slices:
+                lse = None if min_log_prob is None else E.scores_lse(scores, words, temperature)
+                l, s, i = E.scores_range(scores, thr[b0:b1], words, temperature, lse, ids=self._ids_flat, sort=sort)
+                lims.append(l if not lims else l[1:] + lims[-1][-1])      # (cumulative over the slices; a device add, no sync)
+                scores_out.append(s)
+                ids_out.append(i)
+            if len(lims) == 1:
+                return lims[0], scores_out[0], ids_out[0]
+            return torch.cat(lims, 0), torch.cat(scores_out, 0), torch.cat(ids_out, 0)
+
     @contextlib.contextmanager
     def _positions_as_ids(self):
         """Inside this block every call of the module returns POSITIONS where it returns ids: the id table is swapped for 0 .. N - 1, so whichever
