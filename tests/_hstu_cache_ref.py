@@ -5,7 +5,8 @@ prefill(): the states `encode(..., return_cache_states=True)` returns, per layer
 with zeros at positions >= length, outputs jagged (R, D)), R = sum of the lengths, and the current embeddings.
 decode(): one row per sequence at positions[b] against those states, updating them in place as the reference does, and the
 postprocessed last layer's outputs row at lengths - 1.  `bug` injects one of the mistakes a kernel could plausibly make, so that the
-tests can show their bars reject it.
+tests can show their bars reject it.  `gemv` replaces the summation order of decode()'s two matrix-vector products (chain_gemv: one
+sequential chain per output column, the least favourable order a correct kernel could use).
 """
 from __future__ import annotations
 
@@ -17,6 +18,28 @@ import torch.nn.functional as F
 from oracle import hstu_oracle as HO
 
 BUGS = ("ts_p", "drop_self", "stale_k", "write_p", "return_p", "no_outputs")
+# mistakes of the decode kernel's own matrix-vector products and head loop (tests/test_hstu_decode_kernel.py): the last k term of a
+# product dropped, its last output column left at the accumulator's initial value (0), the last head's attention never computed
+GEMV_BUGS = ("uvqk_drop_last_k", "uvqk_stale_last_column", "o_drop_last_k", "o_stale_last_column", "skip_head")
+
+
+def chain_gemv(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """x (B, K) @ w (K, C) with every output accumulated as one sequential chain over k in the dtype of the operands."""
+    acc = torch.zeros((x.shape[0], w.shape[1]), dtype=x.dtype)
+    for k in range(w.shape[0]):
+        acc = acc + x[:, k: k + 1] * w[k: k + 1]
+    return acc
+
+
+def _gemv(gemv, x, w, bug, which):
+    """x @ w through `gemv` (None: torch's own order), with the `which`_* mistakes of GEMV_BUGS."""
+    if bug == which + "_drop_last_k":
+        x, w = x[:, :-1], w[:-1]
+    y = x @ w if gemv is None else gemv(x, w)
+    if bug == which + "_stale_last_column":
+        y = y.clone()
+        y[:, -1] = 0
+    return y
 
 
 def _postproc(cfg: HO.HSTUConfig, x: torch.Tensor) -> torch.Tensor:
@@ -57,9 +80,9 @@ def prefill(cfg: HO.HSTUConfig, w: Dict[str, torch.Tensor], lengths: torch.Tenso
 
 
 def decode(cfg: HO.HSTUConfig, w: Dict[str, torch.Tensor], lengths: torch.Tensor, ids: torch.Tensor, ts: Optional[torch.Tensor],
-           positions: torch.Tensor, states: List[Tuple[torch.Tensor, ...]], bug: Optional[str] = None) -> torch.Tensor:
+           positions: torch.Tensor, states: List[Tuple[torch.Tensor, ...]], bug: Optional[str] = None, gemv=None) -> torch.Tensor:
     """Decode row positions[b] of every sequence against `states` (updated in place) -> current embeddings (B, D)."""
-    assert bug is None or bug in BUGS, bug
+    assert bug is None or bug in BUGS + GEMV_BUGS, bug
     D, H, dqk, dv, N, nb = cfg.embedding_dim, cfg.num_heads, cfg.attention_dim, cfg.linear_dim, cfg.max_sequence_len, cfg.num_buckets
     B = ids.shape[0]
     bidx = torch.arange(B)
@@ -70,7 +93,7 @@ def decode(cfg: HO.HSTUConfig, w: Dict[str, torch.Tensor], lengths: torch.Tensor
     for l in range(cfg.num_blocks):
         p = f"_hstu._attention_layers.{l}."
         V, Q, K, OUT = states[l]
-        mm = F.silu(F.layer_norm(x, [D], eps=cfg.eps) @ w[p + "_uvqk"])
+        mm = F.silu(_gemv(gemv, F.layer_norm(x, [D], eps=cfg.eps), w[p + "_uvqk"], bug, "uvqk"))
         u, v, q, k = torch.split(mm, [dv * H, dv * H, dqk * H, dqk * H], dim=-1)
         k_old = K[bidx, positions].clone()
         V[wrows] = v
@@ -91,8 +114,14 @@ def decode(cfg: HO.HSTUConfig, w: Dict[str, torch.Tensor], lengths: torch.Tensor
             pr = F.silu(s) / N
             if bug == "drop_self":
                 pr[:, pb] = 0
+            if bug == "skip_head":
+                pr[H - 1] = 0
             a[b] = torch.einsum("hj,jhd->hd", pr, vals.view(pb + 1, H, dv)).reshape(H * dv)
-        x = F.linear(u * F.layer_norm(a, [dv * H], eps=cfg.eps), w[p + "_o.weight"], w[p + "_o.bias"]) + x
+        oin = u * F.layer_norm(a, [dv * H], eps=cfg.eps)
+        if gemv is None and bug not in ("o_drop_last_k", "o_stale_last_column"):
+            x = F.linear(oin, w[p + "_o.weight"], w[p + "_o.bias"]) + x
+        else:
+            x = _gemv(gemv, oin, w[p + "_o.weight"].t(), bug, "o") + w[p + "_o.bias"] + x
         if bug != "no_outputs":
             OUT[wrows] = x
     last = states[-1][3]
