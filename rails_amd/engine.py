@@ -1604,13 +1604,42 @@ def as_item_mask(item_mask) -> ItemMask:
     return item_mask if isinstance(item_mask, ItemMask) else ItemMask(item_mask)
 
 
+def score_matrix_ld(rows: int, n: int, stride0: int) -> int:
+    """The leading dimension the kernels are given for a (rows, n) matrix whose rows lie stride0 elements apart.  The stride of a single row
+    (or of none) is whatever the view it was cut from carries, a broadcast 0 or 1 included: such a matrix goes as rows of at least n, which is
+    what keeps a one-row slice of a recycled buffer inside its allocation under the kernels' ld >= n rule."""
+    return stride0 if rows > 1 else max(n, stride0)
+
+
+def _score_matrix(t: torch.Tensor, name: str = "scores", error: Optional[str] = None) -> Tuple[int, int, int]:
+    """The one check of a (rows, n) fp32 matrix with unit column stride on the GPU -> (rows, n, ld)."""
+    _require_device(t, name)
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(error or f"{name} must be (rows, n) fp32 with contiguous rows")
+    rows, n = t.shape
+    return rows, n, score_matrix_ld(rows, n, t.stride(0))
+
+
+def _positions_arg(what: str, positions: torch.Tensor, rows: int, device: torch.device, beside: str = "scores", t: str = "t") -> None:
+    """The one check of a (rows, t) int64 `positions` argument on the device of the matrix (`beside`) it addresses."""
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != rows:
+        raise ValueError(f"{what}: positions must be ({rows}, {t}) int64")
+    if positions.device != device:
+        raise ValueError(f"{what}: the positions and the {beside} live on different devices")
+
+
+def _lse_arg(what: str, lse: torch.Tensor, rows: int, device: torch.device) -> torch.Tensor:
+    if not torch.is_tensor(lse) or lse.dtype != torch.float32 or lse.shape != (rows,):
+        raise ValueError(f"{what}: lse must be ({rows},) fp32")
+    if lse.device != device:
+        raise ValueError(f"{what}: the lse and the scores live on different devices")
+    return lse.contiguous()
+
+
 def scores_mask(scores: torch.Tensor, mask: ItemMask, first_item: int = 0, fill: float = float("-inf"), run_if: Optional[torch.Tensor] = None) -> torch.Tensor:
     """In place: scores[b, x] = fill wherever item first_item + x is not in row b's mask (rails_scores_mask); kept entries are not touched.
     scores (rows, n) fp32 with unit column stride; a per-row mask has one row per row of scores."""
-    _require_device(scores, "scores")
-    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
-        raise ValueError("scores must be (rows, n) fp32 with contiguous rows")
-    rows, n = scores.shape
+    rows, n, ld = _score_matrix(scores)
     if first_item < 0 or first_item + n > mask.n_items:
         raise ValueError(f"scores_mask: items [{first_item}, {first_item + n}) are not inside a mask of {mask.n_items} items")
     if not mask.shared and mask.rows != rows:
@@ -1618,7 +1647,7 @@ def scores_mask(scores: torch.Tensor, mask: ItemMask, first_item: int = 0, fill:
     if mask.words.device != scores.device:
         raise ValueError("scores_mask: the mask and the scores live on different devices")
     with _on_device(scores.device):
-        _lib.check(_lib.load().rails_scores_mask(_ptr(scores), scores.stride(0) if rows > 1 else max(n, scores.stride(0)), rows, n, first_item, _ptr(mask.words),
+        _lib.check(_lib.load().rails_scores_mask(_ptr(scores), ld, rows, n, first_item, _ptr(mask.words),
                                                  0 if mask.shared else mask.words.stride(0), float(fill), _pred(run_if), _stream()), "rails_scores_mask")
     return scores
 
@@ -1627,12 +1656,12 @@ def scores_mask(scores: torch.Tensor, mask: ItemMask, first_item: int = 0, fill:
 RANK_MAX_TARGETS = 64      # targets per row and launch (rails_scores_rank); scores_rank slices wider calls
 
 
-def _row_mask_words(what: str, mask, scores: torch.Tensor) -> Optional[torch.Tensor]:
-    """The mask argument of the streaming passes over a (rows, n) score matrix (scores_rank, scores_lse, scores_log_prob, scores_gumbel) ->
-    its int32 words with one row for all or one per row, checked against `scores`; None: every item is eligible."""
+def _row_mask_words(what: str, mask, scores: torch.Tensor) -> Tuple[Optional[int], int]:
+    """The mask argument of the streaming passes over a (rows, n) score matrix -- an ItemMask, or its int32 words with one row for all or one
+    per row --, checked against `scores` -> (the words' pointer, their row stride: 0 for a shared row); (None, 0): every item is eligible."""
     rows, n = scores.shape
     if mask is None:
-        return None
+        return None, 0
     if isinstance(mask, ItemMask):
         if mask.n_items != n:
             raise ValueError(f"{what}: {n} columns of scores against a mask of {mask.n_items} items")
@@ -1645,7 +1674,18 @@ def _row_mask_words(what: str, mask, scores: torch.Tensor) -> Optional[torch.Ten
         raise ValueError(f"{what}: the mask has {mwords.shape[0]} rows but scores has {rows}")
     if mwords.device != scores.device:
         raise ValueError(f"{what}: the mask and the scores live on different devices")
-    return mwords
+    return _ptr(mwords), 0 if mwords.shape[0] == 1 else mwords.stride(0)
+
+
+def _row_pass_args(what: str, scores: torch.Tensor, mask, temperature: Optional[float] = None):
+    """The argument checks of every streaming pass over a score matrix (the rank, softmax and range passes) -> (rows, n, ld, mask words
+    pointer, their row stride, beta); a pass without a temperature gives None and gets beta = None."""
+    rows, n, ld = _score_matrix(scores)
+    beta = None if temperature is None else inv_temperature(temperature, what)
+    words, stride = _row_mask_words(what, mask, scores)
+    if rows > 0 and n < 1:
+        raise ValueError(f"{what}: scores has no columns")
+    return rows, n, ld, words, stride, beta
 
 
 def scores_rank(scores: torch.Tensor, positions: torch.Tensor, mask: Optional[ItemMask] = None) -> torch.Tensor:
@@ -1654,24 +1694,13 @@ def scores_rank(scores: torch.Tensor, positions: torch.Tensor, mask: Optional[It
     the score's bits) is larger, so rank - 1 is the target's index in the row's exhaustive top-k list.  0: not ranked (a position outside
     [0, n), such as the -1 of an unknown id, or a target outside the mask).  Every score is read once per RANK_MAX_TARGETS targets of its
     row; no sync."""
-    _require_device(scores, "scores")
-    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
-        raise ValueError("scores must be (rows, n) fp32 with contiguous rows")
-    rows, n = scores.shape
-    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != rows:
-        raise ValueError(f"scores_rank: positions must be ({rows}, t) int64")
-    if positions.device != scores.device:
-        raise ValueError("scores_rank: the positions and the scores live on different devices")
-    mwords = _row_mask_words("scores_rank", mask, scores)
+    rows, n, ld, words, stride, _ = _row_pass_args("scores_rank", scores, mask)
+    _positions_arg("scores_rank", positions, rows, scores.device)
     t_all = positions.shape[1]
     out = torch.empty((rows, t_all), dtype=torch.int64, device=scores.device)
     if rows == 0 or t_all == 0:
         return out
-    if n < 1:
-        raise ValueError("scores_rank: scores has no columns")
     lib = _lib.load()
-    ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
-    words, stride = (None, 0) if mwords is None else (_ptr(mwords), 0 if mwords.shape[0] == 1 else mwords.stride(0))
     with _on_device(scores.device):
         for t0 in range(0, t_all, RANK_MAX_TARGETS):
             pos = positions[:, t0 : t0 + RANK_MAX_TARGETS].contiguous()
@@ -1695,15 +1724,12 @@ def item_mask_clear_rows(words: torch.Tensor, positions: torch.Tensor, n_items: 
     n = 32 * words.shape[1] if n_items is None else int(n_items)
     if n < 1 or item_mask_words(n) > words.shape[1]:
         raise ValueError(f"item_mask_clear_rows: rows of {words.shape[1]} words do not hold {n} items")
-    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != rows:
-        raise ValueError(f"item_mask_clear_rows: positions must be ({rows}, m) int64")
-    if positions.device != words.device:
-        raise ValueError("item_mask_clear_rows: the positions and the words live on different devices")
+    _positions_arg("item_mask_clear_rows", positions, rows, words.device, "words", "m")
     if rows == 0 or positions.shape[1] == 0:
         return words
     pos = positions.contiguous()
     with _on_device(words.device):
-        _lib.check(_lib.load().rails_item_mask_clear_rows(_ptr(pos), rows, pos.shape[1], n, _ptr(words), words.stride(0) if rows > 1 else max(words.shape[1], words.stride(0)),
+        _lib.check(_lib.load().rails_item_mask_clear_rows(_ptr(pos), rows, pos.shape[1], n, _ptr(words), score_matrix_ld(rows, words.shape[1], words.stride(0)),
                                                           _stream()), "rails_item_mask_clear_rows")
     return words
 
@@ -1720,27 +1746,12 @@ def inv_temperature(temperature: float, what: str = "temperature") -> float:
     return beta
 
 
-def _softmax_args(what: str, scores: torch.Tensor, mask, temperature: float):
-    """The argument checks of scores_rank on the softmax passes -> (rows, n, ld, mask words pointer, their row stride, beta)."""
-    _require_device(scores, "scores")
-    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
-        raise ValueError("scores must be (rows, n) fp32 with contiguous rows")
-    beta = inv_temperature(temperature, what)
-    rows, n = scores.shape
-    mwords = _row_mask_words(what, mask, scores)
-    if rows > 0 and n < 1:
-        raise ValueError(f"{what}: scores has no columns")
-    ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
-    words, stride = (None, 0) if mwords is None else (_ptr(mwords), 0 if mwords.shape[0] == 1 else mwords.stride(0))
-    return rows, n, ld, words, stride, beta
-
-
 def scores_lse(scores: torch.Tensor, mask: Optional[ItemMask] = None, temperature: float = 1.0) -> torch.Tensor:
     """(rows,) fp32: log sum exp(scores[r, x] / temperature) over the items x of row r's `mask` (as scores_rank takes it; None: all of them)
     -- the normaliser of softmax(scores / temperature) over what the row may return (rails_scores_lse: two reads of the matrix, the same
     bits on every run).  -inf for a row with nothing eligible (or -inf alone), NaN with an eligible NaN, otherwise +inf with an eligible
     +inf.  No sync."""
-    rows, n, ld, words, stride, beta = _softmax_args("scores_lse", scores, mask, temperature)
+    rows, n, ld, words, stride, beta = _row_pass_args("scores_lse", scores, mask, temperature)
     out = torch.empty((rows,), dtype=torch.float32, device=scores.device)
     if rows == 0:
         return out
@@ -1757,18 +1768,14 @@ def scores_log_prob(scores: torch.Tensor, positions: torch.Tensor, lse: torch.Te
     """(rows, t) fp32: fl32(fl32(scores[r, p] / temperature) - lse[r]) for p = positions[r, j] -- the log-probability of item p under the
     softmax whose normaliser scores_lse gave for the same mask and temperature --, -inf for a position outside [0, n) or outside row r's
     `mask` (rails_scores_log_prob).  No sync."""
-    rows, n, ld, words, stride, beta = _softmax_args("scores_log_prob", scores, mask, temperature)
-    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != rows:
-        raise ValueError(f"scores_log_prob: positions must be ({rows}, t) int64")
-    if not torch.is_tensor(lse) or lse.dtype != torch.float32 or lse.shape != (rows,):
-        raise ValueError(f"scores_log_prob: lse must be ({rows},) fp32")
-    if positions.device != scores.device or lse.device != scores.device:
-        raise ValueError("scores_log_prob: the positions, the lse and the scores live on different devices")
+    rows, n, ld, words, stride, beta = _row_pass_args("scores_log_prob", scores, mask, temperature)
+    _positions_arg("scores_log_prob", positions, rows, scores.device)
+    lse = _lse_arg("scores_log_prob", lse, rows, scores.device)
     t = positions.shape[1]
     out = torch.empty((rows, t), dtype=torch.float32, device=scores.device)
     if rows == 0 or t == 0:
         return out
-    pos, lse = positions.contiguous(), lse.contiguous()
+    pos = positions.contiguous()
     with _on_device(scores.device):
         _lib.check(_lib.load().rails_scores_log_prob(_ptr(scores), ld, rows, n, _ptr(pos), t, beta, _ptr(lse), words, stride, _ptr(out), _stream()),
                    "rails_scores_log_prob")
@@ -1782,19 +1789,19 @@ def scores_gumbel(scores: torch.Tensor, seed: int, first_row: int = 0, mask: Opt
     row's eligible items, in draw order.  The noise is a function of (seed, first_row + r, column) alone -- Philox4x32-10 --: slicing a batch
     and passing each slice's first row reproduces the unsliced call.  seed: an int in [0, 2^64).  out: a (rows, n) fp32 tensor with
     contiguous rows that does not overlap `scores`.  No sync."""
-    rows, n, ld, words, stride, beta = _softmax_args("scores_gumbel", scores, mask, temperature)
+    rows, n, ld, words, stride, beta = _row_pass_args("scores_gumbel", scores, mask, temperature)
     if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
         raise ValueError(f"scores_gumbel: seed must be an int in [0, 2^64), got {seed!r}")
     if isinstance(first_row, bool) or not isinstance(first_row, int) or not 0 <= first_row < 1 << 62:
         raise ValueError(f"scores_gumbel: first_row must be an int >= 0, got {first_row!r}")
+    refused = f"scores_gumbel: out must be a ({rows}, {n}) fp32 tensor with contiguous rows on the scores' device"
     if out is None:
         out = torch.empty((rows, n), dtype=torch.float32, device=scores.device)
-    elif (not torch.is_tensor(out) or out.shape != (rows, n) or out.dtype != torch.float32 or out.device != scores.device
-          or (n > 1 and out.stride(1) != 1) or (rows > 1 and out.stride(0) < n)):
-        raise ValueError(f"scores_gumbel: out must be a ({rows}, {n}) fp32 tensor with contiguous rows on the scores' device")
+    elif not torch.is_tensor(out) or out.shape != (rows, n) or out.device != scores.device or (rows > 1 and out.stride(0) < n):      # (rows that are written do not overlap)
+        raise ValueError(refused)
+    out_ld = _score_matrix(out, "out", refused)[2]
     if rows == 0:
         return out
-    out_ld = out.stride(0) if rows > 1 else max(n, out.stride(0))
     with _on_device(scores.device):
         _lib.check(_lib.load().rails_scores_gumbel(_ptr(scores), ld, rows, n, beta, seed, first_row, words, stride, _ptr(out), out_ld, _stream()),
                    "rails_scores_gumbel")
@@ -1819,15 +1826,11 @@ def _range_count(what: str, scores: torch.Tensor, thresholds, mask, temperature:
     """The checks and the counting pass of scores_range_count / scores_range -> (the write pass' leading arguments, the tensors behind them,
     counts, lims).  The caller of the write pass holds on to the tensors until it has launched: the workspace carries the slots' counts and
     offsets from one pass to the other, and a freed block would be handed to the next allocation."""
-    rows, n, ld, words, stride, beta = _softmax_args(what, scores, mask, temperature)
+    rows, n, ld, words, stride, beta = _row_pass_args(what, scores, mask, temperature)
     if lse is None and beta != 1.0:
         raise ValueError(f"{what}: temperature = {temperature!r} without lse: a score threshold is compared with the raw score")
     if lse is not None:
-        if not torch.is_tensor(lse) or lse.dtype != torch.float32 or lse.shape != (rows,):
-            raise ValueError(f"{what}: lse must be ({rows},) fp32")
-        if lse.device != scores.device:
-            raise ValueError(f"{what}: the lse and the scores live on different devices")
-        lse = lse.contiguous()
+        lse = _lse_arg(what, lse, rows, scores.device)
     thr = range_thresholds(what, thresholds, rows, scores.device)
     counts = torch.empty((rows,), dtype=torch.int64, device=scores.device)
     lims = torch.zeros((rows + 1,), dtype=torch.int64, device=scores.device)
@@ -1989,10 +1992,7 @@ def scores_mask_tags(scores: torch.Tensor, filt: TagFilter, first_item: int = 0,
     """In place: scores[r, x] = fill wherever item first_item + x carries no bit of the allow word of row r's query (rails_scores_mask_tags); kept
     entries are neither read nor written.  scores (rows, n) fp32 with unit column stride, rows a multiple of the filter's rows: consecutive
     blocks of rows / filt.rows rows share an allow word (the component matrix has P_Q * P_X rows per query; a shared word covers every row)."""
-    _require_device(scores, "scores")
-    if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
-        raise ValueError("scores must be (rows, n) fp32 with contiguous rows")
-    rows, n = scores.shape
+    rows, n, ld = _score_matrix(scores)
     if first_item < 0 or first_item + n > filt.n_items:
         raise ValueError(f"scores_mask_tags: items [{first_item}, {first_item + n}) are not inside the {filt.n_items} tagged items")
     if rows % filt.rows:
@@ -2000,7 +2000,7 @@ def scores_mask_tags(scores: torch.Tensor, filt: TagFilter, first_item: int = 0,
     if filt.eff.device != scores.device:
         raise ValueError("scores_mask_tags: the tags and the scores live on different devices")
     with _on_device(scores.device):
-        _lib.check(_lib.load().rails_scores_mask_tags(_ptr(scores), scores.stride(0) if rows > 1 else max(n, scores.stride(0)), rows, n, first_item,
+        _lib.check(_lib.load().rails_scores_mask_tags(_ptr(scores), ld, rows, n, first_item,
                                                       _ptr(filt.eff), _ptr(filt.allowed), rows // filt.rows, float(fill), _pred(run_if), _stream()),
                    "rails_scores_mask_tags")
     return scores

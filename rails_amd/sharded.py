@@ -303,36 +303,34 @@ class ShardedTopK(TopKModule):
     def remove_items(self, positions: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError(f"{type(self).__name__}.remove_items: shrinking an item-sharded corpus would move the shard bounds; build the shards again")
 
-    # ---- exact ranks: not built on the item-sharded wrappers ----------------------------------------------------------
+    # ---- exact ranks, the softmax over the corpus, range search (DESIGN sections 3.17 - 3.19): not built on the item-sharded wrappers ----------
+    def _refuse_streaming(self, what: str, why: str):
+        raise NotImplementedError(f"{type(self).__name__}.{what}: {why}")
+
     def rank_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids=None, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__}.rank_of: {_RANK_WHY}")
+        self._refuse_streaming("rank_of", _RANK_WHY)
 
     def rank_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids=None, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__}.rank_of_positions: {_RANK_WHY}")
-
-    # ---- softmax over the corpus: not built on the item-sharded wrappers ----------------------------------------------
-    def _refuse_softmax(self, what: str):
-        raise NotImplementedError(f"{type(self).__name__}.{what}: {_SOFTMAX_WHY}")
+        self._refuse_streaming("rank_of_positions", _RANK_WHY)
 
     def log_partition(self, query_embeddings: torch.Tensor, invalid_ids=None, temperature: float = 1.0, **kwargs):
-        self._refuse_softmax("log_partition")
+        self._refuse_streaming("log_partition", _SOFTMAX_WHY)
 
     def log_prob_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids=None, temperature: float = 1.0, **kwargs):
-        self._refuse_softmax("log_prob_of")
+        self._refuse_streaming("log_prob_of", _SOFTMAX_WHY)
 
     def log_prob_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids=None, temperature: float = 1.0, **kwargs):
-        self._refuse_softmax("log_prob_of_positions")
+        self._refuse_streaming("log_prob_of_positions", _SOFTMAX_WHY)
 
     def sample_items(self, query_embeddings: torch.Tensor, num_samples: int, seed: int, temperature: float = 1.0, invalid_ids=None, **kwargs):
-        self._refuse_softmax("sample_items")
+        self._refuse_streaming("sample_items", _SOFTMAX_WHY)
 
-    # ---- range search: not built on the item-sharded wrappers -------------------------------------------------------------
     def count_above(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0, invalid_ids=None, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__}.count_above: {_RANGE_WHY}")
+        self._refuse_streaming("count_above", _RANGE_WHY)
 
     def range_search(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0, invalid_ids=None,
                      sort: bool = True, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__}.range_search: {_RANGE_WHY}")
+        self._refuse_streaming("range_search", _RANGE_WHY)
 
     # ---- hidden items: not built on the item-sharded wrappers -------------------------------------------------------
     def _refuse_hidden(self, what: str):

@@ -469,6 +469,233 @@ class _ItemsById:
             self._id_map = None
 
 
+def _ids_arg(what: str, name: str, ids: torch.Tensor, batch: int, width: str = "T") -> None:
+    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.shape[0] != batch or ids.is_floating_point() or ids.dtype == torch.bool:
+        raise ValueError(f"{what}: {name} must be ({batch}, {width}) integer ids")
+
+
+def _positions_arg(what: str, positions: torch.Tensor, batch: int) -> None:
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != batch:
+        raise ValueError(f"{what}: positions must be ({batch}, T) int64")
+
+
+def _join_slices(parts: list):
+    """The per-slice results of a streaming call as the call's: tensors joined along the batch, tuples member by member; a single slice is
+    returned as it is."""
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(torch.cat(m, 0) for m in zip(*parts)) if isinstance(parts[0], tuple) else torch.cat(parts, 0)
+
+
+class Streamed(NamedTuple):
+    """What a family of streaming calls says where it refuses."""
+    lacking: str                                # what a module without exact scores is told it does not have
+    whole: str                                  # why a row's logits are needed whole: the tail of the MAX_LOGIT_BYTES refusal
+
+
+_RANK = Streamed("the exact rank of an item", "a target's key must be read from the matrix that is counted, and corpus chunks are not built")
+_SOFTMAX = Streamed("the softmax over every item of the corpus", "the normaliser needs every item of a row, and corpus chunks are not built")
+_RANGE = Streamed("a range search over every item of the corpus", "a row is counted and written whole, and corpus chunks are not built")
+
+
+class _StreamingScores(_ItemsById):
+    """The calls that stream over the dense (b, N) logit matrix of a query batch (DESIGN sections 3.17 - 3.19): rank_of, the softmax over the
+    corpus and range search.  Built on the exact modules, which supply the one hook, _rank_scores; every other module refuses by name before
+    any launch.  All of them share one entry check (_streaming_call) and one host flow (_eligible_rows): the row's eligible set -- the
+    items it may return: not hidden, inside the call's item_mask= / allowed_tags=, their ids not among the row's invalid_ids -- as mask words,
+    and batch slices of the matrix under the logit policy."""
+
+    MAX_LOGIT_BYTES = 4 << 30      # the logit policy: never more (b, N) logits live than this -- a slice of the batch at a time
+    # The hook, _rank_scores(query_embeddings, **kwargs): all_logits' (b, N) fp32 scores for these rows, unmasked (a recycled buffer will do: it
+    # is consumed before the next call).  None: the module has no exact scores.
+    _rank_scores = None
+
+    @contextlib.contextmanager
+    def one_bind(self):
+        """One look at the module's parameters for a whole call, on the modules that have parameters."""
+        yield
+
+    def _refuse_streaming(self, kwargs: dict, what: str, family: Streamed) -> None:
+        """Reads the type and kwargs alone."""
+        if type(self)._rank_scores is None:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: an approximate module ranks its candidates only; {family.lacking} is "
+                                      "built on MoLBruteForceTopK (and MIPSBruteForceTopK) -- ask a MoLBruteForceTopK over the same corpus")
+        refuse_collapse_groups(self, kwargs, what)
+
+    def _streaming_call(self, what: str, family: Streamed, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], kwargs: dict,
+                        family_check: Optional[Callable[[str], None]] = None, matrices: int = 1, policy_as: Optional[str] = None) -> int:
+        """The checks of a streaming call, before any launch -> the rows of a batch slice under the logit policy (`matrices` (b, N) matrices
+        live).  In this order: the two refusals, the family's own argument checks (family_check, given the call's full name), invalid_ids,
+        the policy's refusal (under the name policy_as, where that is not the call's)."""
+        self._refuse_streaming(kwargs, what, family)
+        if family_check is not None:
+            family_check(f"{type(self).__name__}.{what}")
+        N = self.num_items
+        if invalid_ids is not None:
+            _ids_arg(what, "invalid_ids", invalid_ids, query_embeddings.size(0), "S")
+        rows = int(self.MAX_LOGIT_BYTES) // (N * 4 * matrices)
+        if rows < 1:
+            raise NotImplementedError(f"{type(self).__name__}.{policy_as or what}: {'two rows' if matrices == 2 else 'one row'} of {N} logits exceed"
+                                      f"{'' if matrices == 2 else 's'} MAX_LOGIT_BYTES; {family.whole}")
+        return rows
+
+    @contextlib.contextmanager
+    def _eligible_rows(self, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], kwargs: dict, rows: int):
+        """The host flow of the streaming calls: inside the block (inference mode, one bind) the value is a generator of (b0, b1, scores,
+        words) over batch slices of at most `rows` rows -- scores: _rank_scores of the slice (a recycled buffer: consumed before the next
+        step), words: the eligible items of these rows as engine.scores_rank takes them (None: every item)."""
+        B, N = query_embeddings.size(0), self.num_items
+        with torch.inference_mode(), self.one_bind():
+            mask = self._take_item_mask(kwargs, B, None)      # the hidden set, allowed_tags= and item_mask= as one mask (its syncs are the call's only ones)
+            words = None if mask is None else mask.words
+            if invalid_ids is not None and invalid_ids.shape[1] > 0:
+                seen = self.positions_of(invalid_ids.reshape(-1)).view(B, -1)
+                # a per-row COPY of the mask (a shared row, or "every item", repeated), from which each row's seen positions are cleared
+                if words is None:
+                    words = E.visibility_row(N, self._ids_flat.device).repeat(B, 1)
+                elif mask.shared:
+                    words = words.repeat(B, 1)
+                else:
+                    words = words.clone(memory_format=torch.contiguous_format)
+                E.item_mask_clear_rows(words, seen, N)
+
+            def slices():
+                for b0 in range(0, B, rows):
+                    b1 = min(B, b0 + rows)
+                    kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kwargs.items()}
+                    yield b0, b1, self._rank_scores(query_embeddings[b0:b1], **kw), None if words is None else words if words.shape[0] == 1 else words[b0:b1]
+
+            yield slices()
+
+    # ---- rank_of: the exact rank of given items per query row (DESIGN section 3.17) ---------------------------------------------------------
+    # rank(b, x) = 1 + the number of items row b may return whose selection key (score descending, position ascending, on all_logits' bits)
+    # exceeds x's: the index of x in the row's exhaustive get_top_k_outputs list, plus one.  0: not ranked -- x is not in the corpus or not
+    # in the row's eligible set.
+    def rank_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """(B, T) int64: the rank of the item carrying target_ids[b, j] ((B, T) integer ids, resolved through the live id map) for query row b;
+        0 where the corpus has no such item or the row may not return it.  invalid_ids (B, S): the row's seen ids, which leave its eligible
+        set (ids nobody has are ignored).  kwargs: what all_logits takes (user_ids, item_mask=, allowed_tags=)."""
+        self._refuse_streaming(kwargs, "rank_of", _RANK)
+        B = query_embeddings.size(0)
+        _ids_arg("rank_of", "target_ids", target_ids, B)
+        positions = self.positions_of(target_ids.reshape(-1)).view(B, -1)
+        return self.rank_of_positions(query_embeddings, positions, invalid_ids, **kwargs)
+
+    def rank_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """rank_of for targets given as corpus POSITIONS ((B, T) int64; one outside [0, N), such as the -1 positions_of gives an unknown id, gets
+        rank 0)."""
+        rows = self._streaming_call("rank_of_positions", _RANK, query_embeddings, invalid_ids, kwargs, policy_as="rank_of",
+                                    family_check=lambda _: _positions_arg("rank_of_positions", positions, query_embeddings.size(0)))
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            positions = positions.to(self._ids_flat.device)
+            return _join_slices([E.scores_rank(scores, positions[b0:b1], words) for b0, b1, scores, words in slices])
+
+    # ---- softmax over the corpus: log_partition, log_prob_of, sample_items (DESIGN section 3.18) -------------------------------------------------
+    # Over the row's eligible set, with beta = fp32(1 / temperature): log_partition = log sum exp(logit * beta), log_prob_of = logit * beta -
+    # log_partition, sample_items = draws without replacement from that softmax (Gumbel top-k).
+    def _softmax_call(self, what: str, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], temperature: float, kwargs: dict,
+                      matrices: int = 1) -> int:
+        return self._streaming_call(what, _SOFTMAX, query_embeddings, invalid_ids, kwargs, lambda name: E.inv_temperature(temperature, name), matrices)
+
+    def log_partition(self, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, temperature: float = 1.0, **kwargs) -> torch.Tensor:
+        """(B,) fp32: log sum exp(logit / temperature) over the items query row b may return -- all_logits' bits, the hidden set, the call's
+        item_mask= / allowed_tags= and the row's invalid_ids honoured as rank_of honours them --, the normaliser that turns a score of
+        get_top_k_outputs into a log-probability.  -inf for a row that may return nothing.  One dense pass and two reads of its matrix."""
+        rows = self._softmax_call("log_partition", query_embeddings, invalid_ids, temperature, kwargs)
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            return _join_slices([E.scores_lse(scores, words, temperature) for _, _, scores, words in slices])
+
+    def log_prob_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, temperature: float = 1.0,
+                    **kwargs) -> torch.Tensor:
+        """(B, T) fp32: the log-probability of the item carrying target_ids[b, j] under softmax(logits / temperature) over the items query row
+        b may return: fp32(logit * beta) - log_partition.  -inf where the corpus has no such item or the row may not return it."""
+        self._softmax_call("log_prob_of", query_embeddings, invalid_ids, temperature, kwargs)
+        B = query_embeddings.size(0)
+        _ids_arg("log_prob_of", "target_ids", target_ids, B)
+        positions = self.positions_of(target_ids.reshape(-1)).view(B, -1)
+        return self.log_prob_of_positions(query_embeddings, positions, invalid_ids, temperature, **kwargs)
+
+    def log_prob_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None,
+                              temperature: float = 1.0, **kwargs) -> torch.Tensor:
+        """log_prob_of for targets given as corpus POSITIONS ((B, T) int64; one outside [0, N) gets -inf)."""
+        rows = self._softmax_call("log_prob_of_positions", query_embeddings, invalid_ids, temperature, kwargs)
+        _positions_arg("log_prob_of_positions", positions, query_embeddings.size(0))
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            positions = positions.to(self._ids_flat.device)
+            return _join_slices([E.scores_log_prob(scores, positions[b0:b1], E.scores_lse(scores, words, temperature), words, temperature)
+                                 for b0, b1, scores, words in slices])
+
+    def sample_items(self, query_embeddings: torch.Tensor, num_samples: int, seed: int, temperature: float = 1.0,
+                     invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(ids (B, S) int64, log_probs (B, S) fp32): S = num_samples items per query row drawn WITHOUT replacement from softmax(logits /
+        temperature) over the items the row may return, in draw order, each with its log-probability under that softmax (log_prob_of's
+        value; the probability of the FIRST draw).  Gumbel top-k: engine.scores_gumbel, then the exact top-k of the perturbed matrix.  A row
+        with fewer than S items of non-zero probability ends in (-1, -inf) entries.  seed: an int in [0, 2^64); the noise of (seed, batch row,
+        item position) does not depend on how the logit policy slices the batch.  Two (b, N) matrices live per slice."""
+        rows = self._softmax_call("sample_items", query_embeddings, invalid_ids, temperature, kwargs, matrices=2)
+        B, N = query_embeddings.size(0), self.num_items
+        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or not 1 <= num_samples <= min(N, E.TOPK_MAX_K):
+            raise ValueError(f"sample_items: num_samples must be an int in [1, {min(N, E.TOPK_MAX_K)}] (the corpus holds {N} items, the exact top-k "
+                             f"takes k <= {E.TOPK_MAX_K}), got {num_samples!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"sample_items: seed must be an int in [0, 2^64), got {seed!r}")
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            parts = []
+            perturbed = torch.empty((min(rows, B), N), dtype=torch.float32, device=self._ids_flat.device)      # the second matrix, shared by the slices
+            for b0, b1, scores, words in slices:
+                noisy = E.scores_gumbel(scores, seed, b0, words, temperature, out=perturbed[: b1 - b0])
+                top, pos = E.topk(noisy, num_samples)
+                lp = E.scores_log_prob(scores, pos, E.scores_lse(scores, words, temperature), words, temperature)
+                drawn = top != float("-inf")      # (a perturbed -inf: an item outside the row's eligible set, or one of probability zero)
+                parts.append((torch.where(drawn, self._ids_flat[pos], -1), torch.where(drawn, lp, float("-inf"))))
+            return _join_slices(parts)
+
+    # ---- range search: count_above, range_search (DESIGN section 3.19) ---------------------------------------------------------------------------
+    # Which items of the row's eligible set meet the row's threshold, and how many: logit >= min_score on all_logits' bits, or log_prob_of's
+    # value >= min_log_prob.  An IEEE fp32 compare (NaN on either side: no hit).
+    def _range_call(self, what: str, query_embeddings: torch.Tensor, min_score, min_log_prob, temperature: float, invalid_ids: Optional[torch.Tensor],
+                    kwargs: dict) -> Tuple[int, torch.Tensor]:
+        """The checks of a range call, before any launch -> (the rows of a batch slice under the logit policy, the (B,) fp32 thresholds)."""
+        def one_threshold(name: str) -> None:
+            if (min_score is None) == (min_log_prob is None):
+                raise ValueError(f"{name}: exactly one of min_score= and min_log_prob= is given, got {'both' if min_score is not None else 'neither'}")
+            if E.inv_temperature(temperature, name) != 1.0 and min_score is not None:
+                raise ValueError(f"{name}: temperature = {temperature!r} with min_score=: a score threshold is compared with the raw logit; "
+                                 "temperature goes with min_log_prob=")
+
+        rows = self._streaming_call(what, _RANGE, query_embeddings, invalid_ids, kwargs, one_threshold)
+        return rows, E.range_thresholds(f"{type(self).__name__}.{what}", min_score if min_score is not None else min_log_prob, query_embeddings.size(0),
+                                        self._ids_flat.device)
+
+    def count_above(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0,
+                    invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """(B,) int64: how many items query row b may return score at least its threshold -- logit >= min_score on all_logits' bits, or
+        log_prob_of's value (at `temperature`) >= min_log_prob; exactly one of the two, a number or a (B,) tensor.  The hidden set, the
+        call's item_mask= / allowed_tags= and the row's invalid_ids are honoured as rank_of honours them.  One dense pass and one read of its
+        matrix (three in the log-probability form: the normaliser first); no host sync beyond the mask's."""
+        rows, thr = self._range_call("count_above", query_embeddings, min_score, min_log_prob, temperature, invalid_ids, kwargs)
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            return _join_slices([E.scores_range_count(scores, thr[b0:b1], words, temperature,
+                                                      None if min_log_prob is None else E.scores_lse(scores, words, temperature))
+                                 for b0, b1, scores, words in slices])
+
+    def range_search(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0,
+                     invalid_ids: Optional[torch.Tensor] = None, sort: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(lims (B + 1,) int64, scores (lims[B],) fp32, ids (lims[B],) int64): the items count_above counts, row b's in
+        [lims[b], lims[b + 1]) with their raw logits.  sort=True: each row in get_top_k_outputs' order (score descending, then position
+        ascending) -- that exhaustive ranking without the items that miss; a row of more than engine.RANGE_SORT_MAX hits raises ValueError.
+        sort=False: position ascending, any count.  One read-back of lims per batch slice of the logit policy, the call's only sync beyond
+        the mask's."""
+        rows, thr = self._range_call("range_search", query_embeddings, min_score, min_log_prob, temperature, invalid_ids, kwargs)
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+            parts = []
+            for b0, b1, scores, words in slices:
+                lse = None if min_log_prob is None else E.scores_lse(scores, words, temperature)
+                lims, s, i = E.scores_range(scores, thr[b0:b1], words, temperature, lse, ids=self._ids_flat, sort=sort)
+                parts.append((lims if not parts else lims[1:] + parts[-1][0][-1], s, i))      # (cumulative over the slices; a device add, no sync)
+            return _join_slices(parts)
+
+
 IN_PLACE, CONCATENATED, CUT_AND_FILLED = "in place", "concatenated", "cut and filled"
 
 
@@ -494,7 +721,7 @@ class Held(NamedTuple):
     settle: Optional[Callable[..., None]] = None    # (tk, eng): after the edit, resized or not
 
 
-class _CorpusEdits(_ItemsById):
+class _CorpusEdits(_StreamingScores):
     """The in-place corpus API, shared by MoLTopKModule and MIPSBruteForceTopK: the three calls describe themselves as a
     CorpusEdit and _apply is the one flow that carries it out, over the class's list of held buffers.  After any sequence of the calls the
     module holds what a module freshly constructed from the resulting table and ids holds -- every derived buffer bit for bit -- and answers
@@ -816,217 +1043,6 @@ class _CorpusEdits(_ItemsById):
     def collapse_stats(self) -> dict:
         """Which path answered the collapsed calls so far: calls, walk_redos (depth doublings), fallbacks (exact group-maxima passes)."""
         return dict(self.__dict__.setdefault("_collapse_stats", {"calls": 0, "walk_redos": 0, "fallbacks": 0}))
-
-    # ---- rank_of: the exact rank of given items per query row (DESIGN section 3.17) ---------------------------------------------------------
-    # rank(b, x) = 1 + the number of items row b may return whose selection key (score descending, position ascending, on all_logits' bits)
-    # exceeds x's: the index of x in the row's exhaustive get_top_k_outputs list, plus one.  0: not ranked -- x is not in the corpus, is hidden,
-    # lies outside the call's item_mask= / allowed_tags=, or its id is among the row's invalid_ids.  Built on the exact modules, which supply
-    # _rank_scores; every other module refuses by name before any launch.
-    def _rank_scores(self, query_embeddings: torch.Tensor, **kwargs) -> Optional[torch.Tensor]:
-        """all_logits' (b, N) fp32 scores for these rows, unmasked (a recycled buffer will do: it is consumed before the next call); None on
-        the modules that have no exact rank."""
-        return None
-
-    def _refuse_rank_of(self, kwargs: dict, what: str, thing: str = "the exact rank of an item") -> None:
-        if type(self)._rank_scores is _CorpusEdits._rank_scores:
-            raise NotImplementedError(f"{type(self).__name__}.{what}: an approximate module ranks its candidates only; {thing} is "
-                                      "built on MoLBruteForceTopK (and MIPSBruteForceTopK) -- ask a MoLBruteForceTopK over the same corpus")
-        refuse_collapse_groups(self, kwargs, what)
-
-    def rank_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
-        """(B, T) int64: the rank of the item carrying target_ids[b, j] ((B, T) integer ids, resolved through the live id map) for query row b;
-        0 where the corpus has no such item or the row may not return it.  invalid_ids (B, S): the row's seen ids, which leave its eligible
-        set (ids nobody has are ignored).  kwargs: what all_logits takes (user_ids, item_mask=, allowed_tags=)."""
-        self._refuse_rank_of(kwargs, "rank_of")
-        B = query_embeddings.size(0)
-        if not torch.is_tensor(target_ids) or target_ids.dim() != 2 or target_ids.shape[0] != B or target_ids.is_floating_point() or target_ids.dtype == torch.bool:
-            raise ValueError(f"rank_of: target_ids must be ({B}, T) integer ids")
-        positions = self.positions_of(target_ids.reshape(-1)).view(B, -1)
-        return self.rank_of_positions(query_embeddings, positions, invalid_ids, **kwargs)
-
-    def rank_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
-        """rank_of for targets given as corpus POSITIONS ((B, T) int64; one outside [0, N), such as the -1 positions_of gives an unknown id, gets
-        rank 0)."""
-        self._refuse_rank_of(kwargs, "rank_of_positions")
-        B, N = query_embeddings.size(0), self.num_items
-        dev = self._ids_flat.device
-        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != B:
-            raise ValueError(f"rank_of_positions: positions must be ({B}, T) int64")
-        if invalid_ids is not None and (not torch.is_tensor(invalid_ids) or invalid_ids.dim() != 2 or invalid_ids.shape[0] != B
-                                        or invalid_ids.is_floating_point() or invalid_ids.dtype == torch.bool):
-            raise ValueError(f"rank_of_positions: invalid_ids must be ({B}, S) integer ids")
-        rows = int(getattr(self, "MAX_LOGIT_BYTES", 4 << 30)) // (N * 4)      # the logit policy: a slice of the batch at a time
-        if rows < 1:
-            raise NotImplementedError(f"{type(self).__name__}.rank_of: one row of {N} logits exceeds MAX_LOGIT_BYTES; a target's key must be read "
-                                      "from the matrix that is counted, and corpus chunks are not built")
-        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
-            positions = positions.to(dev)
-            out = [E.scores_rank(scores, positions[b0:b1], words) for b0, b1, scores, words in slices]
-            return out[0] if len(out) == 1 else torch.cat(out, 0)
-
-    @contextlib.contextmanager
-    def _eligible_rows(self, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], kwargs: dict, rows: int):
-        """The host flow of the streaming passes over all_logits (rank_of, log_partition, log_prob_of, sample_items): inside the block (inference
-        mode, one bind) the value is a generator of (b0, b1, scores, words) over batch slices of at most `rows` rows -- scores: _rank_scores of
-        the slice (a recycled buffer: consumed before the next step), words: the eligible items of these rows as engine.scores_rank takes
-        them (None: every item)."""
-        B, N = query_embeddings.size(0), self.num_items
-        bind = getattr(self, "one_bind", None)
-        with torch.inference_mode(), (bind() if bind is not None else contextlib.nullcontext()):
-            mask = self._take_item_mask(kwargs, B, None)      # the hidden set, allowed_tags= and item_mask= as one mask (its syncs are the call's only ones)
-            words = None if mask is None else mask.words
-            if invalid_ids is not None and invalid_ids.shape[1] > 0:
-                seen = self.positions_of(invalid_ids.reshape(-1)).view(B, -1)
-                # a per-row COPY of the mask (a shared row, or "every item", repeated), from which each row's seen positions are cleared
-                if words is None:
-                    words = E.visibility_row(N, self._ids_flat.device).repeat(B, 1)
-                elif mask.shared:
-                    words = words.repeat(B, 1)
-                else:
-                    words = words.clone(memory_format=torch.contiguous_format)
-                E.item_mask_clear_rows(words, seen, N)
-
-            def slices():
-                for b0 in range(0, B, rows):
-                    b1 = min(B, b0 + rows)
-                    kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kwargs.items()}
-                    yield b0, b1, self._rank_scores(query_embeddings[b0:b1], **kw), None if words is None else words if words.shape[0] == 1 else words[b0:b1]
-
-            yield slices()
-
-    # ---- softmax over the corpus: log_partition, log_prob_of, sample_items (DESIGN section 3.18) -------------------------------------------------
-    # Over the items row b may return -- rank_of's eligible set -- with beta = fp32(1 / temperature): log_partition = log sum exp(logit * beta),
-    # log_prob_of = logit * beta - log_partition, sample_items = draws without replacement from that softmax (Gumbel top-k).  Built on
-    # _rank_scores like rank_of, with its refusals.
-    def _softmax_call(self, what: str, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], temperature: float, kwargs: dict,
-                      matrices: int = 1) -> int:
-        """The checks of a softmax call, before any launch -> the rows of a batch slice under the logit policy (`matrices` (b, N) matrices live)."""
-        self._refuse_rank_of(kwargs, what, "the softmax over every item of the corpus")
-        E.inv_temperature(temperature, f"{type(self).__name__}.{what}")
-        B, N = query_embeddings.size(0), self.num_items
-        if invalid_ids is not None and (not torch.is_tensor(invalid_ids) or invalid_ids.dim() != 2 or invalid_ids.shape[0] != B
-                                        or invalid_ids.is_floating_point() or invalid_ids.dtype == torch.bool):
-            raise ValueError(f"{what}: invalid_ids must be ({B}, S) integer ids")
-        rows = int(getattr(self, "MAX_LOGIT_BYTES", 4 << 30)) // (N * 4 * matrices)
-        if rows < 1:
-            raise NotImplementedError(f"{type(self).__name__}.{what}: {'two rows' if matrices == 2 else 'one row'} of {N} logits exceed"
-                                      f"{'' if matrices == 2 else 's'} MAX_LOGIT_BYTES; the normaliser needs every item of a row, and corpus chunks are not built")
-        return rows
-
-    def log_partition(self, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, temperature: float = 1.0, **kwargs) -> torch.Tensor:
-        """(B,) fp32: log sum exp(logit / temperature) over the items query row b may return -- all_logits' bits, the hidden set, the call's
-        item_mask= / allowed_tags= and the row's invalid_ids honoured as rank_of honours them --, the normaliser that turns a score of
-        get_top_k_outputs into a log-probability.  -inf for a row that may return nothing.  One dense pass and two reads of its matrix."""
-        rows = self._softmax_call("log_partition", query_embeddings, invalid_ids, temperature, kwargs)
-        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
-            out = [E.scores_lse(scores, words, temperature) for _, _, scores, words in slices]
-            return out[0] if len(out) == 1 else torch.cat(out, 0)
-
-    def log_prob_of(self, query_embeddings: torch.Tensor, target_ids: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, temperature: float = 1.0,
-                    **kwargs) -> torch.Tensor:
-        """(B, T) fp32: the log-probability of the item carrying target_ids[b, j] under softmax(logits / temperature) over the items query row
-        b may return: fp32(logit * beta) - log_partition.  -inf where the corpus has no such item or the row may not return it."""
-        self._softmax_call("log_prob_of", query_embeddings, invalid_ids, temperature, kwargs)
-        B = query_embeddings.size(0)
-        if not torch.is_tensor(target_ids) or target_ids.dim() != 2 or target_ids.shape[0] != B or target_ids.is_floating_point() or target_ids.dtype == torch.bool:
-            raise ValueError(f"log_prob_of: target_ids must be ({B}, T) integer ids")
-        positions = self.positions_of(target_ids.reshape(-1)).view(B, -1)
-        return self.log_prob_of_positions(query_embeddings, positions, invalid_ids, temperature, **kwargs)
-
-    def log_prob_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None,
-                              temperature: float = 1.0, **kwargs) -> torch.Tensor:
-        """log_prob_of for targets given as corpus POSITIONS ((B, T) int64; one outside [0, N) gets -inf)."""
-        rows = self._softmax_call("log_prob_of_positions", query_embeddings, invalid_ids, temperature, kwargs)
-        B = query_embeddings.size(0)
-        if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or positions.shape[0] != B:
-            raise ValueError(f"log_prob_of_positions: positions must be ({B}, T) int64")
-        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
-            positions = positions.to(self._ids_flat.device)
-            out = [E.scores_log_prob(scores, positions[b0:b1], E.scores_lse(scores, words, temperature), words, temperature)
-                   for b0, b1, scores, words in slices]
-            return out[0] if len(out) == 1 else torch.cat(out, 0)
-
-    def sample_items(self, query_embeddings: torch.Tensor, num_samples: int, seed: int, temperature: float = 1.0,
-                     invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(ids (B, S) int64, log_probs (B, S) fp32): S = num_samples items per query row drawn WITHOUT replacement from softmax(logits /
-        temperature) over the items the row may return, in draw order, each with its log-probability under that softmax (log_prob_of's
-        value; the probability of the FIRST draw).  Gumbel top-k: engine.scores_gumbel, then the exact top-k of the perturbed matrix.  A row
-        with fewer than S items of non-zero probability ends in (-1, -inf) entries.  seed: an int in [0, 2^64); the noise of (seed, batch row,
-        item position) does not depend on how the logit policy slices the batch.  Two (b, N) matrices live per slice."""
-        rows = self._softmax_call("sample_items", query_embeddings, invalid_ids, temperature, kwargs, matrices=2)
-        B, N = query_embeddings.size(0), self.num_items
-        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or not 1 <= num_samples <= min(N, E.TOPK_MAX_K):
-            raise ValueError(f"sample_items: num_samples must be an int in [1, {min(N, E.TOPK_MAX_K)}] (the corpus holds {N} items, the exact top-k "
-                             f"takes k <= {E.TOPK_MAX_K}), got {num_samples!r}")
-        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
-            raise ValueError(f"sample_items: seed must be an int in [0, 2^64), got {seed!r}")
-        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
-            ids_out, lp_out = [], []
-            perturbed = torch.empty((min(rows, B), N), dtype=torch.float32, device=self._ids_flat.device)      # the second matrix, shared by the slices
-            for b0, b1, scores, words in slices:
-                noisy = E.scores_gumbel(scores, seed, b0, words, temperature, out=perturbed[: b1 - b0])
-                top, pos = E.topk(noisy, num_samples)
-                lp = E.scores_log_prob(scores, pos, E.scores_lse(scores, words, temperature), words, temperature)
-                drawn = top != float("-inf")      # (a perturbed -inf: an item outside the row's eligible set, or one of probability zero)
-                ids_out.append(torch.where(drawn, self._ids_flat[pos], -1))
-                lp_out.append(torch.where(drawn, lp, float("-inf")))
-            return (ids_out[0], lp_out[0]) if len(ids_out) == 1 else (torch.cat(ids_out, 0), torch.cat(lp_out, 0))
-
-    # ---- range search: count_above, range_search (DESIGN section 3.19) ---------------------------------------------------------------------------
-    # Which items row b may return -- rank_of's eligible set -- meet the row's threshold, and how many: logit >= min_score on all_logits' bits,
-    # or log_prob_of's value >= min_log_prob.  An IEEE fp32 compare (NaN on either side: no hit).  Built on _rank_scores like rank_of, with its
-    # refusals.
-    def _range_call(self, what: str, query_embeddings: torch.Tensor, min_score, min_log_prob, temperature: float, invalid_ids: Optional[torch.Tensor],
-                    kwargs: dict) -> Tuple[int, torch.Tensor]:
-        """The checks of a range call, before any launch -> (the rows of a batch slice under the logit policy, the (B,) fp32 thresholds)."""
-        self._refuse_rank_of(kwargs, what, "a range search over every item of the corpus")
-        name = f"{type(self).__name__}.{what}"
-        if (min_score is None) == (min_log_prob is None):
-            raise ValueError(f"{name}: exactly one of min_score= and min_log_prob= is given, got {'both' if min_score is not None else 'neither'}")
-        if E.inv_temperature(temperature, name) != 1.0 and min_score is not None:
-            raise ValueError(f"{name}: temperature = {temperature!r} with min_score=: a score threshold is compared with the raw logit; "
-                             "temperature goes with min_log_prob=")
-        B, N = query_embeddings.size(0), self.num_items
-        if invalid_ids is not None and (not torch.is_tensor(invalid_ids) or invalid_ids.dim() != 2 or invalid_ids.shape[0] != B
-                                        or invalid_ids.is_floating_point() or invalid_ids.dtype == torch.bool):
-            raise ValueError(f"{what}: invalid_ids must be ({B}, S) integer ids")
-        rows = int(getattr(self, "MAX_LOGIT_BYTES", 4 << 30)) // (N * 4)
-        if rows < 1:
-            raise NotImplementedError(f"{name}: one row of {N} logits exceeds MAX_LOGIT_BYTES; a row is counted and written whole, and corpus "
-                                      "chunks are not built")
-        return rows, E.range_thresholds(name, min_score if min_score is not None else min_log_prob, B, self._ids_flat.device)
-
-    def count_above(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0,
-                    invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
-        """(B,) int64: how many items query row b may return score at least its threshold -- logit >= min_score on all_logits' bits, or
-        log_prob_of's value (at `temperature`) >= min_log_prob; exactly one of the two, a number or a (B,) tensor.  The hidden set, the
-        call's item_mask= / allowed_tags= and the row's invalid_ids are honoured as rank_of honours them.  One dense pass and one read of its
-        matrix (three in the log-probability form: the normaliser first); no host sync beyond the mask's."""
-        rows, thr = self._range_call("count_above", query_embeddings, min_score, min_log_prob, temperature, invalid_ids, kwargs)
-        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
-            out = [E.scores_range_count(scores, thr[b0:b1], words, temperature, None if min_log_prob is None else E.scores_lse(scores, words, temperature))
-                   for b0, b1, scores, words in slices]
-            return out[0] if len(out) == 1 else torch.cat(out, 0)
-
-    def range_search(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0,
-                     invalid_ids: Optional[torch.Tensor] = None, sort: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(lims (B + 1,) int64, scores (lims[B],) fp32, ids (lims[B],) int64): the items count_above counts, row b's in
-        [lims[b], lims[b + 1]) with their raw logits.  sort=True: each row in get_top_k_outputs' order (score descending, then position
-        ascending) -- that exhaustive ranking without the items that miss; a row of more than engine.RANGE_SORT_MAX hits raises ValueError.
-        sort=False: position ascending, any count.  One read-back of lims per batch slice of the logit policy, the call's only sync beyond
-        the mask's."""
-        rows, thr = self._range_call("range_search", query_embeddings, min_score, min_log_prob, temperature, invalid_ids, kwargs)
-        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
-            lims, scores_out, ids_out = [], [], []
-            for b0, b1, scores, words in slices:
-                lse = None if min_log_prob is None else E.scores_lse(scores, words, temperature)
-                l, s, i = E.scores_range(scores, thr[b0:b1], words, temperature, lse, ids=self._ids_flat, sort=sort)
-                lims.append(l if not lims else l[1:] + lims[-1][-1])      # (cumulative over the slices; a device add, no sync)
-                scores_out.append(s)
-                ids_out.append(i)
-            if len(lims) == 1:
-                return lims[0], scores_out[0], ids_out[0]
-            return torch.cat(lims, 0), torch.cat(scores_out, 0), torch.cat(ids_out, 0)
 
     @contextlib.contextmanager
     def _positions_as_ids(self):
