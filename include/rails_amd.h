@@ -50,6 +50,7 @@ extern "C" {
  * item-tag entries rails_item_tags_effective / rails_item_tags_count / rails_item_mask_from_tags / rails_scores_mask_tags / rails_mol_coarse_topk_tagged /
  * rails_mol_component_topk_tagged / rails_mol_scan_plan and the filtered-list entries rails_ivf_list_words / rails_ivf_list_counts /
  * rails_ivf_plan_filtered / rails_ivf_search_filtered and the group-collapse entries rails_topk_collapse / rails_scores_group_max / rails_topk_keys
+ * (and their quota forms rails_topk_collapse_quota / rails_scores_group_next)
  * and the generic route's candidate entries rails_mol_generic_score_indexed / rails_mol_generic_table_width / rails_mol_generic_coarse_build /
  * rails_mol_generic_coarse_update / rails_mol_generic_component_build / rails_mol_generic_component_update / rails_mol_generic_eq_pad
  * and the rank entries rails_scores_rank_keys / rails_scores_rank / rails_item_mask_clear_rows
@@ -759,6 +760,25 @@ int rails_rerank_topk_filtered(const float* scores, int64_t ld, int32_t rows, in
 int rails_topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const int32_t* group_ranks,
                         int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, float* out_scores,
                         int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, void* stream);
+/* The walk with a quota: at most max_per_group (>= 1) results per group.  Arguments, eligibility, outputs, out_counts and *out_of_range as
+ * rails_topk_collapse; an eligible entry is kept iff FEWER THAN max_per_group earlier eligible entries of the list have its rank, and the
+ * outputs are the first k kept entries.  max_per_group = 1 gives rails_topk_collapse's outputs bit for bit; a rank that occurs at most
+ * max_per_group times among the eligible entries (every ungrouped item) never loses one.  One workgroup per row, one launch, no LDS beyond
+ * rails_topk_collapse's; 1 <= depth <= 16 384.  RAILS_EINVAL for max_per_group < 1. */
+int rails_topk_collapse_quota(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const int32_t* group_ranks,
+                              int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, int32_t max_per_group,
+                              float* out_scores, int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, void* stream);
+/* One round of the per-group BEST-m of a score matrix.  The entries rails_scores_group_max considers, by the same tests (finite score, id not
+ * among the row's invalid_ids, the same key); entry x of row b enters table[b * table_stride + r], r = group_ranks[first_item + x], by a
+ * 64-bit integer maximum, only where below[b * below_stride + r] is non-zero and the entry's key is BELOW it.  below == NULL: no bound
+ * (round 0, rails_scores_group_max's result).  With `below` the finished table of round t - 1, round t leaves in every slot the key of its
+ * group's (t + 1)-th best eligible item, 0 once the group has fewer; the result does not depend on the order of arrival, and chunks of one
+ * round may come in any order.  Strides count keys and are >= n_groups, so the m rounds of a row may lie side by side as one row of
+ * m * n_groups keys (table = base + t * n_groups, below = base + (t - 1) * n_groups, both strides m * n_groups), which rails_topk_keys then
+ * ranks: the keys stay distinct.  The CALLER zeroes a round's slots before its first chunk.  Limits as rails_scores_group_max. */
+int rails_scores_group_next(const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const int32_t* group_ranks, int64_t n_groups,
+                            uint64_t* table, int64_t table_stride, const uint64_t* below, int64_t below_stride, const int64_t* ids,
+                            const int64_t* invalid_ids, int32_t width, void* stream);
 /* The per-group maxima of a score matrix: for every FINITE scores[b * ld + x], x < n, whose id is not among row b's invalid_ids,
  * table[b * n_groups + group_ranks[first_item + x]] = max(itself, key) with key = (orderable(score) << 32) | ~(first_item + x), the selection
  * key of rails_topk: afterwards a slot holds the key of its group's best eligible item under (score desc, position asc), 0 where the group

@@ -1295,9 +1295,41 @@ int rails_topk_collapse(const float* scores, int64_t ld, const int64_t* position
     return RAILS_EINVAL;
   }
   if (ld < depth) { set_error("topk_collapse: ld < depth"); return RAILS_EINVAL; }
-  const int r = topk_collapse(scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k, out_scores, out_positions, out_ids,
+  const int r = topk_collapse(scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k, 0, out_scores, out_positions, out_ids,
                               out_counts, out_of_range, (hipStream_t)stream);
   return r == kOk ? r : fail(r, "topk_collapse");
+}
+
+int rails_topk_collapse_quota(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const int32_t* group_ranks,
+                              int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, int32_t max_per_group,
+                              float* out_scores, int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || depth < 0 || k < 0 || width < 0 || n_items < 0) { set_error("topk_collapse_quota: negative size"); return RAILS_EINVAL; }
+  if (max_per_group < 1) { set_error("topk_collapse_quota: max_per_group = %d below 1", max_per_group); return RAILS_EINVAL; }
+  if (rows == 0 || k == 0) return RAILS_OK;
+  if (!scores || !positions || !group_ranks || !out_scores || !out_positions || !out_ids || !out_counts || !out_of_range || (width > 0 && !invalid_ids)) {
+    set_error("topk_collapse_quota: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  if (ld < depth) { set_error("topk_collapse_quota: ld < depth"); return RAILS_EINVAL; }
+  const int r = topk_collapse(scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k, max_per_group, out_scores,
+                              out_positions, out_ids, out_counts, out_of_range, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "topk_collapse_quota");
+}
+
+int rails_scores_group_next(const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const int32_t* group_ranks, int64_t n_groups,
+                            uint64_t* table, int64_t table_stride, const uint64_t* below, int64_t below_stride, const int64_t* ids,
+                            const int64_t* invalid_ids, int32_t width, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || n < 0 || first_item < 0 || n_groups < 0 || width < 0) { set_error("scores_group_next: negative size"); return RAILS_EINVAL; }
+  if (rows == 0 || n_groups == 0 || n == 0) return RAILS_OK;
+  if (!table || !scores || !group_ranks || (width > 0 && !invalid_ids)) { set_error("scores_group_next: NULL pointer"); return RAILS_EINVAL; }
+  if (ld < n) { set_error("scores_group_next: ld < n"); return RAILS_EINVAL; }
+  if (table_stride < n_groups || (below && below_stride < n_groups)) { set_error("scores_group_next: a row stride below n_groups"); return RAILS_EINVAL; }
+  if (below == table) { set_error("scores_group_next: a round cannot bound itself"); return RAILS_EINVAL; }
+  const int r = scores_group_next(scores, ld, rows, n, first_item, group_ranks, n_groups, reinterpret_cast<unsigned long long*>(table), table_stride,
+                                  reinterpret_cast<const unsigned long long*>(below), below_stride, ids, invalid_ids, width, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "scores_group_next");
 }
 
 int rails_scores_group_max(const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const int32_t* group_ranks, int64_t n_groups,

@@ -1,8 +1,11 @@
-// Collapsing a ranked list by item group: at most one result per group.  Three kernels:
+// Collapsing a ranked list by item group: at most one result per group, or at most m.  Four kernels:
 //   collapse_walk_kernel   one workgroup per row over a ranked list of D (score, position) entries in key order: the first k entries whose
-//                          group has not occurred earlier in the list, the seen-id filter inside (rails_topk_collapse)
+//                          group has not occurred earlier in the list, the seen-id filter inside (rails_topk_collapse); its quota form keeps
+//                          the first m entries of every group (rails_topk_collapse_quota)
 //   group_max_kernel       streams a (rows, n) score matrix: table[row][rank] = max over the group's eligible items of the topk_keys.h key
 //                          (rails_scores_group_max) -- the exact fallback where one group owns the head of the ranking
+//   group_next_kernel      the same pass bounded from above by the previous round's table: round t leaves every group's (t + 1)-th best
+//                          eligible item (rails_scores_group_next) -- the fallback of a quota
 //   topk_keys_kernel       the k largest keys of every row of that table, by MSD radix selection, decoded (rails_topk_keys)
 // The kernels see DENSE group ranks (int32 in [0, G), every ungrouped item a rank of its own), never the callers' sparse keys.
 #include "mol_kernels.h"
@@ -23,11 +26,16 @@ constexpr int kSeenTile = 256;                       // seen ids held in LDS at 
 // which puts the entries of one rank side by side with the smallest j first -- the head of every run survives.  A prefix scan over the
 // survivor flags in list order compacts the first k.  Deterministic, order-preserving, no probe loops.
 // LDS: sort_slots keys | depth survivor bytes (dynamic), one tile of seen ids and the scan's wave totals (static).
+// QUOTA: an eligible entry survives iff FEWER THAN max_per_group eligible entries before it have its group rank -- its index within its run
+// of the sorted array is below max_per_group.  The run's start is the last run head at or before the slot: every thread takes a contiguous
+// segment of the sorted slots, a block-wide max-scan of the segments' last head indices hands it the start of the run that reaches into its
+// segment, and it walks the segment once.  No LDS per entry beyond what the plain walk holds; max_per_group = 1 keeps exactly the run heads.
+template <bool QUOTA>
 __global__ __launch_bounds__(kCollapseThreads) void collapse_walk_kernel(
     const float* __restrict__ scores, int64_t ld, const int64_t* __restrict__ positions, int depth, int npad, int sort_slots,
     const int32_t* __restrict__ ranks, int64_t n_items, const int64_t* __restrict__ ids, const int64_t* __restrict__ invalid, int width, int k,
-    float* __restrict__ out_scores, int64_t* __restrict__ out_pos, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_counts,
-    int32_t* __restrict__ out_of_range) {
+    int max_per_group, float* __restrict__ out_scores, int64_t* __restrict__ out_pos, int64_t* __restrict__ out_ids,
+    int32_t* __restrict__ out_counts, int32_t* __restrict__ out_of_range) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
   unsigned char* surv = reinterpret_cast<unsigned char*>(keys + sort_slots);      // [depth]
   __shared__ int64_t seen[kSeenTile];
@@ -63,9 +71,25 @@ __global__ __launch_bounds__(kCollapseThreads) void collapse_walk_kernel(
   __syncthreads();
   for (int j = tid; j < depth; j += kCollapseThreads) surv[j] = 0;
   lds_sort_desc(keys, npad);                            // (ends with a barrier)
-  for (int i = tid; i < npad; i += kCollapseThreads) {
-    const unsigned long long kv = keys[i];
-    if (kv != 0ull && (i == 0 || (keys[i - 1] >> 32) != (kv >> 32))) surv[~(unsigned int)(kv & 0xFFFFFFFFull)] = 1;
+  if (QUOTA) {
+    const int per = npad / kCollapseThreads, i0 = tid * per;      // (npad is a multiple of the workgroup)
+    int last_head = -1;
+    for (int i = i0; i < i0 + per; ++i) {
+      const unsigned long long kv = keys[i];
+      if (kv != 0ull && (i == 0 || (keys[i - 1] >> 32) != (kv >> 32))) last_head = i;
+    }
+    int start = block_scan_max_excl<kCollapseThreads>(last_head, -1, wave_tot);
+    for (int i = i0; i < i0 + per; ++i) {
+      const unsigned long long kv = keys[i];
+      if (kv == 0ull) break;                              // the padding sorts last
+      if (i == 0 || (keys[i - 1] >> 32) != (kv >> 32)) start = i;
+      if (i - start < max_per_group) surv[~(unsigned int)(kv & 0xFFFFFFFFull)] = 1;
+    }
+  } else {
+    for (int i = tid; i < npad; i += kCollapseThreads) {
+      const unsigned long long kv = keys[i];
+      if (kv != 0ull && (i == 0 || (keys[i - 1] >> 32) != (kv >> 32))) surv[~(unsigned int)(kv & 0xFFFFFFFFull)] = 1;
+    }
   }
   __syncthreads();
   // the first k survivors in list order: a contiguous segment of the list per thread
@@ -94,9 +118,10 @@ __global__ __launch_bounds__(kCollapseThreads) void collapse_walk_kernel(
   }
 }
 
+// max_per_group == 0: the plain walk (rails_topk_collapse); >= 1: the quota form, a kernel of its own.
 int topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int rows, int depth, const int32_t* ranks, int64_t n_items,
-                  const int64_t* ids, const int64_t* invalid, int width, int k, float* out_scores, int64_t* out_pos, int64_t* out_ids,
-                  int32_t* out_counts, int32_t* out_of_range, hipStream_t stream) {
+                  const int64_t* ids, const int64_t* invalid, int width, int k, int max_per_group, float* out_scores, int64_t* out_pos,
+                  int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, hipStream_t stream) {
   if (rows <= 0 || k <= 0) return kOk;
   if (depth < 1 || depth > kCollapseMaxDepth) {
     set_error("topk_collapse: depth = %d outside [1, %d]", depth, kCollapseMaxDepth);
@@ -105,11 +130,18 @@ int topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int
   const int npad = next_pow2(depth, kSortThreads);
   const int sort_slots = npad <= kSortThreads ? 3 * npad : npad;      // lds_sort_desc's exchange buffer
   const int lds = sort_slots * (int)sizeof(unsigned long long) + (depth + 15) / 16 * 16;
+  constexpr int max_lds = kCollapseMaxDepth * ((int)sizeof(unsigned long long) + 1);
+  if (max_per_group > 0) {
+    static DynLdsOnce once_quota;
+    if (ensure_dyn_lds(once_quota, reinterpret_cast<const void*>(&collapse_walk_kernel<true>), max_lds) != kOk) return kErrLaunch;
+    hipLaunchKernelGGL(collapse_walk_kernel<true>, dim3(rows), dim3(kCollapseThreads), lds, stream, scores, ld, positions, depth, npad, sort_slots,
+                       ranks, n_items, ids, invalid, width, k, max_per_group, out_scores, out_pos, out_ids, out_counts, out_of_range);
+    return launched();
+  }
   static DynLdsOnce once;
-  if (ensure_dyn_lds(once, reinterpret_cast<const void*>(&collapse_walk_kernel), kCollapseMaxDepth * ((int)sizeof(unsigned long long) + 1)) != kOk)
-    return kErrLaunch;
-  hipLaunchKernelGGL(collapse_walk_kernel, dim3(rows), dim3(kCollapseThreads), lds, stream, scores, ld, positions, depth, npad, sort_slots, ranks,
-                     n_items, ids, invalid, width, k, out_scores, out_pos, out_ids, out_counts, out_of_range);
+  if (ensure_dyn_lds(once, reinterpret_cast<const void*>(&collapse_walk_kernel<false>), max_lds) != kOk) return kErrLaunch;
+  hipLaunchKernelGGL(collapse_walk_kernel<false>, dim3(rows), dim3(kCollapseThreads), lds, stream, scores, ld, positions, depth, npad, sort_slots,
+                     ranks, n_items, ids, invalid, width, k, 1, out_scores, out_pos, out_ids, out_counts, out_of_range);
   return launched();
 }
 
@@ -150,6 +182,59 @@ __global__ __launch_bounds__(kGroupMaxThreads) void group_max_kernel(const float
     }
     atomicMax(&trow[r], kv);
   }
+}
+
+// The rounds of a quota's fallback.  The entries group_max_kernel considers, by the same tests; an entry enters table[row][r] only where the
+// previous round's slot below[row][r] is non-zero and its key lies BELOW that slot: round t then holds the key of every group's (t + 1)-th
+// best eligible item, 0 once the group is exhausted.  below == NULL is round 0 (no bound: group_max_kernel's result).  The table and the
+// bound take their own row strides, so the m rounds of a row lie side by side as one row of m * n_groups keys for topk_keys_kernel.
+__global__ __launch_bounds__(kGroupMaxThreads) void group_next_kernel(const float* __restrict__ scores, int64_t ld, int64_t n, int64_t first_item,
+                                                                     const int32_t* __restrict__ ranks, int64_t n_groups,
+                                                                     unsigned long long* __restrict__ table, int64_t table_stride,
+                                                                     const unsigned long long* __restrict__ below, int64_t below_stride,
+                                                                     const int64_t* __restrict__ ids, const int64_t* __restrict__ invalid, int width) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long gm_seen[];      // [width]
+  const int row = blockIdx.y, tid = threadIdx.x;
+  for (int w = tid; w < width; w += kGroupMaxThreads) gm_seen[w] = (unsigned long long)invalid[(int64_t)row * width + w];
+  __syncthreads();
+  const int64_t begin = (int64_t)blockIdx.x * kGroupMaxChunk;
+  const int64_t end = begin + kGroupMaxChunk < n ? begin + kGroupMaxChunk : n;
+  const float* srow = scores + (int64_t)row * ld;
+  unsigned long long* trow = table + (int64_t)row * table_stride;
+  const unsigned long long* brow = below != nullptr ? below + (int64_t)row * below_stride : nullptr;
+  for (int64_t x = begin + tid; x < end; x += kGroupMaxThreads) {
+    const float s = srow[x];
+    if (!(fabsf(s) < INFINITY)) continue;               // -inf (masked), +inf, NaN
+    const int64_t p = first_item + x;
+    const int32_t r = ranks[p];
+    if (r < 0 || r >= n_groups) continue;
+    const unsigned long long kv = make_key(s, (unsigned int)p);
+    if (brow != nullptr) {
+      const unsigned long long bound = brow[r];        // (the previous round is complete: a plain read)
+      if (bound == 0ull || kv >= bound) continue;
+    }
+    if (kv <= __atomic_load_n(&trow[r], __ATOMIC_RELAXED)) continue;
+    if (width > 0) {
+      const unsigned long long id = (unsigned long long)(ids != nullptr ? ids[p] : p);
+      bool hit = false;
+      for (int w = 0; w < width; ++w) hit |= (gm_seen[w] == id);
+      if (hit) continue;
+    }
+    atomicMax(&trow[r], kv);
+  }
+}
+
+int scores_group_next(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,
+                      unsigned long long* table, int64_t table_stride, const unsigned long long* below, int64_t below_stride, const int64_t* ids,
+                      const int64_t* invalid, int width, hipStream_t stream) {
+  if (rows <= 0 || n_groups <= 0 || n <= 0) return kOk;
+  if (width > kGroupMaxSeen) { set_error("scores_group_next: width = %d beyond %d seen ids per row", width, kGroupMaxSeen); return kErrUnsupported; }
+  if (first_item + n > 0xFFFFFFFFll) { set_error("scores_group_next: positions beyond 32 bits"); return kErrUnsupported; }
+  if (rows > 65535) { set_error("scores_group_next: more than 65 535 rows"); return kErrUnsupported; }
+  const unsigned int blocks = (unsigned int)((n + kGroupMaxChunk - 1) / kGroupMaxChunk);
+  hipLaunchKernelGGL(group_next_kernel, dim3(blocks, rows), dim3(kGroupMaxThreads), sizeof(unsigned long long) * (size_t)width, stream, scores, ld, n,
+                     first_item, ranks, n_groups, table, table_stride, below, below_stride, ids, invalid, width);
+  return launched();
 }
 
 int scores_group_max(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,

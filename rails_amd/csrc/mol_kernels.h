@@ -190,8 +190,11 @@ int rerank_topk_filtered(const float* scores, int64_t ld, int rows, int n_cand, 
 
 // ---- collapsing by item group (collapse.hip) ----
 int topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int rows, int depth, const int32_t* ranks, int64_t n_items,
-                  const int64_t* ids, const int64_t* invalid, int width, int k, float* out_scores, int64_t* out_pos, int64_t* out_ids,
-                  int32_t* out_counts, int32_t* out_of_range, hipStream_t stream);
+                  const int64_t* ids, const int64_t* invalid, int width, int k, int max_per_group, float* out_scores, int64_t* out_pos,
+                  int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, hipStream_t stream);      // max_per_group 0: the plain walk
+int scores_group_next(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,
+                      unsigned long long* table, int64_t table_stride, const unsigned long long* below, int64_t below_stride, const int64_t* ids,
+                      const int64_t* invalid, int width, hipStream_t stream);
 int scores_group_max(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,
                      unsigned long long* table, int clear_table, const int64_t* ids, const int64_t* invalid, int width, hipStream_t stream);
 int topk_keys(const unsigned long long* table, int rows, int64_t n_groups, int k, const int64_t* ids, float* out_scores, int64_t* out_pos,

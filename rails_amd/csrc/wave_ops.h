@@ -45,6 +45,30 @@ __device__ __forceinline__ int block_scan_excl(int v, int* totals, int& total) {
   return base + inc - v;
 }
 
+// The max form of the scan: the maximum of v over the threads BEFORE this one in thread order, `lowest` for thread 0 (and wherever every
+// earlier thread holds `lowest`).  The same calling rules and scratch as block_scan_excl.
+template <int NT>
+__device__ __forceinline__ int block_scan_max_excl(int v, int lowest, int* totals) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(inc, o, 64);
+    if (lane >= o && u > inc) inc = u;
+  }
+  if (lane == 63) totals[wave] = inc;
+  const int before = __shfl_up(inc, 1, 64);      // the wave's lanes below this one
+  __syncthreads();
+  int base = lane > 0 ? before : lowest;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) {
+    const int t = totals[w];
+    if (w < wave && t > base) base = t;
+  }
+  __syncthreads();
+  return base;
+}
+
 // Sum over the workgroup, returned to every thread.  All NT threads call; `part` is LDS of NT / 64 ints.  The same sequence as the scan.
 template <int NT>
 __device__ __forceinline__ int block_sum(int v, int* part) {

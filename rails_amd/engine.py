@@ -2201,6 +2201,7 @@ def rerank_topk_filtered(scores: torch.Tensor, k_prime: int, positions: torch.Te
 COLLAPSE_MAX_LIST = 16384      # entries of one ranked list rails_topk_collapse walks
 COLLAPSE_MAX_K = 512           # rails_topk_keys' k
 COLLAPSE_MAX_SEEN = 4096       # rails_scores_group_max's seen ids per row
+COLLAPSE_MAX_PER_GROUP = 32    # results per group on the exact modules: their fallback reads the scores once per unit of it
 
 
 def _seen_arg(invalid_ids: Optional[torch.Tensor], rows: int, device) -> Tuple[Optional[torch.Tensor], int]:
@@ -2213,10 +2214,13 @@ def _seen_arg(invalid_ids: Optional[torch.Tensor], rows: int, device) -> Tuple[O
 
 
 def topk_collapse(scores: torch.Tensor, positions: torch.Tensor, ranks: torch.Tensor, k: int, ids: Optional[torch.Tensor],
-                  invalid_ids: Optional[torch.Tensor], flag: torch.Tensor):
+                  invalid_ids: Optional[torch.Tensor], flag: torch.Tensor, max_per_group: Optional[int] = None):
     """The walk of a collapsed top-k (include/rails_amd.h rails_topk_collapse): scores / positions (rows, D) in key order, ranks the (N,) int32
     dense group ranks -> (scores (rows, k), positions, ids, counts (rows,) int32).  `flag` (int32, zeroed by the caller; device or pinned host
-    memory) is raised when a row's list holds fewer than k distinct eligible groups."""
+    memory) is raised when a row's list holds fewer than k distinct eligible groups.  max_per_group = m (an int >= 1): the walk with a quota
+    (rails_topk_collapse_quota) -- up to m entries of a group are kept, and counts / flag speak of the kept entries; None: the plain walk."""
+    if max_per_group is not None and max_per_group < 1:
+        raise ValueError("max_per_group must be >= 1")
     lib = _lib.load()
     _require_device(scores, "scores")
     if scores.dtype != torch.float32 or scores.stride(1) != 1:
@@ -2236,10 +2240,43 @@ def topk_collapse(scores: torch.Tensor, positions: torch.Tensor, ranks: torch.Te
     out_p = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
     out_i = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
     counts = torch.empty(rows, dtype=torch.int32, device=scores.device)
+    lists = (_ptr(scores), scores.stride(0), _ptr(positions), rows, depth, _ptr(ranks), ranks.numel(), _ptr(ids), _ptr(inv), width, k)
+    outs = (_ptr(out_s), _ptr(out_p), _ptr(out_i), _ptr(counts), _ptr(flag), _stream())
     with _on_device(scores.device):
-        _lib.check(lib.rails_topk_collapse(_ptr(scores), scores.stride(0), _ptr(positions), rows, depth, _ptr(ranks), ranks.numel(), _ptr(ids), _ptr(inv),
-                                           width, k, _ptr(out_s), _ptr(out_p), _ptr(out_i), _ptr(counts), _ptr(flag), _stream()), "rails_topk_collapse")
+        if max_per_group is None:
+            _lib.check(lib.rails_topk_collapse(*lists, *outs), "rails_topk_collapse")
+        else:
+            _lib.check(lib.rails_topk_collapse_quota(*lists, min(int(max_per_group), (1 << 31) - 1), *outs), "rails_topk_collapse_quota")
     return out_s, out_p, out_i, counts
+
+
+def scores_group_next(scores: torch.Tensor, ranks: torch.Tensor, table: torch.Tensor, groups: int, round: int, first_item: int = 0,
+                      ids: Optional[torch.Tensor] = None, invalid_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place on `table` ((rows, m * groups) int64, the m rounds of a row side by side, ZEROED by the caller): round `round` of the per-group
+    best-m of the (rows, n) score matrix whose column x is item first_item + x (include/rails_amd.h rails_scores_group_next).  Round t reads
+    round t - 1, which must be complete (every chunk of the corpus); afterwards slot t * groups + r of a row holds the key of rank r's
+    (t + 1)-th best eligible item, 0 where it has fewer."""
+    lib = _lib.load()
+    _require_device(scores, "scores")
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError("scores must be a (rows, n) float32 matrix with unit column stride")
+    rows, n = scores.shape
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[0] != rows or not table.is_contiguous() or table.device != scores.device:
+        raise ValueError("table must be a contiguous (rows, m * groups) int64 tensor on the scores' device")
+    if groups < 1 or table.shape[1] % groups or not 0 <= round < table.shape[1] // groups:
+        raise ValueError("table must hold whole rounds of `groups` keys per row, `round` one of them")
+    if ranks.dtype != torch.int32 or ranks.dim() != 1 or ranks.device != scores.device or not ranks.is_contiguous() or ranks.numel() < first_item + n:
+        raise ValueError("ranks must be a contiguous int32 tensor of at least first_item + n entries on the scores' device")
+    if ids is not None:
+        ids = ids.to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
+    inv, width = _seen_arg(invalid_ids, rows, scores.device)
+    stride = table.shape[1]
+    here = C.c_void_p(table.data_ptr() + 8 * round * groups)
+    below = C.c_void_p(table.data_ptr() + 8 * (round - 1) * groups if round else 0)
+    with _on_device(scores.device):
+        _lib.check(lib.rails_scores_group_next(_ptr(scores), scores.stride(0), rows, n, int(first_item), _ptr(ranks), groups, here, stride, below, stride,
+                                               _ptr(ids), _ptr(inv), width, _stream()), "rails_scores_group_next")
+    return table
 
 
 def scores_group_max(scores: torch.Tensor, ranks: torch.Tensor, table: torch.Tensor, first_item: int = 0, clear: bool = True,

@@ -281,10 +281,14 @@ def refuse_allowed_tags(module, kwargs, why: str) -> None:
 
 def refuse_collapse_groups(module, kwargs, what: Optional[str] = None) -> None:
     """collapse_groups=True where it is not built -- the item-sharded wrappers, the hand-off calls they use, and the calls
-    that return no ranked ids (all_logits, topk_ids): refused by the class's name, before any launch."""
+    that return no ranked ids (all_logits, topk_ids): refused by the class's name, before any launch.  max_per_group= (the quota of the same
+    section) is refused in the same places, by its own name."""
+    name = type(module).__name__ + ("" if what is None else "." + what)
     if kwargs.get("collapse_groups"):
-        name = type(module).__name__ + ("" if what is None else "." + what)
         raise NotImplementedError(f"{name} takes no collapse_groups: collapsing by item group is built on the single-device modules' forward, "
+                                  "forward_filtered, submit and get_top_k_outputs only")
+    if kwargs.get("max_per_group") is not None:
+        raise NotImplementedError(f"{name} takes no max_per_group: a quota per item group is built on the single-device modules' forward, "
                                   "forward_filtered, submit and get_top_k_outputs only")
 
 
@@ -961,6 +965,7 @@ class _CorpusEdits(_StreamingScores):
     # items the row may return and has not seen) whose key is -1 or differs from the key of every earlier item of that ranking: each group is
     # represented by its best eligible item.  Keys belong to the POSITION and follow edits as tags do (groups_after_append / groups_after_removal).
     # The kernels read the DENSE ranks of the keys (group_ranks), computed once per row and kept.
+    # max_per_group=m on the same calls keeps the first m items of each key in place of the first one (m = 1 IS collapse_groups=True).
     _groups: Optional[torch.Tensor] = None
     _group_rank_cache = None       # (ranks (N,) int32, G) of the current row
     COLLAPSE_DEPTH_FACTOR = 2      # the exact modules' first walk looks at this many times k + width ranked items ...
@@ -1031,14 +1036,25 @@ class _CorpusEdits(_StreamingScores):
     def _check_collapsible(self, what: str) -> None:
         """The refusal point of the item groups: modules whose candidate generation cannot honour them raise here, before anything is touched."""
 
-    def _take_collapse(self, kwargs: dict) -> bool:
-        """collapse_groups= of a call, taken OUT of its kwargs and checked against this module before any launch."""
-        if not kwargs.pop("collapse_groups", False):
-            return False
-        self._check_collapsible("collapse_groups")
+    def _take_collapse(self, kwargs: dict) -> int:
+        """collapse_groups= and max_per_group= of a call, taken OUT of its kwargs and checked against this module before any launch -> m, the
+        results a group may have (collapse_groups=True: 1); 0: the call is not collapsed."""
+        collapse = kwargs.pop("collapse_groups", False)
+        m = kwargs.pop("max_per_group", None)
+        if m is None:
+            if not collapse:
+                return 0
+            m, what = 1, "collapse_groups"
+        else:
+            what = "max_per_group"
+            if isinstance(m, bool) or not isinstance(m, int) or m < 1:
+                raise ValueError(f"{type(self).__name__}: max_per_group must be a Python int >= 1, got {m!r}")
+            if collapse and m != 1:
+                raise ValueError(f"{type(self).__name__}: collapse_groups=True means max_per_group=1, got max_per_group={m} with it (pass one of the two)")
+        self._check_collapsible(what)
         if self._groups is None:
-            raise ValueError(f"{type(self).__name__}: collapse_groups=True on a module without groups (set_item_groups first)")
-        return True
+            raise ValueError(f"{type(self).__name__}: {what}={'True' if what == 'collapse_groups' else m} on a module without groups (set_item_groups first)")
+        return m
 
     def collapse_stats(self) -> dict:
         """Which path answered the collapsed calls so far: calls, walk_redos (depth doublings), fallbacks (exact group-maxima passes)."""
@@ -1779,8 +1795,8 @@ class MoLBruteForceTopK(MoLTopKModule):
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """item_mask= (an engine.ItemMask, or a bool tensor (N,) / (B, N) packed for this call): only items inside the mask are returned.
         collapse_groups=True: at most one item per group of set_item_groups."""
-        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
-            return _collapsed_exact(self, query_embeddings, k, None, kwargs)
+        if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
+            return _collapsed_exact(self, query_embeddings, k, None, kwargs, m)
         eng = self._bind()
         mask = self._take_item_mask(kwargs, query_embeddings.size(0), k)
         if mask is not None:
@@ -1800,8 +1816,8 @@ class MoLBruteForceTopK(MoLTopKModule):
         or None when the sizes / the precision route are outside the fused path (the caller then composes forward +
         filter_seen_ids: same bits).  collapse_groups=True never returns None: the seen ids go to the collapse walk (a filter behind the
         collapse would drop a group whose best item is seen instead of promoting its next member)."""
-        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
-            scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs)
+        if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
+            scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs, m)
             return ids, scores
         eng = self._bind()
         B, N = query_embeddings.size(0), self._index.n_items
@@ -2640,28 +2656,53 @@ def _collapse_count(tk, key: str) -> None:
     stats[key] += 1
 
 
-def _too_few_groups(k: int, counts: torch.Tensor) -> RuntimeError:
+def _asks_collapse(kwargs: dict) -> bool:
+    """Does the call name one of the two arguments of section 3.16?  (A call with neither runs none of its code.)"""
+    return "collapse_groups" in kwargs or "max_per_group" in kwargs
+
+
+def _too_few_groups(k: int, counts: torch.Tensor, m: int = 1) -> RuntimeError:
+    if m > 1:
+        return RuntimeError(f"selected index k out of range (k={k}, n={int(counts.min())}: the eligible items within max_per_group={m} of the row "
+                            "with the fewest)")
     return RuntimeError(f"selected index k out of range (k={k}, n={int(counts.min())}: the distinct eligible groups of the row with the fewest)")
 
 
-def _collapse_walk(tk, scores: torch.Tensor, positions: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor]) -> CollapseWalk:
-    """The one walk launch (rails_topk_collapse) behind a ranked list of POSITIONS in key order; the seen-id filter runs inside it."""
+def _collapse_walk(tk, scores: torch.Tensor, positions: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], m: int = 1) -> CollapseWalk:
+    """The one walk launch behind a ranked list of POSITIONS in key order; the seen-id filter runs inside it.  m = 1: rails_topk_collapse;
+    m > 1 (at most k: the caller's m_eff): rails_topk_collapse_quota."""
     ranks, _ = tk._dense_group_ranks()
     word = _pinned_word(tk)
     word.zero_()      # (a word on the free list has been read: nothing in flight writes it)
-    return CollapseWalk(*E.topk_collapse(scores, positions, ranks, k, tk._ids_flat, invalid_ids, word), word)
+    return CollapseWalk(*E.topk_collapse(scores, positions, ranks, k, tk._ids_flat, invalid_ids, word, None if m == 1 else m), word)
 
 
-def _collapsed_exact(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+def _collapsed_exact(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict,
+                     m: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """The collapsed call of an exact module -> (scores, ids).  The module's ordinary ranked top-D BY POSITION, through the
     arm it would take anyway with the call's mask / hidden set / tags -- the seen ids are NOT handed to it: a seen item must not represent its
     group, so they go to the walk --, then the walk; a walk that found fewer than k groups doubles D up to COLLAPSE_MAX_DEPTH, and beyond that
     the exact fallback answers: the group maxima of the materialised scores (_collapse_fallback).  Correctness never depends on the depths:
-    the first k first-occurrences of the top-D are those of the whole ranking whenever the top-D holds k of them."""
+    the first k first-occurrences of the top-D are those of the whole ranking whenever the top-D holds k of them.
+    m > 1 (max_per_group=): whether an item is kept depends on the items before it alone, so the argument is the same one; the walk keeps the
+    first m_eff = min(m, k) members of a group (beyond k a quota excludes nothing among the first k), the fallback the best m_eff.
+    The limits are checked before any launch of the call itself; the size check of the fallback's table needs G, so on a key row whose dense
+    ranks are not cached yet it computes them first (group_ranks: torch integer ops, once per set_item_groups or edit) -- work every
+    collapsed call on that row needs anyway."""
     width = 0 if invalid_ids is None else invalid_ids.shape[1]
     if k > E.COLLAPSE_MAX_K or width > E.COLLAPSE_MAX_SEEN:      # (the fallback's sizes: it must be there for every call the walks may fail on)
-        raise NotImplementedError(f"{type(tk).__name__}: collapse_groups=True takes k <= {E.COLLAPSE_MAX_K} and up to {E.COLLAPSE_MAX_SEEN} seen ids per "
+        how = "collapse_groups=True" if m == 1 else f"max_per_group={m}"
+        raise NotImplementedError(f"{type(tk).__name__}: {how} takes k <= {E.COLLAPSE_MAX_K} and up to {E.COLLAPSE_MAX_SEEN} seen ids per "
                                   f"row (what its exact group-maxima pass selects and filters), got k = {k}, width = {width}")
+    m = min(m, max(k, 1))
+    if m > 1:
+        if m > E.COLLAPSE_MAX_PER_GROUP:
+            raise NotImplementedError(f"{type(tk).__name__}: max_per_group takes min(max_per_group, k) <= {E.COLLAPSE_MAX_PER_GROUP} on the exact modules "
+                                      f"(their fallback reads the scores once per result of a group), got {m}")
+        row_bytes = m * tk._dense_group_ranks()[1] * 8
+        if row_bytes > int(getattr(tk, "MAX_LOGIT_BYTES", 4 << 30)):
+            raise NotImplementedError(f"{type(tk).__name__}: max_per_group={m} needs {row_bytes} bytes of group keys per query for its exact fallback, "
+                                      f"beyond MAX_LOGIT_BYTES = {int(getattr(tk, 'MAX_LOGIT_BYTES', 4 << 30))}")
     _collapse_count(tk, "calls")
     B, n = query_embeddings.size(0), tk.num_items
     # the call's mask -- item_mask= (a bool tensor is packed here: its one sync), allowed_tags=, the hidden set -- is resolved ONCE; every
@@ -2676,7 +2717,7 @@ def _collapsed_exact(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Op
     while depth >= k:
         with tk._positions_as_ids():
             scores, positions = tk.forward(query_embeddings, depth, **dict(kwargs))
-        walk = _collapse_walk(tk, scores, positions, k, invalid_ids)
+        walk = _collapse_walk(tk, scores, positions, k, invalid_ids, m)
         if walk.clear(tk):
             return walk.scores.to(query_embeddings.dtype), walk.ids
         deeper = min(2 * depth, bound, tk.COLLAPSE_MAX_DEPTH, E.COLLAPSE_MAX_LIST)
@@ -2685,64 +2726,84 @@ def _collapsed_exact(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Op
         depth = deeper
         _collapse_count(tk, "walk_redos")
     del kwargs["_resolved_mask"]
-    return _collapse_fallback(tk, query_embeddings, k, invalid_ids, mask, kwargs)
+    return _collapse_fallback(tk, query_embeddings, k, invalid_ids, mask, kwargs, m)
 
 
 def _collapse_fallback(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], mask: Optional[E.ItemMask],
-                       kw: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+                       kw: dict, m: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """The exact fallback of a collapsed call: dense scores of the module's own precision, the call's mask written into them, their per-group
     maxima as 64-bit keys (rails_scores_group_max, per corpus chunk under the logit policy, the seen-id filter inside) and the top-k of the
     (B, G) key table (rails_topk_keys) -- a slice of the batch at a time where that table would exceed the same policy.  A row with fewer than k
     non-empty groups is the RuntimeError of a call for more than there is.  mask: the call's resolved mask; kw: its other keyword arguments.
-    (k and the seen-id width were checked against the pass's limits by _collapsed_exact, before any launch.)"""
+    (k, m and the seen-id width were checked against the pass's limits by _collapsed_exact, before any launch.)
+    m > 1: the table is (B, m * G), round t of a row beside round t - 1 -- every group's (t + 1)-th best eligible item, by
+    rails_scores_group_next bounded by the finished round before it; rounds outermost, corpus chunks inside.  A corpus of one chunk is scored
+    once and read m times, a chunked one is scored again for every round (its pieces share a buffer).  Every key of the table is among its
+    group's best m and every item the quota keeps is in it, so its top-k is the answer."""
     _collapse_count(tk, "fallbacks")
     B = query_embeddings.size(0)
     ranks, groups = tk._dense_group_ranks()
-    rows = max(1, min(B, int(getattr(tk, "MAX_LOGIT_BYTES", 4 << 30)) // (groups * 8)))
+    rows = max(1, min(B, int(getattr(tk, "MAX_LOGIT_BYTES", 4 << 30)) // (m * groups * 8)))
     parts = []
     for b0 in range(0, B, rows):
         b1 = min(B, b0 + rows)
         part_kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kw.items()}
         part_mask = mask if mask is None or mask.shared else mask.rows_slice(b0, b1)
-        table = torch.empty((b1 - b0, groups), dtype=torch.int64, device=query_embeddings.device)
-        first = True
-        for lo, logits in tk._own_score_chunks(query_embeddings[b0:b1], part_mask, **part_kw):
-            E.scores_group_max(logits, ranks, table, first_item=lo, clear=first, ids=tk._ids_flat, invalid_ids=None if invalid_ids is None else invalid_ids[b0:b1])
-            first = False
+        part_seen = None if invalid_ids is None else invalid_ids[b0:b1]
+        if m == 1:
+            table = torch.empty((b1 - b0, groups), dtype=torch.int64, device=query_embeddings.device)
+            first = True
+            for lo, logits in tk._own_score_chunks(query_embeddings[b0:b1], part_mask, **part_kw):
+                E.scores_group_max(logits, ranks, table, first_item=lo, clear=first, ids=tk._ids_flat, invalid_ids=part_seen)
+                first = False
+        else:
+            table = torch.zeros((b1 - b0, m * groups), dtype=torch.int64, device=query_embeddings.device)
+            only = None      # the one chunk of an unchunked corpus, kept for the later rounds
+            for t in range(m):
+                pieces = [only] if only is not None else tk._own_score_chunks(query_embeddings[b0:b1], part_mask, **part_kw)
+                n_pieces = 0
+                for lo, logits in pieces:
+                    E.scores_group_next(logits, ranks, table, groups, t, first_item=lo, ids=tk._ids_flat, invalid_ids=part_seen)
+                    n_pieces += 1
+                if t == 0 and n_pieces == 1:
+                    only = (lo, logits)
+            del only
         parts.append(E.topk_keys(table, k, tk._ids_flat))
     scores, ids, counts = (torch.cat([p[i] for p in parts], 0) for i in (0, 2, 3))
     if int(counts.min()) < k:      # (the one read-back of the fallback)
-        raise _too_few_groups(k, counts)
+        raise _too_few_groups(k, counts, m)
     return scores.to(query_embeddings.dtype), ids
 
 
-def _collapsed_candidates(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], n_ranked: int, kwargs: dict):
+def _collapsed_candidates(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], n_ranked: int, kwargs: dict, m: int = 1):
     """The collapsed call of an approximate module -> a handle for _collapsed_candidates_result.  The walk runs over the module's own ranked
     candidate list -- forward's, by position, in its sorted form, all n_ranked of it -- in place of the final cut to k.  No doubling and no
     fallback: the depth is the list's, and too few distinct groups among the candidates is the RuntimeError.  A list longer than the walk takes
     is refused here, before any launch."""
     n_list = n_ranked if n_ranked else tk._union_width()
     if n_list > E.COLLAPSE_MAX_LIST:
-        raise NotImplementedError(f"{type(tk).__name__}: collapse_groups=True walks ranked lists of up to {E.COLLAPSE_MAX_LIST} candidates per query, this "
+        how = "collapse_groups=True" if m == 1 else f"max_per_group={m}"
+        raise NotImplementedError(f"{type(tk).__name__}: {how} walks ranked lists of up to {E.COLLAPSE_MAX_LIST} candidates per query, this "
                                   f"module ranks {n_list}")
+    m = min(m, max(k, 1))      # (no limit on m here: these modules have no fallback whose cost grows with it)
     _collapse_count(tk, "calls")
     with tk._positions_as_ids(), getattr(tk, "inline_calls", contextlib.nullcontext)():
         inner = MoLAvgTopK.submit(tk, query_embeddings, n_ranked, **dict(kwargs)) if n_ranked else None
         ranked = inner[1:3] if inner is not None else tk.forward(query_embeddings, k, **dict(kwargs))
-    return (tk, inner, _collapse_walk(tk, ranked[0], ranked[1], k, invalid_ids), k, invalid_ids, query_embeddings.dtype)
+    return (tk, inner, _collapse_walk(tk, ranked[0], ranked[1], k, invalid_ids, m), k, invalid_ids, query_embeddings.dtype, m)
 
 
 def _collapsed_candidates_result(handle) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (scores, ids); owns the redo of the candidate scan (MoLAvgTopK.result's) and the look at the walk's verdict."""
-    tk, inner, walk, k, invalid_ids, dtype = handle
+    tk, inner, walk, k, invalid_ids, dtype, m = handle
     if inner is not None:
         with tk._positions_as_ids():
             scores, positions = MoLAvgTopK.result(tk, inner)
         if scores is not inner[1]:      # the scan was redone on the materialising path: walk its list instead
             walk.clear(tk)
-            walk = _collapse_walk(tk, scores, positions, k, invalid_ids)
+            walk = _collapse_walk(tk, scores, positions, k, invalid_ids, m)
     if not walk.clear(tk):
-        raise _too_few_groups(k, walk.counts)
+        raise _too_few_groups(k, walk.counts, m)
     return walk.scores.to(dtype), walk.ids
 
 
@@ -2940,8 +3001,8 @@ class MoLAvgTopK(MoLTopKModule):
     # joined to the caller's stream only by result() -- read them through result(), never through the handle, and do not drop a handle
     # without calling result() (ShardedTopK.submit, which needs the scores earlier, waits on the handle's event explicitly).
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
-        if "collapse_groups" in kwargs and self._take_collapse(kwargs):      # (the walk over the reranked candidates; result owns the redo)
-            return ("collapsed", self._collapse_enqueue(query_embeddings, k, None, kwargs))
+        if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):      # (the walk over the reranked candidates; result owns the redo)
+            return ("collapsed", self._collapse_enqueue(query_embeddings, k, None, kwargs, m))
         refuse_item_mask(self, kwargs)
         if kwargs.get("allowed_tags") is not None:      # allowed_tags=, resolved and checked before any launch; the handle and a
             kwargs["allowed_tags"] = self._take_allowed_tags(kwargs, query_embeddings.size(0), (self._avg_top_k,))      # redo carry the resolved filter
@@ -2973,13 +3034,13 @@ class MoLAvgTopK(MoLTopKModule):
             return ("final", scores, ids)
         return ("speculative", scores, ids, host, done, query_embeddings, k, kwargs, side)
 
-    def _collapse_enqueue(self, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict):
+    def _collapse_enqueue(self, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict, m: int = 1):
         """The collapsed call over this module's own ranked list: MoLAvgTopK's avg_top_k reranked candidates; a subclass with its own forward
         (MoLCombTopK) has that forward rank its union."""
         own = type(self).forward is MoLAvgTopK.forward
         if own and k > self._avg_top_k:
             raise ValueError(f"avg_top_k ({self._avg_top_k}) must be larger than k ({k})")
-        return _collapsed_candidates(self, query_embeddings, k, invalid_ids, self._avg_top_k if own else 0, kwargs)
+        return _collapsed_candidates(self, query_embeddings, k, invalid_ids, self._avg_top_k if own else 0, kwargs, m)
 
     def result(self, handle) -> Tuple[torch.Tensor, torch.Tensor]:
         if handle[0] == "collapsed":
@@ -3015,8 +3076,8 @@ class MoLAvgTopK(MoLTopKModule):
         at the scan's verdict word (it then runs while the host is on its way back) -> (top_k_ids, top_k_scores); None where this
         does not apply (subclasses with their own forward, k_prime beyond K': the caller composes the two calls).  collapse_groups=True never
         returns None: the seen ids go to the collapse walk."""
-        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
-            scores, ids = _collapsed_candidates_result(self._collapse_enqueue(query_embeddings, k, invalid_ids, kwargs))
+        if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
+            scores, ids = _collapsed_candidates_result(self._collapse_enqueue(query_embeddings, k, invalid_ids, kwargs, m))
             return ids, scores
         refuse_item_mask(self, kwargs)
         if type(self).forward is not MoLAvgTopK.forward or k_prime > self._avg_top_k or k_prime < k:
@@ -3079,8 +3140,8 @@ class _ComponentCandidates:
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """All the union's candidates ranked, whatever `k` is, as the reference does.  collapse_groups=True: the first k
         of that ranking with at most one item per group of set_item_groups -- k columns."""
-        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
-            return _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, None, 0, kwargs))
+        if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
+            return _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, None, 0, kwargs, m))
         scores, ids = self._ranked(query_embeddings, sorted, None, kwargs)
         return scores.to(query_embeddings.dtype), ids
 
@@ -3088,8 +3149,8 @@ class _ComponentCandidates:
         """CandidateIndex.get_top_k_outputs' body (the module returns all its candidates whatever k_prime is, the filter keeps the first k unseen):
         -> (top_k_ids, top_k_scores), or None where the filter does not fit the selection launch (_filter_inside).  collapse_groups=True never
         returns None: the seen ids go to the collapse walk, over the sorted form of the ranking."""
-        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
-            scores, ids = _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, invalid_ids, 0, kwargs))
+        if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
+            scores, ids = _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, invalid_ids, 0, kwargs, m))
             return ids, scores
         seen = self._filter_inside(self._union_width(), invalid_ids, k)
         if seen is None:
@@ -3427,8 +3488,8 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
         """item_mask= (an engine.ItemMask or a bool tensor (N,) / (B, N)): only items inside the mask are returned -- the
         dense strategy: the score matrix of the items outside it is set to -inf before the selection.  collapse_groups=True (section 3.16): at
         most one item per group of set_item_groups."""
-        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
-            return _collapsed_exact(self, query_embeddings, k, None, kwargs)
+        if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
+            return _collapsed_exact(self, query_embeddings, k, None, kwargs, m)
         mask = self._take_item_mask(kwargs, query_embeddings.size(0), k)
         logits = self._index.score(query_embeddings)
         if mask is not None:
@@ -3439,8 +3500,8 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
         """CandidateIndex.get_top_k_outputs' body under collapse_groups=True -> (top_k_ids, top_k_scores): the seen ids go to the collapse walk.
         None for every other call (the caller composes forward + filter_seen_ids, as it always has)."""
-        if "collapse_groups" in kwargs and self._take_collapse(kwargs):
-            scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs)
+        if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
+            scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs, m)
             return ids, scores
         return None
 

@@ -7,6 +7,10 @@ events behind a device synchronise; per cell --calls timings after --warmup call
 share the clocks; the median is reported in microseconds with the cell's walk_redos and fallbacks (collapse_stats) over the timed calls.
 Writes profiles/collapse.json (or --out) and prints it as one JSON line.  Reads nothing outside the repository.
   python tools/collapse_bench.py [--calls 20] [--warmup 30] [--items 695762] [--out PATH]
+--max-per-group: the quota leg instead.  Per module and layout with groups, the cells collapse_groups=True (the yardstick of the same run) and
+max_per_group = 1, 2, 4, 8 on ONE module holding the layout's key row; same geometry, seen ids and protocol, all cells of a module interleaved
+call by call; per cell the median, its ratio to the collapse_groups=True cell of its layout, and the walk_redos / fallbacks of its timed
+calls.  Writes profiles/group_quota.json (or --out).
 """
 import argparse
 import json
@@ -48,13 +52,33 @@ def layouts(n, g):
     }
 
 
+QUOTAS = (1, 2, 4, 8)
+
+
+def quota_cells(make, mol, X, ids, keys, dev):
+    """label -> (module, call kwargs): per layout with groups one module, five cells on it"""
+    cells = {}
+    for label, row in keys.items():
+        if row is None:
+            continue
+        tk = make(mol, X, ids)
+        tk.set_item_groups(row.to(dev))
+        cells[f"{label} | collapse_groups=True"] = (tk, {"collapse_groups": True})
+        for m in QUOTAS:
+            cells[f"{label} | max_per_group={m}"] = (tk, {"max_per_group": m})
+    return cells
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--items", type=int, default=695_762)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "collapse.json"))
+    ap.add_argument("--max-per-group", action="store_true", help="the quota leg: max_per_group = 1, 2, 4, 8 against collapse_groups=True")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "group_quota.json" if args.max_per_group else "collapse.json")
     assert torch.cuda.is_available(), "collapse_bench needs a GPU"
     dev = torch.device("cuda", 0)
     cfg = O.CONFIGS["amzn-books"]
@@ -74,11 +98,15 @@ def main():
         for name, make in MODULES.items():
             cells = {}
             for label, row in keys.items():      # one module per cell: each holds its own key row
+                if args.max_per_group and row is not None:
+                    continue
                 tk = make(mol, X, ids)
                 if row is not None:
                     tk.set_item_groups(row.to(dev))
                 cells[label] = (tk, {} if row is None else {"collapse_groups": True})
             _, top_ids = cells["no groups"][0](q, k=kp)
+            if args.max_per_group:
+                cells.update(quota_cells(make, mol, X, ids, keys, dev))
             inv = torch.zeros((B, width), dtype=torch.int64, device=dev)      # bench.py's seen ids
             for b in range(B):
                 sel = torch.randperm(top_ids.shape[1], generator=g)[: width // 2].to(dev)
@@ -88,23 +116,32 @@ def main():
                 for tk, kw in cells.values():
                     call(tk, kw)
             torch.cuda.synchronize()
-            before = {label: tk.collapse_stats() for label, (tk, _) in cells.items()}
             us = {label: [] for label in cells}
+            took = {label: {"calls": 0, "walk_redos": 0, "fallbacks": 0} for label in cells}      # (the quota leg's cells share modules: counted call by call)
             for _ in range(args.calls):
                 for label, (tk, kw) in cells.items():
+                    before = tk.collapse_stats()
                     us[label].append(timed(lambda: call(tk, kw), 1))
+                    after = tk.collapse_stats()
+                    for key in took[label]:
+                        took[label][key] += after[key] - before[key]
             rows = {}
             plain = statistics.median(us["no groups"])
-            for label, (tk, _) in cells.items():
-                after = tk.collapse_stats()
+            for label in cells:
                 med = statistics.median(us[label])
-                rows[label] = {"us": us[label], "us_median": med, "over_plain": med / plain,
-                               **{key: after[key] - before[label][key] for key in ("calls", "walk_redos", "fallbacks")}}
+                rows[label] = {"us": us[label], "us_median": med, "over_plain": med / plain, **took[label]}
+                if args.max_per_group and " | " in label:
+                    rows[label]["over_collapse_groups"] = med / statistics.median(us[label.split(" | ")[0] + " | collapse_groups=True"])
             result["modules"][name] = rows
             del cells
             torch.cuda.empty_cache()
     result["not_measured"] = ["kernel-level times of the walk and of the group-maxima pass (only whole calls)", "other geometries, batch sizes, k or seen widths",
                               "the cost of set_item_groups (one torch.unique over the key row)", "COLLAPSE_DEPTH_FACTOR / COLLAPSE_MAX_DEPTH other than the defaults"]
+    if args.max_per_group:
+        result["not_measured"] = ["the m-round exact fallback (rails_scores_group_next: one pass over the scores per round) and the depth doubling under a quota, "
+                                  "unless a cell's fallbacks / walk_redos say it took them", "max_per_group beyond 8",
+                                  "kernel-level times of the walk with a quota (only whole calls)", "other geometries, batch sizes, k or seen widths",
+                                  "COLLAPSE_DEPTH_FACTOR / COLLAPSE_MAX_DEPTH other than the defaults"]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
