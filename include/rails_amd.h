@@ -56,6 +56,7 @@ extern "C" {
  * and the rank entries rails_scores_rank_keys / rails_scores_rank / rails_item_mask_clear_rows
  * and the softmax entries rails_scores_lse[_workspace_bytes] / rails_scores_log_prob / rails_scores_gumbel
  * and the range-search entries rails_scores_range_workspace_bytes / rails_scores_range_count / _write / _sort / _decode
+ * and the query-fusion entries rails_scores_fuse_rows / rails_topk_fuse_lists
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -486,6 +487,37 @@ int rails_scores_range_sort(uint64_t* keys, const int64_t* lims, int32_t rows, i
 /* scores_out[i] = the score of keys[i] (its bits), ids_out[i] = ids[position] (the position itself when ids is NULL; -1 for a position
  * outside [0, n)), i < total.  total = 0: nothing to do. */
 int rails_scores_range_decode(const uint64_t* keys, int64_t total, const int64_t* ids, int64_t n, float* scores_out, int64_t* ids_out, void* stream);
+
+/* ---- query fusion: several sub-query rows per user become one result row (added under ABI 15: new entries only) ---------------------------
+ * lims: n_out + 1 int64 values ON THE DEVICE; fused row u owns the input rows [lims[u], lims[u + 1]).  The caller has checked lims[0] = 0,
+ * lims[n_out] = rows_in and that it increases strictly; the kernels clamp every segment to [0, rows_in) all the same and read nothing outside
+ * it. */
+#define RAILS_FUSE_MAX 0
+#define RAILS_FUSE_SUM 1
+/* out[u * ld_out + x] = the fusion of scores[r * ld + x] over the rows r of segment u, ascending, for x < n:
+ *   RAILS_FUSE_MAX   the element whose bit pattern is largest under the order of the selection key (sign-magnitude to unsigned: -0 < +0,
+ *                    NaNs by their payload above +inf / below -inf): rails_topk's order, no float compare;  weights must be NULL
+ *   RAILS_FUSE_SUM   weights == NULL: acc = s[r0], then acc = fl32(acc + s[r]);
+ *                    weights (rows_in fp32): acc = fl32(w[r0] * s[r0]), then acc = fl32(acc + fl32(w[r] * s[r])) -- two roundings per term,
+ *                    never an fma, so a float32 loop on the host reproduces it bit for bit
+ * A segment of one row without weights is copied.  Every input is read once, every output written once; no atomics, no LDS, no scratch at any
+ * segment size.  Rows of any 4-byte alignment: 16-byte loads and stores when scores and out are 16-byte aligned and ld and ld_out multiples of
+ * 4, one column per thread otherwise -- the same bits.  run_if: the launch predicate (NULL: run).  0 <= rows_in, n_out <= 2^24, 1 <= n < 2^31,
+ * ld >= n, ld_out >= n; n_out = 0: nothing to do.  RAILS_EINVAL for a NULL pointer, a size outside these, an unknown mode, weights with
+ * RAILS_FUSE_MAX, or an out that overlaps scores. */
+int rails_scores_fuse_rows(const float* scores, int64_t ld, int32_t rows_in, int64_t n, const int64_t* lims, int32_t n_out, int32_t mode, const float* weights,
+                           float* out, int64_t ld_out, const int32_t* run_if, void* stream);
+/* The merge of RAILS_FUSE_MAX on sorted lists: scores (rows_in, depth) fp32 with row stride ld and positions (rows_in, depth) int64, contiguous
+ * -- row r's top-depth list under the selection key.  Per fused row, one workgroup: the entries with a position in [0, n_items) and a score
+ * other than -inf (the padding of a short list) are sorted by (position, score), the best entry of every position becomes its selection key,
+ * a second sort ranks them, and the first k whose id -- ids[position], the position itself when ids is NULL -- is not among
+ * invalid_ids[u * width .. + width) are written to out_ids / out_scores (n_out * k each), the rest of a short row as (-1, -inf).
+ * max_segment: at least the largest lims[u + 1] - lims[u]; it sizes the launch's LDS, and a longer segment is cut to it.  Exact for the top k
+ * of the fused matrix when depth >= min(k + width, items a row may return) and no two items share an id.
+ * RAILS_ENOTSUP (nothing launched) for max_segment * depth > 16 384, k > 512, width > 4 096 or n_items > 2^32 - 1. */
+int rails_topk_fuse_lists(const float* scores, int64_t ld, const int64_t* positions, int32_t rows_in, int32_t depth, const int64_t* lims, int32_t n_out,
+                          int32_t max_segment, int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, int64_t* out_ids,
+                          float* out_scores, void* stream);
 
 /* Per-row candidates: out[bq * n_cand + x] = <queries[bq], items[bq / r][x]> for queries (n_queries, dim) and items
  * (n_queries / r, n_cand, dim) -- the two bmm branches of DotProductSimilarity.forward

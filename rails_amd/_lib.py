@@ -19,6 +19,8 @@ RAILS_EINVAL = -22
 RAILS_ENOTSUP = -95
 RAILS_ENOMEM = -12
 RAILS_ELAUNCH = -5
+RAILS_FUSE_MAX = 0
+RAILS_FUSE_SUM = 1
 RAILS_GEGLU = 0
 RAILS_SWIGLU = 1
 RAILS_MAX_UID_TABLES = 4
@@ -249,6 +251,10 @@ PROTOTYPES = {
                                            C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p]),
     "rails_scores_range_sort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "rails_scores_range_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rails_scores_fuse_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p]),
+    "rails_topk_fuse_lists": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rails_dot_rowwise": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],

@@ -977,6 +977,46 @@ int rails_scores_range_decode(const uint64_t* keys, int64_t total, const int64_t
   return fail(scores_range_decode(keys, total, ids, n, scores_out, ids_out, (hipStream_t)stream), "scores_range_decode");
 }
 
+// ---- query fusion (fuse.hip) ----
+int rails_scores_fuse_rows(const float* scores, int64_t ld, int32_t rows_in, int64_t n, const int64_t* lims, int32_t n_out, int32_t mode, const float* weights,
+                           float* out, int64_t ld_out, const int32_t* run_if, void* stream) {
+  g_err[0] = '\0';
+  if (rows_in < 0 || rows_in > (1 << 24) || n_out < 0 || n_out > (1 << 24) || n < 1 || n >= (1LL << 31) || ld < n || ld_out < n) {
+    set_error("scores_fuse_rows: bad size (rows_in = %d, n_out = %d, n = %lld, ld = %lld, ld_out = %lld)", rows_in, n_out, (long long)n, (long long)ld,
+              (long long)ld_out);
+    return RAILS_EINVAL;
+  }
+  if (mode != RAILS_FUSE_MAX && mode != RAILS_FUSE_SUM) { set_error("scores_fuse_rows: mode = %d is neither RAILS_FUSE_MAX nor RAILS_FUSE_SUM", mode); return RAILS_EINVAL; }
+  if (weights && mode == RAILS_FUSE_MAX) { set_error("scores_fuse_rows: weights go with RAILS_FUSE_SUM"); return RAILS_EINVAL; }
+  if (n_out == 0) return RAILS_OK;
+  if (!lims || !out || (rows_in > 0 && !scores)) { set_error("scores_fuse_rows: NULL pointer"); return RAILS_EINVAL; }
+  if (rows_in > 0) {      // the elements either matrix spans, first to last
+    const float* s_end = scores + ((int64_t)(rows_in - 1) * ld + n);
+    const float* o_end = out + ((int64_t)(n_out - 1) * ld_out + n);
+    if (scores < o_end && out < s_end) { set_error("scores_fuse_rows: out overlaps scores"); return RAILS_EINVAL; }
+  }
+  return fail(scores_fuse_rows(scores, ld, rows_in, n, lims, n_out, mode, weights, out, ld_out, run_if, (hipStream_t)stream), "scores_fuse_rows");
+}
+
+int rails_topk_fuse_lists(const float* scores, int64_t ld, const int64_t* positions, int32_t rows_in, int32_t depth, const int64_t* lims, int32_t n_out,
+                          int32_t max_segment, int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, int64_t* out_ids,
+                          float* out_scores, void* stream) {
+  g_err[0] = '\0';
+  if (rows_in < 0 || depth < 1 || n_out < 0 || max_segment < 1 || n_items < 0 || width < 0 || k < 0 || ld < depth) {
+    set_error("topk_fuse_lists: bad size (rows_in = %d, depth = %d, n_out = %d, max_segment = %d, n_items = %lld, width = %d, k = %d, ld = %lld)", rows_in, depth,
+              n_out, max_segment, (long long)n_items, width, k, (long long)ld);
+    return RAILS_EINVAL;
+  }
+  if (n_out == 0 || k == 0) return RAILS_OK;
+  if (!lims || !out_ids || !out_scores || (rows_in > 0 && (!scores || !positions)) || (width > 0 && !invalid_ids)) {
+    set_error("topk_fuse_lists: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  const int r = topk_fuse_lists(scores, ld, positions, rows_in, depth, lims, n_out, max_segment, n_items, ids, invalid_ids, width, k, out_ids, out_scores,
+                                (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "topk_fuse_lists");
+}
+
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s) || n_items < 0) return 0;
   return (size_t)n_items * (size_t)s->dot_product_dimension * 2;

@@ -286,6 +286,15 @@ int scores_range_write(const float* scores, int64_t ld, int rows, int64_t n, con
 int scores_range_sort(void* keys, const int64_t* lims, int rows, int max_count, hipStream_t stream);
 int scores_range_decode(const void* keys, int64_t total, const int64_t* ids, int64_t n, float* scores_out, int64_t* ids_out, hipStream_t stream);
 
+// ---- query fusion (fuse.hip): fused row u owns the input rows [lims[u], lims[u + 1]); mode RAILS_FUSE_MAX / RAILS_FUSE_SUM ----
+constexpr int kFuseListMaxEntries = 16384;      // (score, position) entries of one fused row topk_fuse_lists merges: what lds_sort_desc sorts
+constexpr int kFuseListMaxK = 512;
+constexpr int kFuseListMaxSeen = 4096;          // seen ids per fused row
+int scores_fuse_rows(const float* scores, int64_t ld, int64_t rows_in, int64_t n, const int64_t* lims, int64_t n_out, int mode, const float* weights, float* out,
+                     int64_t ld_out, const int32_t* run_if, hipStream_t stream);
+int topk_fuse_lists(const float* scores, int64_t ld, const int64_t* positions, int64_t rows_in, int depth, const int64_t* lims, int n_out, int max_segment,
+                    int64_t n_items, const int64_t* ids, const int64_t* invalid, int width, int k, int64_t* out_ids, float* out_scores, hipStream_t stream);
+
 int dot_rowwise(const float* q, const float* items, int64_t Bq, int X, int D, int r, float* out, hipStream_t stream);
 
 size_t topk_workspace_bytes(int rows, int64_t n, int k);

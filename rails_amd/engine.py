@@ -1536,6 +1536,16 @@ class ItemMask:
             part._positions = self._positions[b0:b1, : part.kept_max].contiguous()
         return part
 
+    def rows_take(self, rows: torch.Tensor) -> "ItemMask":
+        """The per-row mask whose row i is this mask's row rows[i] ((M,) int64 on the CPU) -- a fused row's mask repeated over its sub-query
+        rows; a shared mask is returned as it is.  No sync."""
+        if self.shared:
+            return self
+        part = ItemMask.__new__(ItemMask)
+        on_dev = rows.to(self.words.device)
+        part._init(self.words.index_select(0, on_dev), self.counts.index_select(0, on_dev), self.n_items, False, self._counts_host.index_select(0, rows))
+        return part
+
 
 def _check_visible_words(visible: Optional[torch.Tensor], n_items: int, device: torch.device) -> None:
     """The visibility row a scan reads one word per 32-item tile of: exactly the words of n_items, on the table's device -- checked before any launch."""
@@ -1888,6 +1898,134 @@ def scores_range(scores: torch.Tensor, thresholds, mask: Optional[ItemMask] = No
                    "rails_scores_range_decode")
     del held
     return lims, out_scores, out_ids
+
+
+# ---- query fusion: several sub-query rows per fused row (rails_scores_fuse_rows, rails_topk_fuse_lists) -------------------
+FUSE_MODES = {"max": _lib.RAILS_FUSE_MAX, "sum": _lib.RAILS_FUSE_SUM}
+FUSE_LIST_MAX_ENTRIES = 16384      # (score, position) entries of one fused row rails_topk_fuse_lists merges
+FUSE_LIST_MAX_K = 512
+FUSE_LIST_MAX_SEEN = 4096
+
+
+def parse_query_lims(lims, rows: int, what: str = "query_lims") -> torch.Tensor:
+    """query_lims= as given -> the (U + 1,) int64 tensor on the CPU (the ONE read of a device tensor), checked: FAISS-shaped like
+    range_search's lims, lims[0] = 0, lims[U] = rows, strictly increasing.  ValueError names what is wrong."""
+    if not torch.is_tensor(lims) or lims.dtype != torch.int64 or lims.dim() != 1 or lims.numel() < 2:
+        raise ValueError(f"{what}: query_lims must be a (U + 1,) int64 tensor with U >= 1")
+    host = lims.detach().cpu().contiguous()
+    if int(host[0]) != 0:
+        raise ValueError(f"{what}: query_lims[0] must be 0, got {int(host[0])}")
+    if int(host[-1]) != rows:
+        raise ValueError(f"{what}: query_lims[U] = {int(host[-1])} but there are {rows} sub-query rows")
+    sizes = host[1:] - host[:-1]
+    if bool((sizes < 1).any()):
+        u = int(torch.nonzero(sizes < 1)[0])
+        raise ValueError(f"{what}: query_lims must increase strictly: segment {u} = [{int(host[u])}, {int(host[u + 1])}) is empty")
+    return host
+
+
+class QueryLims:
+    """A checked query_lims: `host` (U + 1,) on the CPU, `dev` the same on the device of the scores, fused rows U, sub-query rows S and the
+    largest segment.  Built once per call (parse_query_lims' one read); slices of whole segments are cut from the host copy."""
+
+    def __init__(self, lims, rows: int, device, what: str = "query_lims"):
+        self.host = parse_query_lims(lims, rows, what)
+        self.dev = lims if lims.device == torch.device(device) and lims.is_contiguous() else self.host.to(device)
+        self.fused, self.rows = self.host.numel() - 1, rows
+        self.max_segment = int((self.host[1:] - self.host[:-1]).max())
+        self._rows_of = None
+
+    def rows_slice(self, u0: int, u1: int) -> "QueryLims":
+        """The fused rows u0 .. u1 - 1 as a QueryLims of their own over the sub-query rows [host[u0], host[u1])."""
+        if u0 == 0 and u1 == self.fused:
+            return self
+        host = self.host[u0 : u1 + 1] - self.host[u0]
+        return QueryLims(host.to(self.dev.device), int(host[-1]), self.dev.device)
+
+    def fused_row_of(self) -> torch.Tensor:
+        """(S,) int64 on the CPU: the fused row of every sub-query row (what repeats a per-fused-row argument over its segment)."""
+        if self._rows_of is None:
+            self._rows_of = torch.repeat_interleave(torch.arange(self.fused, dtype=torch.int64), self.host[1:] - self.host[:-1])
+        return self._rows_of
+
+
+def _query_lims_arg(what: str, lims, rows: int, device) -> QueryLims:
+    ql = lims if isinstance(lims, QueryLims) else QueryLims(lims, rows, device, what)
+    if ql.rows != rows:
+        raise ValueError(f"{what}: query_lims[U] = {ql.rows} but there are {rows} sub-query rows")
+    if ql.dev.device != device:
+        raise ValueError(f"{what}: the query_lims and the scores live on different devices")
+    return ql
+
+
+def scores_fuse_rows(scores: torch.Tensor, lims, mode: str = "max", weights: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                     run_if: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(U, n) fp32, out of place: row u is the fusion of the rows [lims[u], lims[u + 1]) of `scores` ((S, n) fp32 with unit column stride), taken
+    ascending (rails_scores_fuse_rows).  mode "max": per column the element that is largest in the selection key's order (on the bits: +-0,
+    +-inf and NaNs as topk ranks them); "sum": acc = s[r0], acc = fl32(acc + s[r]), or with `weights` ((S,) fp32) acc = fl32(w[r0] * s[r0]),
+    acc = fl32(acc + fl32(w[r] * s[r])) -- no fma, a numpy float32 loop gives the same bits.  lims: a (U + 1,) int64 tensor (checked on the
+    host: one read) or a QueryLims.  out: a (U, n) fp32 tensor with contiguous rows that does not overlap `scores`.  One read of every score,
+    one write of every result; no sync beyond the read of lims."""
+    rows, n, ld = _score_matrix(scores)
+    if mode not in FUSE_MODES:
+        raise ValueError(f"scores_fuse_rows: fuse must be one of {sorted(FUSE_MODES)}, got {mode!r}")
+    if weights is not None:
+        if mode != "sum":
+            raise ValueError('scores_fuse_rows: query_weights go with fuse="sum"')
+        if not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.shape != (rows,) or weights.device != scores.device:
+            raise ValueError(f"scores_fuse_rows: query_weights must be ({rows},) fp32 on the scores' device")
+        weights = weights.contiguous()
+    ql = _query_lims_arg("scores_fuse_rows", lims, rows, scores.device)
+    if n < 1:
+        raise ValueError("scores_fuse_rows: scores has no columns")
+    refused = f"scores_fuse_rows: out must be a ({ql.fused}, {n}) fp32 tensor with contiguous rows on the scores' device"
+    if out is None:
+        out = torch.empty((ql.fused, n), dtype=torch.float32, device=scores.device)
+    elif not torch.is_tensor(out) or out.shape != (ql.fused, n) or out.device != scores.device or (ql.fused > 1 and out.stride(0) < n):
+        raise ValueError(refused)
+    out_ld = _score_matrix(out, "out", refused)[2]
+    with _on_device(scores.device):
+        _lib.check(_lib.load().rails_scores_fuse_rows(_ptr(scores), ld, rows, n, _ptr(ql.dev), ql.fused, FUSE_MODES[mode], _ptr(weights), _ptr(out), out_ld,
+                                                      _pred(run_if), _stream()), "rails_scores_fuse_rows")
+    return out
+
+
+def topk_fuse_lists_supported(max_segment: int, depth: int, k: int, width: int, n_items: int) -> bool:
+    """Whether rails_topk_fuse_lists takes these sizes (RAILS_ENOTSUP otherwise)."""
+    return max_segment * depth <= FUSE_LIST_MAX_ENTRIES and k <= FUSE_LIST_MAX_K and width <= FUSE_LIST_MAX_SEEN and n_items <= (1 << 32) - 1
+
+
+def topk_fuse_lists(scores: torch.Tensor, positions: torch.Tensor, lims, k: int, ids: Optional[torch.Tensor], invalid_ids: Optional[torch.Tensor] = None,
+                    n_items: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The top k of the "max" fusion from sorted lists (rails_topk_fuse_lists): scores / positions (S, D) -- row r's top-D list in selection-key
+    order, positions int64, a short list padded with (-inf, anything) or (anything, -1) -- -> (ids (U, k) int64, scores (U, k) fp32), ids
+    first like filter_seen_ids: per fused row the best entry of every position, ranked by the selection key (score descending, then position
+    ascending), without the entries whose id (ids[position]; the position itself when ids is None) is among invalid_ids[u] ((U, w)); a
+    short row ends in (-1, -inf).  n_items: positions outside [0, n_items) are skipped (default: the length of `ids`).  NotImplementedError
+    (nothing launched) beyond FUSE_LIST_MAX_ENTRIES entries per fused row, FUSE_LIST_MAX_K or FUSE_LIST_MAX_SEEN."""
+    rows, depth, ld = _score_matrix(scores)
+    _positions_arg("topk_fuse_lists", positions, rows, scores.device, t="D")
+    if positions.shape[1] != depth:
+        raise ValueError("topk_fuse_lists: positions must be (S, D) like scores")
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"topk_fuse_lists: k must be an int >= 1, got {k!r}")
+    ql = _query_lims_arg("topk_fuse_lists", lims, rows, scores.device)
+    if ids is not None:
+        ids = ids.to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
+    if n_items is None:
+        if ids is None:
+            raise ValueError("topk_fuse_lists: n_items is needed where there is no ids table")
+        n_items = ids.numel()
+    if ids is not None and ids.numel() < n_items:
+        raise ValueError("topk_fuse_lists: ids has fewer entries than n_items")
+    inv, width = _seen_arg(invalid_ids, ql.fused, scores.device)
+    out_i = torch.empty((ql.fused, k), dtype=torch.int64, device=scores.device)
+    out_s = torch.empty((ql.fused, k), dtype=torch.float32, device=scores.device)
+    pos = positions.contiguous()
+    with _on_device(scores.device):
+        _lib.check(_lib.load().rails_topk_fuse_lists(_ptr(scores), ld, _ptr(pos), rows, depth, _ptr(ql.dev), ql.fused, ql.max_segment, int(n_items), _ptr(ids),
+                                                     _ptr(inv), width, k, _ptr(out_i), _ptr(out_s), _stream()), "rails_topk_fuse_lists")
+    return out_i, out_s
 
 
 def tag_word_i32(word: int) -> int:

@@ -292,6 +292,19 @@ def refuse_collapse_groups(module, kwargs, what: Optional[str] = None) -> None:
                                   "forward_filtered, submit and get_top_k_outputs only")
 
 
+_FUSION_KWARGS = ("query_lims", "fuse", "query_weights")
+
+
+def refuse_query_fusion(module, kwargs, what: Optional[str] = None) -> None:
+    """query_lims= / fuse= / query_weights= where query fusion is not built -- the approximate modules (their candidates
+    are generated per query row), the item-sharded wrappers, submit / result, topk_ids: refused by the class's name, before any launch."""
+    given = [name for name in _FUSION_KWARGS if kwargs.get(name) is not None]
+    if given:
+        name = type(module).__name__ + (" (IVF, use_faiss=True)" if getattr(module, "_use_faiss", False) else "") + ("" if what is None else "." + what)
+        raise NotImplementedError(f"{name} takes no {given[0]}: fusing several query rows per user is built on the single-device MoLBruteForceTopK "
+                                  "and MIPSBruteForceTopK (forward, get_top_k_outputs, all_logits and the streaming score calls) only")
+
+
 def _tag_ks(module) -> Tuple[int, ...]:
     """The sizes a candidate-generating module selects per row: each must fit the items a filtered row may return."""
     return tuple(k for k in (getattr(module, "_avg_top_k", None), getattr(module, "_k_per_group", None)) if k is not None)
@@ -497,6 +510,18 @@ class Streamed(NamedTuple):
     whole: str                                  # why a row's logits are needed whole: the tail of the MAX_LOGIT_BYTES refusal
 
 
+class Fusion(NamedTuple):
+    """The resolved query fusion of a call: the checked query_lims=, fuse= and query_weights= (on the module's device)."""
+    lims: E.QueryLims
+    mode: str
+    weights: Optional[torch.Tensor]
+
+    def rows_slice(self, u0: int, u1: int) -> Tuple[int, int, "Fusion"]:
+        """The fused rows u0 .. u1 - 1 -> (their first sub-query row, the row past their last, the fusion of that slice alone)."""
+        s0, s1 = int(self.lims.host[u0]), int(self.lims.host[u1])
+        return s0, s1, Fusion(self.lims.rows_slice(u0, u1), self.mode, None if self.weights is None else self.weights[s0:s1])
+
+
 _RANK = Streamed("the exact rank of an item", "a target's key must be read from the matrix that is counted, and corpus chunks are not built")
 _SOFTMAX = Streamed("the softmax over every item of the corpus", "the normaliser needs every item of a row, and corpus chunks are not built")
 _RANGE = Streamed("a range search over every item of the corpus", "a row is counted and written whole, and corpus chunks are not built")
@@ -532,23 +557,190 @@ class _StreamingScores(_ItemsById):
         live).  In this order: the two refusals, the family's own argument checks (family_check, given the call's full name), invalid_ids,
         the policy's refusal (under the name policy_as, where that is not the call's)."""
         self._refuse_streaming(kwargs, what, family)
+        fusion = self._resolve_fusion(kwargs, query_embeddings, what)
         if family_check is not None:
             family_check(f"{type(self).__name__}.{what}")
         N = self.num_items
         if invalid_ids is not None:
-            _ids_arg(what, "invalid_ids", invalid_ids, query_embeddings.size(0), "S")
+            _ids_arg(what, "invalid_ids", invalid_ids, self._result_rows(query_embeddings, kwargs), "S")
+        if fusion is not None:
+            return self._fused_budget(f"{type(self).__name__}.{policy_as or what}", fusion, matrices, family.whole)
         rows = int(self.MAX_LOGIT_BYTES) // (N * 4 * matrices)
         if rows < 1:
             raise NotImplementedError(f"{type(self).__name__}.{policy_as or what}: {'two rows' if matrices == 2 else 'one row'} of {N} logits exceed"
                                       f"{'' if matrices == 2 else 's'} MAX_LOGIT_BYTES; {family.whole}")
         return rows
 
+    # ---- query fusion: several sub-query rows per result row (DESIGN section 3.20) -----------------------------------------------------------
+    # query_lims= ((U + 1,) int64, FAISS-shaped): the sub-query rows [lims[u], lims[u + 1]) of query_embeddings belong to fused row u.  With
+    # s[r, x] all_logits' bits for sub-query row r, F[u, x] is their fusion over the segment -- fuse="max": the element largest in the
+    # selection key's order; "sum": the fp32 chain acc = fl32(acc + s[r, x]), with query_weights= acc = fl32(acc + fl32(w[r] * s[r, x])) -- and
+    # every call means what it means on a module whose all_logits is F: per-row arguments and results are per FUSED row (user_ids alone
+    # stays per sub-query row).  Two routes: the matrix route fuses the (S, N) logits into (U, N) (engine.scores_fuse_rows) in front of
+    # every streaming call and the dense top-k; the list route ("max" alone) merges the sub-query rows' own top-(k + w) lists
+    # (engine.topk_fuse_lists) and so keeps whatever route the module's forward takes.
+    FUSE_LIST_MAX_ENTRIES = E.FUSE_LIST_MAX_ENTRIES      # entries (sub-query rows x k') of one fused row the list route merges; 0: always the matrix route
+
+    def _resolve_fusion(self, kwargs: dict, query_embeddings: torch.Tensor, what: str) -> Optional[Fusion]:
+        """query_lims= / fuse= / query_weights= of a call, taken OUT of its kwargs and checked before any launch (the one host read of a device
+        query_lims) -> the Fusion, left in kwargs["_fusion"] for the calls this one makes; None: the call is not fused."""
+        if "_fusion" in kwargs:
+            return kwargs["_fusion"]
+        lims, mode, weights = kwargs.pop("query_lims", None), kwargs.pop("fuse", None), kwargs.pop("query_weights", None)
+        name = f"{type(self).__name__}.{what}"
+        if lims is None:
+            for given, value in (("fuse", mode), ("query_weights", weights)):
+                if value is not None:
+                    raise ValueError(f"{name}: {given}= without query_lims=")
+            return None
+        if kwargs.get("collapse_groups") or kwargs.get("max_per_group") is not None:
+            raise NotImplementedError(f"{name}: collapse_groups= / max_per_group= together with query_lims= is not built")
+        mode = "max" if mode is None else mode
+        if mode not in E.FUSE_MODES:
+            raise ValueError(f"{name}: fuse must be one of {sorted(E.FUSE_MODES)}, got {mode!r}")
+        S, dev = query_embeddings.size(0), self._ids_flat.device
+        if weights is not None:
+            if mode != "sum":
+                raise ValueError(f'{name}: query_weights= goes with fuse="sum", not with {mode!r}')
+            if not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.shape != (S,):
+                raise ValueError(f"{name}: query_weights must be ({S},) fp32, one weight per sub-query row")
+            weights = weights.to(dev).contiguous()
+        fusion = kwargs["_fusion"] = Fusion(E.QueryLims(lims, S, dev, name), mode, weights)
+        return fusion
+
+    @staticmethod
+    def _result_rows(query_embeddings: torch.Tensor, kwargs: dict) -> int:
+        """The rows of a call's per-row arguments and results: the fused rows of a resolved fusion, else the query rows."""
+        fusion = kwargs.get("_fusion")
+        return query_embeddings.size(0) if fusion is None else fusion.lims.fused
+
+    def _fused_budget(self, name: str, fusion: Fusion, matrices: int, whole: str) -> int:
+        """The matrix rows a slice of a fused call may hold under the logit policy: its sub-query rows plus `matrices` rows per fused row."""
+        budget = int(self.MAX_LOGIT_BYTES) // (self.num_items * 4)
+        if fusion.lims.max_segment + matrices > budget:
+            raise NotImplementedError(f"{name}: a segment of {fusion.lims.max_segment} sub-query rows and its fused row{'s' if matrices > 1 else ''} of "
+                                      f"{self.num_items} logits exceed MAX_LOGIT_BYTES; a segment is fused whole, and {whole}")
+        return budget
+
+    @staticmethod
+    def _slice_plan(batch: int, rows: int, fusion: Optional[Fusion], matrices: int = 1) -> list:
+        """The batch slices [(b0, b1), ...] of a streaming call: `rows` query rows at a time; under a fusion whole segments, each fused row
+        counting its sub-query rows plus `matrices` rows of its own against the budget `rows` (_fused_budget saw that every segment fits)."""
+        if fusion is None:
+            return [(b0, min(batch, b0 + rows)) for b0 in range(0, batch, rows)]
+        sizes = (fusion.lims.host[1:] - fusion.lims.host[:-1]).tolist()
+        plan, u0, held = [], 0, 0
+        for u, m in enumerate(sizes):
+            if held and held + m + matrices > rows:
+                plan.append((u0, u))
+                u0, held = u, 0
+            held += m + matrices
+        plan.append((u0, len(sizes)))
+        return plan
+
+    def _fused_slices(self, query_embeddings: torch.Tensor, fusion: Fusion, kwargs: dict, plan: list):
+        """(u0, u1, F) per slice of `plan`: the sub-query logits of the slice's segments (_rank_scores: the recycled logits buffer) fused into
+        the (u1 - u0, N) head of a second buffer shared by the slices -- consumed before the next step.  A payload of kwargs with one row per
+        sub-query row is sliced by query_lims, one with a row per fused row by fused row."""
+        S, U = fusion.lims.rows, fusion.lims.fused
+        fused = torch.empty((max(u1 - u0 for u0, u1 in plan), self.num_items), dtype=torch.float32, device=self._ids_flat.device)
+        for u0, u1 in plan:
+            s0, s1, part = fusion.rows_slice(u0, u1)
+            kw = {key: (v[s0:s1] if v.shape[0] == S else v[u0:u1] if v.shape[0] == U else v) if torch.is_tensor(v) and v.dim() >= 1 else v
+                  for key, v in kwargs.items()}
+            scores = self._rank_scores(query_embeddings[s0:s1], **kw)
+            yield u0, u1, E.scores_fuse_rows(scores, part.lims, part.mode, part.weights, out=fused[: u1 - u0])
+
+    def _fusion_count(self, key: str) -> None:
+        stats = self.__dict__.setdefault("_fusion_stats", {"fused_list_calls": 0, "fused_matrix_calls": 0})
+        stats[key] += 1
+
+    def fusion_stats(self) -> dict:
+        """Which route answered the fused top-k calls so far (fused_list_calls / fused_matrix_calls); empty before the first one."""
+        return dict(self.__dict__.get("_fusion_stats", {}))
+
+    def _segment_kwargs(self, kwargs: dict, fusion: Fusion) -> dict:
+        """The kwargs of the list route's call on the sub-query rows: a per-fused-row item_mask= / allowed_tags= repeated over its segment."""
+        kw, U = dict(kwargs), fusion.lims.fused
+        rows = fusion.lims.fused_row_of()
+        m = kw.get("item_mask")
+        if isinstance(m, E.ItemMask):
+            m.check(self.num_items, U, None)
+            kw["item_mask"] = m.rows_take(rows)
+        elif torch.is_tensor(m) and m.dim() == 2:
+            if m.shape[0] != U:
+                raise ValueError(f"item_mask has {m.shape[0]} rows but the batch has {U}")
+            kw["item_mask"] = m.index_select(0, rows.to(m.device))
+        a = kw.get("allowed_tags")
+        if a is not None and not isinstance(a, int):
+            words = a.words if isinstance(a, E.TagFilter) else parse_allowed_tags(a, U)
+            kw["allowed_tags"] = words[0] if len(words) == 1 else [words[u] for u in rows.tolist()]
+        return kw
+
+    def _fused_topk(self, what: str, query_embeddings: torch.Tensor, k_prime: int, seen, fusion: Fusion, kwargs: dict, sorted: bool = True):
+        """The top-k of a fused call -> (ids (U, k), scores (U, k) fp32): the k' best items of F per fused row, and with seen = (invalid_ids
+        (U, w), k) the first k of them whose id is not among the row's invalid_ids (filter_seen_ids' rule).
+        The LIST route ("max", k' = k + w, within engine.topk_fuse_lists' limits, a corpus of distinct ids): this module's own forward on the S
+        sub-query rows for k' results and no seen filter -- every route it has, unchanged --, their positions (positions_of), one merge launch.
+        If x is among the first k eligible-and-unseen items of fused row u and r* the row where x attains its maximum, every item that beats x
+        in row r* beats it in F with the same position in the key, so x is among row r*'s top (k + w).
+        The MATRIX route (everything else): fuse, mask, select, a slice of whole segments at a time under the logit policy."""
+        kwargs.pop("_fusion", None)
+        name = f"{type(self).__name__}.{what}"
+        U, S, N = fusion.lims.fused, fusion.lims.rows, self.num_items
+        inv, k = seen if seen is not None else (None, k_prime)
+        if inv is not None:
+            _ids_arg(what, "invalid_ids", inv, U, "w")
+        w = 0 if inv is None else inv.shape[1]
+        with torch.inference_mode(), self.one_bind():
+            id_map = None
+            if (fusion.mode == "max" and query_embeddings.dtype == torch.float32 and k_prime == k + w and k_prime <= N
+                    and fusion.lims.max_segment * k_prime <= self.FUSE_LIST_MAX_ENTRIES and E.topk_fuse_lists_supported(fusion.lims.max_segment, k_prime, k, w, N)):
+                try:
+                    id_map = self._live_id_map()
+                except ValueError:      # two items share an id (the id map's refusal): no position from an id, the matrix route answers
+                    id_map = None
+            if id_map is not None:
+                scores, ids = self.forward(query_embeddings, k_prime, **self._segment_kwargs(kwargs, fusion))
+                positions = id_map.lookup(ids.reshape(-1)).view(S, k_prime)
+                self._fusion_count("fused_list_calls")
+                return E.topk_fuse_lists(scores, positions, fusion.lims, k, self._ids_flat, inv, n_items=N)
+            mask = self._take_item_mask(kwargs, U, k_prime)
+            budget = self._fused_budget(name, fusion, 1, "corpus chunks are not built for a fused call")
+            if k_prime > N:
+                raise RuntimeError(f"selected index k out of range (k={k_prime}, n={N})")
+            parts = []
+            for u0, u1, fused in self._fused_slices(query_embeddings, fusion, kwargs, self._slice_plan(U, budget, fusion)):
+                if mask is not None:
+                    E.scores_mask(fused, mask.rows_slice(u0, u1))
+                if inv is None:
+                    s, i = E.topk(fused, k_prime, ids=self._ids_flat, sorted=sorted)
+                    parts.append((i, s))
+                elif E.topk_filter_fusable(N, k_prime, w, k):
+                    parts.append(E.topk_filtered(fused, k_prime, self._ids_flat, inv[u0:u1], k))
+                else:
+                    s, i = E.topk(fused, k_prime, ids=self._ids_flat)
+                    parts.append(E.filter_seen_ids(i, s, inv[u0:u1], k))
+            self._fusion_count("fused_matrix_calls")
+            return _join_slices(parts)
+
+    def _fused_all_logits(self, query_embeddings: torch.Tensor, fusion: Fusion, kwargs: dict) -> torch.Tensor:
+        """all_logits(query_lims=...): F as (U, N) fp32, -inf outside the call's mask."""
+        kwargs.pop("_fusion", None)
+        with self.one_bind():
+            mask = self._take_item_mask(kwargs, fusion.lims.fused, None)
+            fused = E.scores_fuse_rows(self._rank_scores(query_embeddings, **kwargs), fusion.lims, fusion.mode, fusion.weights)
+            return fused if mask is None else E.scores_mask(fused, mask)
+
     @contextlib.contextmanager
-    def _eligible_rows(self, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], kwargs: dict, rows: int):
+    def _eligible_rows(self, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], kwargs: dict, rows: int, matrices: int = 1):
         """The host flow of the streaming calls: inside the block (inference mode, one bind) the value is a generator of (b0, b1, scores,
         words) over batch slices of at most `rows` rows -- scores: _rank_scores of the slice (a recycled buffer: consumed before the next
-        step), words: the eligible items of these rows as engine.scores_rank takes them (None: every item)."""
-        B, N = query_embeddings.size(0), self.num_items
+        step), words: the eligible items of these rows as engine.scores_rank takes them (None: every item).  Under a fusion (DESIGN section
+        3.20) the rows are fused rows, the slices hold whole segments (_slice_plan; `matrices`: the (b, N) matrices the call holds per fused
+        row) and scores is the fused matrix."""
+        fusion = kwargs.pop("_fusion", None)
+        B, N = self._result_rows(query_embeddings, {"_fusion": fusion}), self.num_items
         with torch.inference_mode(), self.one_bind():
             mask = self._take_item_mask(kwargs, B, None)      # the hidden set, allowed_tags= and item_mask= as one mask (its syncs are the call's only ones)
             words = None if mask is None else mask.words
@@ -563,13 +755,20 @@ class _StreamingScores(_ItemsById):
                     words = words.clone(memory_format=torch.contiguous_format)
                 E.item_mask_clear_rows(words, seen, N)
 
+            def words_of(b0: int, b1: int):
+                return None if words is None else words if words.shape[0] == 1 else words[b0:b1]
+
             def slices():
                 for b0 in range(0, B, rows):
                     b1 = min(B, b0 + rows)
                     kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kwargs.items()}
-                    yield b0, b1, self._rank_scores(query_embeddings[b0:b1], **kw), None if words is None else words if words.shape[0] == 1 else words[b0:b1]
+                    yield b0, b1, self._rank_scores(query_embeddings[b0:b1], **kw), words_of(b0, b1)
 
-            yield slices()
+            def fused_slices():
+                for u0, u1, fused in self._fused_slices(query_embeddings, fusion, kwargs, self._slice_plan(B, rows, fusion, matrices)):
+                    yield u0, u1, fused, words_of(u0, u1)
+
+            yield slices() if fusion is None else fused_slices()
 
     # ---- rank_of: the exact rank of given items per query row ---------------------------------------------------------
     # rank(b, x) = 1 + the number of items row b may return whose selection key (score descending, position ascending, on all_logits' bits)
@@ -580,7 +779,8 @@ class _StreamingScores(_ItemsById):
         0 where the corpus has no such item or the row may not return it.  invalid_ids (B, S): the row's seen ids, which leave its eligible
         set (ids nobody has are ignored).  kwargs: what all_logits takes (user_ids, item_mask=, allowed_tags=)."""
         self._refuse_streaming(kwargs, "rank_of", _RANK)
-        B = query_embeddings.size(0)
+        self._resolve_fusion(kwargs, query_embeddings, "rank_of")
+        B = self._result_rows(query_embeddings, kwargs)
         _ids_arg("rank_of", "target_ids", target_ids, B)
         positions = self.positions_of(target_ids.reshape(-1)).view(B, -1)
         return self.rank_of_positions(query_embeddings, positions, invalid_ids, **kwargs)
@@ -589,7 +789,7 @@ class _StreamingScores(_ItemsById):
         """rank_of for targets given as corpus POSITIONS ((B, T) int64; one outside [0, N), such as the -1 positions_of gives an unknown id, gets
         rank 0)."""
         rows = self._streaming_call("rank_of_positions", _RANK, query_embeddings, invalid_ids, kwargs, policy_as="rank_of",
-                                    family_check=lambda _: _positions_arg("rank_of_positions", positions, query_embeddings.size(0)))
+                                    family_check=lambda _: _positions_arg("rank_of_positions", positions, self._result_rows(query_embeddings, kwargs)))
         with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
             positions = positions.to(self._ids_flat.device)
             return _join_slices([E.scores_rank(scores, positions[b0:b1], words) for b0, b1, scores, words in slices])
@@ -614,7 +814,7 @@ class _StreamingScores(_ItemsById):
         """(B, T) fp32: the log-probability of the item carrying target_ids[b, j] under softmax(logits / temperature) over the items query row
         b may return: fp32(logit * beta) - log_partition.  -inf where the corpus has no such item or the row may not return it."""
         self._softmax_call("log_prob_of", query_embeddings, invalid_ids, temperature, kwargs)
-        B = query_embeddings.size(0)
+        B = self._result_rows(query_embeddings, kwargs)
         _ids_arg("log_prob_of", "target_ids", target_ids, B)
         positions = self.positions_of(target_ids.reshape(-1)).view(B, -1)
         return self.log_prob_of_positions(query_embeddings, positions, invalid_ids, temperature, **kwargs)
@@ -623,7 +823,7 @@ class _StreamingScores(_ItemsById):
                               temperature: float = 1.0, **kwargs) -> torch.Tensor:
         """log_prob_of for targets given as corpus POSITIONS ((B, T) int64; one outside [0, N) gets -inf)."""
         rows = self._softmax_call("log_prob_of_positions", query_embeddings, invalid_ids, temperature, kwargs)
-        _positions_arg("log_prob_of_positions", positions, query_embeddings.size(0))
+        _positions_arg("log_prob_of_positions", positions, self._result_rows(query_embeddings, kwargs))
         with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
             positions = positions.to(self._ids_flat.device)
             return _join_slices([E.scores_log_prob(scores, positions[b0:b1], E.scores_lse(scores, words, temperature), words, temperature)
@@ -637,15 +837,16 @@ class _StreamingScores(_ItemsById):
         with fewer than S items of non-zero probability ends in (-1, -inf) entries.  seed: an int in [0, 2^64); the noise of (seed, batch row,
         item position) does not depend on how the logit policy slices the batch.  Two (b, N) matrices live per slice."""
         rows = self._softmax_call("sample_items", query_embeddings, invalid_ids, temperature, kwargs, matrices=2)
-        B, N = query_embeddings.size(0), self.num_items
+        B, N, fusion = self._result_rows(query_embeddings, kwargs), self.num_items, kwargs.get("_fusion")
         if isinstance(num_samples, bool) or not isinstance(num_samples, int) or not 1 <= num_samples <= min(N, E.TOPK_MAX_K):
             raise ValueError(f"sample_items: num_samples must be an int in [1, {min(N, E.TOPK_MAX_K)}] (the corpus holds {N} items, the exact top-k "
                              f"takes k <= {E.TOPK_MAX_K}), got {num_samples!r}")
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
             raise ValueError(f"sample_items: seed must be an int in [0, 2^64), got {seed!r}")
-        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows) as slices:
+        with self._eligible_rows(query_embeddings, invalid_ids, kwargs, rows, matrices=2) as slices:
             parts = []
-            perturbed = torch.empty((min(rows, B), N), dtype=torch.float32, device=self._ids_flat.device)      # the second matrix, shared by the slices
+            most = max(b1 - b0 for b0, b1 in self._slice_plan(B, rows, fusion, 2))
+            perturbed = torch.empty((most, N), dtype=torch.float32, device=self._ids_flat.device)      # the second matrix (the third of a fused call), shared by the slices
             for b0, b1, scores, words in slices:
                 noisy = E.scores_gumbel(scores, seed, b0, words, temperature, out=perturbed[: b1 - b0])
                 top, pos = E.topk(noisy, num_samples)
@@ -668,8 +869,8 @@ class _StreamingScores(_ItemsById):
                                  "temperature goes with min_log_prob=")
 
         rows = self._streaming_call(what, _RANGE, query_embeddings, invalid_ids, kwargs, one_threshold)
-        return rows, E.range_thresholds(f"{type(self).__name__}.{what}", min_score if min_score is not None else min_log_prob, query_embeddings.size(0),
-                                        self._ids_flat.device)
+        return rows, E.range_thresholds(f"{type(self).__name__}.{what}", min_score if min_score is not None else min_log_prob,
+                                        self._result_rows(query_embeddings, kwargs), self._ids_flat.device)
 
     def count_above(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0,
                     invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
@@ -1051,6 +1252,9 @@ class _CorpusEdits(_StreamingScores):
                 raise ValueError(f"{type(self).__name__}: max_per_group must be a Python int >= 1, got {m!r}")
             if collapse and m != 1:
                 raise ValueError(f"{type(self).__name__}: collapse_groups=True means max_per_group=1, got max_per_group={m} with it (pass one of the two)")
+        if any(kwargs.get(name) is not None for name in _FUSION_KWARGS):      # (the two are not built together)
+            raise NotImplementedError(f"{type(self).__name__}: {what}= together with query_lims= is not built: collapse the fused ranking on the caller's side, "
+                                      "or fuse without groups")
         self._check_collapsible(what)
         if self._groups is None:
             raise ValueError(f"{type(self).__name__}: {what}={'True' if what == 'collapse_groups' else m} on a module without groups (set_item_groups first)")
@@ -1430,7 +1634,9 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
 
 def refuse_item_mask(module, kwargs, why: str = "its candidates are generated inside the fused scans, and masking their result afterwards is not the "
                                                "contract of a masked call") -> None:
-    """item_mask= is built on the exact modules only: every other module refuses it by name, before any launch."""
+    """item_mask= is built on the exact modules only: every other module refuses it by name, before any launch.
+    query_lims= (section 3.20) is built in the same places and refused in the same places, by its own name."""
+    refuse_query_fusion(module, kwargs)
     if kwargs.get("item_mask") is not None:
         name = type(module).__name__ + (" (IVF, use_faiss=True)" if getattr(module, "_use_faiss", False) else "")
         raise NotImplementedError(f"{name} takes no item_mask: {why}; MoLBruteForceTopK and MIPSBruteForceTopK take it")
@@ -1708,8 +1914,11 @@ class MoLBruteForceTopK(MoLTopKModule):
 
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus -- of the module's OWN precision (the proved mode's internal split-f16
-        engine is not the module's precision: its fp32 companion answers).  item_mask=: the columns outside the mask hold -inf."""
+        engine is not the module's precision: its fp32 companion answers).  item_mask=: the columns outside the mask hold -inf.
+        query_lims=: the fused matrix, (U, N)."""
         refuse_collapse_groups(self, kwargs, "all_logits")
+        if (fusion := self._resolve_fusion(kwargs, query_embeddings, "all_logits")) is not None:
+            return self._fused_all_logits(query_embeddings, fusion, kwargs)
         eng = self._bind()
         mask = self._take_item_mask(kwargs, query_embeddings.size(0), None)
         if eng.exact is not None and self._mol_module.engine() is not eng:
@@ -1794,7 +2003,11 @@ class MoLBruteForceTopK(MoLTopKModule):
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """item_mask= (an engine.ItemMask, or a bool tensor (N,) / (B, N) packed for this call): only items inside the mask are returned.
-        collapse_groups=True: at most one item per group of set_item_groups."""
+        collapse_groups=True: at most one item per group of set_item_groups.  query_lims= (section 3.20): one result row
+        per segment of query rows."""
+        if (fusion := self._resolve_fusion(kwargs, query_embeddings, "forward")) is not None:
+            ids, scores = self._fused_topk("forward", query_embeddings, k, None, fusion, kwargs, sorted)
+            return scores.to(query_embeddings.dtype), ids
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
             return _collapsed_exact(self, query_embeddings, k, None, kwargs, m)
         eng = self._bind()
@@ -1815,7 +2028,10 @@ class MoLBruteForceTopK(MoLTopKModule):
         selection launch (rails_topk_filtered on the dense logits) -> (top_k_ids (B, k), top_k_scores (B, k)),
         or None when the sizes / the precision route are outside the fused path (the caller then composes forward +
         filter_seen_ids: same bits).  collapse_groups=True never returns None: the seen ids go to the collapse walk (a filter behind the
-        collapse would drop a group whose best item is seen instead of promoting its next member)."""
+        collapse would drop a group whose best item is seen instead of promoting its next member).  Nor does query_lims= (section 3.20)."""
+        if (fusion := self._resolve_fusion(kwargs, query_embeddings, "forward_filtered")) is not None:
+            ids, scores = self._fused_topk("forward_filtered", query_embeddings, k_prime, (invalid_ids, k), fusion, kwargs)
+            return ids, scores.to(query_embeddings.dtype)
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
             scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs, m)
             return ids, scores
@@ -2332,6 +2548,7 @@ class MoLBruteForceTopK(MoLTopKModule):
         eng = self._bind()
         if eng.exact is not None:
             out.update(self.rigorous_eps())
+        out.update(self.fusion_stats())      # (fused_list_calls / fused_matrix_calls, once a call has been fused: DESIGN section 3.20)
         return out
 
     def rigorous_eps(self) -> Dict[str, float]:
@@ -3121,6 +3338,7 @@ class MoLAvgTopK(MoLTopKModule):
     def topk_ids(self, query_embeddings: torch.Tensor, sorted: bool = True, **kwargs) -> torch.Tensor:
         """Coarse candidates only, with the P_Q-averaged query (reference mol_top_k.py:398-429) -> positions."""
         refuse_collapse_groups(self, kwargs, "topk_ids")
+        refuse_query_fusion(self, kwargs, "topk_ids")
         return self._coarse_topk(query_embeddings, average_queries=True, **kwargs)[1]
 
 
@@ -3149,6 +3367,7 @@ class _ComponentCandidates:
         """CandidateIndex.get_top_k_outputs' body (the module returns all its candidates whatever k_prime is, the filter keeps the first k unseen):
         -> (top_k_ids, top_k_scores), or None where the filter does not fit the selection launch (_filter_inside).  collapse_groups=True never
         returns None: the seen ids go to the collapse walk, over the sorted form of the ranking."""
+        refuse_query_fusion(self, kwargs)
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
             scores, ids = _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, invalid_ids, 0, kwargs, m))
             return ids, scores
@@ -3487,7 +3706,10 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """item_mask= (an engine.ItemMask or a bool tensor (N,) / (B, N)): only items inside the mask are returned -- the
         dense strategy: the score matrix of the items outside it is set to -inf before the selection.  collapse_groups=True (section 3.16): at
-        most one item per group of set_item_groups."""
+        most one item per group of set_item_groups.  query_lims= (section 3.20): one result row per segment of query rows."""
+        if (fusion := self._resolve_fusion(kwargs, query_embeddings, "forward")) is not None:
+            ids, scores = self._fused_topk("forward", query_embeddings, k, None, fusion, kwargs, sorted)
+            return scores.to(query_embeddings.dtype), ids
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
             return _collapsed_exact(self, query_embeddings, k, None, kwargs, m)
         mask = self._take_item_mask(kwargs, query_embeddings.size(0), k)
@@ -3499,11 +3721,19 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
 
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
         """CandidateIndex.get_top_k_outputs' body under collapse_groups=True -> (top_k_ids, top_k_scores): the seen ids go to the collapse walk.
-        None for every other call (the caller composes forward + filter_seen_ids, as it always has)."""
+        So under query_lims= (section 3.20): the seen ids are per fused row.  None for every other call (the caller composes forward +
+        filter_seen_ids, as it always has)."""
+        if (fusion := self._resolve_fusion(kwargs, query_embeddings, "forward_filtered")) is not None:
+            ids, scores = self._fused_topk("forward_filtered", query_embeddings, k_prime, (invalid_ids, k), fusion, kwargs)
+            return ids, scores.to(query_embeddings.dtype)
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
             scores, ids = _collapsed_exact(self, query_embeddings, k, invalid_ids, kwargs, m)
             return ids, scores
         return None
+
+    def stats(self) -> Dict[str, int]:
+        """Which route answered the fused calls so far (fusion_stats)."""
+        return self.fusion_stats()
 
     def _rank_scores(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         return self._index.score(query_embeddings)
