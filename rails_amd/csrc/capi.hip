@@ -1324,64 +1324,63 @@ int rails_rerank_topk_filtered(const float* scores, int64_t ld, int32_t rows, in
   return r == kOk ? r : fail(r, "rerank_topk_filtered");
 }
 
+// rails_topk_collapse and its quota form: one check list under the called entry's name; the plain walk hands max_per_group = 0 on.
+static int collapse_checked(const char* name, bool quota, const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth,
+                            const int32_t* group_ranks, int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k,
+                            int32_t max_per_group, float* out_scores, int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || depth < 0 || k < 0 || width < 0 || n_items < 0) { set_error("%s: negative size", name); return RAILS_EINVAL; }
+  if (quota && max_per_group < 1) { set_error("%s: max_per_group = %d below 1", name, max_per_group); return RAILS_EINVAL; }
+  if (rows == 0 || k == 0) return RAILS_OK;
+  if (!scores || !positions || !group_ranks || !out_scores || !out_positions || !out_ids || !out_counts || !out_of_range || (width > 0 && !invalid_ids)) { set_error("%s: NULL pointer", name); return RAILS_EINVAL; }
+  if (ld < depth) { set_error("%s: ld < depth", name); return RAILS_EINVAL; }
+  return fail(topk_collapse(scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k, max_per_group, out_scores, out_positions,
+                            out_ids, out_counts, out_of_range, (hipStream_t)stream), name);
+}
+
 int rails_topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const int32_t* group_ranks,
                         int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, float* out_scores,
                         int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, void* stream) {
-  g_err[0] = '\0';
-  if (rows < 0 || depth < 0 || k < 0 || width < 0 || n_items < 0) { set_error("topk_collapse: negative size"); return RAILS_EINVAL; }
-  if (rows == 0 || k == 0) return RAILS_OK;
-  if (!scores || !positions || !group_ranks || !out_scores || !out_positions || !out_ids || !out_counts || !out_of_range || (width > 0 && !invalid_ids)) {
-    set_error("topk_collapse: NULL pointer");
-    return RAILS_EINVAL;
-  }
-  if (ld < depth) { set_error("topk_collapse: ld < depth"); return RAILS_EINVAL; }
-  const int r = topk_collapse(scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k, 0, out_scores, out_positions, out_ids,
-                              out_counts, out_of_range, (hipStream_t)stream);
-  return r == kOk ? r : fail(r, "topk_collapse");
+  return collapse_checked("topk_collapse", false, scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k, 0, out_scores,
+                          out_positions, out_ids, out_counts, out_of_range, stream);
 }
 
 int rails_topk_collapse_quota(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const int32_t* group_ranks,
                               int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, int32_t max_per_group,
                               float* out_scores, int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, void* stream) {
+  return collapse_checked("topk_collapse_quota", true, scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k,
+                          max_per_group, out_scores, out_positions, out_ids, out_counts, out_of_range, stream);
+}
+
+// rails_scores_group_max and rails_scores_group_next: one check list under the called entry's name.  rounds: the next entry, whose empty pass
+// (n == 0) is nothing to do; the max entry's may still clear its table, and its strides and bound (n_groups, none) pass the round's checks.
+static int group_table_checked(const char* name, bool rounds, const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item,
+                               const int32_t* group_ranks, int64_t n_groups, uint64_t* table, int64_t table_stride, const uint64_t* below,
+                               int64_t below_stride, int32_t clear_table, const int64_t* ids, const int64_t* invalid_ids, int32_t width, void* stream) {
   g_err[0] = '\0';
-  if (rows < 0 || depth < 0 || k < 0 || width < 0 || n_items < 0) { set_error("topk_collapse_quota: negative size"); return RAILS_EINVAL; }
-  if (max_per_group < 1) { set_error("topk_collapse_quota: max_per_group = %d below 1", max_per_group); return RAILS_EINVAL; }
-  if (rows == 0 || k == 0) return RAILS_OK;
-  if (!scores || !positions || !group_ranks || !out_scores || !out_positions || !out_ids || !out_counts || !out_of_range || (width > 0 && !invalid_ids)) {
-    set_error("topk_collapse_quota: NULL pointer");
-    return RAILS_EINVAL;
-  }
-  if (ld < depth) { set_error("topk_collapse_quota: ld < depth"); return RAILS_EINVAL; }
-  const int r = topk_collapse(scores, ld, positions, rows, depth, group_ranks, n_items, ids, invalid_ids, width, k, max_per_group, out_scores,
-                              out_positions, out_ids, out_counts, out_of_range, (hipStream_t)stream);
-  return r == kOk ? r : fail(r, "topk_collapse_quota");
+  if (rows < 0 || n < 0 || first_item < 0 || n_groups < 0 || width < 0) { set_error("%s: negative size", name); return RAILS_EINVAL; }
+  if (rows == 0 || n_groups == 0 || (rounds && n == 0)) return RAILS_OK;
+  if (!table || (n > 0 && (!scores || !group_ranks)) || (width > 0 && !invalid_ids)) { set_error("%s: NULL pointer", name); return RAILS_EINVAL; }
+  if (ld < n) { set_error("%s: ld < n", name); return RAILS_EINVAL; }
+  if (table_stride < n_groups || (below && below_stride < n_groups)) { set_error("%s: a row stride below n_groups", name); return RAILS_EINVAL; }
+  if (below == table) { set_error("%s: a round cannot bound itself", name); return RAILS_EINVAL; }
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(table);
+  return fail(rounds ? scores_group_next(scores, ld, rows, n, first_item, group_ranks, n_groups, keys, table_stride, reinterpret_cast<const unsigned long long*>(below),
+                                         below_stride, ids, invalid_ids, width, (hipStream_t)stream)
+                     : scores_group_max(scores, ld, rows, n, first_item, group_ranks, n_groups, keys, clear_table, ids, invalid_ids, width, (hipStream_t)stream), name);
 }
 
 int rails_scores_group_next(const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const int32_t* group_ranks, int64_t n_groups,
                             uint64_t* table, int64_t table_stride, const uint64_t* below, int64_t below_stride, const int64_t* ids,
                             const int64_t* invalid_ids, int32_t width, void* stream) {
-  g_err[0] = '\0';
-  if (rows < 0 || n < 0 || first_item < 0 || n_groups < 0 || width < 0) { set_error("scores_group_next: negative size"); return RAILS_EINVAL; }
-  if (rows == 0 || n_groups == 0 || n == 0) return RAILS_OK;
-  if (!table || !scores || !group_ranks || (width > 0 && !invalid_ids)) { set_error("scores_group_next: NULL pointer"); return RAILS_EINVAL; }
-  if (ld < n) { set_error("scores_group_next: ld < n"); return RAILS_EINVAL; }
-  if (table_stride < n_groups || (below && below_stride < n_groups)) { set_error("scores_group_next: a row stride below n_groups"); return RAILS_EINVAL; }
-  if (below == table) { set_error("scores_group_next: a round cannot bound itself"); return RAILS_EINVAL; }
-  const int r = scores_group_next(scores, ld, rows, n, first_item, group_ranks, n_groups, reinterpret_cast<unsigned long long*>(table), table_stride,
-                                  reinterpret_cast<const unsigned long long*>(below), below_stride, ids, invalid_ids, width, (hipStream_t)stream);
-  return r == kOk ? r : fail(r, "scores_group_next");
+  return group_table_checked("scores_group_next", true, scores, ld, rows, n, first_item, group_ranks, n_groups, table, table_stride, below, below_stride, 0,
+                             ids, invalid_ids, width, stream);
 }
 
 int rails_scores_group_max(const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const int32_t* group_ranks, int64_t n_groups,
                            uint64_t* table, int32_t clear_table, const int64_t* ids, const int64_t* invalid_ids, int32_t width, void* stream) {
-  g_err[0] = '\0';
-  if (rows < 0 || n < 0 || first_item < 0 || n_groups < 0 || width < 0) { set_error("scores_group_max: negative size"); return RAILS_EINVAL; }
-  if (rows == 0 || n_groups == 0) return RAILS_OK;
-  if (!table || (n > 0 && (!scores || !group_ranks)) || (width > 0 && !invalid_ids)) { set_error("scores_group_max: NULL pointer"); return RAILS_EINVAL; }
-  if (ld < n) { set_error("scores_group_max: ld < n"); return RAILS_EINVAL; }
-  const int r = scores_group_max(scores, ld, rows, n, first_item, group_ranks, n_groups, reinterpret_cast<unsigned long long*>(table), clear_table, ids,
-                                 invalid_ids, width, (hipStream_t)stream);
-  return r == kOk ? r : fail(r, "scores_group_max");
+  return group_table_checked("scores_group_max", false, scores, ld, rows, n, first_item, group_ranks, n_groups, table, n_groups, nullptr, 0, clear_table,
+                             ids, invalid_ids, width, stream);
 }
 
 int rails_topk_keys(const uint64_t* table, int32_t rows, int64_t n_groups, int32_t k, const int64_t* ids, float* out_scores, int64_t* out_positions,

@@ -1,14 +1,15 @@
-// Collapsing a ranked list by item group: at most one result per group, or at most m.  Four kernels:
+// Collapsing a ranked list by item group: at most one result per group, or at most m.  Three kernels:
 //   collapse_walk_kernel   one workgroup per row over a ranked list of D (score, position) entries in key order: the first k entries whose
 //                          group has not occurred earlier in the list, the seen-id filter inside (rails_topk_collapse); its quota form keeps
 //                          the first m entries of every group (rails_topk_collapse_quota)
-//   group_max_kernel       streams a (rows, n) score matrix: table[row][rank] = max over the group's eligible items of the topk_keys.h key
-//                          (rails_scores_group_max) -- the exact fallback where one group owns the head of the ranking
-//   group_next_kernel      the same pass bounded from above by the previous round's table: round t leaves every group's (t + 1)-th best
-//                          eligible item (rails_scores_group_next) -- the fallback of a quota
+//   group_next_kernel      streams a (rows, n) score matrix: table[row][rank] = max over the group's eligible items of the topk_keys.h key
+//                          (rails_scores_group_max) -- the exact fallback where one group owns the head of the ranking; bounded from above
+//                          by the previous round's table, round t leaves every group's (t + 1)-th best eligible item
+//                          (rails_scores_group_next) -- the fallback of a quota
 //   topk_keys_kernel       the k largest keys of every row of that table, by MSD radix selection, decoded (rails_topk_keys)
 // The kernels see DENSE group ranks (int32 in [0, G), every ungrouped item a rank of its own), never the callers' sparse keys.
 #include "mol_kernels.h"
+#include "ranked_list.h"
 #include "score_rows.h"
 #include "topk_keys.h"
 #include "wave_ops.h"
@@ -17,7 +18,6 @@ namespace mol {
 
 constexpr int kCollapseThreads = kSortThreads;       // 1024: the in-LDS sorts' workgroup
 constexpr int kCollapseMaxDepth = 16384;             // entries of one ranked list: what lds_sort_desc sorts
-constexpr int kSeenTile = 256;                       // seen ids held in LDS at a time
 
 // ---- the walk ----------------------------------------------------------------------------------------------------
 // Entry j of a row is ELIGIBLE iff its position is one of the corpus, its score is above -inf (what the masks write) and its id is not in
@@ -48,20 +48,7 @@ __global__ __launch_bounds__(kCollapseThreads) void collapse_walk_kernel(
     const int64_t p = prow[j];
     surv[j] = (p >= 0 && p < n_items && srow[j] > -INFINITY) ? 1 : 0;
   }
-  for (int w0 = 0; w0 < width; w0 += kSeenTile) {       // the seen-id filter, a tile of the row's seen ids at a time
-    const int wn = width - w0 < kSeenTile ? width - w0 : kSeenTile;
-    __syncthreads();
-    if (tid < wn) seen[tid] = invalid[(int64_t)row * width + w0 + tid];
-    __syncthreads();
-    for (int j = tid; j < depth; j += kCollapseThreads) {
-      if (!surv[j]) continue;
-      const int64_t p = prow[j];
-      const int64_t id = ids != nullptr ? ids[p] : p;
-      bool hit = false;
-      for (int w = 0; w < wn; ++w) hit |= (seen[w] == id);
-      if (hit) surv[j] = 0;
-    }
-  }
+  drop_seen<kCollapseThreads>(surv, depth, [&](int j) { return prow[j]; }, ids, invalid + (int64_t)row * width, width, seen);
   __syncthreads();
   for (int j = tid; j < npad; j += kCollapseThreads) {
     unsigned long long kv = 0ull;
@@ -92,26 +79,19 @@ __global__ __launch_bounds__(kCollapseThreads) void collapse_walk_kernel(
     }
   }
   __syncthreads();
-  // the first k survivors in list order: a contiguous segment of the list per thread
-  const int seg = (depth + kCollapseThreads - 1) / kCollapseThreads;
-  const int s0 = tid * seg < depth ? tid * seg : depth, s1 = s0 + seg < depth ? s0 + seg : depth;
-  int c = 0;
-  for (int j = s0; j < s1; ++j) c += surv[j];
-  int total;
-  int o = block_scan_excl<kCollapseThreads>(c, wave_tot, total);
-  for (int j = s0; j < s1 && o < k; ++j) {
-    if (!surv[j]) continue;
-    const int64_t p = prow[j];
-    out_scores[(int64_t)row * k + o] = srow[j];
-    out_pos[(int64_t)row * k + o] = p;
-    out_ids[(int64_t)row * k + o] = ids != nullptr ? ids[p] : p;
-    ++o;
-  }
-  for (int e = total + tid; e < k; e += kCollapseThreads) {      // a short row: the rest is empty
-    out_scores[(int64_t)row * k + e] = -INFINITY;
-    out_pos[(int64_t)row * k + e] = -1;
-    out_ids[(int64_t)row * k + e] = -1;
-  }
+  const int total = emit_first_k<kCollapseThreads>(
+      surv, depth, k, wave_tot,
+      [&](int j, int o) {
+        const int64_t p = prow[j];
+        out_scores[(int64_t)row * k + o] = srow[j];
+        out_pos[(int64_t)row * k + o] = p;
+        out_ids[(int64_t)row * k + o] = ids != nullptr ? ids[p] : p;
+      },
+      [&](int e) {
+        out_scores[(int64_t)row * k + e] = -INFINITY;
+        out_pos[(int64_t)row * k + e] = -1;
+        out_ids[(int64_t)row * k + e] = -1;
+      });
   if (tid == 0) {
     out_counts[row] = total;
     if (total < k) *out_of_range = 1;                   // every writer stores the same value
@@ -150,44 +130,14 @@ int topk_collapse(const float* scores, int64_t ld, const int64_t* positions, int
 // row's seen set: afterwards a group's slot holds the key of its best eligible item under (score desc, position asc), 0 where it has none.
 // A slot only grows, so an entry whose key does not beat a plain read of its slot is dropped before its id is looked up -- after the first
 // few items of a group, most are.  One workgroup per (chunk of kGroupMaxChunk columns, row); the row's seen ids sit in LDS.
+// The rounds of a quota's fallback bound the same pass from above: an entry enters table[row][r] only where the previous round's slot
+// below[row][r] is non-zero and its key lies BELOW that slot: round t then holds the key of every group's (t + 1)-th best eligible item, 0
+// once the group is exhausted.  below == NULL is round 0 (no bound: the group maxima themselves).  The table and the bound take their own
+// row strides, so the m rounds of a row lie side by side as one row of m * n_groups keys for topk_keys_kernel.
 constexpr int kGroupMaxThreads = 256;
 constexpr int kGroupMaxChunk = 4096;
 constexpr int kGroupMaxSeen = 4096;      // seen ids per row
 
-__global__ __launch_bounds__(kGroupMaxThreads) void group_max_kernel(const float* __restrict__ scores, int64_t ld, int64_t n, int64_t first_item,
-                                                                    const int32_t* __restrict__ ranks, int64_t n_groups,
-                                                                    unsigned long long* __restrict__ table, const int64_t* __restrict__ ids,
-                                                                    const int64_t* __restrict__ invalid, int width) {
-  extern __shared__ __attribute__((aligned(16))) unsigned long long gm_seen[];      // [width]
-  const int row = blockIdx.y, tid = threadIdx.x;
-  for (int w = tid; w < width; w += kGroupMaxThreads) gm_seen[w] = (unsigned long long)invalid[(int64_t)row * width + w];
-  __syncthreads();
-  const int64_t begin = (int64_t)blockIdx.x * kGroupMaxChunk;
-  const int64_t end = begin + kGroupMaxChunk < n ? begin + kGroupMaxChunk : n;
-  const float* srow = scores + (int64_t)row * ld;
-  unsigned long long* trow = table + (int64_t)row * n_groups;
-  for (int64_t x = begin + tid; x < end; x += kGroupMaxThreads) {
-    const float s = srow[x];
-    if (!(fabsf(s) < INFINITY)) continue;               // -inf (masked), +inf, NaN
-    const int64_t p = first_item + x;
-    const int32_t r = ranks[p];
-    if (r < 0 || r >= n_groups) continue;
-    const unsigned long long kv = make_key(s, (unsigned int)p);
-    if (kv <= __atomic_load_n(&trow[r], __ATOMIC_RELAXED)) continue;
-    if (width > 0) {
-      const unsigned long long id = (unsigned long long)(ids != nullptr ? ids[p] : p);
-      bool hit = false;
-      for (int w = 0; w < width; ++w) hit |= (gm_seen[w] == id);
-      if (hit) continue;
-    }
-    atomicMax(&trow[r], kv);
-  }
-}
-
-// The rounds of a quota's fallback.  The entries group_max_kernel considers, by the same tests; an entry enters table[row][r] only where the
-// previous round's slot below[row][r] is non-zero and its key lies BELOW that slot: round t then holds the key of every group's (t + 1)-th
-// best eligible item, 0 once the group is exhausted.  below == NULL is round 0 (no bound: group_max_kernel's result).  The table and the
-// bound take their own row strides, so the m rounds of a row lie side by side as one row of m * n_groups keys for topk_keys_kernel.
 __global__ __launch_bounds__(kGroupMaxThreads) void group_next_kernel(const float* __restrict__ scores, int64_t ld, int64_t n, int64_t first_item,
                                                                      const int32_t* __restrict__ ranks, int64_t n_groups,
                                                                      unsigned long long* __restrict__ table, int64_t table_stride,
@@ -216,39 +166,41 @@ __global__ __launch_bounds__(kGroupMaxThreads) void group_next_kernel(const floa
     if (kv <= __atomic_load_n(&trow[r], __ATOMIC_RELAXED)) continue;
     if (width > 0) {
       const unsigned long long id = (unsigned long long)(ids != nullptr ? ids[p] : p);
-      bool hit = false;
-      for (int w = 0; w < width; ++w) hit |= (gm_seen[w] == id);
-      if (hit) continue;
+      if (seen_id(gm_seen, width, id)) continue;
     }
     atomicMax(&trow[r], kv);
   }
 }
 
-int scores_group_next(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,
-                      unsigned long long* table, int64_t table_stride, const unsigned long long* below, int64_t below_stride, const int64_t* ids,
-                      const int64_t* invalid, int width, hipStream_t stream) {
-  if (rows <= 0 || n_groups <= 0 || n <= 0) return kOk;
-  if (width > kGroupMaxSeen) { set_error("scores_group_next: width = %d beyond %d seen ids per row", width, kGroupMaxSeen); return kErrUnsupported; }
-  if (first_item + n > 0xFFFFFFFFll) { set_error("scores_group_next: positions beyond 32 bits"); return kErrUnsupported; }
-  if (rows > 65535) { set_error("scores_group_next: more than 65 535 rows"); return kErrUnsupported; }
+// One pass of the kernel for either entry: `entry`'s limits, its clear of a contiguous table (rails_scores_group_max's clear_table), the launch.
+static int group_table_pass(const char* entry, const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks,
+                            int64_t n_groups, unsigned long long* table, int64_t table_stride, bool clear_table, const unsigned long long* below,
+                            int64_t below_stride, const int64_t* ids, const int64_t* invalid, int width, hipStream_t stream) {
+  if (width > kGroupMaxSeen) { set_error("%s: width = %d beyond %d seen ids per row", entry, width, kGroupMaxSeen); return kErrUnsupported; }
+  if (first_item + n > 0xFFFFFFFFll) { set_error("%s: positions beyond 32 bits", entry); return kErrUnsupported; }
+  if (rows > 65535) { set_error("%s: more than 65 535 rows", entry); return kErrUnsupported; }
+  if (clear_table && hipMemsetAsync(table, 0, sizeof(unsigned long long) * (size_t)rows * (size_t)n_groups, stream) != hipSuccess) return kErrLaunch;
+  if (n <= 0) return kOk;
   const unsigned int blocks = (unsigned int)((n + kGroupMaxChunk - 1) / kGroupMaxChunk);
   hipLaunchKernelGGL(group_next_kernel, dim3(blocks, rows), dim3(kGroupMaxThreads), sizeof(unsigned long long) * (size_t)width, stream, scores, ld, n,
                      first_item, ranks, n_groups, table, table_stride, below, below_stride, ids, invalid, width);
   return launched();
 }
 
+int scores_group_next(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,
+                      unsigned long long* table, int64_t table_stride, const unsigned long long* below, int64_t below_stride, const int64_t* ids,
+                      const int64_t* invalid, int width, hipStream_t stream) {
+  if (rows <= 0 || n_groups <= 0 || n <= 0) return kOk;
+  return group_table_pass("scores_group_next", scores, ld, rows, n, first_item, ranks, n_groups, table, table_stride, false, below, below_stride, ids,
+                          invalid, width, stream);
+}
+
+// Round 0 on a table of n_groups keys per row; an empty pass (n == 0) still clears.
 int scores_group_max(const float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const int32_t* ranks, int64_t n_groups,
                      unsigned long long* table, int clear_table, const int64_t* ids, const int64_t* invalid, int width, hipStream_t stream) {
   if (rows <= 0 || n_groups <= 0) return kOk;
-  if (width > kGroupMaxSeen) { set_error("scores_group_max: width = %d beyond %d seen ids per row", width, kGroupMaxSeen); return kErrUnsupported; }
-  if (first_item + n > 0xFFFFFFFFll) { set_error("scores_group_max: positions beyond 32 bits"); return kErrUnsupported; }
-  if (rows > 65535) { set_error("scores_group_max: more than 65 535 rows"); return kErrUnsupported; }
-  if (clear_table && hipMemsetAsync(table, 0, sizeof(unsigned long long) * (size_t)rows * (size_t)n_groups, stream) != hipSuccess) return kErrLaunch;
-  if (n <= 0) return kOk;
-  const unsigned int blocks = (unsigned int)((n + kGroupMaxChunk - 1) / kGroupMaxChunk);
-  hipLaunchKernelGGL(group_max_kernel, dim3(blocks, rows), dim3(kGroupMaxThreads), sizeof(unsigned long long) * (size_t)width, stream, scores, ld, n,
-                     first_item, ranks, n_groups, table, ids, invalid, width);
-  return launched();
+  return group_table_pass("scores_group_max", scores, ld, rows, n, first_item, ranks, n_groups, table, n_groups, clear_table != 0, nullptr, 0, ids, invalid,
+                          width, stream);
 }
 
 // ---- top-k of a key table -------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mol_kernels.h"
+#include "ranked_list.h"
 #include "score_rows.h"
 #include "topk_keys.h"
 #include "wave_ops.h"
@@ -34,7 +35,6 @@ typedef unsigned long long u64;
 constexpr int kThreads = kRowWalkThreads;
 constexpr int kIters = kRowWalkIters;
 constexpr int kListThreads = kSortThreads;
-constexpr int kListSeenTile = 256;      // seen ids held in LDS at a time
 
 enum : int { kFuseMax = RAILS_FUSE_MAX, kFuseSum = RAILS_FUSE_SUM, kFuseWeighted = 2 };
 
@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(kListThreads) topk_fuse_lists_kernel(const flo
                                                                       float* __restrict__ out_scores) {
   extern __shared__ __attribute__((aligned(16))) u64 keys[];
   unsigned char* surv = reinterpret_cast<unsigned char*>(keys + sort_slots);      // [look]
-  __shared__ int64_t seen[kListSeenTile];
+  __shared__ int64_t seen[kSeenTile];
   __shared__ int wave_tot[kListThreads / 64];
   const int tid = threadIdx.x;
   const int64_t u = blockIdx.x;
@@ -219,40 +219,20 @@ __global__ void __launch_bounds__(kListThreads) topk_fuse_lists_kernel(const flo
   lds_sort_desc(keys, npad);
 
   for (int i = tid; i < look; i += kListThreads) surv[i] = keys[i] != 0ull ? 1 : 0;
-  for (int w0 = 0; w0 < width; w0 += kListSeenTile) {      // the seen-id filter, a tile of the row's seen ids at a time
-    const int wn = width - w0 < kListSeenTile ? width - w0 : kListSeenTile;
-    __syncthreads();
-    if (tid < wn) seen[tid] = invalid[u * width + w0 + tid];
-    __syncthreads();
-    for (int i = tid; i < look; i += kListThreads) {
-      if (!surv[i]) continue;
-      const int64_t p = (int64_t)key_pos(keys[i]);
-      const int64_t id = ids != nullptr ? ids[p] : p;
-      bool hit = false;
-      for (int w = 0; w < wn; ++w) hit |= (seen[w] == id);
-      if (hit) surv[i] = 0;
-    }
-  }
+  drop_seen<kListThreads>(surv, look, [&](int i) { return (int64_t)key_pos(keys[i]); }, ids, invalid + u * width, width, seen);
   __syncthreads();
-  // the first k survivors in list order: a contiguous segment of the list per thread
-  const int seg = (look + kListThreads - 1) / kListThreads;
-  const int s0 = tid * seg < look ? tid * seg : look, s1 = s0 + seg < look ? s0 + seg : look;
-  int c = 0;
-  for (int i = s0; i < s1; ++i) c += surv[i];
-  int total;
-  int o = block_scan_excl<kListThreads>(c, wave_tot, total);
-  for (int i = s0; i < s1 && o < k; ++i) {
-    if (!surv[i]) continue;
-    const u64 kv = keys[i];
-    const int64_t p = (int64_t)key_pos(kv);
-    out_ids[u * k + o] = ids != nullptr ? ids[p] : p;
-    out_scores[u * k + o] = unorderable(key_score(kv));
-    ++o;
-  }
-  for (int e = total + tid; e < k; e += kListThreads) {      // a short row: the rest is empty
-    out_ids[u * k + e] = -1;
-    out_scores[u * k + e] = -INFINITY;
-  }
+  emit_first_k<kListThreads>(
+      surv, look, k, wave_tot,
+      [&](int i, int o) {
+        const u64 kv = keys[i];
+        const int64_t p = (int64_t)key_pos(kv);
+        out_ids[u * k + o] = ids != nullptr ? ids[p] : p;
+        out_scores[u * k + o] = unorderable(key_score(kv));
+      },
+      [&](int e) {
+        out_ids[u * k + e] = -1;
+        out_scores[u * k + e] = -INFINITY;
+      });
 }
 
 int topk_fuse_lists(const float* scores, int64_t ld, const int64_t* positions, int64_t rows_in, int depth, const int64_t* lims, int n_out, int max_segment,

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "mol_kernels.h"
+#include "ranked_list.h"
 #include "topk_keys.h"
 #include "wave_ops.h"
 
@@ -335,9 +336,7 @@ __device__ __forceinline__ void filter_from_lds(const int64_t* id_s, const float
   int64_t id = 0;
   if (tid < kp) {
     id = id_s[tid];
-    bool seen = false;
-    for (int w = 0; w < width; ++w) seen |= (inv_s[w] == id);
-    ok = seen ? 0 : 1;
+    ok = seen_id(inv_s, width, id) ? 0 : 1;
   }
   int total_ok;
   const int okc = block_scan_excl<NT>(ok, scratch, total_ok) + ok;      // not-seen candidates up to and including this one
@@ -1155,10 +1154,7 @@ __global__ __launch_bounds__(kFilterThreads) void filter_seen_kernel(const int64
   for (int i = threadIdx.x; i < width; i += kFilterThreads) inv[i] = invalid[(int64_t)row * width + i];
   __syncthreads();
   for (int j = threadIdx.x; j < k_prime; j += kFilterThreads) {
-    const int64_t id = ids[j];
-    bool seen = false;
-    for (int w = 0; w < width; ++w) seen |= (inv[w] == id);
-    ok[j] = seen ? 0 : 1;
+    ok[j] = seen_id(inv, width, ids[j]) ? 0 : 1;
   }
   __syncthreads();
   // contiguous segment per thread; exclusive prefix of not-seen counts over segments

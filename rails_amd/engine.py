@@ -2388,6 +2388,22 @@ def topk_collapse(scores: torch.Tensor, positions: torch.Tensor, ranks: torch.Te
     return out_s, out_p, out_i, counts
 
 
+def _group_table_args(scores: torch.Tensor, ranks: torch.Tensor, table: torch.Tensor, shape: str, first_item: int, ids: Optional[torch.Tensor],
+                      invalid_ids: Optional[torch.Tensor]):
+    """The argument check scores_group_max and scores_group_next share -> (rows, n, ids, seen ids, width); shape: the table's, for the message."""
+    _require_device(scores, "scores")
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError("scores must be a (rows, n) float32 matrix with unit column stride")
+    rows, n = scores.shape
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[0] != rows or not table.is_contiguous() or table.device != scores.device:
+        raise ValueError(f"table must be a contiguous {shape} int64 tensor on the scores' device")
+    if ranks.dtype != torch.int32 or ranks.dim() != 1 or ranks.device != scores.device or not ranks.is_contiguous() or ranks.numel() < first_item + n:
+        raise ValueError("ranks must be a contiguous int32 tensor of at least first_item + n entries on the scores' device")
+    if ids is not None:
+        ids = ids.to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
+    return (rows, n, ids) + _seen_arg(invalid_ids, rows, scores.device)
+
+
 def scores_group_next(scores: torch.Tensor, ranks: torch.Tensor, table: torch.Tensor, groups: int, round: int, first_item: int = 0,
                       ids: Optional[torch.Tensor] = None, invalid_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
     """In place on `table` ((rows, m * groups) int64, the m rounds of a row side by side, ZEROED by the caller): round `round` of the per-group
@@ -2395,19 +2411,9 @@ def scores_group_next(scores: torch.Tensor, ranks: torch.Tensor, table: torch.Te
     round t - 1, which must be complete (every chunk of the corpus); afterwards slot t * groups + r of a row holds the key of rank r's
     (t + 1)-th best eligible item, 0 where it has fewer."""
     lib = _lib.load()
-    _require_device(scores, "scores")
-    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
-        raise ValueError("scores must be a (rows, n) float32 matrix with unit column stride")
-    rows, n = scores.shape
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[0] != rows or not table.is_contiguous() or table.device != scores.device:
-        raise ValueError("table must be a contiguous (rows, m * groups) int64 tensor on the scores' device")
+    rows, n, ids, inv, width = _group_table_args(scores, ranks, table, "(rows, m * groups)", first_item, ids, invalid_ids)
     if groups < 1 or table.shape[1] % groups or not 0 <= round < table.shape[1] // groups:
         raise ValueError("table must hold whole rounds of `groups` keys per row, `round` one of them")
-    if ranks.dtype != torch.int32 or ranks.dim() != 1 or ranks.device != scores.device or not ranks.is_contiguous() or ranks.numel() < first_item + n:
-        raise ValueError("ranks must be a contiguous int32 tensor of at least first_item + n entries on the scores' device")
-    if ids is not None:
-        ids = ids.to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
-    inv, width = _seen_arg(invalid_ids, rows, scores.device)
     stride = table.shape[1]
     here = C.c_void_p(table.data_ptr() + 8 * round * groups)
     below = C.c_void_p(table.data_ptr() + 8 * (round - 1) * groups if round else 0)
@@ -2422,17 +2428,7 @@ def scores_group_max(scores: torch.Tensor, ranks: torch.Tensor, table: torch.Ten
     """In place on `table` ((rows, G) int64 holding the 64-bit keys): the per-group maxima of the (rows, n) score matrix whose column x is
     item first_item + x (include/rails_amd.h rails_scores_group_max).  clear: zero the table first."""
     lib = _lib.load()
-    _require_device(scores, "scores")
-    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
-        raise ValueError("scores must be a (rows, n) float32 matrix with unit column stride")
-    rows, n = scores.shape
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[0] != rows or not table.is_contiguous() or table.device != scores.device:
-        raise ValueError("table must be a contiguous (rows, G) int64 tensor on the scores' device")
-    if ranks.dtype != torch.int32 or ranks.dim() != 1 or ranks.device != scores.device or not ranks.is_contiguous() or ranks.numel() < first_item + n:
-        raise ValueError("ranks must be a contiguous int32 tensor of at least first_item + n entries on the scores' device")
-    if ids is not None:
-        ids = ids.to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
-    inv, width = _seen_arg(invalid_ids, rows, scores.device)
+    rows, n, ids, inv, width = _group_table_args(scores, ranks, table, "(rows, G)", first_item, ids, invalid_ids)
     with _on_device(scores.device):
         _lib.check(lib.rails_scores_group_max(_ptr(scores), scores.stride(0), rows, n, int(first_item), _ptr(ranks), table.shape[1], _ptr(table),
                                               1 if clear else 0, _ptr(ids), _ptr(inv), width, _stream()), "rails_scores_group_max")

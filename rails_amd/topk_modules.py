@@ -2949,14 +2949,14 @@ def _collapsed_exact(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Op
 def _collapse_fallback(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], mask: Optional[E.ItemMask],
                        kw: dict, m: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """The exact fallback of a collapsed call: dense scores of the module's own precision, the call's mask written into them, their per-group
-    maxima as 64-bit keys (rails_scores_group_max, per corpus chunk under the logit policy, the seen-id filter inside) and the top-k of the
-    (B, G) key table (rails_topk_keys) -- a slice of the batch at a time where that table would exceed the same policy.  A row with fewer than k
-    non-empty groups is the RuntimeError of a call for more than there is.  mask: the call's resolved mask; kw: its other keyword arguments.
-    (k, m and the seen-id width were checked against the pass's limits by _collapsed_exact, before any launch.)
-    m > 1: the table is (B, m * G), round t of a row beside round t - 1 -- every group's (t + 1)-th best eligible item, by
-    rails_scores_group_next bounded by the finished round before it; rounds outermost, corpus chunks inside.  A corpus of one chunk is scored
-    once and read m times, a chunked one is scored again for every round (its pieces share a buffer).  Every key of the table is among its
-    group's best m and every item the quota keeps is in it, so its top-k is the answer."""
+    best m as 64-bit keys (rails_scores_group_next, per corpus chunk under the logit policy, the seen-id filter inside) and the top-k of the
+    (B, m * G) key table (rails_topk_keys) -- a slice of the batch at a time where that table would exceed the same policy.  A row with fewer
+    than k non-empty groups is the RuntimeError of a call for more than there is.  mask: the call's resolved mask; kw: its other keyword
+    arguments.  (k, m and the seen-id width were checked against the pass's limits by _collapsed_exact, before any launch.)
+    Round t of a row lies beside round t - 1 -- every group's (t + 1)-th best eligible item, bounded by the finished round before it; rounds
+    outermost, corpus chunks inside.  m = 1 is round 0 alone, the group maxima: one fill and one kernel per chunk.  A corpus of one chunk is
+    scored once and read m times, a chunked one is scored again for every round (its pieces share a buffer).  Every key of the table is among
+    its group's best m and every item the quota keeps is in it, so its top-k is the answer."""
     _collapse_count(tk, "fallbacks")
     B = query_embeddings.size(0)
     ranks, groups = tk._dense_group_ranks()
@@ -2967,24 +2967,17 @@ def _collapse_fallback(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: 
         part_kw = {key: (v[b0:b1] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for key, v in kw.items()}
         part_mask = mask if mask is None or mask.shared else mask.rows_slice(b0, b1)
         part_seen = None if invalid_ids is None else invalid_ids[b0:b1]
-        if m == 1:
-            table = torch.empty((b1 - b0, groups), dtype=torch.int64, device=query_embeddings.device)
-            first = True
-            for lo, logits in tk._own_score_chunks(query_embeddings[b0:b1], part_mask, **part_kw):
-                E.scores_group_max(logits, ranks, table, first_item=lo, clear=first, ids=tk._ids_flat, invalid_ids=part_seen)
-                first = False
-        else:
-            table = torch.zeros((b1 - b0, m * groups), dtype=torch.int64, device=query_embeddings.device)
-            only = None      # the one chunk of an unchunked corpus, kept for the later rounds
-            for t in range(m):
-                pieces = [only] if only is not None else tk._own_score_chunks(query_embeddings[b0:b1], part_mask, **part_kw)
-                n_pieces = 0
-                for lo, logits in pieces:
-                    E.scores_group_next(logits, ranks, table, groups, t, first_item=lo, ids=tk._ids_flat, invalid_ids=part_seen)
-                    n_pieces += 1
-                if t == 0 and n_pieces == 1:
-                    only = (lo, logits)
-            del only
+        table = torch.zeros((b1 - b0, m * groups), dtype=torch.int64, device=query_embeddings.device)
+        only = None      # the one chunk of an unchunked corpus, kept for the later rounds
+        for t in range(m):
+            pieces = [only] if only is not None else tk._own_score_chunks(query_embeddings[b0:b1], part_mask, **part_kw)
+            n_pieces = 0
+            for lo, logits in pieces:
+                E.scores_group_next(logits, ranks, table, groups, t, first_item=lo, ids=tk._ids_flat, invalid_ids=part_seen)
+                n_pieces += 1
+            if t == 0 and n_pieces == 1:
+                only = (lo, logits)
+        del only
         parts.append(E.topk_keys(table, k, tk._ids_flat))
     scores, ids, counts = (torch.cat([p[i] for p in parts], 0) for i in (0, 2, 3))
     if int(counts.min()) < k:      # (the one read-back of the fallback)

@@ -520,7 +520,11 @@ def test_walk_kernel_on_hand_built_lists(depth, k, dev):
     for name, ranks in layouts.items():
         first = torch.stack([ids[positions[r, : min(depth, 40)]] for r in range(rows)])      # seen ids hit the first occurrences
         pad = torch.full((rows, 40 - first.shape[1]), -3, dtype=torch.int64)
-        for invalid in (None, torch.cat([first, pad], dim=1)[:, torch.randperm(40, generator=g)], torch.cat([first, pad, pad, pad, pad, pad, pad, pad], dim=1)):
+        seen_layouts = [None, torch.cat([first, pad], dim=1)[:, torch.randperm(40, generator=g)], torch.cat([first, pad, pad, pad, pad, pad, pad, pad], dim=1)]
+        if depth >= 64:      # 600 seen ids: every hit in the second tile of 256, a third tile read (ids are 2 mod 5: 3 mod 5 is nobody's)
+            absent = (torch.arange(560) * 5 + 3).expand(rows, 560)
+            seen_layouts.append(torch.cat([absent[:, :300], first, absent[:, 300:]], dim=1))
+        for invalid in seen_layouts:
             s, p, i, counts, flag = walk(scores, positions, ranks, k, ids, invalid, dev)
             short = False
             for r in range(rows):

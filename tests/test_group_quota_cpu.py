@@ -330,7 +330,7 @@ def test_kernel_resources():
     # (no skip: the library this suite runs was built from these objects by build(), with these tools; a tree without them is not checked)
     assert os.path.exists(os.path.join(llvm, "llvm-readelf")) and os.path.exists(os.path.join(llvm, "clang-offload-bundler")), "LLVM tools of ROCm not found"
     assert os.path.exists(os.path.join(ROOT, "rails_amd", "csrc", "collapse.o")), "objects not built (python -c 'import __graft_entry__ as g; g.build()')"
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), "collapse_walk_kernel|group_next_kernel|group_max_kernel"],
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), "collapse_walk_kernel|group_next_kernel"],
                          capture_output=True, text=True, timeout=600).stdout
     rows = {}
     for line in out.splitlines():
@@ -338,11 +338,11 @@ def test_kernel_resources():
         if m:
             name = re.search(r"(\w+(?:<\w+>)?)\(", m.group(6)).group(1)
             rows[name] = {"vgpr": int(m.group(1)), "scratch": int(m.group(4)), "lds": int(m.group(5))}
-    table = {"collapse_walk_kernel<true>": 128, "collapse_walk_kernel<false>": 128, "group_next_kernel": 64, "group_max_kernel": 64}      # VGPR ceilings
+    table = {"collapse_walk_kernel<true>": 128, "collapse_walk_kernel<false>": 128, "group_next_kernel": 64}      # VGPR ceilings
     assert sorted(rows) == sorted(table), out[-2000:]
     for name, vgpr in table.items():
         assert rows[name]["scratch"] == 0 and rows[name]["vgpr"] <= vgpr, (name, rows[name])
     assert rows["collapse_walk_kernel<true>"]["lds"] == rows["collapse_walk_kernel<false>"]["lds"]
-    assert rows["group_next_kernel"]["lds"] == 0      # (the seen ids: dynamic, as in group_max_kernel)
+    assert rows["group_next_kernel"]["lds"] == 0      # (the seen ids are dynamic LDS)
     src = open(os.path.join(ROOT, "rails_amd", "csrc", "collapse.hip")).read()
     assert "block_scan_max_excl<kCollapseThreads>" in src and "collapse_walk_kernel<true>" in src and "collapse_walk_kernel<false>" in src

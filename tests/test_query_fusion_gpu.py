@@ -159,6 +159,7 @@ def test_topk_fuse_lists_against_the_reference(m, depth, dev):
     everything = np.arange(N_LIST)
     w = min(61, depth // 2)
     k = depth - w
+    absent = np.broadcast_to(np.arange(1, 601, dtype=np.int64) * 3, (3, 600))      # ids are 1 mod 3: these are nobody's
     # no duplicates: disjoint pools -- every entry a duplicate: one pool of exactly `depth` positions -- overlapping pools
     disjoint = [np.arange(r * depth, (r + 1) * depth) for r in range(rows)]
     one_pool = [np.arange(100, 100 + depth)] * rows
@@ -170,6 +171,8 @@ def test_topk_fuse_lists_against_the_reference(m, depth, dev):
         # seen ids: every row's best items (a best copy's item leaves altogether: its other copies must not surface), one nobody has, a repeat
         seen = np.concatenate([top[:, : w - 2], np.full((3, 1), -5), top[:, :1]], axis=1)
         check_lists(scores, pos, lims, k, ids, seen, dev, f"{what}, seen ids")
+        if (m, depth) == (8, 256):      # 600 seen ids: every hit in the second tile of 256, a third tile read
+            check_lists(scores, pos, lims, k, ids, np.concatenate([absent[:, :300], top[:, : w - 2], absent[:, 300 : 602 - w]], axis=1), dev, f"{what}, 600 seen ids")
     # padding: the tail of every list is (-inf, a real position) or (a score, -1); a position outside the corpus is skipped too
     scores, pos = sorted_lists(rng, rows, depth, overlapping)
     scores[:, depth // 2 :: 2] = -np.inf
@@ -181,6 +184,11 @@ def test_topk_fuse_lists_against_the_reference(m, depth, dev):
     seen = ids[np.arange(100, 100 + w)][None].repeat(3, 0)
     got = check_lists(scores, pos, lims, min(512, depth), ids, seen, dev, "fewer than k survivors")
     assert (got[:, depth - w :] == -1).all() and (got[:, : depth - w] >= 0).all()
+    if (m, depth) == (8, 256):      # k = 512 against 600 seen ids whose 280 hits (second and third tile) leave every row short of k
+        scores, pos = sorted_lists(rng, rows, depth, overlapping)      # (at most 3 * depth = 768 items in a fused row)
+        top = check_lists(scores, pos, lims, 512, ids, None, dev, "k = 512, no seen ids")
+        got = check_lists(scores, pos, lims, 512, ids, np.concatenate([absent[:, :300], top[:, :280], absent[:, 300:320]], axis=1), dev, "k = 512, 600 seen ids")
+        assert (got[:, 768 - 280 :] == -1).all() and (got[:, 0] >= 0).any()
 
 
 def test_topk_fuse_lists_limits(dev):
