@@ -57,6 +57,8 @@ extern "C" {
  * and the softmax entries rails_scores_lse[_workspace_bytes] / rails_scores_log_prob / rails_scores_gumbel
  * and the range-search entries rails_scores_range_workspace_bytes / rails_scores_range_count / _write / _sort / _decode
  * and the query-fusion entries rails_scores_fuse_rows / rails_topk_fuse_lists
+ * and the multi-row SASRec decode step rails_sasrec_decode_rows / RAILS_SASREC_DECODE_MAX_ROWS (rails_sasrec_decode is its max_new = 1 call,
+ * bit for bit what it was)
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -1168,6 +1170,22 @@ int rails_sasrec_decode(const float* embeddings, const int64_t* ids, const int64
                         const rails_sasrec_decode_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int32_t dim,
                         int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* work, float* out,
                         void* stream);
+/* Several rows per sequence in one step: the last m_b rows of sequence b, positions lengths[b] - m_b .. lengths[b] - 1, are
+ * re-encoded in order through all blocks and their k / v written to those cache rows in place; every other cache row keeps its
+ * bits.  Appending m_b events (lengths grew by m_b) and editing an interior row (lengths unchanged, the rows from the edited one on
+ * re-encoded) are the same call.  new_counts: device int64 (batch), or NULL for m_b = max_new everywhere; a count is clamped on the
+ * device into [1, min(max_new, lengths[b])].  embeddings / ids are read at the new rows only; out (batch, dim) is the postprocessed
+ * row lengths[b] - 1.  The step runs batch * max_new work-row slots (slot b * max_new + t is idle when t >= m_b): work holds
+ * rails_sasrec_decode_workspace_floats(batch * max_new, dim, ffn_dim) floats, and still 5 * n_blocks + 1 launches.  A row's
+ * arithmetic does not depend on its slot: the step is bit for bit max_new calls of rails_sasrec_decode at growing lengths, and
+ * rails_sasrec_decode is the max_new = 1, NULL-counts call.  RAILS_ENOTSUP with a message: max_new outside [1, seq_len], or
+ * batch * max_new > RAILS_SASREC_DECODE_MAX_ROWS (checked before any launch; the only limit on the batch, at any head count:
+ * the step's attention launch has its work rows on grid.x and the heads on grid.y). */
+#define RAILS_SASREC_DECODE_MAX_ROWS 2097120   /* 65535 launch-grid rows of 32 work rows */
+int rails_sasrec_decode_rows(const float* embeddings, const int64_t* ids, const int64_t* lengths, const int64_t* new_counts, int32_t max_new,
+                             const float* pos_emb, const rails_sasrec_decode_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len,
+                             int32_t dim, int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* work,
+                             float* out, void* stream);
 /* out[r] = normalise(x[row_index ? row_index[r] : r]); mode 0 LayerNorm (no affine), 1 x / max(||x||, eps).
  * output_postprocessors.py:38-85 + get_current_embeddings (modeling/sequential/utils.py:74-90). */
 int rails_rows_normalize(const float* x, int64_t ldx, const int64_t* row_index, int64_t rows, int32_t dim, int32_t mode, float eps,

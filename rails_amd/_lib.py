@@ -33,6 +33,7 @@ RAILS_ACT_NONE = 0
 RAILS_ACT_SILU = 1
 RAILS_ACT_RELU = 2
 RAILS_ACT_GELU = 3
+RAILS_SASREC_DECODE_MAX_ROWS = 65535 * 32
 
 _f32p = C.POINTER(C.c_float)
 
@@ -336,6 +337,9 @@ PROTOTYPES = {
     "rails_sasrec_decode_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "rails_sasrec_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rails_sasrec_decode_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     "rails_rows_normalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "rails_sort_rows_i64": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "rails_mask_sorted_duplicates": (

@@ -1773,39 +1773,64 @@ int64_t rails_sasrec_decode_workspace_floats(int32_t batch, int32_t dim, int32_t
   return batch < 0 || dim < 0 || ffn_dim < 0 ? 0 : sasrec_decode_workspace_floats(batch, dim, ffn_dim);
 }
 
-int rails_sasrec_decode(const float* embeddings, const int64_t* ids, const int64_t* lengths, const float* pos_emb,
-                        const rails_sasrec_decode_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int32_t dim,
-                        int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* work, float* out,
-                        void* stream) {
+static int sasrec_decode_entry(const char* name, const float* embeddings, const int64_t* ids, const int64_t* lengths, const int64_t* new_counts,
+                               int32_t max_new, const float* pos_emb, const rails_sasrec_decode_layer* layers, int32_t n_blocks, int32_t batch,
+                               int32_t seq_len, int32_t dim, int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps,
+                               float* work, float* out, void* stream) {
   g_err[0] = '\0';
   if (batch < 0 || n_blocks < 1 || seq_len <= 0 || dim <= 0 || heads <= 0 || ffn_dim <= 0) {
-    set_error("sasrec_decode: bad size (batch %d, n_blocks %d, seq_len %d, dim %d, heads %d, ffn_dim %d)", batch, n_blocks, seq_len, dim,
-              heads, ffn_dim);
+    set_error("%s: bad size (batch %d, n_blocks %d, seq_len %d, dim %d, heads %d, ffn_dim %d)", name, batch, n_blocks, seq_len, dim, heads,
+              ffn_dim);
     return RAILS_EINVAL;
   }
-  if (dim % heads != 0) { set_error("sasrec_decode: dim %d is not a multiple of heads %d", dim, heads); return RAILS_EINVAL; }
+  if (dim % heads != 0) { set_error("%s: dim %d is not a multiple of heads %d", name, dim, heads); return RAILS_EINVAL; }
   if ((ffn_act != RAILS_ACT_RELU && ffn_act != RAILS_ACT_GELU) || (postproc_mode != 0 && postproc_mode != 1)) {
-    set_error("sasrec_decode: bad ffn_act %d or postproc_mode %d", ffn_act, postproc_mode);
+    set_error("%s: bad ffn_act %d or postproc_mode %d", name, ffn_act, postproc_mode);
     return RAILS_EINVAL;
   }
   if (!sasrec_decode_supported(seq_len, dim, heads, ffn_dim)) {
-    set_error("sasrec_decode: seq_len %d, dim %d, heads %d, ffn_dim %d not supported (seq_len <= 2048, dim <= 1024, ffn_dim <= 1024, "
-              "head_dim <= 64)", seq_len, dim, heads, ffn_dim);
+    set_error("%s: seq_len %d, dim %d, heads %d, ffn_dim %d not supported (seq_len <= 2048, dim <= 1024, ffn_dim <= 1024, "
+              "head_dim <= 64)", name, seq_len, dim, heads, ffn_dim);
+    return RAILS_ENOTSUP;
+  }
+  if (max_new < 1 || max_new > seq_len) {
+    set_error("%s: max_new %d not supported (1 <= max_new <= seq_len %d)", name, max_new, seq_len);
+    return RAILS_ENOTSUP;
+  }
+  if ((int64_t)batch * max_new > RAILS_SASREC_DECODE_MAX_ROWS) {
+    set_error("%s: batch %d x max_new %d = %lld work rows not supported (at most %d per step)", name, batch, max_new,
+              (long long)batch * max_new, RAILS_SASREC_DECODE_MAX_ROWS);
     return RAILS_ENOTSUP;
   }
   if (batch == 0) return RAILS_OK;
-  if (!embeddings || !ids || !lengths || !pos_emb || !layers || !work || !out) { set_error("sasrec_decode: NULL pointer"); return RAILS_EINVAL; }
+  if (!embeddings || !ids || !lengths || !pos_emb || !layers || !work || !out) { set_error("%s: NULL pointer", name); return RAILS_EINVAL; }
   for (int i = 0; i < n_blocks; ++i) {
     const rails_sasrec_decode_layer& L = layers[i];
     if (!L.in_proj_weight || !L.in_proj_bias || !L.out_proj_weight || !L.out_proj_bias || !L.conv1_weight || !L.conv1_bias ||
         !L.conv2_weight || !L.conv2_bias || !L.k || !L.v) {
-      set_error("sasrec_decode: NULL pointer in layers[%d]", i);
+      set_error("%s: NULL pointer in layers[%d]", name, i);
       return RAILS_EINVAL;
     }
   }
-  const int r = sasrec_decode(embeddings, ids, lengths, pos_emb, layers, n_blocks, batch, seq_len, dim, heads, ffn_dim, ffn_act,
-                              postproc_mode, eps, work, out, (hipStream_t)stream);
-  return r == kOk ? r : fail(r, "sasrec_decode");
+  const int r = sasrec_decode(embeddings, ids, lengths, new_counts, max_new, pos_emb, layers, n_blocks, batch, seq_len, dim, heads, ffn_dim,
+                              ffn_act, postproc_mode, eps, work, out, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, name);
+}
+
+int rails_sasrec_decode(const float* embeddings, const int64_t* ids, const int64_t* lengths, const float* pos_emb,
+                        const rails_sasrec_decode_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int32_t dim,
+                        int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* work, float* out,
+                        void* stream) {
+  return sasrec_decode_entry("sasrec_decode", embeddings, ids, lengths, nullptr, 1, pos_emb, layers, n_blocks, batch, seq_len, dim, heads,
+                             ffn_dim, ffn_act, postproc_mode, eps, work, out, stream);
+}
+
+int rails_sasrec_decode_rows(const float* embeddings, const int64_t* ids, const int64_t* lengths, const int64_t* new_counts, int32_t max_new,
+                             const float* pos_emb, const rails_sasrec_decode_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len,
+                             int32_t dim, int32_t heads, int32_t ffn_dim, int32_t ffn_act, int32_t postproc_mode, float eps, float* work,
+                             float* out, void* stream) {
+  return sasrec_decode_entry("sasrec_decode_rows", embeddings, ids, lengths, new_counts, max_new, pos_emb, layers, n_blocks, batch, seq_len,
+                             dim, heads, ffn_dim, ffn_act, postproc_mode, eps, work, out, stream);
 }
 
 int rails_rows_normalize(const float* x, int64_t ldx, const int64_t* row_index, int64_t rows, int32_t dim, int32_t mode, float eps,

@@ -1,5 +1,21 @@
-// SASRec cached incremental decoding (rails_sasrec_decode): one new row per sequence, p = lengths[b] - 1, re-encoded through every
-// block against the key / value rows 0..p-1 held in a per-block cache (batch, seq_len, dim), which gains row p in place.
+// SASRec cached incremental decoding (rails_sasrec_decode[_rows]): the last m_b rows of every sequence, p = lengths[b] - m_b ..
+// lengths[b] - 1 (one row, m_b = 1, in rails_sasrec_decode), re-encoded through every block against the key / value rows below them
+// held in a per-block cache (batch, seq_len, dim), which gains those rows in place.
+//
+// A WORK ROW is a (sequence, position) pair in one of B * M fixed slots (M = max_new): slot r = b * M + t is active iff t < m_b and
+// stands for position p_r = lengths[b] - m_b + t (dec_row).  m_b = counts[b] (M when there is no count array), clamped on the device
+// into [1, min(M, lengths[b])] like the lengths themselves.  An inactive slot stages zeros and writes nothing; its attention workgroup
+// exits at once.  All new k / v rows of a block are written by the launch in front of that block's attention launch, and each row's own
+// key limit j <= p_r keeps the new rows causal among themselves.  A row's arithmetic does not depend on its slot, so one step over m
+// rows is bit for bit m single-row steps.
+//
+// Two sets of kernels.  kvdec_*: the single-row step, one row per sequence (row b is sequence b at lengths[b] - 1), kept as it was
+// before the slot scheme, source, argument block and launch grids, so that it compiles to the instructions it has always had (the
+// same bodies with the slot arithmetic folded in, even behind a compile-time switch, cost it 2-3 % at B = 32).  kvslot_*: the slot
+// scheme, the same arithmetic row for row, used when max_new > 1 (or the batch is beyond the 65 535 of the single-row attention
+// grid's y); each row tile first resolves its 32 slots into an LDS table (sequence, position or -1), once, which staging, stores
+// and epilogue read.  A change to the arithmetic of one set belongs in the other too: tests/test_sasrec_append_gpu.py holds them
+// bit-equal.
 //
 // SASRec's attention is strictly causal and its only other mask is the per-row id mask, so row p of every block depends on rows
 // 0..p of that block's input alone: the cached K / V of the rows below p are exactly what a full encode would compute there, and
@@ -12,7 +28,7 @@
 // workgroups (64 columns each) so that a weight is read once per 32 rows, never once per sequence:
 //   kvdec_rows_kernel<0>  LN1 + the in-projection (block 0: the embedding / position preprocessor first); q to the work rows, k / v
 //                         into cache row p; column tile 0 also stores Q (and block 0's x)
-//   kvdec_attn_kernel     one workgroup per (head, sequence): scores of keys 0..p, softmax, the weighted sum of values
+//   kvdec_attn_kernel     one workgroup per (work row, head): scores of keys 0..p, softmax, the weighted sum of values
 //   kvdec_rows_kernel<1>  y = Q + a W_o^T + b_o
 //   kvdec_rows_kernel<2>  z = LN2(y) in LDS, h = act(z W_1^T + b_1); column tile 0 stores z
 //   kvdec_rows_kernel<3>  x = (h W_2^T + b_2 + z) * (id != 0)
@@ -40,6 +56,12 @@ constexpr int kDecMaxDim = 1024;       // D and F: the staged A tile is kDecRows
 constexpr int kStageBatch = 8;         // global loads in flight per thread while the A rows are staged
 constexpr int kDecKBatch = 64;         // weights of a lane's row loaded ahead of their FMAs (16 float4)
 constexpr int kDecVBatch = 8;          // value rows in flight per lane in the attention's weighted sum
+constexpr int kDecMaxGridY = 65535;
+// work rows of one step: the row kernels put 32-slot tiles on grid.y; the slot attention kernel has its rows on grid.x (heads, at
+// most kDecMaxDim, on grid.y), where HIP wants grid.x * block size below 2^32
+constexpr int64_t kDecMaxSlots = RAILS_SASREC_DECODE_MAX_ROWS;
+static_assert(kDecMaxSlots == (int64_t)kDecMaxGridY * kDecRows, "rails_amd.h states the grid limit");
+static_assert(kDecMaxSlots * kDecThreads < (1LL << 32) && kDecMaxDim <= kDecMaxGridY, "the slot attention grid (work rows, heads)");
 
 struct KvDecArgs {
   const float* emb; const int64_t* ids; const int64_t* lengths; const float* pos_emb;   // (B, N, D), (B, N), (B), (>= N, D)
@@ -298,7 +320,305 @@ __global__ __launch_bounds__(64) void kvdec_post_kernel(const float* x, int D, i
   }
 }
 
-static size_t kvdec_rows_lds(int K) { return sizeof(float) * ((size_t)kDecRows * ((K + 3) & ~3) + 2 * kDecRows); }
+// ---- the slot scheme: the same kernels over (sequence, position) work rows ----------------------------------------------------
+struct KvSlotArgs : KvDecArgs {        // the slot scheme's additions, behind the single-row step's block
+  const int64_t* counts;               // (B) new rows per sequence, or null: M each
+  int M, R;                            // R = B * M work-row slots
+};
+
+struct DecRow { int b, p; bool active; };   // the sequence and position of a work-row slot
+
+__device__ __forceinline__ DecRow dec_row(const KvSlotArgs& a, int r) {
+  const int b = r / a.M, t = r - b * a.M;
+  const int len = dec_pos(a.lengths, b, a.N) + 1;
+  const int cap = a.M < len ? a.M : len;
+  const int64_t c = a.counts ? a.counts[b] : (int64_t)a.M;
+  const int m = c < 1 ? 1 : c > cap ? cap : (int)c;   // the same policy as dec_pos
+  return DecRow{b, len - m + t, t < m};
+}
+
+// kvdec_rows_kernel over work-row slots.  LDS: as there, then the tile's slot table: sequence and position [kDecRows] each, position
+// -1 for an inactive slot.
+template <int MODE, bool V4>
+__device__ __forceinline__ void kvslot_rows_body(const KvSlotArgs& a, float* dsm) {
+  const int D = a.D, N = a.N;
+  const int K = MODE == 3 ? a.F : D;
+  const int n_cols = MODE == 0 ? 3 * D : MODE == 2 ? a.F : D;
+  const int ks = (K + 3) & ~3;
+  float* As = dsm;
+  float* mean_s = As + kDecRows * ks;
+  float* rstd_s = mean_s + kDecRows;
+  int* slot_b = reinterpret_cast<int*>(rstd_s + kDecRows);
+  int* slot_p = slot_b + kDecRows;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r0 = blockIdx.y * kDecRows;
+  const int nr = a.R - r0 < kDecRows ? a.R - r0 : kDecRows;
+  const float emb_scale = sqrtf((float)D);
+  if (tid < kDecRows) {   // the tile's slots, resolved once
+    int b = -1, p = -1;
+    if (tid < nr) {
+      const DecRow w = dec_row(a, r0 + tid);
+      b = w.b;
+      p = w.active ? w.p : -1;
+    }
+    slot_b[tid] = b;
+    slot_p[tid] = p;
+  }
+  __syncthreads();
+  auto live = [&](int r) -> bool { return slot_p[r] >= 0; };                              // tile row r < nr
+  auto row_at = [&](int r) -> DecRow { return DecRow{slot_b[r], slot_p[r], true}; };      // of a live tile row
+
+  // ---- stage the A rows (zeros past K, past the last row and in inactive slots); kStageBatch global loads in flight per thread
+  auto load = [&](int i) -> float {
+    const int r = i / ks, k = i - r * ks;
+    if (r >= nr || k >= K) return 0.0f;
+    if (!live(r)) return 0.0f;
+    const int b = r0 + r;
+    if (MODE == 0) {
+      if (!a.first) return a.x[(int64_t)b * D + k];
+      const DecRow w = row_at(r);   // x = (emb * sqrt(D) + pos_emb[p]) * (id != 0), as rails_hstu_preprocess
+      return a.ids[(int64_t)w.b * N + w.p] != 0 ? a.emb[((int64_t)w.b * N + w.p) * D + k] * emb_scale + a.pos_emb[(int64_t)w.p * D + k] : 0.0f;
+    }
+    if (MODE == 1) return a.att[(int64_t)b * D + k];
+    if (MODE == 2) return a.y[(int64_t)b * D + k];
+    return a.h[(int64_t)b * a.F + k];
+  };
+  for (int i0 = tid; i0 < kDecRows * ks; i0 += kStageBatch * kDecThreads) {
+    float v[kStageBatch];
+#pragma unroll
+    for (int u = 0; u < kStageBatch; ++u) v[u] = i0 + u * kDecThreads < kDecRows * ks ? load(i0 + u * kDecThreads) : 0.0f;
+#pragma unroll
+    for (int u = 0; u < kStageBatch; ++u)
+      if (i0 + u * kDecThreads < kDecRows * ks) As[i0 + u * kDecThreads] = v[u];
+  }
+  __syncthreads();
+  if (MODE == 0 || MODE == 2) {   // LayerNorm statistics of each row, two-pass, a wave per row
+    for (int r = wave; r < kDecRows; r += kDecWaves) {
+      const float* row = As + r * ks;
+      float sm = 0.0f;
+      for (int k = lane; k < K; k += 64) sm += row[k];
+      const float mean = wave_sum(sm) / (float)K;
+      float vr = 0.0f;
+      for (int k = lane; k < K; k += 64) { const float c = row[k] - mean; vr = __builtin_fmaf(c, c, vr); }
+      vr = wave_sum(vr);
+      if (lane == 0) { mean_s[r] = mean; rstd_s[r] = 1.0f / sqrtf(vr / (float)K + kDecLnEps); }
+    }
+    __syncthreads();
+  }
+  if (MODE == 2) {   // z = LN(y) in place; column tile 0 keeps z for the FFN 2 residual
+    for (int i = tid; i < kDecRows * ks; i += kDecThreads) {
+      const int r = i / ks, k = i - r * ks;
+      if (k < K) {
+        const float zv = (As[i] - mean_s[r]) * rstd_s[r];
+        As[i] = zv;
+        if (blockIdx.x == 0 && r < nr && live(r)) a.z[(int64_t)(r0 + r) * D + k] = zv;
+      }
+    }
+    __syncthreads();
+  }
+  if (MODE == 0 && blockIdx.x == 0) {   // Q for the out-projection residual (and block 0's x, which no later kernel recomputes)
+    for (int i = tid; i < nr * ks; i += kDecThreads) {
+      const int r = i / ks, k = i - r * ks;
+      if (k < K && live(r)) {
+        a.qn[(int64_t)(r0 + r) * D + k] = (As[i] - mean_s[r]) * rstd_s[r];
+        if (a.first) a.x[(int64_t)(r0 + r) * D + k] = As[i];
+      }
+    }
+  }
+
+  const int col = blockIdx.x * kDecCols + lane;
+  if (col >= n_cols) return;   // no barrier follows
+  const int rw = wave * kDecRowsPerWave;   // this wave's rows of the tile
+  if (rw >= nr) return;
+  const float* wr = a.w + (int64_t)col * K;
+  float mu[kDecRowsPerWave], sc[kDecRowsPerWave];   // in-projection: the q columns normalise x on the fly, k / v take it as is
+#pragma unroll
+  for (int j = 0; j < kDecRowsPerWave; ++j) {
+    const bool qcol = MODE == 0 && col < D;
+    mu[j] = qcol ? mean_s[rw + j] : 0.0f;
+    sc[j] = qcol ? rstd_s[rw + j] : 1.0f;
+  }
+  float acc[kDecRowsPerWave][4];
+#pragma unroll
+  for (int j = 0; j < kDecRowsPerWave; ++j) acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0.0f;
+  for (int k0 = 0; k0 < K; k0 += kDecKBatch) {   // kDecKBatch weights of this lane's row in flight, then their FMAs
+    float4 wv[kDecKBatch / 4];
+#pragma unroll
+    for (int u = 0; u < kDecKBatch / 4; ++u) {
+      const int k = k0 + 4 * u;
+      if (V4) {
+        wv[u] = k < K ? *reinterpret_cast<const float4*>(wr + k) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      } else {
+        wv[u].x = k < K ? wr[k] : 0.0f;
+        wv[u].y = k + 1 < K ? wr[k + 1] : 0.0f;
+        wv[u].z = k + 2 < K ? wr[k + 2] : 0.0f;
+        wv[u].w = k + 3 < K ? wr[k + 3] : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kDecKBatch / 4; ++u) {
+      const int k = k0 + 4 * u;
+      if (k >= K) break;   // uniform; the A rows are zero-padded to a multiple of 4 only
+      const float4 w4 = wv[u];
+#pragma unroll
+      for (int j = 0; j < kDecRowsPerWave; ++j) {
+        float4 x4 = *reinterpret_cast<const float4*>(As + (rw + j) * ks + k);   // the same address in every lane: a broadcast
+        if (MODE == 0) {
+          x4.x = (x4.x - mu[j]) * sc[j];   // (x - 0) * 1 == x exactly on the k / v columns
+          x4.y = (x4.y - mu[j]) * sc[j];
+          x4.z = (x4.z - mu[j]) * sc[j];
+          x4.w = (x4.w - mu[j]) * sc[j];
+        }
+        acc[j][0] = __builtin_fmaf(x4.x, w4.x, acc[j][0]);
+        acc[j][1] = __builtin_fmaf(x4.y, w4.y, acc[j][1]);
+        acc[j][2] = __builtin_fmaf(x4.z, w4.z, acc[j][2]);
+        acc[j][3] = __builtin_fmaf(x4.w, w4.w, acc[j][3]);
+      }
+    }
+  }
+  const float bc = a.bias[col];
+#pragma unroll
+  for (int j = 0; j < kDecRowsPerWave; ++j) {
+    if (rw + j >= nr) break;
+    if (!live(rw + j)) continue;   // an inactive slot writes nothing, neither work rows nor the cache
+    const int b = r0 + rw + j;
+    const float v = ((acc[j][0] + acc[j][1]) + (acc[j][2] + acc[j][3])) + bc;
+    if (MODE == 0) {
+      if (col < D) {
+        a.q[(int64_t)b * D + col] = v;
+      } else {
+        const DecRow w = row_at(rw + j);
+        const int64_t crow = ((int64_t)w.b * N + w.p) * D;
+        if (col < 2 * D) a.kc[crow + col - D] = v;
+        else a.vc[crow + col - 2 * D] = v;
+      }
+    } else if (MODE == 1) {
+      a.y[(int64_t)b * D + col] = v + a.qn[(int64_t)b * D + col];
+    } else if (MODE == 2) {
+      a.h[(int64_t)b * a.F + col] = ffn_act(v, a.act);
+    } else {
+      const float o = v + a.z[(int64_t)b * D + col];
+      const DecRow w = row_at(rw + j);
+      a.x[(int64_t)b * D + col] = a.ids[(int64_t)w.b * N + w.p] != 0 ? o : 0.0f;
+    }
+  }
+}
+
+template <int MODE, bool V4>
+__global__ __launch_bounds__(kDecThreads) void kvslot_rows_kernel(KvSlotArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float dsm[];
+  kvslot_rows_body<MODE, V4>(a, dsm);
+}
+
+// One workgroup (4 waves) per (work row `row`, head): sequence b at position p.  Scores: a thread per key j <= p (the key row
+// straight from the cache, HD-unrolled with four partial sums), kept in LDS; the block's maximum and denominator by wave sums; the
+// output: a wave per key residue mod 4, a lane per output dimension (value rows read coalesced, 8 in flight), two partial sums per
+// lane, the four waves summed in a fixed order.
+template <int HD>
+__device__ __forceinline__ void kvslot_attn_body(const KvSlotArgs& a, int row, int head, int b, int p) {
+  __shared__ float sc[kDecMaxSeq];
+  __shared__ float qs[HD];
+  __shared__ float red[kDecWaves];
+  __shared__ float part[kDecWaves][HD];
+  const int N = a.N, D = a.D, hd = D / a.H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float scale = 1.0f / sqrtf((float)hd);
+  if (tid < HD) qs[tid] = tid < hd ? a.q[(int64_t)row * D + head * hd + tid] * scale : 0.0f;
+  __syncthreads();
+  const float* kbase = a.kc + (int64_t)b * N * D + head * hd;
+  const float* vbase = a.vc + (int64_t)b * N * D + head * hd;
+  float mx = -INFINITY;
+  for (int j = tid; j <= p; j += kDecThreads) {
+    const float* kr = kbase + (int64_t)j * D;
+    float s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int d = 0; d < HD; ++d)
+      if (d < hd) s4[d & 3] = __builtin_fmaf(qs[d], kr[d], s4[d & 3]);
+    const float s = ((s4[0] + s4[1]) + (s4[2] + s4[3])) * kLog2e;
+    sc[j] = s;
+    mx = fmaxf(mx, s);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));   // finite: key 0 exists
+  float l = 0.0f;
+  for (int j = tid; j <= p; j += kDecThreads) {
+    const float e = __builtin_amdgcn_exp2f(sc[j] - mx);
+    sc[j] = e;
+    l += e;
+  }
+  l = wave_sum(l);
+  __syncthreads();   // every red[] read above, every sc[] weight written
+  if (lane == 0) red[wave] = l;
+  __syncthreads();
+  const float denom = (red[0] + red[1]) + (red[2] + red[3]);
+  float o0 = 0.0f, o1 = 0.0f;
+  if (lane < hd) {
+    for (int j0 = wave; j0 <= p; j0 += kDecVBatch * kDecWaves) {
+      float vv[kDecVBatch];
+#pragma unroll
+      for (int u = 0; u < kDecVBatch; ++u) {
+        const int j = j0 + u * kDecWaves;
+        vv[u] = j <= p ? vbase[(int64_t)j * D + lane] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < kDecVBatch; ++u) {
+        const int j = j0 + u * kDecWaves;
+        if (j <= p) {
+          if (u & 1) o1 = __builtin_fmaf(sc[j], vv[u], o1);
+          else o0 = __builtin_fmaf(sc[j], vv[u], o0);
+        }
+      }
+    }
+  }
+  if (lane < HD) part[wave][lane] = o0 + o1;
+  __syncthreads();
+  if (tid < hd) {
+    const float o = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+    a.att[(int64_t)row * D + head * hd + tid] = o / denom;
+  }
+}
+
+// grid (work rows, heads); an inactive slot's workgroup exits at once
+template <int HD>
+__global__ __launch_bounds__(kDecThreads) void kvslot_attn_kernel(KvSlotArgs a) {
+  const int row = blockIdx.x, head = blockIdx.y;
+  const DecRow w = dec_row(a, row);
+  if (!w.active) return;   // uniform: before any barrier
+  kvslot_attn_body<HD>(a, row, head, w.b, w.p);
+}
+
+// the postprocessor of one row (one wave): LayerNorm without affine (mode 0) or x / max(||x||, eps) (mode 1)
+__device__ __forceinline__ void kvslot_post_row(const float* xr, int D, int mode, float eps, float* orow, int lane) {
+  if (mode == 0) {
+    float sm = 0.0f;
+    for (int k = lane; k < D; k += 64) sm += xr[k];
+    const float mean = wave_sum(sm) / (float)D;
+    float vr = 0.0f;
+    for (int k = lane; k < D; k += 64) { const float c = xr[k] - mean; vr = __builtin_fmaf(c, c, vr); }
+    const float rstd = 1.0f / sqrtf(wave_sum(vr) / (float)D + eps);
+    for (int k = lane; k < D; k += 64) orow[k] = (xr[k] - mean) * rstd;
+  } else {
+    float vr = 0.0f;
+    for (int k = lane; k < D; k += 64) vr = __builtin_fmaf(xr[k], xr[k], vr);
+    const float nrm = fmaxf(sqrtf(wave_sum(vr)), eps);
+    for (int k = lane; k < D; k += 64) orow[k] = xr[k] / nrm;
+  }
+}
+
+// sequence b's last new row: slot b * M + m_b - 1
+__global__ __launch_bounds__(64) void kvslot_post_kernel(KvSlotArgs a, int mode, float eps, float* out) {
+  const int b = blockIdx.x, D = a.D;
+  const int last = dec_pos(a.lengths, b, a.N) - dec_row(a, b * a.M).p;   // m_b - 1
+  kvslot_post_row(a.x + ((int64_t)b * a.M + last) * D, D, mode, eps, out + (int64_t)b * D, threadIdx.x);
+}
+
+static size_t kvdec_rows_lds(int K, bool slots) {
+  return sizeof(float) * ((size_t)kDecRows * ((K + 3) & ~3) + (slots ? 4 : 2) * kDecRows);
+}
 
 bool sasrec_decode_supported(int N, int D, int H, int F) {
   if (N < 1 || N > kDecMaxSeq || D < 1 || D > kDecMaxDim || F < 1 || F > kDecMaxDim || H < 1 || D % H != 0) return false;
@@ -307,51 +627,84 @@ bool sasrec_decode_supported(int N, int D, int H, int F) {
 
 int64_t sasrec_decode_workspace_floats(int B, int D, int F) { return (int64_t)B * (6 * (int64_t)D + F); }
 
-template <int MODE>
-static int launch_rows(const KvDecArgs& a, int K, int n_cols, hipStream_t stream) {
+template <int MODE, bool SLOTS, class Args>
+static int launch_rows(const Args& a, int K, int n_cols, hipStream_t stream) {
   const bool v4 = K % 4 == 0;
-  const void* fn = v4 ? reinterpret_cast<const void*>(&kvdec_rows_kernel<MODE, true>)
-                      : reinterpret_cast<const void*>(&kvdec_rows_kernel<MODE, false>);
+  const void* fn;
+  if constexpr (SLOTS) fn = v4 ? reinterpret_cast<const void*>(&kvslot_rows_kernel<MODE, true>) : reinterpret_cast<const void*>(&kvslot_rows_kernel<MODE, false>);
+  else fn = v4 ? reinterpret_cast<const void*>(&kvdec_rows_kernel<MODE, true>) : reinterpret_cast<const void*>(&kvdec_rows_kernel<MODE, false>);
   static DynLdsOnce once[2];
-  if (ensure_dyn_lds(once[v4 ? 1 : 0], fn, (int)kvdec_rows_lds(kDecMaxDim)) != kOk) return kErrLaunch;
-  const dim3 grid((n_cols + kDecCols - 1) / kDecCols, (a.B + kDecRows - 1) / kDecRows);
-  const size_t lds = kvdec_rows_lds(K);
-  if (v4) hipLaunchKernelGGL((kvdec_rows_kernel<MODE, true>), grid, dim3(kDecThreads), lds, stream, a);
-  else hipLaunchKernelGGL((kvdec_rows_kernel<MODE, false>), grid, dim3(kDecThreads), lds, stream, a);
+  if (ensure_dyn_lds(once[v4 ? 1 : 0], fn, (int)kvdec_rows_lds(kDecMaxDim, SLOTS)) != kOk) return kErrLaunch;
+  int rows;
+  if constexpr (SLOTS) rows = a.R;
+  else rows = a.B;
+  const dim3 grid((n_cols + kDecCols - 1) / kDecCols, (rows + kDecRows - 1) / kDecRows);
+  const size_t lds = kvdec_rows_lds(K, SLOTS);
+  if constexpr (SLOTS) {
+    if (v4) hipLaunchKernelGGL((kvslot_rows_kernel<MODE, true>), grid, dim3(kDecThreads), lds, stream, a);
+    else hipLaunchKernelGGL((kvslot_rows_kernel<MODE, false>), grid, dim3(kDecThreads), lds, stream, a);
+  } else {
+    if (v4) hipLaunchKernelGGL((kvdec_rows_kernel<MODE, true>), grid, dim3(kDecThreads), lds, stream, a);
+    else hipLaunchKernelGGL((kvdec_rows_kernel<MODE, false>), grid, dim3(kDecThreads), lds, stream, a);
+  }
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
-int sasrec_decode(const float* emb, const int64_t* ids, const int64_t* lengths, const float* pos_emb, const rails_sasrec_decode_layer* layers,
-                  int n_blocks, int B, int N, int D, int H, int F, int act, int mode, float eps, float* work, float* out, hipStream_t stream) {
-  if (B == 0) return kOk;
-  if (!sasrec_decode_supported(N, D, H, F)) { set_error("sasrec_decode: geometry not supported"); return kErrUnsupported; }
-  KvDecArgs a{};
-  a.emb = emb; a.ids = ids; a.lengths = lengths; a.pos_emb = pos_emb;
-  a.B = B; a.N = N; a.D = D; a.H = H; a.F = F; a.act = act;
-  const int64_t bd = (int64_t)B * D;
-  a.x = work; a.qn = work + bd; a.q = work + 2 * bd; a.att = work + 3 * bd; a.y = work + 4 * bd; a.z = work + 5 * bd; a.h = work + 6 * bd;
-  const int hd = D / H;
+// the 5 * n_blocks + 1 launches of one step
+template <bool SLOTS, class Args>
+static int decode_blocks(Args& a, const rails_sasrec_decode_layer* layers, int n_blocks, int mode, float eps, float* out, hipStream_t stream) {
+  const int D = a.D, H = a.H, F = a.F, hd = D / H;
   for (int i = 0; i < n_blocks; ++i) {
     const rails_sasrec_decode_layer& L = layers[i];
     a.first = i == 0;
     a.kc = L.k; a.vc = L.v;
     a.w = L.in_proj_weight; a.bias = L.in_proj_bias;
-    int r = launch_rows<0>(a, D, 3 * D, stream);
+    int r = launch_rows<0, SLOTS>(a, D, 3 * D, stream);
     if (r != kOk) return r;
-    const dim3 agrid(H, B);
-    if (hd <= 16) hipLaunchKernelGGL(kvdec_attn_kernel<16>, agrid, dim3(kDecThreads), 0, stream, a);
-    else if (hd <= 32) hipLaunchKernelGGL(kvdec_attn_kernel<32>, agrid, dim3(kDecThreads), 0, stream, a);
-    else hipLaunchKernelGGL(kvdec_attn_kernel<64>, agrid, dim3(kDecThreads), 0, stream, a);
+    if constexpr (SLOTS) {
+      const dim3 agrid(a.R, H);
+      if (hd <= 16) hipLaunchKernelGGL(kvslot_attn_kernel<16>, agrid, dim3(kDecThreads), 0, stream, a);
+      else if (hd <= 32) hipLaunchKernelGGL(kvslot_attn_kernel<32>, agrid, dim3(kDecThreads), 0, stream, a);
+      else hipLaunchKernelGGL(kvslot_attn_kernel<64>, agrid, dim3(kDecThreads), 0, stream, a);
+    } else {
+      const dim3 agrid(H, a.B);
+      if (hd <= 16) hipLaunchKernelGGL(kvdec_attn_kernel<16>, agrid, dim3(kDecThreads), 0, stream, a);
+      else if (hd <= 32) hipLaunchKernelGGL(kvdec_attn_kernel<32>, agrid, dim3(kDecThreads), 0, stream, a);
+      else hipLaunchKernelGGL(kvdec_attn_kernel<64>, agrid, dim3(kDecThreads), 0, stream, a);
+    }
     if (hipGetLastError() != hipSuccess) return kErrLaunch;
     a.w = L.out_proj_weight; a.bias = L.out_proj_bias;
-    if ((r = launch_rows<1>(a, D, D, stream)) != kOk) return r;
+    if ((r = launch_rows<1, SLOTS>(a, D, D, stream)) != kOk) return r;
     a.w = L.conv1_weight; a.bias = L.conv1_bias;
-    if ((r = launch_rows<2>(a, D, F, stream)) != kOk) return r;
+    if ((r = launch_rows<2, SLOTS>(a, D, F, stream)) != kOk) return r;
     a.w = L.conv2_weight; a.bias = L.conv2_bias;
-    if ((r = launch_rows<3>(a, F, D, stream)) != kOk) return r;
+    if ((r = launch_rows<3, SLOTS>(a, F, D, stream)) != kOk) return r;
   }
-  hipLaunchKernelGGL(kvdec_post_kernel, dim3(B), dim3(64), 0, stream, static_cast<const float*>(a.x), D, mode, eps, out);
+  if constexpr (SLOTS) hipLaunchKernelGGL(kvslot_post_kernel, dim3(a.B), dim3(64), 0, stream, a, mode, eps, out);
+  else hipLaunchKernelGGL(kvdec_post_kernel, dim3(a.B), dim3(64), 0, stream, static_cast<const float*>(a.x), D, mode, eps, out);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+int sasrec_decode(const float* emb, const int64_t* ids, const int64_t* lengths, const int64_t* counts, int M, const float* pos_emb,
+                  const rails_sasrec_decode_layer* layers, int n_blocks, int B, int N, int D, int H, int F, int act, int mode, float eps,
+                  float* work, float* out, hipStream_t stream) {
+  if (B == 0) return kOk;
+  if (!sasrec_decode_supported(N, D, H, F)) { set_error("sasrec_decode: geometry not supported"); return kErrUnsupported; }
+  if (M < 1 || M > N) { set_error("sasrec_decode: max_new %d outside [1, seq_len %d]", M, N); return kErrUnsupported; }
+  if ((int64_t)B * M > kDecMaxSlots) {
+    set_error("sasrec_decode: batch %d x max_new %d = %lld work rows, more than the %lld of one launch grid", B, M, (long long)B * M,
+              (long long)kDecMaxSlots);
+    return kErrUnsupported;
+  }
+  KvSlotArgs a{};
+  a.emb = emb; a.ids = ids; a.lengths = lengths; a.pos_emb = pos_emb;
+  a.B = B; a.N = N; a.D = D; a.H = H; a.F = F; a.act = act;
+  a.counts = counts; a.M = M; a.R = B * M;
+  const int64_t bd = (int64_t)a.R * D;
+  a.x = work; a.qn = work + bd; a.q = work + 2 * bd; a.att = work + 3 * bd; a.y = work + 4 * bd; a.z = work + 5 * bd; a.h = work + 6 * bd;
+  // one row per sequence: the single-row kernels (a count array can only say 1); their attention grid has the batch on y
+  if (M == 1 && B <= kDecMaxGridY) return decode_blocks<false>(static_cast<KvDecArgs&>(a), layers, n_blocks, mode, eps, out, stream);
+  return decode_blocks<true>(a, layers, n_blocks, mode, eps, out, stream);
 }
 
 }  // namespace mol

@@ -168,8 +168,10 @@ int sasrec_encode_fused(const float* emb, const int64_t* ids, const int64_t* len
 // ---- SASRec cached incremental decoding (kvdec.hip) ----
 bool sasrec_decode_supported(int N, int D, int H, int F);
 int64_t sasrec_decode_workspace_floats(int B, int D, int F);
-int sasrec_decode(const float* emb, const int64_t* ids, const int64_t* lengths, const float* pos_emb, const rails_sasrec_decode_layer* layers,
-                  int n_blocks, int B, int N, int D, int H, int F, int act, int mode, float eps, float* work, float* out, hipStream_t stream);
+// counts (B) or null, M = max_new: the last m_b rows of every sequence in B * M work-row slots (M = 1, null: the last row)
+int sasrec_decode(const float* emb, const int64_t* ids, const int64_t* lengths, const int64_t* counts, int M, const float* pos_emb,
+                  const rails_sasrec_decode_layer* layers, int n_blocks, int B, int N, int D, int H, int F, int act, int mode, float eps,
+                  float* work, float* out, hipStream_t stream);
 int select_keys(const unsigned long long* keys, int rows, int keys_per_row, int k, float* out_scores, int64_t* out_pos,
                 hipStream_t stream);
 int bf16_rows_kth(const unsigned short* rows16, int64_t ld, int n_rows, int n, int r, float* thr, hipStream_t stream);

@@ -13,7 +13,9 @@ rows of forward(), and a masked position is still a key of every later query (it
 Cached incremental decoding (encode with `cache=`): a prefill with return_cache_states=True also returns every
 block's key / value rows; a decode step re-encodes row lengths - 1 of every sequence against them in rails_sasrec_decode (5 launches
 per block over the whole batch) and writes that row's k / v into the cache in place.  The attention is strictly causal and the id
-mask is per row, so the step equals encode() of the updated sequence up to fp32 summation order.
+mask is per row, so the step equals encode() of the updated sequence up to fp32 summation order.  With `new_rows=` one step
+re-encodes the last m_b rows of every sequence (rails_sasrec_decode_rows, the same launches): an append of several events, or an
+edit of an interior row.
 
 Not supported (raises): training mode, CPU tensors.
 """
@@ -30,6 +32,7 @@ from .engine import _on_device, _ptr, _stream
 
 BLOCK_LN_EPS = 1e-8     # F.layer_norm(..., eps=1e-8) inside every block (sasrec.py:195-212)
 _ACT = {"relu": _lib.RAILS_ACT_RELU, "gelu": _lib.RAILS_ACT_GELU}
+_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
 
 
 class _MultiheadAttention(torch.nn.Module):
@@ -105,7 +108,7 @@ class SASRec(Encoder):
         return self._normalize(x, None).view(B, N, D)
 
     def encode(self, past_lengths, past_ids, past_embeddings, past_payloads: Optional[Dict[str, torch.Tensor]] = None, cache=None,
-               return_cache_states: bool = False):
+               return_cache_states: bool = False, new_rows=None, max_new_rows: Optional[int] = None):
         """(B, D): the postprocessed embedding at position past_lengths - 1 (modeling/sequential/utils.py:74-90).  Lengths follow
         the encoders' policy (Encoder._lengths): host lengths outside [1, N] raise, device lengths are clamped and
         counted (length_violations()).
@@ -114,9 +117,26 @@ class SASRec(Encoder):
         use_fused_kernel=False; cache[i] = (k, v), contiguous float32 (B, N, D): block i's in-projection key / value rows of its input.
         With a cache (decode step): row p = past_lengths - 1 of every sequence is re-encoded through every block against cache rows
         0..p-1 and its k / v written to cache row p in place (rows > p untouched); only past_ids / past_embeddings at row p are read.
-        Returns the (B, D) embedding of row p, or (emb, cache) with return_cache_states=True -- the same tensors, updated."""
+        Returns the (B, D) embedding of row p, or (emb, cache) with return_cache_states=True -- the same tensors, updated.
+
+        new_rows (with a cache only): several rows per sequence in the one step (rails_sasrec_decode_rows).  The last m_b rows of
+        sequence b, positions past_lengths[b] - m_b .. past_lengths[b] - 1, are re-encoded in order and cache rows
+        [len_b - m_b, len_b) written in place; every other cache row keeps its bits, only past_ids / past_embeddings at those rows
+        are read, and the result is still the (B, D) embedding at len_b - 1 -- bit for bit that of m_b single-row steps.  Two uses:
+          append -- past_lengths grew by m_b since the cache was last written (m_b = past_lengths[b] on an empty cache: a prefill);
+          edit from an interior row p -- past_lengths unchanged, new_rows = len_b - p: the rows from the edited one on are re-encoded.
+        new_rows is None (one row, the call above), an int m >= 1 (the last m rows of every sequence), or m_b per sequence as a list /
+        integer tensor (B,).  Counts on the HOST are validated there (1 <= m_b <= past_lengths[b] when the lengths are on the host
+        too; ValueError before anything is launched) and the step runs max(m_b) work-row slots per sequence, or max_new_rows when that
+        is given (no bit depends on it).  A DEVICE tensor needs max_new_rows=M, an int: its values are clamped on the device into
+        [1, min(M, len_b)] and the out-of-range ones counted in length_violations(), like lengths; nothing is read back unless
+        STRICT_DEVICE_LENGTHS is set."""
+        if cache is None and (new_rows is not None or max_new_rows is not None):
+            raise ValueError("new_rows / max_new_rows select the rows of a decode step: they need cache=")
+        if new_rows is None and max_new_rows is not None:
+            raise ValueError("max_new_rows sizes a new_rows= step: it needs new_rows=")
         if cache is not None:
-            out = self._decode(past_lengths, past_ids, past_embeddings, cache)
+            out = self._decode(past_lengths, past_ids, past_embeddings, cache, new_rows, max_new_rows)
             return (out, cache) if return_cache_states else out
         self._check(past_ids, past_embeddings, device=False)
         N = past_ids.shape[1]
@@ -223,9 +243,59 @@ class SASRec(Encoder):
                 if t.shape != (B, N, D):
                     raise ValueError(f"cache[{i}] {name} {tuple(t.shape)} must be ({B}, {N}, {D})")
 
-    def _decode(self, past_lengths, past_ids, past_embeddings, cache) -> torch.Tensor:
-        """One decode step (rails_sasrec_decode) -> (B, D); the cache is updated in place.  With device-resident lengths nothing
-        here reads the device."""
+    def _new_rows(self, new_rows, max_new_rows, past_lengths, lengths: torch.Tensor, B: int, N: int):
+        """(counts, M) of a multi-row step: counts an int64 device tensor (B,), or None for M rows of every sequence.  `lengths`:
+        _lengths' result (on the device, in range).  Counts on the host raise here when out of range; counts on the device are
+        counted, the kernels clamp them, and nothing is read back (unless STRICT_DEVICE_LENGTHS)."""
+        dev = lengths.device
+        if max_new_rows is not None and (isinstance(max_new_rows, bool) or not isinstance(max_new_rows, int) or not 1 <= max_new_rows <= N):
+            raise ValueError(f"max_new_rows must be an int in [1, {N}], got {max_new_rows!r}")
+        strict = type(self).STRICT_DEVICE_LENGTHS
+        if isinstance(new_rows, torch.Tensor) and new_rows.is_cuda:
+            if max_new_rows is None:
+                raise ValueError("new_rows on the device needs max_new_rows=M (an int): the number of work rows is a host-side launch size")
+            if new_rows.dtype not in _INT_DTYPES or new_rows.shape != (B,):
+                raise ValueError(f"new_rows must be an integer tensor of shape ({B},), got {new_rows.dtype} {tuple(new_rows.shape)}")
+            counts = new_rows.to(device=dev, dtype=torch.int64).contiguous()
+            bad = (counts < 1) | (counts > lengths.clamp(max=max_new_rows))
+            if strict:
+                if bool(bad.any()):
+                    raise ValueError(f"new_rows must lie in [1, min(max_new_rows, past_lengths)] (got min {int(counts.min())}, max {int(counts.max())})")
+            else:
+                self._count_violations(dev, bad.sum())
+            return counts, max_new_rows
+        uniform = isinstance(new_rows, int) and not isinstance(new_rows, bool)
+        if uniform:
+            counts = torch.full((B,), new_rows, dtype=torch.int64)
+        else:
+            try:
+                counts = torch.as_tensor(new_rows)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise ValueError(f"new_rows must be an int, or {B} ints as a list or tensor: {e}") from None
+            if counts.dtype not in _INT_DTYPES or counts.shape != (B,):
+                raise ValueError(f"new_rows must be an integer tensor of shape ({B},), got {counts.dtype} {tuple(counts.shape)}")
+            counts = counts.to(torch.int64)
+        top = int(counts.max()) if B else 1
+        if B and (int(counts.min()) < 1 or top > N):
+            raise ValueError(f"new_rows must lie in [1, past_lengths] (got min {int(counts.min())}, max {top}, seq_len {N})")
+        len_h = past_lengths.to(torch.int64) if not past_lengths.is_cuda else lengths.cpu() if strict else None
+        if len_h is not None and bool((counts > len_h).any()):
+            b = int((counts > len_h).nonzero()[0])
+            raise ValueError(f"new_rows must lie in [1, past_lengths]: sequence {b} has {int(counts[b])} new rows and length {int(len_h[b])}")
+        if max_new_rows is not None and max_new_rows < top:
+            raise ValueError(f"max_new_rows {max_new_rows} is less than the largest new_rows {top}")
+        M = top if max_new_rows is None else max_new_rows
+        if uniform and M == top:
+            counts = None
+        else:
+            counts = counts.to(dev)
+        if len_h is None:   # device lengths: a count past a sequence's length is clamped by the kernels, and counted here
+            self._count_violations(dev, (lengths < (top if counts is None else counts)).sum())
+        return counts, M
+
+    def _decode(self, past_lengths, past_ids, past_embeddings, cache, new_rows=None, max_new_rows: Optional[int] = None) -> torch.Tensor:
+        """One decode step (rails_sasrec_decode; rails_sasrec_decode_rows with new_rows) -> (B, D); the cache is updated in place.
+        With device-resident lengths (and counts) nothing here reads the device."""
         self._check(past_ids, past_embeddings)
         lib = _lib.load()
         B, N = past_ids.shape
@@ -236,6 +306,10 @@ class SASRec(Encoder):
         dev = past_embeddings.device
         self._check_cache(cache, B, N, dev)
         lengths = self._lengths(past_lengths, dev, N)
+        counts, M = (None, 1) if new_rows is None else self._new_rows(new_rows, max_new_rows, past_lengths, lengths, B, N)
+        if B * M > _lib.RAILS_SASREC_DECODE_MAX_ROWS:
+            raise NotImplementedError(f"a decode step runs at most {_lib.RAILS_SASREC_DECODE_MAX_ROWS} work rows (batch x max new rows), "
+                                      f"got {B} x {M}")
         keep = []   # fp32 copies must outlive the launches that read them
         f32 = self._f32(dev, keep)
         self._decode_ptrs = _lib.layer_table(_lib.SasrecDecodeLayer, [[f32(t) for t in p] + [k, v] for p, (k, v) in zip(self._block_params(), cache)],
@@ -243,10 +317,14 @@ class SASRec(Encoder):
         ids = past_ids.to(device=dev, dtype=torch.int64).contiguous()
         emb = f32(past_embeddings)
         pos = f32(self._input_features_preproc._pos_emb.weight)
-        work = torch.empty(lib.rails_sasrec_decode_workspace_floats(B, D, F), dtype=torch.float32, device=dev)
+        work = torch.empty(lib.rails_sasrec_decode_workspace_floats(B * M, D, F), dtype=torch.float32, device=dev)
         out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        tail = (self._decode_ptrs[1], self._num_blocks, B, N, D, H, F, _ACT[self._ffn_activation_fn], self._postproc_mode, C.c_float(self._eps),
+                _ptr(work), _ptr(out))
         with _on_device(dev):
-            _lib.check(lib.rails_sasrec_decode(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(pos), self._decode_ptrs[1], self._num_blocks, B, N, D, H,
-                                               F, _ACT[self._ffn_activation_fn], self._postproc_mode, C.c_float(self._eps), _ptr(work), _ptr(out),
-                                               _stream()), "rails_sasrec_decode")
+            if new_rows is None:
+                _lib.check(lib.rails_sasrec_decode(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(pos), *tail, _stream()), "rails_sasrec_decode")
+            else:
+                _lib.check(lib.rails_sasrec_decode_rows(_ptr(emb), _ptr(ids), _ptr(lengths), _ptr(counts) if counts is not None else None, M,
+                                                        _ptr(pos), *tail, _stream()), "rails_sasrec_decode_rows")
         return out
