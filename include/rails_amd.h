@@ -59,6 +59,7 @@ extern "C" {
  * and the query-fusion entries rails_scores_fuse_rows / rails_topk_fuse_lists
  * and the multi-row SASRec decode step rails_sasrec_decode_rows / RAILS_SASREC_DECODE_MAX_ROWS (rails_sasrec_decode is its max_new = 1 call,
  * bit for bit what it was)
+ * and the diversity entries rails_topk_mmr / rails_topk_mmr_workspace_bytes
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -825,6 +826,26 @@ int rails_scores_group_max(const float* scores, int64_t ld, int32_t rows, int64_
  * radix selection over rows of any length, one workgroup per row; k <= 512. */
 int rails_topk_keys(const uint64_t* table, int32_t rows, int64_t n_groups, int32_t k, const int64_t* ids, float* out_scores, int64_t* out_positions,
                     int64_t* out_ids, int32_t* out_counts, void* stream);
+
+/* ---- diversifying a ranked list by maximal marginal relevance (added under ABI 15; no counterpart in the reference) ------------------------
+ * Row b holds a ranked list of `depth` entries (scores[b * ld + j], positions[b * depth + j]).  Eligibility is rails_topk_collapse's: a position
+ * in [0, n_items), a score above -inf (NaN is not), an id -- ids[position], or the position itself where ids == NULL -- not among the row's
+ * `width` invalid_ids.  The POOL is the first `pool` eligible entries in list order, pool index c = 0 .. P - 1.  vectors: the (n_items, dim)
+ * row-major fp32 item vectors, finite.  All arithmetic is fp32, round to nearest, unfused:  mu = 1.0f - lam;  sim(a, b) = the chain
+ * acc = acc + a[e] * b[e], e = 0 .. dim - 1 ascending from acc = +0;  M[c] = +0 at first and fmaxf(M[c], sim(vec[c], vec[y])) after every pick
+ * y;  val[c] = lam * s[c] - mu * M[c].  Step t = 0 .. k - 1 picks the unpicked pool entry with the largest 64-bit key
+ * (orderable(val[c]) << 32) | ~c -- the largest val, ties to the smaller pool index.  Outputs in PICK order: the picked entries' own scores
+ * (not val: a row is not monotone), positions and ids, with (-inf, -1, -1) behind them where P < k.  out_counts[b] = P; *out_of_range (int32,
+ * device-visible, zeroed by the caller; may be pinned host memory) is set to 1 when some row has P < k.  One workgroup per row, one launch,
+ * no atomics: the result is a function of the inputs, bit for bit.  lam = 1 returns the first k eligible entries of a list in key order.
+ * 0 < lam <= 1 and k <= pool (RAILS_EINVAL otherwise); pool <= 1024, 1 <= dim <= 256, width <= 4096, 1 <= depth <= 16 384 (RAILS_ENOTSUP).
+ * workspace: rails_topk_mmr_workspace_bytes(rows, pool, dim) bytes, 0 for dim <= 64 (workspace may then be NULL); every limit is checked
+ * before any launch. */
+size_t rails_topk_mmr_workspace_bytes(int32_t rows, int32_t pool, int32_t dim);
+int rails_topk_mmr(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const float* vectors, int64_t n_items,
+                   int32_t dim, float lam, int32_t k, int32_t pool, const int64_t* ids, const int64_t* invalid_ids, int32_t width, void* workspace,
+                   size_t workspace_bytes, float* out_scores, int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range,
+                   void* stream);
 
 /* CandidateIndex.get_top_k_outputs' selection in ONE chain (reference indexing/candidate_index.py:149-175 after
  * rails/indexing/mol_top_k.py:123-130): exact top-k' of every row with the id map, then the seen-id filter of

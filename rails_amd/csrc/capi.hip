@@ -1352,6 +1352,33 @@ int rails_topk_collapse_quota(const float* scores, int64_t ld, const int64_t* po
                           max_per_group, out_scores, out_positions, out_ids, out_counts, out_of_range, stream);
 }
 
+// rails_topk_mmr: the arguments and every limit before anything else, so a refused call never launches (and needs no device).
+size_t rails_topk_mmr_workspace_bytes(int32_t rows, int32_t pool, int32_t dim) {
+  return rows > 0 && pool > 0 && dim > 0 ? mmr_workspace_bytes(rows, pool, dim) : 0;
+}
+
+int rails_topk_mmr(const float* scores, int64_t ld, const int64_t* positions, int32_t rows, int32_t depth, const float* vectors, int64_t n_items,
+                   int32_t dim, float lam, int32_t k, int32_t pool, const int64_t* ids, const int64_t* invalid_ids, int32_t width, void* workspace,
+                   size_t workspace_bytes, float* out_scores, int64_t* out_positions, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range,
+                   void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || depth < 0 || k < 0 || pool < 0 || width < 0 || n_items < 0) { set_error("topk_mmr: negative size"); return RAILS_EINVAL; }
+  if (!(lam > 0.0f && lam <= 1.0f)) { set_error("topk_mmr: lam = %g outside (0, 1]", (double)lam); return RAILS_EINVAL; }
+  if (k > pool) { set_error("topk_mmr: k = %d beyond pool = %d", k, pool); return RAILS_EINVAL; }
+  if (dim < 1) { set_error("topk_mmr: dim = %d below 1", dim); return RAILS_EINVAL; }
+  if (pool > 1024) { set_error("topk_mmr: pool = %d beyond 1024", pool); return RAILS_ENOTSUP; }
+  if (dim > 256) { set_error("topk_mmr: dim = %d beyond 256", dim); return RAILS_ENOTSUP; }
+  if (width > 4096) { set_error("topk_mmr: width = %d beyond 4096 seen ids per row", width); return RAILS_ENOTSUP; }
+  if (rows == 0 || k == 0) return RAILS_OK;
+  if (!scores || !positions || !vectors || !out_scores || !out_positions || !out_ids || !out_counts || !out_of_range || (width > 0 && !invalid_ids)) {
+    set_error("topk_mmr: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  if (ld < depth) { set_error("topk_mmr: ld < depth"); return RAILS_EINVAL; }
+  return fail(topk_mmr(scores, ld, positions, rows, depth, vectors, n_items, dim, lam, k, pool, ids, invalid_ids, width, workspace, workspace_bytes,
+                       out_scores, out_positions, out_ids, out_counts, out_of_range, (hipStream_t)stream), "topk_mmr");
+}
+
 // rails_scores_group_max and rails_scores_group_next: one check list under the called entry's name.  rounds: the next entry, whose empty pass
 // (n == 0) is nothing to do; the max entry's may still clear its table, and its strides and bound (n_groups, none) pass the round's checks.
 static int group_table_checked(const char* name, bool rounds, const float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item,

@@ -202,6 +202,12 @@ int scores_group_max(const float* scores, int64_t ld, int rows, int64_t n, int64
 int topk_keys(const unsigned long long* table, int rows, int64_t n_groups, int k, const int64_t* ids, float* out_scores, int64_t* out_pos,
               int64_t* out_ids, int32_t* out_counts, hipStream_t stream);
 
+// ---- diversifying a ranked list by maximal marginal relevance (mmr.hip) ----
+size_t mmr_workspace_bytes(int rows, int pool, int dim);
+int topk_mmr(const float* scores, int64_t ld, const int64_t* positions, int rows, int depth, const float* vectors, int64_t n_items, int dim,
+             float lam, int k, int pool, const int64_t* ids, const int64_t* invalid, int width, void* ws, size_t ws_bytes, float* out_scores,
+             int64_t* out_pos, int64_t* out_ids, int32_t* out_counts, int32_t* out_of_range, hipStream_t stream);
+
 // ---- IVF-Flat index over the item components (ivf.hip) ----
 int ivf_check(const Shape& s, int64_t n, int nlist, bool from_index);
 int ivf_components16(const Shape& s, const float* ipack, int64_t n, void* table, int64_t n_total, int64_t first, hipStream_t st);

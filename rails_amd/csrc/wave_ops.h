@@ -1,4 +1,4 @@
-// Sums and prefix sums over a 64-lane wave and over a workgroup, shared by topk.hip, collapse.hip, item_mask.hip, rank.hip and softmax.hip.
+// Sums and prefix sums over a 64-lane wave and over a workgroup, shared by topk.hip, collapse.hip, mmr.hip, item_mask.hip, rank.hip and softmax.hip.
 // Device-only; no atomics and no LDS of its own: the workgroup forms take their scratch from the caller.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,6 +11,17 @@ template <class T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// Maximum over the wave, returned to every lane (T: any type ordered by >; the 64-bit keys of topk_keys.h).  The same butterfly.
+template <class T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const T u = __shfl_xor(v, d, 64);
+    v = u > v ? u : v;
+  }
   return v;
 }
 

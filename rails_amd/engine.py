@@ -2340,6 +2340,9 @@ COLLAPSE_MAX_LIST = 16384      # entries of one ranked list rails_topk_collapse 
 COLLAPSE_MAX_K = 512           # rails_topk_keys' k
 COLLAPSE_MAX_SEEN = 4096       # rails_scores_group_max's seen ids per row
 COLLAPSE_MAX_PER_GROUP = 32    # results per group on the exact modules: their fallback reads the scores once per unit of it
+MMR_MAX_POOL = 1024            # pool entries of rails_topk_mmr: one thread of its workgroup each
+MMR_MAX_DIM = 256              # entries of an item vector
+MMR_MAX_MAGNITUDE = 2.0 ** 60  # of a vector's entries: no dot product of MMR_MAX_DIM terms overflows
 
 
 def _seen_arg(invalid_ids: Optional[torch.Tensor], rows: int, device) -> Tuple[Optional[torch.Tensor], int]:
@@ -2386,6 +2389,72 @@ def topk_collapse(scores: torch.Tensor, positions: torch.Tensor, ranks: torch.Te
         else:
             _lib.check(lib.rails_topk_collapse_quota(*lists, min(int(max_per_group), (1 << 31) - 1), *outs), "rails_topk_collapse_quota")
     return out_s, out_p, out_i, counts
+
+
+def topk_mmr(scores: torch.Tensor, positions: torch.Tensor, vectors: torch.Tensor, lam: float, k: int, pool: int, ids: Optional[torch.Tensor],
+             invalid_ids: Optional[torch.Tensor], word: torch.Tensor):
+    """The walk of a diversified top-k (include/rails_amd.h rails_topk_mmr): scores / positions (rows, L), a ranked list per
+    row; vectors the (N, E) fp32 item vectors -> (scores (rows, k), positions, ids, counts (rows,) int32) in PICK order -- the scores are the
+    picked items' own relevance scores, so a row is not monotone.  The pool is the first `pool` eligible entries of the list (a position of
+    the corpus, a score above -inf, an id not among the row's invalid_ids); counts: the pool's size per row; `word` (int32, zeroed by the
+    caller; device or pinned host memory) is raised when a row's pool holds fewer than k.  Every argument and limit is checked before the
+    launch."""
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 < float(lam) <= 1.0:
+        raise ValueError(f"lam must be a Python float with 0 < lam <= 1, got {lam!r}")
+    if not 1 <= k <= pool:
+        raise ValueError(f"need 1 <= k <= pool, got k = {k}, pool = {pool}")
+    if pool > MMR_MAX_POOL:
+        raise NotImplementedError(f"pool = {pool} beyond {MMR_MAX_POOL}")
+    if vectors.dtype != torch.float32 or vectors.dim() != 2 or not vectors.is_contiguous():
+        raise ValueError("vectors must be a contiguous (N, E) float32 tensor")
+    n_items, dim = vectors.shape
+    if not 1 <= dim <= MMR_MAX_DIM:
+        raise NotImplementedError(f"vectors of {dim} entries: 1 <= E <= {MMR_MAX_DIM}")
+    if invalid_ids is not None and invalid_ids.dim() == 2 and invalid_ids.shape[1] > COLLAPSE_MAX_SEEN:
+        raise NotImplementedError(f"width = {invalid_ids.shape[1]} beyond {COLLAPSE_MAX_SEEN} seen ids per row")
+    if scores.dim() != 2 or not 1 <= scores.shape[1] <= COLLAPSE_MAX_LIST:
+        raise NotImplementedError(f"scores must be (rows, L) with 1 <= L <= {COLLAPSE_MAX_LIST}")
+    lib = _lib.load()
+    _require_device(scores, "scores")
+    if scores.dtype != torch.float32 or scores.stride(1) != 1:
+        scores = _f32c(scores)
+    rows, depth = scores.shape
+    positions = positions.to(device=scores.device, dtype=torch.int64).contiguous()
+    if positions.shape != (rows, depth):
+        raise ValueError("positions must be (rows, L) like scores")
+    if vectors.device != scores.device:
+        raise ValueError("vectors must live on the scores' device")
+    if word.dtype != torch.int32 or not (word.is_cuda or word.is_pinned()):
+        raise ValueError("word must be an int32 tensor on the device or in pinned host memory")
+    if ids is not None:
+        ids = ids.to(device=scores.device, dtype=torch.int64).reshape(-1).contiguous()
+        if ids.numel() < n_items:
+            raise ValueError(f"ids holds {ids.numel()} entries but vectors has {n_items} rows")
+    inv, width = _seen_arg(invalid_ids, rows, scores.device)
+    need = int(lib.rails_topk_mmr_workspace_bytes(rows, pool, dim))
+    workspace = torch.empty(need, dtype=torch.uint8, device=scores.device) if need else None
+    out_s = torch.empty((rows, k), dtype=torch.float32, device=scores.device)
+    out_p = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
+    out_i = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
+    counts = torch.empty(rows, dtype=torch.int32, device=scores.device)
+    with _on_device(scores.device):
+        _lib.check(lib.rails_topk_mmr(_ptr(scores), scores.stride(0), _ptr(positions), rows, depth, _ptr(vectors), n_items, dim, float(lam), k, pool,
+                                      _ptr(ids), _ptr(inv), width, _ptr(workspace), need, _ptr(out_s), _ptr(out_p), _ptr(out_i), _ptr(counts),
+                                      _ptr(word), _stream()), "rails_topk_mmr")
+    return out_s, out_p, out_i, counts
+
+
+def list_similarity(positions: torch.Tensor, vectors: torch.Tensor) -> torch.Tensor:
+    """Mean pairwise similarity (dot product of the item vectors) of every returned row: positions (rows, k) int64, vectors (N, E) ->
+    (rows,) fp32, the mean over the k (k - 1) / 2 pairs of a row (0 for k < 2).  What tools/mmr_bench.py sets beside the cost of diversify=;
+    plain torch ops, a measurement and no part of any result."""
+    v = vectors.index_select(0, positions.reshape(-1).to(vectors.device)).reshape(positions.shape[0], positions.shape[1], -1).to(torch.float32)
+    k = positions.shape[1]
+    if k < 2:
+        return torch.zeros(positions.shape[0], dtype=torch.float32, device=vectors.device)
+    gram = torch.bmm(v, v.transpose(1, 2))
+    off = gram.sum(dim=(1, 2)) - torch.diagonal(gram, dim1=1, dim2=2).sum(dim=1)
+    return off / float(k * (k - 1))
 
 
 def _group_table_args(scores: torch.Tensor, ranks: torch.Tensor, table: torch.Tensor, shape: str, first_item: int, ids: Optional[torch.Tensor],

@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from . import engine as E
-from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule, _checked_positions, refuse_allowed_tags, refuse_collapse_groups, refuse_generic_candidates, refuse_item_mask
+from .topk_modules import MoLAvgTopK, MoLBruteForceTopK, MoLCombTopK, MoLNaiveTopK, TopKModule, _checked_positions, refuse_allowed_tags, refuse_collapse_groups, refuse_diversity, refuse_generic_candidates, refuse_item_mask
 
 _GENERIC_WHY = "the single-device module runs there, and ShardedMoLBruteForceTopK shards the exact pass"
 
@@ -127,6 +127,7 @@ class ShardedTopK(TopKModule):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         with self._inline():     # a plain call has no neighbouring batch to overlap with (MoLAvgTopK.submit)
             return self.result(self.submit(query_embeddings, k, sorted, **kwargs))
 
@@ -176,6 +177,7 @@ class ShardedTopK(TopKModule):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         if k > self._n_total:
             raise RuntimeError(f"selected index k out of range (k={k}, n={self._n_total})")
         k_local = min(k, self._n_local)
@@ -213,6 +215,7 @@ class ShardedTopK(TopKModule):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         if not self._exchange:
             local = self._local_module
             return local.forward_filtered(query_embeddings, k_prime, invalid_ids, k, **kwargs) if hasattr(local, "forward_filtered") else None
@@ -470,6 +473,7 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         B = query_embeddings.size(0)
         per_shard = -(-self._n_total // max(self._world, 1))
         # (the 4 GiB logit policy: the first pass wants the whole (B, N_shard) matrix -- beyond it every rank alike takes the per-shard path, which chunks)
@@ -574,6 +578,7 @@ class ShardedMoLBruteForceTopK(ShardedTopK):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         if self._exchange and self._global_proof(query_embeddings) and MoLBruteForceTopK.speculation_pays(query_embeddings.size(0), -(-self._n_total // self._world)) and k_prime <= self._n_total:
             with self._inline():
                 return self.result(self.submit(query_embeddings, k_prime, **kwargs), seen=(invalid_ids, k))
@@ -618,6 +623,7 @@ class ShardedMoLAvgTopK(ShardedTopK):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         if k_prime > self._avg_top_k or (self._global and self._exchange):
             return None   # forward's own checks / the global-K' exchange: the caller composes forward + filter_seen_ids
         return super().forward_filtered(query_embeddings, k_prime, invalid_ids, k, **kwargs)
@@ -626,6 +632,7 @@ class ShardedMoLAvgTopK(ShardedTopK):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         if k > self._avg_top_k:
             raise ValueError(f"avg_top_k ({self._avg_top_k}) must be larger than k ({k})")
         if not self._global or not self._exchange:
@@ -781,6 +788,7 @@ class _ShardedComponentCandidates(ShardedTopK):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         kk = self._check_k(k)
         if not (self._global and self._exchange):
             if not self._exchange:       # one rank: the module's own ranking
@@ -793,6 +801,7 @@ class _ShardedComponentCandidates(ShardedTopK):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         if self._global and self._exchange:
             raise NotImplementedError(f"{type(self).__name__}: submit / result pipelining of the global form is not built; call forward")
         return super().submit(query_embeddings, k, sorted, **kwargs)
@@ -801,6 +810,7 @@ class _ShardedComponentCandidates(ShardedTopK):
         refuse_item_mask(self, kwargs, _MASK_WHY)
         refuse_allowed_tags(self, kwargs, _TAGS_WHY)
         refuse_collapse_groups(self, kwargs)
+        refuse_diversity(self, kwargs)
         if self._global and self._exchange:
             return None      # the caller composes forward + filter_seen_ids: same bits
         if not self._exchange or k_prime > self.union_width() or k_prime > self._n_total:

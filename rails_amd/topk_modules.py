@@ -208,6 +208,20 @@ def groups_after_removal(groups: torch.Tensor, n_new: int, holes: torch.Tensor, 
     return tags_after_removal(groups, n_new, holes, movers)
 
 
+def vectors_after_append(vectors: torch.Tensor, n: int, n_new: int) -> torch.Tensor:
+    """append_items on an item-vector table: the (n, E) fp32 table grown to n_new rows, the new items n .. n_new - 1
+    carrying the zero vector (similar to nothing until set_item_vectors(..., positions) gives them one).  Pure tensor arithmetic."""
+    out = torch.zeros((int(n_new), vectors.shape[1]), dtype=torch.float32, device=vectors.device)
+    out[:n] = vectors[:n]
+    return out
+
+
+def vectors_after_removal(vectors: torch.Tensor, n_new: int, holes: torch.Tensor, movers: torch.Tensor) -> torch.Tensor:
+    """remove_items on an item-vector table: vectors belong to the position, so the i-th mover's row -- read BEFORE the cut -- goes to the i-th
+    hole and the table is cut to n_new rows (tags_after_removal's rule on rows; a copy: the table given is not written)."""
+    return tags_after_removal(vectors, n_new, holes, movers)
+
+
 GROUP_KEY_LIMIT = (1 << 31) - 1      # group keys lie in [-1, GROUP_KEY_LIMIT)
 
 
@@ -290,6 +304,16 @@ def refuse_collapse_groups(module, kwargs, what: Optional[str] = None) -> None:
     if kwargs.get("max_per_group") is not None:
         raise NotImplementedError(f"{name} takes no max_per_group: a quota per item group is built on the single-device modules' forward, "
                                   "forward_filtered, submit and get_top_k_outputs only")
+
+
+def refuse_diversity(module, kwargs, what: Optional[str] = None) -> None:
+    """diversify= / diversity_pool= where the re-rank is not built -- the item-sharded wrappers, submit, the hand-off calls
+    (coarse_candidates, local_candidates, topk_ids), all_logits and the streaming score calls: refused by the class's name, before any launch."""
+    for given in ("diversify", "diversity_pool"):
+        if kwargs.get(given) is not None:
+            name = type(module).__name__ + ("" if what is None else "." + what)
+            raise NotImplementedError(f"{name} takes no {given}: diversifying by maximal marginal relevance is built on the single-device modules' "
+                                      "forward, forward_filtered and get_top_k_outputs only")
 
 
 _FUSION_KWARGS = ("query_lims", "fuse", "query_weights")
@@ -550,6 +574,7 @@ class _StreamingScores(_ItemsById):
             raise NotImplementedError(f"{type(self).__name__}.{what}: an approximate module ranks its candidates only; {family.lacking} is "
                                       "built on MoLBruteForceTopK (and MIPSBruteForceTopK) -- ask a MoLBruteForceTopK over the same corpus")
         refuse_collapse_groups(self, kwargs, what)
+        refuse_diversity(self, kwargs, what)
 
     def _streaming_call(self, what: str, family: Streamed, query_embeddings: torch.Tensor, invalid_ids: Optional[torch.Tensor], kwargs: dict,
                         family_check: Optional[Callable[[str], None]] = None, matrices: int = 1, policy_as: Optional[str] = None) -> int:
@@ -1264,6 +1289,99 @@ class _CorpusEdits(_StreamingScores):
         """Which path answered the collapsed calls so far: calls, walk_redos (depth doublings), fallbacks (exact group-maxima passes)."""
         return dict(self.__dict__.setdefault("_collapse_stats", {"calls": 0, "walk_redos": 0, "fallbacks": 0}))
 
+    # ---- item vectors (DESIGN section 3.21): one fp32 vector per item, and diversify=lam on the calls ------------------------------------------
+    # State: an owned contiguous (N, E) fp32 table, None until set_item_vectors -- such a module holds nothing extra and a call without
+    # diversify= runs none of this.  A call with diversify=lam re-ranks the head of the row's ranking greedily by maximal marginal relevance
+    # (rails_topk_mmr): pick after pick, the item with the largest  lam * score - (1 - lam) * max(0, its largest similarity to a picked item).
+    # Vectors belong to the POSITION and follow edits as tags do (vectors_after_append / vectors_after_removal); they are not part of state_dict.
+    _vectors: Optional[torch.Tensor] = None
+
+    @property
+    def item_vectors(self) -> Optional[torch.Tensor]:
+        """The (N, E) fp32 item vectors on the module's device, or None while none are set.  The hand-off of the table -- it is not part of
+        state_dict; set_item_vectors takes this tensor back as it is."""
+        return self._vectors
+
+    def set_item_vectors(self, vectors: torch.Tensor, positions: Optional[torch.Tensor] = None, normalize: bool = False) -> None:
+        """One vector per item, the similarity space of diversify=.  vectors: (N, E) fp32 -- every item -- or (M, E) with positions ((M,) int64,
+        CPU or device, unique POSITIONS), 1 <= E <= 256, on the module's device; entries finite with magnitude <= 2^60 (no dot product of 256
+        terms overflows).  normalize=True divides each row by max(||row||, 1e-12) here, with torch ops; everything downstream reads the stored
+        rows.  A call with positions on a module without vectors builds the table with every other row zero; on a module with vectors E must
+        be the table's.  ValueError before anything is touched for a wrong shape, dtype, device, value or position (the value check and the
+        position check cost one sync each).  The stored table is the module's own: neither argument is aliased."""
+        self._check_diversifiable("set_item_vectors")
+        n = self.num_items
+        dev = self._ids_flat.device
+        if not torch.is_tensor(vectors) or vectors.dim() != 2 or vectors.dtype != torch.float32:
+            raise ValueError("vectors must be an (N, E) or (M, E) float32 tensor")
+        if vectors.device != dev:
+            raise ValueError(f"vectors must live on the module's device {dev}, got {vectors.device}")
+        m, dim = vectors.shape
+        if not 1 <= dim <= E.MMR_MAX_DIM:
+            raise ValueError(f"vectors have {dim} entries per item: 1 <= E <= {E.MMR_MAX_DIM}")
+        if positions is None:
+            if m != n:
+                raise ValueError(f"vectors has {m} rows but the module holds {n} items (pass positions to set a subset)")
+        else:
+            positions = _checked_positions(positions, m, n)
+            if self._vectors is not None and self._vectors.shape[1] != dim:
+                raise ValueError(f"vectors have {dim} entries per item but the module's table has {self._vectors.shape[1]}")
+        with torch.inference_mode():
+            if normalize:
+                vectors = vectors / torch.linalg.vector_norm(vectors, dim=1, keepdim=True).clamp_min(1e-12)
+            if m and not bool((vectors.abs() <= E.MMR_MAX_MAGNITUDE).all()):      # (NaN and inf fail the comparison: the one read-back)
+                raise ValueError("vectors must be finite with magnitude <= 2^60")
+            self._join_side_streams()
+            if positions is None:
+                table = vectors.clone(memory_format=torch.contiguous_format)
+            else:
+                table = torch.zeros((n, dim), dtype=torch.float32, device=dev) if self._vectors is None else self._vectors.clone()
+                table.index_copy_(0, positions.to(dev), vectors)
+            self._vectors = table
+
+    def clear_item_vectors(self) -> None:
+        """No item carries a vector any more: diversify= is refused again, every other call is what it was."""
+        self._vectors = None
+
+    def _vectors_step(self, e: CorpusEdit, n: int) -> None:
+        """The vector table follows an edit (called by _apply with the movers still where they were)."""
+        if self._vectors is None:
+            return
+        if e.how == CONCATENATED:
+            self._vectors = vectors_after_append(self._vectors, n, e.n_new)
+        elif e.how == CUT_AND_FILLED:
+            self._vectors = vectors_after_removal(self._vectors, e.n_new, e.positions, e.movers)
+
+    def _check_diversifiable(self, what: str) -> None:
+        """The refusal point of the item vectors: modules whose candidate generation cannot honour them raise here, before anything is touched."""
+
+    def _take_diversity(self, kwargs: dict) -> Optional[Tuple[float, Optional[int]]]:
+        """diversify= and diversity_pool= of a call, taken OUT of its kwargs and checked against this module before any launch -> (lam, the pool
+        size asked for or None); None: the call is not diversified."""
+        lam = kwargs.pop("diversify", None)
+        pool = kwargs.pop("diversity_pool", None)
+        name = type(self).__name__
+        if lam is None:
+            if pool is not None:
+                raise ValueError(f"{name}: diversity_pool= without diversify=")
+            return None
+        if not isinstance(lam, float) or not 0.0 < lam <= 1.0:
+            raise ValueError(f"{name}: diversify must be a Python float with 0 < diversify <= 1, got {lam!r}")
+        if pool is not None and (isinstance(pool, bool) or not isinstance(pool, int) or pool < 1):
+            raise ValueError(f"{name}: diversity_pool must be a Python int >= 1, got {pool!r}")
+        if kwargs.get("collapse_groups") or kwargs.get("max_per_group") is not None:
+            raise NotImplementedError(f"{name}: diversify= together with collapse_groups= / max_per_group= is not built")
+        if any(kwargs.get(given) is not None for given in _FUSION_KWARGS):
+            raise NotImplementedError(f"{name}: diversify= together with query_lims= is not built")
+        self._check_diversifiable("diversify")
+        if self._vectors is None:
+            raise ValueError(f"{name}: diversify={lam!r} on a module without vectors (set_item_vectors first)")
+        return lam, pool
+
+    def diversity_stats(self) -> dict:
+        """How many diversified calls the module has answered: {"calls": n} (each is one ranked-list call and one walk launch)."""
+        return dict(self.__dict__.setdefault("_diversity_stats", {"calls": 0}))
+
     @contextlib.contextmanager
     def _positions_as_ids(self):
         """Inside this block every call of the module returns POSITIONS where it returns ids: the id table is swapped for 0 .. N - 1, so whichever
@@ -1383,6 +1501,7 @@ class _CorpusEdits(_StreamingScores):
             self._visibility_step(e, n)
             self._tags_step(e, n)
             self._groups_step(e, n)
+            self._vectors_step(e, n)
             held, resize = self._held_buffers(), e.n_new != n
             if resize:
                 self._forget_corpus_choices()
@@ -1550,6 +1669,7 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
     def all_logits(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         """(B, N) fp32 MoL logits against the whole corpus."""
         refuse_collapse_groups(self, kwargs, "all_logits")
+        refuse_diversity(self, kwargs, "all_logits")
         refuse_item_mask(self, kwargs)
         tags = self._take_allowed_tags(kwargs, query_embeddings.size(0), ())
         logits = self._raw_logits(query_embeddings, **kwargs)
@@ -1917,6 +2037,7 @@ class MoLBruteForceTopK(MoLTopKModule):
         engine is not the module's precision: its fp32 companion answers).  item_mask=: the columns outside the mask hold -inf.
         query_lims=: the fused matrix, (U, N)."""
         refuse_collapse_groups(self, kwargs, "all_logits")
+        refuse_diversity(self, kwargs, "all_logits")
         if (fusion := self._resolve_fusion(kwargs, query_embeddings, "all_logits")) is not None:
             return self._fused_all_logits(query_embeddings, fusion, kwargs)
         eng = self._bind()
@@ -2004,7 +2125,10 @@ class MoLBruteForceTopK(MoLTopKModule):
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """item_mask= (an engine.ItemMask, or a bool tensor (N,) / (B, N) packed for this call): only items inside the mask are returned.
         collapse_groups=True: at most one item per group of set_item_groups.  query_lims= (section 3.20): one result row
-        per segment of query rows."""
+        per segment of query rows.  diversify=lam (section 3.21; diversity_pool=D): the head of the ranking re-ranked by maximal marginal relevance
+        against set_item_vectors -- k columns in PICK order, each with the item's own score, so a row is not monotone."""
+        if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (DESIGN section 3.21; results in pick order)
+            return _diversified_exact(self, query_embeddings, k, None, kwargs, div)
         if (fusion := self._resolve_fusion(kwargs, query_embeddings, "forward")) is not None:
             ids, scores = self._fused_topk("forward", query_embeddings, k, None, fusion, kwargs, sorted)
             return scores.to(query_embeddings.dtype), ids
@@ -2029,6 +2153,9 @@ class MoLBruteForceTopK(MoLTopKModule):
         or None when the sizes / the precision route are outside the fused path (the caller then composes forward +
         filter_seen_ids: same bits).  collapse_groups=True never returns None: the seen ids go to the collapse walk (a filter behind the
         collapse would drop a group whose best item is seen instead of promoting its next member).  Nor does query_lims= (section 3.20)."""
+        if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (never None: the seen ids go to the walk)
+            scores, ids = _diversified_exact(self, query_embeddings, k, invalid_ids, kwargs, div)
+            return ids, scores
         if (fusion := self._resolve_fusion(kwargs, query_embeddings, "forward_filtered")) is not None:
             ids, scores = self._fused_topk("forward_filtered", query_embeddings, k_prime, (invalid_ids, k), fusion, kwargs)
             return ids, scores.to(query_embeddings.dtype)
@@ -3025,6 +3152,94 @@ def _generic_takes_no_groups(tk, what: str) -> None:
                                   "single-device exhaustive algorithms without item groups); MoLBruteForceTopK collapses by item group on this route")
 
 
+def _generic_takes_no_vectors(tk, what: str) -> None:
+    """Item vectors on the approximate modules of the generic route: refused by name, as _generic_takes_no_groups refuses groups there."""
+    if (tk._call_eng or tk._engine).route == "generic":
+        raise NotImplementedError(f"{type(tk).__name__}: {what} is not built on the generic scoring route (generic_candidates = True covers the "
+                                  "single-device exhaustive algorithms without item vectors); MoLBruteForceTopK diversifies on this route")
+
+
+# ---- diversify=lam (DESIGN section 3.21): the module's ranked list by position, then one walk launch -- no depth doubling, no fallback ---------
+def _asks_diversity(kwargs: dict) -> bool:
+    """Does the call name one of the two arguments of section 3.21?  (A call with neither runs none of its code.)"""
+    return "diversify" in kwargs or "diversity_pool" in kwargs
+
+
+def diversity_pool_size(k: int, pool: Optional[int], width: int, name: str) -> int:
+    """D of a diversified call, checked before any launch: the pool asked for, else min(1024, max(4 k, 64)); k <= D <= 1024, and the seen ids
+    the walk filters are at most COLLAPSE_MAX_SEEN per row.  Pure host arithmetic."""
+    D = min(E.MMR_MAX_POOL, max(4 * k, 64)) if pool is None else pool
+    if not k <= D <= E.MMR_MAX_POOL or width > E.COLLAPSE_MAX_SEEN:
+        raise NotImplementedError(f"{name}: diversify= takes k <= diversity_pool <= {E.MMR_MAX_POOL} and up to {E.COLLAPSE_MAX_SEEN} seen ids per row "
+                                  f"(the walk's workgroup holds one pool entry per thread), got k = {k}, diversity_pool = {D}, width = {width}")
+    return D
+
+
+def _pool_too_small(k: int, counts: torch.Tensor) -> RuntimeError:
+    return RuntimeError(f"selected index k out of range (k={k}, n={int(counts.min())}: the eligible items of the diversity pool of the row with the fewest)")
+
+
+def _mmr_walk(tk, scores: torch.Tensor, positions: torch.Tensor, lam: float, k: int, pool: int, invalid_ids: Optional[torch.Tensor]) -> CollapseWalk:
+    """The one walk launch behind a ranked list of POSITIONS; the seen-id filter runs inside it (rails_topk_mmr)."""
+    word = _pinned_word(tk)
+    word.zero_()      # (a word on the free list has been read: nothing in flight writes it)
+    return CollapseWalk(*E.topk_mmr(scores, positions, tk._vectors, lam, k, pool, tk._ids_flat, invalid_ids, word), word)
+
+
+def _diversified_exact(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict,
+                       div: Tuple[float, Optional[int]]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The diversified call of an exact module -> (scores, ids) in PICK order: the scores are the items' own relevance
+    scores, so a row is not monotone.  The module's ordinary ranked top-L BY POSITION, L = min(items a row may return, D + width), through the
+    arm it would take anyway with the call's mask / hidden set / tags resolved once -- the seen ids are NOT handed to it: they go to the walk,
+    whose pool is the first D unseen entries -- then the one walk launch.  A row whose pool holds fewer than k is the RuntimeError of a call
+    for more than there is."""
+    lam, pool = div
+    width = 0 if invalid_ids is None else invalid_ids.shape[1]
+    D = diversity_pool_size(k, pool, width, type(tk).__name__)
+    B, n = query_embeddings.size(0), tk.num_items
+    kwargs = dict(kwargs)
+    mask = tk._take_item_mask(kwargs, B, k)
+    kwargs["_resolved_mask"] = mask
+    bound = n if mask is None else mask.kept_min
+    if k > bound:
+        raise RuntimeError(f"selected index k out of range (k={k}, n={bound})")
+    tk.__dict__.setdefault("_diversity_stats", {"calls": 0})["calls"] += 1
+    with tk._positions_as_ids():
+        scores, positions = tk.forward(query_embeddings, min(bound, D + width), **kwargs)
+    walk = _mmr_walk(tk, scores, positions, lam, k, D, invalid_ids)
+    if not walk.clear(tk):
+        raise _pool_too_small(k, walk.counts)
+    return walk.scores.to(query_embeddings.dtype), walk.ids
+
+
+def _diversified_candidates(tk, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], n_ranked: int, kwargs: dict,
+                            div: Tuple[float, Optional[int]]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The diversified call of an approximate module -> (scores, ids) in PICK order.  The walk runs over the module's own ranked candidate
+    list, exactly as _collapsed_candidates takes it -- forward's, by position, all n_ranked of it -- in place of the final cut to k; a scan
+    that was redone on the materialising path is walked again.  A list longer than the walk takes is refused before any launch."""
+    lam, pool = div
+    width = 0 if invalid_ids is None else invalid_ids.shape[1]
+    D = diversity_pool_size(k, pool, width, type(tk).__name__)
+    n_list = n_ranked if n_ranked else tk._union_width()
+    if n_list > E.COLLAPSE_MAX_LIST:
+        raise NotImplementedError(f"{type(tk).__name__}: diversify= walks ranked lists of up to {E.COLLAPSE_MAX_LIST} candidates per query, this "
+                                  f"module ranks {n_list}")
+    tk.__dict__.setdefault("_diversity_stats", {"calls": 0})["calls"] += 1
+    with tk._positions_as_ids(), getattr(tk, "inline_calls", contextlib.nullcontext)():
+        inner = MoLAvgTopK.submit(tk, query_embeddings, n_ranked, **dict(kwargs)) if n_ranked else None
+        ranked = inner[1:3] if inner is not None else tk.forward(query_embeddings, k, **dict(kwargs))
+    walk = _mmr_walk(tk, ranked[0], ranked[1], lam, k, D, invalid_ids)      # (outside the block: the walk looks the ids up; enqueued before the host
+    if inner is not None:                                                    # looks at the scan's verdict)
+        with tk._positions_as_ids():
+            scores, positions = MoLAvgTopK.result(tk, inner)
+        if scores is not inner[1]:      # the scan was redone on the materialising path: walk its list instead
+            walk.clear(tk)
+            walk = _mmr_walk(tk, scores, positions, lam, k, D, invalid_ids)
+    if not walk.clear(tk):
+        raise _pool_too_small(k, walk.counts)
+    return walk.scores.to(query_embeddings.dtype), walk.ids
+
+
 class MoLAvgTopK(MoLTopKModule):
     DEVICE_REDO_BYTES = 1 << 30   # materialised score matrices up to this size are kept as the device-side redo buffer of a fused scan;
                                   # beyond it (a 125 M-item shard: 16 GB) the counts are read on the host after the call is enqueued --
@@ -3073,6 +3288,9 @@ class MoLAvgTopK(MoLTopKModule):
 
     def _check_collapsible(self, what: str) -> None:
         _generic_takes_no_groups(self, what)
+
+    def _check_diversifiable(self, what: str) -> None:
+        _generic_takes_no_vectors(self, what)
 
     OVERLAP_BATCHES = True            # submit(): speculative calls alternate between two streams of the module (see submit)
     PREFILTER_MIN_ITEMS = 4_000_000   # the int8 copy of the coarse table pays where the streaming pass is bound by HBM reads
@@ -3211,6 +3429,7 @@ class MoLAvgTopK(MoLTopKModule):
     # joined to the caller's stream only by result() -- read them through result(), never through the handle, and do not drop a handle
     # without calling result() (ShardedTopK.submit, which needs the scores earlier, waits on the handle's event explicitly).
     def submit(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs):
+        refuse_diversity(self, kwargs, "submit")
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):      # (the walk over the reranked candidates; result owns the redo)
             return ("collapsed", self._collapse_enqueue(query_embeddings, k, None, kwargs, m))
         refuse_item_mask(self, kwargs)
@@ -3277,7 +3496,19 @@ class MoLAvgTopK(MoLTopKModule):
         finally:
             self._no_fused = False
 
+    def _diversified(self, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict, div):
+        """The diversified call over this module's own ranked list: MoLAvgTopK's avg_top_k reranked candidates; a
+        subclass with its own forward (MoLCombTopK) has that forward rank its union.  -> (scores, ids) in pick order."""
+        own = type(self).forward is MoLAvgTopK.forward
+        if own and k > self._avg_top_k:
+            raise ValueError(f"avg_top_k ({self._avg_top_k}) must be larger than k ({k})")
+        return _diversified_candidates(self, query_embeddings, k, invalid_ids, self._avg_top_k if own else 0, kwargs, div)
+
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """diversify=lam: the avg_top_k reranked candidates re-ranked by maximal marginal relevance -- k columns in PICK
+        order, each with the item's own score, so a row is not monotone."""
+        if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:
+            return self._diversified(query_embeddings, k, None, kwargs, div)
         with self.inline_calls():      # nothing to overlap with: stay on the caller's stream (the hand-over between streams costs ~50 us)
             return self.result(self.submit(query_embeddings, k, sorted, **kwargs))
 
@@ -3286,6 +3517,9 @@ class MoLAvgTopK(MoLTopKModule):
         at the scan's verdict word (it then runs while the host is on its way back) -> (top_k_ids, top_k_scores); None where this
         does not apply (subclasses with their own forward, k_prime beyond K': the caller composes the two calls).  collapse_groups=True never
         returns None: the seen ids go to the collapse walk."""
+        if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (never None: the seen ids go to the walk)
+            scores, ids = self._diversified(query_embeddings, k, invalid_ids, kwargs, div)
+            return ids, scores
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
             scores, ids = _collapsed_candidates_result(self._collapse_enqueue(query_embeddings, k, invalid_ids, kwargs, m))
             return ids, scores
@@ -3311,6 +3545,7 @@ class MoLAvgTopK(MoLTopKModule):
     def coarse_candidates(self, query_embeddings: torch.Tensor, **kwargs):
         """Pass 1 on this module's items: -> (coarse scores (B, K'), positions (B, K')), best first (ties by position)."""
         refuse_collapse_groups(self, kwargs, "coarse_candidates")
+        refuse_diversity(self, kwargs, "coarse_candidates")
         refuse_allowed_tags(self, kwargs, "coarse_candidates is the item-sharded wrappers' hand-off, and a tag filter is not built on them; forward, submit "
                             "and topk_ids take it")
         eng = self._bind()
@@ -3331,6 +3566,7 @@ class MoLAvgTopK(MoLTopKModule):
     def topk_ids(self, query_embeddings: torch.Tensor, sorted: bool = True, **kwargs) -> torch.Tensor:
         """Coarse candidates only, with the P_Q-averaged query (reference mol_top_k.py:398-429) -> positions."""
         refuse_collapse_groups(self, kwargs, "topk_ids")
+        refuse_diversity(self, kwargs, "topk_ids")
         refuse_query_fusion(self, kwargs, "topk_ids")
         return self._coarse_topk(query_embeddings, average_queries=True, **kwargs)[1]
 
@@ -3351,6 +3587,8 @@ class _ComponentCandidates:
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """All the union's candidates ranked, whatever `k` is, as the reference does.  collapse_groups=True: the first k
         of that ranking with at most one item per group of set_item_groups -- k columns."""
+        if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (DESIGN section 3.21: k columns in pick order)
+            return _diversified_candidates(self, query_embeddings, k, None, 0, kwargs, div)
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
             return _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, None, 0, kwargs, m))
         scores, ids = self._ranked(query_embeddings, sorted, None, kwargs)
@@ -3360,6 +3598,9 @@ class _ComponentCandidates:
         """CandidateIndex.get_top_k_outputs' body (the module returns all its candidates whatever k_prime is, the filter keeps the first k unseen):
         -> (top_k_ids, top_k_scores), or None where the filter does not fit the selection launch (_filter_inside).  collapse_groups=True never
         returns None: the seen ids go to the collapse walk, over the sorted form of the ranking."""
+        if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (never None: the seen ids go to the walk)
+            scores, ids = _diversified_candidates(self, query_embeddings, k, invalid_ids, 0, kwargs, div)
+            return ids, scores
         refuse_query_fusion(self, kwargs)
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
             scores, ids = _collapsed_candidates_result(_collapsed_candidates(self, query_embeddings, k, invalid_ids, 0, kwargs, m))
@@ -3451,6 +3692,7 @@ class _ComponentCandidates:
         scans are enqueued speculatively, their verdict words read once (the one host look of the single-device call), and a failed verdict
         redoes the scans on the materialising path -- what comes back is exact."""
         refuse_collapse_groups(self, kwargs, "local_candidates")
+        refuse_diversity(self, kwargs, "local_candidates")
         refuse_allowed_tags(self, kwargs, "local_candidates is the item-sharded wrappers' hand-off, and a tag filter is not built on them; forward and "
                             "get_top_k_outputs take it")
         eng = self._bind()
@@ -3635,6 +3877,12 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
             raise NotImplementedError(f"MoLNaiveTopK (IVF, use_faiss=True) takes no {what}: collapsing by item group is not built on the IVF index; the "
                                       "exhaustive MoLNaiveTopK takes it")
 
+    def _check_diversifiable(self, what: str) -> None:
+        _generic_takes_no_vectors(self, what)
+        if self._use_faiss:
+            raise NotImplementedError(f"MoLNaiveTopK (IVF, use_faiss=True) takes no {what}: diversifying by maximal marginal relevance is not built on "
+                                      "the IVF index; the exhaustive MoLNaiveTopK takes it")
+
     def _check_taggable(self, what: str) -> None:
         if self._use_faiss and not getattr(self, "_filtered_lists", False):
             raise NotImplementedError(f"MoLNaiveTopK takes no {what}: the IVF index (use_faiss=True{', frozen_centroids=True' if self._frozen_centroids else ''}) "
@@ -3699,7 +3947,11 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """item_mask= (an engine.ItemMask or a bool tensor (N,) / (B, N)): only items inside the mask are returned -- the
         dense strategy: the score matrix of the items outside it is set to -inf before the selection.  collapse_groups=True (section 3.16): at
-        most one item per group of set_item_groups.  query_lims= (section 3.20): one result row per segment of query rows."""
+        most one item per group of set_item_groups.  query_lims= (section 3.20): one result row per segment of query rows.  diversify=lam (section
+        3.21; diversity_pool=D): the head of the ranking re-ranked by maximal marginal relevance against set_item_vectors -- k columns in PICK
+        order, each with the item's own score, so a row is not monotone."""
+        if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (DESIGN section 3.21; results in pick order)
+            return _diversified_exact(self, query_embeddings, k, None, kwargs, div)
         if (fusion := self._resolve_fusion(kwargs, query_embeddings, "forward")) is not None:
             ids, scores = self._fused_topk("forward", query_embeddings, k, None, fusion, kwargs, sorted)
             return scores.to(query_embeddings.dtype), ids
@@ -3716,6 +3968,9 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
         """CandidateIndex.get_top_k_outputs' body under collapse_groups=True -> (top_k_ids, top_k_scores): the seen ids go to the collapse walk.
         So under query_lims= (section 3.20): the seen ids are per fused row.  None for every other call (the caller composes forward +
         filter_seen_ids, as it always has)."""
+        if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (never None: the seen ids go to the walk)
+            scores, ids = _diversified_exact(self, query_embeddings, k, invalid_ids, kwargs, div)
+            return ids, scores
         if (fusion := self._resolve_fusion(kwargs, query_embeddings, "forward_filtered")) is not None:
             ids, scores = self._fused_topk("forward_filtered", query_embeddings, k_prime, (invalid_ids, k), fusion, kwargs)
             return ids, scores.to(query_embeddings.dtype)
