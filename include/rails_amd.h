@@ -60,6 +60,8 @@ extern "C" {
  * and the multi-row SASRec decode step rails_sasrec_decode_rows / RAILS_SASREC_DECODE_MAX_ROWS (rails_sasrec_decode is its max_new = 1 call,
  * bit for bit what it was)
  * and the diversity entries rails_topk_mmr / rails_topk_mmr_workspace_bytes
+ * and the multi-row HSTU decode step rails_hstu_decode_rows[_supported] / rails_hstu_decode_rows_workspace_floats /
+ * RAILS_HSTU_DECODE_MAX_ROWS (rails_hstu_decode is what it was)
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -1131,6 +1133,32 @@ int rails_hstu_decode(const float* embeddings, const int64_t* ids, const int64_t
                       const int64_t* timestamps, const int64_t* thresholds, const float* pos_emb, const rails_hstu_decode_layer* layers,
                       int32_t n_blocks, int32_t batch, int32_t seq_len, int64_t cache_rows, int32_t dim, int32_t heads, int32_t dqk,
                       int32_t dv, int32_t num_buckets, int32_t linear_act, int32_t postproc_mode, float eps, float* out, void* stream);
+/* Several rows per sequence in one step: the contiguous run of rows positions[b] .. positions[b] + m_b - 1 of sequence b is
+ * re-encoded in ascending order through all layers against the cache, which gains those rows in place (per layer: v / outputs at
+ * the jagged rows off_b + p, q / k at (b, p)); every other cache element keeps its bits.  The step equals m_b calls of the
+ * single-row step at ascending positions, and an append must start at the OLD last row (the relative bias gives query row p the
+ * timestamp of row p + 1, so row len_old - 1 changes when the sequence grows): positions = len_old - 1, m_b = len_new - len_old + 1.
+ * counts: device int64 (batch), or NULL for m_b = max_rows everywhere; a count is clamped on the device into
+ * [1, min(max_rows, lengths[b] - positions[b])].  The step runs batch * max_rows work-row slots (slot b * max_rows + t is idle when
+ * t >= m_b); a row's arithmetic depends on neither its slot nor max_rows, so one step is bit for bit the max_rows = 1 calls at
+ * ascending positions.  embeddings / ids are read at the run's rows only; out (batch, dim) is the postprocessed last layer's
+ * outputs row at lengths[b] - 1 (the cached row when the run ends below it).  The jagged offsets are derived from `lengths` by a
+ * scan into the workspace: no caller offset addresses a write.  A sequence whose length lies outside [1, seq_len] (or which
+ * follows a length outside [0, seq_len]), whose start lies outside [0, length) or whose rows fall outside cache_rows is left
+ * alone: no cache row written, a NaN out row; the others are unaffected.  Other arguments as rails_hstu_decode (`layers` a DEVICE
+ * array).  work: device scratch of rails_hstu_decode_rows_workspace_floats(batch * max_rows, batch, ...) floats.  3 * n_blocks + 2
+ * launches on `stream`, each layer's weights read once per 32 work rows.  rails_hstu_decode_rows_supported:
+ * dim <= 1024, dqk and dv <= 32, num_buckets <= 255, and the LDS bound heads * dv <= 1024 (a tile of 32 rows of max(dim,
+ * heads * dv) floats is staged: 128 KiB at the limit); RAILS_ENOTSUP otherwise.  RAILS_EINVAL: max_rows outside [1, seq_len], or
+ * batch * max_rows > RAILS_HSTU_DECODE_MAX_ROWS (checked before any launch: the row tiles sit on a launch grid's y). */
+#define RAILS_HSTU_DECODE_MAX_ROWS 2097120   /* 65535 launch-grid rows of 32 work rows */
+int rails_hstu_decode_rows_supported(int32_t seq_len, int32_t dim, int32_t heads, int32_t dqk, int32_t dv, int32_t num_buckets);
+int64_t rails_hstu_decode_rows_workspace_floats(int64_t work_rows, int32_t batch, int32_t dim, int32_t heads, int32_t dqk, int32_t dv);
+int rails_hstu_decode_rows(const float* embeddings, const int64_t* ids, const int64_t* positions, const int64_t* counts, int32_t max_rows,
+                           const int64_t* lengths, const int64_t* timestamps, const int64_t* thresholds, const float* pos_emb,
+                           const rails_hstu_decode_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int64_t cache_rows,
+                           int32_t dim, int32_t heads, int32_t dqk, int32_t dv, int32_t num_buckets, int32_t linear_act,
+                           int32_t postproc_mode, float eps, float* work, float* out, void* stream);
 /* ---- SASRec query encoder, eval path ----------------------------------------------------------------------------------
  * modeling/sequential/sasrec.py (SASRec.encode / forward, dropout off).  The per-layer route: rails_hstu_preprocess with every
  * length = seq_len (x = (ids != 0) * (emb * sqrt(dim) + pos_emb)), then per block rails_rows_layer_norm (eps 1e-8),

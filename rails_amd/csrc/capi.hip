@@ -1752,6 +1752,57 @@ int rails_hstu_decode(const float* embeddings, const int64_t* ids, const int64_t
   return r == kOk ? r : fail(r, "hstu_decode");
 }
 
+int rails_hstu_decode_rows_supported(int32_t seq_len, int32_t dim, int32_t heads, int32_t dqk, int32_t dv, int32_t num_buckets) {
+  return hstu_decode_rows_supported(seq_len, dim, heads, dqk, dv, num_buckets) ? 1 : 0;
+}
+
+int64_t rails_hstu_decode_rows_workspace_floats(int64_t work_rows, int32_t batch, int32_t dim, int32_t heads, int32_t dqk, int32_t dv) {
+  if (work_rows < 0 || batch < 0 || dim < 0 || heads < 0 || dqk < 0 || dv < 0) return 0;
+  return hstu_decode_rows_workspace_floats(work_rows, batch, dim, heads, dv);
+}
+
+int rails_hstu_decode_rows(const float* embeddings, const int64_t* ids, const int64_t* positions, const int64_t* counts, int32_t max_rows,
+                           const int64_t* lengths, const int64_t* timestamps, const int64_t* thresholds, const float* pos_emb,
+                           const rails_hstu_decode_layer* layers, int32_t n_blocks, int32_t batch, int32_t seq_len, int64_t cache_rows,
+                           int32_t dim, int32_t heads, int32_t dqk, int32_t dv, int32_t num_buckets, int32_t linear_act,
+                           int32_t postproc_mode, float eps, float* work, float* out, void* stream) {
+  g_err[0] = '\0';
+  if (batch < 0 || n_blocks < 1 || seq_len < 1 || dim < 1 || heads < 1 || dqk < 1 || dv < 1 || cache_rows < batch) {
+    set_error("hstu_decode_rows: bad size (batch %d, n_blocks %d, seq_len %d, dim %d, heads %d, dqk %d, dv %d, cache_rows %lld)", batch,
+              n_blocks, seq_len, dim, heads, dqk, dv, (long long)cache_rows);
+    return RAILS_EINVAL;
+  }
+  if (max_rows < 1) { set_error("hstu_decode_rows: max_rows %d < 1", max_rows); return RAILS_EINVAL; }
+  if ((int64_t)batch * max_rows > RAILS_HSTU_DECODE_MAX_ROWS) {
+    set_error("hstu_decode_rows: batch %d x max_rows %d = %lld work rows, more than the %d of one step", batch, max_rows,
+              (long long)batch * max_rows, RAILS_HSTU_DECODE_MAX_ROWS);
+    return RAILS_EINVAL;
+  }
+  if (max_rows > seq_len) {
+    set_error("hstu_decode_rows: max_rows %d outside [1, seq_len %d]", max_rows, seq_len);
+    return RAILS_EINVAL;
+  }
+  if ((linear_act != RAILS_ACT_NONE && linear_act != RAILS_ACT_SILU) || (postproc_mode != 0 && postproc_mode != 1)) {
+    set_error("hstu_decode_rows: bad linear_act %d or postproc_mode %d", linear_act, postproc_mode);
+    return RAILS_EINVAL;
+  }
+  if (timestamps && (!thresholds || num_buckets < 1)) { set_error("hstu_decode_rows: timestamps without a threshold table"); return RAILS_EINVAL; }
+  if (!hstu_decode_rows_supported(seq_len, dim, heads, dqk, dv, num_buckets)) {
+    set_error("hstu_decode_rows: dim %d, heads %d, dqk %d, dv %d, %d buckets not supported (dim <= 1024, dqk <= 32, dv <= 32, <= 255 buckets, "
+              "heads * dv <= 1024)", dim, heads, dqk, dv, num_buckets);
+    return RAILS_ENOTSUP;
+  }
+  if (batch == 0) return RAILS_OK;
+  if (!embeddings || !ids || !positions || !lengths || !pos_emb || !layers || !work || !out) {
+    set_error("hstu_decode_rows: NULL pointer");
+    return RAILS_EINVAL;
+  }
+  const int r = hstu_decode_rows(embeddings, ids, positions, counts, max_rows, lengths, timestamps, thresholds, pos_emb, layers, n_blocks, batch,
+                                 seq_len, cache_rows, dim, heads, dqk, dv, num_buckets, linear_act, postproc_mode, eps, work, out,
+                                 (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "hstu_decode_rows");
+}
+
 // ---- SASRec query encoder, eval path ----
 int rails_sasrec_attention(const float* qkv, int64_t ld, int32_t batch, int32_t seq_len, int32_t dim, int32_t heads, float* out,
                            void* stream) {

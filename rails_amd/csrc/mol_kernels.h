@@ -160,6 +160,14 @@ bool hstu_decode_supported(int N, int D, int H, int dqk, int dv, int num_buckets
 int hstu_decode(const float* emb, const int64_t* ids, const int64_t* positions, const int64_t* lengths, const int64_t* ts,
                 const int64_t* thresholds, const float* pos_emb, const void* layers, int n_blocks, int B, int N, int64_t cache_rows, int D,
                 int H, int dqk, int dv, int num_buckets, int act, int mode, float eps, float* out, hipStream_t stream);
+// ---- HSTU cached decoding, several rows per sequence (hstu_rows.hip) ----
+bool hstu_decode_rows_supported(int N, int D, int H, int dqk, int dv, int num_buckets);
+int64_t hstu_decode_rows_workspace_floats(int64_t R, int B, int D, int H, int dv);
+// counts (B) or null, M = max_rows: rows positions[b] .. positions[b] + m_b - 1 of every sequence in B * M work-row slots
+int hstu_decode_rows(const float* emb, const int64_t* ids, const int64_t* positions, const int64_t* counts, int M, const int64_t* lengths,
+                     const int64_t* ts, const int64_t* thresholds, const float* pos_emb, const void* layers, int n_blocks, int B, int N,
+                     int64_t cache_rows, int D, int H, int dqk, int dv, int num_buckets, int act, int mode, float eps, float* work, float* out,
+                     hipStream_t stream);
 // ---- SASRec query encoder, eval path (sasrec.hip) ----
 int sasrec_attention(const float* qkv, int64_t ld, int B, int N, int H, int hd, float* out, hipStream_t stream);
 bool sasrec_fused_supported(int N, int D, int H, int F);

@@ -10,10 +10,12 @@ rails_hstu_attention, rails_rows_normalize); torch only holds the parameters and
 Cached incremental decoding (hstu.py:144-213, :276-433, :665-803): `encode` / `generate_user_embeddings` with
 `return_cache_states=True` return the reference's per-layer states (v, padded_q, padded_k, outputs); passing them back as `cache`
 with `delta_x_offsets = (jagged_rows, positions)` re-encodes one row per sequence against the cached K / V of the others in one
-launch of rails_hstu_decode and updates the cache in place.
+launch of rails_hstu_decode and updates the cache in place.  With `delta_rows=` the same call re-encodes a contiguous run of rows
+[position, position + delta_rows) of every sequence in one step of rails_hstu_decode_rows (bit for bit the single-row steps of that
+entry at ascending positions); `extend_cache_states` lays a cache out for grown lengths, and its docstring has the append recipe.
 
 Not supported (raises): training mode, `concat_ua`, `normalization="softmax_rel_bias"`, `linear_activation` other than
-"silu" / "none", autocast / non-fp32 caches, more than one delta row per sequence.
+"silu" / "none", autocast / non-fp32 caches, delta rows of one sequence that are not one contiguous run.
 """
 from __future__ import annotations
 
@@ -123,14 +125,21 @@ class HSTU(Encoder):
         return self._normalize(x.view(B * N, D), None).view(B, N, D)
 
     def encode(self, past_lengths, past_ids, past_embeddings, past_payloads: Dict[str, torch.Tensor], delta_x_offsets=None, cache=None,
-               return_cache_states: bool = False) -> torch.Tensor:
+               return_cache_states: bool = False, delta_rows=None, max_delta_rows: Optional[int] = None) -> torch.Tensor:
         """(B, D): the postprocessed embedding at position past_lengths - 1 (hstu.py:741-803).
         return_cache_states=True: (current embeddings, per-layer states) -- the per-layer route runs (the fused kernel keeps its
         intermediates in LDS).  delta_x_offsets = (jagged_rows (B,), positions (B,)) with `cache`: re-encode one row per sequence
         (rails_hstu_decode), updating the cache in place; the result is the last layer's cached outputs row at past_lengths - 1, as
-        in the reference (a delta at an earlier position leaves it as it was).  A `cache` without delta_x_offsets is ignored."""
+        in the reference (a delta at an earlier position leaves it as it was).  A `cache` without delta_x_offsets is ignored.
+        delta_rows (with delta_x_offsets and cache): re-encode the run of rows [positions[b], positions[b] + m_b) of every sequence in one
+        step (rails_hstu_decode_rows); delta_x_offsets then names the run's first row.  An int m >= 1, or m_b per sequence as a list or
+        a tensor (B,); the run must end at or below past_lengths.  Counts on the host are validated there and the step runs
+        max(m_b) slots per sequence (max_delta_rows if given; no bit depends on it); counts on the device need max_delta_rows=M, are
+        clamped on the device into [1, min(M, length - position)], counted in length_violations(), and never read back.  To APPEND
+        rows see extend_cache_states."""
+        self._delta_rows_need(delta_rows, max_delta_rows, delta_x_offsets, cache)
         if delta_x_offsets is not None:
-            cur, states, _ = self._decode(past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache)
+            cur, states, _ = self._decode(past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache, delta_rows, max_delta_rows)
             return (cur, states) if return_cache_states else cur
         if return_cache_states:
             states = []
@@ -146,15 +155,18 @@ class HSTU(Encoder):
         return self._normalize(x.view(B * N, D), self._last_rows(self._lengths(past_lengths, x.device, N), N))
 
     def generate_user_embeddings(self, past_lengths, past_ids, past_embeddings, past_payloads: Dict[str, torch.Tensor], delta_x_offsets=None,
-                                 cache=None, return_cache_states: bool = False) -> Tuple[torch.Tensor, List[CacheState]]:
+                                 cache=None, return_cache_states: bool = False, delta_rows=None,
+                                 max_delta_rows: Optional[int] = None) -> Tuple[torch.Tensor, List[CacheState]]:
         """(postprocessed (B, N, D), states) as hstu.py:665-703: the states list is [] unless return_cache_states.  With
-        delta_x_offsets and cache the (B, N, D) is the last layer's cached outputs (updated in place) padded and postprocessed."""
+        delta_x_offsets and cache the (B, N, D) is the last layer's cached outputs (updated in place) padded and postprocessed;
+        delta_rows / max_delta_rows as in encode."""
+        self._delta_rows_need(delta_rows, max_delta_rows, delta_x_offsets, cache)
         if delta_x_offsets is None:
             states: Optional[list] = [] if return_cache_states else None
             x = self._run_layers(past_lengths, past_ids, past_embeddings, past_payloads, min_len=0, states=states)
             B, N, D = x.shape
             return self._normalize(x.view(B * N, D), None).view(B, N, D), (states if return_cache_states else [])
-        _, states, lengths = self._decode(past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache)
+        _, states, lengths = self._decode(past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache, delta_rows, max_delta_rows)
         B, N = past_ids.shape
         D = self._embedding_dim
         out = states[-1][3]
@@ -321,14 +333,110 @@ class HSTU(Encoder):
             raise ValueError(f"the cache holds {rows} jagged rows for {B} sequences")
         return rows
 
-    def _decode(self, past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache):
-        """One rails_hstu_decode launch -> ((B, D) current embeddings, the cache's own states, the device lengths)."""
+    @staticmethod
+    def _delta_rows_need(delta_rows, max_delta_rows, delta_x_offsets, cache) -> None:
+        if (delta_rows is not None or max_delta_rows is not None) and (delta_x_offsets is None or cache is None):
+            raise ValueError("delta_rows / max_delta_rows need delta_x_offsets= and cache=")
+
+    def _delta_counts(self, delta_rows, max_delta_rows, delta_x_offsets, past_lengths, B: int, N: int):
+        """(counts, M, checked) of a multi-row step, without touching a device unless the data lives there: counts an int64 tensor (B,)
+        (on the host, or the caller's device tensor), or None for M rows of every sequence; checked: the runs were held against the
+        lengths here.  Raises for whatever the host can see; the rest is counted and clamped on the device (mirrors SASRec._new_rows)."""
+        ints = (torch.int32, torch.int64)
+        if max_delta_rows is not None and (isinstance(max_delta_rows, bool) or not isinstance(max_delta_rows, int) or not 1 <= max_delta_rows <= N):
+            raise ValueError(f"max_delta_rows must be an int in [1, {N}], got {max_delta_rows!r}")
+        if delta_rows is None:
+            raise ValueError("max_delta_rows needs delta_rows=")
+        if isinstance(delta_rows, torch.Tensor) and delta_rows.is_cuda:
+            if max_delta_rows is None:
+                raise ValueError("delta_rows on the device needs max_delta_rows=M (an int): the number of work rows is a host-side launch size")
+            if delta_rows.dtype not in ints or delta_rows.shape != (B,):
+                raise ValueError(f"delta_rows must be an integer tensor of shape ({B},), got {delta_rows.dtype} {tuple(delta_rows.shape)}")
+            return delta_rows, max_delta_rows, False
+        uniform = isinstance(delta_rows, int) and not isinstance(delta_rows, bool)
+        if uniform:
+            counts = torch.full((B,), delta_rows, dtype=torch.int64)
+        else:
+            try:
+                counts = torch.as_tensor(delta_rows)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise ValueError(f"delta_rows must be an int, or {B} ints as a list or tensor: {e}") from None
+            if counts.dtype not in ints or counts.shape != (B,):
+                raise ValueError(f"delta_rows must be an integer tensor of shape ({B},), got {counts.dtype} {tuple(counts.shape)}")
+            counts = counts.to(torch.int64)
+        top = int(counts.max()) if B else 1
+        if B and (int(counts.min()) < 1 or top > N):
+            raise ValueError(f"delta_rows must lie in [1, past_lengths - position] (got min {int(counts.min())}, max {top}, seq_len {N})")
+        if max_delta_rows is not None and max_delta_rows < top:
+            raise ValueError(f"max_delta_rows {max_delta_rows} is less than the largest delta_rows {top}")
+        pos = delta_x_offsets[1] if isinstance(delta_x_offsets, (tuple, list)) and len(delta_x_offsets) == 2 else None
+        pos = torch.as_tensor(pos) if pos is not None else None
+        checked = pos is not None and pos.shape == (B,) and ((not past_lengths.is_cuda and not pos.is_cuda) or type(self).STRICT_DEVICE_LENGTHS)
+        if checked:
+            lh, p = past_lengths.to(dtype=torch.int64).cpu(), pos.to(dtype=torch.int64).cpu()
+            if bool((p + counts > lh).any()):
+                b = int((p + counts > lh).nonzero()[0])
+                raise ValueError(f"delta rows [{int(p[b])}, {int(p[b] + counts[b])}) of sequence {b} end past its length {int(lh[b])}")
+        M = top if max_delta_rows is None else max_delta_rows
+        return (None if uniform and M == top else counts), M, checked
+
+    def extend_cache_states(self, cache, old_lengths, new_lengths) -> List[CacheState]:
+        """The states of `cache` (laid out for old_lengths) laid out for new_lengths: every jagged `v` / `outputs` becomes (sum new, .)
+        with each sequence's old rows at its new offset and its new rows zero; padded_q / padded_k are the same tensors.  Pure row
+        movement, on host lengths.  ValueError unless 1 <= old <= new <= N elementwise and the cache holds sum(old) rows.
+
+        To APPEND len_new - len_old events: extend the cache, then decode the run [len_old - 1, len_new), that is
+        delta_x_offsets = (new offsets + len_old - 1, len_old - 1) and delta_rows = len_new - len_old + 1, with the ids, embeddings and
+        timestamps of the grown sequences.  The run starts one row BELOW the first new one because the relative bias gives query row p
+        the timestamp of row p + 1 (ts[min(p + 1, N - 1)]): row len_old - 1 was encoded against whatever the padding held at
+        ts[len_old], so its attention, and with it every deeper k / v of that row, changes when the sequence grows.  Decoded from
+        len_old - 1 the step equals a prefill at the new lengths; decoded from len_old it does not wherever timestamps are used."""
+        old, new = (torch.as_tensor(t).to(dtype=torch.int64).cpu() for t in (old_lengths, new_lengths))
+        N = self._seq
+        if old.dim() != 1 or old.shape != new.shape:
+            raise ValueError(f"old_lengths {tuple(old.shape)} and new_lengths {tuple(new.shape)} must be two (B,) vectors")
+        if bool(((old < 1) | (old > new) | (new > N)).any()):
+            b = int(((old < 1) | (old > new) | (new > N)).nonzero()[0])
+            raise ValueError(f"sequence {b}: 1 <= old length {int(old[b])} <= new length {int(new[b])} <= {N} does not hold")
+        if not isinstance(cache, (list, tuple)) or not all(isinstance(s, (list, tuple)) and len(s) == 4 for s in cache):
+            raise ValueError("cache must hold one (v, padded_q, padded_k, outputs) state per layer")
+        total_old, total_new = int(old.sum()), int(new.sum())
+        for i, (v, _, _, out) in enumerate(cache):
+            if v.dim() != 2 or out.dim() != 2 or v.shape[0] != total_old or out.shape[0] != total_old:
+                raise ValueError(f"cache[{i}]: v {tuple(v.shape)} / outputs {tuple(out.shape)} must hold the {total_old} rows the old lengths sum to")
+        # jagged row of old row j of sequence b under the new lengths
+        seq = torch.repeat_interleave(torch.arange(old.numel()), old)
+        dst = torch.arange(total_old) + ((torch.cumsum(new, 0) - new) - (torch.cumsum(old, 0) - old))[seq]
+        states = []
+        for v, q, k, out in cache:
+            idx = dst.to(v.device)
+            nv = torch.zeros((total_new, v.shape[1]), dtype=v.dtype, device=v.device)
+            no = torch.zeros((total_new, out.shape[1]), dtype=out.dtype, device=out.device)
+            nv[idx] = v
+            no[idx] = out
+            states.append((nv, q, k, no))
+        return states
+
+    def _decode(self, past_lengths, past_ids, past_embeddings, past_payloads, delta_x_offsets, cache, delta_rows=None, max_delta_rows=None):
+        """One rails_hstu_decode launch (one rails_hstu_decode_rows step with delta_rows) -> ((B, D) current embeddings, the cache's
+        own states, the device lengths)."""
+        multi = delta_rows is not None or max_delta_rows is not None
+        counts = None
+        if multi:   # whatever the host can refuse is refused before the device and the library are touched
+            self._check(past_ids, past_embeddings, device=False)
+            counts, M, counts_checked = self._delta_counts(delta_rows, max_delta_rows, delta_x_offsets, past_lengths, *past_ids.shape)
         self._check(past_ids, past_embeddings)
         lib = _lib.load()
         dev = past_embeddings.device
         B, N = past_ids.shape
         D, H, dqk, dv = self._embedding_dim, self._num_heads, self._dqk, self._dv
-        if not lib.rails_hstu_decode_supported(N, D, H, dqk, dv, self._num_buckets):
+        if multi:
+            if not lib.rails_hstu_decode_rows_supported(N, D, H, dqk, dv, self._num_buckets):
+                raise NotImplementedError(f"multi-row cached decoding supports dim <= 1024, dqk <= 32, dv <= 32, heads * dv <= 1024 and <= 255 "
+                                          f"buckets (got dim {D}, {H} heads, dqk {dqk}, dv {dv}, {self._num_buckets} buckets)")
+            if B * M > _lib.RAILS_HSTU_DECODE_MAX_ROWS:
+                raise ValueError(f"a decode step runs at most {_lib.RAILS_HSTU_DECODE_MAX_ROWS} work rows (batch x max delta rows), got {B} x {M}")
+        elif not lib.rails_hstu_decode_supported(N, D, H, dqk, dv, self._num_buckets):
             raise NotImplementedError(f"cached decoding supports dim <= 1024, dqk <= 32, dv <= 32 and <= 255 buckets within its LDS bound "
                                       f"(got dim {D}, {H} heads, dqk {dqk}, dv {dv}, {self._num_buckets} buckets)")
         # host-side checks of the cache's row count whenever the lengths or the offsets are on the host (the latter read the lengths anyway)
@@ -352,6 +460,24 @@ class HSTU(Encoder):
         self._decode_ptrs = _lib.layer_table(_lib.HstuDecodeLayer, table, dev, self._decode_ptrs)
         thr = self._bucket_thresholds.to(dev)
         res = torch.empty((B, D), dtype=torch.float32, device=dev)
+        if multi:
+            if counts is not None or not counts_checked:
+                c = torch.full((B,), M, dtype=torch.int64, device=dev) if counts is None else counts.to(device=dev, dtype=torch.int64).contiguous()
+                if not counts_checked:   # the scan kernel clamps these; nothing is read back
+                    bad = (c < 1) | (c > (lengths - positions).clamp(max=M))
+                    if type(self).STRICT_DEVICE_LENGTHS and bool(bad.any()):
+                        raise ValueError(f"delta_rows must lie in [1, min(max_delta_rows, past_lengths - position)] (got min {int(c.min())}, max {int(c.max())})")
+                    self._count_violations(dev, bad.sum())
+                counts = None if counts is None else c
+            work = torch.empty(lib.rails_hstu_decode_rows_workspace_floats(B * M, B, D, H, dqk, dv), dtype=torch.float32, device=dev)
+            with _on_device(dev):
+                _lib.check(lib.rails_hstu_decode_rows(_ptr(emb), _ptr(ids), _ptr(positions), _ptr(counts) if counts is not None else None, M,
+                                                      _ptr(lengths), _ptr(ts), _ptr(thr) if ts is not None else None,
+                                                      _ptr(f32(self._input_features_preproc._pos_emb.weight)), _ptr(self._decode_ptrs[1]), len(table),
+                                                      B, N, rows, D, H, dqk, dv, self._num_buckets, 1 if self._linear_activation == "silu" else 0,
+                                                      self._postproc_mode, C.c_float(self._eps), _ptr(work), _ptr(res), _stream()),
+                           "rails_hstu_decode_rows")
+            return res, [(v, q.view(B, N, H * dqk), k.view(B, N, H * dqk), out) for v, q, k, out in cache], lengths
         with _on_device(dev):
             _lib.check(lib.rails_hstu_decode(_ptr(emb), _ptr(ids), _ptr(positions), _ptr(lengths), _ptr(ts), _ptr(thr) if ts is not None else None,
                                              _ptr(f32(self._input_features_preproc._pos_emb.weight)), _ptr(self._decode_ptrs[1]), len(table), B, N,
