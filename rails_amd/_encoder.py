@@ -1,6 +1,6 @@
 """Host layer shared by the HSTU and SASRec query encoders (hstu.py, sasrec.py): the reference's parameter holders, the parsing of
-the two constructor signatures, and the `Encoder` base class (input checks, the length policy and its violation counter, fp32
-parameter staging, the postprocessor launch)."""
+the two constructor signatures, and the `Encoder` base class (input checks, the length policy and its violation counter, the
+row-count contract of a multi-row decode step, fp32 parameter staging, the postprocessor launch)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -190,6 +190,53 @@ class Encoder(torch.nn.Module):
         """Out-of-range past_lengths (and HSTU delta positions) seen and clamped on the sync-free device path since the process
         started, by either encoder: an upstream data bug when non-zero.  One synchronising read per device."""
         return sum(int(v.item()) for v in Encoder._violations.values())
+
+    # ---- rows of a multi-row decode step ---------------------------------------------------------------------------------
+    @staticmethod
+    def _parse_row_counts(rows, max_rows, B: int, N: int, names, int_dtypes, upper: str):
+        """First half of the row-count contract of a multi-row decode step (SASRec's new_rows / max_new_rows, HSTU's delta_rows /
+        max_delta_rows; `names` is that pair, so every message names the caller's arguments) -> (counts, uniform, on_device).
+        `max_rows`, when given, is an int in [1, N].  `rows` on the host: an int (uniform True), or B ints as a list or tensor of a
+        dtype in `int_dtypes`; they must lie in [1, N] (`upper` words the bound in the message) and come back as an int64 host
+        tensor (B,).  A DEVICE tensor needs max_rows, is checked for dtype and shape only and comes back as it is, on_device True:
+        M is then max_rows, and what is held against the values, and where violations are counted, is the encoder's.  The encoder
+        puts its own checks of host counts between this and _finish_row_counts.  Touches neither a device nor the library."""
+        rows_name, max_name = names
+        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, int) or not 1 <= max_rows <= N):
+            raise ValueError(f"{max_name} must be an int in [1, {N}], got {max_rows!r}")
+        if rows is None:
+            raise ValueError(f"{max_name} needs {rows_name}=")
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            if max_rows is None:
+                raise ValueError(f"{rows_name} on the device needs {max_name}=M (an int): the number of work rows is a host-side launch size")
+            if rows.dtype not in int_dtypes or rows.shape != (B,):
+                raise ValueError(f"{rows_name} must be an integer tensor of shape ({B},), got {rows.dtype} {tuple(rows.shape)}")
+            return rows, False, True
+        uniform = isinstance(rows, int) and not isinstance(rows, bool)
+        if uniform:
+            counts = torch.full((B,), rows, dtype=torch.int64)
+        else:
+            try:
+                counts = torch.as_tensor(rows)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise ValueError(f"{rows_name} must be an int, or {B} ints as a list or tensor: {e}") from None
+            if counts.dtype not in int_dtypes or counts.shape != (B,):
+                raise ValueError(f"{rows_name} must be an integer tensor of shape ({B},), got {counts.dtype} {tuple(counts.shape)}")
+            counts = counts.to(torch.int64)
+        if B and (int(counts.min()) < 1 or int(counts.max()) > N):
+            raise ValueError(f"{rows_name} must lie in [1, {upper}] (got min {int(counts.min())}, max {int(counts.max())}, seq_len {N})")
+        return counts, uniform, False
+
+    @staticmethod
+    def _finish_row_counts(counts: torch.Tensor, uniform: bool, max_rows, names):
+        """Second half, for host counts: `max_rows` must not be less than the largest count -> (counts, M).  M: max_rows, else the
+        largest count; counts: None when every sequence has M rows, else the tensor."""
+        rows_name, max_name = names
+        top = int(counts.max()) if counts.numel() else 1
+        if max_rows is not None and max_rows < top:
+            raise ValueError(f"{max_name} {max_rows} is less than the largest {rows_name} {top}")
+        M = top if max_rows is None else max_rows
+        return (None if uniform and M == top else counts), M
 
     @staticmethod
     def _last_rows(lengths: torch.Tensor, N: int) -> torch.Tensor:

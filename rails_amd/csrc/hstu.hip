@@ -76,27 +76,7 @@ __global__ __launch_bounds__(256) void rows_normalize_kernel(const float* __rest
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;
-  const float* xr = x + (row_index ? row_index[r] : r) * ldx;
-  if (mode == 0) {
-    float s = 0.0f;
-    for (int k = lane; k < D; k += 64) s += xr[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s / (float)D;
-    float v = 0.0f;
-    for (int k = lane; k < D; k += 64) { const float c = xr[k] - mean; v = __builtin_fmaf(c, c, v); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const float rstd = 1.0f / sqrtf(v / (float)D + eps);
-    for (int k = lane; k < D; k += 64) out[r * D + k] = (xr[k] - mean) * rstd;
-  } else {
-    float v = 0.0f;
-    for (int k = lane; k < D; k += 64) v = __builtin_fmaf(xr[k], xr[k], v);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const float nrm = fmaxf(sqrtf(v), eps);
-    for (int k = lane; k < D; k += 64) out[r * D + k] = xr[k] / nrm;
-  }
+  normalize_row(x + (row_index ? row_index[r] : r) * ldx, D, mode, eps, out + r * D, lane);
 }
 
 struct GemmArgs {
@@ -1198,30 +1178,10 @@ __global__ __launch_bounds__(kDecThreads) void hstu_decode_kernel(DecodeArgs a) 
   }
 
   // ---- postprocessor on the last layer's outputs row at len - 1 (the cached row, never written by this launch, when p < len - 1):
-  // one wave, the arithmetic of rows_normalize_kernel step for step, so that a stale row gives the prefill's result bit for bit
+  // one wave, normalize_row as in rows_normalize_kernel, so that a stale row gives the prefill's result bit for bit
   if (wave != 0) return;
   const float* xr = p == len - 1 ? xs : a.layers[a.n_blocks - 1].outputs + (off + len - 1) * D;
-  float* o = a.out + (int64_t)b * D;
-  if (a.mode == 0) {
-    float sm = 0.0f;
-    for (int k = lane; k < D; k += 64) sm += xr[k];
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) sm += __shfl_xor(sm, s, 64);
-    const float mean = sm / (float)D;
-    float v = 0.0f;
-    for (int k = lane; k < D; k += 64) { const float c = xr[k] - mean; v = __builtin_fmaf(c, c, v); }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    const float rstd = 1.0f / sqrtf(v / (float)D + a.eps);
-    for (int k = lane; k < D; k += 64) o[k] = (xr[k] - mean) * rstd;
-  } else {
-    float v = 0.0f;
-    for (int k = lane; k < D; k += 64) v = __builtin_fmaf(xr[k], xr[k], v);
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    const float nrm = fmaxf(sqrtf(v), a.eps);
-    for (int k = lane; k < D; k += 64) o[k] = xr[k] / nrm;
-  }
+  normalize_row(xr, D, a.mode, a.eps, a.out + (int64_t)b * D, lane);
 }
 
 bool hstu_decode_supported(int N, int D, int H, int dqk, int dv, int num_buckets) {

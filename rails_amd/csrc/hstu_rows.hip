@@ -6,7 +6,8 @@
 //
 // A WORK ROW is a (sequence, position) pair in one of B * M fixed slots (M = max_rows): slot r = b * M + t is active iff sequence b
 // is valid and t < m_b, and stands for position p_b + t.  m_b = counts[b] (M when there is no count array) clamped on the device into
-// [1, min(M, len_b - p_b)].  The scheme is kvdec.hip's: a row tile resolves its 32 slots into an LDS table once (sequence, position,
+// [1, min(M, len_b - p_b)].  The scheme is kvdec.hip's (the staging loop is written out in both files, the LayerNorm statistics
+// of a staged row are encoder_device.h's row_ln_stats): a row tile resolves its 32 slots into an LDS table once (sequence, position,
 // jagged row; -1 for an idle slot); an idle slot stages zeros and writes nothing, and its attention workgroup exits before its
 // first barrier.  A row's arithmetic depends on neither its slot nor M, so one step over m rows is bit for bit m steps of one row.
 //
@@ -24,8 +25,8 @@
 //                          (row p's own k / v were written by the launch in front); the bucket is a binary search over the
 //                          thresholds staged in LDS
 //   hsturows_gemm_kernel<1> x <- (u * LN(a)) W_o^T + b_o + x, also into the cache's outputs[off_b + p]: the next layer's input
-// then hsturows_post_kernel: rows_normalize_kernel's arithmetic on the last layer's outputs row at len_b - 1 (fresh when the run
-// reaches it, the cached row otherwise).  A layer's attention of row p + 1 needs that layer's fresh k / v of row p: the projection
+// then hsturows_post_kernel: normalize_row (encoder_device.h, the prefill's postprocessor) on the last layer's outputs row at
+// len_b - 1 (fresh when the run reaches it, the cached row otherwise).  A layer's attention of row p + 1 needs that layer's fresh k / v of row p: the projection
 // launch in front of it, on the same stream, wrote them; each row's own key limit j <= p keeps the new rows causal among themselves.
 //
 // The row GEMMs are plain fmaf tiles (a lane per output column, eight rows per wave broadcast from LDS, four partial sums k mod 4
@@ -53,10 +54,10 @@ constexpr int kRowsMaxHead = 32;           // dqk, dv
 constexpr int kRowsMaxBuckets = 255;
 constexpr int kRowsKBatch0 = 32;           // weights of a lane's column loaded ahead of their FMAs: the uvqk projection (one per load)
 constexpr int kRowsKBatch1 = 64;           // ... and the output projection (four per load)
-constexpr int kRowsStageBatch = 8;         // global loads in flight per thread while the A rows are staged
 constexpr int kRowsScanThreads = 1024;
 constexpr int kRowsMaxGridY = 65535;
 constexpr int64_t kRowsMaxSlots = RAILS_HSTU_DECODE_MAX_ROWS;
+static_assert(kRowsTile == kTileRows && kRowsThreads == kTileThreads, "the staging loop is written out here and in kvdec.hip for one geometry");
 static_assert(kRowsMaxSlots == (int64_t)kRowsMaxGridY * kRowsTile, "rails_amd.h states the grid limit");
 static_assert(kRowsMaxSlots * kRowsThreads < (1LL << 32), "the attention grid has its work rows on x");
 
@@ -169,19 +170,10 @@ __device__ __forceinline__ void rows_resolve(const RowsArgs& a, const RowsLds& l
   __syncthreads();
 }
 
-// LayerNorm statistics of each staged row (no affine, biased variance, two-pass), a wave per row
+// LayerNorm statistics of each staged row (row_ln_stats), a wave per row
 __device__ __forceinline__ void rows_stats(const RowsLds& l, int K, int ks, float eps) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < kRowsTile; r += kRowsWaves) {
-    const float* row = l.As + r * ks;
-    float sm = 0.0f;
-    for (int k = lane; k < K; k += 64) sm += row[k];
-    const float mean = wave_sum(sm) / (float)K;
-    float vr = 0.0f;
-    for (int k = lane; k < K; k += 64) { const float c = row[k] - mean; vr = __builtin_fmaf(c, c, vr); }
-    vr = wave_sum(vr);
-    if (lane == 0) { l.mean_s[r] = mean; l.rstd_s[r] = 1.0f / sqrtf(vr / (float)K + eps); }
-  }
+  for (int r = wave; r < kRowsTile; r += kRowsWaves) row_ln_stats(l.As + r * ks, K, eps, l.mean_s + r, l.rstd_s + r, lane);
   __syncthreads();
 }
 
@@ -205,7 +197,7 @@ __global__ __launch_bounds__(kRowsThreads) void hsturows_gemm_kernel(RowsArgs a)
   rows_resolve(a, l, r0, nr);
   auto live = [&](int r) -> bool { return l.slot_p[r] >= 0; };   // idle slots and tile rows past the last slot: -1
 
-  // ---- stage the A rows (zeros past K and in idle slots); kRowsStageBatch global loads in flight per thread
+  // ---- stage the A rows (zeros past K and in idle slots), then the LayerNorm statistics of each row, a wave per row
   const float emb_scale = sqrtf((float)D);
   auto load = [&](int i) -> float {
     const int r = i / ks, k = i - r * ks;
@@ -215,12 +207,12 @@ __global__ __launch_bounds__(kRowsThreads) void hsturows_gemm_kernel(RowsArgs a)
     const int64_t prow = (int64_t)l.slot_b[r] * N + l.slot_p[r];   // x = [id != 0] (emb * sqrt(D) + pos_emb[p])
     return a.ids[prow] != 0 ? a.emb[prow * D + k] * emb_scale + a.pos_emb[(int64_t)l.slot_p[r] * D + k] : 0.0f;
   };
-  for (int i0 = tid; i0 < kRowsTile * ks; i0 += kRowsStageBatch * kRowsThreads) {
-    float v[kRowsStageBatch];
+  for (int i0 = tid; i0 < kRowsTile * ks; i0 += kStageBatch * kRowsThreads) {   // the loop of kvdec.hip's kv_rows_kernel, written out there too
+    float v[kStageBatch];
 #pragma unroll
-    for (int u = 0; u < kRowsStageBatch; ++u) v[u] = i0 + u * kRowsThreads < kRowsTile * ks ? load(i0 + u * kRowsThreads) : 0.0f;
+    for (int u = 0; u < kStageBatch; ++u) v[u] = i0 + u * kRowsThreads < kRowsTile * ks ? load(i0 + u * kRowsThreads) : 0.0f;
 #pragma unroll
-    for (int u = 0; u < kRowsStageBatch; ++u)
+    for (int u = 0; u < kStageBatch; ++u)
       if (i0 + u * kRowsThreads < kRowsTile * ks) As[i0 + u * kRowsThreads] = v[u];
   }
   __syncthreads();
@@ -408,8 +400,8 @@ __global__ __launch_bounds__(kRowsThreads) void hsturows_attn_kernel(RowsArgs a)
   }
 }
 
-// the postprocessor of sequence b (one wave), rows_normalize_kernel's arithmetic step for step on the last layer's outputs row at
-// len - 1; NaN for a sequence left alone
+// the postprocessor of sequence b (one wave): normalize_row, as the prefill's rows_normalize_kernel, on the last layer's outputs row
+// at len - 1; NaN for a sequence left alone
 __global__ __launch_bounds__(64) void hsturows_post_kernel(RowsArgs a) {
   const int b = blockIdx.x, lane = threadIdx.x, D = a.D;
   float* o = a.out + (int64_t)b * D;
@@ -418,27 +410,7 @@ __global__ __launch_bounds__(64) void hsturows_post_kernel(RowsArgs a) {
     for (int k = lane; k < D; k += 64) o[k] = __builtin_nanf("");
     return;
   }
-  const float* xr = a.layers[a.n_blocks - 1].outputs + (off + a.lengths[b] - 1) * D;
-  if (a.mode == 0) {
-    float sm = 0.0f;
-    for (int k = lane; k < D; k += 64) sm += xr[k];
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) sm += __shfl_xor(sm, s, 64);
-    const float mean = sm / (float)D;
-    float v = 0.0f;
-    for (int k = lane; k < D; k += 64) { const float c = xr[k] - mean; v = __builtin_fmaf(c, c, v); }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    const float rstd = 1.0f / sqrtf(v / (float)D + a.eps);
-    for (int k = lane; k < D; k += 64) o[k] = (xr[k] - mean) * rstd;
-  } else {
-    float v = 0.0f;
-    for (int k = lane; k < D; k += 64) v = __builtin_fmaf(xr[k], xr[k], v);
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    const float nrm = fmaxf(sqrtf(v), a.eps);
-    for (int k = lane; k < D; k += 64) o[k] = xr[k] / nrm;
-  }
+  normalize_row(a.layers[a.n_blocks - 1].outputs + (off + a.lengths[b] - 1) * D, D, a.mode, a.eps, o, lane);
 }
 
 template <int MODE>

@@ -341,44 +341,24 @@ class HSTU(Encoder):
     def _delta_counts(self, delta_rows, max_delta_rows, delta_x_offsets, past_lengths, B: int, N: int):
         """(counts, M, checked) of a multi-row step, without touching a device unless the data lives there: counts an int64 tensor (B,)
         (on the host, or the caller's device tensor), or None for M rows of every sequence; checked: the runs were held against the
-        lengths here.  Raises for whatever the host can see; the rest is counted and clamped on the device (mirrors SASRec._new_rows)."""
-        ints = (torch.int32, torch.int64)
-        if max_delta_rows is not None and (isinstance(max_delta_rows, bool) or not isinstance(max_delta_rows, int) or not 1 <= max_delta_rows <= N):
-            raise ValueError(f"max_delta_rows must be an int in [1, {N}], got {max_delta_rows!r}")
-        if delta_rows is None:
-            raise ValueError("max_delta_rows needs delta_rows=")
-        if isinstance(delta_rows, torch.Tensor) and delta_rows.is_cuda:
-            if max_delta_rows is None:
-                raise ValueError("delta_rows on the device needs max_delta_rows=M (an int): the number of work rows is a host-side launch size")
-            if delta_rows.dtype not in ints or delta_rows.shape != (B,):
-                raise ValueError(f"delta_rows must be an integer tensor of shape ({B},), got {delta_rows.dtype} {tuple(delta_rows.shape)}")
-            return delta_rows, max_delta_rows, False
-        uniform = isinstance(delta_rows, int) and not isinstance(delta_rows, bool)
-        if uniform:
-            counts = torch.full((B,), delta_rows, dtype=torch.int64)
-        else:
-            try:
-                counts = torch.as_tensor(delta_rows)
-            except (TypeError, ValueError, RuntimeError) as e:
-                raise ValueError(f"delta_rows must be an int, or {B} ints as a list or tensor: {e}") from None
-            if counts.dtype not in ints or counts.shape != (B,):
-                raise ValueError(f"delta_rows must be an integer tensor of shape ({B},), got {counts.dtype} {tuple(counts.shape)}")
-            counts = counts.to(torch.int64)
-        top = int(counts.max()) if B else 1
-        if B and (int(counts.min()) < 1 or top > N):
-            raise ValueError(f"delta_rows must lie in [1, past_lengths - position] (got min {int(counts.min())}, max {top}, seq_len {N})")
-        if max_delta_rows is not None and max_delta_rows < top:
-            raise ValueError(f"max_delta_rows {max_delta_rows} is less than the largest delta_rows {top}")
+        lengths here.  Raises for whatever the host can see; the rest is counted and clamped on the device (Encoder._parse_row_counts
+        and _finish_row_counts hold the contract SASRec's new_rows shares; the runs against the lengths are this encoder's)."""
+        names = ("delta_rows", "max_delta_rows")
+        counts, uniform, on_device = self._parse_row_counts(delta_rows, max_delta_rows, B, N, names, (torch.int32, torch.int64),
+                                                            "past_lengths - position")
+        if on_device:
+            return counts, max_delta_rows, False
+        counts, M = self._finish_row_counts(counts, uniform, max_delta_rows, names)
         pos = delta_x_offsets[1] if isinstance(delta_x_offsets, (tuple, list)) and len(delta_x_offsets) == 2 else None
         pos = torch.as_tensor(pos) if pos is not None else None
         checked = pos is not None and pos.shape == (B,) and ((not past_lengths.is_cuda and not pos.is_cuda) or type(self).STRICT_DEVICE_LENGTHS)
         if checked:
             lh, p = past_lengths.to(dtype=torch.int64).cpu(), pos.to(dtype=torch.int64).cpu()
-            if bool((p + counts > lh).any()):
-                b = int((p + counts > lh).nonzero()[0])
-                raise ValueError(f"delta rows [{int(p[b])}, {int(p[b] + counts[b])}) of sequence {b} end past its length {int(lh[b])}")
-        M = top if max_delta_rows is None else max_delta_rows
-        return (None if uniform and M == top else counts), M, checked
+            ends = p + (M if counts is None else counts)   # counts None: M rows of every sequence
+            if bool((ends > lh).any()):
+                b = int((ends > lh).nonzero()[0])
+                raise ValueError(f"delta rows [{int(p[b])}, {int(ends[b])}) of sequence {b} end past its length {int(lh[b])}")
+        return counts, M, checked
 
     def extend_cache_states(self, cache, old_lengths, new_lengths) -> List[CacheState]:
         """The states of `cache` (laid out for old_lengths) laid out for new_lengths: every jagged `v` / `outputs` becomes (sum new, .)

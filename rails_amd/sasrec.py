@@ -248,49 +248,29 @@ class SASRec(Encoder):
         _lengths' result (on the device, in range).  Counts on the host raise here when out of range; counts on the device are
         counted, the kernels clamp them, and nothing is read back (unless STRICT_DEVICE_LENGTHS)."""
         dev = lengths.device
-        if max_new_rows is not None and (isinstance(max_new_rows, bool) or not isinstance(max_new_rows, int) or not 1 <= max_new_rows <= N):
-            raise ValueError(f"max_new_rows must be an int in [1, {N}], got {max_new_rows!r}")
         strict = type(self).STRICT_DEVICE_LENGTHS
-        if isinstance(new_rows, torch.Tensor) and new_rows.is_cuda:
-            if max_new_rows is None:
-                raise ValueError("new_rows on the device needs max_new_rows=M (an int): the number of work rows is a host-side launch size")
-            if new_rows.dtype not in _INT_DTYPES or new_rows.shape != (B,):
-                raise ValueError(f"new_rows must be an integer tensor of shape ({B},), got {new_rows.dtype} {tuple(new_rows.shape)}")
-            counts = new_rows.to(device=dev, dtype=torch.int64).contiguous()
-            bad = (counts < 1) | (counts > lengths.clamp(max=max_new_rows))
+        names = ("new_rows", "max_new_rows")
+        counts, uniform, on_device = self._parse_row_counts(new_rows, max_new_rows, B, N, names, _INT_DTYPES, "past_lengths")
+        if on_device:
+            M = max_new_rows
+            counts = counts.to(device=dev, dtype=torch.int64).contiguous()
+            bad = (counts < 1) | (counts > lengths.clamp(max=M))
             if strict:
                 if bool(bad.any()):
                     raise ValueError(f"new_rows must lie in [1, min(max_new_rows, past_lengths)] (got min {int(counts.min())}, max {int(counts.max())})")
             else:
                 self._count_violations(dev, bad.sum())
-            return counts, max_new_rows
-        uniform = isinstance(new_rows, int) and not isinstance(new_rows, bool)
-        if uniform:
-            counts = torch.full((B,), new_rows, dtype=torch.int64)
-        else:
-            try:
-                counts = torch.as_tensor(new_rows)
-            except (TypeError, ValueError, RuntimeError) as e:
-                raise ValueError(f"new_rows must be an int, or {B} ints as a list or tensor: {e}") from None
-            if counts.dtype not in _INT_DTYPES or counts.shape != (B,):
-                raise ValueError(f"new_rows must be an integer tensor of shape ({B},), got {counts.dtype} {tuple(counts.shape)}")
-            counts = counts.to(torch.int64)
-        top = int(counts.max()) if B else 1
-        if B and (int(counts.min()) < 1 or top > N):
-            raise ValueError(f"new_rows must lie in [1, past_lengths] (got min {int(counts.min())}, max {top}, seq_len {N})")
+            return counts, M
+        # the lengths host counts are held against: the host's own, device lengths only when strict
         len_h = past_lengths.to(torch.int64) if not past_lengths.is_cuda else lengths.cpu() if strict else None
         if len_h is not None and bool((counts > len_h).any()):
             b = int((counts > len_h).nonzero()[0])
             raise ValueError(f"new_rows must lie in [1, past_lengths]: sequence {b} has {int(counts[b])} new rows and length {int(len_h[b])}")
-        if max_new_rows is not None and max_new_rows < top:
-            raise ValueError(f"max_new_rows {max_new_rows} is less than the largest new_rows {top}")
-        M = top if max_new_rows is None else max_new_rows
-        if uniform and M == top:
-            counts = None
-        else:
+        counts, M = self._finish_row_counts(counts, uniform, max_new_rows, names)
+        if counts is not None:
             counts = counts.to(dev)
         if len_h is None:   # device lengths: a count past a sequence's length is clamped by the kernels, and counted here
-            self._count_violations(dev, (lengths < (top if counts is None else counts)).sum())
+            self._count_violations(dev, (lengths < (M if counts is None else counts)).sum())
         return counts, M
 
     def _decode(self, past_lengths, past_ids, past_embeddings, cache, new_rows=None, max_new_rows: Optional[int] = None) -> torch.Tensor:

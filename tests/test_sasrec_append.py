@@ -168,21 +168,23 @@ def test_new_rows_api_errors(monkeypatch):
 
 
 def test_slot_kernels_use_no_scratch_and_no_more_registers():
-    """The kvslot_* kernels (the slot scheme beside the single-row kvdec_* ones): twelve, no scratch, and the VGPRs of their
-    single-row twins."""
+    """The slot-scheme instances of the decode kernels (kv_rows_kernel / kv_attn_kernel over KvSlotArgs, kvslot_post_kernel) beside
+    the single-row ones (over KvDecArgs, kvdec_post_kernel): twelve, no scratch, and the VGPRs of their single-row twins."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     llvm = "/opt/rocm/lib/llvm/bin"
     if not (os.path.exists(os.path.join(llvm, "llvm-readelf")) and os.path.exists(os.path.join(llvm, "clang-offload-bundler"))):
         pytest.skip("LLVM tools of the ROCm image not found")
     if not os.path.exists(os.path.join(root, "rails_amd", "csrc", "kvdec.o")):
         pytest.skip("objects not built (python -c 'import __graft_entry__ as g; g.build()')")
-    out = subprocess.run(["bash", os.path.join(root, "tools", "kernel_resources.sh"), "kvslot|kvdec"], capture_output=True, text=True,
-                         timeout=600).stdout
-    rows = [re.match(r"vgpr\s+(\d+) agpr\s+\d+ sgpr\s+\d+ scratch\s+(\d+) lds\s+\d+\s+(?:void )?mol::(kv\w+?)_(\w+_kernel(?:<[^>]*>)?)", line.strip())
-            for line in out.splitlines()]
-    got = {(m.group(3), m.group(4)): (int(m.group(1)), int(m.group(2))) for m in rows if m}
-    slot = {k[1]: v for k, v in got.items() if k[0] == "kvslot"}
-    single = {k[1]: v for k, v in got.items() if k[0] == "kvdec"}
+    out = subprocess.run(["bash", os.path.join(root, "tools", "kernel_resources.sh"), "kv_rows_kernel|kv_attn_kernel|kvslot_post|kvdec_post"],
+                         capture_output=True, text=True, timeout=600).stdout
+    # an instance's twin key: its name and template arguments without the SLOTS flag and the argument block (kv_rows_kernel<0, true>),
+    # the post kernels' without their prefix; it is a slot instance iff it takes a KvSlotArgs
+    rows = [re.match(r"vgpr\s+(\d+) agpr\s+\d+ sgpr\s+\d+ scratch\s+(\d+) lds\s+\d+\s+(?:void )?mol::(?:kvdec_|kvslot_)?(\w+_kernel)"
+                     r"(?:<(.*?), (?:true|false), mol::Kv\w+Args>)?\((mol::Kv(?:Slot|Dec)Args|float const\*)", line.strip()) for line in out.splitlines()]
+    got = {(m.group(5) == "mol::KvSlotArgs", m.group(3), m.group(4)): (int(m.group(1)), int(m.group(2))) for m in rows if m}
+    slot = {k[1:]: v for k, v in got.items() if k[0]}
+    single = {k[1:]: v for k, v in got.items() if not k[0]}
     assert len(slot) == 12 and set(slot) == set(single), out
-    assert all(scratch == 0 for _, scratch in slot.values()), slot
+    assert all(scratch == 0 for _, scratch in list(slot.values()) + list(single.values())), (slot, single)
     assert all(slot[k][0] <= single[k][0] for k in slot), (slot, single)

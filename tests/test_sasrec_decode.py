@@ -170,11 +170,12 @@ def test_new_kernels_use_no_scratch():
         pytest.skip("LLVM tools of the ROCm image not found")
     if not os.path.exists(os.path.join(ROOT, "rails_amd", "csrc", "kvdec.o")):
         pytest.skip("objects not built (python -c 'import __graft_entry__ as g; g.build()')")
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), "kvdec"], capture_output=True, text=True,
+    # the single-row step's kernels: the instances over its argument block KvDecArgs, and its post kernel
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), "KvDecArgs|kvdec_post_kernel"], capture_output=True, text=True,
                          timeout=600).stdout
     rows = [re.match(r"vgpr\s+\d+ agpr\s+\d+ sgpr\s+\d+ scratch\s+(\d+) lds\s+\d+\s+(.*)$", line.strip()) for line in out.splitlines()]
     rows = [(m.group(2), int(m.group(1))) for m in rows if m]
     names = " ".join(n for n, _ in rows)
-    assert "kvdec_rows_kernel" in names and "kvdec_attn_kernel" in names and "kvdec_post_kernel" in names, out
+    assert "kv_rows_kernel" in names and "kv_attn_kernel" in names and "kvdec_post_kernel" in names, out
     assert len(rows) == 12 and all(s == 0 for _, s in rows), rows
     assert not any("sasrec" in n for n, _ in rows)   # tests/test_sasrec.py counts the kernels whose names hold that word
