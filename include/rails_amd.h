@@ -56,7 +56,7 @@ extern "C" {
  * and the rank entries rails_scores_rank_keys / rails_scores_rank / rails_item_mask_clear_rows
  * and the softmax entries rails_scores_lse[_workspace_bytes] / rails_scores_log_prob / rails_scores_gumbel
  * and the range-search entries rails_scores_range_workspace_bytes / rails_scores_range_count / _write / _sort / _decode
- * and the query-fusion entries rails_scores_fuse_rows / rails_topk_fuse_lists
+ * and the query-fusion entries rails_scores_fuse_rows / rails_topk_fuse_lists / rails_lists_union
  * and the multi-row SASRec decode step rails_sasrec_decode_rows / RAILS_SASREC_DECODE_MAX_ROWS (rails_sasrec_decode is its max_new = 1 call,
  * bit for bit what it was)
  * and the diversity entries rails_topk_mmr / rails_topk_mmr_workspace_bytes
@@ -523,6 +523,16 @@ int rails_scores_fuse_rows(const float* scores, int64_t ld, int32_t rows_in, int
 int rails_topk_fuse_lists(const float* scores, int64_t ld, const int64_t* positions, int32_t rows_in, int32_t depth, const int64_t* lims, int32_t n_out,
                           int32_t max_segment, int64_t n_items, const int64_t* ids, const int64_t* invalid_ids, int32_t width, int32_t k, int64_t* out_ids,
                           float* out_scores, void* stream);
+/* The union of candidate lists: positions (rows_in, width) int64 with row stride ld -- row r's candidate positions, in any order, duplicates
+ * allowed (int64 is what every candidate scan hands over; there is no int32 form).  Per fused row, one workgroup: the entries of its segment
+ * with a position in [0, n_items) are sorted in LDS and the first of every run of equal positions is kept: out[u * w_out .. + counts[u]) holds
+ * the segment's distinct positions ascending, out[u * w_out + counts[u] .. + w_out) holds -1.  counts (n_out int32) may be NULL.
+ * max_segment: at least the largest lims[u + 1] - lims[u]; it sizes the launch's LDS, and a longer segment is cut to it.  One launch, no
+ * atomics, no scratch, no host read.  n_out = 0: nothing to do.  RAILS_EINVAL for a NULL pointer, a size below 1 (rows_in, n_out, n_items
+ * below 0), ld < width or w_out < max_segment * width; RAILS_ENOTSUP (nothing launched) for max_segment * width > 16 384 or
+ * n_items > 2^32 - 1. */
+int rails_lists_union(const int64_t* positions, int64_t ld, int32_t rows_in, int32_t width, const int64_t* lims, int32_t n_out, int32_t max_segment,
+                      int64_t n_items, int64_t* out, int32_t w_out, int32_t* counts, void* stream);
 
 /* Per-row candidates: out[bq * n_cand + x] = <queries[bq], items[bq / r][x]> for queries (n_queries, dim) and items
  * (n_queries / r, n_cand, dim) -- the two bmm branches of DotProductSimilarity.forward

@@ -1017,6 +1017,19 @@ int rails_topk_fuse_lists(const float* scores, int64_t ld, const int64_t* positi
   return r == kOk ? r : fail(r, "topk_fuse_lists");
 }
 
+int rails_lists_union(const int64_t* positions, int64_t ld, int32_t rows_in, int32_t width, const int64_t* lims, int32_t n_out, int32_t max_segment,
+                      int64_t n_items, int64_t* out, int32_t w_out, int32_t* counts, void* stream) {
+  g_err[0] = '\0';
+  if (rows_in < 0 || width < 1 || n_out < 0 || max_segment < 1 || n_items < 0 || ld < width || w_out < 1) {
+    set_error("lists_union: bad size (rows_in = %d, width = %d, n_out = %d, max_segment = %d, n_items = %lld, ld = %lld, w_out = %d)", rows_in, width, n_out,
+              max_segment, (long long)n_items, (long long)ld, w_out);
+    return RAILS_EINVAL;
+  }
+  if (n_out == 0) return RAILS_OK;
+  if (!lims || !out || (rows_in > 0 && !positions)) { set_error("lists_union: NULL pointer"); return RAILS_EINVAL; }
+  return fail(lists_union(positions, ld, width, rows_in, lims, n_out, max_segment, n_items, out, w_out, counts, (hipStream_t)stream), "lists_union");
+}
+
 size_t rails_mol_coarse_table_bytes(const rails_mol_shape* s, int64_t n_items) {
   if (!shape_ok(s) || n_items < 0) return 0;
   return (size_t)n_items * (size_t)s->dot_product_dimension * 2;

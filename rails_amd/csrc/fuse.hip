@@ -16,6 +16,9 @@
 //                             top (k + w) -- so the lists hold every answer.  Entries sorted in LDS by (position, orderable(score)) descending:
 //                             the head of each position run is that position's best; heads become make_key(score, position), the rest key 0; a
 //                             second sort puts them in selection order; the first k whose id is not among the row's seen ids are written.
+//   lists_union_kernel        the candidate union of the approximate modules' fused calls (rails_lists_union): one workgroup per fused row sorts
+//                             its sub-query rows' candidate positions in LDS and writes the distinct ones ascending -- the columns on which the
+//                             rows of a segment are scored, so that scores_fuse_rows_kernel fuses aligned columns.
 // Plain C++ with vector stores; every index is tested before it is used.
 #include <hip/hip_runtime.h>
 
@@ -251,6 +254,66 @@ int topk_fuse_lists(const float* scores, int64_t ld, const int64_t* positions, i
   if (ensure_dyn_lds(once, reinterpret_cast<const void*>(&topk_fuse_lists_kernel), max_lds) != kOk) return kErrLaunch;
   hipLaunchKernelGGL(topk_fuse_lists_kernel, dim3(n_out), dim3(kListThreads), lds, stream, scores, ld, positions, rows_in, depth, lims, npad, sort_slots, look,
                      n_items, ids, invalid, width, k, out_ids, out_scores);
+  return launched();
+}
+
+// ---- the candidate union ---------------------------------------------------------------------------------------------------------------------
+// One workgroup of kListThreads per fused row merges the ragged candidate lists of its sub-query rows (W positions each) into one sorted,
+// duplicate-free list.  npad keys in LDS as for the list merge, then npad head bytes.  An entry takes part iff its position lies in
+// [0, n_items).
+//   sort    key 2^32 - position (n_items <= 2^32 - 1: never 0), descending: positions ascending, the copies of one position side by side, the
+//           dropped entries (key 0) last
+//   heads   the first key of every run of equal positions
+//   emit    a prefix scan over the head flags compacts them: out[u, 0 : count) the distinct positions ascending, -1 behind them up to w_out
+__global__ void __launch_bounds__(kListThreads) lists_union_kernel(const int64_t* __restrict__ positions, int64_t ld, int width, int64_t rows_in,
+                                                                  const int64_t* __restrict__ lims, int npad, int sort_slots, int64_t n_items,
+                                                                  int64_t* __restrict__ out, int w_out, int32_t* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) u64 keys[];
+  unsigned char* head = reinterpret_cast<unsigned char*>(keys + sort_slots);      // [npad]
+  __shared__ int wave_tot[kListThreads / 64];
+  const int tid = threadIdx.x;
+  const int64_t u = blockIdx.x;
+  int64_t begin, end;
+  segment_of(lims, u, rows_in, begin, end);
+  const int64_t count64 = (end - begin) * width;
+  const int count = count64 < npad ? (int)count64 : npad;      // (the host sized npad by the largest segment: never cut on a checked call)
+
+  for (int i = tid; i < npad; i += kListThreads) {
+    u64 kv = 0ull;
+    if (i < count) {
+      const int64_t p = positions[(begin + i / width) * ld + i % width];
+      if (p >= 0 && p < n_items) kv = 0x100000000ull - (u64)p;
+    }
+    keys[i] = kv;
+  }
+  __syncthreads();
+  lds_sort_desc(keys, npad);      // (ends with a barrier)
+
+  for (int i = tid; i < npad; i += kListThreads) {
+    const u64 kv = keys[i];
+    head[i] = (kv != 0ull && (i == 0 || keys[i - 1] != kv)) ? 1 : 0;
+  }
+  __syncthreads();
+  int64_t* orow = out + u * (int64_t)w_out;
+  const int total = emit_first_k<kListThreads>(
+      head, npad, w_out, wave_tot, [&](int i, int o) { orow[o] = (int64_t)(0x100000000ull - keys[i]); }, [&](int e) { orow[e] = -1; });
+  if (counts != nullptr && tid == 0) counts[u] = total;
+}
+
+int lists_union(const int64_t* positions, int64_t ld, int width, int64_t rows_in, const int64_t* lims, int n_out, int max_segment, int64_t n_items,
+                int64_t* out, int w_out, int32_t* counts, hipStream_t stream) {
+  const int64_t entries = (int64_t)max_segment * width;
+  if (entries > kFuseListMaxEntries) { set_error("lists_union: %lld entries per fused row beyond %d", (long long)entries, kFuseListMaxEntries); return kErrUnsupported; }
+  if (n_items > 0xFFFFFFFFll) { set_error("lists_union: n_items = %lld, positions beyond 2^32 - 2", (long long)n_items); return kErrUnsupported; }
+  if (w_out < entries) { set_error("lists_union: bad size (w_out = %d below max_segment * width = %lld)", w_out, (long long)entries); return kErrInvalid; }
+  const int npad = next_pow2((int)entries, 64);
+  const int sort_slots = npad <= kSortThreads ? 3 * npad : npad;      // lds_sort_desc's exchange buffer
+  const int lds = sort_slots * (int)sizeof(u64) + npad;
+  constexpr int max_lds = kFuseListMaxEntries * (int)sizeof(u64) + kFuseListMaxEntries;
+  static DynLdsOnce once;
+  if (ensure_dyn_lds(once, reinterpret_cast<const void*>(&lists_union_kernel), max_lds) != kOk) return kErrLaunch;
+  hipLaunchKernelGGL(lists_union_kernel, dim3(n_out), dim3(kListThreads), lds, stream, positions, ld, width, rows_in, lims, npad, sort_slots, n_items, out, w_out,
+                     counts);
   return launched();
 }
 

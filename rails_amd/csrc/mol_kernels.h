@@ -310,6 +310,8 @@ int scores_fuse_rows(const float* scores, int64_t ld, int64_t rows_in, int64_t n
                      int64_t ld_out, const int32_t* run_if, hipStream_t stream);
 int topk_fuse_lists(const float* scores, int64_t ld, const int64_t* positions, int64_t rows_in, int depth, const int64_t* lims, int n_out, int max_segment,
                     int64_t n_items, const int64_t* ids, const int64_t* invalid, int width, int k, int64_t* out_ids, float* out_scores, hipStream_t stream);
+int lists_union(const int64_t* positions, int64_t ld, int width, int64_t rows_in, const int64_t* lims, int n_out, int max_segment, int64_t n_items,
+                int64_t* out, int w_out, int32_t* counts, hipStream_t stream);
 
 int dot_rowwise(const float* q, const float* items, int64_t Bq, int X, int D, int r, float* out, hipStream_t stream);
 

@@ -2028,6 +2028,35 @@ def topk_fuse_lists(scores: torch.Tensor, positions: torch.Tensor, lims, k: int,
     return out_i, out_s
 
 
+def lists_union(positions: torch.Tensor, lims, n_items: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The union of candidate lists per fused row (rails_lists_union): positions (S, W) int64 with unit column stride -- row r's candidate
+    positions, in any order, duplicates allowed -- -> (union (U, W_out) int64, counts (U,) int32): row u holds the distinct positions of its
+    segment inside [0, n_items) ascending, -1 behind them.  out: a contiguous (U, W_out) int64 tensor, W_out >= max_segment * W (default:
+    exactly that).  One launch; no sync beyond the read of lims.  NotImplementedError (nothing launched) beyond FUSE_LIST_MAX_ENTRIES entries
+    per fused row or positions beyond 2^32 - 2."""
+    if not torch.is_tensor(positions) or positions.dim() != 2 or positions.shape[1] < 1 or (positions.shape[1] > 1 and positions.stride(1) != 1):
+        raise ValueError("lists_union: positions must be (S, W) int64 with W >= 1 and contiguous rows")
+    _require_device(positions, "positions")
+    rows, width = positions.shape
+    _positions_arg("lists_union", positions, rows, positions.device, beside="query_lims", t="W")
+    ql = _query_lims_arg("lists_union", lims, rows, positions.device)
+    entries = ql.max_segment * width
+    if entries > FUSE_LIST_MAX_ENTRIES or n_items > (1 << 32) - 1:
+        raise NotImplementedError(f"lists_union: a fused row of {ql.max_segment} sub-query rows x {width} candidates = {entries} entries, {n_items} items: "
+                                  f"one workgroup sorts up to {FUSE_LIST_MAX_ENTRIES} entries with positions up to 2^32 - 2")
+    if out is None:
+        out = torch.empty((ql.fused, entries), dtype=torch.int64, device=positions.device)
+    elif (not torch.is_tensor(out) or out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != ql.fused or out.shape[1] < entries
+          or out.device != positions.device or not out.is_contiguous()):
+        raise ValueError(f"lists_union: out must be a contiguous ({ql.fused}, >= {entries}) int64 tensor on the positions' device")
+    counts = torch.empty((ql.fused,), dtype=torch.int32, device=positions.device)
+    ld = score_matrix_ld(rows, width, positions.stride(0))
+    with _on_device(positions.device):
+        _lib.check(_lib.load().rails_lists_union(_ptr(positions), ld, rows, width, _ptr(ql.dev), ql.fused, ql.max_segment, int(n_items), _ptr(out), out.shape[1],
+                                                 _ptr(counts), _stream()), "rails_lists_union")
+    return out, counts
+
+
 def tag_word_i32(word: int) -> int:
     """A 32-bit tag word as the int32 that holds its bit pattern."""
     return word - (1 << 32) if word >= 1 << 31 else word

@@ -326,7 +326,9 @@ def refuse_query_fusion(module, kwargs, what: Optional[str] = None) -> None:
     if given:
         name = type(module).__name__ + (" (IVF, use_faiss=True)" if getattr(module, "_use_faiss", False) else "") + ("" if what is None else "." + what)
         raise NotImplementedError(f"{name} takes no {given[0]}: fusing several query rows per user is built on the single-device MoLBruteForceTopK "
-                                  "and MIPSBruteForceTopK (forward, get_top_k_outputs, all_logits and the streaming score calls) only")
+                                  "and MIPSBruteForceTopK (forward, get_top_k_outputs, all_logits and the streaming score calls) only; the exhaustive "
+                                  "MoLAvgTopK / MoLNaiveTopK / MoLCombTopK fuse over the union of the rows' candidates in forward and get_top_k_outputs "
+                                  "once fuse_candidates = True is set on the instance")
 
 
 def _tag_ks(module) -> Tuple[int, ...]:
@@ -3240,7 +3242,89 @@ def _diversified_candidates(tk, query_embeddings: torch.Tensor, k: int, invalid_
     return walk.scores.to(query_embeddings.dtype), walk.ids
 
 
+# ---- query fusion over the candidate union: opt-in per instance, fuse_candidates = True -------------------------------------
+def _asks_fusion(tk, kwargs: dict) -> bool:
+    """Does this call go to _fused_candidates?  The switch is read through the class default, so a bare instance, and every module that was not
+    opted in, refuses query_lims= / fuse= / query_weights= by name exactly as before (refuse_query_fusion) and runs none of this code."""
+    return bool(tk.fuse_candidates) and any(kwargs.get(name) is not None for name in _FUSION_KWARGS)
+
+
+def _fused_candidates(tk, what: str, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict):
+    """The fused call of an approximate module -> (scores (U, k) fp32 as the queries' dtype, ids (U, k)).  Fused row u's candidates are the
+    union C_u of the candidates the module's own generator yields for the sub-query rows of its segment -- under the hidden set, and under the
+    fused row's allowed_tags= repeated over the segment --; every candidate is scored under every row of the segment (_score_at: the rerank's
+    bits), the scores are fused (engine.scores_fuse_rows on the aligned columns of the union) and ranked once: the first k of C_u in key order
+    (F descending, position ascending) whose id is not among the row's invalid_ids, (-1, -inf) where fewer remain.
+    The shape of _ComponentCandidates._ranked: the query pack once, two attempts around the speculative scans.  Beside the scans' launches:
+    the union, the expansion to the S rows, the scoring, the fusion, the holes and ids, the selection -- the same number whatever S is -- and
+    no host read beyond the scans' verdict.  Everything is checked before any launch."""
+    name = f"{type(tk).__name__}.{what}"
+    if getattr(tk, "_use_faiss", False):      # (the IVF lists: named by the refusal the module has always raised)
+        refuse_query_fusion(tk, kwargs, what)
+    fusion = tk._resolve_fusion(kwargs, query_embeddings, what)
+    kwargs.pop("_fusion", None)
+    for given in ("collapse_groups", "max_per_group", "diversify", "diversity_pool", "item_mask"):
+        value = kwargs.pop(given, None)
+        if value is not None and value is not False:
+            raise NotImplementedError(f"{name}: {given}= together with query_lims= is not built")
+    own = type(tk).forward is MoLAvgTopK.forward      # MoLAvgTopK itself: the coarse candidates; else the component union (MoLCombTopK: both)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"{name}: k must be an int >= 1, got {k!r}")
+    if own and k > tk._avg_top_k:
+        raise ValueError(f"avg_top_k ({tk._avg_top_k}) must be larger than k ({k})")
+    U, S, N = fusion.lims.fused, fusion.lims.rows, tk.num_items
+    width = tk._avg_top_k if own else tk._union_width()
+    entries = fusion.lims.max_segment * width
+    if entries > E.FUSE_LIST_MAX_ENTRIES:
+        raise NotImplementedError(f"{name}: a fused row of {fusion.lims.max_segment} sub-query rows x {width} candidates holds {entries} candidate entries, "
+                                  f"beyond the {E.FUSE_LIST_MAX_ENTRIES} one workgroup sorts; fuse fewer rows per user")
+    if invalid_ids is not None:
+        _ids_arg(what, "invalid_ids", invalid_ids, U, "w")
+    w = 0 if invalid_ids is None else invalid_ids.shape[1]
+    with torch.inference_mode(), tk.one_bind():
+        kw = tk._segment_kwargs(kwargs, fusion)      # allowed_tags= per fused row -> per sub-query row
+        tags = tk._take_allowed_tags(kw, S, (tk._avg_top_k,) if own else _tag_ks(tk))
+        eng = tk._bind()
+        qpack, eq, _ = eng.query_pack(query_embeddings, kw.get("user_ids"), want_plain=True)
+        dev = tk._ids_flat.device
+        rows_of = fusion.lims.fused_row_of().to(dev)
+        w_out = max(entries, k + w)      # (k + w columns at the least: the selection then never runs short of entries, holes included)
+        neg_inf, no_id = torch.full((), float("-inf"), dtype=torch.float32, device=dev), torch.full((), -1, dtype=torch.int64, device=dev)
+        for attempt in range(2):      # speculate on the fused scans, verify after everything is enqueued
+            pending: list = []
+            if own:
+                cand = tk._coarse_topk_from_eq(eq, False, pending, tags=tags)
+            else:
+                cand = tk._candidates(eq, pending) if tags is None else tk._candidates(eq, pending, tags)
+            union, _ = E.lists_union(cand.to(torch.int64), fusion.lims, N, out=torch.empty((U, w_out), dtype=torch.int64, device=dev))
+            hole = union < 0
+            safe = union.clamp_min(0)      # holes read item 0 and are overwritten below
+            scores = tk._score_at(eng, qpack, S, safe.index_select(0, rows_of))
+            fused = torch.where(hole, neg_inf, E.scores_fuse_rows(scores, fusion.lims, fusion.mode, fusion.weights))
+            ids = torch.where(hole, no_id, tk._ids_flat[safe])
+            if invalid_ids is None:
+                out_s, out_i = E.topk(fused, k, ids=ids)
+            elif E.topk_candidates_filterable(w_out, k + w, w, k):      # (the "positions" are the candidates' ids: no id table behind them)
+                out_i, out_s = E.topk_candidates_filtered(fused, k + w, ids, None, invalid_ids, k)
+            else:
+                top_s, top_i = E.topk(fused, k + w, ids=ids)
+                out_i, out_s = E.filter_seen_ids(top_i, top_s, invalid_ids, k)
+            if _verdicts_clear(pending, tk):
+                break
+            tk._no_fused = True
+        tk._no_fused = False
+    tk.__dict__.setdefault("_fuse_candidate_stats", {"fused_candidate_calls": 0})["fused_candidate_calls"] += 1
+    return out_s.to(query_embeddings.dtype), out_i
+
+
+def _fused_candidate_stats(tk) -> Dict[str, int]:
+    """fused_candidate_calls: the calls _fused_candidates answered so far; absent before the first one."""
+    return dict(tk.__dict__.get("_fuse_candidate_stats", {}))
+
+
 class MoLAvgTopK(MoLTopKModule):
+    fuse_candidates = False       # True (set on an instance): forward, forward_filtered and get_top_k_outputs take query_lims= / fuse= / query_weights=
+                                  # over the union of the sub-query rows' candidates (DESIGN section 3.20); every other call refuses them as before
     DEVICE_REDO_BYTES = 1 << 30   # materialised score matrices up to this size are kept as the device-side redo buffer of a fused scan;
                                   # beyond it (a 125 M-item shard: 16 GB) the counts are read on the host after the call is enqueued --
     DEVICE_REDO_FREE_FRACTION = 0.0    # > 0: larger buffers too, when they fit this fraction of the free memory.  Measured on a full config-5 shard (16 GB
@@ -3496,6 +3580,10 @@ class MoLAvgTopK(MoLTopKModule):
         finally:
             self._no_fused = False
 
+    def stats(self) -> Dict[str, int]:
+        """fused_candidate_calls once a call has been fused over the candidate union (fuse_candidates = True); empty before."""
+        return _fused_candidate_stats(self)
+
     def _diversified(self, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict, div):
         """The diversified call over this module's own ranked list: MoLAvgTopK's avg_top_k reranked candidates; a
         subclass with its own forward (MoLCombTopK) has that forward rank its union.  -> (scores, ids) in pick order."""
@@ -3506,7 +3594,10 @@ class MoLAvgTopK(MoLTopKModule):
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """diversify=lam: the avg_top_k reranked candidates re-ranked by maximal marginal relevance -- k columns in PICK
-        order, each with the item's own score, so a row is not monotone."""
+        order, each with the item's own score, so a row is not monotone.  query_lims= (section 3.20; fuse_candidates = True): one result row per
+        segment of query rows, over the union of their candidates."""
+        if _asks_fusion(self, kwargs):
+            return _fused_candidates(self, "forward", query_embeddings, k, None, kwargs)
         if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:
             return self._diversified(query_embeddings, k, None, kwargs, div)
         with self.inline_calls():      # nothing to overlap with: stay on the caller's stream (the hand-over between streams costs ~50 us)
@@ -3516,7 +3607,11 @@ class MoLAvgTopK(MoLTopKModule):
         """CandidateIndex.get_top_k_outputs' body: forward(k_prime) + the seen-id filter, with the filter enqueued BEFORE the host looks
         at the scan's verdict word (it then runs while the host is on its way back) -> (top_k_ids, top_k_scores); None where this
         does not apply (subclasses with their own forward, k_prime beyond K': the caller composes the two calls).  collapse_groups=True never
-        returns None: the seen ids go to the collapse walk."""
+        returns None: the seen ids go to the collapse walk.  Nor does a fused call (query_lims=, fuse_candidates = True): the seen ids are per
+        fused row and filter the one ranking of the union."""
+        if _asks_fusion(self, kwargs):
+            scores, ids = _fused_candidates(self, "forward_filtered", query_embeddings, k, invalid_ids, kwargs)
+            return ids, scores
         if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (never None: the seen ids go to the walk)
             scores, ids = self._diversified(query_embeddings, k, invalid_ids, kwargs, div)
             return ids, scores
@@ -3546,6 +3641,7 @@ class MoLAvgTopK(MoLTopKModule):
         """Pass 1 on this module's items: -> (coarse scores (B, K'), positions (B, K')), best first (ties by position)."""
         refuse_collapse_groups(self, kwargs, "coarse_candidates")
         refuse_diversity(self, kwargs, "coarse_candidates")
+        refuse_query_fusion(self, kwargs, "coarse_candidates")
         refuse_allowed_tags(self, kwargs, "coarse_candidates is the item-sharded wrappers' hand-off, and a tag filter is not built on them; forward, submit "
                             "and topk_ids take it")
         eng = self._bind()
@@ -3576,6 +3672,7 @@ class _ComponentCandidates:
     supply _candidates(eq, pending) -> (B, _union_width()) positions.  Mixed in BEFORE the MoL base class: its forward / forward_filtered are
     the modules' own."""
 
+    fuse_candidates = False                # as MoLAvgTopK.fuse_candidates
     fused_component_min_items = 262144     # below this the (B * P_Q * P_X, N) component scores are small and one launch chain shorter
     NO_FILTER_FUSION = False               # tests: True keeps the seen-id filter out of the selection launch
 
@@ -3586,7 +3683,10 @@ class _ComponentCandidates:
 
     def forward(self, query_embeddings: torch.Tensor, k: int, sorted: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
         """All the union's candidates ranked, whatever `k` is, as the reference does.  collapse_groups=True: the first k
-        of that ranking with at most one item per group of set_item_groups -- k columns."""
+        of that ranking with at most one item per group of set_item_groups -- k columns.  query_lims= (section 3.20; fuse_candidates = True):
+        one result row per segment of query rows, over the union of their candidates -- k columns."""
+        if _asks_fusion(self, kwargs):
+            return _fused_candidates(self, "forward", query_embeddings, k, None, kwargs)
         if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (DESIGN section 3.21: k columns in pick order)
             return _diversified_candidates(self, query_embeddings, k, None, 0, kwargs, div)
         if _asks_collapse(kwargs) and (m := self._take_collapse(kwargs)):
@@ -3597,7 +3697,11 @@ class _ComponentCandidates:
     def forward_filtered(self, query_embeddings: torch.Tensor, k_prime: int, invalid_ids: torch.Tensor, k: int, **kwargs):
         """CandidateIndex.get_top_k_outputs' body (the module returns all its candidates whatever k_prime is, the filter keeps the first k unseen):
         -> (top_k_ids, top_k_scores), or None where the filter does not fit the selection launch (_filter_inside).  collapse_groups=True never
-        returns None: the seen ids go to the collapse walk, over the sorted form of the ranking."""
+        returns None: the seen ids go to the collapse walk, over the sorted form of the ranking.  Nor does a fused call (query_lims=,
+        fuse_candidates = True)."""
+        if _asks_fusion(self, kwargs):
+            scores, ids = _fused_candidates(self, "forward_filtered", query_embeddings, k, invalid_ids, kwargs)
+            return ids, scores
         if _asks_diversity(kwargs) and (div := self._take_diversity(kwargs)) is not None:      # (never None: the seen ids go to the walk)
             scores, ids = _diversified_candidates(self, query_embeddings, k, invalid_ids, 0, kwargs, div)
             return ids, scores
@@ -3610,6 +3714,10 @@ class _ComponentCandidates:
             return None
         ids, scores = self._ranked(query_embeddings, True, seen, kwargs)
         return ids, scores.to(query_embeddings.dtype)
+
+    def stats(self) -> Dict[str, int]:
+        """fused_candidate_calls once a call has been fused over the candidate union (fuse_candidates = True); empty before."""
+        return _fused_candidate_stats(self)
 
     def _ranked(self, query_embeddings: torch.Tensor, sorted: bool, seen, kwargs):
         refuse_item_mask(self, kwargs)
@@ -3693,6 +3801,7 @@ class _ComponentCandidates:
         redoes the scans on the materialising path -- what comes back is exact."""
         refuse_collapse_groups(self, kwargs, "local_candidates")
         refuse_diversity(self, kwargs, "local_candidates")
+        refuse_query_fusion(self, kwargs, "local_candidates")
         refuse_allowed_tags(self, kwargs, "local_candidates is the item-sharded wrappers' hand-off, and a tag filter is not built on them; forward and "
                             "get_top_k_outputs take it")
         eng = self._bind()
@@ -3826,6 +3935,12 @@ class MoLNaiveTopK(_ComponentCandidates, MoLTopKModule):
                     or ivf_centroids.device != item_embeddings.device):
                 raise ValueError(f"MoLNaiveTopK: ivf_centroids must be a {want} float32 tensor on {item_embeddings.device}")
             self._ivf_args["centroids"] = ivf_centroids.detach().clone()      # (the caller's tensor is never aliased)
+
+    def __setattr__(self, name, value):
+        if name == "fuse_candidates" and value and getattr(self, "_use_faiss", False):
+            raise NotImplementedError("MoLNaiveTopK (IVF, use_faiss=True) takes no fuse_candidates: the candidate union is built on the exhaustive "
+                                      "component scan; the exhaustive MoLNaiveTopK takes it")
+        super().__setattr__(name, value)
 
     def _check_updatable(self, what: str, n_left: Optional[int] = None) -> None:
         if self._use_faiss and not self._frozen_centroids:
