@@ -62,6 +62,7 @@ extern "C" {
  * and the diversity entries rails_topk_mmr / rails_topk_mmr_workspace_bytes
  * and the multi-row HSTU decode step rails_hstu_decode_rows[_supported] / rails_hstu_decode_rows_workspace_floats /
  * RAILS_HSTU_DECODE_MAX_ROWS (rails_hstu_decode is what it was)
+ * and the pair-level entries rails_mol_generic_explain / rails_mol_generic_explain_indexed / rails_scores_at_eligible / rails_mips_score_indexed
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -274,6 +275,16 @@ int rails_mol_generic_score_candidates(const rails_mol_shape* shape, const float
 int rails_mol_generic_score_indexed(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch, const float* index,
                                     int64_t n_items, const int64_t* positions, int64_t n_cand, const int32_t* counts, float* logits, int64_t ld,
                                     const int32_t* run_if, void* stream);
+/* The explaining launches (score_of / explain_of): rails_mol_generic_score_candidates / rails_mol_generic_score_indexed
+ * that also store, per pair, the L = P_Q * P_X cross logits after the division by tau (component_logits[(b * n_cand + j) * L + l], l = p * P_X +
+ * m) and the L mixture weights the reference's combiner returns in eval mode (weights, the same layout; they sum to 1 up to rounding).  The
+ * logit of a pair has the bits of every other rails_mol_generic_score_* launch.  Both outputs hold batch * n_cand * L floats.  The indexed form
+ * takes no per-row counts: every one of the n_cand slots of a row is scored and written. */
+int rails_mol_generic_explain(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch, const float* cand_index,
+                              int64_t n_cand, float* logits, int64_t ld, float* component_logits, float* weights, void* stream);
+int rails_mol_generic_explain_indexed(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch,
+                                      const float* index, int64_t n_items, const int64_t* positions, int64_t n_cand, float* logits, int64_t ld,
+                                      float* component_logits, float* weights, void* stream);
 /* The bf16 candidate tables of the two-pass algorithms from the generic index.  rails_mol_generic_table_width: the smallest of 32 / 64 / 128
  * that is >= dot_product_dimension, 0 for d > 128 (no table; answered without a device).  Rows have that many columns, the columns d .. width
  * exact zeros; the real columns carry rails_mol_coarse_build's / rails_mol_component_build's arithmetic, operation for operation.  The coarse
@@ -332,6 +343,11 @@ int rails_mips_index_update(const float* items, int64_t n_new, int32_t dim, cons
 int rails_mips_index_gather_rows(const float* index, int64_t n_items, int32_t dim, const int64_t* positions, int64_t n_rows, float* rows, void* stream);
 int rails_mips_index_clear_tail(float* index, int64_t n_items, int32_t dim, void* stream);
 size_t rails_mips_query_ws_floats(int32_t dim, int32_t batch);         /* scratch for the packed queries */
+/* rails_mips_score for per-row candidates read in place: logits[b * ld + j] = <queries[b], item positions[b * n_cand + j]> with the bits
+ * rails_mips_score gives that pair (the same MFMA chain; the item operand is fetched by position).  Positions outside [0, n_items) are clamped
+ * into it (the caller overwrites their entries).  query_ws as rails_mips_score. */
+int rails_mips_score_indexed(const float* queries, int32_t batch, int32_t dim, const float* index, int64_t n_items, const int64_t* positions,
+                             int64_t n_cand, float* query_ws, float* logits, int64_t ld, void* stream);
 int rails_mips_score(const float* queries, int32_t batch, int32_t dim, const float* index, int64_t n_items,
                      float* query_ws, float* logits, int64_t ld, void* stream);
 
@@ -404,6 +420,16 @@ int rails_item_tags_count(const uint32_t* eff_tags, int64_t n, const uint32_t* w
  * counts_out[r] = the row's set bits.  What the exact modules hand to their masked strategies. */
 int rails_item_mask_from_tags(const uint32_t* eff_tags, int64_t n, const uint32_t* allowed, int32_t rows, uint32_t* words_out, int32_t* counts_out,
                               void* stream);
+/* The eligibility pass of the pair-level calls.  scores (rows, t) holds the score of item positions[r * t + j] for row
+ * r; in place, scores[r * ld + j] = -inf wherever the position lies outside [0, n) or row r may not return its item:
+ *   words      NULL, or mask words as rails_scores_mask takes them (words_row_stride = 0: one row for every r) -- the bit must be set
+ *   eff_tags / allowed   both NULL, or the effective tags (n) and one allow word per row (rows) -- eff_tags[p] & allowed[r] must be non-zero
+ *   invalid_ids / item_ids   both NULL, or the rows' seen ids (rows, width) and the ids of the n items -- item_ids[p] must not be among row r's
+ * extra_a / extra_b: NULL, or two (rows, t, extra_len) fp32 arrays whose extra_len entries of a pair are set to 0 where its score is set to -inf.
+ * One thread per pair, no atomics; kept entries are neither read nor written. */
+int rails_scores_at_eligible(float* scores, int64_t ld, int32_t rows, int64_t t, const int64_t* positions, int64_t n, const uint32_t* words,
+                             int64_t words_row_stride, const uint32_t* eff_tags, const uint32_t* allowed, const int64_t* invalid_ids, int32_t width,
+                             const int64_t* item_ids, float* extra_a, float* extra_b, int32_t extra_len, void* stream);
 /* rails_scores_mask with the tag test in place of a mask bit.  In place: scores[r * ld + x] = fill for x < n wherever
  * eff_tags[first_item + x] & allowed[r / rows_per_allowed] == 0; kept entries are neither read nor written.  eff_tags holds at least
  * first_item + n words, allowed at least ceil(rows / rows_per_allowed).  rows_per_allowed maps the rows of a matrix with several rows per

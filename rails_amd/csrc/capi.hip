@@ -583,6 +583,41 @@ int rails_mol_generic_score_indexed(const rails_mol_shape* s, const float* gate_
   return r == kOk ? r : fail(r, "generic_score_indexed");
 }
 
+// The explaining launches: the per-row and the indexed launch with the two (batch, n_cand, L) outputs beside the logits.
+static int generic_explain_common(const rails_mol_shape* s, const float* gate_pack, const float* query_pack, int32_t batch, const float* index,
+                                  int64_t n_items, const int64_t* positions, int64_t n_cand, float* logits, int64_t ld, float* component_logits,
+                                  float* weights, void* stream, const char* what) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (batch < 0 || n_items < 0 || n_cand < 0) { set_error("%s: negative size", what); return RAILS_EINVAL; }
+  if (batch == 0 || n_cand == 0) return RAILS_OK;
+  if (positions && n_items == 0) { set_error("%s: candidates of an empty index", what); return RAILS_EINVAL; }
+  if (!gate_pack || !query_pack || !index || !logits || !component_logits || !weights) { set_error("%s: NULL pointer", what); return RAILS_EINVAL; }
+  if (ld < n_cand) { set_error("%s: ld (%lld) < n_cand (%lld)", what, (long long)ld, (long long)n_cand); return RAILS_EINVAL; }
+  const int cu = compute_units();
+  if (cu <= 0) { set_error("%s: no HIP device", what); return RAILS_ELAUNCH; }
+  GenericScoreArgs a{};
+  a.wpack = gate_pack; a.qpack = query_pack; a.ipack = index; a.logits = logits; a.ld = ld; a.n_items = n_cand; a.B = batch;
+  a.per_row = positions ? 0 : 1; a.cand_pos = positions; a.index_items = n_items;
+  a.cl_out = component_logits; a.pi_out = weights;
+  const int r = generic_score(*s, a, cu, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, what);
+}
+
+int rails_mol_generic_explain(const rails_mol_shape* s, const float* gate_pack, const float* query_pack, int32_t batch, const float* cand_index,
+                              int64_t n_cand, float* logits, int64_t ld, float* component_logits, float* weights, void* stream) {
+  return generic_explain_common(s, gate_pack, query_pack, batch, cand_index, 0, nullptr, n_cand, logits, ld, component_logits, weights, stream,
+                                "generic_explain");
+}
+
+int rails_mol_generic_explain_indexed(const rails_mol_shape* s, const float* gate_pack, const float* query_pack, int32_t batch, const float* index,
+                                      int64_t n_items, const int64_t* positions, int64_t n_cand, float* logits, int64_t ld, float* component_logits,
+                                      float* weights, void* stream) {
+  if (!positions) { g_err[0] = '\0'; set_error("generic_explain_indexed: NULL pointer"); return RAILS_EINVAL; }
+  return generic_explain_common(s, gate_pack, query_pack, batch, index, n_items, positions, n_cand, logits, ld, component_logits, weights, stream,
+                                "generic_explain_indexed");
+}
+
 // ---- the bf16 candidate tables from the generic index (mol_coarse.hip) ----
 int32_t rails_mol_generic_table_width(const rails_mol_shape* s) {
   g_err[0] = '\0';
@@ -678,6 +713,19 @@ int rails_mips_index_clear_tail(float* index, int64_t n_items, int32_t dim, void
 size_t rails_mips_query_ws_floats(int32_t dim, int32_t batch) {
   if (dim <= 0 || batch < 0) return 0;
   return (size_t)((batch + 31) / 32) * 32 * (size_t)((dim + 7) / 8 * 8);
+}
+
+int rails_mips_score_indexed(const float* queries, int32_t batch, int32_t dim, const float* index, int64_t n_items, const int64_t* positions,
+                             int64_t n_cand, float* query_ws, float* logits, int64_t ld, void* stream) {
+  g_err[0] = '\0';
+  if (dim <= 0 || batch < 0 || n_items <= 0 || n_cand < 0) { set_error("mips_score_indexed: bad size"); return RAILS_EINVAL; }
+  if (batch == 0 || n_cand == 0) return RAILS_OK;
+  if (!queries || !index || !positions || !query_ws || !logits) { set_error("mips_score_indexed: NULL pointer"); return RAILS_EINVAL; }
+  if (ld < n_cand) { set_error("mips_score_indexed: ld < n_cand"); return RAILS_EINVAL; }
+  const int cu = compute_units();
+  if (cu <= 0) { set_error("mips_score_indexed: no HIP device"); return RAILS_ELAUNCH; }
+  return fail(mips_score_indexed(queries, batch, dim, index, n_items, positions, n_cand, query_ws, logits, ld, cu, (hipStream_t)stream),
+              "mips_score_indexed");
 }
 
 int rails_mips_score(const float* queries, int32_t batch, int32_t dim, const float* index, int64_t n_items, float* query_ws,
@@ -834,6 +882,25 @@ int rails_item_mask_from_tags(const uint32_t* eff_tags, int64_t n, const uint32_
                               void* stream) {
   const int go = item_mask_args("item_mask_from_tags", eff_tags && allowed && words_out && counts_out, rows, n);
   return go <= 0 ? go : fail(item_mask_from_tags(eff_tags, n, allowed, rows, words_out, counts_out, (hipStream_t)stream), "item_mask_from_tags");
+}
+
+int rails_scores_at_eligible(float* scores, int64_t ld, int32_t rows, int64_t t, const int64_t* positions, int64_t n, const uint32_t* words,
+                             int64_t words_row_stride, const uint32_t* eff_tags, const uint32_t* allowed, const int64_t* invalid_ids, int32_t width,
+                             const int64_t* item_ids, float* extra_a, float* extra_b, int32_t extra_len, void* stream) {
+  g_err[0] = '\0';
+  if (rows < 0 || t < 0 || n < 1 || ld < t || width < 0 || extra_len < 0 || words_row_stride < 0) {
+    set_error("scores_at_eligible: bad size (rows = %d, t = %lld, n = %lld, ld = %lld)", rows, (long long)t, (long long)n, (long long)ld);
+    return RAILS_EINVAL;
+  }
+  if (rows == 0 || t == 0) return RAILS_OK;
+  if (!scores || !positions) { set_error("scores_at_eligible: NULL pointer"); return RAILS_EINVAL; }
+  if ((eff_tags == nullptr) != (allowed == nullptr)) { set_error("scores_at_eligible: eff_tags and allowed go together"); return RAILS_EINVAL; }
+  if (words && words_row_stride != 0 && words_row_stride < item_mask_words(n)) { set_error("scores_at_eligible: the mask rows are shorter than n bits"); return RAILS_EINVAL; }
+  if (width == 0) invalid_ids = nullptr;
+  if (invalid_ids && !item_ids) { set_error("scores_at_eligible: invalid_ids without item_ids"); return RAILS_EINVAL; }
+  if ((extra_a == nullptr) != (extra_b == nullptr)) { set_error("scores_at_eligible: the two extra arrays go together"); return RAILS_EINVAL; }
+  return fail(scores_at_eligible(scores, ld, rows, t, positions, n, words, words_row_stride, eff_tags, allowed, invalid_ids, width, item_ids, extra_a, extra_b,
+                                 extra_len, (hipStream_t)stream), "scores_at_eligible");
 }
 
 int rails_scores_mask_tags(float* scores, int64_t ld, int32_t rows, int64_t n, int64_t first_item, const uint32_t* eff_tags, const uint32_t* allowed,

@@ -236,6 +236,48 @@ int scores_mask_tags(float* scores, int64_t ld, int rows, int64_t n, int64_t fir
   return launched();
 }
 
+// ---- the eligibility pass of the pair-level calls: scores[r][j] belongs to item pos[r][j]; -inf where the position is
+// outside [0, n) or row r may not return the item -- its mask bit clear, no bit of the row's allow word among its effective tags, or its id among
+// the row's seen ids (a loop over the row's `width` ids: O(width) per pair, nothing of size n is built).  Where a score is set, the pair's
+// extra_len entries of extra_a / extra_b (explain_of's weights and component logits) are zeroed.  One thread per pair, every index tested first.
+// (Named apart from the item_mask_* / scores_mask kernels: tests/test_item_mask_cpu.py pins that family's list.)
+__global__ void __launch_bounds__(kThreads) pairs_eligible_kernel(float* __restrict__ scores, int64_t ld, int rows, int64_t t, const int64_t* __restrict__ pos,
+                                                                 int64_t n, const u32* __restrict__ words, int64_t words_row_stride,
+                                                                 const u32* __restrict__ eff, const u32* __restrict__ allowed,
+                                                                 const int64_t* __restrict__ invalid, int width, const int64_t* __restrict__ item_ids,
+                                                                 float* __restrict__ extra_a, float* __restrict__ extra_b, int extra_len) {
+  const int64_t total = (int64_t)rows * t;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kThreads) {
+    const int64_t r = i / t, j = i - r * t;
+    const int64_t p = pos[i];
+    bool ok = p >= 0 && p < n;
+    if (ok && words) ok = ((words[r * words_row_stride + (p >> 5)] >> (int)(p & 31)) & 1u) != 0u;
+    if (ok && eff) ok = (eff[p] & allowed[r]) != 0u;
+    if (ok && invalid) {
+      const int64_t id = item_ids[p];
+      const int64_t* seen = invalid + r * (int64_t)width;
+      for (int s = 0; s < width; ++s) ok = ok && seen[s] != id;
+    }
+    if (ok) continue;
+    scores[r * ld + j] = -INFINITY;
+    if (extra_a) {
+      for (int l = 0; l < extra_len; ++l) {
+        extra_a[i * extra_len + l] = 0.0f;
+        extra_b[i * extra_len + l] = 0.0f;
+      }
+    }
+  }
+}
+
+int scores_at_eligible(float* scores, int64_t ld, int rows, int64_t t, const int64_t* positions, int64_t n, const void* words, int64_t words_row_stride,
+                       const void* eff, const void* allowed, const int64_t* invalid_ids, int width, const int64_t* item_ids, float* extra_a, float* extra_b,
+                       int extra_len, hipStream_t stream) {
+  hipLaunchKernelGGL(pairs_eligible_kernel, dim3(grid_for(((int64_t)rows * t + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, scores, ld, rows, t,
+                     positions, n, (const u32*)words, words_row_stride, (const u32*)eff, (const u32*)allowed, invalid_ids, width, item_ids, extra_a, extra_b,
+                     extra_len);
+  return launched();
+}
+
 int64_t item_mask_words(int64_t n) { return (n + 31) / 32; }
 
 int item_mask_count(const void* words, int rows, int64_t n, int32_t* counts, hipStream_t stream) {

@@ -124,6 +124,58 @@ __global__ __launch_bounds__(256) void mips_score_kernel(const float4* __restric
   }
 }
 
+// The indexed mode (score_of): a wave scores 32 candidates of ONE query row b, read in place by position.  The MFMA chain is
+// mips_score_kernel's -- the A operand is the whole group of 32 queries that holds b, the B operand of lane (x, hi) the fragment of item
+// pos[b][j0 + x] (its tile p >> 5, its column p & 31) -- so row b of the accumulator has the dense kernel's bits for the pair; the other 31
+// rows are dropped.  A position outside the index is clamped into it.
+__global__ __launch_bounds__(256) void mips_score_indexed_kernel(const float4* __restrict__ qfrag, const float4* __restrict__ ifrag, int B, int64_t n,
+                                                                const int64_t* __restrict__ pos, int64_t n_cand, int Dp, float* __restrict__ logits,
+                                                                int64_t ld) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int hi = lane >> 5, x = lane & 31;
+  const int nsc = Dp / 8;
+  const int64_t tiles_per_row = (n_cand + 31) / 32, n_units = tiles_per_row * B;
+  for (int64_t u = (int64_t)blockIdx.x * 4 + wave; u < n_units; u += (int64_t)gridDim.x * 4) {
+    const int b = (int)(u / tiles_per_row);
+    const int64_t j = (u - (int64_t)b * tiles_per_row) * 32 + x;
+    int64_t p = pos[(int64_t)b * n_cand + (j < n_cand ? j : n_cand - 1)];
+    p = p < 0 ? 0 : (p < n ? p : n - 1);
+    const float4* a4 = qfrag + (int64_t)(b >> 5) * nsc * 64;
+    const float4* b4 = ifrag + (p >> 5) * nsc * 64 + hi * 32 + (int)(p & 31);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    for (int sc = 0; sc < nsc; ++sc) {
+      const float4 a = a4[sc * 64 + lane], bv = b4[sc * 64];
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bv.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bv.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bv.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bv.w, acc, 0, 0, 0);
+    }
+    // row b & 31 of the tile sits in one register of one lane half
+    float v = 0.0f;
+    bool mine = false;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (acc_row(r, hi) == (b & 31)) { v = acc[r]; mine = true; }
+    if (mine && j < n_cand) logits[(int64_t)b * ld + j] = v;
+  }
+}
+
+int mips_score_indexed(const float* q, int B, int D, const float* ifrag, int64_t n, const int64_t* positions, int64_t n_cand, float* qfrag_ws,
+                       float* logits, int64_t ld, int n_cu, hipStream_t stream) {
+  const int Dp = (D + 7) / 8 * 8;
+  const int n_groups = (B + 31) / 32;
+  if (B <= 0 || n_cand <= 0 || n <= 0) return kOk;
+  hipLaunchKernelGGL(mips_pack_queries_kernel, dim3(n_groups), dim3(256), 0, stream, q, B, D, Dp, qfrag_ws);
+  int64_t grid = ((n_cand + 31) / 32 * B + 3) / 4;
+  if (grid > (int64_t)n_cu * 8) grid = (int64_t)n_cu * 8;
+  hipLaunchKernelGGL(mips_score_indexed_kernel, dim3((unsigned)grid), dim3(256), 0, stream, reinterpret_cast<const float4*>(qfrag_ws),
+                     reinterpret_cast<const float4*>(ifrag), B, n, positions, n_cand, Dp, logits, ld);
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
 int mips_pack_items(const float* items, int64_t n, int D, float* out, hipStream_t stream) {
   const int Dp = (D + 7) / 8 * 8;
   const int64_t tiles = num_tiles(n);

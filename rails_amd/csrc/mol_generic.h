@@ -51,6 +51,10 @@ struct GenericScoreArgs {
   const int64_t* cand_pos;
   const int32_t* cand_count;
   int64_t index_items;
+  // the explaining mode (both non-NULL, per_row or cand_pos, cand_count NULL): the L cross logits and the L mixture weights of every scored pair,
+  // (B, n_items, L) row-major each
+  float* cl_out;
+  float* pi_out;
 };
 int generic_pack_gate_weights(const Shape& s, const Weights& w, float* wpack, hipStream_t stream);
 int generic_index_unpack(const Shape& s, const float* ipack, int64_t n, float* ex, float* gi, hipStream_t stream);

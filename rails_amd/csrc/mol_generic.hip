@@ -18,6 +18,10 @@
 // the batch, N, or on whether the pair came from a shared index, per-row candidates or positions of the shared index (the indexed
 // mode: the item row of a lane comes from a 64-bit position load at the head of the unit): same bits everywhere.
 // fp32 throughout, precise expf and true divisions.
+//
+// The explaining instantiations (EXP; rails_mol_generic_explain*, per-row candidates and the indexed mode) also store what the mixture is
+// made of: per pair the L cross logits cl and the L mixture weights pi = (e / den) / clamp(sum e / den, 1e-6), (B, T, L) row-major.  The
+// logit is the same code as everywhere else; cl and pi leave through the wave's own cl buffer (emit_tile), whole 256-byte runs at a time.
 #include <hip/hip_runtime.h>
 
 #include "mol_generic.h"
@@ -51,9 +55,31 @@ __device__ __forceinline__ float silu_exact(float v) { return v / (1.0f + expf(-
 // cl buffer of a wave: logit l of item x at ((l >> 2) * 32 + x) * 4 + (l & 3): four consecutive logits of an item are one float4
 __device__ __forceinline__ int cl_at(int l, int x) { return ((l >> 2) * 32 + x) * 4 + (l & 3); }
 
+// The wave's cl-shaped buffer holds a value per (l, item): float4 (l >> 2) of item x at slot x ^ ((l >> 2) & 7) of its row of 32 (stage_at).
+// The `nv` first items of the tile are consecutive pairs of one query row, so their L-vectors are ONE run of nv * L floats at dst: lane i of
+// a store instruction writes float f = 64 j + i of it -- 256 contiguous bytes per instruction, whatever L is.  The XOR spreads the 8 float4
+// rows that 32 consecutive l of one item touch over all 32 banks of the dword read.
+__device__ __forceinline__ int stage_at(int l4, int x) { return l4 * 32 + (x ^ (l4 & 7)); }
+
+__device__ __forceinline__ void emit_tile(const float* buf, float* dst, int nv, int L, int lane) {
+  const int total = nv * L;
+  for (int f = lane; f < total; f += 64) {
+    const int item = f / L, l = f - item * L;
+    dst[f] = buf[stage_at(l >> 2, item) * 4 + (l & 3)];
+  }
+}
+
+// orders this wave's LDS writes before its reads of other lanes' slots (the buffer is the wave's own: no workgroup barrier is needed)
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // IDX: the indexed mode (candidates scored in place on the shared index) -- an instantiation of its own, so that the dense and per-row
 // launches keep their registers; the item row address and the count test are all that differs.
-template <int TL, bool RES, bool IDX = false>
+// EXP: the explaining mode, an instantiation of its own for the same reason; the store stage behind the logit is all it adds.
+template <int TL, bool RES, bool IDX = false, bool EXP = false>
 __global__ __launch_bounds__(kGenThreads) void mol_generic_score_kernel(GenKernelArgs k) {
   MOL_RUN_IF(k.a.run_if);
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -187,6 +213,41 @@ __global__ __launch_bounds__(kGenThreads) void mol_generic_score_kernel(GenKerne
       const float rden = 1.0f / den;
       const float res = (num * rden) / fmaxf(den * rden, 1e-6f);
       if (valid && hi == 0) k.a.logits[(int64_t)b * k.a.ld + xi] = res;
+      if constexpr (EXP) {
+        // the tile's valid items are its first nv slots (valid is a prefix of x): pairs b * n_items + (xi - x) .. + nv of the outputs
+        // (the explaining launches take no per-row counts: mol_generic.h)
+        const int64_t left = k.a.n_items - (xi - x);
+        const int nv = left >= 32 ? 32 : left > 0 ? (int)left : 0;
+        const int64_t pair0 = ((int64_t)b * k.a.n_items + (xi - x)) * L;
+        float4* st4 = reinterpret_cast<float4*>(cl);
+        // cl: every lane moves its own float4s to their staged slots (a permutation inside a row of 32: read, then write), rows L .. Lp stay zero
+#pragma unroll
+        for (int v = 0; v < TL; ++v) {
+          const int r0 = 8 * v + hi;
+          const float4 c0 = cl4[r0 * 32 + x], c1 = cl4[(r0 + 2) * 32 + x], c2 = cl4[(r0 + 4) * 32 + x], c3 = cl4[(r0 + 6) * 32 + x];
+          wave_lds_fence();
+          st4[stage_at(r0, x)] = c0;
+          st4[stage_at(r0 + 2, x)] = c1;
+          st4[stage_at(r0 + 4, x)] = c2;
+          st4[stage_at(r0 + 6, x)] = c3;
+        }
+        wave_lds_fence();
+        emit_tile(cl, k.a.cl_out + pair0, nv, L, lane);
+        wave_lds_fence();
+        // pi over the same slots: e recomputed from w (the same bits as in the sums above), 0 in the padded logits
+        const float rnorm = fmaxf(den * rden, 1e-6f);
+#pragma unroll
+        for (int v = 0; v < TL; ++v)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int l0 = 32 * v + 8 * g + 4 * hi;
+            auto pi_of = [&](int j) { return l0 + j < L ? (expf(out[v][4 * g + j] - mx) * rden) / rnorm : 0.0f; };
+            st4[stage_at(8 * v + 2 * g + hi, x)] = make_float4(pi_of(0), pi_of(1), pi_of(2), pi_of(3));
+          }
+        wave_lds_fence();
+        emit_tile(cl, k.a.pi_out + pair0, nv, L, lane);
+        // (the next unit's GEMM1 rewrites every l < L of every item; what is left past L is zeros)
+      }
     }
     __syncthreads();   // the next unit's GEMM1 overwrites cl
   }
@@ -277,10 +338,10 @@ int generic_eq_pad(const Shape& s, const float* eq, int64_t rows, float* out, hi
 // ---- launch ---------------------------------------------------------------------------------------------------------------
 constexpr size_t kGenMaxLds = 160 * 1024;
 
-template <int TL, bool RES, bool IDX>
+template <int TL, bool RES, bool IDX, bool EXP>
 static int launch_generic(const GenKernelArgs& k, size_t lds, int grid, hipStream_t stream) {
   static DynLdsOnce once;
-  auto* fn = &mol_generic_score_kernel<TL, RES, IDX>;
+  auto* fn = &mol_generic_score_kernel<TL, RES, IDX, EXP>;
   // the bytes depend on the shape (L, and H when the weights are resident), not on the instantiation alone: opt in to the route's maximum
   if (ensure_dyn_lds(once, reinterpret_cast<const void*>(fn), (int)kGenMaxLds) != kOk) return kErrLaunch;
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kGenThreads), lds, stream, k);
@@ -289,8 +350,12 @@ static int launch_generic(const GenKernelArgs& k, size_t lds, int grid, hipStrea
 
 template <int TL>
 static int launch_generic_tl(const GenKernelArgs& k, bool res, size_t lds, int grid, hipStream_t stream) {
-  if (k.a.cand_pos) return res ? launch_generic<TL, true, true>(k, lds, grid, stream) : launch_generic<TL, false, true>(k, lds, grid, stream);
-  return res ? launch_generic<TL, true, false>(k, lds, grid, stream) : launch_generic<TL, false, false>(k, lds, grid, stream);
+  if (k.a.cl_out) {      // the explaining instantiations: per-row candidates or the indexed mode
+    if (k.a.cand_pos) return res ? launch_generic<TL, true, true, true>(k, lds, grid, stream) : launch_generic<TL, false, true, true>(k, lds, grid, stream);
+    return res ? launch_generic<TL, true, false, true>(k, lds, grid, stream) : launch_generic<TL, false, false, true>(k, lds, grid, stream);
+  }
+  if (k.a.cand_pos) return res ? launch_generic<TL, true, true, false>(k, lds, grid, stream) : launch_generic<TL, false, true, false>(k, lds, grid, stream);
+  return res ? launch_generic<TL, true, false, false>(k, lds, grid, stream) : launch_generic<TL, false, false, false>(k, lds, grid, stream);
 }
 
 int generic_score(const Shape& s, const GenericScoreArgs& a, int n_cu, hipStream_t stream) {

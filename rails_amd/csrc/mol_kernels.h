@@ -252,6 +252,9 @@ int mips_update_items(const float* items, int64_t n, int D, const int64_t* posit
 int mips_gather_rows(const float* index, int64_t n_index, int D, const int64_t* positions, int64_t m, float* rows, hipStream_t stream);
 int mips_score(const float* q, int B, int D, const float* ifrag, int64_t n, float* qfrag_ws, float* logits, int64_t ld,
                int n_cu, hipStream_t stream);
+// per-row candidates read in place: logits[b][j] = <q[b], item positions[b * n_cand + j]> (clamped into the index), mips_score's bits per pair
+int mips_score_indexed(const float* q, int B, int D, const float* ifrag, int64_t n, const int64_t* positions, int64_t n_cand, float* qfrag_ws,
+                       float* logits, int64_t ld, int n_cu, hipStream_t stream);
 
 // ---- item id -> position map (id_map.hip): int64 keys[slots] then int32 values[slots], slots a power of two ----
 int id_map_clear(void* map, int64_t slots, hipStream_t stream);
@@ -272,6 +275,10 @@ int item_tags_count(const void* eff, int64_t n, const void* words, int n_words, 
 int item_mask_from_tags(const void* eff, int64_t n, const void* allowed, int rows, void* words, int32_t* counts, hipStream_t stream);
 int scores_mask_tags(float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const void* eff, const void* allowed, int rows_per_allowed,
                      float fill, const int32_t* run_if, hipStream_t stream);
+// the eligibility pass of the pair-level calls: -inf (and zeros in the two extra arrays) for an absent or ineligible pair
+int scores_at_eligible(float* scores, int64_t ld, int rows, int64_t t, const int64_t* positions, int64_t n, const void* words, int64_t words_row_stride,
+                       const void* eff, const void* allowed, const int64_t* invalid_ids, int width, const int64_t* item_ids, float* extra_a, float* extra_b,
+                       int extra_len, hipStream_t stream);
 size_t item_mask_positions_workspace_bytes(int rows, int64_t n);
 int item_mask_positions(const void* words, int rows, int64_t n, int64_t* out, int64_t out_ld, void* workspace, hipStream_t stream);
 int scores_mask(float* scores, int64_t ld, int rows, int64_t n, int64_t first_item, const void* words, int64_t words_row_stride, float fill,

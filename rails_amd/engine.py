@@ -628,6 +628,53 @@ class MolEngine:
             )
         return out
 
+    # ---- pair-level scoring on the generic route (score_of / explain_of) ----------------------------------------------
+    def _generic_only(self, what: str) -> None:
+        if self.route != "generic":
+            raise NotImplementedError(f"{what} is built on the generic scoring route only (MolEngine(..., route='generic'))")
+
+    def score_at_generic(self, qpack: torch.Tensor, batch: int, index: MolIndex, positions: torch.Tensor) -> torch.Tensor:
+        """(B, T) logits of per-row positions of a generic index, read in place -- the indexed launch whether or not the engine is
+        candidate-capable (the index is row-major on this route; rails_mol_generic_score_indexed clamps the positions into it)."""
+        self._generic_only("score_at_generic")
+        positions = positions.to(device=index.buf.device, dtype=torch.int64).contiguous()
+        t = positions.shape[1]
+        out = torch.empty((batch, t), dtype=torch.float32, device=index.buf.device)
+        with _on_device(index.buf.device):
+            _lib.check(self.lib.rails_mol_generic_score_indexed(C.byref(self.shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(index.buf), index.n_items,
+                                                                _ptr(positions), t, None, _ptr(out), out.stride(0), None, _stream()),
+                       "rails_mol_generic_score_indexed")
+        return out
+
+    def explain_indexed(self, qpack: torch.Tensor, batch: int, index: MolIndex, positions: torch.Tensor):
+        """score_at_generic's launch in its explaining instantiation -> (logits (B, T), component_logits (B, T, L), weights (B, T, L)): the
+        logits carry score_at_generic's bits (include/rails_amd.h rails_mol_generic_explain_indexed)."""
+        self._generic_only("explain_indexed")
+        dev = index.buf.device
+        positions = positions.to(device=dev, dtype=torch.int64).contiguous()
+        t, L = positions.shape[1], self.spec.num_logits
+        out = torch.empty((batch, t), dtype=torch.float32, device=dev)
+        cl = torch.empty((batch, t, L), dtype=torch.float32, device=dev)
+        pi = torch.empty((batch, t, L), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _lib.check(self.lib.rails_mol_generic_explain_indexed(C.byref(self.shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(index.buf), index.n_items,
+                                                                  _ptr(positions), t, _ptr(out), out.stride(0), _ptr(cl), _ptr(pi), _stream()),
+                       "rails_mol_generic_explain_indexed")
+        return out, cl, pi
+
+    def explain_candidates(self, qpack: torch.Tensor, batch: int, cand_index: MolIndex, n_cand: int):
+        """explain_indexed for per-row candidates held in a generic index of their own (candidate j of row b is its item b * n_cand + j)."""
+        self._generic_only("explain_candidates")
+        dev = cand_index.buf.device
+        L = self.spec.num_logits
+        out = torch.empty((batch, n_cand), dtype=torch.float32, device=dev)
+        cl = torch.empty((batch, n_cand, L), dtype=torch.float32, device=dev)
+        pi = torch.empty((batch, n_cand, L), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _lib.check(self.lib.rails_mol_generic_explain(C.byref(self.shape), _ptr(self.gate_pack), _ptr(qpack), batch, _ptr(cand_index.buf), n_cand,
+                                                          _ptr(out), out.stride(0), _ptr(cl), _ptr(pi), _stream()), "rails_mol_generic_explain")
+        return out, cl, pi
+
     def score_candidates(self, qpack: torch.Tensor, batch: int, cand_index: MolIndex, n_cand_padded: int) -> torch.Tensor:
         out = torch.empty((batch, n_cand_padded), dtype=torch.float32, device=cand_index.buf.device)
         with _on_device(cand_index.buf.device):
@@ -1290,6 +1337,24 @@ class MipsIndex:
         return out
 
 
+    def score_at(self, q: torch.Tensor, positions: torch.Tensor) -> torch.Tensor:
+        """(B, D), (B, T) int64 positions -> (B, T) fp32: <q[b], item positions[b, j]> with score()'s bits for that pair, the items read in place
+        (rails_mips_score_indexed); a position outside [0, N) is clamped into it -- the caller overwrites such entries."""
+        lib = _lib.load()
+        _require_device(q, "query_embeddings")
+        if q.dim() != 2 or q.shape[1] != self.dim:
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({tuple(q.shape)} and {self.dim}x{self.n_items})")
+        q = _f32c(q)
+        B = q.shape[0]
+        positions = positions.to(device=q.device, dtype=torch.int64).contiguous()
+        ws = torch.empty(lib.rails_mips_query_ws_floats(self.dim, B), dtype=torch.float32, device=q.device)
+        out = torch.empty((B, positions.shape[1]), dtype=torch.float32, device=q.device)
+        with _on_device(q.device):
+            _lib.check(lib.rails_mips_score_indexed(_ptr(q), B, self.dim, _ptr(self.buf), self.n_items, _ptr(positions), positions.shape[1], _ptr(ws), _ptr(out),
+                                                    out.stride(0), _stream()), "rails_mips_score_indexed")
+        return out
+
+
 # ---- item id -> position map (rails_id_map_*) ---------------------------------------------------
 ID_MAP_RESERVED = (-(1 << 63), -(1 << 63) + 1)      # EMPTY and ERASED: no item may carry these ids
 
@@ -1659,6 +1724,50 @@ def scores_mask(scores: torch.Tensor, mask: ItemMask, first_item: int = 0, fill:
     with _on_device(scores.device):
         _lib.check(_lib.load().rails_scores_mask(_ptr(scores), ld, rows, n, first_item, _ptr(mask.words),
                                                  0 if mask.shared else mask.words.stride(0), float(fill), _pred(run_if), _stream()), "rails_scores_mask")
+    return scores
+
+
+def scores_at_eligible(scores: torch.Tensor, positions: torch.Tensor, n_items: int, mask: Optional[ItemMask] = None, tags: Optional["TagFilter"] = None,
+                       invalid_ids: Optional[torch.Tensor] = None, item_ids: Optional[torch.Tensor] = None,
+                       extras: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+    """In place: scores[r, j] (the score of item positions[r, j] for row r; (rows, t) fp32) = -inf wherever the position lies outside
+    [0, n_items) or row r may not return the item -- outside `mask` (shared or one row per row), no bit of the row's allow word of `tags` among
+    its effective tags, or its id (`item_ids`, (n_items,) int64) among the row's `invalid_ids` ((rows, W)).  extras: two (rows, t, L) fp32
+    arrays zeroed in the same pairs (rails_scores_at_eligible).  One launch, O(rows t (1 + W)); no sync."""
+    rows, t, ld = _score_matrix(scores)
+    _positions_arg("scores_at_eligible", positions, rows, scores.device)
+    if positions.shape[1] != t:
+        raise ValueError(f"scores_at_eligible: {t} scores but {positions.shape[1]} positions per row")
+    words, stride = None, 0
+    if mask is not None:
+        if mask.n_items != n_items or (not mask.shared and mask.rows != rows) or mask.words.device != scores.device:
+            raise ValueError(f"scores_at_eligible: the mask must cover the {n_items} items on {scores.device} with 1 or {rows} rows")
+        words, stride = mask.words, 0 if mask.shared else mask.words.stride(0)
+    eff = allowed = None
+    if tags is not None:
+        _check_tag_filter(tags, n_items, rows, scores.device, None)
+        eff, allowed = tags.eff, tags.allowed_for(rows)
+    inv, width = None, 0
+    if invalid_ids is not None and (not torch.is_tensor(invalid_ids) or invalid_ids.dim() != 2 or invalid_ids.shape[0] != rows):
+        raise ValueError(f"scores_at_eligible: invalid_ids must be ({rows}, W) integer ids")
+    if invalid_ids is not None and invalid_ids.shape[1] > 0:
+        if item_ids is None or item_ids.numel() != n_items:
+            raise ValueError(f"scores_at_eligible: invalid_ids need the ids of the {n_items} items beside them")
+        inv = invalid_ids.to(device=scores.device, dtype=torch.int64).contiguous()
+        width = inv.shape[1]
+    ea = eb = None
+    length = 0
+    if extras is not None:
+        ea, eb = extras
+        length = ea.shape[-1]
+        if ea.shape != (rows, t, length) or eb.shape != ea.shape or not ea.is_contiguous() or not eb.is_contiguous() or ea.dtype != torch.float32 or eb.dtype != torch.float32:
+            raise ValueError(f"scores_at_eligible: extras must be two contiguous ({rows}, {t}, L) fp32 arrays")
+    if rows == 0 or t == 0:
+        return scores
+    with _on_device(scores.device):
+        _lib.check(_lib.load().rails_scores_at_eligible(_ptr(scores), ld, rows, t, _ptr(positions.contiguous()), n_items, _ptr(words), stride, _ptr(eff),
+                                                        _ptr(allowed), _ptr(inv), width, _ptr(item_ids), _ptr(ea), _ptr(eb), length, _stream()),
+                   "rails_scores_at_eligible")
     return scores
 
 

@@ -414,6 +414,23 @@ class MoLSimilarity(SimilarityModule):
             self._engine_key = key
         return self._engine
 
+    def explain_engine(self) -> MolEngine:
+        """The fp32 engine on the generic scoring route over the CURRENT parameter values, whatever the module's own precision and route: the
+        companion whose kernel writes a pair's cross logits and mixture weights out (explain_of on a fused-shape module).
+        Cached as the other extra engines are; NotImplementedError, with the route's own words, for a shape outside its envelope."""
+        _eval_only(self)
+        plist = self._param_list
+        if plist is None:
+            plist = self._param_list = [v for _, v in self.state_dict(keep_vars=True).items()]
+        key = (("explain",),) + tuple((v.data_ptr(), _version(v)) for v in plist)
+        hit = self._extra_engines.get("explain")
+        if hit is None or hit[0] != key:
+            params = dict(self.state_dict(keep_vars=True))
+            self._param_list = list(params.values())
+            key = (("explain",),) + tuple((v.data_ptr(), _version(v)) for v in self._param_list)
+            hit = self._extra_engines["explain"] = (key, MolEngine(self.shape_spec(), params, precision="fp32", route="generic"))
+        return hit[1]
+
     def _apply(self, fn, *args, **kwargs):
         self._param_list = None
         return super()._apply(fn, *args, **kwargs)

@@ -44,6 +44,8 @@ _RANK_WHY = ("the exact rank of an item is built on the single-device MoLBruteFo
              "and needs the target's key on every rank (out of scope, DESIGN section 3.17)")
 _SOFTMAX_WHY = ("the softmax over the corpus is built on the single-device MoLBruteForceTopK: a sharded one would merge the shards' (max, sum) pairs, "
                 "which combine associatively, in one all-gather (out of scope, DESIGN section 3.18)")
+_PAIRS_WHY = ("scoring caller-given items is built on the single-device modules: a sharded one would route each pair to the rank that owns the item and "
+              "gather the scores (out of scope, DESIGN section 3.22)")
 _RANGE_WHY = ("the range search is built on the single-device MoLBruteForceTopK: a sharded one would gather the shards' ragged results and merge each "
               "row's sorted runs (out of scope, DESIGN section 3.19)")
 
@@ -334,6 +336,19 @@ class ShardedTopK(TopKModule):
     def range_search(self, query_embeddings: torch.Tensor, min_score=None, *, min_log_prob=None, temperature: float = 1.0, invalid_ids=None,
                      sort: bool = True, **kwargs):
         self._refuse_streaming("range_search", _RANGE_WHY)
+
+    # ---- score_of / explain_of: not built on the item-sharded wrappers ------------------------------------------------------
+    def score_of(self, query_embeddings: torch.Tensor, item_ids: torch.Tensor, invalid_ids=None, **kwargs):
+        self._refuse_streaming("score_of", _PAIRS_WHY)
+
+    def score_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids=None, **kwargs):
+        self._refuse_streaming("score_of_positions", _PAIRS_WHY)
+
+    def explain_of(self, query_embeddings: torch.Tensor, item_ids: torch.Tensor, invalid_ids=None, **kwargs):
+        self._refuse_streaming("explain_of", _PAIRS_WHY)
+
+    def explain_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids=None, **kwargs):
+        self._refuse_streaming("explain_of_positions", _PAIRS_WHY)
 
     # ---- hidden items: not built on the item-sharded wrappers -------------------------------------------------------
     def _refuse_hidden(self, what: str):

@@ -927,6 +927,129 @@ class _StreamingScores(_ItemsById):
                 parts.append((lims if not parts else lims[1:] + parts[-1][0][-1], s, i))      # (cumulative over the slices; a device add, no sync)
             return _join_slices(parts)
 
+    # ---- score_of / explain_of: caller-given items, scored and explained pair by pair -----------------------------------
+    # score_of[b, j] is all_logits(q, **kwargs)[b, position of item_ids[b, j]] bit for bit -- -inf where the corpus has no such item or row b may
+    # not return it (rank_of's eligible set) -- at O(B T) cost: the positions are scored in place on the index (the hooks below), one
+    # eligibility launch follows (engine.scores_at_eligible), and nothing of size N is allocated, read or written.  explain_of adds the
+    # mixture behind each score: the L = P_Q P_X cross logits after the division by tau and the weights of the reference's eval-mode combiner.
+    # The hooks: _pair_scores(query_embeddings, positions, kwargs) -> (B, T) fp32, all_logits' bits at VALID positions (the flow clamps them);
+    # _pair_explained(query_embeddings, positions, kwargs) -> (component_logits, weights), (B, T, L) each.
+    _pair_scores = None
+    _pair_explained = None
+
+    def _refuse_pair_engine(self, what: str) -> None:
+        """The refusals that need the module's engine (the MoL modules: precision, envelope); behind _refuse_pairs, before any launch."""
+    _PAIR_ITEM_MASK = True      # item_mask= is taken where all_logits takes it
+
+    def _refuse_pairs(self, kwargs: dict, what: str) -> None:
+        """The refusals of the pair-level calls, before any launch; reads the type and kwargs alone."""
+        name = f"{type(self).__name__}.{what}"
+        if getattr(self, "_use_faiss", False):
+            raise NotImplementedError(f"{type(self).__name__} (IVF, use_faiss=True).{what}: the IVF module keeps no index of every item to score "
+                                      "positions on; the exhaustive modules over the same corpus take the call")
+        if type(self)._pair_scores is None:
+            raise NotImplementedError(f"{name}: scoring caller-given items is built on the single-device MoL top-k modules and MIPSBruteForceTopK")
+        for given in _FUSION_KWARGS:
+            if kwargs.get(given) is not None:
+                raise NotImplementedError(f"{name} takes no {given}: a pair-level call scores (query row, item) pairs, and fusing query rows "
+                                          "over caller-given items is not built; fuse the returned scores")
+        refuse_collapse_groups(self, kwargs, what)
+        refuse_diversity(self, kwargs, what)
+        if not self._PAIR_ITEM_MASK and kwargs.get("item_mask") is not None:
+            raise NotImplementedError(f"{name} takes no item_mask: {type(self).__name__} takes none in any call; MoLBruteForceTopK and "
+                                      "MIPSBruteForceTopK take it")
+        if what.startswith("explain_of") and type(self)._pair_explained is None:
+            raise NotImplementedError(f"{name}: there is no mixture to explain -- {type(self).__name__} scores plain dot products; score_of "
+                                      "returns them")
+
+    def _pair_count(self, key: str) -> None:
+        stats = self.__dict__.setdefault("_pair_stats", {"score_of_calls": 0, "explain_calls": 0})
+        stats[key] += 1
+
+    def pair_stats(self) -> dict:
+        """score_of_calls / explain_calls (part of stats()); empty before the first pair-level call."""
+        return dict(self.__dict__.get("_pair_stats", {}))
+
+    def _pairs_call(self, what: str, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor], kwargs: dict,
+                    explain: bool):
+        """The one host flow of the four calls.  positions: (B, T) int64 on the module's device, anything outside [0, N) is absent."""
+        B, N = query_embeddings.size(0), self.num_items
+        if invalid_ids is not None:
+            _ids_arg(what, "invalid_ids", invalid_ids, B, "S")
+        with torch.inference_mode(), self.one_bind():
+            # the row's eligible set, as rank_of / log_prob_of take it -- but never as a per-row matrix of N bits: a tag filter stays its
+            # effective tags and allow words, the seen ids stay ids
+            tags = mask = None
+            if kwargs.get("allowed_tags") is not None:
+                if kwargs.get("item_mask") is not None:
+                    raise ValueError("allowed_tags= and item_mask= in one call: combining the two is not built; fold one into the other")
+                tags = self._take_allowed_tags(kwargs, B, ())
+            else:
+                mask = self._take_item_mask(kwargs, B, None)
+            valid = positions.clamp(0, N - 1)
+            extras = None
+            if explain:
+                cl, pi = self._pair_explained(query_embeddings, valid, kwargs)
+                extras = (pi, cl)
+            scores = self._pair_scores(query_embeddings, valid, kwargs)
+            E.scores_at_eligible(scores, positions, N, mask, tags, invalid_ids, self._ids_flat, extras)
+            self._pair_count("explain_calls" if explain else "score_of_calls")
+            if not explain:
+                return scores
+            s = self.mol_module.shape_spec()
+            shape4 = (B, positions.shape[1], s.query_dot_product_groups, s.item_dot_product_groups)
+            return Explained(scores, pi.view(shape4), cl.view(shape4))
+
+    def _pairs_by_id(self, what: str, query_embeddings: torch.Tensor, item_ids: torch.Tensor, kwargs: dict) -> torch.Tensor:
+        self._refuse_pairs(kwargs, what)
+        self._refuse_pair_engine(what)
+        B = query_embeddings.size(0)
+        _ids_arg(what, "item_ids", item_ids, B)
+        if item_ids.shape[1] < 1:
+            raise ValueError(f"{what}: item_ids must be ({B}, T) with T >= 1")
+        return self.positions_of(item_ids.reshape(-1)).view(B, -1)
+
+    def _pairs_by_position(self, what: str, query_embeddings: torch.Tensor, positions: torch.Tensor, kwargs: dict) -> torch.Tensor:
+        self._refuse_pairs(kwargs, what)
+        self._refuse_pair_engine(what)
+        _positions_arg(what, positions, query_embeddings.size(0))
+        if positions.shape[1] < 1:
+            raise ValueError(f"{what}: positions must be ({query_embeddings.size(0)}, T) with T >= 1")
+        return positions.to(self._ids_flat.device).contiguous()
+
+    def score_of(self, query_embeddings: torch.Tensor, item_ids: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """(B, T) fp32: the score of the item carrying item_ids[b, j] ((B, T) integer ids, CPU or device, repeats allowed, resolved through the
+        live id map) for query row b -- all_logits' bits for that pair, -inf where the corpus has no such item or the row may not return it
+        (hidden, outside item_mask= / allowed_tags=, its id among the row's invalid_ids).  No dense pass: O(B T).  kwargs: what all_logits
+        takes (user_ids, item_mask=, allowed_tags=)."""
+        positions = self._pairs_by_id("score_of", query_embeddings, item_ids, kwargs)
+        return self._pairs_call("score_of", query_embeddings, positions, invalid_ids, kwargs, False)
+
+    def score_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        """score_of for items given as corpus POSITIONS ((B, T) int64; one outside [0, N), such as the -1 positions_of gives an unknown id, gets -inf)."""
+        positions = self._pairs_by_position("score_of_positions", query_embeddings, positions, kwargs)
+        return self._pairs_call("score_of_positions", query_embeddings, positions, invalid_ids, kwargs, False)
+
+    def explain_of(self, query_embeddings: torch.Tensor, item_ids: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> "Explained":
+        """score_of with the mixture behind each score -> Explained(logits (B, T), weights (B, T, P_Q, P_X), component_logits (B, T, P_Q, P_X)):
+        logits is score_of's result for the same call; component_logits[b, j, p, m] the cross logit of query component p and item component m
+        after the division by the temperature; weights the mixture weights of the reference's eval-mode combiner (they sum to 1).  Both are 0
+        where logits is -inf.  fp32 MoL engines inside the generic route's envelope only."""
+        positions = self._pairs_by_id("explain_of", query_embeddings, item_ids, kwargs)
+        return self._pairs_call("explain_of", query_embeddings, positions, invalid_ids, kwargs, True)
+
+    def explain_of_positions(self, query_embeddings: torch.Tensor, positions: torch.Tensor, invalid_ids: Optional[torch.Tensor] = None, **kwargs) -> "Explained":
+        """explain_of for items given as corpus POSITIONS ((B, T) int64)."""
+        positions = self._pairs_by_position("explain_of_positions", query_embeddings, positions, kwargs)
+        return self._pairs_call("explain_of_positions", query_embeddings, positions, invalid_ids, kwargs, True)
+
+
+class Explained(NamedTuple):
+    """What explain_of returns."""
+    logits: torch.Tensor                        # (B, T) fp32: score_of's result
+    weights: torch.Tensor                       # (B, T, P_Q, P_X) fp32: the mixture weights, 0 where logits is -inf
+    component_logits: torch.Tensor              # (B, T, P_Q, P_X) fp32: the cross logits after the division by tau, 0 where logits is -inf
+
 
 IN_PLACE, CONCATENATED, CUT_AND_FILLED = "in place", "concatenated", "cut and filled"
 
@@ -1734,6 +1857,55 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
         first call that can read it."""
         return self._score_positions(eng, qpack, batch, self._index, self._index_rows, positions)
 
+    # ---- the hooks of score_of / explain_of (DESIGN section 3.22) ------------------------------------------------------------------------------
+    _PAIR_ITEM_MASK = False      # (all_logits refuses item_mask= on the candidate modules; MoLBruteForceTopK takes it)
+
+    def _pair_engine(self):
+        """The engine whose dense pass all_logits returns: this module's own."""
+        return self._bind()
+
+    def _pair_scorer(self):
+        """(_pair_engine, its index, the row-major copy or a function yielding it)."""
+        return self._pair_engine(), self._index, self._index_rows
+
+    def _refuse_pair_engine(self, what: str) -> None:
+        """What the engine decides, still before any launch of the call: the split-f16 precisions (refuse_pair_precision) and, for explain_of
+        on a fused-shape module, a MoL shape outside the generic route's envelope (answered by the library without a device; inside it the
+        companion engine is built here, once)."""
+        eng = self._pair_engine()
+        refuse_pair_precision(self, eng, what)
+        if what.startswith("explain_of") and eng.route != "generic":
+            try:
+                self._mol_module.explain_engine()
+            except NotImplementedError as e:
+                raise explain_outside_envelope(self, e) from None
+
+    def _pair_scores(self, query_embeddings: torch.Tensor, positions: torch.Tensor, kwargs: dict) -> torch.Tensor:
+        eng, index, rows = self._pair_scorer()
+        B = query_embeddings.size(0)
+        qpack, _, _ = eng.query_pack(query_embeddings, kwargs.get("user_ids"))
+        if eng.route == "generic":      # (candidate-capable or not: the generic index is read in place)
+            return eng.score_at_generic(qpack, B, index, positions)
+        return self._score_positions(eng, qpack, B, index, rows, positions)
+
+    def _pair_explained(self, query_embeddings: torch.Tensor, positions: torch.Tensor, kwargs: dict):
+        """-> (component_logits (B, T, L), weights (B, T, L)); the explaining launch's own logits are dropped (on the generic route they are
+        score_of's bits, which the tests hold the engine's explain_indexed to).  A module on the generic route reads its
+        own index in place; a fused-shape module gathers the B T raw rows, builds a per-row generic index of them with its companion engine
+        (MoLSimilarity.explain_engine) and launches once -- nothing of size N."""
+        eng, index, _ = self._pair_scorer()
+        B, T = positions.shape
+        user_ids = kwargs.get("user_ids")
+        if eng.route == "generic":
+            qpack, _, _ = eng.query_pack(query_embeddings, user_ids)
+            _, cl, pi = eng.explain_indexed(qpack, B, index, positions)
+            return cl, pi
+        comp = self._mol_module.explain_engine()      # (inside the envelope: _refuse_pair_engine has asked)
+        cand = comp.build_index(self._rows_at(positions.reshape(-1)))
+        qpack, _, _ = comp.query_pack(query_embeddings, user_ids)
+        _, cl, pi = comp.explain_candidates(qpack, B, cand, T)
+        return cl, pi
+
     RERANK_ROWS_COPY_MAX_BYTES = 8 << 30     # fp32 indexes up to this size get a row-major copy for the candidate re-scoring of the rerank paths (0: never)
     _rows_cache = None
 
@@ -1752,6 +1924,27 @@ class MoLTopKModule(_CorpusEdits, TopKModule):
                 rows = eng.build_index_rows(self._index)
         self._rows_cache = (eng, self._index, rows)
         return rows
+
+
+def refuse_pair_precision(module, eng, what: str) -> None:
+    """score_of / explain_of on an engine of a split-f16 precision, by the class's name and the precision, before any
+    launch.  score_of runs on 'f16x3': _score_positions' gather route returns the dense pass's bits there (the same three-product kernels on
+    a gathered index; verified on the device, tests/test_score_of_gpu.py).  It is refused where the dense pass runs the one-product kernels
+    ('f16x1', 'f16-exact'): the gathered index is scored by the three-product ones, every entry differs, and nothing weaker than all_logits'
+    bits is returned.  explain_of needs the fp32 kernels, which alone write the mixture out."""
+    if eng.precision == "fp32" or (not what.startswith("explain_of") and eng.dense_precision == "f16x3"):
+        return
+    why = ("the mixture is written out by the fp32 kernels only" if what.startswith("explain_of") else
+           "the dense pass runs the one-product split-f16 kernels and given positions are scored by the three-product ones: not all_logits' bits")
+    raise NotImplementedError(f"{type(module).__name__}.{what}: precision={eng.dense_precision!r} -- {why}; a module of precision 'fp32' (or an "
+                              "exact mode of MoLBruteForceTopK, whose scores are its fp32 companion's) takes the call")
+
+
+def explain_outside_envelope(module, err: Exception) -> NotImplementedError:
+    """explain_of on a MoL shape the generic scoring route does not take (a pair gate without hidden layer, L > 256, d > 256, H > 512): the
+    refusal, by the class's name, with the route's own words."""
+    return NotImplementedError(f"{type(module).__name__}.explain_of: the mixture is written out by the shape-generic scoring kernel, and this MoL "
+                               f"shape lies outside its envelope ({err})")
 
 
 def refuse_item_mask(module, kwargs, why: str = "its candidates are generated inside the fused scans, and masking their result afterwards is not the "
@@ -2058,6 +2251,20 @@ class MoLBruteForceTopK(MoLTopKModule):
         if eng.exact is not None and self._mol_module.engine() is not eng:
             return self._all_logits_scratch(query_embeddings, _eng=eng.exact, _index=self._dense_fp32_index(), _tag="qpack32", **kwargs)
         return self._all_logits_scratch(query_embeddings, **kwargs)
+
+    _PAIR_ITEM_MASK = True
+
+    def _pair_engine(self):
+        """all_logits' engine: the fp32 companion in the exact modes, the module's own otherwise."""
+        eng = self._bind()
+        return eng.exact if eng.exact is not None and self._mol_module.engine() is not eng else eng
+
+    def _pair_scorer(self):
+        """... and its index: the dense fp32 index in the exact modes (built at first use and kept, as all_logits builds it)."""
+        eng = self._pair_engine()
+        if eng is not self._bind():
+            return eng, self._dense_fp32_index(), self._rows32
+        return eng, self._index, self._index_rows
 
     # ---- item_mask=: a call restricted to a subset of the corpus (DESIGN section 3.13) ------------------------------------------------------
     # The call equals the same call on a module freshly constructed from the kept rows and their ids, bit for bit (scores are per item and
@@ -2678,6 +2885,7 @@ class MoLBruteForceTopK(MoLTopKModule):
         if eng.exact is not None:
             out.update(self.rigorous_eps())
         out.update(self.fusion_stats())      # (fused_list_calls / fused_matrix_calls, once a call has been fused: DESIGN section 3.20)
+        out.update(self.pair_stats())        # (score_of_calls / explain_calls, once a pair-level call has been made: DESIGN section 3.22)
         return out
 
     def rigorous_eps(self) -> Dict[str, float]:
@@ -3581,8 +3789,9 @@ class MoLAvgTopK(MoLTopKModule):
             self._no_fused = False
 
     def stats(self) -> Dict[str, int]:
-        """fused_candidate_calls once a call has been fused over the candidate union (fuse_candidates = True); empty before."""
-        return _fused_candidate_stats(self)
+        """fused_candidate_calls once a call has been fused over the candidate union (fuse_candidates = True), score_of_calls / explain_calls
+        once a pair-level call has been made; empty before."""
+        return {**_fused_candidate_stats(self), **self.pair_stats()}
 
     def _diversified(self, query_embeddings: torch.Tensor, k: int, invalid_ids: Optional[torch.Tensor], kwargs: dict, div):
         """The diversified call over this module's own ranked list: MoLAvgTopK's avg_top_k reranked candidates; a
@@ -3716,8 +3925,9 @@ class _ComponentCandidates:
         return ids, scores.to(query_embeddings.dtype)
 
     def stats(self) -> Dict[str, int]:
-        """fused_candidate_calls once a call has been fused over the candidate union (fuse_candidates = True); empty before."""
-        return _fused_candidate_stats(self)
+        """fused_candidate_calls once a call has been fused over the candidate union (fuse_candidates = True), score_of_calls / explain_calls
+        once a pair-level call has been made; empty before."""
+        return {**_fused_candidate_stats(self), **self.pair_stats()}
 
     def _ranked(self, query_embeddings: torch.Tensor, sorted: bool, seen, kwargs):
         refuse_item_mask(self, kwargs)
@@ -4095,11 +4305,15 @@ class MIPSBruteForceTopK(_CorpusEdits, MIPSTopKModule):
         return None
 
     def stats(self) -> Dict[str, int]:
-        """Which route answered the fused calls so far (fusion_stats)."""
-        return self.fusion_stats()
+        """Which route answered the fused calls so far (fusion_stats), and score_of_calls once score_of has been called."""
+        return {**self.fusion_stats(), **self.pair_stats()}
 
     def _rank_scores(self, query_embeddings: torch.Tensor, **kwargs) -> torch.Tensor:
         return self._index.score(query_embeddings)
+
+    def _pair_scores(self, query_embeddings: torch.Tensor, positions: torch.Tensor, kwargs: dict) -> torch.Tensor:
+        """score_of's hook: the dense scan's MFMA chain per pair, the items fetched by position."""
+        return self._index.score_at(query_embeddings, positions)
 
     def _own_score_chunks(self, query_embeddings: torch.Tensor, mask: Optional[E.ItemMask], **kwargs):
         logits = self._index.score(query_embeddings)
