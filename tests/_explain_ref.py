@@ -88,23 +88,33 @@ def emulate32(cfg, w, Eq, Ex, gq, gi, mut=None, eps=None):
     """The explaining kernel's values in fp32 torch arithmetic (not its bits: torch's sums are not the kernel's chains) -> (cl, pi, out) fp32.
     mut: "transposed", "no_tau", "silu_gqgi" as explain64; "padded_softmax" (the softmax over Lp = L rounded up to 32, the padded w at 0);
     "no_renorm" (the renormalising division dropped; visible with eps forced above 1); "pi_before_den" (pi written before the division by
-    den).  eps: the clamp of the renormalisation (default 1e-6, the kernel's)."""
+    den).  The generic kernel's padded axes (tests/test_generic_sweep_cpu.py): "padded_softmax_lq" (the softmax over Lq = L rounded up to 4,
+    the width of the gq / gi rows); "q_block" (the last block of 32 query groups, p >= 32 floor((P_Q - 1) / 32), leaves its cl rows zero);
+    "d_tail" (GEMM1 stops at k = 8 floor(d / 8)); "hid_tail" (the hidden units from 32 floor(H / 32) on are dropped).
+    eps: the clamp of the renormalisation (default 1e-6, the kernel's)."""
     f = torch.float32
     Eq, Ex, gq, gi = (t.detach().to("cpu", f) for t in (Eq, Ex, gq, gi))
     B, PQ, d = Eq.shape
     tau = torch.tensor(cfg.temperature, dtype=f)
     eqs = Eq if mut == "no_tau" else Eq / tau
+    if mut == "d_tail":
+        eqs, Ex = eqs[..., : d // 8 * 8], Ex[..., : d // 8 * 8]
     if Ex.dim() == 3:
         cl = torch.einsum("bpd,nmd->bnpm", eqs, Ex)
         gi = gi.unsqueeze(0)
     else:
         cl = torch.einsum("bpd,bnmd->bnpm", eqs, Ex)
     N, L = cl.shape[1], cfg.num_logits
+    if mut == "q_block":
+        cl[:, :, (PQ - 1) // 32 * 32 :, :] = 0
     if mut == "transposed":
         cl = cl.transpose(2, 3)
     cl = cl.reshape(B, N, L)
     p = "_gating_fn._qi_partial_module."
     W1, b1, W2, b2 = (w[p + k].detach().to("cpu", f) for k in ("1.weight", "1.bias", "3.weight", "3.bias"))
+    if mut == "hid_tail":
+        kept = W1.shape[0] // 32 * 32
+        W1, b1, W2 = W1[:kept], b1[:kept], W2[:, :kept]
     pre = cl @ W1.T + b1
     hid = pre / (1 + torch.exp(-pre))
     gqi = hid @ W2.T + b2
@@ -118,8 +128,8 @@ def emulate32(cfg, w, Eq, Ex, gq, gi, mut=None, eps=None):
         g = gq * gi + gqi
         wv = g / (1 + torch.exp(-g))
     clp = cl
-    if mut == "padded_softmax":
-        Lp = (L + 31) // 32 * 32
+    if mut in ("padded_softmax", "padded_softmax_lq"):
+        Lp = (L + 31) // 32 * 32 if mut == "padded_softmax" else (L + 3) // 4 * 4
         wv = torch.nn.functional.pad(wv, (0, Lp - L))
         clp = torch.nn.functional.pad(cl, (0, Lp - L))
     e = torch.exp(wv - wv.amax(-1, keepdim=True))

@@ -19,6 +19,7 @@ import torch
 import rails_amd
 from rails_amd import engine as E
 from rails_amd import topk_modules as T
+from tests import _generic_sweep as G
 from tests import _mol_ref64 as R
 from tests import _scan_ref as S
 from tests.test_candidate_scans_gpu import bits, check_contract, ref_topk, same_bits, table_dev, to_dev
@@ -33,6 +34,7 @@ INDEXED_CASES = ("g_4x4x64",                 # pair-gate weights resident in LDS
                  "g_1x1x64",                 # odd P_Q
                  "g_8x8x40")
 MODULE_CASES = ("g_8x8x40", "g_12x3x20_h50_swiglu")      # table widths 64 and 32
+TABLE_CASES = MODULE_CASES + tuple(G.TABLE_SHAPES)      # and synthetic shapes at every width: d = 7 -> 32, 33 -> 64, 72 -> 128, 128 -> 128 (= d)
 MASKED = -32767.0
 
 
@@ -42,7 +44,11 @@ def dev():
 
 
 def candidate_module(name, dev):
-    cfg, w, a = CASES[name]
+    """-> (cfg, fixture arrays (None for a synthetic shape of tests/_generic_sweep.py), the candidate-capable module)"""
+    if name in G.TABLE_SHAPES:
+        cfg, w, a = G.config(G.TABLE_SHAPES[name]), G.weights(G.TABLE_SHAPES[name], "plain"), None
+    else:
+        cfg, w, a = CASES[name]
     mol = build_module(cfg, w, dev)
     mol.generic_candidates = True
     return cfg, a, mol
@@ -167,7 +173,12 @@ def exact_index(eng, cfg, ex):
     return E.MolIndex(rows.reshape(-1).to(eng.device), n)
 
 
-@pytest.mark.parametrize("name", MODULE_CASES)
+def gen_table_width(d):
+    """mol_generic.h gen_table_width, restated: the smallest of 32 / 64 / 128 that holds d, 0 where none does"""
+    return next((width for width in (32, 64, 128) if d <= width), 0)
+
+
+@pytest.mark.parametrize("name", TABLE_CASES)
 def test_tables_on_exact_inputs_and_their_update_form(name, dev):
     cfg, a, mol = candidate_module(name, dev)
     px, d = cfg.item_dot_product_groups, cfg.dot_product_dimension
@@ -175,7 +186,8 @@ def test_tables_on_exact_inputs_and_their_update_form(name, dev):
     with torch.inference_mode():
         eng = mol.engine()
         dt = eng.table_width
-        assert dt == (64 if d == 40 else 32) and dt > d
+        assert eng.route == "generic" and eng.candidates and dt == gen_table_width(d) and dt >= d
+        assert dt > d or name == "s_2x3x128"      # (the one case whose width is d itself, on a shape without a fused kernel)
         for n in (N_SMALL, N_LARGE):
             ex = S.dyadic_rows(rng, n * px, d).reshape(n, px, d)      # bf16 numbers: the tables' first rounding is exact, the restatement does the rest
             index = exact_index(eng, cfg, ex)
@@ -213,7 +225,32 @@ def padded_table(table, dt):
     return table_dev(out)
 
 
-@pytest.mark.parametrize("name", MODULE_CASES)
+def test_no_table_past_d_128_the_two_pass_modules_refuse(dev):
+    """d = 129: table_width == 0.  A candidate-capable engine still scores positions in place; the three two-pass modules and the table
+    builders refuse by name, at construction."""
+    cfg, w = G.config(G.NO_TABLE), G.weights(G.NO_TABLE, "plain")
+    assert gen_table_width(cfg.dot_product_dimension) == 0 and gen_table_width(128) == 128
+    mol = build_module(cfg, w, dev)
+    mol.generic_candidates = True
+    X, ids = corpus(cfg, N_SMALL).unsqueeze(0).to(dev), ids_of(N_SMALL, dev)
+    with torch.inference_mode():
+        eng = mol.engine()
+        assert eng.route == "generic" and eng.candidates and eng.table_width == 0
+        for kind in ("avg", "naive", "comb"):
+            with pytest.raises(NotImplementedError, match=r"dot_product_dimension <= 128 .* got d = 129"):
+                make(kind, mol, X, ids)
+        index = eng.build_index(X[0])
+        for call in (lambda: eng.build_coarse_table(index), lambda: eng.build_component_table(index), lambda: eng.update_source(index, X[0, :1])):
+            with pytest.raises(NotImplementedError, match=r"dot_product_dimension <= 128 .* got d = 129"):
+                call()
+        # what does not need a table runs: positions scored in place carry the dense bits
+        q = torch.from_numpy(np.random.default_rng(9).standard_normal((3, cfg.query_embedding_dim)).astype(np.float32)).to(dev)
+        qpack, _, _ = eng.query_pack(q, None)
+        pos = _positions(3, 45, N_SMALL, 5).to(dev)
+        assert same_bits(eng.score_indexed(qpack, 3, index, pos), torch.gather(eng.score_dense(qpack, 3, index), 1, pos.clamp(0, N_SMALL - 1)))
+
+
+@pytest.mark.parametrize("name", TABLE_CASES)
 def test_scan_scores_equal_the_restatement_fed_the_unpadded_values(name, dev):
     cfg, a, mol = candidate_module(name, dev)
     pq, px, d = cfg.query_dot_product_groups, cfg.item_dot_product_groups, cfg.dot_product_dimension
