@@ -63,6 +63,8 @@ extern "C" {
  * and the multi-row HSTU decode step rails_hstu_decode_rows[_supported] / rails_hstu_decode_rows_workspace_floats /
  * RAILS_HSTU_DECODE_MAX_ROWS (rails_hstu_decode is what it was)
  * and the pair-level entries rails_mol_generic_explain / rails_mol_generic_explain_indexed / rails_scores_at_eligible / rails_mips_score_indexed
+ * and the backward entries rails_mol_generic_pair_backward[_supported / _workspace_bytes] / rails_mol_generic_pack_gate_weights_t /
+ * rails_mol_generic_gate_pack_t_floats
  * were added under 15 as well: no struct
  * and no existing entry point changed, so callers built against the earlier header of 15 stay valid).  A binding checks rails_abi_version() == RAILS_ABI_VERSION at load time: callers built
  * against an older header pass shorter structs, and the library would read the new fields from whatever follows them. */
@@ -285,6 +287,29 @@ int rails_mol_generic_explain(const rails_mol_shape* shape, const float* gate_pa
 int rails_mol_generic_explain_indexed(const rails_mol_shape* shape, const float* gate_pack, const float* query_pack, int32_t batch,
                                       const float* index, int64_t n_items, const int64_t* positions, int64_t n_cand, float* logits, int64_t ld,
                                       float* component_logits, float* weights, void* stream);
+/* The backward of rails_mol_generic_score_candidates (the differentiable MoLSimilarity.forward): gradients of
+ * sum(dy * logits) in eval-mode arithmetic; dy is (batch, n_cand) with leading dimension ld_dy.  The kernels read what the forward reads
+ * (gate_pack, query_pack, cand_index) plus gate_pack_t: the two pair-gate matrices transposed, rails_mol_generic_gate_pack_t_floats floats
+ * written by rails_mol_generic_pack_gate_weights_t.  Outputs, each optional (NULL: its work is skipped):
+ *   d_query_pack  rails_mol_generic_query_pack_floats(batch) floats, the query pack's layout: the gradient of the l2-normalised Eq BEFORE its
+ *                 division by tau, and of gq; pads zero
+ *   d_cand_index  batch * n_cand rows of the item layout (P_X * dp + Lq floats each, no tile padding): the gradient of Ex and gi; pads zero
+ *   dw1 (H, L), db1 (H), dw2 (L, H), db2 (L), row-major, together or not at all: the pair gate's weight gradients.  They are summed through
+ *                 `workspace` (rails_mol_generic_pair_backward_workspace_bytes(shape, chunk_pairs) bytes, uninitialised; RAILS_ENOMEM if
+ *                 shorter): the rows run in chunks of whole rows of at most chunk_pairs pairs (rounded up to 256; a row of more candidates
+ *                 is RAILS_EINVAL), so no buffer grows with batch * n_cand.
+ * n_cand == 0: d_query_pack and the weight gradients are set to zero.
+ * No floating-point atomics: every sum over pairs runs over a fixed partition in a fixed order, so the bits depend on neither the device nor
+ * the run.  rails_mol_generic_pair_backward_supported: 1 iff the shape is inside the generic route's envelope and
+ * ceil(P_Q / 32) * ceil(d / 32) <= 4 (the dEq accumulators of a row live in registers); answered without a device. */
+int rails_mol_generic_pair_backward_supported(const rails_mol_shape* shape);
+size_t rails_mol_generic_gate_pack_t_floats(const rails_mol_shape* shape);
+int rails_mol_generic_pack_gate_weights_t(const rails_mol_shape* shape, const rails_mol_weights* weights, float* gate_pack_t, void* stream);
+size_t rails_mol_generic_pair_backward_workspace_bytes(const rails_mol_shape* shape, int64_t chunk_pairs);
+int rails_mol_generic_pair_backward(const rails_mol_shape* shape, const float* gate_pack, const float* gate_pack_t, const float* query_pack,
+                                    int32_t batch, const float* cand_index, int64_t n_cand, const float* dy, int64_t ld_dy, float* d_query_pack,
+                                    float* d_cand_index, float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes,
+                                    int64_t chunk_pairs, void* stream);
 /* The bf16 candidate tables of the two-pass algorithms from the generic index.  rails_mol_generic_table_width: the smallest of 32 / 64 / 128
  * that is >= dot_product_dimension, 0 for d > 128 (no table; answered without a device).  Rows have that many columns, the columns d .. width
  * exact zeros; the real columns carry rails_mol_coarse_build's / rails_mol_component_build's arithmetic, operation for operation.  The coarse

@@ -210,6 +210,16 @@ PROTOTYPES = {
         C.c_int,
         [_SHAPE_P, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
+    # the backward of the per-row-candidates launch (the differentiable MoLSimilarity.forward)
+    "rails_mol_generic_pair_backward_supported": (C.c_int, [_SHAPE_P]),
+    "rails_mol_generic_gate_pack_t_floats": (C.c_size_t, [_SHAPE_P]),
+    "rails_mol_generic_pack_gate_weights_t": (C.c_int, [_SHAPE_P, _WEIGHTS_P, C.c_void_p, C.c_void_p]),
+    "rails_mol_generic_pair_backward_workspace_bytes": (C.c_size_t, [_SHAPE_P, C.c_int64]),
+    "rails_mol_generic_pair_backward": (
+        C.c_int,
+        [_SHAPE_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p],
+    ),
     "rails_mol_generic_table_width": (C.c_int32, [_SHAPE_P]),
     "rails_mol_generic_coarse_build": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "rails_mol_generic_coarse_update": (C.c_int, [_SHAPE_P, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -618,6 +618,64 @@ int rails_mol_generic_explain_indexed(const rails_mol_shape* s, const float* gat
                                 "generic_explain_indexed");
 }
 
+// ---- the backward of the per-row-candidates launch (mol_generic_bwd.hip) ----
+int rails_mol_generic_pair_backward_supported(const rails_mol_shape* s) {
+  g_err[0] = '\0';
+  return generic_supported(s) && generic_backward_supported(*s) ? 1 : 0;
+}
+
+size_t rails_mol_generic_gate_pack_t_floats(const rails_mol_shape* s) { return generic_supported(s) ? gen_gate_pack_t_floats(*s) : 0; }
+
+int rails_mol_generic_pack_gate_weights_t(const rails_mol_shape* s, const rails_mol_weights* w, float* gate_pack_t, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (!w || !gate_pack_t || !w->gqi_w1 || !w->gqi_w2) { set_error("generic_pack_gate_weights_t: NULL pointer"); return RAILS_EINVAL; }
+  return fail(generic_pack_gate_weights_t(*s, *w, gate_pack_t, (hipStream_t)stream), "generic_pack_gate_weights_t");
+}
+
+size_t rails_mol_generic_pair_backward_workspace_bytes(const rails_mol_shape* s, int64_t chunk_pairs) {
+  if (!generic_supported(s) || chunk_pairs < 1) return 0;
+  return sizeof(float) * generic_backward_workspace_floats(*s, chunk_pairs);
+}
+
+int rails_mol_generic_pair_backward(const rails_mol_shape* s, const float* gate_pack, const float* gate_pack_t, const float* query_pack, int32_t batch,
+                                    const float* cand_index, int64_t n_cand, const float* dy, int64_t ld_dy, float* d_query_pack,
+                                    float* d_cand_index, float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes,
+                                    int64_t chunk_pairs, void* stream) {
+  g_err[0] = '\0';
+  if (!generic_supported(s)) return RAILS_ENOTSUP;
+  if (!generic_backward_supported(*s)) return RAILS_ENOTSUP;
+  if (batch < 0 || n_cand < 0) { set_error("generic_pair_backward: negative size"); return RAILS_EINVAL; }
+  if (batch == 0) return RAILS_OK;
+  if (n_cand == 0) {      // sums over no pairs: the query side and the weight gradients are zeros (d_cand_index has no rows)
+    hipStream_t st = (hipStream_t)stream;
+    bool ok = !d_query_pack || hipMemsetAsync(d_query_pack, 0, sizeof(float) * (size_t)batch * gen_query_floats(*s), st) == hipSuccess;
+    const size_t L = (size_t)num_logits(*s), H = (size_t)s->gating_qi_hidden_dim;
+    ok = ok && (!dw1 || hipMemsetAsync(dw1, 0, sizeof(float) * H * L, st) == hipSuccess) && (!db1 || hipMemsetAsync(db1, 0, sizeof(float) * H, st) == hipSuccess);
+    ok = ok && (!dw2 || hipMemsetAsync(dw2, 0, sizeof(float) * H * L, st) == hipSuccess) && (!db2 || hipMemsetAsync(db2, 0, sizeof(float) * L, st) == hipSuccess);
+    return ok ? RAILS_OK : fail(kErrLaunch, "generic_pair_backward");
+  }
+  if (!gate_pack || !gate_pack_t || !query_pack || !cand_index || !dy) { set_error("generic_pair_backward: NULL pointer"); return RAILS_EINVAL; }
+  if (ld_dy < n_cand) { set_error("generic_pair_backward: ld_dy (%lld) < n_cand (%lld)", (long long)ld_dy, (long long)n_cand); return RAILS_EINVAL; }
+  const int n_w = (dw1 ? 1 : 0) + (db1 ? 1 : 0) + (dw2 ? 1 : 0) + (db2 ? 1 : 0);
+  if (n_w != 0 && n_w != 4) { set_error("generic_pair_backward: dw1, db1, dw2, db2 are given together or not at all"); return RAILS_EINVAL; }
+  if (n_w == 4) {
+    if (chunk_pairs < 1) { set_error("generic_pair_backward: chunk_pairs < 1"); return RAILS_EINVAL; }
+    if (!workspace || workspace_bytes < rails_mol_generic_pair_backward_workspace_bytes(s, chunk_pairs)) {
+      set_error("generic_pair_backward: workspace shorter than rails_mol_generic_pair_backward_workspace_bytes");
+      return RAILS_ENOMEM;
+    }
+  }
+  const int cu = compute_units();
+  if (cu <= 0) { set_error("generic_pair_backward: no HIP device"); return RAILS_ELAUNCH; }
+  GenericBackwardArgs a{};
+  a.wpack = gate_pack; a.wtpack = gate_pack_t; a.qpack = query_pack; a.ipack = cand_index; a.dy = dy; a.ld_dy = ld_dy; a.n_cand = n_cand; a.B = batch;
+  a.d_qpack = d_query_pack; a.d_ipack = d_cand_index; a.dw1 = dw1; a.db1 = db1; a.dw2 = dw2; a.db2 = db2;
+  a.workspace = static_cast<float*>(workspace); a.chunk_pairs = chunk_pairs;
+  const int r = generic_pair_backward(*s, a, cu, (hipStream_t)stream);
+  return r == kOk ? r : fail(r, "generic_pair_backward");
+}
+
 // ---- the bf16 candidate tables from the generic index (mol_coarse.hip) ----
 int32_t rails_mol_generic_table_width(const rails_mol_shape* s) {
   g_err[0] = '\0';

@@ -60,6 +60,26 @@ int generic_pack_gate_weights(const Shape& s, const Weights& w, float* wpack, hi
 int generic_index_unpack(const Shape& s, const float* ipack, int64_t n, float* ex, float* gi, hipStream_t stream);
 int generic_score(const Shape& s, const GenericScoreArgs& a, int n_cu, hipStream_t stream);
 
+// The backward of the per-row-candidates launch (mol_generic_bwd.hip): gradients of sum(dy * logits).
+//   wtpack      W2^T and W1^T in the A-operand orders of W1 and W2 (generic_pack_gate_weights_t), gen_gate_pack_t_floats floats
+//   d_qpack     (B, query_floats): dEq (of the UNSCALED Eq: the 1/tau of the pack is applied) and dgq in the query pack's layout, pads zero; or NULL
+//   d_ipack     (B * n_cand, item_floats): dEx and dgi in the item pack's layout, pads zero; or NULL
+//   dw1 .. db2  (H, L), (H), (L, H), (L) row-major, all four or none; with them `workspace` of generic_backward_workspace_floats(chunk_pairs)
+//               floats: the rows run in chunks of at most chunk_pairs pairs (whole rows; a row longer than the chunk is refused)
+constexpr int kGenericBwdMaxQTiles = 4;
+inline size_t gen_gate_pack_t_floats(const Shape& s) { return 2 * (size_t)gen_hp(s) * gen_lp(s); }
+struct GenericBackwardArgs {
+  const float *wpack, *wtpack, *qpack, *ipack, *dy;
+  int64_t ld_dy, n_cand;
+  int B;
+  float *d_qpack, *d_ipack, *dw1, *db1, *dw2, *db2, *workspace;
+  int64_t chunk_pairs;
+};
+int generic_pack_gate_weights_t(const Shape& s, const Weights& w, float* wtpack, hipStream_t stream);
+bool generic_backward_supported(const Shape& s);      // sets the error text when not
+size_t generic_backward_workspace_floats(const Shape& s, int64_t chunk_pairs);
+int generic_pair_backward(const Shape& s, const GenericBackwardArgs& a, int n_cu, hipStream_t stream);
+
 // The bf16 candidate tables of the two-pass algorithms, cut from the generic index (mol_coarse.hip): rows of gen_table_width(s) columns,
 // the columns d .. width exact zeros, so that the bf16 scans run their d = 32 / 64 / 128 instantiations on them.  0: d > 128, no table.
 inline int gen_table_width(const Shape& s) {

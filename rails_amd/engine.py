@@ -675,6 +675,58 @@ class MolEngine:
                                                           _ptr(out), out.stride(0), _ptr(cl), _ptr(pi), _stream()), "rails_mol_generic_explain")
         return out, cl, pi
 
+    # ---- the backward of score_candidates on the generic route (the differentiable MoLSimilarity.forward) -------------
+    GRAD_CHUNK_PAIRS = 16384     # pairs per chunk of the weight-gradient workspace (whole rows; a multiple of 256)
+
+    def pair_backward_supported(self) -> bool:
+        """True iff rails_mol_generic_pair_backward takes this engine's shape (the message is in _lib.last_error() otherwise)."""
+        return self.route == "generic" and bool(self.lib.rails_mol_generic_pair_backward_supported(C.byref(self.shape)))
+
+    def pair_backward(self, qpack: torch.Tensor, batch: int, cand_index: MolIndex, n_cand: int, dY: torch.Tensor,
+                      need: Tuple[bool, bool, bool] = (True, True, True), chunk_pairs: Optional[int] = None):
+        """Gradients of sum(dY * score_candidates(qpack, batch, cand_index, n_cand)) -> (d_qpack, d_ipack, (dW1, db1, dW2, db2)):
+        d_qpack (batch, query_floats) holds dEq (of the unscaled Eq) and dgq in the query pack's layout, d_ipack (batch * n_cand, item_floats)
+        dEx and dgi in the item layout, the last four the pair gate's weight gradients.  need = (query side, item side, weights): an entry
+        that is False comes back None and its work is skipped.  dY is (batch, n_cand) fp32 with any row stride.  The weight gradients are
+        summed through a workspace of `chunk_pairs` pairs (GRAD_CHUNK_PAIRS by default), whatever batch * n_cand is; a row of more
+        candidates than that is refused when they are asked for."""
+        self._generic_only("pair_backward")
+        if not self.pair_backward_supported():
+            raise NotImplementedError(_lib.last_error())
+        dev = cand_index.buf.device
+        if dY.shape != (batch, n_cand) or dY.dtype != torch.float32 or dY.device != dev or (n_cand > 1 and dY.stride(1) != 1):
+            raise ValueError(f"dY must be ({batch}, {n_cand}) fp32 on {dev} with unit column stride, got {tuple(dY.shape)} {dY.dtype} strides {dY.stride()}")
+        ld = dY.stride(0) if batch > 1 else n_cand
+        if ld < n_cand:
+            dY, ld = dY.contiguous(), n_cand
+        if "gate_pack_t" not in self.__dict__:
+            self.gate_pack_t = torch.empty(self.lib.rails_mol_generic_gate_pack_t_floats(C.byref(self.shape)), dtype=torch.float32, device=self.device)
+            with _on_device(self.device):
+                _lib.check(self.lib.rails_mol_generic_pack_gate_weights_t(C.byref(self.shape), C.byref(self.weights), _ptr(self.gate_pack_t), _stream()),
+                           "rails_mol_generic_pack_gate_weights_t")
+        s = self.spec
+        qf = self.lib.rails_mol_generic_query_pack_floats(C.byref(self.shape), 1)
+        itf = self.lib.rails_mol_generic_index_floats(C.byref(self.shape), 32) // 32
+        dq = (torch.zeros if n_cand == 0 else torch.empty)((batch, qf), dtype=torch.float32, device=dev) if need[0] else None      # (no candidates: the launch is skipped)
+        di = torch.empty((batch * n_cand, itf), dtype=torch.float32, device=dev) if need[1] else None
+        dw = ws = None
+        ws_bytes = 0
+        chunk = int(chunk_pairs or self.GRAD_CHUNK_PAIRS)
+        if need[2]:
+            L, H = s.num_logits, s.gating_qi_hidden_dim
+            dw = (torch.zeros((H, L), dtype=torch.float32, device=dev), torch.zeros(H, dtype=torch.float32, device=dev),
+                  torch.zeros((L, H), dtype=torch.float32, device=dev), torch.zeros(L, dtype=torch.float32, device=dev))
+            if (n_cand + 31) // 32 * 32 > (chunk + 255) // 256 * 256:      # a row is never split, and the workspace does not grow with it
+                raise NotImplementedError(f"pair_backward: the pair gate's weight gradients take rows of at most chunk_pairs = {chunk} candidates, got {n_cand}")
+            ws_bytes = self.lib.rails_mol_generic_pair_backward_workspace_bytes(C.byref(self.shape), chunk)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        with _on_device(dev):
+            _lib.check(self.lib.rails_mol_generic_pair_backward(
+                C.byref(self.shape), _ptr(self.gate_pack), _ptr(self.gate_pack_t), _ptr(qpack), batch, _ptr(cand_index.buf), n_cand, _ptr(dY), ld,
+                _ptr(dq), _ptr(di), _ptr(dw[0]) if dw else None, _ptr(dw[1]) if dw else None, _ptr(dw[2]) if dw else None,
+                _ptr(dw[3]) if dw else None, _ptr(ws), ws_bytes, chunk, _stream()), "rails_mol_generic_pair_backward")
+        return dq, di, dw
+
     def score_candidates(self, qpack: torch.Tensor, batch: int, cand_index: MolIndex, n_cand_padded: int) -> torch.Tensor:
         out = torch.empty((batch, n_cand_padded), dtype=torch.float32, device=cand_index.buf.device)
         with _on_device(cand_index.buf.device):

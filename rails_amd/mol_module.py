@@ -334,6 +334,10 @@ class MoLSimilarity(SimilarityModule):
         # coarse / component tables are cut from it, so MoLAvgTopK / MoLNaiveTopK / MoLCombTopK run there.  No effect on
         # the fused route.  Part of the engine cache key, as `route` and `precision` are.
         self.generic_candidates: bool = False
+        # True -> with grad enabled, in eval mode, and an input or parameter that requires grad, forward returns logits that carry the
+        # graph: the pair stage runs forward and backward on the fp32 generic route's kernels, whatever `precision` and `route` say
+        # (DESIGN section 3.23).  No effect under no_grad / inference_mode or when nothing requires grad.
+        self.differentiable: bool = False
 
     # ---- binding the parameters to the HIP engine -----------------------------------------------
     def shape_spec(self) -> MolShapeSpec:
@@ -431,6 +435,27 @@ class MoLSimilarity(SimilarityModule):
             hit = self._extra_engines["explain"] = (key, MolEngine(self.shape_spec(), params, precision="fp32", route="generic"))
         return hit[1]
 
+    def grad_engine(self) -> MolEngine:
+        """The engine of the differentiable forward: explain_engine()'s fp32 companion on the generic route, after the refusals of the
+        feature (NotImplementedError, before any launch): a shape outside the route's envelope or a pair gate of one Linear, in the
+        route's own words; a shape whose dEq accumulators do not fit the backward kernel; apply_*_embeddings_fn = False."""
+        from . import _lib
+
+        _eval_only(self)
+        what = "the differentiable MoLSimilarity.forward (differentiable=True) runs on the generic route's kernels"
+        if not self._apply_query_embeddings_fn or not self._apply_item_embeddings_fn:
+            raise NotImplementedError(f"apply_query_embeddings_fn / apply_item_embeddings_fn = False is not supported; {what}")
+        import ctypes
+
+        shape = self.shape_spec().to_c("fp32")
+        lib = _lib.load()
+        if not lib.rails_mol_generic_supported(ctypes.byref(shape)) or not lib.rails_mol_generic_pair_backward_supported(ctypes.byref(shape)):
+            raise NotImplementedError(f"{_lib.last_error()}; {what}")
+        return self.explain_engine()
+
+    def _wants_grad(self, query_embeddings: torch.Tensor, item_embeddings: torch.Tensor) -> bool:
+        return query_embeddings.requires_grad or item_embeddings.requires_grad or any(p.requires_grad for p in self.parameters())
+
     def _apply(self, fn, *args, **kwargs):
         self._param_list = None
         return super()._apply(fn, *args, **kwargs)
@@ -463,6 +488,10 @@ class MoLSimilarity(SimilarityModule):
 
     def forward(self, query_embeddings: torch.Tensor, item_embeddings: torch.Tensor, **kwargs) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
         """(B, D), (1/B, X, D') -> ((B, X), {}).  Reference similarity_fn.py:341-413."""
+        if self.differentiable and not self.training and torch.is_grad_enabled() and self._wants_grad(query_embeddings, item_embeddings):
+            from .mol_grad import differentiable_forward
+
+            return differentiable_forward(self, query_embeddings, item_embeddings, kwargs.get("user_ids")), {}
         eng = self.engine()
         B = query_embeddings.size(0)
         Bp, X = item_embeddings.shape[0], item_embeddings.shape[1]
